@@ -17,6 +17,9 @@ Other SURVEY.md 8(d) configurations (parity-test scale cases, reported in DESIGN
   --config 5   5M x 500k, rank 64, explicit feedback, CG(3), dynamic lambda (add --solver cholesky for 5b)
 or any mix of --users/--items/--rank/--solver/--feedback.
 
+--dump-outputs DIR writes what the last timed step computed (losses, user and item factors; a seeded sample of rows beyond
+30 MB per matrix) as DIR/<name>.npy, so that two builds run with the same arguments can be compared output for output.
+
 Extra objects on the line:
   roofline      dominant kernel (the CG launch with the largest share of the iteration), algorithmic bytes / measured duration
                 (HIP events on the launch stream, recorded inside the library) vs the 8 TB/s HBM peak
@@ -188,6 +191,29 @@ def parity_check(als, U, V, solver, per_bucket=64, threads=None):
             "oracle": "fp64 restatement (oracle/wrmf_oracle.cpp), same inputs; ~%d rows per length class and side" % per_bucket}
 
 
+DUMP_BYTES_PER_MATRIX = 30 << 20   # two factor matrices + their row ids + the losses stay below 64 MB
+
+
+def dump_outputs(out_dir, last_losses, factors, seed):
+    """--dump-outputs: what the last timed step computed, as a caller of it receives it -- the item- and user-half losses
+    (losses.npy, float64) and the factor matrices in global row order (<name>.npy, float32).  A matrix larger than
+    DUMP_BYTES_PER_MATRIX is written as a fixed sample of its rows, drawn from the bench seed, with the global ids of those
+    rows in <name>_rows.npy (float64, exact)."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "losses.npy", np.asarray(last_losses, dtype=np.float64))
+    for m, (name, (S, lay)) in enumerate(sorted(factors.items())):
+        n, k = lay.n, S.shape[1]
+        cap = DUMP_BYTES_PER_MATRIX // (4 * k + 8)
+        if n <= cap:
+            rows = np.arange(n, dtype=np.int64)
+        else:
+            rows = np.sort(np.random.default_rng([seed, m]).choice(n, size=cap, replace=False)).astype(np.int64)
+            np.save(out / (name + "_rows.npy"), rows.astype(np.float64))
+        ids = lay.to_storage(torch.from_numpy(rows).to(S.device))
+        np.save(out / (name + ".npy"), S[ids].to(torch.float32).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -208,6 +234,10 @@ def main():
                     help="issue the CG bucket kernels back to back instead of overlapping them on side streams "
                          "(use under rocprofv3 so that per-kernel durations are well defined)")
     ap.add_argument("--seed", type=int, default=20250222)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the losses, and the user and item "
+                         "factors: every row, or a fixed seeded sample of rows where that would exceed the size cap) as "
+                         "DIR/<name>.npy")
     args = ap.parse_args()
     for key, val in CONFIGS[args.config].items():
         if getattr(args, key) is None:
@@ -329,6 +359,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     ms_per_step = 1e3 * elapsed / max(args.steps, 1)
+    if args.dump_outputs and rank == 0:   # before anything below moves U and V on
+        dump_outputs(args.dump_outputs, losses[-1] if losses else (float("nan"), float("nan")),
+                     {"user_factors": (U, lay_u), "item_factors": (V, lay_i)}, args.seed)
 
     # ---- per-kernel durations (HIP events inside the library, same stream), separate pass ----
     # segments of rsparse_hip_profile_last: CG -> one per row-length bucket; Cholesky -> [0] normal-equation launch (long

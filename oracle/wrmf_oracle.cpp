@@ -843,23 +843,30 @@ double initialize_biases_explicit(int n_items, const int32_t* csc_p, const int32
 
 // R/model_WRMF.R:474-486 (and :347-353): XtX = tcrossprod(X) + fl(diag(lambda)).
 // The ridge passes through float::fl(), i.e. lambda is rounded to fp32 even in the double build.
+// The columns are cut into GRAMIAN_BLOCKS fixed blocks, each summed in T, and the blocks are added in double in block
+// order: the result is the same at any thread count and on any host (the fp32 NNLS fits downstream change trajectory
+// with the last bits of XtX, so a Gramian that followed OMP_NUM_THREADS moved the tests' fp32-oracle yardsticks).
+constexpr int64_t GRAMIAN_BLOCKS = 64;
+
 template <class T>
 void gramian(const T* X, int k, int64_t n, double lambda, T* out) {
-  std::vector<double> acc((size_t)k * k, 0.0);
-#pragma omp parallel
-  {
-    std::vector<T> loc((size_t)k * k, (T)0);
-#pragma omp for schedule(static)
-    for (int64_t j = 0; j < n; j++) {
+  const int64_t nb = std::max<int64_t>(1, std::min<int64_t>(GRAMIAN_BLOCKS, n));
+  const size_t kk = (size_t)k * k;
+  std::vector<T> part((size_t)nb * kk, (T)0);
+#pragma omp parallel for schedule(static)
+  for (int64_t blk = 0; blk < nb; blk++) {
+    T* loc = part.data() + (size_t)blk * kk;
+    for (int64_t j = n * blk / nb; j < n * (blk + 1) / nb; j++) {
       const T* col = X + (size_t)j * k;
       for (int b = 0; b < k; b++) {
         const T f = col[b];
         for (int a = 0; a < k; a++) loc[(size_t)b * k + a] += col[a] * f;
       }
     }
-#pragma omp critical
-    for (size_t e = 0; e < (size_t)k * k; e++) acc[e] += (double)loc[e];
   }
+  std::vector<double> acc(kk, 0.0);
+  for (int64_t blk = 0; blk < nb; blk++)
+    for (size_t e = 0; e < kk; e++) acc[e] += (double)part[(size_t)blk * kk + e];
   const T ridge = (T)(float)lambda;
   for (int b = 0; b < k; b++)
     for (int a = 0; a < k; a++) out[(size_t)b * k + a] = (T)acc[(size_t)b * k + a] + (a == b ? ridge : (T)0);
