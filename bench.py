@@ -20,11 +20,19 @@ or any mix of --users/--items/--rank/--solver/--feedback.
 --dump-outputs DIR writes what the last timed step computed (losses, user and item factors; a seeded sample of rows beyond
 30 MB per matrix) as DIR/<name>.npy, so that two builds run with the same arguments can be compared output for output.
 
-Extra objects on the line:
-  roofline      dominant kernel (the CG launch with the largest share of the iteration), algorithmic bytes / measured duration
-                (HIP events on the launch stream, recorded inside the library) vs the 8 TB/s HBM peak
+A plain run does only what the headline needs: data generation, warm-up, the timed steps, the dump if asked for, and the
+line.  --full adds everything else the bench measures or checks, each after the timed steps (and after the dump):
+  user_rows_per_sec, roofline
+                per-kernel pass: dominant kernel (the CG launch with the largest share of the iteration), algorithmic
+                bytes / measured duration (HIP events on the launch stream, recorded inside the library) vs the 8 TB/s HBM
+                peak; user rows/s from the same pass's user half-iterations
+  comm_ms       N>1: the slab all-gathers of both sides alone
+  loss_first_vs_n1_rel
+                N>1: the first iteration's losses against the committed N=1 values (profiles/bench_n1_first_losses.json)
   cpu_baseline  the CPU oracle (rsparse-shaped C++/OpenMP port, oracle/) timed on this node's host
-                cores on a bounded sample of the same workload (rank 0, N=1 only)
+                cores on a bounded sample of the same workload (rank 0, N=1 only; not with --no-cpu-baseline)
+  parity        rows of this run re-solved by the fp64 oracle (rank 0, N=1 only; not with --no-cpu-baseline)
+  transform     one exact user half-iteration from the final item factors (rank 0, N=1, implicit, rank <= 128)
 """
 import argparse
 import json
@@ -229,7 +237,10 @@ def main():
     ap.add_argument("--mean-deg", type=float, default=50.0)
     ap.add_argument("--cg-steps", type=int, default=3)
     ap.add_argument("--lambda", dest="lam", type=float, default=0.1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline: per-kernel "
+                         "roofline, user rows/s, the N>1 exchange alone and loss check, CPU baseline, parity, transform")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline and parity")
     ap.add_argument("--serial-launches", action="store_true",
                     help="issue the CG bucket kernels back to back instead of overlapping them on side streams "
                          "(use under rocprofv3 so that per-kernel durations are well defined)")
@@ -363,7 +374,42 @@ def main():
         dump_outputs(args.dump_outputs, losses[-1] if losses else (float("nan"), float("nan")),
                      {"user_factors": (U, lay_u), "item_factors": (V, lay_i)}, args.seed)
 
-    # ---- per-kernel durations (HIP events inside the library, same stream), separate pass ----
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "als_iterations_per_sec", "value": args.steps / elapsed, "unit": "iterations/s",
+            "n_gpus": ws, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": ("f32 (Gram products of rows > 512 / <= 32 non-zeros as 2 x fp16 / 3 x bf16 split terms of the fp32 operands, "
+                      "fp32 accumulate; everything else fp32)" if (solver == 1 and k > 32 and k % 4 == 0) else
+                      ("f32 (normal equations of rows beyond 64 / 512 non-zeros assembled from 2 x fp16 / 3 x bf16 split terms, "
+                       "fp32 accumulate; factorisations fp32)" if solver == 0 else "f32")),
+            "data": "synthetic",
+            "config": {"workload": "WRMF %s ALS, %s, synthetic %dx%d, %d nnz, rank %d, lambda %g%s"
+                                   % (args.feedback, "CG(%d)" % args.cg_steps if solver == 1 else ("Cholesky" if solver == 0 else "NNLS"), n_user, n_item,
+                                      nnz, k, lam, "" if implicit else ", dynamic_lambda"),
+                       "survey_config": args.config, "feedback": args.feedback,
+                       "n_users": n_user, "n_items": n_item, "nnz": nnz, "rank": k,
+                       "solver": {0: "cholesky", 1: "conjugate_gradient", 2: "nnls"}[solver],
+                       "cg_steps": args.cg_steps, "parallelism": "rows sharded x%d, factors replicated" % ws},
+            "full": args.full,
+            "loss_users_last": losses[-1][1] if losses else None,
+            "loss_first_iteration": list(losses[0]) if losses else None,
+            "n_ranks_seen": n_ranks_seen, "shard_nnz_rank0": shard_nnz,
+            "partition": "contiguous blocks balanced by non-zeros, %d sub-blocks per rank and side (in-place slab all-gathers)" % lay_u.n_sub if ws > 1 else "single rank",
+            "launch_mode": ("serial (--serial-launches)" if args.serial_launches else
+                            "long-row launch alone, then the resident buckets on side streams (library default%s)"
+                            % ("; the per-kernel times under roofline are measured in a serialised pass" if args.full else "")),
+            "datagen_s": t_gen,
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line))
+        if ws > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full from here on: per-kernel durations (HIP events inside the library, same stream), separate pass ----
     # segments of rsparse_hip_profile_last: CG -> one per row-length bucket; Cholesky -> [0] normal-equation launch (long
     # rows, exact solve), [1] low-rank kernel (short rows), [2] k x k kernel, [3] wave-per-row kernel (rank 65..128, rows of 65..512 non-zeros);
     # NNLS -> [0].  The kernel NAMES come from the
@@ -576,40 +622,18 @@ def main():
 
     if rank == 0:
         user_half_ms = mean(half_ms["users"])
-        line = {
-            "metric": "als_iterations_per_sec", "value": args.steps / elapsed, "unit": "iterations/s",
-            "n_gpus": ws, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": ("f32 (Gram products of rows > 512 / <= 32 non-zeros as 2 x fp16 / 3 x bf16 split terms of the fp32 operands, "
-                      "fp32 accumulate; everything else fp32)" if (solver == 1 and k > 32 and k % 4 == 0) else
-                      ("f32 (normal equations of rows beyond 64 / 512 non-zeros assembled from 2 x fp16 / 3 x bf16 split terms, "
-                       "fp32 accumulate; factorisations fp32)" if solver == 0 else "f32")),
-            "data": "synthetic",
-            "config": {"workload": "WRMF %s ALS, %s, synthetic %dx%d, %d nnz, rank %d, lambda %g%s"
-                                   % (args.feedback, "CG(%d)" % args.cg_steps if solver == 1 else ("Cholesky" if solver == 0 else "NNLS"), n_user, n_item,
-                                      nnz, k, lam, "" if implicit else ", dynamic_lambda"),
-                       "survey_config": args.config, "feedback": args.feedback,
-                       "n_users": n_user, "n_items": n_item, "nnz": nnz, "rank": k,
-                       "solver": {0: "cholesky", 1: "conjugate_gradient", 2: "nnls"}[solver],
-                       "cg_steps": args.cg_steps, "parallelism": "rows sharded x%d, factors replicated" % ws},
+        line.update({
             "user_rows_per_sec": n_user / (user_half_ms * 1e-3) if user_half_ms > 0 else None,
             "transform": transform,
-            "loss_users_last": losses[-1][1] if losses else None,
-            "loss_first_iteration": list(losses[0]) if losses else None,
             # N > 1: the first iteration's losses against the committed N = 1 values of the same configuration (the
             # factors do not depend on the sharding; only the Gramian / loss summation order does)
             "loss_first_vs_n1_rel": (max(abs(a / b - 1.0) for a, b in zip(losses[0], first_ref))
                                      if (first_ref and losses) else None),
-            "n_ranks_seen": n_ranks_seen, "shard_nnz_rank0": shard_nnz, "comm_ms": comm_ms,
-            "partition": "contiguous blocks balanced by non-zeros, %d sub-blocks per rank and side (in-place slab all-gathers)" % lay_u.n_sub if ws > 1 else "single rank",
-            "launch_mode": ("serial (--serial-launches)" if args.serial_launches else
-                            "long-row launch alone, then the resident buckets on side streams (library default; the "
-                            "per-kernel times under roofline are measured in a serialised pass)"),
-            "datagen_s": t_gen,
+            "comm_ms": comm_ms,
             "roofline": roofline,
             "cpu_baseline": cpu,
             "parity": parity,
-        }
+        })
         print(json.dumps(line))
     if ws > 1:
         dist.destroy_process_group()

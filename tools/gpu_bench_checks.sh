@@ -1,8 +1,8 @@
 #!/bin/bash
-# bench.py end to end: default N=1 line (cpu_baseline + parity), and the N=2 control flow through the driver's entry
+# bench.py end to end: the default N=1 line with --full (cpu_baseline + parity), and the N=2 control flow through the driver's entry
 # command (self-launch) with gloo on the single GPU (RSPARSE_BENCH_BACKEND=gloo dry run)
 TAG=${1:-bc}; OUT=gpurun_out/$TAG; mkdir -p $OUT
-timeout 900 python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "bench default rc=$?"
+timeout 900 python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "bench default rc=$?"
 python - <<PY
 import json
 try:
@@ -12,8 +12,8 @@ try:
 except Exception as e:
     print("parse failed", e); print(open("$OUT/bench_full.err").read()[-2000:])
 PY
-RSPARSE_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --config 2 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err; echo "bench gloo n2 rc=$?"
-timeout 600 python bench.py --gpus 1 --config 2 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_n1_c2.json 2> $OUT/bench_n1_c2.err; echo "bench n1 config2 rc=$?"
+RSPARSE_BENCH_BACKEND=gloo timeout 600 python bench.py --full --gpus 2 --config 2 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_n2_gloo.json 2> $OUT/bench_n2_gloo.err; echo "bench gloo n2 rc=$?"
+timeout 600 python bench.py --full --gpus 1 --config 2 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_n1_c2.json 2> $OUT/bench_n1_c2.err; echo "bench n1 config2 rc=$?"
 python - <<PY
 import json
 for f in ("$OUT/bench_n2_gloo.json","$OUT/bench_n1_c2.json"):

@@ -7,6 +7,6 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for sfx in "${@:-prof}"; do
   export RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/librsparse_wrmf_hip_$sfx.so
-  RSPARSE_MF_PROF=1 timeout 900 python bench.py --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_$sfx.json 2> $OUT/prof_$sfx.txt; echo "$sfx rc=$?"
+  RSPARSE_MF_PROF=1 timeout 900 python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_$sfx.json 2> $OUT/prof_$sfx.txt; echo "$sfx rc=$?"
   grep cgmf_prof $OUT/prof_$sfx.txt | tail -2
 done | tee $OUT/summary.txt

@@ -5,7 +5,7 @@ TAG=${1:-cgsteps}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for n in 0 1 2 3; do
-  timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --cg-steps $n > $OUT/b_$n.json 2> $OUT/b_$n.err
+  timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --cg-steps $n > $OUT/b_$n.json 2> $OUT/b_$n.err
   python - $OUT/b_$n.json $n <<'PY'
 import json, sys
 try:

@@ -8,7 +8,7 @@ mkdir -p $OUT
 run() {
   name=$1; shift
   case " $WHAT " in *" $name "*) ;; *) return;; esac
-  timeout 900 python bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name rc=$?" >> $OUT/summary.txt
+  timeout 900 python bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name rc=$?" >> $OUT/summary.txt
   python - $OUT/$name.json <<'PY' >> $OUT/summary.txt 2>&1
 import json, sys
 try:

@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_hip_parity.py tests/test_wrmf_core.py -m
 tail -8 $OUT/pytest.log
 fi
 for m in 1 0; do
-  RSPARSE_HIP_DENSE_MFMA=$m timeout 900 python bench.py --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench_dmf$m.json 2> $OUT/bench_dmf$m.err; echo "bench dmf=$m rc=$?"
+  RSPARSE_HIP_DENSE_MFMA=$m timeout 900 python bench.py --full --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench_dmf$m.json 2> $OUT/bench_dmf$m.err; echo "bench dmf=$m rc=$?"
   python - $OUT/bench_dmf$m.json <<'PY'
 import json, sys
 try:

@@ -4,7 +4,7 @@ TAG=${1:-dyn}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 timeout 1500 python -m pytest tests/test_hip_parity.py tests/test_sampled_parity.py tests/test_bias.py -m gpu -q -x --timeout=900 -p no:cacheprovider > $OUT/pytest.log 2>&1; echo "pytest rc=$?" | tee $OUT/summary.txt
 tail -2 $OUT/pytest.log >> $OUT/summary.txt
-timeout 600 python bench.py --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" >> $OUT/summary.txt
+timeout 600 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" >> $OUT/summary.txt
 python - $OUT/bench.json >> $OUT/summary.txt 2>&1 <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

@@ -6,7 +6,7 @@ mkdir -p $OUT
 timeout 1200 python -m pytest tests/test_hip_parity.py tests/test_sampled_parity.py tests/test_bias.py tests/test_wrmf_core.py -m gpu -q -x --timeout=900 -p no:cacheprovider > $OUT/pytest.log 2>&1; echo "pytest rc=$?" | tee $OUT/summary.txt
 tail -3 $OUT/pytest.log >> $OUT/summary.txt
 for c in 2 5; do
-  timeout 600 python bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline > $OUT/config$c.json 2> $OUT/config$c.err; echo "config$c rc=$?" >> $OUT/summary.txt
+  timeout 600 python bench.py --full --config $c --steps 5 --warmup 1 --no-cpu-baseline > $OUT/config$c.json 2> $OUT/config$c.err; echo "config$c rc=$?" >> $OUT/summary.txt
   python - $OUT/config$c.json >> $OUT/summary.txt 2>&1 <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

@@ -6,7 +6,7 @@ mkdir -p $OUT
 for rep in 1 2; do
 for v in "$@"; do
   lib=$PWD/rsparse_amd/lib/librsparse_wrmf_hip${v/main/}.so
-  RSPARSE_HIP_LIB=$lib timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/b_$v.$rep.json 2> $OUT/b_$v.$rep.err
+  RSPARSE_HIP_LIB=$lib timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/b_$v.$rep.json 2> $OUT/b_$v.$rep.err
   python - $OUT/b_$v.$rep.json $v <<'PY'
 import json, sys
 try:

@@ -8,7 +8,7 @@ timeout 900 python -m pytest tests/test_sampled_parity.py -m gpu -q --timeout=60
 tail -8 $OUT/sampled.log | cut -c1-400
 fi
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-timeout 900 python bench.py --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 python - <<PY
 import json
 try:

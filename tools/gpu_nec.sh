@@ -4,7 +4,7 @@ TAG=${1:-nec}; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 RSPARSE_HIP_NE_CHOL_MIN=96 timeout 600 python -m pytest tests/test_hip_parity.py tests/test_sampled_parity.py -m gpu -q -x --timeout=500 -p no:cacheprovider -k "chol or Chol" 2>&1 | tail -3
 for t in "$@"; do
-  RSPARSE_HIP_NE_CHOL_MIN=$t timeout 300 python bench.py --config 4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/c4_$t.json 2> $OUT/c4_$t.err
+  RSPARSE_HIP_NE_CHOL_MIN=$t timeout 300 python bench.py --full --config 4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/c4_$t.json 2> $OUT/c4_$t.err
   python - $OUT/c4_$t.json $t <<'PY'
 import json, sys
 try:

@@ -5,7 +5,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 REPO=$PWD
-CMD="python $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline"
+CMD="python $REPO/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline"
 for c in FETCH_SIZE WRITE_SIZE; do
   (cd /tmp && timeout 900 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $REPO/$OUT/$c -o p -- $CMD > $REPO/$OUT/$c.log 2>&1); echo "pass $c rc=$?"
 done

@@ -1,7 +1,7 @@
 #!/bin/bash
 # SQ / TCC counters of the normal-equation kernel on the bench configuration (separate --pmc passes, kernel-trace only)
 TAG=${1:-pmcne}; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp; REPO=$PWD
-CMD="python $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline --serial-launches ${BENCH_ARGS:-}"
+CMD="python $REPO/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --serial-launches ${BENCH_ARGS:-}"
 run() { n=$1; shift; (cd /tmp && timeout 600 rocprofv3 --pmc "$@" --kernel-trace --kernel-include-regex "als_ne" --output-format csv -d $REPO/$OUT/$n -o p -- $CMD > $REPO/$OUT/$n.log 2>&1); echo "pass $n rc=$?"; }
 run sq1 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS
 run sq2 SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_SMEM SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS

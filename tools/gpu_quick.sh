@@ -6,7 +6,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 900 python -m pytest tests -m gpu -q --timeout=600 -p no:cacheprovider -x -k "not config2" > $OUT/pytest.log 2>&1; echo "pytest rc=$?" > $OUT/summary.txt
 tail -3 $OUT/pytest.log | cut -c1-300 >> $OUT/summary.txt
-timeout 900 python bench.py ${BENCH_ARGS:---no-cpu-baseline} > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "bench rc=$?" >> $OUT/summary.txt
+timeout 900 python bench.py --full ${BENCH_ARGS:---no-cpu-baseline} > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "bench rc=$?" >> $OUT/summary.txt
 python - <<PY >> $OUT/summary.txt 2>&1
 import json
 try:

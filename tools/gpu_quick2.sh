@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -m gpu -q --timeout=900 -p no:cacheprovider ${PYTEST_ARGS:-} > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee $OUT/summary.txt
 grep -v "Warning\|warnings.warn\|^$\|model = WRMF\|WRMF(rank" $OUT/pytest_gpu.log | tail -${TAILN:-25} >> $OUT/summary.txt
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
-timeout 900 python bench.py --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt
+timeout 900 python bench.py --full --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/summary.txt
 python - $OUT/bench.json >> $OUT/summary.txt 2>&1 <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

@@ -15,7 +15,7 @@ tail -15 $OUT/pytest_core.log >> $OUT/summary.txt
 cp gpurun_out/wrmf_core_errors.jsonl $OUT/ 2>/dev/null
 timeout 600 python tools/core_trace.py > $OUT/core_trace.txt 2>&1; echo "trace rc=$?" | tee -a $OUT/summary.txt
 echo "== bench baseline" | tee -a $OUT/summary.txt
-timeout 900 python bench.py --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "rc=$?" | tee -a $OUT/summary.txt
+timeout 900 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "rc=$?" | tee -a $OUT/summary.txt
 python - $OUT/bench_full.json >> $OUT/summary.txt 2>&1 <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

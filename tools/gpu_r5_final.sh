@@ -19,7 +19,7 @@ echo "== rank 128 double, 3 iterations: kernels" >> $OUT/summary.txt
 find $OUT/prof128 -name "*kernel_stats*" | head -1 | while read f; do python tools/rocpd_summary.py "$f" | cut -c1-200 | head -12; done >> $OUT/summary.txt 2>&1
 find $OUT/prof128 -name "*kernel_trace*" -delete 2>/dev/null
 echo "== bench (default command)" | tee -a $OUT/summary.txt
-timeout 600 python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "rc=$?" | tee -a $OUT/summary.txt
+timeout 600 python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "rc=$?" | tee -a $OUT/summary.txt
 python - $OUT/bench_full.json >> $OUT/summary.txt 2>&1 <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

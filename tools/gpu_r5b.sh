@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests -m gpu -q --timeout=600 -p no:cacheprovider -
 tail -5 $OUT/pytest.log | cut -c1-400 >> $OUT/summary.txt
 run() {  # name lib
   name=$1; lib=$2
-  RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/$lib timeout 600 python bench.py --steps 4 --warmup 1 --no-cpu-baseline > $OUT/b_$name.json 2> $OUT/b_$name.err
+  RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/$lib timeout 600 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline > $OUT/b_$name.json 2> $OUT/b_$name.err
   python - $OUT/b_$name.json $name <<'PY' >> $OUT/summary.txt
 import json, sys
 try:

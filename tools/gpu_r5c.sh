@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests -m gpu -q --timeout=600 -p no:cacheprovider -
 tail -5 $OUT/pytest.log | cut -c1-400 >> $OUT/summary.txt
 run() {  # name lib
   name=$1; lib=$2
-  RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/$lib timeout 600 python bench.py --steps 4 --warmup 1 --no-cpu-baseline > $OUT/b_$name.json 2> $OUT/b_$name.err
+  RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/$lib timeout 600 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline > $OUT/b_$name.json 2> $OUT/b_$name.err
   python - $OUT/b_$name.json $name <<'PY' >> $OUT/summary.txt
 import json, sys
 try:
@@ -24,7 +24,7 @@ for rep in 1 2; do
     run main$v.$rep librsparse_wrmf_hip$v.so
   done
 done
-RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/librsparse_wrmf_hip.so timeout 600 python bench.py --config 4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/config4.json 2> $OUT/config4.err
+RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/librsparse_wrmf_hip.so timeout 600 python bench.py --full --config 4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/config4.json 2> $OUT/config4.err
 python - $OUT/config4.json <<'PY' >> $OUT/summary.txt
 import json, sys
 try:

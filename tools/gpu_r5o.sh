@@ -10,7 +10,7 @@ timeout 600 python -m pytest tests/test_hip_parity.py tests/test_sampled_parity.
 tail -2 $OUT/pytest.log | cut -c1-200 >> $OUT/summary.txt
 run() {
   name=$1; lib=$2
-  RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/$lib timeout 600 python bench.py --steps 4 --warmup 1 --no-cpu-baseline > $OUT/b_$name.json 2> $OUT/b_$name.err
+  RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/$lib timeout 600 python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline > $OUT/b_$name.json 2> $OUT/b_$name.err
   python - $OUT/b_$name.json $name <<'PY' >> $OUT/summary.txt
 import json, sys
 try:
@@ -24,7 +24,7 @@ for rep in 1 2; do
   run main.$rep librsparse_wrmf_hip.so
   run nol2.$rep librsparse_wrmf_hip_nol2.so
 done
-(cd /tmp && timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $REPO/$OUT/FETCH_SIZE -o p -- python $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline > $REPO/$OUT/FETCH_SIZE.log 2>&1); echo "pmc rc=$?" >> $OUT/summary.txt
+(cd /tmp && timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $REPO/$OUT/FETCH_SIZE -o p -- python $REPO/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > $REPO/$OUT/FETCH_SIZE.log 2>&1); echo "pmc rc=$?" >> $OUT/summary.txt
 python - $OUT <<'PY' >> $OUT/summary.txt 2>&1
 import csv, glob, re, sys
 from collections import defaultdict

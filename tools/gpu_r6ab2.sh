@@ -8,7 +8,7 @@ tail -3 $OUT/pytest.log | cut -c1-300
 for rep in 1 2; do
 for v in $SFX rel; do
   if [ $v = rel ]; then unset RSPARSE_HIP_LIB; else export RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/librsparse_wrmf_hip_$v.so; fi
-  timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/b_$v.$rep.json 2> $OUT/b_$v.$rep.err
+  timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/b_$v.$rep.json 2> $OUT/b_$v.$rep.err
   python - $OUT/b_$v.$rep.json $v <<'PY'
 import json, sys
 try:

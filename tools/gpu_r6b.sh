@@ -12,7 +12,7 @@ for mf in 0 1; do
 done
 done | tee $OUT/chol_time_ab.txt
 for mf in 0 1; do
-  RSPARSE_HIP_CHOL_MF=$mf timeout 900 python bench.py --config 4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/config4_mf$mf.json 2> $OUT/config4_mf$mf.err
+  RSPARSE_HIP_CHOL_MF=$mf timeout 900 python bench.py --full --config 4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/config4_mf$mf.json 2> $OUT/config4_mf$mf.err
   python - $OUT/config4_mf$mf.json $mf <<'PY'
 import json, sys
 try:

@@ -11,7 +11,7 @@ for mf in 0 1; do
 done | tee $OUT/chol_time_ab.txt
 RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/librsparse_wrmf_hip_prof.so RSPARSE_MF_PROF=1 timeout 600 python tools/gpu_chol_time.py 2>&1 >/dev/null | grep mf_prof | tail -3 | tee $OUT/mf_prof.txt
 for mf in 1; do
-  RSPARSE_HIP_CHOL_MF=$mf timeout 900 python bench.py --config 4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/config4_mf$mf.json 2> $OUT/config4_mf$mf.err
+  RSPARSE_HIP_CHOL_MF=$mf timeout 900 python bench.py --full --config 4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/config4_mf$mf.json 2> $OUT/config4_mf$mf.err
   python - $OUT/config4_mf$mf.json $mf <<'PY'
 import json, sys
 try:

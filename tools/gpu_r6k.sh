@@ -5,7 +5,7 @@ TAG=${1:-r6k}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for v in ab abl7; do
-  RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/librsparse_wrmf_hip_$v.so RSPARSE_HIP_CHOL_MF_ALL=${MF_ALL:-1} timeout 900 python bench.py --config 4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/config4_$v.json 2> $OUT/config4_$v.err
+  RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/librsparse_wrmf_hip_$v.so RSPARSE_HIP_CHOL_MF_ALL=${MF_ALL:-1} timeout 900 python bench.py --full --config 4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/config4_$v.json 2> $OUT/config4_$v.err
   python - $OUT/config4_$v.json $v <<'PY'
 import json, sys
 try:

@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_hip_parity.py -m gpu -q -x --timeout=600
 tail -12 $OUT/pytest.log | cut -c1-300
 for rep in 1 2; do
 for v in 0 1; do
-  RSPARSE_HIP_CG_MF=$v timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/b_$v.$rep.json 2> $OUT/b_$v.$rep.err
+  RSPARSE_HIP_CG_MF=$v timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/b_$v.$rep.json 2> $OUT/b_$v.$rep.err
   python - $OUT/b_$v.$rep.json $v <<'PY'
 import json, sys
 try:

@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_nnls.py -m gpu -q -x --timeout=600 -p no
 for rep in 1 2; do
 for v in before rel; do
   if [ $v = rel ]; then unset RSPARSE_HIP_LIB; else export RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/librsparse_wrmf_hip_$v.so; fi
-  timeout 600 python bench.py --config 2 --solver nnls --steps 2 --warmup 1 --no-cpu-baseline > $OUT/b_$v.$rep.json 2> $OUT/b_$v.$rep.err
+  timeout 600 python bench.py --full --config 2 --solver nnls --steps 2 --warmup 1 --no-cpu-baseline > $OUT/b_$v.$rep.json 2> $OUT/b_$v.$rep.err
   python - $OUT/b_$v.$rep.json $v <<'PY'
 import json, sys
 try:

@@ -12,7 +12,7 @@ timeout 2700 python -m pytest tests -m gpu -q --timeout=900 -p no:cacheprovider 
 grep -v "Warning\|warnings.warn\|^$\|model = WRMF\|WRMF(rank" $OUT/pytest_gpu.log | tail -30 >> $OUT/summary.txt
 cp gpurun_out/wrmf_core_errors.jsonl $OUT/ 2>/dev/null; cp gpurun_out/sampled_parity_*.json $OUT/ 2>/dev/null
 echo "== bench (default command)" | tee -a $OUT/summary.txt
-timeout 1200 python bench.py > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "rc=$?" | tee -a $OUT/summary.txt
+timeout 1200 python bench.py --full > $OUT/bench_full.json 2> $OUT/bench_full.err; echo "rc=$?" | tee -a $OUT/summary.txt
 python - $OUT/bench_full.json >> $OUT/summary.txt 2>&1 <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

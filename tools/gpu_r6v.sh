@@ -10,7 +10,7 @@ tail -8 $OUT/pytest.log | cut -c1-300
 export TMPDIR=/tmp
 for sfx in "${@:-rel}"; do
   if [ "$sfx" = rel ]; then unset RSPARSE_HIP_LIB; else export RSPARSE_HIP_LIB=$REPO/rsparse_amd/lib/librsparse_wrmf_hip_$sfx.so; fi
-  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/prof_$sfx -o bench -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --serial-launches > $REPO/$OUT/prof_bench_$sfx.json 2> $REPO/$OUT/prof_bench_$sfx.err); echo "$sfx rocprof rc=$?"
+  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/prof_$sfx -o bench -- python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --serial-launches > $REPO/$OUT/prof_bench_$sfx.json 2> $REPO/$OUT/prof_bench_$sfx.err); echo "$sfx rocprof rc=$?"
   find $OUT/prof_$sfx -name "*kernel_stats*" | head -1 | while read f; do python tools/rocpd_summary.py "$f" | cut -c1-170 | head -12; done > $OUT/kernel_stats_$sfx.txt 2>&1
   grep -i "cg_mf\|kernel  " $OUT/kernel_stats_$sfx.txt
   python -c "
@@ -19,7 +19,7 @@ d=json.load(open('$OUT/prof_bench_$sfx.json')); print('$sfx serial-launch bench:
   rm -rf $OUT/prof_$sfx
 done
 unset RSPARSE_HIP_LIB
-timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
 python - $OUT/bench.json <<'PY' | tee $OUT/summary.txt
 import json, sys
 try:

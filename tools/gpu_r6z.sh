@@ -6,7 +6,7 @@ mkdir -p $OUT
 for sfx in rel "$@"; do
   if [ "$sfx" = rel ]; then unset RSPARSE_HIP_LIB; else export RSPARSE_HIP_LIB=$PWD/rsparse_amd/lib/librsparse_wrmf_hip_$sfx.so; fi
   for rep in 1 2; do
-  timeout 900 python bench.py --config 4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/config4_$sfx.json 2> $OUT/config4_$sfx.err
+  timeout 900 python bench.py --full --config 4 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/config4_$sfx.json 2> $OUT/config4_$sfx.err
   python - $OUT/config4_$sfx.json $sfx <<'PY'
 import json, sys
 try:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the bench at 1M x 100k (fixed sides of 512 MB / 51 MB: the gathers hit MALL / L2 instead of HBM)
 TAG=${1:-small}; OUT=gpurun_out/$TAG; mkdir -p $OUT
-timeout 300 python bench.py --users 1000000 --items 100000 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/small.json 2> $OUT/small.err
+timeout 300 python bench.py --full --users 1000000 --items 100000 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/small.json 2> $OUT/small.err
 python - <<PY
 import json
 d=json.loads(open("$OUT/small.json").read().strip().splitlines()[-1])

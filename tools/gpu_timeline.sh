@@ -2,7 +2,7 @@
 # kernel timeline of the timed loop as it really runs (side streams, no --serial-launches): start / end of every
 # kernel of the last iteration relative to its first kernel
 TAG=${1:-tl}; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp; REPO=$PWD
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d $REPO/$OUT/trace -o t -- python $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > $REPO/$OUT/bench.json 2> $REPO/$OUT/bench.err); echo "rc=$?"
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d $REPO/$OUT/trace -o t -- python $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > $REPO/$OUT/bench.json 2> $REPO/$OUT/bench.err); echo "rc=$?"
 python - <<PY
 import csv,glob
 f=glob.glob("$OUT/trace/**/*kernel_trace.csv",recursive=True)[0]

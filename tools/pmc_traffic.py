@@ -32,7 +32,7 @@ for line in open("%s/FETCH_SIZE.log" % root, errors="replace"):
                     "feedback": cfg["feedback"], "solver": {"conjugate_gradient": "cg"}.get(cfg["solver"], cfg["solver"]),
                     "cg_steps": cfg["cg_steps"], "n_gpus": 1}
 res = {"how": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, kernel-trace only; KB per dispatch, mean over the "
-              "dispatches of `python bench.py --steps 1 --warmup 0 --no-cpu-baseline`); hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 "
+              "dispatches of `python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline`); hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 "
               "per MI355X_MICROARCH.md (gfx950 FETCH_SIZE reports half the bytes of wide coalesced reads; Infinity-Cache hits "
               "are counted)",
        "workload": workload, "kernels": {}}
