@@ -312,7 +312,16 @@ int rsparse_hip_weighted_sumsq_device(const float* d_X, int rank, int64_t n, con
  * ---------------------------------------------------------------------------------------------- */
 
 #define RSPARSE_HIP_NA_INTEGER INT32_MIN /* R's NA_integer_: fewer than k admissible items */
+/* k up to RSPARSE_HIP_MAX_TOPK runs the fused path (wrmf_topk.hip: candidates in LDS / a per-workgroup scratch while the items
+ * stream past); RSPARSE_HIP_MAX_TOPK < k <= RSPARSE_HIP_MAX_TOPK_LARGE runs the large-k path (wrmf_topk_large.hip): per chunk of
+ * users the scores go to a key matrix in the workspace, a radix select finds every user's kc-th key, the items at or above it are
+ * ordered in LDS (re-scored in double by the f64 form) and users whose list overflows (exact ties) replay the reference's heap.
+ * Its workspace (the library's grow-only pad buffer) is chunk x (round_up(n_items, 4) + 2052 + 2 x cap) words with
+ * cap = min(10240, max(the power of two >= k, round_up(2 kc, 256))) and chunk = the users that fit 2 GiB (at most 32768):
+ * 2 GiB for any call with more than a few hundred users over a million items.  k above RSPARSE_HIP_MAX_TOPK_LARGE ->
+ * ERR_UNSUPPORTED. */
 #define RSPARSE_HIP_MAX_TOPK 256
+#define RSPARSE_HIP_MAX_TOPK_LARGE 8192
 
 /* replaces top_product (src/matrix_top_product.cpp:20-102; .Call `_rsparse_top_product`,
  * R/RcppExports.R).  x: nr x rank and y: rank x nc, both column-major doubles as arma::mat holds them;
@@ -321,7 +330,7 @@ int rsparse_hip_weighted_sumsq_device(const float* d_X, int rank, int64_t n, con
  * than k items are admissible), scores: nr x k column-major (+ glob_mean), best first; equal scores keep the
  * reference's order (larger index first).  The candidates (k + max(8, k / 4) per row) come from an fp32 matrix-core pass,
  * their scores are recomputed in double from x and y as given and the reference's heap is replayed over them
- * (rsparse_hip_top_product_f64_device below).  k > 256 -> ERR_UNSUPPORTED.  n_threads is accepted and ignored. */
+ * (rsparse_hip_top_product_f64_device below).  k > 8192 -> ERR_UNSUPPORTED.  n_threads is accepted and ignored. */
 int rsparse_hip_top_product(const double* x, const double* y, int nr, int nc, int rank, unsigned k,
                             unsigned n_threads, const int32_t* not_recommend_p,
                             const int32_t* not_recommend_j, const int32_t* exclude, int n_exclude,
@@ -331,7 +340,7 @@ int rsparse_hip_top_product(const double* x, const double* y, int nr, int nc, in
  * d_exclude0: sorted 0-based item indices, d_res / d_scores: n_users x k row-major.
  * A call for more than 128 users (rank <= 128) keeps its per-user candidate buffers in the library's grow-only workspace:
  * min(n_users, 131072) x 2 x (k + 32 + max(64, k)) words, 121 MB at k = 10, 570 MB at k = 256; longer calls run in chunks of
- * 131072 users on the stream and reuse it. */
+ * 131072 users on the stream and reuse it.  256 < k <= 8192: the large-k path (above) on the fp32 scores, kc = k. */
 int rsparse_hip_top_product_device(const float* d_U, const float* d_V, int n_users, int n_items, int rank,
                                    int k, const int32_t* d_not_recommend_p, const int32_t* d_not_recommend_j,
                                    const int32_t* d_exclude0, int n_exclude, double glob_mean,
@@ -339,7 +348,8 @@ int rsparse_hip_top_product_device(const float* d_U, const float* d_V, int n_use
 
 /* `$predict` that ORDERS like the reference.  find_top_product casts both factor matrices to double before the product
  * (R/utils.R:35-36) and top_product takes arma::mat (src/matrix_top_product.cpp:20): the fp32 pass above only nominates -- it keeps
- * the k + extra best items of every user (extra < 0: max(8, k / 4); never more than 256 candidates) --, their scores are
+ * the k + extra best items of every user (extra < 0: max(8, k / 4); never more than 256 candidates for k <= 256, 10240 for the
+ * large-k path) --, their scores are
  * recomputed in double from d_U64 / d_V64 (n x rank row-major doubles; both NULL: from the fp32 factors widened) and the
  * reference's heap is replayed over the candidates in ascending item order: strict `>` replacement, equal scores with the
  * larger index first, and when more candidates sit AT the k-th score than places, the ones the reference's heap keeps.

@@ -1699,8 +1699,17 @@ int rsparse_hip_top_product_device(const float* d_U, const float* d_V, int n_use
   if (!d_U || !d_V || !d_res || !d_scores) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
   if (n_users < 0 || n_items < 0 || rank <= 0 || k < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions");
   if (rank > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 256 is not on the device path");
-  if (k > RSPARSE_HIP_MAX_TOPK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 256 is not on the device path");
+  if (k > RSPARSE_HIP_MAX_TOPK_LARGE) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
   if (n_exclude > 0 && !d_excl0) return fail(RSPARSE_HIP_ERR_INVALID, "exclude is NULL");
+  if (k > RSPARSE_HIP_MAX_TOPK) {   // the large-k path (wrmf_topk_large.hip): its key matrix and lists in the grow-only workspace
+    if (n_users == 0) return RSPARSE_HIP_OK;
+    int rc = g_ws.ensure_pad(top_product_large_ws_floats(n_users, n_items, k, k));
+    if (rc) return rc;
+    hipError_t e = launch_top_product_large(d_U, d_V, n_users, n_items, rank, k, d_nr_p, d_nr_p ? d_nr_j : nullptr, d_excl0, n_exclude,
+                                            (float)glob_mean, d_res, d_scores, (hipStream_t)stream, g_ws.pad_buf);
+    if (e != hipSuccess) return hip_fail(e, "launch_top_product_large");
+    return RSPARSE_HIP_OK;
+  }
   // (few users over many items: the items are split over the workgroups, the slices' lists land in this scratch)
   float* scratch = nullptr;
   const size_t sfl = top_product_scratch_floats(n_users, n_items, rank, k);
@@ -1723,8 +1732,18 @@ int rsparse_hip_top_product_f64_device(const float* d_U, const float* d_V, const
   if ((d_U64 == nullptr) != (d_V64 == nullptr)) return fail(RSPARSE_HIP_ERR_INVALID, "the double factors come as a pair");
   if (n_users < 0 || n_items < 0 || rank <= 0 || k < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions");
   if (rank > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 256 is not on the device path");
-  if (k > RSPARSE_HIP_MAX_TOPK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 256 is not on the device path");
+  if (k > RSPARSE_HIP_MAX_TOPK_LARGE) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
   if (n_users == 0) return RSPARSE_HIP_OK;
+  if (k > RSPARSE_HIP_MAX_TOPK) {   // the large-k path: kc = k + extra candidates (at most 10240), re-scored in double
+    if (n_exclude > 0 && !d_excl0) return fail(RSPARSE_HIP_ERR_INVALID, "exclude is NULL");
+    const int kcl = top_product_large_kc(k, extra, n_items);
+    int rc = g_ws.ensure_pad(top_product_large_ws_floats(n_users, n_items, k, kcl));
+    if (rc) return rc;
+    hipError_t e = launch_top_product_large_f64(d_U, d_V, d_U64, d_V64, n_users, n_items, rank, k, kcl, d_nr_p, d_nr_p ? d_nr_j : nullptr,
+                                                d_excl0, n_exclude, glob_mean, d_res, d_scores, (hipStream_t)stream, g_ws.pad_buf);
+    if (e != hipSuccess) return hip_fail(e, "launch_top_product_large_f64");
+    return RSPARSE_HIP_OK;
+  }
   // candidates per user: k + extra (default: a quarter of k, at least 8), never more than the kernel's 256 or the items
   if (extra < 0) extra = std::max(8, k / 4);
   const int kc = std::max(k, std::min(std::min(k + extra, RSPARSE_HIP_MAX_TOPK), std::max(n_items, 1)));
@@ -1749,7 +1768,7 @@ int rsparse_hip_top_product(const double* x, const double* y, int nr, int nc, in
   if (!x || !y || !res || !scores) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
   if (nr < 0 || nc < 0 || rank <= 0 || k < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions");
   if (rank > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 256 is not on the device path");
-  if (k > RSPARSE_HIP_MAX_TOPK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 256 is not on the device path");
+  if (k > RSPARSE_HIP_MAX_TOPK_LARGE) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
   if (n_exclude < 0 || (n_exclude > 0 && !exclude)) return fail(RSPARSE_HIP_ERR_INVALID, "bad exclude");
   // x is nr x rank column-major -> row-major fp32; y (rank x nc column-major) already has item vectors contiguous
   std::vector<float> U((size_t)nr * rank), V((size_t)nc * rank);

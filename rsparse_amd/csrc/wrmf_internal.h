@@ -312,6 +312,21 @@ size_t top_product_scratch_entries(int n_users, int n_items, int topk);
 // not fit the LDS -- the global candidate buffers of the two-tile kernel (wrmf_topk.hip "GBUF")
 size_t top_product_scratch_floats(int n_users, int n_items, int k_rank, int topk);
 bool top_product_wants_gbuf(int n_users, int k_rank, int topk);
+// 256 < topk <= 8192 (wrmf_topk_large.hip): scores to a global key matrix per chunk of users, the kc-th key of every user by a radix
+// select, the candidates at or above it ordered in LDS (fp32 scores, or re-scored in double), the reference heap's result in closed
+// form; users whose candidate list overflows replay the heap.  ws: top_product_large_ws_floats(...) floats (chunk_users: users
+// per chunk).  kc: top_product_large_kc (the fp32 form selects kc = topk).
+constexpr int kTopLargeMin = 256;    // RSPARSE_HIP_MAX_TOPK: larger k only
+constexpr int kTopLargeMax = 8192;   // RSPARSE_HIP_MAX_TOPK_LARGE
+size_t top_product_large_ws_floats(int n_users, int n_items, int topk, int kc, int* chunk_users = nullptr);
+int top_product_large_kc(int topk, int extra, int n_items);
+hipError_t launch_top_product_large(const float* U, const float* V, int n_users, int n_items, int rank, int topk,
+                                    const int32_t* nr_ptr, const int32_t* nr_idx, const int32_t* excl, int n_excl, float glob_mean,
+                                    int32_t* res, float* scores, hipStream_t s, float* ws);
+hipError_t launch_top_product_large_f64(const float* U32, const float* V32, const double* U64, const double* V64, int n_users,
+                                        int n_items, int rank, int topk, int kc, const int32_t* nr_ptr, const int32_t* nr_idx,
+                                        const int32_t* excl, int n_excl, double glob_mean, int32_t* res, double* scores,
+                                        hipStream_t s, float* ws);
 
 // device helpers of the multi-GPU context (wrmf_ctx_kernels.hip / wrmf_ctx.cpp)
 hipError_t launch_ctx_accumulate(const float* Gpart, const double* sumsq, double* red, int k, hipStream_t s);

@@ -336,6 +336,10 @@ class HipBackend:
         # few million users in one call); a batch bounds it and the next batch reuses it.  The CSR slots of
         # not_recommend are absolute positions into nr_j, so a batch passes its slice of nr_p unchanged.
         B = self.top_product_batch
+        if k > 256:
+            # the large-k path (k <= 8192): the same budget of n * (2 kc + 2 k + 1) words as a full batch at k = 256
+            kc = k + max(8, k // 4)
+            B = max(1, min(B, B * (2 * 320 + 2 * 256 + 1) // (2 * kc + 2 * k + 1)))
         for a0 in range(0, max(n, 1), B):
             nb = min(B, n - a0)
             if nb <= 0:

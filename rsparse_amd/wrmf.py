@@ -499,7 +499,9 @@ class WRMF:
         rows of `x` by `transform`, then the k best items per row on the device, skipping each row's
         `not_recommend` entries (default: `x` itself, as in the reference; None = nothing) and the globally
         excluded `items_exclude` (0-based here, 1-based in R).  Returns a `TopItems` array (n x k item
-        indices, 0-based, -1 where fewer than k items are admissible) with `.scores` (n x k)."""
+        indices, 0-based, -1 where fewer than k items are admissible) with `.scores` (n x k).  k up to 256 runs the fused
+        device path, 256 < k <= 8192 the large-k path (a radix select per user over the stored scores); a larger k raises
+        UnsupportedOnDevice."""
         import ctypes
         if self._V is None:
             raise RuntimeError("model is not fitted")

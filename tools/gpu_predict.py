@@ -80,7 +80,18 @@ if nr_p is not None:
 ref = torch.topk(S, a.topk, dim=1)
 ok = float((torch.abs(ref.values - sc[:64].to(torch.float32)) <= 1e-4 * ref.values.abs().clamp_min(1e-6)).float().mean())
 flops = 2.0 * done * a.items * a.rank
+large = {}
+if 256 < a.topk <= 8192:
+    # the large-k path's plan (include/rsparse_wrmf_hip.h, RSPARSE_HIP_MAX_TOPK_LARGE): users per chunk and workspace
+    kc = min(a.topk + max(8, a.topk // 4), 10240, max(a.items, 1)) if a.rescore else a.topk
+    kc = max(kc, a.topk)
+    cap = min(10240, max(1 << (a.topk - 1).bit_length(), (2 * kc + 255) // 256 * 256))
+    wpu = (max(a.items, 1) + 3) // 4 * 4 + 2048 + 4 + 2 * cap
+    c = (1 << 29) // wpu
+    c = c // 256 * 256 if c > 256 else c
+    chunk = max(1, min(c, 32768, nb))
+    large = {"path": "large-k", "kc": kc, "cand_cap": cap, "chunk_users": chunk, "scratch_bytes": 4 * (chunk * wpu + 64)}
 print(json.dumps({"what": "top_product_kernel ($predict)" + (" + double re-scoring" if a.rescore else ""), "users": done, "items": a.items, "rank": a.rank, "topk": a.topk,
                   "exclude_per_user": a.exclude_deg, "users_per_call": nb, "seconds": dt, "users_per_sec": done / dt,
                   "score_tflops": flops / dt / 1e12, "fp32_matrix_peak_tflops": 157.3, "frac_of_fp32_peak": flops / dt / 1e12 / 157.3,
-                  "scores_match_torch_topk_frac": ok}))
+                  "scores_match_torch_topk_frac": ok, **large}))
