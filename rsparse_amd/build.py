@@ -4,12 +4,10 @@ One object per source (compiled in parallel, rebuilt only when the source or a s
 In-tree output (rsparse_amd/lib/) so the .so travels with the repo snapshot to the GPU box; the objects live in
 rsparse_amd/lib/obj/ (git-ignored like the .so).
 
-    python -m rsparse_amd.build [--force] [-D NAME[=VALUE] ...] [--out other.so]
+    python -m rsparse_amd.build [--force] [--out other.so]
 
--D / --out are for dev builds (in-kernel profilers, ablations: tools/build_prof.sh, tools/build_abl.sh); such builds use
-their own object directory.
+--out links the same objects into another file (a second library to load through RSPARSE_HIP_LIB).
 """
-import hashlib
 import subprocess
 import sys
 import time
@@ -38,13 +36,13 @@ AUDITED = {"wrmf_chol_mf.hip", "wrmf_cg_mf.hip"}
 REG_LIMIT = {"wrmf_cg_mf.hip": 512}   # (one wave per SIMD by design: 320 accumulator registers per row)
 
 
-def audit_listing(src, extra, defines, obj):
+def audit_listing(src, extra, obj):
     sys.path.insert(0, str(PKG.parent / "tools" / "dbg"))
     import acc_audit
     lst = obj.with_suffix(".s")
 
     def listing(flags, floor):
-        cmd = ["hipcc", *FLAGS, *flags, *["-D" + d for d in defines], "-S", "--cuda-device-only", str(src), "-o", str(lst)]
+        cmd = ["hipcc", *FLAGS, *flags, "-S", "--cuda-device-only", str(src), "-o", str(lst)]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         if r.returncode != 0:
             raise RuntimeError("hipcc -S failed on %s:\n%s" % (src.name, r.stderr[-3000:]))
@@ -62,7 +60,7 @@ def audit_listing(src, extra, defines, obj):
     print("  %s: audit of the two-waves-per-SIMD build failed (accumulator-file %d, in-flight %d, layout ok %s): rebuilding with -DMF_SAFE"
           % (src.name, acc, flight, two_waves), flush=True)
     safe = ["-DMF_SAFE"]
-    cmd = ["hipcc", *FLAGS, *safe, *["-D" + d for d in defines], "-c", str(src), "-o", str(obj)]
+    cmd = ["hipcc", *FLAGS, *safe, "-c", str(src), "-o", str(obj)]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed on %s (MF_SAFE):\n%s" % (src.name, r.stderr[-3000:]))
@@ -72,32 +70,16 @@ def audit_listing(src, extra, defines, obj):
         raise RuntimeError("%s: the MF_SAFE build fails the audit too (accumulator-file %d, in-flight %d)" % (src.name, acc, flight))
 
 
-def build(force=False, verbose=False, defines=(), out=None):
+def build(force=False, verbose=False, out=None):
     out = Path(out) if out else OUT
     out.parent.mkdir(exist_ok=True)
-    import os
-    # dev builds only: RSPARSE_HIPCC_EXTRA="wrmf_cg_mf.hip=-fno-slp-vectorize;other.hip=-flag1,-flag2" (compiler switches of one source)
-    per_file = {}
-    for item in filter(None, os.environ.get("RSPARSE_HIPCC_EXTRA", "").split(";")):
-        name, _, fl = item.partition("=")
-        per_file[name] = [f for f in fl.split(",") if f]
-    if per_file and out == OUT:
-        raise RuntimeError("RSPARSE_HIPCC_EXTRA is for dev builds (--out)")
-    tag = hashlib.sha1((" ".join(sorted(defines)) + repr(sorted(per_file.items()))).encode()).hexdigest()[:8] if (defines or per_file) else "release"
-    objdir = OUT.parent / "obj" / tag
+    objdir = OUT.parent / "obj"
     objdir.mkdir(parents=True, exist_ok=True)
     src = [s for s in SRC if s.exists()]
     hdr_m = max(h.stat().st_mtime for h in HEADERS)
     todo, objs = [], []
-    names = [d.split("=")[0] for d in defines]
-    hdr_text = "".join(h.read_text() for h in HEADERS if h.suffix == ".h")
     for s in src:
         o = objdir / (s.stem + ".o")
-        if (defines or per_file) and s.name not in per_file and not any(n in s.read_text() or n in hdr_text for n in names):
-            rel = OUT.parent / "obj" / "release" / (s.stem + ".o")   # a dev define this source never mentions: the release object
-            if rel.exists() and rel.stat().st_mtime >= max(s.stat().st_mtime, hdr_m):
-                objs.append(rel)
-                continue
         objs.append(o)
         if force or not o.exists() or o.stat().st_mtime < max(s.stat().st_mtime, hdr_m):
             todo.append((s, o))
@@ -107,13 +89,13 @@ def build(force=False, verbose=False, defines=(), out=None):
     def compile_one(so):
         s, o = so
         t0 = time.time()
-        extra = list(EXTRA_FLAGS.get(s.name, [])) + per_file.get(s.name, [])
-        cmd = ["hipcc", *FLAGS, *extra, *["-D" + d for d in defines], "-c", str(s), "-o", str(o)]
+        extra = EXTRA_FLAGS.get(s.name, [])
+        cmd = ["hipcc", *FLAGS, *extra, "-c", str(s), "-o", str(o)]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         if r.returncode != 0:
             raise RuntimeError("hipcc failed on %s:\n%s" % (s.name, r.stderr[-6000:]))
         if s.name in AUDITED:
-            audit_listing(s, extra, defines, o)
+            audit_listing(s, extra, o)
         if verbose:
             print("  %-20s %.1f s" % (s.name, time.time() - t0), flush=True)
 
@@ -126,15 +108,6 @@ def build(force=False, verbose=False, defines=(), out=None):
 
 if __name__ == "__main__":
     argv = sys.argv[1:]
-    defs, outp, i = [], None, 0
-    while i < len(argv):
-        if argv[i] == "-D":
-            defs.append(argv[i + 1]); i += 2
-        elif argv[i].startswith("-D"):
-            defs.append(argv[i][2:]); i += 1
-        elif argv[i] == "--out":
-            outp = argv[i + 1]; i += 2
-        else:
-            i += 1
+    outp = argv[argv.index("--out") + 1] if "--out" in argv else None
     t0 = time.time()
-    print(build(force="--force" in argv, verbose=True, defines=tuple(defs), out=outp), "%.1f s" % (time.time() - t0))
+    print(build(force="--force" in argv, verbose=True, out=outp), "%.1f s" % (time.time() - t0))

@@ -11,7 +11,6 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
@@ -427,7 +426,7 @@ int build_q_schedule(DevCSC& d, const int32_t* host_col_ptrs) {
   d.q_ne_segs = nullptr; d.q_ne_nseg = 0; d.q_ne_entries = 0;
   d.q_ne_split_rows = nullptr; d.q_ne_split_ptr = nullptr; d.q_ne_nsplit = 0;
   d.q_nec_rows = nullptr; d.q_nec_ptr = nullptr; d.q_nec_wg = 0; d.q_nec_segs = nullptr; d.q_nec_nseg = 0; d.q_nec_entries = 0;
-  d.q_nec_split_rows = nullptr; d.q_nec_split_ptr = nullptr; d.q_nec_nsplit = 0; d.q_nec_own = false; d.q_nec_min = kNeCholMinLen;
+  d.q_nec_split_rows = nullptr; d.q_nec_split_ptr = nullptr; d.q_nec_nsplit = 0; d.q_nec_own = false;
   d.q_n_chol_long = 0;
   d.q_lr_first = 0; d.q_n_lr = 0; d.q_gt32 = 0; d.q_gt48 = 0;
   d.q_pair_first = 0;
@@ -482,14 +481,9 @@ int build_q_schedule(DevCSC& d, const int32_t* host_col_ptrs) {
   }
   // a second set of lists for a longer prefix of the order.  Round 6: the rows beyond kCgMfMax non-zeros -- what is left to the
   // normal-equation kernel when wrmf_cg_mf.hip takes the rows of 513..kCgMfMax (rank 128, implicit conjugate gradient).
-  // (Rounds 2-5: the rows beyond 64, for solver == CHOLESKY at rank 65..128 -- wrmf_chol_mf.hip has those now; dev builds
-  // still set that threshold with RSPARSE_HIP_NE_CHOL_MIN = 64..512 for A/B runs of the old routing.)
-  d.q_nec_min = kCgMfMax;
-#ifdef RSP_AB
-  if (const char* e = std::getenv("RSPARSE_HIP_NE_CHOL_MIN")) d.q_nec_min = std::min(kNeMinLen, std::max(kCholLrMax, std::atoi(e)));
-#endif
+  // (Rounds 2-5: the rows beyond 64, for solver == CHOLESKY at rank 65..128 -- wrmf_chol_mf.hip has those now.)
   int n_nec = 0;
-  while (n_nec < n && host_col_ptrs[order[(size_t)n_nec] + 1] - host_col_ptrs[order[(size_t)n_nec]] > d.q_nec_min) n_nec++;
+  while (n_nec < n && host_col_ptrs[order[(size_t)n_nec] + 1] - host_col_ptrs[order[(size_t)n_nec]] > kCgMfMax) n_nec++;
   d.q_n_nec = n_nec;
   if (n_nec == n_stream) {
     d.q_nec_rows = d.q_ne_rows; d.q_nec_ptr = d.q_ne_ptr; d.q_nec_wg = d.q_ne_wg; d.q_nec_segs = d.q_ne_segs;
@@ -497,7 +491,7 @@ int build_q_schedule(DevCSC& d, const int32_t* host_col_ptrs) {
     d.q_nec_split_ptr = d.q_ne_split_ptr; d.q_nec_nsplit = d.q_ne_nsplit;
   } else {
     NeLists L;
-    if (int rc2 = build_ne_lists(order, host_col_ptrs, n_nec, d.q_nec_min < kNeMinLen ? 72 : 12, L)) return rc2;
+    if (int rc2 = build_ne_lists(order, host_col_ptrs, n_nec, 12, L)) return rc2;
     d.q_nec_own = true;
     d.q_nec_rows = L.rows; d.q_nec_ptr = L.ptr; d.q_nec_wg = L.wg; d.q_nec_segs = L.segs; d.q_nec_nseg = L.nseg;
     d.q_nec_entries = L.entries; d.q_nec_split_rows = L.split_rows; d.q_nec_split_ptr = L.split_ptr; d.q_nec_nsplit = L.nsplit;
@@ -676,11 +670,7 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   qs.ne_split_rows = d.q_ne_split_rows; qs.ne_split_ptr = d.q_ne_split_ptr; qs.ne_nsplit = d.q_ne_nsplit;
   // round 6, rank 128, implicit conjugate gradient without bias operands: the rows of 513..kCgMfMax non-zeros of the first bucket on
   // the wave-per-row kernel of wrmf_cg_mf.hip, the giant rows (a prefix of the order) on the normal-equation kernel's second lists
-  bool cgm_on = cgq && implicit && !bias && cg_mf_supported(rank, implicit) && d.q_nec_min == kCgMfMax;
-#ifdef RSP_AB
-  if (const char* e = std::getenv("RSPARSE_HIP_CG_MF")) cgm_on = cgm_on && std::atoi(e) != 0;
-#endif
-  const bool cg_mf = cgm_on && d.q_order && d.q_off[1] > d.q_n_nec;
+  const bool cg_mf = cgq && implicit && !bias && cg_mf_supported(rank, implicit) && d.q_order && d.q_off[1] > d.q_n_nec;
   if (cg_mf) {
     qs.ne_rows = d.q_nec_rows; qs.ne_ptr = d.q_nec_ptr; qs.ne_wg = d.q_nec_wg; qs.ne_entries = d.q_nec_entries;
     qs.ne_split_rows = d.q_nec_split_rows; qs.ne_split_ptr = d.q_nec_split_ptr; qs.ne_nsplit = d.q_nec_nsplit;
@@ -692,25 +682,15 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   // (the lower threshold pays at rank 65..128 only: at rank <= 64 wrmf_chol.hip's kernel is cheaper than the fixed cost of
   // the tile solve up to 512 non-zeros -- config 5 with Cholesky 4.5 against 4.1 iterations/s)
   // (round 6, rank 65..128: the rows of 65..512 non-zeros go to the wave-per-row kernel of wrmf_chol_mf.hip instead -- the
-  // normal-equation launch keeps the rows beyond 512, its CG lists; RSPARSE_HIP_CHOL_MF=0 in -DRSP_AB builds: the round-5 routing)
-  bool mf_on = chol_mf_supported(rank);
-#ifdef RSP_AB
-  if (const char* e = std::getenv("RSPARSE_HIP_CHOL_MF")) mf_on = mf_on && std::atoi(e) != 0;
-#endif
-  const bool chol_mf = mf_on && !cg && solver == RSPARSE_SOLVER_CHOLESKY && !bias && d.q_order && ne_supported(rank) &&
+  // normal-equation launch keeps the rows beyond 512, its CG lists)
+  const bool chol_mf = chol_mf_supported(rank) && !cg && solver == RSPARSE_SOLVER_CHOLESKY && !bias && d.q_order && ne_supported(rank) &&
                        use_cgq(rank, d_X, d_Y) && d.q_lr_first > d.q_off[1];
-  int n_mf = chol_mf ? d.q_lr_first - d.q_off[1] : 0;
-  int mf_first = d.q_off[1];
-#ifdef RSP_AB   // timing experiments: every row beyond 64 non-zeros on the wave-per-row kernel (giant rows included: one wave each)
-  if (chol_mf && std::getenv("RSPARSE_HIP_CHOL_MF_ALL")) {   // (= 2: without the rows beyond 4096 non-zeros, which nobody solves then)
-    mf_first = std::atoi(std::getenv("RSPARSE_HIP_CHOL_MF_ALL")) == 2 ? d.q_n_chol_long : 0;
-    n_mf = d.q_lr_first - mf_first;
-  }
-#endif
+  const int mf_first = d.q_off[1];
+  const int n_mf = chol_mf ? d.q_lr_first - mf_first : 0;
   const bool nec_lists = padded_rank(rank) > 64 && d.q_nec_wg > 0 && !chol_mf;
   const bool ne_chol = !cg && solver == RSPARSE_SOLVER_CHOLESKY && !bias && (nec_lists || d.q_ne_wg > 0 || chol_mf) &&
                        ne_supported(rank) && use_cgq(rank, d_X, d_Y);
-  if (ne_chol && nec_lists) {   // its own lists: the rows beyond d.q_nec_min non-zeros
+  if (ne_chol && nec_lists) {   // its own lists: the rows beyond kCgMfMax non-zeros
     qs.ne_rows = d.q_nec_rows; qs.ne_ptr = d.q_nec_ptr; qs.ne_wg = d.q_nec_wg; qs.ne_entries = d.q_nec_entries;
     qs.ne_split_rows = d.q_nec_split_rows; qs.ne_split_ptr = d.q_nec_split_ptr; qs.ne_nsplit = d.q_nec_nsplit;
   }
@@ -752,11 +732,10 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   a.gbias = gb_cg ? bias->gbias : 0.f;
   a.ne_r0 = nullptr; a.ne_r0_slot = nullptr;
   a.tscr = nullptr; a.stream_off = d.q_stream_off; a.stream_nnz = d.q_nnz[0];
-  a.ne_prof = nullptr;
   a.ne_stats = nullptr; a.wave_stats = nullptr; a.mf_XtX = nullptr;
   a.ne_segs = nullptr; a.ne_seg_scratch = nullptr; a.ne_seg_flags = nullptr;
   a.ne_chol = ne_chol ? 1 : 0;
-  a.ne_chol_min = nec_lists ? d.q_nec_min : kNeMinLen;
+  a.ne_chol_min = nec_lists ? kCgMfMax : kNeMinLen;
   if (d.q_order && solver == RSPARSE_SOLVER_CHOLESKY) {
     // the k x k kernel's own rows as ranges of the length-sorted order: behind the prefix that the normal-equation launch
     // (or the LONG launch) takes, down to the short rows of the low-rank kernel, and the empty rows at the end
@@ -798,12 +777,6 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
       a.ne_r0 = g_ws.gb_r0; a.ne_r0_slot = g_ws.gb_slot;
     }
   }
-#ifdef RSP_NE_PROF
-  static unsigned long long* prof_buf = nullptr;
-  if (!prof_buf) { HIP_TRY(hipMalloc(&prof_buf, (size_t)65536 * 4 * 20 * 8)); }
-  HIP_TRY(hipMemsetAsync(prof_buf, 0, (size_t)65536 * 4 * 20 * 8, s));
-  a.ne_prof = prof_buf;
-#endif
   // ranks the normal-equation kernel does not take (<= 32): the streamed CG bucket keeps its per-sweep dot products in
   // an HBM scratch instead of re-gathering for the loss
   if (cgq && !ne_supported(rank) && d.q_stream_off && d.q_nnz[0] > 0 && cg_steps >= 1 && cg_steps <= 4) {
@@ -864,17 +837,6 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
     if (me != hipSuccess) return hip_fail(me, "launch_als_chol_mf");
   }
   if (chol && ev) HIP_TRY(hipEventRecord(ev[4], s));
-#if defined(RSP_NE_PROF) && defined(RSP_MF_PROF)
-  if (chol_mf && std::getenv("RSPARSE_MF_PROF")) {   // phase ticks of wrmf_chol_mf.hip, summed over its waves
-    HIP_TRY(hipStreamSynchronize(s));
-    unsigned long long hp[8];
-    HIP_TRY(hipMemcpy(hp, prof_buf + 8, sizeof(hp), hipMemcpyDeviceToHost));
-    const char* nm[8] = {"zero", "assembly", "finalize", "forward", "backward", "fail/store", "loss", "row-head"};
-    std::fprintf(stderr, "[mf_prof] n_cols %d rows %d: G ticks summed over the waves:", d.n_cols, n_mf);
-    for (int j = 0; j < 8; j++) std::fprintf(stderr, " %s %.3f", nm[j], (double)hp[j] / 1e9);
-    std::fprintf(stderr, "\n");
-  }
-#endif
   if (chol) {
     // rows whose factorisation met a non-positive pivot: the general solver, as arma::solve falls back to (wrmf_lu.hip).
     // The counters are per call: a previous call's count was taken by rsparse_hip_take_numeric_failures or is added to.
@@ -883,63 +845,6 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   }
   e = launch_sum_partials(g_ws.partials, slots, out, s, g_ws.partials + g_ws.partial_slots);
   if (e != hipSuccess) return hip_fail(e, "launch_sum_partials");
-#if defined(RSP_NE_PROF) && defined(RSP_NNLS_PROF)
-  if (solver == RSPARSE_SOLVER_NNLS && std::getenv("RSPARSE_NNLS_PROF")) {   // phase ticks of als_nnls_wave_kernel, summed over its waves
-    HIP_TRY(hipStreamSynchronize(s));
-    unsigned long long hp[8];
-    HIP_TRY(hipMemcpy(hp, prof_buf + 32, sizeof(hp), hipMemcpyDeviceToHost));
-    std::fprintf(stderr, "[nnls_prof] n_cols %d: rows %llu, sweeps per row %.1f, coordinates visited per sweep %.1f; G ticks summed over the waves: assembly %.3f square %.3f sweeps %.3f loss %.3f row-head %.3f\n",
-                 d.n_cols, hp[5], hp[5] ? (double)hp[6] / (double)hp[5] : 0.0, hp[6] ? (double)hp[7] / (double)hp[6] : 0.0,
-                 (double)hp[0] / 1e9, (double)hp[1] / 1e9, (double)hp[2] / 1e9, (double)hp[3] / 1e9, (double)hp[4] / 1e9);
-  }
-#endif
-#if defined(RSP_NE_PROF) && defined(RSP_MF_PROF)
-  if (cgq && std::getenv("RSPARSE_MF_PROF")) {   // phase ticks of wrmf_cg_mf.hip, summed over its waves
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipDeviceSynchronize());
-    unsigned long long hp[12];
-    HIP_TRY(hipMemcpy(hp, prof_buf + 16, sizeof(hp), hipMemcpyDeviceToHost));
-    const char* nm[8] = {"row-head", "prologue", "wait", "request", "step", "flush+unscale", "cg", "loss+tail"};
-    std::fprintf(stderr, "[cgmf_prof] n_cols %d: rows %llu steps %llu, shader clock %.3f GHz (s_memtime / s_memrealtime), wave-seconds %.3f, G ticks summed over the waves (total %.3f):",
-                 d.n_cols, hp[9], hp[8], hp[11] ? (double)hp[10] / (double)hp[11] * 0.1 : 0.0, (double)hp[11] / 1e8, (double)hp[10] / 1e9);
-    for (int j = 0; j < 8; j++) std::fprintf(stderr, " %s %.3f", nm[j], (double)hp[j] / 1e9);
-    std::fprintf(stderr, "\n");
-  }
-#endif
-#ifdef RSP_NE_PROF
-  if ((cgq || ne_chol) && qs.ne_wg > 0 && std::getenv("RSPARSE_NE_PROF")) {   // (solver == CHOLESKY: mv_* = diagonal tile, panel, trailing, backward)
-    HIP_TRY(hipStreamSynchronize(s));
-    std::vector<unsigned long long> hp((size_t)qs.ne_wg * 4 * 20);
-    HIP_TRY(hipMemcpy(hp.data(), prof_buf, hp.size() * 8, hipMemcpyDeviceToHost));
-    const char* nm[20] = {"wait_vm", "barrier", "issue", "consume", "tail", "total", "rows", "pre", "chain", "cg", "quad", "fin", "ch_sync", "ch_add", "ch_bar", "mv_pub", "mv_units", "mv_bar", "mv_comb", "-"};
-    for (int w = 0; w < 4; w++) {
-      std::fprintf(stderr, "[ne_prof] wave %d (n_cols %d):", w, d.n_cols);
-      for (int j = 0; j < 19; j++) {
-        double sum = 0, mx = 0;
-        for (int b = 0; b < qs.ne_wg; b++) { const double v = (double)hp[((size_t)b * 4 + w) * 20 + j]; sum += v; mx = std::max(mx, v); }
-        std::fprintf(stderr, " %s %.2f/%.2f", nm[j], sum / qs.ne_wg / 1e6, mx / 1e6);
-      }
-      std::fprintf(stderr, " Mcycles (mean/max over %d workgroups)\n", qs.ne_wg);
-    }
-#ifdef RSP_CGQ_PROF
-    {
-      unsigned long long cq[6];
-      HIP_TRY(hipMemcpy(cq, prof_buf + (size_t)65536 * 80 - 16, sizeof(cq), hipMemcpyDeviceToHost));
-      std::fprintf(stderr, "[cgq_prof] 8-wave launch (n_cols %d), G ticks summed over its waves: gather %.2f setup %.2f sweeps %.2f issue %.2f cg %.2f tail %.2f\n",
-                   d.n_cols, cq[0] / 1e9, cq[1] / 1e9, cq[2] / 1e9, cq[3] / 1e9, cq[4] / 1e9, cq[5] / 1e9);
-    }
-#endif
-    if (const char* dump = std::getenv("RSPARSE_NE_PROF_DUMP")) {   // per workgroup: total, rows, consume, wait_vm of wave 0
-      if (FILE* f = std::fopen(dump, "a")) {
-        std::fprintf(f, "# launch n_cols %d wgs %d\n", d.n_cols, qs.ne_wg);
-        for (int b = 0; b < qs.ne_wg; b++)
-          std::fprintf(f, "%d %llu %llu %llu %llu\n", b, hp[((size_t)b * 4) * 20 + 5], hp[((size_t)b * 4) * 20 + 6],
-                       hp[((size_t)b * 4) * 20 + 3], hp[((size_t)b * 4) * 20 + 0]);
-        std::fclose(f);
-      }
-    }
-  }
-#endif
   if (ev) {
     const int last = cgq ? 7 : (chol ? 5 : 3);
     HIP_TRY(hipEventRecord(ev[last], s));

@@ -218,15 +218,6 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
   if (lane == 0) sw.loss = 0.0;
   __syncthreads();
 
-#ifdef RSP_MF_PROF   // dev builds (tools/gpu_cgmf_prof.sh): s_memtime ticks per phase, summed over the waves into a.ne_prof[16 ..]
-  unsigned long long pt[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, pt0 = __builtin_amdgcn_s_memtime();
-  const unsigned long long pt_start = pt0, rt_start = __builtin_amdgcn_s_memrealtime();   // (100 MHz: ticks / realtime = the shader clock)
-#define CGM_TICK(i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); pt[i] += t_ - pt0; pt0 = t_; }
-#define CGM_COUNT(i, n) pt[i] += (n);
-#else
-#define CGM_TICK(i)
-#define CGM_COUNT(i, n)
-#endif
   auto uni = [](const float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); };
   const int ex = rfl(mf_scale_exp(fmaxf(__uint_as_float(a.ne_stats[0]), 1e-30f)));
   const float wmax = uni(fmaxf(__uint_as_float(a.ne_stats[1]) - 1.f, 1.f));
@@ -237,7 +228,6 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
   const int n_waves = 4 * gridDim.x;
 
   for (int it = 4 * blockIdx.x + wv; it < n_rows; it += n_waves) {
-    CGM_TICK(7)
     const int row = rfl(rows[it]);
     const int p1 = rfl(a.col_ptrs[row]), p2 = rfl(a.col_ptrs[row + 1]);
     float* yrow = a.Y + (size_t)row * k;
@@ -408,9 +398,6 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
       }
       auto mm = [&](auto it, const CgmOps& P) __attribute__((always_inline)) {
         constexpr CgmProd pd = cgm_prod(decltype(it)::value);
-#if defined(CGM_ABL) && (CGM_ABL & 1)   // timing-only dev build: no matrix instructions
-        return;
-#endif
         if constexpr (pd.kind == 0) {
           if constexpr (pd.T < 6) cgm_mma16<10 + pd.T>(P.mh[pd.K], P.mh[pd.I]);
           else hi[pd.T - 6] = __builtin_amdgcn_mfma_f32_32x32x16_f16(P.mh[pd.K], P.mh[pd.I], hi[pd.T - 6], 0, 0, 0);
@@ -457,11 +444,6 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
         float4 va[2], vb[2];
         va[0] = va0;
         vb[0] = vb0;
-#if defined(CGM_ABL) && (CGM_ABL & 2)   // timing-only dev build: the matrix instructions alone
-        mf_sfor<40>([&](auto it) { mm(it, P); __builtin_amdgcn_sched_barrier(0); });
-        N = P;
-        return;
-#endif
         unsigned hm[4][4], hh[4][4], ll[4][4];   // [block][pair]
         mf_sfor<4>([&](auto qt) {
           constexpr int q = decltype(qt)::value;
@@ -513,8 +495,6 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
         }
       };
       // prologue: chunks 0 and 1 of the indices, then steps 0 and 1
-      CGM_TICK(0)
-      CGM_COUNT(8, nsteps) CGM_COUNT(9, 1)
       wave_sync();
       request_meta(0);
       request_meta(1);
@@ -523,7 +503,6 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
       request(0, 0);
       request(1, 1);
       const int tail_st = ((p2 - p1) & 15) ? nsteps - 1 : -1;
-      CGM_TICK(1)
       int slot = 0;   // = st % 3
       for (int c = 0; 4 * c < nsteps; c++) {
         bool done = false;
@@ -547,16 +526,13 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
             // younger than step st in the queue: step st + 1 (8) and, behind sub-step j = 0, a chunk of indices (2)
             if constexpr (j == 1) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            CGM_TICK(2)
             if constexpr (SYM) first_reads(slot, c % 3, j);   // (their latency passes while the requests below are issued)
             // (measured and not kept: the eight pieces one by one BETWEEN the step's matrix instructions, like the vector work:
             // 16.8 ms per launch against 15.0 -- a piece costs more there than the ~55 cycles it takes in a block in front)
             request(st + 2, slot2);
             if constexpr (j == 0) request_meta(c + 2);
-            CGM_TICK(3)
           } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            CGM_TICK(2)
             if constexpr (SYM) {
               if (st == tail_st) zero_tail(slot, (p2 - p1) & 15);   // wave-uniform (the row's last step is never in the branch above)
               first_reads(slot, c % 3, j);
@@ -580,7 +556,6 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
             __builtin_amdgcn_sched_barrier(0);
           }
           slot = slot == 2 ? 0 : slot + 1;
-          CGM_TICK(4)
         });
         if (done) break;
       }
@@ -646,7 +621,6 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
       }
     };
     // ---- cg_solver_implicit (wrmf_implicit.hpp:8-32) on A = XtX + M1 ----
-    CGM_TICK(5)
     float r[4], p[4], ap[4];
     cgm_matvec(rd_m1, g_tile, sw, n, hf, ln, x, ap);
 #pragma unroll
@@ -665,7 +639,6 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
       rsold = rsnew;
     }
     // ---- the row and its loss term: sum c - 2 y.b + y^T (M1 + M2) y + lambda |y|^2 ----
-    CGM_TICK(6)
     if (hf == 0) {
       int row2 = row;   // (the row's address again from scalar registers: held in a vector pair since the warm start it was the one spill)
       asm volatile("" : "+s"(row2));
@@ -715,13 +688,6 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
     wave_sync();
   }
   if (lane == 0) a.loss_partials[loss_slot0 + 4 * blockIdx.x + wv] = sw.loss;
-#ifdef RSP_MF_PROF
-  CGM_TICK(7)
-  pt[10] = __builtin_amdgcn_s_memtime() - pt_start;
-  pt[11] = __builtin_amdgcn_s_memrealtime() - rt_start;
-  if (a.ne_prof && lane == 0)
-    for (int j = 0; j < 12; j++) atomicAdd(a.ne_prof + 16 + j, pt[j]);
-#endif
 }
 
 }  // namespace

@@ -23,7 +23,6 @@
 // LDS with one barrier per CG sweep.  Rows beyond the workgroup's capacity are streamed (STREAM = 1
 // instantiation): the first 16 non-zeros per wave stay in LDS, the rest is re-gathered in every sweep.
 #include <algorithm>
-#include <cstdlib>
 
 #include "wrmf_internal.h"
 #include "wrmf_device.h"
@@ -35,34 +34,18 @@ using namespace dev;
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// tuning switches (resident kernels with CAPQ >= the value use the feature)
-#ifndef RSP_ZPAD_MINCAPQ
-#define RSP_ZPAD_MINCAPQ 0
-#endif
-#ifndef RSP_TSAVE_MINCAPQ
-#define RSP_TSAVE_MINCAPQ 0
-#endif
-#ifndef RSP_GVFIRST_MINCAPQ
-#define RSP_GVFIRST_MINCAPQ 16
-#endif
-// streamed rows: request the next chunk's indices / values (lane-major) while the current chunk is in flight -- one
-// HBM round trip per chunk instead of two (-3 % on the streamed launch).  Implicit instantiations only: the explicit
-// one is at 256 VGPRs and would spill
-#ifndef RSP_STREAM_IDX_PREFETCH
-#define RSP_STREAM_IDX_PREFETCH 1
-#endif
-// streamed rows: quads per wave of the row's prefix that stay in LDS across the sweeps (0 disables).  4 = one
-// quad-pass block = 128 non-zeros per 8-wave team = 64 KB of LDS next to the 64 KB Gramian; 5 measured 1.5 % faster
-// on the launch but needs the idle quads of the second block zeroed (they are stale registers otherwise)
+// resident kernels with CAPQ >= this many quads run the dense G v product of a sweep before the quad pass, not after it
+constexpr int kGvFirstMinCapq = 16;
+// streamed rows: quads per wave of the row's prefix that stay in LDS across the sweeps.  4 = one quad-pass block = 128
+// non-zeros per 8-wave team = 64 KB of LDS next to the 64 KB Gramian; 5 measured 1.5 % faster on the launch but needs the
+// idle quads of the second block zeroed (they are stale registers otherwise)
+constexpr int kStreamPrefixQ = 4;
 // resident rows: prefetch the next row's indices / values (one per lane, 2 VGPRs) during the current row's sweeps, so
 // the gather at the row switch is one HBM round trip instead of two.  Teams of up to this many waves use it: -4..6 %
-// on the 1- and 2-wave kernels; the 4- and 8-wave kernels sit at 256 VGPRs and the two registers spill (+5 %)
-#ifndef RSP_IDX_PREFETCH_MAXWPR
-#define RSP_IDX_PREFETCH_MAXWPR 2
-#endif
-#ifndef RSP_STREAM_PREFIX_Q
-#define RSP_STREAM_PREFIX_Q 4
-#endif
+// on the 1- and 2-wave kernels; the 4- and 8-wave kernels sit at 256 VGPRs and the two registers spill (+5 %).
+// Streamed rows of the implicit instantiations request the next chunk's indices / values (lane-major) the same way
+// while the current chunk is in flight (-3 % on the streamed launch); the explicit one is at 256 VGPRs and would spill
+constexpr int kIdxPrefetchMaxWpr = 2;
 
 constexpr float kCgTolQ = 1e-10f;  // CG_TOL, inst/include/wrmf.hpp:22
 constexpr int kMaxSavedSweeps = 4;  // streamed rows keep the dot products of up to this many CG steps
@@ -133,11 +116,6 @@ __device__ __forceinline__ void groups_all_gather4(const float r, float& o0, flo
   o2 = __uint_as_float(hi[0]);
   o3 = __uint_as_float(hi[1]);
 }
-#ifndef RSP_NO_GRS
-#define RSP_GRS 1
-#else
-#define RSP_GRS 0
-#endif
 
 // ---- dense product on the matrix cores (DMF instantiation: one-wave rows of <= 32 non-zeros at rank 65..128) ----
 // The four rows a workgroup solves side by side share every G v product: G is held in REGISTERS as two fp16 terms
@@ -191,17 +169,17 @@ struct QSmem {
   static constexpr size_t red_floats = WPR > 1 ? (size_t)2 * WAVES * KP + 2 * WAVES : 0;
   // resident rows: per wave, t_acc[CAP] = x_j . y accumulated over the CG steps and t_cur[CAP] = x_j . p of the
   // current step (the loss is rebuilt from them instead of a fifth pass over the registers)
-  static constexpr size_t tsv_floats = (STREAM && !(RSP_STREAM_IDX_PREFETCH && IMPLICIT)) ? 0 : (size_t)WAVES * 2 * CAPQ * 4;
-  // streamed rows: the first RSP_STREAM_PREFIX_Q quads of every wave (gathered in the first sweep) stay in LDS,
+  static constexpr size_t tsv_floats = (STREAM && !IMPLICIT) ? 0 : (size_t)WAVES * 2 * CAPQ * 4;
+  // streamed rows: the first kStreamPrefixQ quads of every wave (gathered in the first sweep) stay in LDS,
   // so the other sweeps re-gather only the rest of the row
-  static constexpr size_t pre_floats = STREAM ? (size_t)WAVES * RSP_STREAM_PREFIX_Q * 4 * KP : 0;
+  static constexpr size_t pre_floats = STREAM ? (size_t)WAVES * kStreamPrefixQ * 4 * KP : 0;
   // DMF: the published fp16 terms of the workgroup's vectors (row stride KP + 8 halves) and the products (KP + 4 floats):
   // the paddings shift consecutive rows by four banks, so the operand reads / result writes of four rows do not collide
   static constexpr int dmf_ps = KP + 8, dmf_os = KP + 4;
   static constexpr size_t dmf_floats = DMF ? (size_t)WAVES * dmf_ps + (size_t)WAVES * dmf_os : 0;
-  // resident rows on teams of more than RSP_IDX_PREFETCH_MAXWPR waves: the next row's indices / values (one per lane) land here
+  // resident rows on teams of more than kIdxPrefetchMaxWpr waves: the next row's indices / values (one per lane) land here
   // by LDS-DMA during the current row's sweeps -- those kernels have no two registers to hold them (KFULL instantiations)
-  static constexpr size_t pfx_floats = (!STREAM && WPR > RSP_IDX_PREFETCH_MAXWPR && CAPQ * 4 == 64) ? (size_t)WAVES * 2 * 64 : 0;
+  static constexpr size_t pfx_floats = (!STREAM && WPR > kIdxPrefetchMaxWpr && CAPQ * 4 == 64) ? (size_t)WAVES * 2 * 64 : 0;
   static constexpr size_t bytes = (gram_floats + vec_floats + red_floats + tsv_floats + pre_floats + dmf_floats + pfx_floats) * 4 + 16;
 };
 
@@ -219,7 +197,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
   using piece_t = typename Piece<VW>::type;
   using SM = QSmem<KP, CAPQ, WAVES, WPR, STREAM, IMPLICIT, DMF>;
   static_assert(WAVES % WPR == 0, "teams must tile the workgroup");
-  constexpr bool GRS = RSP_GRS && RPN == 8 && VW == 4;   // the four-registers-at-once group reductions (rank 65..128)
+  constexpr bool GRS = RPN == 8 && VW == 4;   // the four-registers-at-once group reductions (rank 65..128)
   auto groups_all_reduce8 = [](float(&a8)[RPN]) {
     if constexpr (RPN == 8) {
       const float r0 = groups_reduce_scatter4(a8[0], a8[1], a8[2], a8[3]);
@@ -340,14 +318,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
   float* tcur = tacc + CAP;
   int buf = 0;
   double wloss = 0.0;
-#ifdef RSP_CGQ_PROF   // dev builds: ticks per phase, summed over the waves of the 8-wave launch (wrmf_capi.cpp prints them)
-  unsigned long long cq_t[6] = {0, 0, 0, 0, 0, 0};
-  unsigned long long cq_l = __builtin_amdgcn_s_memtime();
-#define CQ_T(j) { const unsigned long long t1_ = __builtin_amdgcn_s_memtime(); cq_t[j] += t1_ - cq_l; cq_l = t1_; }
-#else
-#define CQ_T(j)
-#endif
-  int pf_id = 0, pf_cnt = -1;   // next row's share of this wave, lane-major (RSP_IDX_PREFETCH)
+  int pf_id = 0, pf_cnt = -1;   // next row's share of this wave, lane-major (IDXPF)
   float pf_c = 0.f;
   const int team_global = blockIdx.x * TEAMS + team;
   const int total_teams = gridDim.x * TEAMS;
@@ -389,7 +360,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
       if constexpr (!DMF) continue;   // DMF: the workgroup's waves share the dense products, so this wave keeps in step
     }
     // streamed rows: the first PTEAM non-zeros are the LDS-resident prefix (PCAP per wave), the rest is streamed
-    constexpr int PQ = STREAM ? RSP_STREAM_PREFIX_Q : 0, PCAP = PQ * 4, PTEAM = PCAP * WPR;
+    constexpr int PQ = STREAM ? kStreamPrefixQ : 0, PCAP = PQ * 4, PTEAM = PCAP * WPR;
     const int pre = STREAM ? min(cnt, PTEAM) : 0;
     const int pw = STREAM ? max(0, min(PCAP, pre - tw * PCAP)) : 0;   // this wave's share of the prefix
     const int nchunks = (cnt - pre + CAP - 1) / CAP;
@@ -422,16 +393,12 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
     // all-zero row and carry c = 0, so t = 0 and every weight derived from (c, t) is 0 -- they drop out of all
     // sums without a select in the sweeps.  Streamed rows (gathered every sweep): clamped duplicates of the
     // last non-zero, masked by `valid` in quad_pass (cheaper than the pointer selects per gather).
-    constexpr bool ZPAD = STREAM == 0 && CAPQ >= RSP_ZPAD_MINCAPQ;
-    constexpr bool TSAVE = STREAM == 0 && CAPQ >= RSP_TSAVE_MINCAPQ;
-    constexpr bool GVFIRST = STREAM == 0 && CAPQ >= RSP_GVFIRST_MINCAPQ;
-    constexpr bool IDXPF = CAP <= 64 && ((STREAM == 0 && WPR <= RSP_IDX_PREFETCH_MAXWPR) || (STREAM == 1 && IMPLICIT && RSP_STREAM_IDX_PREFETCH));
+    constexpr bool ZPAD = STREAM == 0;
+    constexpr bool TSAVE = STREAM == 0;
+    constexpr bool GVFIRST = STREAM == 0 && CAPQ >= kGvFirstMinCapq;
+    constexpr bool IDXPF = CAP <= 64 && ((STREAM == 0 && WPR <= kIdxPrefetchMaxWpr) || (STREAM == 1 && IMPLICIT));
     // the LDS-DMA variant of the same prefetch for the kernels that have no registers for it (see QSmem::pfx_floats)
-#ifdef RSP_NO_DMAPF   // dev builds: A/B of the LDS-DMA prefetch alone
-    constexpr bool DMAPF = false;
-#else
     constexpr bool DMAPF = KFULL && !IDXPF && SM::pfx_floats > 0;
-#endif
     int* pfxI = reinterpret_cast<int*>(sPfx) + wv * 128;
     float* pfxC = sPfx + wv * 128 + 64;
     int pf_pos = -1;   // streamed rows: chunk the prefetch registers belong to
@@ -561,15 +528,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
     if constexpr (resident) {
       // balanced shares: every wave of the team takes ceil(cnt / WPR) non-zeros rounded up to a quad-pass block (16),
       // so the team's sweep time is that of the average wave, not of a full one next to idle ones
-#ifdef RSP_SEQ_FILL
-      const int per = CAP;
-#else
       const int per = min(CAP, (((cnt + WPR - 1) / WPR) + 15) & ~15);
-#endif
       ccnt = max(0, min(per, cnt - tw * per));
-#ifdef RSP_GATHER_PRIO   // dev builds: a gathering wave issues ahead of the waves that sweep on the same SIMD
-      __builtin_amdgcn_s_setprio(3);
-#endif
       if constexpr (WS_FIRST) {
         // no branch around the gather: at a join the compiler has to assume that the warm start is the NEWEST load in
         // flight and drains the queue where it is first used.  A wave without a share gathers the all-zero row (n = 0)
@@ -578,12 +538,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         if (ccnt > 0) gather(p1 + tw * per, ccnt, pf_cnt == ccnt);
       }
       pf_cnt = -1;
-#ifdef RSP_GATHER_PRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
     }
 
-    CQ_T(0)   // row switch + gather
     if constexpr (!WS_FIRST) load_warm_start();
 
     // one pass over the resident quads: t = X_nnz^T v, then acc += X_nnz w  (or the loss terms)
@@ -594,7 +550,6 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
       for (int q0 = 0; q0 < CAPQ; q0 += QB) {
         if (4 * q0 < ccnt) {  // wave-uniform
           float t[QB];
-#ifndef RSP_NO_QUAD_ILV
           // the four quads' dot chains and DPP reductions written INTERLEAVED: a packed FMA / DPP add and the instruction
           // that consumes its result need one / two wait states, which four independent chains fill with work
           // (tools/dbg/loop_mix.py counted 21 hazard s_nops per 79-instruction quad block in the chain-after-chain order)
@@ -620,22 +575,6 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
           for (int u = 0; u < QB; u++) t[u] += dpp<0x141>(t[u]);  // row_half_mirror
 #pragma unroll
           for (int u = 0; u < QB; u++) t[u] += dpp<0x140>(t[u]);  // row_mirror
-#else
-#pragma unroll
-          for (int u = 0; u < QB; u++) {
-            // two interleaved partial sums -> v_pk_fma_f32 (RPN is even for every supported rank)
-            f32x2 s2 = {0.f, 0.f};
-#pragma unroll
-            for (int rr = 0; rr < RPN; rr += 2) {
-              const f32x2 xa = {xt[q0 + u][rr], xt[q0 + u][rr + 1]};
-              const f32x2 va = {v[rr], v[rr + 1]};
-              s2 = __builtin_elementwise_fma(xa, va, s2);
-            }
-            t[u] = s2.x + s2.y;
-          }
-#pragma unroll
-          for (int u = 0; u < QB; u++) t[u] = row16_sum(t[u]);
-#endif
 #pragma unroll
           for (int u = 0; u < QB; u++) {
             const int q = q0 + u;
@@ -955,9 +894,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
 
     const bool live = have && (GB || cnt > 0);
     float dummy = 0.f;
-    CQ_T(1)   // warm start, setup
     sweep(x, 0, r, dummy, live);
-    CQ_T(2)   // sweeps
     if constexpr (IDXPF && STREAM == 0) {
       // the next row's pointers were requested at the top of this iteration and have arrived by now
       if (it + 1 < rows_per_team && row_index(it + 1) < n_rows) {
@@ -985,17 +922,13 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         }
       }
     }
-    CQ_T(3)   // staging issue / index prefetch
 #pragma unroll
     for (int rr = 0; rr < RPN; rr++) p[rr] = r[rr];
     float rsold = dot16(r, r);
     bool conv = false;
     for (int itc = 0; itc < a.cg_steps; ++itc) {
       if (WPR == 1 && !DMF && conv) break;
-      CQ_T(4)   // CG scalars and updates
       sweep(p, 1, ap, dummy, live && !conv, itc + 1);
-      CQ_T(2)
-      CQ_T(3)
       if (!conv) {
         const float pap = dot16(p, ap);
         // rsold / alpha / beta as the reference holds them: double scalars fed by T-valued dot products
@@ -1030,9 +963,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
       }
     }
     float rl = 0.f;
-    CQ_T(4)
     sweep(x, 2, ap, rl, live);
-    CQ_T(2)
     if constexpr (DMAPF) wait_vm0();   // the announced row's indices have long landed; nothing of this wave's is in flight after this
     if constexpr (IDXPF && STREAM == 0) {
       // settle the prefetch registers HERE (their loads were issued three sweeps ago): left to the next row's first use, the
@@ -1057,11 +988,6 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
       }
     }
   }
-  CQ_T(5)   // loss, store of the row
-#ifdef RSP_CGQ_PROF
-  if (WAVES == 8 && WPR == 8 && !STREAM && a.ne_prof && lane == 0)
-    for (int j = 0; j < 6; j++) atomicAdd(a.ne_prof + (size_t)65536 * 80 - 16 + j, cq_t[j]);
-#endif
   if (lane == 0) a.loss_partials[loss_slot0 + (size_t)blockIdx.x * WAVES + wv] = wloss;
 }
 
@@ -1087,58 +1013,31 @@ constexpr BucketDef kBuckets[kNCfg][kNB] = {
 };
 constexpr int cfg_of_kp(int KP) { return KP == 64 ? 1 : 0; }
 
-// dev builds (-DRSP_AB): RSPARSE_HIP_DENSE_MFMA=0 keeps the one-wave rows of <= 32 non-zeros on the vector-unit G v
-// product (the A/B switch behind DESIGN.md 3.1)
-bool dense_mfma_enabled() {
-#ifdef RSP_AB
-  static const bool on = [] {
-    const char* e = std::getenv("RSPARSE_HIP_DENSE_MFMA");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-#else
-  return true;
-#endif
-}
-
-// dev builds (-DRSP_AB): RSPARSE_HIP_KFULL=0 keeps the instantiations that drain the gather before the first sweep
-bool kfull_enabled() {
-#ifdef RSP_AB
-  static const bool on = [] {
-    const char* e = std::getenv("RSPARSE_HIP_KFULL");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-#else
-  return true;
-#endif
-}
-
 template <int KP, int WAVES, int CAPQ, int WPR, int STREAM, bool IMPLICIT, bool GB, int DMF = 0, bool KFULL = false>
 hipError_t launch_bucket(const AlsArgs& a, const int32_t* rows, int n_rows, int grid, size_t slot0, hipStream_t s,
                          hipEvent_t* ev_slot) {
   if (n_rows <= 0) return hipSuccess;
   constexpr bool kDmfGeometry = IMPLICIT && KP == 128 && WAVES == 4 && WPR == 1 && (CAPQ == 8 || CAPQ == 16) && STREAM == 0;
   if constexpr (kDmfGeometry && !DMF) {
-    if (dense_mfma_enabled())
-      return launch_bucket<KP, WAVES, CAPQ, WPR, STREAM, IMPLICIT, GB, CAPQ == 8 ? 1 : 2>(a, rows, n_rows, grid, slot0, s, ev_slot);
+    return launch_bucket<KP, WAVES, CAPQ, WPR, STREAM, IMPLICIT, GB, CAPQ == 8 ? 1 : 2>(a, rows, n_rows, grid, slot0, s, ev_slot);
+  } else {
+    // the rank is the padded rank (32 / 64 / 128): the instantiation whose first sweep runs behind the gather
+    if constexpr (!KFULL && STREAM == 0) {
+      if (a.k == KP)
+        return launch_bucket<KP, WAVES, CAPQ, WPR, STREAM, IMPLICIT, GB, DMF, true>(a, rows, n_rows, grid, slot0, s, ev_slot);
+    }
+    constexpr int TEAMS = WAVES / WPR;
+    auto kern = als_cgq_kernel<KP, CAPQ, WAVES, WPR, STREAM, IMPLICIT, DMF, GB, KFULL>;
+    const size_t lds = QSmem<KP, CAPQ, WAVES, WPR, STREAM, IMPLICIT, DMF>::bytes;
+    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) return err;
+    const int total_teams = grid * TEAMS;
+    const int rpt = (n_rows + total_teams - 1) / total_teams;
+    prof_note(ev_slot, reinterpret_cast<const void*>(kern));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, s, a, rows, n_rows, rpt, slot0);
+    return hipGetLastError();
   }
-  // the rank is the padded rank (32 / 64 / 128): the instantiation whose first sweep runs behind the gather
-  if constexpr (!KFULL && STREAM == 0) {
-    if (a.k == KP && kfull_enabled())
-      return launch_bucket<KP, WAVES, CAPQ, WPR, STREAM, IMPLICIT, GB, DMF, true>(a, rows, n_rows, grid, slot0, s, ev_slot);
-  }
-  constexpr int TEAMS = WAVES / WPR;
-  auto kern = als_cgq_kernel<KP, CAPQ, WAVES, WPR, STREAM, IMPLICIT, DMF, GB, KFULL>;
-  const size_t lds = QSmem<KP, CAPQ, WAVES, WPR, STREAM, IMPLICIT, DMF>::bytes;
-  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (err != hipSuccess) return err;
-  const int total_teams = grid * TEAMS;
-  const int rpt = (n_rows + total_teams - 1) / total_teams;
-  prof_note(ev_slot, reinterpret_cast<const void*>(kern));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, s, a, rows, n_rows, rpt, slot0);
-  return hipGetLastError();
 }
 
 // Side streams for overlapping the bucket launches (they touch disjoint rows): forked from / joined to the
@@ -1178,7 +1077,7 @@ size_t bucket_slots(const QSchedule& q, int b, int k, bool implicit) {
   if (d.wpr <= 0) return 0;
   if (d.stream && ne_supported(k)) return (size_t)(q.ne_entries + q.ne_nsplit) + (size_t)(q.mf_n > 0 ? cg_mf_loss_slots(q.mf_n) : 0);
   const int rows = q.off[b + 1] - q.off[b];
-  if (b == kNB - 1 && rows > 0 && cgp_supported(k, implicit) && dense_mfma_enabled()) {
+  if (b == kNB - 1 && rows > 0 && cgp_supported(k, implicit)) {
     const int split = std::min(std::max(q.pair_first, q.off[b]), q.off[b + 1]);
     return (size_t)cgq_bucket_grid(split - q.off[b], b, cfg) * d.waves + (size_t)cgp_grid(q.off[b + 1] - split) * 4;
   }
@@ -1241,7 +1140,7 @@ hipError_t launch_all(const AlsArgs& a, const QSchedule& q, hipStream_t s, hipEv
           }                                                                                                 \
         } else if constexpr (D.stream && KP > 32) {   /* ranks above 32 always take the branch above */     \
           return hipErrorInvalidValue;                                                                      \
-        } else if (B == kNB - 1 && cgp_supported(a.k, IMPLICIT) && dense_mfma_enabled()) {                    \
+        } else if (B == kNB - 1 && cgp_supported(a.k, IMPLICIT)) {                    \
           /* the last bucket in two launches: rows of 17..32 non-zeros one per wave, the rest two per wave (wrmf_cgp.hip) */ \
           const int first = q.off[B], split = std::min(std::max(q.pair_first, first), q.off[B + 1]);         \
           const int n_main = split - first, n_pair = q.off[B + 1] - split;                                   \

@@ -75,15 +75,13 @@ __device__ __forceinline__ void chol_gather_chunk(const AlsArgs& a, int base, in
 
 // 3 waves per SIMD (168 VGPRs): three rows per CU overlap each other's serial phases; measured 0.160 s ->
 // 0.133 s per 1M users at k = 128 against 2 (a fourth changes nothing and spills)
-#ifndef RSP_CHOL_MINW
-#define RSP_CHOL_MINW 3
-#endif
+constexpr int kCholMinWaves = 3;
 // LONG: the launch for rows of more than kCholLongLen non-zeros (a.chol_long_rows, longest first).  A row of n
 // non-zeros summed one rank-one update after the other in fp32 drifts by ~n eps (8e-4 on the 5e5-non-zero item of
 // the 10M x 1M configuration); here the running block is folded into a second register block every kFold chunks, so
 // no partial sum sees more than 128 terms before it joins a sum of n/128 terms.  Twice the registers: 2 waves per SIMD.
 template <int KP, bool IMPLICIT, bool VEC, bool LONG>
-__global__ __launch_bounds__(256, LONG ? 2 : RSP_CHOL_MINW) void als_chol2_kernel(AlsArgs a, int loss_slot0) {
+__global__ __launch_bounds__(256, LONG ? 2 : kCholMinWaves) void als_chol2_kernel(AlsArgs a, int loss_slot0) {
   using SM = Chol2Smem<KP>;
   constexpr int BS = SM::BS, TC = SM::TC, LDT = SM::LDT, NB = 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];

@@ -28,7 +28,6 @@
 // Needs every confidence >= 1 (D^1/2) and XtX positive definite: both are decided on the device (flags[0] != 0 ->
 // this kernel returns at once and wrmf_chol.hip's kernel, which otherwise skips the short rows, takes them).
 #include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
 
@@ -71,12 +70,6 @@ __device__ __forceinline__ void lr_sfor(F&& f) {
   lr_sfor_impl(f, std::make_integer_sequence<int, N>{});
 }
 
-#ifndef RSP_LR_ABL
-#define RSP_LR_ABL 0   // dev builds: timing-only ablations (1 no V' GEMM, 2 no S GEMM, 4 no LDL^T, 8 no substitution, 16 no y = M q, 32 no gather)
-#endif
-#ifndef RSP_LRW_ABL
-#define RSP_LRW_ABL 0   // dev builds of the wave-per-pass kernel, timing only: 1 no V' GEMM, 2 no T GEMM, 4 no n x n solve, 8 no P GEMM
-#endif
 constexpr int kLrLd = 130;   // LDS row stride (floats) of V' (fp32)
 constexpr int kLrLh = 136;   // ... (halves) of the fp16 terms of X_nnz and of W: 16-byte aligned rows for the operand reads
 constexpr int kLrLs = 65;    // ... of the n x n system
@@ -293,23 +286,22 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
     // before the first LDS store (empty slots are stored as zeros).
     {
       float2 v[16];
-      const bool on = !(RSP_LR_ABL & 32);
 #pragma unroll
       for (int u = 0; u < 8; u++) {
         const int j = wv + 4 * u;
         const int id = __builtin_amdgcn_readlane(id_c, j);
-        v[u] = (on && ((vmask >> j) & 1) && 2 * lane < k) ? *reinterpret_cast<const float2*>(a.X + (size_t)id * k + 2 * lane) : float2{0.f, 0.f};
+        v[u] = (((vmask >> j) & 1) && 2 * lane < k) ? *reinterpret_cast<const float2*>(a.X + (size_t)id * k + 2 * lane) : float2{0.f, 0.f};
       }
       if (nrt == 2) {
 #pragma unroll
         for (int u = 8; u < 16; u++) {
           const int j = wv + 4 * u;
           const int id = __builtin_amdgcn_readlane(id_c, j);
-          v[u] = (on && ((vmask >> j) & 1) && 2 * lane < k) ? *reinterpret_cast<const float2*>(a.X + (size_t)id * k + 2 * lane) : float2{0.f, 0.f};
+          v[u] = (((vmask >> j) & 1) && 2 * lane < k) ? *reinterpret_cast<const float2*>(a.X + (size_t)id * k + 2 * lane) : float2{0.f, 0.f};
         }
       }
       if (wv == 0) {
-        const float c = on ? c_c : 1.f;
+        const float c = c_c;
         sC[lane] = valid ? c : 0.f;
         sQ[lane] = valid ? sqrtf(fmaxf(c - 1.f, 0.f)) : 0.f;
       }
@@ -333,7 +325,7 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
     // upper triangular, so the chunks beyond 2 wv + 1 are zero and skipped.  (The pointer is made opaque so that the loads
     // stay inside the row loop -- hoisted, they pin 64 registers for the whole launch.)
     float wmax = 0.f;   // max |W| of this wave's part (for the scale of the second product)
-    if (!(RSP_LR_ABL & 1)) {
+    {   // (a scope of its own: the register allocation of this kernel depends on where the fragments' lifetime ends)
       const _Float16* Mp = M16 + (size_t)(32 * wv + col) * KP + 8 * half;
       asm volatile("" : "+v"(Mp));
       f16x8 bh[8], bl[8];
@@ -371,7 +363,7 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
     __syncthreads();   // V' complete, every wave is done with the fp16 terms of X_nnz
     // 2b. the fp16 terms of W = D^1/2 V' * 2^ew over the X_nnz terms (thread t: slot t / 4, 32 columns)
     const int ew = lr_scale_exp(fmaxf(fmaxf(fmaxf(sT[0], sT[1]), fmaxf(sT[2], sT[3])), 1e-30f));
-    if (!(RSP_LR_ABL & 2)) {
+    {
       const int j = tid >> 2, part = tid & 3;
       if (j < 32 * nrt) {
         const float sw = lr_pow2(ew) * sQ[j];
@@ -424,7 +416,7 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
     __syncthreads();   // the terms of W are complete (and g, h above have been formed from V')
     {
       const int rt = wv == 0 ? 0 : 1, ct = wv == 2 ? 1 : 0;
-      const bool mine = !(RSP_LR_ABL & 2) && wv < (nrt == 1 ? 1 : 3) && (lsh == 6 || wv != 1);
+      const bool mine = wv < (nrt == 1 ? 1 : 3) && (lsh == 6 || wv != 1);
       f32x16 acc, acc2;
 #pragma unroll
       for (int e = 0; e < 16; e++) acc[e] = acc2[e] = 0.f;
@@ -457,7 +449,7 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
     // left of the diagonal, column values frozen at their pivot steps (row i of L times D) and, right of it, its own pivot row
     // (column i of L times d_i) -- both triangular solves read nothing but the lane's own registers and broadcasts.  The
     // forward substitution rides along with the elimination.  No barriers, no LDS traffic after the system is loaded.
-    if (!(RSP_LR_ABL & 4) && wv == ((blockIdx.x + (it / G)) & 3)) {
+    if (wv == ((blockIdx.x + (it / G)) & 3)) {
       int i = lane;
       asm volatile("" : "+v"(i));   // laundered per pass: hipcc otherwise hoists the 64 load addresses below out of the loop and spills them
       // one row of 33..64 non-zeros: the whole wave is one system
@@ -559,12 +551,10 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
         });
         sH[i] = live ? z * sQ[i] : 0.f;   // D^1/2 z (empty slots: sQ = 0)
       };
-      if (!(RSP_LR_ABL & 8)) {
-        if (lsh == 4) solve_packed(std::integral_constant<int, 16>{});
-        else if (lsh == 5) solve_packed(std::integral_constant<int, 32>{});
-        else if (rfl(n_c) <= 48) solve(std::integral_constant<int, 48>{});
-        else solve(std::integral_constant<int, NP>{});
-      }
+      if (lsh == 4) solve_packed(std::integral_constant<int, 16>{});
+      else if (lsh == 5) solve_packed(std::integral_constant<int, 32>{});
+      else if (rfl(n_c) <= 48) solve(std::integral_constant<int, 48>{});
+      else solve(std::integral_constant<int, NP>{});
     }
     __syncthreads();
     // 8. q_r = g_r - V'_r^T (D^1/2 z)_r
@@ -593,7 +583,7 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
       asm volatile("" : "+v"(Mtp));   // (opaque: these loads must not be hoisted out of the row loop either)
       float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
 #pragma unroll
-      for (int j0 = 0; j0 < ((RSP_LR_ABL & 16) ? 0 : 64); j0 += 32) {   // 32 independent L2 reads in flight per thread
+      for (int j0 = 0; j0 < 64; j0 += 32) {   // 32 independent L2 reads in flight per thread
         float m[32];
 #pragma unroll
         for (int e = 0; e < 32; e++) m[e] = Mtp[(size_t)(j0 + e) * KP];
@@ -813,22 +803,6 @@ __device__ __forceinline__ void lrw_solve(float (&rl)[NS], float u, const int i,
   }
 }
 
-#ifdef RSP_LRW_PROF
-// dev builds: s_memtime ticks per phase, summed over the waves of a class (read by rsparse_hip_dev_lrw_prof)
-__device__ unsigned long long g_lrw_prof[4][8];
-#define LRW_TICK(k, dep)                                  \
-  {                                                       \
-    __builtin_amdgcn_sched_barrier(0);                    \
-    asm volatile("s_nop 0" ::"v"(dep) : "memory");        \
-    const unsigned long long now_ = __builtin_readcyclecounter(); \
-    __builtin_amdgcn_sched_barrier(0);                    \
-    prof_t[k] += now_ - prof_last;                        \
-    prof_last = now_;                                     \
-  }
-#else
-#define LRW_TICK(k, dep)
-#endif
-
 // One instantiation per class of passes -- SL = slots per row (64, 32, 16), NS = columns of the system held (48 for the rows
 // of 33..48 non-zeros: the list is longest first, so they are a range of passes too) -- and one launch per class over its
 // passes [pass_lo, pass_hi): every launch's code fits the instruction cache (all four unrolled solves in one kernel were
@@ -899,10 +873,6 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
       c_c = a.vals[p1_c + nz];
     }
   }
-#ifdef RSP_LRW_PROF
-  unsigned long long prof_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long prof_last = __builtin_readcyclecounter();
-#endif
   for (; it < pass_hi; it += G) {
     int ln = lane;
     asm volatile("" : "+v"(ln));   // the lane id as this pass sees it (keeps lane-dependent addresses inside the pass)
@@ -949,10 +919,8 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
         lrw_ld16<64 * c8>(xr[1][c8][0], x1);
         lrw_ld16<64 * c8 + 16>(xr[1][c8][1], x1);
       });
-      LRW_TICK(0, ln);
       lrw_wait_all(xr[0]);
       lrw_wait_all(xr[1]);
-      LRW_TICK(1, xr[0][0][0].x);
       const _Float16* ap0 = sM + (size_t)n * LH + 8 * hf;
       lr_sfor<8>([&](auto cht) {
         constexpr int ch = 7 - decltype(cht)::value;
@@ -978,21 +946,15 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
           const _Float16* ap = ap0 + (size_t)(32 * ob) * LH + 16 * ch;
           const f16x8 ah = *reinterpret_cast<const f16x8*>(ap);
           const f16x8 al = *reinterpret_cast<const f16x8*>(ap + (size_t)KP * LH);
-          if constexpr (!(RSP_LRW_ABL & 1)) {
-            acc[ob][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[0], acc[ob][0], 0, 0, 0);
-            acc[ob][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[1], acc[ob][1], 0, 0, 0);
-            acc[ob][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[0], acc[ob][0], 0, 0, 0);
-            acc[ob][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[1], acc[ob][1], 0, 0, 0);
-            acc[ob][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[0], acc[ob][0], 0, 0, 0);
-            acc[ob][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[1], acc[ob][1], 0, 0, 0);
-          } else {   // (timing only)
-            acc[ob][0][0] += (float)ah[0] * (float)bh[0][0] + (float)al[1] * (float)bl[0][1];
-            acc[ob][1][0] += (float)ah[0] * (float)bh[1][0] + (float)al[1] * (float)bl[1][1];
-          }
+          acc[ob][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[0], acc[ob][0], 0, 0, 0);
+          acc[ob][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[1], acc[ob][1], 0, 0, 0);
+          acc[ob][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[0], acc[ob][0], 0, 0, 0);
+          acc[ob][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[1], acc[ob][1], 0, 0, 0);
+          acc[ob][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[0], acc[ob][0], 0, 0, 0);
+          acc[ob][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[1], acc[ob][1], 0, 0, 0);
         });
       });
     }
-    LRW_TICK(2, acc[0][0][0] + acc[3][1][0]);
     // ---- 2. the fp16 terms of V'^T * 2^ew (th / tl[ob][st][g]: the 16 factor dimensions of chunk 2 ob + g, in the order the
     // accumulator holds them) ----
     float wm = 0.f;
@@ -1033,22 +995,18 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
 #pragma unroll
         for (int g = 0; g < 2; g++) {
           const f16x8 a0h = th[ob][0][g], a0l = tl[ob][0][g], a1h = th[ob][1][g], a1l = tl[ob][1][g];
-          if constexpr (!(RSP_LRW_ABL & 2)) {
-            t[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, a0h, t[0][0], 0, 0, 0);
-            if constexpr (SL == 64) t[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, a0h, t[1][0], 0, 0, 0);
-            if constexpr (SL == 64) t[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, a1h, t[0][1], 0, 0, 0);
-            t[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, a1h, t[1][1], 0, 0, 0);
-            t[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, a0l, t[0][0], 0, 0, 0);
-            if constexpr (SL == 64) t[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, a0l, t[1][0], 0, 0, 0);
-            if constexpr (SL == 64) t[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, a1l, t[0][1], 0, 0, 0);
-            t[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, a1l, t[1][1], 0, 0, 0);
-            t[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0l, a0h, t[0][0], 0, 0, 0);
-            if constexpr (SL == 64) t[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1l, a0h, t[1][0], 0, 0, 0);
-            if constexpr (SL == 64) t[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0l, a1h, t[0][1], 0, 0, 0);
-            t[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1l, a1h, t[1][1], 0, 0, 0);
-          } else {
-            t[0][0][0] += (float)a0h[0]; t[1][0][0] += (float)a0l[0]; t[0][1][0] += (float)a1h[0]; t[1][1][0] += (float)a1l[0];
-          }
+          t[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, a0h, t[0][0], 0, 0, 0);
+          if constexpr (SL == 64) t[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, a0h, t[1][0], 0, 0, 0);
+          if constexpr (SL == 64) t[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, a1h, t[0][1], 0, 0, 0);
+          t[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, a1h, t[1][1], 0, 0, 0);
+          t[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, a0l, t[0][0], 0, 0, 0);
+          if constexpr (SL == 64) t[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, a0l, t[1][0], 0, 0, 0);
+          if constexpr (SL == 64) t[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0h, a1l, t[0][1], 0, 0, 0);
+          t[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1h, a1l, t[1][1], 0, 0, 0);
+          t[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0l, a0h, t[0][0], 0, 0, 0);
+          if constexpr (SL == 64) t[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1l, a0h, t[1][0], 0, 0, 0);
+          if constexpr (SL == 64) t[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0l, a1h, t[0][1], 0, 0, 0);
+          t[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1l, a1h, t[1][1], 0, 0, 0);
         }
       // (the columns of the lane's own group only: rl[t] = T[slot][base + t], base = slot - slot % SL)
       auto swp = [&](const int ta, const int v, float& c_lo, float& c_hi) {   // columns 32 ta + rho(v, 0) and + rho(v, 1)
@@ -1093,7 +1051,6 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
         }
       }
     }
-    LRW_TICK(3, rl[0] + rl[NS - 1]);
     // ---- 4. lane i = slot i: S z = h in registers, e, the loss terms ----
     const float sqs = sq * c2;   // (D^1/2 T D^1/2)_ic = r[c] sqs_i sqs_c
     float e_i = 0.f, p_i = 0.f;   // p = x_j . y
@@ -1121,11 +1078,7 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
       tc = -(tc * c2) * c2;   // (T c)_i
       float u = unit ? tc : tc * sq;   // h_i
       float z = 0.f;
-      if constexpr (RSP_LRW_ABL & 4) {
-        z = u + rl[0] + rl[NS - 1];
-      } else {
-        lrw_solve<SL, NS>(rl, u, i, unit, 1.f, z, p_i);
-      }
+      lrw_solve<SL, NS>(rl, u, i, unit, 1.f, z, p_i);
       e_i = cval - sq * z;   // (slots beyond the row: c = 0, sq = 0; unit slots: z = 0)
       // x_i . y = (T e)_i, and D^1/2 T e = D^1/2 T c - D^1/2 T D^1/2 z = h - (S - I) z = z
       if (!unit) p_i = z * __builtin_amdgcn_rcpf(fmaxf(sq, 1e-30f));
@@ -1134,7 +1087,6 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
     //  hipcc waits for loop-carried loads with vmcnt(0) at their first use, which at the top of the next pass would be a wait for
     //  those stores)
     asm volatile("" : "+v"(id_nx), "+v"(c_nx), "+v"(p1_nn), "+v"(n_nn), "+v"(rid_n3));
-    LRW_TICK(4, e_i + p_i);
     wave_sync();   // (the previous pass has read its e)
     sE[ln] = e_i;
     wave_sync();
@@ -1159,17 +1111,12 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
           const _Float16* bp = bp0 + (size_t)(32 * cb) * LH + 16 * chunk;
           const f16x8 bh = *reinterpret_cast<const f16x8*>(bp);
           const f16x8 bl = *reinterpret_cast<const f16x8*>(bp + (size_t)KP * LH);
-          if constexpr (!(RSP_LRW_ABL & 8)) {
-            p0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(th[ob][0][g], bh, p0, 0, 0, 0);
-            p1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(th[ob][1][g], bh, p1, 0, 0, 0);
-            p0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(th[ob][0][g], bl, p0, 0, 0, 0);
-            p1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(th[ob][1][g], bl, p1, 0, 0, 0);
-            p0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl[ob][0][g], bh, p0, 0, 0, 0);
-            p1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl[ob][1][g], bh, p1, 0, 0, 0);
-          } else {
-            p0[0] += (float)th[ob][0][g][0] * (float)bh[0] + (float)tl[ob][0][g][0] * (float)bl[0];
-            p1[0] += (float)th[ob][1][g][0] * (float)bh[1] + (float)tl[ob][1][g][0] * (float)bl[1];
-          }
+          p0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(th[ob][0][g], bh, p0, 0, 0, 0);
+          p1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(th[ob][1][g], bh, p1, 0, 0, 0);
+          p0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(th[ob][0][g], bl, p0, 0, 0, 0);
+          p1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(th[ob][1][g], bl, p1, 0, 0, 0);
+          p0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl[ob][0][g], bh, p0, 0, 0, 0);
+          p1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(tl[ob][1][g], bh, p1, 0, 0, 0);
         });
         // sums over the slots of this lane half, by 16-slot group: q[2 st + (a >> 1)], a = 8-row block of the tile
         float q[4];
@@ -1204,7 +1151,6 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
         }
       });
     }
-    LRW_TICK(5, yy);
     const float dlt = 1.f - p_i;
     const float loss_i = cval * dlt * dlt;
     const float lsum = wave_sum(loss_i), ysum = wave_sum(yy);
@@ -1213,17 +1159,7 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
     rid_n = rid_nn; p1_n = p1_nn; n_n = n_nn;
     rid_nn = rid_n3;
     id_c = id_nx; c_c = c_nx;
-    LRW_TICK(6, (float)(id_c + rid_c) + c_c);
-#ifdef RSP_LRW_PROF
-    prof_t[7] += 1;
-#endif
   }
-#ifdef RSP_LRW_PROF
-  if (lane == 0) {
-    constexpr int cls = SL == 64 ? (NS == 64 ? 0 : 1) : (SL == 32 ? 2 : 3);
-    for (int q = 0; q < 8; q++) atomicAdd(&g_lrw_prof[cls][q], prof_t[q]);
-  }
-#endif
   if (lane == 0) sRed[wv] = wloss;
   __syncthreads();
   if (tid == 0) {
@@ -1528,19 +1464,6 @@ __global__ __launch_bounds__(512) void als_chol_lrx_kernel(AlsArgs a, const int3
 
 }  // namespace
 
-// dev builds (-DRSP_AB): RSPARSE_HIP_LR_WAVE=0 keeps rank 128 on the workgroup kernel, for same-box comparisons
-static bool lr_wave_on() {
-#ifdef RSP_AB
-  static const bool on = [] {
-    const char* e = std::getenv("RSPARSE_HIP_LR_WAVE");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-#else
-  return true;
-#endif
-}
-
 bool chol_lr_supported(const AlsArgs& a, bool implicit) {
   return implicit && a.k > 96 && a.k <= 128 && a.k % 2 == 0 && !a.rhs_vals && !a.loss_tgt && !a.rhs_init &&
          (reinterpret_cast<uintptr_t>(a.X) & 7) == 0;
@@ -1570,7 +1493,7 @@ hipError_t launch_als_chol_lr(const AlsArgs& a, const int32_t* rows, int n_rows,
                                  prep_lds)) != hipSuccess)
     return err;
   _Float16* MT16 = reinterpret_cast<_Float16*>(Mt + 128 * 128);   // (the scratch is 3 x 128 x 128 floats)
-  const bool wave_form = lr_wave_on() && a.k == KP;
+  const bool wave_form = a.k == KP;
   hipLaunchKernelGGL(prep, dim3(1), dim3(256), prep_lds, s, a.XtX, a.k, reinterpret_cast<_Float16*>(M), Mt, flags,
                      wave_form ? MT16 : nullptr);
   if ((err = hipGetLastError()) != hipSuccess) return err;
@@ -1661,15 +1584,3 @@ hipError_t launch_als_chol_lrx(const AlsArgs& a, const int32_t* rows, int n_rows
 
 }  // namespace rsparse_hip
 
-#ifdef RSP_LRW_PROF
-// dev builds: out[4][8] = per class (49..64, 33..48, 17..32, <= 16 non-zeros) the s_memtime ticks of the phases (issue of the
-// gather, wait for it, split + V' GEMM, terms + T GEMM + lane swaps, n x n solve, P GEMM + y, bookkeeping) and the passes
-extern "C" int rsparse_hip_dev_lrw_prof(unsigned long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rsparse_hip::g_lrw_prof), sizeof(unsigned long long) * 32) != hipSuccess) return 1;
-  if (reset) {
-    unsigned long long z[32] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(rsparse_hip::g_lrw_prof), z, sizeof(z)) != hipSuccess) return 1;
-  }
-  return 0;
-}
-#endif

@@ -35,7 +35,6 @@
 //     asm statement: every matrix instruction opens with s_nop 1 (a VALU-written operand), every read of the accumulator
 //     file sits behind an explicit s_nop block (a 16-pass result), see MF_DRAIN.
 // A non-positive pivot sends the row to the general solver (wrmf_lu.hip), exactly as the other exact kernels do.
-#include <cstdio>
 #include <utility>
 
 #pragma clang diagnostic ignored "-Winline-asm"   // (the named accumulator registers are "reserved": that is the point)
@@ -154,12 +153,6 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
   }
 
   if (lane == 0) sm.loss = 0.0;
-#ifdef RSP_MF_PROF   // dev builds (tools/gpu_mf_prof.sh): s_memtime ticks per phase, summed over the waves into a.ne_prof[8 ..]
-  unsigned long long pt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pt0 = __builtin_amdgcn_s_memtime();
-#define MF_TICK(i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); pt[i] += t_ - pt0; pt0 = t_; }
-#else
-#define MF_TICK(i)
-#endif
   // operand scales: powers of two from max |X| and max c (launch_ne_stats), as in wrmf_chol_wave.hip.  (Through
   // readfirstlane: loaded values are vector registers to hipcc, and a dozen uniform constants held in vector registers
   // through every phase are a dozen registers the assembly loop then spills its operands for.)
@@ -185,11 +178,9 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
     const int lc0 = min(ln, k - 1), lc1 = min(ln + 64, k - 1);
 
     // ---------------- assembly on the matrix cores ----------------
-    MF_TICK(7)
     MF_DRAIN();   // (the previous row's last matrix instructions)
     mf_sfor<160>([&](auto rt) { mf_wr<decltype(rt)::value>(0.f); });
     float u0 = 0.f, u1 = 0.f;   // rhs, lane = coordinate (ln, 64 + ln)
-    MF_TICK(0)
     {
       // A step = 16 non-zeros.  Its vectors are requested at the top of the loop body (asm loads: one coordinate per lane
       // and register, no wait), the matrix instructions of the PREVIOUS step run while they fly, then ONE wait, the
@@ -324,7 +315,6 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
     // the padded coordinates were zero), per lane = row with the columns at uniform offsets: no clamps, no selects (a
     // selected load is sunk under its condition, one round trip per entry)
     const float unscale = (un1 * un1) * unw;   // (powers of two: exact)
-    MF_TICK(1)
     MF_DRAIN();
     mf_sfor<4>([&](auto it2) {
       constexpr int I = decltype(it2)::value;
@@ -356,13 +346,8 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
     wave_sync();
 
     // ---------------- blocked Cholesky, 16 panels of 8 columns ----------------
-    MF_TICK(2)
     bool bad = false;
-#ifdef RSP_MF_ABL   // timing-only dev builds: the assembly alone (bit 0: no factorisation, bit 1: no backward pass, bit 2: no loss pass)
-    for (int p = 0; p < ((RSP_MF_ABL & 1) ? 0 : 16); p++) {
-#else
     for (int p = 0; p < 16; p++) {
-#endif
       const int K = p >> 2, q = p & 3;
       const int nsl = 4 - K;          // tiles (K + s, K), s < nsl
       const int thr = 8 * (q + 1);    // rows of tile (K, K) below the panel's diagonal block: n >= thr
@@ -487,14 +472,9 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
     }
 
     // ---------------- backward: L^T y = u, last panel first; y replaces u in sm.U ----------------
-    MF_TICK(3)
     MF_DRAIN();
     wave_sync();
-#ifdef RSP_MF_ABL
-    for (int p = ((RSP_MF_ABL & 2) ? -1 : 15); p >= 0; p--) {
-#else
     for (int p = 15; p >= 0; p--) {
-#endif
       const int K = p >> 2, q = p & 3;
       const int nsl = 4 - K;
       const int thr = 8 * (q + 1);
@@ -558,7 +538,6 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
       wave_sync();
     }
 
-    MF_TICK(4)
     if (bad) {   // wave-uniform: the general solver re-solves the row and owns its loss term (wrmf_lu.hip)
       int pos = 0;
       if (lane == 0) pos = atomicAdd(a.fail_counter, 1);
@@ -577,11 +556,7 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
 
     // ---------------- loss row term: lane j takes non-zero j of a chunk, y from LDS ----------------
     float lacc = 0.f;
-#ifdef RSP_MF_ABL
-    for (int base = p1; base < ((RSP_MF_ABL & 4) ? p1 : p2); base += 64) {
-#else
     for (int base = p1; base < p2; base += 64) {
-#endif
       const int ccnt = min(64, p2 - base);
       const int jl = min(lane, ccnt - 1);
       const float* xr = a.X + (size_t)a.row_idx[base + jl] * k;
@@ -624,15 +599,10 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
     }
     const float lpart = wave_sum(lacc);
     const float xxp = wave_sum(z0 * z0 + z1 * z1);
-    MF_TICK(5)
     if (lane == 0) sm.loss += IMPLICIT ? (double)lpart + a.lambda_loss * (double)xxp : (double)(lpart + lam_use * xxp);
     wave_sync();
   }
   if (lane == 0) a.loss_partials[loss_slot0 + blockIdx.x] = sm.loss;
-#ifdef RSP_MF_PROF
-  if (lane == 0 && a.ne_prof)
-    for (int i = 0; i < 8; i++) atomicAdd(a.ne_prof + 8 + i, pt[i]);
-#endif
 }
 
 }  // namespace
@@ -666,16 +636,6 @@ hipError_t launch_als_chol_mf(const AlsArgs& a, bool implicit, const int32_t* ro
   if (n_rows <= 0) return hipSuccess;
   if (!a.wave_stats || !chol_mf_supported(a.k)) return hipErrorInvalidValue;
   const int grid = chol_mf_grid(n_rows);
-#ifdef RSP_MF_PROF
-  {
-    int nb = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rsparse_hip_als_chol_mf_implicit, 64, 0);
-    hipFuncAttributes fa{};
-    (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(rsparse_hip_als_chol_mf_implicit));
-    std::fprintf(stderr, "[mf_prof] occupancy %d workgroups of one wave per CU; %d registers, %zu bytes of LDS, %zu of scratch\n", nb,
-                 fa.numRegs, fa.sharedSizeBytes, fa.localSizeBytes);
-  }
-#endif
   const bool full = a.k == 128 && (reinterpret_cast<uintptr_t>(a.X) & 15) == 0;   // (the full kernels read 16 bytes at a time in their loss pass)
   if (implicit) {
     // (both: the device-side flag decides; the symmetric one is the normal case and is named for the profile)

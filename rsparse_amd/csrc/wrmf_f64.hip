@@ -33,7 +33,6 @@
 // per row (a wave per chunk of a long row), the operator applied from the gathered vectors as the reference does (no k1 x k1
 // matrix).  Everything else goes through the workgroup-per-row family.
 #include <algorithm>
-#include <cstdlib>
 
 #include <type_traits>
 #include <utility>
@@ -183,18 +182,8 @@ __device__ __forceinline__ void rank_update_mfma(double* A, int lda, int kp, con
   }
 }
 
-// (dev build -DRSP_F64_PROF, tools/gpu_f64_phases.sh: s_memtime ticks of workgroup 0 per phase of a row, printed at the end)
-#ifdef RSP_F64_PROF
-#define F64_T(j) { const unsigned long long _t1 = __builtin_amdgcn_s_memtime(); prof_t[j] += _t1 - _tl; _tl = _t1; }
-#else
-#define F64_T(j)
-#endif
-
-#ifndef RSP_F64_W64   // waves per SIMD asked of the one-wave instantiation (ranks <= 32): see the measurement at the launch
-#define RSP_F64_W64 2
-#endif
 template <int NT>
-__global__ __launch_bounds__(NT, NT == 64 ? RSP_F64_W64 : 2) void f64_als_kernel(F64Args a, int KP, int CH, int m2_in_lds) {   // (two waves per SIMD: two workgroups of 256 at rank 33..64, one of 512 beyond)
+__global__ __launch_bounds__(NT, 2) void f64_als_kernel(F64Args a, int KP, int CH, int m2_in_lds) {   // (two waves per SIMD: two workgroups of 256 at rank 33..64, one of 512 beyond)
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   double* sm = reinterpret_cast<double*>(smem_raw);
   constexpr int NW = NT / 64;
@@ -228,11 +217,6 @@ __global__ __launch_bounds__(NT, NT == 64 ? RSP_F64_W64 : 2) void f64_als_kernel
   const int CG = NT / RT, ri = tid & (RT - 1), cgi = tid / RT;
 
   double wloss = 0.0;   // thread 0: loss terms of this workgroup's rows, in row order
-#ifdef RSP_F64_PROF
-  unsigned long long prof_t[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long _tl = __builtin_amdgcn_s_memtime();
-  int prof_rows = 0;
-#endif
 
   auto stage = [&](const int p1, const int c0, const int cn) {
     if (tid < cn) {
@@ -295,7 +279,6 @@ __global__ __launch_bounds__(NT, NT == 64 ? RSP_F64_W64 : 2) void f64_als_kernel
     // the row's system into the LDS: lower triangle of A (+ whole diagonal tiles), rhs, sv
     auto assemble = [&]() {
       __syncthreads();   // the previous readers are done with the LDS
-      F64_T(7)
       for (int i0 = 0; i0 < LDA; i0 += 64) {   // XtX (or zeros): eight columns per wave and trip, their loads in flight together
         const int i = i0 + lane;
         for (int c0 = wv * 8; c0 < KP; c0 += NW * 8) {
@@ -313,13 +296,10 @@ __global__ __launch_bounds__(NT, NT == 64 ? RSP_F64_W64 : 2) void f64_als_kernel
         x[t] = t < k1 ? yrow[a.ioff + t] : 0.0;   // warm start (CG, NNLS): Y.col(i), drop_row(init, !is_x_bias_last_row)
       }
       __syncthreads();
-      F64_T(0)
       for (int c0 = 0; c0 < n; c0 += CH) {
         const int cn = min(CH, n - c0);
         stage(p1, c0, cn);
-        F64_T(12)
         rank_update_mfma<NT>(A, LDA, KP, xs, cw, cn);
-        F64_T(13)
         for (int t = tid; t < k1; t += NT) {
           double s1 = 0.0, s2 = 0.0;
           for (int j = 0; j < cn; j++) {
@@ -331,9 +311,7 @@ __global__ __launch_bounds__(NT, NT == 64 ? RSP_F64_W64 : 2) void f64_als_kernel
           sv[t] += s2;
         }
         __syncthreads();
-        F64_T(14)
       }
-      F64_T(1)
       if (!a.implicit)
         for (int t = tid; t < k1; t += NT) A[t + (size_t)t * LDA] += lam_use;   // lhs.diag() += lambda_use
       __syncthreads();
@@ -348,7 +326,6 @@ __global__ __launch_bounds__(NT, NT == 64 ? RSP_F64_W64 : 2) void f64_als_kernel
     assemble();
     if (cg || nnls) mirror();
 
-    F64_T(2)
     if (cg) {
       // ---- conjugate gradient on the assembled system (wrmf_implicit.hpp:8-57, wrmf_explicit.hpp:8-31) ----
       double part = 0.0;
@@ -508,7 +485,6 @@ __global__ __launch_bounds__(NT, NT == 64 ? RSP_F64_W64 : 2) void f64_als_kernel
             z[c] = zc * di;
           }
           if (tid == 0) spiv[1] = bad ? 1 : 0;   // (every wave that factors sees the same tile; the others read the verdict)
-          F64_T(8)
           if (!bad)
             for (int i = j2 + tid; i < k1; i += NT) {   // the panel: row i of L against the tile, in registers
               double lr[NB], av[NB];
@@ -528,7 +504,6 @@ __global__ __launch_bounds__(NT, NT == 64 ? RSP_F64_W64 : 2) void f64_als_kernel
             }
         }
         __syncthreads();   // the panel is in place (and nobody reads the diagonal tile any more)
-        F64_T(9)
         if (spiv[1]) return false;
         if (tid == 0) {   // the tile's factor
 #pragma unroll
@@ -588,16 +563,13 @@ __global__ __launch_bounds__(NT, NT == 64 ? RSP_F64_W64 : 2) void f64_als_kernel
             }
           }
         }
-        F64_T(10)
         return true;
       };
       for (int jb = 0; jb < k1 && ok; jb += NB) {
         __syncthreads();   // the previous block's trailing update has landed
-        F64_T(11)
         ok = k1 - jb >= NB ? block(std::true_type{}, jb) : block(std::false_type{}, jb);
       }
       __syncthreads();
-      F64_T(3)
       if (ok) {
         if (wv == 0) {   // L^T y = z: lane l holds entries l and l + 64
           double z0 = lane < k1 ? x[lane] : 0.0, z1 = lane + 64 < k1 ? x[lane + 64] : 0.0;
@@ -715,7 +687,6 @@ __global__ __launch_bounds__(NT, NT == 64 ? RSP_F64_W64 : 2) void f64_als_kernel
       }
     }
 
-    F64_T(4)
     // ---- write back, loss term (wrmf_implicit.hpp:254-270, wrmf_explicit.hpp:113-132) ----
     for (int t = tid; t < k1; t += NT) yrow[a.ooff + t] = x[t];
     // (the row's vectors once more, straight from memory: a wave takes four non-zeros per trip, no staging, no barrier)
@@ -749,17 +720,7 @@ __global__ __launch_bounds__(NT, NT == 64 ? RSP_F64_W64 : 2) void f64_als_kernel
     for (int t = tid; t < k1; t += NT) yy += x[t] * x[t];
     const double tot = block_sum<NT>((lane == 0 ? lpart : 0.0) + lam_use * yy, red);
     if (tid == 0) wloss += tot;
-    F64_T(5)
-#ifdef RSP_F64_PROF
-    prof_rows++;
-#endif
   }
-#ifdef RSP_F64_PROF
-  if (blockIdx.x == 0 && tid == 0)
-    printf("f64_als_kernel phases (ticks of s_memtime, workgroup 0, %d rows): copy %llu assembly %llu [stage %llu update %llu rhs %llu] mirror %llu solve %llu [tile %llu panel %llu trailing %llu barrier %llu] backsub %llu loss %llu between %llu\n",
-           prof_rows, prof_t[0], prof_t[1] + prof_t[12] + prof_t[13] + prof_t[14], prof_t[12], prof_t[13], prof_t[14], prof_t[2],
-           prof_t[3] + prof_t[8] + prof_t[9] + prof_t[10] + prof_t[11], prof_t[8], prof_t[9], prof_t[10], prof_t[11], prof_t[4], prof_t[5], prof_t[7]);
-#endif
   if (tid == 0) a.loss_partials[blockIdx.x] = wloss;
 }
 
@@ -1492,12 +1453,6 @@ F64Geo f64_geometry(int k1, int solver) {
   }
   // small systems: no need for the whole LDS (more workgroups per CU instead)
   if (g.KP <= 32) ch = std::min(ch, 32);
-#ifdef RSP_AB   // (dev builds: the shipped library reads no environment variable)
-  if (const char* e = std::getenv("RSPARSE_HIP_F64_CHUNK")) {   // dev: pin the chunk of staged vectors (occupancy experiments)
-    const int c = std::atoi(e);
-    if (c >= 4 && c <= 64 && (c & (c - 1)) == 0 && bytes(mats, c) <= kF64LdsBudget) ch = c;
-  }
-#endif
   g.CH = ch;
   g.lds = bytes(mats, ch);
   return g;

@@ -46,11 +46,10 @@ struct DevCSC {
   int32_t* q_ne_split_rows = nullptr;   // lists of the COLLECT launch (one workgroup per split row)
   int32_t* q_ne_split_ptr = nullptr;
   int q_ne_nsplit = 0;
-  // the same lists for solver == CHOLESKY, whose normal-equation launch takes the rows beyond q_nec_min non-zeros (a
-  // longer prefix of q_order, dealt with the larger fixed cost of the exact solve); they alias the lists above when the
-  // two thresholds coincide
-  int q_nec_min = 0;
-  int q_n_nec = 0;      // rows of more than q_nec_min non-zeros (a prefix of q_order)
+  // the same lists for the rows beyond kCgMfMax non-zeros (a shorter prefix of q_order): the normal-equation launch beside
+  // wrmf_cg_mf.hip, and solver == CHOLESKY's when wrmf_chol_mf.hip does not run; they alias the lists above when the two
+  // prefixes coincide
+  int q_n_nec = 0;      // rows of more than kCgMfMax non-zeros (a prefix of q_order)
   bool q_nec_own = false;
   int32_t* q_nec_rows = nullptr;
   int32_t* q_nec_ptr = nullptr;
@@ -142,7 +141,6 @@ struct AlsArgs {
   const unsigned* ne_stats;      // implicit NE launches: {bits of max |x|, bits of max c, any c < 1} (launch_ne_stats), or nullptr
   const float* mf_XtX;           // wrmf_chol_mf.hip, implicit feedback: XtX padded to 128 x 128 (identity beyond the rank); = XtX at rank 128
   const unsigned* wave_stats;    // the same block for the wave-per-row kernels at rank 33..64 (operand scales of their matrix-core assembly), or nullptr
-  unsigned long long* ne_prof;   // RSP_NE_PROF builds: [workgroup][wave][8] cycle counters of wrmf_ne.hip (else nullptr)
 };
 
 struct QSchedule {
@@ -178,7 +176,6 @@ hipError_t launch_als_cgp(const AlsArgs& a, const int32_t* rows, int n_rows, siz
 // long rows (bucket 0) by one-pass normal equations on the matrix cores (wrmf_ne.hip) instead of the streamed CG kernel
 bool ne_supported(int k);
 constexpr int kNeMinLen = 512;       // its rows: more non-zeros than the largest resident bucket of wrmf_cgq.hip holds
-constexpr int kNeCholMinLen = 64;   // (rounds 2-5: solver == CHOLESKY's threshold of the same launch; dev builds: RSPARSE_HIP_NE_CHOL_MIN)
 constexpr int kNeMaxSeg = 16;        // segments per split row
 constexpr int kNeMaxSegTotal = 1024;   // ... per list set (186 MB of partial accumulators at most)
 constexpr int kNeSegFloats = 4 * (11 * 16 * 64 + 128 + 2);   // per segment: 4 waves x (<= 11 accumulator tiles + b + sum c)

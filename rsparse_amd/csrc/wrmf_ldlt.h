@@ -24,12 +24,6 @@
 
 #include "wrmf_device.h"
 
-#ifdef LDLT_PROF   // tools/probes/ldlt_probe.hip: ticks per phase and wave
-#define LDLT_T(j) { const unsigned long long t1_ = __builtin_amdgcn_s_memtime(); ldlt_prof[j] += t1_ - ldlt_tl; ldlt_tl = t1_; }
-#else
-#define LDLT_T(j)
-#endif
-
 namespace rsparse_hip {
 namespace dev {
 
@@ -248,14 +242,7 @@ struct Ldlt {
   // tiles complete), sU: right-hand side -> solution, sCh: FLOATS of scratch that MAY overlap sA (the tiles are dead after
   // the first barrier in here).  Called by all four waves; the caller has synchronised the tiles and sU.
   static __device__ __forceinline__ bool solve(const float* sA, float* sCh, float* sU, int* sFlag, const int wv,
-                                               const int lane
-#ifdef LDLT_PROF
-                                               , unsigned long long* ldlt_prof
-#endif
-  ) {
-#ifdef LDLT_PROF
-    unsigned long long ldlt_tl = __builtin_amdgcn_s_memtime();
-#endif
+                                               const int lane) {
     float c[NOWN][BC][RH];
     sfor<NOWN>([&](auto st) {
       constexpr int s = decltype(st)::value;
@@ -272,9 +259,7 @@ struct Ldlt {
     int* sRdy = sFlag + 1;    // half panels published (2 J + 2 = panel J complete)
     int* sDone = sFlag + 2;   // [4] panels a wave has applied to all of its blocks
     if (wv == 0 && lane < 6) sFlag[lane] = 0;
-    LDLT_T(0)
     __syncthreads();
-    LDLT_T(1)
     // Forward pass as a data flow, no barriers: panel J goes to buffer J % NBUF and is announced in sRdy, half by half; a
     // wave applies the panels in order.  The owner of block J + 1 applies panel J to that block only -- its first half while
     // block J's owner is still busy with the second --, factors it, announces it, and catches up on its other blocks
@@ -298,7 +283,6 @@ struct Ldlt {
 #pragma unroll
           for (int w2 = 0; w2 < 4; w2++) lds_wait_ge(sDone + w2, J - NBUF + 1);
         }
-        LDLT_T(6)
         __builtin_amdgcn_s_setprio(3);
         sfor<NOWN>([&](auto st) {
           constexpr int s = decltype(st)::value;
@@ -306,12 +290,10 @@ struct Ldlt {
         });
         __builtin_amdgcn_s_setprio(0);
         if (bad) *sFlag = 1;
-        LDLT_T(3)
         if (deferred >= 0) {
           apply(deferred, J);
           deferred = -1;
         }
-        LDLT_T(4)
       }
       if (J + 1 == NBLK) break;
       if (wv == owner(J + 1)) {
@@ -320,25 +302,18 @@ struct Ldlt {
           constexpr int s = decltype(st)::value;
           if (((J + 1) >> 2) == s) {
             lds_wait_ge(sRdy, 2 * J + 1);
-            LDLT_T(6)
             update_half<nh(s), 0>(c[s], J + 1, J % NBUF, sCh, lane);
-            LDLT_T(2)
             lds_wait_ge(sRdy, 2 * J + 2);
-            LDLT_T(6)
             update_half<nh(s), 1>(c[s], J + 1, J % NBUF, sCh, lane);
-            LDLT_T(2)
           }
         });
         deferred = J;
       } else {
         lds_wait_ge(sRdy, 2 * J + 2);
-        LDLT_T(6)
         apply(J, J);
-        LDLT_T(4)
       }
     }
     __syncthreads();
-    LDLT_T(6)
     for (int J = NBLK - 1; J >= 0; J--) {
       if (wv == owner(J)) {
         __builtin_amdgcn_s_setprio(3);
@@ -348,9 +323,7 @@ struct Ldlt {
         });
         __builtin_amdgcn_s_setprio(0);
       }
-      LDLT_T(7)
       __syncthreads();
-      LDLT_T(8)
     }
     return *sFlag != 0;
   }

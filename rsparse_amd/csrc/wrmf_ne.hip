@@ -48,9 +48,6 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef RSP_ABL
-#define RSP_ABL 0   // dev builds only: ablations of the accumulate step (1 = no MFMA, 2 = no split, 4 = no look-ahead copies)
-#endif
 constexpr float kCgTolNe = 1e-10f;  // CG_TOL, inst/include/wrmf.hpp:22
 constexpr int kStepNnz = 16;        // K of v_mfma_f32_32x32x16_bf16
 
@@ -593,17 +590,6 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
   int cslot = 0;  // ring slot of the next step this wave consumes
   int buf = 0;
   int nbuf = 0;   // solved rows waiting in sY
-#ifdef RSP_NE_PROF
-  unsigned long long prof_t[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  const unsigned long long prof_start = __builtin_amdgcn_s_memtime();
-  unsigned long long _tl = prof_start;
-#define NE_T(j) { const unsigned long long _t1 = __builtin_amdgcn_s_memtime(); prof_t[j] += _t1 - _tl; _tl = _t1; }
-#else
-#define NE_T(j)
-#endif
-#ifndef RSP_NECH_ABL
-#define RSP_NECH_ABL 0
-#endif
 
   for (int li = list_begin; li < list_end; li++) {
     const NeEntry en = decode(li);
@@ -616,7 +602,6 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
     // It is older than every vector group this row issues, so it has landed once a step issued in this row has been
     // waited for, i.e. after D - 1 steps of wave 0's group; shorter rows drain explicitly below
     if (wv == 0) dma16(a.Y + (size_t)row * k + min((lane & 31) * 4, k - 4), rfl((int)lds_addr(sX0)));
-    NE_T(7)
 
     // accumulators: NSLOT tiles; what a slot holds depends on the wave's role (NeRoles::slot)
     f32x16 acc[NSLOT];
@@ -660,11 +645,8 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
       auto sync_step = [&](const int i) {
         const bool has = i < nst;   // PAIR mode: a group with one step fewer than group 0 still meets the barrier
         if (has) wait_vm<(D - 2) * G_::group_of(ROLE)>();  // this wave's share of the step has landed; D-2 later ones in flight
-        NE_T(0)
         if constexpr (NROLES > 1) __builtin_amdgcn_s_barrier();  // ... and the partners' shares; the previous slot is released
-        NE_T(1)
         if (has) prepare_read();   // the addresses are formed inside the step, behind its first MFMAs
-        NE_T(2)
         return has;
       };
       // MFMAs on `cur` (step i-1) interleaved with the split of step i into `nxt`; masked = partial step or rank < KP
@@ -769,29 +751,21 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
         static_for<NMFMA>([&](auto jc) {
           constexpr int J = decltype(jc)::value;
           pin(jc);
-#if !(RSP_ABL & 1)
           mfma_j(jc, cur);
-#endif
           // (before the first look-ahead piece, which goes behind MFMA NMFMA / (GROUP + 1))
           if constexpr (J == (BARE - 1 < NMFMA / (G_::GROUP + 1) ? BARE - 1 : NMFMA / (G_::GROUP + 1)))
             prepare(std::integral_constant<int, ROLE>{});
-#if !(RSP_ABL & 2)
           if constexpr (J >= BARE && J - BARE < NHU) half_unit(std::integral_constant<int, J - BARE>{});
-#endif
           // piece n of the look-ahead copy behind MFMA (n + 1) NMFMA / (GROUP + 1)
           static_for<G_::GROUP>([&](auto nc) {
-#if !(RSP_ABL & 4)
             if constexpr (J == (decltype(nc)::value + 1) * NMFMA / (G_::GROUP + 1))
               piece(std::integral_constant<int, ROLE>{}, nc);
-#endif
           });
           __builtin_amdgcn_sched_barrier(0);
         });
-#if !(RSP_ABL & 2)
         static_for<(NHU > NMFMA - BARE ? NHU - (NMFMA - BARE) : 0)>([&](auto hc) {
           half_unit(std::integral_constant<int, decltype(hc)::value + NMFMA - BARE>{});
         });
-#endif
         if constexpr (RHS) {
           float s = 0.f;
 #pragma unroll
@@ -805,7 +779,6 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
             bp[t] -= f32x2{fm, fm} * bp[t];
           }
         }
-        NE_T(3)
       };
       // QUAD: no software pipeline and no pinned interleave -- the second workgroup on the CU fills this wave's gaps.
       // Split the step's operands, start the look-ahead copies, then the 15 MFMAs back to back.
@@ -884,7 +857,6 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
             bp[t] -= f32x2{fm, fm} * bp[t];
           }
         }
-        NE_T(3)
       };
       const int niter = NROLES > 1 ? nst_max : nst;
       // only the row's last step can be partial, and it belongs to exactly one ring group; rank < KP: all masked
@@ -927,7 +899,6 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
         for (int t = 0; t < NB; t++) sB[wv * KP + 32 * t + lane] = bsum[t];
       }
       if (lane == 0) reinterpret_cast<double*>(sScal)[wv] = SCR ? sc : 0.0;
-      NE_T(4)
     };
     // ---- A = XtX + M1 (explicit: lambda_use I + M2).  The tiles are dealt round robin to the ring groups: in phase ph
     // group g works on the tiles t with t % NSETS == (g + ph) % NSETS -- in phase 0 it writes G + its partial sums there,
@@ -1083,15 +1054,11 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
     auto solve_row = [&]() __attribute__((always_inline)) {
     if (wv == 0 && (COLLECT || nst < D)) wait_vm<0>();   // short row: make sure the warm start has landed (see above)
     __syncthreads();   // warm start and every wave's right-hand-side partial are in LDS
-    NE_T(12)
     for (int ph = 0; ph < NSETS; ph++) {
       if constexpr (QUAD) with_role([&](auto rc) { chain_add_quad(rc); });
       else with_role([&](auto rc) { chain_add(rc, ph); });
-      NE_T(13)
       __syncthreads();
-      NE_T(14)
     }
-    NE_T(8)
 
     // ---- warm start, right-hand side and sum c, replicated in every wave; rank-vectors live as element 32 t + d in
     // register t (both halves of the wave alike)
@@ -1120,7 +1087,6 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
       }
       wave_sync();
       float* part = sPart + buf * NB * NB * 32;
-      NE_T(15)
       // the wave's NB^2 / 4 units together: all their LDS reads first (hipcc otherwise waits for each read before it
       // issues the next -- 16 round trips per unit), then the arithmetic
       constexpr int UW = NB * NB / 4, UB = QUAD ? 1 : UW;   // units in flight together (QUAD: 256 registers per wave, 80 of them accumulators)
@@ -1160,9 +1126,7 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
       }
       __builtin_amdgcn_sched_barrier(0);
       }
-      NE_T(16)
       __syncthreads();
-      NE_T(17)
 #pragma unroll
       for (int t = 0; t < NB; t++) {
         float s = part[(t * NB) * 32 + d];
@@ -1171,7 +1135,6 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
         out[t] = s;
       }
       buf ^= 1;
-      NE_T(18)
     };
     auto dot = [&](const float (&u)[NB], const float (&v)[NB]) {
       float s = 0.f;
@@ -1195,17 +1158,14 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
         for (int t = 0; t < NB; t++) sU[32 * t + d] = b[t];
       }
       __syncthreads();
-      NE_T(15)
       row_bad = LD::solve(sA, sA, sU, reinterpret_cast<int*>(sScal + 32), wv, lane);
       if (row_bad && tid == 0) {
         const int pos = atomicAdd(a.fail_counter, 1);
         if (pos < a.fail_cap) a.fail_rows[pos] = row;
       }
-      NE_T(16)
 #pragma unroll
       for (int t = 0; t < NB; t++) x[t] = (32 * t + d < k) ? sU[32 * t + d] : 0.f;
       __syncthreads();   // sPub is per-wave scratch again below
-      NE_T(18)
     } else {
     // cg_solver_implicit / cg_solver_explicit on the assembled operator (one matrix-vector product per pass: pass 0
     // forms r = b - A x); rsold / alpha in double like the reference (wrmf_implicit.hpp:18)
@@ -1247,7 +1207,6 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
       }
     }
     }
-    NE_T(9)
 
     // ---- loss of the row: sum c - 2 y.b + y^T (M1 + M2) y + lambda |y|^2  (explicit: sum r^2 - 2 y.b + y^T M2 y)
     wave_sync();
@@ -1258,7 +1217,6 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
     wave_sync();
     float qf = 0.f;
     with_role([&](auto rc) { qf = quad_form(rc, pub, x); });
-    NE_T(10)
     if (lane == 0) sScal[16 + wv] = qf;
     const float yb = dot(x, b), yy = dot(x, x);
     __syncthreads();
@@ -1296,16 +1254,8 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
       }
       nbuf = 0;
     }
-    NE_T(11)
   }
   wait_vm<0>();  // the look-ahead copies issued past the end of the list
-#ifdef RSP_NE_PROF
-  if (a.ne_prof && lane == 0) {
-    prof_t[5] = __builtin_amdgcn_s_memtime() - prof_start;
-    prof_t[6] = list_end - list_begin;
-    for (int j = 0; j < 20; j++) a.ne_prof[((size_t)blockIdx.x * 4 + wv) * 20 + j] = prof_t[j];
-  }
-#endif
 }
 
 template <int KP, int NS, bool IMPLICIT, bool SYM, bool QUAD, bool COLLECT, bool CHOL, bool GB = false>

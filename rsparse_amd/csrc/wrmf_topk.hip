@@ -45,11 +45,7 @@ __host__ __device__ constexpr int top_cap(int topk, int tiles_per_round) { retur
 // per workgroup: appends are fire-and-forget stores, only the counts and thresholds stay in LDS) with room for a BATCH of
 // arrivals beyond one tile's worth -- a user is settled once per max(64, k) arrivals, in the settling wave's LDS work area,
 // by a radix select (topk_reduce_user).  One geometry, 256 users per workgroup, for every k.
-#ifdef RSP_TOPK_GBATCH   // dev builds: a fixed batch room
-__host__ __device__ constexpr int top_gcap(int topk) { return ((topk + 32 + RSP_TOPK_GBATCH + 3) / 4) * 4; }
-#else
 __host__ __device__ constexpr int top_gcap(int topk) { return ((topk + 32 + (topk > 64 ? topk : 64) + 3) / 4) * 4; }
-#endif
 constexpr int kTopGbufChunk = 131072;   // users per launch of a GBUF call: 512 slots of scratch, two full rounds of workgroups
 
 // the kernel in which every wave walks its own item tiles against the workgroup's 32 UB users (W waves = W tiles per round)
@@ -1195,9 +1191,6 @@ size_t top_product_scratch_entries(int n_users, int n_items, int topk) {
 // TFLOP/s (the LDS took 32 users per workgroup there), top-10 80 -> 96, top-1 89 -> 98 (profiles/r06/r6topk_*).
 bool top_product_wants_gbuf(int n_users, int k_rank, int topk) {
   if (n_users <= 128 || k_rank > 128 || topk < 1 || topk > kTopMaxK) return false;
-#ifdef RSP_TOPK_NO_GBUF   // dev builds: the round-5 geometries
-  return false;
-#endif
   return padded_rank(k_rank) != 0;
 }
 // floats of scratch launch_top_product wants for this call (0 = none): the slices' lists of a call for few users, or the

@@ -14,7 +14,6 @@
 // It is the functional path of these ranks (one workgroup per row, k^2 flops per non-zero), not a tuned one; the bench line
 // (rank 128) does not run through it.  Gramian of a factor matrix at these ranks: the same packed tiles (below).
 #include <algorithm>
-#include <cstdlib>
 
 #include "wrmf_internal.h"
 #include "wrmf_device.h"
@@ -29,9 +28,6 @@ constexpr int kScdMaxIterW = 10000;
 constexpr float kScdTolW = 1e-4f;
 constexpr float kNnlsEpsW = 1e-16f;
 constexpr int NT = 256;
-#ifndef RSP_WIDE_ABL   // dev builds (timing only, results are garbage): bits switch phases of als_wide_kernel off
-#define RSP_WIDE_ABL 0   // 1 trailing update, 2 rank-one updates, 4 loss pass, 8 Gramian copy, 16 backward substitution, 32 staging
-#endif
 
 __device__ __forceinline__ int tri(const int i) { return (i * (i + 1)) >> 1; }
 
@@ -201,7 +197,7 @@ __global__ __launch_bounds__(NT) void als_wide_kernel(WideArgs a, int KP, int CH
       __syncthreads();
       for (int e = tid; e < tri(KP); e += NT) A[e] = 0.f;
       __syncthreads();
-      if (implicit && !(RSP_WIDE_ABL & 8)) {
+      if (implicit) {
         // thread i brings row i of the lower triangle, GU columns in flight at a time (coalesced over i; was one load per trip
         // behind a division: k k / NT = 68 round trips to L2 in a row at order 132)
         constexpr int GU = 16;
@@ -224,8 +220,8 @@ __global__ __launch_bounds__(NT) void als_wide_kernel(WideArgs a, int KP, int CH
       __syncthreads();
       for (int c0 = 0; c0 < n; c0 += CH) {
         const int cn = min(CH, n - c0);
-        if (!(RSP_WIDE_ABL & 32)) stage(p1, c0, cn);
-        if (!(RSP_WIDE_ABL & 2)) rank_update_packed(A, xs, KP, cw, cn, ntiles);
+        stage(p1, c0, cn);
+        rank_update_packed(A, xs, KP, cw, cn, ntiles);
         for (int t = tid; t < k; t += NT) {
           float s1 = 0.f, s2 = 0.f;
           for (int j = 0; j < cn; j++) {
@@ -419,7 +415,7 @@ __global__ __launch_bounds__(NT) void als_wide_kernel(WideArgs a, int KP, int CH
         }
         __syncthreads();
         const float zj1 = x[j1];
-        for (int i = j + 2 + rc; i < k && !(RSP_WIDE_ABL & 1); i += RTC) {
+        for (int i = j + 2 + rc; i < k; i += RTC) {
           float* rowi = A + tri(i);
           const float li = p[i], li1 = ap[i];
           int c = j + 2 + cc;
@@ -440,7 +436,7 @@ __global__ __launch_bounds__(NT) void als_wide_kernel(WideArgs a, int KP, int CH
       }
       __syncthreads();
       if (ok) {
-        if (wv == 0 && !(RSP_WIDE_ABL & 16)) {   // L^T y = z: lane l holds entries l + 64 q; row m of L is contiguous in the packed triangle
+        if (wv == 0) {   // L^T y = z: lane l holds entries l + 64 q; row m of L is contiguous in the packed triangle
           float z[4];
 #pragma unroll
           for (int q = 0; q < 4; q++) z[q] = lane + 64 * q < k ? x[lane + 64 * q] : 0.f;
@@ -541,7 +537,7 @@ __global__ __launch_bounds__(NT) void als_wide_kernel(WideArgs a, int KP, int CH
     // ---- write back, loss term ----
     for (int t = tid; t < k; t += NT) yrow[t] = x[t];
     float lpart = 0.f;
-    for (int c0 = 0; c0 < n && !(RSP_WIDE_ABL & 4); c0 += CH) {
+    for (int c0 = 0; c0 < n; c0 += CH) {
       const int cn = min(CH, n - c0);
       stage(p1, c0, cn);
       for (int j = wv; j < cn; j += 4) {
@@ -659,18 +655,12 @@ hipError_t launch_als_wide(const AlsArgs& a, bool implicit, unsigned solver, flo
   // A row is a chain of barriers and LDS round trips: what hides one workgroup's is ANOTHER workgroup on the CU.  Where a smaller
   // chunk of staged vectors (16 at least: one trip of the staging loop) buys a SECOND resident workgroup, take it: order 160,
   // 98 KB -> 77 KB, 335 -> 194 ms per iteration.  (A third one -- order 132 at 16 vectors per chunk -- measured 13 % slower than
-  // two at 64: profiles/r06/r6wide_ab_*.  RSPARSE_HIP_WIDE_CHUNK pins the chunk for such measurements in -DRSP_AB builds.)
+  // two at 64: profiles/r06/r6wide_ab_*.)
   if (2 * lds_of(ch) > (size_t)158 * 1024) {
     int c = ch;
     while (c >= 16 && 2 * lds_of(c) > (size_t)158 * 1024) c >>= 1;
     if (c >= 16) ch = c;
   }
-#ifdef RSP_AB   // (dev builds: the shipped library reads no environment variable)
-  if (const char* e = std::getenv("RSPARSE_HIP_WIDE_CHUNK")) {
-    const int c = std::atoi(e);
-    if (c >= 4 && c <= 64 && (c & (c - 1)) == 0 && lds_of(c) <= kWideLds) ch = c;
-  }
-#endif
   const size_t lds = lds_of(ch);
   auto kern = als_wide_kernel;
   hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -1,4 +1,4 @@
-import os, sys, numpy as np
+import sys, numpy as np
 sys.path.insert(0, "tests"); sys.path.insert(0, ".")
 from oracle import wrmf_oracle as O
 from rsparse_amd import als
@@ -30,6 +30,6 @@ for outlier in (1.0, 30.0):
         m = lens > 0
         ratio = err[m] / np.maximum(err32[m], 1e-9)
         sel = np.zeros(n_cols, bool); sel[::7] = True
-        print("dmf=%s outlier %4.0f scale %6g warm %d: max err %.2e (fp32 oracle %.2e)  median ratio %.2f  max ratio %.1f  [warm cols: max err %.2e, fp32 %.2e]" % (
-            os.environ.get("RSPARSE_HIP_DENSE_MFMA", "1"), outlier, scale, warm, err[m].max(), err32[m].max(), np.median(ratio), ratio.max(),
+        print("outlier %4.0f scale %6g warm %d: max err %.2e (fp32 oracle %.2e)  median ratio %.2f  max ratio %.1f  [warm cols: max err %.2e, fp32 %.2e]" % (
+            outlier, scale, warm, err[m].max(), err32[m].max(), np.median(ratio), ratio.max(),
             err[m & sel].max(), err32[m & sel].max()))
