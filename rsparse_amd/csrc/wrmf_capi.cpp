@@ -430,6 +430,7 @@ int build_q_schedule(DevCSC& d, const int32_t* host_col_ptrs) {
   d.q_n_chol_long = 0;
   d.q_lr_first = 0; d.q_n_lr = 0; d.q_gt32 = 0; d.q_gt48 = 0;
   d.q_pair_first = 0;
+  d.q_team4_first = 0;
   d.q_cfg = cgq_default_cfg();
   if (n <= 0) return RSPARSE_HIP_OK;
   const int max_len = d.max_len;
@@ -441,6 +442,7 @@ int build_q_schedule(DevCSC& d, const int32_t* host_col_ptrs) {
     const int b = cgq_bucket_of(len, d.q_cfg);
     if (len > kCholLongLen) d.q_n_chol_long++;
     if (len > 16) d.q_pair_first++;                // the order is longest first: the rows of <= 16 non-zeros are a suffix
+    if (len > kTeam4Max) d.q_team4_first++;        // ... and so are those of <= kTeam4Max
     if (len > 32) d.q_gt32++;
     if (len > 48) d.q_gt48++;
     if (len > kCholLrMax) d.q_lr_first++;          // the order is longest first: the short rows are a suffix
@@ -663,6 +665,8 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   qs.cfg = d.q_cfg;
   qs.pair_first = d.q_pair_first;
   for (int b = 0; b < 7; b++) qs.off[b] = d.q_off[b];
+  // (the global-bias CG keeps bucket 1 on the 8-wave kernel: no 4-wave launch, no loss slots for one)
+  qs.team4_first = (implicit && bias && bias->gbias != 0.f) ? d.q_off[2] : d.q_team4_first;
   // (two workgroups per CU only for implicit feedback at rank 97..128: the fp16 QUAD kernel of wrmf_ne.hip)
   const bool ne_fine = implicit && padded_rank(rank) == 128;
   qs.ne_rows = ne_fine ? d.q_ne_rows : d.q_ne1_rows; qs.ne_ptr = ne_fine ? d.q_ne_ptr : d.q_ne1_ptr;

@@ -169,7 +169,10 @@ struct QSmem {
   static constexpr size_t red_floats = WPR > 1 ? (size_t)2 * WAVES * KP + 2 * WAVES : 0;
   // resident rows: per wave, t_acc[CAP] = x_j . y accumulated over the CG steps and t_cur[CAP] = x_j . p of the
   // current step (the loss is rebuilt from them instead of a fifth pass over the registers)
-  static constexpr size_t tsv_floats = (STREAM && !IMPLICIT) ? 0 : (size_t)WAVES * 2 * CAPQ * 4;
+  // cv_lds: resident rows whose gathered vectors take more than 128 registers (20 quads at rank 128) keep the confidences /
+  // ratings of the chunk in a third slot, [group][quad], read as one 16-byte broadcast per block of four quads
+  static constexpr bool cv_lds = !STREAM && CAPQ * (KP / 16) > 128;
+  static constexpr size_t tsv_floats = (STREAM && !IMPLICIT) ? 0 : (size_t)WAVES * (cv_lds ? 3 : 2) * CAPQ * 4;
   // streamed rows: the first kStreamPrefixQ quads of every wave (gathered in the first sweep) stay in LDS,
   // so the other sweeps re-gather only the rest of the row
   static constexpr size_t pre_floats = STREAM ? (size_t)WAVES * kStreamPrefixQ * 4 * KP : 0;
@@ -178,9 +181,16 @@ struct QSmem {
   static constexpr int dmf_ps = KP + 8, dmf_os = KP + 4;
   static constexpr size_t dmf_floats = DMF ? (size_t)WAVES * dmf_ps + (size_t)WAVES * dmf_os : 0;
   // resident rows on teams of more than kIdxPrefetchMaxWpr waves: the next row's indices / values (one per lane) land here
-  // by LDS-DMA during the current row's sweeps -- those kernels have no two registers to hold them (KFULL instantiations)
-  static constexpr size_t pfx_floats = (!STREAM && WPR > kIdxPrefetchMaxWpr && CAPQ * 4 == 64) ? (size_t)WAVES * 2 * 64 : 0;
-  static constexpr size_t bytes = (gram_floats + vec_floats + red_floats + tsv_floats + pre_floats + dmf_floats + pfx_floats) * 4 + 16;
+  // by LDS-DMA during the current row's sweeps -- those kernels have no two registers to hold them (KFULL instantiations).
+  // One slot of CAP indices + CAP values per wave; CAP = 80 (the 20-quad team kernel) takes a second, 16-lane DMA per array
+  static constexpr size_t pfx_floats =
+      (!STREAM && WPR > kIdxPrefetchMaxWpr && (CAPQ == 16 || CAPQ == 20)) ? (size_t)WAVES * 2 * CAPQ * 4 : 0;
+  // cv_lds: the wave's loss sum (a double) and the CG iterate x between the first sweep and the loss are kept here too, not in
+  // registers that would live across the sweeps (x is touched once per CG step, the quads four times per sweep)
+  static constexpr size_t wl_floats = cv_lds ? (size_t)WAVES * 2 : 0;
+  static constexpr size_t xs_floats = cv_lds ? (size_t)WAVES * KP : 0;
+  static constexpr size_t bytes =
+      (gram_floats + vec_floats + red_floats + tsv_floats + pre_floats + dmf_floats + pfx_floats + wl_floats + xs_floats) * 4 + 16;
 };
 
 // GB: implicit feedback with a global bias (cg_solver_implicit_global_bias, wrmf_implicit.hpp:35-57,203): the first
@@ -314,10 +324,15 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
     if constexpr (DMF == 2) wave_sync();   // (each wave reads back only what it wrote)
   }
   float* vec = sVec + wv * KP;
-  float* tacc = sTsv + wv * 2 * CAP;  // resident rows only
+  constexpr bool CVLDS = SM::cv_lds;
+  float* tacc = sTsv + wv * (CVLDS ? 3 : 2) * CAP;  // resident rows only
   float* tcur = tacc + CAP;
+  float* csv = tcur + CAP;   // CVLDS: [4][CAPQ], group g's quad q at g * CAPQ + q
   int buf = 0;
   double wloss = 0.0;
+  double* wl_lds = reinterpret_cast<double*>(sPfx + SM::pfx_floats) + wv;   // CVLDS: the loss sum instead of wloss
+  if (CVLDS && lane == 0) *wl_lds = 0.0;
+  float* xs = sPfx + SM::pfx_floats + SM::wl_floats + wv * KP;   // CVLDS: x during the CG steps (group 0 writes, all read)
   int pf_id = 0, pf_cnt = -1;   // next row's share of this wave, lane-major (IDXPF)
   float pf_c = 0.f;
   const int team_global = blockIdx.x * TEAMS + team;
@@ -380,11 +395,19 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
     }
 
     float xt[CAPQ][RPN];  // gathered vectors: quad q, group g holds non-zero 4q+g of the chunk
-    float cv[CAPQ];       // its confidence / rating (uniform inside the group)
-    constexpr int NSL = (CAP + 63) / 64;   // slots of the chunk per lane (2 only for the rank <= 64 geometry, CAP = 128)
-    float cl[NSL];        // resident rows: confidence / rating of non-zero `lane` (+ 64) of the chunk (loss)
+    float cv[CVLDS ? 1 : CAPQ];   // its confidence / rating (uniform inside the group; CVLDS: in csv instead)
+    constexpr int NSL = (CAP + 63) / 64;   // slots of the chunk per lane (2 for CAP = 80 and the rank <= 64 geometry's 128)
+    float cl[CVLDS ? 1 : NSL];   // resident rows: confidence / rating of non-zero `lane` (+ 64) of the chunk (loss; CVLDS: csv)
 #pragma unroll
-    for (int s2 = 0; s2 < NSL; s2++) cl[s2] = 0.f;
+    for (int s2 = 0; s2 < (CVLDS ? 1 : NSL); s2++) cl[s2] = 0.f;
+    // CVLDS: slot s of the chunk <- its confidence (0 beyond n), one lane per slot
+    auto csv_fill = [&](auto&& conf_of, const int n) {
+#pragma unroll
+      for (int s2 = 0; s2 < NSL; s2++) {
+        const int sl = lane + 64 * s2;
+        if (s2 == 0 || sl < CAP) csv[(sl & 3) * CAPQ + (sl >> 2)] = sl < n ? conf_of(sl) : 0.f;
+      }
+    };
     int ccnt = 0;
 
     // Gather n (1..CAP) non-zeros starting at `base` into the registers: all index loads, then all vector
@@ -399,8 +422,21 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
     constexpr bool IDXPF = CAP <= 64 && ((STREAM == 0 && WPR <= kIdxPrefetchMaxWpr) || (STREAM == 1 && IMPLICIT));
     // the LDS-DMA variant of the same prefetch for the kernels that have no registers for it (see QSmem::pfx_floats)
     constexpr bool DMAPF = KFULL && !IDXPF && SM::pfx_floats > 0;
-    int* pfxI = reinterpret_cast<int*>(sPfx) + wv * 128;
-    float* pfxC = sPfx + wv * 128 + 64;
+    int* pfxI = reinterpret_cast<int*>(sPfx) + wv * 2 * CAP;
+    float* pfxC = sPfx + wv * 2 * CAP + CAP;
+    // announce the next n (> 0) non-zeros from `j0` on: slots [0, 64) from every lane, [64, CAP) from the first lanes
+    auto dma_slot = [&](const int j0, const int n) {
+      const int j = j0 + min(lane, n - 1);
+      dma4(a.row_idx + j, lds_addr(pfxI));
+      dma4(a.vals + j, lds_addr(pfxC));
+      if constexpr (CAP > 64) {
+        if (lane < CAP - 64) {
+          const int j2 = j0 + min(lane + 64, n - 1);
+          dma4(a.row_idx + j2, lds_addr(pfxI + 64));
+          dma4(a.vals + j2, lds_addr(pfxC + 64));
+        }
+      }
+    };
     int pf_pos = -1;   // streamed rows: chunk the prefetch registers belong to
     auto gather_q = [&](auto nq_tag, const int base, const int n, const bool from_pf = false) {
       constexpr int NQG = decltype(nq_tag)::value;
@@ -409,9 +445,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         // one path: the indices / values come from the wave's LDS slot, where the previous row's sweeps left them; a row
         // that was not announced (the team's first) fetches them the same way and waits
         if (!from_pf && n > 0) {
-          const int j = base + min(lane, n - 1);
-          dma4(a.row_idx + j, lds_addr(pfxI));
-          dma4(a.vals + j, lds_addr(pfxC));
+          dma_slot(base, n);
           wait_vm0();
         }
         wave_sync();
@@ -419,9 +453,14 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         for (int q = 0; q < NQG; q++) {
           const int j = max(min(4 * q + g, n - 1), 0);
           id[q] = pfxI[j];
-          cv[q] = (!ZPAD || 4 * q + g < n) ? pfxC[j] : 0.f;
+          if constexpr (!CVLDS) cv[q] = (!ZPAD || 4 * q + g < n) ? pfxC[j] : 0.f;
         }
-        if constexpr (TSAVE) cl[0] = lane < n ? pfxC[lane] : 0.f;
+        if constexpr (CVLDS) {
+          csv_fill([&](int sl) { return pfxC[sl]; }, n);
+        } else if constexpr (TSAVE) {
+#pragma unroll
+          for (int s2 = 0; s2 < NSL; s2++) cl[s2] = lane + 64 * s2 < n ? pfxC[min(lane + 64 * s2, CAP - 1)] : 0.f;
+        }
         wave_sync();
       } else if (IDXPF && from_pf) {
         // lane-major prefetch registers -> quad layout through the wave's t-slots (dead between two rows)
@@ -434,7 +473,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         for (int q = 0; q < NQG; q++) {
           const int j = max(min(4 * q + g, n - 1), 0);
           id[q] = xi[j];
-          cv[q] = (!ZPAD || 4 * q + g < n) ? tcur[j] : 0.f;
+          if constexpr (!CVLDS) cv[q] = (!ZPAD || 4 * q + g < n) ? tcur[j] : 0.f;
         }
         if constexpr (TSAVE) cl[0] = lane < n ? pf_c : 0.f;
         wave_sync();
@@ -443,10 +482,16 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         for (int q = 0; q < NQG; q++) {
           const int j = max(min(4 * q + g, n - 1), 0);
           id[q] = a.row_idx[base + j];
-          const float c = a.vals[base + j];
-          cv[q] = (!ZPAD || 4 * q + g < n) ? c : 0.f;
+          if constexpr (!CVLDS) {
+            const float c = a.vals[base + j];
+            cv[q] = (!ZPAD || 4 * q + g < n) ? c : 0.f;
+          }
         }
-        if constexpr (TSAVE) {
+        if constexpr (CVLDS) {
+          wave_sync();   // (the previous row's loss has read the slots)
+          csv_fill([&](int sl) { return a.vals[base + sl]; }, n);
+          wave_sync();
+        } else if constexpr (TSAVE) {
 #pragma unroll
           for (int s2 = 0; s2 < NSL; s2++) cl[s2] = lane + 64 * s2 < n ? a.vals[base + lane + 64 * s2] : 0.f;
         }
@@ -575,11 +620,19 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
           for (int u = 0; u < QB; u++) t[u] += dpp<0x141>(t[u]);  // row_half_mirror
 #pragma unroll
           for (int u = 0; u < QB; u++) t[u] += dpp<0x140>(t[u]);  // row_mirror
+          float cq[QB];
+          if constexpr (CVLDS) {
+            const float4 c4 = *reinterpret_cast<const float4*>(csv + g * CAPQ + q0);
+            cq[0] = c4.x; cq[1] = c4.y; cq[2] = c4.z; cq[3] = c4.w;
+          } else {
+#pragma unroll
+            for (int u = 0; u < QB; u++) cq[u] = cv[q0 + u];
+          }
 #pragma unroll
           for (int u = 0; u < QB; u++) {
             const int q = q0 + u;
             const bool valid = ZPAD || 4 * q + g < ccnt;
-            const float c = cv[q];
+            const float c = cq[u];
             if constexpr (STREAM == 1) {  // keep t_j = x_j . v of this sweep: the loss is rebuilt from them
               if (tsave && valid && i == 0) tsave[4 * q + g] = t[u];
             } else if constexpr (TSAVE) {
@@ -730,9 +783,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
             float esum = 0.f;
 #pragma unroll
             for (int s2 = 0; s2 < NSL; s2++) {
-              const int sl = NSL == 1 ? (lane & (CAP - 1)) : lane + 64 * s2;
+              const int sl = NSL == 1 ? (lane & (CAP - 1)) : min(lane + 64 * s2, CAP - 1);
               const float t = tacc[sl];
-              const float clv = cl[s2];
+              const float clv = CVLDS ? csv[(sl & 3) * CAPQ + (sl >> 2)] : cl[s2];
               const float d = IMPLICIT ? ltgt - t : clv - t;
               const float e = IMPLICIT ? clv * d * d : d * d;
               esum += lane + 64 * s2 < ccnt ? e : 0.f;
@@ -895,6 +948,20 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
     const bool live = have && (GB || cnt > 0);
     float dummy = 0.f;
     sweep(x, 0, r, dummy, live);
+    // x: park in LDS until the loss; the CG steps update it there (x_lds / x_axpy / x_back: no-ops without CVLDS)
+    auto x_piece = [&](const int b) { return reinterpret_cast<piece_t*>(xs + b * 16 * VW + i * VW); };
+    if constexpr (CVLDS) {
+      if (g == 0) {
+#pragma unroll
+        for (int b = 0; b < NV; b++) {
+          piece_t pc;
+          float* pf = reinterpret_cast<float*>(&pc);
+#pragma unroll
+          for (int c = 0; c < VW; c++) pf[c] = x[b * VW + c];
+          *x_piece(b) = pc;
+        }
+      }
+    }
     if constexpr (IDXPF && STREAM == 0) {
       // the next row's pointers were requested at the top of this iteration and have arrived by now
       if (it + 1 < rows_per_team && row_index(it + 1) < n_rows) {
@@ -915,9 +982,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         const int nper = min(CAP, (((ncnt + WPR - 1) / WPR) + 15) & ~15);
         const int ncc = max(0, min(nper, ncnt - tw * nper));
         if (ncc > 0) {   // (the slot's previous content was consumed by this row's gather)
-          const int j = np1 + tw * nper + min(lane, ncc - 1);
-          dma4(a.row_idx + j, lds_addr(pfxI));
-          dma4(a.vals + j, lds_addr(pfxC));
+          dma_slot(np1 + tw * nper, ncc);
           pf_cnt = ncc;
         }
       }
@@ -942,13 +1007,25 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
 #pragma unroll
           for (int s2 = 0; s2 < NSL; s2++) {
             const int sl = NSL == 1 ? (lane & (CAP - 1)) : lane + 64 * s2;
-            tacc[sl] = fmaf(alpha, tcur[sl], tacc[sl]);
+            if (CAP % 64 == 0 || sl < CAP) tacc[sl] = fmaf(alpha, tcur[sl], tacc[sl]);
           }
           wave_sync();
         }
+        if constexpr (CVLDS) {
+          if (g == 0) {
+#pragma unroll
+            for (int b = 0; b < NV; b++) {
+              piece_t pc = *x_piece(b);
+              float* pf = reinterpret_cast<float*>(&pc);
+#pragma unroll
+              for (int c = 0; c < VW; c++) pf[c] = fmaf(alpha, p[b * VW + c], pf[c]);
+              *x_piece(b) = pc;
+            }
+          }
+        }
 #pragma unroll
         for (int rr = 0; rr < RPN; rr++) {
-          x[rr] = fmaf(alpha, p[rr], x[rr]);
+          if constexpr (!CVLDS) x[rr] = fmaf(alpha, p[rr], x[rr]);
           r[rr] = fmaf(-alpha, ap[rr], r[rr]);
         }
         const float rsnew = dot16(r, r);
@@ -962,6 +1039,16 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         }
       }
     }
+    if constexpr (CVLDS) {
+      wave_sync();
+#pragma unroll
+      for (int b = 0; b < NV; b++) {
+        const piece_t pc = *x_piece(b);
+        const float* pf = reinterpret_cast<const float*>(&pc);
+#pragma unroll
+        for (int c = 0; c < VW; c++) x[b * VW + c] = pf[c];
+      }
+    }
     float rl = 0.f;
     sweep(x, 2, ap, rl, live);
     if constexpr (DMAPF) wait_vm0();   // the announced row's indices have long landed; nothing of this wave's is in flight after this
@@ -972,7 +1059,12 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
     }
     if (live && tw == 0) {
       const float xx = dot16(x, x);
-      wloss += IMPLICIT ? (double)rl + a.lambda_loss * (double)xx : (double)(rl + lam_use * xx);
+      const double wl_row = IMPLICIT ? (double)rl + a.lambda_loss * (double)xx : (double)(rl + lam_use * xx);
+      if constexpr (CVLDS) {
+        if (lane == 0) *wl_lds += wl_row;
+      } else {
+        wloss += wl_row;
+      }
       if (g == 0) {
 #pragma unroll
         for (int b = 0; b < NV; b++) {
@@ -988,13 +1080,17 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
       }
     }
   }
-  if (lane == 0) a.loss_partials[loss_slot0 + (size_t)blockIdx.x * WAVES + wv] = wloss;
+  if (lane == 0) a.loss_partials[loss_slot0 + (size_t)blockIdx.x * WAVES + wv] = CVLDS ? *wl_lds : wloss;
 }
 
 // Launch table.  Rows are bucketed by length; each bucket is one launch of the kernel instantiated for
 // (waves per workgroup W, waves per row WPR, resident quads per wave, streamed?):
 //   bucket 0  streamed rows (longer than 512 non-zeros): teams of 8 waves, 512-thread workgroups
-//   bucket 1  257..512 non-zeros: resident on 8-wave teams
+//   bucket 1  257..512 non-zeros: resident on 8-wave teams -- at rank 97..128 (no global bias) only the rows of
+//             kTeam4Max + 1..512; the rows up to kTeam4Max run in a second launch on 4-wave teams of 20 quads per wave
+//             (256-thread workgroups, two per CU, like bucket 2).  The split is a position in the order
+//             (QSchedule::team4_first), not a bucket of its own.  Rank 33..64 runs the whole bucket on 4-wave teams
+//             (geometry 1); ranks <= 32 and the global-bias variant keep it on the 8-wave kernel
 //   bucket 2.. 129..256 / 65..128 / 33..64 non-zeros: resident on teams of 4 / 2 / 1 waves of 256-thread
 //             workgroups (two per CU: they run out of phase, one gathers while the other sweeps)
 //   bucket 5  <= 32 non-zeros: one wave per row with a 32-slot tile (half the redundant gather slots)
@@ -1012,6 +1108,12 @@ constexpr BucketDef kBuckets[kNCfg][kNB] = {
     {{8, 8, 16, 1, 0x7fffffff}, {4, 4, 32, 0, 512}, {4, 2, 32, 0, 256}, {4, 1, 32, 0, 128}, {4, 1, 16, 0, 64}, {4, 1, 8, 0, 32}},
 };
 constexpr int cfg_of_kp(int KP) { return KP == 64 ? 1 : 0; }
+// the second launch of bucket 1 at rank 97..128: rows of up to kTeam4Max = 4 waves x 20 quads x 4 non-zeros
+constexpr int kTeam4Waves = 4, kTeam4Capq = 20;
+static_assert(kTeam4Max == kTeam4Waves * kTeam4Capq * 4, "wrmf_internal.h's split and the kernel's capacity");
+constexpr bool team4_split(int KP, bool GB) { return KP == 128 && !GB; }
+// position in the order where bucket 1's 4-wave launch starts (= the bucket's end when there is none)
+int team4_first(const QSchedule& q) { return std::min(std::max(q.team4_first, q.off[1]), q.off[2]); }
 
 template <int KP, int WAVES, int CAPQ, int WPR, int STREAM, bool IMPLICIT, bool GB, int DMF = 0, bool KFULL = false>
 hipError_t launch_bucket(const AlsArgs& a, const int32_t* rows, int n_rows, int grid, size_t slot0, hipStream_t s,
@@ -1077,6 +1179,10 @@ size_t bucket_slots(const QSchedule& q, int b, int k, bool implicit) {
   if (d.wpr <= 0) return 0;
   if (d.stream && ne_supported(k)) return (size_t)(q.ne_entries + q.ne_nsplit) + (size_t)(q.mf_n > 0 ? cg_mf_loss_slots(q.mf_n) : 0);
   const int rows = q.off[b + 1] - q.off[b];
+  if (b == 1 && padded_rank(k) == 128) {   // (the global-bias variant gets team4_first = off[2] from its caller)
+    const int split = team4_first(q);
+    return (size_t)cgq_bucket_grid(split - q.off[b], b, cfg) * d.waves + (size_t)cgq_team4_grid(q.off[b + 1] - split) * kTeam4Waves;
+  }
   if (b == kNB - 1 && rows > 0 && cgp_supported(k, implicit)) {
     const int split = std::min(std::max(q.pair_first, q.off[b]), q.off[b + 1]);
     return (size_t)cgq_bucket_grid(split - q.off[b], b, cfg) * d.waves + (size_t)cgp_grid(q.off[b + 1] - split) * 4;
@@ -1140,6 +1246,18 @@ hipError_t launch_all(const AlsArgs& a, const QSchedule& q, hipStream_t s, hipEv
           }                                                                                                 \
         } else if constexpr (D.stream && KP > 32) {   /* ranks above 32 always take the branch above */     \
           return hipErrorInvalidValue;                                                                      \
+        } else if constexpr (B == 1 && team4_split(KP, GB)) {                                              \
+          /* bucket 1 in two launches: rows of kTeam4Max + 1..512 non-zeros on 8-wave teams, the shorter ones on 4-wave teams */ \
+          const int first = q.off[B], split = team4_first(q);                                               \
+          const int n_main = split - first, n_t4 = q.off[B + 1] - split;                                    \
+          const int g_main = cgq_bucket_grid(n_main, B, CFG);                                               \
+          if ((err = launch_bucket<KP, D.waves, D.capq, D.wpr, D.stream, IMPLICIT, GB>(a, q.order + first, n_main, g_main, slot, \
+                                                                                  bs, ev ? ev + B : nullptr)) != hipSuccess) \
+            return err;                                                                                     \
+          if ((err = launch_bucket<KP, kTeam4Waves, kTeam4Capq, kTeam4Waves, 0, IMPLICIT, GB>(              \
+                   a, q.order + split, n_t4, cgq_team4_grid(n_t4), slot + (size_t)g_main * D.waves, bs,     \
+                   n_main > 0 ? nullptr : (ev ? ev + B : nullptr))) != hipSuccess)                          \
+            return err;                                                                                     \
         } else if (B == kNB - 1 && cgp_supported(a.k, IMPLICIT)) {                    \
           /* the last bucket in two launches: rows of 17..32 non-zeros one per wave, the rest two per wave (wrmf_cgp.hip) */ \
           const int first = q.off[B], split = std::min(std::max(q.pair_first, first), q.off[B + 1]);         \
@@ -1181,15 +1299,8 @@ int cgq_bucket_capq(int cfg, int b) { return kBuckets[cfg][b].capq; }
 int cgq_bucket_waves(int cfg, int b) { return kBuckets[cfg][b].waves; }
 int cgq_bucket_stream(int cfg, int b) { return kBuckets[cfg][b].stream; }
 
-int cgq_bucket_grid(int n_rows, int b, int cfg) {
-  const BucketDef d = kBuckets[cfg][b];
-  if (n_rows <= 0 || d.wpr <= 0) return 0;
-  const int teams = d.waves / d.wpr;
-  // rows per team: amortises the per-workgroup start-up (64 KB Gramian load, LDS clear); the streamed
-  // bucket holds few, very long rows and keeps a small quota for balance
-  // (measured on config 3: doubling the quota of the team kernels from 4 / 16 is worth 3 % of the iteration, a
-  // further doubling is flat; the one-wave kernels prefer 64)
-  const int base = d.stream ? 16 : (d.wpr == 1 ? 64 : (d.wpr == 2 ? 64 : 32));
+namespace {
+int team_grid(int n_rows, int teams, int base) {
   int rows_per_team = base;
   // small buckets (shards of a multi-GPU run, tiny matrices): spread the rows over the CUs first -- the quota
   // only grows once there are two workgroups per CU
@@ -1201,6 +1312,21 @@ int cgq_bucket_grid(int n_rows, int b, int cfg) {
   if (grid < 1) grid = 1;
   return (int)grid;
 }
+}  // namespace
+
+int cgq_bucket_grid(int n_rows, int b, int cfg) {
+  const BucketDef d = kBuckets[cfg][b];
+  if (n_rows <= 0 || d.wpr <= 0) return 0;
+  // rows per team: amortises the per-workgroup start-up (64 KB Gramian load, LDS clear); the streamed
+  // bucket holds few, very long rows and keeps a small quota for balance
+  // (measured on config 3: doubling the quota of the team kernels from 4 / 16 is worth 3 % of the iteration, a
+  // further doubling is flat; the one-wave kernels prefer 64)
+  const int base = d.stream ? 16 : (d.wpr == 1 ? 64 : (d.wpr == 2 ? 64 : 32));
+  return team_grid(n_rows, d.waves / d.wpr, base);
+}
+
+// bucket 1's 4-wave launch: one team per workgroup, the team kernels' quota
+int cgq_team4_grid(int n_rows) { return n_rows <= 0 ? 0 : team_grid(n_rows, 1, 32); }
 
 int cgq_bucket_of(int len, int cfg) {  // last (smallest-team) bucket whose capacity holds the row
   int best = 0;

@@ -26,6 +26,7 @@ struct DevCSC {
   int q_off[7] = {0, 0, 0, 0, 0, 0, 0};
   int q_cfg = 0;
   int q_pair_first = 0;   // position in q_order of the first row with at most 16 non-zeros (wrmf_cgp.hip: two rows per wave)
+  int q_team4_first = 0;  // ... of the first row with at most kTeam4Max non-zeros (bucket 1's 4-wave launch at rank 97..128)
   int64_t q_nnz[6] = {0, 0, 0, 0, 0, 0};
   int64_t* q_stream_off = nullptr;  // prefix sums of the streamed bucket's row lengths (device)
   // normal-equation kernel (wrmf_ne.hip): the long rows (bucket 0) dealt to q_ne_wg workgroups, longest processing
@@ -147,6 +148,7 @@ struct QSchedule {
   const int32_t* order;
   int off[7];
   int pair_first;   // see DevCSC::q_pair_first
+  int team4_first;  // see DevCSC::q_team4_first; = off[2] when bucket 1 runs on the 8-wave kernel alone (global bias)
   int cfg;  // geometry the schedule was built for (see wrmf_cgq.hip kBuckets)
   const int32_t* ne_rows;  // see DevCSC::q_ne_*
   const int32_t* ne_ptr;
@@ -166,6 +168,9 @@ int cgq_bucket_capq(int cfg, int b);
 int cgq_bucket_waves(int cfg, int b);  // waves per workgroup of bucket b's kernel
 int cgq_bucket_stream(int cfg, int b);
 int cgq_bucket_grid(int n_rows, int bucket, int cfg);
+// bucket 1 at rank 97..128: the rows of up to kTeam4Max non-zeros on 4-wave teams of 20 quads per wave (wrmf_cgq.hip)
+constexpr int kTeam4Max = 320;
+int cgq_team4_grid(int n_rows);
 int cgq_bucket_of(int len, int cfg);
 size_t cgq_loss_slots(const QSchedule& q, int k, bool implicit);
 // the rows of at most 16 non-zeros of the last bucket, two per wave (wrmf_cgp.hip): rank 65..128, implicit feedback
