@@ -361,6 +361,30 @@ int rsparse_hip_top_product_f64_device(const float* d_U, const float* d_V, const
                                        double* d_scores, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * ranking metrics of the `$predict` lists: ap_k() / ndcg_k() (R/metrics.R:31-127, NAMESPACE)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* replaces the per-user loops of ap_k / ndcg_k.  predictions: n_users x k column-major 1-based item indices with NA_integer_
+ * (R's integer matrix, what rsparse_hip_top_product writes); actual: the dgRMatrix slots p (n_users + 1), j (sorted 0-based
+ * columns), x (relevances).  Per user, kk = min(k, stored entries of the row): ap = the mean over positions 1..kk of the hits
+ * so far / position; ndcg = dcg / idcg over the first kk positions (idcg = 1 for an empty row; ap of an empty row is NaN).
+ * NA, out-of-range and repeated predictions are looked up one by one like `%in%` / `match`; stored zeros are relevant items
+ * of relevance 0.  Double arithmetic with a fixed reduction order: a repeated call returns the same bits.  Either output may
+ * be NULL, not both; actual_x is read only for ndcg_out.  NULL where needed, n_users < 0, k < 1, p[0] != 0, a decreasing p or
+ * j not strictly ascending within a row -> ERR_INVALID; k > RSPARSE_HIP_MAX_TOPK_LARGE -> ERR_UNSUPPORTED (the R loop
+ * stays, as for k = 0). */
+int rsparse_hip_ranking_metrics(const int32_t* predictions, int n_users, int k, const int32_t* actual_p,
+                                const int32_t* actual_j, const double* actual_x, double* ap_out, double* ndcg_out);
+
+/* device-resident form: d_predictions n_users x k ROW-major, as rsparse_hip_top_product_{,f64_}device write them; outputs
+ * n_users doubles.  Enqueued on `stream`, no synchronisation.  Same status codes, except that a valid p and j strictly
+ * ascending within every row are preconditions here, not checked (they live on the device).  Keeps n_users + 1 ints of the
+ * library's grow-only workspace. */
+int rsparse_hip_ranking_metrics_device(const int32_t* d_predictions, int n_users, int k, const int32_t* d_actual_p,
+                                       const int32_t* d_actual_j, const double* d_actual_x, double* d_ap_out,
+                                       double* d_ndcg_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * (3) fp64 device layer: als_implicit<double> / als_explicit<double> with the data resident in HBM
  * ---------------------------------------------------------------------------------------------- */
 

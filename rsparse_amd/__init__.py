@@ -2,6 +2,7 @@
 
 Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit,explicit}.hpp):
   rsparse_amd.WRMF            host-side mirror of the R6 class
+  rsparse_amd.metrics         ap_k() / ndcg_k(), the reference's ranking metrics, on the device
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
   rsparse_amd.engine          device-resident, row-sharded driver (one process per GPU)
   rsparse_amd.synth           synthetic interaction matrices for the BASELINE configs
@@ -14,4 +15,7 @@ def __getattr__(name):
     if name == "WRMF":
         from .wrmf import WRMF
         return WRMF
+    if name == "metrics":
+        import importlib
+        return importlib.import_module(".metrics", __name__)
     raise AttributeError(name)

@@ -71,6 +71,8 @@ struct Workspace {
   size_t wide_m2_floats = 0;
   float* wide_lu = nullptr;
   size_t wide_lu_floats = 0;
+  int* met_buf = nullptr;      // ranking metrics (wrmf_metrics.hip): count + list of the users whose idcg takes the long-row launch
+  size_t met_ints = 0;
   int device = -1;
 
   int ensure_device() {
@@ -201,7 +203,19 @@ struct Workspace {
     }
     return RSPARSE_HIP_OK;
   }
+  int ensure_met(size_t ints) {
+    if (ints > met_ints) {
+      if (met_buf) (void)hipFree(met_buf);
+      met_buf = nullptr;
+      met_ints = 0;
+      HIP_TRY(hipMalloc(&met_buf, ints * sizeof(int)));
+      met_ints = ints;
+    }
+    return RSPARSE_HIP_OK;
+  }
   void release() {
+    if (met_buf) (void)hipFree(met_buf);
+    met_buf = nullptr; met_ints = 0;
     if (wide_m2) (void)hipFree(wide_m2);
     if (wide_lu) (void)hipFree(wide_lu);
     wide_m2 = wide_lu = nullptr; wide_m2_floats = wide_lu_floats = 0;
@@ -1734,6 +1748,69 @@ int rsparse_hip_top_product(const double* x, const double* y, int nr, int nc, in
       res[(size_t)c * nr + j] = hr[(size_t)j * k + c];
       scores[(size_t)c * nr + j] = hs[(size_t)j * k + c];
     }
+  return RSPARSE_HIP_OK;
+}
+
+namespace {
+// the arguments both forms of rsparse_hip_ranking_metrics check before anything else
+int ranking_metrics_args(const int32_t* pred, int n_users, int k, const int32_t* p, const int32_t* j, const double* x,
+                         const double* ap_out, const double* ndcg_out) {
+  if (!ap_out && !ndcg_out) return fail(RSPARSE_HIP_ERR_INVALID, "ap_out and ndcg_out are both NULL");
+  if (!pred || !p || !j) return fail(RSPARSE_HIP_ERR_INVALID, "predictions or actual (p, j) is NULL");
+  if (ndcg_out && !x) return fail(RSPARSE_HIP_ERR_INVALID, "ndcg needs the relevances: actual_x is NULL");
+  if (n_users < 0 || k < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0 or k < 1)");
+  if (k > RSPARSE_HIP_MAX_TOPK_LARGE)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+
+int rsparse_hip_ranking_metrics_device(const int32_t* d_pred, int n_users, int k, const int32_t* d_p, const int32_t* d_j,
+                                       const double* d_x, double* d_ap_out, double* d_ndcg_out, void* stream) {
+  int rc = ranking_metrics_args(d_pred, n_users, k, d_p, d_j, d_x, d_ap_out, d_ndcg_out);
+  if (rc || n_users == 0) return rc;
+  if ((rc = g_ws.ensure_device())) return rc;
+  if ((rc = g_ws.ensure_met((size_t)n_users + 1))) return rc;
+  hipError_t e = launch_ranking_metrics(d_pred, n_users, k, d_p, d_j, d_ndcg_out ? d_x : nullptr, d_ap_out, d_ndcg_out,
+                                        g_ws.met_buf, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_ranking_metrics");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_ranking_metrics(const int32_t* pred, int n_users, int k, const int32_t* p, const int32_t* j, const double* x,
+                                double* ap_out, double* ndcg_out) {
+  int rc = ranking_metrics_args(pred, n_users, k, p, j, x, ap_out, ndcg_out);
+  if (rc) return rc;
+  // the dgRMatrix slots: p from 0, non-decreasing; j strictly ascending within a row (what the kernels' binary search needs)
+  if (p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "actual_p[0] != 0");
+  for (int u = 0; u < n_users; u++) {
+    if (p[u + 1] < p[u]) return fail(RSPARSE_HIP_ERR_INVALID, "actual_p decreases");
+    for (int32_t e = p[u] + 1; e < p[u + 1]; e++)
+      if (j[e] <= j[e - 1]) return fail(RSPARSE_HIP_ERR_INVALID, "actual_j is not strictly ascending within a row");
+  }
+  if (n_users == 0) return RSPARSE_HIP_OK;
+  const size_t nk = (size_t)n_users * k, nnz = (size_t)p[n_users];
+  std::vector<int32_t> rows(nk);   // column-major (R's integer matrix) -> the row-major lists of the device form
+  for (int c = 0; c < k; c++)
+    for (int u = 0; u < n_users; u++) rows[(size_t)u * k + c] = pred[(size_t)c * n_users + u];
+  DevBuf dPred, dP, dJ, dX, dAp, dNdcg;
+  HIP_TRY(dPred.alloc(nk * 4));
+  HIP_TRY(dP.alloc(((size_t)n_users + 1) * 4));
+  HIP_TRY(dJ.alloc(std::max<size_t>(nnz, 1) * 4));
+  if (ndcg_out) HIP_TRY(dX.alloc(std::max<size_t>(nnz, 1) * 8));
+  if (ap_out) HIP_TRY(dAp.alloc((size_t)n_users * 8));
+  if (ndcg_out) HIP_TRY(dNdcg.alloc((size_t)n_users * 8));
+  HIP_TRY(hipMemcpy(dPred.p, rows.data(), nk * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dP.p, p, ((size_t)n_users + 1) * 4, hipMemcpyHostToDevice));
+  if (nnz) HIP_TRY(hipMemcpy(dJ.p, j, nnz * 4, hipMemcpyHostToDevice));
+  if (nnz && ndcg_out) HIP_TRY(hipMemcpy(dX.p, x, nnz * 8, hipMemcpyHostToDevice));
+  rc = rsparse_hip_ranking_metrics_device(dPred.as<int32_t>(), n_users, k, dP.as<int32_t>(), dJ.as<int32_t>(),
+                                          ndcg_out ? dX.as<double>() : nullptr, ap_out ? dAp.as<double>() : nullptr,
+                                          ndcg_out ? dNdcg.as<double>() : nullptr, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if (ap_out) HIP_TRY(hipMemcpy(ap_out, dAp.p, (size_t)n_users * 8, hipMemcpyDeviceToHost));
+  if (ndcg_out) HIP_TRY(hipMemcpy(ndcg_out, dNdcg.p, (size_t)n_users * 8, hipMemcpyDeviceToHost));
   return RSPARSE_HIP_OK;
 }
 

@@ -330,6 +330,11 @@ hipError_t launch_top_product_large_f64(const float* U32, const float* V32, cons
                                         const int32_t* excl, int n_excl, double glob_mean, int32_t* res, double* scores,
                                         hipStream_t s, float* ws);
 
+// ranking metrics ap@k / ndcg@k of row-major 1-based lists (wrmf_metrics.hip).  X may be null when ndcg_out is; either output may
+// be null, not both.  long_buf: n_users + 1 ints of scratch (a count and the users whose idcg takes the long-row launch).
+hipError_t launch_ranking_metrics(const int32_t* pred, int n_users, int k, const int32_t* P, const int32_t* J, const double* X,
+                                  double* ap_out, double* ndcg_out, int* long_buf, hipStream_t s);
+
 // device helpers of the multi-GPU context (wrmf_ctx_kernels.hip / wrmf_ctx.cpp)
 hipError_t launch_ctx_accumulate(const float* Gpart, const double* sumsq, double* red, int k, hipStream_t s);
 hipError_t launch_ctx_put_absmax(const float* absmax, double* red, int k, hipStream_t s);

@@ -352,6 +352,23 @@ class HipBackend:
                 float(glob_mean), res[a0:].data_ptr(), sc[a0:].data_ptr(), self._stream()))
         return res, sc
 
+    def ranking_metrics(self, res, p, j, x, want_ap=True, want_ndcg=True):
+        """ap_k / ndcg_k (R/metrics.R:31-127) of the lists `res` (n x k int32 on the device, 1-based with NA_integer_, as
+        top_product returns them) against `actual` as CSR slots on the device (p, j int32 with j sorted within rows; x float64,
+        needed for ndcg only): (ap, ndcg), float64 vectors of n on the device, None for a metric not asked for."""
+        n, k = res.shape
+        ap = torch.empty(n, dtype=torch.float64, device=res.device) if want_ap else None
+        ndcg = torch.empty(n, dtype=torch.float64, device=res.device) if want_ndcg else None
+        if n == 0:
+            return ap, ndcg
+        if j.numel() == 0:   # (no stored entry at all: the library still wants non-NULL slots)
+            j = torch.zeros(1, dtype=torch.int32, device=res.device)
+            x = torch.zeros(1, dtype=torch.float64, device=res.device)
+        _lib.check(self.lib.rsparse_hip_ranking_metrics_device(
+            res.data_ptr(), n, k, p.data_ptr(), j.data_ptr(), x.data_ptr() if want_ndcg else None,
+            None if ap is None else ap.data_ptr(), None if ndcg is None else ndcg.data_ptr(), self._stream()))
+        return ap, ndcg
+
     def _v32(self, V):
         """the fp32 replica of a factor matrix the fp64 layer holds (kept until the matrix changes: ADVICE r04 -- `predict` of
         one user paid an n_item x rank conversion per call)"""

@@ -502,7 +502,19 @@ class WRMF:
         indices, 0-based, -1 where fewer than k items are admissible) with `.scores` (n x k).  k up to 256 runs the fused
         device path, 256 < k <= 8192 the large-k path (a radix select per user over the stored scores); a larger k raises
         UnsupportedOnDevice."""
-        import ctypes
+        res, sc, x = self._predict_device(x, k, not_recommend, items_exclude)
+        n_new = x.shape[0]
+        if self._dist()[0] > 1:
+            res, sc = self._share_rows(res, self._row_bounds, n_new), self._share_rows(sc, self._row_bounds, n_new)
+        idx = res.cpu().numpy().astype(np.int64)
+        idx = np.where(idx == -2147483648, -1, idx - 1)       # R is 1-based with NA_integer_
+        out = idx.view(TopItems)
+        out.scores = sc.cpu().numpy().astype(self._np_dtype())
+        return out
+
+    def _predict_device(self, x, k, not_recommend, items_exclude):
+        """the device part of `predict`: (indices int32, scores float64) of this rank's block of rows, _row_bounds[rank], still
+        on the device -- 1-based with NA_integer_ as top_product writes them --, and x as CSR"""
         if self._V is None:
             raise RuntimeError("model is not fitted")
         x = sp.csr_matrix(x, dtype=np.float64)
@@ -538,12 +550,34 @@ class WRMF:
         else:
             res = torch.empty((0, k), dtype=torch.int32, device=emb.device)
             sc = torch.empty((0, k), dtype=torch.float64, device=emb.device)
-        if ws > 1:
-            res, sc = self._share_rows(res, self._row_bounds, n_new), self._share_rows(sc, self._row_bounds, n_new)
-        idx = res.cpu().numpy().astype(np.int64)
-        idx = np.where(idx == -2147483648, -1, idx - 1)       # R is 1-based with NA_integer_
-        out = idx.view(TopItems)
-        out.scores = sc.cpu().numpy().astype(self._np_dtype())
+        return res, sc, x
+
+    def evaluate(self, x, actual, k, not_recommend="x", items_exclude=(), metrics=("ap", "ndcg")):
+        """`predict(x, k, ...)` scored against the held-out interactions `actual` (n x anything sparse, relevances as values) by
+        the reference's ap_k / ndcg_k (R/metrics.R:31-127) without the lists leaving the device: {name: float64 vector of n}
+        for each name in `metrics` ("ap", "ndcg").  Equals `rsparse_amd.metrics.ap_k(self.predict(x, k, ...), actual)` (and
+        ndcg_k) bit for bit.  Under torch.distributed every rank scores the block of rows it predicts."""
+        from .metrics import canonical_actual
+        metrics = tuple(metrics)
+        if not metrics or any(m not in ("ap", "ndcg") for m in metrics):
+            raise ValueError("metrics must name some of 'ap', 'ndcg'")
+        x = sp.csr_matrix(x, dtype=np.float64)
+        n_new = x.shape[0]
+        act = canonical_actual(actual, n_new)
+        res, _, x = self._predict_device(x, k, not_recommend, items_exclude)
+        ws, me = self._dist()
+        a, b = self._row_bounds[me]
+        mine = act[a:b]
+        be = self._backend()
+        want_ap, want_ndcg = "ap" in metrics, "ndcg" in metrics
+        ap, ndcg = be.ranking_metrics(res, be.to_device(mine.indptr, torch.int32), be.to_device(mine.indices, torch.int32),
+                                      be.to_device(mine.data, torch.float64), want_ap, want_ndcg)
+        out = {}
+        for name, v in (("ap", ap), ("ndcg", ndcg)):
+            if name in metrics:
+                if ws > 1:
+                    v = self._share_rows(v, self._row_bounds, n_new)
+                out[name] = v.cpu().numpy()
         return out
 
     def transform(self, x):
