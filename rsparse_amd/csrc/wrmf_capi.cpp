@@ -681,6 +681,7 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   for (int b = 0; b < 7; b++) qs.off[b] = d.q_off[b];
   // (the global-bias CG keeps bucket 1 on the 8-wave kernel: no 4-wave launch, no loss slots for one)
   qs.team4_first = (implicit && bias && bias->gbias != 0.f) ? d.q_off[2] : d.q_team4_first;
+  qs.pair_wide = cgp_wide_supported(rank, implicit, implicit && bias && bias->gbias != 0.f);
   // (two workgroups per CU only for implicit feedback at rank 97..128: the fp16 QUAD kernel of wrmf_ne.hip)
   const bool ne_fine = implicit && padded_rank(rank) == 128;
   qs.ne_rows = ne_fine ? d.q_ne_rows : d.q_ne1_rows; qs.ne_ptr = ne_fine ? d.q_ne_ptr : d.q_ne1_ptr;

@@ -1,4 +1,4 @@
-// CG half-iteration for the SHORTEST rows (1..16 non-zeros, and empty ones), two rows per wave (gfx950, wave64).
+// CG half-iteration for the SHORT rows (at most 16 or 32 non-zeros, and empty ones), two rows per wave (gfx950, wave64).
 //
 // Same arithmetic as als_cgq_kernel (wrmf_cgq.hip: cg_solver_implicit<T>, inst/include/wrmf_implicit.hpp:8-32, column loop
 // :160-283; with a global bias cg_solver_implicit_global_bias, :35-57).  Half of the rows of the <= 32 bucket of the bench
@@ -15,6 +15,13 @@
 // workgroup's EIGHT rows on the matrix cores (G as two fp16 terms in registers, the vectors published as two fp16 terms
 // through LDS, three products of order < 2: the DMF scheme of wrmf_cgq.hip with 8 instead of 4 live columns of the
 // 16-column tile).  Slots beyond a row's length read the all-zero row and carry c = 0.
+//
+// NQ = 16 (rows of 17..32 non-zeros, rank 128, no global bias): slot s = 2 q + (group & 1), q = 0..15 -> 32 non-zeros in 128
+// registers per lane.  G's fp16 terms then do not fit beside them and sit in LDS in fragment order (the DMF = 2 layout of
+// wrmf_cgq.hip: [wave][tile][k-step][term] x 1 KB, lane l's 16 bytes at l * 16, conflict-free), and the next pair's indices /
+// confidences are not prefetched into registers but copied by LDS-DMA into one of two LDS slots of the wave (one
+// global_load_lds_dword each for the 64 entries of the two rows), from which the row switch reads the indices and the sweeps
+// the confidences.
 #include "wrmf_internal.h"
 #include "wrmf_device.h"
 
@@ -64,31 +71,38 @@ __device__ __forceinline__ void p_split(const float x0, const float x1, unsigned
   lo = __builtin_bit_cast(unsigned, l);
 }
 
+template <int NQ>
 struct PairSmem {
   static constexpr int KP = 128, ps = KP + 8, os = KP + 4;
-  static constexpr size_t bytes = (size_t)2 * 8 * ps * 2 + (size_t)8 * os * 4 + (size_t)4 * 64 * 4 + 16;
+  static constexpr size_t gfrag = NQ == 16 ? (size_t)4 * 16 * 1024 : 0;   // G's fp16 fragments (NQ = 16)
+  static constexpr size_t nxt = NQ == 16 ? (size_t)4 * 2 * 2 * 64 * 4 : 0;   // NQ = 16: [wave][slot][index, value][64]
+  static constexpr size_t bytes = gfrag + (size_t)2 * 8 * ps * 2 + (size_t)8 * os * 4 + (size_t)4 * 8 * NQ * 4 + nxt + 16;
 };
 
 // KFULL (rank 128): unconditional vector loads and the warm start requested before them -- the first sweep's publish / dense
 // product run while the vectors are in flight and its quad pass takes them as they arrive (als_cgq_kernel's KFULL)
-template <bool GB, bool KFULL = false>
+template <bool GB, bool KFULL = false, int NQ = 8>
 __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_t* __restrict__ rows, int n_rows, int iters,
                                                         size_t loss_slot0) {
-  constexpr int KP = 128, RPN = 8, VW = 4, NV = 2, NQ = 8;
-  using SM = PairSmem;
+  constexpr int KP = 128, RPN = 8, VW = 4, NV = 2;
+  static_assert(NQ == 8 || (NQ == 16 && KFULL && !GB), "the 32-slot kernel: rank 128, no global bias");
+  constexpr bool GREG = NQ == 8;   // G's fp16 terms and the prefetched indices in registers (else in LDS)
+  using SM = PairSmem<NQ>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  _Float16* sPh = reinterpret_cast<_Float16*>(smem);            // [8][KP + 8] leading fp16 terms of the published vectors
+  char* sGf = smem + (size_t)(threadIdx.x >> 6) * 16 * 1024;     // NQ = 16: this wave's G fragments, [tile][step][term] x 1 KB
+  _Float16* sPh = reinterpret_cast<_Float16*>(smem + SM::gfrag); // [8][KP + 8] leading fp16 terms of the published vectors
   _Float16* sPl = sPh + 8 * SM::ps;                             // [8][KP + 8] second terms
   float* sOut = reinterpret_cast<float*>(sPl + 8 * SM::ps);     // [8][KP + 4] G v (times the scales)
-  float* sTsv = sOut + 8 * SM::os;                              // [4][2][32]  x_j . y accumulated / of the current step
+  float* sTsv = sOut + 8 * SM::os;                              // [4][2][2 NQ]  x_j . y accumulated / of the current step
+  float* sNx = sTsv + 4 * 8 * NQ + (threadIdx.x >> 6) * 256;     // NQ = 16: this wave's [2][index, value][64]
   const int tid = threadIdx.x, lane = tid & 63, wv = rfl(tid >> 6);
   const int g = lane >> 4, i = lane & 15, H = lane >> 5, g2 = g & 1;
   const int k = KFULL ? KP : a.k;
   const float gbias = GB ? a.gbias : 0.f, ltgt = GB ? a.loss_tgt_const : 1.f;
-  for (int e = tid; e < 4 * 64; e += 256) sTsv[e] = 0.f;
+  for (int e = tid; e < 4 * 8 * NQ; e += 256) sTsv[e] = 0.f;
   // this wave's 32 rows of G as A operands of v_mfma_f32_16x16x32_f16 (tile t = rows 32 wv + 16 t + (lane & 15), step ks =
   // columns 32 ks + 8 (lane >> 4) + 0..7), two fp16 terms of G * 2^ge; ginv = 2^-ge
-  f16x8 gAh[2][4], gAl[2][4];
+  f16x8 gAh[GREG ? 2 : 1][GREG ? 4 : 1], gAl[GREG ? 2 : 1][GREG ? 4 : 1];
   float ginv;
   {
     const int m = lane & 15, kb = lane >> 4;
@@ -126,13 +140,21 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
           p_split(g0 * gs, g1 * gs, hi[e / 2], lo[e / 2]);
         }
         const uint4 h4 = {hi[0], hi[1], hi[2], hi[3]}, l4 = {lo[0], lo[1], lo[2], lo[3]};
-        gAh[t][ks] = __builtin_bit_cast(f16x8, h4);
-        gAl[t][ks] = __builtin_bit_cast(f16x8, l4);
+        if constexpr (GREG) {
+          gAh[t][ks] = __builtin_bit_cast(f16x8, h4);
+          gAl[t][ks] = __builtin_bit_cast(f16x8, l4);
+        } else {
+          *reinterpret_cast<uint4*>(sGf + ((t * 4 + ks) * 2 + 0) * 1024 + lane * 16) = h4;
+          *reinterpret_cast<uint4*>(sGf + ((t * 4 + ks) * 2 + 1) * 1024 + lane * 16) = l4;
+        }
       }
   }
   __syncthreads();
-  float* tacc = sTsv + wv * 64 + 16 * H;   // this half's 16 slots: x_j . y accumulated over the CG steps
-  float* tcur = tacc + 32;                 // ... x_j . p of the current step
+  float* tacc = sTsv + wv * 8 * NQ + 2 * NQ * H;   // this half's 2 NQ slots: x_j . y accumulated over the CG steps
+  float* tcur = tacc + 4 * NQ;                     // ... x_j . p of the current step
+  // the slot whose x_j . y this lane holds for the loss: group 0 slots 0..15, with NQ = 16 group 1 slots 16..31
+  const int lslot = NQ == 16 ? i + 16 * g2 : i;
+  const bool lgrp = NQ == 16 || g2 == 0;
   const int col = 2 * wv + H;              // this half's column of the shared dense product
   double wloss = 0.0;
   const int wave_global = blockIdx.x * 4 + wv, total_waves = gridDim.x * 4;
@@ -148,16 +170,25 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
 
   // KFULL: the indices / values of a pair of rows are requested during the PREVIOUS pair's sweeps (the first pair's here): the
   // gather at the row switch is then one HBM round trip -- the vectors -- instead of two (what the one- and two-wave kernels of
-  // wrmf_cgq.hip have done since round 2; this kernel sits at 238 registers: 17 more).  All eight
+  // wrmf_cgq.hip have done since round 2; this kernel sits at 238 registers: 17 more).  All NQ
   // slots of a lane are requested whatever the rows' lengths (a slot outside its row reads entry 0 and is dropped).
-  int idn[NQ];
-  float cvn[NQ], cln = 0.f;
+  int idn[GREG ? NQ : 1];
+  float cvn[GREG ? NQ : 1], cln = 0.f;
 #pragma unroll
-  for (int q = 0; q < NQ; q++) {
+  for (int q = 0; q < (GREG ? NQ : 1); q++) {
     idn[q] = 0;
     cvn[q] = 0.f;
   }
-  auto request_indices = [&](const bool valid, const int np1, const int ncnt) {
+  // NQ = 16: lane l copies entry l & 31 of its half's row into slot `buf` (entries beyond the row: index 0, confidence 0)
+  auto request_indices = [&](const bool valid, const int np1, const int ncnt, const int buf) {
+    if constexpr (!GREG) {
+      const int e = lane & 31;
+      const bool in = valid && e < ncnt;
+      float* slot = sNx + buf * 128;
+      dma4(in ? static_cast<const void*>(a.row_idx + np1 + e) : static_cast<const void*>(a.zero_row), (unsigned)rfl((int)lds_addr(slot)));
+      dma4(in ? static_cast<const void*>(a.vals + np1 + e) : static_cast<const void*>(a.zero_row), (unsigned)rfl((int)lds_addr(slot + 64)));
+      return;
+    }
 #pragma unroll
     for (int q = 0; q < NQ; q++) {
       const int s = 2 * q + g2;
@@ -165,14 +196,22 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
       idn[q] = a.row_idx[j];
       cvn[q] = a.vals[j];
     }
-    cln = a.vals[(valid && i < ncnt) ? np1 + i : 0];
+    cln = a.vals[(valid && lslot < ncnt) ? np1 + lslot : 0];
   };
   auto settle_indices = [&]() {   // a use the compiler cannot move: the wait for the request sits HERE
-    asm volatile("" : "+v"(idn[0]), "+v"(idn[1]), "+v"(idn[2]), "+v"(idn[3]), "+v"(idn[4]), "+v"(idn[5]), "+v"(idn[6]), "+v"(idn[7]));
-    asm volatile("" : "+v"(cvn[0]), "+v"(cvn[1]), "+v"(cvn[2]), "+v"(cvn[3]), "+v"(cvn[4]), "+v"(cvn[5]), "+v"(cvn[6]), "+v"(cvn[7]), "+v"(cln));
+    if constexpr (!GREG) {
+      wait_vm0();
+      return;
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; q += 8) {
+      asm volatile("" : "+v"(idn[q]), "+v"(idn[q + 1]), "+v"(idn[q + 2]), "+v"(idn[q + 3]), "+v"(idn[q + 4]), "+v"(idn[q + 5]), "+v"(idn[q + 6]), "+v"(idn[q + 7]));
+      asm volatile("" : "+v"(cvn[q]), "+v"(cvn[q + 1]), "+v"(cvn[q + 2]), "+v"(cvn[q + 3]), "+v"(cvn[q + 4]), "+v"(cvn[q + 5]), "+v"(cvn[q + 6]), "+v"(cvn[q + 7]));
+    }
+    asm volatile("" : "+v"(cln));
   };
   if constexpr (KFULL) {
-    request_indices(iters > 0 && ridx(0) < n_rows, p1_c, p2_c - p1_c);
+    request_indices(iters > 0 && ridx(0) < n_rows, p1_c, p2_c - p1_c, 0);
     settle_indices();   // (once per wave: the first pair pays the round trip)
   }
 
@@ -191,14 +230,16 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
       p2_c = p2_n;
       row_n = row_nn;
     }
-    const int cnt = p2 - p1;   // 0..16 (launcher)
+    const int cnt = p2 - p1;   // 0..2 NQ (launcher)
     float* yrow = a.Y + (size_t)row * k;
     const bool live = have && (GB || cnt > 0);
     if (have && !live) {  // empty column -> zeros (wrmf_implicit.hpp:281); the 32 lanes of the half write it
       for (int e = lane & 31; e < k; e += 32) yrow[e] = 0.f;
     }
-    // does any of the wave's two rows reach the second block of slots (8..15)?  (wave-uniform)
-    const bool blk2 = max(__builtin_amdgcn_readlane(cnt, 0), __builtin_amdgcn_readlane(cnt, 32)) > 8;
+    // the longer of the wave's two rows (wave-uniform): block b of four quads (slots 8 b .. 8 b + 7) is touched only when it
+    // reaches the block; the first block always is
+    const int wcnt = max(__builtin_amdgcn_readlane(cnt, 0), __builtin_amdgcn_readlane(cnt, 32));
+    auto blk_on = [&](const int q) { return q < 4 || wcnt > 2 * (q & ~3); };
 
     float x[RPN], r[RPN], p[RPN], ap[RPN];
     auto load_warm_start = [&]() {
@@ -214,7 +255,8 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
     };
     if constexpr (KFULL) load_warm_start();
     // ---- gather: all index loads, then all vector loads; slots beyond the row read the zero row and carry c = 0 ----
-    float xt[NQ][RPN], cv[NQ];
+    float xt[NQ][RPN], cv[GREG ? NQ : 1];
+    const float* nx = sNx + (it & 1) * 128 + 32 * H;   // NQ = 16: this half's indices (nx[s]) / confidences (nx[64 + s])
     {
       // (the loads WITHOUT a per-lane predicate: `in ? load : 0` compiles to a branch per slot with the address arithmetic of
       //  the vector load -- and its wait for the index -- inside: up to eight index round trips one after the other per pair of
@@ -222,7 +264,9 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
       int id[NQ];
 #pragma unroll
       for (int q = 0; q < NQ; q++) {
-        if constexpr (KFULL) {
+        if constexpr (!GREG) {
+          id[q] = __float_as_int(nx[2 * q + g2]);
+        } else if constexpr (KFULL) {
           id[q] = idn[q];
           cv[q] = cvn[q];
         } else {
@@ -230,7 +274,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
           const int j = s < cnt ? p1 + s : 0;
           id[q] = 0;
           cv[q] = 0.f;
-          if (q < 4 || blk2) {   // wave-uniform
+          if (blk_on(q)) {   // wave-uniform
             id[q] = a.row_idx[j];
             cv[q] = a.vals[j];
           }
@@ -240,7 +284,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
       for (int q = 0; q < NQ; q++) {
         const bool in = 2 * q + g2 < cnt;
         id[q] = in ? id[q] : 0;
-        cv[q] = in ? cv[q] : 0.f;
+        if constexpr (GREG) cv[q] = in ? cv[q] : 0.f;
       }
 #pragma unroll
       for (int q = 0; q < NQ; q++) {
@@ -253,13 +297,13 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
             // the first block without a branch; the second only when one of the wave's two rows reaches it (half of the rows of
             // this launch have at most 8 non-zeros: gathering the zero row for them cost 0.4 ms of the launch's 5.7)
             float4 pc = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (q < 4 || blk2) pc = *reinterpret_cast<const float4*>(src + off);
+            if (blk_on(q)) pc = *reinterpret_cast<const float4*>(src + off);
             const float* pf = reinterpret_cast<const float*>(&pc);
 #pragma unroll
             for (int c = 0; c < VW; c++) xt[q][b * VW + c] = pf[c];
           } else {
             float4 pc = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (q < 4 || blk2) pc = *reinterpret_cast<const float4*>(src + min(off, k - VW));
+            if (blk_on(q)) pc = *reinterpret_cast<const float4*>(src + min(off, k - VW));
             const float* pf = reinterpret_cast<const float*>(&pc);
 #pragma unroll
             for (int c = 0; c < VW; c++) xt[q][b * VW + c] = off < k ? pf[c] : 0.f;
@@ -267,10 +311,11 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
         }
       }
     }
-    // confidence of non-zero i of the half's row (loss)
+    // confidence of non-zero lslot of the half's row (loss)
     float cl;
-    if constexpr (KFULL) cl = (g2 == 0 && i < cnt) ? cln : 0.f;
-    else cl = (g2 == 0 && i < cnt) ? a.vals[p1 + i] : 0.f;
+    if constexpr (!GREG) cl = nx[64 + lslot];   // (0 beyond the row)
+    else if constexpr (KFULL) cl = (lgrp && lslot < cnt) ? cln : 0.f;
+    else cl = (lgrp && lslot < cnt) ? a.vals[p1 + lslot] : 0.f;
 
     if constexpr (!KFULL) load_warm_start();
 
@@ -312,9 +357,17 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
           const f16x8 bl = *reinterpret_cast<const f16x8*>(sPl + nb + 32 * ks);
 #pragma unroll
           for (int t = 0; t < 2; t++) {
-            d0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(gAh[t][ks], bh, d0[t], 0, 0, 0);
-            d1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(gAh[t][ks], bl, d1[t], 0, 0, 0);
-            d1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(gAl[t][ks], bh, d1[t], 0, 0, 0);
+            f16x8 ah, al;
+            if constexpr (GREG) {
+              ah = gAh[t][ks];
+              al = gAl[t][ks];
+            } else {
+              ah = *reinterpret_cast<const f16x8*>(sGf + ((t * 4 + ks) * 2 + 0) * 1024 + lane * 16);
+              al = *reinterpret_cast<const f16x8*>(sGf + ((t * 4 + ks) * 2 + 1) * 1024 + lane * 16);
+            }
+            d0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, d0[t], 0, 0, 0);
+            d1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, d1[t], 0, 0, 0);
+            d1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, d1[t], 0, 0, 0);
           }
         }
         if ((lane & 15) < 8) {   // D: column = lane & 15, rows 4 (lane >> 4) + 0..3 of the tile
@@ -330,7 +383,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
         float* trec = (mode == 0 ? tacc : tcur) + g2;   // slot 2 q + g2 <- t (the 16 lanes of the group write the same value)
 #pragma unroll
         for (int q0 = 0; q0 < NQ; q0 += 4) {
-          if (q0 == 0 || blk2) {   // wave-uniform
+          if (blk_on(q0)) {   // wave-uniform
             // (the four quads' dot chains and DPP reductions interleaved: see quad_pass in wrmf_cgq.hip)
             float t[4];
             f32x2 s2[4];
@@ -358,7 +411,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
 #pragma unroll
             for (int u = 0; u < 4; u++) {
               const int q = q0 + u;
-              const float c = cv[q];
+              const float c = GREG ? cv[q] : nx[64 + 2 * q + g2];
               trec[2 * q] = t[u];
               const float w = mode == 0 ? c - (c - 1.f) * (GB ? t[u] + gbias : t[u]) : (c - 1.f) * t[u];
 #pragma unroll
@@ -369,9 +422,9 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
       } else {
         // loss from t_acc = X_nnz^T y built up by the sweeps (the vectors are not touched again)
         wave_sync();
-        const float t = tacc[i];
+        const float t = tacc[lslot];
         const float dd = ltgt - t;
-        lacc = p_pair_sum(p_row16_sum((g2 == 0 && i < cnt) ? cl * dd * dd : 0.f));
+        lacc = p_pair_sum(p_row16_sum((lgrp && lslot < cnt) ? cl * dd * dd : 0.f));
       }
       if (mode != 2) {
         // (3) the products are complete: fold this row's G v into group 0's partial sums, then reduce the two groups
@@ -411,7 +464,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
     float dummy = 0.f;
     sweep(x, 0, r, dummy);
     if constexpr (KFULL)   // (p1_c / p2_c are the next pair's since the top of this iteration)
-      request_indices(it + 1 < iters && ridx(it + 1) < n_rows, p1_c, p2_c - p1_c);
+      request_indices(it + 1 < iters && ridx(it + 1) < n_rows, p1_c, p2_c - p1_c, (it + 1) & 1);
 #pragma unroll
     for (int rr = 0; rr < RPN; rr++) p[rr] = r[rr];
     float rsold = dot16(r, r);
@@ -422,7 +475,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
       // rsold / alpha / beta as the reference holds them: double scalars fed by T-valued dot products (wrmf_implicit.hpp:18-27)
       const float alpha = conv ? 0.f : (float)((double)rsold / (double)pap);
       wave_sync();
-      if (g2 == 0) tacc[i] = fmaf(alpha, tcur[i], tacc[i]);   // X_nnz^T x += alpha X_nnz^T p
+      if (lgrp) tacc[lslot] = fmaf(alpha, tcur[lslot], tacc[lslot]);   // X_nnz^T x += alpha X_nnz^T p
       wave_sync();
 #pragma unroll
       for (int rr = 0; rr < RPN; rr++) {
@@ -473,6 +526,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
 }  // namespace
 
 bool cgp_supported(int k, bool implicit) { return implicit && k > 64 && k <= 128 && k % 4 == 0; }
+bool cgp_wide_supported(int k, bool implicit, bool gbias) { return implicit && k == 128 && !gbias; }
 
 // grid (workgroups of 4 waves x 2 rows) for n_rows rows: about 32 pairs per wave, small sets spread over the CUs first
 int cgp_grid(int n_rows) {
@@ -486,25 +540,31 @@ int cgp_grid(int n_rows) {
 }
 
 // rows: n_rows row ids, each with at most 16 non-zeros (empty ones included), rank 65..128 (multiple of 4), implicit feedback;
+// wide: the rows have 17..32 non-zeros instead (rank 128, no global bias: cgp_wide_supported);
 // loss partials: cgp_grid(n_rows) * 4 slots from loss_slot0 on
-hipError_t launch_als_cgp(const AlsArgs& a, const int32_t* rows, int n_rows, size_t loss_slot0, hipStream_t s,
+hipError_t launch_als_cgp(const AlsArgs& a, const int32_t* rows, int n_rows, bool wide, size_t loss_slot0, hipStream_t s,
                           hipEvent_t* ev_slot) {
   const int grid = cgp_grid(n_rows);
   if (grid <= 0) return hipSuccess;
   const long pairs = ((long)n_rows + 1) / 2;
   const int iters = (int)((pairs + (long)grid * 4 - 1) / ((long)grid * 4));
   const bool gb = a.gbias != 0.f;
+  const bool full = !gb && a.k == 128;
+  if (wide && !full) return hipErrorInvalidValue;
   auto k0 = als_cgp_kernel<false, false>;
   auto k0f = als_cgp_kernel<false, true>;
   auto k1 = als_cgp_kernel<true, false>;
-  const bool full = !gb && a.k == 128;
-  const void* fn = gb ? reinterpret_cast<const void*>(k1) : (full ? reinterpret_cast<const void*>(k0f) : reinterpret_cast<const void*>(k0));
-  hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PairSmem::bytes);
+  auto kw = als_cgp_kernel<false, true, 16>;
+  const void* fn = wide ? reinterpret_cast<const void*>(kw)
+                        : gb ? reinterpret_cast<const void*>(k1) : (full ? reinterpret_cast<const void*>(k0f) : reinterpret_cast<const void*>(k0));
+  const size_t lds = wide ? PairSmem<16>::bytes : PairSmem<8>::bytes;
+  hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (err != hipSuccess) return err;
-  (void)ev_slot;   // (the bucket's segment is named after its main kernel)
-  if (gb) hipLaunchKernelGGL(k1, dim3(grid), dim3(256), PairSmem::bytes, s, a, rows, n_rows, iters, loss_slot0);
-  else if (full) hipLaunchKernelGGL(k0f, dim3(grid), dim3(256), PairSmem::bytes, s, a, rows, n_rows, iters, loss_slot0);
-  else hipLaunchKernelGGL(k0, dim3(grid), dim3(256), PairSmem::bytes, s, a, rows, n_rows, iters, loss_slot0);
+  prof_note(ev_slot, fn);   // (names the bucket's segment when this is its first launch)
+  if (wide) hipLaunchKernelGGL(kw, dim3(grid), dim3(256), lds, s, a, rows, n_rows, iters, loss_slot0);
+  else if (gb) hipLaunchKernelGGL(k1, dim3(grid), dim3(256), lds, s, a, rows, n_rows, iters, loss_slot0);
+  else if (full) hipLaunchKernelGGL(k0f, dim3(grid), dim3(256), lds, s, a, rows, n_rows, iters, loss_slot0);
+  else hipLaunchKernelGGL(k0, dim3(grid), dim3(256), lds, s, a, rows, n_rows, iters, loss_slot0);
   return hipGetLastError();
 }
 

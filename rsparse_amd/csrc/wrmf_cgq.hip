@@ -147,17 +147,6 @@ __device__ __forceinline__ float row16_max(float v) {
   return v;
 }
 
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(reinterpret_cast<uintptr_t>(p));  // low 32 bits of a generic LDS pointer = LDS byte address
-}
-// LDS-DMA, one dword per lane: LDS destination = M0 + lane * 4 (wave-uniform base), source = each lane's own pointer.  Counts in
-// vmcnt like a load; the compiler does not know about it, which is harmless as long as nothing is issued between it and
-// the explicit wait that precedes the first read of its destination (older operations complete first)
-__device__ __forceinline__ void dma4(const void* g, unsigned lds_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" : : "v"(g), "s"(lds_base) : "memory", "m0");
-}
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
 // DMF: 0 = dense product on the vector units (G in LDS as fp32), 1 = on the matrix cores with this wave's rows of G as fp16
 // terms in REGISTERS (rows <= 32 non-zeros: 64 registers are free), 2 = the same with the fp16 terms in LDS, stored in
 // fragment order (rows of 33..64 non-zeros: the gathered vectors take 128 registers, G's 64 KB of LDS hold the terms instead
@@ -1124,7 +1113,8 @@ hipError_t launch_bucket(const AlsArgs& a, const int32_t* rows, int n_rows, int 
     return launch_bucket<KP, WAVES, CAPQ, WPR, STREAM, IMPLICIT, GB, CAPQ == 8 ? 1 : 2>(a, rows, n_rows, grid, slot0, s, ev_slot);
   } else {
     // the rank is the padded rank (32 / 64 / 128): the instantiation whose first sweep runs behind the gather
-    if constexpr (!KFULL && STREAM == 0) {
+    // (not for the one-wave rows of <= 32 non-zeros without a global bias: at rank 128 those run two per wave, wrmf_cgp.hip)
+    if constexpr (!KFULL && STREAM == 0 && !(DMF == 1 && !GB)) {
       if (a.k == KP)
         return launch_bucket<KP, WAVES, CAPQ, WPR, STREAM, IMPLICIT, GB, DMF, true>(a, rows, n_rows, grid, slot0, s, ev_slot);
     }
@@ -1185,7 +1175,8 @@ size_t bucket_slots(const QSchedule& q, int b, int k, bool implicit) {
   }
   if (b == kNB - 1 && rows > 0 && cgp_supported(k, implicit)) {
     const int split = std::min(std::max(q.pair_first, q.off[b]), q.off[b + 1]);
-    return (size_t)cgq_bucket_grid(split - q.off[b], b, cfg) * d.waves + (size_t)cgp_grid(q.off[b + 1] - split) * 4;
+    const size_t main = q.pair_wide ? (size_t)cgp_grid(split - q.off[b]) * 4 : (size_t)cgq_bucket_grid(split - q.off[b], b, cfg) * d.waves;
+    return main + (size_t)cgp_grid(q.off[b + 1] - split) * 4;
   }
   return (size_t)cgq_bucket_grid(rows, b, cfg) * d.waves;
 }
@@ -1259,14 +1250,23 @@ hipError_t launch_all(const AlsArgs& a, const QSchedule& q, hipStream_t s, hipEv
                    n_main > 0 ? nullptr : (ev ? ev + B : nullptr))) != hipSuccess)                          \
             return err;                                                                                     \
         } else if (B == kNB - 1 && cgp_supported(a.k, IMPLICIT)) {                    \
-          /* the last bucket in two launches: rows of 17..32 non-zeros one per wave, the rest two per wave (wrmf_cgp.hip) */ \
+          /* the last bucket in two launches: rows of 17..32 non-zeros two per wave in 32 slots (q.pair_wide) or one per */ \
+          /* wave, the rest two per wave in 16 slots (wrmf_cgp.hip) */                                       \
           const int first = q.off[B], split = std::min(std::max(q.pair_first, first), q.off[B + 1]);         \
           const int n_main = split - first, n_pair = q.off[B + 1] - split;                                   \
-          const int g_main = cgq_bucket_grid(n_main, B, CFG);                                                \
-          if ((err = launch_bucket<KP, D.waves, D.capq, D.wpr, D.stream, IMPLICIT, GB>(a, q.order + first, n_main, g_main, slot, \
-                                                                                  bs, ev ? ev + B : nullptr)) != hipSuccess) \
-            return err;                                                                                     \
-          if ((err = launch_als_cgp(a, q.order + split, n_pair, slot + (size_t)g_main * D.waves, bs,          \
+          size_t main_slots;                                                                                \
+          if (q.pair_wide) {                                                                                \
+            if ((err = launch_als_cgp(a, q.order + first, n_main, true, slot, bs, ev ? ev + B : nullptr)) != hipSuccess) \
+              return err;                                                                                   \
+            main_slots = (size_t)cgp_grid(n_main) * 4;                                                      \
+          } else {                                                                                          \
+            const int g_main = cgq_bucket_grid(n_main, B, CFG);                                             \
+            if ((err = launch_bucket<KP, D.waves, D.capq, D.wpr, D.stream, IMPLICIT, GB>(a, q.order + first, n_main, g_main, slot, \
+                                                                                    bs, ev ? ev + B : nullptr)) != hipSuccess) \
+              return err;                                                                                   \
+            main_slots = (size_t)g_main * D.waves;                                                          \
+          }                                                                                                 \
+          if ((err = launch_als_cgp(a, q.order + split, n_pair, false, slot + main_slots, bs,               \
                                     n_main > 0 ? nullptr : (ev ? ev + B : nullptr))) != hipSuccess)           \
             return err;                                                                                     \
         } else if ((err = launch_bucket<KP, D.waves, D.capq, D.wpr, D.stream, IMPLICIT, GB>(a, q.order + q.off[B], n, grid, slot, \

@@ -149,6 +149,7 @@ struct QSchedule {
   int off[7];
   int pair_first;   // see DevCSC::q_pair_first
   int team4_first;  // see DevCSC::q_team4_first; = off[2] when bucket 1 runs on the 8-wave kernel alone (global bias)
+  bool pair_wide;   // the last bucket's rows of 17..32 non-zeros two per wave as well (cgp_wide_supported), else one per wave
   int cfg;  // geometry the schedule was built for (see wrmf_cgq.hip kBuckets)
   const int32_t* ne_rows;  // see DevCSC::q_ne_*
   const int32_t* ne_ptr;
@@ -173,10 +174,12 @@ constexpr int kTeam4Max = 320;
 int cgq_team4_grid(int n_rows);
 int cgq_bucket_of(int len, int cfg);
 size_t cgq_loss_slots(const QSchedule& q, int k, bool implicit);
-// the rows of at most 16 non-zeros of the last bucket, two per wave (wrmf_cgp.hip): rank 65..128, implicit feedback
+// the rows of at most 16 non-zeros of the last bucket, two per wave (wrmf_cgp.hip): rank 65..128, implicit feedback;
+// its rows of 17..32 non-zeros too ("wide") at rank 128 without a global bias
 bool cgp_supported(int k, bool implicit);
+bool cgp_wide_supported(int k, bool implicit, bool gbias);
 int cgp_grid(int n_rows);
-hipError_t launch_als_cgp(const AlsArgs& a, const int32_t* rows, int n_rows, size_t loss_slot0, hipStream_t s,
+hipError_t launch_als_cgp(const AlsArgs& a, const int32_t* rows, int n_rows, bool wide, size_t loss_slot0, hipStream_t s,
                           hipEvent_t* ev_slot);
 // long rows (bucket 0) by one-pass normal equations on the matrix cores (wrmf_ne.hip) instead of the streamed CG kernel
 bool ne_supported(int k);

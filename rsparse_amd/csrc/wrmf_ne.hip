@@ -216,18 +216,10 @@ struct NeGeo {
   __host__ __device__ static constexpr int tile(int R, int C) { return R * (R + 1) / 2 + C; }
 };
 
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(reinterpret_cast<uintptr_t>(p));  // low 32 bits of a generic LDS pointer = LDS byte address
-}
-
 // ---- LDS-DMA, issued from asm so that the loop's s_waitcnt can be counted (see the header) ----
 // One 16-byte piece per lane: LDS destination = M0 + lane * 16 (wave-uniform base), source = each lane's own pointer.
 __device__ __forceinline__ void dma16(const void* g, unsigned lds_base) {
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(g), "s"(lds_base) : "memory", "m0");
-}
-// One dword per lane: LDS destination = M0 + lane * 4.
-__device__ __forceinline__ void dma4(const void* g, unsigned lds_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" : : "v"(g), "s"(lds_base) : "memory", "m0");
 }
 template <int N>
 __device__ __forceinline__ void wait_vm() {
