@@ -361,6 +361,53 @@ int rsparse_hip_top_product_f64_device(const float* d_U, const float* d_V, const
                                        double* d_scores, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * `$get_similar_items`: item-to-item cosine top-k (R/MatrixFactorizationRecommender.R:79-116)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The reference normalises the item embeddings once (L2 norm of every item's vector) and answers one item at a time with a
+ * product against all of them.  Here: the normalised matrix is prepared once per model (rsparse_hip_normalize_items*_device),
+ * and a batch of query items is ONE call of the `$predict` path above against it -- cosine(i, j) is the dot product of two unit
+ * vectors, so fp32 nomination, re-scoring and ordering in double, the tie rule (larger index first) and both k ranges are
+ * rsparse_hip_top_product_f64_device's, unchanged.
+ *
+ * rsparse_hip_normalize_items_device (fp32 factors) / rsparse_hip_normalize_items_f64_device (fp64 factors): d_V is
+ * n_items x ld row-major (= ld x n_items column-major); the columns [c0, c1) are the latent coordinates (a model with user/item
+ * biases keeps the item bias and the constant one outside the window), r = c1 - c0.  Per item the sum of squares over the window
+ * is accumulated in double whatever the input type; d_Vn64 (n_items x r doubles, compact) = V[item, c0:c1] / sqrt(sum),
+ * d_Vn32 = (float)d_Vn64, d_flags[item] = 0.  An item whose sum of squares is zero or not finite is DEGENERATE: its rows are
+ * written as zeros and d_flags[item] = 1 (items without interactions keep zero factors under the conjugate-gradient solver, so
+ * this is an ordinary case).  One streaming launch on `stream`: 4 r or 8 r bytes read, 12 r written per item.
+ * not 0 <= c0 < c1 <= ld, n_items < 0, NULL where needed -> ERR_INVALID; r > RSPARSE_HIP_MAX_RANK -> ERR_UNSUPPORTED. */
+int rsparse_hip_normalize_items_device(const float* d_V, int n_items, int ld, int c0, int c1, float* d_Vn32, double* d_Vn64,
+                                       int32_t* d_flags, void* stream);
+int rsparse_hip_normalize_items_f64_device(const double* d_V, int n_items, int ld, int c0, int c1, float* d_Vn32,
+                                           double* d_Vn64, int32_t* d_flags, void* stream);
+
+/* The k most similar items of n_q query items.  d_Vn32 / d_Vn64: the prepared operands (n_items x r); d_query: 0-based item ids
+ * (repeats allowed); exclude_self != 0 removes every query from its own list; d_exclude0: sorted 0-based ids that are never
+ * returned -- the caller puts the degenerate items there (the non-zeros of d_flags) next to its own exclusions.
+ * d_res (n_q x k row-major, 1-based, NA_integer_ where fewer than k items are admissible) and d_scores (n_q x k doubles, the
+ * cosines, best first, NaN beside NA_integer_).  A query that is degenerate (its row of d_Vn64 is all zeros) or out of range
+ * gets a row of NA_integer_ / NaN; nothing is read out of bounds for it.  Asynchronous on `stream`.
+ * Workspace (grow-only): the queries are scored in batches of 262144 (fewer above k = 256: the same rule as the callers of
+ * rsparse_hip_top_product_f64_device use, so its workspace bounds above hold), and a batch keeps its gathered operands and
+ * self-exclusion slots, min(n_q, batch) x (12 r + 12) bytes: 406 MB for a full batch at r = 128.
+ * NULL where needed, n_items < 0, n_q < 0, k < 1, r < 1, n_exclude < 0 -> ERR_INVALID; r > RSPARSE_HIP_MAX_RANK or
+ * k > RSPARSE_HIP_MAX_TOPK_LARGE -> ERR_UNSUPPORTED. */
+int rsparse_hip_similar_items_device(const float* d_Vn32, const double* d_Vn64, int n_items, int r, const int32_t* d_query,
+                                     int n_q, int k, int exclude_self, const int32_t* d_exclude0, int n_exclude,
+                                     int32_t* d_res, double* d_scores, void* stream);
+
+/* host form: components as R holds it (rank x n_items column-major doubles); the latent rows are first_row (0-based) ..
+ * first_row + n_rows - 1 (all of them: 0, rank; a model with user/item biases: 1, rank - 2).  query (n_q) and exclude
+ * (n_exclude; out-of-range entries are ignored, as rsparse_hip_top_product does) are 1-based item indices; res / scores are
+ * n_q x k column-major like rsparse_hip_top_product's.  Degenerate items are excluded by the call itself.  A query id outside
+ * 1..n_items, or first_row / n_rows outside components -> ERR_INVALID (before a device is touched, like every check above). */
+int rsparse_hip_similar_items(const double* components, int rank, int n_items, int first_row, int n_rows, const int32_t* query,
+                              int n_q, int k, int exclude_self, const int32_t* exclude, int n_exclude, int32_t* res,
+                              double* scores);
+
+/* ------------------------------------------------------------------------------------------------
  * ranking metrics of the `$predict` lists: ap_k() / ndcg_k() (R/metrics.R:31-127, NAMESPACE)
  * ---------------------------------------------------------------------------------------------- */
 

@@ -68,6 +68,10 @@ SIGNATURES = {
     "rsparse_hip_top_product_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_dbl, _vp, _vp, _vp]),
     "rsparse_hip_top_product_f64_device": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp,
                                                     _c_int, _c_dbl, _vp, _vp, _vp]),
+    "rsparse_hip_normalize_items_device": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_normalize_items_f64_device": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_similar_items_device": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp]),
+    "rsparse_hip_similar_items": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp]),
     "rsparse_hip_ranking_metrics": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
     "rsparse_hip_ranking_metrics_device": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rsparse_hip_csc_f64_create_device": (_c_int, [_c_int, _c_int, _vp, _vp, _vp, ctypes.POINTER(_vp)]),

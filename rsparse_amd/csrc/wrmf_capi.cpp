@@ -73,6 +73,8 @@ struct Workspace {
   size_t wide_lu_floats = 0;
   int* met_buf = nullptr;      // ranking metrics (wrmf_metrics.hip): count + list of the users whose idcg takes the long-row launch
   size_t met_ints = 0;
+  void* sim_buf = nullptr;     // item-to-item similarity (wrmf_similar.hip): a batch's gathered queries and self-exclusion slots
+  size_t sim_bytes = 0;
   int device = -1;
 
   int ensure_device() {
@@ -213,7 +215,19 @@ struct Workspace {
     }
     return RSPARSE_HIP_OK;
   }
+  int ensure_sim(size_t bytes) {
+    if (bytes > sim_bytes) {
+      if (sim_buf) (void)hipFree(sim_buf);
+      sim_buf = nullptr;
+      sim_bytes = 0;
+      HIP_TRY(hipMalloc(&sim_buf, bytes));
+      sim_bytes = bytes;
+    }
+    return RSPARSE_HIP_OK;
+  }
   void release() {
+    if (sim_buf) (void)hipFree(sim_buf);
+    sim_buf = nullptr; sim_bytes = 0;
     if (met_buf) (void)hipFree(met_buf);
     met_buf = nullptr; met_ints = 0;
     if (wide_m2) (void)hipFree(wide_m2);
@@ -1748,6 +1762,129 @@ int rsparse_hip_top_product(const double* x, const double* y, int nr, int nc, in
     for (unsigned c = 0; c < k; c++) {
       res[(size_t)c * nr + j] = hr[(size_t)j * k + c];
       scores[(size_t)c * nr + j] = hs[(size_t)j * k + c];
+    }
+  return RSPARSE_HIP_OK;
+}
+
+namespace {
+// the arguments every form of the item-to-item similarity checks before a device is touched
+int similar_items_args(int n_items, int r, int n_q, int k, int n_exclude, const void* exclude) {
+  if (n_items < 0 || n_q < 0 || k < 1 || r < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_items < 0, n_q < 0, k < 1 or no latent coordinate)");
+  if (n_exclude < 0 || (n_exclude > 0 && !exclude)) return fail(RSPARSE_HIP_ERR_INVALID, "bad exclude");
+  if (r > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 256 latent coordinates are not on the device path");
+  if (k > RSPARSE_HIP_MAX_TOPK_LARGE) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
+  return RSPARSE_HIP_OK;
+}
+int normalize_items_args(const void* d_V, int n_items, int ld, int c0, int c1, const void* d_Vn32, const void* d_Vn64,
+                         const void* d_flags) {
+  if (n_items < 0 || c0 < 0 || c1 - c0 < 1 || c1 > ld) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_items < 0 or not 0 <= c0 < c1 <= ld)");
+  if (c1 - c0 > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 256 latent coordinates are not on the device path");
+  if (n_items > 0 && (!d_V || !d_Vn32 || !d_Vn64 || !d_flags)) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
+  return RSPARSE_HIP_OK;
+}
+// rows of queries per call of the top-k path: what HipBackend.top_product uses (the same re-scoring budget above k = 256)
+int similar_items_batch(int k) {
+  int64_t B = 1 << 18;
+  if (k > RSPARSE_HIP_MAX_TOPK) {
+    const int64_t kc = k + std::max(8, k / 4);
+    B = std::max<int64_t>(1, std::min<int64_t>(B, B * (2 * 320 + 2 * 256 + 1) / (2 * kc + 2 * (int64_t)k + 1)));
+  }
+  return (int)B;
+}
+}  // namespace
+
+int rsparse_hip_normalize_items_device(const float* d_V, int n_items, int ld, int c0, int c1, float* d_Vn32, double* d_Vn64,
+                                       int32_t* d_flags, void* stream) {
+  int rc = normalize_items_args(d_V, n_items, ld, c0, c1, d_Vn32, d_Vn64, d_flags);
+  if (rc || n_items == 0) return rc;
+  hipError_t e = launch_normalize_items(d_V, false, n_items, ld, c0, c1 - c0, d_Vn32, d_Vn64, d_flags, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_normalize_items");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_similar_items_device(const float* d_Vn32, const double* d_Vn64, int n_items, int r, const int32_t* d_query,
+                                     int n_q, int k, int exclude_self, const int32_t* d_exclude0, int n_exclude,
+                                     int32_t* d_res, double* d_scores, void* stream) {
+  int rc = similar_items_args(n_items, r, n_q, k, n_exclude, d_exclude0);
+  if (rc) return rc;
+  if (n_q > 0 && (!d_query || !d_res || !d_scores)) return fail(RSPARSE_HIP_ERR_INVALID, "NULL query or output");
+  if (n_items > 0 && (!d_Vn32 || !d_Vn64)) return fail(RSPARSE_HIP_ERR_INVALID, "NULL normalised factors");
+  if (n_q == 0) return RSPARSE_HIP_OK;
+  if ((rc = g_ws.ensure_device())) return rc;
+  const int B = similar_items_batch(k);
+  if ((rc = g_ws.ensure_sim(similar_query_ws_bytes(std::min(n_q, B), r)))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  for (int a0 = 0; a0 < n_q; a0 += B) {   // (batches reuse the workspace: they are ordered on the stream)
+    const int nb = std::min(B, n_q - a0);
+    const SimilarQueryWs w = similar_query_ws(g_ws.sim_buf, nb, r);
+    hipError_t e = launch_gather_queries(d_Vn32, d_Vn64, n_items, r, d_query + a0, nb, w, s);
+    if (e != hipSuccess) return hip_fail(e, "launch_gather_queries");
+    int32_t* res = d_res + (size_t)a0 * k;
+    double* sc = d_scores + (size_t)a0 * k;
+    rc = rsparse_hip_top_product_f64_device(w.Q32, d_Vn32, w.Q64, d_Vn64, nb, n_items, r, k, -1, exclude_self ? w.nr_p : nullptr,
+                                            exclude_self ? w.nr_j : nullptr, d_exclude0, n_exclude, 0.0, res, sc, stream);
+    if (rc) return rc;
+    if ((e = launch_mask_queries(w.bad, nb, k, res, sc, s)) != hipSuccess) return hip_fail(e, "launch_mask_queries");
+  }
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_similar_items(const double* components, int rank, int n_items, int first_row, int n_rows, const int32_t* query,
+                              int n_q, int k, int exclude_self, const int32_t* exclude, int n_exclude, int32_t* res,
+                              double* scores) {
+  int rc = similar_items_args(n_items, n_rows, n_q, k, n_exclude, exclude);
+  if (rc) return rc;
+  if (first_row < 0 || rank < 1 || (int64_t)first_row + n_rows > rank)
+    return fail(RSPARSE_HIP_ERR_INVALID, "first_row / n_rows do not select rows of components");
+  if (!components || (n_q > 0 && (!query || !res || !scores))) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix, query or output");
+  std::vector<int32_t> q0((size_t)n_q);
+  for (int q = 0; q < n_q; q++) {   // R indices are 1-based
+    if (query[q] < 1 || query[q] > n_items) return fail(RSPARSE_HIP_ERR_INVALID, "query item id out of range");
+    q0[q] = query[q] - 1;
+  }
+  if (n_q == 0) return RSPARSE_HIP_OK;
+  const int r = n_rows;
+  // rank x n_items column-major = item vectors contiguous: the device form's n_items x ld row-major with ld = rank
+  DevBuf dV, dVn32, dVn64, dF, dQ, dE, dR, dS;
+  HIP_TRY(dV.alloc((size_t)n_items * rank * 8));
+  HIP_TRY(dVn32.alloc((size_t)n_items * r * 4));
+  HIP_TRY(dVn64.alloc((size_t)n_items * r * 8));
+  HIP_TRY(dF.alloc((size_t)n_items * 4));
+  HIP_TRY(dQ.alloc((size_t)n_q * 4));
+  HIP_TRY(dR.alloc((size_t)n_q * k * 4));
+  HIP_TRY(dS.alloc((size_t)n_q * k * 8));
+  HIP_TRY(hipMemcpy(dV.p, components, (size_t)n_items * rank * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dQ.p, q0.data(), (size_t)n_q * 4, hipMemcpyHostToDevice));
+  hipError_t e = launch_normalize_items(dV.p, true, n_items, rank, first_row, r, dVn32.as<float>(), dVn64.as<double>(),
+                                        dF.as<int32_t>(), nullptr);
+  if (e != hipSuccess) return hip_fail(e, "launch_normalize_items");
+  HIP_TRY(hipDeviceSynchronize());
+  // never returned: the caller's exclusions and the degenerate items
+  std::vector<int32_t> flags((size_t)n_items), ex;
+  HIP_TRY(hipMemcpy(flags.data(), dF.p, (size_t)n_items * 4, hipMemcpyDeviceToHost));
+  for (int e2 = 0; e2 < n_exclude; e2++)
+    if (exclude[e2] >= 1 && exclude[e2] <= n_items) ex.push_back(exclude[e2] - 1);
+  for (int i = 0; i < n_items; i++)
+    if (flags[i]) ex.push_back(i);
+  std::sort(ex.begin(), ex.end());
+  ex.erase(std::unique(ex.begin(), ex.end()), ex.end());
+  if (!ex.empty()) {
+    HIP_TRY(dE.alloc(ex.size() * 4));
+    HIP_TRY(hipMemcpy(dE.p, ex.data(), ex.size() * 4, hipMemcpyHostToDevice));
+  }
+  rc = rsparse_hip_similar_items_device(dVn32.as<float>(), dVn64.as<double>(), n_items, r, dQ.as<int32_t>(), n_q, k, exclude_self,
+                                        ex.empty() ? nullptr : dE.as<int32_t>(), (int)ex.size(), dR.as<int32_t>(),
+                                        dS.as<double>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<int32_t> hr((size_t)n_q * k);
+  std::vector<double> hs((size_t)n_q * k);
+  HIP_TRY(hipMemcpy(hr.data(), dR.p, hr.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hs.data(), dS.p, hs.size() * 8, hipMemcpyDeviceToHost));
+  for (int j = 0; j < n_q; j++)
+    for (int c = 0; c < k; c++) {
+      res[(size_t)c * n_q + j] = hr[(size_t)j * k + c];
+      scores[(size_t)c * n_q + j] = hs[(size_t)j * k + c];
     }
   return RSPARSE_HIP_OK;
 }

@@ -467,6 +467,21 @@ int rsparse_hip_weighted_sumsq_f64_device(const double* d_X, int rank, int64_t n
   return RSPARSE_HIP_OK;
 }
 
+// the cosine operands of rsparse_hip_similar_items_device from double factors (kernel: wrmf_similar.hip; the fp32 form and
+// the argument rules are in wrmf_capi.cpp)
+int rsparse_hip_normalize_items_f64_device(const double* d_V, int n_items, int ld, int c0, int c1, float* d_Vn32,
+                                           double* d_Vn64, int32_t* d_flags, void* stream) {
+  if (n_items < 0 || c0 < 0 || c1 - c0 < 1 || c1 > ld)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_items < 0 or not 0 <= c0 < c1 <= ld)");
+  if (c1 - c0 > RSPARSE_HIP_MAX_RANK)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 256 latent coordinates are not on the device path");
+  if (n_items > 0 && (!d_V || !d_Vn32 || !d_Vn64 || !d_flags)) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
+  if (n_items == 0) return RSPARSE_HIP_OK;
+  hipError_t e = launch_normalize_items(d_V, true, n_items, ld, c0, c1 - c0, d_Vn32, d_Vn64, d_flags, (hipStream_t)stream);
+  if (e != hipSuccess) return capi_hip_fail(e, "launch_normalize_items");
+  return RSPARSE_HIP_OK;
+}
+
 int rsparse_hip_values_subtract_mean_f64_device(int64_t n, double* d_x, double* d_x_other, double* mean_out, void* stream) {
   if (n < 0) return fail(RSPARSE_HIP_ERR_INVALID, "negative length");
   if (mean_out) *mean_out = 0.0;

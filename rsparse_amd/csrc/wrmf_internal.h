@@ -338,6 +338,28 @@ hipError_t launch_top_product_large_f64(const float* U32, const float* V32, cons
 hipError_t launch_ranking_metrics(const int32_t* pred, int n_users, int k, const int32_t* P, const int32_t* J, const double* X,
                                   double* ap_out, double* ndcg_out, int* long_buf, hipStream_t s);
 
+// item-to-item cosine similarity (wrmf_similar.hip): the operands of the top-k path above.
+// launch_normalize_items: V (fp32, or fp64 when f64) n_items x ld row-major, columns [c0, c0 + r), 1 <= r <= 256 ->
+// Vn64 / Vn32 (n_items x r, compact) with unit rows, flags[item] = 1 and a row of zeros where the sum of squares is zero or
+// not finite.
+hipError_t launch_normalize_items(const void* V, bool f64, int n_items, int64_t ld, int c0, int r, float* Vn32, double* Vn64,
+                                  int32_t* flags, hipStream_t s);
+// what a batch of n_q queries needs next to the top-k call, carved from one allocation of similar_query_ws_bytes(n_q, r):
+// the gathered operands, the self-exclusion slots (nr_p = 0..n_q, nr_j = the query's id) and bad[q] = 1 for a query that is
+// degenerate or out of range (launch_mask_queries then overwrites its row with NA_integer_ / NaN)
+struct SimilarQueryWs {
+  double* Q64;
+  float* Q32;
+  int32_t* nr_p;
+  int32_t* nr_j;
+  int32_t* bad;
+};
+size_t similar_query_ws_bytes(int n_q, int r);
+SimilarQueryWs similar_query_ws(void* ws, int n_q, int r);
+hipError_t launch_gather_queries(const float* Vn32, const double* Vn64, int n_items, int r, const int32_t* query, int n_q,
+                                 const SimilarQueryWs& w, hipStream_t s);
+hipError_t launch_mask_queries(const int32_t* bad, int n_q, int k, int32_t* res, double* scores, hipStream_t s);
+
 // device helpers of the multi-GPU context (wrmf_ctx_kernels.hip / wrmf_ctx.cpp)
 hipError_t launch_ctx_accumulate(const float* Gpart, const double* sumsq, double* red, int k, hipStream_t s);
 hipError_t launch_ctx_put_absmax(const float* absmax, double* red, int k, hipStream_t s);

@@ -384,6 +384,47 @@ class HipBackend:
     def drop_v32(self):
         self._v32_cache = self._v32_src = None
         self._v32_ver = -1
+        self._vn_cache = self._vn_src = None   # the cosine operands derive from the same matrix
+        self._vn_key = None
+
+    def normalized_items(self, V, c0, c1):
+        """the cosine operands of a factor matrix V (n_item x ld, fp32 or fp64, on the device) over its columns [c0, c1):
+        (Vn32, Vn64, exclude0) -- unit rows as float32 and float64 (n_item x (c1 - c0)) and the sorted int32 ids of the
+        degenerate items (zero or non-finite norm: rows of zeros), which `similar_items` never returns.  One streaming launch
+        (wrmf_similar.hip); kept until the matrix changes, keyed and dropped exactly like the fp32 replica `_v32`."""
+        key = (V._version, int(c0), int(c1))
+        if getattr(self, "_vn_src", None) is not V or self._vn_key != key:
+            assert V.is_contiguous() and V.dim() == 2 and V.dtype in (torch.float32, torch.float64)
+            n, ld = V.shape
+            r = int(c1) - int(c0)
+            Vn32 = torch.empty((n, max(r, 0)), dtype=torch.float32, device=V.device)
+            Vn64 = torch.empty((n, max(r, 0)), dtype=torch.float64, device=V.device)
+            flags = torch.empty(n, dtype=torch.int32, device=V.device)
+            fn = (self.lib.rsparse_hip_normalize_items_f64_device if V.dtype == torch.float64
+                  else self.lib.rsparse_hip_normalize_items_device)
+            _lib.check(fn(V.data_ptr(), n, ld, int(c0), int(c1), Vn32.data_ptr(), Vn64.data_ptr(), flags.data_ptr(),
+                          self._stream()))
+            excl = torch.nonzero(flags).flatten().to(torch.int32)   # ascending
+            self._vn_cache, self._vn_src, self._vn_key = (Vn32, Vn64, excl), V, key
+        return self._vn_cache
+
+    def similar_items(self, V, c0, c1, query, k, exclude0=None, exclude_self=True):
+        """the k items most similar (cosine over the columns [c0, c1) of V) to each item of `query` (int32 ids on the device):
+        (indices int32 n_q x k, 1-based with NA_integer_; cosines float64 n_q x k), as top_product returns them.  exclude0:
+        sorted 0-based ids excluded for every query (or None); the degenerate items are excluded besides."""
+        Vn32, Vn64, degenerate = self.normalized_items(V, c0, c1)
+        n_item, r = Vn32.shape
+        excl = degenerate
+        if exclude0 is not None and exclude0.numel():
+            excl = torch.unique(torch.cat([degenerate, exclude0.to(torch.int32)])).to(torch.int32)   # sorted
+        query = query.to(torch.int32).contiguous()
+        n_q = int(query.numel())
+        res = torch.empty((n_q, k), dtype=torch.int32, device=V.device)
+        sc = torch.empty((n_q, k), dtype=torch.float64, device=V.device)
+        _lib.check(self.lib.rsparse_hip_similar_items_device(
+            Vn32.data_ptr(), Vn64.data_ptr(), n_item, r, query.data_ptr(), n_q, int(k), int(bool(exclude_self)),
+            excl.data_ptr() if excl.numel() else None, int(excl.numel()), res.data_ptr(), sc.data_ptr(), self._stream()))
+        return res, sc
 
     def initialize_biases_explicit(self, csc_ui, csc_iu, user_bias, item_bias, lambda_, dynamic_lambda, non_negative,
                                    calculate_global_bias):

@@ -580,6 +580,83 @@ class WRMF:
                 out[name] = v.cpu().numpy()
         return out
 
+    def similar_items(self, items=None, k=10, items_exclude=(), exclude_self=True):
+        """R/MatrixFactorizationRecommender.R:79-116 (`get_similar_items`: cosine similarity on the L2-normalised item
+        embeddings), for a batch of query items at once: `items` = 0-based item ids (any integer sequence, repeats allowed;
+        None = every item in order, the item-item k-NN graph).  Returns a `TopItems` array (n_q x k item indices, 0-based,
+        best first, equal cosines with the larger index first, -1 where fewer than k items are admissible) with `.scores`
+        (n_q x k cosines, NaN beside -1).  The cosine is taken over the LATENT coordinates only: with user/item biases the item
+        bias (column 0) and the constant one (last column) stay out, and a global bias plays no part.  Items whose latent
+        vector has no direction (zero norm: e.g. items without interactions under the conjugate-gradient solver) are never
+        returned, and as queries they get a row of -1 / NaN.  exclude_self=False keeps each query in its own list (cosine 1
+        up to rounding); `items_exclude` as in `predict`.  The scoring is `predict`'s device path against the normalised
+        factors (k up to 8192); under torch.distributed every rank scores a contiguous block of the queries."""
+        if self._V is None:
+            raise RuntimeError("model is not fitted")
+        n_item = self._V.shape[0]
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        if items is None:
+            q = np.arange(n_item, dtype=np.int64)
+        else:
+            q = np.asarray(items)
+            if q.size and not np.issubdtype(q.dtype, np.integer):
+                raise TypeError("items must be integer item ids")
+            q = q.astype(np.int64).ravel()
+            if q.size and (q.min() < 0 or q.max() >= n_item):
+                raise ValueError("some of items indices are bigger than number of items")
+        excl = np.unique(np.asarray(list(items_exclude), dtype=np.int64))
+        if excl.size and (excl.min() < 0 or excl.max() >= n_item):
+            raise ValueError("some of items_exclude indices are bigger than number of items")
+        c0, c1 = (1, self._rank - 1) if self._with_bias else (0, self._rank)   # [item_bias, latent ..., 1]: fit_transform
+        be = self._backend()
+        ws, me = self._dist()
+        from .engine import equal_bounds
+        bounds = equal_bounds(int(q.size), ws)
+        a, b = bounds[me]
+        dev = self._V.device
+        if b > a:
+            qd = be.to_device(q[a:b], torch.int32)
+            d_ex = be.to_device(excl, torch.int32) if excl.size else None
+            if hasattr(be, "normalized_items"):
+                res, sc = be.similar_items(self._V, c0, c1, qd, k, d_ex, exclude_self)
+            else:
+                res, sc = self._similar_items_host(be, c0, c1, qd, k, d_ex, exclude_self)
+        else:
+            res = torch.empty((0, k), dtype=torch.int32, device=dev)
+            sc = torch.empty((0, k), dtype=torch.float64, device=dev)
+        if ws > 1:
+            res, sc = self._share_rows(res, bounds, int(q.size)), self._share_rows(sc, bounds, int(q.size))
+        idx = res.cpu().numpy().astype(np.int64)
+        idx = np.where(idx == -2147483648, -1, idx - 1)       # 1-based with NA_integer_ on the device
+        out = idx.view(TopItems)
+        sc = sc.cpu().numpy().copy()
+        sc[idx == -1] = np.nan
+        out.scores = sc.astype(self._np_dtype())
+        return out
+
+    def _similar_items_host(self, be, c0, c1, qd, k, d_ex, exclude_self):
+        """`similar_items` for a backend without `normalized_items` (the CPU stand-in of the tests): the operands from plain
+        torch ops, the scoring by the backend's `top_product` on doubles.  Same rules as wrmf_similar.hip."""
+        Vl = self._V[:, c0:c1].to(torch.float64)
+        ss = (Vl * Vl).sum(dim=1)
+        ok = (ss > 0) & torch.isfinite(ss)
+        Vn = torch.where(ok[:, None], Vl / torch.sqrt(torch.where(ok, ss, torch.ones_like(ss)))[:, None],
+                         torch.zeros_like(Vl)).contiguous()
+        excl = torch.nonzero(~ok).flatten().to(torch.int32)
+        if d_ex is not None:
+            excl = torch.unique(torch.cat([excl, d_ex.to(torch.int32)])).to(torch.int32)
+        q64 = qd.to(torch.int64)
+        n_q = int(q64.numel())
+        nr_p = torch.arange(n_q + 1, dtype=torch.int32, device=qd.device) if exclude_self else None
+        nr_j = qd.to(torch.int32).contiguous() if exclude_self else None
+        res, sc = be.top_product(Vn[q64].contiguous(), Vn, k, nr_p, nr_j, excl if excl.numel() else None, 0.0)
+        bad = ~ok[q64]
+        res = res.clone()
+        res[bad] = -2147483648
+        return res, sc
+
     def transform(self, x):
         """R/model_WRMF.R:365-385: embeddings for new rows of a users x items matrix."""
         if self._V is None:
