@@ -13,8 +13,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <queue>
 #include <string>
 #include <vector>
 
@@ -25,6 +23,7 @@ using namespace rsparse_hip;
 struct rsparse_hip_csc {
   DevCSC d;
   int device = 0;
+  std::vector<void*> owned;   // every device array the handle allocated: rsparse_hip_csc_destroy frees each, once
 };
 
 namespace {
@@ -47,220 +46,59 @@ int hip_fail(hipError_t e, const char* what) {
 // Grow-only per-process scratch (single host thread drives the library, like the reference's
 // single R thread; not re-entrant across streams).
 struct Workspace {
-  float* gram = nullptr;
-  size_t gram_floats = 0;
-  double* partials = nullptr;
-  size_t partial_slots = 0;
-  double* scalars = nullptr;  // [0] loss rows, [1] sumsq, [2..] spare
-  int* fails = nullptr;
-  unsigned* ne_stats = nullptr;   // normal-equation kernel: max |x|, max c, any c < 1 (launch_ne_stats)
-  float* lr_M = nullptr;
-  float* ne_seg_scratch = nullptr;
-  int* ne_seg_flags = nullptr;
-  size_t ne_seg_slots = 0;
-  float* zero_row = nullptr;  // 256 zero floats (padding slots of the CG gathers)
-  float* tscr = nullptr;   // streamed CG rows: per-non-zero dot products of every sweep
-  size_t tscr_floats = 0;
-  float* bias_buf = nullptr;   // explicit + biases: X', Y', shifted ratings
-  size_t bias_floats = 0;
-  float* gb_r0 = nullptr;      // global bias + CG: per long row, base - g X_nnz (c - 1)  (launch_gb_row_terms)
-  size_t gb_r0_floats = 0;
-  int32_t* gb_slot = nullptr;  // ... and the slot of every row in it
-  size_t gb_slot_ints = 0;
-  float* wide_m2 = nullptr;    // ranks 129..256 (wrmf_wide.hip): NNLS squared systems / the general solver's matrices
-  size_t wide_m2_floats = 0;
-  float* wide_lu = nullptr;
-  size_t wide_lu_floats = 0;
-  int* met_buf = nullptr;      // ranking metrics (wrmf_metrics.hip): count + list of the users whose idcg takes the long-row launch
-  size_t met_ints = 0;
-  void* sim_buf = nullptr;     // item-to-item similarity (wrmf_similar.hip): a batch's gathered queries and self-exclusion slots
-  size_t sim_bytes = 0;
+  GrowBufBase* all = nullptr;
+  GrowBuf<float> gram{all};
+  GrowBuf<double> partials{all};   // partial_slots() slots + the tail of the two-stage sum
+  GrowBuf<double> scalars{all};    // [0] loss rows, [1] sumsq, [2..] spare
+  GrowBuf<int> fails{all};         // see launch_fail_roll
+  GrowBuf<unsigned> ne_stats{all};   // normal-equation kernel: max |x|, max c, any c < 1 (launch_ne_stats)
+  GrowBuf<float> lr_M{all};          // M = L^-T and its transpose of the low-rank Cholesky path
+  GrowBuf<float> ne_seg_scratch{all};   // split rows of the normal-equation kernel: partial accumulators + ready flags
+  GrowBuf<int> ne_seg_flags{all};
+  GrowBuf<float> zero_row{all};   // 256 zero floats (padding slots of the CG gathers)
+  GrowBuf<float> tscr{all};       // streamed CG rows: per-non-zero dot products of every sweep
+  GrowBuf<float> bias_buf{all};   // explicit + biases: X', Y', shifted ratings
+  GrowBuf<float> gb_r0{all};      // global bias + CG: per long row, base - g X_nnz (c - 1)  (launch_gb_row_terms)
+  GrowBuf<int32_t> gb_slot{all};  // ... and the slot of every row in it
+  GrowBuf<float> wide_m2{all};    // ranks 129..256 (wrmf_wide.hip): NNLS squared systems / the general solver's matrices
+  GrowBuf<float> wide_lu{all};
+  GrowBuf<int> met_buf{all};      // ranking metrics (wrmf_metrics.hip): count + list of the users whose idcg takes the long-row launch
+  GrowBuf<char> sim_buf{all};     // item-to-item similarity (wrmf_similar.hip): a batch's gathered queries and self-exclusion slots
+  GrowBuf<float> mf_G{all};       // wrmf_chol_mf.hip at rank 65..127: XtX padded to 128 x 128
+  GrowBuf<float> pad_buf{all};    // ranks that are not a multiple of 4: the padded copies of X, Y, XtX, rhs_init (run_half_iteration)
   int device = -1;
 
   int ensure_device() {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (dev != device) {  // buffers belong to the device they were allocated on
-      release();
+      GrowBufBase::release_all(all);
       device = dev;
     }
+    // the fixed blocks that start zeroed
     if (!scalars) {
-      HIP_TRY(hipMalloc(&scalars, 16 * sizeof(double)));
+      HIP_TRY(scalars.ensure(16));
       HIP_TRY(hipMemset(scalars, 0, 16 * sizeof(double)));
     }
-    if (!fails) {   // see launch_fail_roll
-      HIP_TRY(hipMalloc(&fails, (size_t)(4 + kFailCap) * sizeof(int)));
+    if (!fails) {
+      HIP_TRY(fails.ensure((size_t)(4 + kFailCap)));
       HIP_TRY(hipMemset(fails, 0, 4 * sizeof(int)));
     }
     if (!ne_stats) {
-      HIP_TRY(hipMalloc(&ne_stats, 4 * sizeof(unsigned)));
+      HIP_TRY(ne_stats.ensure(4));
       HIP_TRY(hipMemset(ne_stats, 0, 4 * sizeof(unsigned)));
     }
     if (!zero_row) {
-      HIP_TRY(hipMalloc(&zero_row, 256 * sizeof(float)));
+      HIP_TRY(zero_row.ensure(256));
       HIP_TRY(hipMemset(zero_row, 0, 256 * sizeof(float)));
     }
     return RSPARSE_HIP_OK;
   }
-  int ensure_lr() {   // M = L^-T and its transpose of the low-rank Cholesky path
-    if (!lr_M) HIP_TRY(hipMalloc(&lr_M, (size_t)3 * 128 * 128 * sizeof(float)));
-    return RSPARSE_HIP_OK;
-  }
-  int ensure_ne_seg(size_t slots) {   // split rows of the normal-equation kernel: partial accumulators + ready flags
-    if (slots > ne_seg_slots) {
-      if (ne_seg_scratch) (void)hipFree(ne_seg_scratch);
-      if (ne_seg_flags) (void)hipFree(ne_seg_flags);
-      ne_seg_scratch = nullptr; ne_seg_flags = nullptr; ne_seg_slots = 0;
-      HIP_TRY(hipMalloc(&ne_seg_scratch, slots * (size_t)kNeSegFloats * sizeof(float)));
-      HIP_TRY(hipMalloc(&ne_seg_flags, slots * sizeof(int)));
-      ne_seg_slots = slots;
-    }
-    return RSPARSE_HIP_OK;
-  }
-  int ensure_gram(size_t floats) {
-    if (floats > gram_floats) {
-      if (gram) (void)hipFree(gram);
-      gram = nullptr;
-      gram_floats = 0;
-      HIP_TRY(hipMalloc(&gram, floats * sizeof(float)));
-      gram_floats = floats;
-    }
-    return RSPARSE_HIP_OK;
-  }
   int ensure_partials(size_t slots) {
-    if (slots < 1024) slots = 1024;
-    if (slots > partial_slots) {
-      if (partials) (void)hipFree(partials);
-      partials = nullptr;
-      partial_slots = 0;
-      HIP_TRY(hipMalloc(&partials, (slots + kSumStageBlocks) * sizeof(double)));   // + the tail of the two-stage sum
-      partial_slots = slots;
-    }
+    HIP_TRY(partials.ensure(std::max<size_t>(slots, 1024) + kSumStageBlocks));   // + the tail of the two-stage sum
     return RSPARSE_HIP_OK;
   }
-  float* mf_G = nullptr;      // wrmf_chol_mf.hip at rank 65..127: XtX padded to 128 x 128
-  int ensure_mf() {
-    if (!mf_G) HIP_TRY(hipMalloc(&mf_G, (size_t)128 * 128 * sizeof(float)));
-    return RSPARSE_HIP_OK;
-  }
-  float* pad_buf = nullptr;   // ranks that are not a multiple of 4: the padded copies of X, Y, XtX, rhs_init (run_half_iteration)
-  size_t pad_floats = 0;
-  int ensure_pad(size_t floats) {
-    if (floats > pad_floats) {
-      if (pad_buf) (void)hipFree(pad_buf);
-      pad_buf = nullptr;
-      pad_floats = 0;
-      HIP_TRY(hipMalloc(&pad_buf, floats * sizeof(float)));
-      pad_floats = floats;
-    }
-    return RSPARSE_HIP_OK;
-  }
-  int ensure_bias(size_t floats) {
-    if (floats > bias_floats) {
-      if (bias_buf) (void)hipFree(bias_buf);
-      bias_buf = nullptr;
-      bias_floats = 0;
-      HIP_TRY(hipMalloc(&bias_buf, floats * sizeof(float)));
-      bias_floats = floats;
-    }
-    return RSPARSE_HIP_OK;
-  }
-  int ensure_gb(size_t floats, size_t ints) {
-    if (floats > gb_r0_floats) {
-      if (gb_r0) (void)hipFree(gb_r0);
-      gb_r0 = nullptr; gb_r0_floats = 0;
-      HIP_TRY(hipMalloc(&gb_r0, floats * sizeof(float)));
-      gb_r0_floats = floats;
-    }
-    if (ints > gb_slot_ints) {
-      if (gb_slot) (void)hipFree(gb_slot);
-      gb_slot = nullptr; gb_slot_ints = 0;
-      HIP_TRY(hipMalloc(&gb_slot, ints * sizeof(int32_t)));
-      gb_slot_ints = ints;
-    }
-    return RSPARSE_HIP_OK;
-  }
-  int ensure_wide(size_t m2, size_t lu) {
-    if (m2 > wide_m2_floats) {
-      if (wide_m2) (void)hipFree(wide_m2);
-      wide_m2 = nullptr; wide_m2_floats = 0;
-      HIP_TRY(hipMalloc(&wide_m2, m2 * sizeof(float)));
-      wide_m2_floats = m2;
-    }
-    if (lu > wide_lu_floats) {
-      if (wide_lu) (void)hipFree(wide_lu);
-      wide_lu = nullptr; wide_lu_floats = 0;
-      HIP_TRY(hipMalloc(&wide_lu, lu * sizeof(float)));
-      wide_lu_floats = lu;
-    }
-    return RSPARSE_HIP_OK;
-  }
-  int ensure_tscr(size_t floats) {
-    if (floats > tscr_floats) {
-      if (tscr) (void)hipFree(tscr);
-      tscr = nullptr;
-      tscr_floats = 0;
-      HIP_TRY(hipMalloc(&tscr, floats * sizeof(float)));
-      tscr_floats = floats;
-    }
-    return RSPARSE_HIP_OK;
-  }
-  int ensure_met(size_t ints) {
-    if (ints > met_ints) {
-      if (met_buf) (void)hipFree(met_buf);
-      met_buf = nullptr;
-      met_ints = 0;
-      HIP_TRY(hipMalloc(&met_buf, ints * sizeof(int)));
-      met_ints = ints;
-    }
-    return RSPARSE_HIP_OK;
-  }
-  int ensure_sim(size_t bytes) {
-    if (bytes > sim_bytes) {
-      if (sim_buf) (void)hipFree(sim_buf);
-      sim_buf = nullptr;
-      sim_bytes = 0;
-      HIP_TRY(hipMalloc(&sim_buf, bytes));
-      sim_bytes = bytes;
-    }
-    return RSPARSE_HIP_OK;
-  }
-  void release() {
-    if (sim_buf) (void)hipFree(sim_buf);
-    sim_buf = nullptr; sim_bytes = 0;
-    if (met_buf) (void)hipFree(met_buf);
-    met_buf = nullptr; met_ints = 0;
-    if (wide_m2) (void)hipFree(wide_m2);
-    if (wide_lu) (void)hipFree(wide_lu);
-    wide_m2 = wide_lu = nullptr; wide_m2_floats = wide_lu_floats = 0;
-    if (gb_r0) (void)hipFree(gb_r0);
-    if (gb_slot) (void)hipFree(gb_slot);
-    gb_r0 = nullptr; gb_slot = nullptr; gb_r0_floats = 0; gb_slot_ints = 0;
-    if (tscr) (void)hipFree(tscr);
-    tscr = nullptr;
-    tscr_floats = 0;
-    if (bias_buf) (void)hipFree(bias_buf);
-    bias_buf = nullptr;
-    bias_floats = 0;
-    if (gram) (void)hipFree(gram);
-    if (partials) (void)hipFree(partials);
-    if (scalars) (void)hipFree(scalars);
-    if (fails) (void)hipFree(fails);
-    if (ne_stats) (void)hipFree(ne_stats);
-    ne_stats = nullptr;
-    if (ne_seg_scratch) (void)hipFree(ne_seg_scratch);
-    if (ne_seg_flags) (void)hipFree(ne_seg_flags);
-    ne_seg_scratch = nullptr; ne_seg_flags = nullptr; ne_seg_slots = 0;
-    if (lr_M) (void)hipFree(lr_M);
-    lr_M = nullptr;
-    if (mf_G) (void)hipFree(mf_G);
-    mf_G = nullptr;
-    if (pad_buf) (void)hipFree(pad_buf);
-    pad_buf = nullptr; pad_floats = 0;
-    if (zero_row) (void)hipFree(zero_row);
-    gram = nullptr; partials = nullptr; scalars = nullptr; fails = nullptr; zero_row = nullptr;
-    gram_floats = 0; partial_slots = 0;
-  }
+  size_t partial_slots() const { return partials.cap - kSumStageBlocks; }
 };
 thread_local Workspace g_ws;   // per host thread: the multi-GPU context (wrmf_ctx.cpp) drives one device from one thread each
 
@@ -281,250 +119,63 @@ struct Profiler {
 };
 thread_local Profiler g_prof;
 
-struct DevBuf {  // RAII for the stateless entry points
+// a planned vector as a device array of handle m (nullptr for an empty one)
+template <class T>
+int upload(rsparse_hip_csc& m, const std::vector<T>& v, const T** out) {
+  *out = nullptr;
+  if (v.empty()) return RSPARSE_HIP_OK;
   void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  template <class T> T* as() { return static_cast<T*>(p); }
-};
-
-// rows with more than kTileNnz non-zeros, longest first (counting sort on the host; one-off per matrix)
-int build_schedule(DevCSC& d, const int32_t* host_col_ptrs) {
-  const int n = d.n_cols;
-  int max_len = 0;
-  size_t n_long = 0;
-  int64_t nnz_long = 0;
-  int n_empty = 0;
-  for (int i = 0; i < n; i++) {
-    const int len = host_col_ptrs[i + 1] - host_col_ptrs[i];
-    if (len < 0) return fail(RSPARSE_HIP_ERR_INVALID, "col_ptrs is not non-decreasing");
-    max_len = std::max(max_len, len);
-    if (len > kTileNnz) { n_long++; nnz_long += len; }
-    if (len == 0) n_empty++;
-  }
-  d.max_len = max_len;
-  d.nnz_long = nnz_long;
-  d.n_empty = n_empty;
-  d.short_max = kTileNnz;
-  d.n_long = (int)n_long;
-  d.long_rows = nullptr;
-  if (!n_long) return RSPARSE_HIP_OK;
-  // counting sort by length, descending; ties keep ascending row order (deterministic)
-  std::vector<int64_t> start((size_t)max_len + 2, 0);
-  for (int i = 0; i < n; i++) {
-    const int len = host_col_ptrs[i + 1] - host_col_ptrs[i];
-    if (len > kTileNnz) start[(size_t)(max_len - len) + 1]++;
-  }
-  for (size_t b = 1; b < start.size(); b++) start[b] += start[b - 1];
-  std::vector<int32_t> order(n_long);
-  for (int i = 0; i < n; i++) {
-    const int len = host_col_ptrs[i + 1] - host_col_ptrs[i];
-    if (len > kTileNnz) order[(size_t)start[(size_t)(max_len - len)]++] = i;
-  }
-  HIP_TRY(hipMalloc(&d.long_rows, n_long * sizeof(int32_t)));
-  HIP_TRY(hipMemcpy(d.long_rows, order.data(), n_long * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMalloc(&p, v.size() * sizeof(T)));
+  m.owned.push_back(p);
+  HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  *out = static_cast<const T*>(p);
   return RSPARSE_HIP_OK;
 }
 
-struct NeLists {
-  int32_t* rows = nullptr; int32_t* ptr = nullptr; int wg = 0;
-  int32_t* segs = nullptr; int nseg = 0; int entries = 0;
-  int32_t* split_rows = nullptr; int32_t* split_ptr = nullptr; int nsplit = 0;
-};
-
-// Lists of the normal-equation launch over the n_prefix longest rows (order = every row, longest first); `fixed` = the
-// per-row cost of the solve in 16-non-zero steps (CG: 12; the exact solve of solver == CHOLESKY: 72).
-int build_ne_lists(const std::vector<int32_t>& order, const int32_t* host_col_ptrs, int n_prefix, int64_t fixed, NeLists& L,
-                   bool fine = true) {
-  if (n_prefix <= 0) return RSPARSE_HIP_OK;
-  auto len_of = [&](int r) { return (int64_t)(host_col_ptrs[order[(size_t)r] + 1] - host_col_ptrs[order[(size_t)r]]); };
-  {
-  // Row lists of the normal-equation kernel: one workgroup per CU, rows dealt longest-processing-time first (the rows
-  // arrive sorted by length, each goes to the least loaded workgroup; cost = the row's 16-non-zero steps + a fixed
-  // per-row solve).  Static lists make the per-row loss slots and the summation order deterministic.
-  int dev = 0, cus = 256;
-  HIP_TRY(hipGetDevice(&dev));
-  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  // Many more lists than workgroup slots (eight rows or more per list, up to 256 lists per CU; two workgroups of the
-  // rank-128 fp16 kernel are resident per CU): the
-  // hardware hands the next list to whichever slot frees up.  With exactly one list per slot the launch ended 13 % after
-  // its mean workgroup (round 3, in-kernel counters): of the two workgroups that share a CU's SIMDs the one dispatched
-  // first wins the issue arbitration and runs 27 % faster -- every workgroup of index < 256 took 63.9 M ticks for its
-  // list, every one of index >= 256 81.4 M for an equal list, the last 17 M of them alone on its CU.
-  // (round 6, `fine` lists: the slots of the whole machine even when there are fewer rows than slots -- the giant rows that
-  //  wrmf_cg_mf.hip leaves to this kernel are a few hundred: one workgroup per row left 40 % of the slots empty and every row as
-  //  long as its wave could stream it, 4.4 GB in 4.7 ms; cut to the machine's share they are segments of >= 64 steps)
-  // The CUT must not depend on the deal: the two list sets of a matrix (fine / one list per slot) share ONE segment table and
-  // one list of split rows (build_q_schedule) -- cut by the fine rule only, a row was whole in the coarse lists and "split" in
-  // the table, and the collecting launch overwrote its solution with the sum of two stale partials (ranks up to 96, fewer
-  // than 512 long rows, a row of >= 2048 non-zeros: tests/test_bias.py caught it at the end of round 6).
-  const int n_slots = 2 * std::max(cus, 1);   // what the share of the split rule refers to
-  // (`fine` = false: one list per slot, for the kernels that are resident once per CU -- no such asymmetry there, and a
-  //  workgroup start costs more: XtX tiles into LDS; many short lists cost them 1..7 %)
-  int n_wg = fine ? std::max(n_slots, std::min(n_prefix / 8, 256 * std::max(cus, 1))) : n_slots;   // (at most one per item: below)
-  // Items of the deal: whole rows, and SEGMENTS of the rows that are too long to balance (the 5e5-non-zero item of the
-  // bench matrix is by itself an average workgroup's share; on a rank of an 8-GPU run it is eight shares).  A row
-  // whose cost exceeds half a share is cut into up to kNeMaxSeg runs of whole steps of about a quarter share; the
-  // workgroups that get the leading segments write their partial accumulators to an HBM scratch, the one with the
-  // last segment adds them in segment order and solves (wrmf_ne.hip).  List entry >= 0: a row; -(s + 1): segment s
-  // of the table {row, first non-zero, non-zeros, index within the row, segments of the row, scratch slot}.
-  auto steps_of = [](int64_t len) { return (len + 15) / 16; };
-  int64_t total = 0;
-  for (int r = 0; r < n_prefix; r++) total += steps_of(len_of(r)) + fixed;
-  const int64_t share = std::max<int64_t>(1, total / n_slots);
-  struct Item { int64_t cost; int32_t entry; };
-  std::vector<Item> items;
-  items.reserve((size_t)n_prefix + 64);
-  std::vector<int32_t> segs;
-  int n_seg = 0;
-  for (int r = 0; r < n_prefix; r++) {
-    const int64_t len = len_of(r);
-    const int64_t st = steps_of(len);
-    int parts = 1;
-    if (n_slots >= 8 && 2 * (st + fixed) > share)
-      parts = (int)std::min<int64_t>(std::min<int64_t>(kNeMaxSeg, st / 64), (4 * st + share - 1) / share);   // (a segment: >= 64 steps)
-    if (parts < 2 || n_seg + parts > kNeMaxSegTotal) {
-      items.push_back({st + fixed, order[(size_t)r]});
-      continue;
-    }
-    const int64_t per = (st + parts - 1) / parts;   // steps per segment
-    const int slot = n_seg;
-    int made = 0;
-    for (int64_t s0 = 0; s0 < st; s0 += per, made++) {}
-    int idx = 0;
-    for (int64_t s0 = 0; s0 < st; s0 += per, idx++) {
-      const int64_t n0 = s0 * 16, n1 = std::min(len, (s0 + per) * 16);
-      segs.insert(segs.end(), {order[(size_t)r], (int32_t)n0, (int32_t)(n1 - n0), idx, made, slot});
-      items.push_back({steps_of(n1 - n0) + fixed, -(int32_t)(n_seg + 1)});
-      n_seg++;
-    }
-  }
-  std::stable_sort(items.begin(), items.end(), [](const Item& x, const Item& y) { return x.cost > y.cost; });
-  const size_t n_items = items.size();
-  n_wg = (int)std::min<size_t>((size_t)n_wg, n_items);   // (no empty lists)
-  std::vector<int> owner(n_items);
-  std::vector<int32_t> cnt_wg((size_t)n_wg + 1, 0);
-  std::priority_queue<std::pair<int64_t, int>, std::vector<std::pair<int64_t, int>>, std::greater<>> heap;
-  for (int w = 0; w < n_wg; w++) heap.push({0, w});
-  for (size_t e = 0; e < n_items; e++) {
-    auto top = heap.top();
-    heap.pop();
-    owner[e] = top.second;
-    cnt_wg[(size_t)top.second + 1]++;
-    heap.push({top.first + items[e].cost, top.second});
-  }
-  for (int w = 0; w < n_wg; w++) cnt_wg[(size_t)w + 1] += cnt_wg[(size_t)w];
-  std::vector<int32_t> lists(n_items), fill(cnt_wg.begin(), cnt_wg.end() - 1);
-  for (size_t e = 0; e < n_items; e++) lists[(size_t)fill[(size_t)owner[e]]++] = items[e].entry;
-  HIP_TRY(hipMalloc(&L.rows, lists.size() * sizeof(int32_t)));
-  HIP_TRY(hipMemcpy(L.rows, lists.data(), lists.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&L.ptr, cnt_wg.size() * sizeof(int32_t)));
-  HIP_TRY(hipMemcpy(L.ptr, cnt_wg.data(), cnt_wg.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  if (n_seg > 0) {
-    HIP_TRY(hipMalloc(&L.segs, segs.size() * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(L.segs, segs.data(), segs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    std::vector<int32_t> srows, sptr{0};
-    for (int sg = 0; sg < n_seg; sg++)
-      if (segs[(size_t)sg * 6 + 3] == 0) {   // first segment of its row
-        srows.push_back(-(int32_t)(sg + 1));
-        sptr.push_back((int32_t)srows.size());
-      }
-    HIP_TRY(hipMalloc(&L.split_rows, srows.size() * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(L.split_rows, srows.data(), srows.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&L.split_ptr, sptr.size() * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(L.split_ptr, sptr.data(), sptr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    L.nsplit = (int)srows.size();
-  }
-    L.nseg = n_seg;
-    L.entries = (int)n_items;
-    L.wg = n_wg;
-  }
-  return RSPARSE_HIP_OK;
+int upload_cut(rsparse_hip_csc& m, const NeCut& cut, NeListSet& L) {
+  L = NeListSet();
+  L.entries = (int)cut.items.size();
+  L.nseg = cut.nseg();
+  L.nsplit = (int)cut.split_rows.size();
+  if (int rc = upload(m, cut.segs, &L.segs)) return rc;
+  if (int rc = upload(m, cut.split_rows, &L.split_rows)) return rc;
+  return upload(m, cut.split_ptr, &L.split_ptr);
+}
+int upload_deal(rsparse_hip_csc& m, const NeDeal& deal, NeListSet& L) {
+  L.wg = deal.wg();
+  if (int rc = upload(m, deal.rows, &L.rows)) return rc;
+  return upload(m, deal.ptr, &L.ptr);
 }
 
-// every row, longest first, with the bucket boundaries of the quad-layout CG kernels
-int build_q_schedule(DevCSC& d, const int32_t* host_col_ptrs) {
-  const int n = d.n_cols;
-  for (int b = 0; b < 7; b++) d.q_off[b] = 0;
-  for (int b = 0; b < 6; b++) d.q_nnz[b] = 0;
-  d.q_order = nullptr;
-  d.q_stream_off = nullptr;
-  d.q_ne_rows = nullptr; d.q_ne_ptr = nullptr; d.q_ne_wg = 0;
-  d.q_ne1_rows = nullptr; d.q_ne1_ptr = nullptr; d.q_ne1_wg = 0;
-  d.q_ne_segs = nullptr; d.q_ne_nseg = 0; d.q_ne_entries = 0;
-  d.q_ne_split_rows = nullptr; d.q_ne_split_ptr = nullptr; d.q_ne_nsplit = 0;
-  d.q_nec_rows = nullptr; d.q_nec_ptr = nullptr; d.q_nec_wg = 0; d.q_nec_segs = nullptr; d.q_nec_nseg = 0; d.q_nec_entries = 0;
-  d.q_nec_split_rows = nullptr; d.q_nec_split_ptr = nullptr; d.q_nec_nsplit = 0; d.q_nec_own = false;
-  d.q_n_chol_long = 0;
-  d.q_lr_first = 0; d.q_n_lr = 0; d.q_gt32 = 0; d.q_gt48 = 0;
-  d.q_pair_first = 0;
-  d.q_team4_first = 0;
+// The launch schedule of handle m (one-off per matrix): planned on the host from the column pointers (wrmf_schedule.cpp),
+// published here
+int build_schedule(rsparse_hip_csc& m, const int32_t* host_col_ptrs) {
+  DevCSC& d = m.d;
+  int cus = 256;
+  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m.device));
   d.q_cfg = cgq_default_cfg();
-  if (n <= 0) return RSPARSE_HIP_OK;
-  const int max_len = d.max_len;
-  std::vector<int64_t> start((size_t)max_len + 2, 0);
-  int cnt_b[6] = {0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < n; i++) {
-    const int len = host_col_ptrs[i + 1] - host_col_ptrs[i];
-    start[(size_t)(max_len - len) + 1]++;
-    const int b = cgq_bucket_of(len, d.q_cfg);
-    if (len > kCholLongLen) d.q_n_chol_long++;
-    if (len > 16) d.q_pair_first++;                // the order is longest first: the rows of <= 16 non-zeros are a suffix
-    if (len > kTeam4Max) d.q_team4_first++;        // ... and so are those of <= kTeam4Max
-    if (len > 32) d.q_gt32++;
-    if (len > 48) d.q_gt48++;
-    if (len > kCholLrMax) d.q_lr_first++;          // the order is longest first: the short rows are a suffix
-    else if (len >= 1) d.q_n_lr++;
-    cnt_b[b]++;
-    d.q_nnz[b] += len;
-  }
-  for (size_t b = 1; b < start.size(); b++) start[b] += start[b - 1];
-  std::vector<int32_t> order((size_t)n);
-  for (int i = 0; i < n; i++) {
-    const int len = host_col_ptrs[i + 1] - host_col_ptrs[i];
-    order[(size_t)start[(size_t)(max_len - len)]++] = i;
-  }
-  for (int b = 0; b < 6; b++) d.q_off[b + 1] = d.q_off[b] + cnt_b[b];
-  HIP_TRY(hipMalloc(&d.q_order, (size_t)n * sizeof(int32_t)));
-  HIP_TRY(hipMemcpy(d.q_order, order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-  // streamed bucket (bucket 0): slot of each row's first non-zero in the per-sweep scratch
-  const int n_stream = d.q_off[1];
-  if (n_stream > 0) {
-    std::vector<int64_t> soff((size_t)n_stream + 1, 0);
-    for (int r = 0; r < n_stream; r++) {
-      const int row = order[(size_t)r];
-      soff[(size_t)r + 1] = soff[(size_t)r] + (host_col_ptrs[row + 1] - host_col_ptrs[row]);
-    }
-    HIP_TRY(hipMalloc(&d.q_stream_off, soff.size() * sizeof(int64_t)));
-    HIP_TRY(hipMemcpy(d.q_stream_off, soff.data(), soff.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    NeLists L;
-    if (int rc2 = build_ne_lists(order, host_col_ptrs, n_stream, 12, L)) return rc2;
-    d.q_ne_rows = L.rows; d.q_ne_ptr = L.ptr; d.q_ne_wg = L.wg; d.q_ne_segs = L.segs; d.q_ne_nseg = L.nseg;
-    d.q_ne_entries = L.entries; d.q_ne_split_rows = L.split_rows; d.q_ne_split_ptr = L.split_ptr; d.q_ne_nsplit = L.nsplit;
-    // the same rows and segments as one list per workgroup slot, for the ranks whose kernel is resident once per CU
-    NeLists L1;
-    if (int rc2 = build_ne_lists(order, host_col_ptrs, n_stream, 12, L1, false)) return rc2;
-    d.q_ne1_rows = L1.rows; d.q_ne1_ptr = L1.ptr; d.q_ne1_wg = L1.wg;
-    if (L1.segs) (void)hipFree(L1.segs);   // (identical to the tables above: the deal does not change the cut)
-    if (L1.split_rows) (void)hipFree(L1.split_rows);
-    if (L1.split_ptr) (void)hipFree(L1.split_ptr);
-  }
-  // a second set of lists for a longer prefix of the order.  Round 6: the rows beyond kCgMfMax non-zeros -- what is left to the
-  // normal-equation kernel when wrmf_cg_mf.hip takes the rows of 513..kCgMfMax (rank 128, implicit conjugate gradient).
-  // (Rounds 2-5: the rows beyond 64, for solver == CHOLESKY at rank 65..128 -- wrmf_chol_mf.hip has those now.)
-  int n_nec = 0;
-  while (n_nec < n && host_col_ptrs[order[(size_t)n_nec] + 1] - host_col_ptrs[order[(size_t)n_nec]] > kCgMfMax) n_nec++;
-  d.q_n_nec = n_nec;
-  if (n_nec == n_stream) {
-    d.q_nec_rows = d.q_ne_rows; d.q_nec_ptr = d.q_ne_ptr; d.q_nec_wg = d.q_ne_wg; d.q_nec_segs = d.q_ne_segs;
-    d.q_nec_nseg = d.q_ne_nseg; d.q_nec_entries = d.q_ne_entries; d.q_nec_split_rows = d.q_ne_split_rows;
-    d.q_nec_split_ptr = d.q_ne_split_ptr; d.q_nec_nsplit = d.q_ne_nsplit;
+  SchedulePlan plan;
+  if (!plan_schedule(host_col_ptrs, d.n_cols, cus, [](int len) { return cgq_bucket_of(len, cgq_default_cfg()); }, plan))
+    return fail(RSPARSE_HIP_ERR_INVALID, "col_ptrs is not non-decreasing");
+  d.max_len = plan.max_len; d.nnz_long = plan.nnz_long; d.n_empty = plan.n_empty;
+  d.short_max = kTileNnz; d.n_long = plan.n_long;
+  for (int b = 0; b < 7; b++) d.q_off[b] = plan.off[b];
+  for (int b = 0; b < 6; b++) d.q_nnz[b] = plan.nnz[b];
+  d.q_pair_first = plan.pair_first; d.q_team4_first = plan.team4_first;
+  d.q_gt32 = plan.gt32; d.q_gt48 = plan.gt48; d.q_lr_first = plan.lr_first; d.q_n_lr = plan.n_lr;
+  d.q_n_chol_long = plan.n_chol_long; d.q_n_nec = plan.n_nec;
+  int rc;
+  if ((rc = upload(m, plan.order, &d.q_order))) return rc;
+  if ((rc = upload(m, plan.stream_off, &d.q_stream_off))) return rc;
+  if ((rc = upload_cut(m, plan.cut, d.q_ne))) return rc;
+  d.q_ne1 = d.q_ne;   // (the same segment table and split rows: the deal does not change the cut)
+  if ((rc = upload_deal(m, plan.fine, d.q_ne))) return rc;
+  if ((rc = upload_deal(m, plan.coarse, d.q_ne1))) return rc;
+  if (plan.nec_is_ne) {
+    d.q_nec = d.q_ne;
   } else {
-    NeLists L;
-    if (int rc2 = build_ne_lists(order, host_col_ptrs, n_nec, 12, L)) return rc2;
-    d.q_nec_own = true;
-    d.q_nec_rows = L.rows; d.q_nec_ptr = L.ptr; d.q_nec_wg = L.wg; d.q_nec_segs = L.segs; d.q_nec_nseg = L.nseg;
-    d.q_nec_entries = L.entries; d.q_nec_split_rows = L.split_rows; d.q_nec_split_ptr = L.split_ptr; d.q_nec_nsplit = L.nsplit;
+    if ((rc = upload_cut(m, plan.cut_nec, d.q_nec))) return rc;
+    if ((rc = upload_deal(m, plan.nec, d.q_nec))) return rc;
   }
   return RSPARSE_HIP_OK;
 }
@@ -535,15 +186,13 @@ bool use_cgq(int rank, const void* X, const void* Y) {
   return rank % 4 == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) & 15) == 0;
 }
 
-int check_common(int n_rows, int n_cols, const void* col_ptrs, const void* row_indices, const void* values,
-                 const void* X, const void* Y, int rank) {
+int check_common(int n_rows, int n_cols, const void* col_ptrs, const void* X, const void* Y, int rank) {
   if (n_rows < 0 || n_cols < 0) return fail(RSPARSE_HIP_ERR_INVALID, "negative matrix dimension");
   if (!col_ptrs) return fail(RSPARSE_HIP_ERR_INVALID, "col_ptrs is NULL");
   if (!X || !Y) return fail(RSPARSE_HIP_ERR_INVALID, "X or Y is NULL");
   if (rank <= 0) return fail(RSPARSE_HIP_ERR_INVALID, "rank must be positive");
   if (rank > RSPARSE_HIP_MAX_RANK)
     return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 256 is not on the device path");
-  (void)row_indices; (void)values;
   return RSPARSE_HIP_OK;
 }
 
@@ -627,7 +276,7 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
     // half-iteration runs on copies padded to the next multiple of 4 and the solved rows are copied back.
     const int kp = pad_to_128 ? 128 : (pad_to_64 ? 64 : ((rank + 3) & ~3));
     const size_t nx = (size_t)d.n_rows * kp, ny = (size_t)d.n_cols * kp, ng = (size_t)kp * kp;
-    if ((rc = g_ws.ensure_pad(nx + ny + ng + 256 + 16))) return rc;
+    HIP_TRY(g_ws.pad_buf.ensure(nx + ny + ng + 256 + 16));
     float* Xp = g_ws.pad_buf;
     float* Yp = Xp + nx;
     float* Gp = Yp + ny;
@@ -662,9 +311,8 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
     const int grid = wide_als_grid(d.n_cols);
     const int grid_w = wide_cg_wave_grid(d.n_cols) + wide_cg_team_grid(d.n_cols);   // (plain conjugate gradient: wrmf_wide_cg.hip's two launches)
     if ((rc = g_ws.ensure_partials((size_t)grid + (size_t)grid_w))) return rc;
-    if ((rc = g_ws.ensure_wide(solver == RSPARSE_SOLVER_NNLS ? (size_t)grid * wide_m2_floats_per_wg(rank) : 0,
-                               solver == RSPARSE_SOLVER_CHOLESKY ? (size_t)grid * rank * rank : 0)))
-      return rc;
+    HIP_TRY(g_ws.wide_m2.ensure(solver == RSPARSE_SOLVER_NNLS ? (size_t)grid * wide_m2_floats_per_wg(rank) : 0));
+    HIP_TRY(g_ws.wide_lu.ensure(solver == RSPARSE_SOLVER_CHOLESKY ? (size_t)grid * rank * rank : 0));
     AlsArgs a{};
     a.col_ptrs = d.col_ptrs; a.row_idx = d.row_idx; a.vals = d.vals;
     a.X = d_X; a.Y = d_Y; a.XtX = implicit ? d_XtX : nullptr;
@@ -682,7 +330,7 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
     hipError_t we = wave_cg ? launch_wide_cg_wave(a, implicit, kWideCgMaxLen, d.max_len > kWideCgMaxLen ? d.q_order : nullptr, 0, s)
                             : launch_als_wide(a, implicit, solver, g_ws.wide_m2, g_ws.wide_lu, s);
     if (we != hipSuccess) return hip_fail(we, wave_cg ? "launch_wide_cg_wave" : "launch_als_wide");
-    if ((we = launch_sum_partials(g_ws.partials, wave_cg ? (size_t)grid_w : (size_t)grid, outw, s, g_ws.partials + g_ws.partial_slots)) != hipSuccess)
+    if ((we = launch_sum_partials(g_ws.partials, wave_cg ? (size_t)grid_w : (size_t)grid, outw, s, g_ws.partials + g_ws.partial_slots())) != hipSuccess)
       return hip_fail(we, "launch_sum_partials");
     return RSPARSE_HIP_OK;
   }
@@ -696,17 +344,10 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   // (the global-bias CG keeps bucket 1 on the 8-wave kernel: no 4-wave launch, no loss slots for one)
   qs.team4_first = (implicit && bias && bias->gbias != 0.f) ? d.q_off[2] : d.q_team4_first;
   qs.pair_wide = cgp_wide_supported(rank, implicit, implicit && bias && bias->gbias != 0.f);
-  // (two workgroups per CU only for implicit feedback at rank 97..128: the fp16 QUAD kernel of wrmf_ne.hip)
-  const bool ne_fine = implicit && padded_rank(rank) == 128;
-  qs.ne_rows = ne_fine ? d.q_ne_rows : d.q_ne1_rows; qs.ne_ptr = ne_fine ? d.q_ne_ptr : d.q_ne1_ptr;
-  qs.ne_wg = ne_fine ? d.q_ne_wg : d.q_ne1_wg; qs.ne_entries = d.q_ne_entries;
-  qs.ne_split_rows = d.q_ne_split_rows; qs.ne_split_ptr = d.q_ne_split_ptr; qs.ne_nsplit = d.q_ne_nsplit;
   // round 6, rank 128, implicit conjugate gradient without bias operands: the rows of 513..kCgMfMax non-zeros of the first bucket on
   // the wave-per-row kernel of wrmf_cg_mf.hip, the giant rows (a prefix of the order) on the normal-equation kernel's second lists
   const bool cg_mf = cgq && implicit && !bias && cg_mf_supported(rank, implicit) && d.q_order && d.q_off[1] > d.q_n_nec;
   if (cg_mf) {
-    qs.ne_rows = d.q_nec_rows; qs.ne_ptr = d.q_nec_ptr; qs.ne_wg = d.q_nec_wg; qs.ne_entries = d.q_nec_entries;
-    qs.ne_split_rows = d.q_nec_split_rows; qs.ne_split_ptr = d.q_nec_split_ptr; qs.ne_nsplit = d.q_nec_nsplit;
     qs.mf_rows = d.q_order + d.q_n_nec;
     qs.mf_n = d.q_off[1] - d.q_n_nec;
   }
@@ -720,19 +361,17 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
                        use_cgq(rank, d_X, d_Y) && d.q_lr_first > d.q_off[1];
   const int mf_first = d.q_off[1];
   const int n_mf = chol_mf ? d.q_lr_first - mf_first : 0;
-  const bool nec_lists = padded_rank(rank) > 64 && d.q_nec_wg > 0 && !chol_mf;
-  const bool ne_chol = !cg && solver == RSPARSE_SOLVER_CHOLESKY && !bias && (nec_lists || d.q_ne_wg > 0 || chol_mf) &&
+  const bool nec_lists = padded_rank(rank) > 64 && d.q_nec.wg > 0 && !chol_mf;
+  const bool ne_chol = !cg && solver == RSPARSE_SOLVER_CHOLESKY && !bias && (nec_lists || d.q_ne.wg > 0 || chol_mf) &&
                        ne_supported(rank) && use_cgq(rank, d_X, d_Y);
-  if (ne_chol && nec_lists) {   // its own lists: the rows beyond kCgMfMax non-zeros
-    qs.ne_rows = d.q_nec_rows; qs.ne_ptr = d.q_nec_ptr; qs.ne_wg = d.q_nec_wg; qs.ne_entries = d.q_nec_entries;
-    qs.ne_split_rows = d.q_nec_split_rows; qs.ne_split_ptr = d.q_nec_split_ptr; qs.ne_nsplit = d.q_nec_nsplit;
-  }
-  const int ne_nseg = ((ne_chol && nec_lists) || cg_mf) ? d.q_nec_nseg : d.q_ne_nseg;
-  const int32_t* ne_segs = ((ne_chol && nec_lists) || cg_mf) ? d.q_nec_segs : d.q_ne_segs;
+  // which lists the normal-equation launch walks: the rows beyond kCgMfMax non-zeros beside wrmf_cg_mf.hip and for the exact
+  // solve's own lists; else the streamed bucket's -- many lists where two workgroups per CU pick them up (only for implicit
+  // feedback at rank 97..128: the fp16 QUAD kernel of wrmf_ne.hip), else one list per slot
+  qs.ne = (cg_mf || (ne_chol && nec_lists)) ? d.q_nec : ((implicit && padded_rank(rank) == 128) ? d.q_ne : d.q_ne1);
   const size_t chol_base = chol2_loss_slots(d.n_cols);
   const size_t slots = cgq ? cgq_loss_slots(qs, rank, implicit) : (cg ? cg_loss_slots(d.n_cols, d.n_long)
                                    : (solver == RSPARSE_SOLVER_NNLS ? chol_loss_slots(d.n_cols)
-                                      : chol_base + (ne_chol ? (size_t)(qs.ne_entries + qs.ne_nsplit) : 0) +
+                                      : chol_base + (ne_chol ? (size_t)(qs.ne.entries + qs.ne.nsplit) : 0) +
                                             (size_t)(chol_mf ? chol_mf_loss_slots(n_mf, implicit) : 0) + (size_t)kLuGrid));
   if ((rc = g_ws.ensure_partials(slots))) return rc;
   double* out = d_loss_rows_out ? d_loss_rows_out : g_ws.scalars;
@@ -743,14 +382,14 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   AlsArgs a;
   a.col_ptrs = d.col_ptrs; a.row_idx = d.row_idx; a.vals = d.vals;
   a.X = d_X; a.Y = d_Y; a.XtX = implicit ? d_XtX : nullptr;
-  a.long_rows = d.long_rows; a.n_long = d.n_long; a.n_cols = d.n_cols;
+  a.long_rows = d.n_long ? d.q_order : nullptr; a.n_long = d.n_long; a.n_cols = d.n_cols;
   a.chol_long_rows = d.q_order; a.n_chol_long = d.q_order ? d.q_n_chol_long : 0;
   a.chol_list = nullptr; a.chol_first = 0; a.chol_n_main = 0; a.chol_empty_first = 0;
   a.lr_rows = nullptr; a.n_lr = 0; a.lr_flags = nullptr; a.lr_M = nullptr; a.lr_n_gt32 = a.lr_n_gt16 = a.lr_n_gt48 = -1; a.lrx = 0;
   a.nnls_order = solver == RSPARSE_SOLVER_NNLS ? d.q_order : nullptr;
   a.nnls_lhs = nullptr;
   if (solver == RSPARSE_SOLVER_NNLS && padded_rank(rank) == 128) {   // (the wide family's buffer: no rank uses both)
-    if ((rc = g_ws.ensure_wide(chol_loss_slots(d.n_cols) * (size_t)128 * 128, 0))) return rc;
+    HIP_TRY(g_ws.wide_m2.ensure(chol_loss_slots(d.n_cols) * (size_t)128 * 128));
     a.nnls_lhs = g_ws.wide_m2;
   }
   a.k = rank; a.cg_steps = (int)cg_steps;
@@ -778,33 +417,43 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
     a.chol_n_main = std::max(0, d.q_lr_first - first);
     a.chol_empty_first = d.q_lr_first + d.q_n_lr;
   }
-  if ((cgq || ne_chol) && ne_nseg > 0 && ne_supported(rank)) {
-    if ((rc = g_ws.ensure_ne_seg((size_t)ne_nseg))) return rc;
-    a.ne_segs = ne_segs; a.ne_seg_scratch = g_ws.ne_seg_scratch; a.ne_seg_flags = g_ws.ne_seg_flags;
+  if ((cgq || ne_chol) && qs.ne.nseg > 0 && ne_supported(rank)) {
+    HIP_TRY(g_ws.ne_seg_scratch.ensure((size_t)qs.ne.nseg * (size_t)kNeSegFloats));
+    HIP_TRY(g_ws.ne_seg_flags.ensure((size_t)qs.ne.nseg));
+    a.ne_segs = qs.ne.segs; a.ne_seg_scratch = g_ws.ne_seg_scratch; a.ne_seg_flags = g_ws.ne_seg_flags;
   }
-  if (chol_mf) {   // the operand scales of its matrix-core assembly (max |X|, max c)
+  // the statistics of the values and of X in g_ws.ne_stats (take_value_stats): scanned by the first launch set-up below that
+  // wants them, once per call
+  bool stats_taken = false;
+  auto want_stats = [&]() -> int {
+    if (stats_taken) return RSPARSE_HIP_OK;
     hipError_t se = take_value_stats(d, d_X, (int64_t)d.n_rows * rank, s, d_absmax);
     if (se != hipSuccess) return hip_fail(se, "launch_ne_stats");
+    stats_taken = true;
+    return RSPARSE_HIP_OK;
+  };
+  if (chol_mf) {   // the operand scales of its matrix-core assembly (max |X|, max c)
+    if ((rc = want_stats())) return rc;
     a.wave_stats = g_ws.ne_stats;
     if (implicit) {
       a.ne_stats = g_ws.ne_stats;
       a.mf_XtX = d_XtX;
       if (rank != 128) {
-        if ((rc = g_ws.ensure_mf())) return rc;
+        HIP_TRY(g_ws.mf_G.ensure((size_t)128 * 128));
         hipError_t pe = launch_pad_gramian(d_XtX, rank, 128, g_ws.mf_G, s);
         if (pe != hipSuccess) return hip_fail(pe, "launch_pad_gramian");
         a.mf_XtX = g_ws.mf_G;
       }
     }
   }
-  if (!a.ne_stats && (cgq || ne_chol) && implicit && (qs.ne_wg > 0 || qs.mf_n > 0) && ne_supported(rank) && (!bias || gb_cg)) {
+  if (!a.ne_stats && (cgq || ne_chol) && implicit && (qs.ne.wg > 0 || qs.mf_n > 0) && ne_supported(rank) && (!bias || gb_cg)) {
     // operand scales of the fp16 normal-equation kernel (and whether it may run at all), decided on the device
-    hipError_t se = take_value_stats(d, d_X, (int64_t)d.n_rows * rank, s, d_absmax);
-    if (se != hipSuccess) return hip_fail(se, "launch_ne_stats");
+    if ((rc = want_stats())) return rc;
     a.ne_stats = g_ws.ne_stats;
     if (gb_cg && cgq) {   // the long rows' share of the first residual: base - g X_nnz (c - 1), one more pass over them
       const int n_ne = d.q_off[1];
-      if ((rc = g_ws.ensure_gb((size_t)n_ne * rank, (size_t)d.n_cols))) return rc;
+      HIP_TRY(g_ws.gb_r0.ensure((size_t)n_ne * rank));
+      HIP_TRY(g_ws.gb_slot.ensure((size_t)d.n_cols));
       hipError_t ge = launch_gb_row_terms(a, d.q_order, n_ne, g_ws.gb_r0, g_ws.gb_slot, s);
       if (ge != hipSuccess) return hip_fail(ge, "launch_gb_row_terms");
       a.ne_r0 = g_ws.gb_r0; a.ne_r0_slot = g_ws.gb_slot;
@@ -813,17 +462,15 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   // ranks the normal-equation kernel does not take (<= 32): the streamed CG bucket keeps its per-sweep dot products in
   // an HBM scratch instead of re-gathering for the loss
   if (cgq && !ne_supported(rank) && d.q_stream_off && d.q_nnz[0] > 0 && cg_steps >= 1 && cg_steps <= 4) {
-    if ((rc = g_ws.ensure_tscr((size_t)(cg_steps + 1) * (size_t)d.q_nnz[0]))) return rc;
+    HIP_TRY(g_ws.tscr.ensure((size_t)(cg_steps + 1) * (size_t)d.q_nnz[0]));
     a.tscr = g_ws.tscr;
   }
   if (!cg && solver == RSPARSE_SOLVER_CHOLESKY && d.q_order && d.q_n_lr > 0 && chol_lr_supported(a, implicit)) {
     // low-rank form for the short rows; "some confidence < 1" comes from the values scan of launch_ne_stats (word 2)
-    if ((rc = g_ws.ensure_lr())) return rc;
-    if (!a.ne_stats) {   // (with the long rows on the normal-equation kernel the full statistics were just taken)
-      // max |X| too: the low-rank kernel scales its fp16 operand terms by it
-      hipError_t se = take_value_stats(d, d_X, (int64_t)d.n_rows * rank, s, d_absmax);
-      if (se != hipSuccess) return hip_fail(se, "launch_ne_stats");
-    }
+    HIP_TRY(g_ws.lr_M.ensure((size_t)3 * 128 * 128));
+    // (with the long rows on the normal-equation kernel the full statistics were just taken)
+    // max |X| too: the low-rank kernel scales its fp16 operand terms by it
+    if ((rc = want_stats())) return rc;
     a.lr_rows = d.q_order + d.q_lr_first; a.n_lr = d.q_n_lr; a.lr_flags = g_ws.ne_stats + 2; a.lr_M = g_ws.lr_M;
     a.lr_n_gt32 = d.q_gt32 - d.q_lr_first; a.lr_n_gt16 = d.q_pair_first - d.q_lr_first;
     a.lr_n_gt48 = d.q_gt48 - d.q_lr_first;
@@ -831,10 +478,7 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   const bool chol = !cg && solver == RSPARSE_SOLVER_CHOLESKY;
   if (chol && d.q_order && d.q_n_lr > 0 && chol_lrx_supported(a, implicit)) {
     // explicit feedback, ranks 64 / 128: the rows of 1..64 ratings in push-through form, one wave per pass
-    if (!a.ne_stats && !a.wave_stats) {
-      hipError_t se = take_value_stats(d, d_X, (int64_t)d.n_rows * rank, s, d_absmax);
-      if (se != hipSuccess) return hip_fail(se, "launch_ne_stats");
-    }
+    if ((rc = want_stats())) return rc;
     a.wave_stats = g_ws.ne_stats;
     a.lr_rows = d.q_order + d.q_lr_first; a.n_lr = d.q_n_lr; a.lrx = 1;
     a.lr_n_gt32 = d.q_gt32 - d.q_lr_first; a.lr_n_gt16 = d.q_pair_first - d.q_lr_first;
@@ -842,10 +486,7 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   }
   if (chol && chol_wave_supported(rank) && padded_rank(rank) == 64) {
     // rank 33..64, one wave per row: the assembly runs on the matrix cores from fp16 operand terms scaled by max |X| (and max c)
-    if (!a.ne_stats && !a.wave_stats) {
-      hipError_t se = take_value_stats(d, d_X, (int64_t)d.n_rows * rank, s, d_absmax);
-      if (se != hipSuccess) return hip_fail(se, "launch_ne_stats");
-    }
+    if ((rc = want_stats())) return rc;
     a.wave_stats = g_ws.ne_stats;
   }
   if (chol) {
@@ -854,7 +495,7 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   }
   hipEvent_t* ev = g_prof.begin();
   if (chol && ev) HIP_TRY(hipEventRecord(ev[0], s));   // Cholesky: [0] normal-equation launch, [1] low-rank, [2] k x k, [3] wave-per-row (rank 65..128), [4] loss
-  if (ne_chol && qs.ne_wg > 0 && mf_first != 0) {
+  if (ne_chol && qs.ne.wg > 0 && mf_first != 0) {
     hipError_t ne = launch_als_ne(a, qs, implicit, g_ws.partials + chol_base, s, ev);
     if (ne != hipSuccess) return hip_fail(ne, "launch_als_ne");
   }
@@ -865,7 +506,7 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
                                   : launch_als_chol2(a, implicit, s, ev ? ev + 1 : nullptr)));
   if (e != hipSuccess) return hip_fail(e, cgq ? "launch_als_cgq" : (cg ? "launch_als_cg" : "launch_als_chol"));
   if (chol_mf) {   // (launch_als_chol2 recorded ev[3] behind its kernels)
-    const size_t mf_base = chol_base + (size_t)(qs.ne_entries + qs.ne_nsplit);
+    const size_t mf_base = chol_base + (size_t)(qs.ne.entries + qs.ne.nsplit);
     hipError_t me = launch_als_chol_mf(a, implicit, d.q_order + mf_first, n_mf, (int)mf_base, s, ev ? ev + 3 : nullptr);
     if (me != hipSuccess) return hip_fail(me, "launch_als_chol_mf");
   }
@@ -876,7 +517,7 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
     if ((e = launch_als_lu_fallback(a, implicit, slots - (size_t)kLuGrid, s)) != hipSuccess)
       return hip_fail(e, "launch_als_lu_fallback");
   }
-  e = launch_sum_partials(g_ws.partials, slots, out, s, g_ws.partials + g_ws.partial_slots);
+  e = launch_sum_partials(g_ws.partials, slots, out, s, g_ws.partials + g_ws.partial_slots());
   if (e != hipSuccess) return hip_fail(e, "launch_sum_partials");
   if (ev) {
     const int last = cgq ? 7 : (chol ? 5 : 3);
@@ -913,7 +554,7 @@ int run_half_iteration_explicit_biased(const rsparse_hip_csc* conf, const float*
   // the copies are padded to a multiple of 4 (wrmf_bias.hip: why) -- unless the padding would make the systems singular
   const int k1p = zero_padding_is_neutral(false, solver, lambda) ? std::min((k1 + 3) & ~3, RSPARSE_HIP_MAX_RANK) : k1;
   const size_t nx = (size_t)d.n_rows * k1p, ny = (size_t)d.n_cols * k1p, nv = (size_t)std::max<int64_t>(d.nnz, 1);
-  if ((rc = g_ws.ensure_bias(nx + ny + nv + 16))) return rc;
+  HIP_TRY(g_ws.bias_buf.ensure(nx + ny + nv + 16));
   float* Xp = g_ws.bias_buf;
   float* Yp = Xp + nx;
   float* vp = Yp + ny;
@@ -922,10 +563,10 @@ int run_half_iteration_explicit_biased(const rsparse_hip_csc* conf, const float*
   if ((e = launch_pad_rows(d_Y, rank, ioff, k1, k1p, d.n_cols, Yp, s)) != hipSuccess) return hip_fail(e, "launch_pad_rows");
   e = launch_bias_shift_values(d.vals, d.row_idx, d_X, rank, xb, d.nnz, vp, s);
   if (e != hipSuccess) return hip_fail(e, "launch_bias_shift_values");
-  rsparse_hip_csc shifted = *conf;   // same sparsity and schedule, shifted ratings (a view: never destroyed)
+  rsparse_hip_csc shifted;   // same sparsity and schedule, shifted ratings (a view: it owns nothing and is never destroyed)
+  shifted.d = conf->d; shifted.device = conf->device;
   shifted.d.vals_frozen = false; shifted.d.vstats_valid = false; shifted.d.vstats = nullptr;   // (its values are this call's)
   shifted.d.vals = vp;
-  shifted.d.owns_matrix = false;
   rc = run_half_iteration(&shifted, false, Xp, Yp, nullptr, k1p, lambda, solver, cg_steps, dynamic_lambda,
                           d_loss_rows_out, s);
   if (rc) return rc;
@@ -955,7 +596,7 @@ int run_half_iteration_implicit_biased(const rsparse_hip_csc* conf, const float*
   const int k1p = std::min((k1 + 3) & ~3, RSPARSE_HIP_MAX_RANK);   // the copies are padded to a multiple of 4 (wrmf_bias.hip: why)
   const size_t nx = (size_t)d.n_rows * k1p, ny = (size_t)d.n_cols * k1p, nv = (size_t)std::max<int64_t>(d.nnz, 1);
   const size_t nscr = bias_rhs_init_scratch_floats(), ng = (size_t)k1p * k1p;
-  if ((rc = g_ws.ensure_bias(nx + ny + 2 * nv + nscr + ng + 16))) return rc;
+  HIP_TRY(g_ws.bias_buf.ensure(nx + ny + 2 * nv + nscr + ng + 16));
   float* Xp = g_ws.bias_buf;
   float* Yp = Xp + nx;
   float* rcoef = Yp + ny;
@@ -1001,7 +642,7 @@ int run_half_iteration_implicit_global(const rsparse_hip_csc* conf, const float*
   if (rc) return rc;
   const DevCSC& d = conf->d;
   const size_t nscr = bias_rhs_init_scratch_floats();
-  if ((rc = g_ws.ensure_bias(nscr + 16))) return rc;
+  HIP_TRY(g_ws.bias_buf.ensure(nscr + 16));
   float* scratch = g_ws.bias_buf;
   float* rinit = scratch + (nscr - 256);
   if (d_base_in) {
@@ -1018,12 +659,11 @@ int run_half_iteration_implicit_global(const rsparse_hip_csc* conf, const float*
                             &bt, d_absmax);
 }
 
-// Shared body of the four stateless drop-ins.  TX = float or double (host element type).
-template <class TX>
+// Shared body of the two stateless fp32 drop-ins (the `_double` ones: wrmf_f64_capi.cpp).
 int stateless(bool implicit, int n_rows, int n_cols, const int32_t* col_ptrs, const int32_t* row_indices,
-              const double* values, const TX* X, TX* Y, const TX* XtX, const TX* cnt_X, int rank, double lambda,
+              const double* values, const float* X, float* Y, const float* XtX, const float* cnt_X, int rank, double lambda,
               unsigned solver, unsigned cg_steps, int dynamic_lambda, double* loss_out, int with_biases = 0,
-              int is_x_bias_last_row = 0, double global_bias = 0.0, TX* global_bias_base = nullptr,
+              int is_x_bias_last_row = 0, double global_bias = 0.0, float* global_bias_base = nullptr,
               int global_bias_base_len = 0, int initialize_bias_base = 1) {
   rsparse_hip_csc* conf = nullptr;
   int rc = rsparse_hip_csc_create_host(n_rows, n_cols, col_ptrs, row_indices, values, &conf);
@@ -1034,12 +674,8 @@ int stateless(bool implicit, int n_rows, int n_cols, const int32_t* col_ptrs, co
   DevBuf dX, dY, dG, dW;
   HIP_TRY(dX.alloc(nx * 4));
   HIP_TRY(dY.alloc(ny * 4));
-  std::vector<float> tmp;
-  auto upload = [&](DevBuf& b, const TX* src, size_t n) -> hipError_t {
-    if (!n) return hipSuccess;
-    if (sizeof(TX) == sizeof(float)) return hipMemcpy(b.p, src, n * 4, hipMemcpyHostToDevice);
-    tmp = to_f32(src, n);
-    return hipMemcpy(b.p, tmp.data(), n * 4, hipMemcpyHostToDevice);
+  auto upload = [](DevBuf& b, const float* src, size_t n) -> hipError_t {
+    return n ? hipMemcpy(b.p, src, n * 4, hipMemcpyHostToDevice) : hipSuccess;
   };
   HIP_TRY(upload(dX, X, nx));
   HIP_TRY(upload(dY, Y, ny));
@@ -1058,7 +694,7 @@ int stateless(bool implicit, int n_rows, int n_cols, const int32_t* col_ptrs, co
   // counters left behind by earlier device-resident calls are not this call's: set aside here, handed back when this call
   // ends (a stateless call between a resident fit's half-iterations and its check must not swallow the fit's failures)
   StaleFailures stale_guard;
-  const bool gbias = implicit && has_global_bias(global_bias, sizeof(TX) == sizeof(double));
+  const bool gbias = implicit && has_global_bias(global_bias);
   DevBuf dBase;
   if (gbias && !with_biases) {
     // global_bias_base = -global_bias * rowSums(X), `rank` entries (wrmf_implicit.hpp:111-112).  The caller's buffer holds
@@ -1076,12 +712,11 @@ int stateless(bool implicit, int n_rows, int n_cols, const int32_t* col_ptrs, co
     if (!rc && !given && initialize_bias_base && blen > 0) {
       std::vector<float> hb((size_t)rank);
       HIP_TRY(hipMemcpy(hb.data(), dBase.p, (size_t)rank * 4, hipMemcpyDeviceToHost));
-      for (int t = 0; t < std::min(blen, rank); t++) global_bias_base[t] = (TX)hb[(size_t)t];
+      for (int t = 0; t < std::min(blen, rank); t++) global_bias_base[t] = hb[(size_t)t];
     }
   } else if (with_biases && implicit)
     rc = run_half_iteration_implicit_biased(conf, dX.as<float>(), dY.as<float>(), dG.as<float>(), rank, lambda, solver,
-                                            is_x_bias_last_row, g_ws.scalars, nullptr, global_bias,
-                                            sizeof(TX) == sizeof(double));
+                                            is_x_bias_last_row, g_ws.scalars, nullptr, global_bias);
   else if (with_biases)
     rc = run_half_iteration_explicit_biased(conf, dX.as<float>(), dY.as<float>(), rank, lambda, solver, cg_steps,
                                             dynamic_lambda, is_x_bias_last_row, g_ws.scalars, nullptr);
@@ -1112,15 +747,7 @@ int stateless(bool implicit, int n_rows, int n_cols, const int32_t* col_ptrs, co
   double host_scalars[2] = {0, 0};
   HIP_TRY(hipMemcpy(host_scalars, g_ws.scalars, 2 * sizeof(double), hipMemcpyDeviceToHost));
   if (lambda > 0 && nx > 0) reg = lambda * host_scalars[1];
-  if (ny) {
-    if (sizeof(TX) == sizeof(float)) {
-      HIP_TRY(hipMemcpy(Y, dY.p, ny * 4, hipMemcpyDeviceToHost));
-    } else {
-      tmp.resize(ny);
-      HIP_TRY(hipMemcpy(tmp.data(), dY.p, ny * 4, hipMemcpyDeviceToHost));
-      for (size_t i = 0; i < ny; i++) Y[i] = (TX)tmp[i];
-    }
-  }
+  if (ny) HIP_TRY(hipMemcpy(Y, dY.p, ny * 4, hipMemcpyDeviceToHost));
   const double nnz = (double)conf->d.nnz;
   if (loss_out) *loss_out = (host_scalars[0] + reg) / nnz;  // wrmf_implicit.hpp:304
   if (nfail)
@@ -1182,14 +809,17 @@ int rsparse_hip_csc_create_host(int n_rows, int n_cols, const int32_t* col_ptrs,
   struct Guard { rsparse_hip_csc* c; ~Guard() { if (c) rsparse_hip_csc_destroy(c); } } guard{m};
   if (hipGetDevice(&m->device) != hipSuccess) return fail(RSPARSE_HIP_ERR_RUNTIME, "no HIP device");
   DevCSC& d = m->d;
-  d.n_rows = n_rows; d.n_cols = n_cols; d.nnz = nnz; d.owns_matrix = true;
+  d.n_rows = n_rows; d.n_cols = n_cols; d.nnz = nnz;
   int32_t *dp = nullptr, *di = nullptr;
   float* dv = nullptr;
   HIP_TRY(hipMalloc(&dp, ((size_t)n_cols + 1) * 4));
+  m->owned.push_back(dp);
   d.col_ptrs = dp;
   HIP_TRY(hipMalloc(&di, (size_t)std::max<int64_t>(nnz, 4) * 4));
+  m->owned.push_back(di);
   d.row_idx = di;
   HIP_TRY(hipMalloc(&dv, (size_t)std::max<int64_t>(nnz, 4) * 4));
+  m->owned.push_back(dv);
   d.vals = dv;
   HIP_TRY(hipMemcpy(dp, col_ptrs, ((size_t)n_cols + 1) * 4, hipMemcpyHostToDevice));
   if (nnz) {
@@ -1199,9 +829,7 @@ int rsparse_hip_csc_create_host(int n_rows, int n_cols, const int32_t* col_ptrs,
     std::vector<float> v32 = to_f32(values, (size_t)nnz);
     HIP_TRY(hipMemcpy(dv, v32.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
   }
-  int rc = build_schedule(d, col_ptrs);
-  if (rc) return rc;
-  if ((rc = build_q_schedule(d, col_ptrs))) return rc;
+  if (int rc = build_schedule(*m, col_ptrs)) return rc;
   guard.c = nullptr;
   *out = m;
   return RSPARSE_HIP_OK;
@@ -1230,11 +858,9 @@ int rsparse_hip_csc_create_device(int n_rows, int n_cols, const int32_t* d_col_p
   struct Guard { rsparse_hip_csc* c; ~Guard() { if (c) rsparse_hip_csc_destroy(c); } } guard{m};
   if (hipGetDevice(&m->device) != hipSuccess) return fail(RSPARSE_HIP_ERR_RUNTIME, "no HIP device");
   DevCSC& d = m->d;
-  d.n_rows = n_rows; d.n_cols = n_cols; d.nnz = nnz; d.owns_matrix = false;
+  d.n_rows = n_rows; d.n_cols = n_cols; d.nnz = nnz;   // (the caller's arrays: not in m->owned)
   d.col_ptrs = d_col_ptrs; d.row_idx = d_row_indices; d.vals = d_values;
-  int rc = build_schedule(d, hp.data());
-  if (rc) return rc;
-  if ((rc = build_q_schedule(d, hp.data()))) return rc;
+  if (int rc = build_schedule(*m, hp.data())) return rc;
   guard.c = nullptr;
   *out = m;
   return RSPARSE_HIP_OK;
@@ -1270,30 +896,8 @@ int rsparse_hip_values_to_float_device(int64_t n, const double* d_src, float* d_
 
 int rsparse_hip_csc_destroy(rsparse_hip_csc* m) {
   if (!m) return RSPARSE_HIP_OK;
-  DevCSC& d = m->d;
-  if (d.long_rows) (void)hipFree(d.long_rows);
-  if (d.q_order) (void)hipFree(d.q_order);
-  if (d.q_stream_off) (void)hipFree(d.q_stream_off);
-  if (d.q_ne_rows) (void)hipFree(d.q_ne_rows);
-  if (d.q_ne1_rows) (void)hipFree(d.q_ne1_rows);
-  if (d.q_ne1_ptr) (void)hipFree(d.q_ne1_ptr);
-  if (d.q_ne_ptr) (void)hipFree(d.q_ne_ptr);
-  if (d.q_ne_segs) (void)hipFree(d.q_ne_segs);
-  if (d.q_ne_split_rows) (void)hipFree(d.q_ne_split_rows);
-  if (d.q_ne_split_ptr) (void)hipFree(d.q_ne_split_ptr);
-  if (d.q_nec_own) {
-    if (d.q_nec_rows) (void)hipFree(d.q_nec_rows);
-    if (d.q_nec_ptr) (void)hipFree(d.q_nec_ptr);
-    if (d.q_nec_segs) (void)hipFree(d.q_nec_segs);
-    if (d.q_nec_split_rows) (void)hipFree(d.q_nec_split_rows);
-    if (d.q_nec_split_ptr) (void)hipFree(d.q_nec_split_ptr);
-  }
-  if (d.vstats) (void)hipFree(d.vstats);
-  if (d.owns_matrix) {
-    if (d.col_ptrs) (void)hipFree(const_cast<int32_t*>(d.col_ptrs));
-    if (d.row_idx) (void)hipFree(const_cast<int32_t*>(d.row_idx));
-    if (d.vals) (void)hipFree(const_cast<float*>(d.vals));
-  }
+  for (void* p : m->owned) (void)hipFree(p);
+  if (m->d.vstats) (void)hipFree(m->d.vstats);
   delete m;
   return RSPARSE_HIP_OK;
 }
@@ -1313,7 +917,7 @@ int rsparse_hip_csc_info(const rsparse_hip_csc* m, int64_t info_out[40]) {
     info_out[14 + b] = m->d.q_nnz[b];
   }
   info_out[20] = m->d.q_cfg;
-  info_out[21] = m->d.q_ne_nseg;
+  info_out[21] = m->d.q_ne.nseg;
   for (int b = 0; b < 6; b++) {
     info_out[22 + b] = cgq_bucket_wpr(m->d.q_cfg, b);
     info_out[28 + b] = cgq_bucket_capq(m->d.q_cfg, b);
@@ -1389,12 +993,12 @@ int rsparse_hip_gramian_absmax_device(const float* d_X, int rank, int64_t n, dou
   int rc = g_ws.ensure_device();
   if (rc) return rc;
   if (wide_supported(rank)) {   // ranks 129..256 (d_absmax_inout is left as it is: only the rank <= 128 long-row kernel reads it)
-    if ((rc = g_ws.ensure_gram(wide_gramian_scratch_floats(rank)))) return rc;
+    HIP_TRY(g_ws.gram.ensure(wide_gramian_scratch_floats(rank)));
     hipError_t we = launch_gramian_wide(d_X, rank, n, (float)lambda, d_XtX_out, d_sumsq_out, g_ws.gram, (hipStream_t)stream);
     if (we != hipSuccess) return hip_fail(we, "launch_gramian_wide");
     return RSPARSE_HIP_OK;
   }
-  if ((rc = g_ws.ensure_gram(gramian_scratch_floats(rank, n)))) return rc;
+  HIP_TRY(g_ws.gram.ensure(gramian_scratch_floats(rank, n)));
   const float ridge = (float)lambda;  // float::fl(diag(lambda)), R/model_WRMF.R:476
   hipEvent_t* ev = g_prof.begin();
   hipError_t e = launch_gramian(d_X, rank, n, ridge, d_XtX_out, d_sumsq_out, g_ws.gram, (hipStream_t)stream, ev,
@@ -1641,8 +1245,7 @@ int rsparse_hip_top_product_device(const float* d_U, const float* d_V, int n_use
   if (n_exclude > 0 && !d_excl0) return fail(RSPARSE_HIP_ERR_INVALID, "exclude is NULL");
   if (k > RSPARSE_HIP_MAX_TOPK) {   // the large-k path (wrmf_topk_large.hip): its key matrix and lists in the grow-only workspace
     if (n_users == 0) return RSPARSE_HIP_OK;
-    int rc = g_ws.ensure_pad(top_product_large_ws_floats(n_users, n_items, k, k));
-    if (rc) return rc;
+    HIP_TRY(g_ws.pad_buf.ensure(top_product_large_ws_floats(n_users, n_items, k, k)));
     hipError_t e = launch_top_product_large(d_U, d_V, n_users, n_items, rank, k, d_nr_p, d_nr_p ? d_nr_j : nullptr, d_excl0, n_exclude,
                                             (float)glob_mean, d_res, d_scores, (hipStream_t)stream, g_ws.pad_buf);
     if (e != hipSuccess) return hip_fail(e, "launch_top_product_large");
@@ -1652,8 +1255,7 @@ int rsparse_hip_top_product_device(const float* d_U, const float* d_V, int n_use
   float* scratch = nullptr;
   const size_t sfl = top_product_scratch_floats(n_users, n_items, rank, k);
   if (sfl > 0) {
-    int rc = g_ws.ensure_pad(sfl);
-    if (rc) return rc;
+    HIP_TRY(g_ws.pad_buf.ensure(sfl));
     scratch = g_ws.pad_buf;
   }
   hipError_t e = launch_top_product(d_U, d_V, n_users, n_items, rank, k, d_nr_p, d_nr_p ? d_nr_j : nullptr, d_excl0,
@@ -1675,8 +1277,7 @@ int rsparse_hip_top_product_f64_device(const float* d_U, const float* d_V, const
   if (k > RSPARSE_HIP_MAX_TOPK) {   // the large-k path: kc = k + extra candidates (at most 10240), re-scored in double
     if (n_exclude > 0 && !d_excl0) return fail(RSPARSE_HIP_ERR_INVALID, "exclude is NULL");
     const int kcl = top_product_large_kc(k, extra, n_items);
-    int rc = g_ws.ensure_pad(top_product_large_ws_floats(n_users, n_items, k, kcl));
-    if (rc) return rc;
+    HIP_TRY(g_ws.pad_buf.ensure(top_product_large_ws_floats(n_users, n_items, k, kcl)));
     hipError_t e = launch_top_product_large_f64(d_U, d_V, d_U64, d_V64, n_users, n_items, rank, k, kcl, d_nr_p, d_nr_p ? d_nr_j : nullptr,
                                                 d_excl0, n_exclude, glob_mean, d_res, d_scores, (hipStream_t)stream, g_ws.pad_buf);
     if (e != hipSuccess) return hip_fail(e, "launch_top_product_large_f64");
@@ -1685,12 +1286,11 @@ int rsparse_hip_top_product_f64_device(const float* d_U, const float* d_V, const
   // candidates per user: k + extra (default: a quarter of k, at least 8), never more than the kernel's 256 or the items
   if (extra < 0) extra = std::max(8, k / 4);
   const int kc = std::max(k, std::min(std::min(k + extra, RSPARSE_HIP_MAX_TOPK), std::max(n_items, 1)));
-  int rc = g_ws.ensure_bias(top_product_f64_scratch_words(n_users, kc, k));   // (nothing else uses this buffer meanwhile)
-  if (rc) return rc;
+  HIP_TRY(g_ws.bias_buf.ensure(top_product_f64_scratch_words(n_users, kc, k)));   // (nothing else uses this buffer meanwhile)
   float* split = nullptr;   // few users over many items: the nominating pass splits the items over the workgroups
   const size_t sfl = top_product_scratch_floats(n_users, n_items, rank, kc);   // (or the candidate buffers of a large k)
   if (sfl > 0) {
-    if ((rc = g_ws.ensure_pad(sfl))) return rc;
+    HIP_TRY(g_ws.pad_buf.ensure(sfl));
     split = g_ws.pad_buf;
   }
   hipError_t e = launch_top_product_f64(d_U, d_V, d_U64, d_V64, n_users, n_items, rank, k, kc, d_nr_p, d_nr_p ? d_nr_j : nullptr,
@@ -1812,7 +1412,7 @@ int rsparse_hip_similar_items_device(const float* d_Vn32, const double* d_Vn64, 
   if (n_q == 0) return RSPARSE_HIP_OK;
   if ((rc = g_ws.ensure_device())) return rc;
   const int B = similar_items_batch(k);
-  if ((rc = g_ws.ensure_sim(similar_query_ws_bytes(std::min(n_q, B), r)))) return rc;
+  HIP_TRY(g_ws.sim_buf.ensure(similar_query_ws_bytes(std::min(n_q, B), r)));
   hipStream_t s = (hipStream_t)stream;
   for (int a0 = 0; a0 < n_q; a0 += B) {   // (batches reuse the workspace: they are ordered on the stream)
     const int nb = std::min(B, n_q - a0);
@@ -1908,7 +1508,7 @@ int rsparse_hip_ranking_metrics_device(const int32_t* d_pred, int n_users, int k
   int rc = ranking_metrics_args(d_pred, n_users, k, d_p, d_j, d_x, d_ap_out, d_ndcg_out);
   if (rc || n_users == 0) return rc;
   if ((rc = g_ws.ensure_device())) return rc;
-  if ((rc = g_ws.ensure_met((size_t)n_users + 1))) return rc;
+  HIP_TRY(g_ws.met_buf.ensure((size_t)n_users + 1));
   hipError_t e = launch_ranking_metrics(d_pred, n_users, k, d_p, d_j, d_ndcg_out ? d_x : nullptr, d_ap_out, d_ndcg_out,
                                         g_ws.met_buf, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "launch_ranking_metrics");
@@ -1977,25 +1577,21 @@ int rsparse_hip_als_implicit_float(int n_rows, int n_cols, const int32_t* col_pt
                                    float* global_bias_base, int global_bias_base_len, int initialize_bias_base,
                                    double* loss_out) {
   (void)n_threads;
-  int rc = check_common(n_rows, n_cols, col_ptrs, row_indices, values, X, Y, rank);
+  int rc = check_common(n_rows, n_cols, col_ptrs, X, Y, rank);
   if (rc) return rc;
   if ((rc = check_variant(solver, with_biases, global_bias))) return rc;
-  return stateless<float>(true, n_rows, n_cols, col_ptrs, row_indices, values, X, Y, XtX, nullptr, rank, lambda,
-                          solver, cg_steps, 0, loss_out, with_biases, is_x_bias_last_row, global_bias, global_bias_base,
-                          global_bias_base_len, initialize_bias_base);
+  return stateless(true, n_rows, n_cols, col_ptrs, row_indices, values, X, Y, XtX, nullptr, rank, lambda, solver, cg_steps, 0,
+                   loss_out, with_biases, is_x_bias_last_row, global_bias, global_bias_base, global_bias_base_len,
+                   initialize_bias_base);
 }
 
-}  // extern "C"
-
-namespace {
-
-// Stateless counterpart of the .Call targets _rsparse_initialize_biases_{double,float} (src/wrmf_init.cpp:5-34,
-// src/RcppExports.cpp:417-454): the two S4 matrices flattened to their slots, bias vectors in TX.
-template <class TX>
-int initialize_biases_host(int n_users, int n_items, const int32_t* csc_p, const int32_t* csc_i, double* csc_x,
-                           const int32_t* csr_p, const int32_t* csr_i, double* csr_x, TX* user_bias, TX* item_bias,
-                           double lambda, int dynamic_lambda, int non_negative, int calculate_global_bias,
-                           int is_explicit_feedback, double* global_bias_out) {
+// Stateless counterpart of the .Call target _rsparse_initialize_biases_float (src/wrmf_init.cpp:5-34,
+// src/RcppExports.cpp:417-454): the two S4 matrices flattened to their slots.  (The `_double` one: wrmf_f64_capi.cpp.)
+int rsparse_hip_initialize_biases_float(int n_users, int n_items, const int32_t* csc_p, const int32_t* csc_i,
+                                        double* csc_x, const int32_t* csr_p, const int32_t* csr_i, double* csr_x,
+                                        float* user_bias, float* item_bias, double lambda, int dynamic_lambda,
+                                        int non_negative, int calculate_global_bias, int is_explicit_feedback,
+                                        double* global_bias_out) {
   if (!user_bias || !item_bias) return fail(RSPARSE_HIP_ERR_INVALID, "user_bias or item_bias is NULL");
   rsparse_hip_csc *c_ui = nullptr, *c_iu = nullptr;
   int rc = rsparse_hip_csc_create_host(n_users, n_items, csc_p, csc_i, csc_x, &c_ui);   // columns = items
@@ -2006,10 +1602,8 @@ int initialize_biases_host(int n_users, int n_items, const int32_t* csc_p, const
   DevBuf dU, dI;
   HIP_TRY(dU.alloc((size_t)n_users * 4));
   HIP_TRY(dI.alloc((size_t)n_items * 4));
-  std::vector<float> tmp = to_f32(user_bias, (size_t)n_users);
-  if (n_users) HIP_TRY(hipMemcpy(dU.p, tmp.data(), (size_t)n_users * 4, hipMemcpyHostToDevice));
-  tmp = to_f32(item_bias, (size_t)n_items);
-  if (n_items) HIP_TRY(hipMemcpy(dI.p, tmp.data(), (size_t)n_items * 4, hipMemcpyHostToDevice));
+  if (n_users) HIP_TRY(hipMemcpy(dU.p, user_bias, (size_t)n_users * 4, hipMemcpyHostToDevice));
+  if (n_items) HIP_TRY(hipMemcpy(dI.p, item_bias, (size_t)n_items * 4, hipMemcpyHostToDevice));
   double gb = 0.0;
   if (is_explicit_feedback)
     rc = rsparse_hip_initialize_biases_explicit_device(c_ui, c_iu, dU.as<float>(), dI.as<float>(), lambda, dynamic_lambda,
@@ -2019,11 +1613,8 @@ int initialize_biases_host(int n_users, int n_items, const int32_t* csc_p, const
                                                        calculate_global_bias, &gb, nullptr);
   if (rc) return rc;
   HIP_TRY(hipDeviceSynchronize());
-  tmp.resize((size_t)std::max(n_users, n_items));
-  if (n_users) HIP_TRY(hipMemcpy(tmp.data(), dU.p, (size_t)n_users * 4, hipMemcpyDeviceToHost));
-  for (int e = 0; e < n_users; e++) user_bias[e] = (TX)tmp[(size_t)e];
-  if (n_items) HIP_TRY(hipMemcpy(tmp.data(), dI.p, (size_t)n_items * 4, hipMemcpyDeviceToHost));
-  for (int e = 0; e < n_items; e++) item_bias[e] = (TX)tmp[(size_t)e];
+  if (n_users) HIP_TRY(hipMemcpy(user_bias, dU.p, (size_t)n_users * 4, hipMemcpyDeviceToHost));
+  if (n_items) HIP_TRY(hipMemcpy(item_bias, dI.p, (size_t)n_items * 4, hipMemcpyDeviceToHost));
   if (is_explicit_feedback && calculate_global_bias) {
     // the reference removes the global mean from the @x slots of BOTH matrices in place (wrmf_utils.hpp:41-52)
     const int64_t nnz = csc_p[n_items];
@@ -2034,36 +1625,16 @@ int initialize_biases_host(int n_users, int n_items, const int32_t* csc_p, const
   return RSPARSE_HIP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rsparse_hip_initialize_biases_float(int n_users, int n_items, const int32_t* csc_p, const int32_t* csc_i,
-                                        double* csc_x, const int32_t* csr_p, const int32_t* csr_i, double* csr_x,
-                                        float* user_bias, float* item_bias, double lambda, int dynamic_lambda,
-                                        int non_negative, int calculate_global_bias, int is_explicit_feedback,
-                                        double* global_bias_out) {
-  return initialize_biases_host<float>(n_users, n_items, csc_p, csc_i, csc_x, csr_p, csr_i, csr_x, user_bias, item_bias,
-                                       lambda, dynamic_lambda, non_negative, calculate_global_bias, is_explicit_feedback,
-                                       global_bias_out);
-}
-}  // extern "C"
-
-namespace {
-}  // namespace
-
-extern "C" {
-
 int rsparse_hip_als_explicit_float(int n_rows, int n_cols, const int32_t* col_ptrs, const int32_t* row_indices,
                                    const double* values, const float* X, float* Y, const float* cnt_X, int rank,
                                    double lambda, unsigned n_threads, unsigned solver, unsigned cg_steps,
                                    int dynamic_lambda, int with_biases, int is_x_bias_last_row, double* loss_out) {
   (void)n_threads;
-  int rc = check_common(n_rows, n_cols, col_ptrs, row_indices, values, X, Y, rank);
+  int rc = check_common(n_rows, n_cols, col_ptrs, X, Y, rank);
   if (rc) return rc;
   if ((rc = check_variant(solver, with_biases, 0.0, false))) return rc;
-  return stateless<float>(false, n_rows, n_cols, col_ptrs, row_indices, values, X, Y, nullptr, cnt_X, rank, lambda,
-                          solver, cg_steps, dynamic_lambda, loss_out, with_biases, is_x_bias_last_row);
+  return stateless(false, n_rows, n_cols, col_ptrs, row_indices, values, X, Y, nullptr, cnt_X, rank, lambda, solver, cg_steps,
+                   dynamic_lambda, loss_out, with_biases, is_x_bias_last_row);
 }
 
 }  // extern "C"

@@ -1167,7 +1167,7 @@ size_t bucket_slots(const QSchedule& q, int b, int k, bool implicit) {
   const int cfg = cfg_of_kp(padded_rank(k));
   const BucketDef d = kBuckets[cfg][b];
   if (d.wpr <= 0) return 0;
-  if (d.stream && ne_supported(k)) return (size_t)(q.ne_entries + q.ne_nsplit) + (size_t)(q.mf_n > 0 ? cg_mf_loss_slots(q.mf_n) : 0);
+  if (d.stream && ne_supported(k)) return (size_t)(q.ne.entries + q.ne.nsplit) + (size_t)(q.mf_n > 0 ? cg_mf_loss_slots(q.mf_n) : 0);
   const int rows = q.off[b + 1] - q.off[b];
   if (b == 1 && padded_rank(k) == 128) {   // (the global-bias variant gets team4_first = off[2] from its caller)
     const int split = team4_first(q);
@@ -1215,10 +1215,10 @@ hipError_t launch_all(const AlsArgs& a, const QSchedule& q, hipStream_t s, hipEv
           /* the giant rows on the normal-equation kernel beside it (few workgroups: they start first, they end last) */ \
           /* (the giant rows' launch is SUBMITTED first: the wave-per-row workgroups live as long as their launch and */ \
           /*  leave no register file for a partner, so a launch submitted behind them starts when they end) */ \
-          const bool mside = overlap && q.ne_wg > 0 && q.mf_n > 0;                                          \
+          const bool mside = overlap && q.ne.wg > 0 && q.mf_n > 0;                                          \
           /* (a fork point of its own in FRONT of the giant rows' launch; the other buckets still fork behind both) */ \
           if (mside && (err = hipEventRecord(g_bs.fork0, s)) != hipSuccess) return err;                     \
-          if (q.ne_wg > 0 &&                                                                                \
+          if (q.ne.wg > 0 &&                                                                                \
               (err = launch_als_ne(a, q, IMPLICIT, a.loss_partials + slot, bs, q.mf_n > 0 ? nullptr : (ev ? ev + B : nullptr))) != hipSuccess) \
             return err;                                                                                     \
           if (q.mf_n > 0) {                                                                                 \
@@ -1227,7 +1227,7 @@ hipError_t launch_all(const AlsArgs& a, const QSchedule& q, hipStream_t s, hipEv
               ms = g_bs.st[B];                                                                              \
               if ((err = hipStreamWaitEvent(ms, g_bs.fork0, 0)) != hipSuccess) return err;                  \
             }                                                                                               \
-            if ((err = launch_als_cg_mf(a, q.mf_rows, q.mf_n, (int)(slot + (size_t)(q.ne_entries + q.ne_nsplit)), ms, \
+            if ((err = launch_als_cg_mf(a, q.mf_rows, q.mf_n, (int)(slot + (size_t)(q.ne.entries + q.ne.nsplit)), ms, \
                                         ev ? ev + B : nullptr)) != hipSuccess)                              \
               return err;                                                                                   \
             if (mside) {                                                                                    \

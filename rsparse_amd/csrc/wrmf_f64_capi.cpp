@@ -77,82 +77,31 @@ int list_long_rows(rsparse_hip_csc_f64& m, const int32_t* host_col_ptrs) {
 
 // grow-only scratch of the fp64 path (one host thread drives the library, as in wrmf_capi.cpp)
 struct WorkspaceF64 {
-  double* gram = nullptr;
-  size_t gram_n = 0;
-  double* partials = nullptr;   // per-workgroup loss terms + the tail of the two-stage sum
-  double* scalars = nullptr;    // [0] loss rows, [1] sumsq, [2], [3] sums of the bias sweeps
-  double* rinit = nullptr;      // 256 x 128 partials + the k1 entries of rhs_init
-  double* m2 = nullptr;
-  size_t m2_n = 0;
-  double* longs = nullptr;      // the long rows' partial sums and vectors (f64_long_scratch_doubles)
-  size_t longs_n = 0;
-  double* repack = nullptr;     // explicit feedback with biases, conjugate gradient: X', Y', shifted ratings
-  size_t repack_n = 0;
+  GrowBufBase* all = nullptr;
+  GrowBuf<double> gram{all};
+  GrowBuf<double> partials{all};   // per-workgroup loss terms + the tail of the two-stage sum
+  GrowBuf<double> scalars{all};    // [0] loss rows, [1] sumsq, [2], [3] sums of the bias sweeps
+  GrowBuf<double> rinit{all};      // 256 x 128 partials + the k1 entries of rhs_init
+  GrowBuf<double> m2{all};
+  GrowBuf<double> longs{all};      // the long rows' partial sums and vectors (f64_long_scratch_doubles)
+  GrowBuf<double> repack{all};     // explicit feedback with biases, conjugate gradient: X', Y', shifted ratings
   int device = -1;
-  void release() {
-    for (double** q : {&gram, &partials, &scalars, &rinit, &m2, &longs, &repack})
-      if (*q) { (void)hipFree(*q); *q = nullptr; }
-    gram_n = m2_n = longs_n = repack_n = 0;
-  }
-  int ensure_repack(size_t n) {
-    if (n > repack_n) {
-      if (repack) (void)hipFree(repack);
-      repack = nullptr; repack_n = 0;
-      HIP_TRY(hipMalloc(&repack, n * sizeof(double)));
-      repack_n = n;
-    }
-    return RSPARSE_HIP_OK;
-  }
-  int ensure_longs(size_t n) {
-    if (n > longs_n) {
-      if (longs) (void)hipFree(longs);
-      longs = nullptr; longs_n = 0;
-      HIP_TRY(hipMalloc(&longs, n * sizeof(double)));
-      longs_n = n;
-    }
-    return RSPARSE_HIP_OK;
-  }
   int ensure() {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (dev != device) {
-      release();
+      GrowBufBase::release_all(all);
       device = dev;
     }
-    if (!partials) HIP_TRY(hipMalloc(&partials, ((size_t)std::max(kF64MaxGrid, 1024) + kSumStageBlocks + 16) * sizeof(double)));
+    HIP_TRY(partials.ensure((size_t)std::max(kF64MaxGrid, 1024) + kSumStageBlocks + 16));
     if (!scalars) {
-      HIP_TRY(hipMalloc(&scalars, 16 * sizeof(double)));
+      HIP_TRY(scalars.ensure(16));
       HIP_TRY(hipMemset(scalars, 0, 16 * sizeof(double)));
     }
-    if (!rinit) HIP_TRY(hipMalloc(&rinit, kRhsInitDoubles * sizeof(double)));
-    return RSPARSE_HIP_OK;
-  }
-  int ensure_gram(size_t n) {
-    if (n > gram_n) {
-      if (gram) (void)hipFree(gram);
-      gram = nullptr; gram_n = 0;
-      HIP_TRY(hipMalloc(&gram, n * sizeof(double)));
-      gram_n = n;
-    }
-    return RSPARSE_HIP_OK;
-  }
-  int ensure_m2(size_t n) {
-    if (n > m2_n) {
-      if (m2) (void)hipFree(m2);
-      m2 = nullptr; m2_n = 0;
-      HIP_TRY(hipMalloc(&m2, n * sizeof(double)));
-      m2_n = n;
-    }
+    HIP_TRY(rinit.ensure(kRhsInitDoubles));
     return RSPARSE_HIP_OK;
   }
 } g_w64;
-
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-  template <class T> T* as() { return static_cast<T*>(p); }
-};
 
 // One half-iteration in double.  d_base_in / d_base_out: global_bias_base of the no-bias global-bias variant (`rank`
 // doubles; in = use it instead of recomputing -global_bias * rowSums(X), out = receives what was used), both nullable.
@@ -214,14 +163,14 @@ int f64_half_iteration(const rsparse_hip_csc_f64* conf, bool implicit, const dou
   a.fail_counter = fails;
   a.m2_scratch = nullptr;
   if (f64_needs_m2_scratch(a.k1, a.solver)) {
-    if ((rc = g_w64.ensure_m2((size_t)grid * f64_m2_doubles_per_wg(a.k1)))) return rc;
+    HIP_TRY(g_w64.m2.ensure((size_t)grid * f64_m2_doubles_per_wg(a.k1)));
     a.m2_scratch = g_w64.m2;
   }
   a.long_min = 0x7fffffff; a.chunk_len = 0; a.n_long = a.n_chunks = 0;
   a.long_rows = a.long_chunk0 = a.chunk_long = a.chunk_off = nullptr;
   a.long_scratch = nullptr;
   if (conf->n_long > 0 && solver == RSPARSE_SOLVER_CONJUGATE_GRADIENT) {   // (only the wave-per-row path looks at these)
-    if ((rc = g_w64.ensure_longs(f64_long_scratch_doubles(rank, conf->n_long, conf->n_chunks)))) return rc;
+    HIP_TRY(g_w64.longs.ensure(f64_long_scratch_doubles(rank, conf->n_long, conf->n_chunks)));
     a.long_min = conf->long_min; a.chunk_len = conf->chunk_len; a.n_long = conf->n_long; a.n_chunks = conf->n_chunks;
     a.long_rows = conf->long_table;
     a.long_chunk0 = a.long_rows + conf->n_long;
@@ -236,7 +185,7 @@ int f64_half_iteration(const rsparse_hip_csc_f64* conf, bool implicit, const dou
   if (repack) {
     const int k1 = a.k1;
     const size_t nx = (size_t)conf->n_rows * k1, ny = (size_t)conf->n_cols * k1, nv = (size_t)conf->nnz;
-    if ((rc = g_w64.ensure_repack(nx + ny + nv + 16))) return rc;
+    HIP_TRY(g_w64.repack.ensure(nx + ny + nv + 16));
     double* Xp = g_w64.repack;
     double* Yp = Xp + nx;
     double* Vp = Yp + ny;
@@ -426,7 +375,7 @@ int rsparse_hip_gramian_f64_device(const double* d_X, int rank, int64_t n, doubl
   if (rank > RSPARSE_HIP_MAX_RANK_F64) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 128 is not on the fp64 device path");
   int rc = g_w64.ensure();
   if (rc) return rc;
-  if ((rc = g_w64.ensure_gram(f64_gramian_scratch_doubles(rank)))) return rc;
+  HIP_TRY(g_w64.gram.ensure(f64_gramian_scratch_doubles(rank)));
   const double ridge = (double)(float)lambda;   // float::fl(diag(lambda)): rounded to fp32 in the double build too, R/model_WRMF.R:476
   hipError_t e = launch_f64_gramian(d_X, rank, n, ridge, d_XtX_out, d_sumsq_out, g_w64.gram, (hipStream_t)stream);
   if (e != hipSuccess) return capi_hip_fail(e, "launch_f64_gramian");

@@ -5,7 +5,25 @@
 #include <cstdint>
 #include <string>
 
+#include "wrmf_schedule.h"
+
 namespace rsparse_hip {
+
+// One list set of the normal-equation launch (wrmf_ne.hip), on the device: the rows of a prefix of the order dealt to `wg`
+// workgroups, longest processing time first -- workgroup b owns rows[ptr[b], ptr[b + 1]); an entry >= 0 is a row, -(s + 1)
+// segment s of the rows that are split across workgroups (planned by wrmf_schedule.cpp: NeCut / NeDeal).  A view: the
+// arrays belong to the handle (rsparse_hip_csc::owned), and list sets of one handle may share them.
+struct NeListSet {
+  const int32_t* rows = nullptr;
+  const int32_t* ptr = nullptr;
+  int wg = 0;
+  int entries = 0;                       // list entries = rows that are not split + segments
+  const int32_t* segs = nullptr;         // [nseg][6]: segments of the rows split across workgroups
+  int nseg = 0;
+  const int32_t* split_rows = nullptr;   // lists of the COLLECT launch (one workgroup per split row): -(index of its first segment + 1)
+  const int32_t* split_ptr = nullptr;    // 0, 1, 2, ...
+  int nsplit = 0;
+};
 
 // Device-resident CSC + launch schedule.
 struct DevCSC {
@@ -15,55 +33,33 @@ struct DevCSC {
   const int32_t* col_ptrs = nullptr;
   const int32_t* row_idx = nullptr;
   const float* vals = nullptr;
-  // rows with more than `short_max` non-zeros, longest first: solved one workgroup per row
-  int32_t* long_rows = nullptr;
+  // rows with more than `short_max` non-zeros, longest first (solved one workgroup per row): the first n_long entries of q_order
   int n_long = 0;
   int short_max = 0;  // tile capacity T the schedule was built for
   int max_len = 0;
   // quad-layout CG schedule: every row, longest first; bucket b occupies order[q_off[b], q_off[b+1])
   // (bucket table: wrmf_cgq.hip kBuckets)
-  int32_t* q_order = nullptr;
+  const int32_t* q_order = nullptr;
   int q_off[7] = {0, 0, 0, 0, 0, 0, 0};
   int q_cfg = 0;
   int q_pair_first = 0;   // position in q_order of the first row with at most 16 non-zeros (wrmf_cgp.hip: two rows per wave)
   int q_team4_first = 0;  // ... of the first row with at most kTeam4Max non-zeros (bucket 1's 4-wave launch at rank 97..128)
   int64_t q_nnz[6] = {0, 0, 0, 0, 0, 0};
-  int64_t* q_stream_off = nullptr;  // prefix sums of the streamed bucket's row lengths (device)
-  // normal-equation kernel (wrmf_ne.hip): the long rows (bucket 0) dealt to q_ne_wg workgroups, longest processing
-  // time first; workgroup b owns q_ne_rows[q_ne_ptr[b], q_ne_ptr[b+1])
+  const int64_t* q_stream_off = nullptr;  // prefix sums of the streamed bucket's row lengths (device)
   int q_n_chol_long = 0;   // rows of more than kCholLongLen non-zeros (a prefix of q_order)
   int q_gt32 = 0;                   // rows of more than 32 non-zeros
   int q_gt48 = 0;                   // ... of more than 48
   int q_lr_first = 0, q_n_lr = 0;   // rows of 1..kCholLrMax non-zeros: q_order[q_lr_first, q_lr_first + q_n_lr)
-  int32_t* q_ne_rows = nullptr;
-  int32_t* q_ne_ptr = nullptr;
-  int q_ne_wg = 0;
-  int32_t* q_ne1_rows = nullptr;   // the same rows dealt to one list per workgroup slot (kernels resident once per CU)
-  int32_t* q_ne1_ptr = nullptr;
-  int q_ne1_wg = 0;
-  int32_t* q_ne_segs = nullptr;   // [q_ne_nseg][6]: segments of the rows split across workgroups (wrmf_capi.cpp)
-  int q_ne_nseg = 0;
-  int q_ne_entries = 0;           // list entries = rows that are not split + segments
-  int32_t* q_ne_split_rows = nullptr;   // lists of the COLLECT launch (one workgroup per split row)
-  int32_t* q_ne_split_ptr = nullptr;
-  int q_ne_nsplit = 0;
+  // normal-equation kernel (wrmf_ne.hip): the long rows (bucket 0) as many lists (two workgroups per CU pick them up) ...
+  NeListSet q_ne;
+  // ... and the same rows and segments dealt to one list per workgroup slot (kernels resident once per CU)
+  NeListSet q_ne1;
   // the same lists for the rows beyond kCgMfMax non-zeros (a shorter prefix of q_order): the normal-equation launch beside
-  // wrmf_cg_mf.hip, and solver == CHOLESKY's when wrmf_chol_mf.hip does not run; they alias the lists above when the two
-  // prefixes coincide
+  // wrmf_cg_mf.hip, and solver == CHOLESKY's when wrmf_chol_mf.hip does not run; = q_ne when the two prefixes coincide
   int q_n_nec = 0;      // rows of more than kCgMfMax non-zeros (a prefix of q_order)
-  bool q_nec_own = false;
-  int32_t* q_nec_rows = nullptr;
-  int32_t* q_nec_ptr = nullptr;
-  int q_nec_wg = 0;
-  int32_t* q_nec_segs = nullptr;
-  int q_nec_nseg = 0;
-  int q_nec_entries = 0;
-  int32_t* q_nec_split_rows = nullptr;
-  int32_t* q_nec_split_ptr = nullptr;
-  int q_nec_nsplit = 0;
+  NeListSet q_nec;
   int64_t nnz_long = 0;
   int n_empty = 0;
-  bool owns_matrix = false;
   // rsparse_hip_csc_freeze_values: the caller promises that the values do not change while the flag is set; the statistics of
   // the values that the fp16 kernels scale their operands by (max c, "some c < 1": launch_ne_stats) are then scanned once per
   // handle instead of once per half-iteration.  vstats: 2 words on the device, valid once vstats_valid
@@ -151,13 +147,7 @@ struct QSchedule {
   int team4_first;  // see DevCSC::q_team4_first; = off[2] when bucket 1 runs on the 8-wave kernel alone (global bias)
   bool pair_wide;   // the last bucket's rows of 17..32 non-zeros two per wave as well (cgp_wide_supported), else one per wave
   int cfg;  // geometry the schedule was built for (see wrmf_cgq.hip kBuckets)
-  const int32_t* ne_rows;  // see DevCSC::q_ne_*
-  const int32_t* ne_ptr;
-  int ne_wg;
-  int ne_entries;                 // list entries = rows that are not split + segments
-  const int32_t* ne_split_rows;   // per split row: -(index of its first segment + 1); ne_split_ptr = 0, 1, 2, ...
-  const int32_t* ne_split_ptr;
-  int ne_nsplit;
+  NeListSet ne;   // the list set of this call's normal-equation launch (one of DevCSC::q_ne / q_ne1 / q_nec)
   const int32_t* mf_rows = nullptr;   // wrmf_cg_mf.hip's rows of the first bucket (the normal-equation lists above then hold the giant rows only)
   int mf_n = 0;
 };
@@ -169,8 +159,7 @@ int cgq_bucket_capq(int cfg, int b);
 int cgq_bucket_waves(int cfg, int b);  // waves per workgroup of bucket b's kernel
 int cgq_bucket_stream(int cfg, int b);
 int cgq_bucket_grid(int n_rows, int bucket, int cfg);
-// bucket 1 at rank 97..128: the rows of up to kTeam4Max non-zeros on 4-wave teams of 20 quads per wave (wrmf_cgq.hip)
-constexpr int kTeam4Max = 320;
+// bucket 1 at rank 97..128: the rows of up to kTeam4Max (wrmf_schedule.h) non-zeros on 4-wave teams of 20 quads per wave (wrmf_cgq.hip)
 int cgq_team4_grid(int n_rows);
 int cgq_bucket_of(int len, int cfg);
 size_t cgq_loss_slots(const QSchedule& q, int k, bool implicit);
@@ -184,8 +173,7 @@ hipError_t launch_als_cgp(const AlsArgs& a, const int32_t* rows, int n_rows, boo
 // long rows (bucket 0) by one-pass normal equations on the matrix cores (wrmf_ne.hip) instead of the streamed CG kernel
 bool ne_supported(int k);
 constexpr int kNeMinLen = 512;       // its rows: more non-zeros than the largest resident bucket of wrmf_cgq.hip holds
-constexpr int kNeMaxSeg = 16;        // segments per split row
-constexpr int kNeMaxSegTotal = 1024;   // ... per list set (186 MB of partial accumulators at most)
+// (kNeMaxSeg segments per split row, kNeMaxSegTotal per list set -- 186 MB of partial accumulators at most: wrmf_schedule.h)
 constexpr int kNeSegFloats = 4 * (11 * 16 * 64 + 128 + 2);   // per segment: 4 waves x (<= 11 accumulator tiles + b + sum c)
 // absmax_hint (nullable, device float): max |X| supplied by the caller -- X is then not scanned
 // cached_vstats (nullable, 2 device words = stats[1..2] of an earlier scan of the same values): the values are not read;
@@ -193,7 +181,6 @@ constexpr int kNeSegFloats = 4 * (11 * 16 * 64 + 128 + 2);   // per segment: 4 w
 hipError_t launch_ne_stats(const float* X, int64_t nx, const float* vals, int64_t nnz, unsigned* stats, hipStream_t s,
                            const float* absmax_hint = nullptr, const unsigned* cached_vstats = nullptr,
                            unsigned* save_vstats = nullptr);
-struct QSchedule;
 hipError_t launch_als_ne(const AlsArgs& a, const QSchedule& q, bool implicit, double* row_loss, hipStream_t s,
                          hipEvent_t* ev_slot = nullptr);
 // global bias + conjugate gradient: out[r][:] = base - gbias * sum_j (c_j - 1) x_j for the n rows `rows` (one workgroup
@@ -202,8 +189,7 @@ hipError_t launch_gb_row_terms(const AlsArgs& a, const int32_t* rows, int n, flo
 // ev (optional): 7 events, ev[b] before bucket b's kernel, ev[6] after the last one
 hipError_t launch_als_cgq(const AlsArgs& a, const QSchedule& q, bool implicit, hipStream_t s, hipEvent_t* ev = nullptr);
 
-// tile capacity (non-zeros per wave tile) the CG kernels are instantiated for
-constexpr int kTileNnz = 32;
+// (kTileNnz, the tile capacity the CG kernels are instantiated for: wrmf_schedule.h)
 constexpr int kWavesPerWG = 4;
 constexpr int kRowsPerWGShort = 64;  // rows handed to one short-row workgroup
 constexpr int kRowsPerWGLong = 8;    // rows handed to one long-row workgroup
@@ -219,11 +205,9 @@ size_t chol_loss_slots(int n_cols);
 hipError_t launch_als_cg(const AlsArgs& a, bool implicit, hipStream_t s, hipEvent_t* ev = nullptr);
 // register-blocked Cholesky (wrmf_chol.hip); rows beyond kCholLongLen non-zeros go to a second launch that sums the
 // rank-one updates in two levels (see there); its workgroups' loss slots follow the main launch's
-constexpr int kCholLongLen = 4096;
 constexpr int kCholLongGrid = 512;
 // rows of 1..kCholLrMax non-zeros, implicit feedback, rank 98..128: the low-rank form of the exact solve (wrmf_chol_lr.hip)
-constexpr int kCholLrMax = 64;
-constexpr int kCholLrGrid = 65536;   // (many more than workgroup slots: the hardware deals them as slots free up, see build_ne_lists)
+constexpr int kCholLrGrid = 65536;   // (many more than workgroup slots: the hardware deals them as slots free up, see ne_deal, wrmf_schedule.cpp)
 size_t chol2_loss_slots(int n_cols);
 bool chol_lr_supported(const AlsArgs& a, bool implicit);
 bool chol_lrx_supported(const AlsArgs& a, bool implicit);
@@ -248,7 +232,6 @@ hipError_t launch_als_chol_mf(const AlsArgs& a, bool implicit, const int32_t* ro
 // rank 128, implicit feedback, conjugate gradient (round 6, wrmf_cg_mf.hip): the rows of kNeMinLen + 1 .. kCgMfMax non-zeros as one
 // wave per row -- both normal-equation matrices in the accumulator registers, CG from the tiles.  The rows beyond kCgMfMax stay
 // on wrmf_ne.hip (it splits them across workgroups).  Needs a.ne_stats.  Loss partials [loss_slot0, + cg_mf_loss_slots(n_rows))
-constexpr int kCgMfMax = 16384;
 constexpr int kCgMfGrid = 256 * 16;   // workgroups of four waves (a row each at a time), grid-stride over the rows (longest first)
 bool cg_mf_supported(int k, bool implicit);
 int cg_mf_grid(int n_rows);
@@ -402,6 +385,44 @@ int* capi_fail_counters();
 // RAII for the stateless entry points: takes the failure counts an earlier device-resident call left on the device when the
 // stateless call starts (they are not its own) and hands them back to the next reader when it ends
 void capi_fail_carry_add(int64_t unresolved, int64_t fallback);
+// Grow-only device scratch of the two workspaces.  Every buffer is a member constructed on its workspace's chain, so that
+// the workspace's release (a device change) reaches each of them without naming it.
+struct GrowBufBase {
+  void* p = nullptr;
+  size_t cap = 0;   // elements
+  GrowBufBase* const next;
+  explicit GrowBufBase(GrowBufBase*& chain) : next(chain) { chain = this; }
+  GrowBufBase(const GrowBufBase&) = delete;
+  GrowBufBase& operator=(const GrowBufBase&) = delete;
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  static void release_all(GrowBufBase* chain) {
+    for (; chain; chain = chain->next) chain->release();
+  }
+};
+template <class T>
+struct GrowBuf : GrowBufBase {
+  using GrowBufBase::GrowBufBase;
+  // at least n elements; growing frees first, with plain hipFree: it waits for work still using the old buffer
+  hipError_t ensure(size_t n) {
+    if (n <= cap) return hipSuccess;
+    release();
+    hipError_t e = hipMalloc(&p, n * sizeof(T));
+    if (e == hipSuccess) cap = n;
+    return e;
+  }
+  operator T*() const { return static_cast<T*>(p); }
+};
+struct DevBuf {  // RAII for the stateless entry points
+  void* p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+  template <class T> T* as() { return static_cast<T*>(p); }
+};
+
 struct StaleFailures {
   int64_t unresolved = 0, fallback = 0;
   StaleFailures();

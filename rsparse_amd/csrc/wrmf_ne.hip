@@ -1389,7 +1389,7 @@ hipError_t launch_gb_row_terms(const AlsArgs& a, const int32_t* rows, int n, flo
 
 bool ne_supported(int k) { return k > 32 && k <= 128 && k % 4 == 0; }
 
-// wg_rows / wg_ptr: per-workgroup row lists (host-balanced, wrmf_capi.cpp build_ne_lists); row_loss: one double per
+// wg_rows / wg_ptr: per-workgroup row lists (host-balanced, wrmf_schedule.cpp ne_deal); row_loss: one double per
 // entry of wg_rows
 __global__ void ne_stats_words_kernel(unsigned* __restrict__ dst, const unsigned* __restrict__ src) {
   if (threadIdx.x < 2) dst[threadIdx.x] = src[threadIdx.x];
@@ -1434,23 +1434,23 @@ hipError_t launch_ne_mode(const AlsArgs& a, const int32_t* wg_rows, const int32_
   return hipErrorInvalidValue;
 }
 
-// The long rows of one half-iteration: the streaming launch over the per-workgroup lists (q.ne_rows / ne_ptr; an entry is
+// The long rows of one half-iteration: the streaming launch over the per-workgroup lists (q.ne.rows / ptr; an entry is
 // a row or a segment of a split row), then, if rows were split, the COLLECT launch (one workgroup per split row).
 // row_loss: one double per list entry, then one per split row.
 hipError_t launch_als_ne(const AlsArgs& a, const QSchedule& q, bool implicit, double* row_loss, hipStream_t s,
                          hipEvent_t* ev_slot) {
-  if (q.ne_wg <= 0) return hipSuccess;
+  if (q.ne.wg <= 0) return hipSuccess;
   // a.ne_chol (solver == CHOLESKY): the instantiations whose per-row solve is the blocked LDL^T instead of CG -- separate
   // kernels, so neither solve costs the other's streaming loops a register
   const bool gb = !a.ne_chol && implicit && a.gbias != 0.f;   // conjugate gradient with a global bias
   if (gb && !(a.ne_r0 && a.ne_r0_slot)) return hipErrorInvalidValue;
-  hipError_t err = a.ne_chol ? launch_ne_mode<false, true>(a, q.ne_rows, q.ne_ptr, q.ne_wg, implicit, row_loss, s, ev_slot)
-                   : gb      ? launch_ne_mode<false, false, true>(a, q.ne_rows, q.ne_ptr, q.ne_wg, implicit, row_loss, s, ev_slot)
-                             : launch_ne_mode<false, false>(a, q.ne_rows, q.ne_ptr, q.ne_wg, implicit, row_loss, s, ev_slot);
-  if (err != hipSuccess || q.ne_nsplit <= 0) return err;
-  return a.ne_chol ? launch_ne_mode<true, true>(a, q.ne_split_rows, q.ne_split_ptr, q.ne_nsplit, implicit, row_loss + q.ne_entries, s)
-         : gb      ? launch_ne_mode<true, false, true>(a, q.ne_split_rows, q.ne_split_ptr, q.ne_nsplit, implicit, row_loss + q.ne_entries, s)
-                   : launch_ne_mode<true, false>(a, q.ne_split_rows, q.ne_split_ptr, q.ne_nsplit, implicit, row_loss + q.ne_entries, s);
+  hipError_t err = a.ne_chol ? launch_ne_mode<false, true>(a, q.ne.rows, q.ne.ptr, q.ne.wg, implicit, row_loss, s, ev_slot)
+                   : gb      ? launch_ne_mode<false, false, true>(a, q.ne.rows, q.ne.ptr, q.ne.wg, implicit, row_loss, s, ev_slot)
+                             : launch_ne_mode<false, false>(a, q.ne.rows, q.ne.ptr, q.ne.wg, implicit, row_loss, s, ev_slot);
+  if (err != hipSuccess || q.ne.nsplit <= 0) return err;
+  return a.ne_chol ? launch_ne_mode<true, true>(a, q.ne.split_rows, q.ne.split_ptr, q.ne.nsplit, implicit, row_loss + q.ne.entries, s)
+         : gb      ? launch_ne_mode<true, false, true>(a, q.ne.split_rows, q.ne.split_ptr, q.ne.nsplit, implicit, row_loss + q.ne.entries, s)
+                   : launch_ne_mode<true, false>(a, q.ne.split_rows, q.ne.split_ptr, q.ne.nsplit, implicit, row_loss + q.ne.entries, s);
 }
 
 }  // namespace rsparse_hip
