@@ -49,7 +49,6 @@ constexpr int MF_A0 = 0;
 namespace rsparse_hip {
 namespace {
 
-constexpr float kCgTolMf = 1e-10f;   // CG_TOL, inst/include/wrmf.hpp:22
 // Measured and not kept, first version (two REGISTER buffers, asm loads, one `s_waitcnt vmcnt(0)` per step: 17.3 ms per launch):
 //  - the previous step's matrix instructions in five groups of eight BETWEEN the pieces of this step's vector work, their operands
 //    waiting in LDS: 19.8 ms (profiles/r06/r6o_*) -- the staging writes, 60 operand reads per step and the lost scheduling freedom
@@ -72,8 +71,8 @@ __device__ __forceinline__ void cgm_operands_hi(const float (&x)[16], f16x8& h0,
     hh0[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(v0, f16x2));
     hh1[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(v1, f16x2));
   }
-  h0 = mf_pack(hh0[0], hh0[1], hh0[2], hh0[3]);
-  h1 = mf_pack(hh1[0], hh1[1], hh1[2], hh1[3]);
+  h0 = pack_f16x8(hh0[0], hh0[1], hh0[2], hh0[3]);
+  h1 = pack_f16x8(hh1[0], hh1[1], hh1[2], hh1[3]);
 }
 
 // A step's fp16 operands by 32-coordinate block: M1's two terms and M2's one
@@ -134,7 +133,7 @@ __device__ __forceinline__ void cgm_matvec(RD&& rd, GV&& gtile, WV& sw, const in
   }
   wave_sync();
   float dsum[4] = {0.f, 0.f, 0.f, 0.f};
-  mf_sfor<4>([&](auto kt) {
+  static_for<4>([&](auto kt) {
     constexpr int K = decltype(kt)::value;
     float pc[16];
 #pragma unroll
@@ -145,12 +144,12 @@ __device__ __forceinline__ void cgm_matvec(RD&& rd, GV&& gtile, WV& sw, const in
     float ts[16];   // transposed partials of block column K: sum over the tiles (I, K), I > K, of tile[v] * p[32 I + n]
 #pragma unroll
     for (int v = 0; v < 16; v++) ts[v] = 0.f;
-    mf_sfor<4 - K>([&](auto st) {
+    static_for<4 - K>([&](auto st) {
       constexpr int I = K + decltype(st)::value;
       constexpr int T = mf_tid(I, K);
       float g[16];
       gtile(std::integral_constant<int, T>{}, g);
-      mf_sfor<16>([&](auto vt) {
+      static_for<16>([&](auto vt) {
         constexpr int v = decltype(vt)::value;
         const float av = rd(std::integral_constant<int, T>{}, std::integral_constant<int, v>{}) + g[v];
         dsum[I] = fmaf(av, pc[v], dsum[I]);
@@ -219,12 +218,12 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
   __syncthreads();
 
   auto uni = [](const float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); };
-  const int ex = rfl(mf_scale_exp(fmaxf(__uint_as_float(a.ne_stats[0]), 1e-30f)));
+  const int ex = rfl(fp16_scale_exp(fmaxf(__uint_as_float(a.ne_stats[0]), 1e-30f)));
   const float wmax = uni(fmaxf(__uint_as_float(a.ne_stats[1]) - 1.f, 1.f));
   const int ewb = rfl((int)((__float_as_uint(wmax) >> 23) & 0xffu));
-  const float sx = uni(mf_pow2(ex)), sw_ = uni(mf_pow2(min(253, max(1, 253 - ewb))));   // sw_ = 2^(126 - ewb) <= 1 / wmax
-  const float un1 = uni(mf_pow2(254 - ex));                                              // 1 / sx
-  const float unw = uni(mf_pow2(254 - min(253, max(1, 253 - ewb))));                     // 1 / sw_
+  const float sx = uni(pow2(ex)), sw_ = uni(pow2(min(253, max(1, 253 - ewb))));   // sw_ = 2^(126 - ewb) <= 1 / wmax
+  const float un1 = uni(pow2(254 - ex));                                              // 1 / sx
+  const float unw = uni(pow2(254 - min(253, max(1, 253 - ewb))));                     // 1 / sw_
   const int n_waves = 4 * gridDim.x;
 
   for (int it = 4 * blockIdx.x + wv; it < n_rows; it += n_waves) {
@@ -237,7 +236,7 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
     sw.x0[ln] = yrow[ln];
     sw.x0[64 + ln] = yrow[64 + ln];
     MF_DRAIN();
-    mf_sfor<256>([&](auto rt) { mf_wr<decltype(rt)::value>(0.f); });
+    static_for<256>([&](auto rt) { mf_wr<decltype(rt)::value>(0.f); });
     f32x16 hi[4];
 #pragma unroll
     for (int t = 0; t < 4; t++)
@@ -332,9 +331,9 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
         // 2^e' (c - 1) 2^e x.
         f16x8 ah[4], al[4], mh[4], bh[4], bl[4];
         auto m2_products = [&]() __attribute__((always_inline)) {   // (first: their operand dies before M1's are built)
-          mf_sfor<4>([&](auto kt) {
+          static_for<4>([&](auto kt) {
             constexpr int K = decltype(kt)::value;
-            mf_sfor<4 - K>([&](auto st2) {
+            static_for<4 - K>([&](auto st2) {
               constexpr int I = K + decltype(st2)::value;
               constexpr int T = mf_tid(I, K);
               if constexpr (T < 6) mf_mma16<10 + T>(mh[K], mh[I]);
@@ -371,11 +370,11 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
         __builtin_amdgcn_sched_barrier(0);
         mf_operands(xs1, ah[2], al[2], ah[3], al[3]);
         __builtin_amdgcn_sched_barrier(0);
-        mf_sfor<3>([&](auto pt) {
+        static_for<3>([&](auto pt) {
           constexpr int pr = decltype(pt)::value;
-          mf_sfor<4>([&](auto kt) {
+          static_for<4>([&](auto kt) {
             constexpr int K = decltype(kt)::value;
-            mf_sfor<4 - K>([&](auto st2) {
+            static_for<4 - K>([&](auto st2) {
               constexpr int I = K + decltype(st2)::value;
               if constexpr (SYM) mf_mma16<mf_tid(I, K)>(pr == 2 ? al[K] : ah[K], pr == 1 ? al[I] : ah[I]);
               else mf_mma16<mf_tid(I, K)>(pr == 2 ? al[K] : ah[K], pr == 1 ? bl[I] : bh[I]);
@@ -392,7 +391,7 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
       // M1's) come from LDS in that order too, prepared once per chunk of 64: no v_readlane.
       CgmOps OA, OB;   // ping-pong: even steps read OA (their predecessor's operands) and build OB, odd steps the other way round
       if constexpr (SYM) {
-        const f16x8 z = mf_pack(0u, 0u, 0u, 0u);
+        const f16x8 z = pack_f16x8(0u, 0u, 0u, 0u);
 #pragma unroll
         for (int t = 0; t < 4; t++) { OA.ah[t] = z; OA.al[t] = z; OA.mh[t] = z; }   // (step 0 has no predecessor: its 40 instructions add zero)
       }
@@ -445,7 +444,7 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
         va[0] = va0;
         vb[0] = vb0;
         unsigned hm[4][4], hh[4][4], ll[4][4];   // [block][pair]
-        mf_sfor<4>([&](auto qt) {
+        static_for<4>([&](auto qt) {
           constexpr int q = decltype(qt)::value;
           if constexpr (q < 3) {
             va[(q + 1) & 1] = *reinterpret_cast<const float4*>(rs + (2 * q + 2) * 256);
@@ -456,7 +455,7 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
           const float c0 = wc[q & 1].x, c1 = wc[q & 1].y, g0 = wg[q & 1].x, g1 = wg[q & 1].y;
           const float4 xa = va[q & 1], xb = vb[q & 1];
           const float a0s[4] = {xa.x, xa.y, xa.z, xa.w}, a1s[4] = {xb.x, xb.y, xb.z, xb.w};
-          mf_sfor<4>([&](auto It) {
+          static_for<4>([&](auto It) {
             constexpr int I = decltype(It)::value, u = 4 * q + I, m0 = (5 * u) / 2, m1 = (5 * (u + 1)) / 2;
             const float a0 = a0s[I], a1 = a1s[I];
             ua[I] = fmaf(c1, a1, fmaf(c0, a0, ua[I]));
@@ -489,9 +488,9 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
         });
 #pragma unroll
         for (int I = 0; I < 4; I++) {
-          N.mh[I] = mf_pack(hm[I][0], hm[I][1], hm[I][2], hm[I][3]);
-          N.ah[I] = mf_pack(hh[I][0], hh[I][1], hh[I][2], hh[I][3]);
-          N.al[I] = mf_pack(ll[I][0], ll[I][1], ll[I][2], ll[I][3]);
+          N.mh[I] = pack_f16x8(hm[I][0], hm[I][1], hm[I][2], hm[I][3]);
+          N.ah[I] = pack_f16x8(hh[I][0], hh[I][1], hh[I][2], hh[I][3]);
+          N.al[I] = pack_f16x8(ll[I][0], ll[I][1], ll[I][2], ll[I][3]);
         }
       };
       // prologue: chunks 0 and 1 of the indices, then steps 0 and 1
@@ -506,7 +505,7 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
       int slot = 0;   // = st % 3
       for (int c = 0; 4 * c < nsteps; c++) {
         bool done = false;
-        mf_sfor<4>([&](auto jt) {
+        static_for<4>([&](auto jt) {
           constexpr int j = decltype(jt)::value;
           const int st = 4 * c + j;
           if (done || st >= nsteps) { done = true; return; }   // wave-uniform
@@ -560,8 +559,8 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
         if (done) break;
       }
       if constexpr (SYM) {   // the last step's matrix instructions; the right-hand side: the halves' partials added
-        if (nsteps & 1) mf_sfor<40>([&](auto it) { mm(it, OB); });   // (wave-uniform: which set the last step built)
-        else mf_sfor<40>([&](auto it) { mm(it, OA); });
+        if (nsteps & 1) static_for<40>([&](auto it) { mm(it, OB); });   // (wave-uniform: which set the last step built)
+        else static_for<40>([&](auto it) { mm(it, OA); });
 #pragma unroll
         for (int I = 0; I < 4; I++) {
           const unsigned du = __float_as_uint(ua[I]);
@@ -577,11 +576,11 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
     const int n = ln & 31, hf = ln >> 5;
     const float un_m1 = (un1 * un1) * (SYM ? unw : unw), un_m2 = un1 * un1;
     MF_DRAIN();
-    mf_sfor<160>([&](auto rt) {
+    static_for<160>([&](auto rt) {
       constexpr int R = decltype(rt)::value;
       mf_wr<R>(mf_rd<R>() * un_m1);
     });
-    mf_sfor<96>([&](auto rt) {
+    static_for<96>([&](auto rt) {
       constexpr int R = 160 + decltype(rt)::value;
       mf_wr<R>(mf_rd<R>() * un_m2);
     });
@@ -632,7 +631,7 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
 #pragma unroll
       for (int I = 0; I < 4; I++) { x[I] = fmaf(alpha, p[I], x[I]); r[I] = fmaf(-alpha, ap[I], r[I]); }
       const double rsnew = (double)cgm_dot(r, r, hf);
-      if (rsnew < (double)kCgTolMf) break;
+      if (rsnew < (double)kCgTol) break;
       const float beta = (float)(rsnew / rsold);
 #pragma unroll
       for (int I = 0; I < 4; I++) p[I] = fmaf(p[I], beta, r[I]);
@@ -661,7 +660,7 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
       }
       wave_sync();
       float part = 0.f;
-      mf_sfor<4>([&](auto kt) {
+      static_for<4>([&](auto kt) {
         constexpr int K = decltype(kt)::value;
         float pc[16];
 #pragma unroll
@@ -669,11 +668,11 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
           const float4 t = *reinterpret_cast<const float4*>(&sw.vec[32 * K + 8 * q + 4 * hf]);
           pc[4 * q] = t.x; pc[4 * q + 1] = t.y; pc[4 * q + 2] = t.z; pc[4 * q + 3] = t.w;
         }
-        mf_sfor<4 - K>([&](auto st) {
+        static_for<4 - K>([&](auto st) {
           constexpr int I = K + decltype(st)::value;
           constexpr int T = mf_tid(I, K);
           float d = 0.f;
-          mf_sfor<16>([&](auto vt) {
+          static_for<16>([&](auto vt) {
             constexpr int v = decltype(vt)::value;
             d = fmaf(rd_m1(std::integral_constant<int, T>{}, vt) + rd_m2(std::integral_constant<int, T>{}, vt), pc[v], d);
           });

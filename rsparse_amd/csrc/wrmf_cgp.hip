@@ -30,46 +30,7 @@ namespace {
 
 using namespace dev;
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-constexpr float kCgTolP = 1e-10f;  // CG_TOL, inst/include/wrmf.hpp:22
 constexpr int kPairMaxSweeps = 4;
-
-__device__ __forceinline__ float p_row16_sum(float v) {
-  v += dpp<0xB1>(v);
-  v += dpp<0x4E>(v);
-  v += dpp<0x141>(v);
-  v += dpp<0x140>(v);
-  return v;
-}
-__device__ __forceinline__ float p_row16_max(float v) {
-  v = fmaxf(v, dpp<0xB1>(v));
-  v = fmaxf(v, dpp<0x4E>(v));
-  v = fmaxf(v, dpp<0x141>(v));
-  v = fmaxf(v, dpp<0x140>(v));
-  return v;
-}
-// sum over the two groups of a half-wave (lanes l and l ^ 16), result in both, bitwise identical
-__device__ __forceinline__ float p_pair_sum(float v) {
-  const unsigned u = __float_as_uint(v);
-  const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ int p_scale_exp(float vmax) {
-  const int eb = (int)((__float_as_uint(vmax) >> 23) & 0xffu);
-  return min(253, max(1, 267 - eb));
-}
-__device__ __forceinline__ void p_split(const float x0, const float x1, unsigned& hi, unsigned& lo) {
-  const f32x2 v = {x0, x1};
-  const f16x2 h = __builtin_convertvector(v, f16x2);
-  const f32x2 r = v - __builtin_convertvector(h, f32x2);
-  const f16x2 l = __builtin_convertvector(r, f16x2);
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, l);
-}
 
 template <int NQ>
 struct PairSmem {
@@ -122,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
           }
         }
     for (int o = 32; o > 0; o >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, o));
-    const int ge = p_scale_exp(gmax);
+    const int ge = fp16_scale_exp(gmax);
     const float gs = __uint_as_float((unsigned)ge << 23);
     ginv = __uint_as_float((unsigned)(254 - ge) << 23);
 #pragma unroll
@@ -137,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
           const float g0 = g0v * ((r < k && c < k) ? 1.f : 0.f);
           const float g1v = a.XtX[(size_t)min(r, k - 1) * k + min(c + 1, k - 1)];
           const float g1 = g1v * ((r < k && c + 1 < k) ? 1.f : 0.f);
-          p_split(g0 * gs, g1 * gs, hi[e / 2], lo[e / 2]);
+          split_f16(g0 * gs, g1 * gs, hi[e / 2], lo[e / 2]);
         }
         const uint4 h4 = {hi[0], hi[1], hi[2], hi[3]}, l4 = {lo[0], lo[1], lo[2], lo[3]};
         if constexpr (GREG) {
@@ -200,7 +161,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
   };
   auto settle_indices = [&]() {   // a use the compiler cannot move: the wait for the request sits HERE
     if constexpr (!GREG) {
-      wait_vm0();
+      wait_vm<0>();
       return;
     }
 #pragma unroll
@@ -330,8 +291,8 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
         float vmax = 0.f;
 #pragma unroll
         for (int rr = 0; rr < RPN; rr++) vmax = fmaxf(vmax, fabsf(v[rr]));
-        vmax = p_row16_max(vmax);
-        const int ve = p_scale_exp(vmax);
+        vmax = row16_max(vmax);
+        const int ve = fp16_scale_exp(vmax);
         const float vs = __uint_as_float((unsigned)ve << 23);
         vinv = __uint_as_float((unsigned)(254 - ve) << 23) * (mode == 0 ? -1.f : 1.f);
         {
@@ -339,8 +300,8 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
 #pragma unroll
           for (int c = 0; c < VW; c++) w4[c] = (g2 == 0 ? v[c] : v[VW + c]) * vs;
           unsigned h0, l0, h1, l1;
-          p_split(w4[0], w4[1], h0, l0);
-          p_split(w4[2], w4[3], h1, l1);
+          split_f16(w4[0], w4[1], h0, l0);
+          split_f16(w4[2], w4[3], h1, l1);
           const int off = col * SM::ps + g2 * 16 * VW + i * VW;
           *reinterpret_cast<uint2*>(sPh + off) = make_uint2(h0, h1);
           *reinterpret_cast<uint2*>(sPl + off) = make_uint2(l0, l1);
@@ -424,7 +385,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
         wave_sync();
         const float t = tacc[lslot];
         const float dd = ltgt - t;
-        lacc = p_pair_sum(p_row16_sum((lgrp && lslot < cnt) ? cl * dd * dd : 0.f));
+        lacc = pair_sum(row16_sum((lgrp && lslot < cnt) ? cl * dd * dd : 0.f));
       }
       if (mode != 2) {
         // (3) the products are complete: fold this row's G v into group 0's partial sums, then reduce the two groups
@@ -437,7 +398,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
           for (int c = 0; c < VW; c++) acc[b * VW + c] = fmaf(f, o[c], acc[b * VW + c]);
         }
 #pragma unroll
-        for (int rr = 0; rr < RPN; rr++) out[rr] = p_pair_sum(acc[rr]);
+        for (int rr = 0; rr < RPN; rr++) out[rr] = pair_sum(acc[rr]);
         if constexpr (GB) {
           if (mode == 0) {
 #pragma unroll
@@ -458,7 +419,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
       float s = 0.f;
 #pragma unroll
       for (int rr = 0; rr < RPN; rr++) s = fmaf(u[rr], w[rr], s);
-      return p_row16_sum(s);
+      return row16_sum(s);
     };
 
     float dummy = 0.f;
@@ -484,7 +445,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
       }
       const float rsnew = dot16(r, r);   // (outside the per-half branch: the DPP reductions want whole rows of lanes)
       if (!conv) {
-        if (rsnew < kCgTolP) {
+        if (rsnew < kCgTol) {
           conv = true;
         } else {
           const float beta = (float)((double)rsnew / (double)rsold);

@@ -32,8 +32,6 @@ namespace {
 
 using namespace dev;
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 // resident kernels with CAPQ >= this many quads run the dense G v product of a sweep before the quad pass, not after it
 constexpr int kGvFirstMinCapq = 16;
 // streamed rows: quads per wave of the row's prefix that stay in LDS across the sweeps.  4 = one quad-pass block = 128
@@ -47,7 +45,6 @@ constexpr int kStreamPrefixQ = 4;
 // while the current chunk is in flight (-3 % on the streamed launch); the explicit one is at 256 VGPRs and would spill
 constexpr int kIdxPrefetchMaxWpr = 2;
 
-constexpr float kCgTolQ = 1e-10f;  // CG_TOL, inst/include/wrmf.hpp:22
 constexpr int kMaxSavedSweeps = 4;  // streamed rows keep the dot products of up to this many CG steps
 
 template <int KP>
@@ -66,34 +63,7 @@ struct Piece<4> { using type = float4; };
 template <>
 struct Piece<2> { using type = float2; };
 
-// sum over the 16 lanes of a DPP row; every lane of the row gets the result (needs full EXEC)
-__device__ __forceinline__ float row16_sum(float v) {
-  v += dpp<0xB1>(v);   // quad_perm:[1,0,3,2]
-  v += dpp<0x4E>(v);   // quad_perm:[2,3,0,1]
-  v += dpp<0x141>(v);  // row_half_mirror
-  v += dpp<0x140>(v);  // row_mirror
-  return v;
-}
-// sum over the 4 groups (lanes l, l^16, l^32, l^48), result in all 4, bitwise identical everywhere.
-// v_permlane16_swap exchanges the odd rows of its first operand with the even rows of its second,
-// v_permlane32_swap the upper half of the first with the lower half of the second; fed two copies of v
-// they leave {v_even, v_even | ...} and {v_odd, v_odd | ...}, whose sum is the pairwise all-reduce --
-// pure VALU, no LDS round trip (ds_bpermute costs ~100+ cycles of latency per stage).
-__device__ __forceinline__ float groups_sum(float v) {
-  {
-    const unsigned u = __float_as_uint(v);
-    const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-  {
-    const unsigned u = __float_as_uint(v);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-  return v;
-}
-
-// The same sum for FOUR registers at once, as a reduce-scatter: row g of the result holds the total of a_g.  Fed two
+// groups_sum for FOUR registers at once, as a reduce-scatter: row g of the result holds the total of a_g.  Fed two
 // DIFFERENT registers a lane swap is already the exchange step of both -- (a0, a1) -> rows (a0: 0+1, a1: 0+1, a0: 2+3, a1: 2+3)
 // -- so four registers cost 3 swaps + 3 adds instead of 8 + 8 (+ 8 copies: the swap overwrites both operands).  The pairing
 // is groups_sum's, (0 + 1) + (2 + 3): the totals are bit for bit the same.
@@ -105,48 +75,11 @@ __device__ __forceinline__ float groups_reduce_scatter4(const float a0, const fl
   const auto t = __builtin_amdgcn_permlane32_swap(__float_as_uint(c), __float_as_uint(d), false, false);
   return __uint_as_float(t[0]) + __uint_as_float(t[1]);
 }
-// ... and back: row g of `r` to every row of out[g]
-__device__ __forceinline__ void groups_all_gather4(const float r, float& o0, float& o1, float& o2, float& o3) {
-  const unsigned u = __float_as_uint(r);
-  const auto h = __builtin_amdgcn_permlane32_swap(u, u, false, false);            // rows (0, 1, 0, 1), (2, 3, 2, 3)
-  const auto lo = __builtin_amdgcn_permlane16_swap(h[0], h[0], false, false);     // rows (0, 0, 0, 0), (1, 1, 1, 1)
-  const auto hi = __builtin_amdgcn_permlane16_swap(h[1], h[1], false, false);
-  o0 = __uint_as_float(lo[0]);
-  o1 = __uint_as_float(lo[1]);
-  o2 = __uint_as_float(hi[0]);
-  o3 = __uint_as_float(hi[1]);
-}
-
 // ---- dense product on the matrix cores (DMF instantiation: one-wave rows of <= 32 non-zeros at rank 65..128) ----
 // The four rows a workgroup solves side by side share every G v product: G is held in REGISTERS as two fp16 terms
 // (wave w owns rows [32w, 32w + 32) as A operands of v_mfma_f32_16x16x32_f16), the four vectors are published to LDS as
 // two fp16 terms each, and G v = (Gh + Gl)(vh + vl) is accumulated in fp32 from the three products of order < 2
 // (2^-21 per product; both operands scaled by powers of two so that their largest entry lands in [2^13, 2^14)).
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-// power of two that brings `vmax` into [2^13, 2^14), as the biased exponent (1..253, so that its inverse is normal too)
-__device__ __forceinline__ int fp16_scale_exp(float vmax) {
-  const int eb = (int)((__float_as_uint(vmax) >> 23) & 0xffu);
-  return min(253, max(1, 267 - eb));
-}
-// x (already scaled) -> fl16(x), fl16(x - fl16(x)); the residual is exact in fp32
-__device__ __forceinline__ void split_f16(const float x0, const float x1, unsigned& hi, unsigned& lo) {
-  const f32x2 v = {x0, x1};
-  const f16x2 h = __builtin_convertvector(v, f16x2);
-  const f32x2 r = v - __builtin_convertvector(h, f32x2);
-  const f16x2 l = __builtin_convertvector(r, f16x2);
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, l);
-}
-__device__ __forceinline__ float row16_max(float v) {
-  v = fmaxf(v, dpp<0xB1>(v));
-  v = fmaxf(v, dpp<0x4E>(v));
-  v = fmaxf(v, dpp<0x141>(v));
-  v = fmaxf(v, dpp<0x140>(v));
-  return v;
-}
-
 // DMF: 0 = dense product on the vector units (G in LDS as fp32), 1 = on the matrix cores with this wave's rows of G as fp16
 // terms in REGISTERS (rows <= 32 non-zeros: 64 registers are free), 2 = the same with the fp16 terms in LDS, stored in
 // fragment order (rows of 33..64 non-zeros: the gathered vectors take 128 registers, G's 64 KB of LDS hold the terms instead
@@ -201,8 +134,11 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
     if constexpr (RPN == 8) {
       const float r0 = groups_reduce_scatter4(a8[0], a8[1], a8[2], a8[3]);
       const float r1 = groups_reduce_scatter4(a8[4], a8[5], a8[6], a8[7]);
-      groups_all_gather4(r0, a8[0], a8[1], a8[2], a8[3]);
-      groups_all_gather4(r1, a8[4], a8[5], a8[6], a8[7]);
+      float g0[4], g1[4];   // ... and back: row g of the totals to every row
+      rows_to_all<4>(r0, g0);
+      rows_to_all<4>(r1, g1);
+#pragma unroll
+      for (int e = 0; e < 4; e++) a8[e] = g0[e], a8[4 + e] = g1[e];
     }
   };
   static_assert(!DMF || (IMPLICIT && KP == 128 && WAVES == 4 && WPR == 1 && STREAM == 0), "DMF geometry");
@@ -435,7 +371,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         // that was not announced (the team's first) fetches them the same way and waits
         if (!from_pf && n > 0) {
           dma_slot(base, n);
-          wait_vm0();
+          wait_vm<0>();
         }
         wave_sync();
 #pragma unroll
@@ -1018,7 +954,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
           r[rr] = fmaf(-alpha, ap[rr], r[rr]);
         }
         const float rsnew = dot16(r, r);
-        if (rsnew < kCgTolQ) {
+        if (rsnew < kCgTol) {
           conv = true;
         } else {
           const float beta = (float)((double)rsnew / (double)rsold);
@@ -1040,7 +976,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
     }
     float rl = 0.f;
     sweep(x, 2, ap, rl, live);
-    if constexpr (DMAPF) wait_vm0();   // the announced row's indices have long landed; nothing of this wave's is in flight after this
+    if constexpr (DMAPF) wait_vm<0>();   // the announced row's indices have long landed; nothing of this wave's is in flight after this
     if constexpr (IDXPF && STREAM == 0) {
       // settle the prefetch registers HERE (their loads were issued three sweeps ago): left to the next row's first use, the
       // wait sits behind that row's warm-start request -- loads return in order -- and the vectors are requested a round trip late

@@ -24,14 +24,6 @@ namespace {
 
 using namespace dev;
 
-__device__ __forceinline__ float row16_sum_c(float v) {
-  v += dpp<0xB1>(v);
-  v += dpp<0x4E>(v);
-  v += dpp<0x141>(v);
-  v += dpp<0x140>(v);
-  return v;
-}
-
 template <int KP>
 struct Chol2Smem {
   static constexpr int BS = KP / 16;
@@ -43,35 +35,6 @@ struct Chol2Smem {
   static constexpr size_t vec_floats = (size_t)3 * KP + 2 * TC;    // rhs/z/y, S accumulator, spare, c, c1
   static constexpr size_t bytes = (tile_floats + panel_floats + diag_floats + vec_floats + 16) * 4 + 64;
 };
-
-// The 4 waves gather one 32-vector chunk: wave w fetches tile rows [8w, 8w+8).  VEC: all index loads, then
-// all 16-byte vector loads of the wave are in flight together (2 dependent round trips per chunk).
-template <int KP, bool VEC>
-__device__ __forceinline__ void chol_gather_chunk(const AlsArgs& a, int base, int ccnt, float* sT, int wv, int lane) {
-  constexpr int LDT = KP + 4;
-  const int k = a.k;
-  if constexpr (VEC) {
-    constexpr int LPV = KP / 4, VPI = 64 / LPV, NQ = 8 / VPI;
-    const int c4 = lane % LPV, jo = lane / LPV;
-    int ids[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) ids[q] = a.row_idx[base + min(8 * wv + q * VPI + jo, ccnt - 1)];
-    float4 v[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) v[q] = *reinterpret_cast<const float4*>(a.X + (size_t)ids[q] * k + min(c4 * 4, k - 4));
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-      const int j = 8 * wv + q * VPI + jo;
-      if (j < ccnt && c4 * 4 < k) *reinterpret_cast<float4*>(sT + j * LDT + c4 * 4) = v[q];
-    }
-  } else {
-    for (int j = 8 * wv; j < min(8 * wv + 8, ccnt); j++) {
-      const int id = rfl(a.row_idx[base + j]);
-      const float* src = a.X + (size_t)id * k;
-      for (int e = lane; e < k; e += 64) sT[j * LDT + e] = src[e];
-    }
-  }
-}
 
 // 3 waves per SIMD (168 VGPRs): three rows per CU overlap each other's serial phases; measured 0.160 s ->
 // 0.133 s per 1M users at k = 128 against 2 (a fourth changes nothing and spills)
@@ -183,7 +146,7 @@ __global__ __launch_bounds__(256, LONG ? 2 : kCholMinWaves) void als_chol2_kerne
         sC[tid] = a.rhs_vals ? a.rhs_vals[base + tid] : cvv;   // coefficient in the right-hand side
         sC1[tid] = IMPLICIT ? cvv - 1.f : 1.f;
       }
-      chol_gather_chunk<KP, VEC>(a, base, ccnt, sT, wv, lane);
+      gather_chunk4<KP, VEC, TC>(a, base, ccnt, sT, wv, lane);
       __syncthreads();
       if (lower) {
         for (int j = 0; j < ccnt; j++) {
@@ -321,7 +284,7 @@ __global__ __launch_bounds__(256, LONG ? 2 : kCholMinWaves) void als_chol2_kerne
           }
         }
 #pragma unroll
-        for (int x = 0; x < BS; x++) part[x] = row16_sum_c(part[x]);  // the 16 threads of block row J are one DPP row
+        for (int x = 0; x < BS; x++) part[x] = row16_sum(part[x]);  // the 16 threads of block row J are one DPP row
         if (K == J) {
           float z[BS];
 #pragma unroll
@@ -390,7 +353,7 @@ __global__ __launch_bounds__(256, LONG ? 2 : kCholMinWaves) void als_chol2_kerne
           sC[tid] = a.vals[base + tid];
           sC1[tid] = a.loss_tgt ? a.loss_tgt[base + tid] : a.loss_tgt_const;
         }
-        chol_gather_chunk<KP, VEC>(a, base, ccnt, sT, wv, lane);
+        gather_chunk4<KP, VEC, TC>(a, base, ccnt, sT, wv, lane);
         __syncthreads();
         if (wv == 0) {
           const float t = tile_dot<KP, TC>(sT, sV, lane);

@@ -39,37 +39,6 @@ namespace {
 
 using namespace dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// x (already scaled) -> fl16(x), fl16(x - fl16(x)) for a pair; the residual is exact in fp32
-__device__ __forceinline__ void lr_split(const float x0, const float x1, unsigned& hi, unsigned& lo) {
-  const f32x2 v = {x0, x1};
-  const f16x2 h = __builtin_convertvector(v, f16x2);
-  const f32x2 r = v - __builtin_convertvector(h, f32x2);
-  const f16x2 l = __builtin_convertvector(r, f16x2);
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, l);
-}
-// biased exponent e (1..253) of the power of two that brings `vmax` into [2^13, 2^14); 2^(e - 127) is the scale
-__device__ __forceinline__ int lr_scale_exp(float vmax) {
-  const int eb = (int)((__float_as_uint(vmax) >> 23) & 0xffu);
-  return min(253, max(1, 267 - eb));
-}
-__device__ __forceinline__ float lr_pow2(int biased) { return __uint_as_float((unsigned)biased << 23); }
-
-template <class F, int... I>
-__device__ __forceinline__ void lr_sfor_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void lr_sfor(F&& f) {
-  lr_sfor_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 constexpr int kLrLd = 130;   // LDS row stride (floats) of V' (fp32)
 constexpr int kLrLh = 136;   // ... (halves) of the fp16 terms of X_nnz and of W: 16-byte aligned rows for the operand reads
 constexpr int kLrLs = 65;    // ... of the n x n system
@@ -142,8 +111,8 @@ __global__ __launch_bounds__(256) void chol_lr_prep_kernel(const float* __restri
     if (tid < o) smx[tid] = fmaxf(smx[tid], smx[tid + o]);
     __syncthreads();
   }
-  const int eM = lr_scale_exp(fmaxf(smx[0], 1e-30f));
-  const float sM = lr_pow2(eM);
+  const int eM = fp16_scale_exp(fmaxf(smx[0], 1e-30f));
+  const float sM = pow2(eM);
   if (tid == 0) flags[1] = (unsigned)eM;
   for (int e = tid; e < KP * KP; e += 256) {
     const int r = e / KP, c = e % KP;
@@ -213,8 +182,8 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
   if (flags[0] != 0) return;   // some confidence < 1 or XtX not positive definite: wrmf_chol.hip takes these rows
   // operand scales: max |X| from the statistics block in front of the flags (launch_ne_stats: flags = stats + 2), the
   // exponent of Mt from the prep kernel
-  const int ex = lr_scale_exp(fmaxf(__uint_as_float(flags[-2]), 1e-30f)), eM = (int)flags[1];
-  const float sx = lr_pow2(ex), inv_xm = lr_pow2(254 - ex) * lr_pow2(254 - eM);   // 2^-(ex - 127) * 2^-(eM - 127)
+  const int ex = fp16_scale_exp(fmaxf(__uint_as_float(flags[-2]), 1e-30f)), eM = (int)flags[1];
+  const float sx = pow2(ex), inv_xm = pow2(254 - ex) * pow2(254 - eM);   // 2^-(ex - 127) * 2^-(eM - 127)
 
   // the passes: [0, P64) one row each, [P64, P64 + P32) two rows, then four; the list is longest first
   const int n16 = n_rows - n64 - n32;
@@ -308,7 +277,7 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
       auto put = [&](const int u) {
         const int j = wv + 4 * u;
         unsigned hi = 0u, lo = 0u;
-        if ((vmask >> j) & 1) lr_split(v[u].x * sx, v[u].y * sx, hi, lo);
+        if ((vmask >> j) & 1) split_f16(v[u].x * sx, v[u].y * sx, hi, lo);
         *reinterpret_cast<unsigned*>(sXh + j * LH + 2 * lane) = hi;
         *reinterpret_cast<unsigned*>(sXl + j * LH + 2 * lane) = lo;
       };
@@ -362,16 +331,16 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
     if (lane == 0) sT[wv] = wmax;
     __syncthreads();   // V' complete, every wave is done with the fp16 terms of X_nnz
     // 2b. the fp16 terms of W = D^1/2 V' * 2^ew over the X_nnz terms (thread t: slot t / 4, 32 columns)
-    const int ew = lr_scale_exp(fmaxf(fmaxf(fmaxf(sT[0], sT[1]), fmaxf(sT[2], sT[3])), 1e-30f));
+    const int ew = fp16_scale_exp(fmaxf(fmaxf(fmaxf(sT[0], sT[1]), fmaxf(sT[2], sT[3])), 1e-30f));
     {
       const int j = tid >> 2, part = tid & 3;
       if (j < 32 * nrt) {
-        const float sw = lr_pow2(ew) * sQ[j];
+        const float sw = pow2(ew) * sQ[j];
         const float* vr = sV + j * LD + 32 * part;
 #pragma unroll
         for (int e = 0; e < 32; e += 2) {
           unsigned hi, lo;
-          lr_split(vr[e] * sw, vr[e + 1] * sw, hi, lo);
+          split_f16(vr[e] * sw, vr[e + 1] * sw, hi, lo);
           *reinterpret_cast<unsigned*>(sXh + j * LH + 32 * part + e) = hi;
           *reinterpret_cast<unsigned*>(sXl + j * LH + 32 * part + e) = lo;
         }
@@ -433,7 +402,7 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
         }
       }
       __syncthreads();   // every wave has read its operands: the region becomes S
-      const float inv_w2 = lr_pow2(254 - ew) * lr_pow2(254 - ew);
+      const float inv_w2 = pow2(254 - ew) * pow2(254 - ew);
       if (mine) {
 #pragma unroll
         for (int e = 0; e < 16; e++) {
@@ -467,7 +436,7 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
         // pivot column, is served first and by v_readlane, so that the next pivot's chain (broadcast, reciprocal, scale) starts
         // before this pivot's other columns are done.
         float pj = readlane_f(r[0], 0);
-        lr_sfor<NS>([&](auto jt) {
+        static_for<NS>([&](auto jt) {
           constexpr int j = decltype(jt)::value;
           const float inv = __builtin_amdgcn_rcpf(pj);   // (>= 1: S = I + W W^T; 1 ulp)
           const float uj = readlane_f(u, j);
@@ -482,7 +451,7 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
               dpp_ready(r[j]);
               rows_to_all<4>(r[j], rep);
               dpp_ready(rep[0], rep[1], rep[2], rep[3]);
-              lr_sfor<NS - j - 2>([&](auto ct) {
+              static_for<NS - j - 2>([&](auto ct) {
                 constexpr int c = j + 2 + decltype(ct)::value;
                 fnma_row_bcast<c % 16>(r[c], rep[c / 16], lij);
               });
@@ -522,7 +491,7 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
             rep[0] = rep[1] = v;
           }
         };
-        lr_sfor<SL>([&](auto tt) {
+        static_for<SL>([&](auto tt) {
           constexpr int t = decltype(tt)::value;
           float rep[2], ur[2];
           dpp_ready(r[t], u);   // (both were last written by the FMAs of the step before, which hipcc cannot see into)
@@ -534,13 +503,13 @@ __global__ __launch_bounds__(256, 2) void als_chol_lr_kernel(AlsArgs a, const in
           if (il == t) dinv = inv;
           const float lij = il > t ? r[t] * inv : 0.f;
           fnma_row_bcast<t % 16>(u, ur[t / 16], lij);
-          lr_sfor<SL - t - 1>([&](auto ct) {
+          static_for<SL - t - 1>([&](auto ct) {
             constexpr int c = t + 1 + decltype(ct)::value;
             fnma_row_bcast<c % 16>(r[c], rep[c / 16], lij);
           });
         });
         float acc = 0.f, z = 0.f;
-        lr_sfor<SL>([&](auto tt) {
+        static_for<SL>([&](auto tt) {
           constexpr int c = SL - 1 - decltype(tt)::value;
           if (il == c) z = (u - acc) * dinv;
           float zr[2];
@@ -685,23 +654,6 @@ template <int E>
 __device__ __forceinline__ void mul_row_bcast(float& r, const float u) {
   asm("v_mul_f32_dpp %0, %1, %0 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "+v"(r) : "v"(u), "n"(E));
 }
-// copies of the value held one per lane such that lane t of a GROUP of SL lanes is lane t % 16 of rep[t / 16] in every lane
-// of the group (SL = 64: the wave; 32; 16: a row of 16 lanes)
-template <int SL>
-__device__ __forceinline__ void lrw_group(const float v, float (&rep)[4]) {
-  if constexpr (SL == 64) {
-    rows_to_all<4>(v, rep);
-  } else if constexpr (SL == 32) {
-    const unsigned uu = __float_as_uint(v);
-    const auto sw = __builtin_amdgcn_permlane16_swap(uu, uu, false, false);   // rows (0, 0, 2, 2) and (1, 1, 3, 3)
-    rep[0] = __uint_as_float(sw[0]);
-    rep[1] = __uint_as_float(sw[1]);
-    rep[2] = rep[3] = 0.f;
-  } else {
-    rep[0] = v;
-    rep[1] = rep[2] = rep[3] = 0.f;
-  }
-}
 // 16 bytes at p + OFF, not waited for (the caller counts)
 template <int OFF>
 __device__ __forceinline__ void lrw_ld16(f32x4& d, const float* p) {
@@ -713,12 +665,6 @@ __device__ __forceinline__ void lrw_wait_all(f32x4 (&x)[8][2]) {   // (tied to t
                  "+v"(x[4][0]), "+v"(x[4][1]), "+v"(x[5][0]), "+v"(x[5][1]), "+v"(x[6][0]), "+v"(x[6][1]), "+v"(x[7][0]), "+v"(x[7][1])
                :: "memory");
 }
-__device__ __forceinline__ f16x8 lrw_pack(const unsigned a, const unsigned b, const unsigned c, const unsigned d) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 v = {a, b, c, d};
-  return __builtin_bit_cast(f16x8, v);
-}
-
 // (S + padd I) z = u in registers, S symmetric, lane i = row i of its system: rl[t] = S[i][base + t] (diagonal entries are only
 // ever read as pivots, which is where padd is added: the identity of S = I + D^1/2 T D^1/2, or lambda).  SL = 64: one system on
 // the whole wave, NS <= 64 columns held (the register solve of the workgroup kernel: the pivot column's rows of 16 lanes are
@@ -736,7 +682,7 @@ __device__ __forceinline__ void lrw_solve(float (&rl)[NS], float u, const int i,
   z = 0.f;
   if constexpr (SL == 64) {
     float pj = readlane_f(rl[0], 0) + readlane_f(padd, 0);
-    lr_sfor<NS>([&](auto jt) {
+    static_for<NS>([&](auto jt) {
       constexpr int j = decltype(jt)::value;
       const float inv = __builtin_amdgcn_rcpf(pj);
       const float uj = readlane_f(u, j);
@@ -752,7 +698,7 @@ __device__ __forceinline__ void lrw_solve(float (&rl)[NS], float u, const int i,
           dpp_ready(cj);
           rows_to_all<4>(cj, rep);
           dpp_ready(rep[0], rep[1], rep[2], rep[3]);
-          lr_sfor<NS - j - 2>([&](auto ct) {
+          static_for<NS - j - 2>([&](auto ct) {
             constexpr int c = j + 2 + decltype(ct)::value;
             fnma_row_bcast<c % 16>(rl[c], rep[c / 16], lij);
           });
@@ -770,20 +716,20 @@ __device__ __forceinline__ void lrw_solve(float (&rl)[NS], float u, const int i,
     }
   } else {
     static_assert(NS == SL || SL == 64, "packed systems hold all their columns");
-    lr_sfor<SL>([&](auto tt) {
+    static_for<SL>([&](auto tt) {
       constexpr int t = decltype(tt)::value;
       float rep[4], ur[4];
       float ct = unit ? 0.f : rl[t];   // column t as the symmetric system has it
       dpp_ready(ct, u);
-      lrw_group<SL>(ct, rep);
-      lrw_group<SL>(u, ur);
+      group_rows_to_all<SL>(ct, rep);
+      group_rows_to_all<SL>(u, ur);
       dpp_ready(rep[0], rep[1], ur[0], ur[1]);
       const float pv = lr_row_bcast<t % 16>(rep[t / 16]) + padd;   // (padd is uniform inside a group)
       const float inv = __builtin_amdgcn_rcpf(pv);
       if (il == t) dinv = inv;
       const float lij = ie > t ? rl[t] * inv : 0.f;
       fnma_row_bcast<t % 16>(u, ur[t / 16], lij);
-      lr_sfor<SL - t - 1>([&](auto ct2) {
+      static_for<SL - t - 1>([&](auto ct2) {
         constexpr int c = t + 1 + decltype(ct2)::value;
         fnma_row_bcast<c % 16>(rl[c], rep[c / 16], lij);
       });
@@ -791,11 +737,11 @@ __device__ __forceinline__ void lrw_solve(float (&rl)[NS], float u, const int i,
     u_fwd = u;
     if (unit) dinv = 0.f;
     float bacc = 0.f;
-    lr_sfor<SL>([&](auto tt) {
+    static_for<SL>([&](auto tt) {
       constexpr int c = SL - 1 - decltype(tt)::value;
       if (il == c) z = (u - bacc) * dinv;
       float zr[4];
-      lrw_group<SL>(z, zr);
+      group_rows_to_all<SL>(z, zr);
       dpp_ready(zr[0], zr[1]);
       const float m = il < c ? -rl[c] : 0.f;
       fnma_row_bcast<c % 16>(bacc, zr[c / 16], m);
@@ -831,8 +777,8 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
         *reinterpret_cast<const uint4*>(MT16 + (size_t)t * KP * KP + (size_t)r * KP + 8 * p);
   }
   __syncthreads();
-  const int ex = lr_scale_exp(fmaxf(__uint_as_float(flags[-2]), 1e-30f)), eM = (int)flags[1];
-  const float sx = lr_pow2(ex), cs = lr_pow2(254 - ex) * lr_pow2(254 - eM), cm = lr_pow2(254 - eM);
+  const int ex = fp16_scale_exp(fmaxf(__uint_as_float(flags[-2]), 1e-30f)), eM = (int)flags[1];
+  const float sx = pow2(ex), cs = pow2(254 - ex) * pow2(254 - eM), cm = pow2(254 - eM);
 
   const int P64 = n64, P32 = (n32 + 1) >> 1;
   struct PassGeo { int lsh, li, lim; };
@@ -912,7 +858,7 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
       // (from inline asm: hipcc sinks plain loads to their uses -- six in flight, a round trip per chunk -- whatever
       //  scheduling barrier follows them; the one wait below covers everything this wave has in flight)
       f32x4 xr[2][8][2];   // [slot tile][chunk][two 16-byte pieces]
-      lr_sfor<8>([&](auto ct) {
+      static_for<8>([&](auto ct) {
         constexpr int c8 = 7 - decltype(ct)::value;
         lrw_ld16<64 * c8>(xr[0][c8][0], x0);
         lrw_ld16<64 * c8 + 16>(xr[0][c8][1], x0);
@@ -922,7 +868,7 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
       lrw_wait_all(xr[0]);
       lrw_wait_all(xr[1]);
       const _Float16* ap0 = sM + (size_t)n * LH + 8 * hf;
-      lr_sfor<8>([&](auto cht) {
+      static_for<8>([&](auto cht) {
         constexpr int ch = 7 - decltype(cht)::value;
         if constexpr (ch % 2 == 1) {   // first use of block row ch / 2
 #pragma unroll
@@ -934,14 +880,14 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
           const f32x4 p0 = xr[st][ch][0], p1 = xr[st][ch][1];
           const float sxs = st ? sx1 : sx0;
           unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-          lr_split(p0.x * sxs, p0.y * sxs, h0, l0);
-          lr_split(p0.z * sxs, p0.w * sxs, h1, l1);
-          lr_split(p1.x * sxs, p1.y * sxs, h2, l2);
-          lr_split(p1.z * sxs, p1.w * sxs, h3, l3);
-          bh[st] = lrw_pack(h0, h1, h2, h3);
-          bl[st] = lrw_pack(l0, l1, l2, l3);
+          split_f16(p0.x * sxs, p0.y * sxs, h0, l0);
+          split_f16(p0.z * sxs, p0.w * sxs, h1, l1);
+          split_f16(p1.x * sxs, p1.y * sxs, h2, l2);
+          split_f16(p1.z * sxs, p1.w * sxs, h3, l3);
+          bh[st] = pack_f16x8(h0, h1, h2, h3);
+          bl[st] = pack_f16x8(l0, l1, l2, l3);
         }
-        lr_sfor<4 - ch / 2>([&](auto obt) {
+        static_for<4 - ch / 2>([&](auto obt) {
           constexpr int ob = ch / 2 + decltype(obt)::value;   // Mt is lower triangular: block row ob ends at chunk 2 ob + 1
           const _Float16* ap = ap0 + (size_t)(32 * ob) * LH + 16 * ch;
           const f16x8 ah = *reinterpret_cast<const f16x8*>(ap);
@@ -965,8 +911,8 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
 #pragma unroll
         for (int e = 0; e < 16; e++) wm = fmaxf(wm, fabsf(acc[ob][st][e]));
     for (int o = 32; o > 0; o >>= 1) wm = fmaxf(wm, __shfl_xor(wm, o));
-    const int ew = lr_scale_exp(fmaxf(wm, 1e-30f));
-    const float fw = lr_pow2(ew), c2 = cs * lr_pow2(254 - ew);   // terms = V' / c2
+    const int ew = fp16_scale_exp(fmaxf(wm, 1e-30f));
+    const float fw = pow2(ew), c2 = cs * pow2(254 - ew);   // terms = V' / c2
     f16x8 th[4][2][2], tl[4][2][2];
 #pragma unroll
     for (int ob = 0; ob < 4; ob++)
@@ -977,9 +923,9 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
           unsigned hh[4], ll[4];
 #pragma unroll
           for (int p = 0; p < 4; p++)
-            lr_split(acc[ob][st][8 * g + 2 * p] * fw, acc[ob][st][8 * g + 2 * p + 1] * fw, hh[p], ll[p]);
-          th[ob][st][g] = lrw_pack(hh[0], hh[1], hh[2], hh[3]);
-          tl[ob][st][g] = lrw_pack(ll[0], ll[1], ll[2], ll[3]);
+            split_f16(acc[ob][st][8 * g + 2 * p] * fw, acc[ob][st][8 * g + 2 * p + 1] * fw, hh[p], ll[p]);
+          th[ob][st][g] = pack_f16x8(hh[0], hh[1], hh[2], hh[3]);
+          tl[ob][st][g] = pack_f16x8(ll[0], ll[1], ll[2], ll[3]);
         }
     // ---- 3. T = V' V'^T / c2^2, all four tiles (packed rows: the two diagonal ones, the others only feed lanes that do not read them); tile (a, b) at lane (n, hf), register v = T[32 a + rho(v, hf)][32 b + n] with
     // rho(v, hf) = 8 (v / 4) + 4 hf + v % 4 -- by symmetry ROW 32 b + n at the columns 32 a + rho(v, hf).  Lane (n, 0) is slot n
@@ -1063,13 +1009,13 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
       // the other rows never see them: the system stays the symmetric one.
       const bool unit = valid && !(sq > 0.f);
       float repc[4], repq[4];
-      lrw_group<SL>(cval, repc);
-      lrw_group<SL>(sqs, repq);
+      group_rows_to_all<SL>(cval, repc);
+      group_rows_to_all<SL>(sqs, repq);
       dpp_ready(repc[0], repc[1], repc[2], repc[3]);
       dpp_ready(repq[0], repq[1], repq[2], repq[3]);
       const float rowf = unit ? c2 : sqs;
       float tc = 0.f;   // -(T c)_i / c2^2
-      lr_sfor<NS>([&](auto tt) {
+      static_for<NS>([&](auto tt) {
         constexpr int t = decltype(tt)::value;
         fnma_row_bcast<t % 16>(tc, repc[t / 16], rl[t]);
         rl[t] *= rowf;
@@ -1100,12 +1046,12 @@ __global__ __launch_bounds__(512) void als_chol_lrw_kernel(AlsArgs a, const int3
         for (int q = 0; q < 4; q++) ec[st][q] = *reinterpret_cast<const float4*>(sE + 32 * st + 8 * q + 4 * hf);
       const _Float16* bp0 = sMT + (size_t)n * LH + 8 * hf;
       const float pscale = c2;
-      lr_sfor<4>([&](auto cbt) {
+      static_for<4>([&](auto cbt) {
         constexpr int cb = decltype(cbt)::value;
         f32x16 p0, p1;
 #pragma unroll
         for (int e = 0; e < 16; e++) p0[e] = p1[e] = 0.f;
-        lr_sfor<8 - 2 * cb>([&](auto cht) {
+        static_for<8 - 2 * cb>([&](auto cht) {
           constexpr int chunk = 2 * cb + decltype(cht)::value;   // Mt[kk][c] = 0 for kk < c
           constexpr int ob = chunk / 2, g = chunk % 2;
           const _Float16* bp = bp0 + (size_t)(32 * cb) * LH + 16 * chunk;
@@ -1201,8 +1147,8 @@ __global__ __launch_bounds__(512) void als_chol_lrx_kernel(AlsArgs a, const int3
   __shared__ double sRed[8];
   const int tid = threadIdx.x, lane = tid & 63, wv = rfl(tid >> 6);
   float* sE = sEall[wv];
-  const int ex = lr_scale_exp(fmaxf(__uint_as_float(stats[0]), 1e-30f));
-  const float sx = lr_pow2(ex), ux = lr_pow2(254 - ex);   // scale of the fp16 terms and its inverse
+  const int ex = fp16_scale_exp(fmaxf(__uint_as_float(stats[0]), 1e-30f));
+  const float sx = pow2(ex), ux = pow2(254 - ex);   // scale of the fp16 terms and its inverse
 
   const int P64 = n64, P32 = (n32 + 1) >> 1;
   struct PassGeo { int lsh, li, lim; };
@@ -1253,7 +1199,7 @@ __global__ __launch_bounds__(512) void als_chol_lrx_kernel(AlsArgs a, const int3
       unsigned w[4];
 #pragma unroll
       for (int q = 0; q < 4; q++) w[q] = (mine && (e1 >> 1) == q) ? ((e1 & 1) ? 0x3c000000u : 0x00003c00u) : 0u;
-      idf[cc] = lrw_pack(w[0], w[1], w[2], w[3]);
+      idf[cc] = pack_f16x8(w[0], w[1], w[2], w[3]);
     }
   }
   for (; it < pass_hi; it += G) {
@@ -1290,7 +1236,7 @@ __global__ __launch_bounds__(512) void als_chol_lrx_kernel(AlsArgs a, const int3
       const float* x0 = a.X + (size_t)idsw[0] * KP + 8 * hf;
       const float* x1 = a.X + (size_t)idsw[1] * KP + 8 * hf;
       f32x4 xr[2][NCH][2];
-      lr_sfor<NCH>([&](auto ct) {
+      static_for<NCH>([&](auto ct) {
         constexpr int c8 = decltype(ct)::value;
         lrw_ld16<64 * c8>(xr[0][c8][0], x0);
         lrw_ld16<64 * c8 + 16>(xr[0][c8][1], x0);
@@ -1306,12 +1252,12 @@ __global__ __launch_bounds__(512) void als_chol_lrx_kernel(AlsArgs a, const int3
           const f32x4 p0 = xr[st][ch][0], p1 = xr[st][ch][1];
           const float sxs = st ? sx1 : sx0;
           unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-          lr_split(p0.x * sxs, p0.y * sxs, h0, l0);
-          lr_split(p0.z * sxs, p0.w * sxs, h1, l1);
-          lr_split(p1.x * sxs, p1.y * sxs, h2, l2);
-          lr_split(p1.z * sxs, p1.w * sxs, h3, l3);
-          th[ch][st] = lrw_pack(h0, h1, h2, h3);
-          tl[ch][st] = lrw_pack(l0, l1, l2, l3);
+          split_f16(p0.x * sxs, p0.y * sxs, h0, l0);
+          split_f16(p0.z * sxs, p0.w * sxs, h1, l1);
+          split_f16(p1.x * sxs, p1.y * sxs, h2, l2);
+          split_f16(p1.z * sxs, p1.w * sxs, h3, l3);
+          th[ch][st] = pack_f16x8(h0, h1, h2, h3);
+          tl[ch][st] = pack_f16x8(l0, l1, l2, l3);
         }
     }
     // ---- 2. T sx^2 = X_nnz^T X_nnz on the matrix cores, rows by lane swaps (see the implicit kernel) ----
@@ -1402,7 +1348,7 @@ __global__ __launch_bounds__(512) void als_chol_lrx_kernel(AlsArgs a, const int3
       for (int st = 0; st < 2; st++)
 #pragma unroll
         for (int q = 0; q < 4; q++) ec[st][q] = *reinterpret_cast<const float4*>(sE + 32 * st + 8 * q + 4 * hf);
-      lr_sfor<NB>([&](auto cbt) {
+      static_for<NB>([&](auto cbt) {
         constexpr int cb = decltype(cbt)::value;
         f32x16 p0, p1;
 #pragma unroll

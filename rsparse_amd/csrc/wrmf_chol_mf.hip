@@ -90,9 +90,9 @@ struct MfSmem {
 // panel (K, Q): registers 4 Q .. 4 Q + 3 of the tiles (K + s, K), s < 4 - K; the slots [S0, S1) of them
 template <int K, int Q, int S0, int S1>
 __device__ __forceinline__ void mf_copy_out(float (&P)[4][4]) {
-  mf_sfor<(S1 < 4 - K ? S1 : 4 - K) - S0>([&](auto st) {
+  static_for<(S1 < 4 - K ? S1 : 4 - K) - S0>([&](auto st) {
     constexpr int s = S0 + decltype(st)::value;
-    mf_sfor<4>([&](auto mt) {
+    static_for<4>([&](auto mt) {
       constexpr int m = decltype(mt)::value;
       P[s][m] = mf_rd<16 * mf_tid(K + s, K) + 4 * Q + m>();
     });
@@ -103,9 +103,9 @@ template <int K, int Q>
 __device__ __forceinline__ void mf_copy_in_update(const float (&Pm)[4][4]) {
   // (the rows at and above the panel's diagonal block are stored as the zeros the operands need: nothing reads them again --
   // the backward pass takes the diagonal blocks from LDS)
-  mf_sfor<4 - K>([&](auto st) {
+  static_for<4 - K>([&](auto st) {
     constexpr int s = decltype(st)::value;
-    mf_sfor<4>([&](auto mt) {
+    static_for<4>([&](auto mt) {
       constexpr int m = decltype(mt)::value;
       mf_wr<16 * mf_tid(K + s, K) + 4 * Q + m>(Pm[s][m]);
     });
@@ -113,13 +113,13 @@ __device__ __forceinline__ void mf_copy_in_update(const float (&Pm)[4][4]) {
   // tile (K + s, K + s2) -= P_{s2} P_s^T: register m = columns (m, 4 + m).  m outermost: consecutive matrix instructions go
   // to different tiles (a tile's four are a dependent chain).  The tiles of block column K are skipped after its last panel
   // (the operand is all zeros there).
-  mf_sfor<4>([&](auto mt) {
+  static_for<4>([&](auto mt) {
     constexpr int m = decltype(mt)::value;
-    mf_sfor<4 - K>([&](auto k2t) {
+    static_for<4 - K>([&](auto k2t) {
       constexpr int s2 = decltype(k2t)::value;   // K2 = K + s2
       if constexpr (s2 > 0 || Q < 3) {
         const float na = -Pm[s2][m];
-        mf_sfor<4 - K - s2>([&](auto it) {
+        static_for<4 - K - s2>([&](auto it) {
           constexpr int s = s2 + decltype(it)::value;  // I2 = K + s >= K2
           mf_mma2<mf_tid(K + s, K + s2)>(na, Pm[s][m]);
         });
@@ -157,12 +157,12 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
   // readfirstlane: loaded values are vector registers to hipcc, and a dozen uniform constants held in vector registers
   // through every phase are a dozen registers the assembly loop then spills its operands for.)
   auto uni = [](const float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); };
-  const int ex = rfl(mf_scale_exp(fmaxf(__uint_as_float(a.wave_stats[0]), 1e-30f)));
+  const int ex = rfl(fp16_scale_exp(fmaxf(__uint_as_float(a.wave_stats[0]), 1e-30f)));
   const float wmax = uni(IMPLICIT ? fmaxf(__uint_as_float(a.wave_stats[1]) - 1.f, 1.f) : 1.f);
   const int ewb = rfl((int)((__float_as_uint(wmax) >> 23) & 0xffu));
-  const float sx = uni(mf_pow2(ex)), sw = uni(mf_pow2(min(253, max(1, 253 - ewb))));   // sw = 2^(126 - ewb) <= 1 / wmax
-  const float un1 = uni(mf_pow2(254 - ex));                                             // 1 / sx
-  const float unw = uni(IMPLICIT ? mf_pow2(254 - min(253, max(1, 253 - ewb))) : 1.f);   // 1 / sw
+  const float sx = uni(pow2(ex)), sw = uni(pow2(min(253, max(1, 253 - ewb))));   // sw = 2^(126 - ewb) <= 1 / wmax
+  const float un1 = uni(pow2(254 - ex));                                             // 1 / sx
+  const float unw = uni(IMPLICIT ? pow2(254 - min(253, max(1, 253 - ewb))) : 1.f);   // 1 / sw
 
   for (int it = blockIdx.x; it < n_rows; it += gridDim.x) {
     const int row = rfl(rows[it]);
@@ -179,7 +179,7 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
 
     // ---------------- assembly on the matrix cores ----------------
     MF_DRAIN();   // (the previous row's last matrix instructions)
-    mf_sfor<160>([&](auto rt) { mf_wr<decltype(rt)::value>(0.f); });
+    static_for<160>([&](auto rt) { mf_wr<decltype(rt)::value>(0.f); });
     float u0 = 0.f, u1 = 0.f;   // rhs, lane = coordinate (ln, 64 + ln)
     {
       // A step = 16 non-zeros.  Its vectors are requested at the top of the loop body (asm loads: one coordinate per lane
@@ -205,11 +205,11 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
         }
         if constexpr (SYM) {
           // three products of order < 2, product-outermost: consecutive instructions go to different tiles
-          mf_sfor<3>([&](auto pt) {
+          static_for<3>([&](auto pt) {
             constexpr int pr = decltype(pt)::value;
-            mf_sfor<4>([&](auto kt) {
+            static_for<4>([&](auto kt) {
               constexpr int K = decltype(kt)::value;
-              mf_sfor<4 - K>([&](auto st) {
+              static_for<4 - K>([&](auto st) {
                 constexpr int I = K + decltype(st)::value;
                 mf_mma16<mf_tid(I, K)>(pr == 2 ? bl[K] : bh[K], pr == 1 ? bl[I] : bh[I]);
               });
@@ -217,12 +217,12 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
           });
         } else {
           // the A side (2^e' (c - 1) 2^e x) one block column at a time
-          mf_sfor<4>([&](auto kt) {
+          static_for<4>([&](auto kt) {
             constexpr int K = decltype(kt)::value;
             const f16x8 ah = fetch_op(8 + K), al = fetch_op(12 + K);
-            mf_sfor<3>([&](auto pt) {
+            static_for<3>([&](auto pt) {
               constexpr int pr = decltype(pt)::value;
-              mf_sfor<4 - K>([&](auto st) {
+              static_for<4 - K>([&](auto st) {
                 constexpr int I = K + decltype(st)::value;
                 mf_mma16<mf_tid(I, K)>(pr == 2 ? al : ah, pr == 1 ? bl[I] : bh[I]);
               });
@@ -316,9 +316,9 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
     // selected load is sunk under its condition, one round trip per entry)
     const float unscale = (un1 * un1) * unw;   // (powers of two: exact)
     MF_DRAIN();
-    mf_sfor<4>([&](auto it2) {
+    static_for<4>([&](auto it2) {
       constexpr int I = decltype(it2)::value;
-      mf_sfor<I + 1>([&](auto kt) {
+      static_for<I + 1>([&](auto kt) {
         constexpr int K = decltype(kt)::value;
         constexpr int T = mf_tid(I, K);
         float gv[16];
@@ -331,7 +331,7 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
 #pragma unroll
           for (int v = 0; v < 16; v++) gv[v] = (I == K && n == 8 * (v >> 2) + 4 * hf + (v & 3)) ? dg : 0.f;
         }
-        mf_sfor<16>([&](auto vt) {
+        static_for<16>([&](auto vt) {
           constexpr int v = decltype(vt)::value;
           mf_wr<16 * T + v>(fmaf(mf_rd<16 * T + v>(), unscale, gv[v]));
         });

@@ -24,41 +24,6 @@ namespace {
 
 using namespace dev;
 
-template <class F, int... I>
-__device__ __forceinline__ void cw_sfor_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void cw_sfor(F&& f) {
-  cw_sfor_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// x (already scaled into fp16's range) -> fl16(x), fl16(x - fl16(x)) for a pair; the residual is exact in fp32
-__device__ __forceinline__ void cw_split(const float x0, const float x1, unsigned& hi, unsigned& lo) {
-  const f32x2 v = {x0, x1};
-  const f16x2 h = __builtin_convertvector(v, f16x2);
-  const f32x2 r = v - __builtin_convertvector(h, f32x2);
-  const f16x2 l = __builtin_convertvector(r, f16x2);
-  hi = __builtin_bit_cast(unsigned, h);
-  lo = __builtin_bit_cast(unsigned, l);
-}
-__device__ __forceinline__ f16x8 cw_pack(const unsigned a, const unsigned b, const unsigned c, const unsigned d) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 v = {a, b, c, d};
-  return __builtin_bit_cast(f16x8, v);
-}
-// biased exponent e of the power of two that brings `vmax` into [2^13, 2^14); 2^(e - 127) is the scale
-__device__ __forceinline__ int cw_scale_exp(float vmax) {
-  const int eb = (int)((__float_as_uint(vmax) >> 23) & 0xffu);
-  return min(253, max(1, 267 - eb));
-}
-__device__ __forceinline__ float cw_pow2(int biased) { return __uint_as_float((unsigned)biased << 23); }
-
 template <int KP, bool IMPLICIT>
 __global__ __launch_bounds__(64, 3) void als_chol_wave_kernel(AlsArgs a, int loss_slot0) {
   // (one wave per WORKGROUP: with four, a workgroup held its slot until the longest of its four rows was done)
@@ -112,10 +77,10 @@ __global__ __launch_bounds__(64, 3) void als_chol_wave_kernel(AlsArgs a, int los
         // wrmf_ne.hip); the accumulator tiles (lane: column, registers: rows) are, the matrix being symmetric, rows spread over
         // the lane pair (n, n + 32): one lane swap per register pair hands every lane its row (as in wrmf_chol_lr.hip).
         // 64 FMAs + 16 LDS reads per non-zero become ~ 15 instructions.
-        const int ex = cw_scale_exp(fmaxf(__uint_as_float(a.wave_stats[0]), 1e-30f));
+        const int ex = fp16_scale_exp(fmaxf(__uint_as_float(a.wave_stats[0]), 1e-30f));
         const float wmax = IMPLICIT ? fmaxf(__uint_as_float(a.wave_stats[1]) - 1.f, 1.f) : 1.f;
         const int ewb = (int)((__float_as_uint(wmax) >> 23) & 0xffu);   // 2^(127 - ewb - 1 + 127...) below: |w| 2^-(ewb - 126) <= 1
-        const float sx = cw_pow2(ex), sw = cw_pow2(min(253, max(1, 253 - ewb)));   // sw = 2^(126 - ewb) <= 1 / wmax
+        const float sx = pow2(ex), sw = pow2(min(253, max(1, 253 - ewb)));   // sw = 2^(126 - ewb) <= 1 / wmax
         f32x16 t[2][2];
 #pragma unroll
         for (int e = 0; e < 16; e++) t[0][0][e] = t[0][1][e] = t[1][0][e] = t[1][1][e] = 0.f;
@@ -164,11 +129,11 @@ __global__ __launch_bounds__(64, 3) void als_chol_wave_kernel(AlsArgs a, int los
             }
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-              cw_split(b0[2 * q], b0[2 * q + 1], h0[q], l0[q]);
-              cw_split(b1[2 * q], b1[2 * q + 1], h1[q], l1[q]);
+              split_f16(b0[2 * q], b0[2 * q + 1], h0[q], l0[q]);
+              split_f16(b1[2 * q], b1[2 * q + 1], h1[q], l1[q]);
             }
-            bh[0] = cw_pack(h0[0], h0[1], h0[2], h0[3]); bl[0] = cw_pack(l0[0], l0[1], l0[2], l0[3]);
-            bh[1] = cw_pack(h1[0], h1[1], h1[2], h1[3]); bl[1] = cw_pack(l1[0], l1[1], l1[2], l1[3]);
+            bh[0] = pack_f16x8(h0[0], h0[1], h0[2], h0[3]); bl[0] = pack_f16x8(l0[0], l0[1], l0[2], l0[3]);
+            bh[1] = pack_f16x8(h1[0], h1[1], h1[2], h1[3]); bl[1] = pack_f16x8(l1[0], l1[1], l1[2], l1[3]);
             if constexpr (IMPLICIT) {
 #pragma unroll
               for (int e = 0; e < 8; e++) {
@@ -178,11 +143,11 @@ __global__ __launch_bounds__(64, 3) void als_chol_wave_kernel(AlsArgs a, int los
               }
 #pragma unroll
               for (int q = 0; q < 4; q++) {
-                cw_split(b0[2 * q], b0[2 * q + 1], h0[q], l0[q]);
-                cw_split(b1[2 * q], b1[2 * q + 1], h1[q], l1[q]);
+                split_f16(b0[2 * q], b0[2 * q + 1], h0[q], l0[q]);
+                split_f16(b1[2 * q], b1[2 * q + 1], h1[q], l1[q]);
               }
-              ah[0] = cw_pack(h0[0], h0[1], h0[2], h0[3]); al[0] = cw_pack(l0[0], l0[1], l0[2], l0[3]);
-              ah[1] = cw_pack(h1[0], h1[1], h1[2], h1[3]); al[1] = cw_pack(l1[0], l1[1], l1[2], l1[3]);
+              ah[0] = pack_f16x8(h0[0], h0[1], h0[2], h0[3]); al[0] = pack_f16x8(l0[0], l0[1], l0[2], l0[3]);
+              ah[1] = pack_f16x8(h1[0], h1[1], h1[2], h1[3]); al[1] = pack_f16x8(l1[0], l1[1], l1[2], l1[3]);
             } else {
               ah[0] = bh[0]; al[0] = bl[0]; ah[1] = bh[1]; al[1] = bl[1];
             }
@@ -200,8 +165,8 @@ __global__ __launch_bounds__(64, 3) void als_chol_wave_kernel(AlsArgs a, int los
           idj = idn; cvj = cvn; rcj = rcn; ccnt = cnn;
         }
         // rows: tile (a, b) at lane (n, hf), register v = lhs[32 a + rho(v, hf)][32 b + n] = row 32 b + n, column 32 a + rho(v, hf)
-        const float un1 = cw_pow2(254 - ex), un2 = IMPLICIT ? un1 * (wmax >= 1.f ? 1.f : 1.f) : un1;
-        const float unw = IMPLICIT ? cw_pow2(254 - min(253, max(1, 253 - ewb))) : 1.f;   // 1 / sw
+        const float un1 = pow2(254 - ex), un2 = IMPLICIT ? un1 * (wmax >= 1.f ? 1.f : 1.f) : un1;
+        const float unw = IMPLICIT ? pow2(254 - min(253, max(1, 253 - ewb))) : 1.f;   // 1 / sw
         (void)un2;
 #pragma unroll
         for (int ta = 0; ta < 2; ta++)
@@ -291,7 +256,7 @@ __global__ __launch_bounds__(64, 3) void als_chol_wave_kernel(AlsArgs a, int los
     bool bad = false;
     float dinv = 1.f;
     float pj = readlane_f(r[0], 0);
-    cw_sfor<KP>([&](auto jt) {
+    static_for<KP>([&](auto jt) {
       constexpr int j = decltype(jt)::value;
       bad = bad || !(pj > 0.f);
       const float i0 = __builtin_amdgcn_rcpf(pj);
@@ -308,7 +273,7 @@ __global__ __launch_bounds__(64, 3) void als_chol_wave_kernel(AlsArgs a, int los
           dpp_ready(r[j]);
           rows_to_all<(KP > 32 ? 4 : 2)>(r[j], rep);
           dpp_ready(rep[0], rep[1], rep[2], rep[3]);
-          cw_sfor<KP - j - 2>([&](auto ct) {
+          static_for<KP - j - 2>([&](auto ct) {
             constexpr int c = j + 2 + decltype(ct)::value;
             fnma_row_bcast<c % 16>(r[c], rep[c / 16], lij);
           });

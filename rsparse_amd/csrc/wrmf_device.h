@@ -16,79 +16,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "wrmf_internal.h"
+#include "wrmf_wave.h"
+
 namespace rsparse_hip {
 namespace dev {
-
-__device__ __forceinline__ void wave_sync() {
-  // LDS traffic of one wave is executed in order; this only pins the compiler's ordering.
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ float readlane_f(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(reinterpret_cast<uintptr_t>(p));  // low 32 bits of a generic LDS pointer = LDS byte address
-}
-// LDS-DMA, one dword per lane: LDS destination = M0 + lane * 4 (wave-uniform base), source = each lane's own pointer.  Counts in
-// vmcnt like a load; the compiler does not know about it, which is harmless as long as nothing is issued between it and
-// the explicit wait that precedes the first read of its destination (older operations complete first)
-__device__ __forceinline__ void dma4(const void* g, unsigned lds_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" : : "v"(g), "s"(lds_base) : "memory", "m0");
-}
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-
-// acc -= u(lane E of the row of 16 lanes this lane sits in) * l: v_fmac_f32 with a DPP row broadcast on its first operand.
-// 4.8 cycles per wave against 8.4 + 4.3 for v_readlane + v_fma (tools/probes/valu_rate_probe.hip).  Needs EXEC = all ones.
-template <int E>
-__device__ __forceinline__ void fnma_row_bcast(float& acc, const float u, const float l) {
-  asm("v_fmac_f32_dpp %0, -%1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(u), "v"(l), "n"(E));
-}
-// A register that a DPP operand (or a lane swap) is about to read must not have been written by the one or two vector
-// instructions before it (2 wait states).  hipcc inserts them between instructions it knows; it does not look inside inline
-// asm, neither as the writer nor as the reader -- these tie an s_nop to the registers (the asm "rewrites" them, so the real
-// writers stay in front of it and the readers behind).
-__device__ __forceinline__ void dpp_ready(float& a) { asm("s_nop 1" : "+v"(a)); }
-__device__ __forceinline__ void dpp_ready(float& a, float& b) { asm("s_nop 1" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ void dpp_ready(float& a, float& b, float& c, float& d) {
-  asm("s_nop 1" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
-}
-// rep[g] = row g (lanes 16 g .. 16 g + 15) of v in every row of 16 lanes, g < NG (two or three lane-swap instructions)
-template <int NG>
-__device__ __forceinline__ void rows_to_all(const float v, float (&rep)[4]) {
-  const unsigned u = __float_as_uint(v);
-  const auto h = __builtin_amdgcn_permlane32_swap(u, u, false, false);   // h[0] = rows (0, 1, 0, 1), h[1] = rows (2, 3, 2, 3)
-  const auto lo = __builtin_amdgcn_permlane16_swap(h[0], h[0], false, false);   // rows (0, 0, 0, 0), (1, 1, 1, 1)
-  rep[0] = __uint_as_float(lo[0]);
-  rep[1] = __uint_as_float(lo[1]);
-  if constexpr (NG > 2) {
-    const auto hi = __builtin_amdgcn_permlane16_swap(h[1], h[1], false, false);
-    rep[2] = __uint_as_float(hi[0]);
-    rep[3] = __uint_as_float(hi[1]);
-  } else {
-    rep[2] = rep[3] = 0.f;
-  }
-}
-
-// Sum over the 64 lanes, result uniform.  Needs EXEC = all ones.  Fixed order -> deterministic.
-__device__ __forceinline__ float wave_sum(float v) {
-  v += dpp<0xB1>(v);   // quad_perm:[1,0,3,2]
-  v += dpp<0x4E>(v);   // quad_perm:[2,3,0,1]
-  v += dpp<0x141>(v);  // row_half_mirror
-  v += dpp<0x140>(v);  // row_mirror  -> every lane of a 16-lane row holds the row sum
-  const float s0 = readlane_f(v, 0), s1 = readlane_f(v, 16);
-  const float s2 = readlane_f(v, 32), s3 = readlane_f(v, 48);
-  return (s0 + s1) + (s2 + s3);
-}
 
 template <int KP>
 struct Geo {
@@ -221,6 +153,85 @@ __device__ __forceinline__ void gather_chunk(const float* __restrict__ X, int k,
       for (int e = lane; e < k; e += 64) tile[j * LDT + e] = src[e];
     }
   }
+}
+
+// The four waves of a workgroup gather one chunk of TC factor vectors of a row (non-zeros base .. base + ccnt - 1) into the tile
+// sT, row stride KP + 4: wave wv fetches tile rows [TC/4 wv, TC/4 wv + TC/4).  VEC: all index loads, then all 16-byte vector loads
+// of the wave are in flight together (2 dependent round trips per chunk).
+template <int KP, bool VEC, int TC>
+__device__ __forceinline__ void gather_chunk4(const AlsArgs& a, int base, int ccnt, float* sT, int wv, int lane) {
+  constexpr int LDT = KP + 4, TCW = TC / 4;   // (TCW vectors of the chunk per wave)
+  const int k = a.k;
+  if constexpr (VEC) {
+    constexpr int LPV = KP / 4, VPI = 64 / LPV, NQ = TCW / VPI;
+    static_assert(NQ >= 1, "a wave's share of the chunk is at least one load instruction");
+    const int c4 = lane % LPV, jo = lane / LPV;
+    int ids[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) ids[q] = a.row_idx[base + min(TCW * wv + q * VPI + jo, ccnt - 1)];
+    float4 v[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) v[q] = *reinterpret_cast<const float4*>(a.X + (size_t)ids[q] * k + min(c4 * 4, k - 4));
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+      const int j = TCW * wv + q * VPI + jo;
+      if (j < ccnt && c4 * 4 < k) *reinterpret_cast<float4*>(sT + j * LDT + c4 * 4) = v[q];
+    }
+  } else {
+    for (int j = TCW * wv; j < min(TCW * wv + TCW, ccnt); j++) {
+      const int id = rfl(a.row_idx[base + j]);
+      const float* src = a.X + (size_t)id * k;
+      for (int e = lane; e < k; e += 64) sT[j * LDT + e] = src[e];
+    }
+  }
+}
+
+// The kth largest of the keys key(e, ok) (e < n; ok = false leaves the entry out) by a radix select on `nbits` bits, 8 per pass.
+// A workgroup of 256 threads, all of which must call it.  Needs 1 <= kth <= the number of valid entries.  hist: 256 words,
+// sres / srem: one each.  Integer arithmetic throughout: the result does not depend on the order of the atomics.
+template <class KeyFn>
+__device__ u64 block_kth_largest(int n, int kth, int nbits, KeyFn key, unsigned* hist, u64* sres, int* srem) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  u64 prefix = 0;
+  int rem = kth;
+  for (int shift = nbits - 8; shift >= 0; shift -= 8) {
+    hist[tid] = 0u;
+    __syncthreads();
+    const u64 hmask = shift + 8 >= 64 ? 0ull : (~0ull << (shift + 8));
+    for (int e = tid; e < n; e += 256) {
+      bool ok;
+      const u64 k = key(e, ok);
+      if (ok && (k & hmask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid < 64) {   // bins from the top: lane l holds bins 255 - 4l .. 252 - 4l
+      unsigned s = 0;
+      for (int j = 0; j < 4; j++) s += hist[255 - 4 * lane - j];
+      unsigned incl = s;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned t = __shfl_up(incl, o);
+        if (lane >= o) incl += t;
+      }
+      const unsigned excl = incl - s;
+      if (excl < (unsigned)rem && incl >= (unsigned)rem) {
+        unsigned cum = excl;
+        for (int j = 0; j < 4; j++) {
+          const int b = 255 - 4 * lane - j;
+          if (cum + hist[b] >= (unsigned)rem) {
+            *sres = prefix | ((u64)b << shift);
+            *srem = rem - (int)cum;
+            break;
+          }
+          cum += hist[b];
+        }
+      }
+    }
+    __syncthreads();
+    prefix = *sres;
+    rem = *srem;
+  }
+  return prefix;
 }
 
 }  // namespace dev

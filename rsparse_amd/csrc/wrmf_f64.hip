@@ -34,44 +34,25 @@
 // matrix).  Everything else goes through the workgroup-per-row family.
 #include <algorithm>
 
-#include <type_traits>
-#include <utility>
-
 #include "wrmf_f64.h"
 #include "wrmf_internal.h"
+#include "wrmf_device.h"
 
 namespace rsparse_hip {
 namespace {
 
-constexpr double kCgTolD = 1e-10;        // CG_TOL, inst/include/wrmf.hpp:22
-template <class F, int... I>
-__device__ __forceinline__ void static_for_f64_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for_f64(F&& f) {
-  static_for_f64_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-constexpr unsigned kScdMaxIter = 10000;  // SCD_MAX_ITER, wrmf.hpp:20
-constexpr double kScdTol = 1e-4;         // SCD_TOL, wrmf.hpp:21
-constexpr double kNnlsEps = 1e-16;       // EPS, nnls.hpp:8
-
-__device__ __forceinline__ double wave_sum_d(double v) {   // butterfly: every lane ends with the same bits
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
+using namespace dev;
 
 // v of lane `src` (wave-uniform) in every lane
 __device__ __forceinline__ double f64_readlane_uniform(const double v, const int src) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
 }
 
-// sum over the workgroup, every thread gets it; all threads must call it.  red: NT / 64 doubles
+// sum over the workgroup, every thread gets it; all threads must call it.  red: NT / 64 doubles.  The waves' partials are
+// added in wave order onto 0.0 (wrmf_wide.hip and wrmf_metrics.hip pair theirs differently: each keeps its own block_sum)
 template <int NT>
 __device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum_d(v);
+  v = butterfly_sum(v);
   __syncthreads();   // red may still be read from the previous call
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -79,14 +60,6 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 #pragma unroll
   for (int w = 0; w < NT / 64; w++) s += red[w];
   return s;
-}
-
-// t-th 4 x 4 tile of the lower triangle, row-major over the tile rows: (ti, tj), tj <= ti
-__device__ __forceinline__ void tile_of(int t, int& ti, int& tj) {
-  ti = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
-  while ((ti + 1) * (ti + 2) / 2 <= t) ti++;
-  while (ti * (ti + 1) / 2 > t) ti--;
-  tj = t - ti * (ti + 1) / 2;
 }
 
 // A[(4 ti + r) + (4 tj + c) lda] += sum_{j < cn} xs[j][4 ti + r] * w[j] * xs[j][4 tj + c] over the tiles of the lower triangle
@@ -121,8 +94,6 @@ __device__ __forceinline__ void rank_update_tiles(double* A, int lda, const doub
       for (int r = 0; r < 4; r++) A[(4 * ti + r) + (size_t)(4 * tj + c) * lda] += acc[r][c];
   }
 }
-
-using f64x4 = __attribute__((ext_vector_type(4))) double;
 
 // The same update on the matrix cores: 16 x 16 tiles of the lower triangle (the whole diagonal tiles: their upper halves come out
 // as the mirror image), one tile per wave and trip, four non-zeros per v_mfma_f64_16x16x4_f64 -- lane l hands over A[l & 15][l >> 4]
@@ -385,7 +356,7 @@ __global__ __launch_bounds__(NT, 2) void f64_als_kernel(F64Args a, int KP, int C
 #pragma unroll
           for (int rr = 0; rr < 4; rr++) {
             const int gi = 4 * ti + rr, gc = 4 * tj + c;
-            const double v = acc[rr][c] + (gi == gc ? kNnlsEps : 0.0);
+            const double v = acc[rr][c] + (gi == gc ? kNnlsEpsD : 0.0);
             M2[gi + (size_t)gc * LDA] = v;
             M2[gc + (size_t)gi * LDA] = v;
           }
@@ -428,7 +399,7 @@ __global__ __launch_bounds__(NT, 2) void f64_als_kernel(F64Args a, int KP, int C
                 const double* col = M2 + (size_t)c * LDA;
                 if (own0) mu0 += diff * col[lane];
                 if (own1) mu1 += diff * col[lane + 64];
-                const double se = fabs(diff) / (fabs(old) + kNnlsEps);
+                const double se = fabs(diff) / (fabs(old) + kNnlsEpsD);
                 if (se > rel) rel = se;
                 act = __ballot(!((hi ? h1 : h0) == 0.0 && (hi ? mu1 : mu0) >= 0.0)) & in_range & above;
               } else {
@@ -436,7 +407,7 @@ __global__ __launch_bounds__(NT, 2) void f64_als_kernel(F64Args a, int KP, int C
               }
             }
           }
-          if (rel <= kScdTol) break;
+          if (rel <= kScdTolD) break;
         }
         if (own0) x[lane] = h0;
         if (own1) x[lane + 64] = h1;
@@ -708,7 +679,7 @@ __global__ __launch_bounds__(NT, 2) void f64_als_kernel(F64Args a, int KP, int C
         for (int u = 0; u < 4; u++) {
           double sd = lane < k1 ? v[u][0] * x0 : 0.0;
           sd = lane + 64 < k1 ? fma(v[u][1], x1, sd) : sd;
-          sd = wave_sum_d(sd);
+          sd = butterfly_sum(sd);
           const double lwj = a.implicit ? cj[u] : 1.0;                                    // (as `stage` forms them)
           const double ltj = a.implicit ? (1.0 - a.gbias) - xbj[u] : cj[u] - xbj[u];   // wrmf_implicit.hpp:259-270, wrmf_explicit.hpp:131
           const double dlt = ltj - sd;
@@ -795,7 +766,7 @@ __device__ __forceinline__ int f64_from_step_lane(const int v, const int g) {
 // the rows of 16 lanes with a select and one DPP move.  15 additions and 15 exchanges per lane for 16 sums, where sixteen
 // butterflies (f64_group_sum) take 96 of each -- the lane-crossing sum of a non-zero's dot product was most of the fp64
 // conjugate-gradient kernel's instructions at rank 65..128 (round 5).
-__device__ __forceinline__ double f64_transposed_sum16(double (&p)[16], const int lane) {
+__device__ __forceinline__ double transposed_sum16(double (&p)[16], const int lane) {
   auto swap32 = [](const double a, const double b) {
     const auto sl = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
     const auto sh = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
@@ -854,7 +825,7 @@ __device__ __forceinline__ F64Vec<EPL> f64_row_pass(const F64Args& a, const int 
   auto fetch = [&](auto bt, const int idj, const int nst, double (&dst)[BS][EPL]) {
     constexpr int B = decltype(bt)::value;
     if (B * BS < nst) {   // wave-uniform
-      static_for_f64<BS>([&](auto ut) {
+      static_for<BS>([&](auto ut) {
         constexpr int U = decltype(ut)::value, ST = B * BS + U;
         const int id = f64_from_step_lane<W, ST>(idj, g);   // (steps beyond the chunk repeat its last non-zero: weight 0)
 #pragma unroll
@@ -872,7 +843,7 @@ __device__ __forceinline__ F64Vec<EPL> f64_row_pass(const F64Args& a, const int 
     const int nst = (cn + NPS - 1) / NPS;                                       // steps of this chunk (<= W)
     const int nst1 = c0 + 64 < n ? (min(64, n - c0 - 64) + NPS - 1) / NPS : 0;   // ... of the next one
     meta(c0 + 128, id2, c2l, c2h);
-    static_for_f64<NBATCH>([&](auto bt) {
+    static_for<NBATCH>([&](auto bt) {
       constexpr int B = decltype(bt)::value;
       if (B * BS < nst) {   // wave-uniform
         // the batch after this one: of this chunk, or the first of the next chunk
@@ -887,13 +858,13 @@ __device__ __forceinline__ F64Vec<EPL> f64_row_pass(const F64Args& a, const int 
           // the sum over the vectors.  (Ranks 33..64 kept the per-non-zero butterfly -- six fp64 exchange stages each --
           // until the end of round 5, and a rank-64 fit took as long as a rank-128 one: profiles/r05/r5z_f64_per_iteration.txt.)
           double part[BS];
-          static_for_f64<BS>([&](auto ut) {
+          static_for<BS>([&](auto ut) {
             constexpr int U = decltype(ut)::value;
             part[U] = (lk[0] ? cur[U][0] : 0.0) * v.c[0];
 #pragma unroll
             for (int e = 1; e < EPL; e++) part[U] = fma(lk[e] ? cur[U][e] : 0.0, v.c[e], part[U]);
           });
-          const double t = f64_transposed_sum16(part, lane);
+          const double t = transposed_sum16(part, lane);
           const int st = B * BS + (lane >> 2);                        // the lane's non-zero of the chunk
           const double c = __hiloint2double(__shfl(c0h, st), __shfl(c0l, st));
           const bool in = st < cn;
@@ -906,7 +877,7 @@ __device__ __forceinline__ F64Vec<EPL> f64_row_pass(const F64Args& a, const int 
             else coef = IMPLICIT ? (c - 1.0) * t : t;
             coef = in ? coef : 0.0;
             const int ch = __double2hiint(coef), cl = __double2loint(coef);
-            static_for_f64<BS>([&](auto ut) {
+            static_for<BS>([&](auto ut) {
               constexpr int U = decltype(ut)::value, ST = B * BS + U;
               if (ST < nst) {   // wave-uniform
                 const double cu = __hiloint2double(__builtin_amdgcn_readlane(ch, 4 * U), __builtin_amdgcn_readlane(cl, 4 * U));
@@ -916,7 +887,7 @@ __device__ __forceinline__ F64Vec<EPL> f64_row_pass(const F64Args& a, const int 
             });
           }
         } else
-        static_for_f64<BS>([&](auto ut) {
+        static_for<BS>([&](auto ut) {
           constexpr int U = decltype(ut)::value, ST = B * BS + U;
           if (ST < nst) {   // wave-uniform
             double yv[EPL];
@@ -1021,7 +992,7 @@ __global__ __launch_bounds__(256, EPL == 2 ? 2 : 1) void f64_cg_wave_kernel(F64A
         gv[e] = sG[at];
       }
     };
-    static_for_f64<EPL>([&](auto e2t) {
+    static_for<EPL>([&](auto e2t) {
       constexpr int E2 = decltype(e2t)::value;
       const int lim = min(64, k - 64 * E2);
       int m = 0;
@@ -1421,7 +1392,7 @@ __global__ __launch_bounds__(256) void f64_weighted_sumsq_kernel(const double* _
     }
     s += (w ? w[j] : 1.0) * q;
   }
-  s = wave_sum_d(s);
+  s = butterfly_sum(s);
   if (lane == 0) partials[wave] = s;
 }
 

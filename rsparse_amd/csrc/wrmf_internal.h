@@ -9,6 +9,15 @@
 
 namespace rsparse_hip {
 
+// Constants of the reference (inst/include/wrmf.hpp:20-22, inst/include/nnls.hpp:8), once per type
+constexpr float kCgTol = 1e-10f;      // CG_TOL: the conjugate-gradient exit on the squared residual
+constexpr double kCgTolD = 1e-10;
+constexpr int kScdMaxIter = 10000;    // SCD_MAX_ITER: sweeps of the coordinate descent (NNLS)
+constexpr float kScdTol = 1e-4f;      // SCD_TOL: its exit on the largest relative coordinate change of a sweep
+constexpr double kScdTolD = 1e-4;
+constexpr float kNnlsEps = 1e-16f;    // EPS: added to the diagonal of XtX and to the denominators
+constexpr double kNnlsEpsD = 1e-16;
+
 // One list set of the normal-equation launch (wrmf_ne.hip), on the device: the rows of a prefix of the order dealt to `wg`
 // workgroups, longest processing time first -- workgroup b owns rows[ptr[b], ptr[b + 1]); an entry >= 0 is a row, -(s + 1)
 // segment s of the rows that are split across workgroups (planned by wrmf_schedule.cpp: NeCut / NeDeal).  A view: the

@@ -27,8 +27,6 @@ namespace {
 
 using namespace dev;
 
-constexpr float kCgTol = 1e-10f;  // CG_TOL, inst/include/wrmf.hpp:22
-
 template <int KP, int T, int W, bool IMPLICIT>
 struct CgSmem {
   static constexpr int LDT = Geo<KP>::LDT;
@@ -366,7 +364,6 @@ __global__ __launch_bounds__(W * 64) void als_cg_long_kernel(AlsArgs a, size_t l
 // Gramian  G = X X^T (+ ridge I),  X is k x n column-major: fp32 MFMA 32x32x2, lower-triangular
 // 32x32 tiles only, one partial per wave, deterministic two-stage reduction.
 // ------------------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <int KP>
 __global__ __launch_bounds__(256, 2) void gramian_partial_kernel(const float* __restrict__ X, int k, int64_t n,

@@ -49,15 +49,6 @@ struct Ldlt {
   __host__ __device__ static constexpr int hd(int s) { return (4 * s) / BPH; }
   __host__ __device__ static constexpr int nh(int s) { return RH - hd(s); }
 
-  template <class F, int... I>
-  static __device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-  }
-  template <int N, class F>
-  static __device__ __forceinline__ void sfor(F&& f) {
-    sfor_impl(f, std::make_integer_sequence<int, N>{});
-  }
-
   template <int E>
   static __device__ __forceinline__ void fnma_bcast(float& acc, const float u, const float l) { fnma_row_bcast<E>(acc, u, l); }
   static __device__ __forceinline__ float swap32_add(float a, float b) {   // lanes < 32: sum of a's halves, >= 32: of b's
@@ -67,13 +58,6 @@ struct Ldlt {
   static __device__ __forceinline__ float swap16_add(float a, float b) {   // rows 0, 2: a's rows 0+1, 2+3; rows 1, 3: b's
     const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-  static __device__ __forceinline__ float row_sum(float v) {   // sum over each row of 16 lanes, in all of its lanes
-    v += dpp<0xB1>(v);
-    v += dpp<0x4E>(v);
-    v += dpp<0x141>(v);
-    v += dpp<0x140>(v);
-    return v;
   }
 
   // Flags in LDS between the waves.  The LDS executes one wave's instructions in order, so a flag written after the data
@@ -112,7 +96,7 @@ struct Ldlt {
       l[0] = lane > jl0 ? col[0][0] * inv : 0.f;
       if constexpr (NH == 2) l[1] = col[0][1] * inv;
     }
-    sfor<BC>([&](auto cct) {
+    static_for<BC>([&](auto cct) {
       constexpr int cc = decltype(cct)::value;
       const int jl = jl0 + cc;
       auto upd = [&](const int c2) {   // rank-1 update of column c2 by column cc
@@ -189,7 +173,7 @@ struct Ldlt {
     // (consecutive FMAs go to different accumulators: a dependent one would wait for its predecessor's result)
 #pragma unroll
     for (int e = 0; e < 4; e++)
-      sfor<BC>([&](auto ct) {
+      static_for<BC>([&](auto ct) {
         constexpr int c2 = decltype(ct)::value;
 #pragma unroll
         for (int x = 0; x < NH; x++) fnma_bcast<c2>(col[c2][x], ue[e], lv[e][x]);
@@ -222,7 +206,7 @@ struct Ldlt {
 #pragma unroll
       for (int i = 0; i < 4; i++) q4[i] = swap32_add(p[2 * i], p[2 * i + 1]);       // lanes < 32: column 2 i, else 2 i + 1
 #pragma unroll
-      for (int m = 0; m < 2; m++) r2[m] = row_sum(swap16_add(q4[2 * m], q4[2 * m + 1]));   // rows: columns 4m, 4m+2, 4m+1, 4m+3
+      for (int m = 0; m < 2; m++) r2[m] = row16_sum(swap16_add(q4[2 * m], q4[2 * m + 1]));   // rows: columns 4m, 4m+2, 4m+1, 4m+3
       t -= (lane & 4) ? r2[1] : r2[0];
     }
     const float* dg = sCh + 2 * PS_FLOATS + J * BC * BC + cl;
@@ -244,7 +228,7 @@ struct Ldlt {
   static __device__ __forceinline__ bool solve(const float* sA, float* sCh, float* sU, int* sFlag, const int wv,
                                                const int lane) {
     float c[NOWN][BC][RH];
-    sfor<NOWN>([&](auto st) {
+    static_for<NOWN>([&](auto st) {
       constexpr int s = decltype(st)::value;
       const int c0 = BC * blk(wv, s);   // first column of the block
       const int C = c0 >> 5, cin = c0 & 31;
@@ -267,7 +251,7 @@ struct Ldlt {
     bool bad = false;
     int deferred = -1;   // panel this wave has applied to its next block only
     auto apply = [&](const int P, const int above) {   // panel P -> this wave's blocks beyond block `above`
-      sfor<NOWN>([&](auto st) {
+      static_for<NOWN>([&](auto st) {
         constexpr int s = decltype(st)::value;
         const int Js = blk(wv, s);
         if (Js > above) {
@@ -284,7 +268,7 @@ struct Ldlt {
           for (int w2 = 0; w2 < 4; w2++) lds_wait_ge(sDone + w2, J - NBUF + 1);
         }
         __builtin_amdgcn_s_setprio(3);
-        sfor<NOWN>([&](auto st) {
+        static_for<NOWN>([&](auto st) {
           constexpr int s = decltype(st)::value;
           if ((J >> 2) == s) factor<nh(s)>(c[s], J, (BC * J) & 63, J % NBUF, sCh, sU, sRdy, bad, lane);
         });
@@ -298,7 +282,7 @@ struct Ldlt {
       if (J + 1 == NBLK) break;
       if (wv == owner(J + 1)) {
         __builtin_amdgcn_s_setprio(3);
-        sfor<NOWN>([&](auto st) {
+        static_for<NOWN>([&](auto st) {
           constexpr int s = decltype(st)::value;
           if (((J + 1) >> 2) == s) {
             lds_wait_ge(sRdy, 2 * J + 1);
@@ -317,7 +301,7 @@ struct Ldlt {
     for (int J = NBLK - 1; J >= 0; J--) {
       if (wv == owner(J)) {
         __builtin_amdgcn_s_setprio(3);
-        sfor<NOWN>([&](auto st) {
+        static_for<NOWN>([&](auto st) {
           constexpr int s = decltype(st)::value;
           if ((J >> 2) == s) back<nh(s)>(c[s], J, sCh, sU, lane);
         });

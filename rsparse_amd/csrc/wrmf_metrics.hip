@@ -26,40 +26,19 @@
 #include <cmath>
 
 #include "wrmf_internal.h"
+#include "wrmf_device.h"
 
 namespace rsparse_hip {
 namespace {
 
-typedef unsigned long long u64;
+using namespace dev;
 
 constexpr int kMetWaves = 4;            // users (waves) per workgroup of launch 1
 constexpr int kMetRowCap = 512;         // rows up to this long: staged in LDS, idcg sorted there (a power of two)
-constexpr int kMetLongThreads = 256;
+constexpr int kMetLongThreads = 256;    // (what block_kth_largest is written for)
 constexpr int kMetLongCap = 8192;       // keys launch 2 sorts in LDS: > the c < kk <= RSPARSE_HIP_MAX_TOPK_LARGE values above
 constexpr int kMetLongGrid = 512;       // workgroups of launch 2 (two per CU: 66 KiB of LDS each)
 constexpr int kNaInteger = INT32_MIN;   // RSPARSE_HIP_NA_INTEGER
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// butterfly: every lane ends with the same value (a + b == b + a), in an order fixed by the lane numbers
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// order-preserving key of a double: larger value <=> larger key (-0.0 just below +0.0)
-__device__ __forceinline__ u64 dkey(double v) {
-  const u64 b = (u64)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | (1ull << 63));
-}
-__device__ __forceinline__ double dval(u64 k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & ~(1ull << 63)) : ~k));
-}
 
 __device__ __forceinline__ double discount(int i) {   // log2(i + 1), the divisor of the 1-based position i
   return log2((double)i + 1.0);
@@ -126,11 +105,11 @@ __global__ __launch_bounds__(64 * kMetWaves) void metrics_rows_kernel(const int3
     if (NDCG && pos >= 0) dcg_acc += rx[pos] / discount(i + 1);
   }
   if (AP) {
-    const double s = wave_sum(ap_acc);
+    const double s = butterfly_sum(ap_acc);
     if (lane == 0) ap_out[u] = s / (double)kk;
   }
   if (!NDCG) return;
-  const double dcg = wave_sum(dcg_acc);
+  const double dcg = butterfly_sum(dcg_acc);
   if (!staged) {   // idcg in launch 2; dcg waits in the output
     if (lane == 0) {
       ndcg_out[u] = dcg;
@@ -173,62 +152,18 @@ __global__ __launch_bounds__(64 * kMetWaves) void metrics_rows_kernel(const int3
       }
     for (int i = lane; i < kk; i += 64) idcg_acc += sx[i] / discount(i + 1);
   }
-  const double idcg = wave_sum(idcg_acc);
+  const double idcg = butterfly_sum(idcg_acc);
   if (lane == 0) ndcg_out[u] = dcg / idcg;
 }
 
-// workgroup (256) sum in a fixed order: per wave, then the waves in order.  red: 4 doubles.
+// workgroup (256) sum in a fixed order: per wave, then the waves in order, ((r0 + r1) + r2) + r3.  red: 4 doubles.
 __device__ __forceinline__ double block_sum(double v, double* red) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  v = wave_sum(v);
+  v = butterfly_sum(v);
   __syncthreads();
   if (lane == 0) red[w] = v;
   __syncthreads();
   return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// kth largest key (1 <= kth <= n) of the n doubles at x, 8 bits per pass.  hist: 256 words.
-__device__ u64 block_kth_key(const double* __restrict__ x, int n, int kth, unsigned* hist, u64* sres, int* srem) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  u64 prefix = 0;
-  int rem = kth;
-  for (int shift = 56; shift >= 0; shift -= 8) {
-    hist[tid] = 0u;
-    __syncthreads();
-    const u64 hmask = shift == 56 ? 0ull : (~0ull << (shift + 8));
-    for (int e = tid; e < n; e += kMetLongThreads) {
-      const u64 kx = dkey(x[e]);
-      if ((kx & hmask) == prefix) atomicAdd(&hist[(kx >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (tid < 64) {   // bins from the top: lane l holds bins 255 - 4l .. 252 - 4l
-      unsigned s = 0;
-      for (int q = 0; q < 4; q++) s += hist[255 - 4 * lane - q];
-      unsigned incl = s;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-      }
-      const unsigned excl = incl - s;
-      if (excl < (unsigned)rem && incl >= (unsigned)rem) {
-        unsigned cum = excl;
-        for (int q = 0; q < 4; q++) {
-          const int b = 255 - 4 * lane - q;
-          if (cum + hist[b] >= (unsigned)rem) {
-            *sres = prefix | ((u64)b << shift);
-            *srem = rem - (int)cum;
-            break;
-          }
-          cum += hist[b];
-        }
-      }
-    }
-    __syncthreads();
-    prefix = *sres;
-    rem = *srem;
-  }
-  return prefix;
 }
 
 __global__ __launch_bounds__(kMetLongThreads) void metrics_long_kernel(int k, const int32_t* __restrict__ P,
@@ -251,7 +186,7 @@ __global__ __launch_bounds__(kMetLongThreads) void metrics_long_kernel(int k, co
     // the kk-th largest: min / max first (an all-equal row needs no select)
     u64 kmin = ~0ull, kmax = 0ull;
     for (int e = tid; e < n_u; e += kMetLongThreads) {
-      const u64 kx = dkey(x[e]);
+      const u64 kx = f64_key(x[e]);
       kmin = min(kmin, kx);
       kmax = max(kmax, kx);
     }
@@ -270,12 +205,12 @@ __global__ __launch_bounds__(kMetLongThreads) void metrics_long_kernel(int k, co
     kmin = min(min(s_key[0], s_key[2]), min(s_key[4], s_key[6]));
     kmax = max(max(s_key[1], s_key[3]), max(s_key[5], s_key[7]));
     __syncthreads();
-    const u64 thr = kmin == kmax ? kmin : block_kth_key(x, n_u, kk, s_hist, &s_res, &s_rem);
+    const u64 thr = kmin == kmax ? kmin : block_kth_largest(n_u, kk, 64, [&](int e, bool& ok) { ok = true; return f64_key(x[e]); }, s_hist, &s_res, &s_rem);
     // the c < kk values strictly above the threshold, sorted descending by key (a total order: the result does not depend on
     // the order the compaction wrote them in)
     if (kmin != kmax) {
       for (int e = tid; e < n_u; e += kMetLongThreads) {
-        const u64 kx = dkey(x[e]);
+        const u64 kx = f64_key(x[e]);
         if (kx > thr) s_key[atomicAdd(&s_cnt, 1)] = kx;
       }
     }
@@ -298,9 +233,9 @@ __global__ __launch_bounds__(kMetLongThreads) void metrics_long_kernel(int k, co
         }
         __syncthreads();
       }
-    const double tv = dval(thr);
+    const double tv = key_f64(thr);
     double acc = 0.0;
-    for (int i = tid; i < kk; i += kMetLongThreads) acc += (i < c ? dval(s_key[i]) : tv) / discount(i + 1);
+    for (int i = tid; i < kk; i += kMetLongThreads) acc += (i < c ? key_f64(s_key[i]) : tv) / discount(i + 1);
     const double idcg = block_sum(acc, s_red);
     if (tid == 0) ndcg_out[u] = ndcg_out[u] / idcg;
     __syncthreads();   // (s_key / s_cnt are reused by the next user)

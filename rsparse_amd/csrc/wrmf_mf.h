@@ -12,21 +12,9 @@
 namespace rsparse_hip {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+using namespace dev;
 
-template <class F, int... I>
-__device__ __forceinline__ void mf_sfor_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void mf_sfor(F&& f) {
-  mf_sfor_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-// x (already scaled into fp16's range) -> fl16(x), fl16(x - fl16(x)) for a pair; the residual is exact in fp32
+// dev::split_f16 with SCALAR subtractions
 __device__ __forceinline__ void mf_split(const float x0, const float x1, unsigned& hi, unsigned& lo) {
   // (scalar subtractions on purpose: a packed fp32 instruction -- v_pk_add_f32 and friends -- issued behind a matrix instruction
   // waits ~28 cycles for it where a plain one is free, tools/probes/mfma_filler_probe.hip; these files are also compiled with
@@ -39,21 +27,9 @@ __device__ __forceinline__ void mf_split(const float x0, const float x1, unsigne
   hi = __builtin_bit_cast(unsigned, h);
   lo = __builtin_bit_cast(unsigned, l);
 }
-__device__ __forceinline__ f16x8 mf_pack(const unsigned a, const unsigned b, const unsigned c, const unsigned d) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 v = {a, b, c, d};
-  return __builtin_bit_cast(f16x8, v);
-}
-// biased exponent e of the power of two that brings `vmax` into [2^13, 2^14); 2^(e - 127) is the scale
-__device__ __forceinline__ int mf_scale_exp(float vmax) {
-  const int eb = (int)((__float_as_uint(vmax) >> 23) & 0xffu);
-  return min(253, max(1, 267 - eb));
-}
-__device__ __forceinline__ float mf_pow2(int biased) { return __uint_as_float((unsigned)biased << 23); }
-
 // sixteen fp32 registers of one coordinate half (register s = non-zero s of the step, lane l = coordinate l of the half) ->
 // the fp16-term operands of the two 32-coordinate blocks of that half: lanes (n, 0) get the non-zeros 0..7, lanes (n, 1) the
-// non-zeros 8..15 (one lane swap per register pair, as in wrmf_chol_wave.hip)
+// non-zeros 8..15 (one lane swap per register pair, as in als_chol_wave_kernel)
 __device__ __forceinline__ void mf_operands(const float (&x)[16], f16x8& h0, f16x8& l0, f16x8& h1, f16x8& l1) {
   float b0[8], b1[8];
 #pragma unroll
@@ -68,8 +44,8 @@ __device__ __forceinline__ void mf_operands(const float (&x)[16], f16x8& h0, f16
     mf_split(b0[2 * q], b0[2 * q + 1], hh0[q], ll0[q]);
     mf_split(b1[2 * q], b1[2 * q + 1], hh1[q], ll1[q]);
   }
-  h0 = mf_pack(hh0[0], hh0[1], hh0[2], hh0[3]); l0 = mf_pack(ll0[0], ll0[1], ll0[2], ll0[3]);
-  h1 = mf_pack(hh1[0], hh1[1], hh1[2], hh1[3]); l1 = mf_pack(ll1[0], ll1[1], ll1[2], ll1[3]);
+  h0 = pack_f16x8(hh0[0], hh0[1], hh0[2], hh0[3]); l0 = pack_f16x8(ll0[0], ll0[1], ll0[2], ll0[3]);
+  h1 = pack_f16x8(hh1[0], hh1[1], hh1[2], hh1[3]); l1 = pack_f16x8(ll1[0], ll1[1], ll1[2], ll1[3]);
 }
 
 constexpr int mf_tid(int I, int K) { return I * (I + 1) / 2 + K; }   // the ten lower tiles, I >= K; tile t = a[MF_A0 + 16 t : MF_A0 + 16 t + 15]

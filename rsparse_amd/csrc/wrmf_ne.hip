@@ -42,13 +42,6 @@ namespace {
 
 using namespace dev;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float kCgTolNe = 1e-10f;  // CG_TOL, inst/include/wrmf.hpp:22
 constexpr int kStepNnz = 16;        // K of v_mfma_f32_32x32x16_bf16
 
 // Which wave accumulates what.  Rank 128 with implicit feedback needs 20 accumulator tiles (320 registers): more than
@@ -216,15 +209,6 @@ struct NeGeo {
   __host__ __device__ static constexpr int tile(int R, int C) { return R * (R + 1) / 2 + C; }
 };
 
-// ---- LDS-DMA, issued from asm so that the loop's s_waitcnt can be counted (see the header) ----
-// One 16-byte piece per lane: LDS destination = M0 + lane * 16 (wave-uniform base), source = each lane's own pointer.
-__device__ __forceinline__ void dma16(const void* g, unsigned lds_base) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(g), "s"(lds_base) : "memory", "m0");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // scalar load (lgkmcnt, not vmcnt: does not disturb the DMA queue accounting); the address must be wave-uniform
 __device__ __forceinline__ int sload(const int* p) {
   int v;
@@ -248,8 +232,6 @@ __device__ __forceinline__ unsigned split_stage(f32x2& r, bool last) {
   return pk;
 }
 
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // the same with fp16 terms (v_cvt_pk_f16_f32, round to nearest even; x - fl16(x) is exact in fp32 whatever fl16 did)
 __device__ __forceinline__ unsigned split_stage_h(f32x2& r, bool last) {
   const f16x2 hb = __builtin_convertvector(r, f16x2);
@@ -294,45 +276,10 @@ __device__ __forceinline__ f32x16 mfma_bf16(const u32x4 a, const u32x4 b, const 
                                                  0);
 }
 
-__device__ __forceinline__ float row16_sum_ne(float v) {
-  v += dpp<0xB1>(v);
-  v += dpp<0x4E>(v);
-  v += dpp<0x141>(v);
-  v += dpp<0x140>(v);
-  return v;
-}
-// sum over lanes l, l^16, l^32, l^48 (bitwise identical in all four)
-__device__ __forceinline__ float groups_sum_ne(float v) {
-  {
-    const unsigned u = __float_as_uint(v);
-    const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-  {
-    const unsigned u = __float_as_uint(v);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    v = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-  }
-  return v;
-}
-__device__ __forceinline__ float half_swap_sum(float v) {  // v(l) + v(l ^ 32)
-  const unsigned u = __float_as_uint(v);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float wave_sum_all(float v) { return groups_sum_ne(row16_sum_ne(v)); }
+__device__ __forceinline__ float wave_sum_all(float v) { return groups_sum(row16_sum(v)); }
 // LDS float add without return value (ds_add_f32)
 __device__ __forceinline__ void lds_add(float* p, float v) {
   (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
 // position of a ring group's gather stream: row `li` of the workgroup's list, step `s` of the group's steps in that row
@@ -882,7 +829,7 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
 #pragma unroll
         for (int t = 0; t < NB; t++) {
           const f32x2 v = bp_hi[t] + bp[t];
-          bsum[t] = half_swap_sum(v.x + v.y);
+          bsum[t] = half_sum(v.x + v.y);
         }
         sc += __shfl_xor(sc, 32);  // sc is uniform inside each half of the wave
       }
@@ -1113,7 +1060,7 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
           s2 = fmaf(tv[i][4 * q4 + 2], vv[i][4 * q4 + 2], s2);
           s3 = fmaf(tv[i][4 * q4 + 3], vv[i][4 * q4 + 3], s3);
         }
-        const float s = half_swap_sum((s0 + s1) + (s2 + s3));
+        const float s = half_sum((s0 + s1) + (s2 + s3));
         if (h == 0) part[(wv + 4 * (i0 + i)) * 32 + d] = s;
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -1188,7 +1135,7 @@ __global__ __launch_bounds__(256, QUAD ? 2 : 1) void als_ne_kernel(AlsArgs a, co
           r[t] = fmaf(-alpha, ap[t], r[t]);
         }
         const double rsnew = (double)dot(r, r);
-        if (rsnew < (double)kCgTolNe) {
+        if (rsnew < (double)kCgTol) {
           conv = true;
         } else {
           const float beta = (float)(rsnew / rsold);

@@ -25,10 +25,6 @@ namespace {
 
 using namespace dev;
 
-constexpr int kScdMaxIter = 10000;   // SCD_MAX_ITER, inst/include/wrmf.hpp:20
-constexpr float kScdTol = 1e-4f;     // SCD_TOL, inst/include/wrmf.hpp:21
-constexpr float kNnlsEps = 1e-16f;   // EPS, inst/include/nnls.hpp:8
-
 template <int KP, bool GLHS = false>
 struct NnlsSmem {
   // GLHS (end of round 6, rank 65..128): lhs lives in a global scratch of the workgroup (L2) and the tile holds 16 vectors, so that
@@ -42,34 +38,6 @@ struct NnlsSmem {
   static constexpr size_t vec_floats = (size_t)3 * KP + 2 * TC;  // rhs, init/result, spare, c, c1
   static constexpr size_t bytes = (tile_floats + (GLHS ? 1 : 2) * mat_floats + vec_floats + 16) * 4 + 64;
 };
-
-template <int KP, bool VEC, int TC = 32>
-__device__ __forceinline__ void nnls_gather_chunk(const AlsArgs& a, int base, int ccnt, float* sT, int wv, int lane) {
-  constexpr int LDT = KP + 4, TCW = TC / 4;   // (TCW vectors of the chunk per wave)
-  const int k = a.k;
-  if constexpr (VEC) {
-    constexpr int LPV = KP / 4, VPI = 64 / LPV, NQ = TCW / VPI;
-    static_assert(NQ >= 1, "a wave's share of the chunk is at least one load instruction");
-    const int c4 = lane % LPV, jo = lane / LPV;
-    int ids[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) ids[q] = a.row_idx[base + min(TCW * wv + q * VPI + jo, ccnt - 1)];
-    float4 v[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) v[q] = *reinterpret_cast<const float4*>(a.X + (size_t)ids[q] * k + min(c4 * 4, k - 4));
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-      const int j = TCW * wv + q * VPI + jo;
-      if (j < ccnt && c4 * 4 < k) *reinterpret_cast<float4*>(sT + j * LDT + c4 * 4) = v[q];
-    }
-  } else {
-    for (int j = TCW * wv; j < min(TCW * wv + TCW, ccnt); j++) {
-      const int id = rfl(a.row_idx[base + j]);
-      const float* src = a.X + (size_t)id * k;
-      for (int e = lane; e < k; e += 64) sT[j * LDT + e] = src[e];
-    }
-  }
-}
 
 template <int KP, bool IMPLICIT, bool VEC, bool GLHS = false>
 __global__ __launch_bounds__(256) void als_nnls_kernel(AlsArgs a) {
@@ -130,7 +98,7 @@ __global__ __launch_bounds__(256) void als_nnls_kernel(AlsArgs a) {
         sC[tid] = a.rhs_vals ? a.rhs_vals[base + tid] : cvv;   // coefficient in the right-hand side
         sC1[tid] = IMPLICIT ? cvv - 1.f : 1.f;
       }
-      nnls_gather_chunk<KP, VEC, TC>(a, base, ccnt, sT, wv, lane);
+      gather_chunk4<KP, VEC, TC>(a, base, ccnt, sT, wv, lane);
       __syncthreads();
       if (lower) {
         for (int j = 0; j < ccnt; j++) {
@@ -289,7 +257,7 @@ __global__ __launch_bounds__(256) void als_nnls_kernel(AlsArgs a) {
           sC[tid] = a.vals[base + tid];
           sC1[tid] = a.loss_tgt ? a.loss_tgt[base + tid] : a.loss_tgt_const;
         }
-        nnls_gather_chunk<KP, VEC, TC>(a, base, ccnt, sT, wv, lane);
+        gather_chunk4<KP, VEC, TC>(a, base, ccnt, sT, wv, lane);
         __syncthreads();
         if (wv == 0) {
           const float t = tile_dot<KP, TC>(sT, sH, lane);
@@ -325,10 +293,6 @@ __global__ __launch_bounds__(256) void als_nnls_kernel(AlsArgs a) {
 // Twelve chains per CU (168 registers: three waves per SIMD).
 // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>) in order: an unrolled loop whose index is a constant
 // expression (the lane number of a v_writelane_b32 has to be one)
-template <class F, int... Cs>
-__device__ __forceinline__ void static_for_seq(F&& f, std::integer_sequence<int, Cs...>) {
-  (f(std::integral_constant<int, Cs>{}), ...);
-}
 // h with lane C replaced by the (wave-uniform) value sval
 template <int C>
 __device__ __forceinline__ float writelane_c(float h, float sval) {
@@ -548,7 +512,7 @@ __global__ __launch_bounds__(64, 3) void als_nnls_wave_kernel(AlsArgs a) {
       float nv, df;
       step_of(nv, df);
       unsigned long long act = __ballot(df != 0.f) & in_range;
-      static_for_seq([&](auto c_tag) {
+      static_for<KP>([&](auto c_tag) {
         constexpr int c = decltype(c_tag)::value;
         if (__builtin_expect((act >> c) & 1ull, 0)) {
           const float d_c = readlane_f(df, c);
@@ -566,7 +530,7 @@ __global__ __launch_bounds__(64, 3) void als_nnls_wave_kernel(AlsArgs a) {
           step_of(nv, df);
           act = __ballot(df != 0.f) & in_range;
         }
-      }, std::make_integer_sequence<int, KP>{});
+      });
       if (!moved_far) break;
     }
     if (lk) yrow[ln] = h;

@@ -32,8 +32,6 @@ namespace {
 
 using namespace dev;
 
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-
 constexpr int kTopBlock = 32;    // users per MFMA block
 constexpr int kTopMaxK = 256;    // RSPARSE_HIP_MAX_TOPK
 constexpr int kTopMaxCap = 576;  // no candidate buffer is longer (top_gcap(256) = 544; the LDS geometries: k + 128 at most)
@@ -401,7 +399,7 @@ __global__ __launch_bounds__(W * 64) void top_product_kernel(const float* __rest
     load_tile(tl + kTopWaves);   // the next tile's loads fly during this tile's MFMAs
     if (tl < n_tiles) {
       const int i0 = tl * 32;
-      f32x16_t acc[UB];
+      f32x16 acc[UB];
 #pragma unroll
       for (int ub = 0; ub < UB; ub++)
 #pragma unroll
@@ -550,7 +548,7 @@ __global__ __launch_bounds__(256) void top_product_shared_kernel(const float* __
   for (int tl = 0; tl < n_tiles; tl++) {
     load_tile(tl + 1);   // the next tile's loads fly during this tile's MFMAs
     const int i0 = tl * 32;
-    f32x16_t acc[UB];
+    f32x16 acc[UB];
 #pragma unroll
     for (int ub = 0; ub < UB; ub++)
 #pragma unroll
@@ -756,7 +754,7 @@ __global__ __launch_bounds__(256) void top_product_pipe_kernel(const float* __re
   store_tile(0);
   load_tile(1);
   __syncthreads();
-  f32x16_t acc[2][UB];   // [tile parity]
+  f32x16 acc[2][UB];   // [tile parity]
 #pragma unroll
   for (int ub = 0; ub < UB; ub++)
 #pragma unroll
@@ -770,7 +768,7 @@ __global__ __launch_bounds__(256) void top_product_pipe_kernel(const float* __re
   store_tile(1);
   __syncthreads();
 
-  auto body = [&](const int tl, f32x16_t (&cur)[UB], f32x16_t (&nxt)[UB]) {
+  auto body = [&](const int tl, f32x16 (&cur)[UB], f32x16 (&nxt)[UB]) {
     // cur: scores of tile tl; LDS buffer (tl + 1) & 1 holds tile tl + 1
     load_tile(tl + 2);
     const float* tn = tiles + ((tl + 1) & 1) * 32 * LDT + col * LDT + half;

@@ -34,9 +34,6 @@ namespace {
 
 using namespace dev;
 
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned long long u64;
-
 constexpr int kLgMaxCand = 10240;          // the largest candidate list one workgroup orders in LDS (12 bytes an entry)
 constexpr int kLgHistBins = 2048;          // bins of the global per-user histogram (11 bits)
 constexpr size_t kLgWorkspaceWords = (size_t)1 << 29;   // 2 GiB: a chunk of users is sized to stay under it
@@ -48,13 +45,6 @@ __device__ __forceinline__ unsigned f32_key(float s) {
 }
 __device__ __forceinline__ float key_f32(unsigned k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ u64 f64_key(double s) {
-  const u64 u = (u64)__double_as_longlong(s + 0.0);
-  return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-__device__ __forceinline__ double key_f64(u64 k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
 }
 
 // ---- 1. scores -> keys ------------------------------------------------------------------------------------------------------
@@ -117,7 +107,7 @@ __global__ __launch_bounds__(256) void topl_score_kernel(const float* __restrict
     store_tile(tl);
     __syncthreads();
     load_tile(tl + 1);
-    f32x16_t acc[UB];
+    f32x16 acc[UB];
 #pragma unroll
     for (int ub = 0; ub < UB; ub++)
 #pragma unroll
@@ -297,53 +287,6 @@ __device__ __forceinline__ int block_prefix(bool f, int* sw, int* total) {
   return off + __popcll(m & ((1ull << lane) - 1ull));
 }
 
-// the kth largest of the keys key(e) (e < n, where valid) by a radix select on `nbits` bits, 8 per pass (256 threads).  Needs
-// 1 <= kth <= the number of valid entries.  hist: 256 words, sres / srem: one each.
-template <class KeyFn>
-__device__ u64 block_kth_largest(int n, int kth, int nbits, KeyFn key, unsigned* hist, u64* sres, int* srem) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  u64 prefix = 0;
-  int rem = kth;
-  for (int shift = nbits - 8; shift >= 0; shift -= 8) {
-    hist[tid] = 0u;
-    __syncthreads();
-    const u64 hmask = shift + 8 >= 64 ? 0ull : (~0ull << (shift + 8));
-    for (int e = tid; e < n; e += 256) {
-      bool ok;
-      const u64 k = key(e, ok);
-      if (ok && (k & hmask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (tid < 64) {
-      unsigned s = 0;
-      for (int j = 0; j < 4; j++) s += hist[255 - 4 * lane - j];
-      unsigned incl = s;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-      }
-      const unsigned excl = incl - s;
-      if (excl < (unsigned)rem && incl >= (unsigned)rem) {
-        unsigned cum = excl;
-        for (int j = 0; j < 4; j++) {
-          const int b = 255 - 4 * lane - j;
-          if (cum + hist[b] >= (unsigned)rem) {
-            *sres = prefix | ((u64)b << shift);
-            *srem = rem - (int)cum;
-            break;
-          }
-          cum += hist[b];
-        }
-      }
-    }
-    __syncthreads();
-    prefix = *sres;
-    rem = *srem;
-  }
-  return prefix;
-}
-
 // bitonic sort of sk / si [0, P) (P a power of two): descending by (key, index), or ascending
 __device__ void block_bitonic(u64* sk, int* si, int P, bool asc) {
   for (int size = 2; size <= P; size <<= 1)
@@ -420,14 +363,14 @@ __global__ __launch_bounds__(256) void topl_order_kernel(const TF* __restrict__ 
     for (int r = tid; r < rank; r += 256) uu[r] = (double)U[(size_t)u * rank + r];
   for (int e = tid; e < n; e += 256) {
     si[e] = cidx[(size_t)u * cap + e];
-    if constexpr (!RESCORE) sk[e] = f64_key((double)key_f32(ckey[(size_t)u * cap + e]));
+    if constexpr (!RESCORE) sk[e] = f64_key((double)key_f32(ckey[(size_t)u * cap + e]) + 0.0);
   }
   __syncthreads();
   if constexpr (RESCORE) {
     const int grp = tid >> 4, gl = tid & 15;
     for (int e = grp; e < n; e += 16) {
       const double s = dot16(uu, V, si[e], rank, gl);
-      if (gl == 0) sk[e] = f64_key(s);
+      if (gl == 0) sk[e] = f64_key(s + 0.0);
     }
     __syncthreads();
   }
@@ -523,13 +466,13 @@ __global__ __launch_bounds__(256) void topl_heap_kernel(const TF* __restrict__ U
         const unsigned kj = row[b0 + j];
         if (kj != 0u && kj >= t) {   // (uniform over the 16 lanes)
           const double s = dot16(uu, V, b0 + j, rank, gl);
-          if (gl == 0) sc[j] = f64_key(s);
+          if (gl == 0) sc[j] = f64_key(s + 0.0);
         }
       }
       __syncthreads();
       if (ok) mk = sc[tid];
     } else {
-      mk = f64_key((double)key_f32(k32));
+      mk = f64_key((double)key_f32(k32) + 0.0);
     }
     const bool enter = ok && (size < kk || mk > hk[0]);
     int ns;

@@ -23,38 +23,21 @@ namespace {
 
 using namespace dev;
 
-constexpr float kCgTolW = 1e-10f;
-constexpr int kScdMaxIterW = 10000;
-constexpr float kScdTolW = 1e-4f;
-constexpr float kNnlsEpsW = 1e-16f;
 constexpr int NT = 256;
 
-__device__ __forceinline__ int tri(const int i) { return (i * (i + 1)) >> 1; }
-
-__device__ __forceinline__ float wave_sum_f(float v) {   // butterfly: every lane ends with the same bits
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-// sum over the workgroup, every thread gets it; all threads must call it
+// sum over the workgroup, every thread gets it; all threads must call it.  The waves' partials as (r0 + r1) + (r2 + r3)
 __device__ __forceinline__ float block_sum_f(float v, float* red) {
-  v = wave_sum_f(v);
+  v = butterfly_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
-__device__ __forceinline__ void tile_of_w(int t, int& ti, int& tj) {
-  ti = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
-  while ((ti + 1) * (ti + 2) / 2 <= t) ti++;
-  while (ti * (ti + 1) / 2 > t) ti--;
-  tj = t - ti * (ti + 1) / 2;
-}
 // packed A(i, c) += sum_j xs[j][i] w[j] xs[j][c] over the 4 x 4 tiles of the lower triangle
 __device__ __forceinline__ void rank_update_packed(float* A, const float* xs, int kp, const float* w, int cn, int ntiles) {
   for (int t = threadIdx.x; t < ntiles; t += NT) {
     int ti, tj;
-    tile_of_w(t, ti, tj);
+    tile_of(t, ti, tj);
     float acc[4][4];
 #pragma unroll
     for (int r = 0; r < 4; r++)
@@ -269,7 +252,7 @@ __global__ __launch_bounds__(NT) void als_wide_kernel(WideArgs a, int KP, int CH
           part = fmaf(rr, rr, part);
         }
         const float rsnew = block_sum_f(part, red);
-        if (rsnew < kCgTolW) break;
+        if (rsnew < kCgTol) break;
         const float beta = (float)((double)rsnew / (double)rsold);
         for (int t = tid; t < k; t += NT) p[t] = fmaf(p[t], beta, r[t]);
         rsold = rsnew;
@@ -279,7 +262,7 @@ __global__ __launch_bounds__(NT) void als_wide_kernel(WideArgs a, int KP, int CH
       // XtX = lhs^T lhs + EPS I (full, global scratch), mu = XtX init - lhs^T rhs
       for (int t = tid; t < ntiles; t += NT) {
         int ti, tj;
-        tile_of_w(t, ti, tj);
+        tile_of(t, ti, tj);
         float acc[4][4];
 #pragma unroll
         for (int rr = 0; rr < 4; rr++)
@@ -301,7 +284,7 @@ __global__ __launch_bounds__(NT) void als_wide_kernel(WideArgs a, int KP, int CH
 #pragma unroll
           for (int rr = 0; rr < 4; rr++) {
             const int gi = 4 * ti + rr, gc = 4 * tj + c;
-            const float v = acc[rr][c] + (gi == gc ? kNnlsEpsW : 0.f);
+            const float v = acc[rr][c] + (gi == gc ? kNnlsEps : 0.f);
             M2[gi + (size_t)gc * LD2] = v;
             M2[gc + (size_t)gi * LD2] = v;
           }
@@ -322,7 +305,7 @@ __global__ __launch_bounds__(NT) void als_wide_kernel(WideArgs a, int KP, int CH
           mu[q] = c < k ? p[c] : 0.f;
           dg[q] = c < k ? M2[c + (size_t)c * LD2] : 1.f;
         }
-        for (int t = 0; t < kScdMaxIterW; t++) {
+        for (int t = 0; t < kScdMaxIter; t++) {
           float rel = 0.f;
 #pragma unroll
           for (int q = 0; q < 4; q++) {
@@ -344,14 +327,14 @@ __global__ __launch_bounds__(NT) void als_wide_kernel(WideArgs a, int KP, int CH
 #pragma unroll
                 for (int q2 = 0; q2 < 4; q2++)
                   if (lane + 64 * q2 < k) mu[q2] = fmaf(diff, col[lane + 64 * q2], mu[q2]);
-                rel = fmaxf(rel, fabsf(diff) / (fabsf(old_v) + kNnlsEpsW));
+                rel = fmaxf(rel, fabsf(diff) / (fabsf(old_v) + kNnlsEps));
                 act = __ballot(!(h[q] == 0.f && mu[q] >= 0.f)) & in_range & above;
               } else {
                 act &= above;
               }
             }
           }
-          if (rel <= kScdTolW) break;
+          if (rel <= kScdTol) break;
         }
 #pragma unroll
         for (int q = 0; q < 4; q++)
@@ -543,7 +526,7 @@ __global__ __launch_bounds__(NT) void als_wide_kernel(WideArgs a, int KP, int CH
       for (int j = wv; j < cn; j += 4) {
         float s = 0.f;
         for (int t = lane; t < k; t += 64) s = fmaf(xs[j * KP + t], x[t], s);
-        s = wave_sum_f(s);
+        s = butterfly_sum(s);
         const float dlt = lt[j] - s;
         lpart = fmaf(lw[j] * dlt, dlt, lpart);
       }

@@ -25,32 +25,6 @@ namespace {
 
 using namespace dev;
 
-constexpr float kCgTolWc = 1e-10f;   // CG_TOL, inst/include/wrmf.hpp:22
-
-__device__ __forceinline__ int tri_wc(const int i) { return (i * (i + 1)) >> 1; }
-
-// sixteen per-lane partial sums -> lane L holds the wave's sum of part[(L >> 2) & 15] (the four lanes of a quad hold copies):
-// every stage halves the number of values a lane carries by exchanging the half it does not keep with the lane across
-__device__ __forceinline__ float transposed_sum16(float (&v)[16], const int lane) {
-#pragma unroll
-  for (int st = 0; st < 4; st++) {
-    const int m = 32 >> st, n = 8 >> st;   // lane bit 5, 4, 3, 2 <-> value bit 3, 2, 1, 0
-    const bool up = (lane & m) != 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      if (i < n) {
-        const float keep = up ? v[i + n] : v[i];
-        const float send = up ? v[i] : v[i + n];
-        v[i] = keep + __shfl_xor(send, m);
-      }
-    }
-  }
-  float s = v[0];
-  s += __shfl_xor(s, 2);
-  s += __shfl_xor(s, 1);
-  return s;
-}
-
 template <int EPL>
 struct WVec {
   float c[EPL];
@@ -159,12 +133,12 @@ __global__ __launch_bounds__(TEAM > 1 ? 64 * TEAM : 256, TEAM > 1 ? 1 : 2) void 
   for (int e = 0; e < EPL; e++) {
     lk[e] = lane + 64 * e < k;
     lc[e] = min(lane + 64 * e, k - 1);
-    tl[e] = tri_wc(lc[e]);
+    tl[e] = tri(lc[e]);
   }
   if (IMPLICIT) {
     for (int e = tid; e < k * k; e += NTW) {
       const int i = e / k, j = e - i * k;
-      if (j <= i) sG[tri_wc(i) + j] = a.XtX[e];
+      if (j <= i) sG[tri(i) + j] = a.XtX[e];
     }
     __syncthreads();
   }
@@ -182,7 +156,7 @@ __global__ __launch_bounds__(TEAM > 1 ? 64 * TEAM : 256, TEAM > 1 ? 1 : 2) void 
 #pragma unroll
         for (int u = 0; u < 8; u++) {
           const int mm = 64 * e2 + min(m0 + u, lim - 1);
-          const int tm = tri_wc(mm);
+          const int tm = tri(mm);
 #pragma unroll
           for (int e = 0; e < EPL; e++) gv[u][e] = sG[lc[e] >= mm ? tl[e] + mm : tm + lc[e]];   // symmetric: (row, col) with row >= col
         }
@@ -248,7 +222,7 @@ __global__ __launch_bounds__(TEAM > 1 ? 64 * TEAM : 256, TEAM > 1 ? 1 : 2) void 
         r.c[e] = fmaf(-alpha, ap.c[e], r.c[e]);
       }
       const double rsnew = (double)dot(r, r);
-      if (rsnew < (double)kCgTolWc) break;
+      if (rsnew < (double)kCgTol) break;
       const float beta = (float)(rsnew / rsold);
 #pragma unroll
       for (int e = 0; e < EPL; e++) pv.c[e] = fmaf(pv.c[e], beta, r.c[e]);
