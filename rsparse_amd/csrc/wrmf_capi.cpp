@@ -16,7 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "wrmf_internal.h"
+#include "wrmf_capi_common.h"
 
 using namespace rsparse_hip;
 
@@ -27,21 +27,20 @@ struct rsparse_hip_csc {
 };
 
 namespace {
+thread_local std::string g_err;   // behind rsparse_hip_last_error()
+}
 
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
+int rsparse_hip::capi_fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-int hip_fail(hipError_t e, const char* what) {
+int rsparse_hip::capi_hip_fail(hipError_t e, const char* what) {
   return fail(RSPARSE_HIP_ERR_RUNTIME, std::string(what) + ": " + hipGetErrorString(e));
 }
-#define HIP_TRY(expr)                                       \
-  do {                                                      \
-    hipError_t _e = (expr);                                 \
-    if (_e != hipSuccess) return hip_fail(_e, #expr);       \
-  } while (0)
+
+namespace {
+
+using CscGuard = HandleGuard<rsparse_hip_csc, rsparse_hip_csc_destroy>;
 
 // Grow-only per-process scratch (single host thread drives the library, like the reference's
 // single R thread; not re-entrant across streams).
@@ -101,6 +100,15 @@ struct Workspace {
   size_t partial_slots() const { return partials.cap - kSumStageBlocks; }
 };
 thread_local Workspace g_ws;   // per host thread: the multi-GPU context (wrmf_ctx.cpp) drives one device from one thread each
+
+// the sum scratch of this thread's workspace for the bodies of wrmf_capi_common.h
+int sum_scratch(SumScratch& w) {
+  int rc = g_ws.ensure_device();
+  if (rc) return rc;
+  if ((rc = g_ws.ensure_partials(1024))) return rc;
+  w = {g_ws.partials, g_ws.scalars};
+  return RSPARSE_HIP_OK;
+}
 
 struct Profiler {
   bool on = false;
@@ -528,13 +536,6 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   return RSPARSE_HIP_OK;
 }
 
-template <class T>
-std::vector<float> to_f32(const T* src, size_t n) {
-  std::vector<float> v(n);
-  for (size_t i = 0; i < n; i++) v[i] = (float)src[i];
-  return v;
-}
-
 // als_explicit<T> with_biases (inst/include/wrmf_explicit.hpp:41-64,86-91,113-127) by re-packing: see wrmf_bias.hip.
 int run_half_iteration_explicit_biased(const rsparse_hip_csc* conf, const float* d_X, float* d_Y, int rank, double lambda,
                                        unsigned solver, unsigned cg_steps, int dynamic_lambda, int is_x_bias_last_row,
@@ -659,108 +660,45 @@ int run_half_iteration_implicit_global(const rsparse_hip_csc* conf, const float*
                             &bt, d_absmax);
 }
 
-// Shared body of the two stateless fp32 drop-ins (the `_double` ones: wrmf_f64_capi.cpp).
+// Body of the two stateless fp32 drop-ins (the `_double` ones: wrmf_f64_capi.cpp): stateless_half_iteration on a handle
+// made from the host arrays, with the four half-iterations of this side.
 int stateless(bool implicit, int n_rows, int n_cols, const int32_t* col_ptrs, const int32_t* row_indices,
               const double* values, const float* X, float* Y, const float* XtX, const float* cnt_X, int rank, double lambda,
               unsigned solver, unsigned cg_steps, int dynamic_lambda, double* loss_out, int with_biases = 0,
               int is_x_bias_last_row = 0, double global_bias = 0.0, float* global_bias_base = nullptr,
               int global_bias_base_len = 0, int initialize_bias_base = 1) {
-  rsparse_hip_csc* conf = nullptr;
-  int rc = rsparse_hip_csc_create_host(n_rows, n_cols, col_ptrs, row_indices, values, &conf);
+  int rc = check_common(n_rows, n_cols, col_ptrs, X, Y, rank);
   if (rc) return rc;
-  struct Guard { rsparse_hip_csc* c; ~Guard() { rsparse_hip_csc_destroy(c); } } guard{conf};
-  const size_t nx = (size_t)rank * n_rows, ny = (size_t)rank * n_cols;
-  const size_t ng = implicit && with_biases ? (size_t)(rank - 1) * (rank - 1) : (size_t)rank * rank;
-  DevBuf dX, dY, dG, dW;
-  HIP_TRY(dX.alloc(nx * 4));
-  HIP_TRY(dY.alloc(ny * 4));
-  auto upload = [](DevBuf& b, const float* src, size_t n) -> hipError_t {
-    return n ? hipMemcpy(b.p, src, n * 4, hipMemcpyHostToDevice) : hipSuccess;
+  if ((rc = check_variant(solver, with_biases, global_bias, implicit))) return rc;
+  rsparse_hip_csc* conf = nullptr;   // (validates the arrays; the values become floats here)
+  if ((rc = rsparse_hip_csc_create_host(n_rows, n_cols, col_ptrs, row_indices, values, &conf))) return rc;
+  CscGuard guard{conf};
+  const bool use_base = implicit && !with_biases && has_global_bias(global_bias);   // the threshold of float
+  auto scratch = [](SumScratch& w) {   // (the half-iterations size the partials themselves)
+    int rc = g_ws.ensure_device();
+    w = {g_ws.partials, g_ws.scalars};
+    return rc;
   };
-  HIP_TRY(upload(dX, X, nx));
-  HIP_TRY(upload(dY, Y, ny));
-  if (implicit) {
-    if (!XtX) return fail(RSPARSE_HIP_ERR_INVALID, "XtX is NULL");
-    HIP_TRY(dG.alloc(ng * 4));
-    HIP_TRY(upload(dG, XtX, ng));
-  }
-  const bool weighted = !implicit && dynamic_lambda;
-  if (weighted && lambda > 0) {
-    if (!cnt_X) return fail(RSPARSE_HIP_ERR_INVALID, "cnt_X is NULL with dynamic_lambda");
-    HIP_TRY(dW.alloc((size_t)n_rows * 4));
-    HIP_TRY(upload(dW, cnt_X, (size_t)n_rows));
-  }
-  if ((rc = g_ws.ensure_device())) return rc;
-  // counters left behind by earlier device-resident calls are not this call's: set aside here, handed back when this call
-  // ends (a stateless call between a resident fit's half-iterations and its check must not swallow the fit's failures)
-  StaleFailures stale_guard;
-  const bool gbias = implicit && has_global_bias(global_bias);
-  DevBuf dBase;
-  if (gbias && !with_biases) {
-    // global_bias_base = -global_bias * rowSums(X), `rank` entries (wrmf_implicit.hpp:111-112).  The caller's buffer holds
-    // global_bias_base_len entries -- the R driver allocates rank - 1 (R/model_WRMF.R:292) although the reference's C++ reads
-    // and assigns `rank`; here never more than the stated length is touched: it is READ (initialize_bias_base == 0) only
-    // when it holds the whole vector, otherwise the vector is recomputed from X (its definition); it is WRITTEN up to
-    // min(len, rank) entries
-    HIP_TRY(dBase.alloc((size_t)rank * 4));
-    const int blen = global_bias_base ? std::max(global_bias_base_len, 0) : 0;
-    const bool given = !initialize_bias_base && blen >= rank;
-    if (given) HIP_TRY(upload(dBase, global_bias_base, (size_t)rank));
-    rc = run_half_iteration_implicit_global(conf, dX.as<float>(), dY.as<float>(), dG.as<float>(), rank, lambda, solver,
-                                            cg_steps, global_bias, given ? dBase.as<float>() : nullptr,
-                                            given ? nullptr : dBase.as<float>(), g_ws.scalars, nullptr);
-    if (!rc && !given && initialize_bias_base && blen > 0) {
-      std::vector<float> hb((size_t)rank);
-      HIP_TRY(hipMemcpy(hb.data(), dBase.p, (size_t)rank * 4, hipMemcpyDeviceToHost));
-      for (int t = 0; t < std::min(blen, rank); t++) global_bias_base[t] = hb[(size_t)t];
-    }
-  } else if (with_biases && implicit)
-    rc = run_half_iteration_implicit_biased(conf, dX.as<float>(), dY.as<float>(), dG.as<float>(), rank, lambda, solver,
-                                            is_x_bias_last_row, g_ws.scalars, nullptr, global_bias);
-  else if (with_biases)
-    rc = run_half_iteration_explicit_biased(conf, dX.as<float>(), dY.as<float>(), rank, lambda, solver, cg_steps,
-                                            dynamic_lambda, is_x_bias_last_row, g_ws.scalars, nullptr);
-  else
-    rc = run_half_iteration(conf, implicit, dX.as<float>(), dY.as<float>(), dG.as<float>(), rank, lambda, solver,
-                            cg_steps, dynamic_lambda, g_ws.scalars, nullptr);
-  if (rc) return rc;
-  double reg = 0.0;
-  if (lambda > 0 && nx > 0) {  // + lambda * accu(X % X)  [* cnt_X]
-    const float* Xreg = dX.as<float>();
-    int kreg = rank;
-    DevBuf dXe;
-    if (with_biases) {  // every row of X but the ones: drop_row(X, !is_x_bias_last_row), wrmf_explicit.hpp:147-159
-      kreg = rank - 1;
-      HIP_TRY(dXe.alloc((size_t)kreg * n_rows * 4));
-      HIP_TRY(hipMemcpy2D(dXe.p, (size_t)kreg * 4, dX.as<float>() + (is_x_bias_last_row ? 1 : 0), (size_t)rank * 4,
-                          (size_t)kreg * 4, (size_t)n_rows, hipMemcpyDeviceToDevice));
-      Xreg = dXe.as<float>();
-    }
-    hipError_t e = launch_weighted_sumsq(Xreg, kreg, n_rows, weighted ? dW.as<float>() : nullptr,
-                                         g_ws.scalars + 1, g_ws.partials, nullptr);
-    if (e != hipSuccess) return hip_fail(e, "launch_weighted_sumsq");
-    HIP_TRY(hipDeviceSynchronize());   // dXe is released at the end of this block
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  int64_t nfail = 0;
-  rsparse_hip_take_numeric_failures(&nfail, nullptr);
-  double host_scalars[2] = {0, 0};
-  HIP_TRY(hipMemcpy(host_scalars, g_ws.scalars, 2 * sizeof(double), hipMemcpyDeviceToHost));
-  if (lambda > 0 && nx > 0) reg = lambda * host_scalars[1];
-  if (ny) HIP_TRY(hipMemcpy(Y, dY.p, ny * 4, hipMemcpyDeviceToHost));
-  const double nnz = (double)conf->d.nnz;
-  if (loss_out) *loss_out = (host_scalars[0] + reg) / nnz;  // wrmf_implicit.hpp:304
-  if (nfail)
-    return fail(RSPARSE_HIP_ERR_NUMERIC, std::to_string(nfail) + " per-row systems were singular (not positive definite, and "
-                                         "the general solver found a zero pivot column)");
-  return RSPARSE_HIP_OK;
+  auto half = [&](const float* dX, float* dY, const float* dG, const float* base_in, float* base_out, double* d_loss) {
+    if (use_base)
+      return run_half_iteration_implicit_global(conf, dX, dY, dG, rank, lambda, solver, cg_steps, global_bias, base_in, base_out,
+                                                d_loss, nullptr);
+    if (with_biases && implicit)
+      return run_half_iteration_implicit_biased(conf, dX, dY, dG, rank, lambda, solver, is_x_bias_last_row, d_loss, nullptr,
+                                                global_bias);
+    if (with_biases)
+      return run_half_iteration_explicit_biased(conf, dX, dY, rank, lambda, solver, cg_steps, dynamic_lambda, is_x_bias_last_row,
+                                                d_loss, nullptr);
+    return run_half_iteration(conf, implicit, dX, dY, dG, rank, lambda, solver, cg_steps, dynamic_lambda, d_loss, nullptr);
+  };
+  return stateless_half_iteration(scratch, half, implicit, n_rows, n_cols, conf->d.nnz, X, Y, XtX, cnt_X, rank, lambda,
+                                  dynamic_lambda, loss_out, with_biases, is_x_bias_last_row, use_base, global_bias_base,
+                                  global_bias_base_len, initialize_bias_base);
 }
 
 }  // namespace
 
 namespace rsparse_hip {
-int capi_fail(int code, const std::string& msg) { return fail(code, msg); }
-int capi_hip_fail(hipError_t e, const char* what) { return hip_fail(e, what); }
 int* capi_fail_counters() { return g_ws.ensure_device() ? nullptr : g_ws.fails; }
 void capi_fail_carry_add(int64_t unresolved, int64_t fallback) {
   g_fail_carry[0] += unresolved;
@@ -806,7 +744,7 @@ int rsparse_hip_csc_create_host(int n_rows, int n_cols, const int32_t* col_ptrs,
     if (row_indices[e] < 0 || row_indices[e] >= n_rows)
       return fail(RSPARSE_HIP_ERR_INVALID, "row index out of range");
   rsparse_hip_csc* m = new rsparse_hip_csc();
-  struct Guard { rsparse_hip_csc* c; ~Guard() { if (c) rsparse_hip_csc_destroy(c); } } guard{m};
+  CscGuard guard{m};
   if (hipGetDevice(&m->device) != hipSuccess) return fail(RSPARSE_HIP_ERR_RUNTIME, "no HIP device");
   DevCSC& d = m->d;
   d.n_rows = n_rows; d.n_cols = n_cols; d.nnz = nnz;
@@ -826,7 +764,7 @@ int rsparse_hip_csc_create_host(int n_rows, int n_cols, const int32_t* col_ptrs,
     HIP_TRY(hipMemcpy(di, row_indices, (size_t)nnz * 4, hipMemcpyHostToDevice));
     // values: f64 on the wire (dgCMatrix@x), f32 once resident -- the conversion the reference does per
     // column with arma::conv_to (wrmf_implicit.hpp:182-183)
-    std::vector<float> v32 = to_f32(values, (size_t)nnz);
+    std::vector<float> v32(values, values + nnz);
     HIP_TRY(hipMemcpy(dv, v32.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
   }
   if (int rc = build_schedule(*m, col_ptrs)) return rc;
@@ -855,7 +793,7 @@ int rsparse_hip_csc_create_device(int n_rows, int n_cols, const int32_t* d_col_p
     if (bad) return fail(RSPARSE_HIP_ERR_INVALID, "row index out of range");
   }
   rsparse_hip_csc* m = new rsparse_hip_csc();
-  struct Guard { rsparse_hip_csc* c; ~Guard() { if (c) rsparse_hip_csc_destroy(c); } } guard{m};
+  CscGuard guard{m};
   if (hipGetDevice(&m->device) != hipSuccess) return fail(RSPARSE_HIP_ERR_RUNTIME, "no HIP device");
   DevCSC& d = m->d;
   d.n_rows = n_rows; d.n_cols = n_cols; d.nnz = nnz;   // (the caller's arrays: not in m->owned)
@@ -1012,17 +950,9 @@ int rsparse_hip_gramian_absmax_device(const float* d_X, int rank, int64_t n, dou
 }
 
 int rsparse_hip_gramian_float(const float* X, int rank, int64_t n, double lambda, float* XtX_out) {
-  if (!X || !XtX_out) return fail(RSPARSE_HIP_ERR_INVALID, "X or XtX_out is NULL");
-  if (rank <= 0 || n < 0) return fail(RSPARSE_HIP_ERR_INVALID, "rank must be positive and n non-negative");
-  DevBuf dX, dG;
-  HIP_TRY(dX.alloc((size_t)rank * n * 4));
-  HIP_TRY(dG.alloc((size_t)rank * rank * 4));
-  if (n) HIP_TRY(hipMemcpy(dX.p, X, (size_t)rank * n * 4, hipMemcpyHostToDevice));
-  int rc = rsparse_hip_gramian_device(dX.as<float>(), rank, n, lambda, dG.as<float>(), nullptr, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(XtX_out, dG.p, (size_t)rank * rank * 4, hipMemcpyDeviceToHost));
-  return RSPARSE_HIP_OK;
+  return gramian_host(X, rank, n, XtX_out, [&](const float* dX, float* dG) {
+    return rsparse_hip_gramian_device(dX, rank, n, lambda, dG, nullptr, nullptr);
+  });
 }
 
 int rsparse_hip_als_implicit_device(const rsparse_hip_csc* conf, const float* d_X, float* d_Y, const float* d_XtX,
@@ -1070,85 +1000,36 @@ int rsparse_hip_initialize_biases_implicit_device(const rsparse_hip_csc* c_ui, c
                                                   int non_negative, int calculate_global_bias,
                                                   double* global_bias_out, void* stream) {
   if (!c_ui || !c_iu || !d_user_bias || !d_item_bias) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or bias vector");
-  const DevCSC& a = c_ui->d;   // users x items, columns = items
-  const DevCSC& b = c_iu->d;   // items x users, columns = users
+  const CscView<float> a(c_ui->d), b(c_iu->d);   // users x items (columns = items), items x users (columns = users)
   if (a.n_rows != b.n_cols || a.n_cols != b.n_rows || a.nnz != b.nnz)
     return fail(RSPARSE_HIP_ERR_INVALID, "the two matrices are not transposes of each other");
-  hipStream_t s = (hipStream_t)stream;
-  int rc = g_ws.ensure_device();
-  if (rc) return rc;
-  if ((rc = g_ws.ensure_partials(1024))) return rc;
-  const int n_items = a.n_cols, n_users = b.n_cols;
-  DevBuf stats;   // means / adjustments of both sides (wrmf_utils.hpp:97-124), doubles
-  HIP_TRY(stats.alloc(((size_t)2 * n_items + (size_t)2 * n_users + 4) * sizeof(double)));
-  double* item_means = stats.as<double>();
-  double* item_adj = item_means + n_items;
-  double* user_means = item_adj + n_items;
-  double* user_adj = user_means + n_users;
-  hipError_t e;
-  if ((e = launch_bias_implicit_prep(a.col_ptrs, a.vals, n_items, n_users, lambda, item_means, item_adj, s)) != hipSuccess ||
-      (e = launch_bias_implicit_prep(b.col_ptrs, b.vals, n_users, n_items, lambda, user_means, user_adj, s)) != hipSuccess)
-    return hip_fail(e, "launch_bias_implicit_prep");
-  double global_bias = 0.0;
-  if (calculate_global_bias) {   // :90-93: sum(x) / (sum(x) + n_users n_items - nnz)
-    if ((e = launch_values_sum(a.vals, a.nnz, g_ws.partials, g_ws.scalars + 2, s)) != hipSuccess)
-      return hip_fail(e, "launch_values_sum");
-    double sum = 0.0;
-    HIP_TRY(hipMemcpyAsync(&sum, g_ws.scalars + 2, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    global_bias = sum / (sum + (double)n_users * (double)n_items - (double)a.nnz);
-  }
-  if (non_negative) global_bias = std::fmax(0.0, global_bias);
-  if (global_bias_out) *global_bias_out = global_bias;
-  for (int iter = 0; iter < 5; iter++) {   // :130-162
-    const double* usum = nullptr;
-    if (iter > 0) {                        // mean of the user biases of the previous sweep (:131-135)
-      if ((e = launch_values_sum(d_user_bias, n_users, g_ws.partials, g_ws.scalars + 2, s)) != hipSuccess)
-        return hip_fail(e, "launch_values_sum");
-      usum = g_ws.scalars + 2;
-    }
-    if ((e = launch_bias_implicit_sweep(a.col_ptrs, a.row_idx, a.vals, d_user_bias, n_items, n_users, usum, item_means,
-                                        item_adj, non_negative, global_bias, d_item_bias, s)) != hipSuccess)
-      return hip_fail(e, "launch_bias_implicit_sweep");
-    if ((e = launch_values_sum(d_item_bias, n_items, g_ws.partials, g_ws.scalars + 3, s)) != hipSuccess)
-      return hip_fail(e, "launch_values_sum");
-    if ((e = launch_bias_implicit_sweep(b.col_ptrs, b.row_idx, b.vals, d_item_bias, n_users, n_items, g_ws.scalars + 3,
-                                        user_means, user_adj, non_negative, global_bias, d_user_bias, s)) != hipSuccess)
-      return hip_fail(e, "launch_bias_implicit_sweep");
-  }
-  HIP_TRY(hipStreamSynchronize(s));   // `stats` is released on return
-  return RSPARSE_HIP_OK;
+  SumScratch w;
+  if (int rc = sum_scratch(w)) return rc;
+  return initialize_biases_implicit(a, b, d_user_bias, d_item_bias, lambda, non_negative, calculate_global_bias, w,
+                                    (hipStream_t)stream, global_bias_out);
 }
 
 // ---- single sweeps of the bias initialisation over ONE column block (sharded drivers; see the header) ----
 int rsparse_hip_bias_sweep_explicit_device(const rsparse_hip_csc* conf, const float* d_other_bias, double lambda,
                                            int dynamic_lambda, int non_negative, float* d_out, void* stream) {
   if (!conf || !d_other_bias || !d_out) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or bias vector");
-  const DevCSC& a = conf->d;
-  hipError_t e = launch_bias_sweep(a.col_ptrs, a.row_idx, a.vals, d_other_bias, a.n_cols, (float)lambda, dynamic_lambda,
-                                   non_negative, d_out, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "launch_bias_sweep");
-  return RSPARSE_HIP_OK;
+  // (float)lambda: the reference's T lambda of the float instantiation
+  return bias_sweep_explicit(CscView<float>(conf->d), d_other_bias, (float)lambda, dynamic_lambda, non_negative, d_out,
+                             (hipStream_t)stream);
 }
 
 int rsparse_hip_bias_prep_implicit_device(const rsparse_hip_csc* conf, int n_other, double lambda, double* d_means,
                                           double* d_adj, void* stream) {
   if (!conf || !d_means || !d_adj) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
-  const DevCSC& a = conf->d;
-  hipError_t e = launch_bias_implicit_prep(a.col_ptrs, a.vals, a.n_cols, n_other, lambda, d_means, d_adj, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "launch_bias_implicit_prep");
-  return RSPARSE_HIP_OK;
+  return bias_prep_implicit(CscView<float>(conf->d), n_other, lambda, d_means, d_adj, (hipStream_t)stream);
 }
 
 int rsparse_hip_bias_sweep_implicit_device(const rsparse_hip_csc* conf, const float* d_other_bias, int n_other,
                                            const double* d_other_sum, const double* d_means, const double* d_adj,
                                            int non_negative, double global_bias, float* d_out, void* stream) {
   if (!conf || !d_other_bias || !d_means || !d_adj || !d_out) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or vector");
-  const DevCSC& a = conf->d;
-  hipError_t e = launch_bias_implicit_sweep(a.col_ptrs, a.row_idx, a.vals, d_other_bias, a.n_cols, n_other, d_other_sum, d_means,
-                                            d_adj, non_negative, global_bias, d_out, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "launch_bias_implicit_sweep");
-  return RSPARSE_HIP_OK;
+  return bias_sweep_implicit(CscView<float>(conf->d), d_other_bias, n_other, d_other_sum, d_means, d_adj, non_negative,
+                             global_bias, d_out, (hipStream_t)stream);
 }
 
 int rsparse_hip_als_explicit_bias_device(const rsparse_hip_csc* conf, const float* d_X, float* d_Y, int rank,
@@ -1165,39 +1046,17 @@ int rsparse_hip_initialize_biases_explicit_device(rsparse_hip_csc* c_ui, rsparse
                                                   int non_negative, int calculate_global_bias,
                                                   double* global_bias_out, void* stream) {
   if (!c_ui || !c_iu || !d_user_bias || !d_item_bias) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or bias vector");
-  const DevCSC& a = c_ui->d;   // users x items, columns = items
-  const DevCSC& b = c_iu->d;   // items x users, columns = users
+  const CscView<float> a(c_ui->d), b(c_iu->d);   // users x items (columns = items), items x users (columns = users)
   if (a.n_rows != b.n_cols || a.n_cols != b.n_rows || a.nnz != b.nnz)
     return fail(RSPARSE_HIP_ERR_INVALID, "the two matrices are not transposes of each other");
-  hipStream_t s = (hipStream_t)stream;
-  int rc = g_ws.ensure_device();
-  if (rc) return rc;
-  if ((rc = g_ws.ensure_partials(1024))) return rc;
-  double global_bias = 0.0;
-  hipError_t e;
-  if (calculate_global_bias && a.nnz > 0) {   // wrmf_utils.hpp:41-52: mean of the values, removed from both orientations
-    if (a.vals_frozen || b.vals_frozen)
-      return fail(RSPARSE_HIP_ERR_INVALID, "the values of a frozen handle cannot lose their mean (rsparse_hip_csc_freeze_values)");
-    if ((e = launch_values_sum(a.vals, a.nnz, g_ws.partials, g_ws.scalars + 2, s)) != hipSuccess)
-      return hip_fail(e, "launch_values_sum");
-    const double inv = 1.0 / (double)a.nnz;
-    if ((e = launch_values_subtract_mean(const_cast<float*>(a.vals), a.nnz, g_ws.scalars + 2, inv, s)) != hipSuccess ||
-        (e = launch_values_subtract_mean(const_cast<float*>(b.vals), b.nnz, g_ws.scalars + 2, inv, s)) != hipSuccess)
-      return hip_fail(e, "launch_values_subtract_mean");
-    double sum = 0.0;
-    HIP_TRY(hipMemcpyAsync(&sum, g_ws.scalars + 2, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    global_bias = sum * inv;
-  }
-  for (int iter = 0; iter < 5; iter++) {       // :54-82
-    if ((e = launch_bias_sweep(a.col_ptrs, a.row_idx, a.vals, d_user_bias, a.n_cols, (float)lambda, dynamic_lambda,
-                               non_negative, d_item_bias, s)) != hipSuccess ||
-        (e = launch_bias_sweep(b.col_ptrs, b.row_idx, b.vals, d_item_bias, b.n_cols, (float)lambda, dynamic_lambda,
-                               non_negative, d_user_bias, s)) != hipSuccess)
-      return hip_fail(e, "launch_bias_sweep");
-  }
-  if (global_bias_out) *global_bias_out = global_bias;
-  return RSPARSE_HIP_OK;
+  SumScratch w;
+  if (int rc = sum_scratch(w)) return rc;
+  // a frozen handle promises unchanged values (the fp64 handle has no such flag)
+  if (calculate_global_bias && a.nnz > 0 && (c_ui->d.vals_frozen || c_iu->d.vals_frozen))
+    return fail(RSPARSE_HIP_ERR_INVALID, "the values of a frozen handle cannot lose their mean (rsparse_hip_csc_freeze_values)");
+  // (float)lambda: the reference's T lambda of the float instantiation
+  return initialize_biases_explicit(a, b, d_user_bias, d_item_bias, (float)lambda, dynamic_lambda, non_negative,
+                                    calculate_global_bias, w, (hipStream_t)stream, global_bias_out);
 }
 
 int rsparse_hip_values_subtract_mean_device(int64_t n, float* d_x, float* d_x_other, double* mean_out, void* stream) {
@@ -1205,21 +1064,11 @@ int rsparse_hip_values_subtract_mean_device(int64_t n, float* d_x, float* d_x_ot
   if (mean_out) *mean_out = 0.0;
   if (n == 0) return RSPARSE_HIP_OK;
   if (!d_x) return fail(RSPARSE_HIP_ERR_INVALID, "values is NULL");
-  hipStream_t s = (hipStream_t)stream;
-  int rc = g_ws.ensure_device();
-  if (rc) return rc;
-  if ((rc = g_ws.ensure_partials(1024))) return rc;
-  hipError_t e = launch_values_sum(d_x, n, g_ws.partials, g_ws.scalars + 2, s);
-  if (e != hipSuccess) return hip_fail(e, "launch_values_sum");
-  const double inv = 1.0 / (double)n;
-  if ((e = launch_values_subtract_mean(d_x, n, g_ws.scalars + 2, inv, s)) != hipSuccess)
-    return hip_fail(e, "launch_values_subtract_mean");
-  if (d_x_other && (e = launch_values_subtract_mean(d_x_other, n, g_ws.scalars + 2, inv, s)) != hipSuccess)
-    return hip_fail(e, "launch_values_subtract_mean");
-  double sum = 0.0;
-  HIP_TRY(hipMemcpyAsync(&sum, g_ws.scalars + 2, sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (mean_out) *mean_out = sum * inv;
+  SumScratch w;
+  if (int rc = sum_scratch(w)) return rc;
+  double mean = 0.0;
+  if (int rc = subtract_mean(d_x, d_x_other, n, w, (hipStream_t)stream, &mean)) return rc;
+  if (mean_out) *mean_out = mean;
   return RSPARSE_HIP_OK;
 }
 
@@ -1227,12 +1076,9 @@ int rsparse_hip_weighted_sumsq_device(const float* d_X, int rank, int64_t n, con
                                       void* stream) {
   if (!d_X || !d_out) return fail(RSPARSE_HIP_ERR_INVALID, "X or out is NULL");
   if (rank <= 0 || n < 0) return fail(RSPARSE_HIP_ERR_INVALID, "rank must be positive and n non-negative");
-  int rc = g_ws.ensure_device();
-  if (rc) return rc;
-  if ((rc = g_ws.ensure_partials(1024))) return rc;
-  hipError_t e = launch_weighted_sumsq(d_X, rank, n, d_w, d_out, g_ws.partials, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "launch_weighted_sumsq");
-  return RSPARSE_HIP_OK;
+  SumScratch w;
+  if (int rc = sum_scratch(w)) return rc;
+  return weighted_sumsq(d_X, rank, n, d_w, d_out, w, (hipStream_t)stream);
 }
 
 int rsparse_hip_top_product_device(const float* d_U, const float* d_V, int n_users, int n_items, int rank, int k,
@@ -1577,9 +1423,6 @@ int rsparse_hip_als_implicit_float(int n_rows, int n_cols, const int32_t* col_pt
                                    float* global_bias_base, int global_bias_base_len, int initialize_bias_base,
                                    double* loss_out) {
   (void)n_threads;
-  int rc = check_common(n_rows, n_cols, col_ptrs, X, Y, rank);
-  if (rc) return rc;
-  if ((rc = check_variant(solver, with_biases, global_bias))) return rc;
   return stateless(true, n_rows, n_cols, col_ptrs, row_indices, values, X, Y, XtX, nullptr, rank, lambda, solver, cg_steps, 0,
                    loss_out, with_biases, is_x_bias_last_row, global_bias, global_bias_base, global_bias_base_len,
                    initialize_bias_base);
@@ -1596,27 +1439,21 @@ int rsparse_hip_initialize_biases_float(int n_users, int n_items, const int32_t*
   rsparse_hip_csc *c_ui = nullptr, *c_iu = nullptr;
   int rc = rsparse_hip_csc_create_host(n_users, n_items, csc_p, csc_i, csc_x, &c_ui);   // columns = items
   if (rc) return rc;
-  struct Guard { rsparse_hip_csc* c; ~Guard() { rsparse_hip_csc_destroy(c); } } g1{c_ui};
+  CscGuard g1{c_ui};
   if ((rc = rsparse_hip_csc_create_host(n_items, n_users, csr_p, csr_i, csr_x, &c_iu))) return rc;   // columns = users
-  Guard g2{c_iu};
-  DevBuf dU, dI;
-  HIP_TRY(dU.alloc((size_t)n_users * 4));
-  HIP_TRY(dI.alloc((size_t)n_items * 4));
-  if (n_users) HIP_TRY(hipMemcpy(dU.p, user_bias, (size_t)n_users * 4, hipMemcpyHostToDevice));
-  if (n_items) HIP_TRY(hipMemcpy(dI.p, item_bias, (size_t)n_items * 4, hipMemcpyHostToDevice));
+  CscGuard g2{c_iu};
   double gb = 0.0;
-  if (is_explicit_feedback)
-    rc = rsparse_hip_initialize_biases_explicit_device(c_ui, c_iu, dU.as<float>(), dI.as<float>(), lambda, dynamic_lambda,
-                                                       non_negative, calculate_global_bias, &gb, nullptr);
-  else
-    rc = rsparse_hip_initialize_biases_implicit_device(c_ui, c_iu, dU.as<float>(), dI.as<float>(), lambda, non_negative,
-                                                       calculate_global_bias, &gb, nullptr);
+  rc = with_device_biases(n_users, n_items, user_bias, item_bias, [&](float* dU, float* dI) {
+    return is_explicit_feedback
+               ? rsparse_hip_initialize_biases_explicit_device(c_ui, c_iu, dU, dI, lambda, dynamic_lambda, non_negative,
+                                                               calculate_global_bias, &gb, nullptr)
+               : rsparse_hip_initialize_biases_implicit_device(c_ui, c_iu, dU, dI, lambda, non_negative, calculate_global_bias,
+                                                               &gb, nullptr);
+  });
   if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  if (n_users) HIP_TRY(hipMemcpy(user_bias, dU.p, (size_t)n_users * 4, hipMemcpyDeviceToHost));
-  if (n_items) HIP_TRY(hipMemcpy(item_bias, dI.p, (size_t)n_items * 4, hipMemcpyDeviceToHost));
   if (is_explicit_feedback && calculate_global_bias) {
-    // the reference removes the global mean from the @x slots of BOTH matrices in place (wrmf_utils.hpp:41-52)
+    // the reference removes the global mean from the @x slots of BOTH matrices in place (wrmf_utils.hpp:41-52): on the host
+    // here, from the caller's doubles (the resident values are their float copies)
     const int64_t nnz = csc_p[n_items];
     for (int64_t e = 0; e < nnz; e++) csc_x[e] -= gb;
     for (int64_t e = 0; e < nnz; e++) csr_x[e] -= gb;
@@ -1630,9 +1467,6 @@ int rsparse_hip_als_explicit_float(int n_rows, int n_cols, const int32_t* col_pt
                                    double lambda, unsigned n_threads, unsigned solver, unsigned cg_steps,
                                    int dynamic_lambda, int with_biases, int is_x_bias_last_row, double* loss_out) {
   (void)n_threads;
-  int rc = check_common(n_rows, n_cols, col_ptrs, X, Y, rank);
-  if (rc) return rc;
-  if ((rc = check_variant(solver, with_biases, 0.0, false))) return rc;
   return stateless(false, n_rows, n_cols, col_ptrs, row_indices, values, X, Y, nullptr, cnt_X, rank, lambda, solver, cg_steps,
                    dynamic_lambda, loss_out, with_biases, is_x_bias_last_row);
 }

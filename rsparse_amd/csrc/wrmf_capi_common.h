@@ -1,0 +1,288 @@
+// Host bodies of the C-ABI entries that exist in float and in double, written once (wrmf_capi.cpp and wrmf_f64_capi.cpp hold
+// the thin `extern "C"` forms: validate, make sure of their own workspace, build the views below, call the template).
+// What differs between the two sides on purpose is listed in DESIGN.md ("shared between the precisions").
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/rsparse_wrmf_hip.h"
+#include "wrmf_f64.h"
+#include "wrmf_internal.h"
+
+namespace rsparse_hip {
+
+inline int fail(int code, const std::string& msg) { return capi_fail(code, msg); }
+inline int hip_fail(hipError_t e, const char* what) { return capi_hip_fail(e, what); }
+#define HIP_TRY(expr)                                       \
+  do {                                                      \
+    hipError_t _e = (expr);                                 \
+    if (_e != hipSuccess) return hip_fail(_e, #expr);       \
+  } while (0)
+
+// the two launchers whose names differ by an `f64_` infix, as overloads (the float forms: wrmf_internal.h)
+inline hipError_t launch_weighted_sumsq(const double* X, int k, int64_t n, const double* w, double* out, double* partials,
+                                        hipStream_t s) {
+  return launch_f64_weighted_sumsq(X, k, n, w, out, partials, s);
+}
+template <class T>
+constexpr const char* weighted_sumsq_name() {   // (what the error text of each side has always said)
+  return std::is_same<T, double>::value ? "launch_f64_weighted_sumsq" : "launch_weighted_sumsq";
+}
+
+// a handle released at the end of a scope (H: rsparse_hip_csc / rsparse_hip_csc_f64); `c = nullptr` keeps it
+template <class H, int (*Destroy)(H*)>
+struct HandleGuard {
+  H* c;
+  ~HandleGuard() { if (c) Destroy(c); }
+};
+
+// A device CSC as the bodies below see it: from rsparse_hip_csc::d (T = float) or from rsparse_hip_csc_f64 (T = double).
+// Only subtract_mean writes through `vals`.
+template <class T>
+struct CscView {
+  int n_rows, n_cols;
+  int64_t nnz;
+  const int32_t* col_ptrs;
+  const int32_t* row_idx;
+  T* vals;
+  template <class M>
+  explicit CscView(const M& m)
+      : n_rows(m.n_rows), n_cols(m.n_cols), nnz(m.nnz), col_ptrs(m.col_ptrs), row_idx(m.row_idx), vals(const_cast<T*>(m.vals)) {}
+};
+
+// the sum scratch of a workspace, after its own ensure...() call: `partials` >= 1024 + kSumStageBlocks doubles, `scalars` 16
+// doubles ([0] loss rows, [1] sumsq, [2], [3] sums of the bias sweeps)
+struct SumScratch {
+  double* partials;
+  double* scalars;
+};
+
+// mean(x) out of x and (if given) x_other, n entries each: sum -> subtract from both -> read the sum back
+template <class T>
+int subtract_mean(T* x, T* x_other, int64_t n, SumScratch w, hipStream_t s, double* mean_out) {
+  hipError_t e = launch_values_sum(x, n, w.partials, w.scalars + 2, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_values_sum");
+  const double inv = 1.0 / (double)n;
+  if ((e = launch_values_subtract_mean(x, n, w.scalars + 2, inv, s)) != hipSuccess)
+    return hip_fail(e, "launch_values_subtract_mean");
+  if (x_other && (e = launch_values_subtract_mean(x_other, n, w.scalars + 2, inv, s)) != hipSuccess)
+    return hip_fail(e, "launch_values_subtract_mean");
+  double sum = 0.0;
+  HIP_TRY(hipMemcpyAsync(&sum, w.scalars + 2, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *mean_out = sum * inv;
+  return RSPARSE_HIP_OK;
+}
+
+// ---- single sweeps of the bias initialisation over ONE column block (sharded drivers; see the header) ----
+template <class T>
+int bias_sweep_explicit(CscView<T> a, const T* d_other_bias, T lambda, int dynamic_lambda, int non_negative, T* d_out,
+                        hipStream_t s) {
+  hipError_t e = launch_bias_sweep(a.col_ptrs, a.row_idx, a.vals, d_other_bias, a.n_cols, lambda, dynamic_lambda, non_negative,
+                                   d_out, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_bias_sweep");
+  return RSPARSE_HIP_OK;
+}
+
+template <class T>
+int bias_prep_implicit(CscView<T> a, int n_other, double lambda, double* d_means, double* d_adj, hipStream_t s) {
+  hipError_t e = launch_bias_implicit_prep(a.col_ptrs, a.vals, a.n_cols, n_other, lambda, d_means, d_adj, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_bias_implicit_prep");
+  return RSPARSE_HIP_OK;
+}
+
+template <class T>
+int bias_sweep_implicit(CscView<T> a, const T* d_other_bias, int n_other, const double* d_other_sum, const double* d_means,
+                        const double* d_adj, int non_negative, double global_bias, T* d_out, hipStream_t s) {
+  hipError_t e = launch_bias_implicit_sweep(a.col_ptrs, a.row_idx, a.vals, d_other_bias, a.n_cols, n_other, d_other_sum, d_means,
+                                            d_adj, non_negative, global_bias, d_out, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_bias_implicit_sweep");
+  return RSPARSE_HIP_OK;
+}
+
+// initialize_biases_explicit, wrmf_utils.hpp:32-84.  a: users x items, columns = items; b: items x users, columns = users
+template <class T>
+int initialize_biases_explicit(CscView<T> a, CscView<T> b, T* d_user_bias, T* d_item_bias, T lambda, int dynamic_lambda,
+                               int non_negative, int calculate_global_bias, SumScratch w, hipStream_t s,
+                               double* global_bias_out) {
+  double global_bias = 0.0;
+  if (calculate_global_bias && a.nnz > 0)   // :41-52: mean of the values, removed from both orientations in place
+    if (int rc = subtract_mean(a.vals, b.vals, a.nnz, w, s, &global_bias)) return rc;
+  for (int iter = 0; iter < 5; iter++) {    // :54-82
+    if (int rc = bias_sweep_explicit(a, d_user_bias, lambda, dynamic_lambda, non_negative, d_item_bias, s)) return rc;
+    if (int rc = bias_sweep_explicit(b, d_item_bias, lambda, dynamic_lambda, non_negative, d_user_bias, s)) return rc;
+  }
+  if (global_bias_out) *global_bias_out = global_bias;
+  return RSPARSE_HIP_OK;
+}
+
+// initialize_biases_implicit, wrmf_utils.hpp:86-165 (a, b as above)
+template <class T>
+int initialize_biases_implicit(CscView<T> a, CscView<T> b, T* d_user_bias, T* d_item_bias, double lambda, int non_negative,
+                               int calculate_global_bias, SumScratch w, hipStream_t s, double* global_bias_out) {
+  const int n_items = a.n_cols, n_users = b.n_cols;
+  DevBuf stats;   // means / adjustments of both sides (:97-124), doubles
+  HIP_TRY(stats.alloc(((size_t)2 * n_items + (size_t)2 * n_users + 4) * sizeof(double)));
+  double* item_means = stats.as<double>();
+  double* item_adj = item_means + n_items;
+  double* user_means = item_adj + n_items;
+  double* user_adj = user_means + n_users;
+  int rc;
+  if ((rc = bias_prep_implicit(a, n_users, lambda, item_means, item_adj, s))) return rc;
+  if ((rc = bias_prep_implicit(b, n_items, lambda, user_means, user_adj, s))) return rc;
+  double global_bias = 0.0;
+  hipError_t e;
+  if (calculate_global_bias) {   // :90-93: sum(x) / (sum(x) + n_users n_items - nnz)
+    if ((e = launch_values_sum(a.vals, a.nnz, w.partials, w.scalars + 2, s)) != hipSuccess) return hip_fail(e, "launch_values_sum");
+    double sum = 0.0;
+    HIP_TRY(hipMemcpyAsync(&sum, w.scalars + 2, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    global_bias = sum / (sum + (double)n_users * (double)n_items - (double)a.nnz);
+  }
+  if (non_negative) global_bias = std::fmax(0.0, global_bias);
+  if (global_bias_out) *global_bias_out = global_bias;
+  for (int iter = 0; iter < 5; iter++) {   // :130-162
+    const double* usum = nullptr;
+    if (iter > 0) {                        // mean of the user biases of the previous sweep (:131-135)
+      if ((e = launch_values_sum(d_user_bias, n_users, w.partials, w.scalars + 2, s)) != hipSuccess)
+        return hip_fail(e, "launch_values_sum");
+      usum = w.scalars + 2;
+    }
+    if ((rc = bias_sweep_implicit(a, d_user_bias, n_users, usum, item_means, item_adj, non_negative, global_bias, d_item_bias, s)))
+      return rc;
+    if ((e = launch_values_sum(d_item_bias, n_items, w.partials, w.scalars + 3, s)) != hipSuccess)
+      return hip_fail(e, "launch_values_sum");
+    if ((rc = bias_sweep_implicit(b, d_item_bias, n_items, w.scalars + 3, user_means, user_adj, non_negative, global_bias,
+                                  d_user_bias, s)))
+      return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(s));   // `stats` is released on return
+  return RSPARSE_HIP_OK;
+}
+
+// lambda-free part of the regularisation term: accu(X % X), each column times w if given
+template <class T>
+int weighted_sumsq(const T* d_X, int rank, int64_t n, const T* d_w, double* d_out, SumScratch w, hipStream_t s) {
+  hipError_t e = launch_weighted_sumsq(d_X, rank, n, d_w, d_out, w.partials, s);
+  if (e != hipSuccess) return hip_fail(e, weighted_sumsq_name<T>());
+  return RSPARSE_HIP_OK;
+}
+
+// X'X + lambda I of a host matrix; device_gramian(d_X, d_G) is the side's resident entry
+template <class T, class DeviceGramian>
+int gramian_host(const T* X, int rank, int64_t n, T* XtX_out, DeviceGramian device_gramian) {
+  if (!X || !XtX_out) return fail(RSPARSE_HIP_ERR_INVALID, "X or XtX_out is NULL");
+  if (rank <= 0 || n < 0) return fail(RSPARSE_HIP_ERR_INVALID, "rank must be positive and n non-negative");
+  DevBuf dX, dG;
+  HIP_TRY(dX.alloc((size_t)rank * n * sizeof(T)));
+  HIP_TRY(dG.alloc((size_t)rank * rank * sizeof(T)));
+  if (n) HIP_TRY(hipMemcpy(dX.p, X, (size_t)rank * n * sizeof(T), hipMemcpyHostToDevice));
+  int rc = device_gramian(dX.as<T>(), dG.as<T>());
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(XtX_out, dG.p, (size_t)rank * rank * sizeof(T), hipMemcpyDeviceToHost));
+  return RSPARSE_HIP_OK;
+}
+
+template <class T>
+hipError_t upload_host(DevBuf& b, const T* src, size_t n) {   // n host elements into a fresh buffer
+  hipError_t e = b.alloc(n * sizeof(T));
+  return (e != hipSuccess || !n) ? e : hipMemcpy(b.p, src, n * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// Shared body of the stateless drop-ins (als_implicit / als_explicit, src/wrmf_implicit.cpp:5-26, src/wrmf_explicit.cpp:5-26)
+// once the caller has validated what its side validates and made its resident matrix (nnz non-zeros).  Handed in:
+//   int scratch(SumScratch& w)    makes sure of the side's workspace and gives its sum scratch as it is now
+//   int half(const T* dX, T* dY, const T* dG, const T* base_in, T* base_out, double* d_loss)    the side's half-iteration
+// use_base: implicit feedback, no user/item biases and a global bias above the side's threshold.
+template <class T, class Scratch, class Half>
+int stateless_half_iteration(Scratch scratch, Half half, bool implicit, int n_rows, int n_cols, int64_t nnz, const T* X, T* Y,
+                             const T* XtX, const T* cnt_X, int rank, double lambda, int dynamic_lambda, double* loss_out,
+                             int with_biases, int is_x_bias_last_row, bool use_base, T* global_bias_base,
+                             int global_bias_base_len, int initialize_bias_base) {
+  if (implicit && !XtX) return fail(RSPARSE_HIP_ERR_INVALID, "XtX is NULL");
+  const size_t nx = (size_t)rank * n_rows, ny = (size_t)rank * n_cols;
+  const size_t ng = implicit && with_biases ? (size_t)(rank - 1) * (rank - 1) : (size_t)rank * rank;
+  DevBuf dX, dY, dG, dW, dBase;
+  HIP_TRY(upload_host(dX, X, nx));
+  HIP_TRY(upload_host(dY, Y, ny));
+  if (implicit) HIP_TRY(upload_host(dG, XtX, ng));
+  const bool weighted = !implicit && dynamic_lambda && lambda > 0;
+  if (weighted) {
+    if (!cnt_X) return fail(RSPARSE_HIP_ERR_INVALID, "cnt_X is NULL with dynamic_lambda");
+    HIP_TRY(upload_host(dW, cnt_X, (size_t)n_rows));
+  }
+  int rc;
+  SumScratch w;
+  if ((rc = scratch(w))) return rc;
+  // counters left behind by earlier device-resident calls are not this call's: set aside here, handed back when this call
+  // ends (a stateless call between a resident fit's half-iterations and its check must not swallow the fit's failures)
+  StaleFailures stale_guard;
+  const int blen = global_bias_base ? std::max(global_bias_base_len, 0) : 0;
+  const bool given = use_base && !initialize_bias_base && blen >= rank;
+  if (use_base) {
+    // global_bias_base = -global_bias * rowSums(X), `rank` entries (wrmf_implicit.hpp:111-112).  The caller's buffer holds
+    // global_bias_base_len entries -- the R driver allocates rank - 1 (R/model_WRMF.R:292) although the reference's C++ reads
+    // and assigns `rank`; here never more than the stated length is touched: it is READ (initialize_bias_base == 0) only
+    // when it holds the whole vector, otherwise the vector is recomputed from X (its definition); it is WRITTEN up to
+    // min(len, rank) entries
+    HIP_TRY(dBase.alloc((size_t)rank * sizeof(T)));
+    if (given) HIP_TRY(hipMemcpy(dBase.p, global_bias_base, (size_t)rank * sizeof(T), hipMemcpyHostToDevice));
+  }
+  rc = half(dX.as<T>(), dY.as<T>(), dG.as<T>(), given ? dBase.as<T>() : nullptr, use_base && !given ? dBase.as<T>() : nullptr,
+            w.scalars);
+  if (rc) return rc;
+  if (use_base && !given && initialize_bias_base && blen > 0) {
+    std::vector<T> hb((size_t)rank);
+    HIP_TRY(hipMemcpy(hb.data(), dBase.p, (size_t)rank * sizeof(T), hipMemcpyDeviceToHost));
+    for (int t = 0; t < std::min(blen, rank); t++) global_bias_base[t] = hb[(size_t)t];
+  }
+  if ((rc = scratch(w))) return rc;   // (the half-iteration may have grown the partials)
+  const bool regularised = lambda > 0 && nx > 0;
+  if (regularised) {  // + lambda * accu(X % X)  [* cnt_X]
+    const T* Xreg = dX.as<T>();
+    int kreg = rank;
+    DevBuf dXe;
+    if (with_biases) {  // every row of X but the ones: drop_row(X, !is_x_bias_last_row), wrmf_explicit.hpp:147-159, :287-297
+      kreg = rank - 1;
+      HIP_TRY(dXe.alloc((size_t)kreg * n_rows * sizeof(T)));
+      HIP_TRY(hipMemcpy2D(dXe.p, (size_t)kreg * sizeof(T), dX.as<T>() + (is_x_bias_last_row ? 1 : 0), (size_t)rank * sizeof(T),
+                          (size_t)kreg * sizeof(T), (size_t)n_rows, hipMemcpyDeviceToDevice));
+      Xreg = dXe.as<T>();
+    }
+    if ((rc = weighted_sumsq(Xreg, kreg, n_rows, weighted ? dW.as<T>() : nullptr, w.scalars + 1, w, nullptr))) return rc;
+    HIP_TRY(hipDeviceSynchronize());   // dXe is released at the end of this block
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  int64_t nfail = 0;
+  rsparse_hip_take_numeric_failures(&nfail, nullptr);
+  double host_scalars[2] = {0, 0};
+  HIP_TRY(hipMemcpy(host_scalars, w.scalars, 2 * sizeof(double), hipMemcpyDeviceToHost));
+  const double reg = regularised ? lambda * host_scalars[1] : 0.0;
+  if (ny) HIP_TRY(hipMemcpy(Y, dY.p, ny * sizeof(T), hipMemcpyDeviceToHost));
+  if (loss_out) *loss_out = (host_scalars[0] + reg) / (double)nnz;  // wrmf_implicit.hpp:304
+  if (nfail)
+    return fail(RSPARSE_HIP_ERR_NUMERIC, std::to_string(nfail) + " per-row systems were singular (not positive definite, and "
+                                         "the general solver found a zero pivot column)");
+  return RSPARSE_HIP_OK;
+}
+
+// The host bias vectors of the stateless bias initialisation (initialize_biases_float / _double, src/wrmf_init.cpp:5-34)
+// up, `run(d_user_bias, d_item_bias)` on them, and down again.
+template <class T, class Run>
+int with_device_biases(int n_users, int n_items, T* user_bias, T* item_bias, Run run) {
+  DevBuf dU, dI;
+  HIP_TRY(upload_host(dU, user_bias, (size_t)n_users));
+  HIP_TRY(upload_host(dI, item_bias, (size_t)n_items));
+  if (int rc = run(dU.as<T>(), dI.as<T>())) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if (n_users) HIP_TRY(hipMemcpy(user_bias, dU.p, (size_t)n_users * sizeof(T), hipMemcpyDeviceToHost));
+  if (n_items) HIP_TRY(hipMemcpy(item_bias, dI.p, (size_t)n_items * sizeof(T), hipMemcpyDeviceToHost));
+  return RSPARSE_HIP_OK;
+}
+
+}  // namespace rsparse_hip

@@ -9,8 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "wrmf_f64.h"
-#include "wrmf_internal.h"
+#include "wrmf_capi_common.h"
 
 using namespace rsparse_hip;
 
@@ -30,13 +29,7 @@ struct rsparse_hip_csc_f64 {
 
 namespace {
 
-#define HIP_TRY(expr)                                       \
-  do {                                                      \
-    hipError_t _e = (expr);                                 \
-    if (_e != hipSuccess) return capi_hip_fail(_e, #expr);  \
-  } while (0)
-
-int fail(int code, const std::string& msg) { return capi_fail(code, msg); }
+using CscGuardF64 = HandleGuard<rsparse_hip_csc_f64, rsparse_hip_csc_f64_destroy>;
 
 constexpr size_t kRhsInitDoubles = (size_t)256 * 128 + 128;
 
@@ -101,6 +94,7 @@ struct WorkspaceF64 {
     HIP_TRY(rinit.ensure(kRhsInitDoubles));
     return RSPARSE_HIP_OK;
   }
+  SumScratch scratch() const { return {partials, scalars}; }   // (for the bodies of wrmf_capi_common.h, after ensure())
 } g_w64;
 
 // One half-iteration in double.  d_base_in / d_base_out: global_bias_base of the no-bias global-bias variant (`rank`
@@ -147,13 +141,13 @@ int f64_half_iteration(const rsparse_hip_csc_f64* conf, bool implicit, const dou
   hipError_t e;
   if (implicit && with_biases) {        // rhs_init = -X' (x_b + global_bias)  (:142-153)
     if ((e = launch_f64_rhs_init(d_X, rank, a.xoff, a.k1, a.xb, gb, conf->n_rows, g_w64.rinit, rinit, s)) != hipSuccess)
-      return capi_hip_fail(e, "launch_f64_rhs_init");
+      return hip_fail(e, "launch_f64_rhs_init");
     a.rhs_init = rinit;
   } else if (gb != 0.0) {               // global_bias_base = -global_bias * rowSums(X)  (:110-112, :155-157)
     if (d_base_in) {
       HIP_TRY(hipMemcpyAsync(rinit, d_base_in, (size_t)rank * sizeof(double), hipMemcpyDeviceToDevice, s));
     } else if ((e = launch_f64_rhs_init(d_X, rank, 0, rank, -1, gb, conf->n_rows, g_w64.rinit, rinit, s)) != hipSuccess) {
-      return capi_hip_fail(e, "launch_f64_rhs_init");
+      return hip_fail(e, "launch_f64_rhs_init");
     }
     if (d_base_out) HIP_TRY(hipMemcpyAsync(d_base_out, rinit, (size_t)rank * sizeof(double), hipMemcpyDeviceToDevice, s));
     a.rhs_init = rinit;
@@ -189,10 +183,10 @@ int f64_half_iteration(const rsparse_hip_csc_f64* conf, bool implicit, const dou
     double* Xp = g_w64.repack;
     double* Yp = Xp + nx;
     double* Vp = Yp + ny;
-    if ((e = launch_f64_pack_rows(d_X, rank, a.xoff, k1, conf->n_rows, Xp, s)) != hipSuccess) return capi_hip_fail(e, "launch_f64_pack_rows");
-    if ((e = launch_f64_pack_rows(d_Y, rank, a.ioff, k1, conf->n_cols, Yp, s)) != hipSuccess) return capi_hip_fail(e, "launch_f64_pack_rows");
+    if ((e = launch_f64_pack_rows(d_X, rank, a.xoff, k1, conf->n_rows, Xp, s)) != hipSuccess) return hip_fail(e, "launch_f64_pack_rows");
+    if ((e = launch_f64_pack_rows(d_Y, rank, a.ioff, k1, conf->n_cols, Yp, s)) != hipSuccess) return hip_fail(e, "launch_f64_pack_rows");
     if ((e = launch_f64_shift_values(conf->vals, conf->row_idx, d_X, rank, a.xb, conf->nnz, Vp, s)) != hipSuccess)
-      return capi_hip_fail(e, "launch_f64_shift_values");
+      return hip_fail(e, "launch_f64_shift_values");
     F64Args b = a;
     b.X = Xp; b.Y = Yp; b.vals = Vp;
     b.k = k1; b.k1 = k1;
@@ -200,16 +194,16 @@ int f64_half_iteration(const rsparse_hip_csc_f64* conf, bool implicit, const dou
     if (conf->n_long > 0) {   // (the long rows' scratch was sized for `rank` coordinates: enough for k1)
       b.long_scratch = g_w64.longs;
     }
-    if ((e = launch_f64_als(b, s)) != hipSuccess) return capi_hip_fail(e, "launch_f64_als");
-    if ((e = launch_f64_unpack_rows(Yp, k1, conf->n_cols, rank, a.ooff, d_Y, s)) != hipSuccess) return capi_hip_fail(e, "launch_f64_unpack_rows");
+    if ((e = launch_f64_als(b, s)) != hipSuccess) return hip_fail(e, "launch_f64_als");
+    if ((e = launch_f64_unpack_rows(Yp, k1, conf->n_cols, rank, a.ooff, d_Y, s)) != hipSuccess) return hip_fail(e, "launch_f64_unpack_rows");
   } else {
-    if ((e = launch_f64_als(a, s)) != hipSuccess) return capi_hip_fail(e, "launch_f64_als");
+    if ((e = launch_f64_als(a, s)) != hipSuccess) return hip_fail(e, "launch_f64_als");
   }
-  if ((e = launch_sum_partials(g_w64.partials, (size_t)grid, out, s)) != hipSuccess) return capi_hip_fail(e, "launch_sum_partials");
+  if ((e = launch_sum_partials(g_w64.partials, (size_t)grid, out, s)) != hipSuccess) return hip_fail(e, "launch_sum_partials");
   return RSPARSE_HIP_OK;
 }
 
-// Shared body of the two stateless `*_double` drop-ins.
+// Body of the two stateless `*_double` drop-ins: stateless_half_iteration on the matrix uploaded as it is.
 int stateless_double(bool implicit, int n_rows, int n_cols, const int32_t* col_ptrs, const int32_t* row_indices,
                      const double* values, const double* X, double* Y, const double* XtX, const double* cnt_X, int rank,
                      double lambda, unsigned solver, unsigned cg_steps, int dynamic_lambda, double* loss_out,
@@ -231,94 +225,27 @@ int stateless_double(bool implicit, int n_rows, int n_cols, const int32_t* col_p
   if (nnz > 0 && (!row_indices || !values)) return fail(RSPARSE_HIP_ERR_INVALID, "row_indices or values is NULL");
   for (int64_t e = 0; e < nnz; e++)
     if (row_indices[e] < 0 || row_indices[e] >= n_rows) return fail(RSPARSE_HIP_ERR_INVALID, "row index out of range");
-  const size_t nx = (size_t)rank * n_rows, ny = (size_t)rank * n_cols;
-  const size_t ng = implicit && with_biases ? (size_t)(rank - 1) * (rank - 1) : (size_t)rank * rank;
-  DevBuf dP, dI, dV, dX, dY, dG, dW, dBase;
-  HIP_TRY(dP.alloc(((size_t)n_cols + 1) * 4));
-  HIP_TRY(dI.alloc((size_t)nnz * 4));
-  HIP_TRY(dV.alloc((size_t)nnz * 8));
-  HIP_TRY(dX.alloc(nx * 8));
-  HIP_TRY(dY.alloc(ny * 8));
-  HIP_TRY(hipMemcpy(dP.p, col_ptrs, ((size_t)n_cols + 1) * 4, hipMemcpyHostToDevice));
-  if (nnz) {
-    HIP_TRY(hipMemcpy(dI.p, row_indices, (size_t)nnz * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dV.p, values, (size_t)nnz * 8, hipMemcpyHostToDevice));
-  }
-  if (nx) HIP_TRY(hipMemcpy(dX.p, X, nx * 8, hipMemcpyHostToDevice));
-  if (ny) HIP_TRY(hipMemcpy(dY.p, Y, ny * 8, hipMemcpyHostToDevice));
-  if (implicit) {
-    HIP_TRY(dG.alloc(ng * 8));
-    HIP_TRY(hipMemcpy(dG.p, XtX, ng * 8, hipMemcpyHostToDevice));
-  }
-  const bool weighted = !implicit && dynamic_lambda;
-  if (weighted && lambda > 0) {
-    if (!cnt_X) return fail(RSPARSE_HIP_ERR_INVALID, "cnt_X is NULL with dynamic_lambda");
-    HIP_TRY(dW.alloc((size_t)n_rows * 8));
-    if (n_rows) HIP_TRY(hipMemcpy(dW.p, cnt_X, (size_t)n_rows * 8, hipMemcpyHostToDevice));
-  }
-  int rc = g_w64.ensure();
-  if (rc) return rc;
-  StaleFailures stale_guard;   // counters left by earlier device-resident calls are not this call's (handed back at the end)
+  DevBuf dP, dI, dV;
+  HIP_TRY(upload_host(dP, col_ptrs, (size_t)n_cols + 1));
+  HIP_TRY(upload_host(dI, row_indices, (size_t)nnz));
+  HIP_TRY(upload_host(dV, values, (size_t)nnz));
   rsparse_hip_csc_f64 conf;
   conf.n_rows = n_rows; conf.n_cols = n_cols; conf.nnz = nnz;
   conf.col_ptrs = dP.as<int32_t>(); conf.row_idx = dI.as<int32_t>(); conf.vals = dV.as<double>();
-  if ((rc = list_long_rows(conf, col_ptrs))) return rc;
-  const bool gbias = implicit && !with_biases && global_bias >= std::sqrt(DBL_EPSILON);
-  const double* base_in = nullptr;
-  double* base_out = nullptr;
-  const int blen = global_bias_base ? std::max(global_bias_base_len, 0) : 0;
-  bool given = false;
-  if (gbias) {
-    // global_bias_base: `rank` entries (wrmf_implicit.hpp:111-112); the caller's buffer holds global_bias_base_len of them
-    // (the R driver allocates rank - 1, R/model_WRMF.R:292).  Never more than the stated length is touched: it is READ
-    // (initialize_bias_base == 0) only when it holds the whole vector, otherwise recomputed from X (its definition); it is
-    // WRITTEN up to min(len, rank) entries
-    HIP_TRY(dBase.alloc((size_t)rank * 8));
-    given = !initialize_bias_base && blen >= rank;
-    if (given) {
-      HIP_TRY(hipMemcpy(dBase.p, global_bias_base, (size_t)rank * 8, hipMemcpyHostToDevice));
-      base_in = dBase.as<double>();
-    } else {
-      base_out = dBase.as<double>();
-    }
-  }
-  rc = f64_half_iteration(&conf, implicit, dX.as<double>(), dY.as<double>(), dG.as<double>(), rank, lambda, solver, cg_steps,
-                          dynamic_lambda, with_biases, is_x_bias_last_row, global_bias, base_in, base_out, g_w64.scalars,
-                          nullptr);
-  if (rc) return rc;
-  if (gbias && !given && initialize_bias_base && blen > 0) {
-    std::vector<double> hb((size_t)rank);
-    HIP_TRY(hipMemcpy(hb.data(), dBase.p, (size_t)rank * 8, hipMemcpyDeviceToHost));
-    for (int t = 0; t < std::min(blen, rank); t++) global_bias_base[t] = hb[(size_t)t];
-  }
-  if (lambda > 0 && nx > 0) {  // + lambda * accu(X % X)  [* cnt_X]; with biases every row of X but the ones (:147-159, :287-297)
-    const double* Xreg = dX.as<double>();
-    int kreg = rank;
-    DevBuf dXe;
-    if (with_biases) {
-      kreg = rank - 1;
-      HIP_TRY(dXe.alloc((size_t)kreg * n_rows * 8));
-      HIP_TRY(hipMemcpy2D(dXe.p, (size_t)kreg * 8, dX.as<double>() + (is_x_bias_last_row ? 1 : 0), (size_t)rank * 8,
-                          (size_t)kreg * 8, (size_t)n_rows, hipMemcpyDeviceToDevice));
-      Xreg = dXe.as<double>();
-    }
-    hipError_t e = launch_f64_weighted_sumsq(Xreg, kreg, n_rows, (weighted && lambda > 0) ? dW.as<double>() : nullptr,
-                                             g_w64.scalars + 1, g_w64.partials, nullptr);
-    if (e != hipSuccess) return capi_hip_fail(e, "launch_f64_weighted_sumsq");
-    HIP_TRY(hipDeviceSynchronize());   // dXe is released at the end of this block
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  int64_t nfail = 0;
-  rsparse_hip_take_numeric_failures(&nfail, nullptr);
-  double hs[2] = {0, 0};
-  HIP_TRY(hipMemcpy(hs, g_w64.scalars, 2 * sizeof(double), hipMemcpyDeviceToHost));
-  const double reg = (lambda > 0 && nx > 0) ? lambda * hs[1] : 0.0;
-  if (ny) HIP_TRY(hipMemcpy(Y, dY.p, ny * 8, hipMemcpyDeviceToHost));
-  if (loss_out) *loss_out = (hs[0] + reg) / (double)nnz;   // wrmf_implicit.hpp:304
-  if (nfail)
-    return fail(RSPARSE_HIP_ERR_NUMERIC, std::to_string(nfail) + " per-row systems were singular (not positive definite, and "
-                                         "the general solver found a zero pivot column)");
-  return RSPARSE_HIP_OK;
+  if (int rc = list_long_rows(conf, col_ptrs)) return rc;
+  const bool use_base = implicit && !with_biases && global_bias >= std::sqrt(DBL_EPSILON);   // the threshold of double
+  auto scratch = [](SumScratch& w) {
+    int rc = g_w64.ensure();
+    w = g_w64.scratch();
+    return rc;
+  };
+  auto half = [&](const double* dX, double* dY, const double* dG, const double* base_in, double* base_out, double* d_loss) {
+    return f64_half_iteration(&conf, implicit, dX, dY, dG, rank, lambda, solver, cg_steps, dynamic_lambda, with_biases,
+                              is_x_bias_last_row, global_bias, base_in, base_out, d_loss, nullptr);
+  };
+  return stateless_half_iteration(scratch, half, implicit, n_rows, n_cols, nnz, X, Y, XtX, cnt_X, rank, lambda, dynamic_lambda,
+                                  loss_out, with_biases, is_x_bias_last_row, use_base, global_bias_base, global_bias_base_len,
+                                  initialize_bias_base);
 }
 
 }  // namespace
@@ -378,22 +305,14 @@ int rsparse_hip_gramian_f64_device(const double* d_X, int rank, int64_t n, doubl
   HIP_TRY(g_w64.gram.ensure(f64_gramian_scratch_doubles(rank)));
   const double ridge = (double)(float)lambda;   // float::fl(diag(lambda)): rounded to fp32 in the double build too, R/model_WRMF.R:476
   hipError_t e = launch_f64_gramian(d_X, rank, n, ridge, d_XtX_out, d_sumsq_out, g_w64.gram, (hipStream_t)stream);
-  if (e != hipSuccess) return capi_hip_fail(e, "launch_f64_gramian");
+  if (e != hipSuccess) return hip_fail(e, "launch_f64_gramian");
   return RSPARSE_HIP_OK;
 }
 
 int rsparse_hip_gramian_double(const double* X, int rank, int64_t n, double lambda, double* XtX_out) {
-  if (!X || !XtX_out) return fail(RSPARSE_HIP_ERR_INVALID, "X or XtX_out is NULL");
-  if (rank <= 0 || n < 0) return fail(RSPARSE_HIP_ERR_INVALID, "rank must be positive and n non-negative");
-  DevBuf dX, dG;
-  HIP_TRY(dX.alloc((size_t)rank * n * 8));
-  HIP_TRY(dG.alloc((size_t)rank * rank * 8));
-  if (n) HIP_TRY(hipMemcpy(dX.p, X, (size_t)rank * n * 8, hipMemcpyHostToDevice));
-  int rc = rsparse_hip_gramian_f64_device(dX.as<double>(), rank, n, lambda, dG.as<double>(), nullptr, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(XtX_out, dG.p, (size_t)rank * rank * 8, hipMemcpyDeviceToHost));
-  return RSPARSE_HIP_OK;
+  return gramian_host(X, rank, n, XtX_out, [&](const double* dX, double* dG) {
+    return rsparse_hip_gramian_f64_device(dX, rank, n, lambda, dG, nullptr, nullptr);
+  });
 }
 
 int rsparse_hip_als_f64_device(const rsparse_hip_csc_f64* conf, int implicit, const double* d_X, double* d_Y,
@@ -409,11 +328,8 @@ int rsparse_hip_weighted_sumsq_f64_device(const double* d_X, int rank, int64_t n
                                           void* stream) {
   if (!d_X || !d_out) return fail(RSPARSE_HIP_ERR_INVALID, "X or out is NULL");
   if (rank <= 0 || n < 0) return fail(RSPARSE_HIP_ERR_INVALID, "rank must be positive and n non-negative");
-  int rc = g_w64.ensure();
-  if (rc) return rc;
-  hipError_t e = launch_f64_weighted_sumsq(d_X, rank, n, d_w, d_out, g_w64.partials, (hipStream_t)stream);
-  if (e != hipSuccess) return capi_hip_fail(e, "launch_f64_weighted_sumsq");
-  return RSPARSE_HIP_OK;
+  if (int rc = g_w64.ensure()) return rc;
+  return weighted_sumsq(d_X, rank, n, d_w, d_out, g_w64.scratch(), (hipStream_t)stream);
 }
 
 // the cosine operands of rsparse_hip_similar_items_device from double factors (kernel: wrmf_similar.hip; the fp32 form and
@@ -427,7 +343,7 @@ int rsparse_hip_normalize_items_f64_device(const double* d_V, int n_items, int l
   if (n_items > 0 && (!d_V || !d_Vn32 || !d_Vn64 || !d_flags)) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
   if (n_items == 0) return RSPARSE_HIP_OK;
   hipError_t e = launch_normalize_items(d_V, true, n_items, ld, c0, c1 - c0, d_Vn32, d_Vn64, d_flags, (hipStream_t)stream);
-  if (e != hipSuccess) return capi_hip_fail(e, "launch_normalize_items");
+  if (e != hipSuccess) return hip_fail(e, "launch_normalize_items");
   return RSPARSE_HIP_OK;
 }
 
@@ -436,49 +352,32 @@ int rsparse_hip_values_subtract_mean_f64_device(int64_t n, double* d_x, double* 
   if (mean_out) *mean_out = 0.0;
   if (n == 0) return RSPARSE_HIP_OK;
   if (!d_x) return fail(RSPARSE_HIP_ERR_INVALID, "values is NULL");
-  hipStream_t s = (hipStream_t)stream;
-  int rc = g_w64.ensure();
-  if (rc) return rc;
-  hipError_t e = launch_values_sum(d_x, n, g_w64.partials, g_w64.scalars + 2, s);
-  if (e != hipSuccess) return capi_hip_fail(e, "launch_values_sum");
-  const double inv = 1.0 / (double)n;
-  if ((e = launch_values_subtract_mean(d_x, n, g_w64.scalars + 2, inv, s)) != hipSuccess)
-    return capi_hip_fail(e, "launch_values_subtract_mean");
-  if (d_x_other && (e = launch_values_subtract_mean(d_x_other, n, g_w64.scalars + 2, inv, s)) != hipSuccess)
-    return capi_hip_fail(e, "launch_values_subtract_mean");
-  double sum = 0.0;
-  HIP_TRY(hipMemcpyAsync(&sum, g_w64.scalars + 2, sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (mean_out) *mean_out = sum * inv;
+  if (int rc = g_w64.ensure()) return rc;
+  double mean = 0.0;
+  if (int rc = subtract_mean(d_x, d_x_other, n, g_w64.scratch(), (hipStream_t)stream, &mean)) return rc;
+  if (mean_out) *mean_out = mean;
   return RSPARSE_HIP_OK;
 }
 
 int rsparse_hip_bias_sweep_explicit_f64_device(const rsparse_hip_csc_f64* conf, const double* d_other_bias, double lambda,
                                                int dynamic_lambda, int non_negative, double* d_out, void* stream) {
   if (!conf || !d_other_bias || !d_out) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or bias vector");
-  hipError_t e = launch_bias_sweep(conf->col_ptrs, conf->row_idx, conf->vals, d_other_bias, conf->n_cols, lambda, dynamic_lambda,
-                                   non_negative, d_out, (hipStream_t)stream);
-  if (e != hipSuccess) return capi_hip_fail(e, "launch_bias_sweep");
-  return RSPARSE_HIP_OK;
+  return bias_sweep_explicit(CscView<double>(*conf), d_other_bias, lambda, dynamic_lambda, non_negative, d_out,
+                             (hipStream_t)stream);
 }
 
 int rsparse_hip_bias_prep_implicit_f64_device(const rsparse_hip_csc_f64* conf, int n_other, double lambda, double* d_means,
                                               double* d_adj, void* stream) {
   if (!conf || !d_means || !d_adj) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
-  hipError_t e = launch_bias_implicit_prep(conf->col_ptrs, conf->vals, conf->n_cols, n_other, lambda, d_means, d_adj,
-                                           (hipStream_t)stream);
-  if (e != hipSuccess) return capi_hip_fail(e, "launch_bias_implicit_prep");
-  return RSPARSE_HIP_OK;
+  return bias_prep_implicit(CscView<double>(*conf), n_other, lambda, d_means, d_adj, (hipStream_t)stream);
 }
 
 int rsparse_hip_bias_sweep_implicit_f64_device(const rsparse_hip_csc_f64* conf, const double* d_other_bias, int n_other,
                                                const double* d_other_sum, const double* d_means, const double* d_adj,
                                                int non_negative, double global_bias, double* d_out, void* stream) {
   if (!conf || !d_other_bias || !d_means || !d_adj || !d_out) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or vector");
-  hipError_t e = launch_bias_implicit_sweep(conf->col_ptrs, conf->row_idx, conf->vals, d_other_bias, conf->n_cols, n_other,
-                                            d_other_sum, d_means, d_adj, non_negative, global_bias, d_out, (hipStream_t)stream);
-  if (e != hipSuccess) return capi_hip_fail(e, "launch_bias_implicit_sweep");
-  return RSPARSE_HIP_OK;
+  return bias_sweep_implicit(CscView<double>(*conf), d_other_bias, n_other, d_other_sum, d_means, d_adj, non_negative,
+                             global_bias, d_out, (hipStream_t)stream);
 }
 
 int rsparse_hip_initialize_biases_f64_device(rsparse_hip_csc_f64* c_ui, rsparse_hip_csc_f64* c_iu, double* d_user_bias,
@@ -486,77 +385,16 @@ int rsparse_hip_initialize_biases_f64_device(rsparse_hip_csc_f64* c_ui, rsparse_
                                              int calculate_global_bias, int is_explicit_feedback,
                                              double* global_bias_out, void* stream) {
   if (!c_ui || !c_iu || !d_user_bias || !d_item_bias) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or bias vector");
-  const rsparse_hip_csc_f64& a = *c_ui;   // users x items, columns = items
-  const rsparse_hip_csc_f64& b = *c_iu;   // items x users, columns = users
+  const CscView<double> a(*c_ui), b(*c_iu);   // users x items (columns = items), items x users (columns = users)
   if (a.n_rows != b.n_cols || a.n_cols != b.n_rows || a.nnz != b.nnz)
     return fail(RSPARSE_HIP_ERR_INVALID, "the two matrices are not transposes of each other");
+  if (int rc = g_w64.ensure()) return rc;
   hipStream_t s = (hipStream_t)stream;
-  int rc = g_w64.ensure();
-  if (rc) return rc;
-  const int n_items = a.n_cols, n_users = b.n_cols;
-  double global_bias = 0.0;
-  hipError_t e;
-  if (is_explicit_feedback) {   // wrmf_utils.hpp:32-84
-    if (calculate_global_bias && a.nnz > 0) {   // :41-52: mean of the values, removed from both orientations in place
-      if ((e = launch_values_sum(a.vals, a.nnz, g_w64.partials, g_w64.scalars + 2, s)) != hipSuccess)
-        return capi_hip_fail(e, "launch_values_sum");
-      const double inv = 1.0 / (double)a.nnz;
-      if ((e = launch_values_subtract_mean(a.vals, a.nnz, g_w64.scalars + 2, inv, s)) != hipSuccess ||
-          (e = launch_values_subtract_mean(b.vals, b.nnz, g_w64.scalars + 2, inv, s)) != hipSuccess)
-        return capi_hip_fail(e, "launch_values_subtract_mean");
-      double sum = 0.0;
-      HIP_TRY(hipMemcpyAsync(&sum, g_w64.scalars + 2, sizeof(double), hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      global_bias = sum * inv;
-    }
-    for (int iter = 0; iter < 5; iter++) {       // :54-82
-      if ((e = launch_bias_sweep(a.col_ptrs, a.row_idx, a.vals, d_user_bias, a.n_cols, lambda, dynamic_lambda, non_negative,
-                                 d_item_bias, s)) != hipSuccess ||
-          (e = launch_bias_sweep(b.col_ptrs, b.row_idx, b.vals, d_item_bias, b.n_cols, lambda, dynamic_lambda, non_negative,
-                                 d_user_bias, s)) != hipSuccess)
-        return capi_hip_fail(e, "launch_bias_sweep");
-    }
-    if (global_bias_out) *global_bias_out = global_bias;
-    return RSPARSE_HIP_OK;
-  }
-  // wrmf_utils.hpp:86-165
-  DevBuf stats;   // means / adjustments of both sides (:97-124)
-  HIP_TRY(stats.alloc(((size_t)2 * n_items + (size_t)2 * n_users + 4) * sizeof(double)));
-  double* item_means = stats.as<double>();
-  double* item_adj = item_means + n_items;
-  double* user_means = item_adj + n_items;
-  double* user_adj = user_means + n_users;
-  if ((e = launch_bias_implicit_prep(a.col_ptrs, a.vals, n_items, n_users, lambda, item_means, item_adj, s)) != hipSuccess ||
-      (e = launch_bias_implicit_prep(b.col_ptrs, b.vals, n_users, n_items, lambda, user_means, user_adj, s)) != hipSuccess)
-    return capi_hip_fail(e, "launch_bias_implicit_prep");
-  if (calculate_global_bias) {   // :90-93: sum(x) / (sum(x) + n_users n_items - nnz)
-    if ((e = launch_values_sum(a.vals, a.nnz, g_w64.partials, g_w64.scalars + 2, s)) != hipSuccess)
-      return capi_hip_fail(e, "launch_values_sum");
-    double sum = 0.0;
-    HIP_TRY(hipMemcpyAsync(&sum, g_w64.scalars + 2, sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    global_bias = sum / (sum + (double)n_users * (double)n_items - (double)a.nnz);
-  }
-  if (non_negative) global_bias = std::fmax(0.0, global_bias);
-  if (global_bias_out) *global_bias_out = global_bias;
-  for (int iter = 0; iter < 5; iter++) {   // :130-162
-    const double* usum = nullptr;
-    if (iter > 0) {                        // mean of the user biases of the previous sweep (:131-135)
-      if ((e = launch_values_sum(d_user_bias, n_users, g_w64.partials, g_w64.scalars + 2, s)) != hipSuccess)
-        return capi_hip_fail(e, "launch_values_sum");
-      usum = g_w64.scalars + 2;
-    }
-    if ((e = launch_bias_implicit_sweep(a.col_ptrs, a.row_idx, a.vals, d_user_bias, n_items, n_users, usum, item_means,
-                                        item_adj, non_negative, global_bias, d_item_bias, s)) != hipSuccess)
-      return capi_hip_fail(e, "launch_bias_implicit_sweep");
-    if ((e = launch_values_sum(d_item_bias, n_items, g_w64.partials, g_w64.scalars + 3, s)) != hipSuccess)
-      return capi_hip_fail(e, "launch_values_sum");
-    if ((e = launch_bias_implicit_sweep(b.col_ptrs, b.row_idx, b.vals, d_item_bias, n_users, n_items, g_w64.scalars + 3,
-                                        user_means, user_adj, non_negative, global_bias, d_user_bias, s)) != hipSuccess)
-      return capi_hip_fail(e, "launch_bias_implicit_sweep");
-  }
-  HIP_TRY(hipStreamSynchronize(s));   // `stats` is released on return
-  return RSPARSE_HIP_OK;
+  if (is_explicit_feedback)
+    return initialize_biases_explicit(a, b, d_user_bias, d_item_bias, lambda, dynamic_lambda, non_negative,
+                                      calculate_global_bias, g_w64.scratch(), s, global_bias_out);
+  return initialize_biases_implicit(a, b, d_user_bias, d_item_bias, lambda, non_negative, calculate_global_bias,
+                                    g_w64.scratch(), s, global_bias_out);
 }
 
 int rsparse_hip_als_implicit_double(int n_rows, int n_cols, const int32_t* col_ptrs, const int32_t* row_indices,
@@ -591,36 +429,25 @@ int rsparse_hip_initialize_biases_double(int n_users, int n_items, const int32_t
   const int64_t nnz = csc_p[n_items];
   if (csr_p[n_users] != nnz) return fail(RSPARSE_HIP_ERR_INVALID, "the two matrices are not transposes of each other");
   if (nnz > 0 && (!csc_i || !csc_x || !csr_i || !csr_x)) return fail(RSPARSE_HIP_ERR_INVALID, "NULL index or value array");
-  DevBuf p1, i1, x1, p2, i2, x2, dU, dI;
-  HIP_TRY(p1.alloc(((size_t)n_items + 1) * 4)); HIP_TRY(i1.alloc((size_t)nnz * 4)); HIP_TRY(x1.alloc((size_t)nnz * 8));
-  HIP_TRY(p2.alloc(((size_t)n_users + 1) * 4)); HIP_TRY(i2.alloc((size_t)nnz * 4)); HIP_TRY(x2.alloc((size_t)nnz * 8));
-  HIP_TRY(dU.alloc((size_t)n_users * 8)); HIP_TRY(dI.alloc((size_t)n_items * 8));
-  HIP_TRY(hipMemcpy(p1.p, csc_p, ((size_t)n_items + 1) * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(p2.p, csr_p, ((size_t)n_users + 1) * 4, hipMemcpyHostToDevice));
-  if (nnz) {
-    HIP_TRY(hipMemcpy(i1.p, csc_i, (size_t)nnz * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(x1.p, csc_x, (size_t)nnz * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(i2.p, csr_i, (size_t)nnz * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(x2.p, csr_x, (size_t)nnz * 8, hipMemcpyHostToDevice));
-  }
-  if (n_users) HIP_TRY(hipMemcpy(dU.p, user_bias, (size_t)n_users * 8, hipMemcpyHostToDevice));
-  if (n_items) HIP_TRY(hipMemcpy(dI.p, item_bias, (size_t)n_items * 8, hipMemcpyHostToDevice));
+  DevBuf p1, i1, x1, p2, i2, x2;
+  HIP_TRY(upload_host(p1, csc_p, (size_t)n_items + 1)); HIP_TRY(upload_host(i1, csc_i, (size_t)nnz)); HIP_TRY(upload_host(x1, csc_x, (size_t)nnz));
+  HIP_TRY(upload_host(p2, csr_p, (size_t)n_users + 1)); HIP_TRY(upload_host(i2, csr_i, (size_t)nnz)); HIP_TRY(upload_host(x2, csr_x, (size_t)nnz));
   rsparse_hip_csc_f64 *c_ui = nullptr, *c_iu = nullptr;
   int rc = rsparse_hip_csc_f64_create_device(n_users, n_items, p1.as<int32_t>(), i1.as<int32_t>(), x1.as<double>(), &c_ui);
   if (rc) return rc;
-  struct Guard { rsparse_hip_csc_f64* c; ~Guard() { rsparse_hip_csc_f64_destroy(c); } } g1{c_ui};
+  CscGuardF64 g1{c_ui};
   if ((rc = rsparse_hip_csc_f64_create_device(n_items, n_users, p2.as<int32_t>(), i2.as<int32_t>(), x2.as<double>(), &c_iu)))
     return rc;
-  Guard g2{c_iu};
+  CscGuardF64 g2{c_iu};
   double gb = 0.0;
-  rc = rsparse_hip_initialize_biases_f64_device(c_ui, c_iu, dU.as<double>(), dI.as<double>(), lambda, dynamic_lambda,
-                                                non_negative, calculate_global_bias, is_explicit_feedback, &gb, nullptr);
+  rc = with_device_biases(n_users, n_items, user_bias, item_bias, [&](double* dU, double* dI) {
+    return rsparse_hip_initialize_biases_f64_device(c_ui, c_iu, dU, dI, lambda, dynamic_lambda, non_negative,
+                                                    calculate_global_bias, is_explicit_feedback, &gb, nullptr);
+  });
   if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  if (n_users) HIP_TRY(hipMemcpy(user_bias, dU.p, (size_t)n_users * 8, hipMemcpyDeviceToHost));
-  if (n_items) HIP_TRY(hipMemcpy(item_bias, dI.p, (size_t)n_items * 8, hipMemcpyDeviceToHost));
   if (is_explicit_feedback && calculate_global_bias && nnz) {
-    // the reference removes the global mean from the @x slots of BOTH matrices in place (wrmf_utils.hpp:41-52)
+    // the reference removes the global mean from the @x slots of BOTH matrices in place (wrmf_utils.hpp:41-52): the resident
+    // values are those doubles, so they are downloaded as the device left them
     HIP_TRY(hipMemcpy(csc_x, x1.p, (size_t)nnz * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(csr_x, x2.p, (size_t)nnz * 8, hipMemcpyDeviceToHost));
   }
