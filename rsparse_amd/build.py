@@ -34,6 +34,42 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 EXTRA_FLAGS = {n: ["-mllvm", "-forceattrs-csv-path=" + str(CSRC / "wrmf_chol_mf.attrs.csv"), "-fno-slp-vectorize"] for n in ("wrmf_chol_mf.hip", "wrmf_cg_mf.hip")}
 AUDITED = {"wrmf_chol_mf.hip", "wrmf_cg_mf.hip"}
 REG_LIMIT = {"wrmf_cg_mf.hip": 512}   # (one wave per SIMD by design: 320 accumulator registers per row)
+# Kernels that fit two waves per SIMD only without a spill (the 24-quad team kernel of wrmf_cgq.hip keeps 192 registers of
+# gathered vectors; a spilling form loses 2x): their compilation reports its resource usage and the build fails
+# when one of them spills, uses scratch or passes 256 registers -- another compiler may allocate differently.
+NO_SPILL = {"wrmf_cgq.hip": ("14als_cgq_kernelILi128ELi24ELi4ELi4E",)}
+RESOURCE_FLAG = "-Rpass-analysis=kernel-resource-usage"
+
+
+def resource_violations(remarks, patterns, limit=256):
+    """-> [(mangled name, what)] for the kernels of hipcc's kernel-resource-usage remarks whose name contains one of
+    `patterns` and that spill, use scratch or need more than `limit` vector registers; every pattern must match a kernel"""
+    import re
+    rows, cur = [], None
+    for line in remarks.splitlines():
+        m = re.search(r"remark:\s+(.*?) \[-Rpass", line)
+        if not m:
+            continue
+        t = m.group(1).strip()
+        if t.startswith("Function Name:"):
+            cur = {"name": t.split(":", 1)[1].strip()}
+            rows.append(cur)
+        elif ":" in t and cur is not None:
+            k, v = t.rsplit(":", 1)
+            cur[k.strip()] = v.strip()
+    bad = []
+    for pat in patterns:
+        hit = [r for r in rows if pat in r["name"]]
+        if not hit:
+            bad.append((pat, "no such kernel in the compilation"))
+        for r in hit:
+            regs = int(r.get("VGPRs", "0")) + int(r.get("AGPRs", "0"))
+            for key in ("VGPRs Spill", "ScratchSize [bytes/lane]"):
+                if int(r.get(key, "0")):
+                    bad.append((r["name"], "%s = %s" % (key, r[key])))
+            if regs > limit:
+                bad.append((r["name"], "%d vector registers" % regs))
+    return bad
 
 
 def audit_listing(src, extra, obj):
@@ -90,10 +126,16 @@ def build(force=False, verbose=False, out=None):
         s, o = so
         t0 = time.time()
         extra = EXTRA_FLAGS.get(s.name, [])
-        cmd = ["hipcc", *FLAGS, *extra, "-c", str(s), "-o", str(o)]
+        guard = NO_SPILL.get(s.name)
+        cmd = ["hipcc", *FLAGS, *extra, *([RESOURCE_FLAG] if guard else []), "-c", str(s), "-o", str(o)]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         if r.returncode != 0:
             raise RuntimeError("hipcc failed on %s:\n%s" % (s.name, r.stderr[-6000:]))
+        if guard:
+            bad = resource_violations(r.stderr, guard)
+            if bad:
+                o.unlink()
+                raise RuntimeError("%s: kernels that must not spill do:\n%s" % (s.name, "\n".join("  %s: %s" % b for b in bad)))
         if s.name in AUDITED:
             audit_listing(s, extra, o)
         if verbose:

@@ -170,6 +170,7 @@ int build_schedule(rsparse_hip_csc& m, const int32_t* host_col_ptrs) {
   for (int b = 0; b < 7; b++) d.q_off[b] = plan.off[b];
   for (int b = 0; b < 6; b++) d.q_nnz[b] = plan.nnz[b];
   d.q_pair_first = plan.pair_first; d.q_team4_first = plan.team4_first;
+  d.q_team4_wide_first = plan.team4_wide_first;
   d.q_gt32 = plan.gt32; d.q_gt48 = plan.gt48; d.q_lr_first = plan.lr_first; d.q_n_lr = plan.n_lr;
   d.q_n_chol_long = plan.n_chol_long; d.q_n_nec = plan.n_nec;
   int rc;
@@ -351,6 +352,7 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   for (int b = 0; b < 7; b++) qs.off[b] = d.q_off[b];
   // (the global-bias CG keeps bucket 1 on the 8-wave kernel: no 4-wave launch, no loss slots for one)
   qs.team4_first = (implicit && bias && bias->gbias != 0.f) ? d.q_off[2] : d.q_team4_first;
+  qs.team4_wide_first = (implicit && bias && bias->gbias != 0.f) ? d.q_off[2] : d.q_team4_wide_first;
   qs.pair_wide = cgp_wide_supported(rank, implicit, implicit && bias && bias->gbias != 0.f);
   // round 6, rank 128, implicit conjugate gradient without bias operands: the rows of 513..kCgMfMax non-zeros of the first bucket on
   // the wave-per-row kernel of wrmf_cg_mf.hip, the giant rows (a prefix of the order) on the normal-equation kernel's second lists

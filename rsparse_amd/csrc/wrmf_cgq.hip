@@ -75,6 +75,12 @@ __device__ __forceinline__ float groups_reduce_scatter4(const float a0, const fl
   const auto t = __builtin_amdgcn_permlane32_swap(__float_as_uint(c), __float_as_uint(d), false, false);
   return __uint_as_float(t[0]) + __uint_as_float(t[1]);
 }
+// the lane number, or (ON) a copy of it that the compiler has to take as a new value: see WIDEQ in als_cgq_kernel
+template <bool ON>
+__device__ __forceinline__ int opaque_lane(int l) {
+  if constexpr (ON) asm volatile("" : "+v"(l));
+  return l;
+}
 // ---- dense product on the matrix cores (DMF instantiation: one-wave rows of <= 32 non-zeros at rank 65..128) ----
 // The four rows a workgroup solves side by side share every G v product: G is held in REGISTERS as two fp16 terms
 // (wave w owns rows [32w, 32w + 32) as A operands of v_mfma_f32_16x16x32_f16), the four vectors are published to LDS as
@@ -94,6 +100,8 @@ struct QSmem {
   // cv_lds: resident rows whose gathered vectors take more than 128 registers (20 quads at rank 128) keep the confidences /
   // ratings of the chunk in a third slot, [group][quad], read as one 16-byte broadcast per block of four quads
   static constexpr bool cv_lds = !STREAM && CAPQ * (KP / 16) > 128;
+  // more than 20 quads at rank 128 (the 24-quad team kernel): see WIDEQ in als_cgq_kernel
+  static constexpr bool wideq = !STREAM && CAPQ * (KP / 16) > 160;
   static constexpr size_t tsv_floats = (STREAM && !IMPLICIT) ? 0 : (size_t)WAVES * (cv_lds ? 3 : 2) * CAPQ * 4;
   // streamed rows: the first kStreamPrefixQ quads of every wave (gathered in the first sweep) stay in LDS,
   // so the other sweeps re-gather only the rest of the row
@@ -104,9 +112,10 @@ struct QSmem {
   static constexpr size_t dmf_floats = DMF ? (size_t)WAVES * dmf_ps + (size_t)WAVES * dmf_os : 0;
   // resident rows on teams of more than kIdxPrefetchMaxWpr waves: the next row's indices / values (one per lane) land here
   // by LDS-DMA during the current row's sweeps -- those kernels have no two registers to hold them (KFULL instantiations).
-  // One slot of CAP indices + CAP values per wave; CAP = 80 (the 20-quad team kernel) takes a second, 16-lane DMA per array
+  // One slot of CAP indices + CAP values per wave; CAP = 80 / 96 (the 20- and 24-quad team kernels) takes a second, 16- / 32-lane
+  // DMA per array
   static constexpr size_t pfx_floats =
-      (!STREAM && WPR > kIdxPrefetchMaxWpr && (CAPQ == 16 || CAPQ == 20)) ? (size_t)WAVES * 2 * CAPQ * 4 : 0;
+      (!STREAM && WPR > kIdxPrefetchMaxWpr && (CAPQ == 16 || CAPQ == 20 || CAPQ == 24)) ? (size_t)WAVES * 2 * CAPQ * 4 : 0;
   // cv_lds: the wave's loss sum (a double) and the CG iterate x between the first sweep and the loss are kept here too, not in
   // registers that would live across the sweeps (x is touched once per CG step, the quads four times per sweep)
   static constexpr size_t wl_floats = cv_lds ? (size_t)WAVES * 2 : 0;
@@ -250,6 +259,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
   }
   float* vec = sVec + wv * KP;
   constexpr bool CVLDS = SM::cv_lds;
+  constexpr bool WIDEQ = SM::wideq;   // more than 20 quads at rank 128: see RSP_SLOT_IN / RSP_SLOT_J
+  // ... and the lane number as a value the compiler cannot see through (opaque_lane), taken where a per-lane LDS address is formed
+  // once per row (confidence slots, t-slots): the address is then rebuilt from `lane` there instead of living across the row loop
   float* tacc = sTsv + wv * (CVLDS ? 3 : 2) * CAP;  // resident rows only
   float* tcur = tacc + CAP;
   float* csv = tcur + CAP;   // CVLDS: [4][CAPQ], group g's quad q at g * CAPQ + q
@@ -280,18 +292,25 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
     const int row = have ? rfl(row_c) : 0;
     const int p1 = have ? rfl(p1_c) : 0;
     const int p2 = have ? rfl(p2_c) : 0;
-    {  // issue the loads for the next iterations now; they are consumed at the top of the next iteration
-      int p1_n = 0, p2_n = 0, row_nn = 0;
-      if (it + 1 < rows_per_team && row_index(it + 1) < n_rows) {
-        p1_n = a.col_ptrs[row_n];
-        p2_n = a.col_ptrs[row_n + 1];
-      }
-      if (it + 2 < rows_per_team && row_index(it + 2) < n_rows) row_nn = rows[row_index(it + 2)];
-      row_c = row_n;
-      p1_c = p1_n;
-      p2_c = p2_n;
-      row_n = row_nn;
+    // issue the loads for the next iterations; they are consumed at the top of the next iteration
+    // META_LATE (24 quads, padded rank): not here but behind the first sweep, where x has left the registers -- the two
+    // pointer registers have no room across the gather -- and settled into scalars behind the loss
+    // (a macro, not a lambda: the reference captures reorder the loop's register copies in every instantiation)
+    constexpr bool META_LATE = WIDEQ && !KFULL;
+#define RSP_ADVANCE_META()                                                      \
+    {                                                                           \
+      int p1_n = 0, p2_n = 0, row_nn = 0;                                       \
+      if (it + 1 < rows_per_team && row_index(it + 1) < n_rows) {               \
+        p1_n = a.col_ptrs[row_n];                                               \
+        p2_n = a.col_ptrs[row_n + 1];                                           \
+      }                                                                         \
+      if (it + 2 < rows_per_team && row_index(it + 2) < n_rows) row_nn = rows[row_index(it + 2)]; \
+      row_c = row_n;                                                            \
+      p1_c = p1_n;                                                              \
+      p2_c = p2_n;                                                              \
+      row_n = row_nn;                                                           \
     }
+    if constexpr (!META_LATE) RSP_ADVANCE_META()
     const int cnt = p2 - p1;
     float* yrow = a.Y + (size_t)row * k;
     if (!GB && WPR == 1 && cnt <= 0) {  // empty column -> zeros (wrmf_implicit.hpp:281, wrmf_explicit.hpp:142)
@@ -327,9 +346,10 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
     for (int s2 = 0; s2 < (CVLDS ? 1 : NSL); s2++) cl[s2] = 0.f;
     // CVLDS: slot s of the chunk <- its confidence (0 beyond n), one lane per slot
     auto csv_fill = [&](auto&& conf_of, const int n) {
+      const int ln = opaque_lane<WIDEQ>(lane);
 #pragma unroll
       for (int s2 = 0; s2 < NSL; s2++) {
-        const int sl = lane + 64 * s2;
+        const int sl = ln + 64 * s2;
         if (s2 == 0 || sl < CAP) csv[(sl & 3) * CAPQ + (sl >> 2)] = sl < n ? conf_of(sl) : 0.f;
       }
     };
@@ -363,6 +383,12 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
       }
     };
     int pf_pos = -1;   // streamed rows: chunk the prefetch registers belong to
+    // slot 4 q + g of the chunk against its length n.  WIDEQ (24 quads): written against g alone with a uniform bound, so
+    // that no per-quad lane value exists for the compiler to keep across the row loop (24 hoisted registers spilled)
+    // (macros on QSmem::wideq, not lambdas or the local WIDEQ: a new capture of this generic lambda reorders the code of the
+    //  other instantiations)
+#define RSP_SLOT_IN(q, n) (SM::wideq ? g < (n) - 4 * (q) : 4 * (q) + g < (n))
+#define RSP_SLOT_J(q, n) max(SM::wideq ? min(g, (n) - 1 - 4 * (q)) + 4 * (q) : min(4 * (q) + g, (n) - 1), 0)
     auto gather_q = [&](auto nq_tag, const int base, const int n, const bool from_pf = false) {
       constexpr int NQG = decltype(nq_tag)::value;
       int id[NQG > 0 ? NQG : 1];
@@ -376,9 +402,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         wave_sync();
 #pragma unroll
         for (int q = 0; q < NQG; q++) {
-          const int j = max(min(4 * q + g, n - 1), 0);
+          const int j = RSP_SLOT_J(q, n);
           id[q] = pfxI[j];
-          if constexpr (!CVLDS) cv[q] = (!ZPAD || 4 * q + g < n) ? pfxC[j] : 0.f;
+          if constexpr (!CVLDS) cv[q] = (!ZPAD || RSP_SLOT_IN(q, n)) ? pfxC[j] : 0.f;
         }
         if constexpr (CVLDS) {
           csv_fill([&](int sl) { return pfxC[sl]; }, n);
@@ -396,20 +422,20 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         wave_sync();
 #pragma unroll
         for (int q = 0; q < NQG; q++) {
-          const int j = max(min(4 * q + g, n - 1), 0);
+          const int j = RSP_SLOT_J(q, n);
           id[q] = xi[j];
-          if constexpr (!CVLDS) cv[q] = (!ZPAD || 4 * q + g < n) ? tcur[j] : 0.f;
+          if constexpr (!CVLDS) cv[q] = (!ZPAD || RSP_SLOT_IN(q, n)) ? tcur[j] : 0.f;
         }
         if constexpr (TSAVE) cl[0] = lane < n ? pf_c : 0.f;
         wave_sync();
       } else {
 #pragma unroll
         for (int q = 0; q < NQG; q++) {
-          const int j = max(min(4 * q + g, n - 1), 0);
+          const int j = RSP_SLOT_J(q, n);
           id[q] = a.row_idx[base + j];
           if constexpr (!CVLDS) {
             const float c = a.vals[base + j];
-            cv[q] = (!ZPAD || 4 * q + g < n) ? c : 0.f;
+            cv[q] = (!ZPAD || RSP_SLOT_IN(q, n)) ? c : 0.f;
           }
         }
         if constexpr (CVLDS) {
@@ -421,12 +447,13 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
           for (int s2 = 0; s2 < NSL; s2++) cl[s2] = lane + 64 * s2 < n ? a.vals[base + lane + 64 * s2] : 0.f;
         }
       }
+      const int ig = (SM::wideq && !KFULL) ? (opaque_lane<true>(lane) & 15) : i;   // (the clamped piece offsets: per row, not per launch)
 #pragma unroll
       for (int q = 0; q < NQG; q++) {
-        const float* src = (!ZPAD || 4 * q + g < n) ? a.X + (size_t)id[q] * k : a.zero_row;
+        const float* src = (!ZPAD || RSP_SLOT_IN(q, n)) ? a.X + (size_t)id[q] * k : a.zero_row;
 #pragma unroll
         for (int b = 0; b < NV; b++) {
-          const int off = b * 16 * VW + i * VW;
+          const int off = b * 16 * VW + ig * VW;
           if constexpr (KFULL) {
             const piece_t pc = *reinterpret_cast<const piece_t*>(src + off);
             const float* pf = reinterpret_cast<const float*>(&pc);
@@ -441,6 +468,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         }
       }
     };
+#undef RSP_SLOT_IN
+#undef RSP_SLOT_J
     auto gather = [&](const int base, const int n, const bool from_pf = false) {
       gather_q(std::integral_constant<int, CAPQ>{}, base, n, from_pf);
     };
@@ -706,14 +735,15 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
             // loss from t_acc = X_nnz^T y built up by the sweeps (the vectors are not touched again)
             wave_sync();
             float esum = 0.f;
+            const int ln = opaque_lane<WIDEQ>(lane);
 #pragma unroll
             for (int s2 = 0; s2 < NSL; s2++) {
-              const int sl = NSL == 1 ? (lane & (CAP - 1)) : min(lane + 64 * s2, CAP - 1);
+              const int sl = NSL == 1 ? (lane & (CAP - 1)) : min(ln + 64 * s2, CAP - 1);
               const float t = tacc[sl];
               const float clv = CVLDS ? csv[(sl & 3) * CAPQ + (sl >> 2)] : cl[s2];
               const float d = IMPLICIT ? ltgt - t : clv - t;
               const float e = IMPLICIT ? clv * d * d : d * d;
-              esum += lane + 64 * s2 < ccnt ? e : 0.f;
+              esum += ln + 64 * s2 < ccnt ? e : 0.f;
             }
             lacc = row16_sum(esum);  // groups_sum below finishes the wave sum
           }
@@ -887,6 +917,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         }
       }
     }
+    if constexpr (META_LATE) RSP_ADVANCE_META()
+#undef RSP_ADVANCE_META
     if constexpr (IDXPF && STREAM == 0) {
       // the next row's pointers were requested at the top of this iteration and have arrived by now
       if (it + 1 < rows_per_team && row_index(it + 1) < n_rows) {
@@ -929,9 +961,10 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
           if (s2 == itc) alph[s2] = alpha;
         if constexpr (TSAVE) {  // t_acc += alpha * t_cur  (x += alpha p  =>  X_nnz^T x += alpha X_nnz^T p)
           wave_sync();
+          const int ln = opaque_lane<WIDEQ>(lane);
 #pragma unroll
           for (int s2 = 0; s2 < NSL; s2++) {
-            const int sl = NSL == 1 ? (lane & (CAP - 1)) : lane + 64 * s2;
+            const int sl = NSL == 1 ? (lane & (CAP - 1)) : ln + 64 * s2;
             if (CAP % 64 == 0 || sl < CAP) tacc[sl] = fmaf(alpha, tcur[sl], tacc[sl]);
           }
           wave_sync();
@@ -976,6 +1009,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
     }
     float rl = 0.f;
     sweep(x, 2, ap, rl, live);
+    if constexpr (META_LATE) p1_c = rfl(p1_c), p2_c = rfl(p2_c);
     if constexpr (DMAPF) wait_vm<0>();   // the announced row's indices have long landed; nothing of this wave's is in flight after this
     if constexpr (IDXPF && STREAM == 0) {
       // settle the prefetch registers HERE (their loads were issued three sweeps ago): left to the next row's first use, the
@@ -1012,9 +1046,10 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
 // (waves per workgroup W, waves per row WPR, resident quads per wave, streamed?):
 //   bucket 0  streamed rows (longer than 512 non-zeros): teams of 8 waves, 512-thread workgroups
 //   bucket 1  257..512 non-zeros: resident on 8-wave teams -- at rank 97..128 (no global bias) only the rows of
-//             kTeam4Max + 1..512; the rows up to kTeam4Max run in a second launch on 4-wave teams of 20 quads per wave
-//             (256-thread workgroups, two per CU, like bucket 2).  The split is a position in the order
-//             (QSchedule::team4_first), not a bucket of its own.  Rank 33..64 runs the whole bucket on 4-wave teams
+//             kTeam4WideMax + 1..512; the rows of kTeam4Max + 1..kTeam4WideMax run in a second launch on 4-wave teams of 24
+//             quads per wave, the rows up to kTeam4Max in a third on 4-wave teams of 20 quads per wave (256-thread
+//             workgroups, two per CU, like bucket 2).  The splits are positions in the order (QSchedule::team4_wide_first
+//             <= team4_first), not buckets of their own.  Rank 33..64 runs the whole bucket on 4-wave teams
 //             (geometry 1); ranks <= 32 and the global-bias variant keep it on the 8-wave kernel
 //   bucket 2.. 129..256 / 65..128 / 33..64 non-zeros: resident on teams of 4 / 2 / 1 waves of 256-thread
 //             workgroups (two per CU: they run out of phase, one gathers while the other sweeps)
@@ -1036,9 +1071,17 @@ constexpr int cfg_of_kp(int KP) { return KP == 64 ? 1 : 0; }
 // the second launch of bucket 1 at rank 97..128: rows of up to kTeam4Max = 4 waves x 20 quads x 4 non-zeros
 constexpr int kTeam4Waves = 4, kTeam4Capq = 20;
 static_assert(kTeam4Max == kTeam4Waves * kTeam4Capq * 4, "wrmf_internal.h's split and the kernel's capacity");
+// the launch in front of it: rows of kTeam4Max + 1..kTeam4WideMax = 4 waves x 24 quads x 4 non-zeros.  24 quads are 192 of a
+// wave's 256 registers: the kernel (WIDEQ) holds no per-lane value across the row loop that it can rebuild from the lane number
+constexpr int kTeam4WideCapq = 24;
+static_assert(kTeam4WideMax == kTeam4Waves * kTeam4WideCapq * 4, "wrmf_schedule.h's split and the wide kernel's capacity");
+static_assert(kTeam4Max < kTeam4WideMax && kTeam4WideMax < 512, "the 4-wave launches take bucket 1's rows from its short end");
+// two workgroups per CU (160 KB of LDS, allocated in 2 KB steps)
+static_assert(QSmem<128, kTeam4WideCapq, kTeam4Waves, kTeam4Waves, 0, true>::bytes <= 80 * 1024, "the wide team kernel's LDS");
 constexpr bool team4_split(int KP, bool GB) { return KP == 128 && !GB; }
-// position in the order where bucket 1's 4-wave launch starts (= the bucket's end when there is none)
+// positions in the order where bucket 1's 4-wave launches start (= the bucket's end when there is none)
 int team4_first(const QSchedule& q) { return std::min(std::max(q.team4_first, q.off[1]), q.off[2]); }
+int team4_wide_first(const QSchedule& q) { return std::min(std::max(q.team4_wide_first, q.off[1]), team4_first(q)); }
 
 template <int KP, int WAVES, int CAPQ, int WPR, int STREAM, bool IMPLICIT, bool GB, int DMF = 0, bool KFULL = false>
 hipError_t launch_bucket(const AlsArgs& a, const int32_t* rows, int n_rows, int grid, size_t slot0, hipStream_t s,
@@ -1105,9 +1148,10 @@ size_t bucket_slots(const QSchedule& q, int b, int k, bool implicit) {
   if (d.wpr <= 0) return 0;
   if (d.stream && ne_supported(k)) return (size_t)(q.ne.entries + q.ne.nsplit) + (size_t)(q.mf_n > 0 ? cg_mf_loss_slots(q.mf_n) : 0);
   const int rows = q.off[b + 1] - q.off[b];
-  if (b == 1 && padded_rank(k) == 128) {   // (the global-bias variant gets team4_first = off[2] from its caller)
-    const int split = team4_first(q);
-    return (size_t)cgq_bucket_grid(split - q.off[b], b, cfg) * d.waves + (size_t)cgq_team4_grid(q.off[b + 1] - split) * kTeam4Waves;
+  if (b == 1 && padded_rank(k) == 128) {   // (the global-bias variant gets both positions = off[2] from its caller)
+    const int wide = team4_wide_first(q), split = team4_first(q);
+    return (size_t)cgq_bucket_grid(wide - q.off[b], b, cfg) * d.waves + (size_t)cgq_team4_wide_grid(split - wide) * kTeam4Waves +
+           (size_t)cgq_team4_grid(q.off[b + 1] - split) * kTeam4Waves;
   }
   if (b == kNB - 1 && rows > 0 && cgp_supported(k, implicit)) {
     const int split = std::min(std::max(q.pair_first, q.off[b]), q.off[b + 1]);
@@ -1174,16 +1218,22 @@ hipError_t launch_all(const AlsArgs& a, const QSchedule& q, hipStream_t s, hipEv
         } else if constexpr (D.stream && KP > 32) {   /* ranks above 32 always take the branch above */     \
           return hipErrorInvalidValue;                                                                      \
         } else if constexpr (B == 1 && team4_split(KP, GB)) {                                              \
-          /* bucket 1 in two launches: rows of kTeam4Max + 1..512 non-zeros on 8-wave teams, the shorter ones on 4-wave teams */ \
-          const int first = q.off[B], split = team4_first(q);                                               \
-          const int n_main = split - first, n_t4 = q.off[B + 1] - split;                                    \
-          const int g_main = cgq_bucket_grid(n_main, B, CFG);                                               \
+          /* bucket 1 in three launches: rows of kTeam4WideMax + 1..512 non-zeros on 8-wave teams, the shorter ones on 4-wave */ \
+          /* teams of 24 (kTeam4Max + 1..kTeam4WideMax) and 20 quads per wave; an empty one is skipped and owns no loss slot */ \
+          const int first = q.off[B], wide = team4_wide_first(q), split = team4_first(q);                   \
+          const int n_main = wide - first, n_w4 = split - wide, n_t4 = q.off[B + 1] - split;                \
+          const int g_main = cgq_bucket_grid(n_main, B, CFG), g_w4 = cgq_team4_wide_grid(n_w4);             \
           if ((err = launch_bucket<KP, D.waves, D.capq, D.wpr, D.stream, IMPLICIT, GB>(a, q.order + first, n_main, g_main, slot, \
                                                                                   bs, ev ? ev + B : nullptr)) != hipSuccess) \
             return err;                                                                                     \
-          if ((err = launch_bucket<KP, kTeam4Waves, kTeam4Capq, kTeam4Waves, 0, IMPLICIT, GB>(              \
-                   a, q.order + split, n_t4, cgq_team4_grid(n_t4), slot + (size_t)g_main * D.waves, bs,     \
+          if ((err = launch_bucket<KP, kTeam4Waves, kTeam4WideCapq, kTeam4Waves, 0, IMPLICIT, GB>(          \
+                   a, q.order + wide, n_w4, g_w4, slot + (size_t)g_main * D.waves, bs,                      \
                    n_main > 0 ? nullptr : (ev ? ev + B : nullptr))) != hipSuccess)                          \
+            return err;                                                                                     \
+          if ((err = launch_bucket<KP, kTeam4Waves, kTeam4Capq, kTeam4Waves, 0, IMPLICIT, GB>(              \
+                   a, q.order + split, n_t4, cgq_team4_grid(n_t4),                                          \
+                   slot + (size_t)g_main * D.waves + (size_t)g_w4 * kTeam4Waves, bs,                        \
+                   n_main + n_w4 > 0 ? nullptr : (ev ? ev + B : nullptr))) != hipSuccess)                   \
             return err;                                                                                     \
         } else if (B == kNB - 1 && cgp_supported(a.k, IMPLICIT)) {                    \
           /* the last bucket in two launches: rows of 17..32 non-zeros two per wave in 32 slots (q.pair_wide) or one per */ \
@@ -1263,6 +1313,7 @@ int cgq_bucket_grid(int n_rows, int b, int cfg) {
 
 // bucket 1's 4-wave launch: one team per workgroup, the team kernels' quota
 int cgq_team4_grid(int n_rows) { return n_rows <= 0 ? 0 : team_grid(n_rows, 1, 32); }
+int cgq_team4_wide_grid(int n_rows) { return cgq_team4_grid(n_rows); }
 
 int cgq_bucket_of(int len, int cfg) {  // last (smallest-team) bucket whose capacity holds the row
   int best = 0;

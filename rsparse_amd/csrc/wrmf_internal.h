@@ -53,6 +53,7 @@ struct DevCSC {
   int q_cfg = 0;
   int q_pair_first = 0;   // position in q_order of the first row with at most 16 non-zeros (wrmf_cgp.hip: two rows per wave)
   int q_team4_first = 0;  // ... of the first row with at most kTeam4Max non-zeros (bucket 1's 4-wave launch at rank 97..128)
+  int q_team4_wide_first = 0;  // ... with at most kTeam4WideMax non-zeros (bucket 1's wide 4-wave launch in front of it)
   int64_t q_nnz[6] = {0, 0, 0, 0, 0, 0};
   const int64_t* q_stream_off = nullptr;  // prefix sums of the streamed bucket's row lengths (device)
   int q_n_chol_long = 0;   // rows of more than kCholLongLen non-zeros (a prefix of q_order)
@@ -154,6 +155,7 @@ struct QSchedule {
   int off[7];
   int pair_first;   // see DevCSC::q_pair_first
   int team4_first;  // see DevCSC::q_team4_first; = off[2] when bucket 1 runs on the 8-wave kernel alone (global bias)
+  int team4_wide_first;  // see DevCSC::q_team4_wide_first; = off[2] in the same case
   bool pair_wide;   // the last bucket's rows of 17..32 non-zeros two per wave as well (cgp_wide_supported), else one per wave
   int cfg;  // geometry the schedule was built for (see wrmf_cgq.hip kBuckets)
   NeListSet ne;   // the list set of this call's normal-equation launch (one of DevCSC::q_ne / q_ne1 / q_nec)
@@ -170,6 +172,8 @@ int cgq_bucket_stream(int cfg, int b);
 int cgq_bucket_grid(int n_rows, int bucket, int cfg);
 // bucket 1 at rank 97..128: the rows of up to kTeam4Max (wrmf_schedule.h) non-zeros on 4-wave teams of 20 quads per wave (wrmf_cgq.hip)
 int cgq_team4_grid(int n_rows);
+// ... and the rows of kTeam4Max + 1..kTeam4WideMax on 4-wave teams of 24 quads per wave
+int cgq_team4_wide_grid(int n_rows);
 int cgq_bucket_of(int len, int cfg);
 size_t cgq_loss_slots(const QSchedule& q, int k, bool implicit);
 // the rows of at most 16 non-zeros of the last bucket, two per wave (wrmf_cgp.hip): rank 65..128, implicit feedback;

@@ -132,6 +132,7 @@ bool plan_schedule(const int32_t* col_ptrs, int n_cols, int cus, int (*bucket_of
     if (len > kCgMfMax) out.n_nec += cnt;
     if (len > 16) out.pair_first += cnt;
     if (len > kTeam4Max) out.team4_first += cnt;
+    if (len > kTeam4WideMax) out.team4_wide_first += cnt;
     if (len > 32) out.gt32 += cnt;
     if (len > 48) out.gt48 += cnt;
     if (len > kCholLrMax) out.lr_first += cnt;

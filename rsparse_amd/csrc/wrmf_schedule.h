@@ -11,6 +11,7 @@ namespace rsparse_hip {
 // Row lengths (non-zeros) at which the launchers cut the order; what each launcher does with its rows: wrmf_internal.h
 constexpr int kTileNnz = 32;         // tile capacity (non-zeros per wave tile) the CG kernels are instantiated for
 constexpr int kTeam4Max = 320;       // bucket 1 at rank 97..128: the rows of up to kTeam4Max non-zeros on 4-wave teams of 20 quads per wave (wrmf_cgq.hip)
+constexpr int kTeam4WideMax = 384;   // ... and the rows of kTeam4Max + 1..kTeam4WideMax on 4-wave teams of 24 quads per wave
 constexpr int kCholLrMax = 64;       // rows of 1..kCholLrMax non-zeros, implicit feedback, rank 98..128: the low-rank form of the exact solve (wrmf_chol_lr.hip)
 constexpr int kCholLongLen = 4096;   // Cholesky: rows beyond it go to a second launch that sums the rank-one updates in two levels (wrmf_chol.hip)
 constexpr int kCgMfMax = 16384;      // rank 128, implicit CG: the rows of kNeMinLen + 1 .. kCgMfMax non-zeros one wave per row (wrmf_cg_mf.hip), the rows beyond on wrmf_ne.hip
@@ -50,6 +51,7 @@ struct SchedulePlan {
   // positions in `order` (it is longest first: the rows of at most L non-zeros are a suffix)
   int pair_first = 0;     // first row of at most 16 non-zeros
   int team4_first = 0;    // ... of at most kTeam4Max
+  int team4_wide_first = 0;   // ... of at most kTeam4WideMax (<= team4_first)
   int gt32 = 0, gt48 = 0;   // rows of more than 32 / 48 non-zeros
   int lr_first = 0, n_lr = 0;   // rows of 1..kCholLrMax non-zeros: order[lr_first, lr_first + n_lr)
   int n_chol_long = 0;    // rows of more than kCholLongLen non-zeros
