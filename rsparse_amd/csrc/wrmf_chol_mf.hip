@@ -610,6 +610,24 @@ __device__ __forceinline__ void als_chol_mf_body(const AlsArgs& a, const int32_t
 
 // the kernels by fixed names (wrmf_chol_mf.attrs.csv): implicit feedback with every confidence >= 1 (one operand set), implicit
 // feedback in general, explicit feedback; each at rank 128 and at the ranks 65..127 (padded coordinates masked)
+//
+// Which of the six run_half_iteration (wrmf_capi.cpp) can reach, and the test that does (tests/test_exact_solver_classes.py
+// unless another file is named):
+//   _implicit               rank 128, and every rank 65..127 -- implicit fits below 128 always run on copies padded to 128
+//                           (pad_to_128: zero_padding_is_neutral() is true for implicit feedback).
+//                           ::test_wave_per_row_exact_kernel_every_row_length_class[implicit]; test_hip_parity.py at ranks 100 / 128
+//   _implicit_any           the same with a confidence below 1.  ...[implicit_below_one]; its `bad` path:
+//                           ::test_every_cholesky_kernel_hands_indefinite_rows_to_the_general_solver at ranks 128 and 100
+//   _explicit               rank 128, and the ranks 65..127 with lambda > 0 (padded to 128).  ...[explicit_*]; with lambda = 0:
+//                           ::test_explicit_lambda_zero_above_rank_64_keeps_the_true_rank[128-False]
+//   _explicit_padded        explicit feedback, lambda = 0, rank 68, 72 .. 124: the padding is off, the call keeps its rank (also a
+//                           biased fit whose rank - 1 is one of these).  ::test_explicit_lambda_zero_above_rank_64_keeps_the_true_rank
+//                           at 68 / 100 / 124 -- the only caller of the KFULL = false body
+//   _implicit_padded, _implicit_any_padded
+//                           NOT reachable: launch_als_chol_mf picks them for a.k != 128 (or an X that is not 16-byte aligned),
+//                           but chol_mf needs !bias and use_cgq() -- 16-byte alignment --, and without bias operands an implicit call
+//                           of rank 65..127 has been padded to 128 before it gets here.  Kept until build.py's audit and the attrs csv
+//                           that name them are changed with them.
 #define MF_KERNEL(NAME, IMP, SYM, KF)                                                                                      \
   extern "C" __global__ __launch_bounds__(64, MF_WAVES) __attribute__((amdgpu_num_vgpr(MF_NUM_VGPR))) void NAME(            \
       rsparse_hip::AlsArgs a, const int32_t* __restrict__ rows, int n_rows, int loss_slot0) {                               \

@@ -565,8 +565,11 @@ def test_cholesky_falls_back_to_the_general_solver(k):
     bound = np.maximum(1e-4, 20.0 * cond * 6e-8)                                  # fp32 elimination: ~ cond x eps
     worst = int(np.argmax(err / bound))
     assert np.all(err <= bound), (worst, float(err[worst]), float(cond[worst]))
-    ok = cond < 1e3
-    assert abs(loss - lref) <= 1e-3 * abs(lref) or not ok.all()
+    # the loss, every row's term counted once (by the kernel that solved the row or by the fallback that re-solved it): the yardstick
+    # is the fp32 oracle's own loss on the same systems
+    Y32 = Y0.copy(order="F")
+    l32 = O.als_implicit(p, i, x, X, Y32, np.asfortranarray(G, dtype=np.float32), 0.1, 0, 3)
+    assert abs(loss - lref) <= max(1e-4 * abs(lref), 3.0 * abs(l32 - lref)), (loss, lref, l32)
     # the device-resident layer reports the count like the reference's warning
     be = HipBackend()
     dev = be.device
