@@ -432,6 +432,43 @@ int rsparse_hip_ranking_metrics_device(const int32_t* d_predictions, int n_users
                                        double* d_ndcg_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * pointwise predictions: the model's values at given (row, column) pairs -- cpp_make_sparse_approximation
+ * (src/utils.cpp:4-56, src/RcppExports.cpp)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Per stored position t of a CSR pattern (d_p: n_rows + 1, d_j: 0-based columns), row(t) the row that owns it:
+ *   d_scores[t] = add + sum_c d_U[row(t), c] * d_V[d_j[t], c]        d_U: n_rows x r, d_V: n_cols x r, both row-major.
+ * Accumulated in double whatever the factors' type: with fp32 factors every product is exact in double and only the sum rounds
+ * (the product find_top_product orders by, R/utils.R:35-36); `add` (a global bias) goes on once at the end
+ * (src/matrix_top_product.cpp:98-99).  With d_actual (one double per stored position) every row also gets
+ *   d_sse[row] = sum (score - actual)^2,   d_sae[row] = sum |score - actual|     over its stored positions, 0 for an empty row.
+ * Each of d_scores (p[n_rows] doubles), d_sse, d_sae (n_rows doubles) may be NULL, not all three; d_actual is read only for the
+ * sums.  The reduction order is fixed and there are no atomics: a repeated call returns the same bits.
+ * Enqueued on `stream` without synchronisation, with one exception: without d_scores the scores live in the library's grow-only
+ * workspace (8 bytes per stored position), and to size it the call reads p[n_rows] back, which waits for `stream`.
+ * A valid p (from 0, non-decreasing) and j in [0, n_cols) are preconditions, not checked (they live on the device), as for
+ * rsparse_hip_ranking_metrics_device; a position whose column is outside [0, n_cols) gets NaN and nothing outside d_U and d_V is
+ * read for it.  j need not be sorted and may repeat.
+ * Every output NULL, NULL among d_U, d_V, d_p, d_j, d_sse / d_sae without d_actual, n_rows < 0, n_cols < 0, r < 1 -> ERR_INVALID;
+ * r > RSPARSE_HIP_MAX_RANK (both element types: there is no per-row system to fit) -> ERR_UNSUPPORTED; n_rows == 0 -> OK, no
+ * device is touched.  A pattern without stored positions scores nothing and zeroes d_sse / d_sae. */
+int rsparse_hip_score_pairs_device(const float* d_U, const float* d_V, int n_rows, int n_cols, int r, const int32_t* d_p,
+                                   const int32_t* d_j, double add, const double* d_actual, double* d_scores, double* d_sse,
+                                   double* d_sae, void* stream);
+int rsparse_hip_score_pairs_f64_device(const double* d_U, const double* d_V, int n_rows, int n_cols, int r, const int32_t* d_p,
+                                       const int32_t* d_j, double add, const double* d_actual, double* d_scores, double* d_sse,
+                                       double* d_sae, void* stream);
+
+/* host form, the drop-in for cpp_make_sparse_approximation: the values of X^T Y at the stored positions of a template matrix of
+ * n_rows x n_cols, given by its slots p and idx (dgRMatrix p / j with sparse_matrix_type = 2 (CSR), dgCMatrix p / i with 1
+ * (CSC), as the reference numbers them).  X: rank x n_rows, Y: rank x n_cols, column-major doubles; values_out: one double per
+ * stored position, in the template's own order.  Runs the f64 kernel (for CSC the two operands swap roles).
+ * Another sparse_matrix_type, p[0] != 0, a decreasing p, an index outside the matrix, NULL where needed, negative dimensions,
+ * rank < 1 -> ERR_INVALID, before a device is touched; rank > RSPARSE_HIP_MAX_RANK -> ERR_UNSUPPORTED. */
+int rsparse_hip_sparse_approximation(int n_rows, int n_cols, const int32_t* p, const int32_t* idx, int sparse_matrix_type,
+                                     const double* X, const double* Y, int rank, double* values_out);
+
+/* ------------------------------------------------------------------------------------------------
  * (3) fp64 device layer: als_implicit<double> / als_explicit<double> with the data resident in HBM
  * ---------------------------------------------------------------------------------------------- */
 

@@ -134,3 +134,28 @@ def als_explicit(x, X, Y, cnt_X, lambda_, n_threads, solver_code, cg_steps, dyna
                   int(n_threads), int(solver_code), int(cg_steps), int(bool(dynamic_lambda)),
                   int(bool(with_user_item_bias)), int(bool(is_bias_last_row)), ctypes.addressof(loss)))
     return loss.value
+
+
+def sparse_approximation(template, X, Y):
+    """`cpp_make_sparse_approximation` (src/utils.cpp:4-56): the values of t(X) %*% Y at the stored positions of `template`
+    (a scipy CSR or CSC matrix of ncol(X) x ncol(Y); another format is taken as CSR), in the template's own order -- one
+    float64 per stored position.  X (rank x nrow) and Y (rank x ncol): column-major float64."""
+    import scipy.sparse as sp
+    lib = _lib.load()
+    if not sp.issparse(template):
+        raise TypeError("template must be a scipy sparse matrix")
+    if template.format not in ("csr", "csc"):
+        template = template.tocsr()
+    kind = 2 if template.format == "csr" else 1          # CSC = 1, CSR = 2, as the reference numbers them
+    _f_contig(X, np.float64, "X")
+    _f_contig(Y, np.float64, "Y")
+    n_rows, n_cols = template.shape
+    rank = X.shape[0]
+    if X.shape[1] != n_rows or Y.shape != (rank, n_cols):
+        raise ValueError("X must be rank x nrow(template) and Y rank x ncol(template)")
+    p = np.ascontiguousarray(template.indptr, dtype=np.int32)
+    idx = np.ascontiguousarray(template.indices, dtype=np.int32)
+    out = np.empty(idx.size, dtype=np.float64)
+    _lib.check(lib.rsparse_hip_sparse_approximation(int(n_rows), int(n_cols), _vp(p), _vp(idx) if idx.size else None, kind,
+                                                    _vp(X), _vp(Y), int(rank), _vp(out) if idx.size else None))
+    return out

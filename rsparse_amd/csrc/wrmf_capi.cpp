@@ -63,6 +63,7 @@ struct Workspace {
   GrowBuf<float> wide_lu{all};
   GrowBuf<int> met_buf{all};      // ranking metrics (wrmf_metrics.hip): count + list of the users whose idcg takes the long-row launch
   GrowBuf<char> sim_buf{all};     // item-to-item similarity (wrmf_similar.hip): a batch's gathered queries and self-exclusion slots
+  GrowBuf<double> score_buf{all};   // pointwise predictions (wrmf_score.hip): the scores of a call that asks for the error sums only
   GrowBuf<float> mf_G{all};       // wrmf_chol_mf.hip at rank 65..127: XtX padded to 128 x 128
   GrowBuf<float> pad_buf{all};    // ranks that are not a multiple of 4: the padded copies of X, Y, XtX, rhs_init (run_half_iteration)
   int device = -1;
@@ -1398,6 +1399,19 @@ int rsparse_hip_ranking_metrics(const int32_t* pred, int n_users, int k, const i
   if (ap_out) HIP_TRY(hipMemcpy(ap_out, dAp.p, (size_t)n_users * 8, hipMemcpyDeviceToHost));
   if (ndcg_out) HIP_TRY(hipMemcpy(ndcg_out, dNdcg.p, (size_t)n_users * 8, hipMemcpyDeviceToHost));
   return RSPARSE_HIP_OK;
+}
+
+// `_f64_device` and the host form rsparse_hip_sparse_approximation: wrmf_f64_capi.cpp
+int rsparse_hip_score_pairs_device(const float* d_U, const float* d_V, int n_rows, int n_cols, int r, const int32_t* d_p,
+                                   const int32_t* d_j, double add, const double* d_actual, double* d_scores, double* d_sse,
+                                   double* d_sae, void* stream) {
+  return score_pairs_device(d_U, d_V, n_rows, n_cols, r, d_p, d_j, add, d_actual, d_scores, d_sse, d_sae, (hipStream_t)stream,
+                            [](size_t n, double*& buf) {
+                              if (int rc = g_ws.ensure_device()) return rc;
+                              HIP_TRY(g_ws.score_buf.ensure(n));
+                              buf = g_ws.score_buf;
+                              return (int)RSPARSE_HIP_OK;
+                            });
 }
 
 int rsparse_hip_take_numeric_failures(int64_t* unresolved_out, int64_t* fallback_out) {

@@ -194,6 +194,39 @@ hipError_t upload_host(DevBuf& b, const T* src, size_t n) {   // n host elements
   return (e != hipSuccess || !n) ? e : hipMemcpy(b.p, src, n * sizeof(T), hipMemcpyHostToDevice);
 }
 
+// rsparse_hip_score_pairs_device / _f64_device (kernels: wrmf_score.hip).  Handed in:
+//   int workspace(size_t n, double*& buf)    makes sure of n doubles of the side's grow-only workspace
+// which is only asked for the sums without the scores: the scores then live there, and their count, p[n_rows], has to be
+// read back first (the one case in which this call waits for the stream).
+template <class T, class Workspace>
+int score_pairs_device(const T* d_U, const T* d_V, int n_rows, int n_cols, int r, const int32_t* d_p, const int32_t* d_j, double add,
+                       const double* d_actual, double* d_scores, double* d_sse, double* d_sae, hipStream_t s, Workspace workspace) {
+  if (!d_scores && !d_sse && !d_sae) return fail(RSPARSE_HIP_ERR_INVALID, "scores, sse and sae are all NULL");
+  if (!d_U || !d_V || !d_p || !d_j) return fail(RSPARSE_HIP_ERR_INVALID, "U, V or the pattern (p, j) is NULL");
+  if ((d_sse || d_sae) && !d_actual) return fail(RSPARSE_HIP_ERR_INVALID, "the error sums need the values: actual is NULL");
+  if (n_rows < 0 || n_cols < 0 || r < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, n_cols < 0 or r < 1)");
+  if (r > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "r > 256 is not on the device path");
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  const bool sums = d_sse || d_sae;
+  double* sc = d_scores;
+  if (!sc) {
+    int32_t nnz = 0;
+    HIP_TRY(hipMemcpyAsync(&nnz, d_p + n_rows, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (nnz <= 0) {   // nothing stored: every row's sums are 0
+      if (d_sse) HIP_TRY(hipMemsetAsync(d_sse, 0, (size_t)n_rows * sizeof(double), s));
+      if (d_sae) HIP_TRY(hipMemsetAsync(d_sae, 0, (size_t)n_rows * sizeof(double), s));
+      return RSPARSE_HIP_OK;
+    }
+    if (int rc = workspace((size_t)nnz, sc)) return rc;
+  }
+  hipError_t e = launch_score_pairs(d_U, d_V, n_rows, n_cols, r, d_p, d_j, add, sc, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_score_pairs");
+  if (sums && (e = launch_score_error_sums(sc, d_actual, d_p, n_rows, d_sse, d_sae, s)) != hipSuccess)
+    return hip_fail(e, "launch_score_error_sums");
+  return RSPARSE_HIP_OK;
+}
+
 // Shared body of the stateless drop-ins (als_implicit / als_explicit, src/wrmf_implicit.cpp:5-26, src/wrmf_explicit.cpp:5-26)
 // once the caller has validated what its side validates and made its resident matrix (nnz non-zeros).  Handed in:
 //   int scratch(SumScratch& w)    makes sure of the side's workspace and gives its sum scratch as it is now

@@ -78,6 +78,7 @@ struct WorkspaceF64 {
   GrowBuf<double> m2{all};
   GrowBuf<double> longs{all};      // the long rows' partial sums and vectors (f64_long_scratch_doubles)
   GrowBuf<double> repack{all};     // explicit feedback with biases, conjugate gradient: X', Y', shifted ratings
+  GrowBuf<double> score{all};      // pointwise predictions (wrmf_score.hip): the scores of a call that asks for the error sums only
   int device = -1;
   int ensure() {
     int dev = 0;
@@ -344,6 +345,54 @@ int rsparse_hip_normalize_items_f64_device(const double* d_V, int n_items, int l
   if (n_items == 0) return RSPARSE_HIP_OK;
   hipError_t e = launch_normalize_items(d_V, true, n_items, ld, c0, c1 - c0, d_Vn32, d_Vn64, d_flags, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "launch_normalize_items");
+  return RSPARSE_HIP_OK;
+}
+
+// pointwise predictions from double factors (kernels: wrmf_score.hip; the fp32 form: wrmf_capi.cpp)
+int rsparse_hip_score_pairs_f64_device(const double* d_U, const double* d_V, int n_rows, int n_cols, int r, const int32_t* d_p,
+                                       const int32_t* d_j, double add, const double* d_actual, double* d_scores, double* d_sse,
+                                       double* d_sae, void* stream) {
+  return score_pairs_device(d_U, d_V, n_rows, n_cols, r, d_p, d_j, add, d_actual, d_scores, d_sse, d_sae, (hipStream_t)stream,
+                            [](size_t n, double*& buf) {
+                              if (int rc = g_w64.ensure()) return rc;
+                              HIP_TRY(g_w64.score.ensure(n));
+                              buf = g_w64.score;
+                              return (int)RSPARSE_HIP_OK;
+                            });
+}
+
+// cpp_make_sparse_approximation (src/utils.cpp:4-56): the values of X^T Y at the stored positions of a template.  CSR: position t
+// of row i holds X[:, i] . Y[:, idx[t]]; CSC: position t of column c holds Y[:, c] . X[:, idx[t]] -- the two operands swap roles.
+int rsparse_hip_sparse_approximation(int n_rows, int n_cols, const int32_t* p, const int32_t* idx, int sparse_matrix_type,
+                                     const double* X, const double* Y, int rank, double* values_out) {
+  if (sparse_matrix_type != 1 && sparse_matrix_type != 2)
+    return fail(RSPARSE_HIP_ERR_INVALID, "sparse_matrix_type should be CSC = 1 or CSR = 2");
+  if (n_rows < 0 || n_cols < 0 || rank < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, n_cols < 0 or rank < 1)");
+  if (rank > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 256 is not on the device path");
+  if (!p || !X || !Y) return fail(RSPARSE_HIP_ERR_INVALID, "p, X or Y is NULL");
+  const bool csr = sparse_matrix_type == 2;
+  const int n_outer = csr ? n_rows : n_cols, n_inner = csr ? n_cols : n_rows;
+  if (p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "p[0] != 0");
+  for (int i = 0; i < n_outer; i++)
+    if (p[i + 1] < p[i]) return fail(RSPARSE_HIP_ERR_INVALID, "p decreases");
+  const size_t nnz = (size_t)p[n_outer];
+  if (nnz && (!idx || !values_out)) return fail(RSPARSE_HIP_ERR_INVALID, "the indices or values_out is NULL");
+  for (size_t t = 0; t < nnz; t++)
+    if (idx[t] < 0 || idx[t] >= n_inner) return fail(RSPARSE_HIP_ERR_INVALID, "an index is outside the matrix");
+  if (nnz == 0) return RSPARSE_HIP_OK;
+  const double* outer = csr ? X : Y;
+  const double* inner = csr ? Y : X;
+  DevBuf dO, dI, dP, dJ, dS;
+  HIP_TRY(upload_host(dO, outer, (size_t)rank * n_outer));
+  HIP_TRY(upload_host(dI, inner, (size_t)rank * n_inner));
+  HIP_TRY(upload_host(dP, p, (size_t)n_outer + 1));
+  HIP_TRY(upload_host(dJ, idx, nnz));
+  HIP_TRY(dS.alloc(nnz * sizeof(double)));
+  int rc = rsparse_hip_score_pairs_f64_device(dO.as<double>(), dI.as<double>(), n_outer, n_inner, rank, dP.as<int32_t>(),
+                                              dJ.as<int32_t>(), 0.0, nullptr, dS.as<double>(), nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(values_out, dS.p, nnz * sizeof(double), hipMemcpyDeviceToHost));
   return RSPARSE_HIP_OK;
 }
 

@@ -334,6 +334,15 @@ hipError_t launch_top_product_large_f64(const float* U32, const float* V32, cons
 hipError_t launch_ranking_metrics(const int32_t* pred, int n_users, int k, const int32_t* P, const int32_t* J, const double* X,
                                   double* ap_out, double* ndcg_out, int* long_buf, hipStream_t s);
 
+// pointwise predictions at a CSR pattern (wrmf_score.hip), T = float or double, 1 <= r <= 256: scores[t] = add + U[row(t)] .
+// V[J[t]] in double for every stored position t < P[n_rows] (the count stays on the device: a capped grid strides over it); then
+// the squared / absolute error sums per row of given scores against `actual` (sse / sae: either may be null)
+template <class T>
+hipError_t launch_score_pairs(const T* U, const T* V, int n_rows, int n_cols, int r, const int32_t* P, const int32_t* J, double add,
+                              double* scores, hipStream_t s);
+hipError_t launch_score_error_sums(const double* scores, const double* actual, const int32_t* P, int n_rows, double* sse,
+                                   double* sae, hipStream_t s);
+
 // item-to-item cosine similarity (wrmf_similar.hip): the operands of the top-k path above.
 // launch_normalize_items: V (fp32, or fp64 when f64) n_items x ld row-major, columns [c0, c0 + r), 1 <= r <= 256 ->
 // Vn64 / Vn32 (n_items x r, compact) with unit rows, flags[item] = 1 and a row of zeros where the sum of squares is zero or

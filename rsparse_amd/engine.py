@@ -369,6 +369,36 @@ class HipBackend:
             None if ap is None else ap.data_ptr(), None if ndcg is None else ndcg.data_ptr(), self._stream()))
         return ap, ndcg
 
+    def score_pairs(self, U, V, p, j, add=0.0, actual=None, want_scores=True):
+        """the model's values at the stored positions of a CSR pattern (p, j: int32 on the device) whose rows are the rows of U
+        (n x rank) and whose columns index V (n_item x rank): score[t] = add + U[row(t)] . V[j[t]], accumulated in double from
+        the factors as they are -- fp32 or fp64, no replica (wrmf_score.hip).  With `actual` (float64, one per stored position)
+        also the rows' sums of squared and of absolute errors.  -> (scores, sse, sae): float64 on the device, scores one per
+        position, sse / sae one per row, None for what was not asked for."""
+        if actual is None and not want_scores:
+            raise ValueError("score_pairs: nothing asked for (no actual and want_scores=False)")
+        if U.dtype != V.dtype:
+            U = U.to(V.dtype)
+        assert V.dtype in (torch.float32, torch.float64) and U.shape[1] == V.shape[1]
+        assert p.dtype == torch.int32 and j.dtype == torch.int32
+        U, V = U.contiguous(), V.contiguous()
+        n, rank = U.shape
+        nnz = int(j.numel())
+        dev = U.device
+        scores = torch.empty(nnz, dtype=torch.float64, device=dev) if want_scores else None
+        sse = torch.zeros(n, dtype=torch.float64, device=dev) if actual is not None else None
+        sae = torch.zeros(n, dtype=torch.float64, device=dev) if actual is not None else None
+        if n == 0 or nnz == 0:   # (nothing stored: no scores, and every row's sums are zero)
+            return scores, sse, sae
+        if actual is not None:
+            assert actual.dtype == torch.float64 and actual.numel() == nnz
+            actual = actual.contiguous()
+        fn = self.lib.rsparse_hip_score_pairs_f64_device if V.dtype == torch.float64 else self.lib.rsparse_hip_score_pairs_device
+        _lib.check(fn(U.data_ptr(), V.data_ptr(), n, int(V.shape[0]), rank, p.data_ptr(), j.data_ptr(), float(add),
+                      None if actual is None else actual.data_ptr(), None if scores is None else scores.data_ptr(),
+                      None if sse is None else sse.data_ptr(), None if sae is None else sae.data_ptr(), self._stream()))
+        return scores, sse, sae
+
     def _v32(self, V):
         """the fp32 replica of a factor matrix the fp64 layer holds (kept until the matrix changes: ADVICE r04 -- `predict` of
         one user paid an n_item x rank conversion per call)"""

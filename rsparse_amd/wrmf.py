@@ -580,6 +580,87 @@ class WRMF:
                 out[name] = v.cpu().numpy()
         return out
 
+    def _score_device(self, x, pattern, actual, want_scores):
+        """the device part of `score` / `evaluate_values`: the embeddings of the rows of x (as `predict` gets them), then this
+        rank's block of rows of `pattern` (canonical CSR, n x n_item) scored against the item factors.  -> (scores, sse, sae)
+        of the block, on the device, as the backend's `score_pairs` returns them."""
+        be = self._backend()
+        emb = self._transform_device(x)             # (n, rank), complete on every rank
+        a, b, _ = self._my_rows(x)
+        mine = pattern[a:b]
+        p, j = be.to_device(mine.indptr, torch.int32), be.to_device(mine.indices, torch.int32)
+        act = be.to_device(mine.data, torch.float64) if actual else None
+        # with user/item biases the augmented coordinates carry them (user: [1, latent, user_bias], item: [item_bias, latent,
+        # 1]): the whole rank + 2 vectors are multiplied -- `similar_items`, by contrast, cuts them out
+        fn = be.score_pairs if hasattr(be, "score_pairs") else self._score_pairs_host
+        return fn(emb[a:b], self._V, p, j, float(self.global_bias), act, want_scores)
+
+    @staticmethod
+    def _score_pairs_host(U, V, p, j, add=0.0, actual=None, want_scores=True):
+        """`score_pairs` for a backend without it (the CPU stand-in of the tests), in plain torch double ops: the same values
+        up to the order of the sums"""
+        n = U.shape[0]
+        rows = torch.repeat_interleave(torch.arange(n, device=U.device), torch.diff(p.to(torch.int64)))
+        sc = (U.to(torch.float64)[rows] * V.to(torch.float64)[j.to(torch.int64)]).sum(dim=1) + add
+        sse = sae = None
+        if actual is not None:
+            d = sc - actual
+            sse = torch.zeros(n, dtype=torch.float64, device=U.device).index_add_(0, rows, d * d)
+            sae = torch.zeros(n, dtype=torch.float64, device=U.device).index_add_(0, rows, d.abs())
+        return (sc if want_scores else None), sse, sae
+
+    def _pairs_pattern(self, x, pairs, what):
+        """x as CSR and `pairs` as canonical CSR (sorted columns, duplicates merged, stored zeros kept), shapes checked"""
+        if self._V is None:
+            raise RuntimeError("model is not fitted")
+        x = sp.csr_matrix(x, dtype=np.float64)
+        n_item = self._V.shape[0]
+        if x.shape[1] != n_item:
+            raise ValueError("ncol(x) == ncol(self$components) is not TRUE")
+        if not sp.issparse(pairs):
+            raise TypeError("'%s' should be a 'sparseMatrix'" % what)
+        if pairs.shape != (x.shape[0], n_item):
+            raise ValueError("%s must have the shape of x" % what)
+        from .metrics import canonical_actual
+        return x, canonical_actual(pairs, x.shape[0])
+
+    def score(self, x, pairs):
+        """What the model predicts at given (user, item) cells: the embeddings of the rows of `x` by `transform`, as in
+        `predict`, then `u . v + global_bias` at every stored position of `pairs` (n x n_item, any sparse format; its values are
+        ignored, stored zeros are positions too) on the device.  Returns a scipy CSR matrix with the pattern of `pairs`
+        (columns sorted, duplicates merged) and the predictions as values, in the model's `precision`.  With user/item biases
+        the prediction includes them.  The reference's primitive: cpp_make_sparse_approximation (src/utils.cpp:4-56).  Under
+        torch.distributed every rank scores the block of rows it transforms."""
+        x, pat = self._pairs_pattern(x, pairs, "pairs")
+        sc, _, _ = self._score_device(x, pat, False, True)
+        ws, me = self._dist()
+        if ws > 1:
+            bounds = [(int(pat.indptr[a]), int(pat.indptr[b])) for a, b in self._row_bounds]
+            sc = self._share_rows(sc, bounds, int(pat.nnz))
+        return sp.csr_matrix((sc.cpu().numpy().astype(self._np_dtype()), pat.indices, pat.indptr), shape=pat.shape)
+
+    def evaluate_values(self, x, actual, per_user=False):
+        """Error of the predictions against held-out VALUES (ratings): {"rmse", "mae", "n"} over all stored entries of `actual`
+        (n x n_item sparse; stored zeros count), with the embeddings of the rows of `x` as in `score`.  The per-row error sums
+        are computed on the device in double with a fixed order and the totals are their sums: a call repeats bit for bit, and
+        no per-entry value leaves the device.  per_user=True adds "rmse_per_user" / "mae_per_user", float64 vectors of n, NaN
+        for a row without entries.  rmse / mae are NaN when nothing is stored."""
+        x, act = self._pairs_pattern(x, actual, "actual")
+        _, sse, sae = self._score_device(x, act, True, False)
+        ws, me = self._dist()
+        n_new = x.shape[0]
+        if ws > 1:
+            sse, sae = self._share_rows(sse, self._row_bounds, n_new), self._share_rows(sae, self._row_bounds, n_new)
+        n = int(act.nnz)
+        tot2, tot1 = float(torch.sum(sse)), float(torch.sum(sae))
+        out = {"rmse": float(np.sqrt(tot2 / n)) if n else float("nan"), "mae": tot1 / n if n else float("nan"), "n": n}
+        if per_user:
+            cnt = np.diff(act.indptr).astype(np.float64)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                out["rmse_per_user"] = np.sqrt(sse.cpu().numpy() / cnt)
+                out["mae_per_user"] = sae.cpu().numpy() / cnt
+        return out
+
     def similar_items(self, items=None, k=10, items_exclude=(), exclude_self=True):
         """R/MatrixFactorizationRecommender.R:79-116 (`get_similar_items`: cosine similarity on the L2-normalised item
         embeddings), for a batch of query items at once: `items` = 0-based item ids (any integer sequence, repeats allowed;
