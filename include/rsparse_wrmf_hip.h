@@ -432,6 +432,60 @@ int rsparse_hip_ranking_metrics_device(const int32_t* d_predictions, int n_users
                                        double* d_ndcg_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * full-ranking metrics: where the held-out items stand among ALL items -- the expected percentile rank of
+ * Hu, Koren and Volinsky (the measure of the method's own paper), AUC and MRR off the same per-item ranks
+ * ---------------------------------------------------------------------------------------------- */
+
+/* For user u the ADMISSIBLE set A_u is the items outside the user's not_recommend row and outside exclude; n_adm = |A_u|.
+ * Scores are the fp32 scores of the large-k `$predict` path (exact fp32 product on the matrix cores), compared through their
+ * order-preserving keys: -0 and +0 are one score; a global bias shifts every score alike and plays no part; non-finite factors
+ * are undefined here as in `$predict`.  For a stored entry (u, h) of `actual` (CSR slots p / j, j strictly ascending within a row;
+ * stored zeros are entries):
+ *   above = #{j in A_u : s_j > s_h},     tied = #{j in A_u, j != h : s_j == s_h};
+ *   h not in A_u (or outside 0..n_items-1): the entry is INADMISSIBLE, above = tied = -1, and it takes no part in any sum.
+ * The midrank is r_h = above + tied / 2 (0-based).  Per user, with P the admissible entries, w_h the stored values and sums over
+ * the admissible entries:
+ *   pct_h = r_h / (n_adm - 1)                                   (NaN when n_adm <= 1)
+ *   mpr   = sum w_h pct_h / sum w_h                             (NaN when sum w_h == 0 or P == 0; the expected percentile rank)
+ *   auc   = 1 - (sum r_h - P (P - 1) / 2) / (P (n_adm - P))     (NaN when P == 0 or n_adm == P; the pairs between two held-out
+ *                                                                items add exactly P (P - 1) / 2 to sum r_h whatever their order)
+ *   mrr   = 1 / (1 + min r_h)                                   (NaN when P == 0)
+ *
+ * rsparse_hip_held_out_ranks_device: d_U n_users x rank, d_V n_items x rank, row-major fp32 (a double model passes its fp32
+ * replica, as for the nominating pass of `$predict`); d_not_recommend_p / _j as rsparse_hip_top_product_device (NULL = none),
+ * d_exclude0 sorted 0-based; d_above / d_tied: int32, one per stored entry of actual; d_n_adm: int32, one per user.  Users run in
+ * chunks whose key matrix (chunk x round_up(n_items, 4) words) stays within 2 GiB of the library's grow-only workspace, at most
+ * 32768; max_chunk_users > 0 lowers the chunk (0: the plan).  A held-out row is counted RSPARSE_HIP_RANKS_BATCH entries at a
+ * time.  Integer atomics only: a repeated call returns the same bits.  Enqueued on `stream`, no synchronisation.
+ * NULL where needed, negative dimensions, rank < 1, max_chunk_users < 0 -> ERR_INVALID; rank > RSPARSE_HIP_MAX_RANK ->
+ * ERR_UNSUPPORTED; n_users == 0 -> OK, no device is touched.  A valid p is a precondition, as for
+ * rsparse_hip_ranking_metrics_device. */
+#define RSPARSE_HIP_RANKS_BATCH 1024
+int rsparse_hip_held_out_ranks_device(const float* d_U, const float* d_V, int n_users, int n_items, int rank,
+                                      const int32_t* d_not_recommend_p, const int32_t* d_not_recommend_j,
+                                      const int32_t* d_exclude0, int n_exclude, const int32_t* d_actual_p,
+                                      const int32_t* d_actual_j, int max_chunk_users, int32_t* d_above, int32_t* d_tied,
+                                      int32_t* d_n_adm, void* stream);
+
+/* The per-user numbers from those counts, one wave per user, double arithmetic in a fixed order (per lane over its positions,
+ * then a butterfly over the wave): d_mpr, d_auc, d_mrr (n_users doubles) and d_sums (n_users x 3 row-major: sum w, sum w pct, P
+ * -- what the data-set numbers are summed from).  Any output may be NULL, not all four; d_actual_x (the weights) is read for
+ * d_mpr and d_sums only.  NULL where needed, n_users < 0 -> ERR_INVALID; n_users == 0 -> OK. */
+int rsparse_hip_rank_summary_device(int n_users, const int32_t* d_actual_p, const double* d_actual_x, const int32_t* d_above,
+                                    const int32_t* d_tied, const int32_t* d_n_adm, double* d_mpr, double* d_auc, double* d_mrr,
+                                    double* d_sums, void* stream);
+
+/* host form, both steps: x (nr x rank) and y (rank x nc) column-major doubles and not_recommend as rsparse_hip_top_product takes
+ * them (converted to fp32: the scores are the fp32 ones), exclude 1-based (out-of-range entries are ignored); actual as dgRMatrix
+ * slots.  above / tied (one int32 per stored entry), n_adm (nr int32), mpr / auc / mrr (nr doubles), sums (nr x 3 row-major): any
+ * may be NULL, not all.  Besides the checks above: actual_p[0] != 0, a decreasing p, j not strictly ascending within a row ->
+ * ERR_INVALID, before a device is touched. */
+int rsparse_hip_held_out_ranks(const double* x, const double* y, int nr, int nc, int rank, const int32_t* not_recommend_p,
+                               const int32_t* not_recommend_j, const int32_t* exclude, int n_exclude, const int32_t* actual_p,
+                               const int32_t* actual_j, const double* actual_x, int32_t* above, int32_t* tied, int32_t* n_adm,
+                               double* mpr, double* auc, double* mrr, double* sums);
+
+/* ------------------------------------------------------------------------------------------------
  * pointwise predictions: the model's values at given (row, column) pairs -- cpp_make_sparse_approximation
  * (src/utils.cpp:4-56, src/RcppExports.cpp)
  * ---------------------------------------------------------------------------------------------- */

@@ -12,6 +12,7 @@ LIB_PATH = Path(os.environ.get("RSPARSE_HIP_LIB", Path(__file__).resolve().paren
 
 OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_RUNTIME, ERR_NUMERIC = 0, 1, 2, 3, 4
 SOLVER_CHOLESKY, SOLVER_CG, SOLVER_NNLS = 0, 1, 2
+RANKS_BATCH = 1024   # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that the rank count takes at a time
 
 _c_int, _c_uint, _c_dbl, _c_i64 = ctypes.c_int, ctypes.c_uint, ctypes.c_double, ctypes.c_int64
 _vp = ctypes.c_void_p
@@ -74,6 +75,11 @@ SIGNATURES = {
     "rsparse_hip_similar_items": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp]),
     "rsparse_hip_ranking_metrics": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
     "rsparse_hip_ranking_metrics_device": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_held_out_ranks_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _c_int, _vp, _vp,
+                                                   _vp, _vp]),
+    "rsparse_hip_rank_summary_device": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_held_out_ranks": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _vp]),
     "rsparse_hip_score_pairs_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_dbl, _vp, _vp, _vp, _vp, _vp]),
     "rsparse_hip_score_pairs_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_dbl, _vp, _vp, _vp, _vp, _vp]),
     "rsparse_hip_sparse_approximation": (_c_int, [_c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_int, _vp]),

@@ -1401,6 +1401,136 @@ int rsparse_hip_ranking_metrics(const int32_t* pred, int n_users, int k, const i
   return RSPARSE_HIP_OK;
 }
 
+namespace {
+// the arguments both forms of rsparse_hip_held_out_ranks check before anything else
+int held_out_ranks_args(const void* U, const void* V, int n_users, int n_items, int rank, int n_exclude, const void* excl,
+                        const void* act_p, const void* act_j, int max_chunk_users) {
+  if (n_users < 0 || n_items < 0 || rank < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0, n_items < 0 or rank < 1)");
+  if (max_chunk_users < 0) return fail(RSPARSE_HIP_ERR_INVALID, "max_chunk_users < 0");
+  if (!U || !V || !act_p || !act_j) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or actual (p, j)");
+  if (n_exclude < 0 || (n_exclude > 0 && !excl)) return fail(RSPARSE_HIP_ERR_INVALID, "bad exclude");
+  if (rank > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 256 is not on the device path");
+  return RSPARSE_HIP_OK;
+}
+int rank_summary_args(int n_users, const void* act_p, const void* act_x, const void* above, const void* tied, const void* n_adm,
+                      const void* mpr, const void* auc, const void* mrr, const void* sums) {
+  if (!mpr && !auc && !mrr && !sums) return fail(RSPARSE_HIP_ERR_INVALID, "mpr, auc, mrr and sums are all NULL");
+  if (n_users < 0) return fail(RSPARSE_HIP_ERR_INVALID, "n_users < 0");
+  if (!act_p || !above || !tied || !n_adm) return fail(RSPARSE_HIP_ERR_INVALID, "actual_p, above, tied or n_adm is NULL");
+  if ((mpr || sums) && !act_x) return fail(RSPARSE_HIP_ERR_INVALID, "mpr and sums need the weights: actual_x is NULL");
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+
+int rsparse_hip_held_out_ranks_device(const float* d_U, const float* d_V, int n_users, int n_items, int rank, const int32_t* d_nr_p,
+                                      const int32_t* d_nr_j, const int32_t* d_excl0, int n_exclude, const int32_t* d_act_p,
+                                      const int32_t* d_act_j, int max_chunk_users, int32_t* d_above, int32_t* d_tied,
+                                      int32_t* d_n_adm, void* stream) {
+  int rc = held_out_ranks_args(d_U, d_V, n_users, n_items, rank, n_exclude, d_excl0, d_act_p, d_act_j, max_chunk_users);
+  if (rc) return rc;
+  if (!d_above || !d_tied || !d_n_adm) return fail(RSPARSE_HIP_ERR_INVALID, "above, tied or n_adm is NULL");
+  if (n_users == 0) return RSPARSE_HIP_OK;
+  if ((rc = g_ws.ensure_device())) return rc;
+  // the key matrix of a chunk of users lives where the large-k path keeps its own (wrmf_topk_large.hip)
+  HIP_TRY(g_ws.pad_buf.ensure(held_out_ranks_ws_floats(n_users, n_items, max_chunk_users)));
+  hipError_t e = launch_held_out_ranks(d_U, d_V, n_users, n_items, rank, (d_nr_p && d_nr_j) ? d_nr_p : nullptr, d_nr_j, d_excl0,
+                                       n_exclude, d_act_p, d_act_j, max_chunk_users, d_above, d_tied, d_n_adm, (hipStream_t)stream,
+                                       g_ws.pad_buf);
+  if (e != hipSuccess) return hip_fail(e, "launch_held_out_ranks");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_rank_summary_device(int n_users, const int32_t* d_act_p, const double* d_act_x, const int32_t* d_above,
+                                    const int32_t* d_tied, const int32_t* d_n_adm, double* d_mpr, double* d_auc, double* d_mrr,
+                                    double* d_sums, void* stream) {
+  int rc = rank_summary_args(n_users, d_act_p, d_act_x, d_above, d_tied, d_n_adm, d_mpr, d_auc, d_mrr, d_sums);
+  if (rc || n_users == 0) return rc;
+  hipError_t e = launch_rank_summary(n_users, d_act_p, (d_mpr || d_sums) ? d_act_x : nullptr, d_above, d_tied, d_n_adm, d_mpr, d_auc,
+                                     d_mrr, d_sums, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_rank_summary");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_held_out_ranks(const double* x, const double* y, int nr, int nc, int rank, const int32_t* nr_p, const int32_t* nr_j,
+                               const int32_t* exclude, int n_exclude, const int32_t* p, const int32_t* j, const double* ax,
+                               int32_t* above, int32_t* tied, int32_t* n_adm, double* mpr, double* auc, double* mrr, double* sums) {
+  int rc = held_out_ranks_args(x, y, nr, nc, rank, n_exclude, exclude, p, j, 0);
+  if (rc) return rc;
+  if (!above && !tied && !n_adm && !mpr && !auc && !mrr && !sums) return fail(RSPARSE_HIP_ERR_INVALID, "every output is NULL");
+  if ((mpr || sums) && !ax) return fail(RSPARSE_HIP_ERR_INVALID, "mpr and sums need the weights: actual_x is NULL");
+  // the dgRMatrix slots: p from 0, non-decreasing; j strictly ascending within a row
+  if (p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "actual_p[0] != 0");
+  for (int u = 0; u < nr; u++) {
+    if (p[u + 1] < p[u]) return fail(RSPARSE_HIP_ERR_INVALID, "actual_p decreases");
+    for (int32_t e = p[u] + 1; e < p[u + 1]; e++)
+      if (j[e] <= j[e - 1]) return fail(RSPARSE_HIP_ERR_INVALID, "actual_j is not strictly ascending within a row");
+  }
+  if (nr == 0) return RSPARSE_HIP_OK;
+  const size_t nnz = (size_t)p[nr];
+  // x is nr x rank column-major -> row-major fp32; y (rank x nc column-major) already has item vectors contiguous
+  std::vector<float> U((size_t)nr * rank), V((size_t)nc * rank);
+  for (int u = 0; u < nr; u++)
+    for (int r = 0; r < rank; r++) U[(size_t)u * rank + r] = (float)x[(size_t)r * nr + u];
+  for (size_t e = 0; e < V.size(); e++) V[e] = (float)y[e];
+  std::vector<int32_t> ex;
+  for (int e = 0; e < n_exclude; e++)
+    if (exclude[e] >= 1 && exclude[e] <= nc) ex.push_back(exclude[e] - 1);   // R indices are 1-based
+  std::sort(ex.begin(), ex.end());
+  ex.erase(std::unique(ex.begin(), ex.end()), ex.end());
+  const int64_t nr_nnz = nr_p ? (int64_t)nr_p[nr] : 0;
+  const bool filter = nr_nnz > 0 && nr_j;
+  const bool summary = mpr || auc || mrr || sums;
+  DevBuf dU, dV, dNP, dNJ, dE, dP, dJ, dX, dA, dT, dN, dM;
+  HIP_TRY(dU.alloc(U.size() * 4));
+  HIP_TRY(dV.alloc(V.size() * 4));
+  HIP_TRY(dP.alloc(((size_t)nr + 1) * 4));
+  HIP_TRY(dJ.alloc(nnz * 4));
+  HIP_TRY(dA.alloc(nnz * 4));
+  HIP_TRY(dT.alloc(nnz * 4));
+  HIP_TRY(dN.alloc((size_t)nr * 4));
+  HIP_TRY(hipMemcpy(dU.p, U.data(), U.size() * 4, hipMemcpyHostToDevice));
+  if (!V.empty()) HIP_TRY(hipMemcpy(dV.p, V.data(), V.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dP.p, p, ((size_t)nr + 1) * 4, hipMemcpyHostToDevice));
+  if (nnz) HIP_TRY(hipMemcpy(dJ.p, j, nnz * 4, hipMemcpyHostToDevice));
+  if (filter) {
+    HIP_TRY(dNP.alloc(((size_t)nr + 1) * 4));
+    HIP_TRY(dNJ.alloc((size_t)nr_nnz * 4));
+    HIP_TRY(hipMemcpy(dNP.p, nr_p, ((size_t)nr + 1) * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dNJ.p, nr_j, (size_t)nr_nnz * 4, hipMemcpyHostToDevice));
+  }
+  if (!ex.empty()) {
+    HIP_TRY(dE.alloc(ex.size() * 4));
+    HIP_TRY(hipMemcpy(dE.p, ex.data(), ex.size() * 4, hipMemcpyHostToDevice));
+  }
+  rc = rsparse_hip_held_out_ranks_device(dU.as<float>(), dV.as<float>(), nr, nc, rank, filter ? dNP.as<int32_t>() : nullptr,
+                                         filter ? dNJ.as<int32_t>() : nullptr, ex.empty() ? nullptr : dE.as<int32_t>(), (int)ex.size(),
+                                         dP.as<int32_t>(), dJ.as<int32_t>(), 0, dA.as<int32_t>(), dT.as<int32_t>(), dN.as<int32_t>(),
+                                         nullptr);
+  if (rc) return rc;
+  double* dm = nullptr;   // mpr, auc, mrr (nr each), sums (3 nr)
+  if (summary) {
+    HIP_TRY(dM.alloc((size_t)nr * 6 * 8));
+    dm = dM.as<double>();
+    if (mpr || sums) {
+      HIP_TRY(dX.alloc(nnz * 8));
+      if (nnz) HIP_TRY(hipMemcpy(dX.p, ax, nnz * 8, hipMemcpyHostToDevice));
+    }
+    rc = rsparse_hip_rank_summary_device(nr, dP.as<int32_t>(), (mpr || sums) ? dX.as<double>() : nullptr, dA.as<int32_t>(),
+                                         dT.as<int32_t>(), dN.as<int32_t>(), mpr ? dm : nullptr, auc ? dm + nr : nullptr,
+                                         mrr ? dm + 2 * (size_t)nr : nullptr, sums ? dm + 3 * (size_t)nr : nullptr, nullptr);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  if (above && nnz) HIP_TRY(hipMemcpy(above, dA.p, nnz * 4, hipMemcpyDeviceToHost));
+  if (tied && nnz) HIP_TRY(hipMemcpy(tied, dT.p, nnz * 4, hipMemcpyDeviceToHost));
+  if (n_adm) HIP_TRY(hipMemcpy(n_adm, dN.p, (size_t)nr * 4, hipMemcpyDeviceToHost));
+  if (mpr) HIP_TRY(hipMemcpy(mpr, dm, (size_t)nr * 8, hipMemcpyDeviceToHost));
+  if (auc) HIP_TRY(hipMemcpy(auc, dm + nr, (size_t)nr * 8, hipMemcpyDeviceToHost));
+  if (mrr) HIP_TRY(hipMemcpy(mrr, dm + 2 * (size_t)nr, (size_t)nr * 8, hipMemcpyDeviceToHost));
+  if (sums) HIP_TRY(hipMemcpy(sums, dm + 3 * (size_t)nr, (size_t)nr * 3 * 8, hipMemcpyDeviceToHost));
+  return RSPARSE_HIP_OK;
+}
+
 // `_f64_device` and the host form rsparse_hip_sparse_approximation: wrmf_f64_capi.cpp
 int rsparse_hip_score_pairs_device(const float* d_U, const float* d_V, int n_rows, int n_cols, int r, const int32_t* d_p,
                                    const int32_t* d_j, double add, const double* d_actual, double* d_scores, double* d_sse,

@@ -328,6 +328,24 @@ hipError_t launch_top_product_large_f64(const float* U32, const float* V32, cons
                                         int n_items, int rank, int topk, int kc, const int32_t* nr_ptr, const int32_t* nr_idx,
                                         const int32_t* excl, int n_excl, double glob_mean, int32_t* res, double* scores,
                                         hipStream_t s, float* ws);
+// its first two stages: the keys of U V^T for nu users (rows of `ld` words, ld % 4 == 0, rank <= 256 as above), and key 0 on every
+// user's not_recommend row (nr_ptr: the nu + 1 slots of these users, absolute positions into nr_idx; nullable) and on `excl`
+hipError_t launch_topl_score(const float* U, const float* V, int nu, int n_items, int rank, unsigned* keys, size_t ld, hipStream_t s);
+hipError_t launch_topl_mask(unsigned* keys, size_t ld, int n_items, int nu, const int32_t* nr_ptr, const int32_t* nr_idx,
+                            const int32_t* excl, int n_excl, hipStream_t s);
+
+// full-ranking counts over that key matrix (wrmf_ranks.hip): per stored entry of `actual` (act_ptr / act_idx: CSR slots) the
+// admissible items scored above it and tied with it (-1, -1 for an inadmissible entry), per user the admissible items.
+// ws: held_out_ranks_ws_floats(...) floats (chunk_users: users per chunk; max_chunk_users > 0 caps it).  Then the per-user
+// numbers from the counts: mpr, auc, mrr (n_users doubles) and sums (n_users x 3: sum w, sum w pct, P), each nullable; act_x is
+// read for mpr and sums only.
+size_t held_out_ranks_ws_floats(int n_users, int n_items, int max_chunk_users, int* chunk_users = nullptr);
+hipError_t launch_held_out_ranks(const float* U, const float* V, int n_users, int n_items, int rank, const int32_t* nr_ptr,
+                                 const int32_t* nr_idx, const int32_t* excl, int n_excl, const int32_t* act_ptr,
+                                 const int32_t* act_idx, int max_chunk_users, int32_t* above, int32_t* tied, int32_t* n_adm,
+                                 hipStream_t s, float* ws);
+hipError_t launch_rank_summary(int n_users, const int32_t* act_ptr, const double* act_x, const int32_t* above, const int32_t* tied,
+                               const int32_t* n_adm, double* mpr, double* auc, double* mrr, double* sums, hipStream_t s);
 
 // ranking metrics ap@k / ndcg@k of row-major 1-based lists (wrmf_metrics.hip).  X may be null when ndcg_out is; either output may
 // be null, not both.  long_buf: n_users + 1 ints of scratch (a count and the users whose idcg takes the long-row launch).

@@ -653,6 +653,17 @@ hipError_t launch_large_t(const float* U32, const float* V32, const TF* U, const
 
 }  // namespace
 
+// the first two stages on their own (wrmf_ranks.hip counts over the same key matrix)
+hipError_t launch_topl_score(const float* U, const float* V, int nu, int n_items, int rank, unsigned* keys, size_t ld, hipStream_t s) {
+  return launch_score(U, V, nu, n_items, rank, keys, ld, s);
+}
+
+hipError_t launch_topl_mask(unsigned* keys, size_t ld, int n_items, int nu, const int32_t* nr_ptr, const int32_t* nr_idx,
+                            const int32_t* excl, int n_excl, hipStream_t s) {
+  hipLaunchKernelGGL(topl_mask_kernel, dim3(nu), dim3(256), 0, s, keys, ld, n_items, nr_ptr, nr_idx, excl, n_excl);
+  return hipGetLastError();
+}
+
 size_t top_product_large_ws_floats(int n_users, int n_items, int topk, int kc, int* chunk_users) {
   const LgPlan p = lg_plan(n_users, n_items, topk, kc);
   if (chunk_users) *chunk_users = p.chunk;

@@ -399,6 +399,53 @@ class HipBackend:
                       None if sse is None else sse.data_ptr(), None if sae is None else sae.data_ptr(), self._stream()))
         return scores, sse, sae
 
+    def held_out_ranks(self, U, V, nr_p, nr_j, exclude0, act_p, act_j, max_chunk_users=0):
+        """where the held-out items stand among all admissible items (wrmf_ranks.hip): for the rows of U (n x rank) against V
+        (n_item x rank), both on the device, and the stored entries of `actual` as CSR slots (act_p, act_j: int32, j sorted within
+        rows) -> (above, tied: int32, one per stored entry, -1 / -1 for an entry that is not admissible; n_adm: int32 of n).
+        nr_p / nr_j / exclude0 as `top_product`.  The scores are the fp32 ones of the large-k `top_product` path: a double
+        model's factors go through their fp32 replica, as for the nominating pass of `$predict`."""
+        n, rank = U.shape
+        n_item = V.shape[0]
+        U32 = U.to(torch.float32).contiguous()
+        V32 = self._v32(V).contiguous()
+        assert act_p.dtype == torch.int32 and act_j.dtype == torch.int32 and act_p.numel() == n + 1
+        nnz = int(act_j.numel())
+        dev = U.device
+        # (an empty view has no address to pass: the library gets the one-element buffers behind the views)
+        above_buf = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+        tied_buf = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+        above, tied = above_buf[:nnz], tied_buf[:nnz]
+        n_adm = torch.empty(n, dtype=torch.int32, device=dev)
+        if n == 0:
+            return above, tied, n_adm
+        if nnz == 0:   # (no stored entry at all: the library still wants non-NULL slots)
+            act_j = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(self.lib.rsparse_hip_held_out_ranks_device(
+            U32.data_ptr(), V32.data_ptr(), n, n_item, rank, None if nr_p is None else nr_p.data_ptr(),
+            None if nr_j is None else nr_j.data_ptr(), None if exclude0 is None else exclude0.data_ptr(),
+            0 if exclude0 is None else int(exclude0.numel()), act_p.data_ptr(), act_j.data_ptr(), int(max_chunk_users),
+            above_buf.data_ptr(), tied_buf.data_ptr(), n_adm.data_ptr(), self._stream()))
+        return above, tied, n_adm
+
+    def rank_summary(self, act_p, act_x, above, tied, n_adm):
+        """the per-user numbers of those counts (weights act_x: float64, one per stored entry): (mpr, auc, mrr: float64 of n;
+        sums: float64 n x 3 = sum w, sum w pct, admissible entries), on the device.  DESIGN.md 3.15."""
+        n = int(n_adm.numel())
+        dev = n_adm.device
+        mpr, auc, mrr = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(3))
+        sums = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        if n == 0:
+            return mpr, auc, mrr, sums
+        assert act_x.dtype == torch.float64 and above.dtype == torch.int32 and tied.dtype == torch.int32
+        if act_x.numel() == 0:
+            act_x = torch.zeros(1, dtype=torch.float64, device=dev)
+            above = tied = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(self.lib.rsparse_hip_rank_summary_device(
+            n, act_p.data_ptr(), act_x.contiguous().data_ptr(), above.data_ptr(), tied.data_ptr(), n_adm.data_ptr(), mpr.data_ptr(),
+            auc.data_ptr(), mrr.data_ptr(), sums.data_ptr(), self._stream()))
+        return mpr, auc, mrr, sums
+
     def _v32(self, V):
         """the fp32 replica of a factor matrix the fp64 layer holds (kept until the matrix changes: ADVICE r04 -- `predict` of
         one user paid an n_item x rank conversion per call)"""

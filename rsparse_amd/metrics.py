@@ -11,6 +11,13 @@ positions 1..kk of (hits so far) / position, ndcg is dcg / idcg over the first k
 own (missing, out-of-range and repeated predictions like `%in%` / `match`), stored zeros are relevant items of relevance 0.
 An empty row gives ap = NaN and ndcg = 0; a row of zero relevances ndcg = NaN.  `WRMF.evaluate` scores the lists of `predict`
 without moving them off the device.
+
+Full-ranking metrics (`WRMF.held_out_ranks` / `WRMF.evaluate_ranks` compute them on the device, wrmf_ranks.hip) have their
+plain-numpy statement here, from a dense score matrix -- the reference the tests hold the kernels to, usable on its own:
+
+    percentile_ranks(scores, actual, not_recommend, items_exclude)   per held-out entry: items above / tied, per row: n_adm
+    rank_summary(above, tied, n_adm, actual)                         per row: mpr, auc, mrr and the sums behind the totals
+    rank_totals(summary)                                             the data-set numbers {"mpr", "auc", "mrr", "n"}
 """
 import ctypes
 
@@ -78,3 +85,90 @@ def ap_k(predictions, actual):
 def ndcg_k(predictions, actual):
     """R/metrics.R:62-89: normalised discounted cumulative gain at k of every row, relevances from the values of `actual`."""
     return ranking_metrics(predictions, actual, ap=False, ndcg=True)[1]
+
+
+# ---- full-ranking metrics: the numpy statement of DESIGN.md 3.15 -------------------------------------------------------------
+def percentile_ranks(scores, actual, not_recommend=None, items_exclude=()):
+    """Where every stored entry (u, h) of `actual` stands among the ADMISSIBLE items of its row -- the items outside the row of
+    `not_recommend` (sparse, n x n_item, or None) and outside `items_exclude` (0-based) --, from the dense `scores` (n x n_item):
+    above = admissible items scored strictly higher, tied = other admissible items with an equal score (-0 equals +0); an entry
+    that is not admissible itself gets -1 / -1.  -> (above, tied, n_adm): two scipy CSR matrices (int32) with the canonical
+    pattern of `actual`, and the admissible items per row (int32)."""
+    S = np.asarray(scores)
+    if S.ndim != 2:
+        raise ValueError("scores must be a matrix (n x n_item)")
+    n, m = S.shape
+    a = canonical_actual(actual, n)
+    if a.shape[1] != m:
+        raise ValueError("actual must have the shape of scores")
+    adm = np.ones((n, m), dtype=bool)
+    if not_recommend is not None:
+        if not sp.issparse(not_recommend) or not_recommend.shape != (n, m):
+            raise ValueError("not_recommend must be sparse and have the shape of scores")
+        nr = sp.csr_matrix(not_recommend)
+        adm[np.repeat(np.arange(n), np.diff(nr.indptr)), nr.indices] = False
+    ex = np.asarray(list(items_exclude), dtype=np.int64)
+    if ex.size:
+        adm[:, ex] = False
+    above = np.full(a.nnz, -1, dtype=np.int32)
+    tied = np.full(a.nnz, -1, dtype=np.int32)
+    for u in range(n):
+        row, ok = S[u], adm[u]
+        for e in range(a.indptr[u], a.indptr[u + 1]):
+            h = a.indices[e]
+            if ok[h]:
+                above[e] = np.count_nonzero(ok & (row > row[h]))
+                tied[e] = np.count_nonzero(ok & (row == row[h])) - 1
+    mk = lambda v: sp.csr_matrix((v, a.indices.copy(), a.indptr.copy()), shape=a.shape)
+    return mk(above), mk(tied), adm.sum(axis=1).astype(np.int32)
+
+
+def rank_summary(above, tied, n_adm, actual):
+    """Per row, from the counts of `percentile_ranks` (CSR matrices or flat arrays in the order of the canonical `actual`) and the
+    stored values w of `actual`, over the admissible entries (P of them), with the midrank r = above + tied / 2:
+        pct = r / (n_adm - 1)                                     NaN when n_adm <= 1
+        mpr = sum w pct / sum w                                   NaN when sum w == 0 or P == 0 (expected percentile rank)
+        auc = 1 - (sum r - P (P - 1) / 2) / (P (n_adm - P))       NaN when P == 0 or n_adm == P
+        mrr = 1 / (1 + min r)                                     NaN when P == 0
+    -> {"mpr", "auc", "mrr", "sum_w", "sum_w_pct", "P"}: float64 vectors of n."""
+    n_adm = np.asarray(n_adm, dtype=np.int64)
+    n = n_adm.size
+    a = canonical_actual(actual, n)
+    ab = np.asarray(above.data if sp.issparse(above) else above, dtype=np.int64)
+    ti = np.asarray(tied.data if sp.issparse(tied) else tied, dtype=np.int64)
+    if ab.size != a.nnz or ti.size != a.nnz:
+        raise ValueError("above / tied must have one value per stored entry of actual")
+    out = {k: np.full(n, np.nan) for k in ("mpr", "auc", "mrr")}
+    out.update(sum_w=np.zeros(n), sum_w_pct=np.zeros(n), P=np.zeros(n))
+    for u in range(n):
+        sl = slice(a.indptr[u], a.indptr[u + 1])
+        ok = ab[sl] >= 0
+        r = ab[sl][ok] + 0.5 * ti[sl][ok]
+        w = a.data[sl][ok]
+        P, na = int(r.size), int(n_adm[u])
+        pct = r / (na - 1.0) if na > 1 else np.full(P, np.nan)
+        sw, swp = float(np.sum(w)), float(np.sum(w * pct))
+        out["sum_w"][u], out["sum_w_pct"][u], out["P"][u] = sw, swp, P
+        if P and sw != 0.0:
+            out["mpr"][u] = swp / sw
+        if P and na != P:
+            out["auc"][u] = 1.0 - (float(np.sum(r)) - P * (P - 1.0) * 0.5) / (P * float(na - P))
+        if P:
+            out["mrr"][u] = 1.0 / (1.0 + float(np.min(r)))
+    return out
+
+
+def rank_totals(summary):
+    """The data-set numbers of a `rank_summary`: mpr = sum_u sum w pct / sum_u sum w over the rows whose terms are finite (Hu,
+    Koren and Volinsky's expected percentile rank), auc and mrr the means over the rows where they are defined, n the admissible
+    entries.  NaN where nothing is defined."""
+    sw, swp = np.asarray(summary["sum_w"], dtype=np.float64), np.asarray(summary["sum_w_pct"], dtype=np.float64)
+    ok = np.isfinite(sw) & np.isfinite(swp) & (np.asarray(summary["P"]) > 0)
+    tot_w, tot = float(np.sum(sw[ok])), float(np.sum(swp[ok]))
+
+    def mean(v):
+        v = np.asarray(v, dtype=np.float64)
+        v = v[~np.isnan(v)]
+        return float(np.mean(v)) if v.size else float("nan")
+    return {"mpr": tot / tot_w if tot_w != 0.0 else float("nan"), "auc": mean(summary["auc"]), "mrr": mean(summary["mrr"]),
+            "n": int(np.sum(summary["P"]))}

@@ -512,16 +512,10 @@ class WRMF:
         out.scores = sc.cpu().numpy().astype(self._np_dtype())
         return out
 
-    def _predict_device(self, x, k, not_recommend, items_exclude):
-        """the device part of `predict`: (indices int32, scores float64) of this rank's block of rows, _row_bounds[rank], still
-        on the device -- 1-based with NA_integer_ as top_product writes them --, and x as CSR"""
-        if self._V is None:
-            raise RuntimeError("model is not fitted")
-        x = sp.csr_matrix(x, dtype=np.float64)
-        n_new, n_item = x.shape[0], self._V.shape[0]
-        if x.shape[1] != n_item:
-            raise ValueError("ncol(x) == ncol(self$components) is not TRUE")
-        k = int(k)
+    def _exclusion_args(self, x, not_recommend, items_exclude):
+        """the checks `predict` makes of its exclusions (x: CSR, n x n_item) -> (items_exclude sorted and unique,
+        not_recommend as a sparse matrix or None)"""
+        n_item = self._V.shape[0]
         excl = np.unique(np.asarray(list(items_exclude), dtype=np.int64))
         if excl.size and (excl.min() < 0 or excl.max() >= n_item):
             raise ValueError("some of items_exclude indices are bigger than number of items")      # :59-60
@@ -529,11 +523,12 @@ class WRMF:
             not_recommend = x
         if not_recommend is not None and not sp.issparse(not_recommend):
             raise TypeError("'not_recommend' should be NULL or 'sparseMatrix'")                     # R/utils.R:47
+        return excl, not_recommend
+
+    def _exclusion_slots(self, x, not_recommend, excl, a, b):
+        """... on the device for the rows [a, b): (nr_p, nr_j, exclude0), None for what is empty"""
         be = self._backend()
-        emb = self._transform_device(x)             # (n_new, rank), complete on every rank
-        # several ranks: every rank scores its own block of rows (the same blocks as transform), then the blocks are shared
-        a, b, ws = self._my_rows(x)
-        n_mine = b - a
+        n_new, n_item = x.shape[0], self._V.shape[0]
         nr_p = nr_j = None
         if not_recommend is not None:
             nr = sp.csr_matrix(not_recommend)
@@ -545,6 +540,25 @@ class WRMF:
                 nr_p = be.to_device(nr.indptr, torch.int32)
                 nr_j = be.to_device(nr.indices, torch.int32)
         d_ex = be.to_device(excl, torch.int32) if excl.size else None
+        return nr_p, nr_j, d_ex
+
+    def _predict_device(self, x, k, not_recommend, items_exclude):
+        """the device part of `predict`: (indices int32, scores float64) of this rank's block of rows, _row_bounds[rank], still
+        on the device -- 1-based with NA_integer_ as top_product writes them --, and x as CSR"""
+        if self._V is None:
+            raise RuntimeError("model is not fitted")
+        x = sp.csr_matrix(x, dtype=np.float64)
+        n_new, n_item = x.shape[0], self._V.shape[0]
+        if x.shape[1] != n_item:
+            raise ValueError("ncol(x) == ncol(self$components) is not TRUE")
+        k = int(k)
+        excl, not_recommend = self._exclusion_args(x, not_recommend, items_exclude)
+        be = self._backend()
+        emb = self._transform_device(x)             # (n_new, rank), complete on every rank
+        # several ranks: every rank scores its own block of rows (the same blocks as transform), then the blocks are shared
+        a, b, ws = self._my_rows(x)
+        n_mine = b - a
+        nr_p, nr_j, d_ex = self._exclusion_slots(x, not_recommend, excl, a, b)
         if n_mine > 0:
             res, sc = be.top_product(emb[a:b], self._V, k, nr_p, nr_j, d_ex, float(self.global_bias))
         else:
@@ -659,6 +673,130 @@ class WRMF:
             with np.errstate(invalid="ignore", divide="ignore"):
                 out["rmse_per_user"] = np.sqrt(sse.cpu().numpy() / cnt)
                 out["mae_per_user"] = sae.cpu().numpy() / cnt
+        return out
+
+    def _ranks_device(self, x, actual, not_recommend, items_exclude, max_chunk_users=0):
+        """the device part of `held_out_ranks` / `evaluate_ranks`: the embeddings of the rows of x (as `predict` gets them), then
+        this rank's block of rows of `actual` counted against every admissible item.  -> (canonical actual, this block's rows of
+        it, (above, tied, n_adm) of the block on the device)"""
+        x, act = self._pairs_pattern(x, actual, "actual")
+        excl, not_recommend = self._exclusion_args(x, not_recommend, items_exclude)
+        be = self._backend()
+        emb = self._transform_device(x)             # (n, rank), complete on every rank
+        a, b, _ = self._my_rows(x)
+        nr_p, nr_j, d_ex = self._exclusion_slots(x, not_recommend, excl, a, b)
+        mine = act[a:b]
+        p, j = be.to_device(mine.indptr, torch.int32), be.to_device(mine.indices, torch.int32)
+        fn = be.held_out_ranks if hasattr(be, "held_out_ranks") else self._held_out_ranks_host
+        return act, mine, fn(emb[a:b], self._V, nr_p, nr_j, d_ex, p, j, max_chunk_users)
+
+    @staticmethod
+    def _held_out_ranks_host(U, V, nr_p, nr_j, exclude0, act_p, act_j, max_chunk_users=0):
+        """`held_out_ranks` for a backend without it (the CPU stand-in of the tests), in plain torch: the scores are the double
+        product rounded to float32, the counts integer sums over the admissible items.  Same rules as wrmf_ranks.hip."""
+        n, n_item = U.shape[0], V.shape[0]
+        dev = U.device
+        p = act_p.to(torch.int64)
+        rows = torch.repeat_interleave(torch.arange(n, device=dev), torch.diff(p))
+        cols = act_j.to(torch.int64)
+        above = torch.full((int(cols.numel()),), -1, dtype=torch.int32, device=dev)
+        tied = torch.full((int(cols.numel()),), -1, dtype=torch.int32, device=dev)
+        n_adm = torch.zeros(n, dtype=torch.int32, device=dev)
+        V64 = V.to(torch.float64)
+        B = int(max_chunk_users) if max_chunk_users else 1024
+        for a0 in range(0, n, B):
+            b0 = min(n, a0 + B)
+            S = (U[a0:b0].to(torch.float64) @ V64.T).to(torch.float32)
+            adm = torch.ones(S.shape, dtype=torch.bool, device=dev)
+            if nr_p is not None:
+                q = nr_p.to(torch.int64)
+                r = torch.repeat_interleave(torch.arange(b0 - a0, device=dev), torch.diff(q[a0:b0 + 1]))
+                adm[r, nr_j.to(torch.int64)[int(q[a0]):int(q[b0])]] = False
+            if exclude0 is not None:
+                adm[:, exclude0.to(torch.int64)] = False
+            n_adm[a0:b0] = adm.sum(dim=1).to(torch.int32)
+            e0, e1 = int(p[a0]), int(p[b0])
+            for c0 in range(e0, e1, 4096):   # (entries x items comparisons, a block of entries at a time)
+                c1 = min(e1, c0 + 4096)
+                r, h = rows[c0:c1] - a0, cols[c0:c1]
+                inside = (h >= 0) & (h < n_item)
+                h = torch.where(inside, h, torch.zeros_like(h))
+                ok = adm[r, h] & inside
+                sh = S[r, h][:, None]
+                ab = ((S[r] > sh) & adm[r]).sum(dim=1).to(torch.int32)
+                ti = ((S[r] == sh) & adm[r]).sum(dim=1).to(torch.int32) - 1
+                above[c0:c1] = torch.where(ok, ab, torch.full_like(ab, -1))
+                tied[c0:c1] = torch.where(ok, ti, torch.full_like(ti, -1))
+        return above, tied, n_adm
+
+    @staticmethod
+    def _rank_summary_host(act_p, act_x, above, tied, n_adm):
+        """`rank_summary` for a backend without it, in torch double ops: DESIGN.md 3.15's formulas, sums by index_add"""
+        n = int(n_adm.numel())
+        dev = n_adm.device
+        nan = float("nan")
+        rows = torch.repeat_interleave(torch.arange(n, device=dev), torch.diff(act_p.to(torch.int64)))
+        ok = above >= 0
+        rows, w = rows[ok], act_x[ok]
+        r = above[ok].to(torch.float64) + 0.5 * tied[ok].to(torch.float64)
+        na = n_adm.to(torch.float64)
+        pct = torch.where(na[rows] > 1, r / (na[rows] - 1.0), torch.full_like(r, nan))
+        zero = lambda: torch.zeros(n, dtype=torch.float64, device=dev)
+        sw, swp, sr = zero().index_add_(0, rows, w), zero().index_add_(0, rows, w * pct), zero().index_add_(0, rows, r)
+        P = zero().index_add_(0, rows, torch.ones_like(r))
+        rmin = torch.full((n,), float("inf"), dtype=torch.float64, device=dev).scatter_reduce_(0, rows, r, "amin")
+        bad = torch.full((n,), nan, dtype=torch.float64, device=dev)
+        mpr = torch.where((P > 0) & (sw != 0), swp / sw, bad)
+        auc = torch.where((P > 0) & (na != P), 1.0 - (sr - P * (P - 1.0) * 0.5) / (P * (na - P)), bad)
+        mrr = torch.where(P > 0, 1.0 / (1.0 + rmin), bad)
+        return mpr, auc, mrr, torch.stack([sw, swp, P], dim=1)
+
+    def held_out_ranks(self, x, actual, not_recommend="x", items_exclude=()):
+        """Where every held-out interaction stands among ALL the items the user could be shown -- the quantity behind the
+        expected percentile rank of Hu, Koren and Volinsky, AUC and MRR.  The embeddings of the rows of `x` by `transform`, as
+        in `predict`; the ADMISSIBLE items of a row are those outside its `not_recommend` row (default: `x` itself) and outside
+        `items_exclude`; the scores are the fp32 scores `predict`'s large-k path ranks by (a global bias shifts them all alike).
+        For every stored entry (u, h) of `actual` (n x n_item sparse, stored zeros are entries): above = admissible items scored
+        strictly higher than h, tied = other admissible items with an equal score; -1 / -1 when h itself is not admissible.
+        Returns (above, tied, n_adm): two scipy CSR matrices (int32) with the canonical pattern of `actual` (columns sorted,
+        duplicates merged) and the admissible items per row (int32 vector).  The 0-based midrank of an entry is
+        above + tied / 2.  Counted on the device in one pass over the scores of each chunk of users (wrmf_ranks.hip); under
+        torch.distributed every rank counts the block of rows it transforms."""
+        act, mine, (above, tied, n_adm) = self._ranks_device(x, actual, not_recommend, items_exclude)
+        ws, me = self._dist()
+        if ws > 1:
+            bounds = [(int(act.indptr[a]), int(act.indptr[b])) for a, b in self._row_bounds]
+            above, tied = self._share_rows(above, bounds, int(act.nnz)), self._share_rows(tied, bounds, int(act.nnz))
+            n_adm = self._share_rows(n_adm, self._row_bounds, act.shape[0])
+        mk = lambda v: sp.csr_matrix((v.cpu().numpy().astype(np.int32), act.indices.copy(), act.indptr.copy()), shape=act.shape)
+        return mk(above), mk(tied), n_adm.cpu().numpy().astype(np.int32)
+
+    def evaluate_ranks(self, x, actual, not_recommend="x", items_exclude=(), per_user=False):
+        """The full-ranking metrics of the held-out interactions `actual` (values = weights), from `held_out_ranks`' counts
+        without a per-entry value leaving the device.  With r = above + tied / 2 and pct = r / (n_adm - 1) -- 0 is the top of
+        the user's admissible items, 1 the bottom -- over the admissible entries of a user (P of them, weights w):
+            mpr = sum w pct / sum w                                 Hu et al.'s expected percentile rank (0.5 = random)
+            auc = 1 - (sum r - P (P - 1) / 2) / (P (n_adm - P))     the share of (held-out, other) pairs ordered correctly
+            mrr = 1 / (1 + min r)
+        Returns {"mpr": sum over users of sum w pct / sum over users of sum w (users with finite terms), "auc", "mrr": means
+        over the users where they are defined, "n": admissible entries}; per_user=True adds "mpr_per_user", "auc_per_user",
+        "mrr_per_user" (float64 vectors of n, NaN where undefined: no admissible entry, or n_adm - 1 / n_adm - P / sum w is 0)
+        and "n_adm_per_user".  Double arithmetic in a fixed order on the device: a call repeats bit for bit."""
+        act, mine, (above, tied, n_adm) = self._ranks_device(x, actual, not_recommend, items_exclude)
+        be = self._backend()
+        fn = be.rank_summary if hasattr(be, "rank_summary") else self._rank_summary_host
+        mpr, auc, mrr, sums = fn(be.to_device(mine.indptr, torch.int32), be.to_device(mine.data, torch.float64), above, tied, n_adm)
+        ws, me = self._dist()
+        if ws > 1:
+            n_new = act.shape[0]
+            mpr, auc, mrr, sums, n_adm = (self._share_rows(v, self._row_bounds, n_new) for v in (mpr, auc, mrr, sums, n_adm))
+        from .metrics import rank_totals
+        sums = sums.cpu().numpy()
+        per = {"mpr": mpr.cpu().numpy(), "auc": auc.cpu().numpy(), "mrr": mrr.cpu().numpy()}
+        out = rank_totals({"sum_w": sums[:, 0], "sum_w_pct": sums[:, 1], "P": sums[:, 2], "auc": per["auc"], "mrr": per["mrr"]})
+        if per_user:
+            out.update({k + "_per_user": v for k, v in per.items()})
+            out["n_adm_per_user"] = n_adm.cpu().numpy().astype(np.int32)
         return out
 
     def similar_items(self, items=None, k=10, items_exclude=(), exclude_self=True):
