@@ -523,6 +523,43 @@ int rsparse_hip_sparse_approximation(int n_rows, int n_cols, const int32_t* p, c
                                      const double* X, const double* Y, int rank, double* values_out);
 
 /* ------------------------------------------------------------------------------------------------
+ * initial factors drawn on the device: a counter-based normal generator
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The reference fills the two factor matrices on the host with R's generator before the first half-iteration
+ * (large_rand_matrix, src/utils.cpp:130-151: rank x n column-major N(0, 1) / 100; R/model_WRMF.R:203-255: the draw, the rows of
+ * ones of a model with user/item biases, abs() for NNLS, zeros for the items under conjugate gradient) and the half-iterations
+ * take the factors as inputs only.  At 10M x 1M and rank 128 that is seconds of host work and a 5.6 GB upload; these two entries
+ * write the same kind of matrix straight into device memory.  The stream is DEFINED here, so that any host (an R shim included)
+ * can reproduce it; rsparse_amd/rng.py is the definition in numpy.
+ *
+ *   Bits.      Philox4x32-10, the standard Random123 rounds: per round  hi0:lo0 = 0xD2511F53 * c0,  hi1:lo1 = 0xCD9E8D57 * c2,
+ *              (c0, c1, c2, c3) <- (hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0); between rounds k0 += 0x9E3779B9, k1 += 0xBB67AE85.
+ *   Index.     The matrix is n x rank row-major (= the reference's column-major rank x n).  Element (row, col) has the 64-bit
+ *              linear index e = row * rank + col over the WHOLE matrix; the leading dimension ld is not used here.
+ *   Counter.   (lo32(e >> 2), hi32(e >> 2), stream, 0); key (lo32(seed), hi32(seed)).  stream 0 = user factors, 1 = item factors.
+ *   Outputs.   One Philox call gives four words o0..o3 and four numbers; element e takes number e & 3 (with rank % 4 != 0 a group
+ *              of four straddles two rows).
+ *   Uniforms.  From the top 24 bits, exact in fp32:  u_a = ((o0 >> 8) + 1) * 2^-24 in (0, 1],  u_b = (o1 >> 8) * 2^-24 in [0, 1).
+ *   Normals.   r = sqrt(-2 ln u_a); numbers 0 and 1 are r cos(2 pi u_b) and r sin(2 pi u_b); numbers 2 and 3 the same from
+ *              (o2, o3).  |z| <= sqrt(48 ln 2) = 5.77.
+ *   Value.     scale * z (the reference: scale = 0.01), its absolute value if abs_values != 0; the column ones_col (-1 = none) is
+ *              written as exactly 1.
+ * A value therefore depends on (seed, stream, row, col, rank) only -- not on the launch, the row range asked for, the number of
+ * devices that each draw their own rows, or the device.  The fp32 entry evaluates the transform in fp32 (within
+ * 2^-21 * scale * max(1, r) of the double evaluation), the f64 entry in double.
+ *
+ * d_out points at the first element of row row0 (so a shard generates only its own rows): rows row0 .. row0 + n_rows - 1 are
+ * written at d_out[(row - row0) * ld + col], col < rank; with ld > rank the padding is not touched.  One write-only launch on
+ * hip_stream (a hipStream_t, NULL = default), no synchronisation.  There is no rank ceiling: nothing here depends on a solver.
+ * n_rows < 0, row0 < 0, rank < 1, ld < rank, stream outside 0..1, ones_col outside -1..rank-1, (row0 + n_rows) * rank beyond
+ * 63 bits, d_out NULL with n_rows > 0 -> ERR_INVALID, before a device is touched; n_rows == 0 -> OK, nothing is launched. */
+int rsparse_hip_init_factors_device(uint64_t seed, int stream, int64_t row0, int n_rows, int rank, int64_t ld, double scale,
+                                    int abs_values, int ones_col, void* d_out /* float */, void* hip_stream);
+int rsparse_hip_init_factors_f64_device(uint64_t seed, int stream, int64_t row0, int n_rows, int rank, int64_t ld, double scale,
+                                        int abs_values, int ones_col, void* d_out /* double */, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------
  * (3) fp64 device layer: als_implicit<double> / als_explicit<double> with the data resident in HBM
  * ---------------------------------------------------------------------------------------------- */
 

@@ -14,7 +14,7 @@ OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_RUNTIME, ERR_NUMERIC = 0, 1, 2, 3, 4
 SOLVER_CHOLESKY, SOLVER_CG, SOLVER_NNLS = 0, 1, 2
 RANKS_BATCH = 1024   # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that the rank count takes at a time
 
-_c_int, _c_uint, _c_dbl, _c_i64 = ctypes.c_int, ctypes.c_uint, ctypes.c_double, ctypes.c_int64
+_c_int, _c_uint, _c_dbl, _c_i64, _c_u64 = ctypes.c_int, ctypes.c_uint, ctypes.c_double, ctypes.c_int64, ctypes.c_uint64
 _vp = ctypes.c_void_p
 
 # name -> (restype, argtypes); mirrors include/rsparse_wrmf_hip.h one to one
@@ -82,6 +82,9 @@ SIGNATURES = {
                                             _vp, _vp, _vp]),
     "rsparse_hip_score_pairs_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_dbl, _vp, _vp, _vp, _vp, _vp]),
     "rsparse_hip_score_pairs_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_dbl, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_init_factors_device": (_c_int, [_c_u64, _c_int, _c_i64, _c_int, _c_int, _c_i64, _c_dbl, _c_int, _c_int, _vp, _vp]),
+    "rsparse_hip_init_factors_f64_device": (_c_int, [_c_u64, _c_int, _c_i64, _c_int, _c_int, _c_i64, _c_dbl, _c_int, _c_int, _vp,
+                                                     _vp]),
     "rsparse_hip_sparse_approximation": (_c_int, [_c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_int, _vp]),
     "rsparse_hip_csc_f64_create_device": (_c_int, [_c_int, _c_int, _vp, _vp, _vp, ctypes.POINTER(_vp)]),
     "rsparse_hip_csc_f64_destroy": (_c_int, [_vp]),

@@ -1544,6 +1544,13 @@ int rsparse_hip_score_pairs_device(const float* d_U, const float* d_V, int n_row
                             });
 }
 
+// `_f64_device`: wrmf_f64_capi.cpp
+int rsparse_hip_init_factors_device(uint64_t seed, int stream, int64_t row0, int n_rows, int rank, int64_t ld, double scale,
+                                    int abs_values, int ones_col, void* d_out, void* hip_stream) {
+  return init_factors_device(seed, stream, row0, n_rows, rank, ld, scale, abs_values, ones_col, static_cast<float*>(d_out),
+                             (hipStream_t)hip_stream);
+}
+
 int rsparse_hip_take_numeric_failures(int64_t* unresolved_out, int64_t* fallback_out) {
   if (!unresolved_out) return fail(RSPARSE_HIP_ERR_INVALID, "unresolved_out is NULL");
   // counts a stateless call found on the device when it started and set aside (see StaleFailures): still the resident layer's

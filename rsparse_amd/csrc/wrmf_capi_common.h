@@ -227,6 +227,23 @@ int score_pairs_device(const T* d_U, const T* d_V, int n_rows, int n_cols, int r
   return RSPARSE_HIP_OK;
 }
 
+// rsparse_hip_init_factors_device / _f64_device (kernel: wrmf_init.hip).  No rank ceiling: nothing here depends on a solver.
+template <class T>
+int init_factors_device(uint64_t seed, int stream, int64_t row0, int n_rows, int rank, int64_t ld, double scale, int abs_values,
+                        int ones_col, T* d_out, hipStream_t s) {
+  if (n_rows < 0 || row0 < 0 || rank < 1 || ld < rank)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, row0 < 0, rank < 1 or ld < rank)");
+  if (stream < 0 || stream > 1) return fail(RSPARSE_HIP_ERR_INVALID, "stream must be 0 (user factors) or 1 (item factors)");
+  if (ones_col < -1 || ones_col >= rank) return fail(RSPARSE_HIP_ERR_INVALID, "ones_col must be -1 or a column of the matrix");
+  if (row0 > INT64_MAX / rank - n_rows)   // (row0 + n_rows) * rank, the end of the element index, in 63 bits
+    return fail(RSPARSE_HIP_ERR_INVALID, "the element index (row0 + n_rows) * rank does not fit 63 bits");
+  if (n_rows > 0 && !d_out) return fail(RSPARSE_HIP_ERR_INVALID, "d_out is NULL");
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  hipError_t e = launch_init_factors(seed, stream, row0, n_rows, rank, ld, scale, abs_values, ones_col, d_out, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_init_factors");
+  return RSPARSE_HIP_OK;
+}
+
 // Shared body of the stateless drop-ins (als_implicit / als_explicit, src/wrmf_implicit.cpp:5-26, src/wrmf_explicit.cpp:5-26)
 // once the caller has validated what its side validates and made its resident matrix (nnz non-zeros).  Handed in:
 //   int scratch(SumScratch& w)    makes sure of the side's workspace and gives its sum scratch as it is now

@@ -361,6 +361,13 @@ int rsparse_hip_score_pairs_f64_device(const double* d_U, const double* d_V, int
                             });
 }
 
+// initial factors in double (kernel: wrmf_init.hip; the fp32 form: wrmf_capi.cpp)
+int rsparse_hip_init_factors_f64_device(uint64_t seed, int stream, int64_t row0, int n_rows, int rank, int64_t ld, double scale,
+                                        int abs_values, int ones_col, void* d_out, void* hip_stream) {
+  return init_factors_device(seed, stream, row0, n_rows, rank, ld, scale, abs_values, ones_col, static_cast<double*>(d_out),
+                             (hipStream_t)hip_stream);
+}
+
 // cpp_make_sparse_approximation (src/utils.cpp:4-56): the values of X^T Y at the stored positions of a template.  CSR: position t
 // of row i holds X[:, i] . Y[:, idx[t]]; CSC: position t of column c holds Y[:, c] . X[:, idx[t]] -- the two operands swap roles.
 int rsparse_hip_sparse_approximation(int n_rows, int n_cols, const int32_t* p, const int32_t* idx, int sparse_matrix_type,

@@ -361,6 +361,13 @@ hipError_t launch_score_pairs(const T* U, const T* V, int n_rows, int n_cols, in
 hipError_t launch_score_error_sums(const double* scores, const double* actual, const int32_t* P, int n_rows, double* sse,
                                    double* sae, hipStream_t s);
 
+// initial factors drawn on the device (wrmf_init.hip), T = float or double: the rows [row0, row0 + n_rows) of the (., rank) matrix
+// of `stream` (0 users, 1 items) under `seed`, written to `out` (row row0's first element, leading dimension ld >= rank) as
+// scale * N(0, 1), |.| with abs_values, the column ones_col (-1: none) exactly 1.  The generator: rsparse_wrmf_hip.h.
+template <class T>
+hipError_t launch_init_factors(uint64_t seed, int stream, int64_t row0, int n_rows, int rank, int64_t ld, double scale,
+                               int abs_values, int ones_col, T* out, hipStream_t s);
+
 // item-to-item cosine similarity (wrmf_similar.hip): the operands of the top-k path above.
 // launch_normalize_items: V (fp32, or fp64 when f64) n_items x ld row-major, columns [c0, c0 + r), 1 <= r <= 256 ->
 // Vn64 / Vn32 (n_items x r, compact) with unit rows, flags[item] = 1 and a row of zeros where the sum of squares is zero or

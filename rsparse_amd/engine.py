@@ -219,6 +219,23 @@ class HipBackend:
     def to_device(self, a, dtype):
         return torch.as_tensor(a, dtype=dtype).to(self.device).contiguous()
 
+    def init_factors(self, seed, stream, n_rows, rank, dtype, abs_values=False, ones_col=-1, row0=0, scale=0.01, out=None):
+        """the rows [row0, row0 + n_rows) of the initial factor matrix of `stream` (0 = users, 1 = items) under `seed`, drawn on
+        the device by the counter-based generator of wrmf_init.hip (rsparse_amd/rng.py is its definition): scale * N(0, 1),
+        |.| with abs_values, the column ones_col (-1: none) exactly 1.  -> an (n_rows, rank) device tensor of `dtype` (float32
+        or float64); `out`: write into this tensor instead (rows of `rank` elements, any row stride >= rank: what lies between
+        the rows is left alone).  No host array and no upload are involved; a value does not depend on row0 / n_rows."""
+        assert dtype in (torch.float32, torch.float64)
+        n_rows, rank = int(n_rows), int(rank)
+        if out is None:
+            out = torch.empty((n_rows, rank), dtype=dtype, device=self.device)
+        assert out.dtype == dtype and out.is_cuda and tuple(out.shape) == (n_rows, rank) and (rank == 1 or out.stride(1) == 1)
+        ld = int(out.stride(0)) if n_rows > 1 else rank
+        fn = self.lib.rsparse_hip_init_factors_f64_device if dtype == torch.float64 else self.lib.rsparse_hip_init_factors_device
+        _lib.check(fn(int(seed), int(stream), int(row0), n_rows, rank, ld, float(scale), int(bool(abs_values)), int(ones_col),
+                      out.data_ptr() if n_rows else None, self._stream()))
+        return out
+
     def make_csc(self, n_rows, n_cols, p, i, x):
         """p/i/x: torch tensors already on the device (int32, int32, float32 -- or float64: the handle then belongs to the
         fp64 layer of the C ABI and every call that takes it computes in double)."""

@@ -1,0 +1,93 @@
+"""The counter-based normal generator behind `WRMF(factor_init="device")`, in numpy: the specification of the stream that
+rsparse_amd/csrc/wrmf_init.hip draws on the device (include/rsparse_wrmf_hip.h states the same definition for C hosts), the
+oracle of its tests, and the fallback of a backend that has no device.
+
+    bits      Philox4x32-10 (Random123): multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85
+    index     the matrix is (n_rows, rank) row-major; e = row * rank + col, 64 bits, over the WHOLE matrix
+    counter   (lo32(e >> 2), hi32(e >> 2), stream, 0);   key (lo32(seed), hi32(seed));   stream 0 = users, 1 = items
+    outputs   one call gives o0..o3 and four normals; element e takes number e & 3
+    uniforms  u_a = ((o0 >> 8) + 1) 2^-24 in (0, 1],  u_b = (o1 >> 8) 2^-24 in [0, 1)        (exact in fp32)
+    normals   r = sqrt(-2 ln u_a);  numbers 0, 1 = r cos(2 pi u_b), r sin(2 pi u_b);  2, 3 the same from (o2, o3)
+    value     scale * z, |.| with abs_values; the column ones_col (-1: none) is exactly 1
+
+A value depends on (seed, stream, row, col, rank) alone: not on the row range asked for, the number of ranks or the device.
+Evaluated in float64 and cast at the end.  |z| <= sqrt(48 ln 2) = 5.77; z is exactly 0 only for u_a = 1 (one pair in 2^24) or
+at a quarter turn of u_b (four values in 2^24).
+"""
+import numpy as np
+
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+STREAM_USERS, STREAM_ITEMS = 0, 1
+_MASK = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32 with 10 rounds.  counter: (..., 4) and key: (..., 2) arrays of 32-bit words (broadcast against each other)
+    -> (..., 4) uint32."""
+    c = np.asarray(counter, dtype=np.uint64) & _MASK
+    k = np.asarray(key, dtype=np.uint64) & _MASK
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., j], shape) for j in range(4))
+    k0, k1 = (np.broadcast_to(k[..., j], shape) for j in range(2))
+    for rnd in range(10):
+        if rnd:
+            k0 = (k0 + np.uint64(PHILOX_W0)) & _MASK
+            k1 = (k1 + np.uint64(PHILOX_W1)) & _MASK
+        p0 = np.uint64(PHILOX_M0) * c0      # 32 x 32 -> 64 bits: no overflow in uint64
+        p1 = np.uint64(PHILOX_M1) * c2
+        c0, c1, c2, c3 = (p1 >> _S32) ^ c1 ^ k0, p1 & _MASK, (p0 >> _S32) ^ c3 ^ k1, p0 & _MASK
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def _cos_sin_2pi(m):
+    """cos and sin of 2 pi m / 2^24 for integers 0 <= m < 2^24.  The quarter turn is taken off exactly, so the argument of the
+    library call is at most pi / 4 and carries one rounding (absolute error below 2e-16, where cos(2 * pi * u) loses 1e-15),
+    and the values at the quarter turns are exact, as a sincospi gives them."""
+    m = m.astype(np.int64)
+    q = (m + (1 << 21)) >> 22                      # nearest quarter turn (2^22 steps): 0..4
+    a = (m - (q << 22)).astype(np.float64) * (np.pi / float(1 << 23))
+    c, s = np.cos(a), np.sin(a)
+    q = q & 3
+    return np.choose(q, [c, -s, -c, s]), np.choose(q, [s, c, -s, -c])
+
+
+def box_muller(words):
+    """(..., 4) uint32 Philox outputs -> ((..., 4) float64 standard normals, (..., 4) their radii r)"""
+    w = np.asarray(words, dtype=np.uint32)
+    z = np.empty(w.shape, dtype=np.float64)
+    rad = np.empty(w.shape, dtype=np.float64)
+    for h in (0, 2):
+        ua = ((w[..., h] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+        r = np.sqrt(-2.0 * np.log(ua))
+        c, s = _cos_sin_2pi(w[..., h + 1] >> np.uint32(8))
+        z[..., h], z[..., h + 1] = r * c, r * s
+        rad[..., h] = rad[..., h + 1] = r
+    return z, rad
+
+
+def init_factors(seed, stream, row0, n_rows, rank, scale=0.01, abs_values=False, ones_col=-1, dtype=np.float64,
+                 return_radius=False):
+    """Rows [row0, row0 + n_rows) of the (anything, rank) matrix of stream `stream` under `seed`: an (n_rows, rank) array of
+    `dtype`.  return_radius=True also gives the Box-Muller radius r of every element (float64; what an error bound of a lower
+    precision evaluation scales with)."""
+    seed, stream, row0, n_rows, rank, ones_col = int(seed), int(stream), int(row0), int(n_rows), int(rank), int(ones_col)
+    if n_rows < 0 or row0 < 0 or rank < 1 or stream not in (0, 1) or not -1 <= ones_col < rank or not 0 <= seed < 2 ** 64:
+        raise ValueError("init_factors: bad arguments")
+    e0, e1 = row0 * rank, (row0 + n_rows) * rank
+    g0, g1 = e0 >> 2, (e1 + 3) >> 2
+    g = np.arange(g0, g1, dtype=np.uint64)
+    counter = np.stack([g & _MASK, g >> _S32, np.full_like(g, stream), np.zeros_like(g)], axis=-1)
+    key = np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64)
+    z, rad = box_muller(philox4x32_10(counter, key))
+    lo, hi = e0 - 4 * g0, e1 - 4 * g0
+    out = (float(scale) * z.reshape(-1)[lo:hi]).reshape(n_rows, rank)
+    if abs_values:
+        out = np.abs(out)
+    if ones_col >= 0:
+        out[:, ones_col] = 1.0
+    out = out.astype(dtype)
+    if return_radius:
+        return out, rad.reshape(-1)[lo:hi].reshape(n_rows, rank)
+    return out

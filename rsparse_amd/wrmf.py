@@ -61,7 +61,7 @@ class WRMF:
     def __init__(self, rank=10, lambda_=0.0, dynamic_lambda=True, init=None, preprocess=_identity,
                  feedback="implicit", solver="conjugate_gradient", with_user_item_bias=False,
                  with_global_bias=False, cg_steps=3, precision="double", rng=None, device=None, group=None,
-                 backend=None, n_sub=None):
+                 backend=None, n_sub=None, factor_init="host"):
         if init is not None and not isinstance(init, np.ndarray):
             raise TypeError("init must be NULL or a matrix")                      # :84
         if solver not in SOLVER_CODES:
@@ -74,6 +74,8 @@ class WRMF:
             raise TypeError("cg_steps must be an integer")                        # :107
         if not callable(preprocess):
             raise TypeError("preprocess must be a function")                      # :165
+        if factor_init not in ("host", "device"):
+            raise ValueError("factor_init must be 'host' or 'device'")
         self._non_negative = solver == "nnls"
         if self._non_negative and with_global_bias:
             with_global_bias = False                                              # :90-93 (the reference warns)
@@ -103,6 +105,10 @@ class WRMF:
         self._be = backend   # None = HipBackend on first use; tests inject the CPU stand-in for the multi-rank control flow
         self._group = group  # torch.distributed process group to shard over (None = the default group if initialised)
         self._n_sub = n_sub  # sub-blocks per rank and half-iteration of a sharded fit (None = engine.default_subblocks)
+        # where the random initial factors come from: "host" = numpy's stream of `rng`, drawn on the host and uploaded (the
+        # stream every seeded result so far is tied to); "device" = one seed from `rng`, the matrices from the counter-based
+        # generator of rsparse_amd/rng.py, written on the device by wrmf_init.hip (another stream, no host array, no upload)
+        self._factor_init = factor_init
         self._V = None       # item factors on the device, (n_item, rank)
         self._XtX = None
         self._cnt_item = None
@@ -164,6 +170,56 @@ class WRMF:
             return dist.get_world_size(self._group), dist.get_rank(self._group)
         return 1, 0
 
+    def _initial_factors_device(self, be, n_user, n_item, share_seed=None, share_given=None):
+        """factor_init = "device": (U, V) on the device, (n_user, rank) and (n_item, rank) in the device dtype, under the rules of
+        the host draw (R/model_WRMF.R:203-255) -- `_init_user_factors` replaces the user draw and `init` the item draw, the
+        conjugate-gradient solver starts the items from zeros, the bias model has its two columns of ones, NNLS takes absolute
+        values -- with one 63-bit seed taken from the model's generator (so `rng=` still makes a fit reproducible) and the
+        draws made by the counter-based generator of rsparse_amd/rng.py: stream 0 for the users, stream 1 for the items, on the
+        device (wrmf_init.hip) when the backend has one.  Sharded fits hand in share_seed (rank 0's seed to every rank) and
+        share_given (rank 0's copy of a given matrix to every rank, in place)."""
+        from . import rng as _rng
+        k, ndt, tdt, nn = self._rank, self._dev_np(), self._dev_t(), self._non_negative
+        seed = int(self._rng.integers(2 ** 63))
+        if share_seed is not None:
+            seed = share_seed(seed)
+        ones_u, ones_v = (0, k - 1) if self._with_bias else (-1, -1)                # :208-245: the two rows of ones
+
+        def draw(stream, n, ones_col):
+            if hasattr(be, "init_factors"):
+                return be.init_factors(seed, stream, n, k, tdt, nn, ones_col)
+            return be.to_device(_rng.init_factors(seed, stream, 0, n, k, 0.01, nn, ones_col, dtype=ndt), tdt)
+
+        def given(a, ones_col):
+            a = np.array(a, dtype=ndt, order="C")
+            if share_given is not None:
+                share_given(a)
+            if ones_col >= 0:
+                a[:, ones_col] = 1.0
+            return be.to_device(np.abs(a) if nn else a, tdt)                       # NNLS: :252-255
+
+        if self._init_user_factors is not None:
+            if np.shape(self._init_user_factors) != (n_user, k):
+                raise ValueError("initial user factors must be n_user x rank")
+            U = given(self._init_user_factors, ones_u)
+        else:
+            U = draw(_rng.STREAM_USERS, n_user, ones_u)
+        if self.components is not None:
+            if self.components.shape != (k, n_item):                               # :246-248
+                raise ValueError("init must be rank x n_item")
+            V = given(self.components.T, ones_v)
+        elif self._solver_code == 1:                                               # CG -> zeros (:219-231)
+            # the same on every rank, so nothing is shared; on a device they are allocated there (no host array, no upload)
+            if hasattr(be, "init_factors"):
+                V = torch.zeros((n_item, k), dtype=tdt, device=U.device)
+            else:
+                V = be.to_device(np.zeros((n_item, k), dtype=ndt), tdt)
+            if ones_v >= 0:
+                V[:, ones_v] = 1.0
+        else:
+            V = draw(_rng.STREAM_ITEMS, n_item, ones_v)
+        return U, V
+
     def fit_transform(self, x, n_iter=10, convergence_tol=None):
         """R/model_WRMF.R:173-360.  Returns the user embeddings (n_user x rank).
 
@@ -194,28 +250,32 @@ class WRMF:
         k = self._rank
         # large_rand_matrix(rank, n_user): N(0,1)/100, column-major rank x n_user  (:204-205)
         ndt, tdt = self._dev_np(), self._dev_t()
-        if self._init_user_factors is not None:
-            U0 = np.array(self._init_user_factors, dtype=ndt, order="C")
-            if U0.shape != (n_user, k):
-                raise ValueError("initial user factors must be n_user x rank")
+        on_device = self._factor_init == "device"
+        if on_device:
+            U, V = self._initial_factors_device(be, n_user, n_item)
         else:
-            U0 = (self._rng.standard_normal((n_user, k)) * 0.01).astype(ndt)
-        if self.components is None:
-            if self._solver_code == 1:                                             # CG -> zeros (:219-231)
-                V0 = np.zeros((n_item, k), dtype=ndt)
+            if self._init_user_factors is not None:
+                U0 = np.array(self._init_user_factors, dtype=ndt, order="C")
+                if U0.shape != (n_user, k):
+                    raise ValueError("initial user factors must be n_user x rank")
             else:
-                V0 = (self._rng.standard_normal((n_item, k)) * 0.01).astype(ndt)
-        else:
-            if self.components.shape != (k, n_item):                               # :246-248
-                raise ValueError("init must be rank x n_item")
-            V0 = np.array(self.components.T, dtype=ndt, order="C")
-        if self._with_bias:                                                        # :208-245: the two rows of ones
-            U0 = U0.copy()
-            V0 = V0.copy()
-            U0[:, 0] = 1.0
-            V0[:, k - 1] = 1.0
-        if self._non_negative:                                                     # NNLS: :252-255
-            U0, V0 = np.abs(U0), np.abs(V0)
+                U0 = (self._rng.standard_normal((n_user, k)) * 0.01).astype(ndt)
+            if self.components is None:
+                if self._solver_code == 1:                                             # CG -> zeros (:219-231)
+                    V0 = np.zeros((n_item, k), dtype=ndt)
+                else:
+                    V0 = (self._rng.standard_normal((n_item, k)) * 0.01).astype(ndt)
+            else:
+                if self.components.shape != (k, n_item):                               # :246-248
+                    raise ValueError("init must be rank x n_item")
+                V0 = np.array(self.components.T, dtype=ndt, order="C")
+            if self._with_bias:                                                        # :208-245: the two rows of ones
+                U0 = U0.copy()
+                V0 = V0.copy()
+                U0[:, 0] = 1.0
+                V0[:, k - 1] = 1.0
+            if self._non_negative:                                                     # NNLS: :252-255
+                U0, V0 = np.abs(U0), np.abs(V0)
         # one orientation crosses the boundary (f64 values as in dgCMatrix@x); the item-user orientation
         # c_iu = t_shallow(as.csr.matrix(c_ui)) (:190) and the f32 values are produced on the device
         x64 = be.to_device(c_ui.data, torch.float64)
@@ -230,8 +290,9 @@ class WRMF:
                          cg_steps=self._cg_steps, with_bias=self._with_bias)
         als.cnt_user = torch.diff(d_iu[0]).to(tdt)                                 # cnt_i in the reference (:312)
         als.cnt_item = torch.diff(d_ui[0]).to(tdt)                                 # cnt_u (:311)
-        U = be.to_device(U0, tdt)
-        V = be.to_device(V0, tdt)
+        if not on_device:
+            U = be.to_device(U0, tdt)
+            V = be.to_device(V0, tdt)
         self.global_bias = 0.0
         if self._with_bias:                                                        # :259-277
             user_bias = torch.zeros(n_user, dtype=tdt, device=U.device)
@@ -313,29 +374,48 @@ class WRMF:
         # the SAME initial factors on every rank: drawn once from the model's generator ...  (copies: the broadcast below
         # writes into them, and the caller's arrays are not ours to change)
         ndt, tdt = self._dev_np(), self._dev_t()
-        if self._init_user_factors is not None:
-            U0 = np.array(self._init_user_factors, dtype=ndt, order="C")
-            if U0.shape != (n_user, k):
-                raise ValueError("initial user factors must be n_user x rank")
+        on_device = self._factor_init == "device"
+        if on_device:
+            dev0 = be.to_device(np.zeros(1, dtype=np.float32), torch.float32).device
+            # ONE seed instead of the two matrices: rank 0's 8 bytes are broadcast and every rank writes the replicated factors on
+            # its own device -- a value is a function of (seed, stream, row, col, rank), so they are the same at every world size
+            # (a matrix that was GIVEN, `init` / `_init_user_factors`, is broadcast as below: rank 0's copy wins)
+            src0 = dist.get_global_rank(self._group, 0) if self._group is not None else 0
+
+            def share_seed(seed):
+                t = torch.tensor([seed], dtype=torch.int64).to(dev0)
+                dist.broadcast(t, src=src0, group=self._group)
+                return int(t.cpu()[0])
+
+            def share_given(buf):
+                t = torch.from_numpy(buf).to(dev0)
+                dist.broadcast(t, src=src0, group=self._group)
+                buf[...] = t.cpu().numpy()
+            U_all, V_all = self._initial_factors_device(be, n_user, n_item, share_seed, share_given)
         else:
-            U0 = (self._rng.standard_normal((n_user, k)) * 0.01).astype(ndt)
-        if self.components is None:
-            V0 = (np.zeros((n_item, k), dtype=ndt) if self._solver_code == 1 else
-                  (self._rng.standard_normal((n_item, k)) * 0.01).astype(ndt))
-        else:
-            if self.components.shape != (k, n_item):
-                raise ValueError("init must be rank x n_item")
-            V0 = np.array(self.components.T, dtype=ndt, order="C")
-        if self._with_bias:                                                        # :208-245: the two rows of ones
-            U0[:, 0] = 1.0
-            V0[:, k - 1] = 1.0
-        if self._non_negative:
-            U0, V0 = np.abs(U0), np.abs(V0)
-        dev0 = be.to_device(np.zeros(1, dtype=np.float32), torch.float32).device
-        for buf in (U0, V0):   # ... and rank 0's copy wins if the ranks were seeded differently
-            t = torch.from_numpy(buf).to(dev0)
-            dist.broadcast(t, src=dist.get_global_rank(self._group, 0) if self._group is not None else 0, group=self._group)
-            buf[...] = t.cpu().numpy()
+            if self._init_user_factors is not None:
+                U0 = np.array(self._init_user_factors, dtype=ndt, order="C")
+                if U0.shape != (n_user, k):
+                    raise ValueError("initial user factors must be n_user x rank")
+            else:
+                U0 = (self._rng.standard_normal((n_user, k)) * 0.01).astype(ndt)
+            if self.components is None:
+                V0 = (np.zeros((n_item, k), dtype=ndt) if self._solver_code == 1 else
+                      (self._rng.standard_normal((n_item, k)) * 0.01).astype(ndt))
+            else:
+                if self.components.shape != (k, n_item):
+                    raise ValueError("init must be rank x n_item")
+                V0 = np.array(self.components.T, dtype=ndt, order="C")
+            if self._with_bias:                                                        # :208-245: the two rows of ones
+                U0[:, 0] = 1.0
+                V0[:, k - 1] = 1.0
+            if self._non_negative:
+                U0, V0 = np.abs(U0), np.abs(V0)
+            dev0 = be.to_device(np.zeros(1, dtype=np.float32), torch.float32).device
+            for buf in (U0, V0):   # ... and rank 0's copy wins if the ranks were seeded differently
+                t = torch.from_numpy(buf).to(dev0)
+                dist.broadcast(t, src=dist.get_global_rank(self._group, 0) if self._group is not None else 0, group=self._group)
+                buf[...] = t.cpu().numpy()
         # ---- my users' rows: a slice of the caller's CSR arrays, uploaded as the CSC-by-user block it already is ----
         cnt_user = torch.from_numpy(np.diff(x.indptr).astype(np.int64))
         bounds_u = balanced_bounds(cnt_user, ws)
@@ -380,8 +460,13 @@ class WRMF:
                          lay_item=lay_i, with_bias=self._with_bias)
         als.cnt_user = be.to_device(cnt_user.numpy().astype(ndt), tdt)
         als.cnt_item = cnt_item.to(tdt)
-        U = lay_u.from_global(lay_u.alloc(k, dev0, tdt), be.to_device(U0, tdt))
-        V = lay_i.from_global(lay_i.alloc(k, dev0, tdt), be.to_device(V0, tdt))
+        if on_device:
+            U = lay_u.from_global(lay_u.alloc(k, dev0, tdt), U_all)
+            V = lay_i.from_global(lay_i.alloc(k, dev0, tdt), V_all)
+            del U_all, V_all
+        else:
+            U = lay_u.from_global(lay_u.alloc(k, dev0, tdt), be.to_device(U0, tdt))
+            V = lay_i.from_global(lay_i.alloc(k, dev0, tdt), be.to_device(V0, tdt))
         if self._with_bias:                                                        # :259-277, sweep by sweep over the shards
             user_bias = torch.zeros(lay_u.rows, dtype=tdt, device=dev0)
             item_bias = torch.zeros(lay_i.rows, dtype=tdt, device=dev0)

@@ -1,5 +1,5 @@
 """where a WRMF.fit_transform call spends its time outside the solves (host-side conversions, upload, schedules): cProfile of one
-call at 1M x 100k, 5e7 non-zeros.  python tools/gpu_fit_profile.py"""
+call at 1M x 100k, 5e7 non-zeros.  [RANK=128] [FACTOR_INIT=device] python tools/gpu_fit_profile.py"""
 import cProfile
 import os
 import pstats
@@ -16,7 +16,8 @@ from rsparse_amd import WRMF, synth
 d = synth.make_dataset(1_000_000, 100_000, device="cpu", feedback="implicit")
 p, i, x = (t.numpy() for t in d["c_iu"])
 m = sp.csc_matrix((x.astype(np.float64), i, p), shape=(100_000, 1_000_000)).T.tocsr()
-model = WRMF(rank=int(os.environ.get("RANK", "64")), lambda_=0.1, feedback="implicit", solver="conjugate_gradient", precision="float", rng=1)
+kw = {"factor_init": os.environ["FACTOR_INIT"]} if "FACTOR_INIT" in os.environ else {}   # (unset: the constructor's default, "host")
+model = WRMF(rank=int(os.environ.get("RANK", "64")), lambda_=0.1, feedback="implicit", solver="conjugate_gradient", precision="float", rng=1, **kw)
 model.fit_transform(m, n_iter=1, convergence_tol=-1)
 torch.cuda.synchronize()
 for n_iter in (1, 10):
