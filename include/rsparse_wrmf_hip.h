@@ -523,6 +523,38 @@ int rsparse_hip_sparse_approximation(int n_rows, int n_cols, const int32_t* p, c
                                      const double* X, const double* Y, int rank, double* values_out);
 
 /* ------------------------------------------------------------------------------------------------
+ * why this item: per-item contributions to a score (Hu, Koren and Volinsky, section 5; `explain` of the `implicit` library)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The folded-in embedding of a row is linear in the row's entries: with A_u = B + d I + sum_t a_t y_t y_t^T over the stored
+ * positions t of row u (y_t = d_V[d_x_j[t]], d = diag + diag_per_nnz * len(row u)) and A_u z = y_i for a target item i,
+ *   score(u, i) = sum_t b_t (z . y_t),
+ * and term t is what the interaction with item d_x_j[t] contributes.  Implicit feedback: B = the Gramian with lambda in it, a = c -
+ * 1, b = c, diag = diag_per_nnz = 0; explicit: B absent (NULL), a = 1, b = r, diag = lambda, or diag_per_nnz = lambda under
+ * dynamic_lambda.
+ *   d_V: n_items x r row-major; d_base: r x r symmetric or NULL; (d_x_p, d_x_j): the rows as CSR over n_users, d_wa / d_wb one per
+ *   stored position; (d_t_p, d_t_j): the targets as CSR over the same users; d_out_p[q]: where the segment of target q starts in
+ *   d_contrib (len(row of q's user) entries, in row order).
+ *   d_contrib[d_out_p[q] + t] = b_t (z . y_t) in the factors' type; d_total[q] = the segment's sum, in double, in a fixed order;
+ *   d_flags[u] = 1 when A_u is not positive definite to working precision (a Cholesky pivot d_j <= 2 r eps a_jj) -- every
+ *   output of that user's targets is then NaN --, 0 for every other user that has a target.
+ * A user with an empty row is not factored: totals 0, flag 0.  Of a user without targets nothing is written, its flag included.
+ * The sums have a fixed order and there are no atomics: a repeated call returns the same bits.  Enqueued on `stream` without
+ * synchronisation.  Valid p arrays and indices in [0, n_items) are preconditions, not checked (they live on the device), as for
+ * rsparse_hip_score_pairs_device; nothing outside d_V is read for an index outside it, and what depends on it is NaN.
+ * NULL among d_V, d_x_p, d_t_p, d_flags, or d_t_j given without d_x_j, d_wa, d_wb, d_out_p, d_contrib, d_total; n_items < 0,
+ * n_users < 0, r < 1 -> ERR_INVALID, before a device is touched; r > 128 (both element types: the system lives in LDS) ->
+ * ERR_UNSUPPORTED; n_users == 0, or d_t_j == NULL (no target at all) -> OK, nothing is launched. */
+int rsparse_hip_explain_device(const float* d_V, int n_items, int r, const float* d_base, double diag, double diag_per_nnz,
+                               int n_users, const int32_t* d_x_p, const int32_t* d_x_j, const float* d_wa, const float* d_wb,
+                               const int32_t* d_t_p, const int32_t* d_t_j, const int64_t* d_out_p, float* d_contrib,
+                               double* d_total, int32_t* d_flags, void* stream);
+int rsparse_hip_explain_f64_device(const double* d_V, int n_items, int r, const double* d_base, double diag, double diag_per_nnz,
+                                   int n_users, const int32_t* d_x_p, const int32_t* d_x_j, const double* d_wa, const double* d_wb,
+                                   const int32_t* d_t_p, const int32_t* d_t_j, const int64_t* d_out_p, double* d_contrib,
+                                   double* d_total, int32_t* d_flags, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * initial factors drawn on the device: a counter-based normal generator
  * ---------------------------------------------------------------------------------------------- */
 

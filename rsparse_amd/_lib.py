@@ -82,6 +82,10 @@ SIGNATURES = {
                                             _vp, _vp, _vp]),
     "rsparse_hip_score_pairs_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_dbl, _vp, _vp, _vp, _vp, _vp]),
     "rsparse_hip_score_pairs_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_dbl, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_explain_device": (_c_int, [_vp, _c_int, _c_int, _vp, _c_dbl, _c_dbl, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _vp]),
+    "rsparse_hip_explain_f64_device": (_c_int, [_vp, _c_int, _c_int, _vp, _c_dbl, _c_dbl, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _vp, _vp, _vp, _vp]),
     "rsparse_hip_init_factors_device": (_c_int, [_c_u64, _c_int, _c_i64, _c_int, _c_int, _c_i64, _c_dbl, _c_int, _c_int, _vp, _vp]),
     "rsparse_hip_init_factors_f64_device": (_c_int, [_c_u64, _c_int, _c_i64, _c_int, _c_int, _c_i64, _c_dbl, _c_int, _c_int, _vp,
                                                      _vp]),

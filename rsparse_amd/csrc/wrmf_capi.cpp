@@ -1545,6 +1545,15 @@ int rsparse_hip_score_pairs_device(const float* d_U, const float* d_V, int n_row
 }
 
 // `_f64_device`: wrmf_f64_capi.cpp
+int rsparse_hip_explain_device(const float* d_V, int n_items, int r, const float* d_base, double diag, double diag_per_nnz,
+                               int n_users, const int32_t* d_x_p, const int32_t* d_x_j, const float* d_wa, const float* d_wb,
+                               const int32_t* d_t_p, const int32_t* d_t_j, const int64_t* d_out_p, float* d_contrib,
+                               double* d_total, int32_t* d_flags, void* stream) {
+  return explain_device(d_V, n_items, r, d_base, diag, diag_per_nnz, n_users, d_x_p, d_x_j, d_wa, d_wb, d_t_p, d_t_j, d_out_p,
+                        d_contrib, d_total, d_flags, (hipStream_t)stream);
+}
+
+// `_f64_device`: wrmf_f64_capi.cpp
 int rsparse_hip_init_factors_device(uint64_t seed, int stream, int64_t row0, int n_rows, int rank, int64_t ld, double scale,
                                     int abs_values, int ones_col, void* d_out, void* hip_stream) {
   return init_factors_device(seed, stream, row0, n_rows, rank, ld, scale, abs_values, ones_col, static_cast<float*>(d_out),

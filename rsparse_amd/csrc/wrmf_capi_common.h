@@ -227,6 +227,24 @@ int score_pairs_device(const T* d_U, const T* d_V, int n_rows, int n_cols, int r
   return RSPARSE_HIP_OK;
 }
 
+// rsparse_hip_explain_device / _f64_device (kernel: wrmf_explain.hip).  The rank ceiling is the kernel's (one k x k system per
+// user in LDS), the same for both element types.
+template <class T>
+int explain_device(const T* d_V, int n_items, int r, const T* d_base, double diag, double diag_per_nnz, int n_users,
+                   const int32_t* d_x_p, const int32_t* d_x_j, const T* d_wa, const T* d_wb, const int32_t* d_t_p,
+                   const int32_t* d_t_j, const int64_t* d_out_p, T* d_contrib, double* d_total, int32_t* d_flags, hipStream_t s) {
+  if (!d_V || !d_x_p || !d_t_p || !d_flags) return fail(RSPARSE_HIP_ERR_INVALID, "V, x_p, t_p or flags is NULL");
+  if (d_t_j && (!d_x_j || !d_wa || !d_wb || !d_out_p || !d_contrib || !d_total))
+    return fail(RSPARSE_HIP_ERR_INVALID, "targets without x_j, wa, wb, out_p, contrib or total");
+  if (n_items < 0 || n_users < 0 || r < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_items < 0, n_users < 0 or r < 1)");
+  if (r > 128) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "explain: r > 128 is not on the device path");
+  if (n_users == 0 || !d_t_j) return RSPARSE_HIP_OK;   // (no user, or no target at all: t_j is NULL)
+  hipError_t e = launch_explain(d_V, n_items, r, d_base, diag, diag_per_nnz, n_users, d_x_p, d_x_j, d_wa, d_wb, d_t_p, d_t_j,
+                                d_out_p, d_contrib, d_total, d_flags, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_explain");
+  return RSPARSE_HIP_OK;
+}
+
 // rsparse_hip_init_factors_device / _f64_device (kernel: wrmf_init.hip).  No rank ceiling: nothing here depends on a solver.
 template <class T>
 int init_factors_device(uint64_t seed, int stream, int64_t row0, int n_rows, int rank, int64_t ld, double scale, int abs_values,

@@ -361,6 +361,15 @@ int rsparse_hip_score_pairs_f64_device(const double* d_U, const double* d_V, int
                             });
 }
 
+// per-item contributions to a score from double factors (kernel: wrmf_explain.hip; the fp32 form: wrmf_capi.cpp)
+int rsparse_hip_explain_f64_device(const double* d_V, int n_items, int r, const double* d_base, double diag, double diag_per_nnz,
+                                   int n_users, const int32_t* d_x_p, const int32_t* d_x_j, const double* d_wa, const double* d_wb,
+                                   const int32_t* d_t_p, const int32_t* d_t_j, const int64_t* d_out_p, double* d_contrib,
+                                   double* d_total, int32_t* d_flags, void* stream) {
+  return explain_device(d_V, n_items, r, d_base, diag, diag_per_nnz, n_users, d_x_p, d_x_j, d_wa, d_wb, d_t_p, d_t_j, d_out_p,
+                        d_contrib, d_total, d_flags, (hipStream_t)stream);
+}
+
 // initial factors in double (kernel: wrmf_init.hip; the fp32 form: wrmf_capi.cpp)
 int rsparse_hip_init_factors_f64_device(uint64_t seed, int stream, int64_t row0, int n_rows, int rank, int64_t ld, double scale,
                                         int abs_values, int ones_col, void* d_out, void* hip_stream) {

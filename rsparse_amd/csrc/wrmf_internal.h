@@ -361,6 +361,16 @@ hipError_t launch_score_pairs(const T* U, const T* V, int n_rows, int n_cols, in
 hipError_t launch_score_error_sums(const double* scores, const double* actual, const int32_t* P, int n_rows, double* sse,
                                    double* sae, hipStream_t s);
 
+// per-item contributions to a score (wrmf_explain.hip), T = float or double, 1 <= r <= 128: for every target q (t_p / t_j: CSR
+// over the users) of a user with the row (x_p / x_j) and the per-non-zero weights wa (assembly) and wb (contribution),
+// contrib[out_p[q] + t] = wb_t (z . V[x_j[t]]) with (base + (diag + diag_per_nnz len) I + sum_t wa_t V[x_j[t]] V[x_j[t]]^T) z =
+// V[t_j[q]], and total[q] their sum; flags[u] = 1 (outputs NaN) where the system is not positive definite, 0 for every other
+// user that has a target.  One workgroup per user.
+template <class T>
+hipError_t launch_explain(const T* V, int n_items, int r, const T* base, double diag, double diag_per_nnz, int n_users,
+                          const int32_t* x_p, const int32_t* x_j, const T* wa, const T* wb, const int32_t* t_p, const int32_t* t_j,
+                          const int64_t* out_p, T* contrib, double* total, int32_t* flags, hipStream_t s);
+
 // initial factors drawn on the device (wrmf_init.hip), T = float or double: the rows [row0, row0 + n_rows) of the (., rank) matrix
 // of `stream` (0 users, 1 items) under `seed`, written to `out` (row row0's first element, leading dimension ld >= rank) as
 // scale * N(0, 1), |.| with abs_values, the column ones_col (-1: none) exactly 1.  The generator: rsparse_wrmf_hip.h.

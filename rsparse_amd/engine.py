@@ -54,6 +54,36 @@ def equal_bounds(n, world_size):
     return [(min(n, r * B), min(n, (r + 1) * B)) for r in range(world_size)]
 
 
+def explain_segments(x_p, t_p):
+    """the ragged layout of `explain_pairs`: target q of user u owns len(row u) contributions -> int64 indptr of n targets + 1
+    (on the device of the inputs; x_p, t_p: the CSR row pointers of the rows and of the targets over the same users)"""
+    lens = torch.diff(x_p.to(torch.int64))
+    seg = torch.repeat_interleave(lens, torch.diff(t_p.to(torch.int64)))
+    indptr = torch.zeros(int(seg.numel()) + 1, dtype=torch.int64, device=x_p.device)
+    torch.cumsum(seg, dim=0, out=indptr[1:])
+    return indptr
+
+
+def explain_top_n(contrib, indptr, items, n):
+    """the n largest contributions of every segment of the ragged output, descending, equal values in storage order (the lower
+    item index of a canonical row) -> (top_items int32, top_contrib in contrib's type), both n_pairs x n, padded with -1 / 0.
+    Two stable torch sorts where the data is: by value, then by segment."""
+    n_pairs = int(indptr.numel()) - 1
+    dev = contrib.device
+    top_items = torch.full((n_pairs, n), -1, dtype=torch.int32, device=dev)
+    top_contrib = torch.zeros((n_pairs, n), dtype=contrib.dtype, device=dev)
+    if n_pairs == 0 or contrib.numel() == 0:
+        return top_items, top_contrib
+    seg = torch.repeat_interleave(torch.arange(n_pairs, device=dev), torch.diff(indptr))
+    by_value = torch.argsort(contrib, descending=True, stable=True)
+    perm = by_value[torch.argsort(seg[by_value], stable=True)]      # segments ascending, values descending inside
+    pos = torch.arange(int(contrib.numel()), device=dev) - indptr[seg]   # (seg itself is sorted: seg[perm] == seg)
+    keep = pos < n
+    top_items[seg[keep], pos[keep]] = items[perm[keep]].to(torch.int32)
+    top_contrib[seg[keep], pos[keep]] = contrib[perm[keep]]
+    return top_items, top_contrib
+
+
 def default_subblocks(world_size):
     """Sub-blocks per rank and half-iteration: with several ranks the all-gather of a solved block (640 MB per rank on
     the user side of config 3) costs about as much as the solve, so it is pipelined sub-block by sub-block.  A caller
@@ -415,6 +445,38 @@ class HipBackend:
                       None if actual is None else actual.data_ptr(), None if scores is None else scores.data_ptr(),
                       None if sse is None else sse.data_ptr(), None if sae is None else sae.data_ptr(), self._stream()))
         return scores, sse, sae
+
+    def explain_pairs(self, V, base, diag, diag_per_nnz, x_p, x_j, wa, wb, t_p, t_j):
+        """what every interaction of a row contributes to the scores of the row's target items (wrmf_explain.hip): for the users
+        of the CSR rows (x_p, x_j: int32 on the device; wa, wb: the assembly and contribution weight of every stored position, in
+        V's type) and their targets (t_p, t_j: CSR over the same users), with A_u = base + (diag + diag_per_nnz len) I + sum_t wa_t
+        v_t v_t^T and A_u z = V[target]: contrib = wb_t (z . v_t), one per (target, stored position of its user's row), and its
+        sum per target.  base: rank x rank symmetric on the device, or None.  -> (contrib: V's type, total: float64 of n targets,
+        flags: int32 of n users, 1 = not positive definite and the user's outputs NaN, indptr: int64 of n targets + 1 into
+        contrib), all on the device."""
+        assert V.dtype in (torch.float32, torch.float64) and x_p.dtype == t_p.dtype == torch.int32
+        V = V.contiguous()
+        dev, dt = V.device, V.dtype
+        n_user, n_pairs = int(x_p.numel()) - 1, int(t_j.numel())
+        assert int(t_p.numel()) == n_user + 1
+        indptr = explain_segments(x_p, t_p)
+        flags = torch.zeros(n_user, dtype=torch.int32, device=dev)
+        total = torch.zeros(n_pairs, dtype=torch.float64, device=dev)
+        n_out = int(indptr[-1]) if n_pairs else 0
+        contrib_buf = torch.zeros(max(n_out, 1), dtype=dt, device=dev)   # (an empty view has no address to pass)
+        if n_user == 0 or n_pairs == 0:
+            return contrib_buf[:n_out], total, flags, indptr
+        one = lambda t, d: t.to(d).contiguous() if t.numel() else torch.zeros(1, dtype=d, device=dev)
+        x_j, wa, wb = one(x_j, torch.int32), one(wa, dt), one(wb, dt)
+        if base is not None:
+            base = base.to(dt).contiguous()
+            assert tuple(base.shape) == (V.shape[1], V.shape[1])
+        fn = self.lib.rsparse_hip_explain_f64_device if dt == torch.float64 else self.lib.rsparse_hip_explain_device
+        _lib.check(fn(V.data_ptr(), int(V.shape[0]), int(V.shape[1]), None if base is None else base.data_ptr(), float(diag),
+                      float(diag_per_nnz), n_user, x_p.data_ptr(), x_j.data_ptr(), wa.data_ptr(), wb.data_ptr(), t_p.data_ptr(),
+                      t_j.contiguous().data_ptr(), indptr.data_ptr(), contrib_buf.data_ptr(), total.data_ptr(), flags.data_ptr(),
+                      self._stream()))
+        return contrib_buf[:n_out], total, flags, indptr
 
     def held_out_ranks(self, U, V, nr_p, nr_j, exclude0, act_p, act_j, max_chunk_users=0):
         """where the held-out items stand among all admissible items (wrmf_ranks.hip): for the rows of U (n x rank) against V

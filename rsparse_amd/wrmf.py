@@ -40,6 +40,40 @@ class TopItems(np.ndarray):
     scores = None
 
 
+class Explanation:
+    """Result of `WRMF.explain`: what every interaction of a user contributes to the model's score of a (user, item) pair.
+      pairs_indptr, pairs_indices   the canonical CSR pattern of `pairs`; pair q is its q-th stored position
+      total                         float64, one per pair: the sum of the pair's contributions = the score `transform` + `score` give
+      indptr                        int64, n_pairs + 1: the contributions of pair q are [indptr[q], indptr[q + 1]), one per stored
+                                    entry of its user's row of x, in the row's (ascending item) order
+      items, contrib                the liked item (int32) and the contribution (the model's precision) of every entry; None
+                                    under torch.distributed.  After `explain(..., n=...)` they are still on the device and are
+                                    copied on first use.
+      top_items, top_contrib        (n_pairs x n), only with `n`: the n largest contributions of every pair, descending, equal
+                                    values with the lower item first, padded with -1 / 0"""
+
+    def __init__(self, pairs_indptr, pairs_indices, total, indptr, ragged=None, top_items=None, top_contrib=None, dtype=np.float64):
+        self.pairs_indptr, self.pairs_indices, self.total, self.indptr = pairs_indptr, pairs_indices, total, indptr
+        self.top_items, self.top_contrib = top_items, top_contrib
+        self._ragged, self._dtype = ragged, dtype     # (items, contrib) as tensors, or None
+
+    def _host(self):
+        if self._ragged is not None and torch.is_tensor(self._ragged[0]):
+            items, contrib = self._ragged
+            self._ragged = (items.cpu().numpy().astype(np.int32), contrib.cpu().numpy().astype(self._dtype))
+        return self._ragged
+
+    @property
+    def items(self):
+        r = self._host()
+        return None if r is None else r[0]
+
+    @property
+    def contrib(self):
+        r = self._host()
+        return None if r is None else r[1]
+
+
 logger = logging.getLogger("rsparse_amd")   # the reference logs through lgr's "rsparse" logger (R/zzz.R); silent unless configured
 
 
@@ -883,6 +917,127 @@ class WRMF:
             out.update({k + "_per_user": v for k, v in per.items()})
             out["n_adm_per_user"] = n_adm.cpu().numpy().astype(np.int32)
         return out
+
+    def explain(self, x, pairs, n=None):
+        """Why this item: the score of a (user, item) pair taken apart into what each interaction of the user contributes (Hu,
+        Koren and Volinsky, section 5; `explain` of the `implicit` library).  The embedding `transform` gives a row of `x` solves
+        A_u x_u = sum_j b_uj y_j with A_u = B + sum_j a_uj y_j y_j^T over the row's entries, so
+            score(u, i) = sum_j b_uj (z_ui . y_j),    A_u z_ui = y_i,
+        and term j is what the interaction with item j contributes to item i's score (implicit feedback: B = the stored Gramian
+        with lambda in it, a = c - 1, b = c; explicit: B = lambda I, times the row's length under dynamic_lambda, a = 1, b = r; c, r
+        the preprocessed values).  `x` and `pairs` as in `score` (the values of `pairs` are ignored, stored zeros are positions); x is
+        canonicalised (columns sorted, duplicates summed) and preprocessed as `transform` does.  One k x k factorisation per user
+        and two triangular solves per pair, on the device (wrmf_explain.hip).  Returns an `Explanation`.  With `n`, also the n
+        largest contributions of every pair, selected on the device; only they and the totals are copied back.
+        Supported: implicit and explicit feedback without user/item biases and with global_bias == 0, every solver but "nnls" (a
+        non-negative embedding is not linear in the row: no such decomposition exists), rank <= 128; anything else raises
+        UnsupportedOnDevice.  A row whose system is not positive definite raises as a singular system does in `transform`.
+        Under torch.distributed every rank explains the block of rows it transforms; `n` is required there."""
+        x, pat = self._pairs_pattern(x, pairs, "pairs")
+        no = lambda what: _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "explain: %s is not on the device path" % what)
+        if self._non_negative:
+            raise no('solver="nnls" (the embedding is not linear in the row, so no decomposition exists)')
+        if self._with_bias:
+            raise no("with_user_item_bias=True")
+        if self.global_bias != 0.0:
+            raise no("a global bias (with_global_bias=True)")
+        if self._rank > 128:
+            raise no("rank > 128")
+        if n is not None:
+            n = int(n)
+            if n < 1:
+                raise ValueError("n must be at least 1")
+        ws, me = self._dist()
+        if ws > 1 and n is None:
+            raise no("the ragged output under torch.distributed (pass n= for the n largest contributions of every pair)")
+        from .engine import explain_top_n
+        be = self._backend()
+        a, b, _ = self._my_rows(x)
+        mine = sp.csr_matrix(x[a:b])
+        mine.sum_duplicates()
+        xt = self._preprocess(sp.csc_matrix(mine.T, dtype=np.float64))   # CSC of x^T == CSR of x, as _transform_device
+        xt.sort_indices()
+        tdt = self._V.dtype
+        c = np.asarray(xt.data, dtype=np.float64)
+        if self._feedback == "implicit":
+            base, diag, per_nnz, wa = self._XtX, 0.0, 0.0, c - 1.0
+        else:
+            base, wa = None, np.ones_like(c)
+            diag, per_nnz = (0.0, self._lambda) if self._dynamic_lambda else (self._lambda, 0.0)
+        x_p, x_j = be.to_device(xt.indptr, torch.int32), be.to_device(xt.indices, torch.int32)
+        tgt = pat[a:b]
+        t_p, t_j = be.to_device(tgt.indptr, torch.int32), be.to_device(tgt.indices, torch.int32)
+        fn = be.explain_pairs if hasattr(be, "explain_pairs") else self._explain_host
+        contrib, total, flags, indptr = fn(self._V, base, diag, per_nnz, x_p, x_j, be.to_device(wa, tdt), be.to_device(c, tdt),
+                                           t_p, t_j)
+        bad = torch.sum(flags != 0).to(torch.int64).reshape(1)
+        if ws > 1:   # every rank raises together
+            from .engine import all_reduce_any
+            all_reduce_any(bad, self._group)
+        be.report_numeric(int(bad[0]), 0)
+        # the liked item of every contribution: position t of the row of the pair's user
+        n_pairs = int(t_j.numel())
+        seg = torch.repeat_interleave(torch.arange(n_pairs, device=indptr.device), torch.diff(indptr))
+        user = torch.repeat_interleave(torch.arange(int(x_p.numel()) - 1, device=indptr.device), torch.diff(t_p.to(torch.int64)))
+        at = x_p.to(torch.int64)[user[seg]] + (torch.arange(int(contrib.numel()), device=indptr.device) - indptr[seg])
+        items = x_j[at]
+        top_i = top_c = None
+        if n is not None:
+            top_i, top_c = explain_top_n(contrib, indptr, items, n)
+        if ws > 1:
+            bounds = [(int(pat.indptr[r0]), int(pat.indptr[r1])) for r0, r1 in self._row_bounds]
+            total, top_i, top_c = (self._share_rows(v, bounds, int(pat.nnz)) for v in (total, top_i, top_c))
+        lens = np.diff(np.asarray(xt.indptr, dtype=np.int64))
+        full_indptr = None
+        if ws <= 1:
+            full_indptr = np.concatenate([[0], np.cumsum(np.repeat(lens, np.diff(tgt.indptr)))]).astype(np.int64)
+        host = lambda t, dt: None if t is None else t.cpu().numpy().astype(dt)
+        return Explanation(pat.indptr.copy(), pat.indices.copy(), host(total, np.float64), full_indptr,
+                           ragged=None if ws > 1 else (items, contrib), top_items=host(top_i, np.int32),
+                           top_contrib=host(top_c, self._np_dtype()), dtype=self._np_dtype())
+
+    @staticmethod
+    def _explain_host(V, base, diag, diag_per_nnz, x_p, x_j, wa, wb, t_p, t_j, batch=256):
+        """`explain_pairs` for a backend without it (the CPU stand-in of the tests), in plain torch double ops: the users in
+        batches, their rows padded to the batch's longest, one batched Cholesky and one batched solve per batch.  Same rules as
+        wrmf_explain.hip (an empty row: totals 0; a system torch finds not positive definite: flag 1 and NaN)."""
+        from .engine import explain_segments
+        dev, k = V.device, int(V.shape[1])
+        V64 = V.to(torch.float64)
+        xp, tp = x_p.to(torch.int64), t_p.to(torch.int64)
+        xj, tj = x_j.to(torch.int64), t_j.to(torch.int64)
+        a64, b64 = wa.to(torch.float64), wb.to(torch.float64)
+        n_user = int(xp.numel()) - 1
+        indptr = explain_segments(x_p, t_p)
+        contrib = torch.zeros(int(indptr[-1]), dtype=torch.float64, device=dev)
+        total = torch.zeros(int(tj.numel()), dtype=torch.float64, device=dev)
+        flags = torch.zeros(n_user, dtype=torch.int32, device=dev)
+        lens, tcnt = torch.diff(xp), torch.diff(tp)
+        users = torch.nonzero((tcnt > 0) & (lens > 0)).flatten()
+        B0 = torch.zeros((k, k), dtype=torch.float64, device=dev) if base is None else base.to(torch.float64)
+        eye = torch.eye(k, dtype=torch.float64, device=dev)
+        for s0 in range(0, int(users.numel()), batch):
+            uu = users[s0:s0 + batch]
+            ar = torch.arange(int(lens[uu].max()), device=dev)
+            at = torch.arange(int(tcnt[uu].max()), device=dev)
+            m = ar[None, :] < lens[uu][:, None]                                   # users x positions
+            mt = at[None, :] < tcnt[uu][:, None]                                  # users x targets
+            e = torch.where(m, xp[uu][:, None] + ar[None, :], torch.zeros_like(ar)[None, :])
+            q = torch.where(mt, tp[uu][:, None] + at[None, :], torch.zeros_like(at)[None, :])
+            Y = V64[xj[e]] * m[:, :, None]
+            A = B0 + (diag + diag_per_nnz * lens[uu].to(torch.float64))[:, None, None] * eye \
+                + (Y * (a64[e] * m)[:, :, None]).transpose(1, 2) @ Y
+            L, info = torch.linalg.cholesky_ex(A)
+            bad = info != 0
+            L = torch.where(bad[:, None, None], eye, L)
+            Z = torch.cholesky_solve(V64[tj[q]].transpose(1, 2), L)              # users x k x targets
+            C = (Y @ Z) * (b64[e] * m)[:, :, None]                               # users x positions x targets
+            C = torch.where(bad[:, None, None], torch.full_like(C, float("nan")), C)
+            both = m[:, :, None] & mt[:, None, :]
+            contrib[(indptr[q][:, None, :] + ar[None, :, None])[both]] = C[both]
+            total[q[mt]] = torch.where(m[:, :, None], C, torch.zeros_like(C)).sum(dim=1)[mt]
+            flags[uu] = bad.to(torch.int32)
+        return contrib.to(V.dtype), total, flags, indptr
 
     def similar_items(self, items=None, k=10, items_exclude=(), exclude_self=True):
         """R/MatrixFactorizationRecommender.R:79-116 (`get_similar_items`: cosine similarity on the L2-normalised item
