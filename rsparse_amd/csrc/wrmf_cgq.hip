@@ -757,7 +757,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
               float t = tscr[pos];
 #pragma unroll
               for (int s2 = 0; s2 < kMaxSavedSweeps; s2++)
-                if (s2 < a.cg_steps) t = fmaf(alph[s2], tscr[(size_t)(s2 + 1) * a.stream_nnz + pos], t);
+                // (only the steps this row ran -- their alpha is set: a row that ended early wrote no later slot, and what
+                // an earlier call left there may be a NaN, which an alpha of zero does not remove)
+                if (s2 < a.cg_steps && alph[s2] != 0.f) t = fmaf(alph[s2], tscr[(size_t)(s2 + 1) * a.stream_nnz + pos], t);
               const float c = a.vals[p1 + pos];
               const float d = IMPLICIT ? ltgt - t : c - t;
               lacc += IMPLICIT ? c * d * d : d * d;
