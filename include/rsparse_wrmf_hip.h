@@ -360,6 +360,39 @@ int rsparse_hip_top_product_f64_device(const float* d_U, const float* d_V, const
                                        const int32_t* d_exclude0, int n_exclude, double glob_mean, int32_t* d_res,
                                        double* d_scores, void* stream);
 
+/* `$predict` WITHIN per-user candidate lists (two-stage serving, sampled-negative evaluation): what find_top_product returns when
+ * every item that is not a stored position of the user's row of the candidate pattern is added to that user's not_recommend row.
+ * d_cand_p (n_users + 1) / d_cand_j: the pattern as CSR slots, columns ascending and unique within a row; slots are absolute
+ * positions into d_cand_j, so a caller may pass a slice of a larger pattern's row pointers.  d_not_recommend_p / _j (columns
+ * ascending within a row; NULL = nothing) and d_exclude0 (ascending 0-based items) as above.  Admissible: candidates minus
+ * not_recommend minus exclude.  The scores are those of rsparse_hip_score_pairs*_device at the same cells with add = glob_mean (the
+ * double sum of the factors as they are, fp32 or fp64), the order is by exactly these doubles (-0 and +0 tie): best first, equal
+ * scores with the larger index first, and at the k-th score the items the reference's heap keeps.  Exact: no nomination pass, no
+ * margin, no overflow path; work and workspace (8 bytes + 1 bit per candidate, 8 bytes per user, in the library's grow-only
+ * buffer) follow the number of candidates, not n_users x n_items.  d_res: n_users x k row-major, 1-based, NA_integer_ where fewer
+ * than k candidates are admissible (d_scores NaN there).  1 <= k <= RSPARSE_HIP_MAX_TOPK_LARGE.  The call reads the two ends of
+ * d_cand_p back (it waits for the stream once).
+ * NULL where a pointer is required, n_users < 0, n_items < 0, rank < 1, k < 1, n_exclude < 0, row pointers that are negative or
+ * end below their start -> ERR_INVALID; rank > RSPARSE_HIP_MAX_RANK (fp32) / RSPARSE_HIP_MAX_RANK_F64 (f64) or
+ * k > RSPARSE_HIP_MAX_TOPK_LARGE -> ERR_UNSUPPORTED; all before any launch.  A column outside [0, n_items) breaks the
+ * precondition: its score is NaN and nothing outside the factors is read for it. */
+int rsparse_hip_top_candidates_device(const float* d_U, const float* d_V, int n_users, int n_items, int rank, int k,
+                                      const int32_t* d_cand_p, const int32_t* d_cand_j, const int32_t* d_not_recommend_p,
+                                      const int32_t* d_not_recommend_j, const int32_t* d_exclude0, int n_exclude,
+                                      double glob_mean, int32_t* d_res, double* d_scores, void* stream);
+int rsparse_hip_top_candidates_f64_device(const double* d_U, const double* d_V, int n_users, int n_items, int rank, int k,
+                                          const int32_t* d_cand_p, const int32_t* d_cand_j, const int32_t* d_not_recommend_p,
+                                          const int32_t* d_not_recommend_j, const int32_t* d_exclude0, int n_exclude,
+                                          double glob_mean, int32_t* d_res, double* d_scores, void* stream);
+/* the host-pointer form, shaped like rsparse_hip_top_product so that R can bind it: x, y, exclude, res, scores as there; cand_p /
+ * cand_j and not_recommend_p / _j: dgRMatrix slots over the rows of x, 0-based columns.  cand_p[0] != 0, decreasing row pointers,
+ * a candidate column outside [0, nc) or not strictly ascending within its row -> ERR_INVALID (checked on the host); rank >
+ * RSPARSE_HIP_MAX_RANK_F64 -> ERR_UNSUPPORTED (the doubles are used as given).  not_recommend rows need not be sorted here. */
+int rsparse_hip_top_candidates(const double* x, const double* y, int nr, int nc, int rank, unsigned k, unsigned n_threads,
+                               const int32_t* cand_p, const int32_t* cand_j, const int32_t* not_recommend_p,
+                               const int32_t* not_recommend_j, const int32_t* exclude, int n_exclude, double glob_mean,
+                               int32_t* res, double* scores);
+
 /* ------------------------------------------------------------------------------------------------
  * `$get_similar_items`: item-to-item cosine top-k (R/MatrixFactorizationRecommender.R:79-116)
  * ---------------------------------------------------------------------------------------------- */

@@ -82,6 +82,12 @@ SIGNATURES = {
                                             _vp, _vp, _vp]),
     "rsparse_hip_score_pairs_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_dbl, _vp, _vp, _vp, _vp, _vp]),
     "rsparse_hip_score_pairs_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_dbl, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_top_candidates_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl, _vp,
+                                                   _vp, _vp]),
+    "rsparse_hip_top_candidates_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl,
+                                                       _vp, _vp, _vp]),
+    "rsparse_hip_top_candidates": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_uint, _c_uint, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl,
+                                            _vp, _vp]),
     "rsparse_hip_explain_device": (_c_int, [_vp, _c_int, _c_int, _vp, _c_dbl, _c_dbl, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp]),
     "rsparse_hip_explain_f64_device": (_c_int, [_vp, _c_int, _c_int, _vp, _c_dbl, _c_dbl, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

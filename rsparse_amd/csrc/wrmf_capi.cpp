@@ -63,7 +63,8 @@ struct Workspace {
   GrowBuf<float> wide_lu{all};
   GrowBuf<int> met_buf{all};      // ranking metrics (wrmf_metrics.hip): count + list of the users whose idcg takes the long-row launch
   GrowBuf<char> sim_buf{all};     // item-to-item similarity (wrmf_similar.hip): a batch's gathered queries and self-exclusion slots
-  GrowBuf<double> score_buf{all};   // pointwise predictions (wrmf_score.hip): the scores of a call that asks for the error sums only
+  GrowBuf<double> score_buf{all};   // pointwise predictions (wrmf_score.hip): the scores of a call that asks for the error sums only;
+                                    // top-k within candidate lists (wrmf_candidates.hip): its scores / keys, bits and row lists
   GrowBuf<float> mf_G{all};       // wrmf_chol_mf.hip at rank 65..127: XtX padded to 128 x 128
   GrowBuf<float> pad_buf{all};    // ranks that are not a multiple of 4: the padded copies of X, Y, XtX, rhs_init (run_half_iteration)
   int device = -1;
@@ -1542,6 +1543,20 @@ int rsparse_hip_score_pairs_device(const float* d_U, const float* d_V, int n_row
                               buf = g_ws.score_buf;
                               return (int)RSPARSE_HIP_OK;
                             });
+}
+
+// `_f64_device` and the host form rsparse_hip_top_candidates: wrmf_f64_capi.cpp
+int rsparse_hip_top_candidates_device(const float* d_U, const float* d_V, int n_users, int n_items, int rank, int k,
+                                      const int32_t* d_cand_p, const int32_t* d_cand_j, const int32_t* d_nr_p, const int32_t* d_nr_j,
+                                      const int32_t* d_excl0, int n_exclude, double glob_mean, int32_t* d_res, double* d_scores,
+                                      void* stream) {
+  return top_candidates_device(d_U, d_V, n_users, n_items, rank, k, d_cand_p, d_cand_j, d_nr_p, d_nr_j, d_excl0, n_exclude, glob_mean,
+                               d_res, d_scores, (hipStream_t)stream, RSPARSE_HIP_MAX_RANK, [](size_t n, double*& buf) {
+                                 if (int rc = g_ws.ensure_device()) return rc;
+                                 HIP_TRY(g_ws.score_buf.ensure(n));
+                                 buf = g_ws.score_buf;
+                                 return (int)RSPARSE_HIP_OK;
+                               });
 }
 
 // `_f64_device`: wrmf_f64_capi.cpp

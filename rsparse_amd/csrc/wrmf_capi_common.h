@@ -227,6 +227,39 @@ int score_pairs_device(const T* d_U, const T* d_V, int n_rows, int n_cols, int r
   return RSPARSE_HIP_OK;
 }
 
+// rsparse_hip_top_candidates_device / _f64_device (kernels: wrmf_score.hip, wrmf_candidates.hip).  `workspace` as above: the
+// scores / keys, the admissibility bits and the row lists live there.  The number of candidates is read back first (this call
+// waits for the stream once): the workspace is sized by it.  max_rank: the side's ceiling.
+template <class T, class Workspace>
+int top_candidates_device(const T* d_U, const T* d_V, int n_users, int n_items, int rank, int k, const int32_t* d_cand_p,
+                          const int32_t* d_cand_j, const int32_t* d_nr_p, const int32_t* d_nr_j, const int32_t* d_excl0, int n_exclude,
+                          double glob_mean, int32_t* d_res, double* d_scores, hipStream_t s, int max_rank, Workspace workspace) {
+  if (!d_U || !d_V || !d_res || !d_scores) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
+  if (!d_cand_p || !d_cand_j) return fail(RSPARSE_HIP_ERR_INVALID, "the candidate pattern (cand_p, cand_j) is NULL");
+  if (d_nr_p && !d_nr_j) return fail(RSPARSE_HIP_ERR_INVALID, "nr_p without nr_j");
+  if (n_users < 0 || n_items < 0 || rank < 1 || k < 1 || n_exclude < 0)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0, n_items < 0, rank < 1, k < 1 or n_exclude < 0)");
+  if (n_exclude > 0 && !d_excl0) return fail(RSPARSE_HIP_ERR_INVALID, "exclude is NULL");
+  if (rank > max_rank)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > " + std::to_string(max_rank) + " is not on the device path");
+  if (k > RSPARSE_HIP_MAX_TOPK_LARGE) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
+  if (n_users == 0) return RSPARSE_HIP_OK;
+  int32_t pe[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(&pe[0], d_cand_p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(&pe[1], d_cand_p + n_users, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (pe[0] < 0 || pe[1] < pe[0]) return fail(RSPARSE_HIP_ERR_INVALID, "the candidate row pointers are negative or decrease");
+  const int64_t nnz = (int64_t)pe[1] - pe[0];
+  const size_t bytes = top_candidates_ws_bytes(n_users, nnz);
+  double* ws = nullptr;
+  if (int rc = workspace((bytes + 7) / 8, ws)) return rc;
+  hipError_t e = launch_top_candidates(d_U, d_V, n_users, n_items, rank, k, d_cand_p, d_cand_j, pe[0], nnz, d_nr_p,
+                                       d_nr_p ? d_nr_j : nullptr, n_exclude > 0 ? d_excl0 : nullptr, n_exclude, glob_mean, d_res,
+                                       d_scores, s, ws);
+  if (e != hipSuccess) return hip_fail(e, "launch_top_candidates");
+  return RSPARSE_HIP_OK;
+}
+
 // rsparse_hip_explain_device / _f64_device (kernel: wrmf_explain.hip).  The rank ceiling is the kernel's (one k x k system per
 // user in LDS), the same for both element types.
 template <class T>

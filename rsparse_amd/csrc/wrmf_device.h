@@ -234,5 +234,62 @@ __device__ u64 block_kth_largest(int n, int kth, int nbits, KeyFn key, unsigned*
   return prefix;
 }
 
+// ---- ordering a selection in LDS (wrmf_topk_large.hip, wrmf_candidates.hip) ----
+// workgroup-wide exclusive prefix of a flag (256 threads); *total = the sum.  Uses sw[4].
+__device__ __forceinline__ int block_prefix(bool f, int* sw, int* total) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const u64 m = __ballot(f);
+  if (lane == 0) sw[wv] = __popcll(m);
+  __syncthreads();
+  int off = 0, tot = 0;
+  for (int w = 0; w < 4; w++) {
+    if (w < wv) off += sw[w];
+    tot += sw[w];
+  }
+  __syncthreads();
+  *total = tot;
+  return off + __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// bitonic sort of sk / si [0, P) (P a power of two): descending by (key, index), or ascending
+__device__ inline void block_bitonic(u64* sk, int* si, int P, bool asc) {
+  for (int size = 2; size <= P; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = threadIdx.x; i < P / 2; i += 256) {
+        const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+        const u64 ka = sk[lo], kb = sk[hi];
+        const int ia = si[lo], ib = si[hi];
+        const bool b_first = asc ? (kb < ka || (kb == ka && ib < ia)) : (kb > ka || (kb == ka && ib > ia));
+        if (((lo & size) == 0) == b_first) {
+          sk[lo] = kb;
+          sk[hi] = ka;
+          si[lo] = ib;
+          si[hi] = ia;
+        }
+      }
+      __syncthreads();
+    }
+}
+
+__device__ __forceinline__ int pow2_at_least(int n) {
+  int p = 1;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+// the kk ordered survivors (sk: order keys of double scores, si: 0-based items) and the padding of a row of topk outputs
+template <class TO>
+__device__ __forceinline__ void topl_emit(const u64* sk, const int* si, int kk, int topk, TO glob_mean, int32_t* ru, TO* su) {
+  for (int p = threadIdx.x; p < topk; p += 256) {
+    if (p < kk) {
+      ru[p] = si[p] + 1;   // 1-based, like R
+      su[p] = (TO)key_f64(sk[p]) + glob_mean;
+    } else {
+      ru[p] = INT32_MIN;   // NA_integer_ / NA_real_
+      su[p] = (TO)__longlong_as_double(0x7ff8000000000000ll);
+    }
+  }
+}
+
 }  // namespace dev
 }  // namespace rsparse_hip

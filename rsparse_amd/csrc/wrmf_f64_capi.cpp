@@ -78,7 +78,8 @@ struct WorkspaceF64 {
   GrowBuf<double> m2{all};
   GrowBuf<double> longs{all};      // the long rows' partial sums and vectors (f64_long_scratch_doubles)
   GrowBuf<double> repack{all};     // explicit feedback with biases, conjugate gradient: X', Y', shifted ratings
-  GrowBuf<double> score{all};      // pointwise predictions (wrmf_score.hip): the scores of a call that asks for the error sums only
+  GrowBuf<double> score{all};      // pointwise predictions (wrmf_score.hip): the scores of a call that asks for the error sums only;
+                                   // top-k within candidate lists (wrmf_candidates.hip): its scores / keys, bits and row lists
   int device = -1;
   int ensure() {
     int dev = 0;
@@ -359,6 +360,93 @@ int rsparse_hip_score_pairs_f64_device(const double* d_U, const double* d_V, int
                               buf = g_w64.score;
                               return (int)RSPARSE_HIP_OK;
                             });
+}
+
+// top-k within per-user candidate lists from double factors (kernels: wrmf_score.hip, wrmf_candidates.hip; the fp32 form:
+// wrmf_capi.cpp)
+int rsparse_hip_top_candidates_f64_device(const double* d_U, const double* d_V, int n_users, int n_items, int rank, int k,
+                                          const int32_t* d_cand_p, const int32_t* d_cand_j, const int32_t* d_nr_p,
+                                          const int32_t* d_nr_j, const int32_t* d_excl0, int n_exclude, double glob_mean,
+                                          int32_t* d_res, double* d_scores, void* stream) {
+  return top_candidates_device(d_U, d_V, n_users, n_items, rank, k, d_cand_p, d_cand_j, d_nr_p, d_nr_j, d_excl0, n_exclude, glob_mean,
+                               d_res, d_scores, (hipStream_t)stream, RSPARSE_HIP_MAX_RANK_F64, [](size_t n, double*& buf) {
+                                 if (int rc = g_w64.ensure()) return rc;
+                                 HIP_TRY(g_w64.score.ensure(n));
+                                 buf = g_w64.score;
+                                 return (int)RSPARSE_HIP_OK;
+                               });
+}
+
+// find_top_product (R/utils.R:31-59) within per-row candidate lists, host pointers, shaped like rsparse_hip_top_product: x is
+// nr x rank and y rank x nc, column-major doubles; cand / nr: CSR over the rows of x with 0-based columns (cand: ascending and
+// unique within a row); exclude: 1-based items; res / scores: nr x k column-major, 1-based with NA_integer_ / NA_real_.
+int rsparse_hip_top_candidates(const double* x, const double* y, int nr, int nc, int rank, unsigned k, unsigned n_threads,
+                               const int32_t* cand_p, const int32_t* cand_j, const int32_t* nr_p, const int32_t* nr_j,
+                               const int32_t* exclude, int n_exclude, double glob_mean, int32_t* res, double* scores) {
+  (void)n_threads;
+  if (!x || !y || !res || !scores) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
+  if (!cand_p) return fail(RSPARSE_HIP_ERR_INVALID, "cand_p is NULL");
+  if (nr < 0 || nc < 0 || rank <= 0 || k < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions");
+  if (rank > RSPARSE_HIP_MAX_RANK_F64) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 128 is not on the fp64 device path");
+  if (k > RSPARSE_HIP_MAX_TOPK_LARGE) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
+  if (n_exclude < 0 || (n_exclude > 0 && !exclude)) return fail(RSPARSE_HIP_ERR_INVALID, "bad exclude");
+  if (cand_p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "cand_p[0] != 0");
+  for (int i = 0; i < nr; i++)
+    if (cand_p[i + 1] < cand_p[i]) return fail(RSPARSE_HIP_ERR_INVALID, "cand_p decreases");
+  const size_t nnz = (size_t)cand_p[nr];
+  if (nnz && !cand_j) return fail(RSPARSE_HIP_ERR_INVALID, "cand_j is NULL");
+  for (int i = 0; i < nr; i++)
+    for (int t = cand_p[i]; t < cand_p[i + 1]; t++)
+      if (cand_j[t] < 0 || cand_j[t] >= nc || (t > cand_p[i] && cand_j[t] <= cand_j[t - 1]))
+        return fail(RSPARSE_HIP_ERR_INVALID, "a candidate index is outside the matrix, or a row's indices are not strictly ascending");
+  const int64_t nr_nnz = (nr_p && nr_j && nr > 0) ? (int64_t)nr_p[nr] : 0;
+  std::vector<int32_t> hp, hj;   // not_recommend with ascending columns (what the device form asks for)
+  if (nr_nnz > 0) {
+    if (nr_p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "nr_p[0] != 0");
+    for (int i = 0; i < nr; i++)
+      if (nr_p[i + 1] < nr_p[i]) return fail(RSPARSE_HIP_ERR_INVALID, "nr_p decreases");
+    hp.assign(nr_p, nr_p + nr + 1);
+    hj.assign(nr_j, nr_j + nr_nnz);
+    for (int i = 0; i < nr; i++) std::sort(hj.begin() + hp[i], hj.begin() + hp[i + 1]);
+  }
+  std::vector<int32_t> ex;
+  for (int e = 0; e < n_exclude; e++)
+    if (exclude[e] >= 1 && exclude[e] <= nc) ex.push_back(exclude[e] - 1);   // R indices are 1-based
+  std::sort(ex.begin(), ex.end());
+  ex.erase(std::unique(ex.begin(), ex.end()), ex.end());
+  std::vector<double> U((size_t)nr * rank);   // x is nr x rank column-major -> row-major; y already has item vectors contiguous
+  for (int j = 0; j < nr; j++)
+    for (int r = 0; r < rank; r++) U[(size_t)j * rank + r] = x[(size_t)r * nr + j];
+  DevBuf dU, dV, dCP, dCJ, dP, dJ, dE, dR, dS;
+  HIP_TRY(upload_host(dU, U.data(), U.size()));
+  HIP_TRY(upload_host(dV, y, (size_t)rank * nc));
+  HIP_TRY(upload_host(dCP, cand_p, (size_t)nr + 1));
+  HIP_TRY(upload_host(dCJ, cand_j, nnz));
+  if (nr_nnz > 0) {
+    HIP_TRY(upload_host(dP, hp.data(), hp.size()));
+    HIP_TRY(upload_host(dJ, hj.data(), hj.size()));
+  }
+  if (!ex.empty()) HIP_TRY(upload_host(dE, ex.data(), ex.size()));
+  HIP_TRY(dR.alloc((size_t)nr * k * 4));
+  HIP_TRY(dS.alloc((size_t)nr * k * 8));
+  int rc = rsparse_hip_top_candidates_f64_device(dU.as<double>(), dV.as<double>(), nr, nc, rank, (int)k, dCP.as<int32_t>(),
+                                                 dCJ.as<int32_t>(), nr_nnz > 0 ? dP.as<int32_t>() : nullptr,
+                                                 nr_nnz > 0 ? dJ.as<int32_t>() : nullptr, ex.empty() ? nullptr : dE.as<int32_t>(),
+                                                 (int)ex.size(), glob_mean, dR.as<int32_t>(), dS.as<double>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<int32_t> hr((size_t)nr * k);
+  std::vector<double> hs((size_t)nr * k);
+  if (!hr.empty()) {
+    HIP_TRY(hipMemcpy(hr.data(), dR.p, hr.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hs.data(), dS.p, hs.size() * 8, hipMemcpyDeviceToHost));
+  }
+  for (int j = 0; j < nr; j++)
+    for (unsigned c = 0; c < k; c++) {
+      res[(size_t)c * nr + j] = hr[(size_t)j * k + c];
+      scores[(size_t)c * nr + j] = hs[(size_t)j * k + c];
+    }
+  return RSPARSE_HIP_OK;
 }
 
 // per-item contributions to a score from double factors (kernel: wrmf_explain.hip; the fp32 form: wrmf_capi.cpp)

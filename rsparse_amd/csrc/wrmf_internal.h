@@ -361,6 +361,19 @@ hipError_t launch_score_pairs(const T* U, const T* V, int n_rows, int n_cols, in
 hipError_t launch_score_error_sums(const double* scores, const double* actual, const int32_t* P, int n_rows, double* sse,
                                    double* sae, hipStream_t s);
 
+// top-k within per-user candidate lists (wrmf_candidates.hip), T = float or double, 1 <= topk <= kTopLargeMax: for every row of
+// the CSR pattern (cand_p: n_users + 1 slots, absolute positions into cand_j; p0 = cand_p[0], nnz = cand_p[n_users] - p0, read by
+// the caller; columns ascending and unique within a row) the topk best admissible candidates by launch_score_pairs' scores
+// (glob_mean included), with the reference heap's tie rule; not_recommend (nr_ptr: the slots of these users, absolute positions
+// into nr_idx, columns ascending; nullable) and excl (ascending; nullable) make a candidate inadmissible.  res: 1-based items,
+// INT32_MIN where fewer than topk are admissible (scores NaN there).  ws: top_candidates_ws_bytes(n_users, nnz) bytes.
+size_t top_candidates_ws_bytes(int n_users, int64_t nnz);
+template <class T>
+hipError_t launch_top_candidates(const T* U, const T* V, int n_users, int n_items, int rank, int topk, const int32_t* cand_p,
+                                 const int32_t* cand_j, int32_t p0, int64_t nnz, const int32_t* nr_ptr, const int32_t* nr_idx,
+                                 const int32_t* excl, int n_excl, double glob_mean, int32_t* res, double* scores, hipStream_t s,
+                                 void* ws);
+
 // per-item contributions to a score (wrmf_explain.hip), T = float or double, 1 <= r <= 128: for every target q (t_p / t_j: CSR
 // over the users) of a user with the row (x_p / x_j) and the per-non-zero weights wa (assembly) and wb (contribution),
 // contrib[out_p[q] + t] = wb_t (z . V[x_j[t]]) with (base + (diag + diag_per_nnz len) I + sum_t wa_t V[x_j[t]] V[x_j[t]]^T) z =

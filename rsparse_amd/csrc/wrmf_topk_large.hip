@@ -271,48 +271,7 @@ __global__ __launch_bounds__(256) void topl_compact_kernel(const unsigned* __res
 }
 
 // ---- 4. order -----------------------------------------------------------------------------------------------------------------
-// workgroup-wide exclusive prefix of a flag (256 threads); *total = the sum.  Uses sw[4].
-__device__ __forceinline__ int block_prefix(bool f, int* sw, int* total) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const u64 m = __ballot(f);
-  if (lane == 0) sw[wv] = __popcll(m);
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int w = 0; w < 4; w++) {
-    if (w < wv) off += sw[w];
-    tot += sw[w];
-  }
-  __syncthreads();
-  *total = tot;
-  return off + __popcll(m & ((1ull << lane) - 1ull));
-}
-
-// bitonic sort of sk / si [0, P) (P a power of two): descending by (key, index), or ascending
-__device__ void block_bitonic(u64* sk, int* si, int P, bool asc) {
-  for (int size = 2; size <= P; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = threadIdx.x; i < P / 2; i += 256) {
-        const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
-        const u64 ka = sk[lo], kb = sk[hi];
-        const int ia = si[lo], ib = si[hi];
-        const bool b_first = asc ? (kb < ka || (kb == ka && ib < ia)) : (kb > ka || (kb == ka && ib > ia));
-        if (((lo & size) == 0) == b_first) {
-          sk[lo] = kb;
-          sk[hi] = ka;
-          si[lo] = ib;
-          si[hi] = ia;
-        }
-      }
-      __syncthreads();
-    }
-}
-
-__device__ __forceinline__ int pow2_at_least(int n) {
-  int p = 1;
-  while (p < n) p <<= 1;
-  return p;
-}
-
+// (block_prefix, block_bitonic, pow2_at_least and topl_emit: wrmf_device.h, shared with wrmf_candidates.hip)
 // the double score u . v_it: 16 lanes per item, lane gl takes the elements gl, gl + 16, ... (uu: the user's vector in LDS)
 template <class TF>
 __device__ __forceinline__ double dot16(const double* uu, const TF* __restrict__ V, int it, int rank, int gl) {
@@ -321,19 +280,6 @@ __device__ __forceinline__ double dot16(const double* uu, const TF* __restrict__
 #pragma unroll
   for (int o = 8; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
   return acc;
-}
-
-template <class TO>
-__device__ __forceinline__ void topl_emit(const u64* sk, const int* si, int kk, int topk, TO glob_mean, int32_t* ru, TO* su) {
-  for (int p = threadIdx.x; p < topk; p += 256) {
-    if (p < kk) {
-      ru[p] = si[p] + 1;   // 1-based, like R
-      su[p] = (TO)key_f64(sk[p]) + glob_mean;
-    } else {
-      ru[p] = INT32_MIN;   // NA_integer_ / NA_real_
-      su[p] = (TO)__longlong_as_double(0x7ff8000000000000ll);
-    }
-  }
 }
 
 // One workgroup per user whose list did not overflow.  LDS: sk[cap] keys (the double score's order key), si[cap] items.

@@ -399,6 +399,48 @@ class HipBackend:
                 float(glob_mean), res[a0:].data_ptr(), sc[a0:].data_ptr(), self._stream()))
         return res, sc
 
+    top_candidates_batch = 1 << 28   # candidates per call: 8 bytes each in the library's grow-only workspace (2 GiB)
+
+    def top_candidates(self, U, V, k, c_p, c_j, nr_p, nr_j, exclude0, glob_mean):
+        """top_product WITHIN per-row candidate lists (wrmf_candidates.hip): for the rows of U (n x rank) the k best of the
+        stored positions of the CSR pattern (c_p, c_j: int32 on the device, columns ascending and unique within a row) that are
+        neither in the row's not_recommend slots (nr_p / nr_j, columns ascending, or None) nor in exclude0 (sorted 0-based ids,
+        or None), by the scores of `score_pairs` (the factors as they are, fp32 or fp64, summed in double, + glob_mean) with the
+        reference's tie rule.  -> (indices int32 n x k, 1-based with NA_integer_; scores float64 n x k, NaN where NA)."""
+        if U.dtype != V.dtype:
+            U = U.to(V.dtype)
+        assert V.dtype in (torch.float32, torch.float64) and U.shape[1] == V.shape[1]
+        assert c_p.dtype == torch.int32 and c_j.dtype == torch.int32 and int(c_p.numel()) == U.shape[0] + 1
+        U, V = U.contiguous(), V.contiguous()
+        n, rank = U.shape
+        dev = U.device
+        res = torch.empty((n, k), dtype=torch.int32, device=dev)
+        sc = torch.empty((n, k), dtype=torch.float64, device=dev)
+        if n == 0:
+            return res, sc
+        nnz = int(c_j.numel())
+        if nnz == 0:   # no candidate at all: every list is empty, nothing to launch
+            res.fill_(-2147483648)
+            sc.fill_(float("nan"))
+            return res, sc
+        fn = self.lib.rsparse_hip_top_candidates_f64_device if V.dtype == torch.float64 else self.lib.rsparse_hip_top_candidates_device
+        # in batches of rows when the pattern is larger than the workspace budget: the slots are absolute positions into c_j
+        # (and nr_j), so a batch passes its slice of the row pointers unchanged
+        bounds = [0, n]
+        if nnz > self.top_candidates_batch:
+            hp = c_p.cpu().numpy().astype(np.int64)
+            bounds, a0 = [0], 0
+            while a0 < n:
+                b0 = int(np.searchsorted(hp, hp[a0] + self.top_candidates_batch, side="right")) - 1
+                a0 = min(n, max(b0, a0 + 1))
+                bounds.append(a0)
+        for a0, b0 in zip(bounds[:-1], bounds[1:]):
+            _lib.check(fn(U[a0:].data_ptr(), V.data_ptr(), b0 - a0, int(V.shape[0]), rank, int(k), c_p[a0:].data_ptr(), c_j.data_ptr(),
+                          None if nr_p is None else nr_p[a0:].data_ptr(), None if nr_j is None else nr_j.data_ptr(),
+                          None if exclude0 is None else exclude0.data_ptr(), 0 if exclude0 is None else int(exclude0.numel()),
+                          float(glob_mean), res[a0:].data_ptr(), sc[a0:].data_ptr(), self._stream()))
+        return res, sc
+
     def ranking_metrics(self, res, p, j, x, want_ap=True, want_ndcg=True):
         """ap_k / ndcg_k (R/metrics.R:31-127) of the lists `res` (n x k int32 on the device, 1-based with NA_integer_, as
         top_product returns them) against `actual` as CSR slots on the device (p, j int32 with j sorted within rows; x float64,

@@ -613,15 +613,22 @@ class WRMF:
         self._check_numeric()   # (collective when the model shards: _transform_device runs it on every rank)
         return res
 
-    def predict(self, x, k, not_recommend="x", items_exclude=()):
+    def predict(self, x, k, not_recommend="x", items_exclude=(), candidates=None):
         """R/MatrixFactorizationRecommender.R:24-34 -> find_top_product (R/utils.R:31-59): embeddings of the
         rows of `x` by `transform`, then the k best items per row on the device, skipping each row's
         `not_recommend` entries (default: `x` itself, as in the reference; None = nothing) and the globally
         excluded `items_exclude` (0-based here, 1-based in R).  Returns a `TopItems` array (n x k item
         indices, 0-based, -1 where fewer than k items are admissible) with `.scores` (n x k).  k up to 256 runs the fused
         device path, 256 < k <= 8192 the large-k path (a radix select per user over the stored scores); a larger k raises
-        UnsupportedOnDevice."""
-        res, sc, x = self._predict_device(x, k, not_recommend, items_exclude)
+        UnsupportedOnDevice.
+
+        `candidates` (n x n_item sparse, any format; values ignored, stored zeros are positions too) ranks every row within its
+        own stored positions only -- a retrieval stage's candidates, the sampled negatives of a leave-one-out evaluation, a
+        slice of the catalogue per user: the result is what the call returns when every item outside the row's candidates is
+        added to its not_recommend row, computed from the candidates alone (work and memory follow their number, not n x
+        n_item).  The scores are those of `score` at the same cells, the order is by exactly these doubles, ties as in the
+        reference; 1 <= k <= 8192."""
+        res, sc, x = self._predict_device(x, k, not_recommend, items_exclude, candidates)
         n_new = x.shape[0]
         if self._dist()[0] > 1:
             res, sc = self._share_rows(res, self._row_bounds, n_new), self._share_rows(sc, self._row_bounds, n_new)
@@ -661,7 +668,7 @@ class WRMF:
         d_ex = be.to_device(excl, torch.int32) if excl.size else None
         return nr_p, nr_j, d_ex
 
-    def _predict_device(self, x, k, not_recommend, items_exclude):
+    def _predict_device(self, x, k, not_recommend, items_exclude, candidates=None):
         """the device part of `predict`: (indices int32, scores float64) of this rank's block of rows, _row_bounds[rank], still
         on the device -- 1-based with NA_integer_ as top_product writes them --, and x as CSR"""
         if self._V is None:
@@ -671,6 +678,13 @@ class WRMF:
         if x.shape[1] != n_item:
             raise ValueError("ncol(x) == ncol(self$components) is not TRUE")
         k = int(k)
+        cand = None
+        if candidates is not None:
+            _, cand = self._pairs_pattern(x, candidates, "candidates")
+            if k < 1:
+                raise ValueError("k must be at least 1")
+            if k > 8192:   # RSPARSE_HIP_MAX_TOPK_LARGE
+                raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "predict: k > 8192 is not on the device path")
         excl, not_recommend = self._exclusion_args(x, not_recommend, items_exclude)
         be = self._backend()
         emb = self._transform_device(x)             # (n_new, rank), complete on every rank
@@ -678,18 +692,62 @@ class WRMF:
         a, b, ws = self._my_rows(x)
         n_mine = b - a
         nr_p, nr_j, d_ex = self._exclusion_slots(x, not_recommend, excl, a, b)
-        if n_mine > 0:
+        if n_mine > 0 and cand is not None:
+            # the rows' own candidate lists: scored like `score` (biases included), then a segmented exact top-k
+            mine = cand[a:b]
+            c_p, c_j = be.to_device(mine.indptr, torch.int32), be.to_device(mine.indices, torch.int32)
+            fn = be.top_candidates if hasattr(be, "top_candidates") else self._top_candidates_host
+            res, sc = fn(emb[a:b], self._V, k, c_p, c_j, nr_p, nr_j, d_ex, float(self.global_bias))
+        elif n_mine > 0:
             res, sc = be.top_product(emb[a:b], self._V, k, nr_p, nr_j, d_ex, float(self.global_bias))
         else:
             res = torch.empty((0, k), dtype=torch.int32, device=emb.device)
             sc = torch.empty((0, k), dtype=torch.float64, device=emb.device)
         return res, sc, x
 
-    def evaluate(self, x, actual, k, not_recommend="x", items_exclude=(), metrics=("ap", "ndcg")):
+    @staticmethod
+    def _top_candidates_host(U, V, k, c_p, c_j, nr_p, nr_j, exclude0, glob_mean):
+        """`top_candidates` for a backend without it (the CPU stand-in of the tests): the scores of `_score_pairs_host`, then the
+        reference heap's result in closed form per row, in numpy.  With kk = min(k, admissible), v the kk-th best score, A the
+        admissible candidates above v and G those equal to it: all of A, plus the kk - |A| largest indices among the G items that
+        fall into the first kk of A u G in ascending item order; best first, equal scores with the larger index first."""
+        n = U.shape[0]
+        sc_all, _, _ = WRMF._score_pairs_host(U, V, c_p, c_j, glob_mean)
+        s_all = sc_all.cpu().numpy() + 0.0                    # (-0 and +0 tie)
+        p, j = c_p.cpu().numpy().astype(np.int64), c_j.cpu().numpy().astype(np.int64)
+        nrp = None if nr_p is None else nr_p.cpu().numpy().astype(np.int64)
+        nrj = None if nr_j is None else nr_j.cpu().numpy().astype(np.int64)
+        ex = np.zeros(0, np.int64) if exclude0 is None else exclude0.cpu().numpy().astype(np.int64)
+        res = np.full((n, k), -2147483648, dtype=np.int32)
+        sc = np.full((n, k), np.nan, dtype=np.float64)
+        for u in range(n):
+            it, s = j[p[u]:p[u + 1]], s_all[p[u]:p[u + 1]]
+            ok = ~np.isin(it, ex)
+            if nrp is not None:
+                ok &= ~np.isin(it, nrj[nrp[u]:nrp[u + 1]])
+            it, s = it[ok], s[ok]                              # ascending item order
+            kk = min(k, it.size)
+            if kk == 0:
+                continue
+            v = np.sort(s)[it.size - kk]
+            above, tied = s > v, s == v
+            keep = above.copy()
+            first = np.flatnonzero(above | tied)[:kk]         # the first kk of A u G in item order
+            t = first[tied[first]]
+            m = kk - int(above.sum())
+            keep[t[t.size - m:]] = True
+            it, s = it[keep], s[keep]
+            order = np.lexsort((-it, -s))
+            res[u, :kk] = it[order] + 1
+            sc[u, :kk] = s[order]
+        return torch.from_numpy(res).to(U.device), torch.from_numpy(sc).to(U.device)
+
+    def evaluate(self, x, actual, k, not_recommend="x", items_exclude=(), metrics=("ap", "ndcg"), candidates=None):
         """`predict(x, k, ...)` scored against the held-out interactions `actual` (n x anything sparse, relevances as values) by
         the reference's ap_k / ndcg_k (R/metrics.R:31-127) without the lists leaving the device: {name: float64 vector of n}
         for each name in `metrics` ("ap", "ndcg").  Equals `rsparse_amd.metrics.ap_k(self.predict(x, k, ...), actual)` (and
-        ndcg_k) bit for bit.  Under torch.distributed every rank scores the block of rows it predicts."""
+        ndcg_k) bit for bit.  Under torch.distributed every rank scores the block of rows it predicts.  `candidates`: as in
+        `predict` -- the lists are ranked within every row's candidates (sampled-negative evaluation)."""
         from .metrics import canonical_actual
         metrics = tuple(metrics)
         if not metrics or any(m not in ("ap", "ndcg") for m in metrics):
@@ -697,7 +755,7 @@ class WRMF:
         x = sp.csr_matrix(x, dtype=np.float64)
         n_new = x.shape[0]
         act = canonical_actual(actual, n_new)
-        res, _, x = self._predict_device(x, k, not_recommend, items_exclude)
+        res, _, x = self._predict_device(x, k, not_recommend, items_exclude, candidates)
         ws, me = self._dist()
         a, b = self._row_bounds[me]
         mine = act[a:b]
