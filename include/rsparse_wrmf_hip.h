@@ -625,6 +625,57 @@ int rsparse_hip_init_factors_f64_device(uint64_t seed, int stream, int64_t row0,
                                         int abs_values, int ones_col, void* d_out /* double */, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * negative sampling on the device: the candidate rows of a sampled-metric evaluation
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Sampled-negative evaluation ranks every user's held-out items against n items the user has not interacted with
+ * (rsparse_hip_top_candidates* on the rows, rsparse_hip_ranking_metrics* on the lists).  These entries make the rows: for row u of
+ * the CSR pattern `seen` (the exclusion list: columns ascending, unique, inside [0, n_item)) the items of row u of `keep` (a
+ * subset of the seen row, ascending and unique; both keep pointers NULL = nothing is kept) merged in ascending order with
+ * min(n, M) items drawn uniformly WITHOUT replacement from the M = n_item - |seen_u| items outside the seen row.  The stream is
+ * DEFINED here, so that any host can reproduce a row; rsparse_amd/rng.py (sample_negatives) is the definition in numpy.
+ *
+ *   Ranks.     The M admissible items of a row are numbered by rank 0 .. M - 1 in ascending item order:
+ *              item(r) = r + #{i : seen_u[i] - i <= r}  (seen_u[i] - i does not decrease: a binary search).
+ *   Draw t.    t = 0, 1, 2, ... of the row with GLOBAL index g = row0 + u: Philox4x32-10 (the rounds above) with key
+ *              (lo32(seed), hi32(seed)) and counter (lo32(t >> 1), g, 2, hi32(t >> 1)) -- word 2 is the stream id, 0 and 1 are
+ *              the factor streams -- gives o0..o3; w = o1 * 2^32 + o0 for even t, o3 * 2^32 + o2 for odd t; the drawn rank is
+ *              floor(w * M / 2^64) = (o_hi * M + ((o_lo * M) >> 32)) >> 32, exact in 64-bit unsigned arithmetic for M < 2^31,
+ *              with a bias of at most M / 2^64.
+ *   Chosen.    n >= M: every rank.  Otherwise d = min(n, M - n) and D = the first d DISTINCT values of the draw sequence; the
+ *              chosen ranks are D when 2 n <= M and every rank except D otherwise (the row draws what it leaves out, so no row
+ *              needs more than about M ln 2 draws).
+ *   Row.       keep_u and the items of the chosen ranks, ascending: |keep_u| + min(n, M) entries; out_p / out_j are a canonical
+ *              CSR pattern from 0.
+ * A row therefore depends on (seed, g, seen_u, keep_u, n_item, n) only -- not on the rows sampled with it (rows [a, b) sampled
+ * with row0 = a are rows a .. b - 1 of the whole), the number of devices, or the device; and "the first d distinct values" does
+ * not depend on the order in which draws are evaluated.
+ *
+ * _device: every pointer is device memory; seen_p / keep_p (n_rows + 1 slots) may be a slice of a larger pattern's row pointers
+ * (absolute positions into seen_j / keep_j).  d_out_p (n_rows + 1) is computed on the device from the lengths of the rows; the
+ * call then waits for the stream once to read back out_p[n_rows] and refuses, BEFORE anything is sampled, row pointers that are
+ * negative or decrease, a seen row longer than n_item, a keep row longer than its seen row, a total beyond 2^31 - 1 or beyond
+ * out_capacity (the entries d_out_j has room for: n_rows * n + the keep entries always suffices) -> ERR_INVALID.  Exactly
+ * out_p[n_rows] entries of d_out_j are written.  The contents of the lists are the caller's contract here (a keep row that is no
+ * subset of its seen row gives a wrong row, never a write outside it); the host form checks them.
+ * 1 <= n <= RSPARSE_HIP_MAX_NEGATIVES, n_item < 2^31, row0 + n_rows <= 2^32, seen rows of any length.
+ *
+ * Host form: host pointers, p from 0.  out_p is always written; with out_j == NULL the call returns after that (out_p[n_rows] is
+ * the capacity a second call needs), otherwise out_capacity must be at least out_p[n_rows].  seen / keep indices out of range,
+ * not strictly ascending, or a keep row that is not a subset of its seen row -> ERR_INVALID.
+ *
+ * Both: a NULL seen_p, seen_j or out_p (the device form: or d_out_j), only one of keep_p / keep_j, n_rows < 0, n_item < 0, n < 1,
+ * row0 < 0, out_capacity < 0 -> ERR_INVALID; n > RSPARSE_HIP_MAX_NEGATIVES -> ERR_UNSUPPORTED; all before a device is touched.
+ * n_rows == 0 -> OK, nothing is launched. */
+#define RSPARSE_HIP_MAX_NEGATIVES 8192
+int rsparse_hip_sample_negatives_device(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* d_seen_p,
+                                        const int32_t* d_seen_j, const int32_t* d_keep_p, const int32_t* d_keep_j,
+                                        int32_t* d_out_p, int32_t* d_out_j, int64_t out_capacity, void* hip_stream);
+int rsparse_hip_sample_negatives(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* seen_p,
+                                 const int32_t* seen_j, const int32_t* keep_p, const int32_t* keep_j, int32_t* out_p, int32_t* out_j,
+                                 int64_t out_capacity);
+
+/* ------------------------------------------------------------------------------------------------
  * (3) fp64 device layer: als_implicit<double> / als_explicit<double> with the data resident in HBM
  * ---------------------------------------------------------------------------------------------- */
 

@@ -12,6 +12,7 @@ LIB_PATH = Path(os.environ.get("RSPARSE_HIP_LIB", Path(__file__).resolve().paren
 
 OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_RUNTIME, ERR_NUMERIC = 0, 1, 2, 3, 4
 SOLVER_CHOLESKY, SOLVER_CG, SOLVER_NNLS = 0, 1, 2
+MAX_NEGATIVES = 8192   # RSPARSE_HIP_MAX_NEGATIVES: negatives per row of rsparse_hip_sample_negatives*
 RANKS_BATCH = 1024   # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that the rank count takes at a time
 
 _c_int, _c_uint, _c_dbl, _c_i64, _c_u64 = ctypes.c_int, ctypes.c_uint, ctypes.c_double, ctypes.c_int64, ctypes.c_uint64
@@ -95,6 +96,8 @@ SIGNATURES = {
     "rsparse_hip_init_factors_device": (_c_int, [_c_u64, _c_int, _c_i64, _c_int, _c_int, _c_i64, _c_dbl, _c_int, _c_int, _vp, _vp]),
     "rsparse_hip_init_factors_f64_device": (_c_int, [_c_u64, _c_int, _c_i64, _c_int, _c_int, _c_i64, _c_dbl, _c_int, _c_int, _vp,
                                                      _vp]),
+    "rsparse_hip_sample_negatives_device": (_c_int, [_c_u64, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp]),
+    "rsparse_hip_sample_negatives": (_c_int, [_c_u64, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64]),
     "rsparse_hip_sparse_approximation": (_c_int, [_c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_int, _vp]),
     "rsparse_hip_csc_f64_create_device": (_c_int, [_c_int, _c_int, _vp, _vp, _vp, ctypes.POINTER(_vp)]),
     "rsparse_hip_csc_f64_destroy": (_c_int, [_vp]),

@@ -17,7 +17,7 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 SRC = [CSRC / n for n in ("wrmf_kernels.hip", "wrmf_cgq.hip", "wrmf_cgp.hip", "wrmf_ne.hip", "wrmf_chol.hip", "wrmf_chol_wave.hip", "wrmf_chol_mf.hip", "wrmf_cg_mf.hip", "wrmf_chol_lr.hip",
-                          "wrmf_topk.hip", "wrmf_topk_large.hip", "wrmf_similar.hip", "wrmf_metrics.hip", "wrmf_ranks.hip", "wrmf_score.hip", "wrmf_candidates.hip", "wrmf_explain.hip", "wrmf_init.hip", "wrmf_ingest.hip", "wrmf_nnls.hip", "wrmf_bias.hip", "wrmf_lu.hip",
+                          "wrmf_topk.hip", "wrmf_topk_large.hip", "wrmf_similar.hip", "wrmf_metrics.hip", "wrmf_ranks.hip", "wrmf_score.hip", "wrmf_candidates.hip", "wrmf_sample.hip", "wrmf_explain.hip", "wrmf_init.hip", "wrmf_ingest.hip", "wrmf_nnls.hip", "wrmf_bias.hip", "wrmf_lu.hip",
                           "wrmf_f64.hip", "wrmf_wide.hip", "wrmf_wide_cg.hip", "wrmf_ctx_kernels.hip", "wrmf_schedule.cpp", "wrmf_capi.cpp", "wrmf_f64_capi.cpp", "wrmf_ctx.cpp")]
 HEADERS = [CSRC / "wrmf_chol_mf.attrs.csv", CSRC / "wrmf_mf.h", CSRC / "wrmf_internal.h", CSRC / "wrmf_capi_common.h", CSRC / "wrmf_schedule.h", CSRC / "wrmf_device.h", CSRC / "wrmf_wave.h", CSRC / "wrmf_ldlt.h", CSRC / "wrmf_f64.h", PKG.parent / "include" / "rsparse_wrmf_hip.h"]
 DEPS = SRC + HEADERS
@@ -39,7 +39,9 @@ REG_LIMIT = {"wrmf_cg_mf.hip": 512}   # (one wave per SIMD by design: 320 accumu
 # when one of them spills, uses scratch or passes 256 registers -- another compiler may allocate differently.
 NO_SPILL = {"wrmf_cgq.hip": ("14als_cgq_kernelILi128ELi24ELi4ELi4E",),
             # the tile a thread assembles and factors stays in registers from the first chunk to the last pivot
-            "wrmf_explain.hip": ("14explain_kernelIfLi128E",)}
+            "wrmf_explain.hip": ("14explain_kernelIfLi128E",),
+            # integer-only, about two dozen registers: scratch here would mean the draw loop lost its registers
+            "wrmf_sample.hip": ("13sample_kernelILi64E", "13sample_kernelILi256E")}
 RESOURCE_FLAG = "-Rpass-analysis=kernel-resource-usage"
 
 

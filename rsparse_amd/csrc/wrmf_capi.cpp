@@ -1575,6 +1575,102 @@ int rsparse_hip_init_factors_device(uint64_t seed, int stream, int64_t row0, int
                              (hipStream_t)hip_stream);
 }
 
+namespace {
+// what both forms of rsparse_hip_sample_negatives check before anything else
+int sample_negatives_args(int64_t row0, int n_rows, int n_item, int n, const void* seen_p, const void* seen_j, const void* keep_p,
+                          const void* keep_j, const void* out_p, int64_t out_capacity) {
+  if (n_rows < 0 || n_item < 0 || n < 1 || row0 < 0 || out_capacity < 0)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, n_item < 0, n < 1, row0 < 0 or out_capacity < 0)");
+  if (row0 + n_rows > (1ll << 32)) return fail(RSPARSE_HIP_ERR_INVALID, "the global row index row0 + n_rows does not fit 32 bits");
+  if (!seen_p || !seen_j || !out_p) return fail(RSPARSE_HIP_ERR_INVALID, "seen_p, seen_j or out_p is NULL");
+  if (!keep_p != !keep_j) return fail(RSPARSE_HIP_ERR_INVALID, "keep_p and keep_j must both be given or both be NULL");
+  if (n > RSPARSE_HIP_MAX_NEGATIVES)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "n > 8192 (RSPARSE_HIP_MAX_NEGATIVES) is not on the device path");
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+
+int rsparse_hip_sample_negatives_device(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* d_seen_p,
+                                        const int32_t* d_seen_j, const int32_t* d_keep_p, const int32_t* d_keep_j,
+                                        int32_t* d_out_p, int32_t* d_out_j, int64_t out_capacity, void* stream) {
+  int rc = sample_negatives_args(row0, n_rows, n_item, n, d_seen_p, d_seen_j, d_keep_p, d_keep_j, d_out_p, out_capacity);
+  if (rc) return rc;
+  if (!d_out_j) return fail(RSPARSE_HIP_ERR_INVALID, "out_j is NULL");
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = g_ws.ensure_device())) return rc;
+  HIP_TRY(g_ws.score_buf.ensure((sample_negatives_ws_bytes(n_rows) + 7) / 8));
+  SampleStatus* d_status = nullptr;
+  hipError_t e = launch_sample_row_pointers(n_rows, n_item, n, d_seen_p, d_keep_p, d_out_p, g_ws.score_buf, &d_status, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_sample_row_pointers");
+  SampleStatus st = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(&st, d_status, sizeof(st), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (st.flag)
+    return fail(RSPARSE_HIP_ERR_INVALID, "row pointers that are negative or decrease, a seen row longer than n_item or a keep row longer than its seen row");
+  if (st.total > 0x7fffffffll) return fail(RSPARSE_HIP_ERR_INVALID, "the output has more than 2^31 - 1 entries: sample the rows in batches");
+  if (st.total > out_capacity)
+    return fail(RSPARSE_HIP_ERR_INVALID, "out_capacity is " + std::to_string(out_capacity) + ", the rows need " + std::to_string(st.total));
+  e = launch_sample_negatives(seed, row0, n_rows, n_item, n, d_seen_p, d_seen_j, d_keep_p, d_keep_j, d_out_p, d_out_j, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_sample_negatives");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_sample_negatives(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* seen_p,
+                                 const int32_t* seen_j, const int32_t* keep_p, const int32_t* keep_j, int32_t* out_p, int32_t* out_j,
+                                 int64_t out_capacity) {
+  int rc = sample_negatives_args(row0, n_rows, n_item, n, seen_p, seen_j, keep_p, keep_j, out_p, out_capacity);
+  if (rc) return rc;
+  // the dgRMatrix slots: p from 0, non-decreasing; j strictly ascending within a row and inside the matrix; keep within seen
+  if (seen_p[0] != 0 || (keep_p && keep_p[0] != 0)) return fail(RSPARSE_HIP_ERR_INVALID, "seen_p[0] or keep_p[0] != 0");
+  int64_t total = 0;
+  out_p[0] = 0;
+  for (int u = 0; u < n_rows; u++) {
+    if (seen_p[u + 1] < seen_p[u] || (keep_p && keep_p[u + 1] < keep_p[u])) return fail(RSPARSE_HIP_ERR_INVALID, "seen_p or keep_p decreases");
+    for (int32_t e = seen_p[u]; e < seen_p[u + 1]; e++)
+      if (seen_j[e] < 0 || seen_j[e] >= n_item || (e > seen_p[u] && seen_j[e] <= seen_j[e - 1]))
+        return fail(RSPARSE_HIP_ERR_INVALID, "a seen index is outside the matrix, or a row's indices are not strictly ascending");
+    const int32_t S = seen_p[u + 1] - seen_p[u];
+    int32_t K = 0;
+    if (keep_p) {
+      K = keep_p[u + 1] - keep_p[u];
+      int32_t e = seen_p[u];
+      for (int32_t t = keep_p[u]; t < keep_p[u + 1]; t++) {   // both ascending: one pass
+        if (t > keep_p[u] && keep_j[t] <= keep_j[t - 1]) return fail(RSPARSE_HIP_ERR_INVALID, "a keep row's indices are not strictly ascending");
+        while (e < seen_p[u + 1] && seen_j[e] < keep_j[t]) e++;
+        if (e == seen_p[u + 1] || seen_j[e] != keep_j[t]) return fail(RSPARSE_HIP_ERR_INVALID, "a keep row is not a subset of its seen row");
+      }
+    }
+    total += (int64_t)K + std::min(n, n_item - S);
+    if (total > 0x7fffffffll) return fail(RSPARSE_HIP_ERR_INVALID, "the output has more than 2^31 - 1 entries: sample the rows in batches");
+    out_p[u + 1] = (int32_t)total;
+  }
+  if (!out_j) return RSPARSE_HIP_OK;   // the sizes only: out_p[n_rows] is the capacity the second call needs
+  if (total > out_capacity)
+    return fail(RSPARSE_HIP_ERR_INVALID, "out_capacity is " + std::to_string(out_capacity) + ", the rows need " + std::to_string(total));
+  if (n_rows == 0 || total == 0) return RSPARSE_HIP_OK;
+  DevBuf dSP, dSJ, dKP, dKJ, dOP, dOJ;
+  HIP_TRY(upload_host(dSP, seen_p, (size_t)n_rows + 1));
+  const size_t s_nnz = (size_t)seen_p[n_rows], k_nnz = keep_p ? (size_t)keep_p[n_rows] : 0;
+  HIP_TRY(dSJ.alloc(std::max<size_t>(s_nnz, 1) * 4));   // (never NULL: the device form wants the slot)
+  if (s_nnz) HIP_TRY(hipMemcpy(dSJ.p, seen_j, s_nnz * 4, hipMemcpyHostToDevice));
+  if (keep_p) {
+    HIP_TRY(upload_host(dKP, keep_p, (size_t)n_rows + 1));
+    HIP_TRY(dKJ.alloc(std::max<size_t>(k_nnz, 1) * 4));
+    if (k_nnz) HIP_TRY(hipMemcpy(dKJ.p, keep_j, k_nnz * 4, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(dOP.alloc(((size_t)n_rows + 1) * 4));
+  HIP_TRY(dOJ.alloc((size_t)total * 4));
+  rc = rsparse_hip_sample_negatives_device(seed, row0, n_rows, n_item, n, dSP.as<int32_t>(), dSJ.as<int32_t>(),
+                                           keep_p ? dKP.as<int32_t>() : nullptr, keep_p ? dKJ.as<int32_t>() : nullptr,
+                                           dOP.as<int32_t>(), dOJ.as<int32_t>(), total, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out_p, dOP.p, ((size_t)n_rows + 1) * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_j, dOJ.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+  return RSPARSE_HIP_OK;
+}
+
 int rsparse_hip_take_numeric_failures(int64_t* unresolved_out, int64_t* fallback_out) {
   if (!unresolved_out) return fail(RSPARSE_HIP_ERR_INVALID, "unresolved_out is NULL");
   // counts a stateless call found on the device when it started and set aside (see StaleFailures): still the resident layer's

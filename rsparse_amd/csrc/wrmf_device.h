@@ -234,6 +234,23 @@ __device__ u64 block_kth_largest(int n, int kth, int nbits, KeyFn key, unsigned*
   return prefix;
 }
 
+// ---- Philox4x32-10 (Random123; wrmf_init.hip, wrmf_sample.hip): counter (c0, c1, c2, c3), key (k0, k1) -> o[0..3] ----
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
+                                              unsigned (&o)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; r++) {
+    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0;
+    c1 = l1;
+    c2 = h0 ^ c3 ^ k1;
+    c3 = l0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
+}
+
 // ---- ordering a selection in LDS (wrmf_topk_large.hip, wrmf_candidates.hip) ----
 // workgroup-wide exclusive prefix of a flag (256 threads); *total = the sum.  Uses sw[4].
 __device__ __forceinline__ int block_prefix(bool f, int* sw, int* total) {

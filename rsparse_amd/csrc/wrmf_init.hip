@@ -26,7 +26,7 @@
 #include <algorithm>
 
 #include "wrmf_internal.h"
-#include "wrmf_wave.h"
+#include "wrmf_device.h"
 
 namespace rsparse_hip {
 namespace {
@@ -38,22 +38,6 @@ typedef double f64x2 __attribute__((ext_vector_type(2)));
 constexpr int kInitThreads = 256;
 // (at 8 waves per SIMD 2048 workgroups of 256 are resident on 256 CUs: 32 rounds of them, enough to even out the tail)
 constexpr unsigned kInitMaxBlocks = 1u << 16;
-
-__device__ __forceinline__ void philox4x32_10(u64 group, unsigned stream, unsigned k0, unsigned k1, unsigned (&o)[4]) {
-  unsigned c0 = (unsigned)group, c1 = (unsigned)(group >> 32), c2 = stream, c3 = 0u;
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0;
-    c1 = l1;
-    c2 = h0 ^ c3 ^ k1;
-    c3 = l0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
 
 // one Box-Muller pair from two words, in the arithmetic of the output type
 __device__ __forceinline__ void normal_pair(unsigned a, unsigned b, float& z0, float& z1) {
@@ -95,7 +79,7 @@ __global__ __launch_bounds__(kInitThreads) void init_factors_kernel(T* __restric
   for (u64 i = (u64)blockIdx.x * kInitThreads + threadIdx.x; i < n_groups; i += stride) {
     const u64 g = g0 + i, first = g << 2;
     unsigned o[4];
-    philox4x32_10(g, stream, k0, k1, o);
+    philox4x32_10((unsigned)g, (unsigned)(g >> 32), stream, 0u, k0, k1, o);
     T v[4];
     normal_pair(o[0], o[1], v[0], v[1]);
     normal_pair(o[2], o[3], v[2], v[3]);

@@ -391,6 +391,23 @@ template <class T>
 hipError_t launch_init_factors(uint64_t seed, int stream, int64_t row0, int n_rows, int rank, int64_t ld, double scale,
                                int abs_values, int ones_col, T* out, hipStream_t s);
 
+// negative sampling (wrmf_sample.hip): the stream is defined in rsparse_wrmf_hip.h.  launch_sample_row_pointers writes out_p
+// (n_rows + 1) from the lengths of the seen / keep rows on the device; ws: sample_negatives_ws_bytes(n_rows) bytes, *d_status
+// points into it, for the caller to read back before it samples: total = the 64-bit out_p[n_rows], flag non-zero = row pointers
+// that are negative or decrease, a seen row longer than n_item, a keep row longer than its seen row.  launch_sample_negatives
+// writes the rows: 1 <= n <= kSampleMaxNegatives, row0 + n_rows <= 2^32, keep_p / keep_j both null or both set.
+constexpr int kSampleMaxNegatives = 8192;
+struct SampleStatus {
+  long long total;
+  int flag, pad;
+};
+size_t sample_negatives_ws_bytes(int n_rows);
+hipError_t launch_sample_row_pointers(int n_rows, int n_item, int n, const int32_t* seen_p, const int32_t* keep_p, int32_t* out_p,
+                                      void* ws, SampleStatus** d_status, hipStream_t s);
+hipError_t launch_sample_negatives(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* seen_p,
+                                   const int32_t* seen_j, const int32_t* keep_p, const int32_t* keep_j, const int32_t* out_p,
+                                   int32_t* out_j, hipStream_t s);
+
 // item-to-item cosine similarity (wrmf_similar.hip): the operands of the top-k path above.
 // launch_normalize_items: V (fp32, or fp64 when f64) n_items x ld row-major, columns [c0, c0 + r), 1 <= r <= 256 ->
 // Vn64 / Vn32 (n_items x r, compact) with unit rows, flags[item] = 1 and a row of zeros where the sum of squares is zero or

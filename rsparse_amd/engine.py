@@ -441,6 +441,32 @@ class HipBackend:
                           float(glob_mean), res[a0:].data_ptr(), sc[a0:].data_ptr(), self._stream()))
         return res, sc
 
+    def sample_negatives(self, seed, row0, seen_p, seen_j, keep_p, keep_j, n_item, n):
+        """the candidate rows of a sampled-metric evaluation, made on the device (wrmf_sample.hip; rsparse_amd/rng.py
+        sample_negatives is the definition): for every row of the CSR pattern (seen_p, seen_j: int32 on the device, columns
+        ascending and unique; seen_p may be a slice of a larger pattern's row pointers) its `keep` items (keep_p / keep_j, a subset
+        of the seen row, or both None) merged with min(n, n_item - |seen|) items drawn without replacement from outside the seen
+        row, under `seed` and the global row index row0 + u.  -> (out_p, out_j): canonical CSR from 0, int32 on the device, out_j
+        sliced to its true length."""
+        assert seen_p.dtype == torch.int32 and seen_j.dtype == torch.int32 and (keep_p is None) == (keep_j is None)
+        n_rows, n = int(seen_p.numel()) - 1, int(n)
+        dev = seen_p.device
+        out_p = torch.zeros(max(n_rows, 0) + 1, dtype=torch.int32, device=dev)
+        if n_rows <= 0:
+            return out_p, torch.empty(0, dtype=torch.int32, device=dev)
+        kept = 0
+        if keep_p is not None:
+            assert keep_p.dtype == torch.int32 and keep_j.dtype == torch.int32 and int(keep_p.numel()) == n_rows + 1
+            kept = int(keep_p[-1]) - int(keep_p[0])
+        cap = max(0, kept) + n_rows * max(min(n, int(n_item)), 0)
+        out_j = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        one = torch.zeros(1, dtype=torch.int32, device=dev)   # (a pattern without entries: the library still wants non-NULL slots)
+        _lib.check(self.lib.rsparse_hip_sample_negatives_device(
+            int(seed), int(row0), n_rows, int(n_item), n, seen_p.data_ptr(), (seen_j if seen_j.numel() else one).data_ptr(),
+            None if keep_p is None else keep_p.data_ptr(), None if keep_p is None else (keep_j if keep_j.numel() else one).data_ptr(),
+            out_p.data_ptr(), out_j.data_ptr(), cap, self._stream()))
+        return out_p, out_j[:int(out_p[-1])]
+
     def ranking_metrics(self, res, p, j, x, want_ap=True, want_ndcg=True):
         """ap_k / ndcg_k (R/metrics.R:31-127) of the lists `res` (n x k int32 on the device, 1-based with NA_integer_, as
         top_product returns them) against `actual` as CSR slots on the device (p, j int32 with j sorted within rows; x float64,

@@ -13,12 +13,30 @@ oracle of its tests, and the fallback of a backend that has no device.
 A value depends on (seed, stream, row, col, rank) alone: not on the row range asked for, the number of ranks or the device.
 Evaluated in float64 and cast at the end.  |z| <= sqrt(48 ln 2) = 5.77; z is exactly 0 only for u_a = 1 (one pair in 2^24) or
 at a quarter turn of u_b (four values in 2^24).
+
+`sample_negatives` is the specification of the third stream of the same generator: per-row uniform samples WITHOUT replacement of
+the items outside a row's exclusion list (rsparse_amd/csrc/wrmf_sample.hip draws it on the device, bit for bit; the header states
+it for C hosts).  For the row with global index g, seen = its sorted unique exclusion list, keep = the sorted unique items copied
+into the output (a subset of seen), M = n_item - |seen| admissible items numbered by RANK 0 .. M - 1 in ascending item order:
+
+    item(r)   r + #{i : seen[i] - i <= r}                     (a binary search: seen[i] - i does not decrease)
+    draw t    Philox4x32-10, key (lo32(seed), hi32(seed)), counter (lo32(t >> 1), g, 2, hi32(t >> 1)) -> o0..o3;
+              w = o1 2^32 + o0 for even t, o3 2^32 + o2 for odd t;  rank = floor(w M / 2^64) = (o_hi M + ((o_lo M) >> 32)) >> 32
+              (exact in 64-bit unsigned arithmetic for M < 2^31; bias at most M / 2^64)
+    chosen    n >= M: every rank.  Otherwise d = min(n, M - n) and D = the first d DISTINCT values of the draw sequence
+              t = 0, 1, 2, ...; the chosen ranks are D when 2 n <= M and every rank but D otherwise (the row then draws what it
+              leaves out: no row needs more than about M ln 2 draws)
+    row       the ascending merge of keep and the items of the chosen ranks: |keep| + min(n, M) entries
+
+The negatives depend on (seed, g, seen, n_item, n) alone: not on the rows asked for together, the device, or the order in which
+the draws are evaluated ("the first d distinct values" is a property of the sequence).
 """
 import numpy as np
 
 PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
 PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
-STREAM_USERS, STREAM_ITEMS = 0, 1
+STREAM_USERS, STREAM_ITEMS, STREAM_NEGATIVES = 0, 1, 2
+MAX_NEGATIVES = 8192   # RSPARSE_HIP_MAX_NEGATIVES
 _MASK = np.uint64(0xFFFFFFFF)
 _S32 = np.uint64(32)
 
@@ -91,3 +109,62 @@ def init_factors(seed, stream, row0, n_rows, rank, scale=0.01, abs_values=False,
     if return_radius:
         return out, rad.reshape(-1)[lo:hi].reshape(n_rows, rank)
     return out
+
+
+def negative_draws(seed, g, t0, count, M):
+    """the ranks of the draws t0 .. t0 + count - 1 of global row g among M admissible items -> uint64 array"""
+    t = np.arange(t0, t0 + count, dtype=np.uint64)
+    c = t >> np.uint64(1)
+    counter = np.stack([c & _MASK, np.full_like(c, g), np.full_like(c, STREAM_NEGATIVES), c >> _S32], axis=-1)
+    key = np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64)
+    o = philox4x32_10(counter, key).astype(np.uint64)
+    odd = (t & np.uint64(1)).astype(bool)
+    lo, hi = np.where(odd, o[:, 2], o[:, 0]), np.where(odd, o[:, 3], o[:, 1])
+    m = np.uint64(M)
+    return (hi * m + ((lo * m) >> _S32)) >> _S32       # hi M < 2^63 and the carry < 2^31: no overflow
+
+
+def first_distinct(seed, g, M, d):
+    """the first d distinct ranks of row g's draw sequence, in the order of their first occurrence (needs d <= M)"""
+    drawn = np.zeros(0, dtype=np.uint64)
+    while True:
+        step = max(64, 2 * d, drawn.size)
+        drawn = np.concatenate([drawn, negative_draws(seed, g, drawn.size, step, M)])
+        vals, first = np.unique(drawn, return_index=True)
+        if vals.size >= d:
+            return vals[np.argsort(first, kind="stable")[:d]].astype(np.int64)
+
+
+def sample_negatives(seed, row0, seen_p, seen_j, keep_p, keep_j, n_item, n):
+    """For every row u of the CSR pattern (seen_p, seen_j) -- global row row0 + u, columns sorted and unique --: the row's `keep`
+    items (CSR (keep_p, keep_j), a subset of its seen items; both None = keep nothing) merged with min(n, M) items sampled
+    uniformly without replacement from the M = n_item - |seen| items outside `seen` (the definition at the top of this file).
+    -> (out_p, out_j): canonical CSR, int32."""
+    seed, row0, n_item, n = int(seed), int(row0), int(n_item), int(n)
+    if not 0 <= seed < 2 ** 64 or row0 < 0 or not 0 <= n_item < 2 ** 31 or n < 1 or (keep_p is None) != (keep_j is None):
+        raise ValueError("sample_negatives: bad arguments")
+    if n > MAX_NEGATIVES:
+        raise NotImplementedError("sample_negatives: n > %d" % MAX_NEGATIVES)
+    sp_, sj = np.asarray(seen_p, dtype=np.int64), np.asarray(seen_j, dtype=np.int64)
+    n_rows = sp_.size - 1
+    if row0 + n_rows > 2 ** 32:
+        raise ValueError("sample_negatives: the global row index does not fit 32 bits")
+    kp = np.zeros(n_rows + 1, dtype=np.int64) if keep_p is None else np.asarray(keep_p, dtype=np.int64)
+    kj = np.zeros(0, dtype=np.int64) if keep_j is None else np.asarray(keep_j, dtype=np.int64)
+    rows = []
+    for u in range(n_rows):
+        seen, keep = sj[sp_[u]:sp_[u + 1]], kj[kp[u]:kp[u + 1]]
+        M = n_item - seen.size
+        if n >= M:
+            ranks = np.arange(max(M, 0), dtype=np.int64)
+        else:
+            d = min(n, M - n)
+            D = first_distinct(seed, row0 + u, M, d)
+            ranks = np.sort(D) if 2 * n <= M else np.setdiff1d(np.arange(M, dtype=np.int64), D)
+        items = ranks + np.searchsorted(seen - np.arange(seen.size), ranks, side="right")
+        rows.append(np.sort(np.concatenate([keep, items])))
+    out_p = np.concatenate([[0], np.cumsum([r.size for r in rows])])
+    if out_p[-1] >= 2 ** 31:
+        raise ValueError("sample_negatives: the output does not fit int32 row pointers")
+    out_j = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+    return out_p.astype(np.int32), out_j.astype(np.int32)

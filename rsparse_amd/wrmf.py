@@ -204,6 +204,15 @@ class WRMF:
             return dist.get_world_size(self._group), dist.get_rank(self._group)
         return 1, 0
 
+    def _share_seed(self, seed, dev0):
+        """rank 0's 64-bit seed on every rank of the group (8 bytes broadcast; dev0: the device the collective runs on)"""
+        import torch.distributed as dist
+        src0 = dist.get_global_rank(self._group, 0) if self._group is not None else 0
+        seed = int(seed)
+        t = torch.tensor([seed - 2 ** 64 if seed >= 2 ** 63 else seed], dtype=torch.int64).to(dev0)
+        dist.broadcast(t, src=src0, group=self._group)
+        return int(t.cpu()[0]) % 2 ** 64
+
     def _initial_factors_device(self, be, n_user, n_item, share_seed=None, share_given=None):
         """factor_init = "device": (U, V) on the device, (n_user, rank) and (n_item, rank) in the device dtype, under the rules of
         the host draw (R/model_WRMF.R:203-255) -- `_init_user_factors` replaces the user draw and `init` the item draw, the
@@ -417,9 +426,7 @@ class WRMF:
             src0 = dist.get_global_rank(self._group, 0) if self._group is not None else 0
 
             def share_seed(seed):
-                t = torch.tensor([seed], dtype=torch.int64).to(dev0)
-                dist.broadcast(t, src=src0, group=self._group)
-                return int(t.cpu()[0])
+                return self._share_seed(seed, dev0)
 
             def share_given(buf):
                 t = torch.from_numpy(buf).to(dev0)
@@ -638,10 +645,10 @@ class WRMF:
         out.scores = sc.cpu().numpy().astype(self._np_dtype())
         return out
 
-    def _exclusion_args(self, x, not_recommend, items_exclude):
+    def _exclusion_args(self, x, not_recommend, items_exclude, n_item=None):
         """the checks `predict` makes of its exclusions (x: CSR, n x n_item) -> (items_exclude sorted and unique,
         not_recommend as a sparse matrix or None)"""
-        n_item = self._V.shape[0]
+        n_item = self._V.shape[0] if n_item is None else n_item
         excl = np.unique(np.asarray(list(items_exclude), dtype=np.int64))
         if excl.size and (excl.min() < 0 or excl.max() >= n_item):
             raise ValueError("some of items_exclude indices are bigger than number of items")      # :59-60
@@ -668,9 +675,10 @@ class WRMF:
         d_ex = be.to_device(excl, torch.int32) if excl.size else None
         return nr_p, nr_j, d_ex
 
-    def _predict_device(self, x, k, not_recommend, items_exclude, candidates=None):
+    def _predict_device(self, x, k, not_recommend, items_exclude, candidates=None, negatives=None):
         """the device part of `predict`: (indices int32, scores float64) of this rank's block of rows, _row_bounds[rank], still
-        on the device -- 1-based with NA_integer_ as top_product writes them --, and x as CSR"""
+        on the device -- 1-based with NA_integer_ as top_product writes them --, and x as CSR.  negatives = (n, seed, actual as
+        canonical CSR): the candidates are sampled here (`sample_negatives`), batch by batch, and never leave the device."""
         if self._V is None:
             raise RuntimeError("model is not fitted")
         x = sp.csr_matrix(x, dtype=np.float64)
@@ -679,14 +687,19 @@ class WRMF:
             raise ValueError("ncol(x) == ncol(self$components) is not TRUE")
         k = int(k)
         cand = None
-        if candidates is not None:
-            _, cand = self._pairs_pattern(x, candidates, "candidates")
+        if candidates is not None or negatives is not None:
+            if candidates is not None:
+                _, cand = self._pairs_pattern(x, candidates, "candidates")
             if k < 1:
                 raise ValueError("k must be at least 1")
             if k > 8192:   # RSPARSE_HIP_MAX_TOPK_LARGE
                 raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "predict: k > 8192 is not on the device path")
         excl, not_recommend = self._exclusion_args(x, not_recommend, items_exclude)
         be = self._backend()
+        if negatives is not None:
+            n_neg, seed, act = negatives
+            seen, keep = self._negatives_lists(x, n_item, act, not_recommend, excl)
+            seed = self._negatives_seed(seed)
         emb = self._transform_device(x)             # (n_new, rank), complete on every rank
         # several ranks: every rank scores its own block of rows (the same blocks as transform), then the blocks are shared
         a, b, ws = self._my_rows(x)
@@ -698,6 +711,13 @@ class WRMF:
             c_p, c_j = be.to_device(mine.indptr, torch.int32), be.to_device(mine.indices, torch.int32)
             fn = be.top_candidates if hasattr(be, "top_candidates") else self._top_candidates_host
             res, sc = fn(emb[a:b], self._V, k, c_p, c_j, nr_p, nr_j, d_ex, float(self.global_bias))
+        elif n_mine > 0 and negatives is not None:
+            fn = be.top_candidates if hasattr(be, "top_candidates") else self._top_candidates_host
+            res = torch.empty((n_mine, k), dtype=torch.int32, device=emb.device)
+            sc = torch.empty((n_mine, k), dtype=torch.float64, device=emb.device)
+            for a0, b0, c_p, c_j in self._negatives_batches(be, seed, seen, keep, a, b, n_item, n_neg):
+                res[a0:b0], sc[a0:b0] = fn(emb[a + a0:a + b0], self._V, k, c_p, c_j, None if nr_p is None else nr_p[a0:b0 + 1], nr_j,
+                                           d_ex, float(self.global_bias))
         elif n_mine > 0:
             res, sc = be.top_product(emb[a:b], self._V, k, nr_p, nr_j, d_ex, float(self.global_bias))
         else:
@@ -742,20 +762,27 @@ class WRMF:
             sc[u, :kk] = s[order]
         return torch.from_numpy(res).to(U.device), torch.from_numpy(sc).to(U.device)
 
-    def evaluate(self, x, actual, k, not_recommend="x", items_exclude=(), metrics=("ap", "ndcg"), candidates=None):
+    def evaluate(self, x, actual, k, not_recommend="x", items_exclude=(), metrics=("ap", "ndcg"), candidates=None, negatives=None,
+                 seed=None):
         """`predict(x, k, ...)` scored against the held-out interactions `actual` (n x anything sparse, relevances as values) by
         the reference's ap_k / ndcg_k (R/metrics.R:31-127) without the lists leaving the device: {name: float64 vector of n}
         for each name in `metrics` ("ap", "ndcg").  Equals `rsparse_amd.metrics.ap_k(self.predict(x, k, ...), actual)` (and
         ndcg_k) bit for bit.  Under torch.distributed every rank scores the block of rows it predicts.  `candidates`: as in
-        `predict` -- the lists are ranked within every row's candidates (sampled-negative evaluation)."""
+        `predict` -- the lists are ranked within every row's candidates (sampled-negative evaluation).  `negatives=n` (with
+        `seed`) makes those candidates itself: every row's held-out items against n sampled negatives, exactly
+        `candidates=self.sample_negatives(x, n, actual, not_recommend, items_exclude, seed)` -- bit for bit -- but sampled on the
+        device in row batches and handed to the ranking without a host copy; it excludes `candidates`."""
         from .metrics import canonical_actual
         metrics = tuple(metrics)
         if not metrics or any(m not in ("ap", "ndcg") for m in metrics):
             raise ValueError("metrics must name some of 'ap', 'ndcg'")
+        if negatives is not None and candidates is not None:
+            raise ValueError("negatives and candidates exclude each other: the negatives ARE the candidates")
         x = sp.csr_matrix(x, dtype=np.float64)
         n_new = x.shape[0]
         act = canonical_actual(actual, n_new)
-        res, _, x = self._predict_device(x, k, not_recommend, items_exclude, candidates)
+        neg = None if negatives is None else (self._negatives_count(negatives), seed, act)
+        res, _, x = self._predict_device(x, k, not_recommend, items_exclude, candidates, neg)
         ws, me = self._dist()
         a, b = self._row_bounds[me]
         mine = act[a:b]
@@ -770,6 +797,124 @@ class WRMF:
                     v = self._share_rows(v, self._row_bounds, n_new)
                 out[name] = v.cpu().numpy()
         return out
+
+    negatives_batch = None   # candidates per sampling call (None: the backend's top_candidates_batch, 2^28): bounds the memory
+
+    @staticmethod
+    def _negatives_count(n):
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+            raise TypeError("negatives must be an integer")
+        if n < 1:
+            raise ValueError("negatives must be at least 1")
+        if n > 8192:   # RSPARSE_HIP_MAX_NEGATIVES
+            raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "more than 8192 negatives per row are not on the device path")
+        return int(n)
+
+    def _negatives_seed(self, seed):
+        """the seed of a sampling call: given, or one 63-bit draw from the model's generator (as factor_init="device" takes
+        its own); with several ranks rank 0's, so that every rank samples the same stream"""
+        seed = int(self._rng.integers(2 ** 63)) if seed is None else int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must fit 64 unsigned bits")
+        if self._dist()[0] > 1:
+            be = self._backend()
+            seed = self._share_seed(seed, be.to_device(np.zeros(1, dtype=np.float32), torch.float32).device)
+        return seed
+
+    @staticmethod
+    def _negatives_lists(x, n_item, act, not_recommend, excl):
+        """(seen, keep) of `sample_negatives` as canonical CSR patterns (n x n_item, values 1): seen = the union of the
+        not_recommend row, the row of `act` and `excl`, formed once on the host; keep = the pattern of `act` (None: empty)"""
+        n_new = x.shape[0]
+
+        def pattern(m):
+            m = sp.csr_matrix(m)
+            if m.shape[0] != n_new or m.shape[1] > n_item:
+                raise ValueError("actual / not_recommend must have the rows of x and at most its columns")
+            return sp.csr_matrix((np.ones(m.indices.size), m.indices, m.indptr), shape=(n_new, n_item))   # stored zeros count
+        seen = sp.csr_matrix((n_new, n_item))
+        keep = sp.csr_matrix((n_new, n_item))
+        if act is not None:
+            keep = pattern(act)
+            seen = seen + keep
+        if not_recommend is not None:
+            seen = seen + pattern(not_recommend)
+        if len(excl):   # n_new x |excl| entries: a long exclusion list is better taken out of the catalogue beforehand
+            seen = seen + sp.csr_matrix((np.ones(n_new * len(excl)), np.tile(excl, n_new), np.arange(n_new + 1) * len(excl)),
+                                        shape=(n_new, n_item))
+        out = []
+        for m in (seen, keep):
+            m = sp.csr_matrix(m)
+            m.sum_duplicates()
+            m.sort_indices()
+            m.data = np.ones(m.indices.size)
+            out.append(m)
+        return out
+
+    def _negatives_batches(self, be, seed, seen, keep, a, b, n_item, n):
+        """the candidate rows of the rows [a, b) in batches of whole rows: yields (a0, b0, c_p, c_j) with a0 / b0 counted from a and
+        (c_p, c_j) the batch's canonical CSR pattern on the device, row pointers from 0.  A batch's rows are sampled with row0 =
+        their first global row, so the batching cannot change a row."""
+        from . import rng as _rng
+        seen, keep = seen[a:b], keep[a:b]
+        budget = self.negatives_batch or getattr(be, "top_candidates_batch", 1 << 28)
+        upper = np.concatenate([[0], np.cumsum(np.diff(keep.indptr).astype(np.int64) + n)])   # most a row can take
+        on_dev = hasattr(be, "sample_negatives")
+        if on_dev:
+            s_p, s_j = be.to_device(seen.indptr, torch.int32), be.to_device(seen.indices, torch.int32)
+            k_p, k_j = (be.to_device(keep.indptr, torch.int32), be.to_device(keep.indices, torch.int32)) if keep.nnz else (None, None)
+        a0, n_mine = 0, b - a
+        while a0 < n_mine:
+            b0 = int(np.searchsorted(upper, upper[a0] + budget, side="right")) - 1
+            b0 = min(n_mine, max(b0, a0 + 1))
+            if on_dev:
+                c_p, c_j = be.sample_negatives(seed, a + a0, s_p[a0:b0 + 1], s_j, None if k_p is None else k_p[a0:b0 + 1], k_j,
+                                               n_item, n)
+            else:   # the backend has no sampler (the CPU stand-in of the tests): the numpy specification
+                c_p, c_j = _rng.sample_negatives(seed, a + a0, seen.indptr[a0:b0 + 1], seen.indices, keep.indptr[a0:b0 + 1],
+                                                 keep.indices, n_item, n)
+                c_p, c_j = be.to_device(c_p, torch.int32), be.to_device(c_j, torch.int32)
+            yield a0, b0, c_p, c_j
+            a0 = b0
+
+    def sample_negatives(self, x, n, actual=None, not_recommend="x", items_exclude=(), seed=None):
+        """The candidate matrix of a sampled-metric evaluation: row u holds the stored positions of row u of `actual` (the
+        held-out items; None: nothing) plus min(n, admissible) items drawn uniformly WITHOUT replacement from the items that are
+        neither in the row of `not_recommend` (default: `x` itself; None = nothing), nor in the row of `actual`, nor in
+        `items_exclude`.  Returns a scipy CSR matrix (n_rows x n_item, values 1) to pass to `candidates=`, store, or reuse across
+        models: the negatives depend on (seed, row, the row's exclusions, n_item, n) alone -- not on the model (two models given
+        the same seed see the same negatives), the number of ranks or the device.  `seed=None` takes one 63-bit seed from the
+        model's generator; under torch.distributed every rank uses rank 0's seed and samples its own block of rows.  The draws
+        are made on the device (wrmf_sample.hip; rsparse_amd/rng.py is the definition); the exclusion lists are joined once on
+        the host with scipy, where `items_exclude` costs n_rows x len(items_exclude) entries.  1 <= n <= 8192.  Needs no fitted
+        factors: an unfitted model samples for the shape of `x`."""
+        n = self._negatives_count(n)
+        x = sp.csr_matrix(x, dtype=np.float64)
+        n_new, n_item = x.shape
+        if self._V is not None and n_item != self._V.shape[0]:
+            raise ValueError("ncol(x) == ncol(self$components) is not TRUE")
+        from .metrics import canonical_actual
+        act = None if actual is None else canonical_actual(actual, n_new)
+        excl, not_recommend = self._exclusion_args(x, not_recommend, items_exclude, n_item)
+        if not_recommend is not None and sp.csr_matrix(not_recommend).shape != (n_new, n_item):
+            raise ValueError("not_recommend must have the shape of x")
+        seen, keep = self._negatives_lists(x, n_item, act, not_recommend, excl)
+        seed = self._negatives_seed(seed)
+        be = self._backend()
+        a, b, ws = self._my_rows(x)
+        dev = be.to_device(np.zeros(1, dtype=np.int32), torch.int32).device
+        lens, cols = [torch.zeros(0, dtype=torch.int64, device=dev)], [torch.zeros(0, dtype=torch.int32, device=dev)]
+        for _, _, c_p, c_j in self._negatives_batches(be, seed, seen, keep, a, b, n_item, n):
+            lens.append(torch.diff(c_p.to(torch.int64)))
+            cols.append(c_j)
+        lens, cols = torch.cat(lens), torch.cat(cols)
+        if ws > 1:
+            lens = self._share_rows(lens, self._row_bounds, n_new)
+            ip = np.concatenate([[0], np.cumsum(lens.cpu().numpy())])
+            cols = self._share_rows(cols, [(int(ip[r0]), int(ip[r1])) for r0, r1 in self._row_bounds], int(ip[-1]))
+        indptr = np.concatenate([[0], np.cumsum(lens.cpu().numpy())])
+        idx = cols.cpu().numpy()
+        return sp.csr_matrix((np.ones(idx.size), idx, indptr), shape=(n_new, n_item))
 
     def _score_device(self, x, pattern, actual, want_scores):
         """the device part of `score` / `evaluate_values`: the embeddings of the rows of x (as `predict` gets them), then this
