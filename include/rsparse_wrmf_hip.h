@@ -675,6 +675,58 @@ int rsparse_hip_sample_negatives(uint64_t seed, int64_t row0, int n_rows, int n_
                                  const int32_t* seen_j, const int32_t* keep_p, const int32_t* keep_j, int32_t* out_p, int32_t* out_j,
                                  int64_t out_capacity);
 
+/* Train / test split of an interaction matrix: every stored entry of the CSR (p, j, v) -- canonical: columns ascending and unique
+ * within a row; stored zeros count as entries -- goes to exactly one of two CSR matrices, `train` and `test`, in its order, with
+ * its index and its value (copied as an opaque word of value_bytes = 4 or 8 bytes; 0 = the pattern only, v and the value outputs
+ * NULL).  The stream is DEFINED here, so that any host can reproduce a row; rsparse_amd/rng.py (split_flags) is the definition
+ * in numpy.  Row u has the GLOBAL index g = row0 + u and L entries; an entry is named by its position t = 0 .. L - 1 in the row;
+ * the key is (lo32(seed), hi32(seed)); word 2 of the counter is the stream id (0, 1 the factor streams, 2 the negatives).
+ *
+ *   RSPARSE_HIP_SPLIT_PROPORTION   Philox4x32-10 with counter (t >> 2, g, 3, 0) gives o0..o3; the entry takes word o[t & 3] and
+ *              is TEST iff word < test_threshold, compared in 64 bits.  test_threshold = floor(p * 2^32) is an integer in
+ *              [0, 2^32] (exact for a double p): 0 puts nothing in test, 2^32 everything.  Every entry is test independently
+ *              with probability p.  leave_out, min_train are ignored; `by` must be NULL.
+ *   RSPARSE_HIP_SPLIT_LEAVE_OUT    exactly h = min(leave_out, max(L - min_train, 0)) entries of the row are test (leave_out >= 1,
+ *              min_train >= 0).  Every entry has a 64-bit key w; the test entries are the first h of the total order in which a
+ *              comes before b iff w_a > w_b, or w_a = w_b and t_a < t_b.
+ *                by == NULL: counter (t >> 1, g, 4, 0); w = o1 * 2^32 + o0 for even t, o3 * 2^32 + o2 for odd t (the word
+ *                  pairing of the negatives' draw).
+ *                by != NULL (one double per stored entry, addressed like j: a timestamp, for a temporal leave-last-out): with u =
+ *                  the bits of by[t], w = ~u if the sign bit is set, else u | 2^63 -- the order-preserving map, so the h LARGEST
+ *                  values are held out and ties go to the lower position; -0.0 therefore orders just below +0.0.  No random
+ *                  word is used and seed is ignored.  NaN has no place in the order: the host form refuses it, the device form
+ *                  leaves it to the caller (a NaN is then ordered by its bits; nothing is written out of place).
+ * A flag depends on (seed, g, t, the mode's parameters) and, in leave-out mode, on the row's L or `by` values -- not on the rows
+ * split together (rows [a, b) split with row0 = a are rows a .. b - 1 of the whole), the number of devices, or the device.
+ * Limits: row0 + n_rows <= 2^32, L < 2^31, fewer than 2^31 entries in all (int32 row pointers).
+ *
+ * _device: every pointer is device memory; d_p (n_rows + 1 slots) may be a slice of a larger pattern's row pointers (absolute
+ * positions into d_j / d_v / d_by).  d_train_p and d_test_p (n_rows + 1 each, from 0) are always written (n_rows >= 1), from counts made on
+ * the device; the call then waits for the stream once to read both totals back and refuses, BEFORE anything else is written, row
+ * pointers that are negative or decrease and a total beyond its capacity (the entries the train / test outputs have room for)
+ * -> ERR_INVALID.  With d_train_j == NULL and d_test_j == NULL the call returns after the row pointers (train_p[n_rows] and
+ * test_p[n_rows] are the capacities a second call needs).  Repeat calls are bit-identical.
+ *
+ * Host form: host pointers, p from 0; additionally checks that the columns of every row ascend strictly and that `by` holds no
+ * NaN -> ERR_INVALID.
+ *
+ * Both: a NULL p, j, train_p or test_p; only one of the two j outputs; n_rows < 0; row0 < 0; row0 + n_rows > 2^32; a mode other
+ * than the two; test_threshold > 2^32 or `by` in proportion mode; leave_out < 1 or min_train < 0 in leave-out mode; value_bytes
+ * not in {0, 4, 8}; v without value_bytes (or value_bytes without v); value outputs missing where the j outputs and values are
+ * given; a negative capacity -> ERR_INVALID, all before a device is touched.  n_rows == 0 -> OK, nothing is launched; the device form then
+ * writes nothing at all (not even slot [0] of the row pointers), the host form writes train_p[0] = test_p[0] = 0. */
+#define RSPARSE_HIP_SPLIT_PROPORTION 0
+#define RSPARSE_HIP_SPLIT_LEAVE_OUT 1
+int rsparse_hip_split_rows_device(uint64_t seed, int64_t row0, int n_rows, int mode, uint64_t test_threshold, int leave_out,
+                                  int min_train, const int32_t* d_p, const int32_t* d_j, const void* d_v, int value_bytes,
+                                  const double* d_by, int32_t* d_train_p, int32_t* d_train_j, void* d_train_v, int32_t* d_test_p,
+                                  int32_t* d_test_j, void* d_test_v, int64_t train_capacity, int64_t test_capacity,
+                                  void* hip_stream);
+int rsparse_hip_split_rows(uint64_t seed, int64_t row0, int n_rows, int mode, uint64_t test_threshold, int leave_out, int min_train,
+                           const int32_t* p, const int32_t* j, const void* v, int value_bytes, const double* by, int32_t* train_p,
+                           int32_t* train_j, void* train_v, int32_t* test_p, int32_t* test_j, void* test_v, int64_t train_capacity,
+                           int64_t test_capacity);
+
 /* ------------------------------------------------------------------------------------------------
  * (3) fp64 device layer: als_implicit<double> / als_explicit<double> with the data resident in HBM
  * ---------------------------------------------------------------------------------------------- */

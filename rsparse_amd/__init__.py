@@ -3,6 +3,7 @@
 Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit,explicit}.hpp):
   rsparse_amd.WRMF            host-side mirror of the R6 class
   rsparse_amd.metrics         ap_k() / ndcg_k(), the reference's ranking metrics, on the device
+  rsparse_amd.train_test_split  the reference's train_test_split (and leave-n-out), drawn on the device
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
   rsparse_amd.engine          device-resident, row-sharded driver (one process per GPU)
   rsparse_amd.synth           synthetic interaction matrices for the BASELINE configs
@@ -15,6 +16,9 @@ def __getattr__(name):
     if name == "WRMF":
         from .wrmf import WRMF
         return WRMF
+    if name == "train_test_split":
+        from .split import train_test_split
+        return train_test_split
     if name == "metrics":
         import importlib
         return importlib.import_module(".metrics", __name__)

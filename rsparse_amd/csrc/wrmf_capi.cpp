@@ -1671,6 +1671,134 @@ int rsparse_hip_sample_negatives(uint64_t seed, int64_t row0, int n_rows, int n_
   return RSPARSE_HIP_OK;
 }
 
+namespace {
+// what both forms of rsparse_hip_split_rows check before anything else
+int split_rows_args(int64_t row0, int n_rows, int mode, uint64_t test_threshold, int leave_out, int min_train, const void* p,
+                    const void* j, const void* v, int value_bytes, const void* by, const void* train_p, const void* train_j,
+                    const void* train_v, const void* test_p, const void* test_j, const void* test_v, int64_t train_capacity,
+                    int64_t test_capacity) {
+  if (n_rows < 0 || row0 < 0 || train_capacity < 0 || test_capacity < 0)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, row0 < 0 or a negative capacity)");
+  if (row0 + n_rows > (1ll << 32)) return fail(RSPARSE_HIP_ERR_INVALID, "the global row index row0 + n_rows does not fit 32 bits");
+  if (!p || !j || !train_p || !test_p) return fail(RSPARSE_HIP_ERR_INVALID, "p, j, train_p or test_p is NULL");
+  if (!train_j != !test_j) return fail(RSPARSE_HIP_ERR_INVALID, "train_j and test_j must both be given or both be NULL");
+  if (mode == RSPARSE_HIP_SPLIT_PROPORTION) {
+    if (test_threshold > (1ull << 32)) return fail(RSPARSE_HIP_ERR_INVALID, "test_threshold > 2^32");
+    if (by) return fail(RSPARSE_HIP_ERR_INVALID, "`by` has no meaning in proportion mode");
+  } else if (mode == RSPARSE_HIP_SPLIT_LEAVE_OUT) {
+    if (leave_out < 1 || min_train < 0) return fail(RSPARSE_HIP_ERR_INVALID, "leave_out < 1 or min_train < 0");
+  } else {
+    return fail(RSPARSE_HIP_ERR_INVALID, "mode is neither RSPARSE_HIP_SPLIT_PROPORTION nor RSPARSE_HIP_SPLIT_LEAVE_OUT");
+  }
+  if (value_bytes != 0 && value_bytes != 4 && value_bytes != 8) return fail(RSPARSE_HIP_ERR_INVALID, "value_bytes must be 0, 4 or 8");
+  if (!v != (value_bytes == 0)) return fail(RSPARSE_HIP_ERR_INVALID, "v and value_bytes must both be given or both be 0");
+  if (v && train_j && (!train_v || !test_v)) return fail(RSPARSE_HIP_ERR_INVALID, "values are given: train_v and test_v must be too");
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+
+int rsparse_hip_split_rows_device(uint64_t seed, int64_t row0, int n_rows, int mode, uint64_t test_threshold, int leave_out,
+                                  int min_train, const int32_t* d_p, const int32_t* d_j, const void* d_v, int value_bytes,
+                                  const double* d_by, int32_t* d_train_p, int32_t* d_train_j, void* d_train_v, int32_t* d_test_p,
+                                  int32_t* d_test_j, void* d_test_v, int64_t train_capacity, int64_t test_capacity, void* stream) {
+  int rc = split_rows_args(row0, n_rows, mode, test_threshold, leave_out, min_train, d_p, d_j, d_v, value_bytes, d_by, d_train_p,
+                           d_train_j, d_train_v, d_test_p, d_test_j, d_test_v, train_capacity, test_capacity);
+  if (rc) return rc;
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = g_ws.ensure_device())) return rc;
+  HIP_TRY(g_ws.score_buf.ensure((split_ws_bytes(n_rows) + 7) / 8));
+  SplitStatus* d_status = nullptr;
+  hipError_t e = launch_split_count(seed, row0, n_rows, mode, test_threshold, leave_out, min_train, d_p, d_by, d_train_p, d_test_p,
+                                    g_ws.score_buf, &d_status, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_split_count");
+  SplitStatus st = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(&st, d_status, sizeof(st), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (st.flag) return fail(RSPARSE_HIP_ERR_INVALID, "row pointers that are negative or decrease");
+  if (!d_train_j) return RSPARSE_HIP_OK;   // the sizes only
+  if (st.total_train > train_capacity || st.total_test > test_capacity)
+    return fail(RSPARSE_HIP_ERR_INVALID, "the capacities are " + std::to_string(train_capacity) + " / " + std::to_string(test_capacity) +
+                                             ", the split needs " + std::to_string(st.total_train) + " / " + std::to_string(st.total_test));
+  if (st.total_train + st.total_test == 0) return RSPARSE_HIP_OK;
+  e = launch_split_write(seed, row0, n_rows, mode, test_threshold, leave_out, min_train, d_p, d_j, d_v, value_bytes, d_by, d_train_p,
+                         d_train_j, d_train_v, d_test_p, d_test_j, d_test_v, g_ws.score_buf, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_split_write");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_split_rows(uint64_t seed, int64_t row0, int n_rows, int mode, uint64_t test_threshold, int leave_out, int min_train,
+                           const int32_t* p, const int32_t* j, const void* v, int value_bytes, const double* by, int32_t* train_p,
+                           int32_t* train_j, void* train_v, int32_t* test_p, int32_t* test_j, void* test_v, int64_t train_capacity,
+                           int64_t test_capacity) {
+  int rc = split_rows_args(row0, n_rows, mode, test_threshold, leave_out, min_train, p, j, v, value_bytes, by, train_p, train_j,
+                           train_v, test_p, test_j, test_v, train_capacity, test_capacity);
+  if (rc) return rc;
+  // the dgRMatrix slots: p from 0, non-decreasing; j strictly ascending within a row; no NaN to order by
+  if (p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "p[0] != 0");
+  for (int u = 0; u < n_rows; u++) {
+    if (p[u + 1] < p[u]) return fail(RSPARSE_HIP_ERR_INVALID, "p decreases");
+    for (int32_t e = p[u]; e < p[u + 1]; e++) {
+      if (j[e] < 0 || (e > p[u] && j[e] <= j[e - 1]))
+        return fail(RSPARSE_HIP_ERR_INVALID, "an index is negative, or a row's indices are not strictly ascending");
+      if (by && by[e] != by[e]) return fail(RSPARSE_HIP_ERR_INVALID, "NaN in `by`");
+    }
+  }
+  train_p[0] = test_p[0] = 0;
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  const size_t nnz = (size_t)p[n_rows], np1 = (size_t)n_rows + 1, slots = std::max<size_t>(nnz, 1);
+  const bool write = train_j != nullptr;
+  DevBuf dP, dJ, dV, dB, dTrP, dTeP, dTrJ, dTeJ, dTrV, dTeV;
+  HIP_TRY(upload_host(dP, p, np1));
+  HIP_TRY(dJ.alloc(slots * 4));   // (never NULL: the device form wants the slot)
+  if (nnz) HIP_TRY(hipMemcpy(dJ.p, j, nnz * 4, hipMemcpyHostToDevice));
+  if (by) {
+    HIP_TRY(dB.alloc(slots * 8));
+    if (nnz) HIP_TRY(hipMemcpy(dB.p, by, nnz * 8, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(dTrP.alloc(np1 * 4));
+  HIP_TRY(dTeP.alloc(np1 * 4));
+  if (write) {
+    // (the host form sizes the device outputs itself: either side holds at most every entry; the caller's capacities are
+    // checked against the counts below)
+    HIP_TRY(dTrJ.alloc(slots * 4));
+    HIP_TRY(dTeJ.alloc(slots * 4));
+    if (v) {
+      HIP_TRY(dV.alloc(slots * (size_t)value_bytes));
+      if (nnz) HIP_TRY(hipMemcpy(dV.p, v, nnz * (size_t)value_bytes, hipMemcpyHostToDevice));
+      HIP_TRY(dTrV.alloc(slots * (size_t)value_bytes));
+      HIP_TRY(dTeV.alloc(slots * (size_t)value_bytes));
+    }
+  }
+  // first the counts (NULL j outputs), so that the caller's capacities are judged before anything of theirs is written
+  rc = rsparse_hip_split_rows_device(seed, row0, n_rows, mode, test_threshold, leave_out, min_train, dP.as<int32_t>(), dJ.as<int32_t>(),
+                                     nullptr, 0, by ? dB.as<double>() : nullptr, dTrP.as<int32_t>(), nullptr, nullptr,
+                                     dTeP.as<int32_t>(), nullptr, nullptr, 0, 0, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(train_p, dTrP.p, np1 * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(test_p, dTeP.p, np1 * 4, hipMemcpyDeviceToHost));
+  if (!write) return RSPARSE_HIP_OK;
+  const int64_t n_tr = train_p[n_rows], n_te = test_p[n_rows];
+  if (n_tr > train_capacity || n_te > test_capacity)
+    return fail(RSPARSE_HIP_ERR_INVALID, "the capacities are " + std::to_string(train_capacity) + " / " + std::to_string(test_capacity) +
+                                             ", the split needs " + std::to_string(n_tr) + " / " + std::to_string(n_te));
+  if (nnz == 0) return RSPARSE_HIP_OK;
+  rc = rsparse_hip_split_rows_device(seed, row0, n_rows, mode, test_threshold, leave_out, min_train, dP.as<int32_t>(), dJ.as<int32_t>(),
+                                     v ? dV.p : nullptr, value_bytes, by ? dB.as<double>() : nullptr, dTrP.as<int32_t>(),
+                                     dTrJ.as<int32_t>(), v ? dTrV.p : nullptr, dTeP.as<int32_t>(), dTeJ.as<int32_t>(),
+                                     v ? dTeV.p : nullptr, n_tr, n_te, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if (n_tr) HIP_TRY(hipMemcpy(train_j, dTrJ.p, (size_t)n_tr * 4, hipMemcpyDeviceToHost));
+  if (n_te) HIP_TRY(hipMemcpy(test_j, dTeJ.p, (size_t)n_te * 4, hipMemcpyDeviceToHost));
+  if (v) {
+    if (n_tr) HIP_TRY(hipMemcpy(train_v, dTrV.p, (size_t)n_tr * (size_t)value_bytes, hipMemcpyDeviceToHost));
+    if (n_te) HIP_TRY(hipMemcpy(test_v, dTeV.p, (size_t)n_te * (size_t)value_bytes, hipMemcpyDeviceToHost));
+  }
+  return RSPARSE_HIP_OK;
+}
+
 int rsparse_hip_take_numeric_failures(int64_t* unresolved_out, int64_t* fallback_out) {
   if (!unresolved_out) return fail(RSPARSE_HIP_ERR_INVALID, "unresolved_out is NULL");
   // counts a stateless call found on the device when it started and set aside (see StaleFailures): still the resident layer's

@@ -407,6 +407,28 @@ hipError_t launch_sample_row_pointers(int n_rows, int n_item, int n, const int32
 hipError_t launch_sample_negatives(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* seen_p,
                                    const int32_t* seen_j, const int32_t* keep_p, const int32_t* keep_j, const int32_t* out_p,
                                    int32_t* out_j, hipStream_t s);
+// the scan behind out_p, for other row-pointer arrays too (wrmf_split.hip): out_p[row + 1] holds the row's length and bsum[b] the
+// sum of the lengths of rows [256 b, 256 b + 256); boff: (n_rows + 255) / 256 words of scratch; *total = the 64-bit out_p[n_rows]
+hipError_t launch_row_pointer_scan(int n_rows, const long long* bsum, long long* boff, long long* total, int32_t* out_p, hipStream_t s);
+
+// train / test split (wrmf_split.hip): the stream is defined in rsparse_wrmf_hip.h.  mode 0 = proportion (threshold <= 2^32, no
+// `by`), 1 = leave-out (leave_out >= 1, min_train >= 0; by: one double per stored entry, or null = random keys).
+// launch_split_count writes both row-pointer arrays (n_rows + 1 each) and keeps the rows' thresholds in ws (split_ws_bytes(n_rows)
+// bytes, which launch_split_write must be given unchanged); *d_status points into it, for the caller to read back before it
+// writes: the two 64-bit totals, flag non-zero = row pointers that are negative or decrease.  launch_split_write copies every
+// entry's index and value (value_bytes 0, 4 or 8: opaque words) to its place.  n_rows >= 1, row0 + n_rows <= 2^32.
+struct SplitStatus {
+  long long total_train, total_test;
+  int flag, pad;
+};
+size_t split_ws_bytes(int n_rows);
+hipError_t launch_split_count(uint64_t seed, int64_t row0, int n_rows, int mode, uint64_t threshold, int leave_out, int min_train,
+                              const int32_t* p, const double* by, int32_t* train_p, int32_t* test_p, void* ws, SplitStatus** d_status,
+                              hipStream_t s);
+hipError_t launch_split_write(uint64_t seed, int64_t row0, int n_rows, int mode, uint64_t threshold, int leave_out, int min_train,
+                              const int32_t* p, const int32_t* j, const void* v, int value_bytes, const double* by,
+                              const int32_t* train_p, int32_t* train_j, void* train_v, const int32_t* test_p, int32_t* test_j,
+                              void* test_v, void* ws, hipStream_t s);
 
 // item-to-item cosine similarity (wrmf_similar.hip): the operands of the top-k path above.
 // launch_normalize_items: V (fp32, or fp64 when f64) n_items x ld row-major, columns [c0, c0 + r), 1 <= r <= 256 ->

@@ -282,6 +282,15 @@ size_t sample_negatives_ws_bytes(int n_rows) {
   return 2 * nb * 8 + sizeof(SampleStatus);
 }
 
+hipError_t launch_row_pointer_scan(int n_rows, const long long* bsum, long long* boff, long long* total, int32_t* out_p, hipStream_t s) {
+  const int nb = (n_rows + 255) / 256;
+  hipLaunchKernelGGL(sample_scan_kernel, dim3(1), dim3(256), 0, s, bsum, nb, boff, total);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(sample_offsets_kernel, dim3((unsigned)nb), dim3(256), 0, s, n_rows, boff, out_p);
+  return hipGetLastError();
+}
+
 hipError_t launch_sample_row_pointers(int n_rows, int n_item, int n, const int32_t* seen_p, const int32_t* keep_p, int32_t* out_p,
                                       void* ws, SampleStatus** d_status, hipStream_t s) {
   const int nb = (n_rows + 255) / 256;
@@ -295,10 +304,7 @@ hipError_t launch_sample_row_pointers(int n_rows, int n_item, int n, const int32
   if ((err = hipMemsetAsync(st, 0, sizeof(SampleStatus), s)) != hipSuccess) return err;
   hipLaunchKernelGGL(sample_len_kernel, dim3((unsigned)nb), dim3(256), 0, s, seen_p, keep_p, n_rows, n_item, n, out_p, bsum, flag);
   if ((err = hipGetLastError()) != hipSuccess) return err;
-  hipLaunchKernelGGL(sample_scan_kernel, dim3(1), dim3(256), 0, s, bsum, nb, boff, total);
-  if ((err = hipGetLastError()) != hipSuccess) return err;
-  hipLaunchKernelGGL(sample_offsets_kernel, dim3((unsigned)nb), dim3(256), 0, s, n_rows, boff, out_p);
-  return hipGetLastError();
+  return launch_row_pointer_scan(n_rows, bsum, boff, total, out_p, s);
 }
 
 template <int BS>

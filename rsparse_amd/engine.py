@@ -467,6 +467,36 @@ class HipBackend:
             out_p.data_ptr(), out_j.data_ptr(), cap, self._stream()))
         return out_p, out_j[:int(out_p[-1])]
 
+    def split_rows(self, seed, row0, p, j, v=None, test_threshold=None, leave_out=None, min_train=1, by=None):
+        """the train / test split of the rows of a canonical CSR, made on the device (wrmf_split.hip; rsparse_amd/rng.py split_flags
+        is the definition): p, j int32 on the device (p may be a slice of a larger pattern's row pointers), v None or a tensor of
+        4- or 8-byte elements that is copied without being interpreted, `by` None or float64, one per stored entry.  Exactly one
+        of test_threshold (proportion mode, floor(p 2^32)) and leave_out (with min_train, by) is given; the global row index of
+        row u is row0 + u.  -> (train_p, train_j, train_v, test_p, test_j, test_v): canonical CSR from 0 on the device, j / v
+        sliced to their true lengths (v None without values)."""
+        assert p.dtype == torch.int32 and j.dtype == torch.int32 and (test_threshold is None) != (leave_out is None)
+        assert by is None or by.dtype == torch.float64
+        n_rows, dev = int(p.numel()) - 1, p.device
+        train_p = torch.zeros(max(n_rows, 0) + 1, dtype=torch.int32, device=dev)
+        test_p = torch.zeros(max(n_rows, 0) + 1, dtype=torch.int32, device=dev)
+        vb = 0 if v is None else int(v.element_size())
+        nnz = max(int(p[-1]) - int(p[0]), 0) if n_rows > 0 else 0
+        cap_test = nnz if leave_out is None else min(nnz, n_rows * max(int(leave_out), 0))
+        outs = []
+        for cap in (nnz, cap_test):
+            outs.append(torch.empty(max(cap, 1), dtype=torch.int32, device=dev))
+            outs.append(None if v is None else torch.empty(max(cap, 1), dtype=v.dtype, device=dev))
+        train_j, train_v, test_j, test_v = outs
+        if n_rows > 0 and nnz > 0:   # (rows without a stored entry: both row-pointer arrays are the zeros they already hold)
+            mode = 0 if leave_out is None else 1
+            _lib.check(self.lib.rsparse_hip_split_rows_device(
+                int(seed), int(row0), n_rows, mode, int(test_threshold or 0), int(leave_out or 0), int(min_train), p.data_ptr(),
+                j.data_ptr(), None if v is None else v.data_ptr(), vb, None if by is None else by.data_ptr(),
+                train_p.data_ptr(), train_j.data_ptr(), None if v is None else train_v.data_ptr(), test_p.data_ptr(), test_j.data_ptr(),
+                None if v is None else test_v.data_ptr(), nnz, cap_test, self._stream()))
+        n_tr, n_te = int(train_p[-1]), int(test_p[-1])
+        return (train_p, train_j[:n_tr], None if v is None else train_v[:n_tr], test_p, test_j[:n_te], None if v is None else test_v[:n_te])
+
     def ranking_metrics(self, res, p, j, x, want_ap=True, want_ndcg=True):
         """ap_k / ndcg_k (R/metrics.R:31-127) of the lists `res` (n x k int32 on the device, 1-based with NA_integer_, as
         top_product returns them) against `actual` as CSR slots on the device (p, j int32 with j sorted within rows; x float64,

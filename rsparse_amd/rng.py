@@ -30,12 +30,29 @@ into the output (a subset of seen), M = n_item - |seen| admissible items numbere
 
 The negatives depend on (seed, g, seen, n_item, n) alone: not on the rows asked for together, the device, or the order in which
 the draws are evaluated ("the first d distinct values" is a property of the sequence).
+
+`split_flags` / `split_rows` are the specification of the fourth and fifth stream: the train / test split of a canonical CSR
+(columns ascending and unique per row; stored zeros count as entries), which rsparse_amd/csrc/wrmf_split.hip draws on the device
+bit for bit.  Row u has the global index g = row0 + u and L entries; an entry is named by its position t = 0 .. L - 1 in the row:
+
+    proportion   Philox4x32-10, key (lo32(seed), hi32(seed)), counter (t >> 2, g, 3, 0) -> o0..o3; the entry takes word o[t & 3]
+                 and is TEST iff word < T (in 64 bits), T = floor(p 2^32) an integer in [0, 2^32]: T = 0 nothing, 2^32 everything
+    leave-out    exactly h = min(n, max(L - min_train, 0)) entries of the row are test: every entry has a 64-bit key w, and the
+                 test entries are the first h of the total order "a before b iff w_a > w_b, or w_a = w_b and t_a < t_b"
+      random     counter (t >> 1, g, 4, 0); w = o1 2^32 + o0 for even t, o3 2^32 + o2 for odd t (the negatives' word pairing)
+      by         one float64 per stored entry (a timestamp); u = its bits, w = ~u if the sign bit is set, else u | 2^63: the
+                 order-preserving map, so the h LARGEST values are held out and ties go to the lower position; -0.0 orders
+                 just below +0.0; NaN is refused; no random word is used
+
+A flag depends on (seed, g, t, the mode's parameters) and, in leave-out mode, on the row's L or `by` values: not on the rows split
+together, the batch, the rank count or the device.  row0 + n_rows <= 2^32, L < 2^31.
 """
 import numpy as np
 
 PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
 PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
 STREAM_USERS, STREAM_ITEMS, STREAM_NEGATIVES = 0, 1, 2
+STREAM_SPLIT, STREAM_LEAVE_OUT = 3, 4
 MAX_NEGATIVES = 8192   # RSPARSE_HIP_MAX_NEGATIVES
 _MASK = np.uint64(0xFFFFFFFF)
 _S32 = np.uint64(32)
@@ -168,3 +185,89 @@ def sample_negatives(seed, row0, seen_p, seen_j, keep_p, keep_j, n_item, n):
         raise ValueError("sample_negatives: the output does not fit int32 row pointers")
     out_j = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
     return out_p.astype(np.int32), out_j.astype(np.int32)
+
+
+def by_keys(by):
+    """the order-preserving 64-bit keys of float64 values: larger value <=> larger key, -0.0 just below +0.0 (NaN refused)"""
+    by = np.ascontiguousarray(by, dtype=np.float64)
+    if np.isnan(by).any():
+        raise ValueError("split: NaN in `by`")
+    u = by.view(np.uint64)
+    return np.where((u >> np.uint64(63)).astype(bool), ~u, u | np.uint64(1 << 63))
+
+
+def _split_positions(indptr):
+    """(row of every entry, its position t in the row) of the row pointers indptr (which may start anywhere)"""
+    lens = np.diff(indptr)
+    row = np.repeat(np.arange(lens.size, dtype=np.int64), lens)
+    t = np.arange(int(indptr[-1] - indptr[0]), dtype=np.int64) - (indptr[:-1] - indptr[0])[row]
+    return lens, row, t
+
+
+def split_flags(seed, row0, indptr, test_threshold=None, leave_out=None, min_train=1, by=None):
+    """The test flag of every stored entry of the rows with row pointers `indptr` (n_rows + 1 absolute positions; they may be a
+    slice of a larger pattern's), global row indices row0, row0 + 1, ...: a bool array of indptr[-1] - indptr[0] entries.
+    Exactly one of test_threshold (proportion mode: T = floor(p 2^32)) and leave_out (n >= 1, with min_train >= 0 and, for the
+    temporal split, `by`: one float64 per entry of the rows, i.e. the slice [indptr[0], indptr[-1]) of the pattern's) is given."""
+    seed, row0 = int(seed), int(row0)
+    ip = np.asarray(indptr, dtype=np.int64)
+    if ip.ndim != 1 or ip.size < 1 or not 0 <= seed < 2 ** 64 or row0 < 0 or (test_threshold is None) == (leave_out is None):
+        raise ValueError("split_flags: bad arguments")
+    n_rows = ip.size - 1
+    if row0 + n_rows > 2 ** 32:
+        raise ValueError("split_flags: the global row index does not fit 32 bits")
+    if ip[0] < 0 or (np.diff(ip) < 0).any() or ip[-1] >= 2 ** 31:
+        raise ValueError("split_flags: row pointers that are negative, decrease or pass int32")
+    lens, row, t = _split_positions(ip)
+    g = (row + row0).astype(np.uint64)
+    t64 = t.astype(np.uint64)
+    key = np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64)
+    if test_threshold is not None:
+        T = int(test_threshold)
+        if not 0 <= T <= 2 ** 32 or by is not None:
+            raise ValueError("split_flags: test_threshold outside [0, 2^32], or `by` in proportion mode")
+        counter = np.stack([t64 >> np.uint64(2), g, np.full_like(g, STREAM_SPLIT), np.zeros_like(g)], axis=-1)
+        o = philox4x32_10(counter, key)
+        word = o[np.arange(t.size), (t & 3)].astype(np.uint64)
+        return word < np.uint64(T)
+    n, min_train = int(leave_out), int(min_train)
+    if n < 1 or min_train < 0:
+        raise ValueError("split_flags: leave_out < 1 or min_train < 0")
+    if by is not None:
+        by = np.asarray(by)
+        if by.shape != (t.size,):
+            raise ValueError("split_flags: `by` needs one value per entry")
+        w = by_keys(by)
+    else:
+        counter = np.stack([t64 >> np.uint64(1), g, np.full_like(g, STREAM_LEAVE_OUT), np.zeros_like(g)], axis=-1)
+        o = philox4x32_10(counter, key).astype(np.uint64)
+        odd = (t & 1).astype(bool)
+        w = (np.where(odd, o[:, 3], o[:, 1]) << _S32) | np.where(odd, o[:, 2], o[:, 0])
+    h = np.minimum(n, np.maximum(lens - min_train, 0))
+    # the total order within every row: key descending, position ascending (entries are stored by row, then position)
+    order = np.lexsort((t, ~w, row))
+    rank = np.empty(t.size, dtype=np.int64)
+    rank[order] = t                       # the k-th entry of a row in that order sits at the row's k-th slot
+    return rank < h[row]
+
+
+def split_rows(seed, row0, indptr, indices, test_threshold=None, leave_out=None, min_train=1, by=None):
+    """`split_flags` applied: -> (train_p, train_j, train_pos, test_p, test_j, test_pos).  `indices` is the WHOLE pattern's index
+    array (indptr holds absolute positions), `by` one value per entry of it or None; *_pos are the absolute source positions of
+    the entries, so that values are gathered without being interpreted.  Both outputs are canonical CSR with row pointers from
+    0, int32; entries keep their order."""
+    ip = np.asarray(indptr, dtype=np.int64)
+    idx = np.asarray(indices)
+    if by is not None:
+        by = np.asarray(by)
+        if by.shape != idx.shape:
+            raise ValueError("split_rows: `by` needs one value per stored entry")
+        by = by[int(ip[0]):int(ip[-1])]
+    flags = split_flags(seed, row0, ip, test_threshold, leave_out, min_train, by)
+    lens, row, _ = _split_positions(ip)
+    pos = np.arange(int(ip[0]), int(ip[-1]), dtype=np.int64)
+    out = []
+    for f in (~flags, flags):
+        cnt = np.bincount(row[f], minlength=lens.size)
+        out += [np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32), idx[pos[f]].astype(np.int32), pos[f]]
+    return tuple(out)

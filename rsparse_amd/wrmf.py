@@ -916,6 +916,39 @@ class WRMF:
         idx = cols.cpu().numpy()
         return sp.csr_matrix((np.ones(idx.size), idx, indptr), shape=(n_new, n_item))
 
+    split_batch = None   # stored entries per device call of train_test_split (None: rsparse_amd.split.SPLIT_BATCH)
+
+    def train_test_split(self, x, test_proportion=0.5, leave_out=None, by=None, min_train=1, seed=None):
+        """`rsparse_amd.train_test_split` on the model's backend: (train, test), two canonical scipy CSR matrices of x's shape
+        and dtype with train + test == x bit for bit.  test_proportion=p: every stored entry is test independently with
+        probability p (the reference's train_test_split); leave_out=n: exactly min(n, max(L - min_train, 0)) entries of a row
+        are test, chosen at random or, with by= (a sparse matrix with x's pattern, e.g. timestamps), the largest `by` values.
+        The split depends on (seed, row, position in the row) alone -- not on the model, the number of ranks or the device.
+        `seed=None` takes one 63-bit seed from the model's generator; under torch.distributed every rank uses rank 0's seed,
+        splits its own block of rows and the blocks are shared.  Needs no fitted factors."""
+        from . import split as _split
+        m, by_v, kw = _split.split_arguments(x, test_proportion, leave_out, by, min_train)
+        seed = self._negatives_seed(seed)
+        be = self._backend()
+        a, b, ws = self._my_rows(m)
+        vals, gather = _split.opaque_values(m)
+        parts = list(_split.split_batches(be, m, vals, by_v, a, b, seed, kw, self.split_batch))
+        if ws > 1:
+            n_rows, tv = m.shape[0], (torch.int32 if vals.dtype == np.int32 else torch.int64)
+            shared = []
+            for o in (0, 3):
+                lens = np.concatenate([np.zeros(0, np.int64)] + [np.diff(part[o].astype(np.int64)) for part in parts])
+                lens = self._share_rows(be.to_device(lens, torch.int64), self._row_bounds, n_rows).cpu().numpy()
+                ip = np.concatenate([[0], np.cumsum(lens)])
+                ebounds = [(int(ip[r0]), int(ip[r1])) for r0, r1 in self._row_bounds]
+                both = []
+                for k, dt, ndt in ((1, torch.int32, np.int32), (2, tv, vals.dtype)):
+                    mine = np.concatenate([np.zeros(0, ndt)] + [part[o + k] for part in parts])
+                    both.append(self._share_rows(be.to_device(mine, dt), ebounds, int(ip[-1])).cpu().numpy())
+                shared += [ip.astype(np.int64), both[0], both[1]]
+            parts = [tuple(shared)]
+        return _split.assemble(m, gather, parts)
+
     def _score_device(self, x, pattern, actual, want_scores):
         """the device part of `score` / `evaluate_values`: the embeddings of the rows of x (as `predict` gets them), then this
         rank's block of rows of `pattern` (canonical CSR, n x n_item) scored against the item factors.  -> (scores, sse, sae)
