@@ -465,6 +465,47 @@ int rsparse_hip_ranking_metrics_device(const int32_t* d_predictions, int n_users
                                        double* d_ndcg_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * hit-based metrics of the same lists at several cutoffs in one pass: precision, recall, hit rate, reciprocal rank
+ * and catalogue coverage.  The reference package has none of them: `hit_metrics_reference` of rsparse_amd/metrics.py
+ * is the definition.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* cutoffs: n_cutoffs <= RSPARSE_HIP_MAX_CUTOFFS strictly ascending integers c_1 < ... < c_T in 1 .. k, always on the HOST (they
+ * travel as a kernel argument).  Per user u with n_u stored entries in its row of actual (p / j as above; the values play no
+ * part, a stored zero is a relevant item), hit_i = the prediction at the 1-based position i is a stored column of the row --
+ * looked up on its own, as for ap: NA, indices below 1 or outside the row are misses, a repeated index hits every time --:
+ *   hits[u, t]      = sum over i <= c_t of hit_i                    first[u] = the smallest i <= c_T with hit_i, 0 without one
+ *   precision[u, t] = hits / c_t  (c_t also where the list is shorter)            recall[u, t] = hits / n_u
+ *   hit[u, t]       = 1 where hits > 0, else 0                      mrr[u, t] = 1 / first where 0 < first <= c_t, else 0
+ * A user with n_u = 0 gets NaN in the four doubles (it is not evaluated, as in ap) and hits = first = 0.  Over ALL users, those
+ * with n_u = 0 included: first_seen[item] = min(first_seen[item], the smallest position i <= c_T at which a list names the
+ * item); only items in 1 .. n_items count.  The catalogue coverage at c_t is #{items with first_seen <= c_t} / n_items, left to
+ * the caller.  Positions beyond c_T are never read.  Every double is one IEEE division of two integers and the only atomics
+ * are integer minima: a repeated call returns the same bits, and they are the bits of the numpy statement.
+ *
+ * device form: d_predictions n_users x k ROW-major (k is the row stride), d_hits and the four doubles n_users x n_cutoffs
+ * row-major, d_first n_users, d_first_seen n_items; every output nullable, not all.  d_first_seen is min-updated and
+ * caller-initialised (INT32_MAX = never listed): calling the entry on successive row batches with the same d_first_seen
+ * accumulates the coverage of all of them.  Enqueued on `stream`, no synchronisation, no workspace.  All before a device is
+ * touched: NULL where a pointer is needed, every output NULL, n_users < 0, k < 1, n_cutoffs < 1, cutoffs not strictly ascending,
+ * below 1 or above k, d_first_seen with n_items < 1 -> ERR_INVALID; n_cutoffs > RSPARSE_HIP_MAX_CUTOFFS or
+ * k > RSPARSE_HIP_MAX_TOPK_LARGE -> ERR_UNSUPPORTED; n_users == 0 -> OK.  A valid p and j strictly ascending within every row
+ * are preconditions, as for rsparse_hip_ranking_metrics_device. */
+#define RSPARSE_HIP_MAX_CUTOFFS 16
+int rsparse_hip_hit_metrics_device(const int32_t* d_predictions, int n_users, int k, const int32_t* d_actual_p,
+                                   const int32_t* d_actual_j, const int32_t* cutoffs, int n_cutoffs, int32_t* d_hits,
+                                   int32_t* d_first, double* d_precision, double* d_recall, double* d_hit, double* d_mrr,
+                                   int32_t* d_first_seen, int n_items, void* stream);
+
+/* host form: predictions as rsparse_hip_ranking_metrics takes them (n_users x k column-major, 1-based with NA_integer_), the
+ * dgRMatrix slots p / j, and the same outputs as n_users x n_cutoffs COLUMN-major matrices (first: n_users).  first_seen
+ * (n_items) is initialised by the call itself (INT32_MAX) and returned min-updated.  Also ERR_INVALID: p[0] != 0, a decreasing
+ * p, j not strictly ascending within a row. */
+int rsparse_hip_hit_metrics(const int32_t* predictions, int n_users, int k, const int32_t* actual_p, const int32_t* actual_j,
+                            const int32_t* cutoffs, int n_cutoffs, int32_t* hits, int32_t* first, double* precision,
+                            double* recall, double* hit, double* mrr, int32_t* first_seen, int n_items);
+
+/* ------------------------------------------------------------------------------------------------
  * full-ranking metrics: where the held-out items stand among ALL items -- the expected percentile rank of
  * Hu, Koren and Volinsky (the measure of the method's own paper), AUC and MRR off the same per-item ranks
  * ---------------------------------------------------------------------------------------------- */

@@ -2,7 +2,8 @@
 
 Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit,explicit}.hpp):
   rsparse_amd.WRMF            host-side mirror of the R6 class
-  rsparse_amd.metrics         ap_k() / ndcg_k(), the reference's ranking metrics, on the device
+  rsparse_amd.metrics         ap_k() / ndcg_k(), the reference's ranking metrics, and precision / recall / hit rate / MRR /
+                              coverage at several cutoffs, on the device
   rsparse_amd.train_test_split  the reference's train_test_split (and leave-n-out), drawn on the device
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
   rsparse_amd.engine          device-resident, row-sharded driver (one process per GPU)

@@ -13,7 +13,8 @@ LIB_PATH = Path(os.environ.get("RSPARSE_HIP_LIB", Path(__file__).resolve().paren
 OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_RUNTIME, ERR_NUMERIC = 0, 1, 2, 3, 4
 SOLVER_CHOLESKY, SOLVER_CG, SOLVER_NNLS = 0, 1, 2
 MAX_NEGATIVES = 8192   # RSPARSE_HIP_MAX_NEGATIVES: negatives per row of rsparse_hip_sample_negatives*
-RANKS_BATCH = 1024   # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that the rank count takes at a time
+MAX_CUTOFFS = 16   # RSPARSE_HIP_MAX_CUTOFFS: cutoffs of one rsparse_hip_hit_metrics* call
+RANKS_BATCH = 1024  # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that the rank count takes at a time
 
 _c_int, _c_uint, _c_dbl, _c_i64, _c_u64 = ctypes.c_int, ctypes.c_uint, ctypes.c_double, ctypes.c_int64, ctypes.c_uint64
 _vp = ctypes.c_void_p
@@ -76,6 +77,9 @@ SIGNATURES = {
     "rsparse_hip_similar_items": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp]),
     "rsparse_hip_ranking_metrics": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
     "rsparse_hip_ranking_metrics_device": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_hit_metrics_device": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int,
+                                                _vp]),
+    "rsparse_hip_hit_metrics": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int]),
     "rsparse_hip_held_out_ranks_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _c_int, _vp, _vp,
                                                    _vp, _vp]),
     "rsparse_hip_rank_summary_device": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1403,6 +1403,102 @@ int rsparse_hip_ranking_metrics(const int32_t* pred, int n_users, int k, const i
 }
 
 namespace {
+// the arguments both forms of rsparse_hip_hit_metrics check before anything else
+int hit_metrics_args(const int32_t* pred, int n_users, int k, const int32_t* p, const int32_t* j, const int32_t* cutoffs,
+                     int n_cutoffs, bool any_output, const int32_t* first_seen, int n_items) {
+  if (!any_output) return fail(RSPARSE_HIP_ERR_INVALID, "every output is NULL");
+  if (!pred || !p || !j || !cutoffs) return fail(RSPARSE_HIP_ERR_INVALID, "predictions, actual (p, j) or cutoffs is NULL");
+  if (n_users < 0 || k < 1 || n_cutoffs < 1)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0, k < 1 or n_cutoffs < 1)");
+  if (first_seen && n_items < 1) return fail(RSPARSE_HIP_ERR_INVALID, "first_seen needs n_items >= 1");
+  if (n_cutoffs > RSPARSE_HIP_MAX_CUTOFFS)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 16 cutoffs (RSPARSE_HIP_MAX_CUTOFFS) are not on the device path");
+  if (k > RSPARSE_HIP_MAX_TOPK_LARGE)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
+  for (int t = 0; t < n_cutoffs; t++)
+    if (cutoffs[t] < 1 || cutoffs[t] > k || (t > 0 && cutoffs[t] <= cutoffs[t - 1]))
+      return fail(RSPARSE_HIP_ERR_INVALID, "cutoffs must be strictly ascending within 1 .. k");
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+
+int rsparse_hip_hit_metrics_device(const int32_t* d_pred, int n_users, int k, const int32_t* d_p, const int32_t* d_j,
+                                   const int32_t* cutoffs, int n_cutoffs, int32_t* d_hits, int32_t* d_first, double* d_precision,
+                                   double* d_recall, double* d_hit, double* d_mrr, int32_t* d_first_seen, int n_items,
+                                   void* stream) {
+  const bool any = d_hits || d_first || d_precision || d_recall || d_hit || d_mrr || d_first_seen;
+  int rc = hit_metrics_args(d_pred, n_users, k, d_p, d_j, cutoffs, n_cutoffs, any, d_first_seen, n_items);
+  if (rc || n_users == 0) return rc;
+  if ((rc = g_ws.ensure_device())) return rc;
+  hipError_t e = launch_hit_metrics(d_pred, n_users, k, d_p, d_j, cutoffs, n_cutoffs, d_hits, d_first, d_precision, d_recall, d_hit,
+                                    d_mrr, d_first_seen, n_items, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_hit_metrics");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_hit_metrics(const int32_t* pred, int n_users, int k, const int32_t* p, const int32_t* j, const int32_t* cutoffs,
+                            int n_cutoffs, int32_t* hits, int32_t* first, double* precision, double* recall, double* hit,
+                            double* mrr, int32_t* first_seen, int n_items) {
+  const bool any = hits || first || precision || recall || hit || mrr || first_seen;
+  int rc = hit_metrics_args(pred, n_users, k, p, j, cutoffs, n_cutoffs, any, first_seen, n_items);
+  if (rc) return rc;
+  // the dgRMatrix slots: p from 0, non-decreasing; j strictly ascending within a row (what the kernel's binary search needs)
+  if (p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "actual_p[0] != 0");
+  for (int u = 0; u < n_users; u++) {
+    if (p[u + 1] < p[u]) return fail(RSPARSE_HIP_ERR_INVALID, "actual_p decreases");
+    for (int32_t e = p[u] + 1; e < p[u + 1]; e++)
+      if (j[e] <= j[e - 1]) return fail(RSPARSE_HIP_ERR_INVALID, "actual_j is not strictly ascending within a row");
+  }
+  if (first_seen) std::fill(first_seen, first_seen + n_items, INT32_MAX);
+  if (n_users == 0) return RSPARSE_HIP_OK;
+  const int T = n_cutoffs;
+  const size_t nk = (size_t)n_users * k, nt = (size_t)n_users * T, nnz = (size_t)p[n_users];
+  std::vector<int32_t> rows(nk);   // column-major (R's integer matrix) -> the row-major lists of the device form
+  for (int c = 0; c < k; c++)
+    for (int u = 0; u < n_users; u++) rows[(size_t)u * k + c] = pred[(size_t)c * n_users + u];
+  DevBuf dPred, dP, dJ, dHits, dFirst, dSeen, dD[4];
+  double* outs[4] = {precision, recall, hit, mrr};
+  HIP_TRY(dPred.alloc(nk * 4));
+  HIP_TRY(dP.alloc(((size_t)n_users + 1) * 4));
+  HIP_TRY(dJ.alloc(std::max<size_t>(nnz, 1) * 4));
+  if (hits) HIP_TRY(dHits.alloc(nt * 4));
+  if (first) HIP_TRY(dFirst.alloc((size_t)n_users * 4));
+  for (int q = 0; q < 4; q++)
+    if (outs[q]) HIP_TRY(dD[q].alloc(nt * 8));
+  HIP_TRY(hipMemcpy(dPred.p, rows.data(), nk * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dP.p, p, ((size_t)n_users + 1) * 4, hipMemcpyHostToDevice));
+  if (nnz) HIP_TRY(hipMemcpy(dJ.p, j, nnz * 4, hipMemcpyHostToDevice));
+  if (first_seen) {
+    HIP_TRY(dSeen.alloc((size_t)n_items * 4));
+    HIP_TRY(hipMemcpy(dSeen.p, first_seen, (size_t)n_items * 4, hipMemcpyHostToDevice));
+  }
+  rc = rsparse_hip_hit_metrics_device(dPred.as<int32_t>(), n_users, k, dP.as<int32_t>(), dJ.as<int32_t>(), cutoffs, T,
+                                      hits ? dHits.as<int32_t>() : nullptr, first ? dFirst.as<int32_t>() : nullptr,
+                                      outs[0] ? dD[0].as<double>() : nullptr, outs[1] ? dD[1].as<double>() : nullptr,
+                                      outs[2] ? dD[2].as<double>() : nullptr, outs[3] ? dD[3].as<double>() : nullptr,
+                                      first_seen ? dSeen.as<int32_t>() : nullptr, n_items, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  // n x T row-major -> R's column-major matrices
+  if (hits) {
+    std::vector<int32_t> h(nt);
+    HIP_TRY(hipMemcpy(h.data(), dHits.p, nt * 4, hipMemcpyDeviceToHost));
+    for (int u = 0; u < n_users; u++)
+      for (int t = 0; t < T; t++) hits[(size_t)t * n_users + u] = h[(size_t)u * T + t];
+  }
+  if (first) HIP_TRY(hipMemcpy(first, dFirst.p, (size_t)n_users * 4, hipMemcpyDeviceToHost));
+  std::vector<double> d(nt);
+  for (int q = 0; q < 4; q++) {
+    if (!outs[q]) continue;
+    HIP_TRY(hipMemcpy(d.data(), dD[q].p, nt * 8, hipMemcpyDeviceToHost));
+    for (int u = 0; u < n_users; u++)
+      for (int t = 0; t < T; t++) outs[q][(size_t)t * n_users + u] = d[(size_t)u * T + t];
+  }
+  if (first_seen) HIP_TRY(hipMemcpy(first_seen, dSeen.p, (size_t)n_items * 4, hipMemcpyDeviceToHost));
+  return RSPARSE_HIP_OK;
+}
+
+namespace {
 // the arguments both forms of rsparse_hip_held_out_ranks check before anything else
 int held_out_ranks_args(const void* U, const void* V, int n_users, int n_items, int rank, int n_exclude, const void* excl,
                         const void* act_p, const void* act_j, int max_chunk_users) {

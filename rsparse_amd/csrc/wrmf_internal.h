@@ -352,6 +352,15 @@ hipError_t launch_rank_summary(int n_users, const int32_t* act_ptr, const double
 hipError_t launch_ranking_metrics(const int32_t* pred, int n_users, int k, const int32_t* P, const int32_t* J, const double* X,
                                   double* ap_out, double* ndcg_out, int* long_buf, hipStream_t s);
 
+// hit-based metrics of the same lists at n_cutoffs <= kHitMaxCutoffs strictly ascending cutoffs in 1 .. k (wrmf_hits.hip), one
+// launch and no scratch: hits / precision / recall / hit / mrr (n_users x n_cutoffs row-major), first (n_users), each nullable;
+// first_seen (n_items, nullable) is min-updated with the first position at which any list names the item.  cutoffs: HOST (they
+// travel as a kernel argument); k is the row stride of the lists.
+constexpr int kHitMaxCutoffs = 16;   // RSPARSE_HIP_MAX_CUTOFFS
+hipError_t launch_hit_metrics(const int32_t* pred, int n_users, int k, const int32_t* P, const int32_t* J, const int32_t* cutoffs,
+                              int n_cutoffs, int32_t* hits, int32_t* first, double* precision, double* recall, double* hit,
+                              double* mrr, int32_t* first_seen, int n_items, hipStream_t s);
+
 // pointwise predictions at a CSR pattern (wrmf_score.hip), T = float or double, 1 <= r <= 256: scores[t] = add + U[row(t)] .
 // V[J[t]] in double for every stored position t < P[n_rows] (the count stays on the device: a capped grid strides over it); then
 // the squared / absolute error sums per row of given scores against `actual` (sse / sae: either may be null)

@@ -514,6 +514,37 @@ class HipBackend:
             None if ap is None else ap.data_ptr(), None if ndcg is None else ndcg.data_ptr(), self._stream()))
         return ap, ndcg
 
+    def hit_metrics(self, res, p, j, cutoffs, want, first_seen=None):
+        """the hit-based metrics of the lists `res` (as for ranking_metrics) at the strictly ascending `cutoffs` (host ints, at
+        most 16, within 1 .. k) in one launch (wrmf_hits.hip; rsparse_amd.metrics.hit_metrics_reference is the definition):
+        {name: tensor on the device} for the names in `want` -- "hits" (n x T int32), "first" (n int32), "precision", "recall",
+        "hit", "mrr" (n x T float64).  first_seen: int32 of n_item on the device, min-updated in place with the first position
+        at which a list names each item (the caller initialises it, INT32_MAX = never; several calls accumulate)."""
+        known = ("hits", "first", "precision", "recall", "hit", "mrr")
+        want = tuple(want)
+        if any(m not in known for m in want) or (not want and first_seen is None):
+            raise ValueError("hit_metrics: want must name some of %s (or first_seen be given)" % ", ".join(known))
+        assert res.dtype == torch.int32 and p.dtype == torch.int32 and j.dtype == torch.int32
+        assert first_seen is None or (first_seen.dtype == torch.int32 and first_seen.is_contiguous())
+        res = res.contiguous()
+        n, k = res.shape
+        cut = np.ascontiguousarray(np.asarray(list(cutoffs), dtype=np.int32))
+        T = int(cut.size)
+        out = {}
+        for m in want:
+            out[m] = torch.empty(n if m == "first" else (n, T), dtype=torch.int32 if m in ("hits", "first") else torch.float64,
+                                 device=res.device)
+        if n == 0:
+            return out
+        if j.numel() == 0:   # (no stored entry at all: the library still wants a non-NULL slot)
+            j = torch.zeros(1, dtype=torch.int32, device=res.device)
+        ptr = lambda m: out[m].data_ptr() if m in out else None
+        _lib.check(self.lib.rsparse_hip_hit_metrics_device(
+            res.data_ptr(), n, k, p.data_ptr(), j.data_ptr(), cut.ctypes.data_as(ctypes.c_void_p), T, ptr("hits"), ptr("first"),
+            ptr("precision"), ptr("recall"), ptr("hit"), ptr("mrr"), None if first_seen is None else first_seen.data_ptr(),
+            0 if first_seen is None else int(first_seen.numel()), self._stream()))
+        return out
+
     def score_pairs(self, U, V, p, j, add=0.0, actual=None, want_scores=True):
         """the model's values at the stored positions of a CSR pattern (p, j: int32 on the device) whose rows are the rows of U
         (n x rank) and whose columns index V (n_item x rank): score[t] = add + U[row(t)] . V[j[t]], accumulated in double from

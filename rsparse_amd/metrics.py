@@ -12,6 +12,14 @@ own (missing, out-of-range and repeated predictions like `%in%` / `match`), stor
 An empty row gives ap = NaN and ndcg = 0; a row of zero relevances ndcg = NaN.  `WRMF.evaluate` scores the lists of `predict`
 without moving them off the device.
 
+Hit-based metrics, which the reference does not have, at up to 16 cutoffs from ONE pass over the lists (wrmf_hits.hip behind
+`rsparse_hip_hit_metrics`; `WRMF.evaluate(k=(5, 10, 20), metrics=("hit", "recall", ...))` runs it on the lists of `predict`):
+
+    hit_metrics_reference(predictions, actual, cutoffs, n_item)   the DEFINITION, plain numpy: the kernel equals it bit for bit
+    topk_metrics(predictions, actual, cutoffs, metrics)           the same on the device, {name: (n, T) array}
+    precision_k / recall_k / hit_rate_k / mrr_k / coverage_k      one metric; a vector for one cutoff, (n, T) for several
+    summarize(ev)                                                 the means per cutoff of what `WRMF.evaluate` returns
+
 Full-ranking metrics (`WRMF.held_out_ranks` / `WRMF.evaluate_ranks` compute them on the device, wrmf_ranks.hip) have their
 plain-numpy statement here, from a dense score matrix -- the reference the tests hold the kernels to, usable on its own:
 
@@ -87,7 +95,191 @@ def ndcg_k(predictions, actual):
     return ranking_metrics(predictions, actual, ap=False, ndcg=True)[1]
 
 
-# ---- full-ranking metrics: the numpy statement of DESIGN.md 3.15 -------------------------------------------------------------
+# ---- hit-based metrics at several cutoffs: the numpy statement of DESIGN.md 3.21 and the device call -------------------------
+HIT_METRICS = ("precision", "recall", "hit", "mrr")
+MAX_CUTOFFS = _lib.MAX_CUTOFFS
+MAX_TOPK = 8192   # RSPARSE_HIP_MAX_TOPK_LARGE
+NEVER_SEEN = np.iinfo(np.int32).max   # first_seen of an item that no list names
+
+
+def check_cutoffs(cutoffs, k=None):
+    """`cutoffs` as a tuple of ints: strictly ascending, at least 1, at most k (where given) -- anything else is a ValueError;
+    more than MAX_CUTOFFS of them are not on the device path"""
+    cut = [cutoffs] if isinstance(cutoffs, (int, np.integer)) and not isinstance(cutoffs, bool) else list(cutoffs)
+    if not cut or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) for c in cut):
+        raise ValueError("cutoffs must be one or more integers")
+    cut = tuple(int(c) for c in cut)
+    if cut[0] < 1 or any(b <= a for a, b in zip(cut, cut[1:])):
+        raise ValueError("cutoffs must be strictly ascending and at least 1")
+    if k is not None and cut[-1] > k:
+        raise ValueError("a cutoff is larger than the lists are long (k = %d)" % k)
+    if len(cut) > MAX_CUTOFFS:
+        raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "more than %d cutoffs are not on the device path" % MAX_CUTOFFS)
+    return cut
+
+
+def coverage_from_first_seen(first_seen, cutoffs):
+    """#{items with first_seen <= c_t} / n_item for every cutoff: float64 (T,)"""
+    fs = np.asarray(first_seen)
+    return np.array([np.count_nonzero(fs <= c) for c in cutoffs], dtype=np.int64) / np.int64(fs.size)
+
+
+def hit_metrics_reference(predictions, actual, cutoffs, n_item=None):
+    """The DEFINITION of the hit-based metrics, pure numpy, no device.  `predictions` n x k 0-based with -1 where a list is
+    short, `actual` sparse with n rows (made canonical), `cutoffs` strictly ascending 1 <= c_1 < ... < c_T <= k.  Per row u with
+    n_u stored entries, hit_i = the prediction at the 1-based position i is a stored column of the row (each position on its
+    own: negative and out-of-range predictions miss, a repeated index hits every time, a stored zero is relevant):
+        hits[u, t] = sum_{i <= c_t} hit_i (int32)          first[u] = the smallest i <= c_T with hit_i, 0 without one (int32)
+        precision  = hits / c_t       recall = hits / n_u       hit = 1.0 where hits > 0       mrr = 1 / first where 0 < first <= c_t
+    and NaN in the four of a row with n_u = 0.  With `n_item`, over ALL rows: first_seen[item] = the smallest position i <= c_T
+    at which a row lists the item (int32, NEVER_SEEN without one; only items in 0 .. n_item - 1 count) and coverage[t] =
+    #{first_seen <= c_t} / n_item.  Every double is one division of two integers."""
+    p = np.asarray(predictions)
+    if p.ndim != 2:
+        raise ValueError("predictions must be a matrix (n x k)")
+    if not np.issubdtype(p.dtype, np.integer):
+        raise TypeError("predictions must hold integer item indices")
+    p = p.astype(np.int64, copy=False)
+    n, k = p.shape
+    a = canonical_actual(actual, n)
+    cut = np.asarray(check_cutoffs(cutoffs, k), dtype=np.int64)
+    T, c_last = cut.size, int(cut[-1])
+    hits = np.zeros((n, T), dtype=np.int32)
+    first = np.zeros(n, dtype=np.int32)
+    n_u = np.diff(a.indptr).astype(np.int64)
+    for u in range(n):
+        h = np.isin(p[u, :c_last], a.indices[a.indptr[u]:a.indptr[u + 1]])
+        cum = np.concatenate([[0], np.cumsum(h)])
+        hits[u] = cum[cut]
+        if h.any():
+            first[u] = int(np.argmax(h)) + 1
+    empty = n_u == 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        precision = hits.astype(np.float64) / cut.astype(np.float64)[None, :]
+        recall = hits.astype(np.float64) / n_u.astype(np.float64)[:, None]
+        mrr = np.where((first[:, None] > 0) & (first[:, None] <= cut[None, :]), 1.0 / first.astype(np.float64)[:, None], 0.0)
+    hit = (hits > 0).astype(np.float64)
+    for v in (precision, recall, hit, mrr):
+        v[empty] = np.nan
+    out = {"hits": hits, "first": first, "precision": precision, "recall": recall, "hit": hit, "mrr": mrr}
+    if n_item is not None:
+        n_item = int(n_item)
+        if n_item < 1:
+            raise ValueError("n_item must be at least 1")
+        first_seen = np.full(n_item, NEVER_SEEN, dtype=np.int32)
+        head = p[:, :c_last]
+        ok = (head >= 0) & (head < n_item)
+        pos = np.broadcast_to(np.arange(1, c_last + 1, dtype=np.int32), head.shape)
+        np.minimum.at(first_seen, head[ok], pos[ok])
+        out["first_seen"] = first_seen
+        out["coverage"] = coverage_from_first_seen(first_seen, cut)
+    return out
+
+
+def topk_metrics(predictions, actual, cutoffs, metrics=HIT_METRICS, n_item=None):
+    """The hit-based metrics of `hit_metrics_reference`, computed on the device in one pass over the lists (wrmf_hits.hip behind
+    `rsparse_hip_hit_metrics`) and equal to it bit for bit.  `metrics` names some of "hits", "first", "precision", "recall",
+    "hit", "mrr" and "coverage"; -> {name: array}: (n, T) per cutoff (first: n; coverage: (T,), with "first_seen" beside it).
+    Coverage counts the items of 0 .. n_item - 1 (default: the columns of `actual`).  k <= 8192, at most 16 cutoffs."""
+    names = tuple(metrics)
+    known = ("hits", "first") + HIT_METRICS + ("coverage",)
+    if not names or any(m not in known for m in names):
+        raise ValueError("metrics must name some of %s" % ", ".join(repr(m) for m in known))
+    pred = _one_based(predictions)
+    n, k = pred.shape
+    a = canonical_actual(actual, n)
+    if k < 1:
+        raise ValueError("predictions must have at least one column")
+    cut = np.asarray(check_cutoffs(cutoffs, k), dtype=np.int32)
+    T = cut.size
+    if k > MAX_TOPK:
+        raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "k > %d is not on the device path" % MAX_TOPK)
+    out = {m: np.empty((n, T), dtype=np.int32 if m == "hits" else np.float64, order="F") for m in names
+           if m not in ("first", "coverage")}
+    if "first" in names:
+        out["first"] = np.empty(n, dtype=np.int32)
+    first_seen = None
+    if "coverage" in names:
+        n_item = a.shape[1] if n_item is None else int(n_item)
+        if n_item < 1:
+            raise ValueError("n_item must be at least 1")
+        first_seen = np.full(n_item, NEVER_SEEN, dtype=np.int32)
+    if n > 0:
+        pred = np.asfortranarray(pred)   # R's integer matrix: column-major
+        p = np.ascontiguousarray(a.indptr, dtype=np.int32)
+        j = np.ascontiguousarray(a.indices, dtype=np.int32)
+        if j.size == 0:   # (no stored entry at all: the library still wants a non-NULL slot)
+            j = np.zeros(1, np.int32)
+        vp = lambda arr: None if arr is None else arr.ctypes.data_as(ctypes.c_void_p)
+        _lib.check(_lib.load().rsparse_hip_hit_metrics(vp(pred), n, k, vp(p), vp(j), vp(cut), T, vp(out.get("hits")),
+                                                       vp(out.get("first")), vp(out.get("precision")), vp(out.get("recall")),
+                                                       vp(out.get("hit")), vp(out.get("mrr")), vp(first_seen),
+                                                       0 if first_seen is None else first_seen.size))
+    if first_seen is not None:
+        out["first_seen"] = first_seen
+        out["coverage"] = coverage_from_first_seen(first_seen, cut)
+    return {m: (np.ascontiguousarray(v) if v.ndim == 2 else v) for m, v in out.items()}
+
+
+def _one_metric(name, predictions, actual, cutoffs):
+    k = np.asarray(predictions).shape[-1]
+    scalar = cutoffs is None or (isinstance(cutoffs, (int, np.integer)) and not isinstance(cutoffs, bool))
+    v = topk_metrics(predictions, actual, k if cutoffs is None else cutoffs, metrics=(name,))[name]
+    return v[:, 0] if scalar else v
+
+
+def precision_k(predictions, actual, cutoffs=None):
+    """hits among the first c predictions / c, per row: a float64 vector of n for one cutoff (default: k, the width of
+    `predictions`), (n, T) for a sequence; NaN for a row of `actual` without a stored entry"""
+    return _one_metric("precision", predictions, actual, cutoffs)
+
+
+def recall_k(predictions, actual, cutoffs=None):
+    """hits among the first c predictions / stored entries of the row; shapes and NaN as `precision_k`"""
+    return _one_metric("recall", predictions, actual, cutoffs)
+
+
+def hit_rate_k(predictions, actual, cutoffs=None):
+    """1.0 where any of the first c predictions is a stored entry of the row, else 0.0; shapes and NaN as `precision_k`"""
+    return _one_metric("hit", predictions, actual, cutoffs)
+
+
+def mrr_k(predictions, actual, cutoffs=None):
+    """1 / (position of the first hit) where it lies within the first c predictions, else 0.0; shapes and NaN as `precision_k`"""
+    return _one_metric("mrr", predictions, actual, cutoffs)
+
+
+def coverage_k(predictions, n_item, cutoffs=None):
+    """the share of the items 0 .. n_item - 1 that some row names among its first c predictions: a float for one cutoff
+    (default: k), a float64 (T,) vector for a sequence"""
+    p = np.asarray(predictions)
+    if p.ndim != 2:
+        raise ValueError("predictions must be a matrix (n x k)")
+    scalar = cutoffs is None or (isinstance(cutoffs, (int, np.integer)) and not isinstance(cutoffs, bool))
+    nothing = sp.csr_matrix((p.shape[0], int(n_item)), dtype=np.float64)
+    v = topk_metrics(p, nothing, p.shape[1] if cutoffs is None else cutoffs, metrics=("coverage",), n_item=n_item)["coverage"]
+    return float(v[0]) if scalar else v
+
+
+def summarize(ev):
+    """The data-set numbers of a dict returned by `WRMF.evaluate`: for every per-row metric the mean over the rows where it is
+    defined (NaN rows -- users with nothing held out -- left out; NaN when no row is defined), per cutoff: a float for a vector
+    of n, a (T,) vector for an (n, T) array.  "coverage" is a data-set number already and is passed through."""
+    out = {}
+    for name, v in ev.items():
+        if name == "coverage":
+            out[name] = v
+            continue
+        v = np.asarray(v, dtype=np.float64)
+        ok = ~np.isnan(v)
+        cnt = ok.sum(axis=0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m = np.where(ok, v, 0.0).sum(axis=0) / cnt
+        out[name] = float(m) if np.ndim(m) == 0 else m
+    return out
+
+
+# ---- full-ranking metrics: the numpy statement of DESIGN.md 3.15-------------------------------------------------------------
 def percentile_ranks(scores, actual, not_recommend=None, items_exclude=()):
     """Where every stored entry (u, h) of `actual` stands among the ADMISSIBLE items of its row -- the items outside the row of
     `not_recommend` (sparse, n x n_item, or None) and outside `items_exclude` (0-based) --, from the dense `scores` (n x n_item):

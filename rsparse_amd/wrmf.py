@@ -771,13 +771,28 @@ class WRMF:
         `predict` -- the lists are ranked within every row's candidates (sampled-negative evaluation).  `negatives=n` (with
         `seed`) makes those candidates itself: every row's held-out items against n sampled negatives, exactly
         `candidates=self.sample_negatives(x, n, actual, not_recommend, items_exclude, seed)` -- bit for bit -- but sampled on the
-        device in row batches and handed to the ranking without a host copy; it excludes `candidates`."""
-        from .metrics import canonical_actual
+        device in row batches and handed to the ranking without a host copy; it excludes `candidates`.
+
+        `metrics` may also name "precision", "recall", "hit", "mrr" and "coverage" (rsparse_amd.metrics.hit_metrics_reference is
+        their definition), and `k` may be a strictly ascending sequence of up to 16 cutoffs: ONE `predict` pass at max(k), one
+        launch over the lists (wrmf_hits.hip) for every hit-based metric at every cutoff.  A sequence returns (n, T) arrays, one
+        column per cutoff; "coverage" -- the share of the catalogue that some list reaches within the cutoff -- is a float for a
+        scalar `k` and a (T,) vector for a sequence.  A user with nothing held out is NaN in the four per-row metrics.  "ap" /
+        "ndcg" with a sequence score, per cutoff c, the first c places of the top-max(k) list; that equals `evaluate(k=c)`
+        except where scores tie exactly at the c-th place, because the reference heap's tie rule depends on k.
+        `rsparse_amd.metrics.summarize` turns the result into data-set means."""
+        from .metrics import HIT_METRICS, NEVER_SEEN, canonical_actual, check_cutoffs
         metrics = tuple(metrics)
-        if not metrics or any(m not in ("ap", "ndcg") for m in metrics):
-            raise ValueError("metrics must name some of 'ap', 'ndcg'")
+        if not metrics or any(m not in ("ap", "ndcg", "coverage") + HIT_METRICS for m in metrics):
+            raise ValueError("metrics must name some of 'ap', 'ndcg', 'precision', 'recall', 'hit', 'mrr', 'coverage'")
         if negatives is not None and candidates is not None:
             raise ValueError("negatives and candidates exclude each other: the negatives ARE the candidates")
+        scalar_k = not isinstance(k, (tuple, list, np.ndarray, range))
+        hit_names = tuple(m for m in HIT_METRICS if m in metrics)
+        cutoffs = None
+        if not scalar_k or hit_names or "coverage" in metrics:
+            cutoffs = check_cutoffs((int(k),) if scalar_k else k)
+            k = cutoffs[-1]
         x = sp.csr_matrix(x, dtype=np.float64)
         n_new = x.shape[0]
         act = canonical_actual(actual, n_new)
@@ -788,15 +803,54 @@ class WRMF:
         mine = act[a:b]
         be = self._backend()
         want_ap, want_ndcg = "ap" in metrics, "ndcg" in metrics
-        ap, ndcg = be.ranking_metrics(res, be.to_device(mine.indptr, torch.int32), be.to_device(mine.indices, torch.int32),
-                                      be.to_device(mine.data, torch.float64), want_ap, want_ndcg)
+        d_p, d_j = be.to_device(mine.indptr, torch.int32), be.to_device(mine.indices, torch.int32)
         out = {}
-        for name, v in (("ap", ap), ("ndcg", ndcg)):
-            if name in metrics:
-                if ws > 1:
-                    v = self._share_rows(v, self._row_bounds, n_new)
-                out[name] = v.cpu().numpy()
-        return out
+        if want_ap or want_ndcg:
+            d_x = be.to_device(mine.data, torch.float64)
+            if scalar_k:
+                ap, ndcg = be.ranking_metrics(res, d_p, d_j, d_x, want_ap, want_ndcg)
+            else:   # per cutoff the prefix of the lists: a device copy, the same kernel
+                cols = [be.ranking_metrics(res[:, :c].contiguous(), d_p, d_j, d_x, want_ap, want_ndcg) for c in cutoffs]
+                ap = torch.stack([c[0] for c in cols], dim=1) if want_ap else None
+                ndcg = torch.stack([c[1] for c in cols], dim=1) if want_ndcg else None
+            out.update(ap=ap, ndcg=ndcg)
+        if hit_names or "coverage" in metrics:
+            first_seen = None
+            if "coverage" in metrics:
+                first_seen = torch.full((self._V.shape[0],), NEVER_SEEN, dtype=torch.int32, device=res.device)
+            fn = be.hit_metrics if hasattr(be, "hit_metrics") else self._hit_metrics_host
+            got = fn(res, d_p, d_j, cutoffs, hit_names, first_seen)
+            out.update({m: (got[m][:, 0] if scalar_k else got[m]) for m in hit_names})
+        for name in [m for m in out if m not in metrics]:
+            del out[name]
+        for name, v in out.items():
+            if ws > 1:
+                v = self._share_rows(v, self._row_bounds, n_new)
+            out[name] = v.cpu().numpy()
+        if "coverage" in metrics:   # the ranks' first positions joined before they are counted
+            if ws > 1:
+                from .engine import all_reduce_any
+                import torch.distributed as dist
+                all_reduce_any(first_seen, self._group, op=dist.ReduceOp.MIN)
+            cut = torch.tensor(cutoffs, dtype=torch.int32, device=first_seen.device)
+            reached = (first_seen[None, :] <= cut[:, None]).sum(dim=1).cpu().numpy().astype(np.int64)
+            cov = reached / np.int64(first_seen.numel())
+            out["coverage"] = float(cov[0]) if scalar_k else cov
+        return {m: out[m] for m in ("ap", "ndcg") + HIT_METRICS + ("coverage",) if m in metrics}
+
+    @staticmethod
+    def _hit_metrics_host(res, p, j, cutoffs, want, first_seen=None):
+        """`hit_metrics` for a backend without it (the CPU stand-in of the tests): the numpy statement,
+        rsparse_amd.metrics.hit_metrics_reference, on the 1-based lists; first_seen is min-updated in place."""
+        from .metrics import hit_metrics_reference
+        n = res.shape[0]
+        pred0 = res.cpu().numpy().astype(np.int64) - 1          # (NA_integer_ and 0 turn negative: misses)
+        jj = j.cpu().numpy()
+        act = sp.csr_matrix((np.ones(jj.size), jj, p.cpu().numpy()), shape=(n, int(jj.max()) + 1 if jj.size else 1))
+        ref = hit_metrics_reference(pred0, act, cutoffs, None if first_seen is None else int(first_seen.numel()))
+        if first_seen is not None:
+            first_seen.copy_(torch.minimum(first_seen, torch.from_numpy(ref["first_seen"]).to(first_seen.device)))
+        return {m: torch.from_numpy(ref[m]).to(res.device) for m in want}
 
     negatives_batch = None   # candidates per sampling call (None: the backend's top_candidates_batch, 2^28): bounds the memory
 
