@@ -196,7 +196,8 @@ int rsparse_hip_csc_info(const rsparse_hip_csc* m, int64_t info_out[40]);
 
 /* XtX = X X^T + fl(lambda) I on the device (MFMA).  d_sumsq_out (nullable, device double[1])
  * receives sum(X^2) = trace before the ridge -- the `accu(X % X)` term of the loss
- * (inst/include/wrmf_implicit.hpp:299-301) for free.  stream: hipStream_t (NULL = default). */
+ * (inst/include/wrmf_implicit.hpp:299-301) for free.  stream: hipStream_t (NULL = default).  n = 0 gives fl(lambda) I and
+ * a sum of 0; d_X is not read then and may be NULL (an empty slice of a torch tensor has no address). */
 int rsparse_hip_gramian_device(const float* d_X, int rank, int64_t n, double lambda,
                                float* d_XtX_out, double* d_sumsq_out, void* stream);
 

@@ -929,7 +929,7 @@ int rsparse_hip_gramian_device(const float* d_X, int rank, int64_t n, double lam
 
 int rsparse_hip_gramian_absmax_device(const float* d_X, int rank, int64_t n, double lambda, float* d_XtX_out,
                                       double* d_sumsq_out, float* d_absmax_inout, void* stream) {
-  if (!d_X || !d_XtX_out) return fail(RSPARSE_HIP_ERR_INVALID, "X or XtX_out is NULL");
+  if ((!d_X && n != 0) || !d_XtX_out) return fail(RSPARSE_HIP_ERR_INVALID, "X or XtX_out is NULL");   // (n = 0: X is never read)
   if (rank <= 0 || n < 0) return fail(RSPARSE_HIP_ERR_INVALID, "rank must be positive and n non-negative");
   if (rank > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 256 is not on the device path");
   int rc = g_ws.ensure_device();

@@ -299,7 +299,7 @@ int rsparse_hip_csc_f64_destroy(rsparse_hip_csc_f64* m) {
 
 int rsparse_hip_gramian_f64_device(const double* d_X, int rank, int64_t n, double lambda, double* d_XtX_out,
                                    double* d_sumsq_out, void* stream) {
-  if (!d_X || !d_XtX_out) return fail(RSPARSE_HIP_ERR_INVALID, "X or XtX_out is NULL");
+  if ((!d_X && n != 0) || !d_XtX_out) return fail(RSPARSE_HIP_ERR_INVALID, "X or XtX_out is NULL");   // (n = 0: X is never read)
   if (rank <= 0 || n < 0) return fail(RSPARSE_HIP_ERR_INVALID, "rank must be positive and n non-negative");
   if (rank > RSPARSE_HIP_MAX_RANK_F64) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 128 is not on the fp64 device path");
   int rc = g_w64.ensure();
