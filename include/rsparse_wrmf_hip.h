@@ -717,6 +717,47 @@ int rsparse_hip_sample_negatives(uint64_t seed, int64_t row0, int n_rows, int n_
                                  const int32_t* seen_j, const int32_t* keep_p, const int32_t* keep_j, int32_t* out_p, int32_t* out_j,
                                  int64_t out_capacity);
 
+/* Popularity-weighted negatives: the rows of rsparse_hip_sample_negatives* with the negatives drawn in proportion to integer item
+ * weights instead of uniformly (the "pop100" protocol of evaluation toolkits, count^0.75 sampling).  The stream is DEFINED here;
+ * rsparse_amd/rng.py (sample_negatives_weighted) is the definition in numpy.
+ *
+ *   Weights.   w[0 .. n_item) are unsigned 32-bit integers, every one >= 1 (a zero is refused: "never a negative" is the job of
+ *              the seen rows).  C[i] = w[0] + ... + w[i] in 64 bits, the inclusive prefix; W = C[n_item - 1] < 2^63, which always
+ *              holds for n_item < 2^31.
+ *   Draw t.    t = 0, 1, 2, ... of the row with GLOBAL index g = row0 + u: Philox4x32-10 with key (lo32(seed), hi32(seed)) and
+ *              counter (lo32(t >> 1), g, 5, hi32(t >> 1)) -- stream id 5; 0 .. 4 are the factor, negatives and split streams --
+ *              gives o0..o3; v = o1 * 2^32 + o0 for even t, o3 * 2^32 + o2 for odd t (the word pairing of stream 2);
+ *              r = floor(v * W / 2^64), the high 64 bits of the 128-bit product; item = #{i : C[i] <= r}.
+ *   Chosen.    M = n_item - |seen_u|.  n >= M: every admissible item, nothing is drawn.  Otherwise A = the first n DISTINCT
+ *              values, in the order of the draw sequence, among the draws t = 0 .. B(n) - 1 that are NOT in seen_u, with the
+ *              budget B(n) = 64 * n + 4096.  If the budget ends with |A| < n, the row is FILLED with the n - |A| admissible items
+ *              of lowest item number that are not in A, and counts as a filled row.  The budget is part of the definition, so
+ *              that no input can make a row spin: ordinary weights (Zipf counts to the power 0.75 or 1 over 1 M items, the most
+ *              popular items in the seen row) complete within 2 n draws; weights such as [2^31, 1, 1, ...] fill, by design.
+ *   Row.       keep_u and the chosen items, ascending: |keep_u| + min(n, M) entries, exactly as for the uniform sampler.
+ * A row depends on (seed, g, seen_u, keep_u, w, n) only -- not on the rows sampled with it, the batch, the number of devices or
+ * the device.
+ *
+ * rsparse_hip_weights_prefix_device writes C (n_item 64-bit words, device memory) from w (device memory) and waits for the stream
+ * once to learn whether a weight is 0 -> ERR_INVALID.  n_item < 0, a NULL d_w or d_cum -> ERR_INVALID before a device is touched;
+ * n_item == 0 -> OK, nothing is launched.  The prefix serves any number of sampling calls over the same weights.
+ *
+ * rsparse_hip_sample_negatives_weighted_device / rsparse_hip_sample_negatives_weighted are rsparse_hip_sample_negatives_device /
+ * rsparse_hip_sample_negatives with that stream: the same arguments, checks (in the same order), status codes, out_p and
+ * out_capacity rules.  In addition: d_cum (the device form: the prefix above, n_item words; its contents are the caller's
+ * contract) or w (the host form: n_item weights, host memory) is NULL -> ERR_INVALID before a device is touched; the host form
+ * refuses a zero weight -> ERR_INVALID, and checks the lists as the uniform host form does.  d_filled_rows (device memory, one
+ * int32) / filled_rows (host, one int64) may be NULL; otherwise the call zeroes it and then counts the filled rows in it.
+ * 1 <= n <= RSPARSE_HIP_MAX_NEGATIVES; n_rows == 0 -> OK, nothing is launched. */
+int rsparse_hip_weights_prefix_device(const uint32_t* d_w, int n_item, uint64_t* d_cum, void* hip_stream);
+int rsparse_hip_sample_negatives_weighted_device(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* d_seen_p,
+                                                 const int32_t* d_seen_j, const int32_t* d_keep_p, const int32_t* d_keep_j,
+                                                 const uint64_t* d_cum, int32_t* d_out_p, int32_t* d_out_j, int64_t out_capacity,
+                                                 int32_t* d_filled_rows, void* hip_stream);
+int rsparse_hip_sample_negatives_weighted(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* seen_p,
+                                          const int32_t* seen_j, const int32_t* keep_p, const int32_t* keep_j, const uint32_t* w,
+                                          int32_t* out_p, int32_t* out_j, int64_t out_capacity, int64_t* filled_rows);
+
 /* Train / test split of an interaction matrix: every stored entry of the CSR (p, j, v) -- canonical: columns ascending and unique
  * within a row; stored zeros count as entries -- goes to exactly one of two CSR matrices, `train` and `test`, in its order, with
  * its index and its value (copied as an opaque word of value_bytes = 4 or 8 bytes; 0 = the pattern only, v and the value outputs

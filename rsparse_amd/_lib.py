@@ -102,6 +102,9 @@ SIGNATURES = {
                                                      _vp]),
     "rsparse_hip_sample_negatives_device": (_c_int, [_c_u64, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp]),
     "rsparse_hip_sample_negatives": (_c_int, [_c_u64, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64]),
+    "rsparse_hip_weights_prefix_device": (_c_int, [_vp, _c_int, _vp, _vp]),
+    "rsparse_hip_sample_negatives_weighted_device": (_c_int, [_c_u64, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp]),
+    "rsparse_hip_sample_negatives_weighted": (_c_int, [_c_u64, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp]),
     "rsparse_hip_split_rows_device": (_c_int, [_c_u64, _c_i64, _c_int, _c_int, _c_u64, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _vp]),
     "rsparse_hip_split_rows": (_c_int, [_c_u64, _c_i64, _c_int, _c_int, _c_u64, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64]),
     "rsparse_hip_sparse_approximation": (_c_int, [_c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_int, _vp]),

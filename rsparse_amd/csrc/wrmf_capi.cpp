@@ -1684,14 +1684,16 @@ int sample_negatives_args(int64_t row0, int n_rows, int n_item, int n, const voi
     return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "n > 8192 (RSPARSE_HIP_MAX_NEGATIVES) is not on the device path");
   return RSPARSE_HIP_OK;
 }
-}  // namespace
 
-int rsparse_hip_sample_negatives_device(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* d_seen_p,
-                                        const int32_t* d_seen_j, const int32_t* d_keep_p, const int32_t* d_keep_j,
-                                        int32_t* d_out_p, int32_t* d_out_j, int64_t out_capacity, void* stream) {
+// the device form of both samplers: d_cum == nullptr is the uniform stream, otherwise the weighted one under that prefix
+int sample_negatives_device(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* d_seen_p,
+                            const int32_t* d_seen_j, const int32_t* d_keep_p, const int32_t* d_keep_j, const uint64_t* d_cum,
+                            bool weighted, int32_t* d_out_p, int32_t* d_out_j, int64_t out_capacity, int32_t* d_filled_rows,
+                            void* stream) {
   int rc = sample_negatives_args(row0, n_rows, n_item, n, d_seen_p, d_seen_j, d_keep_p, d_keep_j, d_out_p, out_capacity);
   if (rc) return rc;
   if (!d_out_j) return fail(RSPARSE_HIP_ERR_INVALID, "out_j is NULL");
+  if (weighted && !d_cum) return fail(RSPARSE_HIP_ERR_INVALID, "d_cum is NULL");
   if (n_rows == 0) return RSPARSE_HIP_OK;
   hipStream_t s = (hipStream_t)stream;
   if ((rc = g_ws.ensure_device())) return rc;
@@ -1707,16 +1709,30 @@ int rsparse_hip_sample_negatives_device(uint64_t seed, int64_t row0, int n_rows,
   if (st.total > 0x7fffffffll) return fail(RSPARSE_HIP_ERR_INVALID, "the output has more than 2^31 - 1 entries: sample the rows in batches");
   if (st.total > out_capacity)
     return fail(RSPARSE_HIP_ERR_INVALID, "out_capacity is " + std::to_string(out_capacity) + ", the rows need " + std::to_string(st.total));
-  e = launch_sample_negatives(seed, row0, n_rows, n_item, n, d_seen_p, d_seen_j, d_keep_p, d_keep_j, d_out_p, d_out_j, s);
-  if (e != hipSuccess) return hip_fail(e, "launch_sample_negatives");
+  if (!weighted) {
+    e = launch_sample_negatives(seed, row0, n_rows, n_item, n, d_seen_p, d_seen_j, d_keep_p, d_keep_j, d_out_p, d_out_j, s);
+    if (e != hipSuccess) return hip_fail(e, "launch_sample_negatives");
+    return RSPARSE_HIP_OK;
+  }
+  if (d_filled_rows) HIP_TRY(hipMemsetAsync(d_filled_rows, 0, sizeof(int32_t), s));
+  e = launch_sample_negatives_weighted(seed, row0, n_rows, n_item, n, d_seen_p, d_seen_j, d_keep_p, d_keep_j, d_cum, d_out_p, d_out_j,
+                                       d_filled_rows, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_sample_negatives_weighted");
   return RSPARSE_HIP_OK;
 }
 
-int rsparse_hip_sample_negatives(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* seen_p,
-                                 const int32_t* seen_j, const int32_t* keep_p, const int32_t* keep_j, int32_t* out_p, int32_t* out_j,
-                                 int64_t out_capacity) {
+// the host form of both samplers: w == nullptr (with weighted false) is the uniform stream
+int sample_negatives_host(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* seen_p, const int32_t* seen_j,
+                          const int32_t* keep_p, const int32_t* keep_j, const uint32_t* w, bool weighted, int32_t* out_p,
+                          int32_t* out_j, int64_t out_capacity, int64_t* filled_rows) {
   int rc = sample_negatives_args(row0, n_rows, n_item, n, seen_p, seen_j, keep_p, keep_j, out_p, out_capacity);
   if (rc) return rc;
+  if (weighted) {
+    if (!w) return fail(RSPARSE_HIP_ERR_INVALID, "w is NULL");
+    for (int i = 0; i < n_item; i++)
+      if (w[i] == 0) return fail(RSPARSE_HIP_ERR_INVALID, "a weight is 0: every weight is at least 1 (exclude an item through the seen rows)");
+    if (filled_rows) *filled_rows = 0;
+  }
   // the dgRMatrix slots: p from 0, non-decreasing; j strictly ascending within a row and inside the matrix; keep within seen
   if (seen_p[0] != 0 || (keep_p && keep_p[0] != 0)) return fail(RSPARSE_HIP_ERR_INVALID, "seen_p[0] or keep_p[0] != 0");
   int64_t total = 0;
@@ -1745,7 +1761,7 @@ int rsparse_hip_sample_negatives(uint64_t seed, int64_t row0, int n_rows, int n_
   if (total > out_capacity)
     return fail(RSPARSE_HIP_ERR_INVALID, "out_capacity is " + std::to_string(out_capacity) + ", the rows need " + std::to_string(total));
   if (n_rows == 0 || total == 0) return RSPARSE_HIP_OK;
-  DevBuf dSP, dSJ, dKP, dKJ, dOP, dOJ;
+  DevBuf dSP, dSJ, dKP, dKJ, dOP, dOJ, dW, dC, dF;
   HIP_TRY(upload_host(dSP, seen_p, (size_t)n_rows + 1));
   const size_t s_nnz = (size_t)seen_p[n_rows], k_nnz = keep_p ? (size_t)keep_p[n_rows] : 0;
   HIP_TRY(dSJ.alloc(std::max<size_t>(s_nnz, 1) * 4));   // (never NULL: the device form wants the slot)
@@ -1757,14 +1773,73 @@ int rsparse_hip_sample_negatives(uint64_t seed, int64_t row0, int n_rows, int n_
   }
   HIP_TRY(dOP.alloc(((size_t)n_rows + 1) * 4));
   HIP_TRY(dOJ.alloc((size_t)total * 4));
-  rc = rsparse_hip_sample_negatives_device(seed, row0, n_rows, n_item, n, dSP.as<int32_t>(), dSJ.as<int32_t>(),
-                                           keep_p ? dKP.as<int32_t>() : nullptr, keep_p ? dKJ.as<int32_t>() : nullptr,
-                                           dOP.as<int32_t>(), dOJ.as<int32_t>(), total, nullptr);
+  if (weighted) {   // (n_item >= 1: total > 0)
+    HIP_TRY(upload_host(dW, w, (size_t)n_item));
+    HIP_TRY(dC.alloc((size_t)n_item * 8));
+    HIP_TRY(dF.alloc(sizeof(int32_t)));
+    if ((rc = rsparse_hip_weights_prefix_device(dW.as<uint32_t>(), n_item, dC.as<uint64_t>(), nullptr))) return rc;
+  }
+  rc = sample_negatives_device(seed, row0, n_rows, n_item, n, dSP.as<int32_t>(), dSJ.as<int32_t>(),
+                               keep_p ? dKP.as<int32_t>() : nullptr, keep_p ? dKJ.as<int32_t>() : nullptr,
+                               weighted ? dC.as<uint64_t>() : nullptr, weighted, dOP.as<int32_t>(), dOJ.as<int32_t>(), total,
+                               weighted ? dF.as<int32_t>() : nullptr, nullptr);
   if (rc) return rc;
   HIP_TRY(hipDeviceSynchronize());
+  if (weighted && filled_rows) {
+    int32_t f = 0;
+    HIP_TRY(hipMemcpy(&f, dF.p, sizeof(f), hipMemcpyDeviceToHost));
+    *filled_rows = f;
+  }
   HIP_TRY(hipMemcpy(out_p, dOP.p, ((size_t)n_rows + 1) * 4, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out_j, dOJ.p, (size_t)total * 4, hipMemcpyDeviceToHost));
   return RSPARSE_HIP_OK;
+}
+}  // namespace
+
+int rsparse_hip_sample_negatives_device(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* d_seen_p,
+                                        const int32_t* d_seen_j, const int32_t* d_keep_p, const int32_t* d_keep_j,
+                                        int32_t* d_out_p, int32_t* d_out_j, int64_t out_capacity, void* stream) {
+  return sample_negatives_device(seed, row0, n_rows, n_item, n, d_seen_p, d_seen_j, d_keep_p, d_keep_j, nullptr, false, d_out_p, d_out_j,
+                                 out_capacity, nullptr, stream);
+}
+
+int rsparse_hip_sample_negatives(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* seen_p,
+                                 const int32_t* seen_j, const int32_t* keep_p, const int32_t* keep_j, int32_t* out_p, int32_t* out_j,
+                                 int64_t out_capacity) {
+  return sample_negatives_host(seed, row0, n_rows, n_item, n, seen_p, seen_j, keep_p, keep_j, nullptr, false, out_p, out_j, out_capacity,
+                               nullptr);
+}
+
+int rsparse_hip_weights_prefix_device(const uint32_t* d_w, int n_item, uint64_t* d_cum, void* stream) {
+  if (n_item < 0) return fail(RSPARSE_HIP_ERR_INVALID, "n_item < 0");
+  if (!d_w || !d_cum) return fail(RSPARSE_HIP_ERR_INVALID, "d_w or d_cum is NULL");
+  if (n_item == 0) return RSPARSE_HIP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = g_ws.ensure_device()) return rc;
+  HIP_TRY(g_ws.score_buf.ensure((weights_prefix_ws_bytes(n_item) + 7) / 8));
+  int* d_flag = nullptr;
+  hipError_t e = launch_weights_prefix(d_w, n_item, d_cum, g_ws.score_buf, &d_flag, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_weights_prefix");
+  int flag = 0;
+  HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof(flag), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (flag) return fail(RSPARSE_HIP_ERR_INVALID, "a weight is 0: every weight is at least 1 (exclude an item through the seen rows)");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_sample_negatives_weighted_device(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* d_seen_p,
+                                                 const int32_t* d_seen_j, const int32_t* d_keep_p, const int32_t* d_keep_j,
+                                                 const uint64_t* d_cum, int32_t* d_out_p, int32_t* d_out_j, int64_t out_capacity,
+                                                 int32_t* d_filled_rows, void* stream) {
+  return sample_negatives_device(seed, row0, n_rows, n_item, n, d_seen_p, d_seen_j, d_keep_p, d_keep_j, d_cum, true, d_out_p, d_out_j,
+                                 out_capacity, d_filled_rows, stream);
+}
+
+int rsparse_hip_sample_negatives_weighted(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* seen_p,
+                                          const int32_t* seen_j, const int32_t* keep_p, const int32_t* keep_j, const uint32_t* w,
+                                          int32_t* out_p, int32_t* out_j, int64_t out_capacity, int64_t* filled_rows) {
+  return sample_negatives_host(seed, row0, n_rows, n_item, n, seen_p, seen_j, keep_p, keep_j, w, true, out_p, out_j, out_capacity,
+                               filled_rows);
 }
 
 namespace {

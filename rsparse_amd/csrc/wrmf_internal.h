@@ -420,6 +420,17 @@ hipError_t launch_sample_negatives(uint64_t seed, int64_t row0, int n_rows, int 
 // sum of the lengths of rows [256 b, 256 b + 256); boff: (n_rows + 255) / 256 words of scratch; *total = the 64-bit out_p[n_rows]
 hipError_t launch_row_pointer_scan(int n_rows, const long long* bsum, long long* boff, long long* total, int32_t* out_p, hipStream_t s);
 
+// popularity-weighted negative sampling (wrmf_sample_weighted.hip): the stream is defined in rsparse_wrmf_hip.h.
+// launch_weights_prefix writes cum[i] = w[0] + ... + w[i] (n_item >= 1 of them); ws: weights_prefix_ws_bytes(n_item) bytes, *d_flag
+// points into it, for the caller to read back: non-zero = a zero weight.  launch_sample_negatives_weighted writes the rows at the
+// out_p of launch_sample_row_pointers (the lengths are the uniform sampler's) and adds the rows it had to fill to *filled_rows
+// (null: not counted); the limits are launch_sample_negatives'.
+size_t weights_prefix_ws_bytes(int n_item);
+hipError_t launch_weights_prefix(const uint32_t* w, int n_item, uint64_t* cum, void* ws, int** d_flag, hipStream_t s);
+hipError_t launch_sample_negatives_weighted(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* seen_p,
+                                            const int32_t* seen_j, const int32_t* keep_p, const int32_t* keep_j, const uint64_t* cum,
+                                            const int32_t* out_p, int32_t* out_j, int* filled_rows, hipStream_t s);
+
 // train / test split (wrmf_split.hip): the stream is defined in rsparse_wrmf_hip.h.  mode 0 = proportion (threshold <= 2^32, no
 // `by`), 1 = leave-out (leave_out >= 1, min_train >= 0; by: one double per stored entry, or null = random keys).
 // launch_split_count writes both row-pointer arrays (n_rows + 1 each) and keeps the rows' thresholds in ws (split_ws_bytes(n_rows)

@@ -467,6 +467,44 @@ class HipBackend:
             out_p.data_ptr(), out_j.data_ptr(), cap, self._stream()))
         return out_p, out_j[:int(out_p[-1])]
 
+    def weights_prefix(self, w_dev):
+        """the inclusive 64-bit prefix of the item weights of the weighted negative stream (rsparse_amd/rng.py weights_prefix):
+        w_dev the uint32 weights (every one >= 1) on the device as an int32 tensor of the same bits (`w.view(np.int32)`) -> an
+        int64 tensor of their running sums (the bits of the library's uint64), to pass to `sample_negatives_weighted` any number
+        of times.  A zero weight is refused by the library."""
+        assert w_dev.dtype == torch.int32 and w_dev.is_contiguous()
+        n_item = int(w_dev.numel())
+        cum = torch.empty(max(n_item, 1), dtype=torch.int64, device=w_dev.device)
+        if n_item:
+            _lib.check(self.lib.rsparse_hip_weights_prefix_device(w_dev.data_ptr(), n_item, cum.data_ptr(), self._stream()))
+        return cum[:n_item]
+
+    def sample_negatives_weighted(self, seed, row0, seen_p, seen_j, keep_p, keep_j, n_item, n, cum):
+        """`sample_negatives` with the negatives drawn in proportion to item weights (wrmf_sample_weighted.hip; rsparse_amd/rng.py
+        sample_negatives_weighted is the definition): cum = `weights_prefix` of the n_item weights.  -> (out_p, out_j,
+        filled_rows): the rows as `sample_negatives` gives them, and the number of rows whose draw budget ended before n distinct
+        admissible items were drawn (filled with the lowest admissible items; 0 for ordinary weights)."""
+        assert seen_p.dtype == torch.int32 and seen_j.dtype == torch.int32 and (keep_p is None) == (keep_j is None)
+        assert cum.dtype == torch.int64 and int(cum.numel()) == int(n_item) and cum.is_contiguous()
+        n_rows, n = int(seen_p.numel()) - 1, int(n)
+        dev = seen_p.device
+        out_p = torch.zeros(max(n_rows, 0) + 1, dtype=torch.int32, device=dev)
+        if n_rows <= 0:
+            return out_p, torch.empty(0, dtype=torch.int32, device=dev), 0
+        kept = 0
+        if keep_p is not None:
+            assert keep_p.dtype == torch.int32 and keep_j.dtype == torch.int32 and int(keep_p.numel()) == n_rows + 1
+            kept = int(keep_p[-1]) - int(keep_p[0])
+        cap = max(0, kept) + n_rows * max(min(n, int(n_item)), 0)
+        out_j = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        one = torch.zeros(2, dtype=torch.int32, device=dev)   # (a pattern without entries: the library still wants non-NULL slots)
+        filled = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(self.lib.rsparse_hip_sample_negatives_weighted_device(
+            int(seed), int(row0), n_rows, int(n_item), n, seen_p.data_ptr(), (seen_j if seen_j.numel() else one).data_ptr(),
+            None if keep_p is None else keep_p.data_ptr(), None if keep_p is None else (keep_j if keep_j.numel() else one).data_ptr(),
+            (cum if cum.numel() else one).data_ptr(), out_p.data_ptr(), out_j.data_ptr(), cap, filled.data_ptr(), self._stream()))
+        return out_p, out_j[:int(out_p[-1])], int(filled[0])
+
     def split_rows(self, seed, row0, p, j, v=None, test_threshold=None, leave_out=None, min_train=1, by=None):
         """the train / test split of the rows of a canonical CSR, made on the device (wrmf_split.hip; rsparse_amd/rng.py split_flags
         is the definition): p, j int32 on the device (p may be a slice of a larger pattern's row pointers), v None or a tensor of

@@ -31,6 +31,23 @@ into the output (a subset of seen), M = n_item - |seen| admissible items numbere
 The negatives depend on (seed, g, seen, n_item, n) alone: not on the rows asked for together, the device, or the order in which
 the draws are evaluated ("the first d distinct values" is a property of the sequence).
 
+`sample_negatives_weighted` is the specification of the sixth stream: the same rows with the negatives drawn in proportion to
+integer item weights (popularity-weighted negatives; rsparse_amd/csrc/wrmf_sample_weighted.hip draws it on the device bit for
+bit, the header states it for C hosts).  w[0 .. n_item) are unsigned 32-bit integers, every one >= 1 (a zero is refused: "never a
+negative" is the job of the exclusion list); C[i] = w[0] + ... + w[i] in 64 bits, W = C[n_item - 1] < 2^63:
+
+    draw t    Philox4x32-10, key (lo32(seed), hi32(seed)), counter (lo32(t >> 1), g, 5, hi32(t >> 1)) -> o0..o3;
+              v = o1 2^32 + o0 for even t, o3 2^32 + o2 for odd t;  r = floor(v W / 2^64), the high 64 bits of the 128-bit
+              product;  item = #{i : C[i] <= r} = searchsorted(C, r, side="right")
+    chosen    M = n_item - |seen|.  n >= M: every admissible item, nothing is drawn.  Otherwise A = the first n DISTINCT values,
+              in the order of the draw sequence, among the draws t = 0 .. B(n) - 1 that are NOT in seen, B(n) = 64 n + 4096.  If
+              the budget ends with |A| < n the row is FILLED with the n - |A| admissible items of lowest item number that are
+              not in A, and counts as a filled row (the budget is part of the definition: no input can make a row spin;
+              ordinary weights never fill, weights such as [2^31, 1, 1, ...] do)
+    row       the ascending merge of keep and the chosen items: |keep| + min(n, M) entries, as for the uniform sampler
+
+A row depends on (seed, g, seen, keep, w, n) alone: not on the rows sampled with it, the batch, the rank count or the device.
+
 `split_flags` / `split_rows` are the specification of the fourth and fifth stream: the train / test split of a canonical CSR
 (columns ascending and unique per row; stored zeros count as entries), which rsparse_amd/csrc/wrmf_split.hip draws on the device
 bit for bit.  Row u has the global index g = row0 + u and L entries; an entry is named by its position t = 0 .. L - 1 in the row:
@@ -53,6 +70,7 @@ PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
 PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
 STREAM_USERS, STREAM_ITEMS, STREAM_NEGATIVES = 0, 1, 2
 STREAM_SPLIT, STREAM_LEAVE_OUT = 3, 4
+STREAM_WEIGHTED_NEGATIVES = 5
 MAX_NEGATIVES = 8192   # RSPARSE_HIP_MAX_NEGATIVES
 _MASK = np.uint64(0xFFFFFFFF)
 _S32 = np.uint64(32)
@@ -185,6 +203,116 @@ def sample_negatives(seed, row0, seen_p, seen_j, keep_p, keep_j, n_item, n):
         raise ValueError("sample_negatives: the output does not fit int32 row pointers")
     out_j = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
     return out_p.astype(np.int32), out_j.astype(np.int32)
+
+
+def mul_hi64(v, W):
+    """floor(v W / 2^64) for uint64 arrays (or scalars) v, W: the high half of the 128-bit product, from 32-bit halves in uint64"""
+    v, W = np.asarray(v, dtype=np.uint64), np.asarray(W, dtype=np.uint64)
+    vl, vh, wl, wh = v & _MASK, v >> _S32, W & _MASK, W >> _S32
+    lh, hl = vl * wh, vh * wl
+    mid = ((vl * wl) >> _S32) + (lh & _MASK) + (hl & _MASK)       # < 3 * 2^32
+    return vh * wh + (lh >> _S32) + (hl >> _S32) + (mid >> _S32)
+
+
+def weights_prefix(w):
+    """C[i] = w[0] + ... + w[i] in uint64, for integer weights in [1, 2^32) (a zero is refused)"""
+    w = np.asarray(w)
+    if w.ndim != 1 or w.dtype.kind not in "iu" or w.size >= 2 ** 31:
+        raise ValueError("weights_prefix: the weights are a 1-d integer array of fewer than 2^31 entries")
+    if w.size and (int(w.min()) < 1 or int(w.max()) >= 2 ** 32):
+        raise ValueError("weights_prefix: a weight outside [1, 2^32)")
+    return np.cumsum(w.astype(np.uint64), dtype=np.uint64)
+
+
+def quantize_weights(v):
+    """item weights as the uint32 the weighted stream is defined on.  An integer-dtype array is taken as is and must lie in
+    [1, 2^32); float weights -- finite, >= 0, max > 0 -- become max(1, floor(v 2^24 / max(v)))."""
+    v = np.asarray(v)
+    if v.ndim != 1:
+        raise ValueError("quantize_weights: the weights are a 1-d array")
+    if v.dtype.kind in "iu":
+        if v.size and (int(v.min()) < 1 or int(v.max()) >= 2 ** 32):
+            raise ValueError("quantize_weights: an integer weight outside [1, 2^32)")
+        return v.astype(np.uint32)
+    if v.dtype.kind != "f":
+        raise TypeError("quantize_weights: the weights are integers or floats")
+    v = v.astype(np.float64)
+    if not v.size or not np.isfinite(v).all() or v.min() < 0 or not v.max() > 0:
+        raise ValueError("quantize_weights: float weights are finite, >= 0 and have a positive maximum")
+    return np.maximum(np.floor(v * float(1 << 24) / v.max()), 1.0).astype(np.uint32)
+
+
+def popularity_weights(x, power=0.75, smoothing=1.0):
+    """(the number of stored entries of every column of the sparse matrix x + smoothing) ** power, quantized"""
+    import scipy.sparse as sp
+    x = sp.csr_matrix(x)
+    cnt = np.bincount(x.indices, minlength=x.shape[1]).astype(np.float64)
+    return quantize_weights((cnt + float(smoothing)) ** float(power))
+
+
+def weighted_draws(seed, g, t0, count, C):
+    """the items of the draws t0 .. t0 + count - 1 of global row g under the inclusive weight prefix C -> int64 array"""
+    C = np.asarray(C, dtype=np.uint64)
+    t = np.arange(t0, t0 + count, dtype=np.uint64)
+    c = t >> np.uint64(1)
+    counter = np.stack([c & _MASK, np.full_like(c, g), np.full_like(c, STREAM_WEIGHTED_NEGATIVES), c >> _S32], axis=-1)
+    key = np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64)
+    o = philox4x32_10(counter, key).astype(np.uint64)
+    odd = (t & np.uint64(1)).astype(bool)
+    v = (np.where(odd, o[:, 3], o[:, 1]) << _S32) | np.where(odd, o[:, 2], o[:, 0])
+    return np.searchsorted(C, mul_hi64(v, C[-1]), side="right").astype(np.int64)
+
+
+def weighted_budget(n):
+    """B(n): the draws a row of the weighted stream may take before it is filled"""
+    return 64 * int(n) + 4096
+
+
+def sample_negatives_weighted(seed, row0, seen_p, seen_j, keep_p, keep_j, n_item, n, w):
+    """`sample_negatives` with the negatives drawn in proportion to the integer weights w (n_item of them, every one in
+    [1, 2^32); the definition at the top of this file).  -> (out_p, out_j, filled_rows): canonical CSR, int32, and the number of
+    rows whose draw budget ended before n distinct admissible items were drawn."""
+    seed, row0, n_item, n = int(seed), int(row0), int(n_item), int(n)
+    if not 0 <= seed < 2 ** 64 or row0 < 0 or not 0 <= n_item < 2 ** 31 or n < 1 or (keep_p is None) != (keep_j is None):
+        raise ValueError("sample_negatives_weighted: bad arguments")
+    if n > MAX_NEGATIVES:
+        raise NotImplementedError("sample_negatives_weighted: n > %d" % MAX_NEGATIVES)
+    C = weights_prefix(w)
+    if C.size != n_item:
+        raise ValueError("sample_negatives_weighted: one weight per item")
+    sp_, sj = np.asarray(seen_p, dtype=np.int64), np.asarray(seen_j, dtype=np.int64)
+    n_rows = sp_.size - 1
+    if row0 + n_rows > 2 ** 32:
+        raise ValueError("sample_negatives_weighted: the global row index does not fit 32 bits")
+    kp = np.zeros(n_rows + 1, dtype=np.int64) if keep_p is None else np.asarray(keep_p, dtype=np.int64)
+    kj = np.zeros(0, dtype=np.int64) if keep_j is None else np.asarray(keep_j, dtype=np.int64)
+    B = weighted_budget(n)
+    rows, filled = [], 0
+    for u in range(n_rows):
+        seen, keep = sj[sp_[u]:sp_[u + 1]], kj[kp[u]:kp[u + 1]]
+        M = n_item - seen.size
+        if n >= M:
+            items = np.setdiff1d(np.arange(n_item, dtype=np.int64), seen)
+        else:
+            A, t0 = np.zeros(0, dtype=np.int64), 0
+            while A.size < n and t0 < B:
+                step = min(max(256, 2 * n), B - t0)
+                d = weighted_draws(seed, row0 + u, t0, step, C)
+                d = np.concatenate([A, d[~np.isin(d, seen)]])
+                vals, first = np.unique(d, return_index=True)
+                A = d[np.sort(first)][:n]                      # distinct, in the order of their first draw
+                t0 += step
+            if A.size < n:
+                filled += 1
+                rest = np.setdiff1d(np.arange(n_item, dtype=np.int64), np.concatenate([seen, A]))
+                A = np.concatenate([A, rest[:n - A.size]])
+            items = A
+        rows.append(np.sort(np.concatenate([keep, items])))
+    out_p = np.concatenate([[0], np.cumsum([r.size for r in rows])])
+    if out_p[-1] >= 2 ** 31:
+        raise ValueError("sample_negatives_weighted: the output does not fit int32 row pointers")
+    out_j = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+    return out_p.astype(np.int32), out_j.astype(np.int32), filled
 
 
 def by_keys(by):

@@ -678,7 +678,8 @@ class WRMF:
     def _predict_device(self, x, k, not_recommend, items_exclude, candidates=None, negatives=None):
         """the device part of `predict`: (indices int32, scores float64) of this rank's block of rows, _row_bounds[rank], still
         on the device -- 1-based with NA_integer_ as top_product writes them --, and x as CSR.  negatives = (n, seed, actual as
-        canonical CSR): the candidates are sampled here (`sample_negatives`), batch by batch, and never leave the device."""
+        canonical CSR, uint32 item weights or None): the candidates are sampled here (`sample_negatives`), batch by batch, and
+        never leave the device."""
         if self._V is None:
             raise RuntimeError("model is not fitted")
         x = sp.csr_matrix(x, dtype=np.float64)
@@ -697,7 +698,7 @@ class WRMF:
         excl, not_recommend = self._exclusion_args(x, not_recommend, items_exclude)
         be = self._backend()
         if negatives is not None:
-            n_neg, seed, act = negatives
+            n_neg, seed, act, neg_w = negatives
             seen, keep = self._negatives_lists(x, n_item, act, not_recommend, excl)
             seed = self._negatives_seed(seed)
         emb = self._transform_device(x)             # (n_new, rank), complete on every rank
@@ -715,7 +716,7 @@ class WRMF:
             fn = be.top_candidates if hasattr(be, "top_candidates") else self._top_candidates_host
             res = torch.empty((n_mine, k), dtype=torch.int32, device=emb.device)
             sc = torch.empty((n_mine, k), dtype=torch.float64, device=emb.device)
-            for a0, b0, c_p, c_j in self._negatives_batches(be, seed, seen, keep, a, b, n_item, n_neg):
+            for a0, b0, c_p, c_j in self._negatives_batches(be, seed, seen, keep, a, b, n_item, n_neg, neg_w):
                 res[a0:b0], sc[a0:b0] = fn(emb[a + a0:a + b0], self._V, k, c_p, c_j, None if nr_p is None else nr_p[a0:b0 + 1], nr_j,
                                            d_ex, float(self.global_bias))
         elif n_mine > 0:
@@ -763,7 +764,7 @@ class WRMF:
         return torch.from_numpy(res).to(U.device), torch.from_numpy(sc).to(U.device)
 
     def evaluate(self, x, actual, k, not_recommend="x", items_exclude=(), metrics=("ap", "ndcg"), candidates=None, negatives=None,
-                 seed=None):
+                 seed=None, negative_weights=None):
         """`predict(x, k, ...)` scored against the held-out interactions `actual` (n x anything sparse, relevances as values) by
         the reference's ap_k / ndcg_k (R/metrics.R:31-127) without the lists leaving the device: {name: float64 vector of n}
         for each name in `metrics` ("ap", "ndcg").  Equals `rsparse_amd.metrics.ap_k(self.predict(x, k, ...), actual)` (and
@@ -771,7 +772,8 @@ class WRMF:
         `predict` -- the lists are ranked within every row's candidates (sampled-negative evaluation).  `negatives=n` (with
         `seed`) makes those candidates itself: every row's held-out items against n sampled negatives, exactly
         `candidates=self.sample_negatives(x, n, actual, not_recommend, items_exclude, seed)` -- bit for bit -- but sampled on the
-        device in row batches and handed to the ranking without a host copy; it excludes `candidates`.
+        device in row batches and handed to the ranking without a host copy; it excludes `candidates`.  `negative_weights` (with
+        `negatives`): the `weights` of `sample_negatives` -- popularity-weighted instead of uniform negatives.
 
         `metrics` may also name "precision", "recall", "hit", "mrr" and "coverage" (rsparse_amd.metrics.hit_metrics_reference is
         their definition), and `k` may be a strictly ascending sequence of up to 16 cutoffs: ONE `predict` pass at max(k), one
@@ -787,6 +789,8 @@ class WRMF:
             raise ValueError("metrics must name some of 'ap', 'ndcg', 'precision', 'recall', 'hit', 'mrr', 'coverage'")
         if negatives is not None and candidates is not None:
             raise ValueError("negatives and candidates exclude each other: the negatives ARE the candidates")
+        if negative_weights is not None and negatives is None:
+            raise ValueError("negative_weights needs negatives: they weight the sampled negatives")
         scalar_k = not isinstance(k, (tuple, list, np.ndarray, range))
         hit_names = tuple(m for m in HIT_METRICS if m in metrics)
         cutoffs = None
@@ -796,7 +800,9 @@ class WRMF:
         x = sp.csr_matrix(x, dtype=np.float64)
         n_new = x.shape[0]
         act = canonical_actual(actual, n_new)
-        neg = None if negatives is None else (self._negatives_count(negatives), seed, act)
+        neg = None
+        if negatives is not None:
+            neg = (self._negatives_count(negatives), seed, act, self._negatives_weights(negative_weights, x.shape[1]))
         res, _, x = self._predict_device(x, k, not_recommend, items_exclude, candidates, neg)
         ws, me = self._dist()
         a, b = self._row_bounds[me]
@@ -864,6 +870,18 @@ class WRMF:
             raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "more than 8192 negatives per row are not on the device path")
         return int(n)
 
+    @staticmethod
+    def _negatives_weights(weights, n_item):
+        """the uint32 weights of the weighted stream from `weights=` / `negative_weights=` (None: the uniform stream): a float
+        array through rsparse_amd.rng.quantize_weights, an integer array as it is"""
+        if weights is None:
+            return None
+        from . import rng as _rng
+        w = _rng.quantize_weights(np.asarray(weights))
+        if w.shape != (n_item,):
+            raise ValueError("the weights are one per item: %d of them" % n_item)
+        return w
+
     def _negatives_seed(self, seed):
         """the seed of a sampling call: given, or one 63-bit draw from the model's generator (as factor_init="device" takes
         its own); with several ranks rank 0's, so that every rank samples the same stream"""
@@ -905,10 +923,12 @@ class WRMF:
             out.append(m)
         return out
 
-    def _negatives_batches(self, be, seed, seen, keep, a, b, n_item, n):
+    def _negatives_batches(self, be, seed, seen, keep, a, b, n_item, n, weights=None):
         """the candidate rows of the rows [a, b) in batches of whole rows: yields (a0, b0, c_p, c_j) with a0 / b0 counted from a and
         (c_p, c_j) the batch's canonical CSR pattern on the device, row pointers from 0.  A batch's rows are sampled with row0 =
-        their first global row, so the batching cannot change a row."""
+        their first global row, so the batching cannot change a row.  weights (uint32, one per item; None: uniform): the
+        weighted stream, its prefix built once for all batches; rows that had to be filled are reported in one RuntimeWarning
+        when the last batch is done."""
         from . import rng as _rng
         seen, keep = seen[a:b], keep[a:b]
         budget = self.negatives_batch or getattr(be, "top_candidates_batch", 1 << 28)
@@ -917,21 +937,38 @@ class WRMF:
         if on_dev:
             s_p, s_j = be.to_device(seen.indptr, torch.int32), be.to_device(seen.indices, torch.int32)
             k_p, k_j = (be.to_device(keep.indptr, torch.int32), be.to_device(keep.indices, torch.int32)) if keep.nnz else (None, None)
-        a0, n_mine = 0, b - a
+            if weights is not None:
+                cum = be.weights_prefix(be.to_device(weights.view(np.int32), torch.int32))
+        a0, n_mine, filled = 0, b - a, 0
         while a0 < n_mine:
             b0 = int(np.searchsorted(upper, upper[a0] + budget, side="right")) - 1
             b0 = min(n_mine, max(b0, a0 + 1))
-            if on_dev:
+            kp_host = keep.indptr[a0:b0 + 1]
+            if on_dev and weights is not None:
+                c_p, c_j, f = be.sample_negatives_weighted(seed, a + a0, s_p[a0:b0 + 1], s_j, None if k_p is None else k_p[a0:b0 + 1],
+                                                           k_j, n_item, n, cum)
+                filled += f
+            elif on_dev:
                 c_p, c_j = be.sample_negatives(seed, a + a0, s_p[a0:b0 + 1], s_j, None if k_p is None else k_p[a0:b0 + 1], k_j,
                                                n_item, n)
             else:   # the backend has no sampler (the CPU stand-in of the tests): the numpy specification
-                c_p, c_j = _rng.sample_negatives(seed, a + a0, seen.indptr[a0:b0 + 1], seen.indices, keep.indptr[a0:b0 + 1],
-                                                 keep.indices, n_item, n)
+                if weights is not None:
+                    c_p, c_j, f = _rng.sample_negatives_weighted(seed, a + a0, seen.indptr[a0:b0 + 1], seen.indices, kp_host,
+                                                                 keep.indices, n_item, n, weights)
+                    filled += f
+                else:
+                    c_p, c_j = _rng.sample_negatives(seed, a + a0, seen.indptr[a0:b0 + 1], seen.indices, kp_host, keep.indices,
+                                                     n_item, n)
                 c_p, c_j = be.to_device(c_p, torch.int32), be.to_device(c_j, torch.int32)
             yield a0, b0, c_p, c_j
             a0 = b0
+        if filled:
+            import warnings
+            warnings.warn("weighted negatives: %d row(s) did not reach %d distinct admissible items within the draw budget and were "
+                          "filled with the lowest admissible items (the weights concentrate on items the rows exclude)" % (filled, n),
+                          RuntimeWarning, stacklevel=3)
 
-    def sample_negatives(self, x, n, actual=None, not_recommend="x", items_exclude=(), seed=None):
+    def sample_negatives(self, x, n, actual=None, not_recommend="x", items_exclude=(), seed=None, weights=None):
         """The candidate matrix of a sampled-metric evaluation: row u holds the stored positions of row u of `actual` (the
         held-out items; None: nothing) plus min(n, admissible) items drawn uniformly WITHOUT replacement from the items that are
         neither in the row of `not_recommend` (default: `x` itself; None = nothing), nor in the row of `actual`, nor in
@@ -941,7 +978,16 @@ class WRMF:
         model's generator; under torch.distributed every rank uses rank 0's seed and samples its own block of rows.  The draws
         are made on the device (wrmf_sample.hip; rsparse_amd/rng.py is the definition); the exclusion lists are joined once on
         the host with scipy, where `items_exclude` costs n_rows x len(items_exclude) entries.  1 <= n <= 8192.  Needs no fitted
-        factors: an unfitted model samples for the shape of `x`."""
+        factors: an unfitted model samples for the shape of `x`.
+
+        `weights` (one per item; None: uniform, as above): the negatives are drawn in proportion to them instead -- the
+        popularity-weighted protocol, e.g. `rsparse_amd.rng.popularity_weights(train, power=0.75)`.  A float array (finite, >= 0)
+        is quantized to integers in [1, 2^24] by `rsparse_amd.rng.quantize_weights`; an integer array in [1, 2^32) is taken as
+        it is; an item that must never be a negative belongs in `items_exclude`.  The stream is the one
+        `rsparse_amd.rng.sample_negatives_weighted` defines (wrmf_sample_weighted.hip on the device): a row depends on (seed, row,
+        its exclusions, the weights, n) alone.  A row whose weights lie almost entirely on excluded items ends its draw budget
+        (64 n + 4096 draws) early and is filled with the lowest admissible items; one RuntimeWarning names the number of such
+        rows.  Under torch.distributed every rank passes the same weights."""
         n = self._negatives_count(n)
         x = sp.csr_matrix(x, dtype=np.float64)
         n_new, n_item = x.shape
@@ -954,11 +1000,12 @@ class WRMF:
             raise ValueError("not_recommend must have the shape of x")
         seen, keep = self._negatives_lists(x, n_item, act, not_recommend, excl)
         seed = self._negatives_seed(seed)
+        weights = self._negatives_weights(weights, n_item)
         be = self._backend()
         a, b, ws = self._my_rows(x)
         dev = be.to_device(np.zeros(1, dtype=np.int32), torch.int32).device
         lens, cols = [torch.zeros(0, dtype=torch.int64, device=dev)], [torch.zeros(0, dtype=torch.int32, device=dev)]
-        for _, _, c_p, c_j in self._negatives_batches(be, seed, seen, keep, a, b, n_item, n):
+        for _, _, c_p, c_j in self._negatives_batches(be, seed, seen, keep, a, b, n_item, n, weights):
             lens.append(torch.diff(c_p.to(torch.int64)))
             cols.append(c_j)
         lens, cols = torch.cat(lens), torch.cat(cols)
