@@ -507,6 +507,71 @@ int rsparse_hip_hit_metrics(const int32_t* predictions, int n_users, int k, cons
                             double* recall, double* hit, double* mrr, int32_t* first_seen, int n_items);
 
 /* ------------------------------------------------------------------------------------------------
+ * beyond-accuracy metrics of the same lists at the same cutoffs: popularity, novelty, exposure of the catalogue and
+ * intra-list diversity.  The reference package has none of them: `list_metrics_reference` and
+ * `list_diversity_reference` of rsparse_amd/metrics.py are the definitions.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Lists and cutoffs as for rsparse_hip_hit_metrics*.  A position is VALID when its item lies in 1 .. n_items; NA_integer_ and
+ * anything else is skipped, a repeated item counts wherever it stands.  item_count: int32 of n_items, values >= 0 (e.g. the
+ * interactions of every item in the training matrix).  item_info: int64 of n_items, fixed point in units of 2^-32, values
+ * 0 <= v < 2^40 (e.g. the items' self-information in bits), so that a sum over 8192 positions stays below 2^53.
+ *   valid[u, t]      = #{valid positions i <= c_t}  (int32)
+ *   count_sum[u, t]  = sum of item_count[item_i] over them  (int64)      popularity = double(count_sum) / double(valid)
+ *   info_sum[u, t]   = sum of item_info[item_i] over them   (int64)      novelty    = double(info_sum) / double(valid 2^32)
+ * popularity and novelty are NaN where valid = 0; every double is one IEEE division of two exactly converted integers.
+ * exposure[b, item] += 1 for every valid position i with c_(b-1) < i <= c_b, over all users: the histogram per cutoff INTERVAL.
+ *
+ * device form: d_predictions n_users x k ROW-major; the five per-row outputs n_users x n_cutoffs row-major; d_exposure
+ * n_cutoffs x n_items int32, caller-ZEROED: calls on successive row batches accumulate, and the caller cumulates along b
+ * afterwards (exposure at c_t = the sum of the intervals 1 .. t).  Every output is nullable, not all; a table is read only when it
+ * is not NULL, and d_count_sum / d_popularity need d_item_count, d_info_sum / d_novelty need d_item_info.  Integer atomics only
+ * and no floating-point sum: a repeated call returns the same bits.  Enqueued on `stream`, no synchronisation, no workspace.
+ * All before a device is touched: NULL where a pointer is needed, every output NULL, n_users < 0, k < 1, n_cutoffs < 1, bad
+ * cutoffs, n_items < 1 -> ERR_INVALID; n_cutoffs > RSPARSE_HIP_MAX_CUTOFFS or k > RSPARSE_HIP_MAX_TOPK_LARGE ->
+ * ERR_UNSUPPORTED; n_users == 0 -> OK.  The value ranges of the two tables are preconditions here. */
+int rsparse_hip_list_metrics_device(const int32_t* d_predictions, int n_users, int k, const int32_t* cutoffs, int n_cutoffs,
+                                    const int32_t* d_item_count, const int64_t* d_item_info, int n_items, int32_t* d_valid,
+                                    int64_t* d_count_sum, int64_t* d_info_sum, double* d_popularity, double* d_novelty,
+                                    int32_t* d_exposure, void* stream);
+
+/* host form: predictions n_users x k column-major (1-based, NA_integer_), the per-row outputs n_users x n_cutoffs COLUMN-major,
+ * exposure n_items x n_cutoffs column-major, initialised by the call and returned CUMULATED: exposure[item, t] = the valid
+ * positions i <= c_t that name the item.  Also ERR_INVALID: item_count < 0, item_info outside 0 <= v < 2^40. */
+int rsparse_hip_list_metrics(const int32_t* predictions, int n_users, int k, const int32_t* cutoffs, int n_cutoffs,
+                             const int32_t* item_count, const int64_t* item_info, int n_items, int32_t* valid,
+                             int64_t* count_sum, int64_t* info_sum, double* popularity, double* novelty, int32_t* exposure);
+
+/* d_inv[item] = 1 / sqrt(sum of squares of V[item, c0 : c1)) in double, 0.0 for a DEGENERATE item (sum zero or not finite: the
+ * rule of rsparse_hip_normalize_items*_device; the zero is the flag).  d_V n_items x ld row-major, fp32 or fp64; one streaming
+ * launch, the squares summed in double in a fixed order.  not 0 <= c0 < c1 <= ld, n_items < 0, NULL where needed ->
+ * ERR_INVALID; c1 - c0 > RSPARSE_HIP_MAX_RANK -> ERR_UNSUPPORTED. */
+int rsparse_hip_item_inv_norms_device(const float* d_V, int n_items, int ld, int c0, int c1, double* d_inv, void* stream);
+int rsparse_hip_item_inv_norms_f64_device(const double* d_V, int n_items, int ld, int c0, int c1, double* d_inv, void* stream);
+
+/* Intra-list distance.  With u_j = V[j, c0 : c1) d_inv[j] (a unit vector; items with d_inv = 0 are skipped like invalid ones):
+ *   counted[u, t]   = #{valid, non-degenerate positions i <= c_t} = m  (int32)
+ *   diversity[u, t] = the mean over the pairs i < j of those positions of 1 - <u_i, u_j>; NaN where m < 2
+ * computed as 1 - (|S|^2 - m) / (m (m - 1)) with S the sum of the m unit vectors, accumulated in double from the factors AS
+ * STORED (r sizeof(T) bytes and one double gathered per position) in an order that depends on (k, cutoffs, c1 - c0) alone: a
+ * repeated call returns the same bits.  It differs from the pairwise form by at most about 2 (2 m + r) 2^-53.  d_inv must be what
+ * rsparse_hip_item_inv_norms*_device made of the same d_V, c0, c1.  Outputs n_users x n_cutoffs row-major, either nullable.
+ * Status codes as rsparse_hip_list_metrics_device, and those of rsparse_hip_item_inv_norms*_device for c0 / c1 / ld. */
+int rsparse_hip_list_diversity_device(const int32_t* d_predictions, int n_users, int k, const int32_t* cutoffs, int n_cutoffs,
+                                      const float* d_V, int n_items, int ld, int c0, int c1, const double* d_inv,
+                                      int32_t* d_counted, double* d_diversity, void* stream);
+int rsparse_hip_list_diversity_f64_device(const int32_t* d_predictions, int n_users, int k, const int32_t* cutoffs,
+                                          int n_cutoffs, const double* d_V, int n_items, int ld, int c0, int c1,
+                                          const double* d_inv, int32_t* d_counted, double* d_diversity, void* stream);
+
+/* host forms: predictions n_users x k column-major, V n_items x ld row-major (= R's ld x n_items components) on the host, the
+ * outputs n_users x n_cutoffs COLUMN-major; the norms are made by the call. */
+int rsparse_hip_list_diversity(const int32_t* predictions, int n_users, int k, const int32_t* cutoffs, int n_cutoffs,
+                               const float* V, int n_items, int ld, int c0, int c1, int32_t* counted, double* diversity);
+int rsparse_hip_list_diversity_f64(const int32_t* predictions, int n_users, int k, const int32_t* cutoffs, int n_cutoffs,
+                                   const double* V, int n_items, int ld, int c0, int c1, int32_t* counted, double* diversity);
+
+/* ------------------------------------------------------------------------------------------------
  * full-ranking metrics: where the held-out items stand among ALL items -- the expected percentile rank of
  * Hu, Koren and Volinsky (the measure of the method's own paper), AUC and MRR off the same per-item ranks
  * ---------------------------------------------------------------------------------------------- */

@@ -80,6 +80,16 @@ SIGNATURES = {
     "rsparse_hip_hit_metrics_device": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int,
                                                 _vp]),
     "rsparse_hip_hit_metrics": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int]),
+    "rsparse_hip_list_metrics_device": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_list_metrics": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_item_inv_norms_device": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    "rsparse_hip_item_inv_norms_f64_device": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    "rsparse_hip_list_diversity_device": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp,
+                                                   _vp]),
+    "rsparse_hip_list_diversity_f64_device": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp,
+                                                       _vp, _vp]),
+    "rsparse_hip_list_diversity": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    "rsparse_hip_list_diversity_f64": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "rsparse_hip_held_out_ranks_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _c_int, _vp, _vp,
                                                    _vp, _vp]),
     "rsparse_hip_rank_summary_device": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1499,6 +1499,221 @@ int rsparse_hip_hit_metrics(const int32_t* pred, int n_users, int k, const int32
 }
 
 namespace {
+// the lists and cutoffs that every entry of the beyond-accuracy metrics checks before anything else (the rules of hit_metrics_args)
+int list_args(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, bool any_output, int n_items) {
+  if (!any_output) return fail(RSPARSE_HIP_ERR_INVALID, "every output is NULL");
+  if (!pred || !cutoffs) return fail(RSPARSE_HIP_ERR_INVALID, "predictions or cutoffs is NULL");
+  if (n_users < 0 || k < 1 || n_cutoffs < 1)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0, k < 1 or n_cutoffs < 1)");
+  if (n_items < 1) return fail(RSPARSE_HIP_ERR_INVALID, "n_items < 1");
+  if (n_cutoffs > RSPARSE_HIP_MAX_CUTOFFS)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 16 cutoffs (RSPARSE_HIP_MAX_CUTOFFS) are not on the device path");
+  if (k > RSPARSE_HIP_MAX_TOPK_LARGE)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
+  for (int t = 0; t < n_cutoffs; t++)
+    if (cutoffs[t] < 1 || cutoffs[t] > k || (t > 0 && cutoffs[t] <= cutoffs[t - 1]))
+      return fail(RSPARSE_HIP_ERR_INVALID, "cutoffs must be strictly ascending within 1 .. k");
+  return RSPARSE_HIP_OK;
+}
+int list_metrics_args(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, const int32_t* item_count,
+                      const int64_t* item_info, int n_items, const void* valid, const void* count_sum, const void* info_sum,
+                      const void* popularity, const void* novelty, const void* exposure) {
+  const bool any = valid || count_sum || info_sum || popularity || novelty || exposure;
+  int rc = list_args(pred, n_users, k, cutoffs, n_cutoffs, any, n_items);
+  if (rc) return rc;
+  if ((count_sum || popularity) && !item_count) return fail(RSPARSE_HIP_ERR_INVALID, "count_sum / popularity need item_count");
+  if ((info_sum || novelty) && !item_info) return fail(RSPARSE_HIP_ERR_INVALID, "info_sum / novelty need item_info");
+  return RSPARSE_HIP_OK;
+}
+// the window of the factors: the rules of normalize_items_args
+int window_args(int n_items, int ld, int c0, int c1) {
+  if (n_items < 0 || c0 < 0 || c1 - c0 < 1 || c1 > ld)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_items < 0 or not 0 <= c0 < c1 <= ld)");
+  if (c1 - c0 > RSPARSE_HIP_MAX_RANK)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 256 latent coordinates are not on the device path");
+  return RSPARSE_HIP_OK;
+}
+int list_diversity_args(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, const void* V, int n_items,
+                        int ld, int c0, int c1, const void* counted, const void* diversity) {
+  int rc = list_args(pred, n_users, k, cutoffs, n_cutoffs, counted || diversity, n_items);
+  if (rc) return rc;
+  if (!V) return fail(RSPARSE_HIP_ERR_INVALID, "the factor matrix is NULL");
+  return window_args(n_items, ld, c0, c1);
+}
+
+int item_inv_norms_device(const void* d_V, bool f64, int n_items, int ld, int c0, int c1, double* d_inv, void* stream) {
+  int rc = window_args(n_items, ld, c0, c1);
+  if (rc) return rc;
+  if (n_items > 0 && (!d_V || !d_inv)) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
+  if (n_items == 0) return RSPARSE_HIP_OK;
+  if ((rc = g_ws.ensure_device())) return rc;
+  hipError_t e = launch_item_inv_norms(d_V, f64, n_items, ld, c0, c1 - c0, d_inv, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_item_inv_norms");
+  return RSPARSE_HIP_OK;
+}
+
+int list_diversity_device(const int32_t* d_pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, const void* d_V, bool f64,
+                          int n_items, int ld, int c0, int c1, const double* d_inv, int32_t* d_counted, double* d_diversity,
+                          void* stream) {
+  int rc = list_diversity_args(d_pred, n_users, k, cutoffs, n_cutoffs, d_V, n_items, ld, c0, c1, d_counted, d_diversity);
+  if (rc) return rc;
+  if (!d_inv) return fail(RSPARSE_HIP_ERR_INVALID, "the inverse norms are NULL");
+  if (n_users == 0) return RSPARSE_HIP_OK;
+  if ((rc = g_ws.ensure_device())) return rc;
+  hipError_t e = launch_list_diversity(d_pred, n_users, k, cutoffs, n_cutoffs, d_V, f64, n_items, ld, c0, c1 - c0, d_inv, d_counted,
+                                       d_diversity, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_list_diversity");
+  return RSPARSE_HIP_OK;
+}
+
+// column-major (R's integer matrix) -> the row-major lists of the device forms
+std::vector<int32_t> lists_row_major(const int32_t* pred, int n_users, int k) {
+  std::vector<int32_t> rows((size_t)n_users * k);
+  for (int c = 0; c < k; c++)
+    for (int u = 0; u < n_users; u++) rows[(size_t)u * k + c] = pred[(size_t)c * n_users + u];
+  return rows;
+}
+// n x T row-major on the device -> a column-major host matrix of 4- or 8-byte elements
+int fetch_col_major(const DevBuf& d, int n_users, int T, void* out, size_t es) {
+  std::vector<char> h((size_t)n_users * T * es);
+  HIP_TRY(hipMemcpy(h.data(), d.p, h.size(), hipMemcpyDeviceToHost));
+  char* o = static_cast<char*>(out);
+  for (int u = 0; u < n_users; u++)
+    for (int t = 0; t < T; t++) std::memcpy(o + ((size_t)t * n_users + u) * es, h.data() + ((size_t)u * T + t) * es, es);
+  return RSPARSE_HIP_OK;
+}
+
+int list_diversity_host(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, const void* V, bool f64,
+                        int n_items, int ld, int c0, int c1, int32_t* counted, double* diversity) {
+  int rc = list_diversity_args(pred, n_users, k, cutoffs, n_cutoffs, V, n_items, ld, c0, c1, counted, diversity);
+  if (rc || n_users == 0) return rc;
+  const int T = n_cutoffs;
+  const size_t nk = (size_t)n_users * k, nt = (size_t)n_users * T, vb = (size_t)n_items * ld * (f64 ? 8 : 4);
+  const std::vector<int32_t> rows = lists_row_major(pred, n_users, k);
+  DevBuf dPred, dV, dInv, dCnt, dDiv;
+  HIP_TRY(dPred.alloc(nk * 4));
+  HIP_TRY(dV.alloc(vb));
+  HIP_TRY(dInv.alloc((size_t)n_items * 8));
+  if (counted) HIP_TRY(dCnt.alloc(nt * 4));
+  if (diversity) HIP_TRY(dDiv.alloc(nt * 8));
+  HIP_TRY(hipMemcpy(dPred.p, rows.data(), nk * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dV.p, V, vb, hipMemcpyHostToDevice));
+  if ((rc = item_inv_norms_device(dV.p, f64, n_items, ld, c0, c1, dInv.as<double>(), nullptr))) return rc;
+  rc = list_diversity_device(dPred.as<int32_t>(), n_users, k, cutoffs, T, dV.p, f64, n_items, ld, c0, c1, dInv.as<double>(),
+                             counted ? dCnt.as<int32_t>() : nullptr, diversity ? dDiv.as<double>() : nullptr, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if (counted && (rc = fetch_col_major(dCnt, n_users, T, counted, sizeof(*counted)))) return rc;
+  if (diversity && (rc = fetch_col_major(dDiv, n_users, T, diversity, sizeof(*diversity)))) return rc;
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+
+int rsparse_hip_list_metrics_device(const int32_t* d_pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs,
+                                    const int32_t* d_item_count, const int64_t* d_item_info, int n_items, int32_t* d_valid,
+                                    int64_t* d_count_sum, int64_t* d_info_sum, double* d_popularity, double* d_novelty,
+                                    int32_t* d_exposure, void* stream) {
+  int rc = list_metrics_args(d_pred, n_users, k, cutoffs, n_cutoffs, d_item_count, d_item_info, n_items, d_valid, d_count_sum,
+                             d_info_sum, d_popularity, d_novelty, d_exposure);
+  if (rc || n_users == 0) return rc;
+  if ((rc = g_ws.ensure_device())) return rc;
+  // (a table that no output needs is not gathered)
+  hipError_t e = launch_list_metrics(d_pred, n_users, k, cutoffs, n_cutoffs, (d_count_sum || d_popularity) ? d_item_count : nullptr,
+                                     (d_info_sum || d_novelty) ? d_item_info : nullptr, n_items, d_valid, d_count_sum, d_info_sum,
+                                     d_popularity, d_novelty, d_exposure, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_list_metrics");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_list_metrics(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs,
+                             const int32_t* item_count, const int64_t* item_info, int n_items, int32_t* valid, int64_t* count_sum,
+                             int64_t* info_sum, double* popularity, double* novelty, int32_t* exposure) {
+  int rc = list_metrics_args(pred, n_users, k, cutoffs, n_cutoffs, item_count, item_info, n_items, valid, count_sum, info_sum,
+                             popularity, novelty, exposure);
+  if (rc) return rc;
+  if (item_count)
+    for (int i = 0; i < n_items; i++)
+      if (item_count[i] < 0) return fail(RSPARSE_HIP_ERR_INVALID, "item_count holds a negative value");
+  if (item_info)
+    for (int i = 0; i < n_items; i++)
+      if (item_info[i] < 0 || item_info[i] >= ((int64_t)1 << 40))
+        return fail(RSPARSE_HIP_ERR_INVALID, "item_info must lie in 0 <= v < 2^40");
+  const int T = n_cutoffs;
+  if (exposure) std::fill(exposure, exposure + (size_t)n_items * T, 0);
+  if (n_users == 0) return RSPARSE_HIP_OK;
+  const size_t nk = (size_t)n_users * k, nt = (size_t)n_users * T, ne = (size_t)n_items * T;
+  const std::vector<int32_t> rows = lists_row_major(pred, n_users, k);
+  const bool use_count = item_count && (count_sum || popularity), use_info = item_info && (info_sum || novelty);
+  DevBuf dPred, dCount, dInfo, dValid, dCs, dIs, dPop, dNov, dExp;
+  HIP_TRY(dPred.alloc(nk * 4));
+  HIP_TRY(hipMemcpy(dPred.p, rows.data(), nk * 4, hipMemcpyHostToDevice));
+  if (use_count) {
+    HIP_TRY(dCount.alloc((size_t)n_items * 4));
+    HIP_TRY(hipMemcpy(dCount.p, item_count, (size_t)n_items * 4, hipMemcpyHostToDevice));
+  }
+  if (use_info) {
+    HIP_TRY(dInfo.alloc((size_t)n_items * 8));
+    HIP_TRY(hipMemcpy(dInfo.p, item_info, (size_t)n_items * 8, hipMemcpyHostToDevice));
+  }
+  if (valid) HIP_TRY(dValid.alloc(nt * 4));
+  if (count_sum) HIP_TRY(dCs.alloc(nt * 8));
+  if (info_sum) HIP_TRY(dIs.alloc(nt * 8));
+  if (popularity) HIP_TRY(dPop.alloc(nt * 8));
+  if (novelty) HIP_TRY(dNov.alloc(nt * 8));
+  if (exposure) {
+    HIP_TRY(dExp.alloc(ne * 4));
+    HIP_TRY(hipMemset(dExp.p, 0, ne * 4));
+  }
+  rc = rsparse_hip_list_metrics_device(dPred.as<int32_t>(), n_users, k, cutoffs, T, use_count ? dCount.as<int32_t>() : nullptr,
+                                       use_info ? dInfo.as<int64_t>() : nullptr, n_items, valid ? dValid.as<int32_t>() : nullptr,
+                                       count_sum ? dCs.as<int64_t>() : nullptr, info_sum ? dIs.as<int64_t>() : nullptr,
+                                       popularity ? dPop.as<double>() : nullptr, novelty ? dNov.as<double>() : nullptr,
+                                       exposure ? dExp.as<int32_t>() : nullptr, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if (valid && (rc = fetch_col_major(dValid, n_users, T, valid, sizeof(*valid)))) return rc;
+  if (count_sum && (rc = fetch_col_major(dCs, n_users, T, count_sum, sizeof(*count_sum)))) return rc;
+  if (info_sum && (rc = fetch_col_major(dIs, n_users, T, info_sum, sizeof(*info_sum)))) return rc;
+  if (popularity && (rc = fetch_col_major(dPop, n_users, T, popularity, sizeof(*popularity)))) return rc;
+  if (novelty && (rc = fetch_col_major(dNov, n_users, T, novelty, sizeof(*novelty)))) return rc;
+  if (exposure) {   // T x n_items per interval -> n_items x T column-major: the same layout, cumulated along the cutoffs
+    HIP_TRY(hipMemcpy(exposure, dExp.p, ne * 4, hipMemcpyDeviceToHost));
+    for (int t = 1; t < T; t++)
+      for (int i = 0; i < n_items; i++) exposure[(size_t)t * n_items + i] += exposure[(size_t)(t - 1) * n_items + i];
+  }
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_item_inv_norms_device(const float* d_V, int n_items, int ld, int c0, int c1, double* d_inv, void* stream) {
+  return item_inv_norms_device(d_V, false, n_items, ld, c0, c1, d_inv, stream);
+}
+int rsparse_hip_item_inv_norms_f64_device(const double* d_V, int n_items, int ld, int c0, int c1, double* d_inv, void* stream) {
+  return item_inv_norms_device(d_V, true, n_items, ld, c0, c1, d_inv, stream);
+}
+
+int rsparse_hip_list_diversity_device(const int32_t* d_pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs,
+                                      const float* d_V, int n_items, int ld, int c0, int c1, const double* d_inv,
+                                      int32_t* d_counted, double* d_diversity, void* stream) {
+  return list_diversity_device(d_pred, n_users, k, cutoffs, n_cutoffs, d_V, false, n_items, ld, c0, c1, d_inv, d_counted, d_diversity,
+                               stream);
+}
+int rsparse_hip_list_diversity_f64_device(const int32_t* d_pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs,
+                                          const double* d_V, int n_items, int ld, int c0, int c1, const double* d_inv,
+                                          int32_t* d_counted, double* d_diversity, void* stream) {
+  return list_diversity_device(d_pred, n_users, k, cutoffs, n_cutoffs, d_V, true, n_items, ld, c0, c1, d_inv, d_counted, d_diversity,
+                               stream);
+}
+
+int rsparse_hip_list_diversity(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, const float* V,
+                               int n_items, int ld, int c0, int c1, int32_t* counted, double* diversity) {
+  return list_diversity_host(pred, n_users, k, cutoffs, n_cutoffs, V, false, n_items, ld, c0, c1, counted, diversity);
+}
+int rsparse_hip_list_diversity_f64(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, const double* V,
+                                   int n_items, int ld, int c0, int c1, int32_t* counted, double* diversity) {
+  return list_diversity_host(pred, n_users, k, cutoffs, n_cutoffs, V, true, n_items, ld, c0, c1, counted, diversity);
+}
+
+namespace {
 // the arguments both forms of rsparse_hip_held_out_ranks check before anything else
 int held_out_ranks_args(const void* U, const void* V, int n_users, int n_items, int rank, int n_exclude, const void* excl,
                         const void* act_p, const void* act_j, int max_chunk_users) {

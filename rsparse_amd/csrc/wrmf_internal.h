@@ -361,6 +361,24 @@ hipError_t launch_hit_metrics(const int32_t* pred, int n_users, int k, const int
                               int n_cutoffs, int32_t* hits, int32_t* first, double* precision, double* recall, double* hit,
                               double* mrr, int32_t* first_seen, int n_items, hipStream_t s);
 
+// beyond-accuracy metrics of the same lists at the same cutoffs (wrmf_lists.hip), one launch and no scratch: valid (int32),
+// count_sum / info_sum (int64), popularity / novelty (double), each n_users x n_cutoffs row-major and nullable.  item_count
+// (int32 of n_items, >= 0) / item_info (int64 of n_items, 0 <= v < 2^40) are gathered only when not null.  exposure (n_cutoffs x
+// n_items int32, nullable, caller-zeroed): += 1 at [b][item] for every valid position of the cutoff INTERVAL b -- the caller
+// cumulates along b.  Items are 1 .. n_items; anything else (NA_integer_ too) is skipped.
+hipError_t launch_list_metrics(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs,
+                               const int32_t* item_count, const int64_t* item_info, int n_items, int32_t* valid, int64_t* count_sum,
+                               int64_t* info_sum, double* popularity, double* novelty, int32_t* exposure, hipStream_t s);
+
+// intra-list cosine distance (wrmf_diversity.hip).  launch_item_inv_norms: inv[item] = 1 / |V[item, c0 : c0 + r)| in double, 0.0
+// for a degenerate item (sum of squares zero or not finite); V fp32, or fp64 when f64, n_items x ld row-major, 1 <= r <= 256.
+// launch_list_diversity: counted (int32) / diversity (double), n_users x n_cutoffs row-major, either nullable, from the
+// factors as stored and that inv.
+hipError_t launch_item_inv_norms(const void* V, bool f64, int n_items, int64_t ld, int c0, int r, double* inv, hipStream_t s);
+hipError_t launch_list_diversity(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, const void* V,
+                                 bool f64, int n_items, int64_t ld, int c0, int r, const double* inv, int32_t* counted,
+                                 double* diversity, hipStream_t s);
+
 // pointwise predictions at a CSR pattern (wrmf_score.hip), T = float or double, 1 <= r <= 256: scores[t] = add + U[row(t)] .
 // V[J[t]] in double for every stored position t < P[n_rows] (the count stays on the device: a capped grid strides over it); then
 // the squared / absolute error sums per row of given scores against `actual` (sse / sae: either may be null)

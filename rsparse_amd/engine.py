@@ -583,6 +583,78 @@ class HipBackend:
             0 if first_seen is None else int(first_seen.numel()), self._stream()))
         return out
 
+    def list_metrics(self, res, cutoffs, n_item, want, item_count=None, item_info=None, exposure=None):
+        """the beyond-accuracy integer metrics of the lists `res` (as for ranking_metrics) at `cutoffs` in one launch
+        (wrmf_lists.hip; rsparse_amd.metrics.list_metrics_reference is the definition): {name: (n, T) tensor on the device} for
+        the names in `want` -- "valid" (int32), "count_sum", "info_sum" (int64), "popularity", "novelty" (float64).  item_count:
+        int32 of n_item on the device (count_sum / popularity), item_info: int64 of n_item (info_sum / novelty).  exposure: int32
+        (T, n_item) on the device, caller-zeroed; it receives the histogram per cutoff INTERVAL (several calls accumulate) and is
+        cumulated along dim 0 by the caller."""
+        known = ("valid", "count_sum", "info_sum", "popularity", "novelty")
+        want = tuple(want)
+        if any(m not in known for m in want) or (not want and exposure is None):
+            raise ValueError("list_metrics: want must name some of %s (or exposure be given)" % ", ".join(known))
+        if ("count_sum" in want or "popularity" in want) and item_count is None:
+            raise ValueError("list_metrics: count_sum / popularity need item_count")
+        if ("info_sum" in want or "novelty" in want) and item_info is None:
+            raise ValueError("list_metrics: info_sum / novelty need item_info")
+        assert res.dtype == torch.int32
+        res = res.contiguous()
+        n, k = res.shape
+        cut = np.ascontiguousarray(np.asarray(list(cutoffs), dtype=np.int32))
+        T = int(cut.size)
+        n_item = int(n_item)
+        assert item_count is None or (item_count.dtype == torch.int32 and item_count.is_contiguous() and item_count.numel() == n_item)
+        assert item_info is None or (item_info.dtype == torch.int64 and item_info.is_contiguous() and item_info.numel() == n_item)
+        assert exposure is None or (exposure.dtype == torch.int32 and exposure.is_contiguous() and tuple(exposure.shape) == (T, n_item))
+        dt = {"valid": torch.int32, "count_sum": torch.int64, "info_sum": torch.int64}
+        out = {m: torch.empty((n, T), dtype=dt.get(m, torch.float64), device=res.device) for m in want}
+        if n == 0:
+            return out
+        ptr = lambda m: out[m].data_ptr() if m in out else None
+        _lib.check(self.lib.rsparse_hip_list_metrics_device(
+            res.data_ptr(), n, k, cut.ctypes.data_as(ctypes.c_void_p), T, None if item_count is None else item_count.data_ptr(),
+            None if item_info is None else item_info.data_ptr(), n_item, ptr("valid"), ptr("count_sum"), ptr("info_sum"),
+            ptr("popularity"), ptr("novelty"), None if exposure is None else exposure.data_ptr(), self._stream()))
+        return out
+
+    def item_inv_norms(self, V, c0, c1):
+        """1 / the Euclidean norm of every row of V over its columns [c0, c1): float64 of n_item on the device, 0.0 for a
+        degenerate item (zero or non-finite norm).  One streaming launch (wrmf_diversity.hip); kept until the matrix changes,
+        keyed and dropped exactly like the cosine operands `normalized_items`."""
+        key = (V._version, int(c0), int(c1))
+        if getattr(self, "_inv_src", None) is not V or self._inv_key != key:
+            assert V.is_contiguous() and V.dim() == 2 and V.dtype in (torch.float32, torch.float64)
+            n, ld = V.shape
+            inv = torch.empty(n, dtype=torch.float64, device=V.device)
+            fn = (self.lib.rsparse_hip_item_inv_norms_f64_device if V.dtype == torch.float64
+                  else self.lib.rsparse_hip_item_inv_norms_device)
+            _lib.check(fn(V.data_ptr(), n, ld, int(c0), int(c1), inv.data_ptr(), self._stream()))
+            self._inv_cache, self._inv_src, self._inv_key = inv, V, key
+        return self._inv_cache
+
+    def list_diversity(self, res, cutoffs, V, c0, c1, want=("counted", "diversity")):
+        """the intra-list cosine distance of the lists `res` (as for ranking_metrics) over the columns [c0, c1) of V (n_item x
+        ld, fp32 or fp64, on the device), at `cutoffs` in one launch (wrmf_diversity.hip; the definition is
+        rsparse_amd.metrics.list_diversity_reference): {"counted": (n, T) int32, "diversity": (n, T) float64} on the device."""
+        want = tuple(want)
+        if not want or any(m not in ("counted", "diversity") for m in want):
+            raise ValueError("list_diversity: want must name 'counted' and / or 'diversity'")
+        assert res.dtype == torch.int32
+        inv = self.item_inv_norms(V, c0, c1)
+        res = res.contiguous()
+        n, k = res.shape
+        cut = np.ascontiguousarray(np.asarray(list(cutoffs), dtype=np.int32))
+        T = int(cut.size)
+        out = {m: torch.empty((n, T), dtype=torch.int32 if m == "counted" else torch.float64, device=res.device) for m in want}
+        if n == 0:
+            return out
+        fn = self.lib.rsparse_hip_list_diversity_f64_device if V.dtype == torch.float64 else self.lib.rsparse_hip_list_diversity_device
+        ptr = lambda m: out[m].data_ptr() if m in out else None
+        _lib.check(fn(res.data_ptr(), n, k, cut.ctypes.data_as(ctypes.c_void_p), T, V.data_ptr(), int(V.shape[0]), int(V.shape[1]),
+                      int(c0), int(c1), inv.data_ptr(), ptr("counted"), ptr("diversity"), self._stream()))
+        return out
+
     def score_pairs(self, U, V, p, j, add=0.0, actual=None, want_scores=True):
         """the model's values at the stored positions of a CSR pattern (p, j: int32 on the device) whose rows are the rows of U
         (n x rank) and whose columns index V (n_item x rank): score[t] = add + U[row(t)] . V[j[t]], accumulated in double from
@@ -709,6 +781,8 @@ class HipBackend:
         self._v32_ver = -1
         self._vn_cache = self._vn_src = None   # the cosine operands derive from the same matrix
         self._vn_key = None
+        self._inv_cache = self._inv_src = None   # ... and so do the inverse norms
+        self._inv_key = None
 
     def normalized_items(self, V, c0, c1):
         """the cosine operands of a factor matrix V (n_item x ld, fp32 or fp64, on the device) over its columns [c0, c1):

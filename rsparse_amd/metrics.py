@@ -20,6 +20,16 @@ Hit-based metrics, which the reference does not have, at up to 16 cutoffs from O
     precision_k / recall_k / hit_rate_k / mrr_k / coverage_k      one metric; a vector for one cutoff, (n, T) for several
     summarize(ev)                                                 the means per cutoff of what `WRMF.evaluate` returns
 
+Beyond-accuracy metrics of the same lists at the same cutoffs (wrmf_lists.hip and wrmf_diversity.hip behind
+`rsparse_hip_list_metrics` / `rsparse_hip_list_diversity`; `WRMF.evaluate(metrics=("popularity", "novelty", "diversity", "gini",
+"entropy"))` runs them on the lists of `predict`):
+
+    list_metrics_reference(predictions, cutoffs, n_item, item_count, item_info)   the DEFINITION, integers only: bit for bit
+    list_diversity_reference(predictions, cutoffs, item_factors, c0, c1)          the DEFINITION of the intra-list distance
+    self_information(item_count)                                                  -log2 of the smoothed item shares, fixed point
+    exposure_summary(exposure)                                                    Gini index and entropy of the exposure counts
+    list_metrics(...) / list_diversity(...)                                       the same on the device
+
 Full-ranking metrics (`WRMF.held_out_ranks` / `WRMF.evaluate_ranks` compute them on the device, wrmf_ranks.hip) have their
 plain-numpy statement here, from a dense score matrix -- the reference the tests hold the kernels to, usable on its own:
 
@@ -264,10 +274,11 @@ def coverage_k(predictions, n_item, cutoffs=None):
 def summarize(ev):
     """The data-set numbers of a dict returned by `WRMF.evaluate`: for every per-row metric the mean over the rows where it is
     defined (NaN rows -- users with nothing held out -- left out; NaN when no row is defined), per cutoff: a float for a vector
-    of n, a (T,) vector for an (n, T) array.  "coverage" is a data-set number already and is passed through."""
+    of n, a (T,) vector for an (n, T) array.  "coverage", "gini" and "entropy" are data-set numbers already and are passed
+    through."""
     out = {}
     for name, v in ev.items():
-        if name == "coverage":
+        if name in ("coverage", "gini", "entropy"):
             out[name] = v
             continue
         v = np.asarray(v, dtype=np.float64)
@@ -277,6 +288,238 @@ def summarize(ev):
             m = np.where(ok, v, 0.0).sum(axis=0) / cnt
         out[name] = float(m) if np.ndim(m) == 0 else m
     return out
+
+
+# ---- beyond-accuracy metrics: the numpy statement of DESIGN.md 3.23 and the device calls -------------------------------------
+LIST_METRICS = ("popularity", "novelty")
+EXPOSURE_METRICS = ("gini", "entropy")
+MAX_RANK = 256          # RSPARSE_HIP_MAX_RANK: latent coordinates of list_diversity
+INFO_LIMIT = 1 << 40    # item_info: fixed point in units of 2^-32, 0 <= v < 2^40 (a sum over 8192 positions stays below 2^53)
+
+
+def _lists(predictions):
+    p = np.asarray(predictions)
+    if p.ndim != 2:
+        raise ValueError("predictions must be a matrix (n x k)")
+    if not np.issubdtype(p.dtype, np.integer):
+        raise TypeError("predictions must hold integer item indices")
+    return p.astype(np.int64, copy=False)
+
+
+def _tables(n_item, item_count, item_info):
+    """the two item tables checked: int32 counts >= 0 and int64 fixed-point values in [0, 2^40), n_item of each (or None)"""
+    n_item = int(n_item)
+    if n_item < 1:
+        raise ValueError("n_item must be at least 1")
+    if item_count is not None:
+        c = np.asarray(item_count)
+        if c.ndim != 1 or c.size != n_item or not np.issubdtype(c.dtype, np.integer):
+            raise ValueError("item_count must be an integer vector of n_item")
+        if c.size and (c.min() < 0 or c.max() > np.iinfo(np.int32).max):
+            raise ValueError("item_count must lie in 0 .. 2^31 - 1")
+        item_count = np.ascontiguousarray(c, dtype=np.int32)
+    if item_info is not None:
+        v = np.asarray(item_info)
+        if v.ndim != 1 or v.size != n_item or not np.issubdtype(v.dtype, np.integer):
+            raise ValueError("item_info must be an integer vector of n_item (fixed point in units of 2^-32)")
+        if v.size and (v.min() < 0 or v.max() >= INFO_LIMIT):
+            raise ValueError("item_info must lie in 0 <= v < 2^40")
+        item_info = np.ascontiguousarray(v, dtype=np.int64)
+    return n_item, item_count, item_info
+
+
+def self_information(item_count):
+    """rint(-log2((cnt_j + 1) / (sum cnt + n_item)) 2^32) as int64: the self-information in bits of the Laplace-smoothed share
+    of interactions of every item, in the fixed point `list_metrics_reference` takes as `item_info`.  Never infinite, at least 0,
+    and below 2^40 for any int32 counts (the share is at least 1 / (n_item 2^31 + n_item) > 2^-63)."""
+    c = np.asarray(item_count)
+    if c.ndim != 1 or c.size < 1 or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError("item_count must be a non-empty integer vector")
+    c = c.astype(np.int64)
+    if c.min() < 0:
+        raise ValueError("item_count must not be negative")
+    total = int(c.sum()) + int(c.size)
+    bits = -np.log2((c + 1).astype(np.float64) / np.float64(total))
+    return np.rint(np.maximum(bits, 0.0) * 4294967296.0).astype(np.int64)
+
+
+def exposure_summary(exposure):
+    """How evenly the lists expose the catalogue, per cutoff, from the integer histogram exposure[t, item] (T x n_item, or one
+    row): {"gini": (T,), "entropy": (T,)}.  Gini = sum_i (2 i - n - 1) e_(i) / (n sum e) over the ascending counts e_(1) <= ... <=
+    e_(n) (0 = every item shown equally often, -> 1 = one item takes everything): numerator and denominator are exact Python
+    integers, one division.  Entropy = the Shannon entropy in bits of e / sum e.  NaN where a cutoff's total is 0."""
+    e = np.atleast_2d(np.asarray(exposure))
+    if e.ndim != 2 or not np.issubdtype(e.dtype, np.integer):
+        raise ValueError("exposure must be an integer (T, n_item) array")
+    T, n = e.shape
+    gini, ent = np.full(T, np.nan), np.full(T, np.nan)
+    for t in range(T):
+        row = np.sort(e[t].astype(np.int64))
+        tot = int(row.sum())
+        if tot <= 0:
+            continue
+        w = 2 * np.arange(1, n + 1, dtype=np.int64) - n - 1
+        if n * float(row[-1]) * n < 2.0 ** 62:
+            num = int(np.dot(w, row))
+        else:
+            num = sum(int(a) * int(b) for a, b in zip(w.tolist(), row.tolist()))
+        gini[t] = num / (n * tot)
+        q = row[row > 0].astype(np.float64) / np.float64(tot)
+        ent[t] = float(-(q * np.log2(q)).sum()) + 0.0
+    return {"gini": gini, "entropy": ent}
+
+
+def list_metrics_reference(predictions, cutoffs, n_item, item_count=None, item_info=None):
+    """The DEFINITION of the popularity, novelty and exposure metrics, integers only, no device.  `predictions` n x k 0-based
+    with -1 where a list is short; `cutoffs` strictly ascending within 1 .. k.  A position is VALID when its item lies in
+    0 .. n_item - 1 (anything else is skipped; a repeated item counts wherever it stands).  Per row u and cutoff c_t:
+        valid[u, t] (int32) = the valid positions i <= c_t
+        count_sum[u, t] (int64) = sum of item_count[item_i] over them       popularity = double(count_sum) / double(valid)
+        info_sum[u, t] (int64) = sum of item_info[item_i] over them         novelty = double(info_sum) / double(valid 2^32)
+    (NaN where valid = 0; what needs a table that is None is left out), and over ALL rows exposure[t, item] (int32) = the valid
+    positions i <= c_t that name the item.  `item_count`: int32 >= 0; `item_info`: int64 fixed point in units of 2^-32,
+    0 <= v < 2^40 (`self_information`).  Every double is one division of two exactly converted integers."""
+    p = _lists(predictions)
+    n, k = p.shape
+    cut = np.asarray(check_cutoffs(cutoffs, k), dtype=np.int64)
+    n_item, item_count, item_info = _tables(n_item, item_count, item_info)
+    T, c_last = cut.size, int(cut[-1])
+    head = p[:, :c_last]
+    ok = (head >= 0) & (head < n_item)
+    safe = np.where(ok, head, 0)
+    zero = np.zeros((n, 1), dtype=np.int64)
+
+    def at_cutoffs(per_position):
+        return np.concatenate([zero, np.cumsum(per_position, axis=1, dtype=np.int64)], axis=1)[:, cut]
+    valid = at_cutoffs(ok).astype(np.int32)
+    out = {"valid": valid}
+    vd = valid.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if item_count is not None:
+            out["count_sum"] = at_cutoffs(np.where(ok, item_count.astype(np.int64)[safe], 0))
+            out["popularity"] = np.where(valid > 0, out["count_sum"].astype(np.float64) / vd, np.nan)
+        if item_info is not None:
+            out["info_sum"] = at_cutoffs(np.where(ok, item_info[safe], 0))
+            out["novelty"] = np.where(valid > 0, out["info_sum"].astype(np.float64) / (vd * 4294967296.0), np.nan)
+    exposure = np.zeros((T, n_item), dtype=np.int32)
+    for t in range(T):
+        m = ok[:, :cut[t]]
+        exposure[t] = np.bincount(head[:, :cut[t]][m], minlength=n_item).astype(np.int32)
+    out["exposure"] = exposure
+    return out
+
+
+def _unit_rows(item_factors, c0, c1):
+    """(unit rows in float64, degenerate flags) of the columns [c0, c1) of a factor matrix: the rule of `similar_items`"""
+    V = np.asarray(item_factors)
+    if V.ndim != 2 or V.dtype not in (np.float32, np.float64):
+        raise ValueError("item_factors must be a float32 or float64 matrix (n_item x rank)")
+    c1 = V.shape[1] if c1 is None else int(c1)
+    c0 = int(c0)
+    if not 0 <= c0 < c1 <= V.shape[1]:
+        raise ValueError("c0 / c1 must satisfy 0 <= c0 < c1 <= columns of item_factors")
+    W = V[:, c0:c1].astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        ss = (W * W).sum(axis=1)
+    bad = ~((ss > 0) & np.isfinite(ss))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        unit = np.where(bad[:, None], 0.0, W / np.sqrt(np.where(bad, 1.0, ss))[:, None])
+    return unit, bad, c0, c1
+
+
+def list_diversity_reference(predictions, cutoffs, item_factors, c0=0, c1=None):
+    """The DEFINITION of the intra-list diversity, float64, no device.  u_j = V[j, c0:c1] / |V[j, c0:c1]| in float64 from the
+    factors as stored; an item whose sum of squares is 0 or not finite is DEGENERATE and its positions are skipped like invalid
+    ones (items outside 0 .. n_item - 1).  Per row u and cutoff c_t:
+        counted[u, t] (int32) = the valid, non-degenerate positions i <= c_t
+        diversity[u, t] = the mean over the pairs i < j of those positions of 1 - <u_i, u_j>      NaN where counted < 2
+    the pairwise form, O(k^2 r) per row.  -> {"counted", "diversity"}, (n, T) each."""
+    p = _lists(predictions)
+    n, k = p.shape
+    cut = np.asarray(check_cutoffs(cutoffs, k), dtype=np.int64)
+    unit, bad, _, _ = _unit_rows(item_factors, c0, c1)
+    n_item = unit.shape[0]
+    T = cut.size
+    counted = np.zeros((n, T), dtype=np.int32)
+    div = np.full((n, T), np.nan)
+    for u in range(n):
+        for t in range(T):
+            it = p[u, :cut[t]]
+            it = it[(it >= 0) & (it < n_item)]
+            it = it[~bad[it]]
+            m = int(it.size)
+            counted[u, t] = m
+            if m >= 2:
+                G = unit[it] @ unit[it].T
+                iu = np.triu_indices(m, 1)
+                div[u, t] = float(np.mean(1.0 - G[iu]))
+    return {"counted": counted, "diversity": div}
+
+
+def list_metrics(predictions, cutoffs, n_item, item_count=None, item_info=None,
+                 metrics=("valid", "count_sum", "info_sum", "popularity", "novelty", "exposure")):
+    """`list_metrics_reference` on the device, one pass over the lists (wrmf_lists.hip behind `rsparse_hip_list_metrics`), equal
+    to it bit for bit.  `metrics` names some of "valid", "count_sum", "info_sum", "popularity", "novelty", "exposure"; names
+    that need a table that is None are left out, as the definition leaves them out.  -> {name: (n, T) array}; exposure (T, n_item)
+    int32.  k <= 8192, at most 16 cutoffs."""
+    known = ("valid", "count_sum", "info_sum", "popularity", "novelty", "exposure")
+    names = tuple(metrics)
+    if not names or any(m not in known for m in names):
+        raise ValueError("metrics must name some of %s" % ", ".join(repr(m) for m in known))
+    pred = _one_based(predictions)
+    n, k = pred.shape
+    if k < 1:
+        raise ValueError("predictions must have at least one column")
+    cut = np.asarray(check_cutoffs(cutoffs, k), dtype=np.int32)
+    n_item, item_count, item_info = _tables(n_item, item_count, item_info)
+    names = tuple(m for m in names if not (m in ("count_sum", "popularity") and item_count is None)
+                  and not (m in ("info_sum", "novelty") and item_info is None))
+    if not names:
+        raise ValueError("every metric asked for needs a table that was not given")
+    T = cut.size
+    if k > MAX_TOPK:
+        raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "k > %d is not on the device path" % MAX_TOPK)
+    dt = {"valid": np.int32, "count_sum": np.int64, "info_sum": np.int64, "exposure": np.int32}
+    out = {m: np.empty((n_item, T) if m == "exposure" else (n, T), dtype=dt.get(m, np.float64), order="F") for m in names}
+    pred = np.asfortranarray(pred)   # R's integer matrix: column-major
+    vp = lambda arr: None if arr is None else arr.ctypes.data_as(ctypes.c_void_p)
+    _lib.check(_lib.load().rsparse_hip_list_metrics(vp(pred), n, k, vp(cut), T, vp(item_count), vp(item_info), n_item,
+                                                    vp(out.get("valid")), vp(out.get("count_sum")), vp(out.get("info_sum")),
+                                                    vp(out.get("popularity")), vp(out.get("novelty")), vp(out.get("exposure"))))
+    return {m: np.ascontiguousarray(v.T if m == "exposure" else v) for m, v in out.items()}
+
+
+def list_diversity(predictions, cutoffs, item_factors, c0=0, c1=None):
+    """`list_diversity_reference` on the device (wrmf_diversity.hip behind `rsparse_hip_list_diversity`): counted exactly,
+    diversity from the sum of the unit vectors, 1 - (|S|^2 - m) / (m (m - 1)), within about 2 (2 m + r) 2^-53 of the pairwise
+    form.  `item_factors`: float32 or float64 (n_item x ld), used as stored; at most 256 columns in [c0, c1)."""
+    pred = _one_based(predictions)
+    n, k = pred.shape
+    if k < 1:
+        raise ValueError("predictions must have at least one column")
+    cut = np.asarray(check_cutoffs(cutoffs, k), dtype=np.int32)
+    V = np.asarray(item_factors)
+    if V.ndim != 2 or V.dtype not in (np.float32, np.float64):
+        raise ValueError("item_factors must be a float32 or float64 matrix (n_item x rank)")
+    V = np.ascontiguousarray(V)
+    n_item, ld = V.shape
+    c1 = ld if c1 is None else int(c1)
+    c0 = int(c0)
+    if n_item < 1 or not 0 <= c0 < c1 <= ld:
+        raise ValueError("c0 / c1 must satisfy 0 <= c0 < c1 <= columns of item_factors")
+    if c1 - c0 > MAX_RANK:
+        raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "more than %d latent coordinates are not on the device path" % MAX_RANK)
+    if k > MAX_TOPK:
+        raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "k > %d is not on the device path" % MAX_TOPK)
+    T = cut.size
+    counted = np.empty((n, T), dtype=np.int32, order="F")
+    div = np.empty((n, T), dtype=np.float64, order="F")
+    pred = np.asfortranarray(pred)
+    vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    lib = _lib.load()
+    fn = lib.rsparse_hip_list_diversity_f64 if V.dtype == np.float64 else lib.rsparse_hip_list_diversity
+    _lib.check(fn(vp(pred), n, k, vp(cut), T, vp(V), n_item, ld, c0, c1, vp(counted), vp(div)))
+    return {"counted": np.ascontiguousarray(counted), "diversity": np.ascontiguousarray(div)}
 
 
 # ---- full-ranking metrics: the numpy statement of DESIGN.md 3.15-------------------------------------------------------------

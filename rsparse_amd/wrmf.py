@@ -764,7 +764,7 @@ class WRMF:
         return torch.from_numpy(res).to(U.device), torch.from_numpy(sc).to(U.device)
 
     def evaluate(self, x, actual, k, not_recommend="x", items_exclude=(), metrics=("ap", "ndcg"), candidates=None, negatives=None,
-                 seed=None, negative_weights=None):
+                 seed=None, negative_weights=None, item_popularity=None):
         """`predict(x, k, ...)` scored against the held-out interactions `actual` (n x anything sparse, relevances as values) by
         the reference's ap_k / ndcg_k (R/metrics.R:31-127) without the lists leaving the device: {name: float64 vector of n}
         for each name in `metrics` ("ap", "ndcg").  Equals `rsparse_amd.metrics.ap_k(self.predict(x, k, ...), actual)` (and
@@ -782,19 +782,44 @@ class WRMF:
         scalar `k` and a (T,) vector for a sequence.  A user with nothing held out is NaN in the four per-row metrics.  "ap" /
         "ndcg" with a sequence score, per cutoff c, the first c places of the top-max(k) list; that equals `evaluate(k=c)`
         except where scores tie exactly at the c-th place, because the reference heap's tie rule depends on k.
-        `rsparse_amd.metrics.summarize` turns the result into data-set means."""
-        from .metrics import HIT_METRICS, NEVER_SEEN, canonical_actual, check_cutoffs
+        `rsparse_amd.metrics.summarize` turns the result into data-set means.
+
+        Beyond accuracy, from the same lists at the same cutoffs (rsparse_amd.metrics.list_metrics_reference and
+        list_diversity_reference are the definitions; wrmf_lists.hip and wrmf_diversity.hip compute them): "popularity" -- the
+        mean of `item_popularity` (an integer vector of n_item, e.g. the column counts of the training matrix) over the items
+        of a list --, "novelty" -- their mean self-information in bits, `rsparse_amd.metrics.self_information(item_popularity)`
+        --, and "diversity" -- the mean cosine distance between the items of a list, over the latent coordinates that
+        `similar_items` uses --, per row like the hit-based metrics (NaN for a list without a valid item, or with fewer than two
+        for "diversity"); "gini" and "entropy" -- how evenly the lists expose the catalogue
+        (`rsparse_amd.metrics.exposure_summary`) -- are data-set numbers like "coverage"."""
+        from .metrics import (EXPOSURE_METRICS, HIT_METRICS, LIST_METRICS, NEVER_SEEN, canonical_actual, check_cutoffs,
+                              exposure_summary, self_information)
         metrics = tuple(metrics)
-        if not metrics or any(m not in ("ap", "ndcg", "coverage") + HIT_METRICS for m in metrics):
-            raise ValueError("metrics must name some of 'ap', 'ndcg', 'precision', 'recall', 'hit', 'mrr', 'coverage'")
+        beyond = LIST_METRICS + ("diversity",) + EXPOSURE_METRICS
+        if not metrics or any(m not in ("ap", "ndcg", "coverage") + HIT_METRICS + beyond for m in metrics):
+            raise ValueError("metrics must name some of 'ap', 'ndcg', 'precision', 'recall', 'hit', 'mrr', 'coverage', "
+                             "'popularity', 'novelty', 'diversity', 'gini', 'entropy'")
         if negatives is not None and candidates is not None:
             raise ValueError("negatives and candidates exclude each other: the negatives ARE the candidates")
         if negative_weights is not None and negatives is None:
             raise ValueError("negative_weights needs negatives: they weight the sampled negatives")
         scalar_k = not isinstance(k, (tuple, list, np.ndarray, range))
         hit_names = tuple(m for m in HIT_METRICS if m in metrics)
+        list_names = tuple(m for m in LIST_METRICS if m in metrics)
+        want_exposure = any(m in metrics for m in EXPOSURE_METRICS)
+        item_count = item_info = None
+        if list_names:
+            if item_popularity is None:
+                raise ValueError("'popularity' and 'novelty' need item_popularity: an integer vector of n_item")
+            item_count = np.asarray(item_popularity)
+            if item_count.ndim != 1 or not np.issubdtype(item_count.dtype, np.integer) or item_count.size != np.shape(x)[1]:
+                raise ValueError("item_popularity must be an integer vector of n_item")
+            if item_count.size and (item_count.min() < 0 or item_count.max() > np.iinfo(np.int32).max):
+                raise ValueError("item_popularity must lie in 0 .. 2^31 - 1")
+            if "novelty" in metrics:
+                item_info = self_information(item_count)
         cutoffs = None
-        if not scalar_k or hit_names or "coverage" in metrics:
+        if not scalar_k or hit_names or "coverage" in metrics or any(m in beyond for m in metrics):
             cutoffs = check_cutoffs((int(k),) if scalar_k else k)
             k = cutoffs[-1]
         x = sp.csr_matrix(x, dtype=np.float64)
@@ -827,6 +852,21 @@ class WRMF:
             fn = be.hit_metrics if hasattr(be, "hit_metrics") else self._hit_metrics_host
             got = fn(res, d_p, d_j, cutoffs, hit_names, first_seen)
             out.update({m: (got[m][:, 0] if scalar_k else got[m]) for m in hit_names})
+        exposure = None
+        if list_names or want_exposure:
+            n_item = int(self._V.shape[0])
+            if want_exposure:
+                exposure = torch.zeros((len(cutoffs), n_item), dtype=torch.int32, device=res.device)
+            d_cnt = be.to_device(item_count, torch.int32) if "popularity" in metrics else None
+            d_info = be.to_device(item_info, torch.int64) if "novelty" in metrics else None
+            fn = be.list_metrics if hasattr(be, "list_metrics") else self._list_metrics_host
+            got = fn(res, cutoffs, n_item, list_names, d_cnt, d_info, exposure)
+            out.update({m: (got[m][:, 0] if scalar_k else got[m]) for m in list_names})
+        if "diversity" in metrics:
+            c0, c1 = (1, self._rank - 1) if self._with_bias else (0, self._rank)   # the latent columns, as similar_items
+            fn = be.list_diversity if hasattr(be, "list_diversity") else self._list_diversity_host
+            got = fn(res, cutoffs, self._V, c0, c1, ("diversity",))
+            out["diversity"] = got["diversity"][:, 0] if scalar_k else got["diversity"]
         for name in [m for m in out if m not in metrics]:
             del out[name]
         for name, v in out.items():
@@ -842,7 +882,36 @@ class WRMF:
             reached = (first_seen[None, :] <= cut[:, None]).sum(dim=1).cpu().numpy().astype(np.int64)
             cov = reached / np.int64(first_seen.numel())
             out["coverage"] = float(cov[0]) if scalar_k else cov
-        return {m: out[m] for m in ("ap", "ndcg") + HIT_METRICS + ("coverage",) if m in metrics}
+        if want_exposure:   # the ranks' histograms added, the cutoff intervals cumulated, then summarised
+            if ws > 1:
+                from .engine import all_reduce_any
+                import torch.distributed as dist
+                all_reduce_any(exposure, self._group, op=dist.ReduceOp.SUM)
+            summ = exposure_summary(torch.cumsum(exposure.to(torch.int64), dim=0).cpu().numpy())
+            for m in EXPOSURE_METRICS:
+                out[m] = float(summ[m][0]) if scalar_k else summ[m]
+        return {m: out[m] for m in ("ap", "ndcg") + HIT_METRICS + ("coverage",) + beyond if m in metrics}
+
+    @staticmethod
+    def _list_metrics_host(res, cutoffs, n_item, want, item_count=None, item_info=None, exposure=None):
+        """`list_metrics` for a backend without it (the CPU stand-in of the tests): the numpy statement,
+        rsparse_amd.metrics.list_metrics_reference, on the 1-based lists; exposure receives the histogram per cutoff interval."""
+        from .metrics import list_metrics_reference
+        pred0 = res.cpu().numpy().astype(np.int64) - 1          # (NA_integer_ and 0 turn negative: skipped)
+        ref = list_metrics_reference(pred0, cutoffs, n_item, None if item_count is None else item_count.cpu().numpy(),
+                                     None if item_info is None else item_info.cpu().numpy())
+        if exposure is not None:
+            step = np.diff(ref["exposure"].astype(np.int64), axis=0, prepend=0).astype(np.int32)
+            exposure.add_(torch.from_numpy(step).to(exposure.device))
+        return {m: torch.from_numpy(ref[m]).to(res.device) for m in want}
+
+    @staticmethod
+    def _list_diversity_host(res, cutoffs, V, c0, c1, want=("counted", "diversity")):
+        """`list_diversity` for a backend without it: the numpy statement, rsparse_amd.metrics.list_diversity_reference"""
+        from .metrics import list_diversity_reference
+        pred0 = res.cpu().numpy().astype(np.int64) - 1
+        ref = list_diversity_reference(pred0, cutoffs, V.cpu().numpy(), c0, c1)
+        return {m: torch.from_numpy(ref[m]).to(res.device) for m in want}
 
     @staticmethod
     def _hit_metrics_host(res, p, j, cutoffs, want, first_seen=None):
