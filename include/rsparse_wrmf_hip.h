@@ -572,6 +572,48 @@ int rsparse_hip_list_diversity_f64(const int32_t* predictions, int n_users, int 
                                    const double* V, int n_items, int ld, int c0, int c1, int32_t* counted, double* diversity);
 
 /* ------------------------------------------------------------------------------------------------
+ * MMR re-ranking: a pool of n_pool ranked positions per user (what rsparse_hip_top_product*_device / top_candidates*_device
+ * write: 1-based items with NA_integer_, double scores) greedily re-ranked down to k for relevance AND dissimilarity.  The
+ * reference package has nothing like it: `mmr_reference` of rsparse_amd/metrics.py is the definition.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* A position is VALID when its item lies in 1 .. n_items and its score is finite; a repeated item is a position of its own.
+ * With u_i = V[item_i, c0 : c1) d_inv[item_i] in double (the zero vector where d_inv is 0: a degenerate item), and over the valid
+ * positions of a row rel_i = (s_i - s_min) / (s_max - s_min) (all 0 where s_max == s_min), step t = 0, 1, .. picks the valid,
+ * untaken position that maximises
+ *   (1 - trade_off) rel_i - trade_off max_{j picked} <u_i, u_j>        (the max over nothing is 0)
+ * -- the LOWER position wins a tie -- until k are picked or no valid position is left.  One workgroup per user runs the k steps;
+ * the dot products are accumulated in double from the factors AS STORED in an order that depends on c1 - c0 alone, so the
+ * objective of a position depends only on the bits of its row, its score and the set already picked: exact ties are exact, a
+ * repeated call returns the same bits, no atomics.  Every pick maximises the definition's objective along the call's own path
+ * to within about (c1 - c0 + 8) 2^-53.
+ *   d_items[u, t]      the item picked at step t, 1-based; NA_integer_ where fewer than k positions are valid  (int32)
+ *   d_scores_out[u, t] its own score s_i; NaN there                                                            (double)
+ *   d_positions[u, t]  its position in the pool, 1-based; NA_integer_ there                                    (int32)
+ *   d_objective[u, t]  the maximised value of step t; NaN there                                                (double)
+ * device form: d_lists / d_scores n_users x n_pool ROW-major, the outputs n_users x k row-major, each nullable except d_items;
+ * d_inv must be what rsparse_hip_item_inv_norms*_device made of the same d_V, c0, c1.  Enqueued on `stream`, no
+ * synchronisation, no workspace.  All before a device is touched: NULL lists, scores, V, inverse norms or d_items, n_users < 0,
+ * k < 1, k > n_pool, trade_off outside [0, 1] or not finite, n_items < 1, not 0 <= c0 < c1 <= ld -> ERR_INVALID; n_pool >
+ * RSPARSE_HIP_MAX_TOPK_LARGE or c1 - c0 > RSPARSE_HIP_MAX_RANK -> ERR_UNSUPPORTED; n_users == 0 -> OK. */
+int rsparse_hip_mmr_rerank_device(const int32_t* d_lists, const double* d_scores, int n_users, int n_pool, int k, double trade_off,
+                                  const float* d_V, int n_items, int ld, int c0, int c1, const double* d_inv, int32_t* d_items,
+                                  double* d_scores_out, int32_t* d_positions, double* d_objective, void* stream);
+int rsparse_hip_mmr_rerank_f64_device(const int32_t* d_lists, const double* d_scores, int n_users, int n_pool, int k,
+                                      double trade_off, const double* d_V, int n_items, int ld, int c0, int c1, const double* d_inv,
+                                      int32_t* d_items, double* d_scores_out, int32_t* d_positions, double* d_objective,
+                                      void* stream);
+
+/* host forms: lists / scores n_users x n_pool column-major, V n_items x ld row-major (= R's ld x n_items components) on the
+ * host, the outputs n_users x k COLUMN-major; the norms are made by the call. */
+int rsparse_hip_mmr_rerank(const int32_t* lists, const double* scores, int n_users, int n_pool, int k, double trade_off,
+                           const float* V, int n_items, int ld, int c0, int c1, int32_t* items, double* scores_out,
+                           int32_t* positions, double* objective);
+int rsparse_hip_mmr_rerank_f64(const int32_t* lists, const double* scores, int n_users, int n_pool, int k, double trade_off,
+                               const double* V, int n_items, int ld, int c0, int c1, int32_t* items, double* scores_out,
+                               int32_t* positions, double* objective);
+
+/* ------------------------------------------------------------------------------------------------
  * full-ranking metrics: where the held-out items stand among ALL items -- the expected percentile rank of
  * Hu, Koren and Volinsky (the measure of the method's own paper), AUC and MRR off the same per-item ranks
  * ---------------------------------------------------------------------------------------------- */

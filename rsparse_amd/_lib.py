@@ -90,6 +90,10 @@ SIGNATURES = {
                                                        _vp, _vp]),
     "rsparse_hip_list_diversity": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "rsparse_hip_list_diversity_f64": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    "rsparse_hip_mmr_rerank_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_mmr_rerank_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_mmr_rerank": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_mmr_rerank_f64": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp]),
     "rsparse_hip_held_out_ranks_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _c_int, _vp, _vp,
                                                    _vp, _vp]),
     "rsparse_hip_rank_summary_device": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

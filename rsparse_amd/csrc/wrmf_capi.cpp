@@ -1714,6 +1714,98 @@ int rsparse_hip_list_diversity_f64(const int32_t* pred, int n_users, int k, cons
 }
 
 namespace {
+// what both forms of the MMR re-ranking check before anything else
+int mmr_rerank_args(const int32_t* lists, const double* scores, int n_users, int n_pool, int k, double trade_off, const void* V,
+                    int n_items, int ld, int c0, int c1, const void* items) {
+  if (!lists || !scores) return fail(RSPARSE_HIP_ERR_INVALID, "lists or scores is NULL");
+  if (!V) return fail(RSPARSE_HIP_ERR_INVALID, "the factor matrix is NULL");
+  if (!items) return fail(RSPARSE_HIP_ERR_INVALID, "the items output is NULL");
+  if (n_users < 0 || n_pool < 1 || k < 1 || k > n_pool)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0 or not 1 <= k <= n_pool)");
+  if (!(trade_off >= 0.0 && trade_off <= 1.0)) return fail(RSPARSE_HIP_ERR_INVALID, "trade_off must lie in [0, 1]");   // (NaN too)
+  if (n_items < 1) return fail(RSPARSE_HIP_ERR_INVALID, "n_items < 1");
+  if (n_pool > RSPARSE_HIP_MAX_TOPK_LARGE)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "a pool of more than 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
+  return window_args(n_items, ld, c0, c1);
+}
+
+int mmr_rerank_device(const int32_t* d_lists, const double* d_scores, int n_users, int n_pool, int k, double trade_off, const void* d_V,
+                      bool f64, int n_items, int ld, int c0, int c1, const double* d_inv, int32_t* d_items, double* d_picked,
+                      int32_t* d_positions, double* d_objective, void* stream) {
+  int rc = mmr_rerank_args(d_lists, d_scores, n_users, n_pool, k, trade_off, d_V, n_items, ld, c0, c1, d_items);
+  if (rc) return rc;
+  if (!d_inv) return fail(RSPARSE_HIP_ERR_INVALID, "the inverse norms are NULL");
+  if (n_users == 0) return RSPARSE_HIP_OK;
+  if ((rc = g_ws.ensure_device())) return rc;
+  hipError_t e = launch_mmr_rerank(d_lists, d_scores, n_users, n_pool, k, trade_off, d_V, f64, n_items, ld, c0, c1 - c0, d_inv, d_items,
+                                   d_picked, d_positions, d_objective, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_mmr_rerank");
+  return RSPARSE_HIP_OK;
+}
+
+int mmr_rerank_host(const int32_t* lists, const double* scores, int n_users, int n_pool, int k, double trade_off, const void* V,
+                    bool f64, int n_items, int ld, int c0, int c1, int32_t* items, double* picked, int32_t* positions,
+                    double* objective) {
+  int rc = mmr_rerank_args(lists, scores, n_users, n_pool, k, trade_off, V, n_items, ld, c0, c1, items);
+  if (rc || n_users == 0) return rc;
+  const size_t nn = (size_t)n_users * n_pool, nk = (size_t)n_users * k, vb = (size_t)n_items * ld * (f64 ? 8 : 4);
+  const std::vector<int32_t> rows = lists_row_major(lists, n_users, n_pool);
+  std::vector<double> srows(nn);
+  for (int c = 0; c < n_pool; c++)
+    for (int u = 0; u < n_users; u++) srows[(size_t)u * n_pool + c] = scores[(size_t)c * n_users + u];
+  DevBuf dLists, dScores, dV, dInv, dItems, dPicked, dPos, dObj;
+  HIP_TRY(dLists.alloc(nn * 4));
+  HIP_TRY(dScores.alloc(nn * 8));
+  HIP_TRY(dV.alloc(vb));
+  HIP_TRY(dInv.alloc((size_t)n_items * 8));
+  HIP_TRY(dItems.alloc(nk * 4));
+  if (picked) HIP_TRY(dPicked.alloc(nk * 8));
+  if (positions) HIP_TRY(dPos.alloc(nk * 4));
+  if (objective) HIP_TRY(dObj.alloc(nk * 8));
+  HIP_TRY(hipMemcpy(dLists.p, rows.data(), nn * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dScores.p, srows.data(), nn * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dV.p, V, vb, hipMemcpyHostToDevice));
+  if ((rc = item_inv_norms_device(dV.p, f64, n_items, ld, c0, c1, dInv.as<double>(), nullptr))) return rc;
+  rc = mmr_rerank_device(dLists.as<int32_t>(), dScores.as<double>(), n_users, n_pool, k, trade_off, dV.p, f64, n_items, ld, c0, c1,
+                         dInv.as<double>(), dItems.as<int32_t>(), picked ? dPicked.as<double>() : nullptr,
+                         positions ? dPos.as<int32_t>() : nullptr, objective ? dObj.as<double>() : nullptr, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if ((rc = fetch_col_major(dItems, n_users, k, items, sizeof(*items)))) return rc;
+  if (picked && (rc = fetch_col_major(dPicked, n_users, k, picked, sizeof(*picked)))) return rc;
+  if (positions && (rc = fetch_col_major(dPos, n_users, k, positions, sizeof(*positions)))) return rc;
+  if (objective && (rc = fetch_col_major(dObj, n_users, k, objective, sizeof(*objective)))) return rc;
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+
+int rsparse_hip_mmr_rerank_device(const int32_t* d_lists, const double* d_scores, int n_users, int n_pool, int k, double trade_off,
+                                  const float* d_V, int n_items, int ld, int c0, int c1, const double* d_inv, int32_t* d_items,
+                                  double* d_scores_out, int32_t* d_positions, double* d_objective, void* stream) {
+  return mmr_rerank_device(d_lists, d_scores, n_users, n_pool, k, trade_off, d_V, false, n_items, ld, c0, c1, d_inv, d_items,
+                           d_scores_out, d_positions, d_objective, stream);
+}
+int rsparse_hip_mmr_rerank_f64_device(const int32_t* d_lists, const double* d_scores, int n_users, int n_pool, int k,
+                                      double trade_off, const double* d_V, int n_items, int ld, int c0, int c1, const double* d_inv,
+                                      int32_t* d_items, double* d_scores_out, int32_t* d_positions, double* d_objective,
+                                      void* stream) {
+  return mmr_rerank_device(d_lists, d_scores, n_users, n_pool, k, trade_off, d_V, true, n_items, ld, c0, c1, d_inv, d_items,
+                           d_scores_out, d_positions, d_objective, stream);
+}
+int rsparse_hip_mmr_rerank(const int32_t* lists, const double* scores, int n_users, int n_pool, int k, double trade_off,
+                           const float* V, int n_items, int ld, int c0, int c1, int32_t* items, double* scores_out,
+                           int32_t* positions, double* objective) {
+  return mmr_rerank_host(lists, scores, n_users, n_pool, k, trade_off, V, false, n_items, ld, c0, c1, items, scores_out, positions,
+                         objective);
+}
+int rsparse_hip_mmr_rerank_f64(const int32_t* lists, const double* scores, int n_users, int n_pool, int k, double trade_off,
+                               const double* V, int n_items, int ld, int c0, int c1, int32_t* items, double* scores_out,
+                               int32_t* positions, double* objective) {
+  return mmr_rerank_host(lists, scores, n_users, n_pool, k, trade_off, V, true, n_items, ld, c0, c1, items, scores_out, positions,
+                         objective);
+}
+
+namespace {
 // the arguments both forms of rsparse_hip_held_out_ranks check before anything else
 int held_out_ranks_args(const void* U, const void* V, int n_users, int n_items, int rank, int n_exclude, const void* excl,
                         const void* act_p, const void* act_j, int max_chunk_users) {

@@ -379,6 +379,14 @@ hipError_t launch_list_diversity(const int32_t* pred, int n_users, int k, const 
                                  bool f64, int n_items, int64_t ld, int c0, int r, const double* inv, int32_t* counted,
                                  double* diversity, hipStream_t s);
 
+// greedy MMR re-ranking of a pool of n_pool positions per user down to k (wrmf_mmr.hip; 1 <= k <= n_pool <= 8192, 1 <= r <= 256,
+// 0 <= theta <= 1).  lists (1-based, INT32_MIN = NA) / scores: n_users x n_pool row-major; V and inv as for launch_list_diversity.
+// items (1-based, NA-padded), picked (the picks' own scores), positions (1-based into the pool), objective: n_users x k
+// row-major, NaN / NA where fewer than k positions are valid; each nullable except items.
+hipError_t launch_mmr_rerank(const int32_t* lists, const double* scores, int n_users, int n_pool, int k, double theta, const void* V,
+                             bool f64, int n_items, int64_t ld, int c0, int r, const double* inv, int32_t* items, double* picked,
+                             int32_t* positions, double* objective, hipStream_t s);
+
 // pointwise predictions at a CSR pattern (wrmf_score.hip), T = float or double, 1 <= r <= 256: scores[t] = add + U[row(t)] .
 // V[J[t]] in double for every stored position t < P[n_rows] (the count stays on the device: a capped grid strides over it); then
 // the squared / absolute error sums per row of given scores against `actual` (sse / sae: either may be null)

@@ -655,6 +655,30 @@ class HipBackend:
                       int(c0), int(c1), inv.data_ptr(), ptr("counted"), ptr("diversity"), self._stream()))
         return out
 
+    def mmr_rerank(self, res, sc, V, c0, c1, k, trade_off, want=("scores", "positions", "objective")):
+        """the greedy MMR re-ranking of the pools `res` / `sc` (n x N: int32 1-based with NA_integer_ and float64, on the device,
+        as top_product / top_candidates write them) down to k over the columns [c0, c1) of V (n_item x ld, fp32 or fp64, on the
+        device), one launch (wrmf_mmr.hip; the definition is rsparse_amd.metrics.mmr_reference): {"items": (n, k) int32 1-based
+        and NA-padded, and of `want`: "scores" (the picks' own scores, float64, NaN where NA), "positions" (int32, 1-based into
+        the pool), "objective" (float64)} on the device."""
+        want = tuple(want)
+        if any(m not in ("scores", "positions", "objective") for m in want):
+            raise ValueError("mmr_rerank: want may name 'scores', 'positions' and 'objective'")
+        assert res.dtype == torch.int32 and sc.dtype == torch.float64 and res.shape == sc.shape and res.dim() == 2
+        inv = self.item_inv_norms(V, c0, c1)
+        res, sc = res.contiguous(), sc.contiguous()
+        n, N = res.shape
+        k = int(k)
+        out = {m: torch.empty((n, k), dtype=torch.float64 if m in ("scores", "objective") else torch.int32, device=res.device)
+               for m in ("items",) + want}
+        if n == 0:
+            return out
+        fn = self.lib.rsparse_hip_mmr_rerank_f64_device if V.dtype == torch.float64 else self.lib.rsparse_hip_mmr_rerank_device
+        ptr = lambda m: out[m].data_ptr() if m in out else None
+        _lib.check(fn(res.data_ptr(), sc.data_ptr(), n, N, k, float(trade_off), V.data_ptr(), int(V.shape[0]), int(V.shape[1]), int(c0),
+                      int(c1), inv.data_ptr(), ptr("items"), ptr("scores"), ptr("positions"), ptr("objective"), self._stream()))
+        return out
+
     def score_pairs(self, U, V, p, j, add=0.0, actual=None, want_scores=True):
         """the model's values at the stored positions of a CSR pattern (p, j: int32 on the device) whose rows are the rows of U
         (n x rank) and whose columns index V (n_item x rank): score[t] = add + U[row(t)] . V[j[t]], accumulated in double from

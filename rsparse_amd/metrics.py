@@ -30,6 +30,12 @@ Beyond-accuracy metrics of the same lists at the same cutoffs (wrmf_lists.hip an
     exposure_summary(exposure)                                                    Gini index and entropy of the exposure counts
     list_metrics(...) / list_diversity(...)                                       the same on the device
 
+MMR re-ranking of a pool of ranked items per row down to k (wrmf_mmr.hip behind `rsparse_hip_mmr_rerank`;
+`WRMF.predict(diversify=)` / `WRMF.evaluate(diversify=)` run it on the pools of `predict`):
+
+    mmr_reference(predictions, scores, k, trade_off, item_factors, c0, c1)        the DEFINITION of the greedy re-ranking
+    mmr_rerank(...)                                                               the same on the device
+
 Full-ranking metrics (`WRMF.held_out_ranks` / `WRMF.evaluate_ranks` compute them on the device, wrmf_ranks.hip) have their
 plain-numpy statement here, from a dense score matrix -- the reference the tests hold the kernels to, usable on its own:
 
@@ -520,6 +526,115 @@ def list_diversity(predictions, cutoffs, item_factors, c0=0, c1=None):
     fn = lib.rsparse_hip_list_diversity_f64 if V.dtype == np.float64 else lib.rsparse_hip_list_diversity
     _lib.check(fn(vp(pred), n, k, vp(cut), T, vp(V), n_item, ld, c0, c1, vp(counted), vp(div)))
     return {"counted": np.ascontiguousarray(counted), "diversity": np.ascontiguousarray(div)}
+
+
+# ---- MMR re-ranking of the lists: the numpy statement of DESIGN.md 3.24 and the device call ---------------------------------
+def check_trade_off(trade_off, what="trade_off"):
+    """the MMR weight as a float in [0, 1]: anything else (NaN, a bool, not a number) is a ValueError"""
+    if isinstance(trade_off, bool) or not isinstance(trade_off, (int, float, np.integer, np.floating)):
+        raise ValueError("%s must be a number in [0, 1]" % what)
+    t = float(trade_off)
+    if not 0.0 <= t <= 1.0:   # (a NaN fails both)
+        raise ValueError("%s must be a number in [0, 1]" % what)
+    return t
+
+
+def _mmr_args(predictions, scores, k, trade_off):
+    p = _lists(predictions)
+    s = np.asarray(scores)
+    if s.shape != p.shape or s.dtype.kind != "f":
+        raise ValueError("scores must be a floating-point matrix of the shape of predictions")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= p.shape[1]:
+        raise ValueError("k must be an integer in 1 .. the width of the lists")
+    return p, s.astype(np.float64), int(k), check_trade_off(trade_off)
+
+
+def mmr_reference(predictions, scores, k, trade_off, item_factors, c0=0, c1=None):
+    """The DEFINITION of the greedy Maximal-Marginal-Relevance re-ranking of a pool of N positions per row down to k, float64,
+    no device.  `predictions` n x N 0-based (-1 where a list is short) with their `scores` (n x N); theta = `trade_off` in [0, 1].
+    A position is VALID when its item lies in 0 .. n_item - 1 and its score is finite; a repeated item is a position of its own.
+    inv_j = 1 / sqrt(sum of squares of V[j, c0:c1]) in float64 from the factors as stored, 0.0 for a DEGENERATE item (sum zero or
+    not finite); u_j = V[j, c0:c1] inv_j, the zero vector for a degenerate item.  Per row, over its valid positions:
+        rel_i = (s_i - s_min) / (s_max - s_min)                        all 0 where s_max == s_min
+        step t = 0, 1, ..: pick the valid, untaken position that maximises
+            (1 - theta) rel_i - theta max_{j picked} <u_i, u_j>        the max over nothing is 0; the LOWER position wins a tie
+    until k are picked or no valid position is left.  -> {"items": (n, k) int64, -1 where nothing was picked, "positions":
+    (n, k) int64 into the pool, -1 likewise, "objective": (n, k) float64, the maximised value of every step, NaN likewise}.
+    theta = 0 returns the first k valid positions of a list sorted by score; the result for k is the k-prefix of the result for
+    any larger k; two positions with bit-identical factor rows and equal scores tie exactly."""
+    p, s, k, theta = _mmr_args(predictions, scores, k, trade_off)
+    V = np.asarray(item_factors)
+    if V.ndim != 2 or V.dtype not in (np.float32, np.float64):
+        raise ValueError("item_factors must be a float32 or float64 matrix (n_item x rank)")
+    c1 = V.shape[1] if c1 is None else int(c1)
+    c0 = int(c0)
+    if not 0 <= c0 < c1 <= V.shape[1]:
+        raise ValueError("c0 / c1 must satisfy 0 <= c0 < c1 <= columns of item_factors")
+    n, N = p.shape
+    n_item = V.shape[0]
+    items = np.full((n, k), -1, dtype=np.int64)
+    positions = np.full((n, k), -1, dtype=np.int64)
+    objective = np.full((n, k), np.nan)
+    for u in range(n):
+        ok = (p[u] >= 0) & (p[u] < n_item) & np.isfinite(s[u])
+        if not ok.any():
+            continue
+        it = np.where(ok, p[u], 0)
+        W = V[it, c0:c1].astype(np.float64)
+        with np.errstate(all="ignore"):
+            ss = (W * W).sum(axis=1)
+            good = (ss > 0) & np.isfinite(ss)
+            inv = np.where(good, 1.0 / np.sqrt(np.where(good, ss, 1.0)), 0.0)
+            unit = np.where(good[:, None], W * inv[:, None], 0.0)
+            s_min, s_max = s[u][ok].min(), s[u][ok].max()
+            rel = np.where(ok, (s[u] - s_min) / (s_max - s_min), 0.0) if s_max != s_min else np.zeros(N)
+        lead = (1.0 - theta) * rel
+        free = ok.copy()
+        sim = np.zeros(N)                        # the max over nothing
+        for t in range(min(k, int(ok.sum()))):
+            obj = np.where(free, lead - theta * sim, -np.inf)
+            i = int(np.argmax(obj))              # (the first of equal maxima: the lower position)
+            items[u, t], positions[u, t], objective[u, t] = p[u, i], i, obj[i]
+            free[i] = False
+            dots = (unit * unit[i]).sum(axis=1)   # (every row summed in the same order: equal rows give equal bits)
+            sim = dots if t == 0 else np.maximum(sim, dots)
+    return {"items": items, "positions": positions, "objective": objective}
+
+
+def mmr_rerank(predictions, scores, k, trade_off, item_factors, c0=0, c1=None):
+    """`mmr_reference` on the device (wrmf_mmr.hip behind `rsparse_hip_mmr_rerank`): one workgroup per row runs the k dependent
+    steps with the dot products accumulated in double from the factors as stored.  Every pick maximises the definition's
+    objective along the device's own path to within about (r + 8) 2^-53; exact ties go to the lower position.
+    -> {"items", "positions" (int64, -1 where nothing was picked), "scores" (the picks' own scores), "objective" (float64, NaN
+    likewise)}.  `item_factors`: float32 or float64 (n_item x ld), used as stored; N <= 8192, at most 256 columns in [c0, c1)."""
+    _, s, k, theta = _mmr_args(predictions, scores, k, trade_off)
+    pred = _one_based(predictions)
+    n, N = pred.shape
+    V = np.asarray(item_factors)
+    if V.ndim != 2 or V.dtype not in (np.float32, np.float64):
+        raise ValueError("item_factors must be a float32 or float64 matrix (n_item x rank)")
+    V = np.ascontiguousarray(V)
+    n_item, ld = V.shape
+    c1 = ld if c1 is None else int(c1)
+    c0 = int(c0)
+    if n_item < 1 or not 0 <= c0 < c1 <= ld:
+        raise ValueError("c0 / c1 must satisfy 0 <= c0 < c1 <= columns of item_factors")
+    if c1 - c0 > MAX_RANK:
+        raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "more than %d latent coordinates are not on the device path" % MAX_RANK)
+    if N > MAX_TOPK:
+        raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "a pool of more than %d is not on the device path" % MAX_TOPK)
+    pred, s = np.asfortranarray(pred), np.asfortranarray(s)
+    items = np.empty((n, k), dtype=np.int32, order="F")
+    pos = np.empty((n, k), dtype=np.int32, order="F")
+    picked = np.empty((n, k), dtype=np.float64, order="F")
+    obj = np.empty((n, k), dtype=np.float64, order="F")
+    vp = lambda arr: arr.ctypes.data_as(ctypes.c_void_p)
+    lib = _lib.load()
+    fn = lib.rsparse_hip_mmr_rerank_f64 if V.dtype == np.float64 else lib.rsparse_hip_mmr_rerank
+    _lib.check(fn(vp(pred), vp(s), n, N, k, theta, vp(V), n_item, ld, c0, c1, vp(items), vp(picked), vp(pos), vp(obj)))
+    zero_based = lambda a: np.ascontiguousarray(np.where(a == NA_INTEGER, -1, a.astype(np.int64) - 1))
+    return {"items": zero_based(items), "positions": zero_based(pos), "scores": np.ascontiguousarray(picked),
+            "objective": np.ascontiguousarray(obj)}
 
 
 # ---- full-ranking metrics: the numpy statement of DESIGN.md 3.15-------------------------------------------------------------

@@ -36,8 +36,10 @@ def _identity(x):
 
 class TopItems(np.ndarray):
     """Result of `WRMF.predict`: (n_users x k) item indices with the scores attached, like the `scores`
-    attribute of the reference's integer matrix (R/MatrixFactorizationRecommender.R:68-76)."""
+    attribute of the reference's integer matrix (R/MatrixFactorizationRecommender.R:68-76).  `objective`: with
+    `predict(diversify=)` the value every pick maximised (n_users x k float64, NaN where nothing was picked), else None."""
     scores = None
+    objective = None
 
 
 class Explanation:
@@ -620,7 +622,7 @@ class WRMF:
         self._check_numeric()   # (collective when the model shards: _transform_device runs it on every rank)
         return res
 
-    def predict(self, x, k, not_recommend="x", items_exclude=(), candidates=None):
+    def predict(self, x, k, not_recommend="x", items_exclude=(), candidates=None, diversify=None, pool=None):
         """R/MatrixFactorizationRecommender.R:24-34 -> find_top_product (R/utils.R:31-59): embeddings of the
         rows of `x` by `transform`, then the k best items per row on the device, skipping each row's
         `not_recommend` entries (default: `x` itself, as in the reference; None = nothing) and the globally
@@ -634,16 +636,74 @@ class WRMF:
         slice of the catalogue per user: the result is what the call returns when every item outside the row's candidates is
         added to its not_recommend row, computed from the candidates alone (work and memory follow their number, not n x
         n_item).  The scores are those of `score` at the same cells, the order is by exactly these doubles, ties as in the
-        reference; 1 <= k <= 8192."""
-        res, sc, x = self._predict_device(x, k, not_recommend, items_exclude, candidates)
+        reference; 1 <= k <= 8192.
+
+        `diversify` = theta in [0, 1] re-ranks every row's top-`pool` down to k by greedy Maximal Marginal Relevance on the
+        device (wrmf_mmr.hip; rsparse_amd.metrics.mmr_reference is the definition): step by step the position that maximises
+        (1 - theta) rel - theta (its largest cosine to the items already picked), rel the pool's scores brought into [0, 1], the
+        cosines over the latent coordinates that the "diversity" metric of `evaluate` uses.  `pool` defaults to min(10 k, 8192,
+        n_item) -- and to k where that is smaller (k above n_item: the lists are NA-padded as without `diversify`) -- and must
+        lie in k .. 8192; `candidates`, `not_recommend` and `items_exclude` shape the pool as they shape the
+        plain lists.  `.scores` then holds the model's scores of the picks (no longer descending) and `.objective` the maximised
+        values; theta = 0 returns the items of the plain call.  None (the default): the plain call, nothing else runs."""
+        div = self._diversify_args(k, diversify, pool)
+        obj = None
+        if div is None:
+            res, sc, x = self._predict_device(x, k, not_recommend, items_exclude, candidates)
+        else:
+            res, sc, x, obj = self._predict_device(x, k, not_recommend, items_exclude, candidates, diversify=div)
         n_new = x.shape[0]
         if self._dist()[0] > 1:
             res, sc = self._share_rows(res, self._row_bounds, n_new), self._share_rows(sc, self._row_bounds, n_new)
+            if obj is not None:
+                obj = self._share_rows(obj, self._row_bounds, n_new)
         idx = res.cpu().numpy().astype(np.int64)
         idx = np.where(idx == -2147483648, -1, idx - 1)       # R is 1-based with NA_integer_
         out = idx.view(TopItems)
         out.scores = sc.cpu().numpy().astype(self._np_dtype())
+        if obj is not None:
+            out.objective = obj.cpu().numpy()
         return out
+
+    def _diversify_args(self, k, diversify, pool):
+        """the checks of `diversify` / `pool` -> None (no re-ranking) or (theta, pool)"""
+        if diversify is None:
+            if pool is not None:
+                raise ValueError("pool needs diversify: it is the number of ranked items the re-ranking chooses from")
+            return None
+        from .metrics import check_trade_off
+        theta = check_trade_off(diversify, "diversify")
+        if self._V is None:
+            raise RuntimeError("model is not fitted")
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be at least 1")
+        if pool is None:   # (at least k: k > n_item ranks at k and pads with NA, as the plain call does)
+            pool = max(k, min(10 * k, 8192, int(self._V.shape[0])))
+        elif isinstance(pool, bool) or not isinstance(pool, (int, np.integer)):
+            raise ValueError("pool must be an integer in k .. 8192")
+        if not k <= int(pool) <= 8192:   # RSPARSE_HIP_MAX_TOPK_LARGE
+            raise ValueError("pool must be an integer in k .. 8192")
+        return theta, int(pool)
+
+    def _latent_window(self):
+        """the columns [c0, c1) of the item factors that are latent coordinates (the bias columns left out), as similar_items"""
+        return (1, self._rank - 1) if self._with_bias else (0, self._rank)
+
+    @staticmethod
+    def _mmr_rerank_host(res, sc, V, c0, c1, k, trade_off, want=("scores", "positions", "objective")):
+        """`mmr_rerank` for a backend without it (the CPU stand-in of the tests): the numpy statement,
+        rsparse_amd.metrics.mmr_reference, on the 1-based pools"""
+        from .metrics import NA_INTEGER, mmr_reference
+        pred0 = res.cpu().numpy().astype(np.int64) - 1          # (NA_integer_ and 0 turn negative: invalid)
+        s = sc.cpu().numpy().astype(np.float64)
+        ref = mmr_reference(pred0, s, k, trade_off, V.cpu().numpy(), c0, c1)
+        pos = ref["positions"]
+        none = pos < 0
+        one_based = lambda a: np.where(none, NA_INTEGER, a + 1).astype(np.int32)
+        out = {"items": one_based(ref["items"]), "positions": one_based(pos), "objective": ref["objective"],
+               "scores": np.where(none, np.nan, np.take_along_axis(s, np.where(none, 0, pos), axis=1))}
+        return {m: torch.from_numpy(np.ascontiguousarray(out[m])).to(res.device) for m in ("items",) + tuple(want)}
 
     def _exclusion_args(self, x, not_recommend, items_exclude, n_item=None):
         """the checks `predict` makes of its exclusions (x: CSR, n x n_item) -> (items_exclude sorted and unique,
@@ -675,11 +735,12 @@ class WRMF:
         d_ex = be.to_device(excl, torch.int32) if excl.size else None
         return nr_p, nr_j, d_ex
 
-    def _predict_device(self, x, k, not_recommend, items_exclude, candidates=None, negatives=None):
+    def _predict_device(self, x, k, not_recommend, items_exclude, candidates=None, negatives=None, diversify=None):
         """the device part of `predict`: (indices int32, scores float64) of this rank's block of rows, _row_bounds[rank], still
         on the device -- 1-based with NA_integer_ as top_product writes them --, and x as CSR.  negatives = (n, seed, actual as
         canonical CSR, uint32 item weights or None): the candidates are sampled here (`sample_negatives`), batch by batch, and
-        never leave the device."""
+        never leave the device.  diversify = (theta, pool): the rows are ranked at `pool` and re-ranked to k (`_diversify_args`);
+        the result is then (indices, scores of the picks, x, objective)."""
         if self._V is None:
             raise RuntimeError("model is not fitted")
         x = sp.csr_matrix(x, dtype=np.float64)
@@ -687,6 +748,9 @@ class WRMF:
         if x.shape[1] != n_item:
             raise ValueError("ncol(x) == ncol(self$components) is not TRUE")
         k = int(k)
+        k_out = k
+        if diversify is not None:
+            k = diversify[1]                        # ranked at the pool's width, re-ranked to k_out below
         cand = None
         if candidates is not None or negatives is not None:
             if candidates is not None:
@@ -724,6 +788,11 @@ class WRMF:
         else:
             res = torch.empty((0, k), dtype=torch.int32, device=emb.device)
             sc = torch.empty((0, k), dtype=torch.float64, device=emb.device)
+        if diversify is not None:   # per row: every rank re-ranks the block it ranked
+            c0, c1 = self._latent_window()
+            fn = be.mmr_rerank if hasattr(be, "mmr_rerank") else self._mmr_rerank_host
+            got = fn(res, sc.to(torch.float64), self._V, c0, c1, k_out, diversify[0], ("scores", "objective"))
+            return got["items"], got["scores"], x, got["objective"]
         return res, sc, x
 
     @staticmethod
@@ -764,7 +833,7 @@ class WRMF:
         return torch.from_numpy(res).to(U.device), torch.from_numpy(sc).to(U.device)
 
     def evaluate(self, x, actual, k, not_recommend="x", items_exclude=(), metrics=("ap", "ndcg"), candidates=None, negatives=None,
-                 seed=None, negative_weights=None, item_popularity=None):
+                 seed=None, negative_weights=None, item_popularity=None, diversify=None, pool=None):
         """`predict(x, k, ...)` scored against the held-out interactions `actual` (n x anything sparse, relevances as values) by
         the reference's ap_k / ndcg_k (R/metrics.R:31-127) without the lists leaving the device: {name: float64 vector of n}
         for each name in `metrics` ("ap", "ndcg").  Equals `rsparse_amd.metrics.ap_k(self.predict(x, k, ...), actual)` (and
@@ -791,7 +860,11 @@ class WRMF:
         --, and "diversity" -- the mean cosine distance between the items of a list, over the latent coordinates that
         `similar_items` uses --, per row like the hit-based metrics (NaN for a list without a valid item, or with fewer than two
         for "diversity"); "gini" and "entropy" -- how evenly the lists expose the catalogue
-        (`rsparse_amd.metrics.exposure_summary`) -- are data-set numbers like "coverage"."""
+        (`rsparse_amd.metrics.exposure_summary`) -- are data-set numbers like "coverage".
+
+        `diversify` / `pool`: as in `predict` -- ONE MMR re-ranking of the top-`pool` at max(k), whose prefixes are the re-ranked
+        lists of the smaller cutoffs, and every metric, "diversity" included, is computed on the re-ranked lists; with
+        `negatives` / `candidates` the pool is the candidates' top-`pool`."""
         from .metrics import (EXPOSURE_METRICS, HIT_METRICS, LIST_METRICS, NEVER_SEEN, canonical_actual, check_cutoffs,
                               exposure_summary, self_information)
         metrics = tuple(metrics)
@@ -828,7 +901,8 @@ class WRMF:
         neg = None
         if negatives is not None:
             neg = (self._negatives_count(negatives), seed, act, self._negatives_weights(negative_weights, x.shape[1]))
-        res, _, x = self._predict_device(x, k, not_recommend, items_exclude, candidates, neg)
+        div = self._diversify_args(k, diversify, pool)
+        res, _, x = self._predict_device(x, k, not_recommend, items_exclude, candidates, neg, diversify=div)[:3]
         ws, me = self._dist()
         a, b = self._row_bounds[me]
         mine = act[a:b]
@@ -863,7 +937,7 @@ class WRMF:
             got = fn(res, cutoffs, n_item, list_names, d_cnt, d_info, exposure)
             out.update({m: (got[m][:, 0] if scalar_k else got[m]) for m in list_names})
         if "diversity" in metrics:
-            c0, c1 = (1, self._rank - 1) if self._with_bias else (0, self._rank)   # the latent columns, as similar_items
+            c0, c1 = self._latent_window()
             fn = be.list_diversity if hasattr(be, "list_diversity") else self._list_diversity_host
             got = fn(res, cutoffs, self._V, c0, c1, ("diversity",))
             out["diversity"] = got["diversity"][:, 0] if scalar_k else got["diversity"]
