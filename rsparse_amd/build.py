@@ -38,6 +38,8 @@ REG_LIMIT = {"wrmf_cg_mf.hip": 512}   # (one wave per SIMD by design: 320 accumu
 # gathered vectors; a spilling form loses 2x): their compilation reports its resource usage and the build fails
 # when one of them spills, uses scratch or passes 256 registers -- another compiler may allocate differently.
 NO_SPILL = {"wrmf_cgq.hip": ("14als_cgq_kernelILi128ELi24ELi4ELi4E",),
+            # four rows per wave: 128 registers of gathered vectors beside four rows' CG state
+            "wrmf_cgp.hip": ("14als_cgp_kernelILb0ELb1ELi16ELb1E",),
             # the tile a thread assembles and factors stays in registers from the first chunk to the last pivot
             "wrmf_explain.hip": ("14explain_kernelIfLi128E",),
             # integer-only, about two dozen registers: scratch here would mean the draw loop lost its registers

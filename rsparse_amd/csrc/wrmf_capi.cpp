@@ -356,6 +356,7 @@ int run_half_iteration(const rsparse_hip_csc* conf, bool implicit, const float* 
   qs.team4_first = (implicit && bias && bias->gbias != 0.f) ? d.q_off[2] : d.q_team4_first;
   qs.team4_wide_first = (implicit && bias && bias->gbias != 0.f) ? d.q_off[2] : d.q_team4_wide_first;
   qs.pair_wide = cgp_wide_supported(rank, implicit, implicit && bias && bias->gbias != 0.f);
+  qs.pair_quad = cgp_quad_supported(rank, implicit, implicit && bias && bias->gbias != 0.f);
   // round 6, rank 128, implicit conjugate gradient without bias operands: the rows of 513..kCgMfMax non-zeros of the first bucket on
   // the wave-per-row kernel of wrmf_cg_mf.hip, the giant rows (a prefix of the order) on the normal-equation kernel's second lists
   const bool cg_mf = cgq && implicit && !bias && cg_mf_supported(rank, implicit) && d.q_order && d.q_off[1] > d.q_n_nec;

@@ -1,4 +1,4 @@
-// CG half-iteration for the SHORT rows (at most 16 or 32 non-zeros, and empty ones), two rows per wave (gfx950, wave64).
+// CG half-iteration for the SHORT rows (at most 16 or 32 non-zeros, and empty ones), two or four rows per wave (gfx950, wave64).
 //
 // Same arithmetic as als_cgq_kernel (wrmf_cgq.hip: cg_solver_implicit<T>, inst/include/wrmf_implicit.hpp:8-32, column loop
 // :160-283; with a global bias cg_solver_implicit_global_bias, :35-57).  Half of the rows of the <= 32 bucket of the bench
@@ -22,6 +22,21 @@
 // confidences are not prefetched into registers but copied by LDS-DMA into one of two LDS slots of the wave (one
 // global_load_lds_dword each for the 64 entries of the two rows), from which the row switch reads the indices and the sweeps
 // the confidences.
+//
+// QUAD (rows of at most 16 non-zeros, rank 128, no global bias; NQ = 16): FOUR rows per wave, one 16-lane group per row.  Slot q
+// (q = 0..15) of the group holds non-zero q of its row, 128 registers of vectors as above; CG state, row id, pointers, alpha,
+// beta and the convergence flag are per-lane values that are uniform inside a GROUP.  There is no cross-group sum (pair_sum
+// and its lane swaps are not instantiated), t_acc / t_cur take 16 slots per group, and a block of four quads is skipped when
+// none of the wave's four rows reaches it.  The workgroup's SIXTEEN rows are the 16 columns of the matrix-core tile -- the same
+// 24 instructions per wave and sweep serve twice the rows; each group publishes both pieces of its vector and folds its own
+// column.  G in LDS and the indices / confidences of the next four rows by LDS-DMA as with NQ = 16 (lane l copies entry l & 15
+// of its group's row).  LDS is what decides the layout: two workgroups per CU leave 81 920 B each, G's fragments (64 KB), the
+// index slots (4 KB) and t_acc / t_cur (2 KB) leave 10 224 B, and sixteen published columns (8704 B) beside sixteen columns of
+// products (8448 B) do not fit.  So column c's products lie OVER column c's two published terms: every wave reads all its B
+// operands right after the barrier that follows the publish, a second barrier directly behind it (the waves are still aligned)
+// frees the bytes for the products, and the next sweep's publish overwrites only what the same lanes folded (PairSmem<16, true>:
+// 80 400 B).  The addresses of a sweep are formed from an opaque copy of the lane number: kept across the row loop they cost a
+// dozen registers and 8 spilled ones (245 registers, no spill, no scratch; rsparse_amd/build.py NO_SPILL).
 #include "wrmf_internal.h"
 #include "wrmf_device.h"
 
@@ -32,32 +47,45 @@ using namespace dev;
 
 constexpr int kPairMaxSweeps = 4;
 
-template <int NQ>
+template <int NQ, bool QUAD = false>
 struct PairSmem {
-  static constexpr int KP = 128, ps = KP + 8, os = KP + 4;
+  static constexpr int KP = 128, ps = KP + 8, os = QUAD ? KP + 8 : KP + 4;
+  static constexpr int cols = QUAD ? 16 : 8;        // live columns of the 16-column tile = rows of the workgroup
+  static constexpr int pcs = QUAD ? 2 * ps : ps;    // halfs from one published column to the next
   static constexpr size_t gfrag = NQ == 16 ? (size_t)4 * 16 * 1024 : 0;   // G's fp16 fragments (NQ = 16)
   static constexpr size_t nxt = NQ == 16 ? (size_t)4 * 2 * 2 * 64 * 4 : 0;   // NQ = 16: [wave][slot][index, value][64]
-  static constexpr size_t bytes = gfrag + (size_t)2 * 8 * ps * 2 + (size_t)8 * os * 4 + (size_t)4 * 8 * NQ * 4 + nxt + 16;
+  static constexpr size_t pub = (size_t)2 * cols * ps * 2, out = (size_t)cols * os * 4;
+  // QUAD: column c's products (os floats) lie over column c's two published terms (2 ps halfs): see the kernel's sweep
+  static_assert(!QUAD || (pub == out && (size_t)pcs * 2 == (size_t)os * 4), "QUAD: one column, one stretch of LDS");
+  static constexpr size_t bytes = gfrag + (QUAD ? pub : pub + out) + (size_t)4 * 8 * NQ * 4 + nxt + 16;
 };
+// two workgroups per CU (what hides the gather) leave 80 KB each
+static_assert(PairSmem<16>::bytes <= 81920 && PairSmem<16, true>::bytes <= 81920, "two workgroups per CU");
 
 // KFULL (rank 128): unconditional vector loads and the warm start requested before them -- the first sweep's publish / dense
 // product run while the vectors are in flight and its quad pass takes them as they arrive (als_cgq_kernel's KFULL)
-template <bool GB, bool KFULL = false, int NQ = 8>
+template <bool GB, bool KFULL = false, int NQ = 8, bool QUAD = false>
 __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_t* __restrict__ rows, int n_rows, int iters,
                                                         size_t loss_slot0) {
   constexpr int KP = 128, RPN = 8, VW = 4, NV = 2;
   static_assert(NQ == 8 || (NQ == 16 && KFULL && !GB), "the 32-slot kernel: rank 128, no global bias");
+  static_assert(!QUAD || NQ == 16, "four rows per wave: 16 slots per group, G in LDS");
   constexpr bool GREG = NQ == 8;   // G's fp16 terms and the prefetched indices in registers (else in LDS)
-  using SM = PairSmem<NQ>;
+  constexpr int RW = QUAD ? 4 : 2, GL = 64 / RW;   // rows per wave, lanes per row
+  constexpr int SS = QUAD ? 1 : 2;                 // a group's slots are gs + SS q
+  using SM = PairSmem<NQ, QUAD>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* sGf = smem + (size_t)(threadIdx.x >> 6) * 16 * 1024;     // NQ = 16: this wave's G fragments, [tile][step][term] x 1 KB
+  // QUAD: [16][2][KP + 8], a column's two terms side by side, and the column's G v in the SAME bytes once the terms are read
   _Float16* sPh = reinterpret_cast<_Float16*>(smem + SM::gfrag); // [8][KP + 8] leading fp16 terms of the published vectors
-  _Float16* sPl = sPh + 8 * SM::ps;                             // [8][KP + 8] second terms
-  float* sOut = reinterpret_cast<float*>(sPl + 8 * SM::ps);     // [8][KP + 4] G v (times the scales)
-  float* sTsv = sOut + 8 * SM::os;                              // [4][2][2 NQ]  x_j . y accumulated / of the current step
+  _Float16* sPl = QUAD ? sPh + SM::ps : sPh + 8 * SM::ps;       // [8][KP + 8] second terms
+  float* sOut = QUAD ? reinterpret_cast<float*>(sPh) : reinterpret_cast<float*>(sPl + 8 * SM::ps);   // [8][KP + 4] G v (times the scales)
+  float* sTsv = QUAD ? reinterpret_cast<float*>(sPh + 16 * SM::pcs) : sOut + 8 * SM::os;   // [4][2][2 NQ]  x_j . y accumulated / of the current step
   float* sNx = sTsv + 4 * 8 * NQ + (threadIdx.x >> 6) * 256;     // NQ = 16: this wave's [2][index, value][64]
   const int tid = threadIdx.x, lane = tid & 63, wv = rfl(tid >> 6);
   const int g = lane >> 4, i = lane & 15, H = lane >> 5, g2 = g & 1;
+  const int R = QUAD ? g : H;     // this lane's row of the wave's RW
+  const int gs = QUAD ? 0 : g2;   // this group's first slot
   const int k = KFULL ? KP : a.k;
   const float gbias = GB ? a.gbias : 0.f, ltgt = GB ? a.loss_tgt_const : 1.f;
   for (int e = tid; e < 4 * 8 * NQ; e += 256) sTsv[e] = 0.f;
@@ -111,15 +139,15 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
       }
   }
   __syncthreads();
-  float* tacc = sTsv + wv * 8 * NQ + 2 * NQ * H;   // this half's 2 NQ slots: x_j . y accumulated over the CG steps
+  float* tacc = sTsv + wv * 8 * NQ + (QUAD ? NQ * g : 2 * NQ * H);   // this half's 2 NQ (QUAD: this group's NQ) slots: x_j . y accumulated over the CG steps
   float* tcur = tacc + 4 * NQ;                     // ... x_j . p of the current step
   // the slot whose x_j . y this lane holds for the loss: group 0 slots 0..15, with NQ = 16 group 1 slots 16..31
-  const int lslot = NQ == 16 ? i + 16 * g2 : i;
+  const int lslot = (NQ == 16 && !QUAD) ? i + 16 * g2 : i;
   const bool lgrp = NQ == 16 || g2 == 0;
-  const int col = 2 * wv + H;              // this half's column of the shared dense product
+  const int col = RW * wv + R;             // this row's column of the shared dense product
   double wloss = 0.0;
   const int wave_global = blockIdx.x * 4 + wv, total_waves = gridDim.x * 4;
-  auto ridx = [&](const int itn) { return (wave_global + itn * total_waves) * 2 + H; };   // position in `rows`, per half
+  auto ridx = [&](const int itn) { return (wave_global + itn * total_waves) * RW + R; };   // position in `rows`, per half (QUAD: per group)
   // row ids run two iterations ahead, pointers one ahead (per-lane values, uniform inside a half)
   int row_c = 0, p1_c = 0, p2_c = 0, row_n = 0;
   if (iters > 0 && ridx(0) < n_rows) {
@@ -140,10 +168,11 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
     idn[q] = 0;
     cvn[q] = 0.f;
   }
-  // NQ = 16: lane l copies entry l & 31 of its half's row into slot `buf` (entries beyond the row: index 0, confidence 0)
+  // NQ = 16: lane l copies entry l & 31 of its half's row (QUAD: l & 15 of its group's) into slot `buf` (entries beyond the row:
+  // index 0, confidence 0)
   auto request_indices = [&](const bool valid, const int np1, const int ncnt, const int buf) {
     if constexpr (!GREG) {
-      const int e = lane & 31;
+      const int e = lane & (GL - 1);
       const bool in = valid && e < ncnt;
       float* slot = sNx + buf * 128;
       dma4(in ? static_cast<const void*>(a.row_idx + np1 + e) : static_cast<const void*>(a.zero_row), (unsigned)rfl((int)lds_addr(slot)));
@@ -195,12 +224,19 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
     float* yrow = a.Y + (size_t)row * k;
     const bool live = have && (GB || cnt > 0);
     if (have && !live) {  // empty column -> zeros (wrmf_implicit.hpp:281); the 32 lanes of the half write it
-      for (int e = lane & 31; e < k; e += 32) yrow[e] = 0.f;
+      if constexpr (QUAD) {   // (the group's 16 lanes, as they store a solution)
+#pragma unroll
+        for (int b = 0; b < NV; b++) *reinterpret_cast<float4*>(yrow + b * 16 * VW + i * VW) = make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {
+        for (int e = lane & 31; e < k; e += 32) yrow[e] = 0.f;
+      }
     }
     // the longer of the wave's two rows (wave-uniform): block b of four quads (slots 8 b .. 8 b + 7) is touched only when it
     // reaches the block; the first block always is
-    const int wcnt = max(__builtin_amdgcn_readlane(cnt, 0), __builtin_amdgcn_readlane(cnt, 32));
-    auto blk_on = [&](const int q) { return q < 4 || wcnt > 2 * (q & ~3); };
+    // (QUAD: the longest of the four; block b is slots 4 b .. 4 b + 3 of every group)
+    int wcnt = max(__builtin_amdgcn_readlane(cnt, 0), __builtin_amdgcn_readlane(cnt, 32));
+    if constexpr (QUAD) wcnt = max(wcnt, max(__builtin_amdgcn_readlane(cnt, 16), __builtin_amdgcn_readlane(cnt, 48)));
+    auto blk_on = [&](const int q) { return q < 4 || wcnt > SS * (q & ~3); };
 
     float x[RPN], r[RPN], p[RPN], ap[RPN];
     auto load_warm_start = [&]() {
@@ -217,7 +253,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
     if constexpr (KFULL) load_warm_start();
     // ---- gather: all index loads, then all vector loads; slots beyond the row read the zero row and carry c = 0 ----
     float xt[NQ][RPN], cv[GREG ? NQ : 1];
-    const float* nx = sNx + (it & 1) * 128 + 32 * H;   // NQ = 16: this half's indices (nx[s]) / confidences (nx[64 + s])
+    const float* nx = sNx + (it & 1) * 128 + (QUAD ? 16 * g : 32 * H);   // NQ = 16: this row's indices (nx[s]) / confidences (nx[64 + s])
     {
       // (the loads WITHOUT a per-lane predicate: `in ? load : 0` compiles to a branch per slot with the address arithmetic of
       //  the vector load -- and its wait for the index -- inside: up to eight index round trips one after the other per pair of
@@ -226,7 +262,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
 #pragma unroll
       for (int q = 0; q < NQ; q++) {
         if constexpr (!GREG) {
-          id[q] = __float_as_int(nx[2 * q + g2]);
+          id[q] = __float_as_int(QUAD ? nx[q] : nx[2 * q + g2]);
         } else if constexpr (KFULL) {
           id[q] = idn[q];
           cv[q] = cvn[q];
@@ -243,13 +279,13 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
       }
 #pragma unroll
       for (int q = 0; q < NQ; q++) {
-        const bool in = 2 * q + g2 < cnt;
+        const bool in = SS * q + gs < cnt;
         id[q] = in ? id[q] : 0;
         if constexpr (GREG) cv[q] = in ? cv[q] : 0.f;
       }
 #pragma unroll
       for (int q = 0; q < NQ; q++) {
-        const bool in = 2 * q + g2 < cnt;
+        const bool in = SS * q + gs < cnt;
         const float* src = in ? a.X + (size_t)id[q] * k : a.zero_row;
 #pragma unroll
         for (int b = 0; b < NV; b++) {
@@ -286,6 +322,10 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
 #pragma unroll
       for (int rr = 0; rr < RPN; rr++) acc[rr] = 0.f;
       float vinv = 0.f;
+      // QUAD: the sweep's per-lane LDS addresses are formed here from an opaque copy of the lane number -- left to the compiler
+      // they are formed once per launch and sit in a dozen registers across the row loop, which the kernel does not have
+      const int ln = opaque_lane<QUAD>(lane), li = ln & 15, lg = ln >> 4;
+      const int lcol = QUAD ? RW * wv + lg : col;
       if (mode != 2) {
         // (1) publish v as two fp16 terms of v * 2^ve: group g2 publishes piece g2 (elements [64 g2 + 4 i, + 4))
         float vmax = 0.f;
@@ -295,7 +335,20 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
         const int ve = fp16_scale_exp(vmax);
         const float vs = __uint_as_float((unsigned)ve << 23);
         vinv = __uint_as_float((unsigned)(254 - ve) << 23) * (mode == 0 ? -1.f : 1.f);
-        {
+        if constexpr (QUAD) {
+          // the group publishes both pieces of its row's vector.  The column's bytes held its G v until this group folded it
+          // (below): same lanes, LDS in order -- the fence only keeps the compiler from moving the stores up
+          wave_sync();
+#pragma unroll
+          for (int b = 0; b < NV; b++) {
+            unsigned h0, l0, h1, l1;
+            split_f16(v[b * VW] * vs, v[b * VW + 1] * vs, h0, l0);
+            split_f16(v[b * VW + 2] * vs, v[b * VW + 3] * vs, h1, l1);
+            const int off = lcol * SM::pcs + b * 16 * VW + li * VW;
+            *reinterpret_cast<uint2*>(sPh + off) = make_uint2(h0, h1);
+            *reinterpret_cast<uint2*>(sPl + off) = make_uint2(l0, l1);
+          }
+        } else {
           float w4[VW];
 #pragma unroll
           for (int c = 0; c < VW; c++) w4[c] = (g2 == 0 ? v[c] : v[VW + c]) * vs;
@@ -307,15 +360,32 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
           *reinterpret_cast<uint2*>(sPl + off) = make_uint2(l0, l1);
         }
         __syncthreads();
-        // (2) this wave's 32 rows of G against the eight vectors (columns 8..15 of the tile repeat them)
+        // (2) this wave's 32 rows of G against the eight vectors (columns 8..15 of the tile repeat them; QUAD: against sixteen)
         f32x4 d0[2], d1[2];
 #pragma unroll
         for (int t = 0; t < 2; t++) d0[t] = d1[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int nb = (lane & 7) * SM::ps + 8 * (lane >> 4);
+        const int nb = QUAD ? li * SM::pcs + 8 * lg : (lane & 7) * SM::ps + 8 * (lane >> 4);
+        // QUAD: every wave takes all its B operands first (the waves are still aligned from the barrier above); behind the second
+        // barrier the columns' bytes take the products
+        f16x8 bhs[QUAD ? 4 : 1], bls[QUAD ? 4 : 1];
+        if constexpr (QUAD) {
+#pragma unroll
+          for (int ks = 0; ks < 4; ks++) {
+            bhs[ks] = *reinterpret_cast<const f16x8*>(sPh + nb + 32 * ks);
+            bls[ks] = *reinterpret_cast<const f16x8*>(sPl + nb + 32 * ks);
+          }
+          __syncthreads();
+        }
 #pragma unroll
         for (int ks = 0; ks < 4; ks++) {
-          const f16x8 bh = *reinterpret_cast<const f16x8*>(sPh + nb + 32 * ks);
-          const f16x8 bl = *reinterpret_cast<const f16x8*>(sPl + nb + 32 * ks);
+          f16x8 bh, bl;
+          if constexpr (QUAD) {
+            bh = bhs[ks];
+            bl = bls[ks];
+          } else {
+            bh = *reinterpret_cast<const f16x8*>(sPh + nb + 32 * ks);
+            bl = *reinterpret_cast<const f16x8*>(sPl + nb + 32 * ks);
+          }
 #pragma unroll
           for (int t = 0; t < 2; t++) {
             f16x8 ah, al;
@@ -323,25 +393,26 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
               ah = gAh[t][ks];
               al = gAl[t][ks];
             } else {
-              ah = *reinterpret_cast<const f16x8*>(sGf + ((t * 4 + ks) * 2 + 0) * 1024 + lane * 16);
-              al = *reinterpret_cast<const f16x8*>(sGf + ((t * 4 + ks) * 2 + 1) * 1024 + lane * 16);
+              ah = *reinterpret_cast<const f16x8*>(sGf + ((t * 4 + ks) * 2 + 0) * 1024 + (QUAD ? ln : lane) * 16);
+              al = *reinterpret_cast<const f16x8*>(sGf + ((t * 4 + ks) * 2 + 1) * 1024 + (QUAD ? ln : lane) * 16);
             }
             d0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, d0[t], 0, 0, 0);
             d1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, d1[t], 0, 0, 0);
             d1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, d1[t], 0, 0, 0);
           }
         }
-        if ((lane & 15) < 8) {   // D: column = lane & 15, rows 4 (lane >> 4) + 0..3 of the tile
+        if (QUAD || (lane & 15) < 8) {   // D: column = lane & 15, rows 4 (lane >> 4) + 0..3 of the tile
 #pragma unroll
           for (int t = 0; t < 2; t++) {
             const f32x4 d = (d0[t] + d1[t]) * ginv;
-            *reinterpret_cast<f32x4*>(sOut + (lane & 15) * SM::os + 32 * wv + 16 * t + 4 * (lane >> 4)) = d;
+            float* po = QUAD ? sOut + li * SM::os + 32 * wv + 16 * t + 4 * lg : sOut + (lane & 15) * SM::os + 32 * wv + 16 * t + 4 * (lane >> 4);
+            *reinterpret_cast<f32x4*>(po) = d;
           }
         }
       }
       float lacc = 0.f;
       if (mode != 2) {
-        float* trec = (mode == 0 ? tacc : tcur) + g2;   // slot 2 q + g2 <- t (the 16 lanes of the group write the same value)
+        float* trec = (mode == 0 ? tacc : tcur) + gs;   // slot 2 q + g2 (QUAD: q) <- t (the 16 lanes of the group write the same value)
 #pragma unroll
         for (int q0 = 0; q0 < NQ; q0 += 4) {
           if (blk_on(q0)) {   // wave-uniform
@@ -372,8 +443,8 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
 #pragma unroll
             for (int u = 0; u < 4; u++) {
               const int q = q0 + u;
-              const float c = GREG ? cv[q] : nx[64 + 2 * q + g2];
-              trec[2 * q] = t[u];
+              const float c = GREG ? cv[q] : (QUAD ? nx[64 + q] : nx[64 + 2 * q + g2]);
+              trec[SS * q] = t[u];
               const float w = mode == 0 ? c - (c - 1.f) * (GB ? t[u] + gbias : t[u]) : (c - 1.f) * t[u];
 #pragma unroll
               for (int rr = 0; rr < RPN; rr++) acc[rr] = fmaf(w, xt[q][rr], acc[rr]);
@@ -385,20 +456,23 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
         wave_sync();
         const float t = tacc[lslot];
         const float dd = ltgt - t;
-        lacc = pair_sum(row16_sum((lgrp && lslot < cnt) ? cl * dd * dd : 0.f));
+        const float ls = row16_sum((lgrp && lslot < cnt) ? cl * dd * dd : 0.f);
+        lacc = QUAD ? ls : pair_sum(ls);
       }
       if (mode != 2) {
         // (3) the products are complete: fold this row's G v into group 0's partial sums, then reduce the two groups
+        // (QUAD: into the group's own sums, and there is nothing to reduce)
         __syncthreads();
-        const float f = g2 == 0 ? vinv : 0.f;
+        const float f = (QUAD || g2 == 0) ? vinv : 0.f;
 #pragma unroll
         for (int b = 0; b < NV; b++) {
-          const f32x4 o = *reinterpret_cast<const f32x4*>(sOut + col * SM::os + b * 16 * VW + i * VW);
+          const float* po = QUAD ? sOut + lcol * SM::os + b * 16 * VW + li * VW : sOut + col * SM::os + b * 16 * VW + i * VW;
+          const f32x4 o = *reinterpret_cast<const f32x4*>(po);
 #pragma unroll
           for (int c = 0; c < VW; c++) acc[b * VW + c] = fmaf(f, o[c], acc[b * VW + c]);
         }
 #pragma unroll
-        for (int rr = 0; rr < RPN; rr++) out[rr] = pair_sum(acc[rr]);
+        for (int rr = 0; rr < RPN; rr++) out[rr] = QUAD ? acc[rr] : pair_sum(acc[rr]);
         if constexpr (GB) {
           if (mode == 0) {
 #pragma unroll
@@ -465,7 +539,7 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
     if (live) {
       const float xx = dot16(x, x);
       wloss += (double)rl + a.lambda_loss * (double)xx;
-      if (g2 == 0) {
+      if (QUAD || g2 == 0) {
 #pragma unroll
         for (int b = 0; b < NV; b++) {
           const int off = b * 16 * VW + i * VW;
@@ -481,48 +555,47 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
     }
   }
   const double other = __shfl(wloss, 32);
-  if (lane == 0) a.loss_partials[loss_slot0 + (size_t)blockIdx.x * 4 + wv] = wloss + other;
+  if constexpr (QUAD) {   // the wave's four groups
+    const double wsum = (wloss + __shfl(wloss, 16)) + (other + __shfl(wloss, 48));
+    if (lane == 0) a.loss_partials[loss_slot0 + (size_t)blockIdx.x * 4 + wv] = wsum;
+  } else {
+    if (lane == 0) a.loss_partials[loss_slot0 + (size_t)blockIdx.x * 4 + wv] = wloss + other;
+  }
 }
 
 }  // namespace
 
 bool cgp_supported(int k, bool implicit) { return implicit && k > 64 && k <= 128 && k % 4 == 0; }
 bool cgp_wide_supported(int k, bool implicit, bool gbias) { return implicit && k == 128 && !gbias; }
+bool cgp_quad_supported(int k, bool implicit, bool gbias) { return implicit && k == 128 && !gbias; }
 
-// grid (workgroups of 4 waves x 2 rows) for n_rows rows: about 32 pairs per wave, small sets spread over the CUs first
-int cgp_grid(int n_rows) {
-  if (n_rows <= 0) return 0;
-  const long pairs = ((long)n_rows + 1) / 2;
-  long per_wave = 32;
-  const long spread = 4L * 512;
-  if (pairs < spread * per_wave) per_wave = (pairs + spread - 1) / spread;
-  if (per_wave < 1) per_wave = 1;
-  return (int)((pairs + 4 * per_wave - 1) / (4 * per_wave));
-}
-
-// rows: n_rows row ids, each with at most 16 non-zeros (empty ones included), rank 65..128 (multiple of 4), implicit feedback;
-// wide: the rows have 17..32 non-zeros instead (rank 128, no global bias: cgp_wide_supported);
-// loss partials: cgp_grid(n_rows) * 4 slots from loss_slot0 on
-hipError_t launch_als_cgp(const AlsArgs& a, const int32_t* rows, int n_rows, bool wide, size_t loss_slot0, hipStream_t s,
+// rows: n_rows row ids, rank 65..128 (multiple of 4), implicit feedback.  form kCgpPair: each with at most 16 non-zeros (empty
+// ones included), two per wave; kCgpWide: 17..32 non-zeros, two per wave (cgp_wide_supported); kCgpQuad: at most 16 non-zeros
+// (empty ones included), four per wave (cgp_quad_supported);
+// loss partials: cgp_loss_slots(n_rows, cgp_rows_per_wave(form)) slots from loss_slot0 on (wrmf_schedule.h)
+hipError_t launch_als_cgp(const AlsArgs& a, const int32_t* rows, int n_rows, CgpForm form, size_t loss_slot0, hipStream_t s,
                           hipEvent_t* ev_slot) {
-  const int grid = cgp_grid(n_rows);
+  const int rpw = cgp_rows_per_wave(form);
+  const int grid = cgp_grid(n_rows, rpw);
   if (grid <= 0) return hipSuccess;
-  const long pairs = ((long)n_rows + 1) / 2;
-  const int iters = (int)((pairs + (long)grid * 4 - 1) / ((long)grid * 4));
+  const int iters = cgp_visits(n_rows, rpw);
   const bool gb = a.gbias != 0.f;
   const bool full = !gb && a.k == 128;
-  if (wide && !full) return hipErrorInvalidValue;
+  const bool wide = form == kCgpWide, quad = form == kCgpQuad;
+  if ((wide || quad) && !full) return hipErrorInvalidValue;
   auto k0 = als_cgp_kernel<false, false>;
   auto k0f = als_cgp_kernel<false, true>;
   auto k1 = als_cgp_kernel<true, false>;
   auto kw = als_cgp_kernel<false, true, 16>;
-  const void* fn = wide ? reinterpret_cast<const void*>(kw)
+  auto kq = als_cgp_kernel<false, true, 16, true>;
+  const void* fn = quad ? reinterpret_cast<const void*>(kq) : wide ? reinterpret_cast<const void*>(kw)
                         : gb ? reinterpret_cast<const void*>(k1) : (full ? reinterpret_cast<const void*>(k0f) : reinterpret_cast<const void*>(k0));
-  const size_t lds = wide ? PairSmem<16>::bytes : PairSmem<8>::bytes;
+  const size_t lds = quad ? PairSmem<16, true>::bytes : wide ? PairSmem<16>::bytes : PairSmem<8>::bytes;
   hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (err != hipSuccess) return err;
   prof_note(ev_slot, fn);   // (names the bucket's segment when this is its first launch)
-  if (wide) hipLaunchKernelGGL(kw, dim3(grid), dim3(256), lds, s, a, rows, n_rows, iters, loss_slot0);
+  if (quad) hipLaunchKernelGGL(kq, dim3(grid), dim3(256), lds, s, a, rows, n_rows, iters, loss_slot0);
+  else if (wide) hipLaunchKernelGGL(kw, dim3(grid), dim3(256), lds, s, a, rows, n_rows, iters, loss_slot0);
   else if (gb) hipLaunchKernelGGL(k1, dim3(grid), dim3(256), lds, s, a, rows, n_rows, iters, loss_slot0);
   else if (full) hipLaunchKernelGGL(k0f, dim3(grid), dim3(256), lds, s, a, rows, n_rows, iters, loss_slot0);
   else hipLaunchKernelGGL(k0, dim3(grid), dim3(256), lds, s, a, rows, n_rows, iters, loss_slot0);

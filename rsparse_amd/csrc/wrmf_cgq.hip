@@ -75,12 +75,6 @@ __device__ __forceinline__ float groups_reduce_scatter4(const float a0, const fl
   const auto t = __builtin_amdgcn_permlane32_swap(__float_as_uint(c), __float_as_uint(d), false, false);
   return __uint_as_float(t[0]) + __uint_as_float(t[1]);
 }
-// the lane number, or (ON) a copy of it that the compiler has to take as a new value: see WIDEQ in als_cgq_kernel
-template <bool ON>
-__device__ __forceinline__ int opaque_lane(int l) {
-  if constexpr (ON) asm volatile("" : "+v"(l));
-  return l;
-}
 // ---- dense product on the matrix cores (DMF instantiation: one-wave rows of <= 32 non-zeros at rank 65..128) ----
 // The four rows a workgroup solves side by side share every G v product: G is held in REGISTERS as two fp16 terms
 // (wave w owns rows [32w, 32w + 32) as A operands of v_mfma_f32_16x16x32_f16), the four vectors are published to LDS as
@@ -1157,8 +1151,9 @@ size_t bucket_slots(const QSchedule& q, int b, int k, bool implicit) {
   }
   if (b == kNB - 1 && rows > 0 && cgp_supported(k, implicit)) {
     const int split = std::min(std::max(q.pair_first, q.off[b]), q.off[b + 1]);
-    const size_t main = q.pair_wide ? (size_t)cgp_grid(split - q.off[b]) * 4 : (size_t)cgq_bucket_grid(split - q.off[b], b, cfg) * d.waves;
-    return main + (size_t)cgp_grid(q.off[b + 1] - split) * 4;
+    const size_t main = q.pair_wide ? (size_t)cgp_loss_slots(split - q.off[b], cgp_rows_per_wave(kCgpWide))
+                                    : (size_t)cgq_bucket_grid(split - q.off[b], b, cfg) * d.waves;
+    return main + (size_t)cgp_loss_slots(q.off[b + 1] - split, cgp_rows_per_wave(q.pair_quad ? kCgpQuad : kCgpPair));
   }
   return (size_t)cgq_bucket_grid(rows, b, cfg) * d.waves;
 }
@@ -1239,14 +1234,14 @@ hipError_t launch_all(const AlsArgs& a, const QSchedule& q, hipStream_t s, hipEv
             return err;                                                                                     \
         } else if (B == kNB - 1 && cgp_supported(a.k, IMPLICIT)) {                    \
           /* the last bucket in two launches: rows of 17..32 non-zeros two per wave in 32 slots (q.pair_wide) or one per */ \
-          /* wave, the rest two per wave in 16 slots (wrmf_cgp.hip) */                                       \
+          /* wave, the rest two per wave in 16 slots or (q.pair_quad) four per wave (wrmf_cgp.hip) */        \
           const int first = q.off[B], split = std::min(std::max(q.pair_first, first), q.off[B + 1]);         \
           const int n_main = split - first, n_pair = q.off[B + 1] - split;                                   \
           size_t main_slots;                                                                                \
           if (q.pair_wide) {                                                                                \
-            if ((err = launch_als_cgp(a, q.order + first, n_main, true, slot, bs, ev ? ev + B : nullptr)) != hipSuccess) \
+            if ((err = launch_als_cgp(a, q.order + first, n_main, kCgpWide, slot, bs, ev ? ev + B : nullptr)) != hipSuccess) \
               return err;                                                                                   \
-            main_slots = (size_t)cgp_grid(n_main) * 4;                                                      \
+            main_slots = (size_t)cgp_loss_slots(n_main, cgp_rows_per_wave(kCgpWide));                       \
           } else {                                                                                          \
             const int g_main = cgq_bucket_grid(n_main, B, CFG);                                             \
             if ((err = launch_bucket<KP, D.waves, D.capq, D.wpr, D.stream, IMPLICIT, GB>(a, q.order + first, n_main, g_main, slot, \
@@ -1254,7 +1249,7 @@ hipError_t launch_all(const AlsArgs& a, const QSchedule& q, hipStream_t s, hipEv
               return err;                                                                                   \
             main_slots = (size_t)g_main * D.waves;                                                          \
           }                                                                                                 \
-          if ((err = launch_als_cgp(a, q.order + split, n_pair, false, slot + main_slots, bs,               \
+          if ((err = launch_als_cgp(a, q.order + split, n_pair, q.pair_quad ? kCgpQuad : kCgpPair, slot + main_slots, bs, \
                                     n_main > 0 ? nullptr : (ev ? ev + B : nullptr))) != hipSuccess)           \
             return err;                                                                                     \
         } else if ((err = launch_bucket<KP, D.waves, D.capq, D.wpr, D.stream, IMPLICIT, GB>(a, q.order + q.off[B], n, grid, slot, \

@@ -157,6 +157,7 @@ struct QSchedule {
   int team4_first;  // see DevCSC::q_team4_first; = off[2] when bucket 1 runs on the 8-wave kernel alone (global bias)
   int team4_wide_first;  // see DevCSC::q_team4_wide_first; = off[2] in the same case
   bool pair_wide;   // the last bucket's rows of 17..32 non-zeros two per wave as well (cgp_wide_supported), else one per wave
+  bool pair_quad = false;   // the last bucket's rows of at most 16 non-zeros four per wave (cgp_quad_supported), else two per wave
   int cfg;  // geometry the schedule was built for (see wrmf_cgq.hip kBuckets)
   NeListSet ne;   // the list set of this call's normal-equation launch (one of DevCSC::q_ne / q_ne1 / q_nec)
   const int32_t* mf_rows = nullptr;   // wrmf_cg_mf.hip's rows of the first bucket (the normal-equation lists above then hold the giant rows only)
@@ -177,11 +178,15 @@ int cgq_team4_wide_grid(int n_rows);
 int cgq_bucket_of(int len, int cfg);
 size_t cgq_loss_slots(const QSchedule& q, int k, bool implicit);
 // the rows of at most 16 non-zeros of the last bucket, two per wave (wrmf_cgp.hip): rank 65..128, implicit feedback;
-// its rows of 17..32 non-zeros too ("wide") at rank 128 without a global bias
+// its rows of 17..32 non-zeros too ("wide") at rank 128 without a global bias; under the same conditions its rows of at
+// most 16 non-zeros four per wave ("quad")
 bool cgp_supported(int k, bool implicit);
 bool cgp_wide_supported(int k, bool implicit, bool gbias);
-int cgp_grid(int n_rows);
-hipError_t launch_als_cgp(const AlsArgs& a, const int32_t* rows, int n_rows, bool wide, size_t loss_slot0, hipStream_t s,
+bool cgp_quad_supported(int k, bool implicit, bool gbias);
+enum CgpForm { kCgpPair = 0, kCgpWide = 1, kCgpQuad = 2 };
+inline int cgp_rows_per_wave(CgpForm form) { return form == kCgpQuad ? 4 : 2; }
+// (grid, visits per wave and loss slots of a launch: cgp_grid / cgp_visits / cgp_loss_slots of wrmf_schedule.h)
+hipError_t launch_als_cgp(const AlsArgs& a, const int32_t* rows, int n_rows, CgpForm form, size_t loss_slot0, hipStream_t s,
                           hipEvent_t* ev_slot);
 // long rows (bucket 0) by one-pass normal equations on the matrix cores (wrmf_ne.hip) instead of the streamed CG kernel
 bool ne_supported(int k);

@@ -14,6 +14,24 @@ namespace {
 int ne_slots(int cus) { return 2 * std::max(cus, 1); }
 }  // namespace
 
+// grid (workgroups of 4 waves x rows_per_wave rows) for n_rows rows: about 32 visits per wave, small sets spread over the CUs first
+int cgp_grid(int n_rows, int rows_per_wave) {
+  if (n_rows <= 0) return 0;
+  const long sets = ((long)n_rows + rows_per_wave - 1) / rows_per_wave;
+  long per_wave = 32;
+  const long spread = 4L * 512;
+  if (sets < spread * per_wave) per_wave = (sets + spread - 1) / spread;
+  if (per_wave < 1) per_wave = 1;
+  return (int)((sets + 4 * per_wave - 1) / (4 * per_wave));
+}
+int cgp_visits(int n_rows, int rows_per_wave) {
+  const long grid = cgp_grid(n_rows, rows_per_wave);
+  if (grid <= 0) return 0;
+  const long sets = ((long)n_rows + rows_per_wave - 1) / rows_per_wave;
+  return (int)((sets + grid * 4 - 1) / (grid * 4));
+}
+int64_t cgp_loss_slots(int n_rows, int rows_per_wave) { return (int64_t)cgp_grid(n_rows, rows_per_wave) * 4; }
+
 // Items of the deal: whole rows, and SEGMENTS of the rows that are too long to balance (the 5e5-non-zero item of the
 // bench matrix is by itself an average workgroup's share; on a rank of an 8-GPU run it is eight shares).  A row
 // whose cost exceeds half a share is cut into up to kNeMaxSeg runs of whole steps of about a quarter share; the

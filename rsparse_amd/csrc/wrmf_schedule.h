@@ -18,6 +18,13 @@ constexpr int kCgMfMax = 16384;      // rank 128, implicit CG: the rows of kNeMi
 constexpr int kNeMaxSeg = 16;        // segments per split row
 constexpr int kNeMaxSegTotal = 1024;   // ... per list set (186 MB of partial accumulators at most)
 
+// The short-row launches of wrmf_cgp.hip: workgroups of 4 waves, a wave VISITS `rows_per_wave` rows of the list at a time (2, or 4
+// in the four-rows form), visit v of wave w taking rows [(w + v * waves) * rows_per_wave, + rows_per_wave).  One loss slot per
+// wave.  The launcher and the loss-slot count of wrmf_cgq.hip both call these, for the same range of rows.
+int cgp_grid(int n_rows, int rows_per_wave = 2);     // workgroups: about 32 visits per wave, small sets spread over the CUs first
+int cgp_visits(int n_rows, int rows_per_wave = 2);   // visits per wave: cgp_grid * 4 * cgp_visits * rows_per_wave >= n_rows
+int64_t cgp_loss_slots(int n_rows, int rows_per_wave = 2);
+
 // The CUT of the normal-equation launch over a prefix of the order: the items that are dealt to workgroups -- whole rows,
 // and SEGMENTS of the rows that are too long to balance -- in the order of the deal (dearest first, stable).
 struct NeCut {

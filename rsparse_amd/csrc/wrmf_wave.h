@@ -45,6 +45,14 @@ __device__ __forceinline__ float readlane_f(float v, int l) {
 }
 __device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// the lane number, or (ON) a copy of it that the compiler has to take as a new value: what is computed from it is computed where
+// it is used instead of living in a register across a loop (WIDEQ in als_cgq_kernel, QUAD in als_cgp_kernel)
+template <bool ON>
+__device__ __forceinline__ int opaque_lane(int l) {
+  if constexpr (ON) asm volatile("" : "+v"(l));
+  return l;
+}
+
 // ---- LDS-DMA ----
 __device__ __forceinline__ unsigned lds_addr(const void* p) {
   return (unsigned)(reinterpret_cast<uintptr_t>(p));  // low 32 bits of a generic LDS pointer = LDS byte address
