@@ -917,6 +917,56 @@ int rsparse_hip_split_rows(uint64_t seed, int64_t row0, int n_rows, int mode, ui
                            int32_t* train_j, void* train_v, int32_t* test_p, int32_t* test_j, void* test_v, int64_t train_capacity,
                            int64_t test_capacity);
 
+/* Confidence weighting of the interaction matrix (the reference's `preprocess` hook, R/model_WRMF.R:184-188, and its
+ * ScaleNormalize): rsparse_amd/confidence.py (confidence_reference) is the definition in numpy.  A matrix is (p, i, x): n_seg
+ * segments with p[0] = 0 and p[n_seg] = nnz (the rows of the user-major arrays, the columns of the item-major ones), int32
+ * indices, double values.  x is users x items, v a stored value at (u, i); fitted on the training matrix: N its number of rows,
+ * df_i the stored entries of column i, idf_i = log(N) - log1p(df_i), sbar = (sum of all values) / N.
+ *
+ *   RSPARSE_HIP_CONFIDENCE_LINEAR     1 + a v                                                     a = alpha
+ *   RSPARSE_HIP_CONFIDENCE_LOG        1 + a log1p(v / b)                                          a = alpha, b = eps
+ *   RSPARSE_HIP_CONFIDENCE_TFIDF      sqrt(v) idf_i
+ *   RSPARSE_HIP_CONFIDENCE_BM25       ((v (a + 1)) / (K1L_u + v)) idf_i                           a = K1; the user table holds K1 L_u
+ *   RSPARSE_HIP_CONFIDENCE_NORMALIZE  v t, t the entry of the ONE table that is given (of the segment or of the index)
+ * in double, in the order written, without contraction.
+ *
+ * _moments_device: d_out[r] = sum over segment r of |x|^power (power 1 or 2; 0 for an empty segment), *d_total = the sum over
+ * all entries.  Fixed summation order, no floating-point atomics: repeat calls are bit-identical; nothing is read back.
+ * _table_device: d_out[r], r < n, from
+ *   RSPARSE_HIP_CONFIDENCE_TABLE_IDF   log(a) - log1p(d_p[r + 1] - d_p[r])                        a = N; d_p of the item-major arrays
+ *   RSPARSE_HIP_CONFIDENCE_TABLE_BM25  a ((1 - b) + (b d_moment[r]) / sbar), sbar = *d_total / c   a = K1, b = B, c = N of the fit;
+ *                                      sbar == 0: (b d_moment[r]) / sbar is replaced by b
+ *   RSPARSE_HIP_CONFIDENCE_TABLE_NORM  n^(a - 1) where n != 0, else 0; n = d_moment[r] (b = 1) or sqrt(d_moment[r]) (b = 2)   a = scale
+ * _apply_device: d_out[e] = f_kind(d_x[e], user table, item table) for every stored entry.  d_seg_table has one entry per segment,
+ * d_idx_table (n_idx entries) is gathered by d_i[e]; seg_is_item says which of the two is the item table (1: the item-major
+ * arrays).  A kind takes the tables it needs and NULL for the others.  d_out: doubles (out_float = 0; may be d_x itself) or
+ * floats (out_float = 1: the double result rounded once; must not overlap d_x).  The same cell gets the same bits from either
+ * orientation.  An index outside [0, n_idx) gives NaN at its entry and reads nothing.
+ *
+ * rsparse_hip_confidence: host pointers; fits on the CSR (p, j, x) of an n_rows x n_cols matrix (p from 0) and writes the weighted
+ * values in its order.  NORMALIZE: a = scale, norm in {1, 2}, along the rows (by_columns = 0) or the columns (1).
+ *
+ * All: a NULL array where a length is positive, negative dimensions, an unknown kind or table, a power / norm outside {1, 2}, a
+ * missing or surplus table, b == 0 for LOG, an overlapping float output -> ERR_INVALID before a device is touched.  Nothing is
+ * launched for n == 0 / nnz == 0 (moments then zero d_out and *d_total). */
+#define RSPARSE_HIP_CONFIDENCE_LINEAR 0
+#define RSPARSE_HIP_CONFIDENCE_LOG 1
+#define RSPARSE_HIP_CONFIDENCE_TFIDF 2
+#define RSPARSE_HIP_CONFIDENCE_BM25 3
+#define RSPARSE_HIP_CONFIDENCE_NORMALIZE 4
+#define RSPARSE_HIP_CONFIDENCE_TABLE_IDF 0
+#define RSPARSE_HIP_CONFIDENCE_TABLE_BM25 1
+#define RSPARSE_HIP_CONFIDENCE_TABLE_NORM 2
+int rsparse_hip_confidence_moments_device(int n_seg, int64_t nnz, const int32_t* d_p, const double* d_x, int power, double* d_out,
+                                          double* d_total, void* hip_stream);
+int rsparse_hip_confidence_table_device(int table, int n, const int32_t* d_p, const double* d_moment, const double* d_total, double a,
+                                        double b, double c, double* d_out, void* hip_stream);
+int rsparse_hip_confidence_apply_device(int kind, int n_seg, int64_t nnz, const int32_t* d_p, const int32_t* d_i, const double* d_x,
+                                        const double* d_seg_table, const double* d_idx_table, int n_idx, int seg_is_item, double a,
+                                        double b, void* d_out, int out_float, void* hip_stream);
+int rsparse_hip_confidence(int kind, int n_rows, int n_cols, const int32_t* p, const int32_t* j, const double* x, double a, double b,
+                           int norm, int by_columns, double* out);
+
 /* ------------------------------------------------------------------------------------------------
  * (3) fp64 device layer: als_implicit<double> / als_explicit<double> with the data resident in HBM
  * ---------------------------------------------------------------------------------------------- */

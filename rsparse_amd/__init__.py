@@ -5,6 +5,8 @@ Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit
   rsparse_amd.metrics         ap_k() / ndcg_k(), the reference's ranking metrics, and precision / recall / hit rate / MRR /
                               coverage at several cutoffs, on the device
   rsparse_amd.train_test_split  the reference's train_test_split (and leave-n-out), drawn on the device
+  rsparse_amd.Confidence      the confidence transformation of WRMF(preprocess=): BM25, TF-IDF, log, linear, on the device
+  rsparse_amd.ScaleNormalize  the reference's ScaleNormalize: p-norm scaling of rows or columns
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
   rsparse_amd.engine          device-resident, row-sharded driver (one process per GPU)
   rsparse_amd.synth           synthetic interaction matrices for the BASELINE configs
@@ -20,6 +22,9 @@ def __getattr__(name):
     if name == "train_test_split":
         from .split import train_test_split
         return train_test_split
+    if name in ("Confidence", "ScaleNormalize", "confidence_reference"):
+        from . import confidence
+        return getattr(confidence, name)
     if name == "metrics":
         import importlib
         return importlib.import_module(".metrics", __name__)

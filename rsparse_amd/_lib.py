@@ -121,6 +121,10 @@ SIGNATURES = {
     "rsparse_hip_sample_negatives_weighted": (_c_int, [_c_u64, _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _vp]),
     "rsparse_hip_split_rows_device": (_c_int, [_c_u64, _c_i64, _c_int, _c_int, _c_u64, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _vp]),
     "rsparse_hip_split_rows": (_c_int, [_c_u64, _c_i64, _c_int, _c_int, _c_u64, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64]),
+    "rsparse_hip_confidence_moments_device": (_c_int, [_c_int, _c_i64, _vp, _vp, _c_int, _vp, _vp, _vp]),
+    "rsparse_hip_confidence_table_device": (_c_int, [_c_int, _c_int, _vp, _vp, _vp, _c_dbl, _c_dbl, _c_dbl, _vp, _vp]),
+    "rsparse_hip_confidence_apply_device": (_c_int, [_c_int, _c_int, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_dbl, _c_dbl, _vp, _c_int, _vp]),
+    "rsparse_hip_confidence": (_c_int, [_c_int, _c_int, _c_int, _vp, _vp, _vp, _c_dbl, _c_dbl, _c_int, _c_int, _vp]),
     "rsparse_hip_sparse_approximation": (_c_int, [_c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_int, _vp]),
     "rsparse_hip_csc_f64_create_device": (_c_int, [_c_int, _c_int, _vp, _vp, _vp, ctypes.POINTER(_vp)]),
     "rsparse_hip_csc_f64_destroy": (_c_int, [_vp]),

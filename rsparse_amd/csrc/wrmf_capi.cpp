@@ -2278,6 +2278,155 @@ int rsparse_hip_split_rows(uint64_t seed, int64_t row0, int n_rows, int mode, ui
   return RSPARSE_HIP_OK;
 }
 
+namespace {
+int confidence_apply_args(int kind, int n_seg, int64_t nnz, const void* p, const void* i, const void* x, const void* seg_table,
+                          const void* idx_table, int n_idx, int seg_is_item, double b, const void* out, int out_float) {
+  if (n_seg < 0 || nnz < 0 || n_idx < 0) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_seg < 0, nnz < 0 or n_idx < 0)");
+  if (kind < RSPARSE_HIP_CONFIDENCE_LINEAR || kind > RSPARSE_HIP_CONFIDENCE_NORMALIZE)
+    return fail(RSPARSE_HIP_ERR_INVALID, "unknown confidence kind " + std::to_string(kind));
+  if (nnz > 0 && (!p || !x || !out)) return fail(RSPARSE_HIP_ERR_INVALID, "p, x or out is NULL");
+  if (nnz > 0 && idx_table && !i) return fail(RSPARSE_HIP_ERR_INVALID, "an index table without indices");
+  const void* item_table = seg_is_item ? seg_table : idx_table;
+  const void* user_table = seg_is_item ? idx_table : seg_table;
+  bool ok = true;
+  switch (kind) {
+    case RSPARSE_HIP_CONFIDENCE_TFIDF: ok = item_table && !user_table; break;
+    case RSPARSE_HIP_CONFIDENCE_BM25: ok = item_table && user_table; break;
+    case RSPARSE_HIP_CONFIDENCE_NORMALIZE: ok = !seg_table != !idx_table; break;
+    default: ok = !seg_table && !idx_table;
+  }
+  if (!ok) return fail(RSPARSE_HIP_ERR_INVALID, "a missing or surplus table for confidence kind " + std::to_string(kind));
+  if (kind == RSPARSE_HIP_CONFIDENCE_LOG && !(b != 0.0)) return fail(RSPARSE_HIP_ERR_INVALID, "eps must not be 0");
+  if (out_float && nnz > 0) {
+    const char *xb = static_cast<const char*>(x), *ob = static_cast<const char*>(out);
+    if (ob < xb + (size_t)nnz * 8 && xb < ob + (size_t)nnz * 4) return fail(RSPARSE_HIP_ERR_INVALID, "a float output overlaps the values");
+  }
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+
+int rsparse_hip_confidence_moments_device(int n_seg, int64_t nnz, const int32_t* d_p, const double* d_x, int power, double* d_out,
+                                          double* d_total, void* stream) {
+  if (n_seg < 0 || nnz < 0) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_seg < 0 or nnz < 0)");
+  if (power != 1 && power != 2) return fail(RSPARSE_HIP_ERR_INVALID, "power must be 1 or 2");
+  if (!d_total || (n_seg > 0 && !d_out) || (nnz > 0 && (!d_p || !d_x))) return fail(RSPARSE_HIP_ERR_INVALID, "NULL array");
+  if (nnz > 0 && n_seg == 0) return fail(RSPARSE_HIP_ERR_INVALID, "entries without a segment");
+  int rc;
+  if ((rc = g_ws.ensure_device())) return rc;
+  HIP_TRY(g_ws.score_buf.ensure(confidence_ws_doubles(nnz)));
+  hipError_t e = launch_confidence_moments(d_p, d_x, n_seg, nnz, power, d_out, d_total, g_ws.score_buf, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_confidence_moments");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_confidence_table_device(int table, int n, const int32_t* d_p, const double* d_moment, const double* d_total, double a,
+                                        double b, double c, double* d_out, void* stream) {
+  if (n < 0) return fail(RSPARSE_HIP_ERR_INVALID, "negative length");
+  if (table < RSPARSE_HIP_CONFIDENCE_TABLE_IDF || table > RSPARSE_HIP_CONFIDENCE_TABLE_NORM)
+    return fail(RSPARSE_HIP_ERR_INVALID, "unknown confidence table " + std::to_string(table));
+  if (table == RSPARSE_HIP_CONFIDENCE_TABLE_NORM && b != 1.0 && b != 2.0) return fail(RSPARSE_HIP_ERR_INVALID, "norm must be 1 or 2");
+  if (n > 0) {
+    const bool ok = d_out && (table == RSPARSE_HIP_CONFIDENCE_TABLE_IDF ? d_p != nullptr
+                              : table == RSPARSE_HIP_CONFIDENCE_TABLE_BM25 ? d_moment && d_total : d_moment != nullptr);
+    if (!ok) return fail(RSPARSE_HIP_ERR_INVALID, "NULL array");
+  }
+  if (n == 0) return RSPARSE_HIP_OK;
+  hipError_t e = launch_confidence_table(table, n, d_p, d_moment, d_total, a, b, c, d_out, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_confidence_table");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_confidence_apply_device(int kind, int n_seg, int64_t nnz, const int32_t* d_p, const int32_t* d_i, const double* d_x,
+                                        const double* d_seg_table, const double* d_idx_table, int n_idx, int seg_is_item, double a,
+                                        double b, void* d_out, int out_float, void* stream) {
+  int rc = confidence_apply_args(kind, n_seg, nnz, d_p, d_i, d_x, d_seg_table, d_idx_table, n_idx, seg_is_item, b, d_out, out_float);
+  if (rc) return rc;
+  if (nnz == 0) return RSPARSE_HIP_OK;
+  if (n_seg == 0) return fail(RSPARSE_HIP_ERR_INVALID, "entries without a segment");
+  hipError_t e = launch_confidence_apply(kind, d_p, d_i, d_x, n_seg, nnz, d_seg_table, d_idx_table, n_idx, seg_is_item ? 1 : 0, a, b,
+                                         d_out, out_float ? 1 : 0, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_confidence_apply");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_confidence(int kind, int n_rows, int n_cols, const int32_t* p, const int32_t* j, const double* x, double a, double b,
+                           int norm, int by_columns, double* out) {
+  if (n_rows < 0 || n_cols < 0) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0 or n_cols < 0)");
+  if (kind < RSPARSE_HIP_CONFIDENCE_LINEAR || kind > RSPARSE_HIP_CONFIDENCE_NORMALIZE)
+    return fail(RSPARSE_HIP_ERR_INVALID, "unknown confidence kind " + std::to_string(kind));
+  if (!p) return fail(RSPARSE_HIP_ERR_INVALID, "p is NULL");
+  if (kind == RSPARSE_HIP_CONFIDENCE_NORMALIZE && norm != 1 && norm != 2) return fail(RSPARSE_HIP_ERR_INVALID, "norm must be 1 or 2");
+  if (kind == RSPARSE_HIP_CONFIDENCE_LOG && !(b != 0.0)) return fail(RSPARSE_HIP_ERR_INVALID, "eps must not be 0");
+  if (p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "p[0] != 0");
+  for (int u = 0; u < n_rows; u++)
+    if (p[u + 1] < p[u]) return fail(RSPARSE_HIP_ERR_INVALID, "p decreases");
+  const int64_t nnz = p[n_rows];
+  if (nnz == 0) return RSPARSE_HIP_OK;
+  if (!j || !x || !out) return fail(RSPARSE_HIP_ERR_INVALID, "j, x or out is NULL");
+  for (int64_t e = 0; e < nnz; e++)
+    if (j[e] < 0 || j[e] >= n_cols) return fail(RSPARSE_HIP_ERR_INVALID, "a column index outside [0, n_cols)");
+  // the item-major side on the host: the columns' counts, and their values where the columns are normalized
+  const bool cols = kind == RSPARSE_HIP_CONFIDENCE_NORMALIZE && by_columns;
+  const bool items = kind == RSPARSE_HIP_CONFIDENCE_TFIDF || kind == RSPARSE_HIP_CONFIDENCE_BM25 || cols;
+  std::vector<int32_t> pt;
+  std::vector<double> xt;
+  if (items) {
+    pt.assign((size_t)n_cols + 1, 0);
+    for (int64_t e = 0; e < nnz; e++) pt[(size_t)j[e] + 1]++;
+    for (int c = 0; c < n_cols; c++) pt[(size_t)c + 1] += pt[c];
+    if (cols) {
+      xt.resize((size_t)nnz);
+      std::vector<int32_t> at(pt.begin(), pt.end() - 1);
+      for (int64_t e = 0; e < nnz; e++) xt[(size_t)at[j[e]]++] = x[e];
+    }
+  }
+  DevBuf dP, dJ, dX, dPt, dXt, dMom, dTot, dUser, dItem;
+  HIP_TRY(upload_host(dP, p, (size_t)n_rows + 1));
+  HIP_TRY(upload_host(dJ, j, (size_t)nnz));
+  HIP_TRY(upload_host(dX, x, (size_t)nnz));
+  HIP_TRY(dTot.alloc(8));
+  const double *user_t = nullptr, *item_t = nullptr;
+  int rc;
+  if (items) {
+    HIP_TRY(upload_host(dPt, pt.data(), pt.size()));
+    HIP_TRY(dItem.alloc((size_t)n_cols * 8));
+    item_t = dItem.as<double>();
+  }
+  if (kind == RSPARSE_HIP_CONFIDENCE_TFIDF || kind == RSPARSE_HIP_CONFIDENCE_BM25) {
+    if ((rc = rsparse_hip_confidence_table_device(RSPARSE_HIP_CONFIDENCE_TABLE_IDF, n_cols, dPt.as<int32_t>(), nullptr, nullptr,
+                                                  (double)n_rows, 0.0, 0.0, dItem.as<double>(), nullptr)))
+      return rc;
+  }
+  if (kind == RSPARSE_HIP_CONFIDENCE_BM25 || (kind == RSPARSE_HIP_CONFIDENCE_NORMALIZE && !cols)) {
+    HIP_TRY(dMom.alloc((size_t)n_rows * 8));
+    HIP_TRY(dUser.alloc((size_t)n_rows * 8));
+    user_t = dUser.as<double>();
+    const bool bm = kind == RSPARSE_HIP_CONFIDENCE_BM25;
+    if ((rc = rsparse_hip_confidence_moments_device(n_rows, nnz, dP.as<int32_t>(), dX.as<double>(), bm ? 1 : norm, dMom.as<double>(),
+                                                    dTot.as<double>(), nullptr)))
+      return rc;
+    if ((rc = rsparse_hip_confidence_table_device(bm ? RSPARSE_HIP_CONFIDENCE_TABLE_BM25 : RSPARSE_HIP_CONFIDENCE_TABLE_NORM, n_rows,
+                                                  nullptr, dMom.as<double>(), dTot.as<double>(), a, bm ? b : (double)norm,
+                                                  (double)n_rows, dUser.as<double>(), nullptr)))
+      return rc;
+  } else if (cols) {
+    HIP_TRY(upload_host(dXt, xt.data(), xt.size()));
+    HIP_TRY(dMom.alloc((size_t)n_cols * 8));
+    if ((rc = rsparse_hip_confidence_moments_device(n_cols, nnz, dPt.as<int32_t>(), dXt.as<double>(), norm, dMom.as<double>(),
+                                                    dTot.as<double>(), nullptr)))
+      return rc;
+    if ((rc = rsparse_hip_confidence_table_device(RSPARSE_HIP_CONFIDENCE_TABLE_NORM, n_cols, nullptr, dMom.as<double>(), nullptr, a,
+                                                  (double)norm, 0.0, dItem.as<double>(), nullptr)))
+      return rc;
+  }
+  if ((rc = rsparse_hip_confidence_apply_device(kind, n_rows, nnz, dP.as<int32_t>(), dJ.as<int32_t>(), dX.as<double>(), user_t, item_t,
+                                                n_cols, 0, a, b, dX.p, 0, nullptr)))
+    return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, dX.p, (size_t)nnz * 8, hipMemcpyDeviceToHost));
+  return RSPARSE_HIP_OK;
+}
+
 int rsparse_hip_take_numeric_failures(int64_t* unresolved_out, int64_t* fallback_out) {
   if (!unresolved_out) return fail(RSPARSE_HIP_ERR_INVALID, "unresolved_out is NULL");
   // counts a stateless call found on the device when it started and set aside (see StaleFailures): still the resident layer's

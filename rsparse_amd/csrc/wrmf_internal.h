@@ -481,6 +481,17 @@ hipError_t launch_split_write(uint64_t seed, int64_t row0, int n_rows, int mode,
                               const int32_t* train_p, int32_t* train_j, void* train_v, const int32_t* test_p, int32_t* test_j,
                               void* test_v, void* ws, hipStream_t s);
 
+// confidence weighting (wrmf_confidence.hip; the kinds and tables are defined in rsparse_wrmf_hip.h).  A matrix is (p, i, x) with
+// n_seg segments, p[0] = 0, p[n_seg] = nnz.  launch_confidence_moments needs confidence_ws_doubles(nnz) doubles of scratch.
+size_t confidence_ws_doubles(int64_t nnz);
+hipError_t launch_confidence_moments(const int32_t* p, const double* x, int n_seg, int64_t nnz, int power, double* out, double* total,
+                                     double* ws, hipStream_t s);
+hipError_t launch_confidence_table(int table, int n, const int32_t* p, const double* moment, const double* total, double a, double b,
+                                   double c, double* out, hipStream_t s);
+hipError_t launch_confidence_apply(int kind, const int32_t* p, const int32_t* i, const double* x, int n_seg, int64_t nnz,
+                                   const double* seg_table, const double* idx_table, int n_idx, int seg_is_item, double a, double b,
+                                   void* out, int out_float, hipStream_t s);
+
 // item-to-item cosine similarity (wrmf_similar.hip): the operands of the top-k path above.
 // launch_normalize_items: V (fp32, or fp64 when f64) n_items x ld row-major, columns [c0, c0 + r), 1 <= r <= 256 ->
 // Vn64 / Vn32 (n_items x r, compact) with unit rows, flags[item] = 1 and a row of zeros where the sum of squares is zero or

@@ -535,6 +535,48 @@ class HipBackend:
         n_tr, n_te = int(train_p[-1]), int(test_p[-1])
         return (train_p, train_j[:n_tr], None if v is None else train_v[:n_tr], test_p, test_j[:n_te], None if v is None else test_v[:n_te])
 
+    def confidence_moments(self, p, x, power):
+        """(out, total) on the device: out[r] = sum |x|^power over segment r of the arrays (p, x) -- p int32 from 0, x float64 --
+        and the sum over all entries (one double), wrmf_confidence.hip: a fixed summation order, repeat calls bit-identical"""
+        assert p.dtype == torch.int32 and x.dtype == torch.float64 and p.numel() >= 1
+        n_seg = int(p.numel()) - 1
+        out = torch.empty(max(n_seg, 1), dtype=torch.float64, device=self.device)[:n_seg]
+        total = torch.empty(1, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.rsparse_hip_confidence_moments_device(n_seg, int(x.numel()), p.data_ptr(), x.data_ptr(), int(power),
+                                                                  out.data_ptr(), total.data_ptr(), self._stream()))
+        return out, total
+
+    def confidence_table(self, table, n, p=None, moment=None, total=None, a=0.0, b=0.0, c=0.0):
+        """the per-row or per-column table of rsparse_amd.confidence ("idf" from the counts diff(p), "bm25" from the row sums and
+        the fit's total, "norm" from the moments): n doubles on the device"""
+        from .confidence import TABLES
+        out = torch.empty(max(int(n), 1), dtype=torch.float64, device=self.device)[:int(n)]
+        ptr = [None if t is None else t.data_ptr() for t in (p, moment, total)]
+        _lib.check(self.lib.rsparse_hip_confidence_table_device(TABLES[table], int(n), ptr[0], ptr[1], ptr[2], float(a), float(b),
+                                                                float(c), out.data_ptr(), self._stream()))
+        return out
+
+    def confidence_apply(self, kind, p, i, x, seg_table=None, idx_table=None, seg_is_item=False, a=0.0, b=0.0, out=None):
+        """x weighted by `kind` (rsparse_amd.confidence) on the resident arrays (p, i, x) of either orientation: seg_table has one
+        entry per segment of p, idx_table is gathered by i; seg_is_item: the segments are the items.  out: None = new doubles,
+        "inplace" = over x, torch.float32 = new floats (the double result rounded once)."""
+        from .confidence import KINDS
+        assert p.dtype == torch.int32 and i.dtype == torch.int32 and x.dtype == torch.float64
+        nnz = int(x.numel())
+        if out is None:
+            dst = torch.empty(max(nnz, 1), dtype=torch.float64, device=self.device)[:nnz]
+        elif out is torch.float32:
+            dst = torch.empty(max(nnz, 1), dtype=torch.float32, device=self.device)[:nnz]
+        else:
+            assert out == "inplace"
+            dst = x
+        _lib.check(self.lib.rsparse_hip_confidence_apply_device(
+            KINDS[kind], int(p.numel()) - 1, nnz, p.data_ptr(), i.data_ptr(), x.data_ptr(),
+            None if seg_table is None else seg_table.data_ptr(), None if idx_table is None else idx_table.data_ptr(),
+            0 if idx_table is None else int(idx_table.numel()), int(bool(seg_is_item)), float(a), float(b), dst.data_ptr(),
+            int(dst.dtype == torch.float32), self._stream()))
+        return dst
+
     def ranking_metrics(self, res, p, j, x, want_ap=True, want_ndcg=True):
         """ap_k / ndcg_k (R/metrics.R:31-127) of the lists `res` (n x k int32 on the device, 1-based with NA_integer_, as
         top_product returns them) against `actual` as CSR slots on the device (p, j int32 with j sorted within rows; x float64,

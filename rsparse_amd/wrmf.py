@@ -27,6 +27,7 @@ import scipy.sparse as sp
 import torch
 
 from . import _lib
+from .confidence import Confidence, canonical_rows
 from .engine import SOLVER_CODES, HipBackend, ShardedALS
 
 
@@ -108,8 +109,8 @@ class WRMF:
             raise ValueError("precision must be 'double' or 'float'")
         if not isinstance(cg_steps, (int, np.integer)):
             raise TypeError("cg_steps must be an integer")                        # :107
-        if not callable(preprocess):
-            raise TypeError("preprocess must be a function")                      # :165
+        if not callable(preprocess) and not isinstance(preprocess, Confidence):
+            raise TypeError("preprocess must be a function or a Confidence")      # :165
         if factor_init not in ("host", "device"):
             raise ValueError("factor_init must be 'host' or 'device'")
         self._non_negative = solver == "nnls"
@@ -133,6 +134,8 @@ class WRMF:
                           "in fp32 (the reference's precision='float' arithmetic); inputs and results are converted at the "
                           "boundary (the library's fp64 layer ends at rank 128, WRMF.f64_max_rank may lower that).  Pass "
                           "precision='float' to silence this." % (self._rank, lim), RuntimeWarning, stacklevel=2)
+        # a callable on the CsparseMatrix, as in the reference, or a `rsparse_amd.Confidence` ("bm25", "tfidf", "log", ...): that
+        # one is fitted and applied on the device, users as rows at every call site, and keeps the fitted item statistics
         self._preprocess = preprocess
         self.components = init
         self.global_bias = 0.0
@@ -158,6 +161,10 @@ class WRMF:
         if isinstance(self._be, HipBackend):
             self._be.double_threshold = self._precision == "double"   # a small global bias: the double build keeps it
         return self._be
+
+    def _confidence(self):
+        """the model's `Confidence` when `preprocess` is one (it never goes down the callable path), else None"""
+        return self._preprocess if isinstance(self._preprocess, Confidence) else None
 
     def _np_dtype(self):
         return np.float64 if self._precision == "double" else np.float32
@@ -283,13 +290,20 @@ class WRMF:
         # it stands and the device produces c_ui from it, instead of the host converting to CSC first (1.4 s of 5e7 non-zeros
         # on one core, more than ten iterations of the fit) and the device converting back.  Same arrays on the device either
         # way.  A user-supplied `preprocess` is defined on the CsparseMatrix (:184-188) and keeps the conversion.
-        by_rows = sp.issparse(x) and x.format == "csr" and self._preprocess is _identity and x.has_canonical_format
+        # A `Confidence` is fitted and applied on the device, on the raw values of both orientations (below); a backend without
+        # the kernels (the CPU stand-in of the tests) gets the numpy reference here and goes on as with no preprocess at all.
+        conf = self._confidence()
+        if conf is not None:
+            x = canonical_rows(x) if hasattr(be, "confidence_apply") else conf.host_fit_transform(x)
+        plain = conf is not None or self._preprocess is _identity
+        by_rows = sp.issparse(x) and x.format == "csr" and plain and x.has_canonical_format
+        weigh = conf is not None and hasattr(be, "confidence_apply")
         if by_rows:
             c_ui = x if x.dtype == np.float64 else x.astype(np.float64)            # (named for what it holds, not its layout)
         else:
             c_ui = self._preprocess(sp.csc_matrix(x, dtype=np.float64))           # :184-188
             c_ui.sort_indices()
-        if (self._feedback != "explicit" or self._non_negative) and c_ui.nnz and c_ui.data.min() < 0:
+        if (self._feedback != "explicit" or self._non_negative) and c_ui.nnz and not weigh and c_ui.data.min() < 0:
             raise ValueError("all(c_ui@x >= 0) is not TRUE")                       # :195-197
         n_user, n_item = c_ui.shape
         k = self._rank
@@ -324,12 +338,30 @@ class WRMF:
         # one orientation crosses the boundary (f64 values as in dgCMatrix@x); the item-user orientation
         # c_iu = t_shallow(as.csr.matrix(c_ui)) (:190) and the f32 values are produced on the device
         x64 = be.to_device(c_ui.data, torch.float64)
-        up = (be.to_device(c_ui.indptr, torch.int32), be.to_device(c_ui.indices, torch.int32),
-              x64 if self._f64 else be.values_to_float(x64))
-        if by_rows:
-            d_iu, d_ui = up, be.transpose_csc(n_item, n_user, *up)
+        sum_weighted = None
+        if weigh:
+            # the raw doubles cross once; both orientations are built from them, then: moments on each, tables, apply on each.
+            # The user-major values are weighted in place in double (the checks below read them), the item-major ones straight
+            # into the fit's element type -- a cell gets the same double from either orientation, rounded once.
+            um = (be.to_device(c_ui.indptr, torch.int32), be.to_device(c_ui.indices, torch.int32), x64)
+            im = be.transpose_csc(n_item, n_user, *um)
+            mom = conf.device_fit(be, n_user, n_item, um, im)
+            user_table = conf.device_user_table(be, um, mom)
+            conf.device_apply(be, um, user_table, out="inplace")
+            w_im = conf.device_apply(be, im, user_table, item_major=True, out="inplace" if self._f64 else torch.float32)
+            if (self._feedback != "explicit" or self._non_negative) and c_ui.nnz and bool(x64.min() < 0):
+                raise ValueError("all(c_ui@x >= 0) is not TRUE")                   # :195-197, on the weighted values
+            if self._with_global_bias and self._feedback != "explicit" and not self._with_bias:
+                sum_weighted = float(x64.sum())
+            d_iu, d_ui = (um[0], um[1], x64 if self._f64 else be.values_to_float(x64)), (im[0], im[1], w_im)
+            del um, im, w_im
         else:
-            d_ui, d_iu = up, be.transpose_csc(n_user, n_item, *up)
+            up = (be.to_device(c_ui.indptr, torch.int32), be.to_device(c_ui.indices, torch.int32),
+                  x64 if self._f64 else be.values_to_float(x64))
+            if by_rows:
+                d_iu, d_ui = up, be.transpose_csc(n_item, n_user, *up)
+            else:
+                d_ui, d_iu = up, be.transpose_csc(n_user, n_item, *up)
         als = ShardedALS(be, n_user, n_item, k, d_ui, d_iu, c_ui.nnz,
                          feedback=self._feedback, lambda_=self._lambda, dynamic_lambda=self._dynamic_lambda,
                          cg_steps=self._cg_steps, with_bias=self._with_bias)
@@ -355,7 +387,7 @@ class WRMF:
         elif self._with_global_bias and self._feedback == "explicit":              # :278-284
             self.global_bias = be.subtract_mean(d_ui[2], d_iu[2])
         elif self._with_global_bias:                                               # :285-287
-            sm = float(c_ui.data.sum())
+            sm = float(c_ui.data.sum()) if sum_weighted is None else sum_weighted
             self.global_bias = sm / (sm + float(n_user) * float(n_item) - float(c_ui.nnz))
         if self._feedback == "implicit":
             als.global_bias = self.global_bias
@@ -389,6 +421,8 @@ class WRMF:
         """the users x items matrix as a canonical CSR (row = user) with float64 values, touching as little as possible: a
         canonical CSR input is used as it stands; a user `preprocess` is defined on the CsparseMatrix (:184-188) and costs
         the two conversions around it"""
+        if self._confidence() is not None:   # users x items, in numpy: the statistics of a sharded fit span the ranks' blocks
+            return self._confidence().host_fit_transform(x)
         if self._preprocess is not _identity:
             x = sp.csr_matrix(self._preprocess(sp.csc_matrix(x, dtype=np.float64)))
         elif not (sp.issparse(x) and x.format == "csr"):
@@ -595,8 +629,24 @@ class WRMF:
     def _transform_device(self, x_csr):
         a, b, ws = self._my_rows(x_csr)
         mine = x_csr[a:b] if ws > 1 else x_csr
-        xt = sp.csc_matrix(mine.T, dtype=np.float64)
-        xt = self._preprocess(xt)
+        conf = self._confidence()
+        if conf is not None and not conf.fitted:
+            raise RuntimeError("model is not fitted")
+        if conf is not None and hasattr(self._backend(), "confidence_apply"):
+            # the rows go up raw and are weighted there, users as rows: their own row moments, the item table of the fit
+            be = self._backend()
+            mine = canonical_rows(mine)
+            p, j = be.to_device(mine.indptr, torch.int32), be.to_device(mine.indices, torch.int32)
+            w = conf.device_transform(be, (p, j, be.to_device(mine.data, torch.float64)))
+            if self.global_bias != 0.0 and self._feedback == "explicit":                      # :381-382
+                w -= self.global_bias
+            csc = be.make_csc(mine.shape[1], mine.shape[0], p, j, w if self._f64 else be.values_to_float(w))
+            res = self._transform_dev(csc, mine.shape[0])
+            return self._share_rows(res, self._row_bounds, x_csr.shape[0]) if ws > 1 else res
+        if conf is not None:
+            xt = sp.csc_matrix(conf.host_transform(mine).T, dtype=np.float64)
+        else:
+            xt = self._preprocess(sp.csc_matrix(mine.T, dtype=np.float64))
         if self.global_bias != 0.0 and self._feedback == "explicit":                          # :381-382
             xt = xt.copy()
             xt.data = xt.data - self.global_bias
@@ -1435,7 +1485,10 @@ class WRMF:
         a, b, _ = self._my_rows(x)
         mine = sp.csr_matrix(x[a:b])
         mine.sum_duplicates()
-        xt = self._preprocess(sp.csc_matrix(mine.T, dtype=np.float64))   # CSC of x^T == CSR of x, as _transform_device
+        if self._confidence() is not None:   # users as rows; on the device where the backend has the kernels
+            xt = sp.csc_matrix(self._confidence().transform(mine, backend=be).T, dtype=np.float64)
+        else:
+            xt = self._preprocess(sp.csc_matrix(mine.T, dtype=np.float64))   # CSC of x^T == CSR of x, as _transform_device
         xt.sort_indices()
         tdt = self._V.dtype
         c = np.asarray(xt.data, dtype=np.float64)
