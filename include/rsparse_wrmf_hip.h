@@ -967,6 +967,53 @@ int rsparse_hip_confidence_apply_device(int kind, int n_seg, int64_t nnz, const 
 int rsparse_hip_confidence(int kind, int n_rows, int n_cols, const int32_t* p, const int32_t* j, const double* x, double a, double b,
                            int norm, int by_columns, double* out);
 
+/* The interaction matrix from an event log: one record (user, item[, value][, timestamp]) per event -- a play, a click, a
+ * purchase -- becomes the canonical CSR over the CELLS, the distinct (user, item) pairs that occur: rows in order, columns
+ * ascending and unique within a row, empty rows included; a cell whose aggregate is 0 stays a stored entry.
+ * rsparse_amd/events.py (events_reference) is the definition in numpy.  The events of a cell are taken in INPUT order.
+ *
+ *   count[c]    the number of events of the cell
+ *   latest[c]   the largest timestamp of the cell, compared through the order-preserving 64-bit map of the double's bits that
+ *               the split defines above (RSPARSE_HIP_SPLIT_LEAVE_OUT, by != NULL): exact, and -0.0 orders below +0.0
+ *   x[c]        RSPARSE_HIP_EVENTS_SUM    the sum of the cell's terms in the order stated below
+ *               RSPARSE_HIP_EVENTS_COUNT  count[c] as a double
+ *               RSPARSE_HIP_EVENTS_MAX    the largest value, by the same bit map
+ *               RSPARSE_HIP_EVENTS_LAST   the value of the event with the largest timestamp; ties go to the event LATER in the
+ *                                         input (needs timestamps)
+ * values == NULL means every value is 1.0.  The term of an event is its value v; with half_life > 0 (SUM only, needs timestamps)
+ * it is v * exp2((t - now) / half_life), every operation in double, without contraction; now is the argument when has_now != 0,
+ * else the largest timestamp of the log (by the bit map).  A cell of m <= 64 events is summed left to right in input order,
+ * starting from its first term.  A longer cell is cut into consecutive chunks of 64 events counted from its first event; every
+ * chunk is summed left to right, and the chunk sums are then summed left to right.  No floating-point atomics: the result is the
+ * reference's bit for bit (with a half life: up to the two libraries' exp2), and repeat calls are bit-identical.
+ *
+ * _device: every pointer is device memory except n_cells.  d_users / d_items: n_events ids each; d_values, d_timestamps: n_events
+ * doubles or NULL.  d_p has n_users + 1 slots; d_j, d_x, d_count, d_latest have `capacity` slots each (n_events always
+ * suffices; d_count and d_latest may be NULL; d_latest is not written without timestamps).  *n_cells receives the number of
+ * cells.  The call waits for the stream: after its first launch, to refuse an id outside [0, n_users) x [0, n_items) ->
+ * ERR_INVALID with nothing else written; after the cells are counted, to refuse a capacity below *n_cells -> ERR_INVALID with no
+ * output array written; and before it returns (its scratch, 16 or 24 bytes per event -- keys of 32 bits when
+ * bits(n_users) + bits(n_items) <= 32, bits(n) = the bits that hold 0 .. n - 1 -- plus about one byte per event, is freed then).
+ * A NaN has no place in the order of max / last / latest: the host form refuses it, the device form leaves it to the caller.
+ *
+ * Host form: host pointers; refuses a NaN in values or timestamps -> ERR_INVALID.
+ *
+ * Both: n_cells or p NULL; users or items NULL with n_events > 0; j or x NULL with n_events > 0; a negative n_events, n_users,
+ * n_items or capacity; n_events >= 2^31; an aggregate other than the four; LAST or a half life without timestamps; a half life
+ * with another aggregate than SUM (half_life <= 0 means none) -> ERR_INVALID before a device is touched.  n_events == 0 -> OK:
+ * p is all zeros and *n_cells = 0. */
+#define RSPARSE_HIP_EVENTS_SUM 0
+#define RSPARSE_HIP_EVENTS_COUNT 1
+#define RSPARSE_HIP_EVENTS_MAX 2
+#define RSPARSE_HIP_EVENTS_LAST 3
+int rsparse_hip_events_to_csr_device(int64_t n_events, int n_users, int n_items, const int32_t* d_users, const int32_t* d_items,
+                                     const double* d_values, const double* d_timestamps, int aggregate, double half_life, double now,
+                                     int has_now, int32_t* d_p, int32_t* d_j, double* d_x, int32_t* d_count, double* d_latest,
+                                     int64_t capacity, int64_t* n_cells, void* hip_stream);
+int rsparse_hip_events_to_csr(int64_t n_events, int n_users, int n_items, const int32_t* users, const int32_t* items,
+                              const double* values, const double* timestamps, int aggregate, double half_life, double now, int has_now,
+                              int32_t* p, int32_t* j, double* x, int32_t* count, double* latest, int64_t capacity, int64_t* n_cells);
+
 /* ------------------------------------------------------------------------------------------------
  * (3) fp64 device layer: als_implicit<double> / als_explicit<double> with the data resident in HBM
  * ---------------------------------------------------------------------------------------------- */

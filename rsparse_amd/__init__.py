@@ -5,6 +5,7 @@ Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit
   rsparse_amd.metrics         ap_k() / ndcg_k(), the reference's ranking metrics, and precision / recall / hit rate / MRR /
                               coverage at several cutoffs, on the device
   rsparse_amd.train_test_split  the reference's train_test_split (and leave-n-out), drawn on the device
+  rsparse_amd.from_events     the interaction matrix from an event log (sum / count / max / last, decay, latest timestamps), on the device
   rsparse_amd.Confidence      the confidence transformation of WRMF(preprocess=): BM25, TF-IDF, log, linear, on the device
   rsparse_amd.ScaleNormalize  the reference's ScaleNormalize: p-norm scaling of rows or columns
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
@@ -25,6 +26,9 @@ def __getattr__(name):
     if name in ("Confidence", "ScaleNormalize", "confidence_reference"):
         from . import confidence
         return getattr(confidence, name)
+    if name in ("from_events", "events_reference"):
+        from . import events
+        return getattr(events, name)
     if name == "metrics":
         import importlib
         return importlib.import_module(".metrics", __name__)

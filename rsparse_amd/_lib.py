@@ -125,6 +125,10 @@ SIGNATURES = {
     "rsparse_hip_confidence_table_device": (_c_int, [_c_int, _c_int, _vp, _vp, _vp, _c_dbl, _c_dbl, _c_dbl, _vp, _vp]),
     "rsparse_hip_confidence_apply_device": (_c_int, [_c_int, _c_int, _c_i64, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_dbl, _c_dbl, _vp, _c_int, _vp]),
     "rsparse_hip_confidence": (_c_int, [_c_int, _c_int, _c_int, _vp, _vp, _vp, _c_dbl, _c_dbl, _c_int, _c_int, _vp]),
+    "rsparse_hip_events_to_csr_device": (_c_int, [_c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_dbl, _c_dbl, _c_int, _vp, _vp, _vp, _vp, _vp,
+                                                  _c_i64, ctypes.POINTER(_c_i64), _vp]),
+    "rsparse_hip_events_to_csr": (_c_int, [_c_i64, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_dbl, _c_dbl, _c_int, _vp, _vp, _vp, _vp, _vp,
+                                           _c_i64, ctypes.POINTER(_c_i64)]),
     "rsparse_hip_sparse_approximation": (_c_int, [_c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_int, _vp]),
     "rsparse_hip_csc_f64_create_device": (_c_int, [_c_int, _c_int, _vp, _vp, _vp, ctypes.POINTER(_vp)]),
     "rsparse_hip_csc_f64_destroy": (_c_int, [_vp]),

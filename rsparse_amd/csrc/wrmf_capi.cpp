@@ -2427,6 +2427,90 @@ int rsparse_hip_confidence(int kind, int n_rows, int n_cols, const int32_t* p, c
   return RSPARSE_HIP_OK;
 }
 
+namespace {
+// what both forms of rsparse_hip_events_to_csr check before anything else
+int events_args(int64_t n_events, int n_users, int n_items, const void* users, const void* items, const void* timestamps, int aggregate,
+                double half_life, const void* p, const void* j, const void* x, int64_t capacity, const void* n_cells) {
+  if (n_events < 0 || n_users < 0 || n_items < 0 || capacity < 0)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_events < 0, n_users < 0, n_items < 0 or capacity < 0)");
+  if (n_events >= (1ll << 31)) return fail(RSPARSE_HIP_ERR_INVALID, "n_events >= 2^31: cut the log into several calls");
+  if (!p || !n_cells) return fail(RSPARSE_HIP_ERR_INVALID, "p or n_cells is NULL");
+  if (n_events > 0 && (!users || !items || !j || !x)) return fail(RSPARSE_HIP_ERR_INVALID, "users, items, j or x is NULL");
+  if (aggregate < RSPARSE_HIP_EVENTS_SUM || aggregate > RSPARSE_HIP_EVENTS_LAST)
+    return fail(RSPARSE_HIP_ERR_INVALID, "unknown aggregate " + std::to_string(aggregate));
+  if (aggregate == RSPARSE_HIP_EVENTS_LAST && !timestamps) return fail(RSPARSE_HIP_ERR_INVALID, "the aggregate `last` needs timestamps");
+  if (half_life > 0.0 && !timestamps) return fail(RSPARSE_HIP_ERR_INVALID, "a half life needs timestamps");
+  if (half_life > 0.0 && aggregate != RSPARSE_HIP_EVENTS_SUM) return fail(RSPARSE_HIP_ERR_INVALID, "a half life goes with the aggregate `sum` only");
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+
+int rsparse_hip_events_to_csr_device(int64_t n_events, int n_users, int n_items, const int32_t* d_users, const int32_t* d_items,
+                                     const double* d_values, const double* d_timestamps, int aggregate, double half_life, double now,
+                                     int has_now, int32_t* d_p, int32_t* d_j, double* d_x, int32_t* d_count, double* d_latest,
+                                     int64_t capacity, int64_t* n_cells, void* stream) {
+  int rc = events_args(n_events, n_users, n_items, d_users, d_items, d_timestamps, aggregate, half_life, d_p, d_j, d_x, capacity, n_cells);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = g_ws.ensure_device())) return rc;
+  *n_cells = 0;
+  if (n_events == 0) {
+    HIP_TRY(hipMemsetAsync(d_p, 0, ((size_t)n_users + 1) * 4, s));
+    return RSPARSE_HIP_OK;
+  }
+  int status = 0;
+  hipError_t e = events_to_csr_device(n_events, n_users, n_items, d_users, d_items, d_values, d_timestamps, aggregate, half_life, has_now,
+                                      now, d_p, d_j, d_x, d_count, d_latest, capacity, n_cells, s, &status);
+  if (e != hipSuccess) return hip_fail(e, "events_to_csr_device");
+  if (status == 1) return fail(RSPARSE_HIP_ERR_INVALID, "a user or item id outside [0, n_users) x [0, n_items)");
+  if (status == 2)
+    return fail(RSPARSE_HIP_ERR_INVALID, "the capacity is " + std::to_string(capacity) + ", the log has " + std::to_string(*n_cells) + " cells");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_events_to_csr(int64_t n_events, int n_users, int n_items, const int32_t* users, const int32_t* items,
+                              const double* values, const double* timestamps, int aggregate, double half_life, double now, int has_now,
+                              int32_t* p, int32_t* j, double* x, int32_t* count, double* latest, int64_t capacity, int64_t* n_cells) {
+  int rc = events_args(n_events, n_users, n_items, users, items, timestamps, aggregate, half_life, p, j, x, capacity, n_cells);
+  if (rc) return rc;
+  for (int64_t e = 0; e < n_events; e++)
+    if ((values && values[e] != values[e]) || (timestamps && timestamps[e] != timestamps[e]))
+      return fail(RSPARSE_HIP_ERR_INVALID, "NaN in values or timestamps");
+  *n_cells = 0;
+  if (n_events == 0) {
+    for (int64_t u = 0; u <= n_users; u++) p[u] = 0;
+    return RSPARSE_HIP_OK;
+  }
+  const size_t n = (size_t)n_events, np1 = (size_t)n_users + 1;
+  DevBuf dU, dI, dV, dT, dP, dJ, dX, dC, dL;
+  HIP_TRY(upload_host(dU, users, n));
+  HIP_TRY(upload_host(dI, items, n));
+  if (values) HIP_TRY(upload_host(dV, values, n));
+  if (timestamps) HIP_TRY(upload_host(dT, timestamps, n));
+  // (the host form sizes the device outputs itself: n_events slots always suffice; the caller's capacity is judged below)
+  const bool want_latest = latest && timestamps;
+  HIP_TRY(dP.alloc(np1 * 4));
+  HIP_TRY(dJ.alloc(n * 4));
+  HIP_TRY(dX.alloc(n * 8));
+  if (count) HIP_TRY(dC.alloc(n * 4));
+  if (want_latest) HIP_TRY(dL.alloc(n * 8));
+  rc = rsparse_hip_events_to_csr_device(n_events, n_users, n_items, dU.as<int32_t>(), dI.as<int32_t>(), values ? dV.as<double>() : nullptr,
+                                        timestamps ? dT.as<double>() : nullptr, aggregate, half_life, now, has_now, dP.as<int32_t>(),
+                                        dJ.as<int32_t>(), dX.as<double>(), count ? dC.as<int32_t>() : nullptr,
+                                        want_latest ? dL.as<double>() : nullptr, n_events, n_cells, nullptr);
+  if (rc) return rc;
+  if (*n_cells > capacity)
+    return fail(RSPARSE_HIP_ERR_INVALID, "the capacity is " + std::to_string(capacity) + ", the log has " + std::to_string(*n_cells) + " cells");
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t nc = (size_t)*n_cells;
+  HIP_TRY(hipMemcpy(p, dP.p, np1 * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(j, dJ.p, nc * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(x, dX.p, nc * 8, hipMemcpyDeviceToHost));
+  if (count) HIP_TRY(hipMemcpy(count, dC.p, nc * 4, hipMemcpyDeviceToHost));
+  if (want_latest) HIP_TRY(hipMemcpy(latest, dL.p, nc * 8, hipMemcpyDeviceToHost));
+  return RSPARSE_HIP_OK;
+}
+
 int rsparse_hip_take_numeric_failures(int64_t* unresolved_out, int64_t* fallback_out) {
   if (!unresolved_out) return fail(RSPARSE_HIP_ERR_INVALID, "unresolved_out is NULL");
   // counts a stateless call found on the device when it started and set aside (see StaleFailures): still the resident layer's

@@ -492,6 +492,16 @@ hipError_t launch_confidence_apply(int kind, const int32_t* p, const int32_t* i,
                                    const double* seg_table, const double* idx_table, int n_idx, int seg_is_item, double a, double b,
                                    void* out, int out_float, hipStream_t s);
 
+// the interaction matrix from an event log (wrmf_events.hip; the aggregates and their summation order are defined in
+// rsparse_wrmf_hip.h).  n >= 1 events, n_users, n_items >= 1; every pointer is device memory, values / ts / count / latest may be
+// null.  Allocates its scratch (16 or 24 bytes per event, plus about one byte per event for the long cells) and
+// waits for the stream: after the pack launch to read the id flag, after the scan to read the number of cells, and at the end.
+// *status: 0 = done; 1 = an id outside the shape (nothing was written); 2 = *n_cells > capacity (nothing was written).
+hipError_t events_to_csr_device(int64_t n, int n_users, int n_items, const int32_t* users, const int32_t* items, const double* values,
+                                const double* ts, int aggregate, double half_life, int has_now, double now, int32_t* p, int32_t* j,
+                                double* x, int32_t* count, double* latest, int64_t capacity, int64_t* n_cells, hipStream_t s,
+                                int* status);
+
 // item-to-item cosine similarity (wrmf_similar.hip): the operands of the top-k path above.
 // launch_normalize_items: V (fp32, or fp64 when f64) n_items x ld row-major, columns [c0, c0 + r), 1 <= r <= 256 ->
 // Vn64 / Vn32 (n_items x r, compact) with unit rows, flags[item] = 1 and a row of zeros where the sum of squares is zero or

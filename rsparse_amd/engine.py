@@ -535,6 +535,29 @@ class HipBackend:
         n_tr, n_te = int(train_p[-1]), int(test_p[-1])
         return (train_p, train_j[:n_tr], None if v is None else train_v[:n_tr], test_p, test_j[:n_te], None if v is None else test_v[:n_te])
 
+    def events_to_csr(self, users, items, values, timestamps, n_users, n_items, aggregate="sum", half_life=None, now=None):
+        """the canonical CSR over the cells of an event log, made on the device (wrmf_events.hip; rsparse_amd/events.py
+        events_reference is the definition): users, items int32, values / timestamps float64 or None, one per event, on the
+        device.  -> (p, j, x, count, latest) on the device, sliced to the number of cells; latest None without timestamps."""
+        from .events import AGGREGATES
+        assert users.dtype == torch.int32 and items.dtype == torch.int32 and users.numel() == items.numel()
+        assert values is None or values.dtype == torch.float64
+        assert timestamps is None or timestamps.dtype == torch.float64
+        n, dev = int(users.numel()), self.device
+        p = torch.empty(int(n_users) + 1, dtype=torch.int32, device=dev)
+        j = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        x = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        count = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        latest = None if timestamps is None else torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        n_cells = ctypes.c_int64(0)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(self.lib.rsparse_hip_events_to_csr_device(
+            n, int(n_users), int(n_items), users.data_ptr(), items.data_ptr(), ptr(values), ptr(timestamps), AGGREGATES[aggregate],
+            0.0 if half_life is None else float(half_life), 0.0 if now is None else float(now), int(now is not None), p.data_ptr(),
+            j.data_ptr(), x.data_ptr(), count.data_ptr(), ptr(latest), max(n, 1), ctypes.byref(n_cells), self._stream()))
+        c = int(n_cells.value)
+        return p, j[:c], x[:c], count[:c], None if latest is None else latest[:c]
+
     def confidence_moments(self, p, x, power):
         """(out, total) on the device: out[r] = sum |x|^power over segment r of the arrays (p, x) -- p int32 from 0, x float64 --
         and the sum over all entries (one double), wrmf_confidence.hip: a fixed summation order, repeat calls bit-identical"""
