@@ -18,7 +18,9 @@
 // chip's power limit (1.57 GHz: DESIGN.md 3.2 "Round 6").
 //
 // Per row: stream (M1 from two fp16 terms of 2^e sqrt(c - 1) x, three products; M2 from the leading fp16 term of 2^e x alone, one
-// product: it feeds only the loss, as in wrmf_ne.hip) -> unscale -> conjugate gradient with A p evaluated FROM THE TILES: tile
+// product: it feeds only the loss, as in wrmf_ne.hip) -> conjugate gradient with A p evaluated FROM THE TILES, which stay as the
+// stream left them: the powers of two that undo the operand scales are applied where an entry is read (one fused multiply-add
+// with XtX's entry in a product, one multiply per sum in the loss form), not in a pass over the accumulator file.  Tile
 // (I, K) of the lower triangle holds, at lane (n, hf), register v, the entry [(block I, row n)][(block K, row rho(v, hf))] -- row r of
 // block I being coordinate 4 r + I, see "COORDINATES" below --, so
 //     (A p)_I += sum over the lane's registers of  tile * p[column]          ("direct": 16 FMAs per tile, then the halves added)
@@ -121,9 +123,10 @@ struct CgmSmem {
 };
 
 // y_I(n) += sum_v tile[v] * pc[K][v] over the lane's registers, for every lower tile; off-diagonal tiles also feed the transposed
-// part.  RD(t, v) reads element v of tile t.
+// part.  RD(t, v) reads element v of tile t as the stream left it: `un` (a power of two, wave-uniform) times it is M1's entry, and
+// un * raw + g is the very number that a pass over the tiles followed by an addition gave (the scaling is exact).
 template <class RD, class GV, class WV>
-__device__ __forceinline__ void cgm_matvec(RD&& rd, GV&& gtile, WV& sw, const int n, const int hf, const int ln,
+__device__ __forceinline__ void cgm_matvec(RD&& rd, GV&& gtile, WV& sw, const float un, const int n, const int hf, const int ln,
                                            const float (&pr)[4], float (&out)[4]) {
   // pr[I] = p[32 I + n] (lane = row).  The column-ordered copy: pc[K][v] = p[32 K + rho(v, hf)] from LDS
   wave_sync();
@@ -151,7 +154,7 @@ __device__ __forceinline__ void cgm_matvec(RD&& rd, GV&& gtile, WV& sw, const in
       gtile(std::integral_constant<int, T>{}, g);
       static_for<16>([&](auto vt) {
         constexpr int v = decltype(vt)::value;
-        const float av = rd(std::integral_constant<int, T>{}, std::integral_constant<int, v>{}) + g[v];
+        const float av = fmaf(rd(std::integral_constant<int, T>{}, std::integral_constant<int, v>{}), un, g[v]);
         dsum[I] = fmaf(av, pc[v], dsum[I]);
         if constexpr (I > K) ts[v] = fmaf(av, pr[I], ts[v]);
       });
@@ -570,28 +573,14 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
       }
       wave_sync();   // (the ring's LDS becomes the solve's)
     }
-    // ---- unscale (powers of two: exact); the right-hand side and the warm start per lane = row ----
+    // ---- the tiles stay raw: M1 = un_m1 * (a0..a159), M2 = un_m2 * (a160..a255, hi) with the powers of two below, applied where the
+    // solve and the loss form read an entry (a pass over the 320 registers cost ~830 instructions per row and changed no mantissa
+    // bit).  The right-hand side and the warm start per lane = row ----
     ln = lane;
     asm volatile("" : "+v"(ln));
     const int n = ln & 31, hf = ln >> 5;
-    const float un_m1 = (un1 * un1) * (SYM ? unw : unw), un_m2 = un1 * un1;
+    const float un_m1 = (un1 * un1) * unw, un_m2 = un1 * un1;   // (wave-uniform: scalar registers)
     MF_DRAIN();
-    static_for<160>([&](auto rt) {
-      constexpr int R = decltype(rt)::value;
-      mf_wr<R>(mf_rd<R>() * un_m1);
-    });
-    static_for<96>([&](auto rt) {
-      constexpr int R = 160 + decltype(rt)::value;
-      mf_wr<R>(mf_rd<R>() * un_m2);
-    });
-    {
-      float um = un_m2;   // (a register of this point's own: held as a pair from the kernel's first lines it was the one spill)
-      asm volatile("" : "+v"(um));
-#pragma unroll
-      for (int t = 0; t < 4; t++)
-#pragma unroll
-        for (int e = 0; e < 16; e++) hi[t][e] *= um;
-    }
     float b[4], x[4];
     if constexpr (SYM) {
 #pragma unroll
@@ -621,12 +610,12 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
     };
     // ---- cg_solver_implicit (wrmf_implicit.hpp:8-32) on A = XtX + M1 ----
     float r[4], p[4], ap[4];
-    cgm_matvec(rd_m1, g_tile, sw, n, hf, ln, x, ap);
+    cgm_matvec(rd_m1, g_tile, sw, un_m1, n, hf, ln, x, ap);
 #pragma unroll
     for (int I = 0; I < 4; I++) { r[I] = b[I] - ap[I]; p[I] = r[I]; }
     double rsold = (double)cgm_dot(r, r, hf);
     for (int stp = 0; stp < a.cg_steps; stp++) {
-      cgm_matvec(rd_m1, g_tile, sw, n, hf, ln, p, ap);
+      cgm_matvec(rd_m1, g_tile, sw, un_m1, n, hf, ln, p, ap);
       const float alpha = (float)(rsold / (double)cgm_dot(p, ap, hf));
 #pragma unroll
       for (int I = 0; I < 4; I++) { x[I] = fmaf(alpha, p[I], x[I]); r[I] = fmaf(-alpha, ap[I], r[I]); }
@@ -650,7 +639,8 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
       else return hi[T - 6][v];
     };
     // y^T (M1 + M2) y from the lower tiles: sum over the tiles of y_I(n) * (tile row . y_K), off-diagonal tiles twice -- the
-    // "direct" half of a product only, both matrices in one pass
+    // "direct" half of a product only, both matrices in one pass, each in a sum of its own over the raw entries:
+    // tile row . y_K = un_m1 * sum m1_raw y + un_m2 * sum m2_raw y
     float yMy;
     {
       wave_sync();
@@ -671,11 +661,13 @@ __device__ __forceinline__ void als_cg_mf_body(const AlsArgs& a, const int32_t* 
         static_for<4 - K>([&](auto st) {
           constexpr int I = K + decltype(st)::value;
           constexpr int T = mf_tid(I, K);
-          float d = 0.f;
+          float d1 = 0.f, d2 = 0.f;
           static_for<16>([&](auto vt) {
             constexpr int v = decltype(vt)::value;
-            d = fmaf(rd_m1(std::integral_constant<int, T>{}, vt) + rd_m2(std::integral_constant<int, T>{}, vt), pc[v], d);
+            d1 = fmaf(rd_m1(std::integral_constant<int, T>{}, vt), pc[v], d1);
+            d2 = fmaf(rd_m2(std::integral_constant<int, T>{}, vt), pc[v], d2);
           });
+          const float d = fmaf(un_m1, d1, un_m2 * d2);
           part = fmaf(I == K ? d : 2.f * d, x[I], part);
         });
       });
