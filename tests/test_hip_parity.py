@@ -330,8 +330,10 @@ def test_config2_scale_properties():
 @pytest.mark.parametrize("k", [128, 64, 40])
 @pytest.mark.parametrize("implicit", [True, False])
 def test_cholesky_long_rows(k, implicit):
-    """Rows up to ~6000 non-zeros through the exact solver: rows beyond 4096 non-zeros take the second launch of
-    wrmf_chol.hip (two-level accumulation of the rank-one updates), the rest the main one; per-row bound."""
+    """Rows up to ~6000 non-zeros through the exact solver, per-row bound.  At these ranks (36..128, no bias operands) the
+    normal-equation kernel owns every row beyond 512 non-zeros (a.ne_chol) and the two-level LONG launch of wrmf_chol.hip is
+    empty (grid_long = 0); the rows up to 512 take the wave-per-row or k x k kernels.  The LONG launch (rows beyond 4096
+    non-zeros of the biased fits and of the ranks below 36) is covered by tests/test_bias_exact_rows.py."""
     fb = "implicit" if implicit else "explicit"
     n_fix, n_solve = 9000, 120
     d = synth.make_dataset(n_solve, n_fix, seed=31 + k, mean_deg=900, d_max=6000, feedback=fb, device="cpu")
