@@ -705,6 +705,39 @@ int rsparse_hip_sparse_approximation(int n_rows, int n_cols, const int32_t* p, c
                                      const double* X, const double* Y, int rank, double* values_out);
 
 /* ------------------------------------------------------------------------------------------------
+ * soft-ALS (soft_svd / soft_impute, R/SoftALS.R): one half-iteration as one fused pass over a CSR matrix
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Edges of the kernel (wrmf_softals.hip), for callers that test it: a wave walks its stored positions in chunks of
+ * RSPARSE_HIP_SOFTALS_CHUNK, and no wave takes fewer than (RSPARSE_HIP_SOFTALS_SPLIT - 1) consecutive positions of the launch,
+ * so a row of RSPARSE_HIP_SOFTALS_SPLIT entries or more is always split between waves (a shorter one may be, where it lies). */
+#define RSPARSE_HIP_SOFTALS_CHUNK 256
+#define RSPARSE_HIP_SOFTALS_SPLIT 1025
+
+/* Per row of a CSR pattern (d_p: n_rows + 1 slots from 0, d_j: 0-based columns, d_x: the values), with d_M (n_cols x r) and
+ * d_W (n_rows x r, nullable) row-major and w, s, t HOST vectors of r doubles (w and t nullable):
+ *   res_t          = x_t - (w ? sum_c w[c] * d_W[row, c] * d_M[j_t, c] : 0)
+ *   d_out[row, c]  = s[c] * sum_t res_t * d_M[j_t, c]  +  (t ? t[c] * d_W[row, c] : 0)
+ *   *d_sumsq       = sum over all stored positions of res_t^2          (nullable, device double[1])
+ * w = t = NULL, s = 1: the product CSR x dense.  w = t = NULL, s = d / (d + lambda): a half-iteration of soft_svd
+ * (R/SoftALS.R:99-102).  w = d, t = s o d: a half-iteration of soft_impute with the `%*% diag(sqrt(d))` that follows it
+ * (:68-94, :157, :174); (*d_sumsq + lambda sum(d)) / nnz is its loss (:83).
+ * Every sum is accumulated in double for both element types and rounded once at the store.  No atomics: partial sums of a row
+ * that is split are added in an order fixed by the pattern and the launch geometry, a repeated call returns the same bits.
+ * j need not be sorted and may repeat; a row with a column outside [0, n_cols) comes out NaN (and so does *d_sumsq) and nothing
+ * outside the operands is read for it; a row without stored positions gets t o W, or zeros.  A valid p is a precondition.
+ * w, s, t are copied before the call returns; the call is enqueued on `stream` without synchronisation and uses the library's
+ * grow-only workspace for the partial sums (calls on one host thread are ordered by their stream, as everywhere here).
+ * NULL among d_p, d_j, d_x, d_M, d_out, s; w or t without d_W; n_rows < 0, n_cols < 0, r < 1 -> ERR_INVALID;
+ * r > RSPARSE_HIP_MAX_RANK (both element types) -> ERR_UNSUPPORTED; n_rows == 0 -> OK; all before a device is touched. */
+int rsparse_hip_softals_half_device(const int32_t* d_p, const int32_t* d_j, const float* d_x, const float* d_M, const float* d_W,
+                                    int n_rows, int n_cols, int r, const double* w, const double* s, const double* t,
+                                    float* d_out, double* d_sumsq, void* stream);
+int rsparse_hip_softals_half_f64_device(const int32_t* d_p, const int32_t* d_j, const double* d_x, const double* d_M,
+                                        const double* d_W, int n_rows, int n_cols, int r, const double* w, const double* s,
+                                        const double* t, double* d_out, double* d_sumsq, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * why this item: per-item contributions to a score (Hu, Koren and Volinsky, section 5; `explain` of the `implicit` library)
  * ---------------------------------------------------------------------------------------------- */
 

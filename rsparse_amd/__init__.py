@@ -8,6 +8,9 @@ Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit
   rsparse_amd.from_events     the interaction matrix from an event log (sum / count / max / last, decay, latest timestamps), on the device
   rsparse_amd.Confidence      the confidence transformation of WRMF(preprocess=): BM25, TF-IDF, log, linear, on the device
   rsparse_amd.ScaleNormalize  the reference's ScaleNormalize: p-norm scaling of rows or columns
+  rsparse_amd.PureSVD         the reference's PureSVD recommender (R/model_PureSVD.R) with WRMF's inference surface
+  rsparse_amd.soft_svd        soft_svd / soft_impute (R/SoftALS.R): soft-thresholded SVD of a sparse matrix by alternating least
+                              squares, on a fused residual-SpMM kernel
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
   rsparse_amd.engine          device-resident, row-sharded driver (one process per GPU)
   rsparse_amd.synth           synthetic interaction matrices for the BASELINE configs
@@ -29,6 +32,12 @@ def __getattr__(name):
     if name in ("from_events", "events_reference"):
         from . import events
         return getattr(events, name)
+    if name in ("soft_svd", "soft_impute", "soft_als_reference", "softals_half_reference"):
+        from . import softals
+        return getattr(softals, name)
+    if name == "PureSVD":
+        from .puresvd import PureSVD
+        return PureSVD
     if name == "metrics":
         import importlib
         return importlib.import_module(".metrics", __name__)

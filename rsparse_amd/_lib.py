@@ -14,6 +14,8 @@ OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_RUNTIME, ERR_NUMERIC = 0, 1, 2, 3, 4
 SOLVER_CHOLESKY, SOLVER_CG, SOLVER_NNLS = 0, 1, 2
 MAX_NEGATIVES = 8192   # RSPARSE_HIP_MAX_NEGATIVES: negatives per row of rsparse_hip_sample_negatives*
 MAX_CUTOFFS = 16   # RSPARSE_HIP_MAX_CUTOFFS: cutoffs of one rsparse_hip_hit_metrics* call
+MAX_RANK, MAX_RANK_F64 = 256, 128   # RSPARSE_HIP_MAX_RANK, RSPARSE_HIP_MAX_RANK_F64
+SOFTALS_CHUNK, SOFTALS_SPLIT = 256, 1025   # RSPARSE_HIP_SOFTALS_CHUNK / _SPLIT: the edges of the soft-ALS kernel (wrmf_softals.hip)
 RANKS_BATCH = 1024  # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that the rank count takes at a time
 
 _c_int, _c_uint, _c_dbl, _c_i64, _c_u64 = ctypes.c_int, ctypes.c_uint, ctypes.c_double, ctypes.c_int64, ctypes.c_uint64
@@ -101,6 +103,8 @@ SIGNATURES = {
                                             _vp, _vp, _vp]),
     "rsparse_hip_score_pairs_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_dbl, _vp, _vp, _vp, _vp, _vp]),
     "rsparse_hip_score_pairs_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_dbl, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_softals_half_device": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_softals_half_f64_device": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rsparse_hip_top_candidates_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl, _vp,
                                                    _vp, _vp]),
     "rsparse_hip_top_candidates_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl,

@@ -65,6 +65,7 @@ struct Workspace {
   GrowBuf<char> sim_buf{all};     // item-to-item similarity (wrmf_similar.hip): a batch's gathered queries and self-exclusion slots
   GrowBuf<double> score_buf{all};   // pointwise predictions (wrmf_score.hip): the scores of a call that asks for the error sums only;
                                     // top-k within candidate lists (wrmf_candidates.hip): its scores / keys, bits and row lists
+  GrowBuf<double> softals_buf{all};   // soft-ALS half-iteration (wrmf_softals.hip): w, s, t and the partial sums of split rows
   GrowBuf<float> mf_G{all};       // wrmf_chol_mf.hip at rank 65..127: XtX padded to 128 x 128
   GrowBuf<float> pad_buf{all};    // ranks that are not a multiple of 4: the padded copies of X, Y, XtX, rhs_init (run_half_iteration)
   int device = -1;
@@ -1947,6 +1948,19 @@ int rsparse_hip_score_pairs_device(const float* d_U, const float* d_V, int n_row
                               buf = g_ws.score_buf;
                               return (int)RSPARSE_HIP_OK;
                             });
+}
+
+// `_f64_device`: wrmf_f64_capi.cpp
+int rsparse_hip_softals_half_device(const int32_t* d_p, const int32_t* d_j, const float* d_x, const float* d_M, const float* d_W,
+                                    int n_rows, int n_cols, int r, const double* w, const double* s, const double* t,
+                                    float* d_out, double* d_sumsq, void* stream) {
+  return softals_half_device(d_p, d_j, d_x, d_M, d_W, n_rows, n_cols, r, w, s, t, d_out, d_sumsq, (hipStream_t)stream,
+                             [](size_t n, double*& buf) {
+                               if (int rc = g_ws.ensure_device()) return rc;
+                               HIP_TRY(g_ws.softals_buf.ensure(n));
+                               buf = g_ws.softals_buf;
+                               return (int)RSPARSE_HIP_OK;
+                             });
 }
 
 // `_f64_device` and the host form rsparse_hip_top_candidates: wrmf_f64_capi.cpp

@@ -227,6 +227,33 @@ int score_pairs_device(const T* d_U, const T* d_V, int n_rows, int n_cols, int r
   return RSPARSE_HIP_OK;
 }
 
+// rsparse_hip_softals_half_device / _f64_device (kernels: wrmf_softals.hip).  `workspace` as above: the coefficient vectors and
+// the partial sums of the rows that are split live there.
+template <class T, class Workspace>
+int softals_half_device(const int32_t* d_p, const int32_t* d_j, const T* d_x, const T* d_M, const T* d_W, int n_rows, int n_cols,
+                        int r, const double* w, const double* sc, const double* t, T* d_out, double* d_sumsq, hipStream_t s,
+                        Workspace workspace) {
+  if (!d_p || !d_j || !d_x || !d_M || !d_out || !sc)
+    return fail(RSPARSE_HIP_ERR_INVALID, "the pattern (p, j, x), M, out or s is NULL");
+  if ((w || t) && !d_W) return fail(RSPARSE_HIP_ERR_INVALID, "w or t without W");
+  if (n_rows < 0 || n_cols < 0 || r < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, n_cols < 0 or r < 1)");
+  if (r > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "r > 256 is not on the device path");
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  double* ws = nullptr;
+  if (int rc = workspace(softals_ws_doubles(r), ws)) return rc;
+  double coef[768];
+  for (int c = 0; c < 256; c++) {
+    coef[c] = w && c < r ? w[c] : 0.0;
+    coef[256 + c] = c < r ? sc[c] : 0.0;
+    coef[512 + c] = t && c < r ? t[c] : 0.0;
+  }
+  // (pageable host memory: the runtime has taken its copy when the call returns)
+  HIP_TRY(hipMemcpyAsync(ws, coef, sizeof(coef), hipMemcpyHostToDevice, s));
+  hipError_t e = launch_softals_half(d_p, d_j, d_x, d_M, d_W, n_rows, n_cols, r, w != nullptr, t != nullptr, d_out, d_sumsq, ws, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_softals_half");
+  return RSPARSE_HIP_OK;
+}
+
 // rsparse_hip_top_candidates_device / _f64_device (kernels: wrmf_score.hip, wrmf_candidates.hip).  `workspace` as above: the
 // scores / keys, the admissibility bits and the row lists live there.  The number of candidates is read back first (this call
 // waits for the stream once): the workspace is sized by it.  max_rank: the side's ceiling.

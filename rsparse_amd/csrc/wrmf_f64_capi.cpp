@@ -80,6 +80,7 @@ struct WorkspaceF64 {
   GrowBuf<double> repack{all};     // explicit feedback with biases, conjugate gradient: X', Y', shifted ratings
   GrowBuf<double> score{all};      // pointwise predictions (wrmf_score.hip): the scores of a call that asks for the error sums only;
                                    // top-k within candidate lists (wrmf_candidates.hip): its scores / keys, bits and row lists
+  GrowBuf<double> softals{all};    // soft-ALS half-iteration (wrmf_softals.hip): w, s, t and the partial sums of split rows
   int device = -1;
   int ensure() {
     int dev = 0;
@@ -360,6 +361,19 @@ int rsparse_hip_score_pairs_f64_device(const double* d_U, const double* d_V, int
                               buf = g_w64.score;
                               return (int)RSPARSE_HIP_OK;
                             });
+}
+
+// one soft-ALS half-iteration on double operands (kernels: wrmf_softals.hip; the fp32 form: wrmf_capi.cpp)
+int rsparse_hip_softals_half_f64_device(const int32_t* d_p, const int32_t* d_j, const double* d_x, const double* d_M,
+                                        const double* d_W, int n_rows, int n_cols, int r, const double* w, const double* s,
+                                        const double* t, double* d_out, double* d_sumsq, void* stream) {
+  return softals_half_device(d_p, d_j, d_x, d_M, d_W, n_rows, n_cols, r, w, s, t, d_out, d_sumsq, (hipStream_t)stream,
+                             [](size_t n, double*& buf) {
+                               if (int rc = g_w64.ensure()) return rc;
+                               HIP_TRY(g_w64.softals.ensure(n));
+                               buf = g_w64.softals;
+                               return (int)RSPARSE_HIP_OK;
+                             });
 }
 
 // top-k within per-user candidate lists from double factors (kernels: wrmf_score.hip, wrmf_candidates.hip; the fp32 form:

@@ -401,6 +401,14 @@ hipError_t launch_score_pairs(const T* U, const T* V, int n_rows, int n_cols, in
 hipError_t launch_score_error_sums(const double* scores, const double* actual, const int32_t* P, int n_rows, double* sse,
                                    double* sae, hipStream_t s);
 
+// one soft-ALS half-iteration over a CSR matrix (wrmf_softals.hip), T = float or double, 1 <= r <= 256: out[row] = s o sum_t res_t
+// M[J[t]] + t o W[row], res_t = X[t] - (w o W[row]) . M[J[t]], *sumsq = sum res^2 (nullable).  ws: softals_ws_doubles(r) doubles
+// whose first 768 hold w, s, t at strides of 256 (zeros where absent and beyond r); res: W and w are used, has_t: W and t are.
+size_t softals_ws_doubles(int r);
+template <class T>
+hipError_t launch_softals_half(const int32_t* P, const int32_t* J, const T* X, const T* M, const T* W, int n_rows, int n_cols, int r,
+                               bool res, bool has_t, T* out, double* sumsq, double* ws, hipStream_t s);
+
 // top-k within per-user candidate lists (wrmf_candidates.hip), T = float or double, 1 <= topk <= kTopLargeMax: for every row of
 // the CSR pattern (cand_p: n_users + 1 slots, absolute positions into cand_j; p0 = cand_p[0], nnz = cand_p[n_users] - p0, read by
 // the caller; columns ascending and unique within a row) the topk best admissible candidates by launch_score_pairs' scores

@@ -774,6 +774,33 @@ class HipBackend:
                       None if sse is None else sse.data_ptr(), None if sae is None else sae.data_ptr(), self._stream()))
         return scores, sse, sae
 
+    def softals_half(self, p, j, x, M, W=None, w=None, s=None, t=None, out=None, want_sumsq=False):
+        """one soft-ALS half-iteration over a CSR matrix (p, j: int32, x: its values; wrmf_softals.hip), M (n_cols x r) gathered
+        by column index, W (n_rows x r) the rows' own factor, w / s / t host vectors of r doubles (rsparse_amd.softals is the
+        definition):  res_t = x_t - (w o W[row]) . M[j_t],  out[row] = s o sum_t res_t M[j_t] + t o W[row].  Without w and t it is
+        CSR x dense scaled by s (s = None: ones).  x, M, W share one element type (float32 or float64), every sum is in double.
+        -> (out in that type, sum of res^2 as a float64[1] tensor or None), both on the device."""
+        assert p.dtype == torch.int32 and j.dtype == torch.int32 and M.dtype in (torch.float32, torch.float64) and x.dtype == M.dtype
+        if (w is not None or t is not None) and W is None:
+            raise ValueError("softals_half: w or t without W")
+        n, r = int(p.numel()) - 1, int(M.shape[1])
+        M = M if M.is_contiguous() else M.contiguous()
+        if W is not None:
+            assert W.dtype == M.dtype and tuple(W.shape) == (n, r)
+            W = W if W.is_contiguous() else W.contiguous()
+        vec = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(r)
+        w, s, t = vec(w), vec(np.ones(r) if s is None else s), vec(t)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        if out is None:
+            out = torch.empty((n, r), dtype=M.dtype, device=M.device)
+        assert out.dtype == M.dtype and tuple(out.shape) == (n, r) and out.is_contiguous()
+        sumsq = torch.zeros(1, dtype=torch.float64, device=M.device) if want_sumsq else None
+        fn = self.lib.rsparse_hip_softals_half_f64_device if M.dtype == torch.float64 else self.lib.rsparse_hip_softals_half_device
+        _lib.check(fn(p.data_ptr(), j.data_ptr(), x.data_ptr() if x.numel() else p.data_ptr(), M.data_ptr() if M.numel() else p.data_ptr(),
+                      None if W is None else W.data_ptr(), n, int(M.shape[0]), r, ptr(w), ptr(s), ptr(t),
+                      out.data_ptr() if n else p.data_ptr(), None if sumsq is None else sumsq.data_ptr(), self._stream()))
+        return out, sumsq
+
     def explain_pairs(self, V, base, diag, diag_per_nnz, x_p, x_j, wa, wb, t_p, t_j):
         """what every interaction of a row contributes to the scores of the row's target items (wrmf_explain.hip): for the users
         of the CSR rows (x_p, x_j: int32 on the device; wa, wb: the assembly and contribution weight of every stored position, in
