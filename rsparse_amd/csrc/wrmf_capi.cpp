@@ -1093,7 +1093,7 @@ int rsparse_hip_top_product_device(const float* d_U, const float* d_V, int n_use
   if (!d_U || !d_V || !d_res || !d_scores) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
   if (n_users < 0 || n_items < 0 || rank <= 0 || k < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions");
   if (rank > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 256 is not on the device path");
-  if (k > RSPARSE_HIP_MAX_TOPK_LARGE) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
+  if (int rc = refuse_large_k(k)) return rc;
   if (n_exclude > 0 && !d_excl0) return fail(RSPARSE_HIP_ERR_INVALID, "exclude is NULL");
   if (k > RSPARSE_HIP_MAX_TOPK) {   // the large-k path (wrmf_topk_large.hip): its key matrix and lists in the grow-only workspace
     if (n_users == 0) return RSPARSE_HIP_OK;
@@ -1124,7 +1124,7 @@ int rsparse_hip_top_product_f64_device(const float* d_U, const float* d_V, const
   if ((d_U64 == nullptr) != (d_V64 == nullptr)) return fail(RSPARSE_HIP_ERR_INVALID, "the double factors come as a pair");
   if (n_users < 0 || n_items < 0 || rank <= 0 || k < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions");
   if (rank > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 256 is not on the device path");
-  if (k > RSPARSE_HIP_MAX_TOPK_LARGE) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
+  if (int rc = refuse_large_k(k)) return rc;
   if (n_users == 0) return RSPARSE_HIP_OK;
   if (k > RSPARSE_HIP_MAX_TOPK) {   // the large-k path: kc = k + extra candidates (at most 10240), re-scored in double
     if (n_exclude > 0 && !d_excl0) return fail(RSPARSE_HIP_ERR_INVALID, "exclude is NULL");
@@ -1151,89 +1151,7 @@ int rsparse_hip_top_product_f64_device(const float* d_U, const float* d_V, const
   return RSPARSE_HIP_OK;
 }
 
-int rsparse_hip_top_product(const double* x, const double* y, int nr, int nc, int rank, unsigned k, unsigned n_threads,
-                            const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude, int n_exclude,
-                            double glob_mean, int32_t* res, double* scores) {
-  (void)n_threads;
-  if (!x || !y || !res || !scores) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
-  if (nr < 0 || nc < 0 || rank <= 0 || k < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions");
-  if (rank > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 256 is not on the device path");
-  if (k > RSPARSE_HIP_MAX_TOPK_LARGE) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
-  if (n_exclude < 0 || (n_exclude > 0 && !exclude)) return fail(RSPARSE_HIP_ERR_INVALID, "bad exclude");
-  // x is nr x rank column-major -> row-major fp32; y (rank x nc column-major) already has item vectors contiguous
-  std::vector<float> U((size_t)nr * rank), V((size_t)nc * rank);
-  std::vector<double> U64((size_t)nr * rank);
-  for (int j = 0; j < nr; j++)
-    for (int r = 0; r < rank; r++) {
-      U64[(size_t)j * rank + r] = x[(size_t)r * nr + j];
-      U[(size_t)j * rank + r] = (float)x[(size_t)r * nr + j];
-    }
-  for (size_t e = 0; e < V.size(); e++) V[e] = (float)y[e];
-  std::vector<int32_t> ex;
-  for (int e = 0; e < n_exclude; e++)
-    if (exclude[e] >= 1 && exclude[e] <= nc) ex.push_back(exclude[e] - 1);   // R indices are 1-based
-  std::sort(ex.begin(), ex.end());
-  ex.erase(std::unique(ex.begin(), ex.end()), ex.end());
-  const int64_t nr_nnz = (nr_p && nr > 0) ? (int64_t)nr_p[nr] : 0;
-  DevBuf dU, dV, dU64, dV64, dP, dJ, dE, dR, dS;
-  HIP_TRY(dU.alloc(U.size() * 4));
-  HIP_TRY(dV.alloc(V.size() * 4));
-  HIP_TRY(dU64.alloc(U64.size() * 8));
-  HIP_TRY(dV64.alloc(V.size() * 8));
-  HIP_TRY(dR.alloc((size_t)nr * k * 4));
-  HIP_TRY(dS.alloc((size_t)nr * k * 8));
-  if (!U.empty()) HIP_TRY(hipMemcpy(dU.p, U.data(), U.size() * 4, hipMemcpyHostToDevice));
-  if (!V.empty()) HIP_TRY(hipMemcpy(dV.p, V.data(), V.size() * 4, hipMemcpyHostToDevice));
-  if (!U64.empty()) HIP_TRY(hipMemcpy(dU64.p, U64.data(), U64.size() * 8, hipMemcpyHostToDevice));
-  if (!V.empty()) HIP_TRY(hipMemcpy(dV64.p, y, V.size() * 8, hipMemcpyHostToDevice));   // rank x nc column-major = item vectors contiguous
-  const bool filter = nr_nnz > 0 && nr_j;   // `not_empty_filter_matrix`, matrix_top_product.cpp:33
-  if (filter) {
-    HIP_TRY(dP.alloc(((size_t)nr + 1) * 4));
-    HIP_TRY(dJ.alloc((size_t)nr_nnz * 4));
-    HIP_TRY(hipMemcpy(dP.p, nr_p, ((size_t)nr + 1) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dJ.p, nr_j, (size_t)nr_nnz * 4, hipMemcpyHostToDevice));
-  }
-  if (!ex.empty()) {
-    HIP_TRY(dE.alloc(ex.size() * 4));
-    HIP_TRY(hipMemcpy(dE.p, ex.data(), ex.size() * 4, hipMemcpyHostToDevice));
-  }
-  // candidates from the fp32 pass, scores and order from the doubles as given (find_top_product multiplies arma::mat)
-  int rc = rsparse_hip_top_product_f64_device(dU.as<float>(), dV.as<float>(), dU64.as<double>(), dV64.as<double>(), nr, nc,
-                                              rank, (int)k, -1, filter ? dP.as<int32_t>() : nullptr,
-                                              filter ? dJ.as<int32_t>() : nullptr, ex.empty() ? nullptr : dE.as<int32_t>(),
-                                              (int)ex.size(), glob_mean, dR.as<int32_t>(), dS.as<double>(), nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  std::vector<int32_t> hr((size_t)nr * k);
-  std::vector<double> hs((size_t)nr * k);
-  if (!hr.empty()) {
-    HIP_TRY(hipMemcpy(hr.data(), dR.p, hr.size() * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hs.data(), dS.p, hs.size() * 8, hipMemcpyDeviceToHost));
-  }
-  for (int j = 0; j < nr; j++)
-    for (unsigned c = 0; c < k; c++) {
-      res[(size_t)c * nr + j] = hr[(size_t)j * k + c];
-      scores[(size_t)c * nr + j] = hs[(size_t)j * k + c];
-    }
-  return RSPARSE_HIP_OK;
-}
-
 namespace {
-// the arguments every form of the item-to-item similarity checks before a device is touched
-int similar_items_args(int n_items, int r, int n_q, int k, int n_exclude, const void* exclude) {
-  if (n_items < 0 || n_q < 0 || k < 1 || r < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_items < 0, n_q < 0, k < 1 or no latent coordinate)");
-  if (n_exclude < 0 || (n_exclude > 0 && !exclude)) return fail(RSPARSE_HIP_ERR_INVALID, "bad exclude");
-  if (r > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 256 latent coordinates are not on the device path");
-  if (k > RSPARSE_HIP_MAX_TOPK_LARGE) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
-  return RSPARSE_HIP_OK;
-}
-int normalize_items_args(const void* d_V, int n_items, int ld, int c0, int c1, const void* d_Vn32, const void* d_Vn64,
-                         const void* d_flags) {
-  if (n_items < 0 || c0 < 0 || c1 - c0 < 1 || c1 > ld) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_items < 0 or not 0 <= c0 < c1 <= ld)");
-  if (c1 - c0 > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 256 latent coordinates are not on the device path");
-  if (n_items > 0 && (!d_V || !d_Vn32 || !d_Vn64 || !d_flags)) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
-  return RSPARSE_HIP_OK;
-}
 // rows of queries per call of the top-k path: what HipBackend.top_product uses (the same re-scoring budget above k = 256)
 int similar_items_batch(int k) {
   int64_t B = 1 << 18;
@@ -1281,80 +1199,6 @@ int rsparse_hip_similar_items_device(const float* d_Vn32, const double* d_Vn64, 
   return RSPARSE_HIP_OK;
 }
 
-int rsparse_hip_similar_items(const double* components, int rank, int n_items, int first_row, int n_rows, const int32_t* query,
-                              int n_q, int k, int exclude_self, const int32_t* exclude, int n_exclude, int32_t* res,
-                              double* scores) {
-  int rc = similar_items_args(n_items, n_rows, n_q, k, n_exclude, exclude);
-  if (rc) return rc;
-  if (first_row < 0 || rank < 1 || (int64_t)first_row + n_rows > rank)
-    return fail(RSPARSE_HIP_ERR_INVALID, "first_row / n_rows do not select rows of components");
-  if (!components || (n_q > 0 && (!query || !res || !scores))) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix, query or output");
-  std::vector<int32_t> q0((size_t)n_q);
-  for (int q = 0; q < n_q; q++) {   // R indices are 1-based
-    if (query[q] < 1 || query[q] > n_items) return fail(RSPARSE_HIP_ERR_INVALID, "query item id out of range");
-    q0[q] = query[q] - 1;
-  }
-  if (n_q == 0) return RSPARSE_HIP_OK;
-  const int r = n_rows;
-  // rank x n_items column-major = item vectors contiguous: the device form's n_items x ld row-major with ld = rank
-  DevBuf dV, dVn32, dVn64, dF, dQ, dE, dR, dS;
-  HIP_TRY(dV.alloc((size_t)n_items * rank * 8));
-  HIP_TRY(dVn32.alloc((size_t)n_items * r * 4));
-  HIP_TRY(dVn64.alloc((size_t)n_items * r * 8));
-  HIP_TRY(dF.alloc((size_t)n_items * 4));
-  HIP_TRY(dQ.alloc((size_t)n_q * 4));
-  HIP_TRY(dR.alloc((size_t)n_q * k * 4));
-  HIP_TRY(dS.alloc((size_t)n_q * k * 8));
-  HIP_TRY(hipMemcpy(dV.p, components, (size_t)n_items * rank * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dQ.p, q0.data(), (size_t)n_q * 4, hipMemcpyHostToDevice));
-  hipError_t e = launch_normalize_items(dV.p, true, n_items, rank, first_row, r, dVn32.as<float>(), dVn64.as<double>(),
-                                        dF.as<int32_t>(), nullptr);
-  if (e != hipSuccess) return hip_fail(e, "launch_normalize_items");
-  HIP_TRY(hipDeviceSynchronize());
-  // never returned: the caller's exclusions and the degenerate items
-  std::vector<int32_t> flags((size_t)n_items), ex;
-  HIP_TRY(hipMemcpy(flags.data(), dF.p, (size_t)n_items * 4, hipMemcpyDeviceToHost));
-  for (int e2 = 0; e2 < n_exclude; e2++)
-    if (exclude[e2] >= 1 && exclude[e2] <= n_items) ex.push_back(exclude[e2] - 1);
-  for (int i = 0; i < n_items; i++)
-    if (flags[i]) ex.push_back(i);
-  std::sort(ex.begin(), ex.end());
-  ex.erase(std::unique(ex.begin(), ex.end()), ex.end());
-  if (!ex.empty()) {
-    HIP_TRY(dE.alloc(ex.size() * 4));
-    HIP_TRY(hipMemcpy(dE.p, ex.data(), ex.size() * 4, hipMemcpyHostToDevice));
-  }
-  rc = rsparse_hip_similar_items_device(dVn32.as<float>(), dVn64.as<double>(), n_items, r, dQ.as<int32_t>(), n_q, k, exclude_self,
-                                        ex.empty() ? nullptr : dE.as<int32_t>(), (int)ex.size(), dR.as<int32_t>(),
-                                        dS.as<double>(), nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  std::vector<int32_t> hr((size_t)n_q * k);
-  std::vector<double> hs((size_t)n_q * k);
-  HIP_TRY(hipMemcpy(hr.data(), dR.p, hr.size() * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(hs.data(), dS.p, hs.size() * 8, hipMemcpyDeviceToHost));
-  for (int j = 0; j < n_q; j++)
-    for (int c = 0; c < k; c++) {
-      res[(size_t)c * n_q + j] = hr[(size_t)j * k + c];
-      scores[(size_t)c * n_q + j] = hs[(size_t)j * k + c];
-    }
-  return RSPARSE_HIP_OK;
-}
-
-namespace {
-// the arguments both forms of rsparse_hip_ranking_metrics check before anything else
-int ranking_metrics_args(const int32_t* pred, int n_users, int k, const int32_t* p, const int32_t* j, const double* x,
-                         const double* ap_out, const double* ndcg_out) {
-  if (!ap_out && !ndcg_out) return fail(RSPARSE_HIP_ERR_INVALID, "ap_out and ndcg_out are both NULL");
-  if (!pred || !p || !j) return fail(RSPARSE_HIP_ERR_INVALID, "predictions or actual (p, j) is NULL");
-  if (ndcg_out && !x) return fail(RSPARSE_HIP_ERR_INVALID, "ndcg needs the relevances: actual_x is NULL");
-  if (n_users < 0 || k < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0 or k < 1)");
-  if (k > RSPARSE_HIP_MAX_TOPK_LARGE)
-    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
-  return RSPARSE_HIP_OK;
-}
-}  // namespace
-
 int rsparse_hip_ranking_metrics_device(const int32_t* d_pred, int n_users, int k, const int32_t* d_p, const int32_t* d_j,
                                        const double* d_x, double* d_ap_out, double* d_ndcg_out, void* stream) {
   int rc = ranking_metrics_args(d_pred, n_users, k, d_p, d_j, d_x, d_ap_out, d_ndcg_out);
@@ -1366,63 +1210,6 @@ int rsparse_hip_ranking_metrics_device(const int32_t* d_pred, int n_users, int k
   if (e != hipSuccess) return hip_fail(e, "launch_ranking_metrics");
   return RSPARSE_HIP_OK;
 }
-
-int rsparse_hip_ranking_metrics(const int32_t* pred, int n_users, int k, const int32_t* p, const int32_t* j, const double* x,
-                                double* ap_out, double* ndcg_out) {
-  int rc = ranking_metrics_args(pred, n_users, k, p, j, x, ap_out, ndcg_out);
-  if (rc) return rc;
-  // the dgRMatrix slots: p from 0, non-decreasing; j strictly ascending within a row (what the kernels' binary search needs)
-  if (p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "actual_p[0] != 0");
-  for (int u = 0; u < n_users; u++) {
-    if (p[u + 1] < p[u]) return fail(RSPARSE_HIP_ERR_INVALID, "actual_p decreases");
-    for (int32_t e = p[u] + 1; e < p[u + 1]; e++)
-      if (j[e] <= j[e - 1]) return fail(RSPARSE_HIP_ERR_INVALID, "actual_j is not strictly ascending within a row");
-  }
-  if (n_users == 0) return RSPARSE_HIP_OK;
-  const size_t nk = (size_t)n_users * k, nnz = (size_t)p[n_users];
-  std::vector<int32_t> rows(nk);   // column-major (R's integer matrix) -> the row-major lists of the device form
-  for (int c = 0; c < k; c++)
-    for (int u = 0; u < n_users; u++) rows[(size_t)u * k + c] = pred[(size_t)c * n_users + u];
-  DevBuf dPred, dP, dJ, dX, dAp, dNdcg;
-  HIP_TRY(dPred.alloc(nk * 4));
-  HIP_TRY(dP.alloc(((size_t)n_users + 1) * 4));
-  HIP_TRY(dJ.alloc(std::max<size_t>(nnz, 1) * 4));
-  if (ndcg_out) HIP_TRY(dX.alloc(std::max<size_t>(nnz, 1) * 8));
-  if (ap_out) HIP_TRY(dAp.alloc((size_t)n_users * 8));
-  if (ndcg_out) HIP_TRY(dNdcg.alloc((size_t)n_users * 8));
-  HIP_TRY(hipMemcpy(dPred.p, rows.data(), nk * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dP.p, p, ((size_t)n_users + 1) * 4, hipMemcpyHostToDevice));
-  if (nnz) HIP_TRY(hipMemcpy(dJ.p, j, nnz * 4, hipMemcpyHostToDevice));
-  if (nnz && ndcg_out) HIP_TRY(hipMemcpy(dX.p, x, nnz * 8, hipMemcpyHostToDevice));
-  rc = rsparse_hip_ranking_metrics_device(dPred.as<int32_t>(), n_users, k, dP.as<int32_t>(), dJ.as<int32_t>(),
-                                          ndcg_out ? dX.as<double>() : nullptr, ap_out ? dAp.as<double>() : nullptr,
-                                          ndcg_out ? dNdcg.as<double>() : nullptr, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  if (ap_out) HIP_TRY(hipMemcpy(ap_out, dAp.p, (size_t)n_users * 8, hipMemcpyDeviceToHost));
-  if (ndcg_out) HIP_TRY(hipMemcpy(ndcg_out, dNdcg.p, (size_t)n_users * 8, hipMemcpyDeviceToHost));
-  return RSPARSE_HIP_OK;
-}
-
-namespace {
-// the arguments both forms of rsparse_hip_hit_metrics check before anything else
-int hit_metrics_args(const int32_t* pred, int n_users, int k, const int32_t* p, const int32_t* j, const int32_t* cutoffs,
-                     int n_cutoffs, bool any_output, const int32_t* first_seen, int n_items) {
-  if (!any_output) return fail(RSPARSE_HIP_ERR_INVALID, "every output is NULL");
-  if (!pred || !p || !j || !cutoffs) return fail(RSPARSE_HIP_ERR_INVALID, "predictions, actual (p, j) or cutoffs is NULL");
-  if (n_users < 0 || k < 1 || n_cutoffs < 1)
-    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0, k < 1 or n_cutoffs < 1)");
-  if (first_seen && n_items < 1) return fail(RSPARSE_HIP_ERR_INVALID, "first_seen needs n_items >= 1");
-  if (n_cutoffs > RSPARSE_HIP_MAX_CUTOFFS)
-    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 16 cutoffs (RSPARSE_HIP_MAX_CUTOFFS) are not on the device path");
-  if (k > RSPARSE_HIP_MAX_TOPK_LARGE)
-    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
-  for (int t = 0; t < n_cutoffs; t++)
-    if (cutoffs[t] < 1 || cutoffs[t] > k || (t > 0 && cutoffs[t] <= cutoffs[t - 1]))
-      return fail(RSPARSE_HIP_ERR_INVALID, "cutoffs must be strictly ascending within 1 .. k");
-  return RSPARSE_HIP_OK;
-}
-}  // namespace
 
 int rsparse_hip_hit_metrics_device(const int32_t* d_pred, int n_users, int k, const int32_t* d_p, const int32_t* d_j,
                                    const int32_t* cutoffs, int n_cutoffs, int32_t* d_hits, int32_t* d_first, double* d_precision,
@@ -1438,111 +1225,7 @@ int rsparse_hip_hit_metrics_device(const int32_t* d_pred, int n_users, int k, co
   return RSPARSE_HIP_OK;
 }
 
-int rsparse_hip_hit_metrics(const int32_t* pred, int n_users, int k, const int32_t* p, const int32_t* j, const int32_t* cutoffs,
-                            int n_cutoffs, int32_t* hits, int32_t* first, double* precision, double* recall, double* hit,
-                            double* mrr, int32_t* first_seen, int n_items) {
-  const bool any = hits || first || precision || recall || hit || mrr || first_seen;
-  int rc = hit_metrics_args(pred, n_users, k, p, j, cutoffs, n_cutoffs, any, first_seen, n_items);
-  if (rc) return rc;
-  // the dgRMatrix slots: p from 0, non-decreasing; j strictly ascending within a row (what the kernel's binary search needs)
-  if (p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "actual_p[0] != 0");
-  for (int u = 0; u < n_users; u++) {
-    if (p[u + 1] < p[u]) return fail(RSPARSE_HIP_ERR_INVALID, "actual_p decreases");
-    for (int32_t e = p[u] + 1; e < p[u + 1]; e++)
-      if (j[e] <= j[e - 1]) return fail(RSPARSE_HIP_ERR_INVALID, "actual_j is not strictly ascending within a row");
-  }
-  if (first_seen) std::fill(first_seen, first_seen + n_items, INT32_MAX);
-  if (n_users == 0) return RSPARSE_HIP_OK;
-  const int T = n_cutoffs;
-  const size_t nk = (size_t)n_users * k, nt = (size_t)n_users * T, nnz = (size_t)p[n_users];
-  std::vector<int32_t> rows(nk);   // column-major (R's integer matrix) -> the row-major lists of the device form
-  for (int c = 0; c < k; c++)
-    for (int u = 0; u < n_users; u++) rows[(size_t)u * k + c] = pred[(size_t)c * n_users + u];
-  DevBuf dPred, dP, dJ, dHits, dFirst, dSeen, dD[4];
-  double* outs[4] = {precision, recall, hit, mrr};
-  HIP_TRY(dPred.alloc(nk * 4));
-  HIP_TRY(dP.alloc(((size_t)n_users + 1) * 4));
-  HIP_TRY(dJ.alloc(std::max<size_t>(nnz, 1) * 4));
-  if (hits) HIP_TRY(dHits.alloc(nt * 4));
-  if (first) HIP_TRY(dFirst.alloc((size_t)n_users * 4));
-  for (int q = 0; q < 4; q++)
-    if (outs[q]) HIP_TRY(dD[q].alloc(nt * 8));
-  HIP_TRY(hipMemcpy(dPred.p, rows.data(), nk * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dP.p, p, ((size_t)n_users + 1) * 4, hipMemcpyHostToDevice));
-  if (nnz) HIP_TRY(hipMemcpy(dJ.p, j, nnz * 4, hipMemcpyHostToDevice));
-  if (first_seen) {
-    HIP_TRY(dSeen.alloc((size_t)n_items * 4));
-    HIP_TRY(hipMemcpy(dSeen.p, first_seen, (size_t)n_items * 4, hipMemcpyHostToDevice));
-  }
-  rc = rsparse_hip_hit_metrics_device(dPred.as<int32_t>(), n_users, k, dP.as<int32_t>(), dJ.as<int32_t>(), cutoffs, T,
-                                      hits ? dHits.as<int32_t>() : nullptr, first ? dFirst.as<int32_t>() : nullptr,
-                                      outs[0] ? dD[0].as<double>() : nullptr, outs[1] ? dD[1].as<double>() : nullptr,
-                                      outs[2] ? dD[2].as<double>() : nullptr, outs[3] ? dD[3].as<double>() : nullptr,
-                                      first_seen ? dSeen.as<int32_t>() : nullptr, n_items, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  // n x T row-major -> R's column-major matrices
-  if (hits) {
-    std::vector<int32_t> h(nt);
-    HIP_TRY(hipMemcpy(h.data(), dHits.p, nt * 4, hipMemcpyDeviceToHost));
-    for (int u = 0; u < n_users; u++)
-      for (int t = 0; t < T; t++) hits[(size_t)t * n_users + u] = h[(size_t)u * T + t];
-  }
-  if (first) HIP_TRY(hipMemcpy(first, dFirst.p, (size_t)n_users * 4, hipMemcpyDeviceToHost));
-  std::vector<double> d(nt);
-  for (int q = 0; q < 4; q++) {
-    if (!outs[q]) continue;
-    HIP_TRY(hipMemcpy(d.data(), dD[q].p, nt * 8, hipMemcpyDeviceToHost));
-    for (int u = 0; u < n_users; u++)
-      for (int t = 0; t < T; t++) outs[q][(size_t)t * n_users + u] = d[(size_t)u * T + t];
-  }
-  if (first_seen) HIP_TRY(hipMemcpy(first_seen, dSeen.p, (size_t)n_items * 4, hipMemcpyDeviceToHost));
-  return RSPARSE_HIP_OK;
-}
-
 namespace {
-// the lists and cutoffs that every entry of the beyond-accuracy metrics checks before anything else (the rules of hit_metrics_args)
-int list_args(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, bool any_output, int n_items) {
-  if (!any_output) return fail(RSPARSE_HIP_ERR_INVALID, "every output is NULL");
-  if (!pred || !cutoffs) return fail(RSPARSE_HIP_ERR_INVALID, "predictions or cutoffs is NULL");
-  if (n_users < 0 || k < 1 || n_cutoffs < 1)
-    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0, k < 1 or n_cutoffs < 1)");
-  if (n_items < 1) return fail(RSPARSE_HIP_ERR_INVALID, "n_items < 1");
-  if (n_cutoffs > RSPARSE_HIP_MAX_CUTOFFS)
-    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 16 cutoffs (RSPARSE_HIP_MAX_CUTOFFS) are not on the device path");
-  if (k > RSPARSE_HIP_MAX_TOPK_LARGE)
-    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
-  for (int t = 0; t < n_cutoffs; t++)
-    if (cutoffs[t] < 1 || cutoffs[t] > k || (t > 0 && cutoffs[t] <= cutoffs[t - 1]))
-      return fail(RSPARSE_HIP_ERR_INVALID, "cutoffs must be strictly ascending within 1 .. k");
-  return RSPARSE_HIP_OK;
-}
-int list_metrics_args(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, const int32_t* item_count,
-                      const int64_t* item_info, int n_items, const void* valid, const void* count_sum, const void* info_sum,
-                      const void* popularity, const void* novelty, const void* exposure) {
-  const bool any = valid || count_sum || info_sum || popularity || novelty || exposure;
-  int rc = list_args(pred, n_users, k, cutoffs, n_cutoffs, any, n_items);
-  if (rc) return rc;
-  if ((count_sum || popularity) && !item_count) return fail(RSPARSE_HIP_ERR_INVALID, "count_sum / popularity need item_count");
-  if ((info_sum || novelty) && !item_info) return fail(RSPARSE_HIP_ERR_INVALID, "info_sum / novelty need item_info");
-  return RSPARSE_HIP_OK;
-}
-// the window of the factors: the rules of normalize_items_args
-int window_args(int n_items, int ld, int c0, int c1) {
-  if (n_items < 0 || c0 < 0 || c1 - c0 < 1 || c1 > ld)
-    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_items < 0 or not 0 <= c0 < c1 <= ld)");
-  if (c1 - c0 > RSPARSE_HIP_MAX_RANK)
-    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 256 latent coordinates are not on the device path");
-  return RSPARSE_HIP_OK;
-}
-int list_diversity_args(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, const void* V, int n_items,
-                        int ld, int c0, int c1, const void* counted, const void* diversity) {
-  int rc = list_args(pred, n_users, k, cutoffs, n_cutoffs, counted || diversity, n_items);
-  if (rc) return rc;
-  if (!V) return fail(RSPARSE_HIP_ERR_INVALID, "the factor matrix is NULL");
-  return window_args(n_items, ld, c0, c1);
-}
-
 int item_inv_norms_device(const void* d_V, bool f64, int n_items, int ld, int c0, int c1, double* d_inv, void* stream) {
   int rc = window_args(n_items, ld, c0, c1);
   if (rc) return rc;
@@ -1567,48 +1250,6 @@ int list_diversity_device(const int32_t* d_pred, int n_users, int k, const int32
   if (e != hipSuccess) return hip_fail(e, "launch_list_diversity");
   return RSPARSE_HIP_OK;
 }
-
-// column-major (R's integer matrix) -> the row-major lists of the device forms
-std::vector<int32_t> lists_row_major(const int32_t* pred, int n_users, int k) {
-  std::vector<int32_t> rows((size_t)n_users * k);
-  for (int c = 0; c < k; c++)
-    for (int u = 0; u < n_users; u++) rows[(size_t)u * k + c] = pred[(size_t)c * n_users + u];
-  return rows;
-}
-// n x T row-major on the device -> a column-major host matrix of 4- or 8-byte elements
-int fetch_col_major(const DevBuf& d, int n_users, int T, void* out, size_t es) {
-  std::vector<char> h((size_t)n_users * T * es);
-  HIP_TRY(hipMemcpy(h.data(), d.p, h.size(), hipMemcpyDeviceToHost));
-  char* o = static_cast<char*>(out);
-  for (int u = 0; u < n_users; u++)
-    for (int t = 0; t < T; t++) std::memcpy(o + ((size_t)t * n_users + u) * es, h.data() + ((size_t)u * T + t) * es, es);
-  return RSPARSE_HIP_OK;
-}
-
-int list_diversity_host(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, const void* V, bool f64,
-                        int n_items, int ld, int c0, int c1, int32_t* counted, double* diversity) {
-  int rc = list_diversity_args(pred, n_users, k, cutoffs, n_cutoffs, V, n_items, ld, c0, c1, counted, diversity);
-  if (rc || n_users == 0) return rc;
-  const int T = n_cutoffs;
-  const size_t nk = (size_t)n_users * k, nt = (size_t)n_users * T, vb = (size_t)n_items * ld * (f64 ? 8 : 4);
-  const std::vector<int32_t> rows = lists_row_major(pred, n_users, k);
-  DevBuf dPred, dV, dInv, dCnt, dDiv;
-  HIP_TRY(dPred.alloc(nk * 4));
-  HIP_TRY(dV.alloc(vb));
-  HIP_TRY(dInv.alloc((size_t)n_items * 8));
-  if (counted) HIP_TRY(dCnt.alloc(nt * 4));
-  if (diversity) HIP_TRY(dDiv.alloc(nt * 8));
-  HIP_TRY(hipMemcpy(dPred.p, rows.data(), nk * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dV.p, V, vb, hipMemcpyHostToDevice));
-  if ((rc = item_inv_norms_device(dV.p, f64, n_items, ld, c0, c1, dInv.as<double>(), nullptr))) return rc;
-  rc = list_diversity_device(dPred.as<int32_t>(), n_users, k, cutoffs, T, dV.p, f64, n_items, ld, c0, c1, dInv.as<double>(),
-                             counted ? dCnt.as<int32_t>() : nullptr, diversity ? dDiv.as<double>() : nullptr, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  if (counted && (rc = fetch_col_major(dCnt, n_users, T, counted, sizeof(*counted)))) return rc;
-  if (diversity && (rc = fetch_col_major(dDiv, n_users, T, diversity, sizeof(*diversity)))) return rc;
-  return RSPARSE_HIP_OK;
-}
 }  // namespace
 
 int rsparse_hip_list_metrics_device(const int32_t* d_pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs,
@@ -1624,65 +1265,6 @@ int rsparse_hip_list_metrics_device(const int32_t* d_pred, int n_users, int k, c
                                      (d_info_sum || d_novelty) ? d_item_info : nullptr, n_items, d_valid, d_count_sum, d_info_sum,
                                      d_popularity, d_novelty, d_exposure, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "launch_list_metrics");
-  return RSPARSE_HIP_OK;
-}
-
-int rsparse_hip_list_metrics(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs,
-                             const int32_t* item_count, const int64_t* item_info, int n_items, int32_t* valid, int64_t* count_sum,
-                             int64_t* info_sum, double* popularity, double* novelty, int32_t* exposure) {
-  int rc = list_metrics_args(pred, n_users, k, cutoffs, n_cutoffs, item_count, item_info, n_items, valid, count_sum, info_sum,
-                             popularity, novelty, exposure);
-  if (rc) return rc;
-  if (item_count)
-    for (int i = 0; i < n_items; i++)
-      if (item_count[i] < 0) return fail(RSPARSE_HIP_ERR_INVALID, "item_count holds a negative value");
-  if (item_info)
-    for (int i = 0; i < n_items; i++)
-      if (item_info[i] < 0 || item_info[i] >= ((int64_t)1 << 40))
-        return fail(RSPARSE_HIP_ERR_INVALID, "item_info must lie in 0 <= v < 2^40");
-  const int T = n_cutoffs;
-  if (exposure) std::fill(exposure, exposure + (size_t)n_items * T, 0);
-  if (n_users == 0) return RSPARSE_HIP_OK;
-  const size_t nk = (size_t)n_users * k, nt = (size_t)n_users * T, ne = (size_t)n_items * T;
-  const std::vector<int32_t> rows = lists_row_major(pred, n_users, k);
-  const bool use_count = item_count && (count_sum || popularity), use_info = item_info && (info_sum || novelty);
-  DevBuf dPred, dCount, dInfo, dValid, dCs, dIs, dPop, dNov, dExp;
-  HIP_TRY(dPred.alloc(nk * 4));
-  HIP_TRY(hipMemcpy(dPred.p, rows.data(), nk * 4, hipMemcpyHostToDevice));
-  if (use_count) {
-    HIP_TRY(dCount.alloc((size_t)n_items * 4));
-    HIP_TRY(hipMemcpy(dCount.p, item_count, (size_t)n_items * 4, hipMemcpyHostToDevice));
-  }
-  if (use_info) {
-    HIP_TRY(dInfo.alloc((size_t)n_items * 8));
-    HIP_TRY(hipMemcpy(dInfo.p, item_info, (size_t)n_items * 8, hipMemcpyHostToDevice));
-  }
-  if (valid) HIP_TRY(dValid.alloc(nt * 4));
-  if (count_sum) HIP_TRY(dCs.alloc(nt * 8));
-  if (info_sum) HIP_TRY(dIs.alloc(nt * 8));
-  if (popularity) HIP_TRY(dPop.alloc(nt * 8));
-  if (novelty) HIP_TRY(dNov.alloc(nt * 8));
-  if (exposure) {
-    HIP_TRY(dExp.alloc(ne * 4));
-    HIP_TRY(hipMemset(dExp.p, 0, ne * 4));
-  }
-  rc = rsparse_hip_list_metrics_device(dPred.as<int32_t>(), n_users, k, cutoffs, T, use_count ? dCount.as<int32_t>() : nullptr,
-                                       use_info ? dInfo.as<int64_t>() : nullptr, n_items, valid ? dValid.as<int32_t>() : nullptr,
-                                       count_sum ? dCs.as<int64_t>() : nullptr, info_sum ? dIs.as<int64_t>() : nullptr,
-                                       popularity ? dPop.as<double>() : nullptr, novelty ? dNov.as<double>() : nullptr,
-                                       exposure ? dExp.as<int32_t>() : nullptr, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  if (valid && (rc = fetch_col_major(dValid, n_users, T, valid, sizeof(*valid)))) return rc;
-  if (count_sum && (rc = fetch_col_major(dCs, n_users, T, count_sum, sizeof(*count_sum)))) return rc;
-  if (info_sum && (rc = fetch_col_major(dIs, n_users, T, info_sum, sizeof(*info_sum)))) return rc;
-  if (popularity && (rc = fetch_col_major(dPop, n_users, T, popularity, sizeof(*popularity)))) return rc;
-  if (novelty && (rc = fetch_col_major(dNov, n_users, T, novelty, sizeof(*novelty)))) return rc;
-  if (exposure) {   // T x n_items per interval -> n_items x T column-major: the same layout, cumulated along the cutoffs
-    HIP_TRY(hipMemcpy(exposure, dExp.p, ne * 4, hipMemcpyDeviceToHost));
-    for (int t = 1; t < T; t++)
-      for (int i = 0; i < n_items; i++) exposure[(size_t)t * n_items + i] += exposure[(size_t)(t - 1) * n_items + i];
-  }
   return RSPARSE_HIP_OK;
 }
 
@@ -1706,31 +1288,7 @@ int rsparse_hip_list_diversity_f64_device(const int32_t* d_pred, int n_users, in
                                stream);
 }
 
-int rsparse_hip_list_diversity(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, const float* V,
-                               int n_items, int ld, int c0, int c1, int32_t* counted, double* diversity) {
-  return list_diversity_host(pred, n_users, k, cutoffs, n_cutoffs, V, false, n_items, ld, c0, c1, counted, diversity);
-}
-int rsparse_hip_list_diversity_f64(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, const double* V,
-                                   int n_items, int ld, int c0, int c1, int32_t* counted, double* diversity) {
-  return list_diversity_host(pred, n_users, k, cutoffs, n_cutoffs, V, true, n_items, ld, c0, c1, counted, diversity);
-}
-
 namespace {
-// what both forms of the MMR re-ranking check before anything else
-int mmr_rerank_args(const int32_t* lists, const double* scores, int n_users, int n_pool, int k, double trade_off, const void* V,
-                    int n_items, int ld, int c0, int c1, const void* items) {
-  if (!lists || !scores) return fail(RSPARSE_HIP_ERR_INVALID, "lists or scores is NULL");
-  if (!V) return fail(RSPARSE_HIP_ERR_INVALID, "the factor matrix is NULL");
-  if (!items) return fail(RSPARSE_HIP_ERR_INVALID, "the items output is NULL");
-  if (n_users < 0 || n_pool < 1 || k < 1 || k > n_pool)
-    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0 or not 1 <= k <= n_pool)");
-  if (!(trade_off >= 0.0 && trade_off <= 1.0)) return fail(RSPARSE_HIP_ERR_INVALID, "trade_off must lie in [0, 1]");   // (NaN too)
-  if (n_items < 1) return fail(RSPARSE_HIP_ERR_INVALID, "n_items < 1");
-  if (n_pool > RSPARSE_HIP_MAX_TOPK_LARGE)
-    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "a pool of more than 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
-  return window_args(n_items, ld, c0, c1);
-}
-
 int mmr_rerank_device(const int32_t* d_lists, const double* d_scores, int n_users, int n_pool, int k, double trade_off, const void* d_V,
                       bool f64, int n_items, int ld, int c0, int c1, const double* d_inv, int32_t* d_items, double* d_picked,
                       int32_t* d_positions, double* d_objective, void* stream) {
@@ -1742,41 +1300,6 @@ int mmr_rerank_device(const int32_t* d_lists, const double* d_scores, int n_user
   hipError_t e = launch_mmr_rerank(d_lists, d_scores, n_users, n_pool, k, trade_off, d_V, f64, n_items, ld, c0, c1 - c0, d_inv, d_items,
                                    d_picked, d_positions, d_objective, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "launch_mmr_rerank");
-  return RSPARSE_HIP_OK;
-}
-
-int mmr_rerank_host(const int32_t* lists, const double* scores, int n_users, int n_pool, int k, double trade_off, const void* V,
-                    bool f64, int n_items, int ld, int c0, int c1, int32_t* items, double* picked, int32_t* positions,
-                    double* objective) {
-  int rc = mmr_rerank_args(lists, scores, n_users, n_pool, k, trade_off, V, n_items, ld, c0, c1, items);
-  if (rc || n_users == 0) return rc;
-  const size_t nn = (size_t)n_users * n_pool, nk = (size_t)n_users * k, vb = (size_t)n_items * ld * (f64 ? 8 : 4);
-  const std::vector<int32_t> rows = lists_row_major(lists, n_users, n_pool);
-  std::vector<double> srows(nn);
-  for (int c = 0; c < n_pool; c++)
-    for (int u = 0; u < n_users; u++) srows[(size_t)u * n_pool + c] = scores[(size_t)c * n_users + u];
-  DevBuf dLists, dScores, dV, dInv, dItems, dPicked, dPos, dObj;
-  HIP_TRY(dLists.alloc(nn * 4));
-  HIP_TRY(dScores.alloc(nn * 8));
-  HIP_TRY(dV.alloc(vb));
-  HIP_TRY(dInv.alloc((size_t)n_items * 8));
-  HIP_TRY(dItems.alloc(nk * 4));
-  if (picked) HIP_TRY(dPicked.alloc(nk * 8));
-  if (positions) HIP_TRY(dPos.alloc(nk * 4));
-  if (objective) HIP_TRY(dObj.alloc(nk * 8));
-  HIP_TRY(hipMemcpy(dLists.p, rows.data(), nn * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dScores.p, srows.data(), nn * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dV.p, V, vb, hipMemcpyHostToDevice));
-  if ((rc = item_inv_norms_device(dV.p, f64, n_items, ld, c0, c1, dInv.as<double>(), nullptr))) return rc;
-  rc = mmr_rerank_device(dLists.as<int32_t>(), dScores.as<double>(), n_users, n_pool, k, trade_off, dV.p, f64, n_items, ld, c0, c1,
-                         dInv.as<double>(), dItems.as<int32_t>(), picked ? dPicked.as<double>() : nullptr,
-                         positions ? dPos.as<int32_t>() : nullptr, objective ? dObj.as<double>() : nullptr, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  if ((rc = fetch_col_major(dItems, n_users, k, items, sizeof(*items)))) return rc;
-  if (picked && (rc = fetch_col_major(dPicked, n_users, k, picked, sizeof(*picked)))) return rc;
-  if (positions && (rc = fetch_col_major(dPos, n_users, k, positions, sizeof(*positions)))) return rc;
-  if (objective && (rc = fetch_col_major(dObj, n_users, k, objective, sizeof(*objective)))) return rc;
   return RSPARSE_HIP_OK;
 }
 }  // namespace
@@ -1794,30 +1317,8 @@ int rsparse_hip_mmr_rerank_f64_device(const int32_t* d_lists, const double* d_sc
   return mmr_rerank_device(d_lists, d_scores, n_users, n_pool, k, trade_off, d_V, true, n_items, ld, c0, c1, d_inv, d_items,
                            d_scores_out, d_positions, d_objective, stream);
 }
-int rsparse_hip_mmr_rerank(const int32_t* lists, const double* scores, int n_users, int n_pool, int k, double trade_off,
-                           const float* V, int n_items, int ld, int c0, int c1, int32_t* items, double* scores_out,
-                           int32_t* positions, double* objective) {
-  return mmr_rerank_host(lists, scores, n_users, n_pool, k, trade_off, V, false, n_items, ld, c0, c1, items, scores_out, positions,
-                         objective);
-}
-int rsparse_hip_mmr_rerank_f64(const int32_t* lists, const double* scores, int n_users, int n_pool, int k, double trade_off,
-                               const double* V, int n_items, int ld, int c0, int c1, int32_t* items, double* scores_out,
-                               int32_t* positions, double* objective) {
-  return mmr_rerank_host(lists, scores, n_users, n_pool, k, trade_off, V, true, n_items, ld, c0, c1, items, scores_out, positions,
-                         objective);
-}
 
 namespace {
-// the arguments both forms of rsparse_hip_held_out_ranks check before anything else
-int held_out_ranks_args(const void* U, const void* V, int n_users, int n_items, int rank, int n_exclude, const void* excl,
-                        const void* act_p, const void* act_j, int max_chunk_users) {
-  if (n_users < 0 || n_items < 0 || rank < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0, n_items < 0 or rank < 1)");
-  if (max_chunk_users < 0) return fail(RSPARSE_HIP_ERR_INVALID, "max_chunk_users < 0");
-  if (!U || !V || !act_p || !act_j) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or actual (p, j)");
-  if (n_exclude < 0 || (n_exclude > 0 && !excl)) return fail(RSPARSE_HIP_ERR_INVALID, "bad exclude");
-  if (rank > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 256 is not on the device path");
-  return RSPARSE_HIP_OK;
-}
 int rank_summary_args(int n_users, const void* act_p, const void* act_x, const void* above, const void* tied, const void* n_adm,
                       const void* mpr, const void* auc, const void* mrr, const void* sums) {
   if (!mpr && !auc && !mrr && !sums) return fail(RSPARSE_HIP_ERR_INVALID, "mpr, auc, mrr and sums are all NULL");
@@ -1857,87 +1358,7 @@ int rsparse_hip_rank_summary_device(int n_users, const int32_t* d_act_p, const d
   return RSPARSE_HIP_OK;
 }
 
-int rsparse_hip_held_out_ranks(const double* x, const double* y, int nr, int nc, int rank, const int32_t* nr_p, const int32_t* nr_j,
-                               const int32_t* exclude, int n_exclude, const int32_t* p, const int32_t* j, const double* ax,
-                               int32_t* above, int32_t* tied, int32_t* n_adm, double* mpr, double* auc, double* mrr, double* sums) {
-  int rc = held_out_ranks_args(x, y, nr, nc, rank, n_exclude, exclude, p, j, 0);
-  if (rc) return rc;
-  if (!above && !tied && !n_adm && !mpr && !auc && !mrr && !sums) return fail(RSPARSE_HIP_ERR_INVALID, "every output is NULL");
-  if ((mpr || sums) && !ax) return fail(RSPARSE_HIP_ERR_INVALID, "mpr and sums need the weights: actual_x is NULL");
-  // the dgRMatrix slots: p from 0, non-decreasing; j strictly ascending within a row
-  if (p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "actual_p[0] != 0");
-  for (int u = 0; u < nr; u++) {
-    if (p[u + 1] < p[u]) return fail(RSPARSE_HIP_ERR_INVALID, "actual_p decreases");
-    for (int32_t e = p[u] + 1; e < p[u + 1]; e++)
-      if (j[e] <= j[e - 1]) return fail(RSPARSE_HIP_ERR_INVALID, "actual_j is not strictly ascending within a row");
-  }
-  if (nr == 0) return RSPARSE_HIP_OK;
-  const size_t nnz = (size_t)p[nr];
-  // x is nr x rank column-major -> row-major fp32; y (rank x nc column-major) already has item vectors contiguous
-  std::vector<float> U((size_t)nr * rank), V((size_t)nc * rank);
-  for (int u = 0; u < nr; u++)
-    for (int r = 0; r < rank; r++) U[(size_t)u * rank + r] = (float)x[(size_t)r * nr + u];
-  for (size_t e = 0; e < V.size(); e++) V[e] = (float)y[e];
-  std::vector<int32_t> ex;
-  for (int e = 0; e < n_exclude; e++)
-    if (exclude[e] >= 1 && exclude[e] <= nc) ex.push_back(exclude[e] - 1);   // R indices are 1-based
-  std::sort(ex.begin(), ex.end());
-  ex.erase(std::unique(ex.begin(), ex.end()), ex.end());
-  const int64_t nr_nnz = nr_p ? (int64_t)nr_p[nr] : 0;
-  const bool filter = nr_nnz > 0 && nr_j;
-  const bool summary = mpr || auc || mrr || sums;
-  DevBuf dU, dV, dNP, dNJ, dE, dP, dJ, dX, dA, dT, dN, dM;
-  HIP_TRY(dU.alloc(U.size() * 4));
-  HIP_TRY(dV.alloc(V.size() * 4));
-  HIP_TRY(dP.alloc(((size_t)nr + 1) * 4));
-  HIP_TRY(dJ.alloc(nnz * 4));
-  HIP_TRY(dA.alloc(nnz * 4));
-  HIP_TRY(dT.alloc(nnz * 4));
-  HIP_TRY(dN.alloc((size_t)nr * 4));
-  HIP_TRY(hipMemcpy(dU.p, U.data(), U.size() * 4, hipMemcpyHostToDevice));
-  if (!V.empty()) HIP_TRY(hipMemcpy(dV.p, V.data(), V.size() * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dP.p, p, ((size_t)nr + 1) * 4, hipMemcpyHostToDevice));
-  if (nnz) HIP_TRY(hipMemcpy(dJ.p, j, nnz * 4, hipMemcpyHostToDevice));
-  if (filter) {
-    HIP_TRY(dNP.alloc(((size_t)nr + 1) * 4));
-    HIP_TRY(dNJ.alloc((size_t)nr_nnz * 4));
-    HIP_TRY(hipMemcpy(dNP.p, nr_p, ((size_t)nr + 1) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dNJ.p, nr_j, (size_t)nr_nnz * 4, hipMemcpyHostToDevice));
-  }
-  if (!ex.empty()) {
-    HIP_TRY(dE.alloc(ex.size() * 4));
-    HIP_TRY(hipMemcpy(dE.p, ex.data(), ex.size() * 4, hipMemcpyHostToDevice));
-  }
-  rc = rsparse_hip_held_out_ranks_device(dU.as<float>(), dV.as<float>(), nr, nc, rank, filter ? dNP.as<int32_t>() : nullptr,
-                                         filter ? dNJ.as<int32_t>() : nullptr, ex.empty() ? nullptr : dE.as<int32_t>(), (int)ex.size(),
-                                         dP.as<int32_t>(), dJ.as<int32_t>(), 0, dA.as<int32_t>(), dT.as<int32_t>(), dN.as<int32_t>(),
-                                         nullptr);
-  if (rc) return rc;
-  double* dm = nullptr;   // mpr, auc, mrr (nr each), sums (3 nr)
-  if (summary) {
-    HIP_TRY(dM.alloc((size_t)nr * 6 * 8));
-    dm = dM.as<double>();
-    if (mpr || sums) {
-      HIP_TRY(dX.alloc(nnz * 8));
-      if (nnz) HIP_TRY(hipMemcpy(dX.p, ax, nnz * 8, hipMemcpyHostToDevice));
-    }
-    rc = rsparse_hip_rank_summary_device(nr, dP.as<int32_t>(), (mpr || sums) ? dX.as<double>() : nullptr, dA.as<int32_t>(),
-                                         dT.as<int32_t>(), dN.as<int32_t>(), mpr ? dm : nullptr, auc ? dm + nr : nullptr,
-                                         mrr ? dm + 2 * (size_t)nr : nullptr, sums ? dm + 3 * (size_t)nr : nullptr, nullptr);
-    if (rc) return rc;
-  }
-  HIP_TRY(hipDeviceSynchronize());
-  if (above && nnz) HIP_TRY(hipMemcpy(above, dA.p, nnz * 4, hipMemcpyDeviceToHost));
-  if (tied && nnz) HIP_TRY(hipMemcpy(tied, dT.p, nnz * 4, hipMemcpyDeviceToHost));
-  if (n_adm) HIP_TRY(hipMemcpy(n_adm, dN.p, (size_t)nr * 4, hipMemcpyDeviceToHost));
-  if (mpr) HIP_TRY(hipMemcpy(mpr, dm, (size_t)nr * 8, hipMemcpyDeviceToHost));
-  if (auc) HIP_TRY(hipMemcpy(auc, dm + nr, (size_t)nr * 8, hipMemcpyDeviceToHost));
-  if (mrr) HIP_TRY(hipMemcpy(mrr, dm + 2 * (size_t)nr, (size_t)nr * 8, hipMemcpyDeviceToHost));
-  if (sums) HIP_TRY(hipMemcpy(sums, dm + 3 * (size_t)nr, (size_t)nr * 3 * 8, hipMemcpyDeviceToHost));
-  return RSPARSE_HIP_OK;
-}
-
-// `_f64_device` and the host form rsparse_hip_sparse_approximation: wrmf_f64_capi.cpp
+// `_f64_device`: wrmf_f64_capi.cpp; the host form rsparse_hip_sparse_approximation: wrmf_capi_host.cpp
 int rsparse_hip_score_pairs_device(const float* d_U, const float* d_V, int n_rows, int n_cols, int r, const int32_t* d_p,
                                    const int32_t* d_j, double add, const double* d_actual, double* d_scores, double* d_sse,
                                    double* d_sae, void* stream) {
@@ -1963,7 +1384,7 @@ int rsparse_hip_softals_half_device(const int32_t* d_p, const int32_t* d_j, cons
                              });
 }
 
-// `_f64_device` and the host form rsparse_hip_top_candidates: wrmf_f64_capi.cpp
+// `_f64_device`: wrmf_f64_capi.cpp; the host form rsparse_hip_top_candidates: wrmf_capi_host.cpp
 int rsparse_hip_top_candidates_device(const float* d_U, const float* d_V, int n_users, int n_items, int rank, int k,
                                       const int32_t* d_cand_p, const int32_t* d_cand_j, const int32_t* d_nr_p, const int32_t* d_nr_j,
                                       const int32_t* d_excl0, int n_exclude, double glob_mean, int32_t* d_res, double* d_scores,
@@ -1994,19 +1415,6 @@ int rsparse_hip_init_factors_device(uint64_t seed, int stream, int64_t row0, int
 }
 
 namespace {
-// what both forms of rsparse_hip_sample_negatives check before anything else
-int sample_negatives_args(int64_t row0, int n_rows, int n_item, int n, const void* seen_p, const void* seen_j, const void* keep_p,
-                          const void* keep_j, const void* out_p, int64_t out_capacity) {
-  if (n_rows < 0 || n_item < 0 || n < 1 || row0 < 0 || out_capacity < 0)
-    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, n_item < 0, n < 1, row0 < 0 or out_capacity < 0)");
-  if (row0 + n_rows > (1ll << 32)) return fail(RSPARSE_HIP_ERR_INVALID, "the global row index row0 + n_rows does not fit 32 bits");
-  if (!seen_p || !seen_j || !out_p) return fail(RSPARSE_HIP_ERR_INVALID, "seen_p, seen_j or out_p is NULL");
-  if (!keep_p != !keep_j) return fail(RSPARSE_HIP_ERR_INVALID, "keep_p and keep_j must both be given or both be NULL");
-  if (n > RSPARSE_HIP_MAX_NEGATIVES)
-    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "n > 8192 (RSPARSE_HIP_MAX_NEGATIVES) is not on the device path");
-  return RSPARSE_HIP_OK;
-}
-
 // the device form of both samplers: d_cum == nullptr is the uniform stream, otherwise the weighted one under that prefix
 int sample_negatives_device(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* d_seen_p,
                             const int32_t* d_seen_j, const int32_t* d_keep_p, const int32_t* d_keep_j, const uint64_t* d_cum,
@@ -2042,80 +1450,6 @@ int sample_negatives_device(uint64_t seed, int64_t row0, int n_rows, int n_item,
   if (e != hipSuccess) return hip_fail(e, "launch_sample_negatives_weighted");
   return RSPARSE_HIP_OK;
 }
-
-// the host form of both samplers: w == nullptr (with weighted false) is the uniform stream
-int sample_negatives_host(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* seen_p, const int32_t* seen_j,
-                          const int32_t* keep_p, const int32_t* keep_j, const uint32_t* w, bool weighted, int32_t* out_p,
-                          int32_t* out_j, int64_t out_capacity, int64_t* filled_rows) {
-  int rc = sample_negatives_args(row0, n_rows, n_item, n, seen_p, seen_j, keep_p, keep_j, out_p, out_capacity);
-  if (rc) return rc;
-  if (weighted) {
-    if (!w) return fail(RSPARSE_HIP_ERR_INVALID, "w is NULL");
-    for (int i = 0; i < n_item; i++)
-      if (w[i] == 0) return fail(RSPARSE_HIP_ERR_INVALID, "a weight is 0: every weight is at least 1 (exclude an item through the seen rows)");
-    if (filled_rows) *filled_rows = 0;
-  }
-  // the dgRMatrix slots: p from 0, non-decreasing; j strictly ascending within a row and inside the matrix; keep within seen
-  if (seen_p[0] != 0 || (keep_p && keep_p[0] != 0)) return fail(RSPARSE_HIP_ERR_INVALID, "seen_p[0] or keep_p[0] != 0");
-  int64_t total = 0;
-  out_p[0] = 0;
-  for (int u = 0; u < n_rows; u++) {
-    if (seen_p[u + 1] < seen_p[u] || (keep_p && keep_p[u + 1] < keep_p[u])) return fail(RSPARSE_HIP_ERR_INVALID, "seen_p or keep_p decreases");
-    for (int32_t e = seen_p[u]; e < seen_p[u + 1]; e++)
-      if (seen_j[e] < 0 || seen_j[e] >= n_item || (e > seen_p[u] && seen_j[e] <= seen_j[e - 1]))
-        return fail(RSPARSE_HIP_ERR_INVALID, "a seen index is outside the matrix, or a row's indices are not strictly ascending");
-    const int32_t S = seen_p[u + 1] - seen_p[u];
-    int32_t K = 0;
-    if (keep_p) {
-      K = keep_p[u + 1] - keep_p[u];
-      int32_t e = seen_p[u];
-      for (int32_t t = keep_p[u]; t < keep_p[u + 1]; t++) {   // both ascending: one pass
-        if (t > keep_p[u] && keep_j[t] <= keep_j[t - 1]) return fail(RSPARSE_HIP_ERR_INVALID, "a keep row's indices are not strictly ascending");
-        while (e < seen_p[u + 1] && seen_j[e] < keep_j[t]) e++;
-        if (e == seen_p[u + 1] || seen_j[e] != keep_j[t]) return fail(RSPARSE_HIP_ERR_INVALID, "a keep row is not a subset of its seen row");
-      }
-    }
-    total += (int64_t)K + std::min(n, n_item - S);
-    if (total > 0x7fffffffll) return fail(RSPARSE_HIP_ERR_INVALID, "the output has more than 2^31 - 1 entries: sample the rows in batches");
-    out_p[u + 1] = (int32_t)total;
-  }
-  if (!out_j) return RSPARSE_HIP_OK;   // the sizes only: out_p[n_rows] is the capacity the second call needs
-  if (total > out_capacity)
-    return fail(RSPARSE_HIP_ERR_INVALID, "out_capacity is " + std::to_string(out_capacity) + ", the rows need " + std::to_string(total));
-  if (n_rows == 0 || total == 0) return RSPARSE_HIP_OK;
-  DevBuf dSP, dSJ, dKP, dKJ, dOP, dOJ, dW, dC, dF;
-  HIP_TRY(upload_host(dSP, seen_p, (size_t)n_rows + 1));
-  const size_t s_nnz = (size_t)seen_p[n_rows], k_nnz = keep_p ? (size_t)keep_p[n_rows] : 0;
-  HIP_TRY(dSJ.alloc(std::max<size_t>(s_nnz, 1) * 4));   // (never NULL: the device form wants the slot)
-  if (s_nnz) HIP_TRY(hipMemcpy(dSJ.p, seen_j, s_nnz * 4, hipMemcpyHostToDevice));
-  if (keep_p) {
-    HIP_TRY(upload_host(dKP, keep_p, (size_t)n_rows + 1));
-    HIP_TRY(dKJ.alloc(std::max<size_t>(k_nnz, 1) * 4));
-    if (k_nnz) HIP_TRY(hipMemcpy(dKJ.p, keep_j, k_nnz * 4, hipMemcpyHostToDevice));
-  }
-  HIP_TRY(dOP.alloc(((size_t)n_rows + 1) * 4));
-  HIP_TRY(dOJ.alloc((size_t)total * 4));
-  if (weighted) {   // (n_item >= 1: total > 0)
-    HIP_TRY(upload_host(dW, w, (size_t)n_item));
-    HIP_TRY(dC.alloc((size_t)n_item * 8));
-    HIP_TRY(dF.alloc(sizeof(int32_t)));
-    if ((rc = rsparse_hip_weights_prefix_device(dW.as<uint32_t>(), n_item, dC.as<uint64_t>(), nullptr))) return rc;
-  }
-  rc = sample_negatives_device(seed, row0, n_rows, n_item, n, dSP.as<int32_t>(), dSJ.as<int32_t>(),
-                               keep_p ? dKP.as<int32_t>() : nullptr, keep_p ? dKJ.as<int32_t>() : nullptr,
-                               weighted ? dC.as<uint64_t>() : nullptr, weighted, dOP.as<int32_t>(), dOJ.as<int32_t>(), total,
-                               weighted ? dF.as<int32_t>() : nullptr, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  if (weighted && filled_rows) {
-    int32_t f = 0;
-    HIP_TRY(hipMemcpy(&f, dF.p, sizeof(f), hipMemcpyDeviceToHost));
-    *filled_rows = f;
-  }
-  HIP_TRY(hipMemcpy(out_p, dOP.p, ((size_t)n_rows + 1) * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(out_j, dOJ.p, (size_t)total * 4, hipMemcpyDeviceToHost));
-  return RSPARSE_HIP_OK;
-}
 }  // namespace
 
 int rsparse_hip_sample_negatives_device(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* d_seen_p,
@@ -2123,13 +1457,6 @@ int rsparse_hip_sample_negatives_device(uint64_t seed, int64_t row0, int n_rows,
                                         int32_t* d_out_p, int32_t* d_out_j, int64_t out_capacity, void* stream) {
   return sample_negatives_device(seed, row0, n_rows, n_item, n, d_seen_p, d_seen_j, d_keep_p, d_keep_j, nullptr, false, d_out_p, d_out_j,
                                  out_capacity, nullptr, stream);
-}
-
-int rsparse_hip_sample_negatives(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* seen_p,
-                                 const int32_t* seen_j, const int32_t* keep_p, const int32_t* keep_j, int32_t* out_p, int32_t* out_j,
-                                 int64_t out_capacity) {
-  return sample_negatives_host(seed, row0, n_rows, n_item, n, seen_p, seen_j, keep_p, keep_j, nullptr, false, out_p, out_j, out_capacity,
-                               nullptr);
 }
 
 int rsparse_hip_weights_prefix_device(const uint32_t* d_w, int n_item, uint64_t* d_cum, void* stream) {
@@ -2156,39 +1483,6 @@ int rsparse_hip_sample_negatives_weighted_device(uint64_t seed, int64_t row0, in
   return sample_negatives_device(seed, row0, n_rows, n_item, n, d_seen_p, d_seen_j, d_keep_p, d_keep_j, d_cum, true, d_out_p, d_out_j,
                                  out_capacity, d_filled_rows, stream);
 }
-
-int rsparse_hip_sample_negatives_weighted(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* seen_p,
-                                          const int32_t* seen_j, const int32_t* keep_p, const int32_t* keep_j, const uint32_t* w,
-                                          int32_t* out_p, int32_t* out_j, int64_t out_capacity, int64_t* filled_rows) {
-  return sample_negatives_host(seed, row0, n_rows, n_item, n, seen_p, seen_j, keep_p, keep_j, w, true, out_p, out_j, out_capacity,
-                               filled_rows);
-}
-
-namespace {
-// what both forms of rsparse_hip_split_rows check before anything else
-int split_rows_args(int64_t row0, int n_rows, int mode, uint64_t test_threshold, int leave_out, int min_train, const void* p,
-                    const void* j, const void* v, int value_bytes, const void* by, const void* train_p, const void* train_j,
-                    const void* train_v, const void* test_p, const void* test_j, const void* test_v, int64_t train_capacity,
-                    int64_t test_capacity) {
-  if (n_rows < 0 || row0 < 0 || train_capacity < 0 || test_capacity < 0)
-    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, row0 < 0 or a negative capacity)");
-  if (row0 + n_rows > (1ll << 32)) return fail(RSPARSE_HIP_ERR_INVALID, "the global row index row0 + n_rows does not fit 32 bits");
-  if (!p || !j || !train_p || !test_p) return fail(RSPARSE_HIP_ERR_INVALID, "p, j, train_p or test_p is NULL");
-  if (!train_j != !test_j) return fail(RSPARSE_HIP_ERR_INVALID, "train_j and test_j must both be given or both be NULL");
-  if (mode == RSPARSE_HIP_SPLIT_PROPORTION) {
-    if (test_threshold > (1ull << 32)) return fail(RSPARSE_HIP_ERR_INVALID, "test_threshold > 2^32");
-    if (by) return fail(RSPARSE_HIP_ERR_INVALID, "`by` has no meaning in proportion mode");
-  } else if (mode == RSPARSE_HIP_SPLIT_LEAVE_OUT) {
-    if (leave_out < 1 || min_train < 0) return fail(RSPARSE_HIP_ERR_INVALID, "leave_out < 1 or min_train < 0");
-  } else {
-    return fail(RSPARSE_HIP_ERR_INVALID, "mode is neither RSPARSE_HIP_SPLIT_PROPORTION nor RSPARSE_HIP_SPLIT_LEAVE_OUT");
-  }
-  if (value_bytes != 0 && value_bytes != 4 && value_bytes != 8) return fail(RSPARSE_HIP_ERR_INVALID, "value_bytes must be 0, 4 or 8");
-  if (!v != (value_bytes == 0)) return fail(RSPARSE_HIP_ERR_INVALID, "v and value_bytes must both be given or both be 0");
-  if (v && train_j && (!train_v || !test_v)) return fail(RSPARSE_HIP_ERR_INVALID, "values are given: train_v and test_v must be too");
-  return RSPARSE_HIP_OK;
-}
-}  // namespace
 
 int rsparse_hip_split_rows_device(uint64_t seed, int64_t row0, int n_rows, int mode, uint64_t test_threshold, int leave_out,
                                   int min_train, const int32_t* d_p, const int32_t* d_j, const void* d_v, int value_bytes,
@@ -2217,78 +1511,6 @@ int rsparse_hip_split_rows_device(uint64_t seed, int64_t row0, int n_rows, int m
   e = launch_split_write(seed, row0, n_rows, mode, test_threshold, leave_out, min_train, d_p, d_j, d_v, value_bytes, d_by, d_train_p,
                          d_train_j, d_train_v, d_test_p, d_test_j, d_test_v, g_ws.score_buf, s);
   if (e != hipSuccess) return hip_fail(e, "launch_split_write");
-  return RSPARSE_HIP_OK;
-}
-
-int rsparse_hip_split_rows(uint64_t seed, int64_t row0, int n_rows, int mode, uint64_t test_threshold, int leave_out, int min_train,
-                           const int32_t* p, const int32_t* j, const void* v, int value_bytes, const double* by, int32_t* train_p,
-                           int32_t* train_j, void* train_v, int32_t* test_p, int32_t* test_j, void* test_v, int64_t train_capacity,
-                           int64_t test_capacity) {
-  int rc = split_rows_args(row0, n_rows, mode, test_threshold, leave_out, min_train, p, j, v, value_bytes, by, train_p, train_j,
-                           train_v, test_p, test_j, test_v, train_capacity, test_capacity);
-  if (rc) return rc;
-  // the dgRMatrix slots: p from 0, non-decreasing; j strictly ascending within a row; no NaN to order by
-  if (p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "p[0] != 0");
-  for (int u = 0; u < n_rows; u++) {
-    if (p[u + 1] < p[u]) return fail(RSPARSE_HIP_ERR_INVALID, "p decreases");
-    for (int32_t e = p[u]; e < p[u + 1]; e++) {
-      if (j[e] < 0 || (e > p[u] && j[e] <= j[e - 1]))
-        return fail(RSPARSE_HIP_ERR_INVALID, "an index is negative, or a row's indices are not strictly ascending");
-      if (by && by[e] != by[e]) return fail(RSPARSE_HIP_ERR_INVALID, "NaN in `by`");
-    }
-  }
-  train_p[0] = test_p[0] = 0;
-  if (n_rows == 0) return RSPARSE_HIP_OK;
-  const size_t nnz = (size_t)p[n_rows], np1 = (size_t)n_rows + 1, slots = std::max<size_t>(nnz, 1);
-  const bool write = train_j != nullptr;
-  DevBuf dP, dJ, dV, dB, dTrP, dTeP, dTrJ, dTeJ, dTrV, dTeV;
-  HIP_TRY(upload_host(dP, p, np1));
-  HIP_TRY(dJ.alloc(slots * 4));   // (never NULL: the device form wants the slot)
-  if (nnz) HIP_TRY(hipMemcpy(dJ.p, j, nnz * 4, hipMemcpyHostToDevice));
-  if (by) {
-    HIP_TRY(dB.alloc(slots * 8));
-    if (nnz) HIP_TRY(hipMemcpy(dB.p, by, nnz * 8, hipMemcpyHostToDevice));
-  }
-  HIP_TRY(dTrP.alloc(np1 * 4));
-  HIP_TRY(dTeP.alloc(np1 * 4));
-  if (write) {
-    // (the host form sizes the device outputs itself: either side holds at most every entry; the caller's capacities are
-    // checked against the counts below)
-    HIP_TRY(dTrJ.alloc(slots * 4));
-    HIP_TRY(dTeJ.alloc(slots * 4));
-    if (v) {
-      HIP_TRY(dV.alloc(slots * (size_t)value_bytes));
-      if (nnz) HIP_TRY(hipMemcpy(dV.p, v, nnz * (size_t)value_bytes, hipMemcpyHostToDevice));
-      HIP_TRY(dTrV.alloc(slots * (size_t)value_bytes));
-      HIP_TRY(dTeV.alloc(slots * (size_t)value_bytes));
-    }
-  }
-  // first the counts (NULL j outputs), so that the caller's capacities are judged before anything of theirs is written
-  rc = rsparse_hip_split_rows_device(seed, row0, n_rows, mode, test_threshold, leave_out, min_train, dP.as<int32_t>(), dJ.as<int32_t>(),
-                                     nullptr, 0, by ? dB.as<double>() : nullptr, dTrP.as<int32_t>(), nullptr, nullptr,
-                                     dTeP.as<int32_t>(), nullptr, nullptr, 0, 0, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(train_p, dTrP.p, np1 * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(test_p, dTeP.p, np1 * 4, hipMemcpyDeviceToHost));
-  if (!write) return RSPARSE_HIP_OK;
-  const int64_t n_tr = train_p[n_rows], n_te = test_p[n_rows];
-  if (n_tr > train_capacity || n_te > test_capacity)
-    return fail(RSPARSE_HIP_ERR_INVALID, "the capacities are " + std::to_string(train_capacity) + " / " + std::to_string(test_capacity) +
-                                             ", the split needs " + std::to_string(n_tr) + " / " + std::to_string(n_te));
-  if (nnz == 0) return RSPARSE_HIP_OK;
-  rc = rsparse_hip_split_rows_device(seed, row0, n_rows, mode, test_threshold, leave_out, min_train, dP.as<int32_t>(), dJ.as<int32_t>(),
-                                     v ? dV.p : nullptr, value_bytes, by ? dB.as<double>() : nullptr, dTrP.as<int32_t>(),
-                                     dTrJ.as<int32_t>(), v ? dTrV.p : nullptr, dTeP.as<int32_t>(), dTeJ.as<int32_t>(),
-                                     v ? dTeV.p : nullptr, n_tr, n_te, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  if (n_tr) HIP_TRY(hipMemcpy(train_j, dTrJ.p, (size_t)n_tr * 4, hipMemcpyDeviceToHost));
-  if (n_te) HIP_TRY(hipMemcpy(test_j, dTeJ.p, (size_t)n_te * 4, hipMemcpyDeviceToHost));
-  if (v) {
-    if (n_tr) HIP_TRY(hipMemcpy(train_v, dTrV.p, (size_t)n_tr * (size_t)value_bytes, hipMemcpyDeviceToHost));
-    if (n_te) HIP_TRY(hipMemcpy(test_v, dTeV.p, (size_t)n_te * (size_t)value_bytes, hipMemcpyDeviceToHost));
-  }
   return RSPARSE_HIP_OK;
 }
 
@@ -2363,102 +1585,6 @@ int rsparse_hip_confidence_apply_device(int kind, int n_seg, int64_t nnz, const 
   return RSPARSE_HIP_OK;
 }
 
-int rsparse_hip_confidence(int kind, int n_rows, int n_cols, const int32_t* p, const int32_t* j, const double* x, double a, double b,
-                           int norm, int by_columns, double* out) {
-  if (n_rows < 0 || n_cols < 0) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0 or n_cols < 0)");
-  if (kind < RSPARSE_HIP_CONFIDENCE_LINEAR || kind > RSPARSE_HIP_CONFIDENCE_NORMALIZE)
-    return fail(RSPARSE_HIP_ERR_INVALID, "unknown confidence kind " + std::to_string(kind));
-  if (!p) return fail(RSPARSE_HIP_ERR_INVALID, "p is NULL");
-  if (kind == RSPARSE_HIP_CONFIDENCE_NORMALIZE && norm != 1 && norm != 2) return fail(RSPARSE_HIP_ERR_INVALID, "norm must be 1 or 2");
-  if (kind == RSPARSE_HIP_CONFIDENCE_LOG && !(b != 0.0)) return fail(RSPARSE_HIP_ERR_INVALID, "eps must not be 0");
-  if (p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "p[0] != 0");
-  for (int u = 0; u < n_rows; u++)
-    if (p[u + 1] < p[u]) return fail(RSPARSE_HIP_ERR_INVALID, "p decreases");
-  const int64_t nnz = p[n_rows];
-  if (nnz == 0) return RSPARSE_HIP_OK;
-  if (!j || !x || !out) return fail(RSPARSE_HIP_ERR_INVALID, "j, x or out is NULL");
-  for (int64_t e = 0; e < nnz; e++)
-    if (j[e] < 0 || j[e] >= n_cols) return fail(RSPARSE_HIP_ERR_INVALID, "a column index outside [0, n_cols)");
-  // the item-major side on the host: the columns' counts, and their values where the columns are normalized
-  const bool cols = kind == RSPARSE_HIP_CONFIDENCE_NORMALIZE && by_columns;
-  const bool items = kind == RSPARSE_HIP_CONFIDENCE_TFIDF || kind == RSPARSE_HIP_CONFIDENCE_BM25 || cols;
-  std::vector<int32_t> pt;
-  std::vector<double> xt;
-  if (items) {
-    pt.assign((size_t)n_cols + 1, 0);
-    for (int64_t e = 0; e < nnz; e++) pt[(size_t)j[e] + 1]++;
-    for (int c = 0; c < n_cols; c++) pt[(size_t)c + 1] += pt[c];
-    if (cols) {
-      xt.resize((size_t)nnz);
-      std::vector<int32_t> at(pt.begin(), pt.end() - 1);
-      for (int64_t e = 0; e < nnz; e++) xt[(size_t)at[j[e]]++] = x[e];
-    }
-  }
-  DevBuf dP, dJ, dX, dPt, dXt, dMom, dTot, dUser, dItem;
-  HIP_TRY(upload_host(dP, p, (size_t)n_rows + 1));
-  HIP_TRY(upload_host(dJ, j, (size_t)nnz));
-  HIP_TRY(upload_host(dX, x, (size_t)nnz));
-  HIP_TRY(dTot.alloc(8));
-  const double *user_t = nullptr, *item_t = nullptr;
-  int rc;
-  if (items) {
-    HIP_TRY(upload_host(dPt, pt.data(), pt.size()));
-    HIP_TRY(dItem.alloc((size_t)n_cols * 8));
-    item_t = dItem.as<double>();
-  }
-  if (kind == RSPARSE_HIP_CONFIDENCE_TFIDF || kind == RSPARSE_HIP_CONFIDENCE_BM25) {
-    if ((rc = rsparse_hip_confidence_table_device(RSPARSE_HIP_CONFIDENCE_TABLE_IDF, n_cols, dPt.as<int32_t>(), nullptr, nullptr,
-                                                  (double)n_rows, 0.0, 0.0, dItem.as<double>(), nullptr)))
-      return rc;
-  }
-  if (kind == RSPARSE_HIP_CONFIDENCE_BM25 || (kind == RSPARSE_HIP_CONFIDENCE_NORMALIZE && !cols)) {
-    HIP_TRY(dMom.alloc((size_t)n_rows * 8));
-    HIP_TRY(dUser.alloc((size_t)n_rows * 8));
-    user_t = dUser.as<double>();
-    const bool bm = kind == RSPARSE_HIP_CONFIDENCE_BM25;
-    if ((rc = rsparse_hip_confidence_moments_device(n_rows, nnz, dP.as<int32_t>(), dX.as<double>(), bm ? 1 : norm, dMom.as<double>(),
-                                                    dTot.as<double>(), nullptr)))
-      return rc;
-    if ((rc = rsparse_hip_confidence_table_device(bm ? RSPARSE_HIP_CONFIDENCE_TABLE_BM25 : RSPARSE_HIP_CONFIDENCE_TABLE_NORM, n_rows,
-                                                  nullptr, dMom.as<double>(), dTot.as<double>(), a, bm ? b : (double)norm,
-                                                  (double)n_rows, dUser.as<double>(), nullptr)))
-      return rc;
-  } else if (cols) {
-    HIP_TRY(upload_host(dXt, xt.data(), xt.size()));
-    HIP_TRY(dMom.alloc((size_t)n_cols * 8));
-    if ((rc = rsparse_hip_confidence_moments_device(n_cols, nnz, dPt.as<int32_t>(), dXt.as<double>(), norm, dMom.as<double>(),
-                                                    dTot.as<double>(), nullptr)))
-      return rc;
-    if ((rc = rsparse_hip_confidence_table_device(RSPARSE_HIP_CONFIDENCE_TABLE_NORM, n_cols, nullptr, dMom.as<double>(), nullptr, a,
-                                                  (double)norm, 0.0, dItem.as<double>(), nullptr)))
-      return rc;
-  }
-  if ((rc = rsparse_hip_confidence_apply_device(kind, n_rows, nnz, dP.as<int32_t>(), dJ.as<int32_t>(), dX.as<double>(), user_t, item_t,
-                                                n_cols, 0, a, b, dX.p, 0, nullptr)))
-    return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, dX.p, (size_t)nnz * 8, hipMemcpyDeviceToHost));
-  return RSPARSE_HIP_OK;
-}
-
-namespace {
-// what both forms of rsparse_hip_events_to_csr check before anything else
-int events_args(int64_t n_events, int n_users, int n_items, const void* users, const void* items, const void* timestamps, int aggregate,
-                double half_life, const void* p, const void* j, const void* x, int64_t capacity, const void* n_cells) {
-  if (n_events < 0 || n_users < 0 || n_items < 0 || capacity < 0)
-    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_events < 0, n_users < 0, n_items < 0 or capacity < 0)");
-  if (n_events >= (1ll << 31)) return fail(RSPARSE_HIP_ERR_INVALID, "n_events >= 2^31: cut the log into several calls");
-  if (!p || !n_cells) return fail(RSPARSE_HIP_ERR_INVALID, "p or n_cells is NULL");
-  if (n_events > 0 && (!users || !items || !j || !x)) return fail(RSPARSE_HIP_ERR_INVALID, "users, items, j or x is NULL");
-  if (aggregate < RSPARSE_HIP_EVENTS_SUM || aggregate > RSPARSE_HIP_EVENTS_LAST)
-    return fail(RSPARSE_HIP_ERR_INVALID, "unknown aggregate " + std::to_string(aggregate));
-  if (aggregate == RSPARSE_HIP_EVENTS_LAST && !timestamps) return fail(RSPARSE_HIP_ERR_INVALID, "the aggregate `last` needs timestamps");
-  if (half_life > 0.0 && !timestamps) return fail(RSPARSE_HIP_ERR_INVALID, "a half life needs timestamps");
-  if (half_life > 0.0 && aggregate != RSPARSE_HIP_EVENTS_SUM) return fail(RSPARSE_HIP_ERR_INVALID, "a half life goes with the aggregate `sum` only");
-  return RSPARSE_HIP_OK;
-}
-}  // namespace
-
 int rsparse_hip_events_to_csr_device(int64_t n_events, int n_users, int n_items, const int32_t* d_users, const int32_t* d_items,
                                      const double* d_values, const double* d_timestamps, int aggregate, double half_life, double now,
                                      int has_now, int32_t* d_p, int32_t* d_j, double* d_x, int32_t* d_count, double* d_latest,
@@ -2479,49 +1605,6 @@ int rsparse_hip_events_to_csr_device(int64_t n_events, int n_users, int n_items,
   if (status == 1) return fail(RSPARSE_HIP_ERR_INVALID, "a user or item id outside [0, n_users) x [0, n_items)");
   if (status == 2)
     return fail(RSPARSE_HIP_ERR_INVALID, "the capacity is " + std::to_string(capacity) + ", the log has " + std::to_string(*n_cells) + " cells");
-  return RSPARSE_HIP_OK;
-}
-
-int rsparse_hip_events_to_csr(int64_t n_events, int n_users, int n_items, const int32_t* users, const int32_t* items,
-                              const double* values, const double* timestamps, int aggregate, double half_life, double now, int has_now,
-                              int32_t* p, int32_t* j, double* x, int32_t* count, double* latest, int64_t capacity, int64_t* n_cells) {
-  int rc = events_args(n_events, n_users, n_items, users, items, timestamps, aggregate, half_life, p, j, x, capacity, n_cells);
-  if (rc) return rc;
-  for (int64_t e = 0; e < n_events; e++)
-    if ((values && values[e] != values[e]) || (timestamps && timestamps[e] != timestamps[e]))
-      return fail(RSPARSE_HIP_ERR_INVALID, "NaN in values or timestamps");
-  *n_cells = 0;
-  if (n_events == 0) {
-    for (int64_t u = 0; u <= n_users; u++) p[u] = 0;
-    return RSPARSE_HIP_OK;
-  }
-  const size_t n = (size_t)n_events, np1 = (size_t)n_users + 1;
-  DevBuf dU, dI, dV, dT, dP, dJ, dX, dC, dL;
-  HIP_TRY(upload_host(dU, users, n));
-  HIP_TRY(upload_host(dI, items, n));
-  if (values) HIP_TRY(upload_host(dV, values, n));
-  if (timestamps) HIP_TRY(upload_host(dT, timestamps, n));
-  // (the host form sizes the device outputs itself: n_events slots always suffice; the caller's capacity is judged below)
-  const bool want_latest = latest && timestamps;
-  HIP_TRY(dP.alloc(np1 * 4));
-  HIP_TRY(dJ.alloc(n * 4));
-  HIP_TRY(dX.alloc(n * 8));
-  if (count) HIP_TRY(dC.alloc(n * 4));
-  if (want_latest) HIP_TRY(dL.alloc(n * 8));
-  rc = rsparse_hip_events_to_csr_device(n_events, n_users, n_items, dU.as<int32_t>(), dI.as<int32_t>(), values ? dV.as<double>() : nullptr,
-                                        timestamps ? dT.as<double>() : nullptr, aggregate, half_life, now, has_now, dP.as<int32_t>(),
-                                        dJ.as<int32_t>(), dX.as<double>(), count ? dC.as<int32_t>() : nullptr,
-                                        want_latest ? dL.as<double>() : nullptr, n_events, n_cells, nullptr);
-  if (rc) return rc;
-  if (*n_cells > capacity)
-    return fail(RSPARSE_HIP_ERR_INVALID, "the capacity is " + std::to_string(capacity) + ", the log has " + std::to_string(*n_cells) + " cells");
-  HIP_TRY(hipDeviceSynchronize());
-  const size_t nc = (size_t)*n_cells;
-  HIP_TRY(hipMemcpy(p, dP.p, np1 * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(j, dJ.p, nc * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(x, dX.p, nc * 8, hipMemcpyDeviceToHost));
-  if (count) HIP_TRY(hipMemcpy(count, dC.p, nc * 4, hipMemcpyDeviceToHost));
-  if (want_latest) HIP_TRY(hipMemcpy(latest, dL.p, nc * 8, hipMemcpyDeviceToHost));
   return RSPARSE_HIP_OK;
 }
 

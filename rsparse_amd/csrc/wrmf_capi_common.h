@@ -1,6 +1,10 @@
-// Host bodies of the C-ABI entries that exist in float and in double, written once (wrmf_capi.cpp and wrmf_f64_capi.cpp hold
-// the thin `extern "C"` forms: validate, make sure of their own workspace, build the views below, call the template).
-// What differs between the two sides on purpose is listed in DESIGN.md ("shared between the precisions").
+// What the translation units of the C ABI share, each thing written once:
+//   * the host bodies of the entries that exist in float and in double (wrmf_capi.cpp and wrmf_f64_capi.cpp hold the thin
+//     `extern "C"` forms: validate, make sure of their own workspace, build the views below, call the template); what differs
+//     between the two sides on purpose is listed in DESIGN.md ("shared between the precisions");
+//   * the argument rules (`*_args`) of the evaluation and data-preparation entries, which the `_device` form of an entry
+//     (wrmf_capi.cpp) and its host-array form (wrmf_capi_host.cpp) both apply first;
+//   * the error helpers and upload_host, all that the host-array forms use besides DevBuf and the public `_device` entries.
 #pragma once
 
 #include <algorithm>
@@ -194,6 +198,165 @@ hipError_t upload_host(DevBuf& b, const T* src, size_t n) {   // n host elements
   return (e != hipSuccess || !n) ? e : hipMemcpy(b.p, src, n * sizeof(T), hipMemcpyHostToDevice);
 }
 
+// ---- the argument rules of the evaluation and data-preparation entries: what the `_device` form (wrmf_capi.cpp) and the
+// host-array form (wrmf_capi_host.cpp) of an entry both check before anything else, and before a pointer is read ----
+
+// the refusal every top-k entry shares (k: a list length)
+inline int refuse_large_k(int64_t k) {
+  if (k > RSPARSE_HIP_MAX_TOPK_LARGE) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
+  return RSPARSE_HIP_OK;
+}
+
+inline int similar_items_args(int n_items, int r, int n_q, int k, int n_exclude, const void* exclude) {
+  if (n_items < 0 || n_q < 0 || k < 1 || r < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_items < 0, n_q < 0, k < 1 or no latent coordinate)");
+  if (n_exclude < 0 || (n_exclude > 0 && !exclude)) return fail(RSPARSE_HIP_ERR_INVALID, "bad exclude");
+  if (r > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 256 latent coordinates are not on the device path");
+  return refuse_large_k(k);
+}
+
+inline int ranking_metrics_args(const int32_t* pred, int n_users, int k, const int32_t* p, const int32_t* j, const double* x,
+                                const double* ap_out, const double* ndcg_out) {
+  if (!ap_out && !ndcg_out) return fail(RSPARSE_HIP_ERR_INVALID, "ap_out and ndcg_out are both NULL");
+  if (!pred || !p || !j) return fail(RSPARSE_HIP_ERR_INVALID, "predictions or actual (p, j) is NULL");
+  if (ndcg_out && !x) return fail(RSPARSE_HIP_ERR_INVALID, "ndcg needs the relevances: actual_x is NULL");
+  if (n_users < 0 || k < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0 or k < 1)");
+  return refuse_large_k(k);
+}
+
+// The lists and cutoffs of the entries that take cutoffs.  What differs between the two families is handed in: whether a
+// needed array is missing (and how the refusal names them), and whether n_items is bad for this call (likewise).
+inline int cutoff_args(bool any_output, bool missing, const char* missing_msg, int n_users, int k, const int32_t* cutoffs,
+                       int n_cutoffs, bool bad_items, const char* bad_items_msg) {
+  if (!any_output) return fail(RSPARSE_HIP_ERR_INVALID, "every output is NULL");
+  if (missing) return fail(RSPARSE_HIP_ERR_INVALID, missing_msg);
+  if (n_users < 0 || k < 1 || n_cutoffs < 1)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0, k < 1 or n_cutoffs < 1)");
+  if (bad_items) return fail(RSPARSE_HIP_ERR_INVALID, bad_items_msg);
+  if (n_cutoffs > RSPARSE_HIP_MAX_CUTOFFS)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 16 cutoffs (RSPARSE_HIP_MAX_CUTOFFS) are not on the device path");
+  if (int rc = refuse_large_k(k)) return rc;
+  for (int t = 0; t < n_cutoffs; t++)
+    if (cutoffs[t] < 1 || cutoffs[t] > k || (t > 0 && cutoffs[t] <= cutoffs[t - 1]))
+      return fail(RSPARSE_HIP_ERR_INVALID, "cutoffs must be strictly ascending within 1 .. k");
+  return RSPARSE_HIP_OK;
+}
+inline int hit_metrics_args(const int32_t* pred, int n_users, int k, const int32_t* p, const int32_t* j, const int32_t* cutoffs,
+                            int n_cutoffs, bool any_output, const int32_t* first_seen, int n_items) {
+  return cutoff_args(any_output, !pred || !p || !j || !cutoffs, "predictions, actual (p, j) or cutoffs is NULL", n_users, k, cutoffs,
+                     n_cutoffs, first_seen && n_items < 1, "first_seen needs n_items >= 1");
+}
+// (every entry of the beyond-accuracy metrics)
+inline int list_args(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, bool any_output, int n_items) {
+  return cutoff_args(any_output, !pred || !cutoffs, "predictions or cutoffs is NULL", n_users, k, cutoffs, n_cutoffs, n_items < 1,
+                     "n_items < 1");
+}
+inline int list_metrics_args(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, const int32_t* item_count,
+                             const int64_t* item_info, int n_items, const void* valid, const void* count_sum, const void* info_sum,
+                             const void* popularity, const void* novelty, const void* exposure) {
+  const bool any = valid || count_sum || info_sum || popularity || novelty || exposure;
+  int rc = list_args(pred, n_users, k, cutoffs, n_cutoffs, any, n_items);
+  if (rc) return rc;
+  if ((count_sum || popularity) && !item_count) return fail(RSPARSE_HIP_ERR_INVALID, "count_sum / popularity need item_count");
+  if ((info_sum || novelty) && !item_info) return fail(RSPARSE_HIP_ERR_INVALID, "info_sum / novelty need item_info");
+  return RSPARSE_HIP_OK;
+}
+// the window c0 .. c1 of the factors' ld columns
+inline int window_args(int n_items, int ld, int c0, int c1) {
+  if (n_items < 0 || c0 < 0 || c1 - c0 < 1 || c1 > ld)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_items < 0 or not 0 <= c0 < c1 <= ld)");
+  if (c1 - c0 > RSPARSE_HIP_MAX_RANK)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 256 latent coordinates are not on the device path");
+  return RSPARSE_HIP_OK;
+}
+// the cosine operands of the item-to-item similarity (rsparse_hip_normalize_items_device / _f64_device)
+inline int normalize_items_args(const void* d_V, int n_items, int ld, int c0, int c1, const void* d_Vn32, const void* d_Vn64,
+                                const void* d_flags) {
+  if (int rc = window_args(n_items, ld, c0, c1)) return rc;
+  if (n_items > 0 && (!d_V || !d_Vn32 || !d_Vn64 || !d_flags)) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
+  return RSPARSE_HIP_OK;
+}
+inline int list_diversity_args(const int32_t* pred, int n_users, int k, const int32_t* cutoffs, int n_cutoffs, const void* V, int n_items,
+                               int ld, int c0, int c1, const void* counted, const void* diversity) {
+  int rc = list_args(pred, n_users, k, cutoffs, n_cutoffs, counted || diversity, n_items);
+  if (rc) return rc;
+  if (!V) return fail(RSPARSE_HIP_ERR_INVALID, "the factor matrix is NULL");
+  return window_args(n_items, ld, c0, c1);
+}
+
+inline int mmr_rerank_args(const int32_t* lists, const double* scores, int n_users, int n_pool, int k, double trade_off, const void* V,
+                           int n_items, int ld, int c0, int c1, const void* items) {
+  if (!lists || !scores) return fail(RSPARSE_HIP_ERR_INVALID, "lists or scores is NULL");
+  if (!V) return fail(RSPARSE_HIP_ERR_INVALID, "the factor matrix is NULL");
+  if (!items) return fail(RSPARSE_HIP_ERR_INVALID, "the items output is NULL");
+  if (n_users < 0 || n_pool < 1 || k < 1 || k > n_pool)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0 or not 1 <= k <= n_pool)");
+  if (!(trade_off >= 0.0 && trade_off <= 1.0)) return fail(RSPARSE_HIP_ERR_INVALID, "trade_off must lie in [0, 1]");   // (NaN too)
+  if (n_items < 1) return fail(RSPARSE_HIP_ERR_INVALID, "n_items < 1");
+  if (n_pool > RSPARSE_HIP_MAX_TOPK_LARGE)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "a pool of more than 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
+  return window_args(n_items, ld, c0, c1);
+}
+
+inline int held_out_ranks_args(const void* U, const void* V, int n_users, int n_items, int rank, int n_exclude, const void* excl,
+                               const void* act_p, const void* act_j, int max_chunk_users) {
+  if (n_users < 0 || n_items < 0 || rank < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0, n_items < 0 or rank < 1)");
+  if (max_chunk_users < 0) return fail(RSPARSE_HIP_ERR_INVALID, "max_chunk_users < 0");
+  if (!U || !V || !act_p || !act_j) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or actual (p, j)");
+  if (n_exclude < 0 || (n_exclude > 0 && !excl)) return fail(RSPARSE_HIP_ERR_INVALID, "bad exclude");
+  if (rank > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 256 is not on the device path");
+  return RSPARSE_HIP_OK;
+}
+
+inline int sample_negatives_args(int64_t row0, int n_rows, int n_item, int n, const void* seen_p, const void* seen_j, const void* keep_p,
+                                 const void* keep_j, const void* out_p, int64_t out_capacity) {
+  if (n_rows < 0 || n_item < 0 || n < 1 || row0 < 0 || out_capacity < 0)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, n_item < 0, n < 1, row0 < 0 or out_capacity < 0)");
+  if (row0 + n_rows > (1ll << 32)) return fail(RSPARSE_HIP_ERR_INVALID, "the global row index row0 + n_rows does not fit 32 bits");
+  if (!seen_p || !seen_j || !out_p) return fail(RSPARSE_HIP_ERR_INVALID, "seen_p, seen_j or out_p is NULL");
+  if (!keep_p != !keep_j) return fail(RSPARSE_HIP_ERR_INVALID, "keep_p and keep_j must both be given or both be NULL");
+  if (n > RSPARSE_HIP_MAX_NEGATIVES)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "n > 8192 (RSPARSE_HIP_MAX_NEGATIVES) is not on the device path");
+  return RSPARSE_HIP_OK;
+}
+
+inline int split_rows_args(int64_t row0, int n_rows, int mode, uint64_t test_threshold, int leave_out, int min_train, const void* p,
+                           const void* j, const void* v, int value_bytes, const void* by, const void* train_p, const void* train_j,
+                           const void* train_v, const void* test_p, const void* test_j, const void* test_v, int64_t train_capacity,
+                           int64_t test_capacity) {
+  if (n_rows < 0 || row0 < 0 || train_capacity < 0 || test_capacity < 0)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, row0 < 0 or a negative capacity)");
+  if (row0 + n_rows > (1ll << 32)) return fail(RSPARSE_HIP_ERR_INVALID, "the global row index row0 + n_rows does not fit 32 bits");
+  if (!p || !j || !train_p || !test_p) return fail(RSPARSE_HIP_ERR_INVALID, "p, j, train_p or test_p is NULL");
+  if (!train_j != !test_j) return fail(RSPARSE_HIP_ERR_INVALID, "train_j and test_j must both be given or both be NULL");
+  if (mode == RSPARSE_HIP_SPLIT_PROPORTION) {
+    if (test_threshold > (1ull << 32)) return fail(RSPARSE_HIP_ERR_INVALID, "test_threshold > 2^32");
+    if (by) return fail(RSPARSE_HIP_ERR_INVALID, "`by` has no meaning in proportion mode");
+  } else if (mode == RSPARSE_HIP_SPLIT_LEAVE_OUT) {
+    if (leave_out < 1 || min_train < 0) return fail(RSPARSE_HIP_ERR_INVALID, "leave_out < 1 or min_train < 0");
+  } else {
+    return fail(RSPARSE_HIP_ERR_INVALID, "mode is neither RSPARSE_HIP_SPLIT_PROPORTION nor RSPARSE_HIP_SPLIT_LEAVE_OUT");
+  }
+  if (value_bytes != 0 && value_bytes != 4 && value_bytes != 8) return fail(RSPARSE_HIP_ERR_INVALID, "value_bytes must be 0, 4 or 8");
+  if (!v != (value_bytes == 0)) return fail(RSPARSE_HIP_ERR_INVALID, "v and value_bytes must both be given or both be 0");
+  if (v && train_j && (!train_v || !test_v)) return fail(RSPARSE_HIP_ERR_INVALID, "values are given: train_v and test_v must be too");
+  return RSPARSE_HIP_OK;
+}
+
+inline int events_args(int64_t n_events, int n_users, int n_items, const void* users, const void* items, const void* timestamps,
+                       int aggregate, double half_life, const void* p, const void* j, const void* x, int64_t capacity, const void* n_cells) {
+  if (n_events < 0 || n_users < 0 || n_items < 0 || capacity < 0)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_events < 0, n_users < 0, n_items < 0 or capacity < 0)");
+  if (n_events >= (1ll << 31)) return fail(RSPARSE_HIP_ERR_INVALID, "n_events >= 2^31: cut the log into several calls");
+  if (!p || !n_cells) return fail(RSPARSE_HIP_ERR_INVALID, "p or n_cells is NULL");
+  if (n_events > 0 && (!users || !items || !j || !x)) return fail(RSPARSE_HIP_ERR_INVALID, "users, items, j or x is NULL");
+  if (aggregate < RSPARSE_HIP_EVENTS_SUM || aggregate > RSPARSE_HIP_EVENTS_LAST)
+    return fail(RSPARSE_HIP_ERR_INVALID, "unknown aggregate " + std::to_string(aggregate));
+  if (aggregate == RSPARSE_HIP_EVENTS_LAST && !timestamps) return fail(RSPARSE_HIP_ERR_INVALID, "the aggregate `last` needs timestamps");
+  if (half_life > 0.0 && !timestamps) return fail(RSPARSE_HIP_ERR_INVALID, "a half life needs timestamps");
+  if (half_life > 0.0 && aggregate != RSPARSE_HIP_EVENTS_SUM) return fail(RSPARSE_HIP_ERR_INVALID, "a half life goes with the aggregate `sum` only");
+  return RSPARSE_HIP_OK;
+}
+
 // rsparse_hip_score_pairs_device / _f64_device (kernels: wrmf_score.hip).  Handed in:
 //   int workspace(size_t n, double*& buf)    makes sure of n doubles of the side's grow-only workspace
 // which is only asked for the sums without the scores: the scores then live there, and their count, p[n_rows], has to be
@@ -269,7 +432,7 @@ int top_candidates_device(const T* d_U, const T* d_V, int n_users, int n_items, 
   if (n_exclude > 0 && !d_excl0) return fail(RSPARSE_HIP_ERR_INVALID, "exclude is NULL");
   if (rank > max_rank)
     return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > " + std::to_string(max_rank) + " is not on the device path");
-  if (k > RSPARSE_HIP_MAX_TOPK_LARGE) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
+  if (int rc = refuse_large_k(k)) return rc;
   if (n_users == 0) return RSPARSE_HIP_OK;
   int32_t pe[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(&pe[0], d_cand_p, sizeof(int32_t), hipMemcpyDeviceToHost, s));

@@ -335,16 +335,12 @@ int rsparse_hip_weighted_sumsq_f64_device(const double* d_X, int rank, int64_t n
   return weighted_sumsq(d_X, rank, n, d_w, d_out, g_w64.scratch(), (hipStream_t)stream);
 }
 
-// the cosine operands of rsparse_hip_similar_items_device from double factors (kernel: wrmf_similar.hip; the fp32 form and
-// the argument rules are in wrmf_capi.cpp)
+// the cosine operands of rsparse_hip_similar_items_device from double factors (kernel: wrmf_similar.hip; the fp32 form:
+// wrmf_capi.cpp, the argument rules: wrmf_capi_common.h)
 int rsparse_hip_normalize_items_f64_device(const double* d_V, int n_items, int ld, int c0, int c1, float* d_Vn32,
                                            double* d_Vn64, int32_t* d_flags, void* stream) {
-  if (n_items < 0 || c0 < 0 || c1 - c0 < 1 || c1 > ld)
-    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_items < 0 or not 0 <= c0 < c1 <= ld)");
-  if (c1 - c0 > RSPARSE_HIP_MAX_RANK)
-    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "more than 256 latent coordinates are not on the device path");
-  if (n_items > 0 && (!d_V || !d_Vn32 || !d_Vn64 || !d_flags)) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
-  if (n_items == 0) return RSPARSE_HIP_OK;
+  int rc = normalize_items_args(d_V, n_items, ld, c0, c1, d_Vn32, d_Vn64, d_flags);
+  if (rc || n_items == 0) return rc;
   hipError_t e = launch_normalize_items(d_V, true, n_items, ld, c0, c1 - c0, d_Vn32, d_Vn64, d_flags, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "launch_normalize_items");
   return RSPARSE_HIP_OK;
@@ -391,78 +387,6 @@ int rsparse_hip_top_candidates_f64_device(const double* d_U, const double* d_V, 
                                });
 }
 
-// find_top_product (R/utils.R:31-59) within per-row candidate lists, host pointers, shaped like rsparse_hip_top_product: x is
-// nr x rank and y rank x nc, column-major doubles; cand / nr: CSR over the rows of x with 0-based columns (cand: ascending and
-// unique within a row); exclude: 1-based items; res / scores: nr x k column-major, 1-based with NA_integer_ / NA_real_.
-int rsparse_hip_top_candidates(const double* x, const double* y, int nr, int nc, int rank, unsigned k, unsigned n_threads,
-                               const int32_t* cand_p, const int32_t* cand_j, const int32_t* nr_p, const int32_t* nr_j,
-                               const int32_t* exclude, int n_exclude, double glob_mean, int32_t* res, double* scores) {
-  (void)n_threads;
-  if (!x || !y || !res || !scores) return fail(RSPARSE_HIP_ERR_INVALID, "NULL matrix or output");
-  if (!cand_p) return fail(RSPARSE_HIP_ERR_INVALID, "cand_p is NULL");
-  if (nr < 0 || nc < 0 || rank <= 0 || k < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions");
-  if (rank > RSPARSE_HIP_MAX_RANK_F64) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 128 is not on the fp64 device path");
-  if (k > RSPARSE_HIP_MAX_TOPK_LARGE) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 8192 (RSPARSE_HIP_MAX_TOPK_LARGE) is not on the device path");
-  if (n_exclude < 0 || (n_exclude > 0 && !exclude)) return fail(RSPARSE_HIP_ERR_INVALID, "bad exclude");
-  if (cand_p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "cand_p[0] != 0");
-  for (int i = 0; i < nr; i++)
-    if (cand_p[i + 1] < cand_p[i]) return fail(RSPARSE_HIP_ERR_INVALID, "cand_p decreases");
-  const size_t nnz = (size_t)cand_p[nr];
-  if (nnz && !cand_j) return fail(RSPARSE_HIP_ERR_INVALID, "cand_j is NULL");
-  for (int i = 0; i < nr; i++)
-    for (int t = cand_p[i]; t < cand_p[i + 1]; t++)
-      if (cand_j[t] < 0 || cand_j[t] >= nc || (t > cand_p[i] && cand_j[t] <= cand_j[t - 1]))
-        return fail(RSPARSE_HIP_ERR_INVALID, "a candidate index is outside the matrix, or a row's indices are not strictly ascending");
-  const int64_t nr_nnz = (nr_p && nr_j && nr > 0) ? (int64_t)nr_p[nr] : 0;
-  std::vector<int32_t> hp, hj;   // not_recommend with ascending columns (what the device form asks for)
-  if (nr_nnz > 0) {
-    if (nr_p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "nr_p[0] != 0");
-    for (int i = 0; i < nr; i++)
-      if (nr_p[i + 1] < nr_p[i]) return fail(RSPARSE_HIP_ERR_INVALID, "nr_p decreases");
-    hp.assign(nr_p, nr_p + nr + 1);
-    hj.assign(nr_j, nr_j + nr_nnz);
-    for (int i = 0; i < nr; i++) std::sort(hj.begin() + hp[i], hj.begin() + hp[i + 1]);
-  }
-  std::vector<int32_t> ex;
-  for (int e = 0; e < n_exclude; e++)
-    if (exclude[e] >= 1 && exclude[e] <= nc) ex.push_back(exclude[e] - 1);   // R indices are 1-based
-  std::sort(ex.begin(), ex.end());
-  ex.erase(std::unique(ex.begin(), ex.end()), ex.end());
-  std::vector<double> U((size_t)nr * rank);   // x is nr x rank column-major -> row-major; y already has item vectors contiguous
-  for (int j = 0; j < nr; j++)
-    for (int r = 0; r < rank; r++) U[(size_t)j * rank + r] = x[(size_t)r * nr + j];
-  DevBuf dU, dV, dCP, dCJ, dP, dJ, dE, dR, dS;
-  HIP_TRY(upload_host(dU, U.data(), U.size()));
-  HIP_TRY(upload_host(dV, y, (size_t)rank * nc));
-  HIP_TRY(upload_host(dCP, cand_p, (size_t)nr + 1));
-  HIP_TRY(upload_host(dCJ, cand_j, nnz));
-  if (nr_nnz > 0) {
-    HIP_TRY(upload_host(dP, hp.data(), hp.size()));
-    HIP_TRY(upload_host(dJ, hj.data(), hj.size()));
-  }
-  if (!ex.empty()) HIP_TRY(upload_host(dE, ex.data(), ex.size()));
-  HIP_TRY(dR.alloc((size_t)nr * k * 4));
-  HIP_TRY(dS.alloc((size_t)nr * k * 8));
-  int rc = rsparse_hip_top_candidates_f64_device(dU.as<double>(), dV.as<double>(), nr, nc, rank, (int)k, dCP.as<int32_t>(),
-                                                 dCJ.as<int32_t>(), nr_nnz > 0 ? dP.as<int32_t>() : nullptr,
-                                                 nr_nnz > 0 ? dJ.as<int32_t>() : nullptr, ex.empty() ? nullptr : dE.as<int32_t>(),
-                                                 (int)ex.size(), glob_mean, dR.as<int32_t>(), dS.as<double>(), nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  std::vector<int32_t> hr((size_t)nr * k);
-  std::vector<double> hs((size_t)nr * k);
-  if (!hr.empty()) {
-    HIP_TRY(hipMemcpy(hr.data(), dR.p, hr.size() * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hs.data(), dS.p, hs.size() * 8, hipMemcpyDeviceToHost));
-  }
-  for (int j = 0; j < nr; j++)
-    for (unsigned c = 0; c < k; c++) {
-      res[(size_t)c * nr + j] = hr[(size_t)j * k + c];
-      scores[(size_t)c * nr + j] = hs[(size_t)j * k + c];
-    }
-  return RSPARSE_HIP_OK;
-}
-
 // per-item contributions to a score from double factors (kernel: wrmf_explain.hip; the fp32 form: wrmf_capi.cpp)
 int rsparse_hip_explain_f64_device(const double* d_V, int n_items, int r, const double* d_base, double diag, double diag_per_nnz,
                                    int n_users, const int32_t* d_x_p, const int32_t* d_x_j, const double* d_wa, const double* d_wb,
@@ -477,41 +401,6 @@ int rsparse_hip_init_factors_f64_device(uint64_t seed, int stream, int64_t row0,
                                         int abs_values, int ones_col, void* d_out, void* hip_stream) {
   return init_factors_device(seed, stream, row0, n_rows, rank, ld, scale, abs_values, ones_col, static_cast<double*>(d_out),
                              (hipStream_t)hip_stream);
-}
-
-// cpp_make_sparse_approximation (src/utils.cpp:4-56): the values of X^T Y at the stored positions of a template.  CSR: position t
-// of row i holds X[:, i] . Y[:, idx[t]]; CSC: position t of column c holds Y[:, c] . X[:, idx[t]] -- the two operands swap roles.
-int rsparse_hip_sparse_approximation(int n_rows, int n_cols, const int32_t* p, const int32_t* idx, int sparse_matrix_type,
-                                     const double* X, const double* Y, int rank, double* values_out) {
-  if (sparse_matrix_type != 1 && sparse_matrix_type != 2)
-    return fail(RSPARSE_HIP_ERR_INVALID, "sparse_matrix_type should be CSC = 1 or CSR = 2");
-  if (n_rows < 0 || n_cols < 0 || rank < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, n_cols < 0 or rank < 1)");
-  if (rank > RSPARSE_HIP_MAX_RANK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > 256 is not on the device path");
-  if (!p || !X || !Y) return fail(RSPARSE_HIP_ERR_INVALID, "p, X or Y is NULL");
-  const bool csr = sparse_matrix_type == 2;
-  const int n_outer = csr ? n_rows : n_cols, n_inner = csr ? n_cols : n_rows;
-  if (p[0] != 0) return fail(RSPARSE_HIP_ERR_INVALID, "p[0] != 0");
-  for (int i = 0; i < n_outer; i++)
-    if (p[i + 1] < p[i]) return fail(RSPARSE_HIP_ERR_INVALID, "p decreases");
-  const size_t nnz = (size_t)p[n_outer];
-  if (nnz && (!idx || !values_out)) return fail(RSPARSE_HIP_ERR_INVALID, "the indices or values_out is NULL");
-  for (size_t t = 0; t < nnz; t++)
-    if (idx[t] < 0 || idx[t] >= n_inner) return fail(RSPARSE_HIP_ERR_INVALID, "an index is outside the matrix");
-  if (nnz == 0) return RSPARSE_HIP_OK;
-  const double* outer = csr ? X : Y;
-  const double* inner = csr ? Y : X;
-  DevBuf dO, dI, dP, dJ, dS;
-  HIP_TRY(upload_host(dO, outer, (size_t)rank * n_outer));
-  HIP_TRY(upload_host(dI, inner, (size_t)rank * n_inner));
-  HIP_TRY(upload_host(dP, p, (size_t)n_outer + 1));
-  HIP_TRY(upload_host(dJ, idx, nnz));
-  HIP_TRY(dS.alloc(nnz * sizeof(double)));
-  int rc = rsparse_hip_score_pairs_f64_device(dO.as<double>(), dI.as<double>(), n_outer, n_inner, rank, dP.as<int32_t>(),
-                                              dJ.as<int32_t>(), 0.0, nullptr, dS.as<double>(), nullptr, nullptr, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(values_out, dS.p, nnz * sizeof(double), hipMemcpyDeviceToHost));
-  return RSPARSE_HIP_OK;
 }
 
 int rsparse_hip_values_subtract_mean_f64_device(int64_t n, double* d_x, double* d_x_other, double* mean_out, void* stream) {

@@ -565,7 +565,7 @@ hipError_t launch_gramian_wide(const float* X, int k, int64_t n, float ridge, fl
 // to the names a profiler prints.  No-op when ev_slot is null.
 void prof_note(hipEvent_t* ev_slot, const void* kernel_fn);
 
-// Shared by the translation units of the C ABI (wrmf_capi.cpp, wrmf_f64_capi.cpp): the thread-local error text behind
+// Shared by the translation units of the C ABI (wrmf_capi.cpp, wrmf_f64_capi.cpp, wrmf_capi_host.cpp): the thread-local error text behind
 // rsparse_hip_last_error(), and the device block of the exact solvers' failure counters (see launch_fail_roll; nullptr if
 // the workspace could not be set up -- the error text then says why).
 int capi_fail(int code, const std::string& msg);
