@@ -738,6 +738,77 @@ int rsparse_hip_softals_half_f64_device(const int32_t* d_p, const int32_t* d_j, 
                                         const double* t, double* d_out, double* d_sumsq, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * ItemKNN: the neighbours of every item by the co-occurrence of items, and top-k lists scored by them
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The definition (rsparse_amd/itemknn.py states it in numpy).  B is the PATTERN of a users x items matrix in canonical CSR
+ * (columns ascending and unique within a row; values are not looked at), n_j the number of users of item j, c_ij = (B^T B)_ij
+ * for i != j, n_users <= 2^26 so that c^2 and n_i n_j are exact in double.  The order key of neighbour j of item i is ONE
+ * division of two integers, evaluated in double:
+ *     RSPARSE_HIP_KNN_COUNT    c / 1
+ *     RSPARSE_HIP_KNN_COSINE   c^2 / (n_i n_j)         (the cosine is its square root, which the caller takes)
+ *     RSPARSE_HIP_KNN_JACCARD  c / (n_i + n_j - c)
+ * The neighbours of i are the K items j != i with c_ij > 0 of largest key, ties to the smaller j: `neighbors` (0-based, -1
+ * where an item has fewer than K) and `counts` (c_ij, 0 in the padding), n x K row-major.  The device returns integers only.
+ *
+ * A user (a row of a pattern x) is scored with an integer weight table q (n_items x K, uint32, q <= 2^30 so that no sum
+ * overflows; the caller makes it, e.g. rint(similarity * 2^30)):
+ *     score_u[j] = sum of q[i, s] over the items i of the row and the slots s with neighbors[i, s] == j       (int64)
+ * The list of u is the k items of largest score among those that are neither in the row's not_recommend entries nor in
+ * items_exclude, ties to the smaller item; items of score 0 are ranked too, so a list is shorter than k only when fewer than k
+ * items are admissible.
+ *
+ * Both entries accumulate into dense rows of a grow-only workspace of this host thread, a batch of rows at a time: rows per
+ * batch = ws_rows, or with ws_rows = 0 what RSPARSE_HIP_KNN_WS_BYTES holds (at least one row; a row is n_items cells of 4
+ * bytes for the neighbours, of 8 for the lists).  The scatter cuts the stored entries of a batch into spans of
+ * RSPARSE_HIP_KNN_SPAN per wave whatever the row lengths; the select of a row keeps up to RSPARSE_HIP_KNN_LDS_CAND non-empty
+ * cells on chip and falls back to a radix select over the dense row beyond that (wrmf_itemknn.hip).  Integer atomics only: a
+ * repeated call returns the same bits. */
+#define RSPARSE_HIP_KNN_COUNT 0
+#define RSPARSE_HIP_KNN_COSINE 1
+#define RSPARSE_HIP_KNN_JACCARD 2
+#define RSPARSE_HIP_KNN_MAX_USERS (1 << 26)
+#define RSPARSE_HIP_KNN_MAX_NEIGHBORS 256
+#define RSPARSE_HIP_KNN_MAX_TOPK 1024
+#define RSPARSE_HIP_KNN_WS_BYTES (1ull << 30)
+#define RSPARSE_HIP_KNN_SPAN 64
+#define RSPARSE_HIP_KNN_LDS_CAND 4096
+
+/* The neighbours of the items [item0, item1): d_ip / d_iu the item-major orientation (item -> its users, n_items + 1 slots),
+ * d_up / d_uj the CSR rows of the users (n_users + 1 slots), both 0-based from 0 and of the same pattern.  d_neighbors, d_counts:
+ * (item1 - item0) x K row-major.  Reads d_ip[item0 .. item1] back (waits for `stream` once), then enqueues without
+ * synchronisation.  An index outside its range is skipped on the device.
+ * NULL pointer, negative dimension, not 0 <= item0 <= item1 <= n_items, unknown similarity, K < 1, ws_rows < 0 -> ERR_INVALID;
+ * K > RSPARSE_HIP_KNN_MAX_NEIGHBORS, n_users > RSPARSE_HIP_KNN_MAX_USERS -> ERR_UNSUPPORTED; all before a device is touched. */
+int rsparse_hip_cooc_neighbors_device(const int32_t* d_ip, const int32_t* d_iu, const int32_t* d_up, const int32_t* d_uj, int n_users,
+                                      int n_items, int item0, int item1, int similarity, int K, int64_t ws_rows,
+                                      int32_t* d_neighbors, int32_t* d_counts, void* stream);
+
+/* The lists of the n_rows rows of the pattern (d_xp, d_xj) under the tables d_neighbors / d_q (n_items x K row-major; -1 slots
+ * are skipped).  d_nr_p / d_nr_j: not_recommend as CSR slots over the same rows (nullable: nothing is filtered); d_excl0:
+ * n_exclude 0-based items.  d_items: n_rows x k row-major, 1-based with INT32_MIN where a list ends, like
+ * rsparse_hip_top_product; d_scores: the int64 sums, 0 in the padding.  Reads d_xp back (waits for `stream` once).
+ * NULL pointer, negative dimension, K < 1, k < 1, ws_rows < 0, nr_p without nr_j -> ERR_INVALID; K >
+ * RSPARSE_HIP_KNN_MAX_NEIGHBORS, k > RSPARSE_HIP_KNN_MAX_TOPK -> ERR_UNSUPPORTED; all before a device is touched. */
+int rsparse_hip_knn_recommend_device(const int32_t* d_xp, const int32_t* d_xj, int n_rows, int n_items, const int32_t* d_neighbors,
+                                     const uint32_t* d_q, int K, const int32_t* d_nr_p, const int32_t* d_nr_j,
+                                     const int32_t* d_excl0, int n_exclude, int k, int64_t ws_rows, int32_t* d_items,
+                                     int64_t* d_scores, void* stream);
+
+/* host-array forms.  p / j: the dgRMatrix slots of the users x items pattern (0-based, ascending and unique within a row).
+ * neighbors / counts: n_items x K COLUMN-major, neighbors 1-based with NA_integer_ (INT32_MIN) where an item has fewer than K.
+ * Besides the refusals of the device form: p[0] != 0, a decreasing p, a column outside [0, n_items) or a row that is not
+ * strictly ascending -> ERR_INVALID, before a device is touched. */
+int rsparse_hip_cooc_neighbors(const int32_t* p, const int32_t* j, int n_users, int n_items, int similarity, int K,
+                               int32_t* neighbors, int32_t* counts);
+/* x_p / x_j and nr_p / nr_j (nullable) as above over the n_rows users; neighbors (1-based, NA or anything outside 1 .. n_items =
+ * an empty slot) and q: n_items x K column-major; exclude: 1-based items; res: n_rows x k column-major, 1-based with
+ * NA_integer_; scores: the int64 sums, column-major.  The same refusals, and q > 2^30 -> ERR_INVALID. */
+int rsparse_hip_knn_recommend(const int32_t* x_p, const int32_t* x_j, int n_rows, int n_items, const int32_t* neighbors,
+                              const uint32_t* q, int K, const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude,
+                              int n_exclude, int k, int32_t* res, int64_t* scores);
+
+/* ------------------------------------------------------------------------------------------------
  * why this item: per-item contributions to a score (Hu, Koren and Volinsky, section 5; `explain` of the `implicit` library)
  * ---------------------------------------------------------------------------------------------- */
 

@@ -11,6 +11,8 @@ Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit
   rsparse_amd.PureSVD         the reference's PureSVD recommender (R/model_PureSVD.R) with WRMF's inference surface
   rsparse_amd.soft_svd        soft_svd / soft_impute (R/SoftALS.R): soft-thresholded SVD of a sparse matrix by alternating least
                               squares, on a fused residual-SpMM kernel
+  rsparse_amd.ItemKNN         item-based k-nearest-neighbours on the co-occurrence of items (cosine, Jaccard, count), integer
+                              from end to end: neighbour table and top-k lists on the device, equal to the numpy definition
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
   rsparse_amd.engine          device-resident, row-sharded driver (one process per GPU)
   rsparse_amd.synth           synthetic interaction matrices for the BASELINE configs
@@ -38,6 +40,9 @@ def __getattr__(name):
     if name == "PureSVD":
         from .puresvd import PureSVD
         return PureSVD
+    if name in ("ItemKNN", "cooccurrence_reference", "knn_recommend_reference"):
+        from . import itemknn
+        return getattr(itemknn, name)
     if name == "metrics":
         import importlib
         return importlib.import_module(".metrics", __name__)

@@ -16,6 +16,10 @@ MAX_NEGATIVES = 8192   # RSPARSE_HIP_MAX_NEGATIVES: negatives per row of rsparse
 MAX_CUTOFFS = 16   # RSPARSE_HIP_MAX_CUTOFFS: cutoffs of one rsparse_hip_hit_metrics* call
 MAX_RANK, MAX_RANK_F64 = 256, 128   # RSPARSE_HIP_MAX_RANK, RSPARSE_HIP_MAX_RANK_F64
 SOFTALS_CHUNK, SOFTALS_SPLIT = 256, 1025   # RSPARSE_HIP_SOFTALS_CHUNK / _SPLIT: the edges of the soft-ALS kernel (wrmf_softals.hip)
+# RSPARSE_HIP_KNN_*: the similarity kinds and the edges of the ItemKNN kernels (wrmf_itemknn.hip)
+KNN_COUNT, KNN_COSINE, KNN_JACCARD = 0, 1, 2
+KNN_MAX_USERS, KNN_MAX_NEIGHBORS, KNN_MAX_TOPK = 1 << 26, 256, 1024
+KNN_WS_BYTES, KNN_SPAN, KNN_LDS_CAND = 1 << 30, 64, 4096
 RANKS_BATCH = 1024  # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that the rank count takes at a time
 
 _c_int, _c_uint, _c_dbl, _c_i64, _c_u64 = ctypes.c_int, ctypes.c_uint, ctypes.c_double, ctypes.c_int64, ctypes.c_uint64
@@ -105,6 +109,11 @@ SIGNATURES = {
     "rsparse_hip_score_pairs_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_dbl, _vp, _vp, _vp, _vp, _vp]),
     "rsparse_hip_softals_half_device": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rsparse_hip_softals_half_f64_device": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_cooc_neighbors_device": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_i64, _vp, _vp, _vp]),
+    "rsparse_hip_knn_recommend_device": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_i64, _vp, _vp,
+                                                  _vp]),
+    "rsparse_hip_cooc_neighbors": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    "rsparse_hip_knn_recommend": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp]),
     "rsparse_hip_top_candidates_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl, _vp,
                                                    _vp, _vp]),
     "rsparse_hip_top_candidates_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl,

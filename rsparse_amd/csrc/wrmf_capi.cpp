@@ -66,6 +66,8 @@ struct Workspace {
   GrowBuf<double> score_buf{all};   // pointwise predictions (wrmf_score.hip): the scores of a call that asks for the error sums only;
                                     // top-k within candidate lists (wrmf_candidates.hip): its scores / keys, bits and row lists
   GrowBuf<double> softals_buf{all};   // soft-ALS half-iteration (wrmf_softals.hip): w, s, t and the partial sums of split rows
+  GrowBuf<char> knn_buf{all};     // ItemKNN (wrmf_itemknn.hip): a batch of dense rows, all zeros between calls
+  bool knn_dirty = false;         // ... unless a call failed between its scatter and its zeroing
   GrowBuf<float> mf_G{all};       // wrmf_chol_mf.hip at rank 65..127: XtX padded to 128 x 128
   GrowBuf<float> pad_buf{all};    // ranks that are not a multiple of 4: the padded copies of X, Y, XtX, rhs_init (run_half_iteration)
   int device = -1;
@@ -1382,6 +1384,74 @@ int rsparse_hip_softals_half_device(const int32_t* d_p, const int32_t* d_j, cons
                                buf = g_ws.softals_buf;
                                return (int)RSPARSE_HIP_OK;
                              });
+}
+
+namespace {
+// The dense rows of the ItemKNN entries: `rows` rows of row_bytes each, all zeros when the work enqueued so far is done.  A
+// buffer that grew, or that a failed call left behind, is zeroed here; a call that ends well leaves zeros itself.
+static int knn_workspace(int64_t total_rows, size_t row_bytes, int64_t ws_rows, int64_t& rows, void*& ws, hipStream_t s) {
+  rows = ws_rows > 0 ? ws_rows : (int64_t)(RSPARSE_HIP_KNN_WS_BYTES / std::max<size_t>(row_bytes, 1));
+  rows = std::max<int64_t>(1, std::min(rows, total_rows));
+  const size_t bytes = std::max<size_t>((size_t)rows * row_bytes, 16);
+  if (int rc = g_ws.ensure_device()) return rc;
+  const bool grows = bytes > g_ws.knn_buf.cap;
+  HIP_TRY(g_ws.knn_buf.ensure(bytes));
+  if (grows || g_ws.knn_dirty) HIP_TRY(hipMemsetAsync(g_ws.knn_buf, 0, g_ws.knn_buf.cap, s));
+  g_ws.knn_dirty = true;   // until the caller has enqueued its last zeroing
+  ws = g_ws.knn_buf;
+  return RSPARSE_HIP_OK;
+}
+
+// n + 1 row pointers of a device pattern on the host (waits for the stream): non-negative and non-decreasing, or a refusal
+static int fetch_row_pointers(const int32_t* d_p, size_t n, std::vector<int32_t>& h, hipStream_t s, const char* name) {
+  h.resize(n + 1);
+  HIP_TRY(hipMemcpyAsync(h.data(), d_p, (n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (size_t r = 0; r <= n; r++)
+    if (h[r] < 0 || (r > 0 && h[r] < h[r - 1])) return fail(RSPARSE_HIP_ERR_INVALID, std::string(name) + " is negative or decreases");
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+
+// the host forms rsparse_hip_cooc_neighbors / rsparse_hip_knn_recommend: wrmf_capi_host.cpp
+int rsparse_hip_cooc_neighbors_device(const int32_t* d_ip, const int32_t* d_iu, const int32_t* d_up, const int32_t* d_uj, int n_users,
+                                      int n_items, int item0, int item1, int similarity, int K, int64_t ws_rows,
+                                      int32_t* d_neighbors, int32_t* d_counts, void* stream) {
+  int rc = cooc_neighbors_args(!d_ip || !d_iu || !d_up || !d_uj || !d_neighbors || !d_counts, n_users, n_items, item0, item1,
+                               similarity, K, ws_rows);
+  if (rc || item1 == item0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> h_ip;
+  if ((rc = fetch_row_pointers(d_ip + item0, (size_t)(item1 - item0), h_ip, s, "ip"))) return rc;
+  int64_t rows = 0;
+  void* ws = nullptr;
+  if ((rc = knn_workspace(item1 - item0, (size_t)n_items * sizeof(uint32_t), ws_rows, rows, ws, s))) return rc;
+  hipError_t e = launch_cooc_neighbors(d_ip, d_iu, d_up, d_uj, n_users, n_items, item0, item1, h_ip.data(), similarity, K, rows,
+                                       static_cast<unsigned*>(ws), d_neighbors, d_counts, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_cooc_neighbors");
+  g_ws.knn_dirty = false;
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_knn_recommend_device(const int32_t* d_xp, const int32_t* d_xj, int n_rows, int n_items, const int32_t* d_neighbors,
+                                     const uint32_t* d_q, int K, const int32_t* d_nr_p, const int32_t* d_nr_j,
+                                     const int32_t* d_excl0, int n_exclude, int k, int64_t ws_rows, int32_t* d_items,
+                                     int64_t* d_scores, void* stream) {
+  int rc = knn_recommend_args(!d_xp || !d_xj || !d_neighbors || !d_q || !d_items || !d_scores, n_rows, n_items, K, d_nr_p, d_nr_j,
+                              d_excl0, n_exclude, k, ws_rows);
+  if (rc || n_rows == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> h_xp;
+  if ((rc = fetch_row_pointers(d_xp, (size_t)n_rows, h_xp, s, "x_p"))) return rc;
+  int64_t rows = 0;
+  void* ws = nullptr;
+  if ((rc = knn_workspace(n_rows, (size_t)n_items * sizeof(uint64_t), ws_rows, rows, ws, s))) return rc;
+  hipError_t e = launch_knn_recommend(d_xp, d_xj, n_rows, n_items, h_xp.data(), d_neighbors, d_q, K, d_nr_p, d_nr_j,
+                                      n_exclude > 0 ? d_excl0 : nullptr, n_exclude, k, rows, static_cast<unsigned long long*>(ws),
+                                      d_items, reinterpret_cast<long long*>(d_scores), s);
+  if (e != hipSuccess) return hip_fail(e, "launch_knn_recommend");
+  g_ws.knn_dirty = false;
+  return RSPARSE_HIP_OK;
 }
 
 // `_f64_device`: wrmf_f64_capi.cpp; the host form rsparse_hip_top_candidates: wrmf_capi_host.cpp

@@ -357,6 +357,35 @@ inline int events_args(int64_t n_events, int n_users, int n_items, const void* u
   return RSPARSE_HIP_OK;
 }
 
+// ItemKNN: the neighbour table and the lists scored by it (both operand sets are named by the caller's form)
+inline int cooc_neighbors_args(bool missing, int n_users, int n_items, int item0, int item1, int similarity, int K, int64_t ws_rows) {
+  if (missing) return fail(RSPARSE_HIP_ERR_INVALID, "a pattern array or an output is NULL");
+  if (n_users < 0 || n_items < 0) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0 or n_items < 0)");
+  if (item0 < 0 || item1 < item0 || item1 > n_items) return fail(RSPARSE_HIP_ERR_INVALID, "not 0 <= item0 <= item1 <= n_items");
+  if (similarity < RSPARSE_HIP_KNN_COUNT || similarity > RSPARSE_HIP_KNN_JACCARD)
+    return fail(RSPARSE_HIP_ERR_INVALID, "unknown similarity " + std::to_string(similarity));
+  if (K < 1) return fail(RSPARSE_HIP_ERR_INVALID, "K < 1");
+  if (ws_rows < 0) return fail(RSPARSE_HIP_ERR_INVALID, "ws_rows < 0");
+  if (K > RSPARSE_HIP_KNN_MAX_NEIGHBORS)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "K > 256 (RSPARSE_HIP_KNN_MAX_NEIGHBORS) is not on the device path");
+  if (n_users > RSPARSE_HIP_KNN_MAX_USERS)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "n_users > 2^26 (RSPARSE_HIP_KNN_MAX_USERS): c^2 and n_i n_j would not be exact in double");
+  return RSPARSE_HIP_OK;
+}
+inline int knn_recommend_args(bool missing, int n_rows, int n_items, int K, const void* nr_p, const void* nr_j, const void* excl,
+                              int n_exclude, int k, int64_t ws_rows) {
+  if (missing) return fail(RSPARSE_HIP_ERR_INVALID, "the pattern (x_p, x_j), a table or an output is NULL");
+  if (n_rows < 0 || n_items < 0) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0 or n_items < 0)");
+  if (K < 1 || k < 1) return fail(RSPARSE_HIP_ERR_INVALID, "K < 1 or k < 1");
+  if (ws_rows < 0) return fail(RSPARSE_HIP_ERR_INVALID, "ws_rows < 0");
+  if (nr_p && !nr_j) return fail(RSPARSE_HIP_ERR_INVALID, "nr_p without nr_j");
+  if (n_exclude < 0 || (n_exclude > 0 && !excl)) return fail(RSPARSE_HIP_ERR_INVALID, "bad exclude");
+  if (K > RSPARSE_HIP_KNN_MAX_NEIGHBORS)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "K > 256 (RSPARSE_HIP_KNN_MAX_NEIGHBORS) is not on the device path");
+  if (k > RSPARSE_HIP_KNN_MAX_TOPK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 1024 (RSPARSE_HIP_KNN_MAX_TOPK) is not on the device path");
+  return RSPARSE_HIP_OK;
+}
+
 // rsparse_hip_score_pairs_device / _f64_device (kernels: wrmf_score.hip).  Handed in:
 //   int workspace(size_t n, double*& buf)    makes sure of n doubles of the side's grow-only workspace
 // which is only asked for the sums without the scores: the scores then live there, and their count, p[n_rows], has to be

@@ -30,6 +30,15 @@ int check_csr(const int32_t* p, int n, const char* p_name, const int32_t* j = nu
   return RSPARSE_HIP_OK;
 }
 
+// the columns of a checked p: inside [0, n_cols) and strictly ascending within a row (a canonical pattern)
+int check_columns(const int32_t* p, const int32_t* j, int n, int n_cols, const char* j_name) {
+  for (int u = 0; u < n; u++)
+    for (int32_t e = p[u]; e < p[u + 1]; e++)
+      if (j[e] < 0 || j[e] >= n_cols || (e > p[u] && j[e] <= j[e - 1]))
+        return fail(RSPARSE_HIP_ERR_INVALID, std::string(j_name) + " has a column outside [0, n_items), or a row is not strictly ascending");
+  return RSPARSE_HIP_OK;
+}
+
 // n x k column-major (an R matrix: the predicted lists, their scores, the user factors) -> row-major T
 template <class T, class S>
 std::vector<T> row_major(const S* a, int n, int k) {
@@ -770,6 +779,83 @@ int rsparse_hip_events_to_csr(int64_t n_events, int n_users, int n_items, const 
   if (count) HIP_TRY(download(count, dC, nc));
   if (want_latest) HIP_TRY(download(latest, dL, nc));
   return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_cooc_neighbors(const int32_t* p, const int32_t* j, int n_users, int n_items, int similarity, int K,
+                               int32_t* neighbors, int32_t* counts) {
+  int rc = cooc_neighbors_args(!p || !neighbors || !counts, n_users, n_items, 0, n_items, similarity, K, 0);
+  if (rc) return rc;
+  if ((rc = check_csr(p, n_users, "p"))) return rc;
+  const size_t nnz = (size_t)p[n_users];
+  if (nnz && !j) return fail(RSPARSE_HIP_ERR_INVALID, "j is NULL");
+  if ((rc = check_columns(p, j, n_users, n_items, "j"))) return rc;
+  if (n_items == 0) return RSPARSE_HIP_OK;
+  // the item-major orientation: a counting sort, users ascending within an item
+  std::vector<int32_t> ip((size_t)n_items + 1, 0), iu(nnz);
+  for (size_t e = 0; e < nnz; e++) ip[(size_t)j[e] + 1]++;
+  for (int i = 0; i < n_items; i++) ip[(size_t)i + 1] += ip[i];
+  std::vector<int32_t> at(ip.begin(), ip.end() - 1);
+  for (int u = 0; u < n_users; u++)
+    for (int32_t e = p[u]; e < p[u + 1]; e++) iu[(size_t)at[j[e]]++] = u;
+  DevBuf dIP, dIU, dUP, dUJ, dN, dC;
+  HIP_TRY(upload_host(dIP, ip.data(), ip.size()));
+  HIP_TRY(upload_host(dIU, iu.data(), nnz));
+  HIP_TRY(upload_host(dUP, p, (size_t)n_users + 1));
+  HIP_TRY(upload_host(dUJ, j, nnz));
+  HIP_TRY(dN.alloc((size_t)n_items * K * 4));
+  HIP_TRY(dC.alloc((size_t)n_items * K * 4));
+  rc = rsparse_hip_cooc_neighbors_device(dIP.as<int32_t>(), dIU.as<int32_t>(), dUP.as<int32_t>(), dUJ.as<int32_t>(), n_users, n_items,
+                                         0, n_items, similarity, K, 0, dN.as<int32_t>(), dC.as<int32_t>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if ((rc = fetch_col_major(dN, n_items, K, neighbors))) return rc;
+  for (size_t t = 0; t < (size_t)n_items * K; t++) neighbors[t] = neighbors[t] < 0 ? INT32_MIN : neighbors[t] + 1;   // R's ids
+  return fetch_col_major(dC, n_items, K, counts);
+}
+
+int rsparse_hip_knn_recommend(const int32_t* x_p, const int32_t* x_j, int n_rows, int n_items, const int32_t* neighbors,
+                              const uint32_t* q, int K, const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude,
+                              int n_exclude, int k, int32_t* res, int64_t* scores) {
+  int rc = knn_recommend_args(!x_p || !neighbors || !q || !res || !scores, n_rows, n_items, K, nr_p, nr_j, exclude, n_exclude, k, 0);
+  if (rc) return rc;
+  if ((rc = check_csr(x_p, n_rows, "x_p"))) return rc;
+  const size_t nnz = (size_t)x_p[n_rows];
+  if (nnz && !x_j) return fail(RSPARSE_HIP_ERR_INVALID, "x_j is NULL");
+  if ((rc = check_columns(x_p, x_j, n_rows, n_items, "x_j"))) return rc;
+  if (nr_p) {
+    if ((rc = check_csr(nr_p, n_rows, "nr_p"))) return rc;
+    for (int32_t e = 0; e < nr_p[n_rows]; e++)
+      if (nr_j[e] < 0 || nr_j[e] >= n_items) return fail(RSPARSE_HIP_ERR_INVALID, "nr_j has a column outside [0, n_items)");
+  }
+  const size_t nt = (size_t)n_items * K;
+  for (size_t t = 0; t < nt; t++)
+    if (q[t] > (1u << 30)) return fail(RSPARSE_HIP_ERR_INVALID, "a weight of q is above 2^30");
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  std::vector<int32_t> nb = row_major<int32_t>(neighbors, n_items, K);
+  for (size_t t = 0; t < nt; t++) nb[t] = (nb[t] >= 1 && nb[t] <= n_items) ? nb[t] - 1 : -1;
+  const std::vector<uint32_t> qr = row_major<uint32_t>(q, n_items, K);
+  std::vector<int32_t> ex;
+  add_excluded(exclude, n_exclude, n_items, ex);
+  const size_t np1 = (size_t)n_rows + 1, nk = (size_t)n_rows * k;
+  DevBuf dXP, dXJ, dNb, dQ, dP, dJ, dE, dR, dS;
+  HIP_TRY(upload_host(dXP, x_p, np1));
+  HIP_TRY(upload_host(dXJ, x_j, nnz));
+  HIP_TRY(upload_host(dNb, nb.data(), nt));
+  HIP_TRY(upload_host(dQ, qr.data(), nt));
+  if (nr_p) {
+    HIP_TRY(upload_host(dP, nr_p, np1));
+    HIP_TRY(upload_host(dJ, nr_j, (size_t)nr_p[n_rows]));
+  }
+  if (!ex.empty()) HIP_TRY(upload_host(dE, ex.data(), ex.size()));
+  HIP_TRY(dR.alloc(nk * 4));
+  HIP_TRY(dS.alloc(nk * 8));
+  rc = rsparse_hip_knn_recommend_device(dXP.as<int32_t>(), dXJ.as<int32_t>(), n_rows, n_items, dNb.as<int32_t>(), dQ.as<uint32_t>(), K,
+                                        opt<int32_t>(nr_p, dP), opt<int32_t>(nr_p, dJ), opt<int32_t>(!ex.empty(), dE), (int)ex.size(),
+                                        k, 0, dR.as<int32_t>(), dS.as<int64_t>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if ((rc = fetch_col_major(dR, n_rows, k, res))) return rc;
+  return fetch_col_major(dS, n_rows, k, scores);
 }
 
 }  // extern "C"

@@ -801,6 +801,42 @@ class HipBackend:
                       out.data_ptr() if n else p.data_ptr(), None if sumsq is None else sumsq.data_ptr(), self._stream()))
         return out, sumsq
 
+    def cooc_neighbors(self, ip, iu, up, uj, n_users, n_items, similarity, K, item0=0, item1=None, ws_rows=0):
+        """the ItemKNN neighbour table of the items [item0, item1) (wrmf_itemknn.hip; rsparse_amd.itemknn.cooccurrence_reference is
+        the definition): ip / iu the item-major orientation of the pattern (item -> its users), up / uj its CSR rows, int32 on the
+        device; similarity: _lib.KNN_COUNT / KNN_COSINE / KNN_JACCARD.  -> (neighbors, counts): (item1 - item0, K) int32 on the
+        device, 0-based with -1 where an item has fewer than K neighbours, counts 0 there.  ws_rows: dense rows per batch (0 =
+        what the default workspace holds)."""
+        item1 = int(n_items) if item1 is None else int(item1)
+        n = max(item1 - int(item0), 0)
+        assert all(t.dtype == torch.int32 for t in (ip, iu, up, uj))
+        nb = torch.empty((n, int(K)), dtype=torch.int32, device=self.device)
+        ct = torch.empty((n, int(K)), dtype=torch.int32, device=self.device)
+        some = lambda t: t.data_ptr() if t.numel() else ip.data_ptr()   # (an empty tensor has no address to pass)
+        _lib.check(self.lib.rsparse_hip_cooc_neighbors_device(ip.data_ptr(), some(iu), up.data_ptr(), some(uj), int(n_users), int(n_items),
+                                                              int(item0), item1, int(similarity), int(K), int(ws_rows),
+                                                              some(nb), some(ct), self._stream()))
+        return nb, ct
+
+    def knn_recommend(self, xp, xj, neighbors, q, k, nr_p=None, nr_j=None, exclude0=None, ws_rows=0):
+        """the ItemKNN lists of the rows of a CSR pattern (xp, xj: int32 on the device) under the tables neighbors (n_items x K
+        int32, 0-based, -1 = empty slot) and q (n_items x K integer weights <= 2^30, held as int64 or int32 here and handed on as
+        uint32): wrmf_itemknn.hip, rsparse_amd.itemknn.knn_recommend_reference is the definition.  nr_p / nr_j: the rows'
+        not_recommend entries as CSR slots (or None), exclude0: 0-based item ids (or None).  -> (items (n, k) int32, 1-based with
+        NA_integer_; scores (n, k) int64, 0 where NA) on the device."""
+        assert xp.dtype == torch.int32 and xj.dtype == torch.int32 and neighbors.dtype == torch.int32 and neighbors.shape == q.shape
+        n, (n_items, K) = int(xp.numel()) - 1, neighbors.shape
+        neighbors = neighbors.contiguous()
+        q32 = q.to(torch.int64).to(torch.int32).contiguous()   # (q <= 2^30: the same bits as uint32)
+        res = torch.empty((n, int(k)), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, int(k)), dtype=torch.int64, device=self.device)
+        some = lambda t: t.data_ptr() if t.numel() else xp.data_ptr()
+        _lib.check(self.lib.rsparse_hip_knn_recommend_device(
+            xp.data_ptr(), some(xj), n, int(n_items), some(neighbors), some(q32), int(K), None if nr_p is None else nr_p.data_ptr(),
+            None if nr_p is None else some(nr_j), None if exclude0 is None or not exclude0.numel() else exclude0.data_ptr(),
+            0 if exclude0 is None else int(exclude0.numel()), int(k), int(ws_rows), some(res), some(sc), self._stream()))
+        return res, sc
+
     def explain_pairs(self, V, base, diag, diag_per_nnz, x_p, x_j, wa, wb, t_p, t_j):
         """what every interaction of a row contributes to the scores of the row's target items (wrmf_explain.hip): for the users
         of the CSR rows (x_p, x_j: int32 on the device; wa, wb: the assembly and contribution weight of every stored position, in
