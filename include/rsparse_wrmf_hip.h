@@ -808,6 +808,56 @@ int rsparse_hip_knn_recommend(const int32_t* x_p, const int32_t* x_j, int n_rows
                               const uint32_t* q, int K, const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude,
                               int n_exclude, int k, int32_t* res, int64_t* scores);
 
+/* ItemKNN on weighted values (rsparse_amd/itemknn.py states it in numpy; its recipes turn BM25 / TF-IDF cosine, the dot product,
+ * the asymmetric cosine and P3alpha / RP3beta into the operands below).  On the canonical CSR pattern of the users x items
+ * matrix an entry (u, i) carries two uint32: l_ui, used when i is the item whose neighbours are sought, and r_ui, used when i is
+ * the neighbour, with max(l) max(r) max_j n_j < 2^53 (n_j = the users of item j), so that
+ *     c_ij = sum_u l_ui r_uj      (j != i; uint64, below 2^53: double(c_ij) is exact)
+ * The order key is  key_ij = double(c_ij) / (a_i b_j + h)  with tables a, b of n_items doubles and one double h, made by the
+ * host: exactly three roundings in double -- the product, the sum, the division -- and no fused multiply-add.  a, b finite and in
+ * [2^-200, 2^200], h finite and in [0, 2^400]: every key of a non-empty cell is then a positive normal double and 0 stays the
+ * mark of an empty cell.  The neighbours of i are the K items j != i with c_ij > 0 of largest key, ties to the smaller j:
+ * `neighbors` as above, `sums` uint64 = c_ij with 0 in the padding.  The device returns integers only; the similarity of a slot
+ * is its key, recomputed by the caller from `sums` and the tables.
+ *
+ * A weighted row is scored as  score_u[j] = sum of xv_ui q[i, s]  over the items i of the row and the slots s with
+ * neighbors[i, s] == j, xv <= 2^16 - 1 and a row's sum of xv below 2^31, so that a score stays below 2^61.
+ *
+ * A dense row of the weighted neighbours is n_items cells of 8 bytes (half as many rows per batch as the binary entry holds);
+ * ws_rows keeps its meaning.  64-bit integer atomics on global memory only. */
+
+/* d_il: l by stored position of the item-major orientation (d_ip / d_iu), d_ur: r by stored position of the CSR rows (d_up /
+ * d_uj); d_a, d_b: n_items doubles on the device.  d_neighbors (int32), d_sums (uint64): (item1 - item0) x K row-major.  Reads
+ * d_ip[item0 .. item1] back (waits for `stream` once).  The ranges of a, b and the 2^53 bound are preconditions here (the host
+ * form checks them); whatever the values hold, nothing outside the operands and the workspace is read or written.
+ * NULL pointer, negative dimension, not 0 <= item0 <= item1 <= n_items, K < 1, ws_rows < 0, h not finite or outside [0, 2^400]
+ * -> ERR_INVALID; K > RSPARSE_HIP_KNN_MAX_NEIGHBORS -> ERR_UNSUPPORTED; all before a device is touched.  (The n_users limit of
+ * the binary entry does not apply: the 2^53 bound replaces it.) */
+int rsparse_hip_cooc_neighbors_weighted_device(const int32_t* d_ip, const int32_t* d_iu, const uint32_t* d_il, const int32_t* d_up,
+                                               const int32_t* d_uj, const uint32_t* d_ur, int n_users, int n_items, int item0,
+                                               int item1, const double* d_a, const double* d_b, double h, int K, int64_t ws_rows,
+                                               int32_t* d_neighbors, uint64_t* d_sums, void* stream);
+
+/* rsparse_hip_knn_recommend_device with the rows' weights d_xv (one uint32 per stored position of d_xj; NULL = all ones, which
+ * is rsparse_hip_knn_recommend_device itself).  The same refusals. */
+int rsparse_hip_knn_recommend_weighted_device(const int32_t* d_xp, const int32_t* d_xj, const uint32_t* d_xv, int n_rows, int n_items,
+                                              const int32_t* d_neighbors, const uint32_t* d_q, int K, const int32_t* d_nr_p,
+                                              const int32_t* d_nr_j, const int32_t* d_excl0, int n_exclude, int k, int64_t ws_rows,
+                                              int32_t* d_items, int64_t* d_scores, void* stream);
+
+/* host-array forms, with the conventions of the pair above.  l, r: one uint32 per stored position of (p, j); a, b: n_items
+ * doubles; neighbors / sums: n_items x K COLUMN-major, neighbors 1-based with NA_integer_.  Besides the refusals of the device
+ * form and of rsparse_hip_cooc_neighbors' arrays: l or r NULL with stored entries, a or b not finite or outside [2^-200, 2^200],
+ * max(l) max(r) max_j n_j >= 2^53 -> ERR_INVALID, before a device is touched. */
+int rsparse_hip_cooc_neighbors_weighted(const int32_t* p, const int32_t* j, const uint32_t* l, const uint32_t* r, int n_users,
+                                        int n_items, const double* a, const double* b, double h, int K, int32_t* neighbors,
+                                        uint64_t* sums);
+/* rsparse_hip_knn_recommend with x_v (nullable = all ones): besides its refusals, x_v above 2^16 - 1 and a row whose x_v sum to
+ * 2^31 or more -> ERR_INVALID. */
+int rsparse_hip_knn_recommend_weighted(const int32_t* x_p, const int32_t* x_j, const uint32_t* x_v, int n_rows, int n_items,
+                                       const int32_t* neighbors, const uint32_t* q, int K, const int32_t* nr_p, const int32_t* nr_j,
+                                       const int32_t* exclude, int n_exclude, int k, int32_t* res, int64_t* scores);
+
 /* ------------------------------------------------------------------------------------------------
  * why this item: per-item contributions to a score (Hu, Koren and Volinsky, section 5; `explain` of the `implicit` library)
  * ---------------------------------------------------------------------------------------------- */

@@ -12,7 +12,8 @@ Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit
   rsparse_amd.soft_svd        soft_svd / soft_impute (R/SoftALS.R): soft-thresholded SVD of a sparse matrix by alternating least
                               squares, on a fused residual-SpMM kernel
   rsparse_amd.ItemKNN         item-based k-nearest-neighbours on the co-occurrence of items (cosine, Jaccard, count), integer
-                              from end to end: neighbour table and top-k lists on the device, equal to the numpy definition
+                              from end to end: neighbour table and top-k lists on the device, equal to the numpy definition;
+                              with weighting= on quantised values: BM25 / TF-IDF cosine, dot, asymmetric cosine, P3alpha / RP3beta
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
   rsparse_amd.engine          device-resident, row-sharded driver (one process per GPU)
   rsparse_amd.synth           synthetic interaction matrices for the BASELINE configs
@@ -40,7 +41,8 @@ def __getattr__(name):
     if name == "PureSVD":
         from .puresvd import PureSVD
         return PureSVD
-    if name in ("ItemKNN", "cooccurrence_reference", "knn_recommend_reference"):
+    if name in ("ItemKNN", "cooccurrence_reference", "knn_recommend_reference", "quantize_values", "weighted_operands",
+                "weighted_cooccurrence_reference"):
         from . import itemknn
         return getattr(itemknn, name)
     if name == "metrics":

@@ -114,6 +114,13 @@ SIGNATURES = {
                                                   _vp]),
     "rsparse_hip_cooc_neighbors": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "rsparse_hip_knn_recommend": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp]),
+    "rsparse_hip_cooc_neighbors_weighted_device": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_dbl,
+                                                            _c_int, _c_i64, _vp, _vp, _vp]),
+    "rsparse_hip_knn_recommend_weighted_device": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _c_int, _c_int,
+                                                           _c_i64, _vp, _vp, _vp]),
+    "rsparse_hip_cooc_neighbors_weighted": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_dbl, _c_int, _vp, _vp]),
+    "rsparse_hip_knn_recommend_weighted": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp,
+                                                    _vp]),
     "rsparse_hip_top_candidates_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl, _vp,
                                                    _vp, _vp]),
     "rsparse_hip_top_candidates_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl,

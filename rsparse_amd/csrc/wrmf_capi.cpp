@@ -1413,7 +1413,7 @@ static int fetch_row_pointers(const int32_t* d_p, size_t n, std::vector<int32_t>
 }
 }  // namespace
 
-// the host forms rsparse_hip_cooc_neighbors / rsparse_hip_knn_recommend: wrmf_capi_host.cpp
+// the host forms rsparse_hip_cooc_neighbors / rsparse_hip_knn_recommend and their `_weighted` forms: wrmf_capi_host.cpp
 int rsparse_hip_cooc_neighbors_device(const int32_t* d_ip, const int32_t* d_iu, const int32_t* d_up, const int32_t* d_uj, int n_users,
                                       int n_items, int item0, int item1, int similarity, int K, int64_t ws_rows,
                                       int32_t* d_neighbors, int32_t* d_counts, void* stream) {
@@ -1433,10 +1433,31 @@ int rsparse_hip_cooc_neighbors_device(const int32_t* d_ip, const int32_t* d_iu, 
   return RSPARSE_HIP_OK;
 }
 
-int rsparse_hip_knn_recommend_device(const int32_t* d_xp, const int32_t* d_xj, int n_rows, int n_items, const int32_t* d_neighbors,
-                                     const uint32_t* d_q, int K, const int32_t* d_nr_p, const int32_t* d_nr_j,
-                                     const int32_t* d_excl0, int n_exclude, int k, int64_t ws_rows, int32_t* d_items,
-                                     int64_t* d_scores, void* stream) {
+int rsparse_hip_cooc_neighbors_weighted_device(const int32_t* d_ip, const int32_t* d_iu, const uint32_t* d_il, const int32_t* d_up,
+                                               const int32_t* d_uj, const uint32_t* d_ur, int n_users, int n_items, int item0,
+                                               int item1, const double* d_a, const double* d_b, double h, int K, int64_t ws_rows,
+                                               int32_t* d_neighbors, uint64_t* d_sums, void* stream) {
+  int rc = cooc_neighbors_weighted_args(!d_ip || !d_iu || !d_il || !d_up || !d_uj || !d_ur || !d_a || !d_b || !d_neighbors || !d_sums,
+                                        n_users, n_items, item0, item1, h, K, ws_rows);
+  if (rc || item1 == item0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> h_ip;
+  if ((rc = fetch_row_pointers(d_ip + item0, (size_t)(item1 - item0), h_ip, s, "ip"))) return rc;
+  int64_t rows = 0;
+  void* ws = nullptr;
+  if ((rc = knn_workspace(item1 - item0, (size_t)n_items * sizeof(uint64_t), ws_rows, rows, ws, s))) return rc;
+  hipError_t e = launch_cooc_neighbors_weighted(d_ip, d_iu, d_il, d_up, d_uj, d_ur, n_users, n_items, item0, item1, h_ip.data(), d_a,
+                                                d_b, h, K, rows, static_cast<unsigned long long*>(ws), d_neighbors,
+                                                reinterpret_cast<unsigned long long*>(d_sums), s);
+  if (e != hipSuccess) return hip_fail(e, "launch_cooc_neighbors_weighted");
+  g_ws.knn_dirty = false;
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_knn_recommend_weighted_device(const int32_t* d_xp, const int32_t* d_xj, const uint32_t* d_xv, int n_rows, int n_items,
+                                              const int32_t* d_neighbors, const uint32_t* d_q, int K, const int32_t* d_nr_p,
+                                              const int32_t* d_nr_j, const int32_t* d_excl0, int n_exclude, int k, int64_t ws_rows,
+                                              int32_t* d_items, int64_t* d_scores, void* stream) {
   int rc = knn_recommend_args(!d_xp || !d_xj || !d_neighbors || !d_q || !d_items || !d_scores, n_rows, n_items, K, d_nr_p, d_nr_j,
                               d_excl0, n_exclude, k, ws_rows);
   if (rc || n_rows == 0) return rc;
@@ -1446,12 +1467,20 @@ int rsparse_hip_knn_recommend_device(const int32_t* d_xp, const int32_t* d_xj, i
   int64_t rows = 0;
   void* ws = nullptr;
   if ((rc = knn_workspace(n_rows, (size_t)n_items * sizeof(uint64_t), ws_rows, rows, ws, s))) return rc;
-  hipError_t e = launch_knn_recommend(d_xp, d_xj, n_rows, n_items, h_xp.data(), d_neighbors, d_q, K, d_nr_p, d_nr_j,
+  hipError_t e = launch_knn_recommend(d_xp, d_xj, d_xv, n_rows, n_items, h_xp.data(), d_neighbors, d_q, K, d_nr_p, d_nr_j,
                                       n_exclude > 0 ? d_excl0 : nullptr, n_exclude, k, rows, static_cast<unsigned long long*>(ws),
                                       d_items, reinterpret_cast<long long*>(d_scores), s);
   if (e != hipSuccess) return hip_fail(e, "launch_knn_recommend");
   g_ws.knn_dirty = false;
   return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_knn_recommend_device(const int32_t* d_xp, const int32_t* d_xj, int n_rows, int n_items, const int32_t* d_neighbors,
+                                     const uint32_t* d_q, int K, const int32_t* d_nr_p, const int32_t* d_nr_j,
+                                     const int32_t* d_excl0, int n_exclude, int k, int64_t ws_rows, int32_t* d_items,
+                                     int64_t* d_scores, void* stream) {
+  return rsparse_hip_knn_recommend_weighted_device(d_xp, d_xj, nullptr, n_rows, n_items, d_neighbors, d_q, K, d_nr_p, d_nr_j, d_excl0,
+                                                   n_exclude, k, ws_rows, d_items, d_scores, stream);
 }
 
 // `_f64_device`: wrmf_f64_capi.cpp; the host form rsparse_hip_top_candidates: wrmf_capi_host.cpp

@@ -372,6 +372,18 @@ inline int cooc_neighbors_args(bool missing, int n_users, int n_items, int item0
     return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "n_users > 2^26 (RSPARSE_HIP_KNN_MAX_USERS): c^2 and n_i n_j would not be exact in double");
   return RSPARSE_HIP_OK;
 }
+// the weighted table: no similarity kind and no n_users limit (the caller's 2^53 bound replaces it), the key's h instead
+inline int cooc_neighbors_weighted_args(bool missing, int n_users, int n_items, int item0, int item1, double h, int K, int64_t ws_rows) {
+  if (missing) return fail(RSPARSE_HIP_ERR_INVALID, "a pattern array, an operand, a table or an output is NULL");
+  if (n_users < 0 || n_items < 0) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0 or n_items < 0)");
+  if (item0 < 0 || item1 < item0 || item1 > n_items) return fail(RSPARSE_HIP_ERR_INVALID, "not 0 <= item0 <= item1 <= n_items");
+  if (K < 1) return fail(RSPARSE_HIP_ERR_INVALID, "K < 1");
+  if (ws_rows < 0) return fail(RSPARSE_HIP_ERR_INVALID, "ws_rows < 0");
+  if (!(h >= 0.0 && h <= 0x1p400)) return fail(RSPARSE_HIP_ERR_INVALID, "h is not finite or outside [0, 2^400]");   // (NaN fails both)
+  if (K > RSPARSE_HIP_KNN_MAX_NEIGHBORS)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "K > 256 (RSPARSE_HIP_KNN_MAX_NEIGHBORS) is not on the device path");
+  return RSPARSE_HIP_OK;
+}
 inline int knn_recommend_args(bool missing, int n_rows, int n_items, int K, const void* nr_p, const void* nr_j, const void* excl,
                               int n_exclude, int k, int64_t ws_rows) {
   if (missing) return fail(RSPARSE_HIP_ERR_INVALID, "the pattern (x_p, x_j), a table or an output is NULL");

@@ -781,6 +781,27 @@ int rsparse_hip_events_to_csr(int64_t n_events, int n_users, int n_items, const 
   return RSPARSE_HIP_OK;
 }
 
+namespace {
+// the item-major orientation of a checked pattern: a counting sort, users ascending within an item; l (nullable): a value per
+// stored position, which moves with its entry into il
+void item_major(const int32_t* p, const int32_t* j, int n_users, int n_items, std::vector<int32_t>& ip, std::vector<int32_t>& iu,
+                const uint32_t* l, std::vector<uint32_t>* il) {
+  const size_t nnz = (size_t)p[n_users];
+  ip.assign((size_t)n_items + 1, 0);
+  iu.resize(nnz);
+  if (l) il->resize(nnz);
+  for (size_t e = 0; e < nnz; e++) ip[(size_t)j[e] + 1]++;
+  for (int i = 0; i < n_items; i++) ip[(size_t)i + 1] += ip[i];
+  std::vector<int32_t> at(ip.begin(), ip.end() - 1);
+  for (int u = 0; u < n_users; u++)
+    for (int32_t e = p[u]; e < p[u + 1]; e++) {
+      const size_t t = (size_t)at[j[e]]++;
+      iu[t] = u;
+      if (l) (*il)[t] = l[e];
+    }
+}
+}  // namespace
+
 int rsparse_hip_cooc_neighbors(const int32_t* p, const int32_t* j, int n_users, int n_items, int similarity, int K,
                                int32_t* neighbors, int32_t* counts) {
   int rc = cooc_neighbors_args(!p || !neighbors || !counts, n_users, n_items, 0, n_items, similarity, K, 0);
@@ -790,13 +811,8 @@ int rsparse_hip_cooc_neighbors(const int32_t* p, const int32_t* j, int n_users, 
   if (nnz && !j) return fail(RSPARSE_HIP_ERR_INVALID, "j is NULL");
   if ((rc = check_columns(p, j, n_users, n_items, "j"))) return rc;
   if (n_items == 0) return RSPARSE_HIP_OK;
-  // the item-major orientation: a counting sort, users ascending within an item
-  std::vector<int32_t> ip((size_t)n_items + 1, 0), iu(nnz);
-  for (size_t e = 0; e < nnz; e++) ip[(size_t)j[e] + 1]++;
-  for (int i = 0; i < n_items; i++) ip[(size_t)i + 1] += ip[i];
-  std::vector<int32_t> at(ip.begin(), ip.end() - 1);
-  for (int u = 0; u < n_users; u++)
-    for (int32_t e = p[u]; e < p[u + 1]; e++) iu[(size_t)at[j[e]]++] = u;
+  std::vector<int32_t> ip, iu;
+  item_major(p, j, n_users, n_items, ip, iu, nullptr, nullptr);
   DevBuf dIP, dIU, dUP, dUJ, dN, dC;
   HIP_TRY(upload_host(dIP, ip.data(), ip.size()));
   HIP_TRY(upload_host(dIU, iu.data(), nnz));
@@ -813,15 +829,78 @@ int rsparse_hip_cooc_neighbors(const int32_t* p, const int32_t* j, int n_users, 
   return fetch_col_major(dC, n_items, K, counts);
 }
 
+int rsparse_hip_cooc_neighbors_weighted(const int32_t* p, const int32_t* j, const uint32_t* l, const uint32_t* r, int n_users,
+                                        int n_items, const double* a, const double* b, double h, int K, int32_t* neighbors,
+                                        uint64_t* sums) {
+  int rc = cooc_neighbors_weighted_args(!p || !a || !b || !neighbors || !sums, n_users, n_items, 0, n_items, h, K, 0);
+  if (rc) return rc;
+  if ((rc = check_csr(p, n_users, "p"))) return rc;
+  const size_t nnz = (size_t)p[n_users];
+  if (nnz && !j) return fail(RSPARSE_HIP_ERR_INVALID, "j is NULL");
+  if (nnz && (!l || !r)) return fail(RSPARSE_HIP_ERR_INVALID, "l or r is NULL");
+  if ((rc = check_columns(p, j, n_users, n_items, "j"))) return rc;
+  for (int i = 0; i < n_items; i++)
+    if (!(a[i] >= 0x1p-200 && a[i] <= 0x1p200 && b[i] >= 0x1p-200 && b[i] <= 0x1p200))   // (NaN fails)
+      return fail(RSPARSE_HIP_ERR_INVALID, "a table entry of a or b is not finite or outside [2^-200, 2^200]");
+  if (n_items == 0) return RSPARSE_HIP_OK;
+  std::vector<int32_t> ip, iu;
+  std::vector<uint32_t> il;
+  item_major(p, j, n_users, n_items, ip, iu, l, &il);
+  uint32_t max_l = 0, max_r = 0;
+  int32_t max_n = 0;
+  for (size_t e = 0; e < nnz; e++) {
+    max_l = std::max(max_l, l[e]);
+    max_r = std::max(max_r, r[e]);
+  }
+  for (int i = 0; i < n_items; i++) max_n = std::max(max_n, ip[(size_t)i + 1] - ip[i]);
+  if ((unsigned __int128)max_l * max_r * (unsigned __int128)max_n >= ((unsigned __int128)1 << 53))
+    return fail(RSPARSE_HIP_ERR_INVALID, "max(l) max(r) max_j n_j >= 2^53: a sum would not be exact in double");
+  DevBuf dIP, dIU, dIL, dUP, dUJ, dUR, dA, dB, dN, dS;
+  HIP_TRY(upload_host(dIP, ip.data(), ip.size()));
+  HIP_TRY(upload_host(dIU, iu.data(), nnz));
+  HIP_TRY(upload_host(dIL, il.data(), nnz));
+  HIP_TRY(upload_host(dUP, p, (size_t)n_users + 1));
+  HIP_TRY(upload_host(dUJ, j, nnz));
+  HIP_TRY(upload_host(dUR, r, nnz));
+  HIP_TRY(upload_host(dA, a, (size_t)n_items));
+  HIP_TRY(upload_host(dB, b, (size_t)n_items));
+  HIP_TRY(dN.alloc((size_t)n_items * K * 4));
+  HIP_TRY(dS.alloc((size_t)n_items * K * 8));
+  rc = rsparse_hip_cooc_neighbors_weighted_device(dIP.as<int32_t>(), dIU.as<int32_t>(), dIL.as<uint32_t>(), dUP.as<int32_t>(),
+                                                  dUJ.as<int32_t>(), dUR.as<uint32_t>(), n_users, n_items, 0, n_items, dA.as<double>(),
+                                                  dB.as<double>(), h, K, 0, dN.as<int32_t>(), dS.as<uint64_t>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if ((rc = fetch_col_major(dN, n_items, K, neighbors))) return rc;
+  for (size_t t = 0; t < (size_t)n_items * K; t++) neighbors[t] = neighbors[t] < 0 ? INT32_MIN : neighbors[t] + 1;   // R's ids
+  return fetch_col_major(dS, n_items, K, sums);
+}
+
 int rsparse_hip_knn_recommend(const int32_t* x_p, const int32_t* x_j, int n_rows, int n_items, const int32_t* neighbors,
                               const uint32_t* q, int K, const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude,
                               int n_exclude, int k, int32_t* res, int64_t* scores) {
+  return rsparse_hip_knn_recommend_weighted(x_p, x_j, nullptr, n_rows, n_items, neighbors, q, K, nr_p, nr_j, exclude, n_exclude, k, res,
+                                            scores);
+}
+
+int rsparse_hip_knn_recommend_weighted(const int32_t* x_p, const int32_t* x_j, const uint32_t* x_v, int n_rows, int n_items,
+                                       const int32_t* neighbors, const uint32_t* q, int K, const int32_t* nr_p, const int32_t* nr_j,
+                                       const int32_t* exclude, int n_exclude, int k, int32_t* res, int64_t* scores) {
   int rc = knn_recommend_args(!x_p || !neighbors || !q || !res || !scores, n_rows, n_items, K, nr_p, nr_j, exclude, n_exclude, k, 0);
   if (rc) return rc;
   if ((rc = check_csr(x_p, n_rows, "x_p"))) return rc;
   const size_t nnz = (size_t)x_p[n_rows];
   if (nnz && !x_j) return fail(RSPARSE_HIP_ERR_INVALID, "x_j is NULL");
   if ((rc = check_columns(x_p, x_j, n_rows, n_items, "x_j"))) return rc;
+  if (x_v)
+    for (int u = 0; u < n_rows; u++) {
+      uint64_t sum = 0;
+      for (int32_t e = x_p[u]; e < x_p[u + 1]; e++) {
+        if (x_v[e] > 0xffffu) return fail(RSPARSE_HIP_ERR_INVALID, "a weight of x_v is above 2^16 - 1");
+        sum += x_v[e];
+      }
+      if (sum >= (1ull << 31)) return fail(RSPARSE_HIP_ERR_INVALID, "the weights x_v of a row sum to 2^31 or more");
+    }
   if (nr_p) {
     if ((rc = check_csr(nr_p, n_rows, "nr_p"))) return rc;
     for (int32_t e = 0; e < nr_p[n_rows]; e++)
@@ -837,9 +916,11 @@ int rsparse_hip_knn_recommend(const int32_t* x_p, const int32_t* x_j, int n_rows
   std::vector<int32_t> ex;
   add_excluded(exclude, n_exclude, n_items, ex);
   const size_t np1 = (size_t)n_rows + 1, nk = (size_t)n_rows * k;
-  DevBuf dXP, dXJ, dNb, dQ, dP, dJ, dE, dR, dS;
+  DevBuf dXP, dXJ, dXV, dNb, dQ, dP, dJ, dE, dR, dS;
   HIP_TRY(upload_host(dXP, x_p, np1));
   HIP_TRY(upload_host(dXJ, x_j, nnz));
+  const bool weighted = x_v && nnz;
+  if (weighted) HIP_TRY(upload_host(dXV, x_v, nnz));
   HIP_TRY(upload_host(dNb, nb.data(), nt));
   HIP_TRY(upload_host(dQ, qr.data(), nt));
   if (nr_p) {
@@ -849,9 +930,10 @@ int rsparse_hip_knn_recommend(const int32_t* x_p, const int32_t* x_j, int n_rows
   if (!ex.empty()) HIP_TRY(upload_host(dE, ex.data(), ex.size()));
   HIP_TRY(dR.alloc(nk * 4));
   HIP_TRY(dS.alloc(nk * 8));
-  rc = rsparse_hip_knn_recommend_device(dXP.as<int32_t>(), dXJ.as<int32_t>(), n_rows, n_items, dNb.as<int32_t>(), dQ.as<uint32_t>(), K,
-                                        opt<int32_t>(nr_p, dP), opt<int32_t>(nr_p, dJ), opt<int32_t>(!ex.empty(), dE), (int)ex.size(),
-                                        k, 0, dR.as<int32_t>(), dS.as<int64_t>(), nullptr);
+  rc = rsparse_hip_knn_recommend_weighted_device(dXP.as<int32_t>(), dXJ.as<int32_t>(), opt<uint32_t>(weighted, dXV), n_rows, n_items,
+                                                 dNb.as<int32_t>(), dQ.as<uint32_t>(), K, opt<int32_t>(nr_p, dP), opt<int32_t>(nr_p, dJ),
+                                                 opt<int32_t>(!ex.empty(), dE), (int)ex.size(), k, 0, dR.as<int32_t>(), dS.as<int64_t>(),
+                                                 nullptr);
   if (rc) return rc;
   HIP_TRY(hipDeviceSynchronize());
   if ((rc = fetch_col_major(dR, n_rows, k, res))) return rc;

@@ -410,12 +410,17 @@ hipError_t launch_softals_half(const int32_t* P, const int32_t* J, const T* X, c
                                bool res, bool has_t, T* out, double* sumsq, double* ws, hipStream_t s);
 
 // ItemKNN (wrmf_itemknn.hip; defined in rsparse_wrmf_hip.h).  `rows` dense rows of n_items cells per batch in ws (uint32 cells
-// for the neighbours, uint64 for the lists), which is all zeros on entry and again when the enqueued work is done.  h_ip: the
-// host copy of ip[item0 .. item1]; h_xp: of xp[0 .. n_rows].  1 <= K <= 256, 1 <= k <= 1024.
+// for the binary neighbours, uint64 for the weighted ones and for the lists), which is all zeros on entry and again when the
+// enqueued work is done.  h_ip: the host copy of ip[item0 .. item1]; h_xp: of xp[0 .. n_rows].  1 <= K <= 256, 1 <= k <= 1024.
+// il / ur: the weighted operands by stored position of either orientation; xv: the rows' weights, or null (all ones).
 hipError_t launch_cooc_neighbors(const int32_t* ip, const int32_t* iu, const int32_t* up, const int32_t* uj, int n_users,
                                  int n_items, int item0, int item1, const int32_t* h_ip, int sim, int K, int64_t rows,
                                  unsigned* ws, int32_t* neighbors, int32_t* counts, hipStream_t s);
-hipError_t launch_knn_recommend(const int32_t* xp, const int32_t* xj, int n_rows, int n_items, const int32_t* h_xp,
+hipError_t launch_cooc_neighbors_weighted(const int32_t* ip, const int32_t* iu, const uint32_t* il, const int32_t* up, const int32_t* uj,
+                                          const uint32_t* ur, int n_users, int n_items, int item0, int item1, const int32_t* h_ip,
+                                          const double* a, const double* b, double h, int K, int64_t rows, unsigned long long* ws,
+                                          int32_t* neighbors, unsigned long long* sums, hipStream_t s);
+hipError_t launch_knn_recommend(const int32_t* xp, const int32_t* xj, const uint32_t* xv, int n_rows, int n_items, const int32_t* h_xp,
                                 const int32_t* neighbors, const uint32_t* q, int K, const int32_t* nr_p, const int32_t* nr_j,
                                 const int32_t* excl, int n_excl, int k, int64_t rows, unsigned long long* ws, int32_t* items,
                                 long long* scores, hipStream_t s);

@@ -1,8 +1,9 @@
-// ItemKNN (rsparse_amd/itemknn.py is the definition): the co-occurrence neighbour table of a binary users x items matrix and
-// the top-k lists of users scored by it.  gfx950, wave64.  Both are ONE operation: an integer product of two sparse operands
-// accumulated into a batch of DENSE rows of a workspace, then an exact select per row.  Everything the device computes is an
-// integer or one IEEE division of two exact doubles, so the result equals the numpy definition bit for bit and the atomics
-// below (integer, vector, on global memory; no floating-point atomic anywhere) leave the same bits whatever their order.
+// ItemKNN (rsparse_amd/itemknn.py is the definition): the co-occurrence neighbour table of a binary users x items matrix, the
+// same table on integer-weighted values (c_ij = sum_u l_ui r_uj), and the top-k lists of users scored by either.  gfx950,
+// wave64.  All are ONE operation: an integer product of two sparse operands accumulated into a batch of DENSE rows of a
+// workspace, then an exact select per row.  Everything the device computes is an integer, one IEEE division of two exact doubles
+// or (weighted fit) the stated product, sum and division in double, so the result equals the numpy definition bit for bit and
+// the atomics below (integer, vector, on global memory; no floating-point atomic anywhere) leave the same bits whatever their order.
 //
 // Launch 1, knn_scatter_kernel: parallel over the STORED ENTRIES of the outer operand for a batch of its rows [row0, row1):
 //   * wave `v` of the launch owns the span of RSPARSE_HIP_KNN_SPAN consecutive entries [t0 + v span, ...), whatever the row
@@ -10,14 +11,18 @@
 //     wrmf_csr_rows.h, a lane group the rows of its own entries by stepping on from there;
 //   * a lane group of 16 takes an outer entry and walks the INNER list of its column, one atomicAdd per inner element into
 //     dense[(row - row0) ld + j].
-//     fit:     outer = item -> its users, inner = the CSR row of the user, addend 1, rows of uint32 (the diagonal is left out);
-//     predict: outer = the CSR row of the user, inner = the (neighbors, q) row of the item (-1 slots skipped), rows of uint64.
+//     fit:          outer = item -> its users, inner = the CSR row of the user, addend 1, rows of uint32 (the diagonal is left out);
+//     weighted fit: the same walk; the outer entry brings its l, the addend is (u64)l * r[e], rows of uint64;
+//     predict:      outer = the CSR row of the user, inner = the (neighbors, q) row of the item (-1 slots skipped), rows of
+//                   uint64; with a value array the addend is (u64)xq * q.
 //   An index outside its range is skipped (the host-array forms refuse it before the upload).
 // Launch 2 (predict), knn_mask_kernel: the cells of the row's not_recommend entries and of items_exclude get the all-ones
 //   sentinel, which no sum reaches (a score is below 2^61).
 // Launch 3, knn_select_kernel: one workgroup per dense row.
 //   * the key of a cell: fit, the bits of the double c / 1, c^2 / (n_i n_j) or c / (n_i + n_j - c) (positive, so they order
-//     as integers), 0 for an empty cell; predict, the score itself, 0 for a masked cell and for a score of 0;
+//     as integers), 0 for an empty cell; weighted fit, the bits of double(c) / (a_i b_j + h): three roundings, the product, the
+//     sum, the division (c < 2^53 converts exactly; a, b in [2^-200, 2^200] and h in [0, 2^400] keep the key a positive normal
+//     double); predict, the score itself, 0 for a masked cell and for a score of 0;
 //   * the cells with a key are compacted into an LDS buffer of RSPARSE_HIP_KNN_LDS_CAND candidates (fit rows are mostly
 //     zeros) and sorted there by (key descending, index ascending) with a bitonic network;
 //   * more candidates than the buffer holds: a radix select over the dense row, most significant byte first, narrows down the
@@ -37,6 +42,9 @@
 #include "wrmf_internal.h"
 #include "wrmf_wave.h"
 
+// the weighted key is the definition's three roundings, double(c) / (a_i * b_j + h): no contraction into a fused multiply-add
+#pragma clang fp contract(off)
+
 namespace rsparse_hip {
 namespace {
 
@@ -48,16 +56,20 @@ constexpr int kGroup = 16, kGroups = 64 / kGroup;   // lanes that walk one inner
 constexpr int kSpan = RSPARSE_HIP_KNN_SPAN;
 constexpr int kCand = RSPARSE_HIP_KNN_LDS_CAND;
 constexpr u64 kMasked = ~0ull;
+// the forms of the two kernels: the lists, the binary fit, the weighted fit, the lists of weighted rows (scatter only)
+enum : int { kLists = 0, kFit = 1, kFitW = 2, kListsW = 3 };
 static_assert(kSpan % kGroups == 0, "a wave's span is shared out evenly between its lane groups");
 static_assert((kCand & (kCand - 1)) == 0 && kCand >= RSPARSE_HIP_KNN_MAX_TOPK && kCand >= RSPARSE_HIP_KNN_MAX_NEIGHBORS,
               "the candidate buffer is a power of two (bitonic sort) and holds the k entries of the fallback");
 
-template <bool FIT>
+// OV: the outer entries' values (kFitW: l, kListsW: xq); Q: the inner elements' (kFitW: r by stored position, lists: q by slot)
+template <int MODE>
 __global__ __launch_bounds__(kThreads) void knn_scatter_kernel(const int32_t* __restrict__ OP, const int32_t* __restrict__ OJ,
                                                                int n_outer, int row0, int n_batch, unsigned t0, unsigned t1,
                                                                const int32_t* __restrict__ IP, const int32_t* __restrict__ IJ,
                                                                const uint32_t* __restrict__ Q, int K, int n_inner, int n_items,
-                                                               size_t ld, void* __restrict__ dense) {
+                                                               size_t ld, void* __restrict__ dense,
+                                                               const uint32_t* __restrict__ OV) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const long long b0l = (long long)t0 + ((long long)blockIdx.x * kWaves + w) * kSpan;
   if (b0l >= (long long)t1) return;   // (whole waves; nothing below synchronises across waves)
@@ -70,18 +82,28 @@ __global__ __launch_bounds__(kThreads) void knn_scatter_kernel(const int32_t* __
     // (a row outside the batch: only row pointers that decrease somewhere else in the array can lead the search there)
     if ((unsigned)c >= (unsigned)n_inner || (unsigned)(row - row0) >= (unsigned)n_batch) continue;
     const size_t base = (size_t)(row - row0) * ld;
-    if constexpr (FIT) {
+    if constexpr (MODE == kFit) {
       unsigned* d = static_cast<unsigned*>(dense) + base;
       const int e1 = IP[c + 1];
       for (int e = IP[c] + l; e < e1; e += kGroup) {
         const int j = IJ[e];
         if ((unsigned)j < (unsigned)n_items && j != row) atomicAdd(d + j, 1u);
       }
+    } else if constexpr (MODE == kFitW) {
+      u64* d = static_cast<u64*>(dense) + base;
+      const u64 lv = OV[t];
+      const int e1 = IP[c + 1];
+      for (int e = IP[c] + l; e < e1; e += kGroup) {
+        const int j = IJ[e];
+        if ((unsigned)j < (unsigned)n_items && j != row) atomicAdd(d + j, lv * Q[e]);
+      }
     } else {
       u64* d = static_cast<u64*>(dense) + base;
+      u64 xv = 1;
+      if constexpr (MODE == kListsW) xv = OV[t];
       for (int s = l; s < K; s += kGroup) {
         const int j = IJ[(size_t)c * K + s];
-        if ((unsigned)j < (unsigned)n_items) atomicAdd(d + j, (u64)Q[(size_t)c * K + s]);
+        if ((unsigned)j < (unsigned)n_items) atomicAdd(d + j, xv * Q[(size_t)c * K + s]);
       }
     }
   }
@@ -126,11 +148,14 @@ __device__ __forceinline__ int block_rank(bool flag, int* s_w, int& total) {
   return off + __popcll(b & ((1ull << lane) - 1));
 }
 
-template <bool FIT>
+// out_scores: the lists' scores, or the weighted fit's sums (as uint64 bits); A, B, h: the weighted key's tables
+template <int MODE>
 __global__ __launch_bounds__(kThreads) void knn_select_kernel(const void* __restrict__ dense, size_t ld, int n, int row0,
                                                               const int32_t* __restrict__ IP, int sim, int k,
                                                               int32_t* __restrict__ out_items, int32_t* __restrict__ out_counts,
-                                                              long long* __restrict__ out_scores) {
+                                                              long long* __restrict__ out_scores, const double* __restrict__ A,
+                                                              const double* __restrict__ B, double h) {
+  constexpr bool FIT = MODE != kLists;
   __shared__ u64 s_key[kCand];
   __shared__ int s_idx[kCand];
   __shared__ int s_hist[256];
@@ -140,9 +165,15 @@ __global__ __launch_bounds__(kThreads) void knn_select_kernel(const void* __rest
   const int i = row0 + (int)blockIdx.x;   // fit: the item whose neighbours these are
   const unsigned* row32 = static_cast<const unsigned*>(dense) + (size_t)blockIdx.x * ld;
   const u64* row64 = static_cast<const u64*>(dense) + (size_t)blockIdx.x * ld;
-  const long long ni = FIT ? (long long)IP[i + 1] - IP[i] : 0;
+  const long long ni = MODE == kFit ? (long long)IP[i + 1] - IP[i] : 0;
+  const double ai = MODE == kFitW ? A[i] : 0.0;   // (read once per workgroup)
   auto cell_key = [&](int j) -> u64 {
-    if constexpr (FIT) {
+    if constexpr (MODE == kFitW) {
+      const u64 c = row64[j];
+      if (c == 0 || j == i) return 0;
+      const double den = ai * B[j] + h;
+      return (u64)__double_as_longlong((double)c / den);
+    } else if constexpr (FIT) {
       const unsigned c = row32[j];
       if (c == 0 || j == i) return 0;
       const long long nj = (long long)IP[j + 1] - IP[j];
@@ -277,7 +308,10 @@ __global__ __launch_bounds__(kThreads) void knn_select_kernel(const void* __rest
   const size_t o = (size_t)blockIdx.x * k;
   for (int t = tid; t < have; t += kThreads) {
     const int j = s_idx[t];
-    if constexpr (FIT) {
+    if constexpr (MODE == kFitW) {
+      out_items[o + t] = j;
+      out_scores[o + t] = (long long)row64[j];
+    } else if constexpr (FIT) {
       out_items[o + t] = j;
       out_counts[o + t] = (int32_t)row32[j];
     } else {
@@ -288,7 +322,8 @@ __global__ __launch_bounds__(kThreads) void knn_select_kernel(const void* __rest
   if constexpr (FIT) {
     for (int t = have + tid; t < k; t += kThreads) {
       out_items[o + t] = -1;
-      out_counts[o + t] = 0;
+      if constexpr (MODE == kFitW) out_scores[o + t] = 0;
+      else out_counts[o + t] = 0;
     }
   } else {
     // the unmasked cells of score 0, ascending, behind the scored ones
@@ -327,10 +362,10 @@ hipError_t launch_cooc_neighbors(const int32_t* ip, const int32_t* iu, const int
     const int r1 = (int)std::min<int64_t>(r0 + rows, item1);
     const unsigned t0 = (unsigned)h_ip[r0 - item0], t1 = (unsigned)h_ip[r1 - item0];
     if (t1 > t0)
-      hipLaunchKernelGGL(knn_scatter_kernel<true>, dim3(scatter_grid(t0, t1)), dim3(kThreads), 0, s, ip, iu, n_items, (int)r0, (int)(r1 - r0),
-                         t0, t1, up, uj, nullptr, 0, n_users, n_items, ld, ws);
-    hipLaunchKernelGGL(knn_select_kernel<true>, dim3((unsigned)(r1 - r0)), dim3(kThreads), 0, s, ws, ld, n_items, (int)r0, ip, sim, K,
-                       neighbors + (size_t)(r0 - item0) * K, counts + (size_t)(r0 - item0) * K, nullptr);
+      hipLaunchKernelGGL(knn_scatter_kernel<kFit>, dim3(scatter_grid(t0, t1)), dim3(kThreads), 0, s, ip, iu, n_items, (int)r0,
+                         (int)(r1 - r0), t0, t1, up, uj, nullptr, 0, n_users, n_items, ld, ws, nullptr);
+    hipLaunchKernelGGL(knn_select_kernel<kFit>, dim3((unsigned)(r1 - r0)), dim3(kThreads), 0, s, ws, ld, n_items, (int)r0, ip, sim, K,
+                       neighbors + (size_t)(r0 - item0) * K, counts + (size_t)(r0 - item0) * K, nullptr, nullptr, nullptr, 0.0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (t1 > t0 && (e = hipMemsetAsync(ws, 0, (size_t)(r1 - r0) * ld * sizeof(unsigned), s)) != hipSuccess) return e;
@@ -338,7 +373,27 @@ hipError_t launch_cooc_neighbors(const int32_t* ip, const int32_t* iu, const int
   return hipSuccess;
 }
 
-hipError_t launch_knn_recommend(const int32_t* xp, const int32_t* xj, int n_rows, int n_items, const int32_t* h_xp,
+hipError_t launch_cooc_neighbors_weighted(const int32_t* ip, const int32_t* iu, const uint32_t* il, const int32_t* up, const int32_t* uj,
+                                          const uint32_t* ur, int n_users, int n_items, int item0, int item1, const int32_t* h_ip,
+                                          const double* a, const double* b, double h, int K, int64_t rows, unsigned long long* ws,
+                                          int32_t* neighbors, unsigned long long* sums, hipStream_t s) {
+  const size_t ld = (size_t)n_items;
+  for (int64_t r0 = item0; r0 < item1; r0 += rows) {
+    const int r1 = (int)std::min<int64_t>(r0 + rows, item1);
+    const unsigned t0 = (unsigned)h_ip[r0 - item0], t1 = (unsigned)h_ip[r1 - item0];
+    if (t1 > t0)
+      hipLaunchKernelGGL(knn_scatter_kernel<kFitW>, dim3(scatter_grid(t0, t1)), dim3(kThreads), 0, s, ip, iu, n_items, (int)r0,
+                         (int)(r1 - r0), t0, t1, up, uj, ur, 0, n_users, n_items, ld, ws, il);
+    hipLaunchKernelGGL(knn_select_kernel<kFitW>, dim3((unsigned)(r1 - r0)), dim3(kThreads), 0, s, ws, ld, n_items, (int)r0, nullptr, 0, K,
+                       neighbors + (size_t)(r0 - item0) * K, nullptr, reinterpret_cast<long long*>(sums) + (size_t)(r0 - item0) * K, a, b, h);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (t1 > t0 && (e = hipMemsetAsync(ws, 0, (size_t)(r1 - r0) * ld * sizeof(unsigned long long), s)) != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_knn_recommend(const int32_t* xp, const int32_t* xj, const uint32_t* xv, int n_rows, int n_items, const int32_t* h_xp,
                                 const int32_t* neighbors, const uint32_t* q, int K, const int32_t* nr_p, const int32_t* nr_j,
                                 const int32_t* excl, int n_excl, int k, int64_t rows, unsigned long long* ws, int32_t* items,
                                 long long* scores, hipStream_t s) {
@@ -347,14 +402,17 @@ hipError_t launch_knn_recommend(const int32_t* xp, const int32_t* xj, int n_rows
     const int r1 = (int)std::min<int64_t>(r0 + rows, n_rows);
     const unsigned t0 = (unsigned)h_xp[r0], t1 = (unsigned)h_xp[r1];
     const bool mask = nr_p || n_excl > 0;
-    if (t1 > t0)
-      hipLaunchKernelGGL(knn_scatter_kernel<false>, dim3(scatter_grid(t0, t1)), dim3(kThreads), 0, s, xp, xj, n_rows, (int)r0, (int)(r1 - r0),
-                         t0, t1, nullptr, neighbors, q, K, n_items, n_items, ld, ws);
+    if (t1 > t0 && xv)
+      hipLaunchKernelGGL(knn_scatter_kernel<kListsW>, dim3(scatter_grid(t0, t1)), dim3(kThreads), 0, s, xp, xj, n_rows, (int)r0,
+                         (int)(r1 - r0), t0, t1, nullptr, neighbors, q, K, n_items, n_items, ld, ws, xv);
+    else if (t1 > t0)
+      hipLaunchKernelGGL(knn_scatter_kernel<kLists>, dim3(scatter_grid(t0, t1)), dim3(kThreads), 0, s, xp, xj, n_rows, (int)r0,
+                         (int)(r1 - r0), t0, t1, nullptr, neighbors, q, K, n_items, n_items, ld, ws, nullptr);
     if (mask)
       hipLaunchKernelGGL(knn_mask_kernel, dim3((unsigned)(r1 - r0)), dim3(kThreads), 0, s, ws, ld, n_items, nr_p ? nr_p + r0 : nullptr,
                          nr_j, excl, n_excl);
-    hipLaunchKernelGGL(knn_select_kernel<false>, dim3((unsigned)(r1 - r0)), dim3(kThreads), 0, s, ws, ld, n_items, (int)r0, nullptr, 0, k,
-                       items + (size_t)r0 * k, nullptr, scores + (size_t)r0 * k);
+    hipLaunchKernelGGL(knn_select_kernel<kLists>, dim3((unsigned)(r1 - r0)), dim3(kThreads), 0, s, ws, ld, n_items, (int)r0, nullptr, 0, k,
+                       items + (size_t)r0 * k, nullptr, scores + (size_t)r0 * k, nullptr, nullptr, 0.0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if ((t1 > t0 || mask) && (e = hipMemsetAsync(ws, 0, (size_t)(r1 - r0) * ld * sizeof(unsigned long long), s)) != hipSuccess)

@@ -818,12 +818,34 @@ class HipBackend:
                                                               some(nb), some(ct), self._stream()))
         return nb, ct
 
-    def knn_recommend(self, xp, xj, neighbors, q, k, nr_p=None, nr_j=None, exclude0=None, ws_rows=0):
+    def cooc_neighbors_weighted(self, ip, iu, il, up, uj, ur, n_users, n_items, a, b, h, K, item0=0, item1=None, ws_rows=0):
+        """the weighted ItemKNN neighbour table of the items [item0, item1) (wrmf_itemknn.hip;
+        rsparse_amd.itemknn.weighted_cooccurrence_reference is the definition): c_ij = sum_u l_ui r_uj, ordered by double(c_ij) /
+        (a_i b_j + h).  ip / iu / il: the item-major orientation with l by stored position, up / uj / ur: the CSR rows with r;
+        the operands are integers below 2^32 held as int64, int32 or float64 here and handed on as uint32; a, b: n_items float64
+        on the device, h a float.  The ranges of a, b and the 2^53 bound are the caller's to keep.  -> (neighbors (item1 - item0,
+        K) int32, sums the same shape int64 holding the uint64 c_ij) on the device."""
+        item1 = int(n_items) if item1 is None else int(item1)
+        n = max(item1 - int(item0), 0)
+        assert all(t.dtype == torch.int32 for t in (ip, iu, up, uj)) and a.dtype == b.dtype == torch.float64
+        assert il.numel() == iu.numel() and ur.numel() == uj.numel() and a.numel() == b.numel() == int(n_items)
+        u32 = lambda t: t.to(torch.int64).to(torch.int32).contiguous()   # (the low 32 bits: the same bits as uint32)
+        il32, ur32, a, b = u32(il), u32(ur), a.contiguous(), b.contiguous()
+        nb = torch.empty((n, int(K)), dtype=torch.int32, device=self.device)
+        sums = torch.empty((n, int(K)), dtype=torch.int64, device=self.device)
+        some = lambda t: t.data_ptr() if t.numel() else ip.data_ptr()   # (an empty tensor has no address to pass)
+        _lib.check(self.lib.rsparse_hip_cooc_neighbors_weighted_device(
+            ip.data_ptr(), some(iu), some(il32), up.data_ptr(), some(uj), some(ur32), int(n_users), int(n_items), int(item0), item1,
+            some(a), some(b), float(h), int(K), int(ws_rows), some(nb), some(sums), self._stream()))
+        return nb, sums
+
+    def knn_recommend(self, xp, xj, neighbors, q, k, nr_p=None, nr_j=None, exclude0=None, ws_rows=0, xv=None):
         """the ItemKNN lists of the rows of a CSR pattern (xp, xj: int32 on the device) under the tables neighbors (n_items x K
         int32, 0-based, -1 = empty slot) and q (n_items x K integer weights <= 2^30, held as int64 or int32 here and handed on as
         uint32): wrmf_itemknn.hip, rsparse_amd.itemknn.knn_recommend_reference is the definition.  nr_p / nr_j: the rows'
-        not_recommend entries as CSR slots (or None), exclude0: 0-based item ids (or None).  -> (items (n, k) int32, 1-based with
-        NA_integer_; scores (n, k) int64, 0 where NA) on the device."""
+        not_recommend entries as CSR slots (or None), exclude0: 0-based item ids (or None).  xv: the rows' integer weights, one
+        per stored position (<= 2^16 - 1, a row's sum below 2^31; None = all ones): a neighbour's addend is xv * q.
+        -> (items (n, k) int32, 1-based with NA_integer_; scores (n, k) int64, 0 where NA) on the device."""
         assert xp.dtype == torch.int32 and xj.dtype == torch.int32 and neighbors.dtype == torch.int32 and neighbors.shape == q.shape
         n, (n_items, K) = int(xp.numel()) - 1, neighbors.shape
         neighbors = neighbors.contiguous()
@@ -831,8 +853,11 @@ class HipBackend:
         res = torch.empty((n, int(k)), dtype=torch.int32, device=self.device)
         sc = torch.empty((n, int(k)), dtype=torch.int64, device=self.device)
         some = lambda t: t.data_ptr() if t.numel() else xp.data_ptr()
-        _lib.check(self.lib.rsparse_hip_knn_recommend_device(
-            xp.data_ptr(), some(xj), n, int(n_items), some(neighbors), some(q32), int(K), None if nr_p is None else nr_p.data_ptr(),
+        if xv is not None:
+            assert xv.numel() == xj.numel()
+            xv = xv.to(torch.int64).to(torch.int32).contiguous()
+        _lib.check(self.lib.rsparse_hip_knn_recommend_weighted_device(
+            xp.data_ptr(), some(xj), None if xv is None or not xv.numel() else xv.data_ptr(), n, int(n_items), some(neighbors), some(q32), int(K), None if nr_p is None else nr_p.data_ptr(),
             None if nr_p is None else some(nr_j), None if exclude0 is None or not exclude0.numel() else exclude0.data_ptr(),
             0 if exclude0 is None else int(exclude0.numel()), int(k), int(ws_rows), some(res), some(sc), self._stream()))
         return res, sc

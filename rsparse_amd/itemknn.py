@@ -23,10 +23,53 @@ those neither in the row's not_recommend entries nor in items_exclude, ties to t
 too, so a list is shorter than k only when fewer than k items are admissible, and is then padded as `WRMF.predict` pads: -1 in
 the result, NaN in `.scores`.  `.scores` is score / 2^30 (the raw sum for "count") as float64.
 
-  cooccurrence_reference    the fit, per item, in numpy integers
-  knn_recommend_reference   the lists, per row
-  ItemKNN                   the model: fit / similar_items / predict / evaluate
+Weighted values (`similarity` "dot", "asymmetric", "rp3beta", and "cosine" with a `weighting`).  On the same canonical pattern
+an entry (u, i) carries two unsigned integers: l_ui, used when i is the item whose neighbours are sought, and r_ui, used when i is
+the neighbour.  Both are uint32 with max(l) max(r) max_j n_j < 2^53, so that
+
+    c_ij = sum_u l_ui r_uj        (j != i; uint64, below 2^53: double(c_ij) is exact)
+    key_ij = double(c_ij) / (a_i b_j + h)
+
+with a, b tables of n_items doubles and h one double, all made on the host.  The key takes exactly three roundings, in double:
+the product, the sum, the division; nothing is contracted into a fused multiply-add.  The neighbours of i are the K items j != i
+with c_ij > 0 of largest key, ties to the smaller j: `neighbors` as above, `sums` (n_items, K) uint64 = c_ij, 0 in the padding.
+The device returns integers only; the reported similarity of a slot is its key, recomputed here from `sums` and the tables.
+Preconditions, checked here: a, b finite and in [2^-200, 2^200], h finite and in [0, 2^400]; every key of a non-empty cell is then
+a positive normal double and 0 stays the mark of an empty cell.
+
+Quantisation.  quantize_values(w, bits) for float64 weights w >= 0, finite (else ValueError): scale = (2^bits - 1) / max(w),
+q = rint(w scale) in double, clipped to [1 if w > 0 else 0, 2^bits - 1].  An operand whose stored weights are all equal is
+quantised to 1 with scale = 1 / value.  bits = min(the `bits` asked for (default 16, at most 24), floor((53 - ceil(log2(max_j
+n_j))) / 2)); if the 2^53 bound still fails: ValueError.
+
+The recipes are host rules for (l, r, a, b, h).  W is the weighted matrix in float64 (`weighting` None: the pattern of ones;
+"values": the stored values; a `Confidence`: fitted on x at fit, applied by its own transform to new users at predict),
+S_i = sum_u q_ui^2 an exact integer, s_l and s_r the two quantisation scales:
+
+    similarity             l          r                            a_i                     b_j              h
+    "dot"                  q(W)       q(W)                         s_l                     s_r              0
+    "cosine" (weighting)   q(W)       q(W)                         sqrt(S_i)               sqrt(S_j)        shrinkage s_l s_r
+    "asymmetric"           q(W)       q(W)                         S_i^alpha               S_j^(1 - alpha)  shrinkage s_l s_r
+    "rp3beta"              q(W^alpha) q((w_uj / d_u)^alpha),       s_l (sum_u w_ui)^alpha  s_r n_j^beta     0
+                                      d_u = sum_j w_uj
+
+(beta = 0 is P3alpha.  A table entry that would be 0 -- an item without a positive weight -- is stored as 1: such an item has no
+non-empty cell in its row and is in none of another's.)  ItemKNN(similarity in ("cosine", "jaccard", "count"), weighting=None) is
+the binary path above, unchanged.
+
+Weighted lists.  q[i, s] = rint(sim (2^30 / max(sim))) clipped to [0, 2^30]; xq holds the row's weights (W, W^alpha for
+"rp3beta") quantised with the FIT's scale of l and clipped to 2^16 - 1, so that a list depends neither on the batch nor on the
+other rows of the call; xq = 1 where the model has no weighting.  score_u[j] = sum of xq_ui q[i, s] over the items i of the row
+and the slots with neighbors[i, s] == j.  A row whose xq sum to 2^31 or more is refused (`UnsupportedOnDevice`): a score stays
+below 2^61.  Selection, ties, zero scores, padding and the filters are as above; `.scores` is score / (s_l 2^30 / max(sim)).
+
+  cooccurrence_reference            the fit, per item, in numpy integers
+  quantize_values, weighted_operands, weighted_cooccurrence_reference      the weighted fit
+  knn_recommend_reference           the lists, per row
+  ItemKNN                           the model: fit / similar_items / predict / evaluate
 """
+import types
+
 import numpy as np
 import scipy.sparse as sp
 import torch
@@ -35,7 +78,11 @@ from . import _lib
 from .wrmf import WRMF, TopItems
 
 SIMILARITIES = {"count": _lib.KNN_COUNT, "cosine": _lib.KNN_COSINE, "jaccard": _lib.KNN_JACCARD}
+WEIGHTED = ("dot", "cosine", "asymmetric", "rp3beta")   # the kinds on weighted values ("cosine": with a weighting)
 Q_ONE = 1 << 30   # the fixed point of the weights
+MAX_BITS = 24     # of a quantised operand
+XQ_MAX = (1 << 16) - 1   # of a row's weight at predict
+TABLE_MIN, TABLE_MAX, H_MAX = 2.0 ** -200, 2.0 ** 200, 2.0 ** 400
 
 
 def canonical_pattern(x, n_items=None):
@@ -133,9 +180,177 @@ def weight_table(neighbors, counts, item_count, similarity):
     return np.where(np.isnan(sim), 0, np.rint(np.nan_to_num(sim) * Q_ONE)).astype(np.int64)
 
 
-def knn_recommend_reference(x, neighbors, q, k, not_recommend=None, items_exclude=()):
+def _check_bits(bits):
+    if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or not 1 <= bits <= MAX_BITS:
+        raise ValueError("bits must be an integer in 1 .. %d" % MAX_BITS)
+    return int(bits)
+
+
+def quantize_values(w, bits=16, scale=None, top=None):
+    """-> (q int64, scale float): the integers of the float64 weights w >= 0 by the module's rule.  scale: use this one (the
+    fit's, at predict) instead of deriving it from w; top: the upper clip (default 2^bits - 1)."""
+    w = np.asarray(w, dtype=np.float64)
+    if w.size and not (np.isfinite(w).all() and w.min() >= 0):
+        raise ValueError("the weights must be finite and non-negative")
+    top = (1 << _check_bits(bits)) - 1 if top is None else int(top)
+    if scale is None:
+        w_max = np.float64(w.max()) if w.size else np.float64(0)
+        if w_max == 0:
+            return np.zeros(w.shape, dtype=np.int64), 1.0
+        if w.min() == w_max:
+            return np.ones(w.shape, dtype=np.int64), float(np.float64(1) / w_max)
+        scale = np.float64(top) / w_max
+        if not np.isfinite(scale):
+            raise ValueError("the largest weight is too small to scale")
+    q = np.rint(w * np.float64(scale))
+    q = np.minimum(np.maximum(q, np.where(w > 0, 1.0, 0.0)), np.float64(top))
+    return q.astype(np.int64), float(scale)
+
+
+def operand_bits(bits, max_n):
+    """min(bits, floor((53 - ceil(log2(max_n))) / 2)): two operands of that width over max_n users keep a sum below 2^53"""
+    max_n = int(max_n)
+    return min(_check_bits(bits), (53 - (max_n - 1).bit_length() if max_n > 1 else 53) // 2)
+
+
+def check_exact_bound(l, r, max_n):
+    """max(l) max(r) max_j n_j < 2^53, in Python integers, or ValueError"""
+    top = (int(np.max(l)) if np.size(l) else 0) * (int(np.max(r)) if np.size(r) else 0) * int(max_n)
+    if top >= 1 << 53:
+        raise ValueError("max(l) max(r) max_j n_j = %d >= 2^53: a sum would not be exact in double" % top)
+
+
+def check_tables(a, b, h):
+    a, b, h = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), float(h)
+    for t in (a, b):
+        if t.size and not (np.isfinite(t).all() and t.min() >= TABLE_MIN and t.max() <= TABLE_MAX):
+            raise ValueError("the tables a, b must be finite and in [2^-200, 2^200]")
+    if not (np.isfinite(h) and 0.0 <= h <= H_MAX):
+        raise ValueError("h must be finite and in [0, 2^400]")
+
+
+def _check_recipe(similarity, shrinkage, alpha, beta):
+    if similarity not in WEIGHTED:
+        raise ValueError("a weighted similarity must be one of 'dot', 'cosine', 'asymmetric', 'rp3beta'")
+    if alpha is None:
+        alpha = 1.0 if similarity == "rp3beta" else 0.5
+    shrinkage, alpha, beta = float(shrinkage), float(alpha), float(beta)
+    if not (np.isfinite(shrinkage) and shrinkage >= 0):
+        raise ValueError("shrinkage must be finite and >= 0")
+    if not (np.isfinite(alpha) and alpha >= 0) or (similarity == "asymmetric" and alpha > 1):
+        raise ValueError("alpha must be finite and >= 0 (asymmetric: in [0, 1])")
+    if not (np.isfinite(beta) and beta >= 0):
+        raise ValueError("beta must be finite and >= 0")
+    return shrinkage, alpha, beta
+
+
+def weighted_operands(w, similarity, shrinkage=0.0, alpha=None, beta=0.0, bits=16):
+    """the recipe of `similarity` on the weighted matrix w (a canonical CSR, float64; its stored entries are the pattern)
+    -> a namespace: l, r (int64, one per stored position of w), a, b (n_items float64), h, scale_l, scale_r, bits, item_count"""
+    shrinkage, alpha, beta = _check_recipe(similarity, shrinkage, alpha, beta)
+    n_items = w.shape[1]
+    j, v = w.indices, np.asarray(w.data, dtype=np.float64)
+    if v.size and not (np.isfinite(v).all() and v.min() >= 0):
+        raise ValueError("the weights must be finite and non-negative")
+    n = np.bincount(j, minlength=n_items).astype(np.int64)
+    max_n = int(n.max()) if n_items else 0
+    bits = operand_bits(bits, max_n)
+    if bits < 1:
+        raise ValueError("an item has too many users for a quantised operand")
+    one = lambda t: np.where(t > 0, t, 1.0)   # (an item without a positive weight: the entry is never used)
+    if similarity == "rp3beta":
+        rows = np.repeat(np.arange(w.shape[0]), np.diff(w.indptr))
+        d = np.bincount(rows, weights=v, minlength=w.shape[0])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            share = np.where(d[rows] > 0, v / d[rows], 0.0)
+        l, s_l = quantize_values(v ** alpha, bits)
+        r, s_r = quantize_values(share ** alpha, bits)
+        col = np.bincount(j, weights=v, minlength=n_items)
+        a = one(s_l * col ** alpha)
+        b = one(s_r * n.astype(np.float64) ** beta)
+        h = 0.0
+    else:
+        l, s_l = quantize_values(v, bits)
+        r, s_r = l, s_l
+        if similarity == "dot":
+            a, b, h = np.full(n_items, s_l), np.full(n_items, s_r), 0.0
+        else:
+            S = np.bincount(j, weights=(l * l).astype(np.float64), minlength=n_items)   # (integers below 2^53: exact)
+            if similarity == "cosine":
+                a = b = one(np.sqrt(S))
+            else:
+                a, b = one(S ** alpha), one(S ** (1.0 - alpha))
+            h = shrinkage * s_l * s_r
+    check_exact_bound(l, r, max_n)
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    check_tables(a, b, h)
+    return types.SimpleNamespace(l=l, r=r, a=a, b=b, h=float(h), scale_l=s_l, scale_r=s_r, bits=bits, item_count=n)
+
+
+def weighted_key(c, a_i, b_j, h):
+    """the order key of the weighted definition: double(c) / (a_i b_j + h), three roundings"""
+    return np.asarray(c).astype(np.float64) / (np.asarray(a_i, dtype=np.float64) * np.asarray(b_j, dtype=np.float64) + np.float64(h))
+
+
+def weighted_cooccurrence_reference(indptr, indices, l, r, n_items, a, b, h, K):
+    """-> (neighbors (n_items, K) int32, sums (n_items, K) uint64): the weighted fit of the definition on the canonical CSR
+    pattern (indptr, indices) with the operands l, r by stored position, one item at a time, on integers; no items x items array
+    is formed."""
+    K, n_items = int(K), int(n_items)
+    up, uj = np.asarray(indptr, dtype=np.int64), np.asarray(indices, dtype=np.int64)
+    l, r = np.asarray(l, dtype=np.int64), np.asarray(r, dtype=np.int64)
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    check_tables(a, b, h)
+    n = np.bincount(uj, minlength=n_items)
+    check_exact_bound(l, r, n.max() if n_items else 0)
+    rows = np.repeat(np.arange(up.size - 1), np.diff(up))
+    order = np.argsort(uj, kind="stable")          # the item-major orientation: users ascending within an item
+    ip = np.concatenate([[0], np.cumsum(n)])
+    iu, il = rows[order], l[order]
+    neighbors = np.full((n_items, K), -1, dtype=np.int32)
+    sums = np.zeros((n_items, K), dtype=np.uint64)
+    for i in range(n_items):
+        users, lv = iu[ip[i]:ip[i + 1]], il[ip[i]:ip[i + 1]]
+        if users.size == 0:
+            continue
+        seen = np.concatenate([uj[up[u]:up[u + 1]] for u in users])
+        add = np.concatenate([lu * r[up[u]:up[u + 1]] for u, lu in zip(users, lv)])
+        j, inv = np.unique(seen, return_inverse=True)
+        c = np.zeros(j.size, dtype=np.int64)
+        np.add.at(c, inv, add)
+        keep = (j != i) & (c > 0)
+        j, c = j[keep], c[keep]
+        key = weighted_key(c, a[i], b[j], h)
+        first = np.lexsort((j, -key))[:K]
+        neighbors[i, :first.size] = j[first]
+        sums[i, :first.size] = c[first].astype(np.uint64)
+    return neighbors, sums
+
+
+def weighted_similarity_values(neighbors, sums, a, b, h):
+    """the key of every slot (float64, NaN in the padding), recomputed from the sums and the tables"""
+    neighbors, a, b = np.asarray(neighbors), np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    pad = neighbors < 0
+    if not neighbors.size:
+        return np.zeros(neighbors.shape, dtype=np.float64)
+    key = weighted_key(np.where(pad, 0, np.asarray(sums)), a[:, None], np.where(pad, 1.0, b[np.where(pad, 0, neighbors)]), h)
+    return np.where(pad, np.nan, key)
+
+
+def weighted_weight_table(similarities):
+    """-> (q (n_items, K) int64 in 0 .. 2^30, 0 in the padding; the scale 2^30 / max(sim), 1.0 for an empty table)"""
+    sim = np.asarray(similarities, dtype=np.float64)
+    live = ~np.isnan(sim)
+    top = sim[live].max() if live.any() else 0.0
+    scale = np.float64(Q_ONE) / np.float64(top) if top > 0 else np.float64(1)
+    q = np.minimum(np.maximum(np.rint(np.where(live, sim, 0.0) * scale), 0.0), np.float64(Q_ONE))
+    return np.where(live, q, 0.0).astype(np.int64), float(scale)
+
+
+def knn_recommend_reference(x, neighbors, q, k, not_recommend=None, items_exclude=(), xv=None):
     """-> (items (n, k) int64, 0-based with -1 where fewer than k items are admissible; scores (n, k) int64, 0 there): the lists
-    of the definition, one row of x at a time.  not_recommend: a sparse matrix of x's shape, or None."""
+    of the definition, one row of x at a time.  not_recommend: a sparse matrix of x's shape, or None.  xv: the integer weight of
+    every stored entry of canonical_pattern(x), in its order (None: all ones); a neighbour's addend is xv q."""
     neighbors, q = np.asarray(neighbors, dtype=np.int64), np.asarray(q, dtype=np.int64)
     n_items = neighbors.shape[0]
     m = canonical_pattern(x, n_items)
@@ -148,9 +363,15 @@ def knn_recommend_reference(x, neighbors, q, k, not_recommend=None, items_exclud
     excl = np.asarray(list(items_exclude), dtype=np.int64)
     items = np.full((m.shape[0], k), -1, dtype=np.int64)
     scores = np.zeros((m.shape[0], k), dtype=np.int64)
+    if xv is not None:
+        xv = np.asarray(xv, dtype=np.int64)
+        if xv.shape != (m.nnz,):
+            raise ValueError("xv must hold one weight per stored entry of the canonical pattern of x")
     for u in range(m.shape[0]):
         own = m.indices[m.indptr[u]:m.indptr[u + 1]]
         nb, w = neighbors[own].ravel(), q[own].ravel()
+        if xv is not None:
+            w = (xv[m.indptr[u]:m.indptr[u + 1], None] * q[own]).ravel()
         score = np.zeros(n_items, dtype=np.int64)
         np.add.at(score, nb[nb >= 0], w[nb >= 0])
         adm = np.ones(n_items, dtype=bool)
@@ -167,15 +388,34 @@ def knn_recommend_reference(x, neighbors, q, k, not_recommend=None, items_exclud
 class ItemKNN:
     """Item-based k-nearest-neighbours on the co-occurrence of items (the module's docstring is the definition).
 
-    k_neighbors: K, 1 .. 256; similarity: "cosine", "jaccard" or "count"; device / backend: as `WRMF`.  A backend without
-    `cooc_neighbors` / `knn_recommend` (the CPU stand-in of the tests) runs the numpy definitions."""
+    k_neighbors: K, 1 .. 256; similarity: "cosine", "jaccard" or "count" on the pattern, "dot", "asymmetric", "rp3beta" -- and
+    "cosine" with a weighting -- on weighted values; weighting: None (the pattern of ones), "values" (the stored values) or a
+    `rsparse_amd.Confidence`, fitted on x at `fit` and applied to new users at `predict`; shrinkage: added to the denominator
+    of "cosine" / "asymmetric"; alpha: the exponent of "asymmetric" (default 0.5) and "rp3beta" (default 1); beta: the
+    popularity exponent of "rp3beta" (0 = P3alpha); bits: of a quantised operand (at most 24); device / backend: as `WRMF`.
+    A backend without `cooc_neighbors` / `cooc_neighbors_weighted` / `knn_recommend` (the CPU stand-in of the tests) runs the
+    numpy definitions.  Fitted: `neighbors`, `similarities`, `item_count`, and `counts` (pattern kinds) or `sums` (weighted)."""
 
-    def __init__(self, k_neighbors=50, similarity="cosine", device=None, backend=None):
+    def __init__(self, k_neighbors=50, similarity="cosine", weighting=None, shrinkage=0.0, alpha=None, beta=0.0, bits=16, device=None,
+                 backend=None):
         self._K = _check_neighbors(k_neighbors)
-        self._similarity = _check_similarity(similarity)
+        if similarity not in SIMILARITIES and similarity not in WEIGHTED:
+            raise ValueError("similarity must be one of 'cosine', 'jaccard', 'count', 'dot', 'asymmetric', 'rp3beta'")
+        from .confidence import Confidence
+        if not (weighting is None or isinstance(weighting, Confidence) or (isinstance(weighting, str) and weighting == "values")):
+            raise ValueError("weighting must be None, 'values' or a Confidence")
+        if weighting is not None and similarity in ("jaccard", "count"):
+            raise ValueError("similarity %r is defined on the pattern: it takes no weighting" % similarity)
+        self._similarity = similarity
+        self._weighted = similarity not in SIMILARITIES or weighting is not None
+        self._weighting = weighting
+        self._bits = _check_bits(bits)
+        self._recipe = _check_recipe(similarity, shrinkage, alpha, beta) if self._weighted else None
         self._device = device
         self._be = backend
-        self.neighbors = self.counts = self.similarities = self.item_count = None
+        self.neighbors = self.counts = self.sums = self.similarities = self.item_count = None
+        self._ops = None        # the weighted fit's tables and scales (weighted_operands, without l and r)
+        self._q = None          # the weighted fit's (q, its scale)
         self._d_tables = None   # (neighbors, q) on the device
 
     def _backend(self):
@@ -196,10 +436,12 @@ class ItemKNN:
 
     # ------------------------------------------------------------------------------------------
     def fit(self, x, ws_rows=0):
-        """the neighbour table of the users x items matrix x -> self (`neighbors`, `counts`, `similarities`, `item_count`)"""
+        """the neighbour table of the users x items matrix x -> self (`neighbors`, `counts` or `sums`, `similarities`, `item_count`)"""
         self._one_rank()
         m = canonical_pattern(x)
         n_users, n_items = m.shape
+        if self._weighted:
+            return self._fit_weighted(m, ws_rows)
         if n_users > _lib.KNN_MAX_USERS:
             raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "n_users > 2^26: c^2 and n_i n_j would not be exact in double")
         be = self._backend()
@@ -218,8 +460,64 @@ class ItemKNN:
         self.similarities = similarity_values(nb, ct, cnt, self._similarity)
         return self
 
+    def _weigh(self, m, be, fit):
+        """the weighted matrix W of the canonical pattern m (float64, m's pattern): the model's `weighting`, fitted on m or applied"""
+        wt = self._weighting
+        if wt is None:
+            w = m.copy()
+            w.data[:] = 1.0
+            return w
+        if isinstance(wt, str):
+            return m
+        w = wt.fit_transform(m, backend=be) if fit else wt.transform(m, backend=be)
+        if not (np.array_equal(w.indptr, m.indptr) and np.array_equal(w.indices, m.indices)):
+            raise RuntimeError("the weighting changed the pattern of the matrix")
+        return w
+
+    def _fit_weighted(self, m, ws_rows):
+        n_users, n_items = m.shape
+        be = self._backend()
+        self._d_tables = None
+        shrinkage, alpha, beta = self._recipe
+        w = self._weigh(m, be, True)
+        ops = weighted_operands(w, self._similarity, shrinkage, alpha, beta, self._bits)
+        if not hasattr(be, "cooc_neighbors_weighted"):
+            nb, sums = weighted_cooccurrence_reference(m.indptr, m.indices, ops.l, ops.r, n_items, ops.a, ops.b, ops.h, self._K)
+        else:
+            up, uj = be.to_device(m.indptr, torch.int32), be.to_device(m.indices, torch.int32)
+            # the CSR rows of x are the CSC columns of its transpose: transposed, item -> its users, l with its entry (float64
+            # carries the integers exactly)
+            ip, iu, il = be.transpose_csc(n_items, n_users, up, uj, be.to_device(ops.l, torch.float64))
+            d_nb, d_sums = be.cooc_neighbors_weighted(ip, iu, il, up, uj, be.to_device(ops.r, torch.int64), n_users, n_items,
+                                                      be.to_device(ops.a, torch.float64), be.to_device(ops.b, torch.float64), ops.h,
+                                                      self._K, ws_rows=ws_rows)
+            nb, sums = d_nb.cpu().numpy(), d_sums.cpu().numpy().view(np.uint64)
+        self.neighbors, self.sums, self.counts, self.item_count = nb, sums, None, ops.item_count
+        self.similarities = weighted_similarity_values(nb, sums, ops.a, ops.b, ops.h)
+        self._q = weighted_weight_table(self.similarities)
+        ops.l = ops.r = None
+        self._ops = ops
+        return self
+
     def _weights(self):
+        if self._weighted:
+            return self._q[0]
         return weight_table(self.neighbors, self.counts, self.item_count, self._similarity)
+
+    def _row_weights(self, m, be):
+        """xq of the definition for the canonical pattern m of new rows, or None (no weighting: all ones)"""
+        if not self._weighted or self._weighting is None:
+            return None
+        v = self._weigh(m, be, False).data
+        if self._similarity == "rp3beta":
+            if v.size and not (np.isfinite(v).all() and v.min() >= 0):
+                raise ValueError("the weights must be finite and non-negative")
+            v = v ** self._recipe[1]
+        xq, _ = quantize_values(v, scale=self._ops.scale_l, top=XQ_MAX)
+        rows = np.repeat(np.arange(m.shape[0]), np.diff(m.indptr))
+        if xq.size and np.bincount(rows, weights=xq).max() >= 1 << 31:   # (sums of integers below 2^53: exact in double)
+            raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "predict: the quantised weights of a row sum to 2^31 or more")
+        return xq
 
     def similar_items(self, items=None, k=10):
         """rows of the table: the k <= k_neighbors nearest items of `items` (default: every item) as `TopItems` (-1 where an item
@@ -259,8 +557,9 @@ class ItemKNN:
             if not_recommend.shape != m.shape:
                 raise ValueError("not_recommend must have the shape of x")
         be = self._backend()
+        xq = self._row_weights(m, be)
         if not hasattr(be, "knn_recommend"):
-            it, sc = knn_recommend_reference(m, self.neighbors, self._weights(), k, not_recommend, excl)
+            it, sc = knn_recommend_reference(m, self.neighbors, self._weights(), k, not_recommend, excl, xv=xq)
             res = np.where(it < 0, np.int64(-2147483648), it + 1).astype(np.int32)
             return m, torch.from_numpy(res), torch.from_numpy(sc)
         if self._d_tables is None:
@@ -269,20 +568,24 @@ class ItemKNN:
         if not_recommend is not None and not_recommend.nnz:
             nr_p, nr_j = be.to_device(not_recommend.indptr, torch.int32), be.to_device(not_recommend.indices, torch.int32)
         d_ex = be.to_device(excl, torch.int32) if excl.size else None
+        kw = {} if xq is None else {"xv": be.to_device(xq, torch.int64)}
         res, sc = be.knn_recommend(be.to_device(m.indptr, torch.int32), be.to_device(m.indices, torch.int32), self._d_tables[0],
-                                   self._d_tables[1], k, nr_p, nr_j, d_ex, ws_rows=ws_rows)
+                                   self._d_tables[1], k, nr_p, nr_j, d_ex, ws_rows=ws_rows, **kw)
         return m, res, sc
 
     def predict(self, x, k, not_recommend="x", items_exclude=(), ws_rows=0):
         """the k best items of every row of x, with the conventions of `WRMF.predict`: `not_recommend` (default: x itself; None =
         nothing) and `items_exclude` (0-based) are skipped; -> `TopItems` (n x k, 0-based, -1 where fewer than k items are
-        admissible) with `.scores` (float64: score / 2^30, the raw sum for "count"; NaN in the padding).  1 <= k <= 1024."""
+        admissible) with `.scores` (float64: score / 2^30, the raw sum for "count", score / (s_l 2^30 / max(sim)) for the weighted
+        kinds; NaN in the padding).  1 <= k <= 1024."""
         _, res, sc = self._lists(x, k, not_recommend, items_exclude, ws_rows)
         idx = res.cpu().numpy().astype(np.int64)
         pad = idx == -2147483648
         out = np.where(pad, -1, idx - 1).view(TopItems)
         s = sc.cpu().numpy().astype(np.float64)
-        if self._similarity != "count":
+        if self._weighted:
+            s = s / (np.float64(self._ops.scale_l) * np.float64(self._q[1]))
+        elif self._similarity != "count":
             s = s / np.float64(Q_ONE)
         out.scores = np.where(pad, np.nan, s)
         return out
