@@ -361,6 +361,16 @@ int rsparse_hip_top_product_f64_device(const float* d_U, const float* d_V, const
                                        const int32_t* d_exclude0, int n_exclude, double glob_mean, int32_t* d_res,
                                        double* d_scores, void* stream);
 
+/* Which kernels a call of rsparse_hip_top_product_device (rescore = 0) or rsparse_hip_top_product_f64_device (rescore = 1, `extra`
+ * as there; the stateless rsparse_hip_top_product is that call with extra = -1) of this shape launches: one text line per launch of a
+ * product kernel, in order, "family=per_wave|shared|pipe KP= UB= W= buffers=lds|global users= threads= lds= k= user0= n_users=
+ * grid=XxY slice_items= flagged= scratch_floats=" -- the padded rank, user blocks per wave, waves, where the candidate buffers live,
+ * users per workgroup, threads, LDS bytes, the k of this launch, its users, its grid (Y = item slices), and whether it is a re-run
+ * for flagged users (its workgroups return at once when nobody is flagged); scratch_floats: the workspace the call takes.  No
+ * device call: the launch plan is host arithmetic, like the launch configuration rsparse_hip_csc_info reports.  text_len too small
+ * -> ERR_INVALID; rank > 256 or k > 256 (the large-k path is not planned here) -> ERR_UNSUPPORTED. */
+int rsparse_hip_top_product_plan(int n_users, int n_items, int rank, int k, int extra, int rescore, char* text, int text_len);
+
 /* `$predict` WITHIN per-user candidate lists (two-stage serving, sampled-negative evaluation): what find_top_product returns when
  * every item that is not a stored position of the user's row of the candidate pattern is added to that user's not_recommend row.
  * d_cand_p (n_users + 1) / d_cand_j: the pattern as CSR slots, columns ascending and unique within a row; slots are absolute

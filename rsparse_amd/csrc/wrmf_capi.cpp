@@ -11,12 +11,14 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "wrmf_capi_common.h"
+#include "wrmf_topk_plan.h"
 
 using namespace rsparse_hip;
 
@@ -1107,7 +1109,7 @@ int rsparse_hip_top_product_device(const float* d_U, const float* d_V, int n_use
   }
   // (few users over many items: the items are split over the workgroups, the slices' lists land in this scratch)
   float* scratch = nullptr;
-  const size_t sfl = top_product_scratch_floats(n_users, n_items, rank, k);
+  const size_t sfl = top_product_plan(n_users, n_items, rank, k, k, false).scratch_floats;
   if (sfl > 0) {
     HIP_TRY(g_ws.pad_buf.ensure(sfl));
     scratch = g_ws.pad_buf;
@@ -1115,6 +1117,35 @@ int rsparse_hip_top_product_device(const float* d_U, const float* d_V, int n_use
   hipError_t e = launch_top_product(d_U, d_V, n_users, n_items, rank, k, d_nr_p, d_nr_p ? d_nr_j : nullptr, d_excl0,
                                     n_exclude, (float)glob_mean, d_res, d_scores, (hipStream_t)stream, scratch);
   if (e != hipSuccess) return hip_fail(e, "launch_top_product");
+  return RSPARSE_HIP_OK;
+}
+
+namespace {
+// candidates per user: k + extra (default: a quarter of k, at least 8), never more than the kernel's 256 or the items
+int top_product_kc(int k, int extra, int n_items) {
+  if (extra < 0) extra = std::max(8, k / 4);
+  return std::max(k, std::min(std::min(k + extra, RSPARSE_HIP_MAX_TOPK), std::max(n_items, 1)));
+}
+}  // namespace
+
+int rsparse_hip_top_product_plan(int n_users, int n_items, int rank, int k, int extra, int rescore, char* text, int text_len) {
+  if (!text || text_len < 1) return fail(RSPARSE_HIP_ERR_INVALID, "no text buffer");
+  if (n_users < 0 || n_items < 0 || rank <= 0 || k < 1) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions");
+  if (rank > RSPARSE_HIP_MAX_RANK || k > RSPARSE_HIP_MAX_TOPK)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "the plan describes the kernels for rank <= 256 and k <= 256");
+  const TopPlan plan = top_product_plan(n_users, n_items, rank, rescore ? top_product_kc(k, extra, n_items) : k, k, rescore != 0);
+  static const char* const family[] = {"per_wave", "shared", "pipe"};
+  std::string out;
+  char line[256];
+  for (const TopLaunch& l : plan.launches) {
+    snprintf(line, sizeof line, "family=%s KP=%d UB=%d W=%d buffers=%s users=%d threads=%d lds=%zu k=%d user0=%d n_users=%d grid=%dx%d "
+             "slice_items=%d flagged=%d scratch_floats=%zu\n", family[l.geo.family], l.geo.KP, l.geo.UB, l.geo.W,
+             l.geo.gbuf ? "global" : "lds", l.geo.users, l.geo.threads, l.geo.lds, l.topk, l.user0, l.n_users, l.grid_x, l.n_slices,
+             l.slice_items, (int)l.flagged, plan.scratch_floats);
+    out += line;
+  }
+  if (out.size() + 1 > (size_t)text_len) return fail(RSPARSE_HIP_ERR_INVALID, "the text buffer is too small for the plan");
+  memcpy(text, out.c_str(), out.size() + 1);
   return RSPARSE_HIP_OK;
 }
 
@@ -1137,12 +1168,10 @@ int rsparse_hip_top_product_f64_device(const float* d_U, const float* d_V, const
     if (e != hipSuccess) return hip_fail(e, "launch_top_product_large_f64");
     return RSPARSE_HIP_OK;
   }
-  // candidates per user: k + extra (default: a quarter of k, at least 8), never more than the kernel's 256 or the items
-  if (extra < 0) extra = std::max(8, k / 4);
-  const int kc = std::max(k, std::min(std::min(k + extra, RSPARSE_HIP_MAX_TOPK), std::max(n_items, 1)));
+  const int kc = top_product_kc(k, extra, n_items);
   HIP_TRY(g_ws.bias_buf.ensure(top_product_f64_scratch_words(n_users, kc, k)));   // (nothing else uses this buffer meanwhile)
   float* split = nullptr;   // few users over many items: the nominating pass splits the items over the workgroups
-  const size_t sfl = top_product_scratch_floats(n_users, n_items, rank, kc);   // (or the candidate buffers of a large k)
+  const size_t sfl = top_product_plan(n_users, n_items, rank, kc, k, true).scratch_floats;   // (or the candidate buffers of a large k)
   if (sfl > 0) {
     HIP_TRY(g_ws.pad_buf.ensure(sfl));
     split = g_ws.pad_buf;

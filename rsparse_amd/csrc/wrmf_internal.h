@@ -311,13 +311,8 @@ hipError_t launch_top_product_f64(const float* U32, const float* V32, const doub
                                   int n_items, int rank, int topk, int kc, const int32_t* nr_ptr, const int32_t* nr_idx,
                                   const int32_t* excl, int n_excl, double glob_mean, int32_t* res, double* scores, hipStream_t s,
                                   float* scratch, float* split_scratch);
-// a call for few users over many items is split over the items (wrmf_topk.hip): floats of scratch it wants
-// (2 x entries + n_users), 0 = not split
-size_t top_product_scratch_entries(int n_users, int n_items, int topk);
-// ... and what launch_top_product wants in all (floats, 0 = none): those lists, or -- many users, a k whose candidate buffers do
-// not fit the LDS -- the global candidate buffers of the two-tile kernel (wrmf_topk.hip "GBUF")
-size_t top_product_scratch_floats(int n_users, int n_items, int k_rank, int topk);
-bool top_product_wants_gbuf(int n_users, int k_rank, int topk);
+// (the scratch both want -- the slices' lists of a call for few users over many items, or the global candidate buffers of a call
+// for many users -- is top_product_plan(...).scratch_floats, wrmf_topk_plan.h)
 // 256 < topk <= 8192 (wrmf_topk_large.hip): scores to a global key matrix per chunk of users, the kc-th key of every user by a radix
 // select, the candidates at or above it ordered in LDS (fp32 scores, or re-scored in double), the reference heap's result in closed
 // form; users whose candidate list overflows replay the heap.  ws: top_product_large_ws_floats(...) floats (chunk_users: users

@@ -7,67 +7,27 @@
 // stays), emit them best first -- equal scores come out with the larger index first, because the heap pops
 // (score, index) pairs in ascending pair order and the output is filled from the end (:88-95).
 //
-// (What follows describes the first geometry -- a wave per item tile, the candidate buffers in LDS --, which still serves calls
-// for up to 32 / 64 users.  Calls for more than 128 users run top_product_pipe_kernel<.., GBUF>: the four waves share the item
-// tile and own 64 users each, two tiles resident, the candidate buffers in a global scratch and settled once per batch of
-// arrivals by a radix select; few users over many items are split over the items and merged.  See launch_top_product_geo.)
-// One 256-thread workgroup per block of 32 * UB users (UB = 2 when the candidate buffers fit LDS, i.e. k <= 16).  The
-// user blocks are the MFMA A operands and stay in registers (UB * k/2 VGPRs); each of the 4 waves walks its own 32-item
-// tiles: while the matrix cores work on tile n, the 16-byte coalesced loads of tile n + 1 are in flight into registers
-// (one wave per SIMD: nothing else would hide them), then the tile goes to LDS (row stride k + 4: aligned 16-byte
-// stores; the 4-way bank conflict of the fragment reads is invisible next to a 64-cycle MFMA), is read back as B
-// fragments -- each fragment feeds UB MFMAs -- and multiplied with v_mfma_f32_32x32x2_f32 (exact fp32).  A score survives
-// only if it beats the user's current k-th best (threshold in LDS); survivors that pass the exclusion checks (binary
-// searches) are appended to the user's LDS buffer; once per round of 4 tiles, buffers holding more than k entries are
-// reduced to their top k by rank counting and the threshold is raised.  After the first few tiles almost nothing
-// survives.  (Round 3: the staging loop used to be 4-byte loads with a run-time division per element and no load in
-// flight during the MFMAs -- 8.6 TFLOP/s at 1M x 1M, rank 128; see profiles/r03.)
+// A map of this file.  Three kernel families multiply 32-user blocks (the MFMA A operands, in registers) with 32-item tiles
+// staged through LDS (v_mfma_f32_32x32x2_f32: exact fp32) and keep per-user candidate buffers of the scores that beat the
+// user's current k-th best:
+//   top_product_kernel         a tile per wave against the workgroup's 32 / 64 users (calls for up to 64 users, or a large k);
+//   top_product_shared_kernel  the four waves share one tile and own 32 users each (a narrow band of k where two tiles do not fit);
+//   top_product_pipe_kernel    the same with two tiles resident and the epilogue hidden behind the next tile's matrix
+//                              instructions; GBUF: the candidate buffers in a global scratch (every call for more than 128 users).
+// Few users over many items are split over the items and merged (top_merge_kernel); top_rescore_kernel re-scores candidates in
+// double.  WHICH kernel runs, how a call is sliced and what scratch it wants is decided in one place, wrmf_topk_plan.h
+// (top_product_plan: an ordered table of rows per rank); launch_top_product{,_f64} below walk that plan and launch_top_row
+// launches one of its rows.
 #include <algorithm>
 
 #include "wrmf_internal.h"
 #include "wrmf_device.h"
+#include "wrmf_topk_plan.h"
 
 namespace rsparse_hip {
 namespace {
 
 using namespace dev;
-
-constexpr int kTopBlock = 32;    // users per MFMA block
-constexpr int kTopMaxK = 256;    // RSPARSE_HIP_MAX_TOPK
-constexpr int kTopMaxCap = 576;  // no candidate buffer is longer (top_gcap(256) = 544; the LDS geometries: k + 128 at most)
-// candidate buffer per user: the heap (k entries) + everything one round can add (32 items per tile of the round)
-__host__ __device__ constexpr int top_cap(int topk, int tiles_per_round) { return ((topk + 32 * tiles_per_round + 3) / 4) * 4; }
-
-// GBUF (round 6): the candidate buffers of 256 users fit the LDS next to two tiles only up to k = 27 at rank 128, and only without
-// a spare entry: a user was settled at EVERY arrival.  The tile-sharing kernel now keeps them in GLOBAL memory (a scratch slot
-// per workgroup: appends are fire-and-forget stores, only the counts and thresholds stay in LDS) with room for a BATCH of
-// arrivals beyond one tile's worth -- a user is settled once per max(64, k) arrivals, in the settling wave's LDS work area,
-// by a radix select (topk_reduce_user).  One geometry, 256 users per workgroup, for every k.
-__host__ __device__ constexpr int top_gcap(int topk) { return ((topk + 32 + (topk > 64 ? topk : 64) + 3) / 4) * 4; }
-constexpr int kTopGbufChunk = 131072;   // users per launch of a GBUF call: 512 slots of scratch, two full rounds of workgroups
-
-// the kernel in which every wave walks its own item tiles against the workgroup's 32 UB users (W waves = W tiles per round)
-template <int KP, int UB, int W>
-struct TopSmem {
-  static constexpr int LDT = KP + 4;  // rows 16-byte aligned (ds_write_b128); fragment reads: 4-way conflict, hidden
-  static constexpr int USERS = kTopBlock * UB;
-  static constexpr size_t tile_floats = (size_t)W * 32 * LDT;
-  static size_t bytes(int topk) {
-    const size_t cap = (size_t)top_cap(topk, W);
-    return (tile_floats + 2 * (size_t)USERS * cap + 8 * USERS) * 4 + 64 + (size_t)W * cap * 8;   // + compaction scratch
-  }
-};
-// the kernel in which the four waves share ONE item tile and own 32 UB users each (round 4)
-template <int KP, int UB>
-struct TopSharedSmem {
-  static constexpr int LDT = KP + 4;
-  static constexpr int USERS = 4 * kTopBlock * UB;
-  static constexpr size_t tile_floats = (size_t)32 * LDT;
-  static size_t bytes(int topk) {
-    const size_t cap = (size_t)top_cap(topk, 1);
-    return (tile_floats + 2 * (size_t)USERS * cap + 3 * USERS) * 4 + 64 + (size_t)4 * cap * 8;
-  }
-};
 
 // is `item` in the sorted list a[0..n) ?
 __device__ __forceinline__ bool sorted_contains(const int32_t* __restrict__ a, int n, int item) {
@@ -79,11 +39,6 @@ __device__ __forceinline__ bool sorted_contains(const int32_t* __restrict__ a, i
     else hi = mid;
   }
   return lo < n && a[lo] == item;
-}
-
-// (va, ia) ranks before (vb, ib) when selecting: larger score first, earlier item on ties
-__device__ __forceinline__ bool sel_before(float va, int ia, float vb, int ib) {
-  return va > vb || (va == vb && ia < ib);
 }
 
 // Reduce one user's over-full candidate buffer (n > topk entries: bv / bi) to its top k by rank counting (tv / ti: scratch
@@ -294,342 +249,6 @@ __device__ __forceinline__ void topk_emit_user(const float* bv, const int* bi, c
   }
 }
 
-// A split launch (few users, many items: blockIdx.y = item slice): the workgroup sees its slice as the matrix -- item ids are
-// item_base + local -- and writes to the slice's block of the scratch; the fall-back launch of the unsplit kernel (user_flags
-// given) runs only the workgroups that hold a flagged user.  See launch_top_product.
-#define RSP_TOPK_SLICE(USERS_, THREADS_)                                                                 \
-  int item_base = 0;                                                                                     \
-  if (slice_items > 0) {                                                                                 \
-    item_base = (int)blockIdx.y * slice_items;                                                           \
-    V += (size_t)item_base * k_rank;                                                                     \
-    n_items = max(0, min(n_items - item_base, slice_items));                                             \
-    res += (size_t)blockIdx.y * n_users * topk;                                                          \
-    scores_out += (size_t)blockIdx.y * n_users * topk;                                                   \
-  }                                                                                                      \
-  if (user_flags) {                                                                                      \
-    int f_ = 0;                                                                                          \
-    for (int e_ = threadIdx.x; e_ < (USERS_); e_ += (THREADS_))                                          \
-      if (u0 + e_ < n_users) f_ |= user_flags[u0 + e_];                                                  \
-    if (!__syncthreads_or(f_)) return;                                                                   \
-  }
-
-template <int KP, int UB, bool VEC, int W>
-__global__ __launch_bounds__(W * 64) void top_product_kernel(const float* __restrict__ U, const float* __restrict__ V,
-                                                          int n_users, int n_items, int k_rank, int topk,
-                                                          const int32_t* __restrict__ nr_ptr,
-                                                          const int32_t* __restrict__ nr_idx,
-                                                          const int32_t* __restrict__ excl, int n_excl,
-                                                          float glob_mean, int32_t* __restrict__ res,
-                                                          float* __restrict__ scores_out, int slice_items,
-                                                          const int* __restrict__ user_flags) {
-  using SM = TopSmem<KP, UB, W>;
-  constexpr int LDT = SM::LDT, NK2 = KP / 2, kTopUsers = SM::USERS, kTopWaves = W;
-  const int kTopCap = top_cap(topk, W);
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* sTile = reinterpret_cast<float*>(smem);
-  float* sVal = sTile + SM::tile_floats;                            // [USERS][CAP]
-  int* sIdx = reinterpret_cast<int*>(sVal + (size_t)kTopUsers * kTopCap);   // [USERS][CAP]
-  int* sCnt = sIdx + (size_t)kTopUsers * kTopCap;                   // [USERS]
-  float* sThr = reinterpret_cast<float*>(sCnt + kTopUsers);         // [USERS]
-  int* sNeed = reinterpret_cast<int*>(sThr + kTopUsers);            // [USERS] spare / flags
-  float* sTmpV = reinterpret_cast<float*>(sNeed + 2 * kTopUsers + 4);  // [W][CAP]
-  int* sTmpI = reinterpret_cast<int*>(sTmpV + kTopWaves * kTopCap);    // [W][CAP]
-
-  const int tid = threadIdx.x, lane = tid & 63, wv = rfl(tid >> 6);
-  const int u0 = blockIdx.x * kTopUsers;
-  RSP_TOPK_SLICE(kTopUsers, W * 64)
-  const int col = lane & 31, half = lane >> 5;
-  if (tid < kTopUsers) {
-    sCnt[tid] = 0;
-    sThr[tid] = -INFINITY;
-    sNeed[tid] = 0;   // entries [0, sNeed) of the user's buffer are the heap as the last reduction left it
-  }
-  // A operands: lane holds U[u0 + 32 ub + (lane & 31)][2t + half], t = 0..KP/2-1 (zero beyond the matrix)
-  float afrag[UB][NK2];
-#pragma unroll
-  for (int ub = 0; ub < UB; ub++) {
-    const int u = u0 + 32 * ub + col;
-#pragma unroll
-    for (int t = 0; t < NK2; t++) {
-      const int kk = 2 * t + half;
-      afrag[ub][t] = (u < n_users && kk < k_rank) ? U[(size_t)u * k_rank + kk] : 0.f;
-    }
-  }
-  float* tile = sTile + wv * 32 * LDT;
-  for (int e = lane; e < 32 * LDT; e += 64) tile[e] = 0.f;
-  __syncthreads();
-
-  const int n_tiles = (n_items + 31) / 32;
-  const int rounds = (n_tiles + kTopWaves - 1) / kTopWaves;
-  // item tile tl -> registers: VEC = rank a multiple of 4 and V 16-byte aligned: NLD 16-byte loads per lane, all in
-  // flight together (piece e4 = j * 64 + lane: item e4 / (KP / 4), floats 4 (e4 % (KP / 4)) ..+3)
-  constexpr int NLD = KP / 8;
-  float4 pf[VEC ? NLD : 1];
-  auto load_tile = [&](const int tl) {
-    if constexpr (VEC) {
-      const int i0 = tl * 32;
-#pragma unroll
-      for (int j = 0; j < NLD; j++) {
-        const int e4 = j * 64 + lane, it = e4 / (KP / 4), c4 = e4 % (KP / 4);
-        pf[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (tl < n_tiles && i0 + it < n_items && 4 * c4 < k_rank)
-          pf[j] = *reinterpret_cast<const float4*>(V + (size_t)(i0 + it) * k_rank + 4 * c4);
-      }
-    }
-  };
-  auto store_tile = [&](const int tl) {
-    if constexpr (VEC) {
-#pragma unroll
-      for (int j = 0; j < NLD; j++) {
-        const int e4 = j * 64 + lane, it = e4 / (KP / 4), c4 = e4 % (KP / 4);
-        *reinterpret_cast<float4*>(tile + it * LDT + 4 * c4) = pf[j];
-      }
-    } else {   // any rank / alignment: scalar staging (slow path)
-      const int i0 = tl * 32;
-      for (int it = 0; it < 32; it++)
-        for (int kk = lane; kk < k_rank; kk += 64)
-          tile[it * LDT + kk] = (tl < n_tiles && i0 + it < n_items) ? V[(size_t)(i0 + it) * k_rank + kk] : 0.f;
-    }
-  };
-  load_tile(wv);
-  store_tile(wv);
-  wave_sync();
-  for (int rd = 0; rd < rounds; rd++) {
-    const int tl = rd * kTopWaves + wv;
-    load_tile(tl + kTopWaves);   // the next tile's loads fly during this tile's MFMAs
-    if (tl < n_tiles) {
-      const int i0 = tl * 32;
-      f32x16 acc[UB];
-#pragma unroll
-      for (int ub = 0; ub < UB; ub++)
-#pragma unroll
-        for (int e = 0; e < 16; e++) acc[ub][e] = 0.f;
-#pragma unroll
-      for (int t = 0; t < NK2; t++) {
-        const float b = tile[col * LDT + 2 * t + half];  // B[kk = 2t + half][item = col]
-#pragma unroll
-        for (int ub = 0; ub < UB; ub++) acc[ub] = __builtin_amdgcn_mfma_f32_32x32x2f32(afrag[ub][t], b, acc[ub], 0, 0, 0);
-      }
-      // lane holds item `col` for users row(e) = (e & 3) + 8 (e >> 2) + 4 half of each block
-      const int item = i0 + col, gitem = item + item_base;
-      const bool item_ok = item < n_items && !(n_excl > 0 && sorted_contains(excl, n_excl, gitem));
-#pragma unroll
-      for (int ub = 0; ub < UB; ub++)
-#pragma unroll
-        for (int e = 0; e < 16; e++) {
-          const int ul = 32 * ub + (e & 3) + 8 * (e >> 2) + 4 * half;
-          const int u = u0 + ul;
-          const float s = acc[ub][e];
-          if (item_ok && u < n_users && s > sThr[ul]) {
-            bool skip = false;
-            if (nr_ptr) {
-              const int p1 = nr_ptr[u], p2 = nr_ptr[u + 1];
-              skip = sorted_contains(nr_idx + p1, p2 - p1, gitem);
-            }
-            if (!skip) {
-              const int pos = atomicAdd(&sCnt[ul], 1);
-              if (pos < kTopCap) {
-                sVal[ul * kTopCap + pos] = s;
-                sIdx[ul * kTopCap + pos] = gitem;
-              }
-            }
-          }
-        }
-    }
-    wave_sync();                 // this wave has read its tile for the last time
-    store_tile(tl + kTopWaves);
-    __syncthreads();
-    // reduce over-full buffers to their top k (one wave per user, rank counting), raise the threshold
-    for (int ul = wv; ul < kTopUsers; ul += kTopWaves) {
-      const int n = min(sCnt[ul], kTopCap);
-      if (n > topk) {  // wave-uniform
-        const float thr = topk_reduce_user(sVal + ul * kTopCap, sIdx + ul * kTopCap, sTmpV + wv * kTopCap, sTmpI + wv * kTopCap, n,
-                                           topk, sNeed[ul], lane);
-        if (lane == 0) {
-          sCnt[ul] = topk;
-          sThr[ul] = thr;
-          sNeed[ul] = topk;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  for (int ul = wv; ul < kTopUsers; ul += kTopWaves) {
-    const int u = u0 + ul;
-    if (u >= n_users) continue;
-    topk_emit_user(sVal + ul * kTopCap, sIdx + ul * kTopCap, min(min(sCnt[ul], kTopCap), topk), topk, lane, glob_mean,
-                   res + (size_t)u * topk, scores_out + (size_t)u * topk);
-  }
-}
-
-
-// Round 4: the four waves SHARE one item tile and own 32 UB users each (128 / 256 users per workgroup).  The kernel above
-// reads every item vector once per 32 UB users -- at 1M x 1M, rank 128 that is 8 TB through the L2 for 64 users per
-// workgroup, and the matrix cores wait for it (52.7 TFLOP/s; one user block, as top-100 needs there, 9) --, this one once per
-// 128 UB: the tile is staged cooperatively (the next tile's 16-byte loads fly during this tile's MFMAs, as above), every
-// wave multiplies it with its own user blocks, and because a wave owns its users' candidate buffers outright the buffers
-// need room for ONE tile's survivors only (cap = k + 32) and are reduced by their wave without a workgroup barrier.
-template <int KP, int UB, bool VEC>
-__global__ __launch_bounds__(256) void top_product_shared_kernel(const float* __restrict__ U, const float* __restrict__ V,
-                                                                 int n_users, int n_items, int k_rank, int topk,
-                                                                 const int32_t* __restrict__ nr_ptr,
-                                                                 const int32_t* __restrict__ nr_idx,
-                                                                 const int32_t* __restrict__ excl, int n_excl,
-                                                                 float glob_mean, int32_t* __restrict__ res,
-                                                                 float* __restrict__ scores_out, int slice_items,
-                                                                 const int* __restrict__ user_flags) {
-  using SM = TopSharedSmem<KP, UB>;
-  constexpr int LDT = SM::LDT, NK2 = KP / 2, USERS = SM::USERS, UPW = 32 * UB;   // users per wave
-  const int cap = top_cap(topk, 1);
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* tile = reinterpret_cast<float*>(smem);                     // [32][LDT]
-  float* sVal = tile + SM::tile_floats;                             // [USERS][cap]
-  int* sIdx = reinterpret_cast<int*>(sVal + (size_t)USERS * cap);   // [USERS][cap]
-  int* sCnt = sIdx + (size_t)USERS * cap;                           // [USERS]
-  float* sThr = reinterpret_cast<float*>(sCnt + USERS);             // [USERS]
-  int* sNeed = reinterpret_cast<int*>(sThr + USERS);                // [USERS]
-  float* sTmpV = reinterpret_cast<float*>(sNeed + USERS);           // [4][cap]
-  int* sTmpI = reinterpret_cast<int*>(sTmpV + 4 * cap);             // [4][cap]
-
-  const int tid = threadIdx.x, lane = tid & 63, wv = rfl(tid >> 6);
-  const int u0 = blockIdx.x * USERS, uw = wv * UPW;                 // this wave's users: [u0 + uw, u0 + uw + UPW)
-  RSP_TOPK_SLICE(USERS, 256)
-  const int col = lane & 31, half = lane >> 5;
-  for (int e = tid; e < USERS; e += 256) {
-    sCnt[e] = 0;
-    sThr[e] = -INFINITY;
-    sNeed[e] = 0;
-  }
-  float afrag[UB][NK2];
-#pragma unroll
-  for (int ub = 0; ub < UB; ub++) {
-    const int u = u0 + uw + 32 * ub + col;
-#pragma unroll
-    for (int t = 0; t < NK2; t++) {
-      const int kk = 2 * t + half;
-      afrag[ub][t] = (u < n_users && kk < k_rank) ? U[(size_t)u * k_rank + kk] : 0.f;
-    }
-  }
-  for (int e = tid; e < 32 * LDT; e += 256) tile[e] = 0.f;
-  __syncthreads();
-
-  const int n_tiles = (n_items + 31) / 32;
-  constexpr int NLD = KP / 32;   // 16-byte pieces per thread and tile
-  float4 pf[VEC ? NLD : 1];
-  auto load_tile = [&](const int tl) {
-    if constexpr (VEC) {
-      const int i0 = tl * 32;
-#pragma unroll
-      for (int j = 0; j < NLD; j++) {
-        const int e4 = j * 256 + tid, it = e4 / (KP / 4), c4 = e4 % (KP / 4);
-        pf[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (tl < n_tiles && i0 + it < n_items && 4 * c4 < k_rank)
-          pf[j] = *reinterpret_cast<const float4*>(V + (size_t)(i0 + it) * k_rank + 4 * c4);
-      }
-    }
-  };
-  auto store_tile = [&](const int tl) {
-    if constexpr (VEC) {
-#pragma unroll
-      for (int j = 0; j < NLD; j++) {
-        const int e4 = j * 256 + tid, it = e4 / (KP / 4), c4 = e4 % (KP / 4);
-        *reinterpret_cast<float4*>(tile + it * LDT + 4 * c4) = pf[j];
-      }
-    } else {   // any rank / alignment: scalar staging (slow path)
-      const int i0 = tl * 32;
-      for (int it = wv; it < 32; it += 4)
-        for (int kk = lane; kk < k_rank; kk += 64)
-          tile[it * LDT + kk] = (tl < n_tiles && i0 + it < n_items) ? V[(size_t)(i0 + it) * k_rank + kk] : 0.f;
-    }
-  };
-  load_tile(0);
-  store_tile(0);
-  __syncthreads();
-  for (int tl = 0; tl < n_tiles; tl++) {
-    load_tile(tl + 1);   // the next tile's loads fly during this tile's MFMAs
-    const int i0 = tl * 32;
-    f32x16 acc[UB];
-#pragma unroll
-    for (int ub = 0; ub < UB; ub++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) acc[ub][e] = 0.f;
-#pragma unroll
-    for (int t = 0; t < NK2; t++) {
-      const float b = tile[col * LDT + 2 * t + half];  // B[kk = 2t + half][item = col]
-#pragma unroll
-      for (int ub = 0; ub < UB; ub++) acc[ub] = __builtin_amdgcn_mfma_f32_32x32x2f32(afrag[ub][t], b, acc[ub], 0, 0, 0);
-    }
-    // lane holds item `col` for users row(e) = (e & 3) + 8 (e >> 2) + 4 half of each block
-    const int item = i0 + col;
-    const bool item_ok = item < n_items;
-    // the thresholds of this lane's users, four 16-byte reads per block in flight together (one read and one wait per
-    // accumulator entry left the matrix cores idle for a third of the tile)
-    float4 thr4[UB][4];
-#pragma unroll
-    for (int ub = 0; ub < UB; ub++)
-#pragma unroll
-      for (int q = 0; q < 4; q++) thr4[ub][q] = *reinterpret_cast<const float4*>(sThr + uw + 32 * ub + 8 * q + 4 * half);
-#pragma unroll
-    for (int ub = 0; ub < UB; ub++)
-#pragma unroll
-      for (int e = 0; e < 16; e++) {
-        const int ul = uw + 32 * ub + (e & 3) + 8 * (e >> 2) + 4 * half;
-        const float sc = acc[ub][e];
-        const float* tq = reinterpret_cast<const float*>(&thr4[ub][e >> 2]);
-        if (item_ok && u0 + ul < n_users && sc > tq[e & 3]) {   // appended unverified: topk_settle_user consults the lists
-          const int pos = atomicAdd(&sCnt[ul], 1);               // (lanes of this wave only: at most 32 per user and tile)
-          sVal[ul * cap + pos] = sc;
-          sIdx[ul * cap + pos] = item + item_base;
-        }
-      }
-    wave_sync();
-    // this wave's over-full buffers: arrivals verified, top k kept, threshold raised (after the first tiles almost nothing survives)
-    for (int b0 = 0; b0 < UPW; b0 += 64) {
-      const int ulq = uw + b0 + lane;
-      unsigned long long over = __ballot(b0 + lane < UPW && sCnt[ulq] > topk);
-      while (over) {
-        const int ul = uw + b0 + __builtin_ctzll(over);
-        over &= over - 1;
-        topk_settle_user(sVal + ul * cap, sIdx + ul * cap, sTmpV + wv * cap, sTmpI + wv * cap, sCnt + ul, sThr + ul, sNeed + ul,
-                         topk, nr_ptr, nr_idx, u0 + ul, excl, n_excl, lane);
-      }
-    }
-    __syncthreads();             // every wave has read the tile for the last time
-    store_tile(tl + 1);
-    __syncthreads();
-  }
-  for (int ul = uw; ul < uw + UPW; ul++) {
-    const int u = u0 + ul;
-    if (u >= n_users) break;
-    if (sCnt[ul] > sNeed[ul])   // arrivals that no reduction has looked at yet (the buffer never filled up again)
-      topk_settle_user(sVal + ul * cap, sIdx + ul * cap, sTmpV + wv * cap, sTmpI + wv * cap, sCnt + ul, sThr + ul, sNeed + ul, topk,
-                       nr_ptr, nr_idx, u, excl, n_excl, lane);
-    topk_emit_user(sVal + ul * cap, sIdx + ul * cap, min(sCnt[ul], topk), topk, lane, glob_mean, res + (size_t)u * topk,
-                   scores_out + (size_t)u * topk);
-  }
-}
-
-// The same with the epilogue hidden behind the NEXT tile's matrix instructions (round 4).  One wave per SIMD (the user blocks
-// take 128 registers, the accumulators 32): nothing else runs while a wave compares its 32 scores per lane with the users'
-// thresholds, so in the kernel above the matrix cores idle for that part of every tile.  Here two tiles are resident in LDS
-// and two accumulator sets alternate: the MFMAs of tile t + 1 are issued in chunks of KP / 32 k-steps between the
-// accumulator entries of tile t (a matrix instruction executes for 64 cycles after it has been issued; the compares, the rare
-// appends and the buffer reductions of tile t run meanwhile), and one barrier per tile is enough -- tile t + 2 lands in the
-// buffer whose last reader finished before the previous barrier.
-template <int KP, int UB>
-struct TopPipeSmem {
-  static constexpr int LDT = KP + 4;
-  static constexpr int USERS = 4 * kTopBlock * UB;
-  static constexpr size_t tile_floats = (size_t)2 * 32 * LDT;
-  static size_t bytes(int topk) {
-    const size_t cap = (size_t)top_cap(topk, 1);
-    return (tile_floats + 2 * (size_t)USERS * cap + 3 * USERS) * 4 + 64 + (size_t)4 * cap * 8;
-  }
-  static size_t gbytes(int topk) {   // GBUF: tiles, counts / thresholds / verified lengths, per wave a work area and a scratch
-    return (tile_floats + 3 * USERS) * 4 + 64 + (size_t)4 * top_gcap(topk) * 16;
-  }
-};
-
 // GBUF: a user's buffer (global: gv / gi, n entries) through the wave's LDS work area (wv_ / wi_): arrivals verified, the buffer
 // reduced when it is over-full, what is left written back.  One wave.
 __device__ __forceinline__ void topk_settle_user_g(float* gv, int* gi, float* wv_, int* wi_, float* tv, int* ti, int* cnt,
@@ -650,6 +269,390 @@ __device__ __forceinline__ void topk_settle_user_g(float* gv, int* gi, float* wv
   }
 }
 
+// ---- the steps the kernel families share ------------------------------------------------------------------------------------------
+// A split launch (few users, many items: blockIdx.y = item slice): the workgroup sees its slice as the matrix -- item ids are
+// item_base (returned) + local -- and writes to the slice's block of the scratch.  See launch_top_first.
+__device__ __forceinline__ int top_enter_slice(const float* __restrict__& V, int& n_items, int32_t* __restrict__& res,
+                                               float* __restrict__& scores_out, const int slice_items, const int n_users,
+                                               const int k_rank, const int topk) {
+  if (slice_items <= 0) return 0;
+  const int item_base = (int)blockIdx.y * slice_items;
+  V += (size_t)item_base * k_rank;
+  n_items = max(0, min(n_items - item_base, slice_items));
+  res += (size_t)blockIdx.y * n_users * topk;
+  scores_out += (size_t)blockIdx.y * n_users * topk;
+  return item_base;
+}
+// the fall-back launch of the unsplit kernel (user_flags given) runs only the workgroups that hold a flagged user: does the block
+// of USERS users from u0 hold one?  (A barrier: every thread of the workgroup calls it.)
+template <int USERS, int THREADS>
+__device__ __forceinline__ bool top_block_flagged(const int* __restrict__ user_flags, const int u0, const int n_users) {
+  int f = 0;
+  for (int e = threadIdx.x; e < USERS; e += THREADS)
+    if (u0 + e < n_users) f |= user_flags[u0 + e];
+  return __syncthreads_or(f);
+}
+
+// A operands: lane holds U[ubase + 32 ub + (lane & 31)][2t + half], t = 0..KP/2-1 (zero beyond the matrix)
+template <int UB, int NK2>
+__device__ __forceinline__ void top_load_users(float (&afrag)[UB][NK2], const float* __restrict__ U, const int ubase,
+                                               const int n_users, const int k_rank, const int col, const int half) {
+#pragma unroll
+  for (int ub = 0; ub < UB; ub++) {
+    const int u = ubase + 32 * ub + col;
+#pragma unroll
+    for (int t = 0; t < NK2; t++) {
+      const int kk = 2 * t + half;
+      afrag[ub][t] = (u < n_users && kk < k_rank) ? U[(size_t)u * k_rank + kk] : 0.f;
+    }
+  }
+}
+
+// Item tile tl -> registers (load) -> LDS (store), by THREADS threads (64: every wave stages its own tiles).  VEC = rank a multiple of 4 and V
+// 16-byte aligned: NLD 16-byte loads per thread, all in flight together (piece e4 = j * THREADS + t: item e4 / (KP / 4), floats
+// 4 (e4 % (KP / 4)) ..+3): load() goes before the matrix instructions of the resident tile, store() after the last reader of the
+// LDS tile it replaces.  Else (any rank / alignment) scalar staging in store(), the slow path: a row per wave and step.
+template <int KP, bool VEC, int THREADS>
+struct TopStager {
+  static constexpr int LDT = KP + 4, NLD = 8 * KP / THREADS;
+  const float* __restrict__ V;
+  int n_tiles, n_items, k_rank;
+  float4 pf[VEC ? NLD : 1];   // the tile in flight
+  __device__ __forceinline__ TopStager(const float* __restrict__ V_, int n_tiles_, int n_items_, int k_rank_)
+      : V(V_), n_tiles(n_tiles_), n_items(n_items_), k_rank(k_rank_) {}
+  __device__ __forceinline__ void load(const int tl) {
+    if constexpr (VEC) {
+      const int i0 = tl * 32;
+#pragma unroll
+      for (int j = 0; j < NLD; j++) {
+        const int e4 = j * THREADS + threadIdx.x % THREADS, it = e4 / (KP / 4), c4 = e4 % (KP / 4);
+        pf[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tl < n_tiles && i0 + it < n_items && 4 * c4 < k_rank)
+          pf[j] = *reinterpret_cast<const float4*>(V + (size_t)(i0 + it) * k_rank + 4 * c4);
+      }
+    }
+  }
+  __device__ __forceinline__ void store(float* tile, const int tl) {
+    if constexpr (VEC) {
+#pragma unroll
+      for (int j = 0; j < NLD; j++) {
+        const int e4 = j * THREADS + threadIdx.x % THREADS, it = e4 / (KP / 4), c4 = e4 % (KP / 4);
+        *reinterpret_cast<float4*>(tile + it * LDT + 4 * c4) = pf[j];
+      }
+    } else {
+      const int i0 = tl * 32, row0 = THREADS == 64 ? 0 : rfl(threadIdx.x >> 6);
+      for (int it = row0; it < 32; it += THREADS / 64)
+        for (int kk = threadIdx.x & 63; kk < k_rank; kk += 64)
+          tile[it * LDT + kk] = (tl < n_tiles && i0 + it < n_items) ? V[(size_t)(i0 + it) * k_rank + kk] : 0.f;
+    }
+  }
+};
+
+// the products of a resident tile with the wave's user blocks, exact fp32: tp = the tile's row `col` + half, so that tp[2 t] is
+// B[kk = 2t + half][item = col]; the lane then holds item `col` for users row(e) = (e & 3) + 8 (e >> 2) + 4 half of each block
+template <int UB, int NK2>
+__device__ __forceinline__ void top_sweep(f32x16 (&acc)[UB], const float (&afrag)[UB][NK2], const float* tp) {
+#pragma unroll
+  for (int ub = 0; ub < UB; ub++)
+#pragma unroll
+    for (int e = 0; e < 16; e++) acc[ub][e] = 0.f;
+#pragma unroll
+  for (int t = 0; t < NK2; t++) {
+    const float b = tp[2 * t];
+#pragma unroll
+    for (int ub = 0; ub < UB; ub++) acc[ub] = __builtin_amdgcn_mfma_f32_32x32x2f32(afrag[ub][t], b, acc[ub], 0, 0, 0);
+  }
+}
+
+// The LDS of a workgroup (top_lds_bytes, wrmf_topk_plan.h, is its size): the item tiles (rows of KP + 4 floats: 16-byte aligned for
+// ds_write_b128; the 4-way bank conflict of the fragment reads is invisible next to a 64-cycle MFMA) | per user `cap` candidate
+// scores | as many items | counts | thresholds | `need_words` words, the first per user = how many leading entries of its buffer
+// are the heap as the last reduction left it | per wave a scratch of cap scores and cap items | GBUF: per wave a work area of the
+// same size, and the candidate buffers themselves are the workgroup's slot of the global scratch
+struct TopLds {
+  float *tiles, *val;
+  int *idx, *cnt;
+  float* thr;
+  int* need;
+  float* tmpv;
+  int* tmpi;
+  float* wrkv;
+  int* wrki;
+};
+template <bool GBUF>
+__device__ __forceinline__ TopLds top_carve(char* smem, const size_t tile_floats, const int users, const int cap,
+                                            const int need_words, const int waves, float* gslot) {
+  TopLds s;
+  s.tiles = reinterpret_cast<float*>(smem);
+  s.val = GBUF ? gslot : s.tiles + tile_floats;
+  s.idx = reinterpret_cast<int*>(s.val + (size_t)users * cap);
+  s.cnt = GBUF ? reinterpret_cast<int*>(s.tiles + tile_floats) : s.idx + (size_t)users * cap;
+  s.thr = reinterpret_cast<float*>(s.cnt + users);
+  s.need = reinterpret_cast<int*>(s.thr + users);
+  s.tmpv = reinterpret_cast<float*>(s.need + need_words);
+  s.tmpi = reinterpret_cast<int*>(s.tmpv + waves * cap);
+  s.wrkv = reinterpret_cast<float*>(s.tmpi + waves * cap);
+  s.wrki = reinterpret_cast<int*>(s.wrkv + waves * cap);
+  return s;
+}
+__device__ __forceinline__ void top_reset_users(const TopLds& s, const int users, const int threads) {
+  for (int e = threadIdx.x; e < users; e += threads) {
+    s.cnt[e] = 0;
+    s.thr[e] = -INFINITY;
+    s.need[e] = 0;
+  }
+}
+
+// ---- ... and the steps of the two tile-sharing kernels, in which a wave owns its users' buffers outright ----------------------------
+// the thresholds of this lane's users (thr_w: the wave's first), four 16-byte reads per block in flight together (one read and one
+// wait per accumulator entry left the matrix cores idle for a third of the tile)
+template <int UB>
+__device__ __forceinline__ void top_load_thresholds(float4 (&thr4)[UB][4], const float* thr_w, const int half) {
+#pragma unroll
+  for (int ub = 0; ub < UB; ub++)
+#pragma unroll
+    for (int q = 0; q < 4; q++) thr4[ub][q] = *reinterpret_cast<const float4*>(thr_w + 32 * ub + 8 * q + 4 * half);
+}
+// Accumulator entry e of user block ub: a score that beats its user's threshold is appended WITHOUT looking at the exclusion
+// lists (lanes of this wave only: at most 32 per user and tile) -- topk_settle_user consults them.  ok: the item and the user exist
+template <int UB>
+__device__ __forceinline__ void top_append(const TopLds& s, const bool ok, const float sc, const float4 (&thr4)[UB][4], const int ub,
+                                           const int e, const int ul, const int gitem, const int cap) {
+  const float* tq = reinterpret_cast<const float*>(&thr4[ub][e >> 2]);
+  if (ok && sc > tq[e & 3]) {
+    const int pos = atomicAdd(&s.cnt[ul], 1);
+    s.val[ul * cap + pos] = sc;
+    s.idx[ul * cap + pos] = gitem;
+  }
+}
+// this wave's buffers whose count passed settle_at: arrivals verified, top k kept, threshold raised (after the first tiles almost
+// nothing survives)
+template <bool GBUF, int UPW>
+__device__ __forceinline__ void top_settle_wave(const TopLds& s, const int uw, const int settle_at, const int cap, const int topk,
+                                                const int32_t* __restrict__ nr_ptr, const int32_t* __restrict__ nr_idx, const int u0,
+                                                const int32_t* __restrict__ excl, const int n_excl, const int wv, const int lane) {
+  for (int b0 = 0; b0 < UPW; b0 += 64) {
+    const int ulq = uw + b0 + lane;
+    unsigned long long over = __ballot(b0 + lane < UPW && s.cnt[ulq] > settle_at);
+    if constexpr (GBUF) {
+      // (the appends are this wave's own stores: complete, and not served from a stale line of the vector cache)
+      if (over) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+    }
+    while (over) {
+      const int ul = uw + b0 + __builtin_ctzll(over);
+      over &= over - 1;
+      if constexpr (GBUF)
+        topk_settle_user_g(s.val + (size_t)ul * cap, s.idx + (size_t)ul * cap, s.wrkv + wv * cap, s.wrki + wv * cap, s.tmpv + wv * cap,
+                           s.tmpi + wv * cap, s.cnt + ul, s.thr + ul, s.need + ul, topk, nr_ptr, nr_idx, u0 + ul, excl, n_excl, lane);
+      else
+        topk_settle_user(s.val + (size_t)ul * cap, s.idx + (size_t)ul * cap, s.tmpv + wv * cap, s.tmpi + wv * cap, s.cnt + ul,
+                         s.thr + ul, s.need + ul, topk, nr_ptr, nr_idx, u0 + ul, excl, n_excl, lane);
+    }
+  }
+}
+// after the last tile: this wave's users settled where arrivals are left that no reduction has looked at (the buffer never filled
+// up again), and emitted.  GBUF: always through the work area -- the last arrivals are verified / reduced there, and the
+// emission reads LDS
+template <bool GBUF, int UPW>
+__device__ __forceinline__ void top_finish_wave(const TopLds& s, const int uw, const int cap, const int topk, const int n_users,
+                                                const int32_t* __restrict__ nr_ptr, const int32_t* __restrict__ nr_idx, const int u0,
+                                                const int32_t* __restrict__ excl, const int n_excl, const float glob_mean,
+                                                int32_t* __restrict__ res, float* __restrict__ scores_out, const int wv,
+                                                const int lane) {
+  if constexpr (GBUF) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
+  for (int ul = uw; ul < uw + UPW; ul++) {
+    const int u = u0 + ul;
+    if (u >= n_users) break;
+    const float* gv = s.val + (size_t)ul * cap;
+    const int* gi = s.idx + (size_t)ul * cap;
+    float* bv = GBUF ? s.wrkv + wv * cap : s.val + (size_t)ul * cap;
+    int* bi = GBUF ? s.wrki + wv * cap : s.idx + (size_t)ul * cap;
+    const int n0 = s.cnt[ul];
+    if constexpr (GBUF) {
+      wave_sync();
+      for (int c = lane; c < n0; c += 64) {
+        bv[c] = gv[c];
+        bi[c] = gi[c];
+      }
+      wave_sync();
+    }
+    if (n0 > s.need[ul])
+      topk_settle_user(bv, bi, s.tmpv + wv * cap, s.tmpi + wv * cap, s.cnt + ul, s.thr + ul, s.need + ul, topk, nr_ptr, nr_idx, u, excl,
+                       n_excl, lane);
+    topk_emit_user(bv, bi, min(s.cnt[ul], topk), topk, lane, glob_mean, res + (size_t)u * topk, scores_out + (size_t)u * topk);
+  }
+}
+
+// ---- a tile per wave: every wave walks its own item tiles against the workgroup's 32 UB users (W waves = W tiles per round) ----------
+// One workgroup per block of 32 UB users; while the matrix cores work on a wave's tile n, the loads of its tile n + 1 are in
+// flight into registers (one wave per SIMD: nothing else would hide them).  A score survives only if it beats the user's current
+// k-th best; survivors that pass the exclusion checks (binary searches) are appended to the user's buffer (the heap + everything
+// one round of W tiles can add); once per round, buffers holding more than k entries are reduced to their top k and the threshold
+// is raised.  After the first few tiles almost nothing survives.  (Round 3: the staging loop used to be 4-byte loads with a
+// run-time division per element and no load in flight during the MFMAs -- 8.6 TFLOP/s at 1M x 1M, rank 128; see profiles/r03.)
+template <int KP, int UB, bool VEC, int W>
+__global__ __launch_bounds__(W * 64) void top_product_kernel(const float* __restrict__ U, const float* __restrict__ V,
+                                                          int n_users, int n_items, int k_rank, int topk,
+                                                          const int32_t* __restrict__ nr_ptr,
+                                                          const int32_t* __restrict__ nr_idx,
+                                                          const int32_t* __restrict__ excl, int n_excl,
+                                                          float glob_mean, int32_t* __restrict__ res,
+                                                          float* __restrict__ scores_out, int slice_items,
+                                                          const int* __restrict__ user_flags) {
+  constexpr int LDT = KP + 4, NK2 = KP / 2, kTopUsers = kTopBlock * UB, kTopWaves = W;
+  const int kTopCap = top_cap(topk, W);
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const TopLds s = top_carve<false>(smem, (size_t)W * 32 * LDT, kTopUsers, kTopCap, 2 * kTopUsers + 4, W, nullptr);
+  float *sVal = s.val, *sThr = s.thr;
+  int *sIdx = s.idx, *sCnt = s.cnt, *sNeed = s.need;
+
+  const int tid = threadIdx.x, lane = tid & 63, wv = rfl(tid >> 6);
+  const int u0 = blockIdx.x * kTopUsers;
+  const int item_base = top_enter_slice(V, n_items, res, scores_out, slice_items, n_users, k_rank, topk);
+  if (user_flags && !top_block_flagged<kTopUsers, W * 64>(user_flags, u0, n_users)) return;
+  const int col = lane & 31, half = lane >> 5;
+  top_reset_users(s, kTopUsers, W * 64);
+  float afrag[UB][NK2];
+  top_load_users(afrag, U, u0, n_users, k_rank, col, half);
+  float* tile = s.tiles + wv * 32 * LDT;
+  for (int e = lane; e < 32 * LDT; e += 64) tile[e] = 0.f;
+  __syncthreads();
+
+  const int n_tiles = (n_items + 31) / 32;
+  const int rounds = (n_tiles + kTopWaves - 1) / kTopWaves;
+  TopStager<KP, VEC, 64> stage(V, n_tiles, n_items, k_rank);
+  stage.load(wv);
+  stage.store(tile, wv);
+  wave_sync();
+  for (int rd = 0; rd < rounds; rd++) {
+    const int tl = rd * kTopWaves + wv;
+    stage.load(tl + kTopWaves);   // the next tile's loads fly during this tile's MFMAs
+    if (tl < n_tiles) {
+      const int i0 = tl * 32;
+      f32x16 acc[UB];
+      top_sweep(acc, afrag, tile + col * LDT + half);
+      const int item = i0 + col, gitem = item + item_base;
+      const bool item_ok = item < n_items && !(n_excl > 0 && sorted_contains(excl, n_excl, gitem));
+#pragma unroll
+      for (int ub = 0; ub < UB; ub++)
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+          const int ul = 32 * ub + (e & 3) + 8 * (e >> 2) + 4 * half;
+          const int u = u0 + ul;
+          const float sc = acc[ub][e];
+          if (item_ok && u < n_users && sc > sThr[ul]) {
+            bool skip = false;
+            if (nr_ptr) {
+              const int p1 = nr_ptr[u], p2 = nr_ptr[u + 1];
+              skip = sorted_contains(nr_idx + p1, p2 - p1, gitem);
+            }
+            if (!skip) {
+              const int pos = atomicAdd(&sCnt[ul], 1);
+              if (pos < kTopCap) {
+                sVal[ul * kTopCap + pos] = sc;
+                sIdx[ul * kTopCap + pos] = gitem;
+              }
+            }
+          }
+        }
+    }
+    wave_sync();                 // this wave has read its tile for the last time
+    stage.store(tile, tl + kTopWaves);
+    __syncthreads();
+    // reduce over-full buffers to their top k (one wave per user), raise the threshold
+    for (int ul = wv; ul < kTopUsers; ul += kTopWaves) {
+      const int n = min(sCnt[ul], kTopCap);
+      if (n > topk) {  // wave-uniform
+        const float thr = topk_reduce_user(sVal + ul * kTopCap, sIdx + ul * kTopCap, s.tmpv + wv * kTopCap, s.tmpi + wv * kTopCap, n,
+                                           topk, sNeed[ul], lane);
+        if (lane == 0) {
+          sCnt[ul] = topk;
+          sThr[ul] = thr;
+          sNeed[ul] = topk;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  for (int ul = wv; ul < kTopUsers; ul += kTopWaves) {
+    const int u = u0 + ul;
+    if (u >= n_users) continue;
+    topk_emit_user(sVal + ul * kTopCap, sIdx + ul * kTopCap, min(min(sCnt[ul], kTopCap), topk), topk, lane, glob_mean,
+                   res + (size_t)u * topk, scores_out + (size_t)u * topk);
+  }
+}
+
+// Round 4: the four waves SHARE one item tile and own 32 users each (128 users per workgroup).  The kernel above
+// reads every item vector once per 32 UB users -- at 1M x 1M, rank 128 that is 8 TB through the L2 for 64 users per
+// workgroup, and the matrix cores wait for it (52.7 TFLOP/s; one user block, as top-100 needs there, 9) --, this one once per
+// 128: the tile is staged cooperatively (the next tile's 16-byte loads fly during this tile's MFMAs, as above), every
+// wave multiplies it with its own user block, and because a wave owns its users' candidate buffers outright the buffers
+// need room for ONE tile's survivors only (cap = k + 32) and are reduced by their wave without a workgroup barrier.
+template <int KP, bool VEC>
+__global__ __launch_bounds__(256) void top_product_shared_kernel(const float* __restrict__ U, const float* __restrict__ V,
+                                                                 int n_users, int n_items, int k_rank, int topk,
+                                                                 const int32_t* __restrict__ nr_ptr,
+                                                                 const int32_t* __restrict__ nr_idx,
+                                                                 const int32_t* __restrict__ excl, int n_excl,
+                                                                 float glob_mean, int32_t* __restrict__ res,
+                                                                 float* __restrict__ scores_out, int slice_items,
+                                                                 const int* __restrict__ user_flags) {
+  constexpr int UB = 1;   // user blocks per wave (two never fit where the two-tile kernel with one does not)
+  constexpr int LDT = KP + 4, NK2 = KP / 2, USERS = 4 * kTopBlock * UB, UPW = 32 * UB;   // users per wave
+  const int cap = top_cap(topk, 1);
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const TopLds s = top_carve<false>(smem, (size_t)32 * LDT, USERS, cap, USERS, 4, nullptr);
+  float* tile = s.tiles;
+
+  const int tid = threadIdx.x, lane = tid & 63, wv = rfl(tid >> 6);
+  const int u0 = blockIdx.x * USERS, uw = wv * UPW;                 // this wave's users: [u0 + uw, u0 + uw + UPW)
+  const int item_base = top_enter_slice(V, n_items, res, scores_out, slice_items, n_users, k_rank, topk);
+  if (user_flags && !top_block_flagged<USERS, 256>(user_flags, u0, n_users)) return;
+  const int col = lane & 31, half = lane >> 5;
+  top_reset_users(s, USERS, 256);
+  float afrag[UB][NK2];
+  top_load_users(afrag, U, u0 + uw, n_users, k_rank, col, half);
+  for (int e = tid; e < 32 * LDT; e += 256) tile[e] = 0.f;
+  __syncthreads();
+
+  const int n_tiles = (n_items + 31) / 32;
+  TopStager<KP, VEC, 256> stage(V, n_tiles, n_items, k_rank);
+  stage.load(0);
+  stage.store(tile, 0);
+  __syncthreads();
+  for (int tl = 0; tl < n_tiles; tl++) {
+    stage.load(tl + 1);   // the next tile's loads fly during this tile's MFMAs
+    f32x16 acc[UB];
+    top_sweep(acc, afrag, tile + col * LDT + half);
+    const int item = tl * 32 + col;
+    const bool item_ok = item < n_items;
+    float4 thr4[UB][4];
+    top_load_thresholds(thr4, s.thr + uw, half);
+#pragma unroll
+    for (int ub = 0; ub < UB; ub++)
+#pragma unroll
+      for (int e = 0; e < 16; e++) {
+        const int ul = uw + 32 * ub + (e & 3) + 8 * (e >> 2) + 4 * half;
+        top_append(s, item_ok && u0 + ul < n_users, acc[ub][e], thr4, ub, e, ul, item + item_base, cap);
+      }
+    wave_sync();
+    top_settle_wave<false, UPW>(s, uw, topk, cap, topk, nr_ptr, nr_idx, u0, excl, n_excl, wv, lane);
+    __syncthreads();             // every wave has read the tile for the last time
+    stage.store(tile, tl + 1);
+    __syncthreads();
+  }
+  top_finish_wave<false, UPW>(s, uw, cap, topk, n_users, nr_ptr, nr_idx, u0, excl, n_excl, glob_mean, res, scores_out, wv, lane);
+}
+
+// The same with the epilogue hidden behind the NEXT tile's matrix instructions (round 4).  One wave per SIMD (the user blocks
+// take 128 registers, the accumulators 32): nothing else runs while a wave compares its 32 scores per lane with the users'
+// thresholds, so in the kernel above the matrix cores idle for that part of every tile.  Here two tiles are resident in LDS
+// and two accumulator sets alternate: the MFMAs of tile t + 1 are issued in chunks of KP / 32 k-steps between the
+// accumulator entries of tile t (a matrix instruction executes for 64 cycles after it has been issued; the compares, the rare
+// appends and the buffer reductions of tile t run meanwhile), and one barrier per tile is enough -- tile t + 2 lands in the
+// buffer whose last reader finished before the previous barrier.
+// GBUF: the candidate buffers are this workgroup's slot of the global scratch ([USERS][cap] scores, then as many indices), with
+// room for a batch of arrivals (top_gcap): a user is settled when its count passes cap - 32 (room for one tile's arrivals).
 template <int KP, int UB, bool VEC, bool GBUF = false>
 __global__ __launch_bounds__(256) void top_product_pipe_kernel(const float* __restrict__ U, const float* __restrict__ V,
                                                                int n_users, int n_items, int k_rank, int topk,
@@ -659,34 +662,18 @@ __global__ __launch_bounds__(256) void top_product_pipe_kernel(const float* __re
                                                                float glob_mean, int32_t* __restrict__ res,
                                                                float* __restrict__ scores_out, int slice_items,
                                                                const int* __restrict__ user_flags, float* gbuf) {
-  using SM = TopPipeSmem<KP, UB>;
-  constexpr int LDT = SM::LDT, NK2 = KP / 2, USERS = SM::USERS, UPW = 32 * UB;
+  constexpr int LDT = KP + 4, NK2 = KP / 2, USERS = 4 * kTopBlock * UB, UPW = 32 * UB;
   constexpr int CH = NK2 / 16;   // k-steps (x UB matrix instructions) issued per accumulator entry of the previous tile
   const int cap = GBUF ? top_gcap(topk) : top_cap(topk, 1);
-  const int settle_at = GBUF ? cap - 32 : topk;   // a user is settled when its count passes this (room for one tile's arrivals)
+  const int settle_at = GBUF ? cap - 32 : topk;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* tiles = reinterpret_cast<float*>(smem);                    // [2][32][LDT]
-  // GBUF: the buffers are this workgroup's slot of the global scratch ([USERS][cap] scores, then as many indices)
-  float* sVal = GBUF ? gbuf + (size_t)blockIdx.x * 2 * USERS * cap : tiles + SM::tile_floats;
-  int* sIdx = reinterpret_cast<int*>(sVal + (size_t)USERS * cap);
-  int* sCnt = GBUF ? reinterpret_cast<int*>(tiles + SM::tile_floats) : sIdx + (size_t)USERS * cap;
-  float* sThr = reinterpret_cast<float*>(sCnt + USERS);
-  int* sNeed = reinterpret_cast<int*>(sThr + USERS);
-  float* sTmpV = reinterpret_cast<float*>(sNeed + USERS);
-  int* sTmpI = reinterpret_cast<int*>(sTmpV + 4 * cap);
-  float* sWrkV = reinterpret_cast<float*>(sTmpI + 4 * cap);          // GBUF: [4][cap] the settling wave's copy of a buffer
-  int* sWrkI = reinterpret_cast<int*>(sWrkV + 4 * cap);
+  const TopLds s = top_carve<GBUF>(smem, (size_t)2 * 32 * LDT, USERS, cap, USERS, 4,
+                                       GBUF ? gbuf + (size_t)blockIdx.x * 2 * USERS * cap : nullptr);
+  float* tiles = s.tiles;                                           // [2][32][LDT]
 
   const int tid = threadIdx.x, lane = tid & 63, wv = rfl(tid >> 6);
   const int uw = wv * UPW;
-  int item_base = 0;
-  if (slice_items > 0) {   // a split launch: this workgroup's slice of the items (see RSP_TOPK_SLICE)
-    item_base = (int)blockIdx.y * slice_items;
-    V += (size_t)item_base * k_rank;
-    n_items = max(0, min(n_items - item_base, slice_items));
-    res += (size_t)blockIdx.y * n_users * topk;
-    scores_out += (size_t)blockIdx.y * n_users * topk;
-  }
+  const int item_base = top_enter_slice(V, n_items, res, scores_out, slice_items, n_users, k_rank, topk);
   // A workgroup takes the user blocks blockIdx.x, + gridDim.x, ...: one block each in the ordinary launch; the fall-back launch for
   // flagged users (user_flags) comes with a grid of at most 512 and every workgroup walks its blocks' flags -- a workgroup that only
   // finds out that it has nothing to do still costs 6..12 us of a CU that it owns alone (150 KB of LDS, 512 registers per lane),
@@ -694,91 +681,34 @@ __global__ __launch_bounds__(256) void top_product_pipe_kernel(const float* __re
   const int n_blocks = (n_users + USERS - 1) / USERS;
   for (int blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
   const int u0 = blk * USERS;
-  if (user_flags) {
-    int f_ = 0;
-    for (int e_ = tid; e_ < USERS; e_ += 256)
-      if (u0 + e_ < n_users) f_ |= user_flags[u0 + e_];
-    if (!__syncthreads_or(f_)) continue;
-  }
+  if (user_flags && !top_block_flagged<USERS, 256>(user_flags, u0, n_users)) continue;
   const int col = lane & 31, half = lane >> 5;
-  for (int e = tid; e < USERS; e += 256) {
-    sCnt[e] = 0;
-    sThr[e] = -INFINITY;
-    sNeed[e] = 0;
-  }
+  top_reset_users(s, USERS, 256);
   float afrag[UB][NK2];
-#pragma unroll
-  for (int ub = 0; ub < UB; ub++) {
-    const int u = u0 + uw + 32 * ub + col;
-#pragma unroll
-    for (int t = 0; t < NK2; t++) {
-      const int kk = 2 * t + half;
-      afrag[ub][t] = (u < n_users && kk < k_rank) ? U[(size_t)u * k_rank + kk] : 0.f;
-    }
-  }
+  top_load_users(afrag, U, u0 + uw, n_users, k_rank, col, half);
   for (int e = tid; e < 2 * 32 * LDT; e += 256) tiles[e] = 0.f;
   __syncthreads();
 
   const int n_tiles = (n_items + 31) / 32;
-  constexpr int NLD = KP / 32;
-  float4 pf[VEC ? NLD : 1];
-  auto load_tile = [&](const int tl) {
-    if constexpr (VEC) {
-      const int i0 = tl * 32;
-#pragma unroll
-      for (int j = 0; j < NLD; j++) {
-        const int e4 = j * 256 + tid, it = e4 / (KP / 4), c4 = e4 % (KP / 4);
-        pf[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (tl < n_tiles && i0 + it < n_items && 4 * c4 < k_rank)
-          pf[j] = *reinterpret_cast<const float4*>(V + (size_t)(i0 + it) * k_rank + 4 * c4);
-      }
-    }
-  };
-  auto store_tile = [&](const int tl) {
-    float* tile = tiles + (tl & 1) * 32 * LDT;
-    if constexpr (VEC) {
-#pragma unroll
-      for (int j = 0; j < NLD; j++) {
-        const int e4 = j * 256 + tid, it = e4 / (KP / 4), c4 = e4 % (KP / 4);
-        *reinterpret_cast<float4*>(tile + it * LDT + 4 * c4) = pf[j];
-      }
-    } else {
-      const int i0 = tl * 32;
-      for (int it = wv; it < 32; it += 4)
-        for (int kk = lane; kk < k_rank; kk += 64)
-          tile[it * LDT + kk] = (tl < n_tiles && i0 + it < n_items) ? V[(size_t)(i0 + it) * k_rank + kk] : 0.f;
-    }
-  };
+  TopStager<KP, VEC, 256> stage(V, n_tiles, n_items, k_rank);
   // tile 0 -> LDS, its products (nothing to hide them behind), tile 1 -> LDS
-  load_tile(0);
-  store_tile(0);
-  load_tile(1);
+  stage.load(0);
+  stage.store(tiles, 0);
+  stage.load(1);
   __syncthreads();
   f32x16 acc[2][UB];   // [tile parity]
-#pragma unroll
-  for (int ub = 0; ub < UB; ub++)
-#pragma unroll
-    for (int e = 0; e < 16; e++) acc[0][ub][e] = 0.f;
-#pragma unroll
-  for (int t = 0; t < NK2; t++) {
-    const float b = tiles[col * LDT + 2 * t + half];
-#pragma unroll
-    for (int ub = 0; ub < UB; ub++) acc[0][ub] = __builtin_amdgcn_mfma_f32_32x32x2f32(afrag[ub][t], b, acc[0][ub], 0, 0, 0);
-  }
-  store_tile(1);
+  top_sweep(acc[0], afrag, tiles + col * LDT + half);
+  stage.store(tiles + 32 * LDT, 1);
   __syncthreads();
 
   auto body = [&](const int tl, f32x16 (&cur)[UB], f32x16 (&nxt)[UB]) {
     // cur: scores of tile tl; LDS buffer (tl + 1) & 1 holds tile tl + 1
-    load_tile(tl + 2);
+    stage.load(tl + 2);
     const float* tn = tiles + ((tl + 1) & 1) * 32 * LDT + col * LDT + half;
     const int item = tl * 32 + col;
     const bool item_ok = item < n_items;
     float4 thr4[UB][4];
-#pragma unroll
-    for (int ub = 0; ub < UB; ub++)
-#pragma unroll
-      for (int q = 0; q < 4; q++) thr4[ub][q] = *reinterpret_cast<const float4*>(sThr + uw + 32 * ub + 8 * q + 4 * half);
+    top_load_thresholds(thr4, s.thr + uw, half);
 #pragma unroll
     for (int ub = 0; ub < UB; ub++)
 #pragma unroll
@@ -799,73 +729,24 @@ __global__ __launch_bounds__(256) void top_product_pipe_kernel(const float* __re
         for (int c = 0; c < CH; c++) bq[c] = tn[2 * ((el + 1) * CH + c)];
       }
       __builtin_amdgcn_sched_barrier(0);
-      // ... and entry el of every user block of the current tile (appended unverified: topk_settle_user consults the lists)
+      // ... and entry el of every user block of the current tile
 #pragma unroll
       for (int ub = 0; ub < UB; ub++) {
         const int ul = uw + 32 * ub + (el & 3) + 8 * (el >> 2) + 4 * half;
-        const float sc = cur[ub][el];
-        const float* tq = reinterpret_cast<const float*>(&thr4[ub][el >> 2]);
-        if (item_ok && u0 + ul < n_users && sc > tq[el & 3]) {
-          const int pos = atomicAdd(&sCnt[ul], 1);
-          sVal[ul * cap + pos] = sc;
-          sIdx[ul * cap + pos] = item + item_base;
-        }
+        top_append(s, item_ok && u0 + ul < n_users, cur[ub][el], thr4, ub, el, ul, item + item_base, cap);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
     wave_sync();
-    for (int b0 = 0; b0 < UPW; b0 += 64) {
-      const int ulq = uw + b0 + lane;
-      unsigned long long over = __ballot(b0 + lane < UPW && sCnt[ulq] > settle_at);
-      if constexpr (GBUF) {
-        // (the appends are this wave's own stores: complete, and not served from a stale line of the vector cache)
-        if (over) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-      }
-      while (over) {
-        const int ul = uw + b0 + __builtin_ctzll(over);
-        over &= over - 1;
-        if constexpr (GBUF)
-          topk_settle_user_g(sVal + (size_t)ul * cap, sIdx + (size_t)ul * cap, sWrkV + wv * cap, sWrkI + wv * cap, sTmpV + wv * cap,
-                             sTmpI + wv * cap, sCnt + ul, sThr + ul, sNeed + ul, topk, nr_ptr, nr_idx, u0 + ul, excl, n_excl, lane);
-        else
-          topk_settle_user(sVal + ul * cap, sIdx + ul * cap, sTmpV + wv * cap, sTmpI + wv * cap, sCnt + ul, sThr + ul, sNeed + ul,
-                           topk, nr_ptr, nr_idx, u0 + ul, excl, n_excl, lane);
-      }
-    }
-    store_tile(tl + 2);   // into the buffer of tile tl: its last reader finished before the previous barrier
+    top_settle_wave<GBUF, UPW>(s, uw, settle_at, cap, topk, nr_ptr, nr_idx, u0, excl, n_excl, wv, lane);
+    stage.store(tiles + (tl & 1) * 32 * LDT, tl + 2);   // into the buffer of tile tl: its last reader finished before the previous barrier
     __syncthreads();
   };
   for (int tl = 0; tl < n_tiles; tl += 2) {
     body(tl, acc[0], acc[1]);
     if (tl + 1 < n_tiles) body(tl + 1, acc[1], acc[0]);
   }
-  if constexpr (GBUF) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");
-  for (int ul = uw; ul < uw + UPW; ul++) {
-    const int u = u0 + ul;
-    if (u >= n_users) break;
-    if constexpr (GBUF) {
-      // always through the work area: the last arrivals are verified / reduced there, and the emission reads LDS
-      float* wv_ = sWrkV + wv * cap;
-      int* wi_ = sWrkI + wv * cap;
-      const int n0 = sCnt[ul];
-      wave_sync();
-      for (int c = lane; c < n0; c += 64) {
-        wv_[c] = sVal[(size_t)ul * cap + c];
-        wi_[c] = sIdx[(size_t)ul * cap + c];
-      }
-      wave_sync();
-      if (n0 > sNeed[ul])
-        topk_settle_user(wv_, wi_, sTmpV + wv * cap, sTmpI + wv * cap, sCnt + ul, sThr + ul, sNeed + ul, topk, nr_ptr, nr_idx, u, excl,
-                         n_excl, lane);
-      topk_emit_user(wv_, wi_, min(sCnt[ul], topk), topk, lane, glob_mean, res + (size_t)u * topk, scores_out + (size_t)u * topk);
-      continue;
-    }
-    if (sCnt[ul] > sNeed[ul])   // arrivals that no reduction has looked at yet (the buffer never filled up again)
-      topk_settle_user(sVal + ul * cap, sIdx + ul * cap, sTmpV + wv * cap, sTmpI + wv * cap, sCnt + ul, sThr + ul, sNeed + ul, topk,
-                       nr_ptr, nr_idx, u, excl, n_excl, lane);
-    topk_emit_user(sVal + ul * cap, sIdx + ul * cap, min(sCnt[ul], topk), topk, lane, glob_mean, res + (size_t)u * topk,
-                   scores_out + (size_t)u * topk);
-  }
+  top_finish_wave<GBUF, UPW>(s, uw, cap, topk, n_users, nr_ptr, nr_idx, u0, excl, n_excl, glob_mean, res, scores_out, wv, lane);
   __syncthreads();   // (the next block of this workgroup starts from the LDS areas again)
   }
 }
@@ -940,11 +821,82 @@ __global__ __launch_bounds__(64) void top_merge_kernel(const float* __restrict__
 }  // namespace
 
 namespace {
-hipError_t launch_top_product_geo(const float* U, const float* V, int n_users, int n_items, int k_rank, int topk,
-                                  const int32_t* nr_ptr, const int32_t* nr_idx, const int32_t* excl, int n_excl,
-                                  float glob_mean, int32_t* res, float* scores, hipStream_t s, int n_slices, int slice_items,
-                                  const int* user_flags, float* gbuf = nullptr);
+// the product kernel of a plan row (VEC: rank a multiple of 4 and V 16-byte aligned -- a property of the pointers, not of the plan)
+template <int KP, bool VEC>
+const void* top_kernel_of(const TopGeo& g) {
+  if (g.family == kTopShared) return reinterpret_cast<const void*>(top_product_shared_kernel<KP, VEC>);
+  if (g.family == kTopPipe) {
+    if constexpr (KP <= 128) {
+      if (g.UB == 2 && g.gbuf) return reinterpret_cast<const void*>(top_product_pipe_kernel<KP, 2, VEC, true>);
+      if (g.UB == 2) return reinterpret_cast<const void*>(top_product_pipe_kernel<KP, 2, VEC>);
+    }
+    return reinterpret_cast<const void*>(top_product_pipe_kernel<KP, 1, VEC>);
+  }
+  if constexpr (KP <= 128) {
+    if (g.UB == 2) return reinterpret_cast<const void*>(top_product_kernel<KP, 2, VEC, 4>);
+    if (g.W == 4) return reinterpret_cast<const void*>(top_product_kernel<KP, 1, VEC, 4>);
+  }
+  if constexpr (KP >= 128) return reinterpret_cast<const void*>(top_product_kernel<KP, 1, VEC, 2>);
+  return nullptr;
 }
+template <bool VEC>
+const void* top_kernel_of(const TopGeo& g) {
+  return g.KP == 32 ? top_kernel_of<32, VEC>(g) : g.KP == 64 ? top_kernel_of<64, VEC>(g) : g.KP == 128 ? top_kernel_of<128, VEC>(g)
+                                                                                                        : top_kernel_of<256, VEC>(g);
+}
+
+struct TopArgs {   // what every launch of a call shares
+  const float* V;
+  int n_items, k_rank;
+  const int32_t *nr_ptr, *nr_idx, *excl;
+  int n_excl;
+  hipStream_t s;
+};
+// one row of the plan: U / nr_ptr / res / scores of the whole call (the row's first user is applied here), `scratch` where the
+// row keeps its candidate buffers there
+hipError_t launch_top_row(const TopLaunch& l, const TopArgs& a, const float* U, float glob_mean, int32_t* res, float* scores,
+                          const int* user_flags, float* scratch) {
+  const float* V = a.V;
+  const bool vec = a.k_rank % 4 == 0 && (reinterpret_cast<uintptr_t>(V) & 15) == 0;
+  const void* kern = vec ? top_kernel_of<true>(l.geo) : top_kernel_of<false>(l.geo);
+  if (!kern) return hipErrorInvalidValue;
+  hipError_t err;
+  if ((err = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.geo.lds)) != hipSuccess) return err;
+  U += (size_t)l.user0 * a.k_rank;
+  res += (size_t)l.user0 * l.topk;
+  scores += (size_t)l.user0 * l.topk;
+  const int32_t *nr_ptr = a.nr_ptr ? a.nr_ptr + l.user0 : nullptr, *nr_idx = a.nr_idx, *excl = a.excl;
+  int n_users = l.n_users, n_items = a.n_items, k_rank = a.k_rank, topk = l.topk, n_excl = a.n_excl, slice_items = l.slice_items;
+  float* gbuf = l.geo.gbuf ? scratch : nullptr;
+  // (the two-tile kernel takes the global candidate scratch as its last parameter; the others have no such parameter)
+  void* args[] = {&U,      &V,          &n_users, &n_items, &k_rank,      &topk,       &nr_ptr, &nr_idx,
+                  &excl,   &n_excl,     &glob_mean, &res,   &scores,      &slice_items, &user_flags, &gbuf};
+  return hipLaunchKernel(kern, dim3(l.grid_x, l.n_slices), dim3(l.geo.threads), args, l.geo.lds, a.s);
+}
+
+// the nominating pass of a plan.  scratch (nullable): what the plan was made with
+hipError_t launch_top_first(const TopPlan& p, const TopArgs& a, const float* U, int n_users, float glob_mean, int32_t* res,
+                            float* scores, float* scratch) {
+  if (!p.valid) return hipErrorInvalidValue;
+  hipError_t err = hipSuccess;
+  if (p.n_slices <= 1) {
+    for (int i = 0; i < p.n_first && err == hipSuccess; i++)
+      err = launch_top_row(p.launches[i], a, U, glob_mean, res, scores, nullptr, scratch);
+    return err;
+  }
+  const TopLaunch& sliced = p.launches[0];
+  const size_t ent = (size_t)p.n_slices * n_users * sliced.topk;
+  float* sl_scores = scratch;
+  int32_t* sl_idx = reinterpret_cast<int32_t*>(scratch + ent);
+  int* flags = reinterpret_cast<int*>(sl_idx + ent);
+  if ((err = hipMemsetAsync(flags, 0, (size_t)n_users * sizeof(int), a.s)) != hipSuccess) return err;
+  if ((err = launch_top_row(sliced, a, U, 0.f, sl_idx, sl_scores, nullptr, nullptr)) != hipSuccess) return err;
+  hipLaunchKernelGGL(top_merge_kernel, dim3(n_users), dim3(64), 0, a.s, sl_scores, sl_idx, p.n_slices, n_users, sliced.topk,
+                     glob_mean, res, scores, flags);
+  if ((err = hipGetLastError()) != hipSuccess) return err;
+  return launch_top_row(p.launches[1], a, U, glob_mean, res, scores, flags, nullptr);
+}
+}  // namespace
 
 // ---- `$predict` that orders like the reference: candidates re-scored in double ----
 // find_top_product casts both factor matrices to double before the product (R/utils.R:35-36) and top_product takes arma::mat
@@ -1129,23 +1081,17 @@ hipError_t launch_top_product_f64_t(const float* U32, const float* V32, const TF
   int32_t* res2 = reinterpret_cast<int32_t*>(cand_sc + (size_t)n_users * kc);
   float* sc2 = reinterpret_cast<float*>(res2 + (size_t)n_users * topk);
   int* flags = reinterpret_cast<int*>(sc2 + (size_t)n_users * topk);
+  const TopPlan plan = top_product_plan(n_users, n_items, rank, kc, topk, true, split_scratch != nullptr);
+  const TopArgs a{V32, n_items, rank, nr_ptr, nr_idx, excl, n_excl, s};
   hipError_t err;
-  if ((err = launch_top_product(U32, V32, n_users, n_items, rank, kc, nr_ptr, nr_idx, excl, n_excl, 0.f, cand, cand_sc, s,
-                                split_scratch)) != hipSuccess)
-    return err;
+  if ((err = launch_top_first(plan, a, U32, n_users, 0.f, cand, cand_sc, split_scratch)) != hipSuccess) return err;
   if ((err = hipMemsetAsync(flags, 0, (size_t)n_users * sizeof(int), s)) != hipSuccess) return err;
   const dim3 grid((n_users + 3) / 4);
   hipLaunchKernelGGL(top_rescore_kernel<TF>, grid, dim3(256), 0, s, U, V, n_users, rank, kc, topk, cand, glob_mean, res, scores,
                      flags, static_cast<const int*>(nullptr));
   if ((err = hipGetLastError()) != hipSuccess) return err;
   if (kc > topk) {
-    // (the tile-sharing kernel with its block loop and the global buffers where the scratch was sized for them -- an unsliced call
-    //  for more than 128 users --, else the geometry the LDS allows)
-    float* rerun_gbuf = (split_scratch && top_product_scratch_entries(n_users, n_items, kc) == 0 && top_product_wants_gbuf(n_users, rank, topk))
-                            ? split_scratch : nullptr;
-    if ((err = launch_top_product_geo(U32, V32, n_users, n_items, rank, topk, nr_ptr, nr_idx, excl, n_excl, 0.f, res2, sc2, s, 1, 0,
-                                      flags, rerun_gbuf)) != hipSuccess)
-      return err;
+    if ((err = launch_top_row(plan.launches.back(), a, U32, 0.f, res2, sc2, flags, split_scratch)) != hipSuccess) return err;
     hipLaunchKernelGGL(top_rescore_kernel<TF>, grid, dim3(256), 0, s, U, V, n_users, rank, topk, topk, res2, glob_mean, res, scores,
                        static_cast<int*>(nullptr), flags);
     if ((err = hipGetLastError()) != hipSuccess) return err;
@@ -1163,182 +1109,13 @@ hipError_t launch_top_product_f64(const float* U32, const float* V32, const doub
                                          glob_mean, res, scores, s, scratch, split_scratch);
 }
 
-// how a call is split: slices of `slice_items` items (a multiple of 32), 1 = not at all
-int top_product_slices(int n_users, int n_items, int topk, int* slice_items) {
-  *slice_items = 0;
-  // (users per workgroup of the geometry launch_top_product_geo picks for this many users; a smaller one -- when the candidate
-  //  buffers of a large k do not fit -- only means more workgroups than planned)
-  const int upw = n_users > 128 ? 256 : (n_users > 64 ? 128 : (n_users > 32 ? 64 : 32));
-  const int ublocks = (n_users + upw - 1) / upw;
-  const int n_tiles = (n_items + 31) / 32;
-  if (n_users <= 0 || ublocks >= 128 || n_tiles < 128) return 1;   // enough workgroups already, or nothing to split
-  int S = std::min(64, std::min((512 + ublocks - 1) / ublocks, n_tiles / 32));
-  if ((size_t)S * n_users * topk > ((size_t)8 << 20)) S = (int)(((size_t)8 << 20) / ((size_t)n_users * topk));
-  if (S < 2) return 1;
-  const int st = (n_tiles + S - 1) / S;
-  *slice_items = 32 * st;
-  return (n_tiles + st - 1) / st;
-}
-size_t top_product_scratch_entries(int n_users, int n_items, int topk) {
-  int si = 0;
-  const int S = top_product_slices(n_users, n_items, topk, &si);
-  return S > 1 ? (size_t)S * n_users * topk : 0;
-}
-// GBUF: does a call of this shape keep its candidate buffers in the global scratch?  Every call for more than 128 users at a rank
-// up to 128 (at 129..256 a wave holds one user block): measured faster than the LDS buffers at EVERY k -- top-100 29 -> 86
-// TFLOP/s (the LDS took 32 users per workgroup there), top-10 80 -> 96, top-1 89 -> 98 (profiles/r06/r6topk_*).
-bool top_product_wants_gbuf(int n_users, int k_rank, int topk) {
-  if (n_users <= 128 || k_rank > 128 || topk < 1 || topk > kTopMaxK) return false;
-  return padded_rank(k_rank) != 0;
-}
-// floats of scratch launch_top_product wants for this call (0 = none): the slices' lists of a call for few users, or the
-// global candidate buffers of a call for many users at a large k (at most 512 workgroup slots: longer calls go in chunks)
-size_t top_product_scratch_floats(int n_users, int n_items, int k_rank, int topk) {
-  const size_t ent = top_product_scratch_entries(n_users, n_items, topk);
-  if (ent > 0) return 2 * ent + (size_t)n_users + 16;
-  if (!top_product_wants_gbuf(n_users, k_rank, topk)) return 0;
-  const size_t blocks = ((size_t)std::min(n_users, kTopGbufChunk) + 255) / 256;
-  return blocks * 2 * 256 * (size_t)top_gcap(topk) + 16;
-}
-
-// scratch (nullable): top_product_scratch_entries floats + as many ints + n_users ints
+// scratch (nullable): top_product_plan(...).scratch_floats floats
 hipError_t launch_top_product(const float* U, const float* V, int n_users, int n_items, int k_rank, int topk,
                               const int32_t* nr_ptr, const int32_t* nr_idx, const int32_t* excl, int n_excl,
                               float glob_mean, int32_t* res, float* scores, hipStream_t s, float* scratch) {
-  int slice_items = 0;
-  const int S = scratch ? top_product_slices(n_users, n_items, topk, &slice_items) : 1;
-  if (S <= 1) {
-    if (scratch && top_product_wants_gbuf(n_users, k_rank, topk)) {
-      // the candidate buffers in the scratch: chunks of users, one after the other on the stream, share its 512 slots
-      for (int c0 = 0; c0 < n_users; c0 += kTopGbufChunk) {
-        const int nu = std::min(kTopGbufChunk, n_users - c0);
-        const hipError_t e = launch_top_product_geo(U + (size_t)c0 * k_rank, V, nu, n_items, k_rank, topk, nr_ptr ? nr_ptr + c0 : nullptr,
-                                                    nr_idx, excl, n_excl, glob_mean, res + (size_t)c0 * topk, scores + (size_t)c0 * topk, s,
-                                                    1, 0, nullptr, scratch);
-        if (e != hipSuccess) return e;
-      }
-      return hipSuccess;
-    }
-    return launch_top_product_geo(U, V, n_users, n_items, k_rank, topk, nr_ptr, nr_idx, excl, n_excl, glob_mean, res, scores, s, 1,
-                                  0, nullptr);
-  }
-  const size_t ent = (size_t)S * n_users * topk;
-  float* sl_scores = scratch;
-  int32_t* sl_idx = reinterpret_cast<int32_t*>(scratch + ent);
-  int* flags = reinterpret_cast<int*>(sl_idx + ent);
-  hipError_t err;
-  if ((err = hipMemsetAsync(flags, 0, (size_t)n_users * sizeof(int), s)) != hipSuccess) return err;
-  if ((err = launch_top_product_geo(U, V, n_users, n_items, k_rank, topk, nr_ptr, nr_idx, excl, n_excl, 0.f, sl_idx, sl_scores, s, S,
-                                    slice_items, nullptr)) != hipSuccess)
-    return err;
-  hipLaunchKernelGGL(top_merge_kernel, dim3(n_users), dim3(64), 0, s, sl_scores, sl_idx, S, n_users, topk, glob_mean, res, scores,
-                     flags);
-  if ((err = hipGetLastError()) != hipSuccess) return err;
-  return launch_top_product_geo(U, V, n_users, n_items, k_rank, topk, nr_ptr, nr_idx, excl, n_excl, glob_mean, res, scores, s, 1, 0,
-                                flags);
+  const TopPlan plan = top_product_plan(n_users, n_items, k_rank, topk, topk, false, scratch != nullptr);
+  return launch_top_first(plan, TopArgs{V, n_items, k_rank, nr_ptr, nr_idx, excl, n_excl, s}, U, n_users, glob_mean, res, scores,
+                          scratch);
 }
-
-namespace {
-hipError_t launch_top_product_geo(const float* U, const float* V, int n_users, int n_items, int k_rank, int topk,
-                                  const int32_t* nr_ptr, const int32_t* nr_idx, const int32_t* excl, int n_excl,
-                                  float glob_mean, int32_t* res, float* scores, hipStream_t s, int n_slices, int slice_items,
-                                  const int* user_flags, float* gbuf) {
-  const int KP = (k_rank > 128 && k_rank <= 256) ? 256 : padded_rank(k_rank);   // (ranks 129..256: one user block per wave)
-  if (!KP || topk < 1 || topk > kTopMaxK) return hipErrorInvalidValue;
-  if (n_users <= 0) return hipSuccess;
-  const bool vec = k_rank % 4 == 0 && (reinterpret_cast<uintptr_t>(V) & 15) == 0;
-  constexpr size_t kLdsMax = 156 * 1024;
-  hipError_t err;
-#define RSP_TOPK_GO(KERN, LDS, USERS, THREADS)                                                               \
-  {                                                                                                          \
-    auto kern = KERN;                                                                                        \
-    const size_t lds = LDS;                                                                                  \
-    if ((err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   (int)lds)) != hipSuccess)                                                 \
-      return err;                                                                                            \
-    const int grid = (n_users + (USERS) - 1) / (USERS);                                                      \
-    hipLaunchKernelGGL(kern, dim3(grid, n_slices), dim3(THREADS), lds, s, U, V, n_users, n_items, k_rank, topk, nr_ptr, \
-                       nr_idx, excl, n_excl, glob_mean, res, scores, slice_items, user_flags);               \
-    return hipGetLastError();                                                                                \
-  }
-  // (the two-tile kernel takes the global candidate scratch as well)
-#define RSP_TOPK_GO_P(KERN, LDS, USERS, THREADS, GB)                                                         \
-  {                                                                                                          \
-    auto kern = KERN;                                                                                        \
-    const size_t lds = LDS;                                                                                  \
-    if ((err = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   (int)lds)) != hipSuccess)                                                 \
-      return err;                                                                                            \
-    const int grid = std::min((n_users + (USERS) - 1) / (USERS), user_flags ? 512 : 0x7fffffff);  /* (see the kernel's block loop) */ \
-    hipLaunchKernelGGL(kern, dim3(grid, n_slices), dim3(THREADS), lds, s, U, V, n_users, n_items, k_rank, topk, nr_ptr, \
-                       nr_idx, excl, n_excl, glob_mean, res, scores, slice_items, user_flags, GB);           \
-    return hipGetLastError();                                                                                \
-  }
-  // GBUF: the launcher hands a scratch when the call is unsliced; taken where the 256-user buffers do not fit the LDS
-  // (a flagged launch has at most 512 workgroups = scratch slots, whatever the number of users)
-  const bool gbuf_now = gbuf && n_slices == 1 && n_users > 128 && (n_users <= kTopGbufChunk || user_flags) && top_product_wants_gbuf(n_users, k_rank, topk);
-  // Geometry, best first: the four waves share the item tile and own 64 / 32 users each (256 / 128 users per workgroup:
-  // every item vector is read once per that many users) -- with two tiles resident and the epilogue hidden behind the next
-  // tile's matrix instructions where the LDS allows it; then one tile per wave against 64 / 32 users; then the same on
-  // two waves (half the tiles and half the per-round candidates in LDS: top-k up to 256 at rank 128).  What decides is
-  // whether the users' candidate buffers fit the LDS next to the tiles, and that there are users enough for the block.
-#define RSP_TOPK(KPV)                                                                                        \
-  if (KP == KPV) {                                                                                           \
-    if (gbuf_now) {                                                                                          \
-      if (vec) RSP_TOPK_GO_P((top_product_pipe_kernel<KPV, 2, true, true>), (TopPipeSmem<KPV, 2>::gbytes(topk)), 256, 256, gbuf) \
-      else RSP_TOPK_GO_P((top_product_pipe_kernel<KPV, 2, false, true>), (TopPipeSmem<KPV, 2>::gbytes(topk)), 256, 256, gbuf)     \
-    }                                                                                                        \
-    if (TopPipeSmem<KPV, 2>::bytes(topk) <= kLdsMax && n_users > 128) {                                      \
-      if (vec) RSP_TOPK_GO_P((top_product_pipe_kernel<KPV, 2, true>), (TopPipeSmem<KPV, 2>::bytes(topk)), 256, 256, nullptr) \
-      else RSP_TOPK_GO_P((top_product_pipe_kernel<KPV, 2, false>), (TopPipeSmem<KPV, 2>::bytes(topk)), 256, 256, nullptr)     \
-    }                                                                                                        \
-    if (TopPipeSmem<KPV, 1>::bytes(topk) <= kLdsMax && n_users > 64) {                                       \
-      if (vec) RSP_TOPK_GO_P((top_product_pipe_kernel<KPV, 1, true>), (TopPipeSmem<KPV, 1>::bytes(topk)), 128, 256, nullptr) \
-      else RSP_TOPK_GO_P((top_product_pipe_kernel<KPV, 1, false>), (TopPipeSmem<KPV, 1>::bytes(topk)), 128, 256, nullptr)     \
-    }                                                                                                        \
-    if (TopSharedSmem<KPV, 2>::bytes(topk) <= kLdsMax && n_users > 128) {                                    \
-      if (vec) RSP_TOPK_GO((top_product_shared_kernel<KPV, 2, true>), (TopSharedSmem<KPV, 2>::bytes(topk)), 256, 256) \
-      else RSP_TOPK_GO((top_product_shared_kernel<KPV, 2, false>), (TopSharedSmem<KPV, 2>::bytes(topk)), 256, 256)     \
-    }                                                                                                        \
-    if (TopSharedSmem<KPV, 1>::bytes(topk) <= kLdsMax && n_users > 64) {                                     \
-      if (vec) RSP_TOPK_GO((top_product_shared_kernel<KPV, 1, true>), (TopSharedSmem<KPV, 1>::bytes(topk)), 128, 256) \
-      else RSP_TOPK_GO((top_product_shared_kernel<KPV, 1, false>), (TopSharedSmem<KPV, 1>::bytes(topk)), 128, 256)     \
-    }                                                                                                        \
-    if (TopSmem<KPV, 2, 4>::bytes(topk) <= kLdsMax && n_users > 32) {                                        \
-      if (vec) RSP_TOPK_GO((top_product_kernel<KPV, 2, true, 4>), (TopSmem<KPV, 2, 4>::bytes(topk)), 64, 256) \
-      else RSP_TOPK_GO((top_product_kernel<KPV, 2, false, 4>), (TopSmem<KPV, 2, 4>::bytes(topk)), 64, 256)    \
-    }                                                                                                        \
-    if (TopSmem<KPV, 1, 4>::bytes(topk) <= kLdsMax) {                                                        \
-      if (vec) RSP_TOPK_GO((top_product_kernel<KPV, 1, true, 4>), (TopSmem<KPV, 1, 4>::bytes(topk)), 32, 256) \
-      else RSP_TOPK_GO((top_product_kernel<KPV, 1, false, 4>), (TopSmem<KPV, 1, 4>::bytes(topk)), 32, 256)    \
-    }                                                                                                        \
-    if (vec) RSP_TOPK_GO((top_product_kernel<KPV, 1, true, 2>), (TopSmem<KPV, 1, 2>::bytes(topk)), 32, 128)  \
-    else RSP_TOPK_GO((top_product_kernel<KPV, 1, false, 2>), (TopSmem<KPV, 1, 2>::bytes(topk)), 32, 128)     \
-  }
-  RSP_TOPK(32)
-  RSP_TOPK(64)
-  RSP_TOPK(128)
-  if (KP == 256) {   // the user block of a wave is 128 registers at this rank: one block per wave in every geometry
-    if (TopPipeSmem<256, 1>::bytes(topk) <= kLdsMax && n_users > 64) {
-      if (vec) RSP_TOPK_GO_P((top_product_pipe_kernel<256, 1, true>), (TopPipeSmem<256, 1>::bytes(topk)), 128, 256, nullptr)
-      else RSP_TOPK_GO_P((top_product_pipe_kernel<256, 1, false>), (TopPipeSmem<256, 1>::bytes(topk)), 128, 256, nullptr)
-    }
-    if (TopSharedSmem<256, 1>::bytes(topk) <= kLdsMax && n_users > 64) {
-      if (vec) RSP_TOPK_GO((top_product_shared_kernel<256, 1, true>), (TopSharedSmem<256, 1>::bytes(topk)), 128, 256)
-      else RSP_TOPK_GO((top_product_shared_kernel<256, 1, false>), (TopSharedSmem<256, 1>::bytes(topk)), 128, 256)
-    }
-    if (TopSmem<256, 1, 4>::bytes(topk) <= kLdsMax) {
-      if (vec) RSP_TOPK_GO((top_product_kernel<256, 1, true, 4>), (TopSmem<256, 1, 4>::bytes(topk)), 32, 256)
-      else RSP_TOPK_GO((top_product_kernel<256, 1, false, 4>), (TopSmem<256, 1, 4>::bytes(topk)), 32, 256)
-    }
-    if (vec) RSP_TOPK_GO((top_product_kernel<256, 1, true, 2>), (TopSmem<256, 1, 2>::bytes(topk)), 32, 128)
-    else RSP_TOPK_GO((top_product_kernel<256, 1, false, 2>), (TopSmem<256, 1, 2>::bytes(topk)), 32, 128)
-  }
-#undef RSP_TOPK
-#undef RSP_TOPK_GO
-#undef RSP_TOPK_GO_P
-  return hipErrorInvalidValue;
-}
-}  // namespace
 
 }  // namespace rsparse_hip

@@ -69,16 +69,52 @@ def _hip_top_product(x, y, k, nr=None, exclude=(), glob_mean=0.0):
     return res, sc
 
 
+def _plan(nr, nc, rank, k, rescore=1, extra=-1):
+    """the launches of a call of this shape (rsparse_hip_top_product_plan; rescore = 1, extra = -1: the host form above), one dict
+    of strings per launch"""
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(1 << 16)
+    _lib.check(lib.rsparse_hip_top_product_plan(nr, nc, rank, k, extra, rescore, buf, len(buf)))
+    return [dict(kv.split("=") for kv in line.split()) for line in buf.value.decode().splitlines()]
+
+
+def _full_geometries(nr, nc, rank, k):
+    """"family KP UB W buffers" of every launch of the host form that is not a re-run for flagged users"""
+    return {" ".join(l[f] for f in ("family", "KP", "UB", "W", "buffers")) for l in _plan(nr, nc, rank, k) if l["flagged"] == "0"}
+
+
+def test_plan_entry_describes_the_launches():
+    """No device call: the plan is host arithmetic.  The host form of (128, 700, 20000, 100) nominates kc = 125 per user over
+    19 item slices on the tile-per-wave kernel, re-runs flagged users of the merge unsliced, and re-runs the users the re-scoring
+    flags at k = 100 on the one-tile shared kernel; the device form of more than 131072 users goes in chunks."""
+    p = _plan(700, 20000, 128, 100)
+    assert [(l["family"], l["k"], l["grid"], l["flagged"]) for l in p] == [("per_wave", "125", "22x19", "0"),
+                                                                           ("per_wave", "125", "22x1", "1"),
+                                                                           ("shared", "100", "6x1", "1")]
+    assert p[0]["scratch_floats"] == str(2 * 19 * 700 * 125 + 700 + 16) and p[0]["slice_items"] == str(32 * 33)
+    p = _plan(131072 + 200, 4200, 32, 60, rescore=0)
+    assert [(l["user0"], l["n_users"], l["buffers"], l["grid"]) for l in p] == [("0", "131072", "global", "512x1"),
+                                                                                ("131072", "200", "global", "1x1")]
+    assert p[0]["scratch_floats"] == str(512 * 2 * 256 * 156 + 16) and p[0]["lds"] == str((2 * 32 * 36 + 3 * 256) * 4 + 64 + 4 * 156 * 16)
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(8)
+    assert lib.rsparse_hip_top_product_plan(10, 10, 8, 300, -1, 1, buf, 8) == _lib.ERR_UNSUPPORTED     # (the large-k path)
+    assert lib.rsparse_hip_top_product_plan(10, 10, 8, 3, -1, 1, buf, 8) == _lib.ERR_INVALID           # (buffer too small)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("rank,nr,nc,k", [(10, 100, 50, 10), (16, 70, 3001, 25), (64, 33, 777, 7), (128, 129, 5000, 100),
                                           (20, 5, 40, 12),
-                                          # round 4: every launch geometry of wrmf_topk.hip -- four waves sharing the item tile
-                                          # with 256 / 128 users per workgroup, one tile per wave with 64 / 32, two waves with
-                                          # 32 (k up to 256 at rank 128) -- and the scalar staging path (rank % 4 != 0)
+                                          # what these reach (the plan entry; kc = k + max(8, k / 4) candidates are nominated, the
+                                          # re-run at k is flagged): (128, 300, 5000, 10) the two-tile kernel with 256 users per
+                                          # workgroup over 4 item slices; (128, 100, 3000, 100) and (128, 40, 1000, 120) a tile per
+                                          # wave with 32 users; (128, 70, 4000, 200) and (128, 33, 2000, 256) the same on two waves;
+                                          # (64, 300, 2000, 256) and (30, 140, 900, 5) the candidate buffers in global memory, the
+                                          # latter with scalar staging (rank % 4 != 0).  Every geometry: test_hip_every_geometry
                                           (128, 300, 5000, 10), (128, 100, 3000, 100), (128, 70, 4000, 200),
                                           (64, 300, 2000, 256), (128, 33, 2000, 256), (30, 140, 900, 5), (128, 40, 1000, 120),
                                           # few users over many items: the items are split over the workgroups and the slices'
-                                          # lists merged (one user: 64 slices; 1000 users: 16)
+                                          # lists merged (one user over 70000 items: 63 slices; 1000 users over 9000: 8)
                                           (128, 1, 70000, 10), (64, 3, 20000, 100), (128, 1000, 9000, 10), (16, 37, 5000, 256)])
 def test_hip_matches_oracle(rank, nr, nc, k):
     rng = np.random.default_rng(rank + nr)
@@ -115,18 +151,21 @@ def test_hip_ties_and_na_fill():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("k", [2, 7, 40])
+@pytest.mark.parametrize("k", [2, 7, 40, 88])
 def test_hip_tied_scores_follow_the_heap(k):
     """Integer-valued factors: every user has many items tied at its k-th score, interleaved with larger scores; which of
     them survive depends on the arrival order exactly as in the reference's heap (the device replays the arrivals of a
-    round through the heap when, and only when, there are more candidates at the k-th score than places)."""
+    round through the heap when, and only when, there are more candidates at the k-th score than places).  k = 88 at 70 users
+    (110 candidates) is the one-tile shared kernel: its settle and replay code with ties."""
     one = np.ones((1, 1))
     for sc, kk in (([1.0, 1.0, 5.0], 2), ([1.0, 5.0, 1.0], 2)):
         ref_i, ref_s = O.top_product(one, np.array([sc]), kk)
         got_i, got_s = _hip_top_product(one, np.array([sc]), kk)
         assert np.array_equal(got_i, ref_i) and np.array_equal(got_s, ref_s)
     rng = np.random.default_rng(100 + k)
-    for n_users in (70, 300, 40):      # (the tile-sharing kernel with 128 / 256 users per workgroup, the tile-per-wave kernel)
+    if k == 88:
+        assert _full_geometries(70, 1500, 4, k) == {"shared 32 1 4 lds"}
+    for n_users in (70, 300, 40):      # (the tile-sharing kernels with 128 users per workgroup, the global buffers, a tile per wave)
         x = rng.integers(0, 3, (n_users, 4)).astype(np.float64)
         y = rng.integers(0, 3, (4, 1500)).astype(np.float64)          # scores are small integers: ties everywhere
         nr = sp.random(n_users, 1500, density=0.02, format="csr", random_state=np.random.RandomState(k))
@@ -185,16 +224,66 @@ def test_hip_orders_like_the_double_product(rank, nr, nc, k):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("rank,nr,nc,k", [(128, 700, 20000, 100), (64, 520, 9000, 60), (32, 300, 7000, 200)])
+@pytest.mark.parametrize("rank,nr,nc,k", [(128, 700, 20000, 100), (64, 520, 9000, 60), (32, 300, 7000, 200), (128, 700, 4000, 100)])
 def test_hip_large_k_many_users_candidates_in_global_memory(rank, nr, nc, k):
-    """Many users at a k whose candidate buffers do not fit the LDS next to two item tiles: the tile-sharing kernel keeps them in
-    a global scratch and settles a user once per batch of arrivals (wrmf_topk.hip GBUF).  Several workgroups, the last one
-    partly filled, hundreds of tiles, exclusion lists; indices equal to the oracle's."""
+    """Many users at a large k.  An unsliced call for more than 128 users -- (128, 700, 4000, 100): fewer than 4096 items -- keeps
+    the candidate buffers in a global scratch and settles a user once per batch of arrivals (wrmf_topk.hip GBUF): three workgroups,
+    the last one partly filled, 125 tiles, exclusion lists.  The three larger shapes are split over the items since slicing came
+    (19 / 8 / 6 slices) and run the LDS geometries a sliced call takes: a tile per wave, the two-tile kernel with 128 users, a tile
+    per wave.  Indices equal to the oracle's."""
+    assert ("pipe %d 2 4 global" % rank in _full_geometries(nr, nc, rank, k)) == (nc < 4096)
     rng = np.random.default_rng(11 * rank + k)
     x = rng.standard_normal((nr, rank))
     y = rng.standard_normal((rank, nc))
     notrec = sp.random(nr, nc, density=0.01, random_state=9, format="csr")
     for args in (dict(), dict(nr=notrec, exclude=[5, 6, nc - 1], glob_mean=-1.25)):
+        ref_i, ref_s = O.top_product(x, y, k, *(None, None) if "nr" not in args else (notrec.indptr, notrec.indices),
+                                     exclude=args.get("exclude", ()), glob_mean=args.get("glob_mean", 0.0))
+        got_i, got_s = _hip_top_product(x, y, k, **args)
+        assert np.array_equal(got_i, ref_i)
+        assert np.allclose(got_s, ref_s, rtol=1e-12, atol=1e-12)
+
+
+# (rank, users, items, k) -> the geometry of the nominating pass, "family KP UB W buffers".  Every instantiation the plan's table can
+# select, with 16-byte staging (ranks 32 / 64 / 128 / 160) and with scalar staging (30 / 62 / 126 / 158), at the smallest shape at
+# which it exists: one workgroup (two at rank > 128) with a partly filled last user block, 47 item tiles, or 129 tiles in 4 slices.
+def _geometry_cases():
+    cases = []
+    for r in (32, 30, 64, 62, 128, 126, 160, 158):
+        kp = 32 if r <= 32 else 64 if r <= 64 else 128 if r <= 128 else 256
+        if kp <= 128:
+            cases += [(r, 130, 1500, 1, "pipe %d 2 4 global" % kp), (r, 130, 4100, 1, "pipe %d 2 4 lds" % kp),
+                      (r, 40, 1500, 1, "per_wave %d 2 4 lds" % kp), (r, 20, 1500, 1, "per_wave %d 1 4 lds" % kp)]
+        cases += [(r, 70, 1500, 1, "pipe %d 1 4 lds" % kp), (r, 70, 1500, {32: 88, 64: 81, 128: 68, 256: 43}[kp], "shared %d 1 4 lds" % kp)]
+        if kp >= 128:
+            cases += [(r, 20, 1500, 152 if kp == 128 else 1, "per_wave %d 1 2 lds" % kp)]
+    # k at the upper edge of a band: the largest candidate buffers that fit the LDS next to the tiles (or, global, the longest)
+    cases += [(128, 130, 4100, 16, "pipe 128 2 4 lds"), (128, 70, 1500, 67, "pipe 128 1 4 lds"), (128, 70, 1500, 80, "shared 128 1 4 lds"),
+              (128, 40, 1500, 28, "per_wave 128 2 4 lds"), (128, 20, 1500, 151, "per_wave 128 1 4 lds"),
+              (160, 70, 1500, 42, "pipe 256 1 4 lds"), (160, 70, 1500, 67, "shared 256 1 4 lds"),
+              (128, 130, 1500, 256, "pipe 128 2 4 global"), (160, 20, 1500, 205, "per_wave 256 1 2 lds")]
+    return cases
+
+
+def test_geometry_cases_cover_every_instantiation():
+    """44 product kernels: per rank class up to 128 the two-tile kernel with 2 (global / LDS) and 1 user blocks per wave, the shared
+    kernel, a tile per wave with 2 and 1 blocks; two waves at 128 and 256; at 256 one block per wave only; each with and without
+    16-byte staging."""
+    assert len({(geo, r % 4 == 0) for r, _, _, _, geo in _geometry_cases()}) == 44
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rank,nr,nc,k,geometry", _geometry_cases())
+def test_hip_every_geometry(rank, nr, nc, k, geometry):
+    """Every kernel the plan can select runs a full (unflagged) launch -- asserted through the plan entry -- and orders like the
+    double product: indices equal to the oracle's everywhere, without and with a not_recommend matrix, exclusions and a global
+    mean."""
+    assert _full_geometries(nr, nc, rank, k) == {geometry}
+    rng = np.random.default_rng(7 * rank + k + nr)
+    x = rng.standard_normal((nr, rank))
+    y = rng.standard_normal((rank, nc))
+    notrec = sp.random(nr, nc, density=0.03, random_state=5, format="csr")
+    for args in (dict(), dict(nr=notrec, exclude=[2, 9, nc], glob_mean=3.5)):
         ref_i, ref_s = O.top_product(x, y, k, *(None, None) if "nr" not in args else (notrec.indptr, notrec.indices),
                                      exclude=args.get("exclude", ()), glob_mean=args.get("glob_mean", 0.0))
         got_i, got_s = _hip_top_product(x, y, k, **args)
