@@ -868,6 +868,68 @@ int rsparse_hip_knn_recommend_weighted(const int32_t* x_p, const int32_t* x_j, c
                                        const int32_t* neighbors, const uint32_t* q, int K, const int32_t* nr_p, const int32_t* nr_j,
                                        const int32_t* exclude, int n_exclude, int k, int32_t* res, int64_t* scores);
 
+/* ItemKNN under the evaluation protocols of the factor models: the score at given cells, the lists within per-row candidates,
+ * and where held-out items stand among all items.  Each entry scores the n_rows rows of the pattern (d_xp, d_xj) with the
+ * weights d_xv (nullable: all ones) under d_neighbors / d_q exactly as rsparse_hip_knn_recommend_weighted_device does -- the same
+ * scatter into the same dense rows, ws_rows with the same meaning -- and differs in what reads a row.  Its own pattern (d_*_p:
+ * n_rows + 1 slots, d_*_j: 0-based columns) lies over the same rows; all row pointers are ABSOLUTE slots into their column
+ * array, so that a caller can pass a slice of the pointers with the whole column array, and an output with one element per
+ * stored position parallels the column array (element t belongs to column slot t).  Integers only on the device, integer
+ * atomics only: a repeated call returns the same bits; the workspace is all zeros again when the enqueued work is done.
+ * Each reads d_xp back (waits for `stream` once), then enqueues without synchronisation.
+ * Refusals, all before a device is touched: NULL where a pointer is required, a negative dimension, K < 1, k < 1, ws_rows < 0,
+ * nr_p without nr_j, n_exclude < 0 (or > 0 without d_excl0) -> ERR_INVALID; K > RSPARSE_HIP_KNN_MAX_NEIGHBORS,
+ * k > RSPARSE_HIP_KNN_MAX_TOPK -> ERR_UNSUPPORTED; n_rows == 0 -> OK.  Row pointers read back that are negative or decrease ->
+ * ERR_INVALID.
+ *
+ * rsparse_hip_knn_score_pairs_device: d_scores[t] = score_row(t)[d_pairs_j[t]] (int64) for every stored position t of the pairs
+ * pattern; nothing is masked; a column outside [0, n_items) gives 0; j need not be sorted and may repeat.  Also reads d_pairs_p
+ * back. */
+int rsparse_hip_knn_score_pairs_device(const int32_t* d_xp, const int32_t* d_xj, const uint32_t* d_xv, int n_rows, int n_items,
+                                       const int32_t* d_neighbors, const uint32_t* d_q, int K, const int32_t* d_pairs_p,
+                                       const int32_t* d_pairs_j, int64_t ws_rows, int64_t* d_scores, void* stream);
+
+/* The k best of every row's candidates: the admissible ones are the candidate columns inside [0, n_items) that are neither in
+ * the row's not_recommend entries nor in d_excl0; order as rsparse_hip_knn_recommend_device -- score descending, equal scores to
+ * the SMALLER item (not the heap's rule of rsparse_hip_top_candidates_device) --, candidates of score 0 are ranked, a list is
+ * shorter than k only when fewer than k candidates are admissible.  d_items / d_scores as there: n_rows x k row-major, 1-based
+ * with INT32_MIN, int64 sums with 0 in the padding.  Candidate columns are unique within a row (a repeated one may be listed
+ * twice).  A row of up to RSPARSE_HIP_KNN_LDS_CAND candidates costs, behind the scatter, work in proportion to its candidates;
+ * a longer one -- up to the whole catalogue -- is restricted to its candidates in the dense row and selected as
+ * rsparse_hip_knn_recommend_device selects.  1 <= k <= RSPARSE_HIP_KNN_MAX_TOPK.  Also reads d_cand_p back. */
+int rsparse_hip_knn_top_candidates_device(const int32_t* d_xp, const int32_t* d_xj, const uint32_t* d_xv, int n_rows, int n_items,
+                                          const int32_t* d_neighbors, const uint32_t* d_q, int K, const int32_t* d_cand_p,
+                                          const int32_t* d_cand_j, const int32_t* d_nr_p, const int32_t* d_nr_j, const int32_t* d_excl0,
+                                          int n_exclude, int k, int64_t ws_rows, int32_t* d_items, int64_t* d_scores, void* stream);
+
+/* above / tied / n_adm as rsparse_hip_held_out_ranks_device defines them, with s the integer score: A_u = the items outside the
+ * row's not_recommend entries and outside d_excl0, d_n_adm[u] = |A_u|; for a stored entry (u, h) of actual, above = #{j in A_u :
+ * s_j > s_h}, tied = #{j in A_u, j != h : s_j == s_h}; an entry outside A_u (or outside [0, n_items)) gets -1 / -1 and takes no
+ * part.  d_above / d_tied: int32, one per stored entry; d_n_adm: int32, one per row.  A row's entries are counted
+ * RSPARSE_HIP_RANKS_BATCH at a time, one pass over the row's n_items cells each; the entries need not be sorted and may repeat.
+ * rsparse_hip_rank_summary_device turns the counts into mpr / auc / mrr.  A valid d_actual_p is a precondition. */
+int rsparse_hip_knn_held_out_ranks_device(const int32_t* d_xp, const int32_t* d_xj, const uint32_t* d_xv, int n_rows, int n_items,
+                                          const int32_t* d_neighbors, const uint32_t* d_q, int K, const int32_t* d_actual_p,
+                                          const int32_t* d_actual_j, const int32_t* d_nr_p, const int32_t* d_nr_j, const int32_t* d_excl0,
+                                          int n_exclude, int64_t ws_rows, int32_t* d_above, int32_t* d_tied, int32_t* d_n_adm,
+                                          void* stream);
+
+/* host-array forms, with the conventions of rsparse_hip_knn_recommend_weighted (x_p / x_j / x_v, neighbors and q column-major
+ * with 1-based neighbours, nr_p / nr_j nullable, exclude 1-based) and all of its refusals.  cand_p / cand_j: dgRMatrix slots over
+ * the rows of x, 0-based; cand_p[0] != 0, a decreasing cand_p, a candidate column outside [0, n_items) or a row that is not
+ * strictly ascending -> ERR_INVALID, before a device is touched.  res / scores: n_rows x k column-major. */
+int rsparse_hip_knn_top_candidates(const int32_t* x_p, const int32_t* x_j, const uint32_t* x_v, int n_rows, int n_items,
+                                   const int32_t* neighbors, const uint32_t* q, int K, const int32_t* cand_p, const int32_t* cand_j,
+                                   const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude, int n_exclude, int k, int32_t* res,
+                                   int64_t* scores);
+/* actual_p / actual_j: dgRMatrix slots over the rows of x; actual_p[0] != 0, a decreasing actual_p, columns not strictly
+ * ascending within a row -> ERR_INVALID (a column outside the items is an inadmissible entry, not a refusal).  above / tied: one
+ * int32 per stored entry; n_adm: n_rows int32. */
+int rsparse_hip_knn_held_out_ranks(const int32_t* x_p, const int32_t* x_j, const uint32_t* x_v, int n_rows, int n_items,
+                                   const int32_t* neighbors, const uint32_t* q, int K, const int32_t* actual_p, const int32_t* actual_j,
+                                   const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude, int n_exclude, int32_t* above,
+                                   int32_t* tied, int32_t* n_adm);
+
 /* ------------------------------------------------------------------------------------------------
  * why this item: per-item contributions to a score (Hu, Koren and Volinsky, section 5; `explain` of the `implicit` library)
  * ---------------------------------------------------------------------------------------------- */

@@ -42,7 +42,7 @@ def __getattr__(name):
         from .puresvd import PureSVD
         return PureSVD
     if name in ("ItemKNN", "cooccurrence_reference", "knn_recommend_reference", "quantize_values", "weighted_operands",
-                "weighted_cooccurrence_reference"):
+                "weighted_cooccurrence_reference", "knn_score_pairs_reference", "knn_candidates_reference", "knn_ranks_reference"):
         from . import itemknn
         return getattr(itemknn, name)
     if name == "metrics":

@@ -122,6 +122,15 @@ SIGNATURES = {
     "rsparse_hip_cooc_neighbors_weighted": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_dbl, _c_int, _vp, _vp]),
     "rsparse_hip_knn_recommend_weighted": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp,
                                                     _vp]),
+    "rsparse_hip_knn_score_pairs_device": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_i64, _vp, _vp]),
+    "rsparse_hip_knn_top_candidates_device": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int,
+                                                       _c_int, _c_i64, _vp, _vp, _vp]),
+    "rsparse_hip_knn_held_out_ranks_device": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int,
+                                                       _c_i64, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_knn_top_candidates": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int,
+                                                _vp, _vp]),
+    "rsparse_hip_knn_held_out_ranks": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp,
+                                                _vp]),
     "rsparse_hip_top_candidates_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl, _vp,
                                                    _vp, _vp]),
     "rsparse_hip_top_candidates_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl,

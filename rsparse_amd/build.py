@@ -69,7 +69,9 @@ NO_SPILL = {"wrmf_cgq.hip": ("14als_cgq_kernelILi128ELi24ELi4ELi4E",),
             # integer-only: a few indices per lane in the scatter, two keys and their indices per lane in the select's sort;
             # scratch would mean the key lambda or the sort's exchange went to memory (the weighted forms, whose
             # key adds one double product and sum, are held to the same: 3.29)
-            "wrmf_itemknn.hip": ("knn_scatter_kernel", "knn_mask_kernel", "knn_select_kernel"),
+            # the evaluation consumers (3.30) hold a cell, its lower bound and two run counters per lane
+            "wrmf_itemknn.hip": ("knn_scatter_kernel", "knn_mask_kernel", "knn_select_kernel", "knn_gather_kernel", "knn_cand_select_kernel",
+                                 "knn_ranks_kernel"),
             "wrmf_split.hip": ("split_count_wave_kernel", "split_count_team_kernel", "split_write_wave_kernel", "split_write_team_kernel")}
 RESOURCE_FLAG = "-Rpass-analysis=kernel-resource-usage"
 

@@ -228,6 +228,8 @@ class Confidence:
         mom = None
         if im is not None:
             st["item_count"] = torch.diff(im[0])
+        else:   # (no item side to read them off: counted from the rows' columns, so that the state is the numpy fit's)
+            st["item_count"] = torch.bincount(um[1].to(torch.int64), minlength=int(n_cols))
         if kind in ("tfidf", "bm25"):
             st["item_table"] = be.confidence_table("idf", n_cols, p=im[0], a=float(n_rows))
         if kind == "bm25":

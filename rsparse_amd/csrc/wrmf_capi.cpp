@@ -1512,6 +1512,79 @@ int rsparse_hip_knn_recommend_device(const int32_t* d_xp, const int32_t* d_xj, i
                                                    n_exclude, k, ws_rows, d_items, d_scores, stream);
 }
 
+namespace {
+// what the evaluation entries do between their argument checks and their launches: x's row pointers on the host, the workspace
+static int knn_rows_begin(const int32_t* d_xp, int n_rows, int n_items, int64_t ws_rows, std::vector<int32_t>& h_xp, int64_t& rows,
+                          unsigned long long*& ws, hipStream_t s) {
+  if (int rc = fetch_row_pointers(d_xp, (size_t)n_rows, h_xp, s, "x_p")) return rc;
+  void* buf = nullptr;
+  if (int rc = knn_workspace(n_rows, (size_t)n_items * sizeof(uint64_t), ws_rows, rows, buf, s)) return rc;
+  ws = static_cast<unsigned long long*>(buf);
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+
+int rsparse_hip_knn_score_pairs_device(const int32_t* d_xp, const int32_t* d_xj, const uint32_t* d_xv, int n_rows, int n_items,
+                                       const int32_t* d_neighbors, const uint32_t* d_q, int K, const int32_t* d_pairs_p,
+                                       const int32_t* d_pairs_j, int64_t ws_rows, int64_t* d_scores, void* stream) {
+  int rc = knn_recommend_args(!d_xp || !d_xj || !d_neighbors || !d_q || !d_pairs_p || !d_pairs_j || !d_scores, n_rows, n_items, K, nullptr,
+                              nullptr, nullptr, 0, 1, ws_rows);
+  if (rc || n_rows == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> h_xp, h_pp;
+  if ((rc = fetch_row_pointers(d_pairs_p, (size_t)n_rows, h_pp, s, "pairs_p"))) return rc;
+  int64_t rows = 0;
+  unsigned long long* ws = nullptr;
+  if ((rc = knn_rows_begin(d_xp, n_rows, n_items, ws_rows, h_xp, rows, ws, s))) return rc;
+  hipError_t e = launch_knn_score_pairs(d_xp, d_xj, d_xv, n_rows, n_items, h_xp.data(), d_neighbors, d_q, K, d_pairs_p, d_pairs_j,
+                                        h_pp.data(), rows, ws, reinterpret_cast<long long*>(d_scores), s);
+  if (e != hipSuccess) return hip_fail(e, "launch_knn_score_pairs");
+  g_ws.knn_dirty = false;
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_knn_top_candidates_device(const int32_t* d_xp, const int32_t* d_xj, const uint32_t* d_xv, int n_rows, int n_items,
+                                          const int32_t* d_neighbors, const uint32_t* d_q, int K, const int32_t* d_cand_p,
+                                          const int32_t* d_cand_j, const int32_t* d_nr_p, const int32_t* d_nr_j, const int32_t* d_excl0,
+                                          int n_exclude, int k, int64_t ws_rows, int32_t* d_items, int64_t* d_scores, void* stream) {
+  int rc = knn_recommend_args(!d_xp || !d_xj || !d_neighbors || !d_q || !d_cand_p || !d_cand_j || !d_items || !d_scores, n_rows, n_items, K,
+                              d_nr_p, d_nr_j, d_excl0, n_exclude, k, ws_rows);
+  if (rc || n_rows == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> h_xp, h_cp;
+  if ((rc = fetch_row_pointers(d_cand_p, (size_t)n_rows, h_cp, s, "cand_p"))) return rc;
+  int64_t rows = 0;
+  unsigned long long* ws = nullptr;
+  if ((rc = knn_rows_begin(d_xp, n_rows, n_items, ws_rows, h_xp, rows, ws, s))) return rc;
+  hipError_t e = launch_knn_top_candidates(d_xp, d_xj, d_xv, n_rows, n_items, h_xp.data(), d_neighbors, d_q, K, d_cand_p, d_cand_j,
+                                           h_cp.data(), d_nr_p, d_nr_j, n_exclude > 0 ? d_excl0 : nullptr, n_exclude, k, rows, ws, d_items,
+                                           reinterpret_cast<long long*>(d_scores), s);
+  if (e != hipSuccess) return hip_fail(e, "launch_knn_top_candidates");
+  g_ws.knn_dirty = false;
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_knn_held_out_ranks_device(const int32_t* d_xp, const int32_t* d_xj, const uint32_t* d_xv, int n_rows, int n_items,
+                                          const int32_t* d_neighbors, const uint32_t* d_q, int K, const int32_t* d_actual_p,
+                                          const int32_t* d_actual_j, const int32_t* d_nr_p, const int32_t* d_nr_j, const int32_t* d_excl0,
+                                          int n_exclude, int64_t ws_rows, int32_t* d_above, int32_t* d_tied, int32_t* d_n_adm,
+                                          void* stream) {
+  int rc = knn_recommend_args(!d_xp || !d_xj || !d_neighbors || !d_q || !d_actual_p || !d_actual_j || !d_above || !d_tied || !d_n_adm,
+                              n_rows, n_items, K, d_nr_p, d_nr_j, d_excl0, n_exclude, 1, ws_rows);
+  if (rc || n_rows == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> h_xp;
+  int64_t rows = 0;
+  unsigned long long* ws = nullptr;
+  if ((rc = knn_rows_begin(d_xp, n_rows, n_items, ws_rows, h_xp, rows, ws, s))) return rc;
+  hipError_t e = launch_knn_held_out_ranks(d_xp, d_xj, d_xv, n_rows, n_items, h_xp.data(), d_neighbors, d_q, K, d_actual_p, d_actual_j,
+                                           d_nr_p, d_nr_j, n_exclude > 0 ? d_excl0 : nullptr, n_exclude, rows, ws, d_above, d_tied, d_n_adm,
+                                           s);
+  if (e != hipSuccess) return hip_fail(e, "launch_knn_held_out_ranks");
+  g_ws.knn_dirty = false;
+  return RSPARSE_HIP_OK;
+}
+
 // `_f64_device`: wrmf_f64_capi.cpp; the host form rsparse_hip_top_candidates: wrmf_capi_host.cpp
 int rsparse_hip_top_candidates_device(const float* d_U, const float* d_V, int n_users, int n_items, int rank, int k,
                                       const int32_t* d_cand_p, const int32_t* d_cand_j, const int32_t* d_nr_p, const int32_t* d_nr_j,

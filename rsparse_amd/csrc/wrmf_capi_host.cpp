@@ -800,6 +800,64 @@ void item_major(const int32_t* p, const int32_t* j, int n_users, int n_items, st
       if (l) (*il)[t] = l[e];
     }
 }
+// The operands the host forms of the lists share -- the rows (x_p, x_j, x_v), the tables, not_recommend and exclude: check()
+// judges the host arrays behind knn_recommend_args, upload() packs them for the device forms (row-major tables, 0-based ids).
+struct KnnHostRows {
+  DevBuf dXP, dXJ, dXV, dNb, dQ, dP, dJ, dE;
+  std::vector<int32_t> ex;
+  bool weighted = false, filter = false;
+
+  int check(const int32_t* x_p, const int32_t* x_j, const uint32_t* x_v, int n_rows, int n_items, const uint32_t* q, int K,
+            const int32_t* nr_p, const int32_t* nr_j) {
+    if (int rc = check_csr(x_p, n_rows, "x_p")) return rc;
+    if (x_p[n_rows] && !x_j) return fail(RSPARSE_HIP_ERR_INVALID, "x_j is NULL");
+    if (int rc = check_columns(x_p, x_j, n_rows, n_items, "x_j")) return rc;
+    if (x_v)
+      for (int u = 0; u < n_rows; u++) {
+        uint64_t sum = 0;
+        for (int32_t e = x_p[u]; e < x_p[u + 1]; e++) {
+          if (x_v[e] > 0xffffu) return fail(RSPARSE_HIP_ERR_INVALID, "a weight of x_v is above 2^16 - 1");
+          sum += x_v[e];
+        }
+        if (sum >= (1ull << 31)) return fail(RSPARSE_HIP_ERR_INVALID, "the weights x_v of a row sum to 2^31 or more");
+      }
+    if (nr_p) {
+      if (int rc = check_csr(nr_p, n_rows, "nr_p")) return rc;
+      for (int32_t e = 0; e < nr_p[n_rows]; e++)
+        if (nr_j[e] < 0 || nr_j[e] >= n_items) return fail(RSPARSE_HIP_ERR_INVALID, "nr_j has a column outside [0, n_items)");
+    }
+    for (size_t t = 0; t < (size_t)n_items * K; t++)
+      if (q[t] > (1u << 30)) return fail(RSPARSE_HIP_ERR_INVALID, "a weight of q is above 2^30");
+    return RSPARSE_HIP_OK;
+  }
+
+  int upload(const int32_t* x_p, const int32_t* x_j, const uint32_t* x_v, int n_rows, int n_items, const int32_t* neighbors,
+             const uint32_t* q, int K, const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude, int n_exclude) {
+    const size_t nnz = (size_t)x_p[n_rows], nt = (size_t)n_items * K, np1 = (size_t)n_rows + 1;
+    std::vector<int32_t> nb = row_major<int32_t>(neighbors, n_items, K);
+    for (size_t t = 0; t < nt; t++) nb[t] = (nb[t] >= 1 && nb[t] <= n_items) ? nb[t] - 1 : -1;
+    const std::vector<uint32_t> qr = row_major<uint32_t>(q, n_items, K);
+    add_excluded(exclude, n_exclude, n_items, ex);
+    HIP_TRY(upload_host(dXP, x_p, np1));
+    HIP_TRY(upload_host(dXJ, x_j, nnz));
+    weighted = x_v && nnz;
+    if (weighted) HIP_TRY(upload_host(dXV, x_v, nnz));
+    HIP_TRY(upload_host(dNb, nb.data(), nt));
+    HIP_TRY(upload_host(dQ, qr.data(), nt));
+    filter = nr_p != nullptr;
+    if (filter) {
+      HIP_TRY(upload_host(dP, nr_p, np1));
+      HIP_TRY(upload_host(dJ, nr_j, (size_t)nr_p[n_rows]));
+    }
+    if (!ex.empty()) HIP_TRY(upload_host(dE, ex.data(), ex.size()));
+    return RSPARSE_HIP_OK;
+  }
+
+  const uint32_t* xv() { return opt<uint32_t>(weighted, dXV); }
+  const int32_t* nr_p() { return opt<int32_t>(filter, dP); }
+  const int32_t* nr_j() { return opt<int32_t>(filter, dJ); }
+  const int32_t* excl() { return opt<int32_t>(!ex.empty(), dE); }
+};
 }  // namespace
 
 int rsparse_hip_cooc_neighbors(const int32_t* p, const int32_t* j, int n_users, int n_items, int similarity, int K,
@@ -888,56 +946,82 @@ int rsparse_hip_knn_recommend_weighted(const int32_t* x_p, const int32_t* x_j, c
                                        const int32_t* exclude, int n_exclude, int k, int32_t* res, int64_t* scores) {
   int rc = knn_recommend_args(!x_p || !neighbors || !q || !res || !scores, n_rows, n_items, K, nr_p, nr_j, exclude, n_exclude, k, 0);
   if (rc) return rc;
-  if ((rc = check_csr(x_p, n_rows, "x_p"))) return rc;
-  const size_t nnz = (size_t)x_p[n_rows];
-  if (nnz && !x_j) return fail(RSPARSE_HIP_ERR_INVALID, "x_j is NULL");
-  if ((rc = check_columns(x_p, x_j, n_rows, n_items, "x_j"))) return rc;
-  if (x_v)
-    for (int u = 0; u < n_rows; u++) {
-      uint64_t sum = 0;
-      for (int32_t e = x_p[u]; e < x_p[u + 1]; e++) {
-        if (x_v[e] > 0xffffu) return fail(RSPARSE_HIP_ERR_INVALID, "a weight of x_v is above 2^16 - 1");
-        sum += x_v[e];
-      }
-      if (sum >= (1ull << 31)) return fail(RSPARSE_HIP_ERR_INVALID, "the weights x_v of a row sum to 2^31 or more");
-    }
-  if (nr_p) {
-    if ((rc = check_csr(nr_p, n_rows, "nr_p"))) return rc;
-    for (int32_t e = 0; e < nr_p[n_rows]; e++)
-      if (nr_j[e] < 0 || nr_j[e] >= n_items) return fail(RSPARSE_HIP_ERR_INVALID, "nr_j has a column outside [0, n_items)");
-  }
-  const size_t nt = (size_t)n_items * K;
-  for (size_t t = 0; t < nt; t++)
-    if (q[t] > (1u << 30)) return fail(RSPARSE_HIP_ERR_INVALID, "a weight of q is above 2^30");
-  if (n_rows == 0) return RSPARSE_HIP_OK;
-  std::vector<int32_t> nb = row_major<int32_t>(neighbors, n_items, K);
-  for (size_t t = 0; t < nt; t++) nb[t] = (nb[t] >= 1 && nb[t] <= n_items) ? nb[t] - 1 : -1;
-  const std::vector<uint32_t> qr = row_major<uint32_t>(q, n_items, K);
-  std::vector<int32_t> ex;
-  add_excluded(exclude, n_exclude, n_items, ex);
-  const size_t np1 = (size_t)n_rows + 1, nk = (size_t)n_rows * k;
-  DevBuf dXP, dXJ, dXV, dNb, dQ, dP, dJ, dE, dR, dS;
-  HIP_TRY(upload_host(dXP, x_p, np1));
-  HIP_TRY(upload_host(dXJ, x_j, nnz));
-  const bool weighted = x_v && nnz;
-  if (weighted) HIP_TRY(upload_host(dXV, x_v, nnz));
-  HIP_TRY(upload_host(dNb, nb.data(), nt));
-  HIP_TRY(upload_host(dQ, qr.data(), nt));
-  if (nr_p) {
-    HIP_TRY(upload_host(dP, nr_p, np1));
-    HIP_TRY(upload_host(dJ, nr_j, (size_t)nr_p[n_rows]));
-  }
-  if (!ex.empty()) HIP_TRY(upload_host(dE, ex.data(), ex.size()));
+  KnnHostRows in;
+  if ((rc = in.check(x_p, x_j, x_v, n_rows, n_items, q, K, nr_p, nr_j)) || n_rows == 0) return rc;
+  if ((rc = in.upload(x_p, x_j, x_v, n_rows, n_items, neighbors, q, K, nr_p, nr_j, exclude, n_exclude))) return rc;
+  const size_t nk = (size_t)n_rows * k;
+  DevBuf dR, dS;
   HIP_TRY(dR.alloc(nk * 4));
   HIP_TRY(dS.alloc(nk * 8));
-  rc = rsparse_hip_knn_recommend_weighted_device(dXP.as<int32_t>(), dXJ.as<int32_t>(), opt<uint32_t>(weighted, dXV), n_rows, n_items,
-                                                 dNb.as<int32_t>(), dQ.as<uint32_t>(), K, opt<int32_t>(nr_p, dP), opt<int32_t>(nr_p, dJ),
-                                                 opt<int32_t>(!ex.empty(), dE), (int)ex.size(), k, 0, dR.as<int32_t>(), dS.as<int64_t>(),
-                                                 nullptr);
+  rc = rsparse_hip_knn_recommend_weighted_device(in.dXP.as<int32_t>(), in.dXJ.as<int32_t>(), in.xv(), n_rows, n_items, in.dNb.as<int32_t>(),
+                                                 in.dQ.as<uint32_t>(), K, in.nr_p(), in.nr_j(), in.excl(), (int)in.ex.size(), k, 0,
+                                                 dR.as<int32_t>(), dS.as<int64_t>(), nullptr);
   if (rc) return rc;
   HIP_TRY(hipDeviceSynchronize());
   if ((rc = fetch_col_major(dR, n_rows, k, res))) return rc;
   return fetch_col_major(dS, n_rows, k, scores);
+}
+
+int rsparse_hip_knn_top_candidates(const int32_t* x_p, const int32_t* x_j, const uint32_t* x_v, int n_rows, int n_items,
+                                   const int32_t* neighbors, const uint32_t* q, int K, const int32_t* cand_p, const int32_t* cand_j,
+                                   const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude, int n_exclude, int k, int32_t* res,
+                                   int64_t* scores) {
+  int rc = knn_recommend_args(!x_p || !neighbors || !q || !cand_p || !res || !scores, n_rows, n_items, K, nr_p, nr_j, exclude, n_exclude,
+                              k, 0);
+  if (rc) return rc;
+  KnnHostRows in;
+  if ((rc = in.check(x_p, x_j, x_v, n_rows, n_items, q, K, nr_p, nr_j))) return rc;
+  if ((rc = check_csr(cand_p, n_rows, "cand_p"))) return rc;
+  const size_t n_cand = (size_t)cand_p[n_rows];
+  if (n_cand && !cand_j) return fail(RSPARSE_HIP_ERR_INVALID, "cand_j is NULL");
+  if ((rc = check_columns(cand_p, cand_j, n_rows, n_items, "cand_j"))) return rc;
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  if ((rc = in.upload(x_p, x_j, x_v, n_rows, n_items, neighbors, q, K, nr_p, nr_j, exclude, n_exclude))) return rc;
+  const size_t nk = (size_t)n_rows * k;
+  DevBuf dCP, dCJ, dR, dS;
+  HIP_TRY(upload_host(dCP, cand_p, (size_t)n_rows + 1));
+  HIP_TRY(upload_host(dCJ, cand_j, n_cand));
+  HIP_TRY(dR.alloc(nk * 4));
+  HIP_TRY(dS.alloc(nk * 8));
+  rc = rsparse_hip_knn_top_candidates_device(in.dXP.as<int32_t>(), in.dXJ.as<int32_t>(), in.xv(), n_rows, n_items, in.dNb.as<int32_t>(),
+                                             in.dQ.as<uint32_t>(), K, dCP.as<int32_t>(), dCJ.as<int32_t>(), in.nr_p(), in.nr_j(), in.excl(),
+                                             (int)in.ex.size(), k, 0, dR.as<int32_t>(), dS.as<int64_t>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if ((rc = fetch_col_major(dR, n_rows, k, res))) return rc;
+  return fetch_col_major(dS, n_rows, k, scores);
+}
+
+int rsparse_hip_knn_held_out_ranks(const int32_t* x_p, const int32_t* x_j, const uint32_t* x_v, int n_rows, int n_items,
+                                   const int32_t* neighbors, const uint32_t* q, int K, const int32_t* actual_p, const int32_t* actual_j,
+                                   const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude, int n_exclude, int32_t* above,
+                                   int32_t* tied, int32_t* n_adm) {
+  int rc = knn_recommend_args(!x_p || !neighbors || !q || !actual_p || !above || !tied || !n_adm, n_rows, n_items, K, nr_p, nr_j, exclude,
+                              n_exclude, 1, 0);
+  if (rc) return rc;
+  KnnHostRows in;
+  if ((rc = in.check(x_p, x_j, x_v, n_rows, n_items, q, K, nr_p, nr_j))) return rc;
+  if ((rc = check_csr(actual_p, n_rows, "actual_p"))) return rc;
+  if (actual_p[n_rows] && !actual_j) return fail(RSPARSE_HIP_ERR_INVALID, "actual_j is NULL");
+  if ((rc = check_csr(actual_p, n_rows, "actual_p", actual_j, "actual_j"))) return rc;
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  if ((rc = in.upload(x_p, x_j, x_v, n_rows, n_items, neighbors, q, K, nr_p, nr_j, exclude, n_exclude))) return rc;
+  const size_t n_act = (size_t)actual_p[n_rows];
+  DevBuf dAP, dAJ, dA, dT, dN;
+  HIP_TRY(upload_host(dAP, actual_p, (size_t)n_rows + 1));
+  HIP_TRY(upload_host(dAJ, actual_j, n_act));
+  HIP_TRY(dA.alloc(n_act * 4));
+  HIP_TRY(dT.alloc(n_act * 4));
+  HIP_TRY(dN.alloc((size_t)n_rows * 4));
+  rc = rsparse_hip_knn_held_out_ranks_device(in.dXP.as<int32_t>(), in.dXJ.as<int32_t>(), in.xv(), n_rows, n_items, in.dNb.as<int32_t>(),
+                                             in.dQ.as<uint32_t>(), K, dAP.as<int32_t>(), dAJ.as<int32_t>(), in.nr_p(), in.nr_j(), in.excl(),
+                                             (int)in.ex.size(), 0, dA.as<int32_t>(), dT.as<int32_t>(), dN.as<int32_t>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(download(above, dA, n_act));
+  HIP_TRY(download(tied, dT, n_act));
+  HIP_TRY(download(n_adm, dN, (size_t)n_rows));
+  return RSPARSE_HIP_OK;
 }
 
 }  // extern "C"

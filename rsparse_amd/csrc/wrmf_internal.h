@@ -419,6 +419,21 @@ hipError_t launch_knn_recommend(const int32_t* xp, const int32_t* xj, const uint
                                 const int32_t* neighbors, const uint32_t* q, int K, const int32_t* nr_p, const int32_t* nr_j,
                                 const int32_t* excl, int n_excl, int k, int64_t rows, unsigned long long* ws, int32_t* items,
                                 long long* scores, hipStream_t s);
+// Three more consumers of the same dense rows of scores (operands and workspace as launch_knn_recommend): the cells at the stored
+// positions of a pattern (pp, pj) over the rows, unmasked; the lists within the rows' candidates (cp, cj); the counts above / tied
+// with every entry of (ap, aj) among the row's admissible cells, and those cells' number.  pp / cp / ap: n_rows + 1 absolute
+// slots; h_pp / h_cp: their host copies; scores / above / tied parallel pj / aj.
+hipError_t launch_knn_score_pairs(const int32_t* xp, const int32_t* xj, const uint32_t* xv, int n_rows, int n_items, const int32_t* h_xp,
+                                  const int32_t* neighbors, const uint32_t* q, int K, const int32_t* pp, const int32_t* pj,
+                                  const int32_t* h_pp, int64_t rows, unsigned long long* ws, long long* scores, hipStream_t s);
+hipError_t launch_knn_top_candidates(const int32_t* xp, const int32_t* xj, const uint32_t* xv, int n_rows, int n_items, const int32_t* h_xp,
+                                     const int32_t* neighbors, const uint32_t* q, int K, const int32_t* cp, const int32_t* cj,
+                                     const int32_t* h_cp, const int32_t* nr_p, const int32_t* nr_j, const int32_t* excl, int n_excl, int k,
+                                     int64_t rows, unsigned long long* ws, int32_t* items, long long* scores, hipStream_t s);
+hipError_t launch_knn_held_out_ranks(const int32_t* xp, const int32_t* xj, const uint32_t* xv, int n_rows, int n_items, const int32_t* h_xp,
+                                     const int32_t* neighbors, const uint32_t* q, int K, const int32_t* ap, const int32_t* aj,
+                                     const int32_t* nr_p, const int32_t* nr_j, const int32_t* excl, int n_excl, int64_t rows,
+                                     unsigned long long* ws, int32_t* above, int32_t* tied, int32_t* n_adm, hipStream_t s);
 
 // top-k within per-user candidate lists (wrmf_candidates.hip), T = float or double, 1 <= topk <= kTopLargeMax: for every row of
 // the CSR pattern (cand_p: n_users + 1 slots, absolute positions into cand_j; p0 = cand_p[0], nnz = cand_p[n_users] - p0, read by

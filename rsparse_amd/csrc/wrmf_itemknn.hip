@@ -34,6 +34,18 @@
 //     cells in ascending order.
 // The rows of a batch are zeroed again by a hipMemsetAsync behind the select (not by the select: the fallback reads the row
 // several times), so the workspace is all zeros between calls.
+//
+// Evaluation: three more consumers of a batch's dense uint64 rows, behind the same scatter and mask launches.
+//   * knn_gather_kernel (score_pairs; no mask): parallel over the stored positions of a second pattern, cut into spans and
+//     searched for their rows like the scatter's; out[t] = the cell of (row, j[t]), 0 for a column outside the items.
+//   * knn_cand_select_kernel (top_candidates): one workgroup per row reads the row's cells at its candidate slots only, drops
+//     the masked ones, and sorts up to RSPARSE_HIP_KNN_LDS_CAND (score, item) pairs in LDS: work follows the candidates, not
+//     n_items.  A longer candidate row is restricted in place instead -- every candidate cell gets a mark bit no score reaches,
+//     then one pass over the row clears the marks and masks the cells without one -- and the host runs knn_select_kernel on
+//     such rows: exact up to the whole catalogue, whatever the order of the candidates.
+//   * knn_ranks_kernel (held_out_ranks): one workgroup per masked row, the counting of wrmf_ranks.hip on 64-bit scores: the
+//     row's held-out scores RSPARSE_HIP_RANKS_BATCH at a time, sorted in LDS; every unmasked cell finds its place among them
+//     by a lower bound and bumps an LDS integer bin; a suffix sum turns the bins into `above`.
 #include <algorithm>
 #include <climits>
 
@@ -347,6 +359,239 @@ __global__ __launch_bounds__(kThreads) void knn_select_kernel(const void* __rest
   }
 }
 
+// ---- evaluation: consumers of a batch's dense rows of scores ------------------------------------------------------------------
+// (Templates without a use for their parameter: hipcc emits a template behind every plain kernel of the file and in the order of
+// first use, so these three come behind the kernels above, whose listings -- the labels of a listing carry the number of their
+// function -- stay byte for byte what they were; profiles/device_helpers/compare_listings.py shows it.)
+
+// the cells at the stored positions [t0, t1) of the pattern (PP, PJ) over the same rows: a wave takes kSpan consecutive
+// positions, one per lane.  out parallels PJ (absolute slots).
+template <int>
+__global__ __launch_bounds__(kThreads) void knn_gather_kernel(const int32_t* __restrict__ PP, const int32_t* __restrict__ PJ,
+                                                              int n_outer, int row0, int n_batch, unsigned t0, unsigned t1,
+                                                              const u64* __restrict__ dense, size_t ld, int n_items,
+                                                              long long* __restrict__ out) {
+  static_assert(kSpan == 64, "one position per lane");
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long b0l = (long long)t0 + ((long long)blockIdx.x * kWaves + w) * kSpan;
+  if (b0l >= (long long)t1) return;   // (whole waves)
+  int row = wave_find_row(PP, n_outer, (unsigned)b0l, lane);
+  const long long tl = b0l + lane;
+  if (tl >= (long long)t1) return;
+  const unsigned t = (unsigned)tl;
+  row = find_row_from(PP, n_outer, t, row);
+  const int j = PJ[t];
+  u64 v = 0;
+  if ((unsigned)j < (unsigned)n_items && (unsigned)(row - row0) < (unsigned)n_batch) v = dense[(size_t)(row - row0) * ld + j];
+  out[t] = (long long)v;
+}
+
+// the m entries of s_key / s_idx (m <= kCand) sorted by (key descending, index ascending): the select's bitonic network
+__device__ __forceinline__ void sort_entries(u64* s_key, int* s_idx, int m) {
+  const int tid = threadIdx.x;
+  int P = 1;
+  while (P < m) P <<= 1;
+  for (int t = m + tid; t < P; t += kThreads) {
+    s_key[t] = 0;
+    s_idx[t] = INT_MAX;
+  }
+  __syncthreads();
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = tid; t < (P >> 1); t += kThreads) {
+        const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+        const u64 ka = s_key[lo], kb = s_key[hi];
+        const int ia = s_idx[lo], ib = s_idx[hi];
+        const bool first_half = (lo & size) == 0;
+        if (first_half ? before(kb, ib, ka, ia) : before(ka, ia, kb, ib)) {
+          s_key[lo] = kb;
+          s_idx[lo] = ib;
+          s_key[hi] = ka;
+          s_idx[hi] = ia;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+constexpr u64 kMark = 1ull << 62;   // on a candidate's cell while a long row is restricted (a score is below 2^61)
+
+// cp: the slots of this batch's rows (absolute positions into cj).  A row of at most kCand candidates gets its list here; a
+// longer one is restricted to its candidates in place and left to knn_select_kernel.
+template <int>
+__global__ __launch_bounds__(kThreads) void knn_cand_select_kernel(u64* __restrict__ dense, size_t ld, int n_items,
+                                                                   const int32_t* __restrict__ cp, const int32_t* __restrict__ cj,
+                                                                   int k, int32_t* __restrict__ out_items,
+                                                                   long long* __restrict__ out_scores) {
+  __shared__ u64 s_key[kCand];
+  __shared__ int s_idx[kCand];
+  __shared__ int s_cnt;
+  const int tid = threadIdx.x;
+  u64* row = dense + (size_t)blockIdx.x * ld;
+  const int c0 = cp[blockIdx.x], c1 = cp[blockIdx.x + 1];
+  if (c1 - c0 > kCand) {   // (uniform over the workgroup)
+    for (int e = c0 + tid; e < c1; e += kThreads) {
+      const int j = cj[e];
+      if ((unsigned)j < (unsigned)n_items && row[j] != kMasked) row[j] |= kMark;   // (a repeated column stores the same value)
+    }
+    __syncthreads();   // the marks of this workgroup's own stores are visible to it behind the barrier
+    for (int j = tid; j < n_items; j += kThreads) {
+      const u64 v = row[j];
+      if (v != kMasked) row[j] = (v & kMark) ? (v & ~kMark) : kMasked;
+    }
+    return;
+  }
+  if (tid == 0) s_cnt = 0;
+  __syncthreads();
+  for (int e = c0 + tid; e < c1; e += kThreads) {
+    const int j = cj[e];
+    if ((unsigned)j >= (unsigned)n_items) continue;
+    const u64 v = row[j];
+    if (v == kMasked) continue;
+    const int slot = atomicAdd(&s_cnt, 1);   // (at most c1 - c0 <= kCand of them)
+    s_key[slot] = v;
+    s_idx[slot] = j;
+  }
+  __syncthreads();
+  const int m = s_cnt;
+  sort_entries(s_key, s_idx, m);   // (a score of 0 sorts behind the scored ones and, by its item, in front of the padding)
+  const int have = min(m, k);
+  const size_t o = (size_t)blockIdx.x * k;
+  for (int t = tid; t < k; t += kThreads) {
+    out_items[o + t] = t < have ? s_idx[t] + 1 : INT_MIN;
+    out_scores[o + t] = t < have ? (long long)s_key[t] : 0;
+  }
+}
+
+constexpr int kRankT = RSPARSE_HIP_RANKS_BATCH;   // held-out scores per pass over the row
+static_assert(kRankT == 4 * kThreads, "knn_ranks_kernel: a thread owns four bins of the suffix sum");
+
+// first position in t[0, hi) (ascending) whose value is >= k
+__device__ __forceinline__ int lower_bound64(const u64* t, int hi, u64 k) {
+  int lo = 0;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (t[mid] < k) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// the score of the held-out item `it` in the masked row, kMasked for an inadmissible one (masked, or outside the items)
+__device__ __forceinline__ u64 held_score(const u64* row, int n_items, int it) {
+  return (unsigned)it < (unsigned)n_items ? row[it] : kMasked;
+}
+
+// ap: the slots of this batch's rows (absolute positions into aj / above / tied); n_adm: of this batch's rows
+template <int>
+__global__ __launch_bounds__(kThreads) void knn_ranks_kernel(const u64* __restrict__ dense, size_t ld, int n_items,
+                                                             const int32_t* __restrict__ ap, const int32_t* __restrict__ aj,
+                                                             int32_t* __restrict__ above, int32_t* __restrict__ tied,
+                                                             int32_t* __restrict__ n_adm) {
+  __shared__ u64 s_own[kRankT];   // the batch's scores in the order of the entries
+  __shared__ u64 s_thr[kRankT];   // ... sorted ascending: the admissible ones, then kMasked (inadmissible entries, padding)
+  __shared__ int s_gt[kRankT];    // bin b: cells above exactly the thresholds 0..b; after the suffix sum: cells above threshold b
+  __shared__ int s_eq[kRankT];    // bin b: cells equal to the run of thresholds that starts at b
+  __shared__ int s_w[kWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const u64* row = dense + (size_t)blockIdx.x * ld;
+  const int p1 = ap[blockIdx.x], n_held = max(ap[blockIdx.x + 1] - p1, 0);
+  for (int b0 = 0; b0 == 0 || b0 < n_held; b0 += kRankT) {
+    const int nb = min(kRankT, n_held - b0);
+    int P = 1;
+    while (P < nb) P <<= 1;
+    for (int e = tid; e < P; e += kThreads) {
+      const u64 key = e < nb ? held_score(row, n_items, aj[p1 + b0 + e]) : kMasked;
+      s_own[e] = key;
+      s_thr[e] = key;
+      s_gt[e] = 0;
+      s_eq[e] = 0;
+    }
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1)
+      for (int stride = size >> 1; stride > 0; stride >>= 1) {
+        for (int i = tid; i < P / 2; i += kThreads) {
+          const int a = 2 * i - (i & (stride - 1)), b = a + stride;
+          const u64 ka = s_thr[a], kb = s_thr[b];
+          if (((a & size) == 0) == (kb < ka)) {
+            s_thr[a] = kb;
+            s_thr[b] = ka;
+          }
+        }
+        __syncthreads();
+      }
+    const int n1 = lower_bound64(s_thr, P, kMasked);   // the admissible thresholds: [0, n1)
+    const u64 tmin = n1 > 0 ? s_thr[0] : kMasked;
+    // (consecutive cells of one bin -- the zeros of a sparse row, a lone threshold -- cost one atomic)
+    int na = 0, gt_bin = -1, gt_cnt = 0, eq_bin = -1, eq_cnt = 0;
+    for (int j = tid; j < n_items; j += kThreads) {
+      const u64 v = row[j];
+      if (v == kMasked) continue;
+      na++;
+      if (v < tmin) continue;   // (also: no admissible threshold)
+      const int pos = lower_bound64(s_thr, n1, v);
+      if (pos < n1 && s_thr[pos] == v) {
+        if (pos != eq_bin) {
+          if (eq_cnt) atomicAdd(&s_eq[eq_bin], eq_cnt);
+          eq_bin = pos;
+          eq_cnt = 0;
+        }
+        eq_cnt++;
+      }
+      if (pos > 0) {
+        if (pos - 1 != gt_bin) {
+          if (gt_cnt) atomicAdd(&s_gt[gt_bin], gt_cnt);
+          gt_bin = pos - 1;
+          gt_cnt = 0;
+        }
+        gt_cnt++;
+      }
+    }
+    if (eq_cnt) atomicAdd(&s_eq[eq_bin], eq_cnt);
+    if (gt_cnt) atomicAdd(&s_gt[gt_bin], gt_cnt);
+    if (b0 == 0) {
+      for (int o = 32; o > 0; o >>= 1) na += __shfl_xor(na, o);
+      if (lane == 0) s_w[wv] = na;
+      __syncthreads();
+      if (tid == 0) {
+        int sum = 0;
+        for (int q = 0; q < kWaves; q++) sum += s_w[q];
+        n_adm[blockIdx.x] = sum;
+      }
+    }
+    __syncthreads();
+    // inclusive suffix sum of s_gt[0, P): thread t owns the bins 4t .. 4t + 3
+    int v[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) v[j] = 4 * tid + j < P ? s_gt[4 * tid + j] : 0;
+    v[2] += v[3];
+    v[1] += v[2];
+    v[0] += v[1];
+    int incl = v[0];   // over the lanes above, then the waves above
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_down(incl, o);
+      if (lane + o < 64) incl += t;
+    }
+    if (lane == 0) s_w[wv] = incl;
+    __syncthreads();
+    int off = incl - v[0];
+    for (int q = wv + 1; q < kWaves; q++) off += s_w[q];
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      if (4 * tid + j < P) s_gt[4 * tid + j] = v[j] + off;
+    __syncthreads();
+    for (int e = tid; e < nb; e += kThreads) {
+      const u64 key = s_own[e];
+      const int pos = key == kMasked ? 0 : lower_bound64(s_thr, n1, key);   // the start of the entry's run of equal scores
+      above[p1 + b0 + e] = key == kMasked ? -1 : s_gt[pos];
+      tied[p1 + b0 + e] = key == kMasked ? -1 : s_eq[pos] - 1;               // (its own cell is one of the equal ones)
+    }
+    __syncthreads();   // (the arrays are reused by the next batch)
+  }
+}
+
 unsigned scatter_grid(unsigned t0, unsigned t1) {
   const long long per = (long long)kSpan * kWaves;
   return (unsigned)(((long long)t1 - t0 + per - 1) / per);
@@ -393,30 +638,116 @@ hipError_t launch_cooc_neighbors_weighted(const int32_t* ip, const int32_t* iu, 
   return hipSuccess;
 }
 
+namespace {
+
+// the rows to score and what filters them: the operands every consumer of the lists' dense rows shares
+struct KnnRows {
+  const int32_t *xp, *xj;
+  const uint32_t* xv;
+  int n_rows, n_items;
+  const int32_t *h_xp, *neighbors;
+  const uint32_t* q;
+  int K;
+  const int32_t *nr_p, *nr_j, *excl;
+  int n_excl;
+  size_t ld() const { return (size_t)n_items; }
+  int batch_end(int64_t r0, int64_t rows) const { return (int)std::min<int64_t>(r0 + rows, n_rows); }
+};
+
+// the first launches of a batch of rows [r0, r1): the scatter of the rows' entries and (with_mask) the mask -> whether the rows
+// hold anything now
+bool fill_list_rows(const KnnRows& in, bool with_mask, int r0, int r1, unsigned long long* ws, hipStream_t s) {
+  const unsigned t0 = (unsigned)in.h_xp[r0], t1 = (unsigned)in.h_xp[r1];
+  const bool mask = with_mask && (in.nr_p || in.n_excl > 0);
+  if (t1 > t0 && in.xv)
+    hipLaunchKernelGGL(knn_scatter_kernel<kListsW>, dim3(scatter_grid(t0, t1)), dim3(kThreads), 0, s, in.xp, in.xj, in.n_rows, r0, r1 - r0,
+                       t0, t1, nullptr, in.neighbors, in.q, in.K, in.n_items, in.n_items, in.ld(), ws, in.xv);
+  else if (t1 > t0)
+    hipLaunchKernelGGL(knn_scatter_kernel<kLists>, dim3(scatter_grid(t0, t1)), dim3(kThreads), 0, s, in.xp, in.xj, in.n_rows, r0, r1 - r0,
+                       t0, t1, nullptr, in.neighbors, in.q, in.K, in.n_items, in.n_items, in.ld(), ws, nullptr);
+  if (mask)
+    hipLaunchKernelGGL(knn_mask_kernel, dim3((unsigned)(r1 - r0)), dim3(kThreads), 0, s, ws, in.ld(), in.n_items,
+                       in.nr_p ? in.nr_p + r0 : nullptr, in.nr_j, in.excl, in.n_excl);
+  return t1 > t0 || mask;
+}
+
+// the last step of a batch, behind its consumer: the launches' status, and the rows zeroed again if anything was written to them
+hipError_t zero_list_rows(const KnnRows& in, bool written, int r0, int r1, unsigned long long* ws, hipStream_t s) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !written) return e;
+  return hipMemsetAsync(ws, 0, (size_t)(r1 - r0) * in.ld() * sizeof(unsigned long long), s);
+}
+
+}  // namespace
+
 hipError_t launch_knn_recommend(const int32_t* xp, const int32_t* xj, const uint32_t* xv, int n_rows, int n_items, const int32_t* h_xp,
                                 const int32_t* neighbors, const uint32_t* q, int K, const int32_t* nr_p, const int32_t* nr_j,
                                 const int32_t* excl, int n_excl, int k, int64_t rows, unsigned long long* ws, int32_t* items,
                                 long long* scores, hipStream_t s) {
-  const size_t ld = (size_t)n_items;
+  const KnnRows in{xp, xj, xv, n_rows, n_items, h_xp, neighbors, q, K, nr_p, nr_j, excl, n_excl};
   for (int64_t r0 = 0; r0 < n_rows; r0 += rows) {
-    const int r1 = (int)std::min<int64_t>(r0 + rows, n_rows);
-    const unsigned t0 = (unsigned)h_xp[r0], t1 = (unsigned)h_xp[r1];
-    const bool mask = nr_p || n_excl > 0;
-    if (t1 > t0 && xv)
-      hipLaunchKernelGGL(knn_scatter_kernel<kListsW>, dim3(scatter_grid(t0, t1)), dim3(kThreads), 0, s, xp, xj, n_rows, (int)r0,
-                         (int)(r1 - r0), t0, t1, nullptr, neighbors, q, K, n_items, n_items, ld, ws, xv);
-    else if (t1 > t0)
-      hipLaunchKernelGGL(knn_scatter_kernel<kLists>, dim3(scatter_grid(t0, t1)), dim3(kThreads), 0, s, xp, xj, n_rows, (int)r0,
-                         (int)(r1 - r0), t0, t1, nullptr, neighbors, q, K, n_items, n_items, ld, ws, nullptr);
-    if (mask)
-      hipLaunchKernelGGL(knn_mask_kernel, dim3((unsigned)(r1 - r0)), dim3(kThreads), 0, s, ws, ld, n_items, nr_p ? nr_p + r0 : nullptr,
-                         nr_j, excl, n_excl);
-    hipLaunchKernelGGL(knn_select_kernel<kLists>, dim3((unsigned)(r1 - r0)), dim3(kThreads), 0, s, ws, ld, n_items, (int)r0, nullptr, 0, k,
-                       items + (size_t)r0 * k, nullptr, scores + (size_t)r0 * k, nullptr, nullptr, 0.0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if ((t1 > t0 || mask) && (e = hipMemsetAsync(ws, 0, (size_t)(r1 - r0) * ld * sizeof(unsigned long long), s)) != hipSuccess)
-      return e;
+    const int r1 = in.batch_end(r0, rows);
+    const bool written = fill_list_rows(in, true, (int)r0, r1, ws, s);
+    hipLaunchKernelGGL(knn_select_kernel<kLists>, dim3((unsigned)(r1 - r0)), dim3(kThreads), 0, s, ws, in.ld(), n_items, (int)r0, nullptr, 0,
+                       k, items + (size_t)r0 * k, nullptr, scores + (size_t)r0 * k, nullptr, nullptr, 0.0);
+    if (hipError_t e = zero_list_rows(in, written, (int)r0, r1, ws, s)) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_knn_score_pairs(const int32_t* xp, const int32_t* xj, const uint32_t* xv, int n_rows, int n_items, const int32_t* h_xp,
+                                  const int32_t* neighbors, const uint32_t* q, int K, const int32_t* pp, const int32_t* pj,
+                                  const int32_t* h_pp, int64_t rows, unsigned long long* ws, long long* scores, hipStream_t s) {
+  const KnnRows in{xp, xj, xv, n_rows, n_items, h_xp, neighbors, q, K, nullptr, nullptr, nullptr, 0};
+  for (int64_t r0 = 0; r0 < n_rows; r0 += rows) {
+    const int r1 = in.batch_end(r0, rows);
+    const bool written = fill_list_rows(in, false, (int)r0, r1, ws, s);
+    const unsigned t0 = (unsigned)h_pp[r0], t1 = (unsigned)h_pp[r1];
+    if (t1 > t0)
+      hipLaunchKernelGGL(knn_gather_kernel<0>, dim3(scatter_grid(t0, t1)), dim3(kThreads), 0, s, pp, pj, n_rows, (int)r0, r1 - (int)r0, t0,
+                         t1, ws, in.ld(), n_items, scores);
+    if (hipError_t e = zero_list_rows(in, written, (int)r0, r1, ws, s)) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_knn_top_candidates(const int32_t* xp, const int32_t* xj, const uint32_t* xv, int n_rows, int n_items, const int32_t* h_xp,
+                                     const int32_t* neighbors, const uint32_t* q, int K, const int32_t* cp, const int32_t* cj,
+                                     const int32_t* h_cp, const int32_t* nr_p, const int32_t* nr_j, const int32_t* excl, int n_excl, int k,
+                                     int64_t rows, unsigned long long* ws, int32_t* items, long long* scores, hipStream_t s) {
+  const KnnRows in{xp, xj, xv, n_rows, n_items, h_xp, neighbors, q, K, nr_p, nr_j, excl, n_excl};
+  auto is_long = [&](int r) { return (int64_t)h_cp[r + 1] - h_cp[r] > kCand; };
+  for (int64_t r0 = 0; r0 < n_rows; r0 += rows) {
+    const int r1 = in.batch_end(r0, rows);
+    bool written = fill_list_rows(in, true, (int)r0, r1, ws, s);
+    hipLaunchKernelGGL(knn_cand_select_kernel<0>, dim3((unsigned)(r1 - r0)), dim3(kThreads), 0, s, ws, in.ld(), n_items, cp + r0, cj, k,
+                       items + (size_t)r0 * k, scores + (size_t)r0 * k);
+    // the rows it restricted instead (more candidates than the LDS buffer holds): the full select, a run of such rows at a time
+    for (int a = (int)r0; a < r1; a++) {
+      if (!is_long(a)) continue;
+      int b = a + 1;
+      while (b < r1 && is_long(b)) b++;
+      hipLaunchKernelGGL(knn_select_kernel<kLists>, dim3((unsigned)(b - a)), dim3(kThreads), 0, s, ws + (size_t)(a - r0) * in.ld(), in.ld(),
+                         n_items, a, nullptr, 0, k, items + (size_t)a * k, nullptr, scores + (size_t)a * k, nullptr, nullptr, 0.0);
+      written = true;   // (the cells outside the candidates are masked now)
+      a = b;
+    }
+    if (hipError_t e = zero_list_rows(in, written, (int)r0, r1, ws, s)) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_knn_held_out_ranks(const int32_t* xp, const int32_t* xj, const uint32_t* xv, int n_rows, int n_items, const int32_t* h_xp,
+                                     const int32_t* neighbors, const uint32_t* q, int K, const int32_t* ap, const int32_t* aj,
+                                     const int32_t* nr_p, const int32_t* nr_j, const int32_t* excl, int n_excl, int64_t rows,
+                                     unsigned long long* ws, int32_t* above, int32_t* tied, int32_t* n_adm, hipStream_t s) {
+  const KnnRows in{xp, xj, xv, n_rows, n_items, h_xp, neighbors, q, K, nr_p, nr_j, excl, n_excl};
+  for (int64_t r0 = 0; r0 < n_rows; r0 += rows) {
+    const int r1 = in.batch_end(r0, rows);
+    const bool written = fill_list_rows(in, true, (int)r0, r1, ws, s);
+    hipLaunchKernelGGL(knn_ranks_kernel<0>, dim3((unsigned)(r1 - r0)), dim3(kThreads), 0, s, ws, in.ld(), n_items, ap + r0, aj, above, tied,
+                       n_adm + r0);
+    if (hipError_t e = zero_list_rows(in, written, (int)r0, r1, ws, s)) return e;
   }
   return hipSuccess;
 }

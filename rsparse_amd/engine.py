@@ -862,6 +862,64 @@ class HipBackend:
             0 if exclude0 is None else int(exclude0.numel()), int(k), int(ws_rows), some(res), some(sc), self._stream()))
         return res, sc
 
+    def _knn_rows(self, xp, xj, neighbors, q, xv):
+        """the operands the ItemKNN evaluation entries share with `knn_recommend`, as the C ABI takes them: -> (the leading
+        arguments, `some`: the address of a tensor, or of xp for an empty one; the tensors that must outlive the call)"""
+        assert xp.dtype == torch.int32 and xj.dtype == torch.int32 and neighbors.dtype == torch.int32 and neighbors.shape == q.shape
+        n, (n_items, K) = int(xp.numel()) - 1, neighbors.shape
+        neighbors = neighbors.contiguous()
+        q32 = q.to(torch.int64).to(torch.int32).contiguous()   # (q <= 2^30: the same bits as uint32)
+        some = lambda t: t.data_ptr() if t.numel() else xp.data_ptr()
+        if xv is not None:
+            assert xv.numel() == xj.numel()
+            xv = xv.to(torch.int64).to(torch.int32).contiguous()
+        head = (xp.data_ptr(), some(xj), None if xv is None or not xv.numel() else xv.data_ptr(), n, int(n_items), some(neighbors),
+                some(q32), int(K))
+        return head, some, (neighbors, q32, xv)
+
+    @staticmethod
+    def _knn_filters(some, nr_p, nr_j, exclude0):
+        return (None if nr_p is None else nr_p.data_ptr(), None if nr_p is None else some(nr_j),
+                None if exclude0 is None or not exclude0.numel() else exclude0.data_ptr(), 0 if exclude0 is None else int(exclude0.numel()))
+
+    def knn_score_pairs(self, xp, xj, neighbors, q, pp, pj, ws_rows=0, xv=None):
+        """the ItemKNN score of the rows of (xp, xj) -- operands as `knn_recommend` -- at the stored positions of the pattern
+        (pp, pj: int32 on the device, over the same rows); nothing is masked, a column outside the items gives 0.
+        rsparse_amd.itemknn.knn_score_pairs_reference is the definition.  -> int64, one per element of pj, on the device."""
+        head, some, keep = self._knn_rows(xp, xj, neighbors, q, xv)
+        assert pp.dtype == torch.int32 and pj.dtype == torch.int32 and pp.numel() == xp.numel()
+        out = torch.zeros(int(pj.numel()), dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.rsparse_hip_knn_score_pairs_device(*head, pp.data_ptr(), some(pj), int(ws_rows), some(out), self._stream()))
+        return out
+
+    def knn_top_candidates(self, xp, xj, neighbors, q, k, cp, cj, nr_p=None, nr_j=None, exclude0=None, ws_rows=0, xv=None):
+        """`knn_recommend` within the rows' candidates (cp, cj: a canonical CSR pattern over the same rows, int32 on the device;
+        cp may be a slice of the row pointers, its slots absolute).  rsparse_amd.itemknn.knn_candidates_reference is the
+        definition: score descending, equal scores to the smaller item.  -> (items (n, k) int32, 1-based with NA_integer_;
+        scores (n, k) int64, 0 where NA) on the device."""
+        head, some, keep = self._knn_rows(xp, xj, neighbors, q, xv)
+        assert cp.dtype == torch.int32 and cj.dtype == torch.int32 and cp.numel() == xp.numel()
+        n = head[3]
+        res = torch.empty((n, int(k)), dtype=torch.int32, device=self.device)
+        sc = torch.empty((n, int(k)), dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.rsparse_hip_knn_top_candidates_device(*head, cp.data_ptr(), some(cj), *self._knn_filters(some, nr_p, nr_j, exclude0),
+                                                                  int(k), int(ws_rows), some(res), some(sc), self._stream()))
+        return res, sc
+
+    def knn_held_out_ranks(self, xp, xj, neighbors, q, ap, aj, nr_p=None, nr_j=None, exclude0=None, ws_rows=0, xv=None):
+        """where the entries of (ap, aj: CSR over the same rows, int32 on the device) stand among the row's admissible items by the
+        ItemKNN score (rsparse_amd.itemknn.knn_ranks_reference; the counts `held_out_ranks` defines).  -> (above, tied: int32,
+        one per element of aj, -1 / -1 for an inadmissible entry; n_adm: int32 per row) on the device."""
+        head, some, keep = self._knn_rows(xp, xj, neighbors, q, xv)
+        assert ap.dtype == torch.int32 and aj.dtype == torch.int32 and ap.numel() == xp.numel()
+        n = head[3]
+        above = torch.full((int(aj.numel()),), -1, dtype=torch.int32, device=self.device)
+        tied = torch.full((int(aj.numel()),), -1, dtype=torch.int32, device=self.device)
+        n_adm = torch.zeros(n, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.rsparse_hip_knn_held_out_ranks_device(*head, ap.data_ptr(), some(aj), *self._knn_filters(some, nr_p, nr_j, exclude0),
+                                                                  int(ws_rows), some(above), some(tied), some(n_adm), self._stream()))
+        return above, tied, n_adm
+
     def explain_pairs(self, V, base, diag, diag_per_nnz, x_p, x_j, wa, wb, t_p, t_j):
         """what every interaction of a row contributes to the scores of the row's target items (wrmf_explain.hip): for the users
         of the CSR rows (x_p, x_j: int32 on the device; wa, wb: the assembly and contribution weight of every stored position, in

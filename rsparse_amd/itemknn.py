@@ -65,8 +65,19 @@ below 2^61.  Selection, ties, zero scores, padding and the filters are as above;
 
   cooccurrence_reference            the fit, per item, in numpy integers
   quantize_values, weighted_operands, weighted_cooccurrence_reference      the weighted fit
+Evaluation.  Three more readers of score_u, integers like it, so that the model runs under the protocols of `WRMF`: the score at
+given cells (nothing masked); the list within a row's own candidates -- admissible = the candidates minus the not_recommend row
+minus items_exclude, the same order (score descending, equal scores to the SMALLER item: not the reference heap's rule that
+`WRMF.predict(candidates=)` follows), candidates of score 0 ranked --; and, for a held-out entry (u, h) with A_u the items outside
+the not_recommend row and outside items_exclude, above = #{j in A_u : s_j > s_h} and tied = #{j in A_u, j != h : s_j == s_h}
+(-1 / -1 for h outside A_u), n_adm = |A_u|, from which `rank_summary` takes MPR, AUC and MRR.
+
+  cooccurrence_reference            the fit, per item, in numpy integers
+  quantize_values, weighted_operands, weighted_cooccurrence_reference      the weighted fit
   knn_recommend_reference           the lists, per row
-  ItemKNN                           the model: fit / similar_items / predict / evaluate
+  knn_score_pairs_reference, knn_candidates_reference, knn_ranks_reference      the evaluation, per row
+  ItemKNN                           the model: fit / similar_items / predict / evaluate / sample_negatives / score / held_out_ranks /
+                                    evaluate_ranks
 """
 import types
 
@@ -385,6 +396,112 @@ def knn_recommend_reference(x, neighbors, q, k, not_recommend=None, items_exclud
     return items, scores
 
 
+def _scored_rows(x, neighbors, q, xv):
+    """-> (m: the canonical pattern of x, score(u): the int64 score of every item for row u, as knn_recommend_reference sums it)"""
+    neighbors, q = np.asarray(neighbors, dtype=np.int64), np.asarray(q, dtype=np.int64)
+    n_items = neighbors.shape[0]
+    m = canonical_pattern(x, n_items)
+    if xv is not None:
+        xv = np.asarray(xv, dtype=np.int64)
+        if xv.shape != (m.nnz,):
+            raise ValueError("xv must hold one weight per stored entry of the canonical pattern of x")
+
+    def score(u):
+        own = m.indices[m.indptr[u]:m.indptr[u + 1]]
+        w = q[own] if xv is None else xv[m.indptr[u]:m.indptr[u + 1], None] * q[own]
+        nb, w = neighbors[own].ravel(), w.ravel()
+        s = np.zeros(n_items, dtype=np.int64)
+        np.add.at(s, nb[nb >= 0], w[nb >= 0])
+        return s
+    return m, score
+
+
+def _admissible_rows(shape, not_recommend, items_exclude):
+    """-> adm(u): the bool mask of the items outside row u of not_recommend (a sparse matrix of `shape`, or None) and outside
+    items_exclude"""
+    nr = None
+    if not_recommend is not None:
+        nr = sp.csr_matrix(not_recommend)
+        if nr.shape != shape:
+            raise ValueError("not_recommend must have the shape of x")
+    excl = np.asarray(list(items_exclude), dtype=np.int64)
+
+    def adm(u):
+        a = np.ones(shape[1], dtype=bool)
+        if nr is not None:
+            a[nr.indices[nr.indptr[u]:nr.indptr[u + 1]]] = False
+        a[excl] = False
+        return a
+    return adm
+
+
+def knn_score_pairs_reference(x, neighbors, q, pairs, xv=None):
+    """-> int64, one per stored position of canonical_pattern(pairs) (a sparse matrix of x's shape): score_u[j] of
+    knn_recommend_reference at that cell, one row at a time.  Nothing is masked."""
+    m, score = _scored_rows(x, neighbors, q, xv)
+    pat = canonical_pattern(pairs, m.shape[1])
+    if pat.shape != m.shape:
+        raise ValueError("pairs must have the shape of x")
+    out = np.zeros(pat.nnz, dtype=np.int64)
+    for u in range(m.shape[0]):
+        a, b = pat.indptr[u], pat.indptr[u + 1]
+        if b > a:
+            out[a:b] = score(u)[pat.indices[a:b]]
+    return out
+
+
+def knn_candidates_reference(x, neighbors, q, candidates, k, not_recommend=None, items_exclude=(), xv=None):
+    """-> (items (n, k) int64 with -1, scores (n, k) int64 with 0 in the padding): knn_recommend_reference within per-row
+    candidates.  The admissible items of a row are the stored positions of its row of canonical_pattern(candidates) minus the
+    row's not_recommend entries minus items_exclude.  The order is ItemKNN's own -- score descending, equal scores to the SMALLER
+    item -- and NOT the reference heap's rule that `WRMF.predict(candidates=)` follows.  Candidates of score 0 are ranked; a list
+    is shorter than k only when fewer than k candidates are admissible."""
+    m, score = _scored_rows(x, neighbors, q, xv)
+    cand = canonical_pattern(candidates, m.shape[1])
+    if cand.shape != m.shape:
+        raise ValueError("candidates must have the shape of x")
+    adm = _admissible_rows(m.shape, not_recommend, items_exclude)
+    k = int(k)
+    items = np.full((m.shape[0], k), -1, dtype=np.int64)
+    scores = np.zeros((m.shape[0], k), dtype=np.int64)
+    for u in range(m.shape[0]):
+        c = cand.indices[cand.indptr[u]:cand.indptr[u + 1]].astype(np.int64)
+        c = c[adm(u)[c]]
+        s = score(u)[c]
+        first = np.lexsort((c, -s))[:k]
+        items[u, :first.size] = c[first]
+        scores[u, :first.size] = s[first]
+    return items, scores
+
+
+def knn_ranks_reference(x, neighbors, q, actual, not_recommend=None, items_exclude=(), xv=None):
+    """-> (above, tied: int32, one per stored entry of `actual` (CSR with sorted columns, duplicates merged, stored zeros kept);
+    n_adm: int32 per row): the counts of rsparse_hip_held_out_ranks_device with s the integer score.  A_u = the items outside the
+    not_recommend row and outside items_exclude, n_adm = |A_u|; above = #{j in A_u : s_j > s_h}, tied = #{j in A_u, j != h : s_j
+    == s_h}; an entry outside A_u (or outside the items) gets -1 / -1."""
+    from .metrics import canonical_actual
+    m, score = _scored_rows(x, neighbors, q, xv)
+    n, n_items = m.shape
+    act = canonical_actual(actual, n)
+    adm = _admissible_rows(m.shape, not_recommend, items_exclude)
+    above = np.full(act.nnz, -1, dtype=np.int32)
+    tied = np.full(act.nnz, -1, dtype=np.int32)
+    n_adm = np.zeros(n, dtype=np.int32)
+    for u in range(n):
+        a = adm(u)
+        n_adm[u] = a.sum()
+        if act.indptr[u + 1] == act.indptr[u]:
+            continue
+        s = score(u)
+        s_adm = s[a]
+        for e in range(act.indptr[u], act.indptr[u + 1]):
+            h = int(act.indices[e])
+            if 0 <= h < n_items and a[h]:
+                above[e] = np.count_nonzero(s_adm > s[h])
+                tied[e] = np.count_nonzero(s_adm == s[h]) - 1
+    return above, tied, n_adm
+
+
 class ItemKNN:
     """Item-based k-nearest-neighbours on the co-occurrence of items (the module's docstring is the definition).
 
@@ -393,8 +510,8 @@ class ItemKNN:
     `rsparse_amd.Confidence`, fitted on x at `fit` and applied to new users at `predict`; shrinkage: added to the denominator
     of "cosine" / "asymmetric"; alpha: the exponent of "asymmetric" (default 0.5) and "rp3beta" (default 1); beta: the
     popularity exponent of "rp3beta" (0 = P3alpha); bits: of a quantised operand (at most 24); device / backend: as `WRMF`.
-    A backend without `cooc_neighbors` / `cooc_neighbors_weighted` / `knn_recommend` (the CPU stand-in of the tests) runs the
-    numpy definitions.  Fitted: `neighbors`, `similarities`, `item_count`, and `counts` (pattern kinds) or `sums` (weighted)."""
+    A backend without `cooc_neighbors` / `cooc_neighbors_weighted` / `knn_recommend` / `knn_top_candidates` / `knn_score_pairs` /
+    `knn_held_out_ranks` (the CPU stand-in of the tests) runs the numpy definitions.  Fitted: `neighbors`, `similarities`, `item_count`, and `counts` (pattern kinds) or `sums` (weighted)."""
 
     def __init__(self, k_neighbors=50, similarity="cosine", weighting=None, shrinkage=0.0, alpha=None, beta=0.0, bits=16, device=None,
                  backend=None):
@@ -534,17 +651,13 @@ class ItemKNN:
         out.scores = self.similarities[q, :k].copy()
         return out
 
-    def _lists(self, x, k, not_recommend, items_exclude, ws_rows=0):
-        """-> (m: x as a canonical pattern, items int32 (n, k) 1-based with NA_integer_, scores int64 (n, k)), as tensors of the
-        backend"""
+    def _rows(self, x, not_recommend="x", items_exclude=()):
+        """what every scoring call starts with -> (m: x as a canonical pattern, be, xq: the rows' weights or None, not_recommend as
+        CSR or None, items_exclude sorted and unique)"""
         self._fitted()
         self._one_rank()
         n_items = self.neighbors.shape[0]
         m = canonical_pattern(x, n_items)
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
-            raise ValueError("k must be an integer >= 1")
-        if k > _lib.KNN_MAX_TOPK:
-            raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "predict: k > 1024 is not on the device path")
         excl = np.unique(np.asarray(list(items_exclude), dtype=np.int64))
         if excl.size and (excl.min() < 0 or excl.max() >= n_items):
             raise ValueError("some of items_exclude indices are bigger than number of items")
@@ -557,44 +670,166 @@ class ItemKNN:
             if not_recommend.shape != m.shape:
                 raise ValueError("not_recommend must have the shape of x")
         be = self._backend()
-        xq = self._row_weights(m, be)
-        if not hasattr(be, "knn_recommend"):
-            it, sc = knn_recommend_reference(m, self.neighbors, self._weights(), k, not_recommend, excl, xv=xq)
-            res = np.where(it < 0, np.int64(-2147483648), it + 1).astype(np.int32)
-            return m, torch.from_numpy(res), torch.from_numpy(sc)
+        return m, be, self._row_weights(m, be), not_recommend, excl
+
+    def _device_rows(self, be, m, xq, not_recommend=None, excl=()):
+        """the operands of the backend's knn_* calls -> ((xp, xj, neighbors, q), {nr_p, nr_j, exclude0}, {xv})"""
         if self._d_tables is None:
             self._d_tables = (be.to_device(self.neighbors, torch.int32), be.to_device(self._weights(), torch.int64))
         nr_p = nr_j = None
         if not_recommend is not None and not_recommend.nnz:
             nr_p, nr_j = be.to_device(not_recommend.indptr, torch.int32), be.to_device(not_recommend.indices, torch.int32)
-        d_ex = be.to_device(excl, torch.int32) if excl.size else None
+        d_ex = be.to_device(excl, torch.int32) if len(excl) else None
         kw = {} if xq is None else {"xv": be.to_device(xq, torch.int64)}
-        res, sc = be.knn_recommend(be.to_device(m.indptr, torch.int32), be.to_device(m.indices, torch.int32), self._d_tables[0],
-                                   self._d_tables[1], k, nr_p, nr_j, d_ex, ws_rows=ws_rows, **kw)
+        rows = (be.to_device(m.indptr, torch.int32), be.to_device(m.indices, torch.int32), self._d_tables[0], self._d_tables[1])
+        return rows, {"nr_p": nr_p, "nr_j": nr_j, "exclude0": d_ex}, kw
+
+    def _pattern(self, pairs, m, what):
+        """`pairs` (a scipy sparse of x's shape) as a canonical CSR pattern of ones: columns ascending, duplicates merged, every
+        stored position kept (a stored zero too)"""
+        if not sp.issparse(pairs):
+            raise TypeError("'%s' should be a 'sparseMatrix'" % what)
+        if pairs.shape != m.shape:
+            raise ValueError("%s must have the shape of x" % what)
+        pat = sp.csr_matrix(pairs, dtype=np.float64, copy=True)
+        pat.data[:] = 1.0
+        return canonical_pattern(pat)
+
+    def _lists(self, x, k, not_recommend, items_exclude, ws_rows=0, candidates=None):
+        """-> (m: x as a canonical pattern, items int32 (n, k) 1-based with NA_integer_, scores int64 (n, k)), as tensors of the
+        backend; candidates: a scipy sparse of x's shape, or None (the whole catalogue)"""
+        m, be, xq, not_recommend, excl = self._rows(x, not_recommend, items_exclude)
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError("k must be an integer >= 1")
+        if k > _lib.KNN_MAX_TOPK:
+            raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "predict: k > 1024 is not on the device path")
+        cand = None if candidates is None else self._pattern(candidates, m, "candidates")
+        if not hasattr(be, "knn_recommend" if cand is None else "knn_top_candidates"):
+            if cand is None:
+                it, sc = knn_recommend_reference(m, self.neighbors, self._weights(), k, not_recommend, excl, xv=xq)
+            else:
+                it, sc = knn_candidates_reference(m, self.neighbors, self._weights(), cand, k, not_recommend, excl, xv=xq)
+            res = np.where(it < 0, np.int64(-2147483648), it + 1).astype(np.int32)
+            return m, torch.from_numpy(res), torch.from_numpy(sc)
+        rows, filters, kw = self._device_rows(be, m, xq, not_recommend, excl)
+        if cand is None:
+            res, sc = be.knn_recommend(*rows, k, filters["nr_p"], filters["nr_j"], filters["exclude0"], ws_rows=ws_rows, **kw)
+        else:
+            res, sc = be.knn_top_candidates(*rows, k, be.to_device(cand.indptr, torch.int32), be.to_device(cand.indices, torch.int32),
+                                            ws_rows=ws_rows, **filters, **kw)
         return m, res, sc
 
-    def predict(self, x, k, not_recommend="x", items_exclude=(), ws_rows=0):
+    def predict(self, x, k, not_recommend="x", items_exclude=(), ws_rows=0, candidates=None):
         """the k best items of every row of x, with the conventions of `WRMF.predict`: `not_recommend` (default: x itself; None =
         nothing) and `items_exclude` (0-based) are skipped; -> `TopItems` (n x k, 0-based, -1 where fewer than k items are
         admissible) with `.scores` (float64: score / 2^30, the raw sum for "count", score / (s_l 2^30 / max(sim)) for the weighted
-        kinds; NaN in the padding).  1 <= k <= 1024."""
-        _, res, sc = self._lists(x, k, not_recommend, items_exclude, ws_rows)
+        kinds; NaN in the padding).  1 <= k <= 1024.
+
+        `candidates` (a scipy sparse of x's shape; its values are ignored): every row is ranked within its own stored positions
+        -- two-stage serving, a catalogue slice per user, sampled-negative evaluation.  The filters still apply; candidates of
+        score 0 are ranked; a list is shorter than k only when fewer than k candidates are admissible.  The order is ItemKNN's
+        own -- score descending, equal scores to the SMALLER item -- and NOT the reference heap's rule that
+        `WRMF.predict(candidates=)` follows.  `candidates` holding every item reproduces `predict(x, k)` exactly."""
+        _, res, sc = self._lists(x, k, not_recommend, items_exclude, ws_rows, candidates)
+        return self._top_items(res, sc)
+
+    def _scale(self, s):
+        """integer scores -> what `.scores` reports (float64)"""
+        s = np.asarray(s).astype(np.float64)
+        if self._weighted:
+            return s / (np.float64(self._ops.scale_l) * np.float64(self._q[1]))
+        if self._similarity != "count":
+            return s / np.float64(Q_ONE)
+        return s
+
+    def _top_items(self, res, sc):
         idx = res.cpu().numpy().astype(np.int64)
         pad = idx == -2147483648
         out = np.where(pad, -1, idx - 1).view(TopItems)
-        s = sc.cpu().numpy().astype(np.float64)
-        if self._weighted:
-            s = s / (np.float64(self._ops.scale_l) * np.float64(self._q[1]))
-        elif self._similarity != "count":
-            s = s / np.float64(Q_ONE)
-        out.scores = np.where(pad, np.nan, s)
+        out.scores = np.where(pad, np.nan, self._scale(sc.cpu().numpy()))
         return out
 
-    def evaluate(self, x, actual, k, not_recommend="x", items_exclude=(), metrics=("ap", "ndcg")):
+    def sample_negatives(self, x, n, actual=None, not_recommend="x", items_exclude=(), seed=None, weights=None):
+        """`WRMF.sample_negatives` for the shape of x: the candidate matrix of a sampled-metric evaluation -- every row's stored
+        positions of `actual` plus min(n, admissible) items drawn without replacement from those neither in `not_recommend`, nor
+        in `actual`, nor in `items_exclude`.  The negatives depend on (seed, row, the row's exclusions, n_items, n) alone, so they
+        ARE the ones `WRMF.sample_negatives(x, n, actual=, seed=)` returns for that seed.  `seed` is required: ItemKNN has no
+        generator to draw one from."""
+        if seed is None:
+            raise ValueError("sample_negatives needs a seed: ItemKNN has no generator to draw one from")
+        self._one_rank()
+        return WRMF(backend=self._backend()).sample_negatives(x, n, actual=actual, not_recommend=not_recommend,
+                                                              items_exclude=items_exclude, seed=seed, weights=weights)
+
+    def score(self, x, pairs):
+        """the model's score of the rows of x at given (user, item) cells: a scipy CSR matrix (float64) with the pattern of `pairs`
+        (x's shape; columns sorted, duplicates merged, stored zeros are positions too) and, as values, the score scaled exactly as
+        `predict`'s `.scores` are.  Nothing is masked: an item of the row's own history has its score too."""
+        m, be, xq, _, _ = self._rows(x, None)
+        pat = self._pattern(pairs, m, "pairs")
+        if not hasattr(be, "knn_score_pairs"):
+            sc = knn_score_pairs_reference(m, self.neighbors, self._weights(), pat, xv=xq)
+        else:
+            rows, _, kw = self._device_rows(be, m, xq)
+            sc = be.knn_score_pairs(*rows, be.to_device(pat.indptr, torch.int32), be.to_device(pat.indices, torch.int32), **kw).cpu().numpy()
+        return sp.csr_matrix((self._scale(sc), pat.indices, pat.indptr), shape=pat.shape)
+
+    def _ranks(self, x, actual, not_recommend, items_exclude, ws_rows=0):
+        """-> (be, actual as canonical CSR, (above, tied, n_adm) as tensors of the backend)"""
+        from .metrics import canonical_actual
+        m, be, xq, not_recommend, excl = self._rows(x, not_recommend, items_exclude)
+        if not sp.issparse(actual):
+            raise TypeError("'actual' should be a 'sparseMatrix'")
+        if actual.shape != m.shape:
+            raise ValueError("actual must have the shape of x")
+        act = canonical_actual(actual, m.shape[0])
+        if not hasattr(be, "knn_held_out_ranks"):
+            got = knn_ranks_reference(m, self.neighbors, self._weights(), act, not_recommend, excl, xv=xq)
+            return be, act, tuple(be.to_device(v, torch.int32) for v in got)
+        rows, filters, kw = self._device_rows(be, m, xq, not_recommend, excl)
+        got = be.knn_held_out_ranks(*rows, be.to_device(act.indptr, torch.int32), be.to_device(act.indices, torch.int32), ws_rows=ws_rows,
+                                    **filters, **kw)
+        return be, act, got
+
+    def held_out_ranks(self, x, actual, not_recommend="x", items_exclude=(), ws_rows=0):
+        """where every held-out interaction stands among ALL the items the user could be shown, by the model's integer score:
+        `WRMF.held_out_ranks` for this model.  The admissible items of a row are those outside its `not_recommend` row (default:
+        x itself) and outside `items_exclude`; for every stored entry (u, h) of `actual` (x's shape; stored zeros are entries):
+        above = admissible items scored strictly higher than h, tied = other admissible items with an equal score, -1 / -1 when h
+        itself is not admissible.  -> (above, tied: scipy CSR (int32) with the canonical pattern of `actual`; n_adm: the
+        admissible items per row, int32).  The 0-based midrank of an entry is above + tied / 2."""
+        _, act, (above, tied, n_adm) = self._ranks(x, actual, not_recommend, items_exclude, ws_rows)
+        mk = lambda v: sp.csr_matrix((v.cpu().numpy().astype(np.int32), act.indices.copy(), act.indptr.copy()), shape=act.shape)
+        return mk(above), mk(tied), n_adm.cpu().numpy().astype(np.int32)
+
+    def evaluate_ranks(self, x, actual, not_recommend="x", items_exclude=(), per_user=False):
+        """the full-ranking metrics of the held-out interactions `actual` (values = weights) from `held_out_ranks`' counts, with
+        the formulas and the return shape of `WRMF.evaluate_ranks`: {"mpr", "auc", "mrr", "n"}; per_user=True adds "mpr_per_user",
+        "auc_per_user", "mrr_per_user" and "n_adm_per_user"."""
+        from .metrics import rank_totals
+        be, act, (above, tied, n_adm) = self._ranks(x, actual, not_recommend, items_exclude)
+        fn = be.rank_summary if hasattr(be, "rank_summary") else WRMF._rank_summary_host
+        mpr, auc, mrr, sums = fn(be.to_device(act.indptr, torch.int32), be.to_device(act.data, torch.float64), above, tied, n_adm)
+        sums = sums.cpu().numpy()
+        per = {"mpr": mpr.cpu().numpy(), "auc": auc.cpu().numpy(), "mrr": mrr.cpu().numpy()}
+        out = rank_totals({"sum_w": sums[:, 0], "sum_w_pct": sums[:, 1], "P": sums[:, 2], "auc": per["auc"], "mrr": per["mrr"]})
+        if per_user:
+            out.update({name + "_per_user": v for name, v in per.items()})
+            out["n_adm_per_user"] = n_adm.cpu().numpy().astype(np.int32)
+        return out
+
+    def evaluate(self, x, actual, k, not_recommend="x", items_exclude=(), metrics=("ap", "ndcg"), candidates=None, negatives=None,
+                 seed=None, negative_weights=None):
         """`predict(x, max(k), ...)` once, scored against the held-out `actual` by the package's list metrics: "ap", "ndcg"
         (`rsparse_amd.metrics.ranking_metrics`), "precision", "recall", "hit", "mrr", "coverage" (`topk_metrics`), "popularity"
         and "novelty" (`list_metrics`, with the fitted item counts).  k: a cutoff or a strictly ascending sequence of them; a
-        sequence returns (n, T) arrays (coverage: (T,)).  The lists stay on the device."""
+        sequence returns (n, T) arrays (coverage: (T,)).  The lists stay on the device.
+
+        `candidates`: as in `predict` -- every metric is computed on the lists ranked within the rows' candidates.
+        `negatives=n` with `seed` makes those candidates itself, the sampled protocol of `WRMF.evaluate(negatives=)`: every row's
+        held-out items against n negatives, exactly `candidates=self.sample_negatives(x, n, actual, not_recommend,
+        items_exclude, seed, negative_weights)` -- the negatives `WRMF.sample_negatives` returns for that seed.  `seed` is
+        required with `negatives`; `negatives` excludes `candidates`; `negative_weights` needs `negatives`."""
         from .metrics import HIT_METRICS, LIST_METRICS, NEVER_SEEN, canonical_actual, check_cutoffs, coverage_from_first_seen, self_information
         metrics = tuple(metrics)
         known = ("ap", "ndcg") + HIT_METRICS + ("coverage",) + LIST_METRICS
@@ -602,7 +837,16 @@ class ItemKNN:
             raise ValueError("metrics must name some of %s" % ", ".join(repr(name) for name in known))
         scalar_k = not isinstance(k, (tuple, list, np.ndarray, range))
         cutoffs = check_cutoffs((int(k),) if scalar_k else k)
-        m, res, _ = self._lists(x, int(cutoffs[-1]), not_recommend, items_exclude)
+        if negatives is not None and candidates is not None:
+            raise ValueError("negatives and candidates exclude each other: the negatives ARE the candidates")
+        if negative_weights is not None and negatives is None:
+            raise ValueError("negative_weights needs negatives: they weight the sampled negatives")
+        if negatives is not None:
+            if seed is None:
+                raise ValueError("negatives needs a seed: ItemKNN has no generator to draw one from")
+            candidates = self.sample_negatives(x, negatives, actual=actual, not_recommend=not_recommend, items_exclude=items_exclude,
+                                               seed=seed, weights=negative_weights)
+        m, res, _ = self._lists(x, int(cutoffs[-1]), not_recommend, items_exclude, candidates=candidates)
         act = canonical_actual(actual, m.shape[0])
         be = self._backend()
         n_items = self.neighbors.shape[0]
