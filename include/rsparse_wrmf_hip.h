@@ -1346,7 +1346,11 @@ int rsparse_hip_take_numeric_failures(int64_t* unresolved_out, int64_t* fallback
  * k x k Gramian partials (+ sum(F^2), max |F|), an in-place all-gather of every solved sub-block (overlapped with the next
  * sub-block's solve on a second stream) and one all-reduce of the loss terms -- SURVEY.md 8(e).  The per-rank arithmetic is
  * layer (2)'s, row for row: results do not depend on the number of ranks except through the summation order of the Gramian
- * and of the loss (as the reference's do not depend on OMP_NUM_THREADS except through its loss reduction).
+ * and of the loss (as the reference's do not depend on OMP_NUM_THREADS except through its loss reduction) -- and, with
+ * implicit feedback on the matrix-core paths, through the power of two that scales their fp16 operand terms: it is taken from
+ * the largest confidence among the values of a HANDLE, and the context holds one handle per rank and sub-block.  Explicit
+ * feedback has neither a Gramian nor such a scale: its factors are the same bits at every number of ranks and sub-blocks
+ * (tests/test_ctx_rows.py).
  *
  * comm_kind: RSPARSE_HIP_COMM_RCCL -- one device per rank, collectives = RCCL over xGMI (ncclCommInitAll; librccl is loaded
  * with dlopen when the context is created, a single-GPU user never needs it); RSPARSE_HIP_COMM_SHARED -- the ranks are threads
@@ -1364,7 +1368,12 @@ int rsparse_hip_ctx_destroy(rsparse_hip_ctx* ctx);
 /* The interaction matrix in both orientations as the R driver holds them (R/model_WRMF.R:184-191): c_ui = users x items as
  * dgCMatrix slots (ui_p int32[n_item + 1], ui_i = user ids, ui_x), c_iu = its transpose (iu_p int32[n_user + 1], iu_i = item
  * ids, iu_x); host arrays, 0-based, row indices ascending inside a column.  Every rank uploads its own blocks only.
- * n_sub_users / n_sub_items: sub-blocks per rank and half-iteration (0 = default: 1 for one rank, else 4). */
+ * n_sub_users / n_sub_items: sub-blocks per rank and half-iteration (0 = default: 1 for one rank, else 4).
+ * Both pointer arrays are checked before any rank is asked to do anything (from 0, non-decreasing, the same number of
+ * non-zeros in the two orientations, indices inside the matrix): RSPARSE_HIP_ERR_INVALID with the array's name, and the
+ * context is as it was before the call.  A call that passes these checks DROPS THE FACTORS of the context (the replicas are
+ * stored in the order of the old matrix's blocks): until the next rsparse_hip_ctx_set_factors, half_iteration and
+ * get_factors return RSPARSE_HIP_ERR_INVALID. */
 int rsparse_hip_ctx_set_matrix(rsparse_hip_ctx* ctx, int n_user, int n_item, const int32_t* ui_p, const int32_t* ui_i,
                                const double* ui_x, const int32_t* iu_p, const int32_t* iu_i, const double* iu_x,
                                int n_sub_users, int n_sub_items);

@@ -81,23 +81,32 @@ struct Workspace {
       GrowBufBase::release_all(all);
       device = dev;
     }
-    // the fixed blocks that start zeroed
+    // The fixed blocks that start zeroed.  hipMemset of device memory may return before it has run, and it runs on the null
+    // stream, which does not order the work of a caller's hipStreamNonBlocking stream (the rank threads of wrmf_ctx.cpp): the
+    // zeroing of ne_stats then landed between a first call's scan and the kernels that read max |X| from it, and their fp16
+    // operand scale became that of 1e-30 -- NaN rows (tests/test_ctx_rows.py).  So the thread waits for it.
+    bool zeroed = false;
     if (!scalars) {
       HIP_TRY(scalars.ensure(16));
       HIP_TRY(hipMemset(scalars, 0, 16 * sizeof(double)));
+      zeroed = true;
     }
     if (!fails) {
       HIP_TRY(fails.ensure((size_t)(4 + kFailCap)));
       HIP_TRY(hipMemset(fails, 0, 4 * sizeof(int)));
+      zeroed = true;
     }
     if (!ne_stats) {
       HIP_TRY(ne_stats.ensure(4));
       HIP_TRY(hipMemset(ne_stats, 0, 4 * sizeof(unsigned)));
+      zeroed = true;
     }
     if (!zero_row) {
       HIP_TRY(zero_row.ensure(256));
       HIP_TRY(hipMemset(zero_row, 0, 256 * sizeof(float)));
+      zeroed = true;
     }
+    if (zeroed) HIP_TRY(hipStreamSynchronize(nullptr));
     return RSPARSE_HIP_OK;
   }
   int ensure_partials(size_t slots) {
@@ -1818,7 +1827,10 @@ int rsparse_hip_take_numeric_failures(int64_t* unresolved_out, int64_t* fallback
   if (!g_ws.fails) return RSPARSE_HIP_OK;
   int v[4] = {0, 0, 0, 0};
   HIP_TRY(hipMemcpy(v, g_ws.fails, sizeof(v), hipMemcpyDeviceToHost));   // (synchronises with the device)
-  if (v[0] | v[1] | v[2] | v[3]) HIP_TRY(hipMemset(g_ws.fails, 0, sizeof(v)));
+  if (v[0] | v[1] | v[2] | v[3]) {
+    HIP_TRY(hipMemset(g_ws.fails, 0, sizeof(v)));
+    HIP_TRY(hipStreamSynchronize(nullptr));   // (before a next call counts on a non-blocking stream: see ensure_device)
+  }
   // rows beyond the list's capacity could not be handed over: they count as unresolved, not as re-solved
   const int64_t lost = v[0] > kFailCap ? (int64_t)v[0] - kFailCap : 0;
   const int64_t sent = (int64_t)std::min(v[0], kFailCap) + v[2];

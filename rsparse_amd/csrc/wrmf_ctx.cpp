@@ -38,61 +38,14 @@
 #include <vector>
 
 #include "../../include/rsparse_wrmf_hip.h"
+#include "wrmf_ctx_layout.h"
 #include "wrmf_internal.h"
 
 namespace rsparse_hip {
 namespace {
 
-// ---- who owns which rows, and where they are stored (engine.Layout) ----
-struct Lay {
-  int64_t n = 0;
-  int ws = 1, n_sub = 1;
-  std::vector<int64_t> b0, b1;   // block of rank r = [b0[r], b1[r])
-  int64_t Bs = 1, rows = 0;
-  void init(int64_t n_, const std::vector<int64_t>& edges, int n_sub_) {
-    n = n_; ws = (int)edges.size() - 1; n_sub = std::max(1, n_sub_);
-    b0.assign(edges.begin(), edges.end() - 1);
-    b1.assign(edges.begin() + 1, edges.end());
-    int64_t biggest = 1;
-    for (int r = 0; r < ws; r++) biggest = std::max(biggest, b1[r] - b0[r]);
-    Bs = (biggest + n_sub - 1) / n_sub;
-    rows = (int64_t)ws * n_sub * Bs;
-  }
-  void sub_rows(int r, int j, int64_t& c0, int64_t& c1) const {   // local rows of sub-block j of rank r
-    const int64_t nr = b1[r] - b0[r];
-    c0 = std::min(nr, (int64_t)j * Bs);
-    c1 = std::min(nr, (int64_t)(j + 1) * Bs);
-  }
-  int64_t sub_start(int r, int j) const { return (int64_t)j * ws * Bs + (int64_t)r * Bs; }
-  int64_t slab_start(int j) const { return (int64_t)j * ws * Bs; }
-  int64_t to_storage(int64_t g) const {
-    // the LAST block whose start is <= g (empty blocks share their start with the next one)
-    const int r = (int)(std::upper_bound(b0.begin(), b0.end(), g) - b0.begin()) - 1;
-    const int64_t loc = g - b0[r], j = loc / Bs;
-    return j * ((int64_t)ws * Bs) + (int64_t)r * Bs + (loc - j * Bs);
-  }
-};
-
-// contiguous blocks balanced by non-zeros: rank r starts where the prefix sum of the row lengths first reaches r / ws of the
-// total (engine.balanced_bounds)
-std::vector<int64_t> balanced_edges(const int32_t* p, int64_t n, int ws) {
-  std::vector<int64_t> e((size_t)ws + 1, n);
-  e[0] = 0;
-  if (ws <= 1 || n == 0) return e;
-  const int64_t total = (int64_t)p[n] - (int64_t)p[0];
-  for (int r = 1; r < ws; r++) {
-    if (total > 0) {
-      const int64_t target = total * r / ws + (int64_t)p[0];
-      // first row i with prefix (p[i + 1]) >= target, + 1
-      const int32_t* it = std::lower_bound(p + 1, p + n + 1, target, [](int32_t a, int64_t t) { return (int64_t)a < t; });
-      e[(size_t)r] = std::min<int64_t>(n, (int64_t)(it - (p + 1)) + 1);
-    } else {
-      e[(size_t)r] = n * r / ws;
-    }
-  }
-  for (int r = 1; r <= ws; r++) e[(size_t)r] = std::max(e[(size_t)r], e[(size_t)r - 1]);
-  return e;
-}
+// who owns which rows and where they are stored (Lay, balanced_edges), and the check of the caller's column pointers:
+// wrmf_ctx_layout.h, host-only
 
 struct HostBarrier {
   std::mutex m;
@@ -285,15 +238,20 @@ namespace {
 void worker(RankState* rs) {
   (void)hipSetDevice(rs->device);
   for (;;) {
-    std::function<void(RankState&)> job;
-    {
-      std::unique_lock<std::mutex> lk(rs->m);
-      rs->cv.wait(lk, [&] { return rs->has_job || rs->quit; });
-      if (rs->quit) return;
-      job = rs->job;
-      rs->has_job = false;
+    try {   // the copy of the job and the job itself: an error code, never std::terminate across the ABI
+      std::function<void(RankState&)> job;
+      {
+        std::unique_lock<std::mutex> lk(rs->m);
+        rs->cv.wait(lk, [&] { return rs->has_job || rs->quit; });
+        if (rs->quit) return;
+        rs->has_job = false;
+        job = rs->job;
+      }
+      job(*rs);
+    } catch (const std::exception& e) {
+      rs->rc = RSPARSE_HIP_ERR_RUNTIME;
+      rs->err = std::string("exception in the rank thread: ") + e.what();
     }
-    job(*rs);
     {
       std::lock_guard<std::mutex> lk(rs->m);
       rs->done = true;
@@ -371,6 +329,15 @@ void upload_counts(RankState& rs, const Lay& lay, const int32_t* p, float** d_ou
   CTX_HIP(rs, hipMemcpy(*d_out, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice));
 }
 
+// The bodies of the entry points allocate on the calling thread (layouts, storage-order images, the jobs' closures): a
+// std::exception there becomes ERR_RUNTIME with its text.
+#define CTX_TRY try {
+#define CTX_CATCH                                                                                          \
+  }                                                                                                        \
+  catch (const std::exception& e_) {                                                                       \
+    return capi_fail(RSPARSE_HIP_ERR_RUNTIME, std::string("exception in the context: ") + e_.what());      \
+  }
+
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace
@@ -379,6 +346,7 @@ double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::
 extern "C" {
 
 int rsparse_hip_ctx_create(int n_ranks, const int* device_ids, int comm_kind, rsparse_hip_ctx** out) {
+  CTX_TRY
   if (!out) return capi_fail(RSPARSE_HIP_ERR_INVALID, "out is NULL");
   *out = nullptr;
   if (n_ranks < 1 || n_ranks > 64) return capi_fail(RSPARSE_HIP_ERR_INVALID, "n_ranks must be in 1..64");
@@ -426,6 +394,7 @@ int rsparse_hip_ctx_create(int n_ranks, const int* device_ids, int comm_kind, rs
   }
   *out = ctx.release();
   return RSPARSE_HIP_OK;
+  CTX_CATCH
 }
 
 int rsparse_hip_ctx_destroy(rsparse_hip_ctx* ctx) {
@@ -454,10 +423,13 @@ int rsparse_hip_ctx_destroy(rsparse_hip_ctx* ctx) {
 int rsparse_hip_ctx_set_matrix(rsparse_hip_ctx* ctx, int n_user, int n_item, const int32_t* ui_p, const int32_t* ui_i,
                                const double* ui_x, const int32_t* iu_p, const int32_t* iu_i, const double* iu_x,
                                int n_sub_users, int n_sub_items) {
+  CTX_TRY
   if (!ctx) return capi_fail(RSPARSE_HIP_ERR_INVALID, "ctx is NULL");
   if (n_user < 0 || n_item < 0 || !ui_p || !iu_p) return capi_fail(RSPARSE_HIP_ERR_INVALID, "bad matrix arguments");
-  const int64_t nnz = (int64_t)ui_p[n_item] - ui_p[0];
-  if (nnz != (int64_t)iu_p[n_user] - iu_p[0]) return capi_fail(RSPARSE_HIP_ERR_INVALID, "the two orientations hold different numbers of non-zeros");
+  // on the calling thread, before anything is sized from the pointers (make_subs runs on the rank threads)
+  const std::string bad_ptrs = check_matrix_ptrs(ui_p, n_item, iu_p, n_user);
+  if (!bad_ptrs.empty()) return capi_fail(RSPARSE_HIP_ERR_INVALID, bad_ptrs);
+  const int64_t nnz = ui_p[n_item];
   if (nnz > 0 && (!ui_i || !ui_x || !iu_i || !iu_x)) return capi_fail(RSPARSE_HIP_ERR_INVALID, "index / value arrays are NULL");
   for (int64_t e = 0; e < nnz; e++) {
     if (ui_i[e] < 0 || ui_i[e] >= n_user) return capi_fail(RSPARSE_HIP_ERR_INVALID, "row index of c_ui outside [0, n_user)");
@@ -470,10 +442,13 @@ int rsparse_hip_ctx_set_matrix(rsparse_hip_ctx* ctx, int n_user, int n_item, con
   ctx->n_user = n_user; ctx->n_item = n_item; ctx->nnz = nnz;
   ctx->n_sub_max = std::max(ctx->lay_u.n_sub, ctx->lay_i.n_sub);
   ctx->have_matrix = false;
+  // the replicas, loss_sub and the exchange buffers were sized for the old layout: a new matrix starts without factors
+  ctx->have_factors = false;
+  ctx->k = 0;
   const Lay& lu = ctx->lay_u;
   const Lay& li = ctx->lay_i;
   const int rc = run_all(ctx, [&](RankState& rs) {
-    free_rank_buffers(rs, true, false);
+    free_rank_buffers(rs, true, true);
     // item half: columns = my items (c_ui), rows = users -> the user layout's storage rows; user half likewise
     make_subs(rs, li, lu, ui_p, ui_i, ui_x, rs.sub_items);
     if (rs.rc) return;
@@ -486,9 +461,11 @@ int rsparse_hip_ctx_set_matrix(rsparse_hip_ctx* ctx, int n_user, int n_item, con
   if (rc) return rc;
   ctx->have_matrix = true;
   return RSPARSE_HIP_OK;
+  CTX_CATCH
 }
 
 int rsparse_hip_ctx_set_factors(rsparse_hip_ctx* ctx, int rank, const float* U, const float* V) {
+  CTX_TRY
   if (!ctx || !ctx->have_matrix) return capi_fail(RSPARSE_HIP_ERR_INVALID, "set the matrix first");
   if (rank < 1 || rank > RSPARSE_HIP_MAX_RANK) return capi_fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank outside 1..256");
   if (!U || !V) return capi_fail(RSPARSE_HIP_ERR_INVALID, "U or V is NULL");
@@ -500,7 +477,12 @@ int rsparse_hip_ctx_set_factors(rsparse_hip_ctx* ctx, int rank, const float* U, 
   for (int64_t g = 0; g < ctx->n_user; g++) std::memcpy(&Us[(size_t)lu.to_storage(g) * k], U + (size_t)g * k, (size_t)k * sizeof(float));
   for (int64_t g = 0; g < ctx->n_item; g++) std::memcpy(&Vs[(size_t)li.to_storage(g) * k], V + (size_t)g * k, (size_t)k * sizeof(float));
   const int ws = ctx->ws, nsm = ctx->n_sub_max;
+  // (set_matrix dropped the factors with the old layout, so equal k and have_factors mean buffers of exactly these sizes)
   const bool realloc_ = ctx->k != k || !ctx->have_factors;
+  if (realloc_) {   // a failure midway leaves a context without factors, not one with half of them
+    ctx->have_factors = false;
+    ctx->k = 0;
+  }
   const int rc = run_all(ctx, [&](RankState& rs) {
     if (realloc_) {
       free_rank_buffers(rs, false, true);
@@ -522,9 +504,11 @@ int rsparse_hip_ctx_set_factors(rsparse_hip_ctx* ctx, int rank, const float* U, 
   ctx->k = k;
   ctx->have_factors = true;
   return RSPARSE_HIP_OK;
+  CTX_CATCH
 }
 
 int rsparse_hip_ctx_get_factors(rsparse_hip_ctx* ctx, float* U, float* V) {
+  CTX_TRY
   if (!ctx || !ctx->have_factors) return capi_fail(RSPARSE_HIP_ERR_INVALID, "no factors in the context");
   const int k = ctx->k;
   const Lay& lu = ctx->lay_u;
@@ -540,12 +524,18 @@ int rsparse_hip_ctx_get_factors(rsparse_hip_ctx* ctx, float* U, float* V) {
   if (U) for (int64_t g = 0; g < ctx->n_user; g++) std::memcpy(U + (size_t)g * k, &Us[(size_t)lu.to_storage(g) * k], (size_t)k * sizeof(float));
   if (V) for (int64_t g = 0; g < ctx->n_item; g++) std::memcpy(V + (size_t)g * k, &Vs[(size_t)li.to_storage(g) * k], (size_t)k * sizeof(float));
   return RSPARSE_HIP_OK;
+  CTX_CATCH
 }
 
 int rsparse_hip_ctx_half_iteration(rsparse_hip_ctx* ctx, int side, int implicit, double lambda, unsigned solver, unsigned cg_steps,
                                    int dynamic_lambda, double* loss_out) {
+  CTX_TRY
   if (!ctx || !ctx->have_matrix || !ctx->have_factors) return capi_fail(RSPARSE_HIP_ERR_INVALID, "the context needs a matrix and factors");
   if (side != RSPARSE_HIP_SIDE_ITEMS && side != RSPARSE_HIP_SIDE_USERS) return capi_fail(RSPARSE_HIP_ERR_INVALID, "side must be 0 (items) or 1 (users)");
+  // Everything layer (2) refuses on argument grounds for the no-bias variants is refused here, on the calling thread: a rank
+  // whose sub-blocks are all empty makes no layer-(2) call, and would wait in a collective that its peers never enter.
+  // (The rank was checked by set_factors; the handles and device pointers are the context's own.)
+  if (solver > RSPARSE_SOLVER_NNLS) return capi_fail(RSPARSE_HIP_ERR_INVALID, "unknown solver code");
   const int k = ctx->k, ws = ctx->ws;
   const Lay& layF = side == RSPARSE_HIP_SIDE_ITEMS ? ctx->lay_u : ctx->lay_i;   // fixed side
   const Lay& layS = side == RSPARSE_HIP_SIDE_ITEMS ? ctx->lay_i : ctx->lay_u;   // solved side
@@ -649,9 +639,11 @@ int rsparse_hip_ctx_half_iteration(rsparse_hip_ctx* ctx, int side, int implicit,
     *loss_out = ctx->nnz > 0 ? (r0.h_scal[1] + lambda * r0.h_scal[0]) / (double)ctx->nnz : 0.0;
   }
   return RSPARSE_HIP_OK;
+  CTX_CATCH
 }
 
 int rsparse_hip_ctx_take_numeric_failures(rsparse_hip_ctx* ctx, int64_t* unresolved_out, int64_t* fallback_out) {
+  CTX_TRY
   if (!ctx || !unresolved_out) return capi_fail(RSPARSE_HIP_ERR_INVALID, "NULL argument");
   std::vector<int64_t> bad((size_t)ctx->ws, 0), fell((size_t)ctx->ws, 0);
   const int rc = run_all(ctx, [&](RankState& rs) {
@@ -665,6 +657,7 @@ int rsparse_hip_ctx_take_numeric_failures(rsparse_hip_ctx* ctx, int64_t* unresol
     if (fallback_out) *fallback_out += fell[(size_t)r];
   }
   return RSPARSE_HIP_OK;
+  CTX_CATCH
 }
 
 int rsparse_hip_ctx_info(const rsparse_hip_ctx* ctx, int64_t info_out[16], double times_out[2]) {

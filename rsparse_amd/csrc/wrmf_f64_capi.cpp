@@ -93,6 +93,7 @@ struct WorkspaceF64 {
     if (!scalars) {
       HIP_TRY(scalars.ensure(16));
       HIP_TRY(hipMemset(scalars, 0, 16 * sizeof(double)));
+      HIP_TRY(hipStreamSynchronize(nullptr));   // (the null stream does not order a caller's non-blocking stream: wrmf_capi.cpp, ensure_device)
     }
     HIP_TRY(rinit.ensure(kRhsInitDoubles));
     return RSPARSE_HIP_OK;

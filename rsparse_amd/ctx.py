@@ -47,6 +47,7 @@ class MultiGpuALS:
         n_user, n_item = c_ui.shape
         _lib.check(self.lib.rsparse_hip_ctx_set_matrix(self.h, int(n_user), int(n_item), *[_vp(a) for a in self._keep],
                                                        int(n_sub[0]), int(n_sub[1])))
+        self.rank = None                 # an accepted matrix drops the factors of the context (rsparse_hip_ctx_set_matrix)
         self._keep = None
         self.shape = (int(n_user), int(n_item))
 
@@ -59,8 +60,9 @@ class MultiGpuALS:
         _lib.check(self.lib.rsparse_hip_ctx_set_factors(self.h, self.rank, _vp(U), _vp(V)))
 
     def get_factors(self):
-        U = np.empty((self.shape[0], self.rank), dtype=np.float32)
-        V = np.empty((self.shape[1], self.rank), dtype=np.float32)
+        k = self.info()["rank"]          # the library's own record: 0 without factors, and the call below then says so
+        U = np.empty((self.shape[0], k), dtype=np.float32)
+        V = np.empty((self.shape[1], k), dtype=np.float32)
         _lib.check(self.lib.rsparse_hip_ctx_get_factors(self.h, _vp(U), _vp(V)))
         return U, V
 
