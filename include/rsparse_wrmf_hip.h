@@ -931,6 +931,63 @@ int rsparse_hip_knn_held_out_ranks(const int32_t* x_p, const int32_t* x_j, const
                                    int32_t* tied, int32_t* n_adm);
 
 /* ------------------------------------------------------------------------------------------------
+ * EASE (Steck 2019): the item Gram matrix on the device, and top-k lists scored by a dense items x items weight matrix
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The definition (rsparse_amd/ease.py states it in numpy).  On the canonical binary pattern of a users x items matrix, G = X^T X:
+ * c_ij off the diagonal (the co-occurrence count, an exact integer), n_j on it.  With P = (G + lambda I)^-1 the weights are
+ * B_ij = -P_ij / P_jj, B_jj = 0; the factorisation is the caller's (dense linear algebra is not part of this library).  A user
+ * (a row of a pattern x) is scored by
+ *     score_u = sum over the stored items i of the row, in ascending stored order, of double(B[i, :])
+ * a sequential sum in double, one rounding per step (a float B converts exactly).  The list of u is the k items of largest score
+ * among those neither in the row's not_recommend entries nor in items_exclude, ties to the smaller item.  The order is that of
+ * the 64-bit KEY of the double -- its bits flipped if it is negative, otherwise its sign bit set --, and the key is what
+ * d_scores returns: key >> 63 ? key ^ (1 << 63) : ~key are the double's bits again.  An accumulator that starts at +0.0 never
+ * becomes -0.0, and no finite score has the key 0 or all ones (B must be finite).
+ *
+ * Both entries work in the dense rows of the ItemKNN workspace, a batch at a time, with its kernels (wrmf_ease.hip,
+ * wrmf_itemknn.hip): rows per batch = ws_rows, or with ws_rows = 0 what RSPARSE_HIP_KNN_WS_BYTES holds (a row is n_items cells of
+ * 4 bytes for the Gram rows, of 8 for the lists).  The scoring kernel gives a workgroup one row and one tile of
+ * RSPARSE_HIP_EASE_TILE_BYTES of columns, stages the row's indices RSPARSE_HIP_EASE_CHUNK at a time and keeps
+ * RSPARSE_HIP_EASE_AHEAD rows of B in flight per thread.  No atomics on floats: a repeated call returns the same bits.
+ * RSPARSE_HIP_EASE_MAX_ITEMS bounds the catalogue: an items x items matrix of doubles is 8 GiB there, and a fit holds three of
+ * them at its peak (G + lambda I, its Cholesky factor, the inverse) beside B. */
+#define RSPARSE_HIP_EASE_MAX_ITEMS 32768
+#define RSPARSE_HIP_EASE_TILE_BYTES 4096
+#define RSPARSE_HIP_EASE_CHUNK 1024
+#define RSPARSE_HIP_EASE_AHEAD 8
+
+/* Rows [item0, item1) of G + lambda I: d_out[(i - item0) ld_out + j] = c_ij for j != i, double(n_i) + lambda (one rounding) for
+ * j == i.  d_ip / d_iu, d_up / d_uj: the two orientations of the pattern, as rsparse_hip_cooc_neighbors_device takes them.
+ * Reads d_ip[item0 .. item1] back (waits for `stream` once), then enqueues without synchronisation.
+ * NULL pointer, negative dimension, not 0 <= item0 <= item1 <= n_items, ws_rows < 0, ld_out < n_items, lambda < 0 or not finite
+ * -> ERR_INVALID; n_items > RSPARSE_HIP_EASE_MAX_ITEMS -> ERR_UNSUPPORTED; all before a device is touched. */
+int rsparse_hip_item_gram_device(const int32_t* d_ip, const int32_t* d_iu, const int32_t* d_up, const int32_t* d_uj, int n_users,
+                                 int n_items, int item0, int item1, double lambda, double* d_out, size_t ld_out, int64_t ws_rows,
+                                 void* stream);
+
+/* The lists of the n_rows rows of the pattern (d_xp, d_xj) under d_B: n_items rows of ld_B elements (float, or double with
+ * b_is_double), 16-byte aligned, ld_B >= n_items and a multiple of 16 bytes (a multiple of 256 bytes keeps every row aligned to
+ * a cache line pair; what lies beyond n_items in a row is read and never used).  d_nr_p / d_nr_j / d_excl0 / d_items: as
+ * rsparse_hip_knn_recommend_device; d_scores: the keys, 0 in the padding.  A column of d_xj outside [0, n_items) is skipped.
+ * Reads d_xp back (waits for `stream` once).  NULL pointer, negative dimension, k < 1, ws_rows < 0, nr_p without nr_j, a bad exclude, a bad ld_B or
+ * alignment -> ERR_INVALID; k > RSPARSE_HIP_KNN_MAX_TOPK, n_items > RSPARSE_HIP_EASE_MAX_ITEMS -> ERR_UNSUPPORTED; all before a
+ * device is touched. */
+int rsparse_hip_ease_recommend_device(const int32_t* d_xp, const int32_t* d_xj, int n_rows, int n_items, const void* d_B, size_t ld_B,
+                                      int b_is_double, const int32_t* d_nr_p, const int32_t* d_nr_j, const int32_t* d_excl0,
+                                      int n_exclude, int k, int64_t ws_rows, int32_t* d_items, uint64_t* d_scores, void* stream);
+
+/* host-array forms.  p / j: the dgRMatrix slots of the users x items pattern, with the checks of rsparse_hip_cooc_neighbors;
+ * out: n_items x n_items doubles (the matrix is symmetric: either layout). */
+int rsparse_hip_item_gram(const int32_t* p, const int32_t* j, int n_users, int n_items, double lambda, double* out);
+/* x_p / x_j, nr_p / nr_j (nullable), exclude (1-based), res (n_rows x k column-major, 1-based with NA_integer_): as
+ * rsparse_hip_knn_recommend, with its refusals.  B: n_items x n_items COLUMN-major (an R matrix), float or double; a non-finite
+ * entry -> ERR_INVALID.  scores: the doubles themselves, column-major, NaN where res is NA. */
+int rsparse_hip_ease_recommend(const int32_t* x_p, const int32_t* x_j, int n_rows, int n_items, const void* B, int b_is_double,
+                               const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude, int n_exclude, int k, int32_t* res,
+                               double* scores);
+
+/* ------------------------------------------------------------------------------------------------
  * why this item: per-item contributions to a score (Hu, Koren and Volinsky, section 5; `explain` of the `implicit` library)
  * ---------------------------------------------------------------------------------------------- */
 

@@ -14,6 +14,8 @@ Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit
   rsparse_amd.ItemKNN         item-based k-nearest-neighbours on the co-occurrence of items (cosine, Jaccard, count), integer
                               from end to end: neighbour table and top-k lists on the device, equal to the numpy definition;
                               with weighting= on quantised values: BM25 / TF-IDF cosine, dot, asymmetric cosine, P3alpha / RP3beta
+  rsparse_amd.EASE            the closed-form item-item model of Steck 2019: Gram rows and top-k lists under a dense items x items
+                              weight matrix on the device, equal to the numpy definition
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
   rsparse_amd.engine          device-resident, row-sharded driver (one process per GPU)
   rsparse_amd.synth           synthetic interaction matrices for the BASELINE configs
@@ -45,6 +47,9 @@ def __getattr__(name):
                 "weighted_cooccurrence_reference", "knn_score_pairs_reference", "knn_candidates_reference", "knn_ranks_reference"):
         from . import itemknn
         return getattr(itemknn, name)
+    if name in ("EASE", "ease_gram_reference", "ease_weights_reference", "ease_scores_reference", "ease_recommend_reference"):
+        from . import ease
+        return getattr(ease, name)
     if name == "metrics":
         import importlib
         return importlib.import_module(".metrics", __name__)

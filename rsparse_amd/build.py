@@ -17,7 +17,7 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 SRC = [CSRC / n for n in ("wrmf_kernels.hip", "wrmf_cgq.hip", "wrmf_cgp.hip", "wrmf_ne.hip", "wrmf_chol.hip", "wrmf_chol_wave.hip", "wrmf_chol_mf.hip", "wrmf_cg_mf.hip", "wrmf_chol_lr.hip",
-                          "wrmf_topk.hip", "wrmf_topk_large.hip", "wrmf_similar.hip", "wrmf_metrics.hip", "wrmf_hits.hip", "wrmf_lists.hip", "wrmf_diversity.hip", "wrmf_mmr.hip", "wrmf_ranks.hip", "wrmf_score.hip", "wrmf_softals.hip", "wrmf_itemknn.hip", "wrmf_candidates.hip", "wrmf_sample.hip", "wrmf_sample_weighted.hip", "wrmf_split.hip", "wrmf_confidence.hip", "wrmf_events.hip", "wrmf_explain.hip", "wrmf_init.hip", "wrmf_ingest.hip", "wrmf_nnls.hip", "wrmf_bias.hip", "wrmf_lu.hip",
+                          "wrmf_topk.hip", "wrmf_topk_large.hip", "wrmf_similar.hip", "wrmf_metrics.hip", "wrmf_hits.hip", "wrmf_lists.hip", "wrmf_diversity.hip", "wrmf_mmr.hip", "wrmf_ranks.hip", "wrmf_score.hip", "wrmf_softals.hip", "wrmf_itemknn.hip", "wrmf_ease.hip", "wrmf_candidates.hip", "wrmf_sample.hip", "wrmf_sample_weighted.hip", "wrmf_split.hip", "wrmf_confidence.hip", "wrmf_events.hip", "wrmf_explain.hip", "wrmf_init.hip", "wrmf_ingest.hip", "wrmf_nnls.hip", "wrmf_bias.hip", "wrmf_lu.hip",
                           "wrmf_f64.hip", "wrmf_wide.hip", "wrmf_wide_cg.hip", "wrmf_ctx_kernels.hip", "wrmf_schedule.cpp", "wrmf_capi.cpp", "wrmf_f64_capi.cpp", "wrmf_capi_host.cpp", "wrmf_ctx.cpp")]
 HEADERS = [CSRC / "wrmf_chol_mf.attrs.csv", CSRC / "wrmf_mf.h", CSRC / "wrmf_internal.h", CSRC / "wrmf_capi_common.h", CSRC / "wrmf_schedule.h", CSRC / "wrmf_device.h", CSRC / "wrmf_sample_team.h", CSRC / "wrmf_wave.h", CSRC / "wrmf_csr_rows.h", CSRC / "wrmf_ldlt.h", CSRC / "wrmf_f64.h", CSRC / "wrmf_topk_plan.h", CSRC / "wrmf_ctx_layout.h", PKG.parent / "include" / "rsparse_wrmf_hip.h"]
 DEPS = SRC + HEADERS
@@ -72,6 +72,9 @@ NO_SPILL = {"wrmf_cgq.hip": ("14als_cgq_kernelILi128ELi24ELi4ELi4E",),
             # the evaluation consumers (3.30) hold a cell, its lower bound and two run counters per lane
             "wrmf_itemknn.hip": ("knn_scatter_kernel", "knn_mask_kernel", "knn_select_kernel", "knn_gather_kernel", "knn_cand_select_kernel",
                                  "knn_ranks_kernel"),
+            # kAhead 16-byte loads in flight and four running doubles per thread: scratch would sit between a load and its add
+            # 
+            "wrmf_ease.hip": ("ease_score_kernel", "ease_gram_rows_kernel"),
             "wrmf_split.hip": ("split_count_wave_kernel", "split_count_team_kernel", "split_write_wave_kernel", "split_write_team_kernel")}
 RESOURCE_FLAG = "-Rpass-analysis=kernel-resource-usage"
 

@@ -1521,6 +1521,49 @@ int rsparse_hip_knn_recommend_device(const int32_t* d_xp, const int32_t* d_xj, i
                                                    n_exclude, k, ws_rows, d_items, d_scores, stream);
 }
 
+// EASE (wrmf_ease.hip) on the same workspace; the host forms rsparse_hip_item_gram / rsparse_hip_ease_recommend: wrmf_capi_host.cpp
+int rsparse_hip_item_gram_device(const int32_t* d_ip, const int32_t* d_iu, const int32_t* d_up, const int32_t* d_uj, int n_users,
+                                 int n_items, int item0, int item1, double lambda, double* d_out, size_t ld_out, int64_t ws_rows,
+                                 void* stream) {
+  int rc = item_gram_args(!d_ip || !d_iu || !d_up || !d_uj || !d_out, n_users, n_items, item0, item1, lambda, ld_out, ws_rows);
+  if (rc || item1 == item0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> h_ip;
+  if ((rc = fetch_row_pointers(d_ip + item0, (size_t)(item1 - item0), h_ip, s, "ip"))) return rc;
+  int64_t rows = 0;
+  void* ws = nullptr;
+  if ((rc = knn_workspace(item1 - item0, (size_t)n_items * sizeof(uint32_t), ws_rows, rows, ws, s))) return rc;
+  hipError_t e = launch_ease_item_gram(d_ip, d_iu, d_up, d_uj, n_users, n_items, item0, item1, h_ip.data(), lambda, rows,
+                                       static_cast<unsigned*>(ws), d_out, ld_out, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_ease_item_gram");
+  g_ws.knn_dirty = false;
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_ease_recommend_device(const int32_t* d_xp, const int32_t* d_xj, int n_rows, int n_items, const void* d_B, size_t ld_B,
+                                      int b_is_double, const int32_t* d_nr_p, const int32_t* d_nr_j, const int32_t* d_excl0,
+                                      int n_exclude, int k, int64_t ws_rows, int32_t* d_items, uint64_t* d_scores, void* stream) {
+  int rc = ease_recommend_args(!d_xp || !d_xj || !d_B || !d_items || !d_scores, n_rows, n_items, d_B, ld_B, b_is_double ? 2 : 4, d_nr_p,
+                               d_nr_j, d_excl0, n_exclude, k, ws_rows);
+  if (rc || n_rows == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> h_xp;
+  if ((rc = fetch_row_pointers(d_xp, (size_t)n_rows, h_xp, s, "x_p"))) return rc;
+  int64_t rows = 0;
+  void* ws = nullptr;
+  if ((rc = knn_workspace(n_rows, (size_t)n_items * sizeof(uint64_t), ws_rows, rows, ws, s))) return rc;
+  const int32_t* excl = n_exclude > 0 ? d_excl0 : nullptr;
+  auto* w64 = static_cast<unsigned long long*>(ws);
+  auto* sc = reinterpret_cast<long long*>(d_scores);
+  hipError_t e = b_is_double ? launch_ease_recommend(d_xp, d_xj, n_rows, n_items, static_cast<const double*>(d_B), ld_B, d_nr_p, d_nr_j,
+                                                     excl, n_exclude, k, rows, w64, d_items, sc, s)
+                             : launch_ease_recommend(d_xp, d_xj, n_rows, n_items, static_cast<const float*>(d_B), ld_B, d_nr_p, d_nr_j,
+                                                     excl, n_exclude, k, rows, w64, d_items, sc, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_ease_recommend");
+  g_ws.knn_dirty = false;
+  return RSPARSE_HIP_OK;
+}
+
 namespace {
 // what the evaluation entries do between their argument checks and their launches: x's row pointers on the host, the workspace
 static int knn_rows_begin(const int32_t* d_xp, int n_rows, int n_items, int64_t ws_rows, std::vector<int32_t>& h_xp, int64_t& rows,

@@ -398,6 +398,36 @@ inline int knn_recommend_args(bool missing, int n_rows, int n_items, int K, cons
   return RSPARSE_HIP_OK;
 }
 
+// EASE: the Gram rows and the lists scored by a dense weight matrix
+inline int item_gram_args(bool missing, int n_users, int n_items, int item0, int item1, double lambda, size_t ld_out, int64_t ws_rows) {
+  if (missing) return fail(RSPARSE_HIP_ERR_INVALID, "a pattern array or the output is NULL");
+  if (n_users < 0 || n_items < 0) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_users < 0 or n_items < 0)");
+  if (item0 < 0 || item1 < item0 || item1 > n_items) return fail(RSPARSE_HIP_ERR_INVALID, "not 0 <= item0 <= item1 <= n_items");
+  if (ws_rows < 0) return fail(RSPARSE_HIP_ERR_INVALID, "ws_rows < 0");
+  if (ld_out < (size_t)n_items) return fail(RSPARSE_HIP_ERR_INVALID, "ld_out < n_items");
+  if (!(lambda >= 0.0 && lambda <= 1.7976931348623157e308))   // (NaN fails both)
+    return fail(RSPARSE_HIP_ERR_INVALID, "lambda is negative or not finite");
+  if (n_items > RSPARSE_HIP_EASE_MAX_ITEMS)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "n_items > 32768 (RSPARSE_HIP_EASE_MAX_ITEMS): an items x items matrix of doubles would pass 8 GiB");
+  return RSPARSE_HIP_OK;
+}
+// B_elems: the alignment of B and ld_B in elements (16 bytes / the element size); 0 = B is a host array without a leading dimension
+inline int ease_recommend_args(bool missing, int n_rows, int n_items, const void* B, size_t ld_B, size_t B_elems, const void* nr_p,
+                               const void* nr_j, const void* excl, int n_exclude, int k, int64_t ws_rows) {
+  if (missing) return fail(RSPARSE_HIP_ERR_INVALID, "the pattern (x_p, x_j), B or an output is NULL");
+  if (n_rows < 0 || n_items < 0) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0 or n_items < 0)");
+  if (k < 1) return fail(RSPARSE_HIP_ERR_INVALID, "k < 1");
+  if (ws_rows < 0) return fail(RSPARSE_HIP_ERR_INVALID, "ws_rows < 0");
+  if (nr_p && !nr_j) return fail(RSPARSE_HIP_ERR_INVALID, "nr_p without nr_j");
+  if (n_exclude < 0 || (n_exclude > 0 && !excl)) return fail(RSPARSE_HIP_ERR_INVALID, "bad exclude");
+  if (B_elems && (ld_B < (size_t)n_items || ld_B % B_elems != 0 || (uintptr_t)B % 16 != 0))
+    return fail(RSPARSE_HIP_ERR_INVALID, "ld_B < n_items, or ld_B or B is not a multiple of 16 bytes");
+  if (k > RSPARSE_HIP_KNN_MAX_TOPK) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "k > 1024 (RSPARSE_HIP_KNN_MAX_TOPK) is not on the device path");
+  if (n_items > RSPARSE_HIP_EASE_MAX_ITEMS)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "n_items > 32768 (RSPARSE_HIP_EASE_MAX_ITEMS): an items x items matrix of doubles would pass 8 GiB");
+  return RSPARSE_HIP_OK;
+}
+
 // rsparse_hip_score_pairs_device / _f64_device (kernels: wrmf_score.hip).  Handed in:
 //   int workspace(size_t n, double*& buf)    makes sure of n doubles of the side's grow-only workspace
 // which is only asked for the sums without the scores: the scores then live there, and their count, p[n_rows], has to be

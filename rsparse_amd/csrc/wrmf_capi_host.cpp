@@ -7,7 +7,10 @@
 #include "../../include/rsparse_wrmf_hip.h"
 
 #include <algorithm>
+#include <climits>
+#include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -1021,6 +1024,100 @@ int rsparse_hip_knn_held_out_ranks(const int32_t* x_p, const int32_t* x_j, const
   HIP_TRY(download(above, dA, n_act));
   HIP_TRY(download(tied, dT, n_act));
   HIP_TRY(download(n_adm, dN, (size_t)n_rows));
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_item_gram(const int32_t* p, const int32_t* j, int n_users, int n_items, double lambda, double* out) {
+  int rc = item_gram_args(!p || !out, n_users, n_items, 0, n_items, lambda, (size_t)std::max(n_items, 0), 0);
+  if (rc) return rc;
+  if ((rc = check_csr(p, n_users, "p"))) return rc;
+  const size_t nnz = (size_t)p[n_users];
+  if (nnz && !j) return fail(RSPARSE_HIP_ERR_INVALID, "j is NULL");
+  if ((rc = check_columns(p, j, n_users, n_items, "j"))) return rc;
+  if (n_items == 0) return RSPARSE_HIP_OK;
+  std::vector<int32_t> ip, iu;
+  item_major(p, j, n_users, n_items, ip, iu, nullptr, nullptr);
+  DevBuf dIP, dIU, dUP, dUJ, dG;
+  HIP_TRY(upload_host(dIP, ip.data(), ip.size()));
+  HIP_TRY(upload_host(dIU, iu.data(), nnz));
+  HIP_TRY(upload_host(dUP, p, (size_t)n_users + 1));
+  HIP_TRY(upload_host(dUJ, j, nnz));
+  HIP_TRY(dG.alloc((size_t)n_items * n_items * sizeof(double)));
+  rc = rsparse_hip_item_gram_device(dIP.as<int32_t>(), dIU.as<int32_t>(), dUP.as<int32_t>(), dUJ.as<int32_t>(), n_users, n_items, 0,
+                                    n_items, lambda, dG.as<double>(), (size_t)n_items, 0, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(download(out, dG, (size_t)n_items * n_items));
+  return RSPARSE_HIP_OK;
+}
+
+extern "C++" {
+namespace {
+// B (n x n column-major, an R matrix) as n row-major rows of ld elements, zeros beyond n; a non-finite entry -> false
+template <class T>
+bool ease_pack_weights(const T* B, int n, size_t ld, std::vector<T>& rows) {
+  rows.assign((size_t)n * ld, T(0));
+  for (int c = 0; c < n; c++)
+    for (int i = 0; i < n; i++) {
+      const T v = B[(size_t)c * n + i];
+      if (!(v - v == T(0))) return false;
+      rows[(size_t)i * ld + c] = v;
+    }
+  return true;
+}
+}  // namespace
+}  // extern "C++"
+
+int rsparse_hip_ease_recommend(const int32_t* x_p, const int32_t* x_j, int n_rows, int n_items, const void* B, int b_is_double,
+                               const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude, int n_exclude, int k, int32_t* res,
+                               double* scores) {
+  int rc = ease_recommend_args(!x_p || !B || !res || !scores, n_rows, n_items, B, 0, 0, nr_p, nr_j, exclude, n_exclude, k, 0);
+  if (rc) return rc;
+  if ((rc = check_csr(x_p, n_rows, "x_p"))) return rc;
+  const size_t nnz = (size_t)x_p[n_rows], np1 = (size_t)n_rows + 1;
+  if (nnz && !x_j) return fail(RSPARSE_HIP_ERR_INVALID, "x_j is NULL");
+  if ((rc = check_columns(x_p, x_j, n_rows, n_items, "x_j"))) return rc;
+  if (nr_p) {
+    if ((rc = check_csr(nr_p, n_rows, "nr_p"))) return rc;
+    for (int32_t e = 0; e < nr_p[n_rows]; e++)
+      if (nr_j[e] < 0 || nr_j[e] >= n_items) return fail(RSPARSE_HIP_ERR_INVALID, "nr_j has a column outside [0, n_items)");
+  }
+  const size_t elem = b_is_double ? sizeof(double) : sizeof(float), ld = ((size_t)n_items * elem + 255) / 256 * 256 / elem;
+  std::vector<float> b32;
+  std::vector<double> b64;
+  if (!(b_is_double ? ease_pack_weights(static_cast<const double*>(B), n_items, ld, b64)
+                    : ease_pack_weights(static_cast<const float*>(B), n_items, ld, b32)))
+    return fail(RSPARSE_HIP_ERR_INVALID, "an entry of B is not finite");
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  std::vector<int32_t> ex;
+  add_excluded(exclude, n_exclude, n_items, ex);
+  DevBuf dXP, dXJ, dB, dP, dJ, dE, dR, dS;
+  HIP_TRY(upload_host(dXP, x_p, np1));
+  HIP_TRY(upload_host(dXJ, x_j, nnz));
+  if (b_is_double) HIP_TRY(upload_host(dB, b64.data(), b64.size()));
+  else HIP_TRY(upload_host(dB, b32.data(), b32.size()));
+  if (nr_p) {
+    HIP_TRY(upload_host(dP, nr_p, np1));
+    HIP_TRY(upload_host(dJ, nr_j, (size_t)nr_p[n_rows]));
+  }
+  if (!ex.empty()) HIP_TRY(upload_host(dE, ex.data(), ex.size()));
+  const size_t nk = (size_t)n_rows * k;
+  HIP_TRY(dR.alloc(nk * 4));
+  HIP_TRY(dS.alloc(nk * 8));
+  rc = rsparse_hip_ease_recommend_device(dXP.as<int32_t>(), dXJ.as<int32_t>(), n_rows, n_items, dB.p, ld, b_is_double,
+                                         opt<int32_t>(nr_p != nullptr, dP), opt<int32_t>(nr_p != nullptr, dJ),
+                                         opt<int32_t>(!ex.empty(), dE), (int)ex.size(), k, 0, dR.as<int32_t>(), dS.as<uint64_t>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  if ((rc = fetch_col_major(dR, n_rows, k, res))) return rc;
+  std::vector<uint64_t> keys(nk);
+  if ((rc = fetch_col_major(dS, n_rows, k, keys.data()))) return rc;
+  for (size_t t = 0; t < nk; t++) {   // the order key back to its double; NaN where the list has ended
+    const uint64_t key = keys[t], bits = (key >> 63) ? key ^ (1ull << 63) : ~key;
+    double v;
+    std::memcpy(&v, &bits, sizeof v);
+    scores[t] = res[t] == INT32_MIN ? std::nan("") : v;
+  }
   return RSPARSE_HIP_OK;
 }
 

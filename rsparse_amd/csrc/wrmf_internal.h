@@ -435,6 +435,32 @@ hipError_t launch_knn_held_out_ranks(const int32_t* xp, const int32_t* xj, const
                                      const int32_t* nr_p, const int32_t* nr_j, const int32_t* excl, int n_excl, int64_t rows,
                                      unsigned long long* ws, int32_t* above, int32_t* tied, int32_t* n_adm, hipStream_t s);
 
+// The steps of the above that another scorer of dense rows shares (wrmf_ease.hip); they enqueue the kernels of wrmf_itemknn.hip as
+// they are.  fit_scatter: the co-occurrence counts of the items [r0, r1), whose stored entries are the slots [t0, t1) of iu, into
+// r1 - r0 uint32 rows of n_items cells (the diagonal left out).  mask_rows: the all-ones sentinel into the not_recommend cells
+// (nr_p: the slots of THESE rows, nullable) and the excl cells of n_batch uint64 rows.  select_lists: the k cells of largest
+// value per row, ties to the smaller item, cells of 0 behind them in ascending order, all-ones cells never (items 1-based with
+// INT32_MIN where a list ends, scores the cells' values).  zero_rows: the memset behind a batch.
+void launch_knn_fit_scatter(const int32_t* ip, const int32_t* iu, const int32_t* up, const int32_t* uj, int n_users, int n_items, int r0,
+                            int r1, unsigned t0, unsigned t1, unsigned* ws, hipStream_t s);
+void launch_knn_mask_rows(unsigned long long* ws, size_t ld, int n_items, int n_batch, const int32_t* nr_p, const int32_t* nr_j,
+                          const int32_t* excl, int n_excl, hipStream_t s);
+void launch_knn_select_lists(const unsigned long long* ws, size_t ld, int n_items, int n_batch, int k, int32_t* items, long long* scores,
+                             hipStream_t s);
+hipError_t launch_knn_zero_rows(void* ws, size_t bytes, hipStream_t s);
+
+// EASE (wrmf_ease.hip; defined in rsparse_wrmf_hip.h), on the ItemKNN workspace (all zeros on entry and again when the enqueued
+// work is done).  item_gram: rows [item0, item1) of G + lambda I in double, `rows` uint32 rows per batch; h_ip: the host copy of
+// ip[item0 .. item1].  recommend: T = float or double, B: n_items rows of ld_B elements, ld_B >= n_items and ld_B sizeof(T) a
+// multiple of 16, B 16-byte aligned; `rows` uint64 rows per batch; scores: the order keys of the doubles.
+hipError_t launch_ease_item_gram(const int32_t* ip, const int32_t* iu, const int32_t* up, const int32_t* uj, int n_users, int n_items,
+                                 int item0, int item1, const int32_t* h_ip, double lambda, int64_t rows, unsigned* ws, double* out,
+                                 size_t ld_out, hipStream_t s);
+template <class T>
+hipError_t launch_ease_recommend(const int32_t* xp, const int32_t* xj, int n_rows, int n_items, const T* B, size_t ld_B,
+                                 const int32_t* nr_p, const int32_t* nr_j, const int32_t* excl, int n_excl, int k, int64_t rows,
+                                 unsigned long long* ws, int32_t* items, long long* scores, hipStream_t s);
+
 // top-k within per-user candidate lists (wrmf_candidates.hip), T = float or double, 1 <= topk <= kTopLargeMax: for every row of
 // the CSR pattern (cand_p: n_users + 1 slots, absolute positions into cand_j; p0 = cand_p[0], nnz = cand_p[n_users] - p0, read by
 // the caller; columns ascending and unique within a row) the topk best admissible candidates by launch_score_pairs' scores

@@ -665,9 +665,7 @@ bool fill_list_rows(const KnnRows& in, bool with_mask, int r0, int r1, unsigned 
   else if (t1 > t0)
     hipLaunchKernelGGL(knn_scatter_kernel<kLists>, dim3(scatter_grid(t0, t1)), dim3(kThreads), 0, s, in.xp, in.xj, in.n_rows, r0, r1 - r0,
                        t0, t1, nullptr, in.neighbors, in.q, in.K, in.n_items, in.n_items, in.ld(), ws, nullptr);
-  if (mask)
-    hipLaunchKernelGGL(knn_mask_kernel, dim3((unsigned)(r1 - r0)), dim3(kThreads), 0, s, ws, in.ld(), in.n_items,
-                       in.nr_p ? in.nr_p + r0 : nullptr, in.nr_j, in.excl, in.n_excl);
+  if (mask) launch_knn_mask_rows(ws, in.ld(), in.n_items, r1 - r0, in.nr_p ? in.nr_p + r0 : nullptr, in.nr_j, in.excl, in.n_excl, s);
   return t1 > t0 || mask;
 }
 
@@ -751,5 +749,26 @@ hipError_t launch_knn_held_out_ranks(const int32_t* xp, const int32_t* xj, const
   }
   return hipSuccess;
 }
+
+// ---- the steps another scorer of dense rows shares (wrmf_ease.hip): host functions only, the kernels above are what they were ----
+
+void launch_knn_fit_scatter(const int32_t* ip, const int32_t* iu, const int32_t* up, const int32_t* uj, int n_users, int n_items, int r0,
+                            int r1, unsigned t0, unsigned t1, unsigned* ws, hipStream_t s) {
+  hipLaunchKernelGGL(knn_scatter_kernel<kFit>, dim3(scatter_grid(t0, t1)), dim3(kThreads), 0, s, ip, iu, n_items, r0, r1 - r0, t0, t1, up,
+                     uj, nullptr, 0, n_users, n_items, (size_t)n_items, ws, nullptr);
+}
+
+void launch_knn_mask_rows(unsigned long long* ws, size_t ld, int n_items, int n_batch, const int32_t* nr_p, const int32_t* nr_j,
+                          const int32_t* excl, int n_excl, hipStream_t s) {
+  hipLaunchKernelGGL(knn_mask_kernel, dim3((unsigned)n_batch), dim3(kThreads), 0, s, ws, ld, n_items, nr_p, nr_j, excl, n_excl);
+}
+
+void launch_knn_select_lists(const unsigned long long* ws, size_t ld, int n_items, int n_batch, int k, int32_t* items, long long* scores,
+                             hipStream_t s) {
+  hipLaunchKernelGGL(knn_select_kernel<kLists>, dim3((unsigned)n_batch), dim3(kThreads), 0, s, ws, ld, n_items, 0, nullptr, 0, k, items,
+                     nullptr, scores, nullptr, nullptr, 0.0);
+}
+
+hipError_t launch_knn_zero_rows(void* ws, size_t bytes, hipStream_t s) { return hipMemsetAsync(ws, 0, bytes, s); }
 
 }  // namespace rsparse_hip

@@ -862,6 +862,42 @@ class HipBackend:
             0 if exclude0 is None else int(exclude0.numel()), int(k), int(ws_rows), some(res), some(sc), self._stream()))
         return res, sc
 
+    def item_gram(self, ip, iu, up, uj, n_users, n_items, lambda_, item0=0, item1=None, ws_rows=0, out=None):
+        """rows [item0, item1) of G + lambda I of a binary pattern (wrmf_ease.hip behind the fit scatter of wrmf_itemknn.hip;
+        rsparse_amd.ease.ease_gram_reference is the definition): the co-occurrence counts off the diagonal, n_i + lambda on it.
+        ip / iu, up / uj: the two orientations, int32 on the device, as `cooc_neighbors` takes them.  -> (item1 - item0, n_items)
+        float64 on the device; `out`: write there instead (rows of n_items doubles at any row stride >= n_items)."""
+        item1 = int(n_items) if item1 is None else int(item1)
+        n = max(item1 - int(item0), 0)
+        assert all(t.dtype == torch.int32 for t in (ip, iu, up, uj))
+        if out is None:
+            out = torch.empty((n, int(n_items)), dtype=torch.float64, device=self.device)
+        assert out.dtype == torch.float64 and out.is_cuda and tuple(out.shape) == (n, int(n_items)) and (n_items <= 1 or out.stride(1) == 1)
+        ld = int(out.stride(0)) if n > 1 else int(n_items)
+        some = lambda t: t.data_ptr() if t.numel() else ip.data_ptr()   # (an empty tensor has no address to pass)
+        _lib.check(self.lib.rsparse_hip_item_gram_device(ip.data_ptr(), some(iu), up.data_ptr(), some(uj), int(n_users), int(n_items),
+                                                         int(item0), item1, float(lambda_), some(out), ld, int(ws_rows), self._stream()))
+        return out
+
+    def ease_recommend(self, xp, xj, B, n_items, k, nr_p=None, nr_j=None, exclude0=None, ws_rows=0):
+        """the EASE lists of the rows of a CSR pattern (xp, xj: int32 on the device) under the dense weights B: an (n_items, ld)
+        float32 or float64 tensor on the device whose first n_items columns are the matrix, rows 16-byte aligned (wrmf_ease.hip;
+        rsparse_amd.ease.ease_recommend_reference is the definition).  nr_p / nr_j / exclude0: as `knn_recommend`.
+        -> (items (n, k) int32, 1-based with NA_integer_; keys (n, k) int64 holding the uint64 order keys of the float64 scores,
+        0 where NA: rsparse_amd.ease.key_scores decodes them) on the device."""
+        assert xp.dtype == torch.int32 and xj.dtype == torch.int32 and B.dtype in (torch.float32, torch.float64) and B.is_cuda
+        n, n_items = int(xp.numel()) - 1, int(n_items)
+        assert B.dim() == 2 and B.shape[0] == n_items and B.shape[1] >= n_items and (B.shape[1] <= 1 or B.stride(1) == 1)
+        ld = int(B.stride(0)) if n_items > 1 else int(B.shape[1])
+        res = torch.empty((n, int(k)), dtype=torch.int32, device=self.device)
+        keys = torch.empty((n, int(k)), dtype=torch.int64, device=self.device)
+        some = lambda t: t.data_ptr() if t.numel() else xp.data_ptr()
+        _lib.check(self.lib.rsparse_hip_ease_recommend_device(
+            xp.data_ptr(), some(xj), n, n_items, some(B), ld, int(B.dtype == torch.float64), None if nr_p is None else nr_p.data_ptr(),
+            None if nr_p is None else some(nr_j), None if exclude0 is None or not exclude0.numel() else exclude0.data_ptr(),
+            0 if exclude0 is None else int(exclude0.numel()), int(k), int(ws_rows), some(res), some(keys), self._stream()))
+        return res, keys
+
     def _knn_rows(self, xp, xj, neighbors, q, xv):
         """the operands the ItemKNN evaluation entries share with `knn_recommend`, as the C ABI takes them: -> (the leading
         arguments, `some`: the address of a tensor, or of xp for an empty one; the tensors that must outlive the call)"""

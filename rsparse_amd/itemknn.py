@@ -502,6 +502,41 @@ def knn_ranks_reference(x, neighbors, q, actual, not_recommend=None, items_exclu
     return above, tied, n_adm
 
 
+def evaluate_lists(be, res, actual, n_items, item_count, metrics, cutoffs, scalar_k):
+    """the list metrics `metrics` (checked by the caller) of the lists `res` ((n, max(cutoffs)) int32 on the backend, 1-based with
+    NA_integer_) against the held-out `actual`, at every cutoff: what `ItemKNN.evaluate` and `EASE.evaluate` return.  The lists
+    stay on the device."""
+    from .metrics import HIT_METRICS, LIST_METRICS, NEVER_SEEN, canonical_actual, coverage_from_first_seen, self_information
+    known = ("ap", "ndcg") + HIT_METRICS + ("coverage",) + LIST_METRICS
+    act = canonical_actual(actual, int(res.shape[0]))
+    d_p, d_j = be.to_device(act.indptr, torch.int32), be.to_device(act.indices, torch.int32)
+    out = {}
+    want_ap, want_ndcg = "ap" in metrics, "ndcg" in metrics
+    if want_ap or want_ndcg:
+        d_x = be.to_device(act.data, torch.float64)
+        cols = [be.ranking_metrics(res[:, :c].contiguous(), d_p, d_j, d_x, want_ap, want_ndcg) for c in cutoffs]
+        for pos, name in enumerate(("ap", "ndcg")):
+            if name in metrics:
+                out[name] = torch.stack([c[pos] for c in cols], dim=1)
+    hit_names = tuple(name for name in HIT_METRICS if name in metrics)
+    if hit_names or "coverage" in metrics:
+        first_seen = torch.full((n_items,), NEVER_SEEN, dtype=torch.int32, device=res.device) if "coverage" in metrics else None
+        fn = be.hit_metrics if hasattr(be, "hit_metrics") else WRMF._hit_metrics_host
+        out.update(fn(res, d_p, d_j, cutoffs, hit_names, first_seen))
+    list_names = tuple(name for name in LIST_METRICS if name in metrics)
+    if list_names:
+        d_cnt = be.to_device(item_count, torch.int32) if "popularity" in metrics else None
+        d_info = be.to_device(self_information(item_count), torch.int64) if "novelty" in metrics else None
+        fn = be.list_metrics if hasattr(be, "list_metrics") else WRMF._list_metrics_host
+        out.update(fn(res, cutoffs, n_items, list_names, d_cnt, d_info, None))
+    out = {name: v.cpu().numpy() for name, v in out.items() if name in metrics}
+    out = {name: (v[:, 0] if scalar_k else v) for name, v in out.items()}
+    if "coverage" in metrics:
+        cov = coverage_from_first_seen(first_seen.cpu().numpy(), np.asarray(cutoffs, dtype=np.int32))
+        out["coverage"] = float(cov[0]) if scalar_k else cov
+    return {name: out[name] for name in known if name in metrics}
+
+
 class ItemKNN:
     """Item-based k-nearest-neighbours on the co-occurrence of items (the module's docstring is the definition).
 
@@ -830,7 +865,7 @@ class ItemKNN:
         held-out items against n negatives, exactly `candidates=self.sample_negatives(x, n, actual, not_recommend,
         items_exclude, seed, negative_weights)` -- the negatives `WRMF.sample_negatives` returns for that seed.  `seed` is
         required with `negatives`; `negatives` excludes `candidates`; `negative_weights` needs `negatives`."""
-        from .metrics import HIT_METRICS, LIST_METRICS, NEVER_SEEN, canonical_actual, check_cutoffs, coverage_from_first_seen, self_information
+        from .metrics import HIT_METRICS, LIST_METRICS, check_cutoffs
         metrics = tuple(metrics)
         known = ("ap", "ndcg") + HIT_METRICS + ("coverage",) + LIST_METRICS
         if not metrics or any(name not in known for name in metrics):
@@ -847,32 +882,4 @@ class ItemKNN:
             candidates = self.sample_negatives(x, negatives, actual=actual, not_recommend=not_recommend, items_exclude=items_exclude,
                                                seed=seed, weights=negative_weights)
         m, res, _ = self._lists(x, int(cutoffs[-1]), not_recommend, items_exclude, candidates=candidates)
-        act = canonical_actual(actual, m.shape[0])
-        be = self._backend()
-        n_items = self.neighbors.shape[0]
-        d_p, d_j = be.to_device(act.indptr, torch.int32), be.to_device(act.indices, torch.int32)
-        out = {}
-        want_ap, want_ndcg = "ap" in metrics, "ndcg" in metrics
-        if want_ap or want_ndcg:
-            d_x = be.to_device(act.data, torch.float64)
-            cols = [be.ranking_metrics(res[:, :c].contiguous(), d_p, d_j, d_x, want_ap, want_ndcg) for c in cutoffs]
-            for pos, name in enumerate(("ap", "ndcg")):
-                if name in metrics:
-                    out[name] = torch.stack([c[pos] for c in cols], dim=1)
-        hit_names = tuple(name for name in HIT_METRICS if name in metrics)
-        if hit_names or "coverage" in metrics:
-            first_seen = torch.full((n_items,), NEVER_SEEN, dtype=torch.int32, device=res.device) if "coverage" in metrics else None
-            fn = be.hit_metrics if hasattr(be, "hit_metrics") else WRMF._hit_metrics_host
-            out.update(fn(res, d_p, d_j, cutoffs, hit_names, first_seen))
-        list_names = tuple(name for name in LIST_METRICS if name in metrics)
-        if list_names:
-            d_cnt = be.to_device(self.item_count, torch.int32) if "popularity" in metrics else None
-            d_info = be.to_device(self_information(self.item_count), torch.int64) if "novelty" in metrics else None
-            fn = be.list_metrics if hasattr(be, "list_metrics") else WRMF._list_metrics_host
-            out.update(fn(res, cutoffs, n_items, list_names, d_cnt, d_info, None))
-        out = {name: v.cpu().numpy() for name, v in out.items() if name in metrics}
-        out = {name: (v[:, 0] if scalar_k else v) for name, v in out.items()}
-        if "coverage" in metrics:
-            cov = coverage_from_first_seen(first_seen.cpu().numpy(), np.asarray(cutoffs, dtype=np.int32))
-            out["coverage"] = float(cov[0]) if scalar_k else cov
-        return {name: out[name] for name in known if name in metrics}
+        return evaluate_lists(self._backend(), res, actual, self.neighbors.shape[0], self.item_count, metrics, cutoffs, scalar_k)
