@@ -987,6 +987,60 @@ int rsparse_hip_ease_recommend(const int32_t* x_p, const int32_t* x_j, int n_row
                                const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude, int n_exclude, int k, int32_t* res,
                                double* scores);
 
+/* EASE under the evaluation protocols of the other models: the score at given cells, the lists within per-row candidates, and
+ * where held-out items stand among all items.  The arguments, conventions and refusals are those of the rsparse_hip_knn_*
+ * entries of the same names (absolute row pointers, outputs parallel to the column arrays, d_xp and the entry's own row pointers
+ * read back, n_rows == 0 -> OK) with d_B, ld_B, b_is_double in place of d_neighbors, d_q, K and d_xv, and with the checks of B of
+ * rsparse_hip_ease_recommend_device (alignment and ld_B -> ERR_INVALID, n_items > RSPARSE_HIP_EASE_MAX_ITEMS -> ERR_UNSUPPORTED).
+ * Scores are the 64-bit keys of the doubles, as there.
+ *
+ * A dense score row costs nnz(row) x n_items cells of B; a row that is asked for m cells needs nnz(row) x m of them.  The host
+ * routes every row by its own m, from the row pointers it has read back:
+ *     m <= RSPARSE_HIP_KNN_LDS_CAND  and  m * RSPARSE_HIP_EASE_CELLS_RATIO <= n_items      -> the CELL route
+ *     otherwise                                                                            -> the DENSE route
+ * Cell route: one kernel scores B at the row's cells only -- a lane owns a cell, a wave 64 consecutive cells of one row, so the
+ * history index is wave-uniform and the lane's column its only vector address; RSPARSE_HIP_EASE_AHEAD loads in flight; the adds
+ * in ascending stored order, the sequence the dense kernel takes for that column -- and, for the lists, a second one masks,
+ * orders and cuts the row's (key, item) pairs in LDS.  Dense route: the scoring kernel of rsparse_hip_ease_recommend_device into
+ * the workspace (ws_rows rows per batch, consecutive dense-route rows only), then ItemKNN's gather, or its mask, a restriction of
+ * the row to its candidates and its select.  Both routes return the same bits; a scattered four-byte cell costs a whole cache
+ * line, which is what the ratio prices (profiles/ease_eval holds the sweep).  No atomics on floats: repeat calls are identical. */
+#ifndef RSPARSE_HIP_EASE_CELLS_RATIO   /* (a build may set another one: the sweep is made that way) */
+#define RSPARSE_HIP_EASE_CELLS_RATIO 16
+#endif
+
+/* d_scores[t] = key(score_row(t)[d_pairs_j[t]]) for every stored position t of the pairs pattern; nothing is masked; a column
+ * outside [0, n_items) gives the key of +0.0 (1 << 63); j need not be sorted and may repeat. */
+int rsparse_hip_ease_score_pairs_device(const int32_t* d_xp, const int32_t* d_xj, int n_rows, int n_items, const void* d_B, size_t ld_B,
+                                        int b_is_double, const int32_t* d_pairs_p, const int32_t* d_pairs_j, int64_t ws_rows,
+                                        uint64_t* d_scores, void* stream);
+
+/* The k best of every row's candidates, as rsparse_hip_knn_top_candidates_device defines them (score descending by key, equal
+ * scores to the smaller item, candidates of score 0 ranked, a column outside [0, n_items) never listed); d_items / d_scores as
+ * rsparse_hip_ease_recommend_device.  PRECONDITION: the candidate columns of a row are strictly ascending (the cell route finds
+ * a row's not_recommend and excluded items among them by a lower bound; the host form refuses a violation). */
+int rsparse_hip_ease_top_candidates_device(const int32_t* d_xp, const int32_t* d_xj, int n_rows, int n_items, const void* d_B, size_t ld_B,
+                                           int b_is_double, const int32_t* d_cand_p, const int32_t* d_cand_j, const int32_t* d_nr_p,
+                                           const int32_t* d_nr_j, const int32_t* d_excl0, int n_exclude, int k, int64_t ws_rows,
+                                           int32_t* d_items, uint64_t* d_scores, void* stream);
+
+/* above / tied / n_adm as rsparse_hip_knn_held_out_ranks_device defines them, with s the double score (compared by key): the
+ * dense scoring kernel, ItemKNN's mask and its rank count on the key rows.  Every row takes the dense route. */
+int rsparse_hip_ease_held_out_ranks_device(const int32_t* d_xp, const int32_t* d_xj, int n_rows, int n_items, const void* d_B, size_t ld_B,
+                                           int b_is_double, const int32_t* d_actual_p, const int32_t* d_actual_j, const int32_t* d_nr_p,
+                                           const int32_t* d_nr_j, const int32_t* d_excl0, int n_exclude, int64_t ws_rows, int32_t* d_above,
+                                           int32_t* d_tied, int32_t* d_n_adm, void* stream);
+
+/* host-array forms: x_p / x_j, B (column-major, a non-finite entry -> ERR_INVALID), nr_p / nr_j, exclude (1-based) as
+ * rsparse_hip_ease_recommend; cand_p / cand_j and actual_p / actual_j with the checks of rsparse_hip_knn_top_candidates and
+ * rsparse_hip_knn_held_out_ranks.  res / scores: n_rows x k column-major, the scores the doubles themselves, NaN where res is NA. */
+int rsparse_hip_ease_top_candidates(const int32_t* x_p, const int32_t* x_j, int n_rows, int n_items, const void* B, int b_is_double,
+                                    const int32_t* cand_p, const int32_t* cand_j, const int32_t* nr_p, const int32_t* nr_j,
+                                    const int32_t* exclude, int n_exclude, int k, int32_t* res, double* scores);
+int rsparse_hip_ease_held_out_ranks(const int32_t* x_p, const int32_t* x_j, int n_rows, int n_items, const void* B, int b_is_double,
+                                    const int32_t* actual_p, const int32_t* actual_j, const int32_t* nr_p, const int32_t* nr_j,
+                                    const int32_t* exclude, int n_exclude, int32_t* above, int32_t* tied, int32_t* n_adm);
+
 /* ------------------------------------------------------------------------------------------------
  * why this item: per-item contributions to a score (Hu, Koren and Volinsky, section 5; `explain` of the `implicit` library)
  * ---------------------------------------------------------------------------------------------- */

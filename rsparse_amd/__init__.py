@@ -47,7 +47,8 @@ def __getattr__(name):
                 "weighted_cooccurrence_reference", "knn_score_pairs_reference", "knn_candidates_reference", "knn_ranks_reference"):
         from . import itemknn
         return getattr(itemknn, name)
-    if name in ("EASE", "ease_gram_reference", "ease_weights_reference", "ease_scores_reference", "ease_recommend_reference"):
+    if name in ("EASE", "ease_gram_reference", "ease_weights_reference", "ease_scores_reference", "ease_recommend_reference",
+                "ease_score_pairs_reference", "ease_candidates_reference", "ease_ranks_reference"):
         from . import ease
         return getattr(ease, name)
     if name == "metrics":

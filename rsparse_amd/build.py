@@ -74,7 +74,10 @@ NO_SPILL = {"wrmf_cgq.hip": ("14als_cgq_kernelILi128ELi24ELi4ELi4E",),
                                  "knn_ranks_kernel"),
             # kAhead 16-byte loads in flight and four running doubles per thread: scratch would sit between a load and its add
             # 
-            "wrmf_ease.hip": ("ease_score_kernel", "ease_gram_rows_kernel"),
+            # the cell scorer (3.32): kAhead 4- or 8-byte loads in flight and one running double per lane; the candidate select
+            # holds two keys and their items per lane in the sort's exchange
+            "wrmf_ease.hip": ("ease_score_kernel", "ease_gram_rows_kernel", "ease_cells_kernel", "ease_cand_select_kernel",
+                              "ease_restrict_kernel"),
             "wrmf_split.hip": ("split_count_wave_kernel", "split_count_team_kernel", "split_write_wave_kernel", "split_write_team_kernel")}
 RESOURCE_FLAG = "-Rpass-analysis=kernel-resource-usage"
 

@@ -1637,6 +1637,79 @@ int rsparse_hip_knn_held_out_ranks_device(const int32_t* d_xp, const int32_t* d_
   return RSPARSE_HIP_OK;
 }
 
+// EASE under the same protocols (wrmf_ease.hip); the host forms rsparse_hip_ease_top_candidates / _held_out_ranks: wrmf_capi_host.cpp
+int rsparse_hip_ease_score_pairs_device(const int32_t* d_xp, const int32_t* d_xj, int n_rows, int n_items, const void* d_B, size_t ld_B,
+                                        int b_is_double, const int32_t* d_pairs_p, const int32_t* d_pairs_j, int64_t ws_rows,
+                                        uint64_t* d_scores, void* stream) {
+  int rc = ease_recommend_args(!d_xp || !d_xj || !d_B || !d_pairs_p || !d_pairs_j || !d_scores, n_rows, n_items, d_B, ld_B,
+                               b_is_double ? 2 : 4, nullptr, nullptr, nullptr, 0, 1, ws_rows);
+  if (rc || n_rows == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> h_xp, h_pp;
+  if ((rc = fetch_row_pointers(d_pairs_p, (size_t)n_rows, h_pp, s, "pairs_p"))) return rc;
+  int64_t rows = 0;
+  unsigned long long* ws = nullptr;
+  if ((rc = knn_rows_begin(d_xp, n_rows, n_items, ws_rows, h_xp, rows, ws, s))) return rc;
+  auto* sc = reinterpret_cast<unsigned long long*>(d_scores);
+  hipError_t e = b_is_double ? launch_ease_score_pairs(d_xp, d_xj, n_rows, n_items, static_cast<const double*>(d_B), ld_B, d_pairs_p,
+                                                       d_pairs_j, h_pp.data(), rows, ws, sc, s)
+                             : launch_ease_score_pairs(d_xp, d_xj, n_rows, n_items, static_cast<const float*>(d_B), ld_B, d_pairs_p,
+                                                       d_pairs_j, h_pp.data(), rows, ws, sc, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_ease_score_pairs");
+  g_ws.knn_dirty = false;
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_ease_top_candidates_device(const int32_t* d_xp, const int32_t* d_xj, int n_rows, int n_items, const void* d_B, size_t ld_B,
+                                           int b_is_double, const int32_t* d_cand_p, const int32_t* d_cand_j, const int32_t* d_nr_p,
+                                           const int32_t* d_nr_j, const int32_t* d_excl0, int n_exclude, int k, int64_t ws_rows,
+                                           int32_t* d_items, uint64_t* d_scores, void* stream) {
+  int rc = ease_recommend_args(!d_xp || !d_xj || !d_B || !d_cand_p || !d_cand_j || !d_items || !d_scores, n_rows, n_items, d_B, ld_B,
+                               b_is_double ? 2 : 4, d_nr_p, d_nr_j, d_excl0, n_exclude, k, ws_rows);
+  if (rc || n_rows == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> h_xp, h_cp;
+  if ((rc = fetch_row_pointers(d_cand_p, (size_t)n_rows, h_cp, s, "cand_p"))) return rc;
+  int64_t rows = 0;
+  unsigned long long* ws = nullptr;
+  if ((rc = knn_rows_begin(d_xp, n_rows, n_items, ws_rows, h_xp, rows, ws, s))) return rc;
+  HIP_TRY(g_ws.score_buf.ensure((size_t)h_cp[n_rows] + 1));   // the cell route's keys, one per candidate slot (absolute)
+  auto* keys = reinterpret_cast<unsigned long long*>(static_cast<double*>(g_ws.score_buf));
+  const int32_t* excl = n_exclude > 0 ? d_excl0 : nullptr;
+  auto* sc = reinterpret_cast<long long*>(d_scores);
+  hipError_t e = b_is_double ? launch_ease_top_candidates(d_xp, d_xj, n_rows, n_items, static_cast<const double*>(d_B), ld_B, d_cand_p,
+                                                          d_cand_j, h_cp.data(), d_nr_p, d_nr_j, excl, n_exclude, k, rows, ws, keys,
+                                                          d_items, sc, s)
+                             : launch_ease_top_candidates(d_xp, d_xj, n_rows, n_items, static_cast<const float*>(d_B), ld_B, d_cand_p,
+                                                          d_cand_j, h_cp.data(), d_nr_p, d_nr_j, excl, n_exclude, k, rows, ws, keys,
+                                                          d_items, sc, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_ease_top_candidates");
+  g_ws.knn_dirty = false;
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_ease_held_out_ranks_device(const int32_t* d_xp, const int32_t* d_xj, int n_rows, int n_items, const void* d_B, size_t ld_B,
+                                           int b_is_double, const int32_t* d_actual_p, const int32_t* d_actual_j, const int32_t* d_nr_p,
+                                           const int32_t* d_nr_j, const int32_t* d_excl0, int n_exclude, int64_t ws_rows, int32_t* d_above,
+                                           int32_t* d_tied, int32_t* d_n_adm, void* stream) {
+  int rc = ease_recommend_args(!d_xp || !d_xj || !d_B || !d_actual_p || !d_actual_j || !d_above || !d_tied || !d_n_adm, n_rows, n_items,
+                               d_B, ld_B, b_is_double ? 2 : 4, d_nr_p, d_nr_j, d_excl0, n_exclude, 1, ws_rows);
+  if (rc || n_rows == 0) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> h_xp;
+  int64_t rows = 0;
+  unsigned long long* ws = nullptr;
+  if ((rc = knn_rows_begin(d_xp, n_rows, n_items, ws_rows, h_xp, rows, ws, s))) return rc;
+  const int32_t* excl = n_exclude > 0 ? d_excl0 : nullptr;
+  hipError_t e = b_is_double ? launch_ease_held_out_ranks(d_xp, d_xj, n_rows, n_items, static_cast<const double*>(d_B), ld_B, d_actual_p,
+                                                          d_actual_j, d_nr_p, d_nr_j, excl, n_exclude, rows, ws, d_above, d_tied, d_n_adm, s)
+                             : launch_ease_held_out_ranks(d_xp, d_xj, n_rows, n_items, static_cast<const float*>(d_B), ld_B, d_actual_p,
+                                                          d_actual_j, d_nr_p, d_nr_j, excl, n_exclude, rows, ws, d_above, d_tied, d_n_adm, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_ease_held_out_ranks");
+  g_ws.knn_dirty = false;
+  return RSPARSE_HIP_OK;
+}
+
 // `_f64_device`: wrmf_f64_capi.cpp; the host form rsparse_hip_top_candidates: wrmf_capi_host.cpp
 int rsparse_hip_top_candidates_device(const float* d_U, const float* d_V, int n_users, int n_items, int rank, int k,
                                       const int32_t* d_cand_p, const int32_t* d_cand_j, const int32_t* d_nr_p, const int32_t* d_nr_j,

@@ -1068,56 +1068,147 @@ bool ease_pack_weights(const T* B, int n, size_t ld, std::vector<T>& rows) {
 }  // namespace
 }  // extern "C++"
 
-int rsparse_hip_ease_recommend(const int32_t* x_p, const int32_t* x_j, int n_rows, int n_items, const void* B, int b_is_double,
-                               const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude, int n_exclude, int k, int32_t* res,
-                               double* scores) {
-  int rc = ease_recommend_args(!x_p || !B || !res || !scores, n_rows, n_items, B, 0, 0, nr_p, nr_j, exclude, n_exclude, k, 0);
-  if (rc) return rc;
-  if ((rc = check_csr(x_p, n_rows, "x_p"))) return rc;
-  const size_t nnz = (size_t)x_p[n_rows], np1 = (size_t)n_rows + 1;
-  if (nnz && !x_j) return fail(RSPARSE_HIP_ERR_INVALID, "x_j is NULL");
-  if ((rc = check_columns(x_p, x_j, n_rows, n_items, "x_j"))) return rc;
-  if (nr_p) {
-    if ((rc = check_csr(nr_p, n_rows, "nr_p"))) return rc;
-    for (int32_t e = 0; e < nr_p[n_rows]; e++)
-      if (nr_j[e] < 0 || nr_j[e] >= n_items) return fail(RSPARSE_HIP_ERR_INVALID, "nr_j has a column outside [0, n_items)");
-  }
-  const size_t elem = b_is_double ? sizeof(double) : sizeof(float), ld = ((size_t)n_items * elem + 255) / 256 * 256 / elem;
+extern "C++" {
+namespace {
+// The operands the host forms of the EASE lists share -- the rows (x_p, x_j), B, not_recommend and exclude: check() judges the
+// host arrays behind ease_recommend_args and packs B, upload() hands them to the device forms (0-based ids).
+struct EaseHostRows {
+  DevBuf dXP, dXJ, dB, dP, dJ, dE;
+  std::vector<int32_t> ex;
   std::vector<float> b32;
   std::vector<double> b64;
-  if (!(b_is_double ? ease_pack_weights(static_cast<const double*>(B), n_items, ld, b64)
-                    : ease_pack_weights(static_cast<const float*>(B), n_items, ld, b32)))
-    return fail(RSPARSE_HIP_ERR_INVALID, "an entry of B is not finite");
-  if (n_rows == 0) return RSPARSE_HIP_OK;
-  std::vector<int32_t> ex;
-  add_excluded(exclude, n_exclude, n_items, ex);
-  DevBuf dXP, dXJ, dB, dP, dJ, dE, dR, dS;
-  HIP_TRY(upload_host(dXP, x_p, np1));
-  HIP_TRY(upload_host(dXJ, x_j, nnz));
-  if (b_is_double) HIP_TRY(upload_host(dB, b64.data(), b64.size()));
-  else HIP_TRY(upload_host(dB, b32.data(), b32.size()));
-  if (nr_p) {
-    HIP_TRY(upload_host(dP, nr_p, np1));
-    HIP_TRY(upload_host(dJ, nr_j, (size_t)nr_p[n_rows]));
+  size_t ld = 0;
+  bool filter = false;
+
+  int check(const int32_t* x_p, const int32_t* x_j, int n_rows, int n_items, const void* B, int b_is_double, const int32_t* nr_p,
+            const int32_t* nr_j) {
+    if (int rc = check_csr(x_p, n_rows, "x_p")) return rc;
+    if (x_p[n_rows] && !x_j) return fail(RSPARSE_HIP_ERR_INVALID, "x_j is NULL");
+    if (int rc = check_columns(x_p, x_j, n_rows, n_items, "x_j")) return rc;
+    if (nr_p) {
+      if (int rc = check_csr(nr_p, n_rows, "nr_p")) return rc;
+      for (int32_t e = 0; e < nr_p[n_rows]; e++)
+        if (nr_j[e] < 0 || nr_j[e] >= n_items) return fail(RSPARSE_HIP_ERR_INVALID, "nr_j has a column outside [0, n_items)");
+    }
+    const size_t elem = b_is_double ? sizeof(double) : sizeof(float);
+    ld = ((size_t)n_items * elem + 255) / 256 * 256 / elem;
+    if (!(b_is_double ? ease_pack_weights(static_cast<const double*>(B), n_items, ld, b64)
+                      : ease_pack_weights(static_cast<const float*>(B), n_items, ld, b32)))
+      return fail(RSPARSE_HIP_ERR_INVALID, "an entry of B is not finite");
+    return RSPARSE_HIP_OK;
   }
-  if (!ex.empty()) HIP_TRY(upload_host(dE, ex.data(), ex.size()));
+
+  int upload(const int32_t* x_p, const int32_t* x_j, int n_rows, int n_items, int b_is_double, const int32_t* nr_p, const int32_t* nr_j,
+             const int32_t* exclude, int n_exclude) {
+    const size_t np1 = (size_t)n_rows + 1;
+    add_excluded(exclude, n_exclude, n_items, ex);
+    HIP_TRY(upload_host(dXP, x_p, np1));
+    HIP_TRY(upload_host(dXJ, x_j, (size_t)x_p[n_rows]));
+    if (b_is_double) HIP_TRY(upload_host(dB, b64.data(), b64.size()));
+    else HIP_TRY(upload_host(dB, b32.data(), b32.size()));
+    filter = nr_p != nullptr;
+    if (filter) {
+      HIP_TRY(upload_host(dP, nr_p, np1));
+      HIP_TRY(upload_host(dJ, nr_j, (size_t)nr_p[n_rows]));
+    }
+    if (!ex.empty()) HIP_TRY(upload_host(dE, ex.data(), ex.size()));
+    return RSPARSE_HIP_OK;
+  }
+
+  const int32_t* nr_p() { return opt<int32_t>(filter, dP); }
+  const int32_t* nr_j() { return opt<int32_t>(filter, dJ); }
+  const int32_t* excl() { return opt<int32_t>(!ex.empty(), dE); }
+};
+
+// the lists of a device form (n_rows x k row-major: 1-based items, order keys) as the host forms return them
+int fetch_ease_lists(const DevBuf& dR, const DevBuf& dS, int n_rows, int k, int32_t* res, double* scores) {
   const size_t nk = (size_t)n_rows * k;
-  HIP_TRY(dR.alloc(nk * 4));
-  HIP_TRY(dS.alloc(nk * 8));
-  rc = rsparse_hip_ease_recommend_device(dXP.as<int32_t>(), dXJ.as<int32_t>(), n_rows, n_items, dB.p, ld, b_is_double,
-                                         opt<int32_t>(nr_p != nullptr, dP), opt<int32_t>(nr_p != nullptr, dJ),
-                                         opt<int32_t>(!ex.empty(), dE), (int)ex.size(), k, 0, dR.as<int32_t>(), dS.as<uint64_t>(), nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  if ((rc = fetch_col_major(dR, n_rows, k, res))) return rc;
+  if (int rc = fetch_col_major(dR, n_rows, k, res)) return rc;
   std::vector<uint64_t> keys(nk);
-  if ((rc = fetch_col_major(dS, n_rows, k, keys.data()))) return rc;
+  if (int rc = fetch_col_major(dS, n_rows, k, keys.data())) return rc;
   for (size_t t = 0; t < nk; t++) {   // the order key back to its double; NaN where the list has ended
     const uint64_t key = keys[t], bits = (key >> 63) ? key ^ (1ull << 63) : ~key;
     double v;
     std::memcpy(&v, &bits, sizeof v);
     scores[t] = res[t] == INT32_MIN ? std::nan("") : v;
   }
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int rsparse_hip_ease_recommend(const int32_t* x_p, const int32_t* x_j, int n_rows, int n_items, const void* B, int b_is_double,
+                               const int32_t* nr_p, const int32_t* nr_j, const int32_t* exclude, int n_exclude, int k, int32_t* res,
+                               double* scores) {
+  int rc = ease_recommend_args(!x_p || !B || !res || !scores, n_rows, n_items, B, 0, 0, nr_p, nr_j, exclude, n_exclude, k, 0);
+  if (rc) return rc;
+  EaseHostRows in;
+  if ((rc = in.check(x_p, x_j, n_rows, n_items, B, b_is_double, nr_p, nr_j)) || n_rows == 0) return rc;
+  if ((rc = in.upload(x_p, x_j, n_rows, n_items, b_is_double, nr_p, nr_j, exclude, n_exclude))) return rc;
+  DevBuf dR, dS;
+  HIP_TRY(dR.alloc((size_t)n_rows * k * 4));
+  HIP_TRY(dS.alloc((size_t)n_rows * k * 8));
+  rc = rsparse_hip_ease_recommend_device(in.dXP.as<int32_t>(), in.dXJ.as<int32_t>(), n_rows, n_items, in.dB.p, in.ld, b_is_double, in.nr_p(),
+                                         in.nr_j(), in.excl(), (int)in.ex.size(), k, 0, dR.as<int32_t>(), dS.as<uint64_t>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  return fetch_ease_lists(dR, dS, n_rows, k, res, scores);
+}
+
+int rsparse_hip_ease_top_candidates(const int32_t* x_p, const int32_t* x_j, int n_rows, int n_items, const void* B, int b_is_double,
+                                    const int32_t* cand_p, const int32_t* cand_j, const int32_t* nr_p, const int32_t* nr_j,
+                                    const int32_t* exclude, int n_exclude, int k, int32_t* res, double* scores) {
+  int rc = ease_recommend_args(!x_p || !B || !cand_p || !res || !scores, n_rows, n_items, B, 0, 0, nr_p, nr_j, exclude, n_exclude, k, 0);
+  if (rc) return rc;
+  EaseHostRows in;
+  if ((rc = in.check(x_p, x_j, n_rows, n_items, B, b_is_double, nr_p, nr_j))) return rc;
+  if ((rc = check_csr(cand_p, n_rows, "cand_p"))) return rc;
+  const size_t n_cand = (size_t)cand_p[n_rows];
+  if (n_cand && !cand_j) return fail(RSPARSE_HIP_ERR_INVALID, "cand_j is NULL");
+  if ((rc = check_columns(cand_p, cand_j, n_rows, n_items, "cand_j"))) return rc;
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  if ((rc = in.upload(x_p, x_j, n_rows, n_items, b_is_double, nr_p, nr_j, exclude, n_exclude))) return rc;
+  DevBuf dCP, dCJ, dR, dS;
+  HIP_TRY(upload_host(dCP, cand_p, (size_t)n_rows + 1));
+  HIP_TRY(upload_host(dCJ, cand_j, n_cand));
+  HIP_TRY(dR.alloc((size_t)n_rows * k * 4));
+  HIP_TRY(dS.alloc((size_t)n_rows * k * 8));
+  rc = rsparse_hip_ease_top_candidates_device(in.dXP.as<int32_t>(), in.dXJ.as<int32_t>(), n_rows, n_items, in.dB.p, in.ld, b_is_double,
+                                              dCP.as<int32_t>(), dCJ.as<int32_t>(), in.nr_p(), in.nr_j(), in.excl(), (int)in.ex.size(), k, 0,
+                                              dR.as<int32_t>(), dS.as<uint64_t>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  return fetch_ease_lists(dR, dS, n_rows, k, res, scores);
+}
+
+int rsparse_hip_ease_held_out_ranks(const int32_t* x_p, const int32_t* x_j, int n_rows, int n_items, const void* B, int b_is_double,
+                                    const int32_t* actual_p, const int32_t* actual_j, const int32_t* nr_p, const int32_t* nr_j,
+                                    const int32_t* exclude, int n_exclude, int32_t* above, int32_t* tied, int32_t* n_adm) {
+  int rc = ease_recommend_args(!x_p || !B || !actual_p || !above || !tied || !n_adm, n_rows, n_items, B, 0, 0, nr_p, nr_j, exclude,
+                               n_exclude, 1, 0);
+  if (rc) return rc;
+  EaseHostRows in;
+  if ((rc = in.check(x_p, x_j, n_rows, n_items, B, b_is_double, nr_p, nr_j))) return rc;
+  if ((rc = check_csr(actual_p, n_rows, "actual_p"))) return rc;
+  if (actual_p[n_rows] && !actual_j) return fail(RSPARSE_HIP_ERR_INVALID, "actual_j is NULL");
+  if ((rc = check_csr(actual_p, n_rows, "actual_p", actual_j, "actual_j"))) return rc;
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  if ((rc = in.upload(x_p, x_j, n_rows, n_items, b_is_double, nr_p, nr_j, exclude, n_exclude))) return rc;
+  const size_t n_act = (size_t)actual_p[n_rows];
+  DevBuf dAP, dAJ, dA, dT, dN;
+  HIP_TRY(upload_host(dAP, actual_p, (size_t)n_rows + 1));
+  HIP_TRY(upload_host(dAJ, actual_j, n_act));
+  HIP_TRY(dA.alloc(n_act * 4));
+  HIP_TRY(dT.alloc(n_act * 4));
+  HIP_TRY(dN.alloc((size_t)n_rows * 4));
+  rc = rsparse_hip_ease_held_out_ranks_device(in.dXP.as<int32_t>(), in.dXJ.as<int32_t>(), n_rows, n_items, in.dB.p, in.ld, b_is_double,
+                                              dAP.as<int32_t>(), dAJ.as<int32_t>(), in.nr_p(), in.nr_j(), in.excl(), (int)in.ex.size(), 0,
+                                              dA.as<int32_t>(), dT.as<int32_t>(), dN.as<int32_t>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(download(above, dA, n_act));
+  HIP_TRY(download(tied, dT, n_act));
+  HIP_TRY(download(n_adm, dN, (size_t)n_rows));
   return RSPARSE_HIP_OK;
 }
 

@@ -448,6 +448,13 @@ void launch_knn_mask_rows(unsigned long long* ws, size_t ld, int n_items, int n_
 void launch_knn_select_lists(const unsigned long long* ws, size_t ld, int n_items, int n_batch, int k, int32_t* items, long long* scores,
                              hipStream_t s);
 hipError_t launch_knn_zero_rows(void* ws, size_t bytes, hipStream_t s);
+// gather_rows: out[t] = the cell (row(t) - row0, pj[t]) of n_batch uint64 rows for the slots [t0, t1) of the pattern (pp: n_rows + 1
+// absolute slots), 0 for a column outside the items.  ranks_rows: above / tied / n_adm of launch_knn_held_out_ranks for n_batch
+// scored and masked rows (ap: the slots of THESE rows, absolute positions into aj / above / tied; n_adm: of these rows).
+void launch_knn_gather_rows(const int32_t* pp, const int32_t* pj, int n_rows, int row0, int n_batch, unsigned t0, unsigned t1,
+                            const unsigned long long* ws, size_t ld, int n_items, long long* out, hipStream_t s);
+void launch_knn_ranks_rows(const unsigned long long* ws, size_t ld, int n_items, int n_batch, const int32_t* ap, const int32_t* aj,
+                           int32_t* above, int32_t* tied, int32_t* n_adm, hipStream_t s);
 
 // EASE (wrmf_ease.hip; defined in rsparse_wrmf_hip.h), on the ItemKNN workspace (all zeros on entry and again when the enqueued
 // work is done).  item_gram: rows [item0, item1) of G + lambda I in double, `rows` uint32 rows per batch; h_ip: the host copy of
@@ -460,6 +467,25 @@ template <class T>
 hipError_t launch_ease_recommend(const int32_t* xp, const int32_t* xj, int n_rows, int n_items, const T* B, size_t ld_B,
                                  const int32_t* nr_p, const int32_t* nr_j, const int32_t* excl, int n_excl, int k, int64_t rows,
                                  unsigned long long* ws, int32_t* items, long long* scores, hipStream_t s);
+// EASE under the evaluation protocols (operands as launch_ease_recommend; pp / cp / ap: n_rows + 1 absolute slots, h_pp / h_cp their
+// host copies).  A row of m pairs / candidates with m <= RSPARSE_HIP_KNN_LDS_CAND and m RSPARSE_HIP_EASE_CELLS_RATIO <= n_items is
+// scored at its cells (no workspace); the others, in runs of at most `rows` consecutive ones, through the dense rows of ws.
+// scores (score_pairs): one key per slot of pj, the key of +0.0 for a column outside the items.  keys (top_candidates): scratch,
+// one per slot of cj; the candidate columns of a row strictly ascending.  held_out_ranks: every row through ws.
+template <class T>
+hipError_t launch_ease_score_pairs(const int32_t* xp, const int32_t* xj, int n_rows, int n_items, const T* B, size_t ld_B,
+                                   const int32_t* pp, const int32_t* pj, const int32_t* h_pp, int64_t rows, unsigned long long* ws,
+                                   unsigned long long* scores, hipStream_t s);
+template <class T>
+hipError_t launch_ease_top_candidates(const int32_t* xp, const int32_t* xj, int n_rows, int n_items, const T* B, size_t ld_B,
+                                      const int32_t* cp, const int32_t* cj, const int32_t* h_cp, const int32_t* nr_p, const int32_t* nr_j,
+                                      const int32_t* excl, int n_excl, int k, int64_t rows, unsigned long long* ws,
+                                      unsigned long long* keys, int32_t* items, long long* scores, hipStream_t s);
+template <class T>
+hipError_t launch_ease_held_out_ranks(const int32_t* xp, const int32_t* xj, int n_rows, int n_items, const T* B, size_t ld_B,
+                                      const int32_t* ap, const int32_t* aj, const int32_t* nr_p, const int32_t* nr_j, const int32_t* excl,
+                                      int n_excl, int64_t rows, unsigned long long* ws, int32_t* above, int32_t* tied, int32_t* n_adm,
+                                      hipStream_t s);
 
 // top-k within per-user candidate lists (wrmf_candidates.hip), T = float or double, 1 <= topk <= kTopLargeMax: for every row of
 // the CSR pattern (cand_p: n_users + 1 slots, absolute positions into cand_j; p0 = cand_p[0], nnz = cand_p[n_users] - p0, read by

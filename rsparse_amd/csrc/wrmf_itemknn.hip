@@ -771,4 +771,15 @@ void launch_knn_select_lists(const unsigned long long* ws, size_t ld, int n_item
 
 hipError_t launch_knn_zero_rows(void* ws, size_t bytes, hipStream_t s) { return hipMemsetAsync(ws, 0, bytes, s); }
 
+void launch_knn_gather_rows(const int32_t* pp, const int32_t* pj, int n_rows, int row0, int n_batch, unsigned t0, unsigned t1,
+                            const unsigned long long* ws, size_t ld, int n_items, long long* out, hipStream_t s) {
+  hipLaunchKernelGGL(knn_gather_kernel<0>, dim3(scatter_grid(t0, t1)), dim3(kThreads), 0, s, pp, pj, n_rows, row0, n_batch, t0, t1, ws, ld,
+                     n_items, out);
+}
+
+void launch_knn_ranks_rows(const unsigned long long* ws, size_t ld, int n_items, int n_batch, const int32_t* ap, const int32_t* aj,
+                           int32_t* above, int32_t* tied, int32_t* n_adm, hipStream_t s) {
+  hipLaunchKernelGGL(knn_ranks_kernel<0>, dim3((unsigned)n_batch), dim3(kThreads), 0, s, ws, ld, n_items, ap, aj, above, tied, n_adm);
+}
+
 }  // namespace rsparse_hip

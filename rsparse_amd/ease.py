@@ -29,18 +29,21 @@ scores have equal keys; and no finite score maps to the key 0 (that would be the
 positive NaN): the device keeps 0 for "no cell" and all ones for "masked".
 
   ease_gram_reference, ease_weights_reference, ease_scores_reference, ease_recommend_reference      the definition, in numpy
+  ease_score_pairs_reference, ease_candidates_reference, ease_ranks_reference      the same scores under the evaluation protocols of
+                                    the other models: at given cells, ranked within per-row candidates, counted against held-out items
   score_keys, key_scores            the order key and its inverse
   spd_inverse, cholesky_inverse_blocked, weights_from_inverse      the factorisation (torch.linalg.cholesky_ex, torch.cholesky_inverse /
                                     torch.cholesky_solve) and the step from P to B
-  EASE                              the model: fit / predict / evaluate / similar_items
+  EASE                              the model: fit / predict / evaluate / similar_items, and score / sample_negatives /
+                                    held_out_ranks / evaluate_ranks with the conventions of `ItemKNN`'s
 """
 import numpy as np
 import scipy.sparse as sp
 import torch
 
 from . import _lib
-from .itemknn import canonical_pattern, evaluate_lists
-from .wrmf import TopItems
+from .itemknn import _admissible_rows, canonical_pattern, evaluate_lists
+from .wrmf import WRMF, TopItems
 
 PRECISIONS = {"float": np.float32, "double": np.float64}
 ROW_BYTES = 256   # every row of the resident B starts at a multiple of this
@@ -132,6 +135,64 @@ def ease_recommend_reference(x, B, k, not_recommend=None, items_exclude=()):
         items[u, :first.size] = first
         scores[u, :first.size] = score[u, first]
     return items, scores
+
+
+def ease_score_pairs_reference(x, B, pairs):
+    """-> float64, one per stored position of canonical_pattern(pairs) (a sparse matrix of x's shape): the score of
+    `ease_scores_reference` at that cell.  Nothing is masked."""
+    score = ease_scores_reference(x, B)
+    pat = canonical_pattern(pairs, score.shape[1])
+    if pat.shape != score.shape:
+        raise ValueError("pairs must have the shape of x")
+    rows = np.repeat(np.arange(pat.shape[0]), np.diff(pat.indptr))
+    return score[rows, pat.indices].astype(np.float64)
+
+
+def ease_candidates_reference(x, B, candidates, k, not_recommend=None, items_exclude=()):
+    """-> (items (n, k) int64 with -1, scores (n, k) float64 with 0 in the padding): `ease_recommend_reference` within per-row
+    candidates.  The admissible items of a row are the stored positions of its row of canonical_pattern(candidates) minus the
+    row's not_recommend entries minus items_exclude; the order is that of the score's key, descending, equal scores to the SMALLER
+    item.  Candidates of score 0 are ranked; a list is shorter than k only when fewer than k candidates are admissible."""
+    score = ease_scores_reference(x, B)
+    cand = canonical_pattern(candidates, score.shape[1])
+    if cand.shape != score.shape:
+        raise ValueError("candidates must have the shape of x")
+    adm = _admissible_rows(score.shape, not_recommend, items_exclude)
+    k = int(k)
+    items = np.full((score.shape[0], k), -1, dtype=np.int64)
+    scores = np.zeros((score.shape[0], k), dtype=np.float64)
+    for u in range(score.shape[0]):
+        c = cand.indices[cand.indptr[u]:cand.indptr[u + 1]].astype(np.int64)
+        c = c[adm(u)[c]]
+        first = c[np.lexsort((c, ~score_keys(score[u, c])))[:k]]
+        items[u, :first.size] = first
+        scores[u, :first.size] = score[u, first]
+    return items, scores
+
+
+def ease_ranks_reference(x, B, actual, not_recommend=None, items_exclude=()):
+    """-> (above, tied: int32, one per stored entry of `actual` (CSR with sorted columns, duplicates merged, stored zeros kept);
+    n_adm: int32 per row), exactly as `itemknn.knn_ranks_reference` defines them with s the double score: A_u = the items outside
+    the not_recommend row and outside items_exclude, n_adm = |A_u|; above = #{j in A_u : s_j > s_h}, tied = #{j in A_u, j != h :
+    s_j == s_h}; an entry outside A_u (or outside the items) gets -1 / -1."""
+    from .metrics import canonical_actual
+    score = ease_scores_reference(x, B)
+    n, n_items = score.shape
+    act = canonical_actual(actual, n)
+    adm = _admissible_rows(score.shape, not_recommend, items_exclude)
+    above = np.full(act.nnz, -1, dtype=np.int32)
+    tied = np.full(act.nnz, -1, dtype=np.int32)
+    n_adm = np.zeros(n, dtype=np.int32)
+    for u in range(n):
+        a = adm(u)
+        n_adm[u] = a.sum()
+        s_adm = score[u, a]
+        for e in range(act.indptr[u], act.indptr[u + 1]):
+            h = int(act.indices[e])
+            if 0 <= h < n_items and a[h]:
+                above[e] = np.count_nonzero(s_adm > score[u, h])
+                tied[e] = np.count_nonzero(s_adm == score[u, h]) - 1
+    return above, tied, n_adm
 
 
 INVERSE_BLOCK = 2048   # right-hand sides of one torch.cholesky_solve
@@ -263,8 +324,9 @@ class EASE:
         self._B, self._n_items, self.item_count = B, n_items, cnt
         return self
 
-    def _lists(self, x, k, not_recommend, items_exclude, ws_rows=0):
-        """-> (items int32 (n, k) 1-based with NA_integer_, scores float64 (n, k) numpy with NaN where NA)"""
+    def _rows(self, x, not_recommend="x", items_exclude=()):
+        """what every scoring call starts with -> (m: x as a canonical pattern, be, not_recommend as CSR or None, items_exclude
+        sorted and unique)"""
         self._fitted()
         self._one_rank()
         n_items = self._n_items
@@ -280,39 +342,156 @@ class EASE:
             not_recommend = sp.csr_matrix(not_recommend)
             if not_recommend.shape != m.shape:
                 raise ValueError("not_recommend must have the shape of x")
+        return m, self._backend(), not_recommend, excl
+
+    def _host_B(self):
+        return self._B[:, :self._n_items].cpu().numpy()
+
+    @staticmethod
+    def _device_filters(be, not_recommend, excl):
+        nr_p = nr_j = None
+        if not_recommend is not None and not_recommend.nnz:
+            nr_p, nr_j = be.to_device(not_recommend.indptr, torch.int32), be.to_device(not_recommend.indices, torch.int32)
+        return {"nr_p": nr_p, "nr_j": nr_j, "exclude0": be.to_device(excl, torch.int32) if len(excl) else None}
+
+    @staticmethod
+    def _pattern(pairs, m, what):
+        """`pairs` (a scipy sparse of x's shape) as a canonical CSR pattern of ones: columns ascending, duplicates merged, every
+        stored position kept (a stored zero too)"""
+        if not sp.issparse(pairs):
+            raise TypeError("'%s' should be a 'sparseMatrix'" % what)
+        if pairs.shape != m.shape:
+            raise ValueError("%s must have the shape of x" % what)
+        pat = sp.csr_matrix(pairs, dtype=np.float64, copy=True)
+        pat.data[:] = 1.0
+        return canonical_pattern(pat)
+
+    def _lists(self, x, k, not_recommend, items_exclude, ws_rows=0, candidates=None):
+        """-> (items int32 (n, k) 1-based with NA_integer_, scores float64 (n, k) numpy with NaN where NA); candidates: a scipy
+        sparse of x's shape, or None (the whole catalogue)"""
+        m, be, not_recommend, excl = self._rows(x, not_recommend, items_exclude)
+        n_items = self._n_items
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
             raise ValueError("k must be an integer >= 1")
         if k > _lib.KNN_MAX_TOPK:
             raise _lib.UnsupportedOnDevice(_lib.ERR_UNSUPPORTED, "predict: k > 1024 is not on the device path")
-        be = self._backend()
-        if not hasattr(be, "ease_recommend"):
-            it, sc = ease_recommend_reference(m, self._B[:, :n_items].cpu().numpy(), k, not_recommend, excl)
+        cand = None if candidates is None else self._pattern(candidates, m, "candidates")
+        if not hasattr(be, "ease_recommend" if cand is None else "ease_top_candidates"):
+            if cand is None:
+                it, sc = ease_recommend_reference(m, self._host_B(), k, not_recommend, excl)
+            else:
+                it, sc = ease_candidates_reference(m, self._host_B(), cand, k, not_recommend, excl)
             res = np.where(it < 0, np.int64(-2147483648), it + 1).astype(np.int32)
             return torch.from_numpy(res), np.where(it < 0, np.nan, sc)
-        nr_p = nr_j = None
-        if not_recommend is not None and not_recommend.nnz:
-            nr_p, nr_j = be.to_device(not_recommend.indptr, torch.int32), be.to_device(not_recommend.indices, torch.int32)
-        d_ex = be.to_device(excl, torch.int32) if len(excl) else None
-        res, keys = be.ease_recommend(be.to_device(m.indptr, torch.int32), be.to_device(m.indices, torch.int32), self._B, n_items, k,
-                                      nr_p, nr_j, d_ex, ws_rows=ws_rows)
+        filters = self._device_filters(be, not_recommend, excl)
+        xp, xj = be.to_device(m.indptr, torch.int32), be.to_device(m.indices, torch.int32)
+        if cand is None:
+            res, keys = be.ease_recommend(xp, xj, self._B, n_items, k, filters["nr_p"], filters["nr_j"], filters["exclude0"], ws_rows=ws_rows)
+        else:
+            res, keys = be.ease_top_candidates(xp, xj, self._B, n_items, k, be.to_device(cand.indptr, torch.int32),
+                                               be.to_device(cand.indices, torch.int32), ws_rows=ws_rows, **filters)
         pad = (res == -2147483648).cpu().numpy()
         return res, np.where(pad, np.nan, key_scores(keys.cpu().numpy()))
 
-    def predict(self, x, k, not_recommend="x", items_exclude=(), ws_rows=0):
+    def predict(self, x, k, not_recommend="x", items_exclude=(), ws_rows=0, candidates=None):
         """the k best items of every row of x, with the conventions of `ItemKNN.predict`: `not_recommend` (default: x itself; None =
         nothing) and `items_exclude` (0-based) are skipped; -> `TopItems` (n x k, 0-based, -1 where fewer than k items are
-        admissible) with `.scores` (float64, the sums of the definition; NaN in the padding).  1 <= k <= 1024."""
-        res, sc = self._lists(x, k, not_recommend, items_exclude, ws_rows)
+        admissible) with `.scores` (float64, the sums of the definition; NaN in the padding).  1 <= k <= 1024.
+
+        `candidates` (a scipy sparse of x's shape; its values are ignored): every row is ranked within its own stored positions
+        -- two-stage serving, a catalogue slice per user, sampled-negative evaluation.  The filters still apply; candidates of
+        score 0 are ranked; a list is shorter than k only when fewer than k candidates are admissible.  The order is the model's
+        own -- score descending, equal scores to the SMALLER item -- and NOT the reference heap's rule that
+        `WRMF.predict(candidates=)` follows.  `candidates` holding every item reproduces `predict(x, k)` exactly.  A row of few
+        candidates is scored at its cells of B alone; one of many through its dense score row (`_lib.EASE_CELLS_RATIO`)."""
+        res, sc = self._lists(x, k, not_recommend, items_exclude, ws_rows, candidates)
         idx = res.cpu().numpy().astype(np.int64)
         out = np.where(idx == -2147483648, -1, idx - 1).view(TopItems)
         out.scores = sc
         return out
 
-    def evaluate(self, x, actual, k, not_recommend="x", items_exclude=(), metrics=("ap", "ndcg"), diversify=None):
+    def sample_negatives(self, x, n, actual=None, not_recommend="x", items_exclude=(), seed=None, weights=None):
+        """`WRMF.sample_negatives` for the shape of x: the candidate matrix of a sampled-metric evaluation -- every row's stored
+        positions of `actual` plus min(n, admissible) items drawn without replacement from those neither in `not_recommend`, nor
+        in `actual`, nor in `items_exclude`.  The negatives depend on (seed, row, the row's exclusions, n_items, n) alone, so they
+        ARE the ones `WRMF.sample_negatives(x, n, actual=, seed=)` returns for that seed.  `seed` is required: EASE has no
+        generator to draw one from."""
+        if seed is None:
+            raise ValueError("sample_negatives needs a seed: EASE has no generator to draw one from")
+        self._one_rank()
+        return WRMF(backend=self._backend()).sample_negatives(x, n, actual=actual, not_recommend=not_recommend,
+                                                              items_exclude=items_exclude, seed=seed, weights=weights)
+
+    def score(self, x, pairs, ws_rows=0):
+        """the model's score of the rows of x at given (user, item) cells: a scipy CSR matrix (float64) with the pattern of `pairs`
+        (x's shape; columns sorted, duplicates merged, stored zeros are positions too) and, as values, the sums of the definition,
+        the bits `predict`'s `.scores` have.  Nothing is masked: an item of the row's own history has its score too."""
+        m, be, _, _ = self._rows(x, None)
+        pat = self._pattern(pairs, m, "pairs")
+        if not hasattr(be, "ease_score_pairs"):
+            sc = ease_score_pairs_reference(m, self._host_B(), pat)
+        else:
+            keys = be.ease_score_pairs(be.to_device(m.indptr, torch.int32), be.to_device(m.indices, torch.int32), self._B, self._n_items,
+                                       be.to_device(pat.indptr, torch.int32), be.to_device(pat.indices, torch.int32), ws_rows=ws_rows)
+            sc = key_scores(keys.cpu().numpy())
+        return sp.csr_matrix((sc, pat.indices, pat.indptr), shape=pat.shape)
+
+    def _ranks(self, x, actual, not_recommend, items_exclude, ws_rows=0):
+        """-> (be, actual as canonical CSR, (above, tied, n_adm) as tensors of the backend)"""
+        from .metrics import canonical_actual
+        m, be, not_recommend, excl = self._rows(x, not_recommend, items_exclude)
+        if not sp.issparse(actual):
+            raise TypeError("'actual' should be a 'sparseMatrix'")
+        if actual.shape != m.shape:
+            raise ValueError("actual must have the shape of x")
+        act = canonical_actual(actual, m.shape[0])
+        if not hasattr(be, "ease_held_out_ranks"):
+            got = ease_ranks_reference(m, self._host_B(), act, not_recommend, excl)
+            return be, act, tuple(be.to_device(v, torch.int32) for v in got)
+        got = be.ease_held_out_ranks(be.to_device(m.indptr, torch.int32), be.to_device(m.indices, torch.int32), self._B, self._n_items,
+                                     be.to_device(act.indptr, torch.int32), be.to_device(act.indices, torch.int32), ws_rows=ws_rows,
+                                     **self._device_filters(be, not_recommend, excl))
+        return be, act, got
+
+    def held_out_ranks(self, x, actual, not_recommend="x", items_exclude=(), ws_rows=0):
+        """where every held-out interaction stands among ALL the items the user could be shown, by the model's score:
+        `WRMF.held_out_ranks` for this model.  The admissible items of a row are those outside its `not_recommend` row (default:
+        x itself) and outside `items_exclude`; for every stored entry (u, h) of `actual` (x's shape; stored zeros are entries):
+        above = admissible items scored strictly higher than h, tied = other admissible items with an equal score, -1 / -1 when h
+        itself is not admissible.  -> (above, tied: scipy CSR (int32) with the canonical pattern of `actual`; n_adm: the
+        admissible items per row, int32).  The 0-based midrank of an entry is above + tied / 2."""
+        _, act, (above, tied, n_adm) = self._ranks(x, actual, not_recommend, items_exclude, ws_rows)
+        mk = lambda v: sp.csr_matrix((v.cpu().numpy().astype(np.int32), act.indices.copy(), act.indptr.copy()), shape=act.shape)
+        return mk(above), mk(tied), n_adm.cpu().numpy().astype(np.int32)
+
+    def evaluate_ranks(self, x, actual, not_recommend="x", items_exclude=(), per_user=False):
+        """the full-ranking metrics of the held-out interactions `actual` (values = weights) from `held_out_ranks`' counts, with
+        the formulas and the return shape of `WRMF.evaluate_ranks`: {"mpr", "auc", "mrr", "n"}; per_user=True adds "mpr_per_user",
+        "auc_per_user", "mrr_per_user" and "n_adm_per_user"."""
+        from .metrics import rank_totals
+        be, act, (above, tied, n_adm) = self._ranks(x, actual, not_recommend, items_exclude)
+        fn = be.rank_summary if hasattr(be, "rank_summary") else WRMF._rank_summary_host
+        mpr, auc, mrr, sums = fn(be.to_device(act.indptr, torch.int32), be.to_device(act.data, torch.float64), above, tied, n_adm)
+        sums = sums.cpu().numpy()
+        per = {"mpr": mpr.cpu().numpy(), "auc": auc.cpu().numpy(), "mrr": mrr.cpu().numpy()}
+        out = rank_totals({"sum_w": sums[:, 0], "sum_w_pct": sums[:, 1], "P": sums[:, 2], "auc": per["auc"], "mrr": per["mrr"]})
+        if per_user:
+            out.update({name + "_per_user": v for name, v in per.items()})
+            out["n_adm_per_user"] = n_adm.cpu().numpy().astype(np.int32)
+        return out
+
+    def evaluate(self, x, actual, k, not_recommend="x", items_exclude=(), metrics=("ap", "ndcg"), diversify=None, candidates=None,
+                 negatives=None, seed=None, negative_weights=None):
         """`predict(x, max(k), ...)` once, scored against the held-out `actual` by the package's list metrics, routed exactly as
         `ItemKNN.evaluate` routes them: "ap", "ndcg", "precision", "recall", "hit", "mrr", "coverage", "popularity", "novelty".
         k: a cutoff or a strictly ascending sequence of them.  "diversity" and `diversify=` need item vectors, which this model
-        does not have: `UnsupportedOnDevice`."""
+        does not have: `UnsupportedOnDevice`.
+
+        `candidates`: as in `predict` -- every metric is computed on the lists ranked within the rows' candidates.
+        `negatives=n` with `seed` makes those candidates itself, the sampled protocol of `WRMF.evaluate(negatives=)`: every row's
+        held-out items against n negatives, exactly `candidates=self.sample_negatives(x, n, actual, not_recommend,
+        items_exclude, seed, negative_weights)` -- the negatives `WRMF.sample_negatives` returns for that seed.  `seed` is
+        required with `negatives`; `negatives` excludes `candidates`; `negative_weights` needs `negatives`."""
         from .metrics import HIT_METRICS, LIST_METRICS, check_cutoffs
         metrics = tuple(metrics)
         if "diversity" in metrics or diversify is not None:
@@ -322,7 +501,16 @@ class EASE:
             raise ValueError("metrics must name some of %s" % ", ".join(repr(name) for name in known))
         scalar_k = not isinstance(k, (tuple, list, np.ndarray, range))
         cutoffs = check_cutoffs((int(k),) if scalar_k else k)
-        res, _ = self._lists(x, int(cutoffs[-1]), not_recommend, items_exclude)
+        if negatives is not None and candidates is not None:
+            raise ValueError("negatives and candidates exclude each other: the negatives ARE the candidates")
+        if negative_weights is not None and negatives is None:
+            raise ValueError("negative_weights needs negatives: they weight the sampled negatives")
+        if negatives is not None:
+            if seed is None:
+                raise ValueError("negatives needs a seed: EASE has no generator to draw one from")
+            candidates = self.sample_negatives(x, negatives, actual=actual, not_recommend=not_recommend, items_exclude=items_exclude,
+                                               seed=seed, weights=negative_weights)
+        res, _ = self._lists(x, int(cutoffs[-1]), not_recommend, items_exclude, candidates=candidates)
         return evaluate_lists(self._backend(), res, actual, self._n_items, self.item_count, metrics, cutoffs, scalar_k)
 
     def similar_items(self, items=None, k=10):

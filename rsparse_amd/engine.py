@@ -898,6 +898,55 @@ class HipBackend:
             0 if exclude0 is None else int(exclude0.numel()), int(k), int(ws_rows), some(res), some(keys), self._stream()))
         return res, keys
 
+    def _ease_rows(self, xp, xj, B, n_items):
+        """the operands the EASE evaluation entries share with `ease_recommend`, as the C ABI takes them: -> (the leading
+        arguments, `some`: the address of a tensor, or of xp for an empty one)"""
+        assert xp.dtype == torch.int32 and xj.dtype == torch.int32 and B.dtype in (torch.float32, torch.float64) and B.is_cuda
+        n, n_items = int(xp.numel()) - 1, int(n_items)
+        assert B.dim() == 2 and B.shape[0] == n_items and B.shape[1] >= n_items and (B.shape[1] <= 1 or B.stride(1) == 1)
+        ld = int(B.stride(0)) if n_items > 1 else int(B.shape[1])
+        some = lambda t: t.data_ptr() if t.numel() else xp.data_ptr()
+        return (xp.data_ptr(), some(xj), n, n_items, some(B), ld, int(B.dtype == torch.float64)), some
+
+    def ease_score_pairs(self, xp, xj, B, n_items, pp, pj, ws_rows=0):
+        """the EASE score of the rows of (xp, xj) -- operands as `ease_recommend` -- at the stored positions of the pattern (pp, pj:
+        int32 on the device, over the same rows); nothing is masked, a column outside the items gives the key of +0.0.
+        rsparse_amd.ease.ease_score_pairs_reference is the definition.  -> int64 holding the uint64 order keys, one per element of
+        pj, on the device."""
+        head, some = self._ease_rows(xp, xj, B, n_items)
+        assert pp.dtype == torch.int32 and pj.dtype == torch.int32 and pp.numel() == xp.numel()
+        out = torch.zeros(int(pj.numel()), dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.rsparse_hip_ease_score_pairs_device(*head, pp.data_ptr(), some(pj), int(ws_rows), some(out), self._stream()))
+        return out
+
+    def ease_top_candidates(self, xp, xj, B, n_items, k, cp, cj, nr_p=None, nr_j=None, exclude0=None, ws_rows=0):
+        """`ease_recommend` within the rows' candidates (cp, cj: a canonical CSR pattern over the same rows -- columns strictly
+        ascending within a row --, int32 on the device; cp may be a slice of the row pointers, its slots absolute).
+        rsparse_amd.ease.ease_candidates_reference is the definition.  -> (items (n, k) int32, 1-based with NA_integer_; keys
+        (n, k) int64 holding the uint64 order keys, 0 where NA) on the device."""
+        head, some = self._ease_rows(xp, xj, B, n_items)
+        assert cp.dtype == torch.int32 and cj.dtype == torch.int32 and cp.numel() == xp.numel()
+        n = head[2]
+        res = torch.empty((n, int(k)), dtype=torch.int32, device=self.device)
+        keys = torch.empty((n, int(k)), dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.rsparse_hip_ease_top_candidates_device(*head, cp.data_ptr(), some(cj), *self._knn_filters(some, nr_p, nr_j, exclude0),
+                                                                   int(k), int(ws_rows), some(res), some(keys), self._stream()))
+        return res, keys
+
+    def ease_held_out_ranks(self, xp, xj, B, n_items, ap, aj, nr_p=None, nr_j=None, exclude0=None, ws_rows=0):
+        """where the entries of (ap, aj: CSR over the same rows, int32 on the device) stand among the row's admissible items by the
+        EASE score (rsparse_amd.ease.ease_ranks_reference; the counts `held_out_ranks` defines).  -> (above, tied: int32, one per
+        element of aj, -1 / -1 for an inadmissible entry; n_adm: int32 per row) on the device."""
+        head, some = self._ease_rows(xp, xj, B, n_items)
+        assert ap.dtype == torch.int32 and aj.dtype == torch.int32 and ap.numel() == xp.numel()
+        n = head[2]
+        above = torch.full((int(aj.numel()),), -1, dtype=torch.int32, device=self.device)
+        tied = torch.full((int(aj.numel()),), -1, dtype=torch.int32, device=self.device)
+        n_adm = torch.zeros(n, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.rsparse_hip_ease_held_out_ranks_device(*head, ap.data_ptr(), some(aj), *self._knn_filters(some, nr_p, nr_j, exclude0),
+                                                                   int(ws_rows), some(above), some(tied), some(n_adm), self._stream()))
+        return above, tied, n_adm
+
     def _knn_rows(self, xp, xj, neighbors, q, xv):
         """the operands the ItemKNN evaluation entries share with `knn_recommend`, as the C ABI takes them: -> (the leading
         arguments, `some`: the address of a tensor, or of xp for an empty one; the tensors that must outlive the call)"""
