@@ -316,7 +316,9 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
 
     if constexpr (!KFULL) load_warm_start();
 
-    // mode 0: out = X_nnz (c - c1 % (X_nnz^T v + g)) - G v (+ base); mode 1: out = X_nnz (c1 % X_nnz^T v) + G v; mode 2: loss
+    // mode 0: out = X_nnz (c - c1 % (X_nnz^T v + g)) - G v (+ base); mode 1: out = X_nnz (c1 % X_nnz^T v) + G v; mode 2: loss;
+    // mode 3: loss_out = v . (mode 1's out) = v . G v + sum_j (c_j - 1) t_j^2 from the dots alone -- t is recorded as in mode 1, no
+    // vector is formed (the last CG step: als_cgq_kernel's mode 3)
     auto sweep = [&](const float(&v)[RPN], const int mode, float(&out)[RPN], float& loss_out) {
       float acc[RPN];
 #pragma unroll
@@ -446,6 +448,10 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
               const float c = GREG ? cv[q] : (QUAD ? nx[64 + q] : nx[64 + 2 * q + g2]);
               trec[SS * q] = t[u];
               const float w = mode == 0 ? c - (c - 1.f) * (GB ? t[u] + gbias : t[u]) : (c - 1.f) * t[u];
+              if (mode == 3) {   // (t is uniform in the group: counted once per group; a slot beyond the row has c = 0, t = 0)
+                lacc = fmaf(w, t[u], lacc);
+                continue;
+              }
 #pragma unroll
               for (int rr = 0; rr < RPN; rr++) acc[rr] = fmaf(w, xt[q][rr], acc[rr]);
             }
@@ -464,6 +470,20 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
         // (QUAD: into the group's own sums, and there is nothing to reduce)
         __syncthreads();
         const float f = (QUAD || g2 == 0) ? vinv : 0.f;
+        if (mode == 3) {
+          // v . G v in place: this lane's eight products, the group's 16 lanes, group 0's share beside the quads' sum
+          float dl = 0.f;
+#pragma unroll
+          for (int b = 0; b < NV; b++) {
+            const float* po = QUAD ? sOut + lcol * SM::os + b * 16 * VW + li * VW : sOut + col * SM::os + b * 16 * VW + i * VW;
+            const f32x4 o = *reinterpret_cast<const f32x4*>(po);
+#pragma unroll
+            for (int c = 0; c < VW; c++) dl = fmaf(o[c], v[b * VW + c], dl);
+          }
+          lacc = fmaf(f, row16_sum(dl), lacc);
+          loss_out = QUAD ? lacc : pair_sum(lacc);
+          return;
+        }
 #pragma unroll
         for (int b = 0; b < NV; b++) {
           const float* po = QUAD ? sOut + lcol * SM::os + b * 16 * VW + li * VW : sOut + col * SM::os + b * 16 * VW + i * VW;
@@ -504,7 +524,8 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
     for (int rr = 0; rr < RPN; rr++) p[rr] = r[rr];
     float rsold = dot16(r, r);
     bool conv = !live;   // a dead half keeps in step: its vectors are zero, its updates are masked
-    for (int itc = 0; itc < a.cg_steps; ++itc) {
+    // every step but the last, which leaves no r and no p behind (below)
+    for (int itc = 0; itc + 1 < a.cg_steps; ++itc) {
       sweep(p, 1, ap, dummy);
       const float pap = dot16(p, ap);
       // rsold / alpha / beta as the reference holds them: double scalars fed by T-valued dot products (wrmf_implicit.hpp:18-27)
@@ -528,6 +549,18 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
           rsold = rsnew;
         }
       }
+    }
+    // the last step: p' A p = p' G p + sum_j (c_j - 1) (x_j . p)^2 needs the dots and the dense product, not the vector A p --
+    // nothing reads the residual behind it: the loss comes from t_acc, the row from x
+    if (a.cg_steps > 0) {
+      float pap = 0.f;
+      sweep(p, 3, ap, pap);
+      const float alpha = conv ? 0.f : (float)((double)rsold / (double)pap);
+      wave_sync();
+      if (lgrp) tacc[lslot] = fmaf(alpha, tcur[lslot], tacc[lslot]);
+      wave_sync();
+#pragma unroll
+      for (int rr = 0; rr < RPN; rr++) x[rr] = fmaf(alpha, p[rr], x[rr]);
     }
     float rl = 0.f;
     sweep(x, 2, ap, rl);
@@ -555,11 +588,14 @@ __global__ __launch_bounds__(256, 2) void als_cgp_kernel(AlsArgs a, const int32_
     }
   }
   const double other = __shfl(wloss, 32);
+  // (the lane number counted afresh: `lane` would keep the thread id in a register across the row loop for this one test, the
+  //  register that the two-row rank-128 kernel does not have)
+  const bool first_lane = __lane_id() == 0;
   if constexpr (QUAD) {   // the wave's four groups
     const double wsum = (wloss + __shfl(wloss, 16)) + (other + __shfl(wloss, 48));
-    if (lane == 0) a.loss_partials[loss_slot0 + (size_t)blockIdx.x * 4 + wv] = wsum;
+    if (first_lane) a.loss_partials[loss_slot0 + (size_t)blockIdx.x * 4 + wv] = wsum;
   } else {
-    if (lane == 0) a.loss_partials[loss_slot0 + (size_t)blockIdx.x * 4 + wv] = wloss + other;
+    if (first_lane) a.loss_partials[loss_slot0 + (size_t)blockIdx.x * 4 + wv] = wloss + other;
   }
 }
 

@@ -118,6 +118,48 @@ struct QSmem {
       (gram_floats + vec_floats + red_floats + tsv_floats + pre_floats + dmf_floats + pfx_floats + wl_floats + xs_floats) * 4 + 16;
 };
 
+// The last CG step of an instantiation (DESIGN.md 3.1 "The last CG step from its dots"): from its dots alone (mode 3 of the sweep),
+// standing as the loop's last trip or behind the loop, or the full step like every other one.  The arithmetic does not care; the
+// register allocator does -- a second inlined sweep moves it at the 256-register edge, one way in one kernel and the other way
+// in its neighbour -- so the form is a compile-time choice per instantiation: dots-only in the loop unless listed here, and an
+// instantiation that neither dots-only form compiles to the parent's spills, scratch and occupancy keeps the full step.  The
+// rows are the template arguments as tools/kernel_resources.py --all prints them; profiles/r12/kernel_resource_usage.md has
+// the three forms of every instantiation, from which this list is read off (another compiler: read it off again).
+constexpr int kLastFull = 0, kLastDotsInLoop = 1, kLastDotsBehind = 2;
+struct LastStepChoice { int kp, capq, waves, wpr, stream; bool implicit; int dmf; bool gb, kfull; int form; };
+constexpr LastStepChoice kLastStepChoices[] = {
+    {64, 32, 4, 1, 0, true, 0, true, false, kLastFull},
+    {64, 16, 4, 1, 0, true, 0, true, true, kLastFull},
+    {64, 32, 4, 1, 0, true, 0, false, true, kLastFull},
+    {64, 16, 4, 1, 0, true, 0, false, false, kLastFull},
+    {64, 16, 4, 1, 0, false, 0, false, true, kLastFull},
+    {128, 16, 8, 8, 0, true, 0, true, true, kLastFull},
+    {128, 16, 8, 8, 0, true, 0, true, false, kLastFull},
+    {128, 16, 4, 2, 0, true, 0, true, true, kLastFull},
+    {128, 16, 4, 1, 0, true, 2, true, true, kLastFull},
+    {128, 16, 8, 8, 0, true, 0, false, false, kLastFull},
+    {32, 8, 4, 1, 0, false, 0, false, true, kLastDotsBehind},
+    {64, 32, 4, 2, 0, true, 0, true, false, kLastDotsBehind},
+    {64, 32, 4, 2, 0, true, 0, false, false, kLastDotsBehind},
+    {128, 16, 4, 4, 0, true, 0, true, false, kLastDotsBehind},
+    {128, 16, 4, 2, 0, true, 0, true, false, kLastDotsBehind},
+    {128, 24, 4, 4, 0, true, 0, false, true, kLastDotsBehind},
+    {128, 24, 4, 4, 0, true, 0, false, false, kLastDotsBehind},
+    {128, 20, 4, 4, 0, true, 0, false, true, kLastDotsBehind},
+    {128, 20, 4, 4, 0, true, 0, false, false, kLastDotsBehind},
+    {128, 16, 4, 4, 0, true, 0, false, false, kLastDotsBehind},
+    {128, 16, 4, 2, 0, true, 0, false, false, kLastDotsBehind},
+    {128, 16, 4, 1, 0, true, 2, false, false, kLastDotsBehind},
+    {128, 20, 4, 4, 0, false, 0, false, true, kLastDotsBehind},
+};
+constexpr int last_step_form(int KP, int CAPQ, int WAVES, int WPR, int STREAM, bool IMPLICIT, int DMF, bool GB, bool KFULL) {
+  for (const LastStepChoice& c : kLastStepChoices)
+    if (c.kp == KP && c.capq == CAPQ && c.waves == WAVES && c.wpr == WPR && c.stream == STREAM && c.implicit == IMPLICIT &&
+        c.dmf == DMF && c.gb == GB && c.kfull == KFULL)
+      return c.form;
+  return kLastDotsInLoop;
+}
+
 // GB: implicit feedback with a global bias (cg_solver_implicit_global_bias, wrmf_implicit.hpp:35-57,203): the first
 // residual is  X_nnz (c - c1 % (X_nnz^T x + global_bias)) - XtX x + global_bias_base  (a.gbias, a.rhs_init), every row is
 // solved -- empty ones too (:178) -- and the loss compares x_j.y with 1 - global_bias (a.loss_tgt_const, :262-264).
@@ -403,8 +445,9 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         if constexpr (CVLDS) {
           csv_fill([&](int sl) { return pfxC[sl]; }, n);
         } else if constexpr (TSAVE) {
+          const int lo = opaque_lane<true>(lane);   // (the slot's address formed here, per row, not kept across the row loop)
 #pragma unroll
-          for (int s2 = 0; s2 < NSL; s2++) cl[s2] = lane + 64 * s2 < n ? pfxC[min(lane + 64 * s2, CAP - 1)] : 0.f;
+          for (int s2 = 0; s2 < NSL; s2++) cl[s2] = lane + 64 * s2 < n ? pfxC[min(lo + 64 * s2, CAP - 1)] : 0.f;
         }
         wave_sync();
       } else if (IDXPF && from_pf) {
@@ -589,6 +632,10 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
             if (mode == 2) {
               const float d = IMPLICIT ? ltgt - t[u] : c - t[u];
               lacc += valid ? (IMPLICIT ? c * d * d : d * d) : 0.f;
+            } else if (mode == 3) {
+              // this non-zero's share of v' A v (t is uniform in the group: counted once per group, as the loss is)
+              const float w = IMPLICIT ? (c - 1.f) * t[u] : t[u];
+              lacc = fmaf(valid ? w : 0.f, t[u], lacc);
             } else {
               float w;
               if (mode == 0) w = IMPLICIT ? c - (c - 1.f) * (GB ? t[u] + gbias : t[u]) : c - t[u];
@@ -603,12 +650,16 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
     };
 
     // mode 0: out = X_nnz (c - c1 % X_nnz^T v) - G v ; mode 1: out = X_nnz (c1 % X_nnz^T v) + G v ; mode 2: loss
+    // mode 3: loss_out = v . (mode 1's out) from the dots alone, v' G v + sum_j (c_j - 1) t_j^2  (explicit: sum_j t_j^2 + lambda v . v):
+    // t is formed and recorded as in mode 1, the dense product is dotted with v in place, and what the waves of a team exchange
+    // is one float through the loss's slot -- no vector is formed, reduced or published.  The barriers are mode 1's.
     auto sweep = [&](const float(&v)[RPN], const int mode, float(&out)[RPN], float& loss_out, const bool live,
                      const int sidx = 0) {
       float acc[RPN];
 #pragma unroll
       for (int rr = 0; rr < RPN; rr++) acc[rr] = 0.f;
       float lacc = 0.f;
+      float dl = 0.f;   // mode 3: this lane's share of v . G v
       float vinv = 0.f;   // DMF: 2^-(scale of v) * 2^-(scale of G) with the sign of the mode
       if constexpr (DMF) {
         if (mode != 2) {
@@ -636,7 +687,10 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
           f32x4 d0[2], d1[2];
 #pragma unroll
           for (int t = 0; t < 2; t++) d0[t] = d1[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-          const int nb = (lane & 3) * SM::dmf_ps + 8 * (lane >> 4);
+          // DMF 2: the operand and result addresses from an opaque copy of the lane number -- formed here, in every sweep, instead
+          // of living across the row loop in registers that the 16-quad kernel does not have (als_cgp_kernel's QUAD does the same)
+          const int ln = opaque_lane<DMF == 2>(lane);
+          const int nb = (ln & 3) * SM::dmf_ps + 8 * (ln >> 4);
 #pragma unroll
           for (int ks = 0; ks < 4; ks++) {
             const f16x8 bh = *reinterpret_cast<const f16x8*>(sPh + nb + 32 * ks);
@@ -648,19 +702,19 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
                 ah = gAh[t][ks];
                 al = gAl[t][ks];
               } else {
-                ah = *reinterpret_cast<const f16x8*>(sGf + ((t * 4 + ks) * 2 + 0) * 1024 + lane * 16);
-                al = *reinterpret_cast<const f16x8*>(sGf + ((t * 4 + ks) * 2 + 1) * 1024 + lane * 16);
+                ah = *reinterpret_cast<const f16x8*>(sGf + ((t * 4 + ks) * 2 + 0) * 1024 + ln * 16);
+                al = *reinterpret_cast<const f16x8*>(sGf + ((t * 4 + ks) * 2 + 1) * 1024 + ln * 16);
               }
               d0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, d0[t], 0, 0, 0);
               d1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, d1[t], 0, 0, 0);
               d1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, d1[t], 0, 0, 0);
             }
           }
-          if ((lane & 15) < 4) {   // D: column = lane & 15, rows 4 (lane >> 4) + 0..3 of the tile
+          if ((ln & 15) < 4) {   // D: column = lane & 15, rows 4 (lane >> 4) + 0..3 of the tile
 #pragma unroll
             for (int t = 0; t < 2; t++) {
               const f32x4 d = (d0[t] + d1[t]) * ginv;
-              *reinterpret_cast<f32x4*>(sOut + (lane & 15) * SM::dmf_os + 32 * wv + 16 * t + 4 * (lane >> 4)) = d;
+              *reinterpret_cast<f32x4*>(sOut + (ln & 15) * SM::dmf_os + 32 * wv + 16 * t + 4 * (ln >> 4)) = d;
             }
           }
         }
@@ -721,7 +775,13 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
             }
           }
         };
-        if constexpr (GVFIRST) dense_part();
+        if constexpr (GVFIRST) {
+          dense_part();
+          if (mode == 3) {   // (dotted at once: no vector lives across the quad pass)
+#pragma unroll
+            for (int rr = 0; rr < RPN; rr++) dl = fmaf(acc[rr], v[rr], dl);
+          }
+        }
         if (resident) {
           if (mode != 2 || !TSAVE) {
             quad_pass(v, mode, acc, lacc, nullptr);
@@ -782,9 +842,19 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
                       tscr ? tscr + (size_t)sidx * a.stream_nnz + (size_t)pre + (size_t)ch * CAP : nullptr);
           }
         }
-        if constexpr (!GVFIRST) dense_part();
+        if constexpr (!GVFIRST) {
+          dense_part();
+          if (mode == 3) {
+#pragma unroll
+            for (int rr = 0; rr < RPN; rr++) dl = fmaf(acc[rr], v[rr], dl);
+          }
+        }
         if constexpr (!DMF) {
-          if (mode != 2) {
+          if (mode == 3) {
+            // the groups split the rows of G and the quads: each adds the 16-lane sum of its share of v . G v to its quads' sum
+            if constexpr (IMPLICIT) lacc += row16_sum(dl);
+            lacc = groups_sum(lacc);
+          } else if (mode != 2) {
             if constexpr (GRS) {
               if constexpr (WPR == 1) groups_all_reduce8(acc);   // (teams: scattered where the partials are published)
             } else {
@@ -805,9 +875,14 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
           for (int b = 0; b < NV; b++) {
             const f32x4 o = *reinterpret_cast<const f32x4*>(sOut + wv * SM::dmf_os + b * 16 * VW + i * VW);
 #pragma unroll
-            for (int c = 0; c < VW; c++) acc[b * VW + c] = fmaf(f, o[c], acc[b * VW + c]);
+            for (int c = 0; c < VW; c++) {
+              if (mode == 3) dl = fmaf(o[c], v[b * VW + c], dl);
+              else acc[b * VW + c] = fmaf(f, o[c], acc[b * VW + c]);
+            }
           }
-          if constexpr (GRS) {
+          if (mode == 3) {   // v . G v in place (every group holds the whole of it: group 0's counts)
+            lacc = groups_sum(fmaf(f, row16_sum(dl), lacc));
+          } else if constexpr (GRS) {
             groups_all_reduce8(acc);
           } else {
 #pragma unroll
@@ -819,7 +894,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
       }
       if constexpr (WPR > 1) {
         float* red = sRed + buf * WAVES * KP;
-        if (mode != 2) {
+        if (mode < 2) {   // (modes 2 and 3: one float per wave)
           if constexpr (GRS) {
             // the groups' partial sums meet on the way to LDS: row g of r0 / r1 = the wave's total of register g / 4 + g, i.e.
             // of the vector elements 4 i + g and 64 + 4 i + g -- every lane publishes two floats (a permutation of the 128)
@@ -841,7 +916,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
           sRedL[buf * WAVES + wv] = lacc;
         }
         __syncthreads();
-        if (mode != 2) {
+        if (mode < 2) {
 #pragma unroll
           for (int rr = 0; rr < RPN; rr++) acc[rr] = 0.f;
 #pragma unroll
@@ -865,7 +940,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         // otherwise the scheduler hoists the next sweep's LDS/global loads and the allocator spills
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (mode != 2) {
+      if (mode < 2) {
 #pragma unroll
         for (int rr = 0; rr < RPN; rr++) out[rr] = acc[rr];
         if constexpr (GB) {
@@ -885,6 +960,14 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
           for (int rr = 0; rr < RPN; rr++) out[rr] = fmaf(mode == 0 ? -lam_use : lam_use, v[rr], out[rr]);
         }
       } else {
+        if constexpr (!IMPLICIT) {
+          if (mode == 3) {   // + lambda v . v (the groups are replicas: the 16 lanes of a group cover the vector)
+            float vv = 0.f;
+#pragma unroll
+            for (int rr = 0; rr < RPN; rr++) vv = fmaf(v[rr], v[rr], vv);
+            lacc = fmaf(lam_use, row16_sum(vv), lacc);
+          }
+        }
         loss_out = lacc;
       }
     };
@@ -944,44 +1027,64 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
     for (int rr = 0; rr < RPN; rr++) p[rr] = r[rr];
     float rsold = dot16(r, r);
     bool conv = false;
+    // what a step's alpha does to the kept dots and to x: alph[step] for the streamed rows' loss, t_acc += alpha * t_cur
+    // (x += alpha p  =>  X_nnz^T x += alpha X_nnz^T p), x += alpha p (CVLDS: in LDS)
+    // (a macro, not a lambda: see RSP_ADVANCE_META)
+#define RSP_STEP_X(alpha, step)                                                                   \
+    do {                                                                                          \
+      _Pragma("unroll") for (int s2 = 0; s2 < kMaxSavedSweeps; s2++)                              \
+        if (s2 == (step)) alph[s2] = (alpha);                                                     \
+      if constexpr (TSAVE) {                                                                      \
+        wave_sync();                                                                              \
+        const int ln = opaque_lane<WIDEQ>(lane);                                                  \
+        _Pragma("unroll") for (int s2 = 0; s2 < NSL; s2++) {                                      \
+          const int sl = NSL == 1 ? (lane & (CAP - 1)) : ln + 64 * s2;                            \
+          if (CAP % 64 == 0 || sl < CAP) tacc[sl] = fmaf((alpha), tcur[sl], tacc[sl]);            \
+        }                                                                                         \
+        wave_sync();                                                                              \
+      }                                                                                           \
+      if constexpr (CVLDS) {                                                                      \
+        if (g == 0) {                                                                             \
+          _Pragma("unroll") for (int b = 0; b < NV; b++) {                                        \
+            piece_t pc = *x_piece(b);                                                             \
+            float* pf = reinterpret_cast<float*>(&pc);                                            \
+            _Pragma("unroll") for (int c = 0; c < VW; c++) pf[c] = fmaf((alpha), p[b * VW + c], pf[c]); \
+            *x_piece(b) = pc;                                                                     \
+          }                                                                                       \
+        }                                                                                         \
+      } else {                                                                                    \
+        _Pragma("unroll") for (int rr = 0; rr < RPN; rr++) x[rr] = fmaf((alpha), p[rr], x[rr]);   \
+      }                                                                                           \
+    } while (0)
+    // The last step from its dots: p' A p = p' G p + sum_j (c_j - 1) (x_j . p)^2 needs the dots and the dense product, not the
+    // vector A p, and nothing reads the residual behind it -- the loss comes from t_acc, the row from x: no r, rsnew, beta or p.
+    // A row that has converged skips it as it skips the others (teams and the shared dense product: it keeps in step).
+#define RSP_LAST_STEP()                                                                           \
+    do {                                                                                          \
+      float pap = 0.f;                                                                            \
+      sweep(p, 3, ap, pap, live && !conv, a.cg_steps);                                            \
+      if (!conv) {                                                                                \
+        const float alpha = (float)((double)rsold / (double)pap);                                 \
+        RSP_STEP_X(alpha, a.cg_steps - 1);                                                        \
+      }                                                                                           \
+    } while (0)
+    // Which form this instantiation's last step takes, and where it stands: last_step_form above the kernel
+    constexpr int LAST = last_step_form(KP, CAPQ, WAVES, WPR, STREAM, IMPLICIT, DMF, GB, KFULL);
     for (int itc = 0; itc < a.cg_steps; ++itc) {
       if (WPR == 1 && !DMF && conv) break;
+      if (LAST != kLastFull && itc + 1 == a.cg_steps) {
+        if constexpr (LAST == kLastDotsInLoop) RSP_LAST_STEP();
+        break;
+      }
       sweep(p, 1, ap, dummy, live && !conv, itc + 1);
       if (!conv) {
         const float pap = dot16(p, ap);
         // rsold / alpha / beta as the reference holds them: double scalars fed by T-valued dot products
         // (wrmf_implicit.hpp:18-27), rounded to float where they meet the vectors
         const float alpha = (float)((double)rsold / (double)pap);
+        RSP_STEP_X(alpha, itc);
 #pragma unroll
-        for (int s2 = 0; s2 < kMaxSavedSweeps; s2++)
-          if (s2 == itc) alph[s2] = alpha;
-        if constexpr (TSAVE) {  // t_acc += alpha * t_cur  (x += alpha p  =>  X_nnz^T x += alpha X_nnz^T p)
-          wave_sync();
-          const int ln = opaque_lane<WIDEQ>(lane);
-#pragma unroll
-          for (int s2 = 0; s2 < NSL; s2++) {
-            const int sl = NSL == 1 ? (lane & (CAP - 1)) : ln + 64 * s2;
-            if (CAP % 64 == 0 || sl < CAP) tacc[sl] = fmaf(alpha, tcur[sl], tacc[sl]);
-          }
-          wave_sync();
-        }
-        if constexpr (CVLDS) {
-          if (g == 0) {
-#pragma unroll
-            for (int b = 0; b < NV; b++) {
-              piece_t pc = *x_piece(b);
-              float* pf = reinterpret_cast<float*>(&pc);
-#pragma unroll
-              for (int c = 0; c < VW; c++) pf[c] = fmaf(alpha, p[b * VW + c], pf[c]);
-              *x_piece(b) = pc;
-            }
-          }
-        }
-#pragma unroll
-        for (int rr = 0; rr < RPN; rr++) {
-          if constexpr (!CVLDS) x[rr] = fmaf(alpha, p[rr], x[rr]);
-          r[rr] = fmaf(-alpha, ap[rr], r[rr]);
-        }
+        for (int rr = 0; rr < RPN; rr++) r[rr] = fmaf(-alpha, ap[rr], r[rr]);
         const float rsnew = dot16(r, r);
         if (rsnew < kCgTol) {
           conv = true;
@@ -993,6 +1096,11 @@ __global__ __launch_bounds__(WAVES * 64, 2) void als_cgq_kernel(AlsArgs a, const
         }
       }
     }
+    if constexpr (LAST == kLastDotsBehind) {
+      if (a.cg_steps > 0 && !(WPR == 1 && !DMF && conv)) RSP_LAST_STEP();
+    }
+#undef RSP_LAST_STEP
+#undef RSP_STEP_X
     if constexpr (CVLDS) {
       wave_sync();
 #pragma unroll
