@@ -1042,6 +1042,50 @@ int rsparse_hip_ease_held_out_ranks(const int32_t* x_p, const int32_t* x_j, int 
                                     const int32_t* exclude, int n_exclude, int32_t* above, int32_t* tied, int32_t* n_adm);
 
 /* ------------------------------------------------------------------------------------------------
+ * SLIM (Ning and Karypis 2011): the non-negative elastic-net item-item weights, by coordinate descent on the Gram rows
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The definition (rsparse_amd/slim.py states it in numpy).  G is the Gram matrix of the canonical binary pattern at lambda = 0,
+ * as rsparse_hip_item_gram_device writes it: c_ij off the diagonal, n_i on it, exact integers in doubles.  Column j minimises,
+ * over w >= 0 with w_j = 0,
+ *     1/2 |h_j - H w|^2 + l2/2 |w|^2 + l1 |w|_1
+ * (sklearn's ElasticNet: l1 = n_users alpha l1_ratio, l2 = n_users alpha (1 - l1_ratio)).  The support S_j is the set of i != j
+ * with c_ij > 0, ascending; no other coordinate is visited (with G >= 0 and w >= 0 its update is max(0, <= 0 - l1) = 0: the
+ * restriction is the problem itself).  State: w and r, doubles over S_j, from +0.0; r_s is (G w)_{S[s]}, kept by the updates.
+ * One sweep visits t = 0 .. m - 1 in order, every operation a separately rounded double operation, nothing fused:
+ *     i = S[t];  d = G[i, i];  c = G[j, i]
+ *     u  = (c - (r[t] - d * w[t])) - l1
+ *     wn = u / (d + l2)  if u > 0  else +0.0
+ *     delta = wn - w[t]
+ *     if delta != 0:  r[s] = r[s] + (delta * G[i, S[s]]) for every s;  w[t] = wn
+ *     dmax = max(dmax, |delta|);  wmax = max(wmax, |wn|)
+ * After a sweep: stop if wmax == 0 or dmax <= tol * wmax, otherwise go on, up to max_iter sweeps; an empty support takes 0 sweeps.
+ * The column's weights are W[S[t], j] = w[t], rounded once into W's type; its other cells are +0.0.  W is scored as the B of EASE.
+ *
+ * The kernel (wrmf_slim.hip) gives a workgroup one column and keeps 36 bytes per support entry: in LDS for a support of up to
+ * RSPARSE_HIP_SLIM_LDS_SUPPORT entries (72 KiB, two workgroups per CU), in a slice of a grow-only workspace beyond.  The sequence
+ * above is kept exactly; its chain is shortened by evaluating 64 consecutive coordinates at once and applying the first that
+ * changes.  No atomics: a repeated call returns the same bits. */
+#define RSPARSE_HIP_SLIM_LDS_SUPPORT 2048
+
+/* Columns d_cols[0 .. n_cols) (any order, repeats allowed; pass long supports first) of the n_items x n_items row-major d_G
+ * (ld_G doubles per row) into the row-major d_W: d_W[i ld_W + j] for every i of S_j, zeros included, as float, or as double with
+ * w_is_double; NO other cell is written, so the caller hands in a zeroed W.  d_W, ld_W: the rules of d_B of
+ * rsparse_hip_ease_recommend_device.  d_sweeps[c]: the sweeps column d_cols[c] took.  Reads the support sizes back (waits for
+ * `stream` once); a column outside [0, n_items) is found there -> ERR_INVALID, with nothing written.
+ * NULL pointer, negative size, l1 / l2 / tol negative or not finite, max_iter < 1, ld_G < n_items, a bad ld_W or alignment
+ * -> ERR_INVALID; n_items > RSPARSE_HIP_EASE_MAX_ITEMS -> ERR_UNSUPPORTED; all before a device is touched.  n_cols == 0 -> OK. */
+int rsparse_hip_slim_columns_device(const double* d_G, size_t ld_G, int n_items, const int32_t* d_cols, int n_cols, double l1,
+                                    double l2, int max_iter, double tol, void* d_W, size_t ld_W, int w_is_double, int32_t* d_sweeps,
+                                    void* stream);
+
+/* host-array form: the Gram matrix of the pattern (p / j: the dgRMatrix slots of the users x items matrix, with the checks of
+ * rsparse_hip_cooc_neighbors), every column's fit, and the download.  W: n_items x n_items doubles, COLUMN-major (an R matrix:
+ * W[j n_items + i] is the weight of item i in the column of item j); sweeps: n_items, by item. */
+int rsparse_hip_slim_fit(const int32_t* p, const int32_t* j, int n_users, int n_items, double l1, double l2, int max_iter, double tol,
+                         double* W, int32_t* sweeps);
+
+/* ------------------------------------------------------------------------------------------------
  * why this item: per-item contributions to a score (Hu, Koren and Volinsky, section 5; `explain` of the `implicit` library)
  * ---------------------------------------------------------------------------------------------- */
 

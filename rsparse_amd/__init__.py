@@ -16,6 +16,8 @@ Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit
                               with weighting= on quantised values: BM25 / TF-IDF cosine, dot, asymmetric cosine, P3alpha / RP3beta
   rsparse_amd.EASE            the closed-form item-item model of Steck 2019: Gram rows and top-k lists under a dense items x items
                               weight matrix on the device, equal to the numpy definition
+  rsparse_amd.SLIM            the sparse linear method of Ning and Karypis 2011: a non-negative elastic net per item column by
+                              coordinate descent on the device, equal to the numpy definition; EASE's inference surface
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
   rsparse_amd.engine          device-resident, row-sharded driver (one process per GPU)
   rsparse_amd.synth           synthetic interaction matrices for the BASELINE configs
@@ -51,6 +53,9 @@ def __getattr__(name):
                 "ease_score_pairs_reference", "ease_candidates_reference", "ease_ranks_reference"):
         from . import ease
         return getattr(ease, name)
+    if name in ("SLIM", "slim_columns_reference", "slim_weights_reference"):
+        from . import slim
+        return getattr(slim, name)
     if name == "metrics":
         import importlib
         return importlib.import_module(".metrics", __name__)

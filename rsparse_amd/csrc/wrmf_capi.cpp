@@ -1565,6 +1565,54 @@ int rsparse_hip_ease_recommend_device(const int32_t* d_xp, const int32_t* d_xj, 
 }
 
 namespace {
+// SLIM's own grow-only scratch, per host thread and per device like the workspace above, and apart from it: no other entry sees it
+struct SlimScratch {
+  GrowBufBase* all = nullptr;
+  GrowBuf<int32_t> m{all};    // the support size of every column of a call
+  GrowBuf<char> state{all};   // the state slices of the columns beyond RSPARSE_HIP_SLIM_LDS_SUPPORT
+  int device = -1;
+  int ensure_device() {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev != device) {
+      GrowBufBase::release_all(all);
+      device = dev;
+    }
+    return RSPARSE_HIP_OK;
+  }
+};
+thread_local SlimScratch g_slim;
+}  // namespace
+
+// SLIM (wrmf_slim.hip); the host form rsparse_hip_slim_fit: wrmf_capi_host.cpp
+int rsparse_hip_slim_columns_device(const double* d_G, size_t ld_G, int n_items, const int32_t* d_cols, int n_cols, double l1,
+                                    double l2, int max_iter, double tol, void* d_W, size_t ld_W, int w_is_double, int32_t* d_sweeps,
+                                    void* stream) {
+  int rc = slim_args(!d_G || !d_cols || !d_W || !d_sweeps, n_items, n_cols, l1, l2, max_iter, tol, ld_G, d_W, ld_W, w_is_double ? 2 : 4);
+  if (rc || n_cols == 0) return rc;
+  if (n_items == 0) return fail(RSPARSE_HIP_ERR_INVALID, "a column outside [0, n_items)");
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = g_slim.ensure_device())) return rc;
+  HIP_TRY(g_slim.m.ensure((size_t)n_cols));
+  launch_slim_support(d_G, ld_G, n_items, d_cols, n_cols, g_slim.m, s);
+  std::vector<int32_t> m((size_t)n_cols);
+  HIP_TRY(hipMemcpyAsync(m.data(), g_slim.m, m.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  int n_lds = 0, n_global = 0, max_support = 0;
+  for (int32_t v : m) {
+    if (v < 0) return fail(RSPARSE_HIP_ERR_INVALID, "a column outside [0, n_items)");
+    (v <= RSPARSE_HIP_SLIM_LDS_SUPPORT ? n_lds : n_global)++;
+    max_support = std::max(max_support, (int)v);
+  }
+  int slices = 0, stride = 0;
+  if (n_global) HIP_TRY(g_slim.state.ensure(slim_state_bytes(n_global, max_support, slices, stride)));
+  hipError_t e = launch_slim_columns(d_G, ld_G, n_items, d_cols, g_slim.m, n_cols, n_lds, slices, stride, l1, l2, max_iter, tol, d_W,
+                                     ld_W, w_is_double != 0, d_sweeps, g_slim.state, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_slim_columns");
+  return RSPARSE_HIP_OK;
+}
+
+namespace {
 // what the evaluation entries do between their argument checks and their launches: x's row pointers on the host, the workspace
 static int knn_rows_begin(const int32_t* d_xp, int n_rows, int n_items, int64_t ws_rows, std::vector<int32_t>& h_xp, int64_t& rows,
                           unsigned long long*& ws, hipStream_t s) {

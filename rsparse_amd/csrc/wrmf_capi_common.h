@@ -428,6 +428,23 @@ inline int ease_recommend_args(bool missing, int n_rows, int n_items, const void
   return RSPARSE_HIP_OK;
 }
 
+// SLIM: what both entries refuse.  W_elems: as B_elems above (0 = W is a host array without a leading dimension)
+inline int slim_args(bool missing, int n_items, int n_cols, double l1, double l2, int max_iter, double tol, size_t ld_G, const void* W,
+                     size_t ld_W, size_t W_elems) {
+  const auto ok = [](double v) { return v >= 0.0 && v <= 1.7976931348623157e308; };   // (NaN fails both)
+  if (missing) return fail(RSPARSE_HIP_ERR_INVALID, "G or the pattern, the columns, W or sweeps is NULL");
+  if (n_items < 0 || n_cols < 0) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_items < 0, n_users < 0 or n_cols < 0)");
+  if (!ok(l1) || !ok(l2)) return fail(RSPARSE_HIP_ERR_INVALID, "l1 or l2 is negative or not finite");
+  if (!ok(tol)) return fail(RSPARSE_HIP_ERR_INVALID, "tol is negative or not finite");
+  if (max_iter < 1) return fail(RSPARSE_HIP_ERR_INVALID, "max_iter < 1");
+  if (ld_G < (size_t)n_items) return fail(RSPARSE_HIP_ERR_INVALID, "ld_G < n_items");
+  if (W_elems && (ld_W < (size_t)n_items || ld_W % W_elems != 0 || (uintptr_t)W % 16 != 0))
+    return fail(RSPARSE_HIP_ERR_INVALID, "ld_W < n_items, or ld_W or W is not a multiple of 16 bytes");
+  if (n_items > RSPARSE_HIP_EASE_MAX_ITEMS)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "n_items > 32768 (RSPARSE_HIP_EASE_MAX_ITEMS): an items x items matrix of doubles would pass 8 GiB");
+  return RSPARSE_HIP_OK;
+}
+
 // rsparse_hip_score_pairs_device / _f64_device (kernels: wrmf_score.hip).  Handed in:
 //   int workspace(size_t n, double*& buf)    makes sure of n doubles of the side's grow-only workspace
 // which is only asked for the sums without the scores: the scores then live there, and their count, p[n_rows], has to be

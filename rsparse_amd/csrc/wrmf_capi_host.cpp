@@ -1051,6 +1051,50 @@ int rsparse_hip_item_gram(const int32_t* p, const int32_t* j, int n_users, int n
   return RSPARSE_HIP_OK;
 }
 
+int rsparse_hip_slim_fit(const int32_t* p, const int32_t* j, int n_users, int n_items, double l1, double l2, int max_iter, double tol,
+                         double* W, int32_t* sweeps) {
+  int rc = slim_args(!p || !W || !sweeps, n_items, n_users, l1, l2, max_iter, tol, (size_t)std::max(n_items, 0), W, 0, 0);
+  if (rc) return rc;
+  if ((rc = check_csr(p, n_users, "p"))) return rc;
+  const size_t nnz = (size_t)p[n_users];
+  if (nnz && !j) return fail(RSPARSE_HIP_ERR_INVALID, "j is NULL");
+  if ((rc = check_columns(p, j, n_users, n_items, "j"))) return rc;
+  if (n_items == 0) return RSPARSE_HIP_OK;
+  std::vector<int32_t> ip, iu;
+  item_major(p, j, n_users, n_items, ip, iu, nullptr, nullptr);
+  // the popular items first: their supports are the long ones
+  std::vector<int32_t> cols((size_t)n_items);
+  for (int i = 0; i < n_items; i++) cols[(size_t)i] = i;
+  std::stable_sort(cols.begin(), cols.end(), [&](int32_t a, int32_t b) { return ip[a + 1] - ip[a] > ip[b + 1] - ip[b]; });
+  const size_t n = (size_t)n_items, ld = (n * sizeof(double) + 255) / 256 * 256 / sizeof(double);
+  DevBuf dIP, dIU, dUP, dUJ, dG, dC, dW, dS;
+  HIP_TRY(upload_host(dIP, ip.data(), ip.size()));
+  HIP_TRY(upload_host(dIU, iu.data(), nnz));
+  HIP_TRY(upload_host(dUP, p, (size_t)n_users + 1));
+  HIP_TRY(upload_host(dUJ, j, nnz));
+  HIP_TRY(upload_host(dC, cols.data(), n));
+  HIP_TRY(dG.alloc(n * n * sizeof(double)));
+  HIP_TRY(dW.alloc(n * ld * sizeof(double)));
+  HIP_TRY(dS.alloc(n * sizeof(int32_t)));
+  HIP_TRY(hipMemsetAsync(dW.p, 0, n * ld * sizeof(double), nullptr));
+  rc = rsparse_hip_item_gram_device(dIP.as<int32_t>(), dIU.as<int32_t>(), dUP.as<int32_t>(), dUJ.as<int32_t>(), n_users, n_items, 0,
+                                    n_items, 0.0, dG.as<double>(), n, 0, nullptr);
+  if (rc) return rc;
+  rc = rsparse_hip_slim_columns_device(dG.as<double>(), n, n_items, dC.as<int32_t>(), n_items, l1, l2, max_iter, tol, dW.p, ld, 1,
+                                       dS.as<int32_t>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  std::vector<double> rows(n * ld);
+  std::vector<int32_t> sw(n);
+  HIP_TRY(download(rows.data(), dW, n * ld));
+  HIP_TRY(download(sw.data(), dS, n));
+  for (size_t c = 0; c < n; c++) {
+    sweeps[cols[c]] = sw[c];
+    for (size_t i = 0; i < n; i++) W[c * n + i] = rows[i * ld + c];
+  }
+  return RSPARSE_HIP_OK;
+}
+
 extern "C++" {
 namespace {
 // B (n x n column-major, an R matrix) as n row-major rows of ld elements, zeros beyond n; a non-finite entry -> false

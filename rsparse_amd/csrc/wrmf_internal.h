@@ -487,6 +487,18 @@ hipError_t launch_ease_held_out_ranks(const int32_t* xp, const int32_t* xj, int 
                                       int n_excl, int64_t rows, unsigned long long* ws, int32_t* above, int32_t* tied, int32_t* n_adm,
                                       hipStream_t s);
 
+// SLIM (wrmf_slim.hip; defined in rsparse_wrmf_hip.h).  support: msize[c] = the support size of column cols[c] of G, -1 for a
+// column outside the items.  state_bytes: the workspace of n_global columns beyond RSPARSE_HIP_SLIM_LDS_SUPPORT whose largest
+// support is max_support -> bytes, with the slices (at most kSlimSlices workgroups, each striding over the columns) and the
+// entries of one.  columns: the fits; n_lds: how many columns are within the LDS bound (0 = that launch is left out), slices = 0
+// leaves the other out; ws: state_bytes bytes, 8-byte aligned.
+constexpr int kSlimSlices = 512;
+void launch_slim_support(const double* G, size_t ld_G, int n_items, const int32_t* cols, int n_cols, int32_t* msize, hipStream_t s);
+size_t slim_state_bytes(int n_global, int max_support, int& slices, int& stride);
+hipError_t launch_slim_columns(const double* G, size_t ld_G, int n_items, const int32_t* cols, const int32_t* msize, int n_cols,
+                               int n_lds, int slices, int stride, double l1, double l2, int max_iter, double tol, void* W,
+                               size_t ld_W, bool w_is_double, int32_t* sweeps, char* ws, hipStream_t s);
+
 // top-k within per-user candidate lists (wrmf_candidates.hip), T = float or double, 1 <= topk <= kTopLargeMax: for every row of
 // the CSR pattern (cand_p: n_users + 1 slots, absolute positions into cand_j; p0 = cand_p[0], nnz = cand_p[n_users] - p0, read by
 // the caller; columns ascending and unique within a row) the topk best admissible candidates by launch_score_pairs' scores

@@ -947,6 +947,27 @@ class HipBackend:
                                                                    int(ws_rows), some(above), some(tied), some(n_adm), self._stream()))
         return above, tied, n_adm
 
+    def slim_columns(self, G, cols, l1, l2, max_iter, tol, W):
+        """the SLIM columns `cols` (int32 on the device: any order, repeats allowed, long supports first) of the Gram matrix G
+        ((n_items, >= n_items) float64 on the device, lambda = 0) by coordinate descent (wrmf_slim.hip;
+        rsparse_amd.slim.slim_columns_reference is the definition), written into W: an (n_items, ld) float32 or float64 tensor
+        on the device with the layout `ease_recommend` takes, ZEROED by the caller -- only the support cells of the columns are
+        written.  -> the sweeps of every element of cols, int32 on the device."""
+        n_items = int(W.shape[0])
+        assert G.dtype == torch.float64 and G.is_cuda and G.dim() == 2 and G.shape[0] == n_items and G.shape[1] >= n_items
+        assert W.dtype in (torch.float32, torch.float64) and W.is_cuda and W.dim() == 2 and W.shape[1] >= n_items
+        assert (G.shape[1] <= 1 or G.stride(1) == 1) and (W.shape[1] <= 1 or W.stride(1) == 1) and cols.dtype == torch.int32
+        ld_G = int(G.stride(0)) if n_items > 1 else int(G.shape[1])
+        ld_W = int(W.stride(0)) if n_items > 1 else int(W.shape[1])
+        sweeps = torch.zeros(int(cols.numel()), dtype=torch.int32, device=self.device)
+        if not cols.numel():
+            return sweeps
+        some = lambda t: t.data_ptr() if t.numel() else sweeps.data_ptr()   # (an empty tensor has no address to pass)
+        _lib.check(self.lib.rsparse_hip_slim_columns_device(some(G), ld_G, n_items, some(cols), int(cols.numel()), float(l1), float(l2),
+                                                            int(max_iter), float(tol), some(W), ld_W, int(W.dtype == torch.float64),
+                                                            some(sweeps), self._stream()))
+        return sweeps
+
     def _knn_rows(self, xp, xj, neighbors, q, xv):
         """the operands the ItemKNN evaluation entries share with `knn_recommend`, as the C ABI takes them: -> (the leading
         arguments, `some`: the address of a tensor, or of xp for an empty one; the tensors that must outlive the call)"""
