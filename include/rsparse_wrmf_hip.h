@@ -1086,6 +1086,86 @@ int rsparse_hip_slim_fit(const int32_t* p, const int32_t* j, int n_users, int n_
                          double* W, int32_t* sweeps);
 
 /* ------------------------------------------------------------------------------------------------
+ * BPR (Rendle et al. 2009): matrix factorisation on the pairwise ranking loss, by deterministic mini-batch SGD
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The definition (rsparse_amd/bpr.py states it in numpy: bpr_triples, bpr_step_reference, bpr_fit_reference).  The input is a
+ * canonical CSR pattern (p from 0, columns ascending and unique per row; nnz = p[n_rows] is handed in, nothing is read back).
+ *
+ * Triples: stream 6 of the Philox4x32-10 of the generators above.  An epoch has one triple per stored entry.  Slot s of the CSR
+ * belongs to row u of L entries at position q = s - p[u]; counter (q, g, 6, epoch + 2^31 mode), key (lo32(seed), hi32(seed)) ->
+ * o0..o3; mode 0 (the fit): g = row0 + u; mode 1 (the fold-in): g = row0 for EVERY row, so that a folded-in row depends on the
+ * row alone (all rows of a fold-in epoch then share the words of a position q and with them its three negative candidates:
+ * harmless with the items frozen, where no row sees another's update).  Positive i = j[p[u] + ((o0 L) >> 32)]; negative = the first of (o1 n_items) >> 32, (o2 n_items) >> 32,
+ * (o3 n_items) >> 32 that is not in the row; all three in the row: the triple is VOID (-1) and takes no part in anything.
+ *
+ * Steps: step t of n_steps holds the slots s = t, t + n_steps, ... in ascending order, numbered k = 0, 1, ...
+ *
+ * One step, from the snapshot (U, V) at its start; every operation a separately rounded double operation, the factors widened:
+ *     dot(a, b)  16 partial sums, partial l = the products of the coordinates l, l + 16, ... added in ascending order from +0.0;
+ *                then v[0:8] + v[8:16], v[0:4] + v[4:8], v[0:2] + v[2:4], v[0] + v[1]
+ *     d_k = dot(U[u], V[i] - V[j])
+ *     E(d): d clamped to [-40, 40]; kk = rint(d * 1.4426950408889634);
+ *           r = (d - kk * 6.93147180369123816490e-01) - kk * 1.90821492927058770002e-10;
+ *           the polynomial sum_{n <= 13} r^n / n! in Horner form with the coefficients 1.0 / n!, then ldexp(., kk)
+ *     z_k = 1 / (1 + E(d_k))
+ *     user u receives z_k (V[i] - V[j]), item i receives z_k U[u], item j receives (-z_k) U[u]
+ *     a destination sums its contributions in ascending k, the positive role before the negative one within a k; the list is cut
+ *     into chunks of RSPARSE_HIP_BPR_CHUNK consecutive contributions, a chunk is summed sequentially from +0.0, the chunk sums
+ *     are added sequentially to a total that starts at +0.0
+ *     a destination with c >= 1 contributions: g = total - (lambda c) row;  a' = a + dot(g, g) / rank;
+ *     row' = row + (learning_rate g) / sqrt(a') unless a' == 0, rounded once into the factors' type; the others keep their bits
+ * a: one double per user and per item (Adagrad's state), part of the model.  counts: (n_valid, n_correct) per epoch -- the triples
+ * that are not void, and those of them with d_k > 0.  update_items = 0 reads V only: d_aV is neither read nor written then (it
+ * must still be a valid pointer).
+ *
+ * The kernels (wrmf_bpr.hip): a thread per triple samples; a 16-lane group per triple scores; a group per run of equal users
+ * sums into a staging row; the item side is grouped by a stable radix sort of (item, 2k + role) and summed by a group per chunk
+ * and a group per item.  No float atomics: a repeated call returns the same bits. */
+#define RSPARSE_HIP_BPR_CHUNK 64
+
+/* Common refusals, all before a device is touched: a NULL pointer, n_rows / n_items / nnz negative, nnz >= 2^31,
+ * row0 + n_rows > 2^32, mode not 0 / 1, an epoch outside [0, 2^31), n_steps < 1 or batch < 1, step outside [0, n_steps), rank < 1,
+ * learning_rate / lambda negative or not finite -> ERR_INVALID; rank > RSPARSE_HIP_MAX_RANK (_f64: RSPARSE_HIP_MAX_RANK_F64)
+ * -> ERR_UNSUPPORTED, and so is a step of 2^30 or more triples with update_items (the item side numbers a step's 2 cnt
+ * contributions in 32 bits): take a smaller batch.  n_rows == 0 -> OK with no device.  U: n_rows x rank, V: n_items x rank, row-major without padding. */
+
+/* the triples of one step: d_u (the LOCAL row), d_i, d_neg (-1: void), ceil((nnz - step) / n_steps) entries each.  Integers only. */
+int rsparse_hip_bpr_triples_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                   uint64_t seed, int mode, int epoch, int step, int n_steps, int32_t* d_u, int32_t* d_i,
+                                   int32_t* d_neg, void* stream);
+
+/* one step, in place; d_counts[0] += n_valid, d_counts[1] += n_correct.  Waits for `stream` before it returns (its scratch: with
+ * cnt the slots of the step, min(n_rows, cnt) staging rows of the factors' type, 28 bytes per slot, and with update_items 16 more
+ * per slot plus the sort's and at most 4 cnt / 64 + 1 chunk sums of rank doubles). */
+int rsparse_hip_bpr_step_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                uint64_t seed, int mode, int epoch, int step, int n_steps, int rank, double learning_rate,
+                                double lambda, int update_items, float* d_U, float* d_V, double* d_aU, double* d_aV,
+                                int64_t* d_counts, void* stream);
+int rsparse_hip_bpr_step_f64_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                    uint64_t seed, int mode, int epoch, int step, int n_steps, int rank, double learning_rate,
+                                    double lambda, int update_items, double* d_U, double* d_V, double* d_aU, double* d_aV,
+                                    int64_t* d_counts, void* stream);
+
+/* the epochs [epoch0, epoch0 + n_epochs), every step of each, on one stream without a host synchronisation between the steps;
+ * n_steps = ceil(nnz / batch) in mode 0 and 1 in mode 1.  d_counts: 2 n_epochs slots, zeroed by the call: (n_valid, n_correct) of
+ * every epoch. */
+int rsparse_hip_bpr_epochs_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                  uint64_t seed, int mode, int epoch0, int n_epochs, int batch, int rank, double learning_rate,
+                                  double lambda, int update_items, float* d_U, float* d_V, double* d_aU, double* d_aV,
+                                  int64_t* d_counts, void* stream);
+int rsparse_hip_bpr_epochs_f64_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                      uint64_t seed, int mode, int epoch0, int n_epochs, int batch, int rank, double learning_rate,
+                                      double lambda, int update_items, double* d_U, double* d_V, double* d_aU, double* d_aV,
+                                      int64_t* d_counts, void* stream);
+
+/* host-array form: a fit in double from the initial factors of rsparse_hip_init_factors_f64_device (streams 0 and 1 of `seed`,
+ * scale 0.01) with a = 0; p / j: the dgRMatrix slots of the users x items pattern, with the checks of rsparse_hip_cooc_neighbors.
+ * U: n_users x rank and V: n_items x rank, ROW-major; aU, aV: their Adagrad states; counts: 2 n_epochs. */
+int rsparse_hip_bpr_fit(const int32_t* p, const int32_t* j, int n_users, int n_items, uint64_t seed, int n_epochs, int batch, int rank,
+                        double learning_rate, double lambda, double* U, double* V, double* aU, double* aV, int64_t* counts);
+
+/* ------------------------------------------------------------------------------------------------
  * why this item: per-item contributions to a score (Hu, Koren and Volinsky, section 5; `explain` of the `implicit` library)
  * ---------------------------------------------------------------------------------------------- */
 

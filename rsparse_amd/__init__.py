@@ -18,6 +18,8 @@ Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit
                               weight matrix on the device, equal to the numpy definition
   rsparse_amd.SLIM            the sparse linear method of Ning and Karypis 2011: a non-negative elastic net per item column by
                               coordinate descent on the device, equal to the numpy definition; EASE's inference surface
+  rsparse_amd.BPR             matrix factorisation on the pairwise ranking loss of Rendle et al. 2009 by deterministic mini-batch SGD
+                              on the device, equal to the numpy definition; WRMF's inference surface with an SGD fold-in
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
   rsparse_amd.engine          device-resident, row-sharded driver (one process per GPU)
   rsparse_amd.synth           synthetic interaction matrices for the BASELINE configs
@@ -56,6 +58,9 @@ def __getattr__(name):
     if name in ("SLIM", "slim_columns_reference", "slim_weights_reference"):
         from . import slim
         return getattr(slim, name)
+    if name in ("BPR", "bpr_triples", "bpr_step_reference", "bpr_fit_reference"):
+        from . import bpr
+        return getattr(bpr, name)
     if name == "metrics":
         import importlib
         return importlib.import_module(".metrics", __name__)

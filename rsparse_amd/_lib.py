@@ -24,6 +24,7 @@ KNN_WS_BYTES, KNN_SPAN, KNN_LDS_CAND = 1 << 30, 64, 4096
 EASE_MAX_ITEMS, EASE_TILE_BYTES, EASE_CHUNK, EASE_AHEAD = 32768, 4096, 1024, 8
 EASE_CELLS_RATIO = 16   # a row of m cells is scored at its cells, not as a dense row, while m <= KNN_LDS_CAND and m * ratio <= n_items
 SLIM_LDS_SUPPORT = 2048   # RSPARSE_HIP_SLIM_LDS_SUPPORT: the support entries of a SLIM column (wrmf_slim.hip) that stay in LDS
+BPR_CHUNK = 64   # RSPARSE_HIP_BPR_CHUNK: consecutive contributions of a destination row that are summed as one chunk (wrmf_bpr.hip)
 RANKS_BATCH = 1024  # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that the rank count takes at a time
 
 _c_int, _c_uint, _c_dbl, _c_i64, _c_u64 = ctypes.c_int, ctypes.c_uint, ctypes.c_double, ctypes.c_int64, ctypes.c_uint64
@@ -150,6 +151,17 @@ SIGNATURES = {
     "rsparse_hip_slim_columns_device": (_c_int, [_vp, ctypes.c_size_t, _c_int, _vp, _c_int, _c_dbl, _c_dbl, _c_int, _c_dbl, _vp,
                                                  ctypes.c_size_t, _c_int, _vp, _vp]),
     "rsparse_hip_slim_fit": (_c_int, [_vp, _vp, _c_int, _c_int, _c_dbl, _c_dbl, _c_int, _c_dbl, _vp, _vp]),
+    "rsparse_hip_bpr_triples_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_u64, _c_int, _c_int, _c_int, _c_int, _vp, _vp,
+                                                _vp, _vp]),
+    "rsparse_hip_bpr_step_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_u64, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                             _c_dbl, _c_dbl, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_bpr_step_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_u64, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                                 _c_dbl, _c_dbl, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_bpr_epochs_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_u64, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                               _c_dbl, _c_dbl, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_bpr_epochs_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_u64, _c_int, _c_int, _c_int, _c_int,
+                                                   _c_int, _c_dbl, _c_dbl, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rsparse_hip_bpr_fit": (_c_int, [_vp, _vp, _c_int, _c_int, _c_u64, _c_int, _c_int, _c_int, _c_dbl, _c_dbl, _vp, _vp, _vp, _vp, _vp]),
     "rsparse_hip_top_candidates_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl, _vp,
                                                    _vp, _vp]),
     "rsparse_hip_top_candidates_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl,

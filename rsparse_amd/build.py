@@ -17,7 +17,7 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 SRC = [CSRC / n for n in ("wrmf_kernels.hip", "wrmf_cgq.hip", "wrmf_cgp.hip", "wrmf_ne.hip", "wrmf_chol.hip", "wrmf_chol_wave.hip", "wrmf_chol_mf.hip", "wrmf_cg_mf.hip", "wrmf_chol_lr.hip",
-                          "wrmf_topk.hip", "wrmf_topk_large.hip", "wrmf_similar.hip", "wrmf_metrics.hip", "wrmf_hits.hip", "wrmf_lists.hip", "wrmf_diversity.hip", "wrmf_mmr.hip", "wrmf_ranks.hip", "wrmf_score.hip", "wrmf_softals.hip", "wrmf_itemknn.hip", "wrmf_ease.hip", "wrmf_slim.hip", "wrmf_candidates.hip", "wrmf_sample.hip", "wrmf_sample_weighted.hip", "wrmf_split.hip", "wrmf_confidence.hip", "wrmf_events.hip", "wrmf_explain.hip", "wrmf_init.hip", "wrmf_ingest.hip", "wrmf_nnls.hip", "wrmf_bias.hip", "wrmf_lu.hip",
+                          "wrmf_topk.hip", "wrmf_topk_large.hip", "wrmf_similar.hip", "wrmf_metrics.hip", "wrmf_hits.hip", "wrmf_lists.hip", "wrmf_diversity.hip", "wrmf_mmr.hip", "wrmf_ranks.hip", "wrmf_score.hip", "wrmf_softals.hip", "wrmf_itemknn.hip", "wrmf_ease.hip", "wrmf_slim.hip", "wrmf_bpr.hip", "wrmf_candidates.hip", "wrmf_sample.hip", "wrmf_sample_weighted.hip", "wrmf_split.hip", "wrmf_confidence.hip", "wrmf_events.hip", "wrmf_explain.hip", "wrmf_init.hip", "wrmf_ingest.hip", "wrmf_nnls.hip", "wrmf_bias.hip", "wrmf_lu.hip",
                           "wrmf_f64.hip", "wrmf_wide.hip", "wrmf_wide_cg.hip", "wrmf_ctx_kernels.hip", "wrmf_schedule.cpp", "wrmf_capi.cpp", "wrmf_f64_capi.cpp", "wrmf_capi_host.cpp", "wrmf_ctx.cpp")]
 HEADERS = [CSRC / "wrmf_chol_mf.attrs.csv", CSRC / "wrmf_mf.h", CSRC / "wrmf_internal.h", CSRC / "wrmf_capi_common.h", CSRC / "wrmf_schedule.h", CSRC / "wrmf_device.h", CSRC / "wrmf_sample_team.h", CSRC / "wrmf_wave.h", CSRC / "wrmf_csr_rows.h", CSRC / "wrmf_ldlt.h", CSRC / "wrmf_f64.h", CSRC / "wrmf_topk_plan.h", CSRC / "wrmf_ctx_layout.h", PKG.parent / "include" / "rsparse_wrmf_hip.h"]
 DEPS = SRC + HEADERS
@@ -35,6 +35,9 @@ EXTRA_FLAGS = {n: ["-mllvm", "-forceattrs-csv-path=" + str(CSRC / "wrmf_chol_mf.
 # wrmf_slim.hip states its coordinate descent in separately rounded float64 operations (rsparse_amd/slim.py): no product may be
 # contracted into the sum that follows it
 EXTRA_FLAGS["wrmf_slim.hip"] = ["-ffp-contract=off"]
+# wrmf_bpr.hip likewise: the score, the sigmoid's polynomial, the gradient sums and the Adagrad update of rsparse_amd/bpr.py are
+# separately rounded float64 operations
+EXTRA_FLAGS["wrmf_bpr.hip"] = ["-ffp-contract=off"]
 AUDITED = {"wrmf_chol_mf.hip", "wrmf_cg_mf.hip"}
 REG_LIMIT = {"wrmf_cg_mf.hip": 512}   # (one wave per SIMD by design: 320 accumulator registers per row)
 # Kernels that fit two waves per SIMD only without a spill (the 24-quad team kernel of wrmf_cgq.hip keeps 192 registers of
@@ -84,6 +87,10 @@ NO_SPILL = {"wrmf_cgq.hip": ("14als_cgq_kernelILi128ELi24ELi4ELi4E",),
             # four doubles of a coordinate per lane in the evaluation, four gathered cells of G in flight in the update: scratch
             # would sit inside the column's serial chain
             "wrmf_slim.hip": ("slim_support_kernel", "14slim_cd_kernelILb1E", "14slim_cd_kernelILb0E"),
+            # integer-only sampling and bisections; the gradient kernels keep a destination's running chunk sum and total in
+            # double registers (two per 16 coordinates and lane): scratch would sit inside the serial walk
+            "wrmf_bpr.hip": ("bpr_sample_kernel", "bpr_z_kernel", "bpr_users_kernel", "bpr_item_chunks_kernel", "bpr_items_kernel",
+                             "bpr_copy_kernel", "bpr_segments_kernel", "bpr_chunks_kernel"),
             "wrmf_split.hip": ("split_count_wave_kernel", "split_count_team_kernel", "split_write_wave_kernel", "split_write_team_kernel")}
 RESOURCE_FLAG = "-Rpass-analysis=kernel-resource-usage"
 

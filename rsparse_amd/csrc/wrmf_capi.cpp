@@ -1788,6 +1788,101 @@ int rsparse_hip_init_factors_device(uint64_t seed, int stream, int64_t row0, int
                              (hipStream_t)hip_stream);
 }
 
+extern "C++" {
+namespace {
+// BPR (wrmf_bpr.hip), both precisions; the host form rsparse_hip_bpr_fit: wrmf_capi_host.cpp
+BprRun bpr_run_of(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0, uint64_t seed, int mode,
+                  int n_steps, int rank, double lr, double lambda, int update_items) {
+  BprRun r;
+  r.p = d_p; r.j = d_j; r.n_rows = n_rows; r.n_items = n_items; r.nnz = nnz; r.row0 = row0; r.seed = seed; r.mode = mode;
+  r.n_steps = n_steps; r.rank = rank; r.lr = lr; r.lambda = lambda; r.update_items = update_items != 0;
+  return r;
+}
+
+template <class T>
+int bpr_step_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0, uint64_t seed, int mode,
+                    int epoch, int step, int n_steps, int rank, double lr, double lambda, int update_items, T* d_U, T* d_V,
+                    double* d_aU, double* d_aV, int64_t* d_counts, void* stream, int max_rank) {
+  int rc = bpr_args(!d_p || !d_j || !d_U || !d_V || !d_aU || !d_aV || !d_counts, n_rows, n_items, nnz, row0, mode, epoch, 1, n_steps,
+                    "n_steps", rank, max_rank, lr, lambda);
+  if (rc) return rc;
+  if (step < 0 || step >= n_steps) return fail(RSPARSE_HIP_ERR_INVALID, "step outside [0, n_steps)");
+  if ((rc = bpr_step_size(nnz, n_steps, update_items))) return rc;
+  if (n_rows == 0 || nnz == 0) return RSPARSE_HIP_OK;
+  hipError_t e = launch_bpr_run<T>(bpr_run_of(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, n_steps, rank, lr, lambda, update_items),
+                                   epoch, 1, step, d_U, d_V, d_aU, d_aV, reinterpret_cast<unsigned long long*>(d_counts),
+                                   (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_bpr_run");
+  return RSPARSE_HIP_OK;
+}
+
+template <class T>
+int bpr_epochs_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0, uint64_t seed, int mode,
+                      int epoch0, int n_epochs, int batch, int rank, double lr, double lambda, int update_items, T* d_U, T* d_V,
+                      double* d_aU, double* d_aV, int64_t* d_counts, void* stream, int max_rank) {
+  int rc = bpr_args(!d_p || !d_j || !d_U || !d_V || !d_aU || !d_aV || !d_counts, n_rows, n_items, nnz, row0, mode, epoch0, n_epochs,
+                    batch, "batch", rank, max_rank, lr, lambda);
+  if (rc) return rc;
+  const int n_steps = mode == 1 || nnz == 0 ? 1 : (int)((nnz + batch - 1) / batch);
+  if ((rc = bpr_step_size(nnz, n_steps, update_items))) return rc;
+  if (n_rows == 0 || n_epochs == 0) return RSPARSE_HIP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * (size_t)n_epochs * sizeof(int64_t), s));
+  if (nnz == 0) return RSPARSE_HIP_OK;
+  hipError_t e = launch_bpr_run<T>(bpr_run_of(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, n_steps, rank, lr, lambda, update_items),
+                                   epoch0, n_epochs, -1, d_U, d_V, d_aU, d_aV, reinterpret_cast<unsigned long long*>(d_counts), s);
+  if (e != hipSuccess) return hip_fail(e, "launch_bpr_run");
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int rsparse_hip_bpr_triples_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                   uint64_t seed, int mode, int epoch, int step, int n_steps, int32_t* d_u, int32_t* d_i,
+                                   int32_t* d_neg, void* stream) {
+  int rc = bpr_args(!d_p || !d_j || !d_u || !d_i || !d_neg, n_rows, n_items, nnz, row0, mode, epoch, 1, n_steps, "n_steps", 0, 0, 0.0,
+                    0.0);
+  if (rc) return rc;
+  if (step < 0 || step >= n_steps) return fail(RSPARSE_HIP_ERR_INVALID, "step outside [0, n_steps)");
+  if (n_rows == 0 || nnz == 0) return RSPARSE_HIP_OK;
+  hipError_t e = launch_bpr_triples(bpr_run_of(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, n_steps, 0, 0.0, 0.0, 0), epoch, step,
+                                    d_u, d_i, d_neg, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_bpr_triples");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_bpr_step_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                uint64_t seed, int mode, int epoch, int step, int n_steps, int rank, double learning_rate,
+                                double lambda, int update_items, float* d_U, float* d_V, double* d_aU, double* d_aV,
+                                int64_t* d_counts, void* stream) {
+  return bpr_step_device<float>(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, epoch, step, n_steps, rank, learning_rate, lambda,
+                                update_items, d_U, d_V, d_aU, d_aV, d_counts, stream, RSPARSE_HIP_MAX_RANK);
+}
+
+int rsparse_hip_bpr_step_f64_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                    uint64_t seed, int mode, int epoch, int step, int n_steps, int rank, double learning_rate,
+                                    double lambda, int update_items, double* d_U, double* d_V, double* d_aU, double* d_aV,
+                                    int64_t* d_counts, void* stream) {
+  return bpr_step_device<double>(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, epoch, step, n_steps, rank, learning_rate, lambda,
+                                 update_items, d_U, d_V, d_aU, d_aV, d_counts, stream, RSPARSE_HIP_MAX_RANK_F64);
+}
+
+int rsparse_hip_bpr_epochs_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                  uint64_t seed, int mode, int epoch0, int n_epochs, int batch, int rank, double learning_rate,
+                                  double lambda, int update_items, float* d_U, float* d_V, double* d_aU, double* d_aV,
+                                  int64_t* d_counts, void* stream) {
+  return bpr_epochs_device<float>(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, epoch0, n_epochs, batch, rank, learning_rate, lambda,
+                                  update_items, d_U, d_V, d_aU, d_aV, d_counts, stream, RSPARSE_HIP_MAX_RANK);
+}
+
+int rsparse_hip_bpr_epochs_f64_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                      uint64_t seed, int mode, int epoch0, int n_epochs, int batch, int rank, double learning_rate,
+                                      double lambda, int update_items, double* d_U, double* d_V, double* d_aU, double* d_aV,
+                                      int64_t* d_counts, void* stream) {
+  return bpr_epochs_device<double>(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, epoch0, n_epochs, batch, rank, learning_rate,
+                                   lambda, update_items, d_U, d_V, d_aU, d_aV, d_counts, stream, RSPARSE_HIP_MAX_RANK_F64);
+}
+
 namespace {
 // the device form of both samplers: d_cum == nullptr is the uniform stream, otherwise the weighted one under that prefix
 int sample_negatives_device(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* d_seen_p,

@@ -445,6 +445,35 @@ inline int slim_args(bool missing, int n_items, int n_cols, double l1, double l2
   return RSPARSE_HIP_OK;
 }
 
+// BPR: what every entry refuses.  per_epoch: n_steps of the triples / step entries, batch of the epochs / fit entries (name: which);
+// rank = 0 with max_rank = 0: the entry has no factors (the triples)
+inline int bpr_args(bool missing, int n_rows, int n_items, int64_t nnz, int64_t row0, int mode, int64_t epoch0, int64_t n_epochs,
+                    int per_epoch, const char* name, int rank, int max_rank, double lr, double lambda) {
+  const auto ok = [](double v) { return v >= 0.0 && v <= 1.7976931348623157e308; };   // (NaN fails both)
+  if (missing) return fail(RSPARSE_HIP_ERR_INVALID, "the pattern, the factors, their Adagrad states or an output is NULL");
+  if (n_rows < 0 || n_items < 0 || nnz < 0 || nnz > 0x7fffffffLL)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, n_items < 0, nnz < 0 or nnz >= 2^31)");
+  if (row0 < 0 || row0 + (int64_t)n_rows > (1LL << 32)) return fail(RSPARSE_HIP_ERR_INVALID, "the global row index does not fit 32 bits");
+  if (mode != 0 && mode != 1) return fail(RSPARSE_HIP_ERR_INVALID, "mode is 0 (fit) or 1 (fold-in)");
+  if (epoch0 < 0 || n_epochs < 0 || epoch0 + n_epochs > (1LL << 31)) return fail(RSPARSE_HIP_ERR_INVALID, "an epoch outside [0, 2^31)");
+  if (per_epoch < 1) return fail(RSPARSE_HIP_ERR_INVALID, std::string(name) + " < 1");
+  if (max_rank) {
+    if (rank < 1) return fail(RSPARSE_HIP_ERR_INVALID, "rank < 1");
+    if (!ok(lr) || !ok(lambda)) return fail(RSPARSE_HIP_ERR_INVALID, "learning_rate or lambda is negative or not finite");
+    if (rank > max_rank)
+      return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > " + std::to_string(max_rank) + " is not on the device path");
+  }
+  if (nnz > 0 && n_items == 0) return fail(RSPARSE_HIP_ERR_INVALID, "entries without items");
+  return RSPARSE_HIP_OK;
+}
+
+// the item side numbers the two contributions of every slot of a step, 2k and 2k + 1, in 32 bits and counts them in an int
+inline int bpr_step_size(int64_t nnz, int n_steps, int update_items) {
+  if (update_items && (nnz + n_steps - 1) / n_steps >= (1LL << 30))
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "a step of 2^30 or more triples with update_items: take a smaller batch");
+  return RSPARSE_HIP_OK;
+}
+
 // rsparse_hip_score_pairs_device / _f64_device (kernels: wrmf_score.hip).  Handed in:
 //   int workspace(size_t n, double*& buf)    makes sure of n doubles of the side's grow-only workspace
 // which is only asked for the sums without the scores: the scores then live there, and their count, p[n_rows], has to be

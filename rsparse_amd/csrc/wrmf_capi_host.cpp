@@ -1095,6 +1095,43 @@ int rsparse_hip_slim_fit(const int32_t* p, const int32_t* j, int n_users, int n_
   return RSPARSE_HIP_OK;
 }
 
+int rsparse_hip_bpr_fit(const int32_t* p, const int32_t* j, int n_users, int n_items, uint64_t seed, int n_epochs, int batch, int rank,
+                        double learning_rate, double lambda, double* U, double* V, double* aU, double* aV, int64_t* counts) {
+  int rc = bpr_args(!p || !U || !V || !aU || !aV || !counts, n_users, n_items, 0, 0, 0, 0, n_epochs, batch, "batch", rank,
+                    RSPARSE_HIP_MAX_RANK_F64, learning_rate, lambda);
+  if (rc) return rc;
+  if ((rc = check_csr(p, n_users, "p"))) return rc;
+  const size_t nnz = (size_t)p[n_users];
+  if (nnz && !j) return fail(RSPARSE_HIP_ERR_INVALID, "j is NULL");
+  if ((rc = check_columns(p, j, n_users, n_items, "j"))) return rc;
+  for (int e = 0; e < 2 * n_epochs; e++) counts[e] = 0;
+  if (n_users == 0) return RSPARSE_HIP_OK;
+  const size_t nu = (size_t)n_users, ni = (size_t)n_items, k = (size_t)rank;
+  DevBuf dP, dJ, dU, dV, dAU, dAV, dC;
+  HIP_TRY(upload_host(dP, p, nu + 1));
+  HIP_TRY(upload_host(dJ, j, nnz));
+  HIP_TRY(dU.alloc(nu * k * sizeof(double)));
+  HIP_TRY(dV.alloc(ni * k * sizeof(double)));
+  HIP_TRY(dAU.alloc(nu * sizeof(double)));
+  HIP_TRY(dAV.alloc(ni * sizeof(double)));
+  HIP_TRY(dC.alloc(2 * (size_t)n_epochs * sizeof(int64_t)));
+  HIP_TRY(hipMemsetAsync(dAU.p, 0, nu * sizeof(double), nullptr));
+  HIP_TRY(hipMemsetAsync(dAV.p, 0, ni * sizeof(double) + (ni ? 0 : 8), nullptr));
+  if ((rc = rsparse_hip_init_factors_f64_device(seed, 0, 0, n_users, rank, rank, 0.01, 0, -1, dU.p, nullptr))) return rc;
+  if (n_items && (rc = rsparse_hip_init_factors_f64_device(seed, 1, 0, n_items, rank, rank, 0.01, 0, -1, dV.p, nullptr))) return rc;
+  rc = rsparse_hip_bpr_epochs_f64_device(dP.as<int32_t>(), dJ.as<int32_t>(), n_users, n_items, (int64_t)nnz, 0, seed, 0, 0, n_epochs, batch,
+                                         rank, learning_rate, lambda, 1, dU.as<double>(), dV.as<double>(), dAU.as<double>(),
+                                         dAV.as<double>(), dC.as<int64_t>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(download(U, dU, nu * k));
+  HIP_TRY(download(V, dV, ni * k));
+  HIP_TRY(download(aU, dAU, nu));
+  HIP_TRY(download(aV, dAV, ni));
+  if (n_epochs) HIP_TRY(download(counts, dC, 2 * (size_t)n_epochs));
+  return RSPARSE_HIP_OK;
+}
+
 extern "C++" {
 namespace {
 // B (n x n column-major, an R matrix) as n row-major rows of ld elements, zeros beyond n; a non-finite entry -> false

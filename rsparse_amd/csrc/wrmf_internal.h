@@ -499,6 +499,26 @@ hipError_t launch_slim_columns(const double* G, size_t ld_G, int n_items, const 
                                int n_lds, int slices, int stride, double l1, double l2, int max_iter, double tol, void* W,
                                size_t ld_W, bool w_is_double, int32_t* sweeps, char* ws, hipStream_t s);
 
+// BPR (wrmf_bpr.hip; defined in rsparse_wrmf_hip.h).  A run: the canonical CSR rows (p from 0, nnz = p[n_rows] handed in, so that
+// nothing is read back), the stream's parameters and the step size; n_steps: the steps of an epoch.  triples: (u, i, j) of one
+// step, cnt = ceil((nnz - step) / n_steps) each.  run: the steps [0, n_steps) (only_step < 0) or the one step only_step of the
+// epochs [epoch0, epoch0 + n_epochs), in place on U, V (ld = rank), aU, aV; counts[2 e], counts[2 e + 1]: n_valid and n_correct of
+// epoch epoch0 + e, ADDED to.  !update_items: V and aV are read only.  Allocates its scratch and waits for `s` before it returns.
+struct BprRun {
+  const int32_t* p;
+  const int32_t* j;
+  int n_rows, n_items;
+  int64_t nnz, row0;
+  uint64_t seed;
+  int mode, n_steps, rank;
+  double lr, lambda;
+  bool update_items;
+};
+hipError_t launch_bpr_triples(const BprRun& r, int epoch, int step, int32_t* tu, int32_t* ti, int32_t* tj, hipStream_t s);
+template <class T>
+hipError_t launch_bpr_run(const BprRun& r, int epoch0, int n_epochs, int only_step, T* U, T* V, double* aU, double* aV,
+                          unsigned long long* counts, hipStream_t s);
+
 // top-k within per-user candidate lists (wrmf_candidates.hip), T = float or double, 1 <= topk <= kTopLargeMax: for every row of
 // the CSR pattern (cand_p: n_users + 1 slots, absolute positions into cand_j; p0 = cand_p[0], nnz = cand_p[n_users] - p0, read by
 // the caller; columns ascending and unique within a row) the topk best admissible candidates by launch_score_pairs' scores

@@ -968,6 +968,43 @@ class HipBackend:
                                                             some(sweeps), self._stream()))
         return sweeps
 
+    def bpr_triples(self, p, j, n_items, nnz, row0, seed, mode, epoch, step, n_steps):
+        """the BPR triples of one step of the canonical CSR rows (p, j: int32 on the device, p from 0, nnz = p[-1]) -> (u, i, neg):
+        int32 on the device, neg = -1 for a void triple (wrmf_bpr.hip; rsparse_amd.bpr.bpr_triples is the definition)"""
+        assert p.dtype == torch.int32 and j.dtype == torch.int32 and p.is_cuda
+        cnt = max(0, -(-(int(nnz) - int(step)) // int(n_steps)))
+        out = torch.empty((3, max(cnt, 1)), dtype=torch.int32, device=self.device)
+        some = lambda t: t.data_ptr() if t.numel() else out.data_ptr()
+        _lib.check(self.lib.rsparse_hip_bpr_triples_device(some(p), some(j), int(p.numel()) - 1, int(n_items), int(nnz), int(row0), int(seed),
+                                                           int(mode), int(epoch), int(step), int(n_steps), out[0].data_ptr(),
+                                                           out[1].data_ptr(), out[2].data_ptr(), self._stream()))
+        return out[0, :cnt], out[1, :cnt], out[2, :cnt]
+
+    def _bpr_call(self, name, p, j, n_items, nnz, row0, seed, mode, a, b, c, U, V, aU, aV, lr, lam, update_items, counts):
+        assert p.dtype == torch.int32 and j.dtype == torch.int32 and U.dtype == V.dtype and U.dtype in (torch.float32, torch.float64)
+        assert U.is_cuda and U.is_contiguous() and V.is_contiguous() and U.shape[1] == V.shape[1] and V.shape[0] == int(n_items)
+        assert aU.dtype == torch.float64 and aV.dtype == torch.float64 and aU.numel() == U.shape[0] and aV.numel() == V.shape[0]
+        assert U.shape[0] == p.numel() - 1 and aU.is_contiguous() and aV.is_contiguous()
+        fn = getattr(self.lib, "rsparse_hip_bpr_%s%s_device" % (name, "_f64" if U.dtype == torch.float64 else ""))
+        some = lambda t: t.data_ptr() if t.numel() else counts.data_ptr()   # (an empty tensor has no address to pass)
+        _lib.check(fn(some(p), some(j), int(U.shape[0]), int(n_items), int(nnz), int(row0), int(seed), int(mode), int(a), int(b), int(c),
+                      int(U.shape[1]), float(lr), float(lam), int(bool(update_items)), some(U), some(V), some(aU), some(aV),
+                      counts.data_ptr(), self._stream()))
+        return counts
+
+    def bpr_step(self, p, j, n_items, nnz, row0, seed, mode, epoch, step, n_steps, U, V, aU, aV, lr, lam, update_items=True):
+        """one BPR step in place on the factors U, V (float32 or float64, contiguous) and their Adagrad states aU, aV (float64)
+        (wrmf_bpr.hip; rsparse_amd.bpr.bpr_step_reference is the definition) -> (n_valid, n_correct): int64 on the device"""
+        counts = torch.zeros(2, dtype=torch.int64, device=self.device)
+        return self._bpr_call("step", p, j, n_items, nnz, row0, seed, mode, epoch, step, n_steps, U, V, aU, aV, lr, lam, update_items, counts)
+
+    def bpr_epochs(self, p, j, n_items, nnz, row0, seed, mode, epoch0, n_epochs, batch, U, V, aU, aV, lr, lam, update_items=True):
+        """the epochs [epoch0, epoch0 + n_epochs) of ceil(nnz / batch) steps each (mode 1, the fold-in: one step), in place, on
+        one stream -> (n_epochs, 2) int64 on the device: (n_valid, n_correct) per epoch"""
+        counts = torch.zeros((max(int(n_epochs), 1), 2), dtype=torch.int64, device=self.device)
+        self._bpr_call("epochs", p, j, n_items, nnz, row0, seed, mode, epoch0, n_epochs, batch, U, V, aU, aV, lr, lam, update_items, counts)
+        return counts[:int(n_epochs)]
+
     def _knn_rows(self, xp, xj, neighbors, q, xv):
         """the operands the ItemKNN evaluation entries share with `knn_recommend`, as the C ABI takes them: -> (the leading
         arguments, `some`: the address of a tensor, or of xp for an empty one; the tensors that must outlive the call)"""

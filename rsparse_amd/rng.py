@@ -63,6 +63,20 @@ bit for bit.  Row u has the global index g = row0 + u and L entries; an entry is
 
 A flag depends on (seed, g, t, the mode's parameters) and, in leave-out mode, on the row's L or `by` values: not on the rows split
 together, the batch, the rank count or the device.  row0 + n_rows <= 2^32, L < 2^31.
+
+`STREAM_BPR` is the seventh stream: the (user, positive, negative) triples of the BPR fit (rsparse_amd/bpr.py: `bpr_triples` is the
+numpy form, rsparse_amd/csrc/wrmf_bpr.hip draws them on the device bit for bit).  An epoch has one triple per stored entry of a
+canonical CSR; slot p belongs to row u of L entries at position q = p - indptr[u]:
+
+    counter   (q, g, 6, epoch + 2^31 mode), key (lo32(seed), hi32(seed)) -> o0..o3;  mode 0 = the fit, g = row0 + u;
+              mode 1 = the fold-in, g = row0 for every row (a folded-in row's triples depend on the row alone; all rows of a
+              fold-in epoch then share the words of a position q, hence its three negative candidates -- harmless with the items
+              frozen, where no row sees another's update)
+    positive  indices[indptr[u] + ((o0 L) >> 32)]
+    negative  the first of (o1 n_items) >> 32, (o2 n_items) >> 32, (o3 n_items) >> 32 that is not in the row (a binary search);
+              all three in the row: the triple is VOID (-1) and takes no part in anything -- no input can make the sampler spin
+
+Integers only.  A triple depends on (seed, mode, epoch, g, q, the row, n_items) alone.  epoch < 2^31.
 """
 import numpy as np
 
@@ -71,6 +85,7 @@ PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
 STREAM_USERS, STREAM_ITEMS, STREAM_NEGATIVES = 0, 1, 2
 STREAM_SPLIT, STREAM_LEAVE_OUT = 3, 4
 STREAM_WEIGHTED_NEGATIVES = 5
+STREAM_BPR = 6
 MAX_NEGATIVES = 8192   # RSPARSE_HIP_MAX_NEGATIVES
 _MASK = np.uint64(0xFFFFFFFF)
 _S32 = np.uint64(32)
