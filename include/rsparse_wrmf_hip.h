@@ -1166,6 +1166,69 @@ int rsparse_hip_bpr_fit(const int32_t* p, const int32_t* j, int n_users, int n_i
                         double learning_rate, double lambda, double* U, double* V, double* aU, double* aV, int64_t* counts);
 
 /* ------------------------------------------------------------------------------------------------
+ * WARP (Weston, Bengio and Usunier 2011): BPR's steps with a searched negative and a rank weight
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The definition (rsparse_amd/warp.py states it in numpy: warp_triples, warp_step_reference, warp_fit_reference).  Everything not
+ * said here is BPR's above: the input, steps, slots, k, dot, E(d), the order of the sums, chunks, the update, modes, the start.
+ *
+ * Stream 7.  Philox call c of the slot at position q of row u has counter (q, g, 7 + 256 c, epoch + 2^31 mode) and BPR's key and g
+ * (the third word of every other stream is 0..6).  Word 0 of call 0 gives the positive, i = j[p[u] + ((o0 L) >> 32)].  Trial t,
+ * 1 <= t <= max_trials <= RSPARSE_HIP_WARP_MAX_TRIALS, is word t & 3 of call t >> 2; its candidate is c_t = (o n_items) >> 32.
+ *
+ * The search, from the snapshot (U, V) at the start of the step, in ascending t: a candidate in the row is skipped (it still
+ * consumes its t); another one is scored, d_t = dot(U[u], V[i] - V[c_t]); the first scored trial with d_t <= margin is the
+ * VIOLATOR and ends the search: j = c_t, t_k = t, z_k = weights[t - 1] / (1 + E(d_t)).  No violator: the triple is VOID (j = -1,
+ * t_k = 0, z_k = 0) and takes no part in anything.  weights: max_trials finite doubles >= 0 of the caller -- the library calls no
+ * logarithm; the model hands in log(2 + (n_items - 1) / t) / log(2 + n_items), the rank weight of the modelled-on solver.
+ * The rows, their order and the update are BPR's with this z_k.
+ *
+ * counts, four per epoch: n_valid (triples with a violator), n_looked (slots with a scored trial), n_correct (of those, the slots
+ * whose first scored trial has d > 0), n_scored (trials scored, the violator included).
+ *
+ * The kernel (warp_search_kernel of wrmf_bpr.hip) takes the place of BPR's sample and score kernels: a 16-lane group per slot
+ * holds U[u] and V[i] in registers, draws trials in rounds of 16 and walks a round's admissible ones in order. */
+#define RSPARSE_HIP_WARP_MAX_TRIALS 64
+
+/* Refusals: BPR's, and max_trials outside [1, RSPARSE_HIP_WARP_MAX_TRIALS], a margin that is not finite, weights NULL or an entry
+ * negative or not finite -> ERR_INVALID; all before a device is touched.  weights is HOST memory in every entry. */
+
+/* the search alone for one step: d_u, d_i, d_neg (-1: void), d_t: ceil((nnz - step) / n_steps) int32 each, d_z as many doubles */
+int rsparse_hip_warp_triples_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                    uint64_t seed, int mode, int epoch, int step, int n_steps, int max_trials, double margin,
+                                    const double* weights, int rank, const float* d_U, const float* d_V, int32_t* d_u, int32_t* d_i,
+                                    int32_t* d_neg, int32_t* d_t, double* d_z, void* stream);
+int rsparse_hip_warp_triples_f64_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                        uint64_t seed, int mode, int epoch, int step, int n_steps, int max_trials, double margin,
+                                        const double* weights, int rank, const double* d_U, const double* d_V, int32_t* d_u,
+                                        int32_t* d_i, int32_t* d_neg, int32_t* d_t, double* d_z, void* stream);
+
+/* one step, in place, as rsparse_hip_bpr_step_device; d_counts[0..3] += n_valid, n_looked, n_correct, n_scored */
+int rsparse_hip_warp_step_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                 uint64_t seed, int mode, int epoch, int step, int n_steps, int max_trials, double margin,
+                                 const double* weights, int rank, double learning_rate, double lambda, int update_items, float* d_U,
+                                 float* d_V, double* d_aU, double* d_aV, int64_t* d_counts, void* stream);
+int rsparse_hip_warp_step_f64_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                     uint64_t seed, int mode, int epoch, int step, int n_steps, int max_trials, double margin,
+                                     const double* weights, int rank, double learning_rate, double lambda, int update_items,
+                                     double* d_U, double* d_V, double* d_aU, double* d_aV, int64_t* d_counts, void* stream);
+
+/* the epochs [epoch0, epoch0 + n_epochs), as rsparse_hip_bpr_epochs_device; d_counts: 4 n_epochs slots, zeroed by the call */
+int rsparse_hip_warp_epochs_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                   uint64_t seed, int mode, int epoch0, int n_epochs, int batch, int max_trials, double margin,
+                                   const double* weights, int rank, double learning_rate, double lambda, int update_items, float* d_U,
+                                   float* d_V, double* d_aU, double* d_aV, int64_t* d_counts, void* stream);
+int rsparse_hip_warp_epochs_f64_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                       uint64_t seed, int mode, int epoch0, int n_epochs, int batch, int max_trials, double margin,
+                                       const double* weights, int rank, double learning_rate, double lambda, int update_items,
+                                       double* d_U, double* d_V, double* d_aU, double* d_aV, int64_t* d_counts, void* stream);
+
+/* host-array form, as rsparse_hip_bpr_fit; counts: 4 n_epochs */
+int rsparse_hip_warp_fit(const int32_t* p, const int32_t* j, int n_users, int n_items, uint64_t seed, int n_epochs, int batch,
+                         int max_trials, double margin, const double* weights, int rank, double learning_rate, double lambda,
+                         double* U, double* V, double* aU, double* aV, int64_t* counts);
+
+/* ------------------------------------------------------------------------------------------------
  * why this item: per-item contributions to a score (Hu, Koren and Volinsky, section 5; `explain` of the `implicit` library)
  * ---------------------------------------------------------------------------------------------- */
 

@@ -20,6 +20,8 @@ Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit
                               coordinate descent on the device, equal to the numpy definition; EASE's inference surface
   rsparse_amd.BPR             matrix factorisation on the pairwise ranking loss of Rendle et al. 2009 by deterministic mini-batch SGD
                               on the device, equal to the numpy definition; WRMF's inference surface with an SGD fold-in
+  rsparse_amd.WARP            BPR with a searched negative and a rank weight (Weston et al. 2011): up to 64 draw-and-score trials per
+                              slot in one kernel on the device, equal to the numpy definition; BPR's surface
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
   rsparse_amd.engine          device-resident, row-sharded driver (one process per GPU)
   rsparse_amd.synth           synthetic interaction matrices for the BASELINE configs
@@ -61,6 +63,9 @@ def __getattr__(name):
     if name in ("BPR", "bpr_triples", "bpr_step_reference", "bpr_fit_reference"):
         from . import bpr
         return getattr(bpr, name)
+    if name in ("WARP", "rank_weights", "warp_triples", "warp_step_reference", "warp_fit_reference"):
+        from . import warp
+        return getattr(warp, name)
     if name == "metrics":
         import importlib
         return importlib.import_module(".metrics", __name__)

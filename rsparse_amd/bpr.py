@@ -71,9 +71,10 @@ def step_slots(nnz, step, n_steps):
     return np.arange(int(step), int(nnz), int(n_steps), dtype=np.int64)
 
 
-def bpr_triples(seed, mode, epoch, row0, indptr, indices, n_items, step=0, n_steps=1):
-    """The triples of one step -> (u, i, j): int32 arrays over k, u the LOCAL row, j = -1 for a void triple.  (indptr, indices): a
-    canonical CSR pattern whose row pointers start at 0; row0: the global index of its first row."""
+def step_slot_rows(seed, mode, epoch, row0, indptr, indices, n_items, step, n_steps):
+    """What the triples of one step are drawn from -> (u, L, counter01, key, idx, ip, inside): per slot of the step, in the order k,
+    the local row, its length and the first two counter words (q, g) of its Philox calls; the key; `inside(cand)`: whether each
+    slot's candidate is in its row."""
     seed, mode, epoch, row0, n_items, step, n_steps = (int(v) for v in (seed, mode, epoch, row0, n_items, step, n_steps))
     ip, idx = np.asarray(indptr, dtype=np.int64), np.asarray(indices, dtype=np.int64)
     n_rows = ip.size - 1
@@ -84,20 +85,30 @@ def bpr_triples(seed, mode, epoch, row0, indptr, indices, n_items, step=0, n_ste
     u = np.searchsorted(ip, p, side="right") - 1
     L, q = (ip[u + 1] - ip[u]).astype(np.uint64), (p - ip[u]).astype(np.uint64)
     g = np.full(p.size, row0, dtype=np.uint64) + (u.astype(np.uint64) if mode == 0 else np.uint64(0))
-    counter = np.stack([q, g, np.full_like(q, _rng.STREAM_BPR), np.full_like(q, epoch + (mode << 31))], axis=-1)
     key = np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64)
-    o = _rng.philox4x32_10(counter, key).astype(np.uint64)
-    s32 = np.uint64(32)
-    pos = idx[ip[u] + ((o[:, 0] * L) >> s32).astype(np.int64)] if p.size else np.zeros(0, np.int64)
     # membership of a candidate in its row: the entries of a canonical pattern are sorted by (row, column)
     cells = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(ip)) * n_items + idx
-    neg = np.full(p.size, -1, dtype=np.int64)
-    for t in (3, 2, 1):
-        cand = ((o[:, t] * np.uint64(n_items)) >> s32).astype(np.int64)
+
+    def inside(cand):
         want = u * n_items + cand
         at = np.searchsorted(cells, want)
-        inside = (at < cells.size) & (cells[np.minimum(at, max(cells.size - 1, 0))] == want) if cells.size else np.zeros(p.size, bool)
-        neg = np.where(inside, neg, cand)
+        return (at < cells.size) & (cells[np.minimum(at, max(cells.size - 1, 0))] == want) if cells.size else np.zeros(p.size, bool)
+
+    return u, L, np.stack([q, g], axis=-1), key, idx, ip, inside
+
+
+def bpr_triples(seed, mode, epoch, row0, indptr, indices, n_items, step=0, n_steps=1):
+    """The triples of one step -> (u, i, j): int32 arrays over k, u the LOCAL row, j = -1 for a void triple.  (indptr, indices): a
+    canonical CSR pattern whose row pointers start at 0; row0: the global index of its first row."""
+    u, L, qg, key, idx, ip, inside = step_slot_rows(seed, mode, epoch, row0, indptr, indices, n_items, step, n_steps)
+    tail = np.broadcast_to(np.array([_rng.STREAM_BPR, int(epoch) + (int(mode) << 31)], dtype=np.uint64), qg.shape)
+    o = _rng.philox4x32_10(np.concatenate([qg, tail], axis=-1), key).astype(np.uint64)
+    s32 = np.uint64(32)
+    pos = idx[ip[u] + ((o[:, 0] * L) >> s32).astype(np.int64)] if u.size else np.zeros(0, np.int64)
+    neg = np.full(u.size, -1, dtype=np.int64)
+    for t in (3, 2, 1):
+        cand = ((o[:, t] * np.uint64(int(n_items))) >> s32).astype(np.int64)
+        neg = np.where(inside(cand), neg, cand)
     return u.astype(np.int32), pos.astype(np.int32), neg.astype(np.int32)
 
 
@@ -173,6 +184,22 @@ def _apply(rows, a, totals, counts, lr, lam):
     return out, a2
 
 
+def step_from_z(U, V, aU, aV, u, i, j, z, diff, learning_rate, lambda_, update_items):
+    """the rows, sums and updates of one step for the triples (u, i, j) (none void, int64) with their z and diff = V[i] - V[j] ->
+    (U', V', aU', aV')"""
+    rank = U.shape[1]
+    tot_u, cnt_u = _ordered_sums(u, z[:, None] * diff, U.shape[0])
+    U2, aU2 = _apply(U, aU, tot_u, cnt_u, learning_rate, lambda_)
+    V2, aV2 = V.copy(), aV.copy()
+    if update_items:
+        Uu = U[u].astype(np.float64)
+        dest = np.stack([i, j], axis=1).reshape(-1)
+        contrib = np.stack([z[:, None] * Uu, (-z)[:, None] * Uu], axis=1).reshape(-1, rank)
+        tot_v, cnt_v = _ordered_sums(dest, contrib, V.shape[0])
+        V2, aV2 = _apply(V, aV, tot_v, cnt_v, learning_rate, lambda_)
+    return U2, V2, aU2, aV2
+
+
 def bpr_step_reference(U, V, aU, aV, tu, ti, tj, learning_rate, lambda_, update_items=True):
     """One step of the definition on the triples (tu, ti, tj) (in the order k; tj = -1: void) from the snapshot (U, V) with the
     Adagrad states (aU, aV) -> (U', V', aU', aV', n_valid, n_correct); nothing is changed in place."""
@@ -180,20 +207,10 @@ def bpr_step_reference(U, V, aU, aV, tu, ti, tj, learning_rate, lambda_, update_
     aU, aV = np.asarray(aU, dtype=np.float64), np.asarray(aV, dtype=np.float64)
     keep = np.flatnonzero(np.asarray(tj) >= 0)
     u, i, j = (np.asarray(t, dtype=np.int64)[keep] for t in (tu, ti, tj))
-    rank = U.shape[1]
-    Uu = U[u].astype(np.float64)
     diff = V[i].astype(np.float64) - V[j].astype(np.float64)
-    d = sum16(Uu * diff)
+    d = sum16(U[u].astype(np.float64) * diff)
     z = 1.0 / (1.0 + bpr_exp(d))
-    tot_u, cnt_u = _ordered_sums(u, z[:, None] * diff, U.shape[0])
-    U2, aU2 = _apply(U, aU, tot_u, cnt_u, learning_rate, lambda_)
-    V2, aV2 = V.copy(), aV.copy()
-    if update_items:
-        dest = np.stack([i, j], axis=1).reshape(-1)
-        contrib = np.stack([z[:, None] * Uu, (-z)[:, None] * Uu], axis=1).reshape(-1, rank)
-        tot_v, cnt_v = _ordered_sums(dest, contrib, V.shape[0])
-        V2, aV2 = _apply(V, aV, tot_v, cnt_v, learning_rate, lambda_)
-    return U2, V2, aU2, aV2, int(keep.size), int((d > 0).sum())
+    return step_from_z(U, V, aU, aV, u, i, j, z, diff, learning_rate, lambda_, update_items) + (int(keep.size), int((d > 0).sum()))
 
 
 def bpr_fit_reference(indptr, indices, n_items, U, V, n_iter, seed, learning_rate, lambda_, batch, mode=0, row0=0,

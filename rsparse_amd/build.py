@@ -90,7 +90,10 @@ NO_SPILL = {"wrmf_cgq.hip": ("14als_cgq_kernelILi128ELi24ELi4ELi4E",),
             # integer-only sampling and bisections; the gradient kernels keep a destination's running chunk sum and total in
             # double registers (two per 16 coordinates and lane): scratch would sit inside the serial walk
             "wrmf_bpr.hip": ("bpr_sample_kernel", "bpr_z_kernel", "bpr_users_kernel", "bpr_item_chunks_kernel", "bpr_items_kernel",
-                             "bpr_copy_kernel", "bpr_segments_kernel", "bpr_chunks_kernel"),
+                             "bpr_copy_kernel", "bpr_segments_kernel", "bpr_chunks_kernel",
+                             # WARP's search keeps U[u], V[i] and two candidate rows per group in registers for up to 64 trials:
+                             # scratch would sit inside every trial
+                             "warp_search_kernel"),
             "wrmf_split.hip": ("split_count_wave_kernel", "split_count_team_kernel", "split_write_wave_kernel", "split_write_team_kernel")}
 RESOURCE_FLAG = "-Rpass-analysis=kernel-resource-usage"
 

@@ -24,6 +24,9 @@
 // update_items = false skips the keys of 1, and 4 and 5.  No float atomics, no host synchronisation between the steps of a
 // call, every grid sized by the step's slot count or the item count with early exit, every loop bounded by the data sizes.
 // The file is built with contraction off: every product, sum, quotient and root is its own rounded float64 operation.
+//
+// WARP (rsparse_amd/warp.py is its definition) replaces 1 and 2 by one launch, warp_search_kernel: per slot up to
+// max_trials dependent draw-and-score trials that stop at the first candidate inside the margin; 3 - 6 run behind it unchanged.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
@@ -42,6 +45,7 @@ constexpr int kBprThreads = 256;
 constexpr int kBprLanes = 16;                          // lanes of a group: the 16 partial sums of the definition's dot product
 constexpr int kBprGroups = kBprThreads / kBprLanes;    // groups per workgroup
 constexpr int kBprChunk = RSPARSE_HIP_BPR_CHUNK;
+static_assert(kWarpMaxTrials == RSPARSE_HIP_WARP_MAX_TRIALS && kWarpMaxTrials <= kBprThreads, "the weights are staged by one pass of a workgroup");
 
 struct BprStep {
   const int32_t* p;
@@ -156,6 +160,148 @@ __global__ __launch_bounds__(kBprThreads) void bpr_z_kernel(const int32_t* __res
     if (bv) atomicAdd(counts, (unsigned long long)__popcll(bv));
     if (bc) atomicAdd(counts + 1, (unsigned long long)__popcll(bc));
   }
+}
+
+// WARP's search: steps 1 and 2 in one launch.  A 16-lane group owns a slot (four slots per wave) and keeps U[u] and V[i] in
+// registers, lane l the coordinates l + 16 q, so that the 16 lanes ARE the 16 partial sums of the definition's dot product.
+// Trials are drawn lazily in rounds of 16: in round r lane l draws trial t = 16 r + l + 1 (one Philox call per lane: call t >> 2,
+// word t & 3) and bisects the row for membership; the group's 16 bits of the wave's ballot are the admissible trials of the
+// round.  The group walks them in ascending t with the row of the NEXT admissible candidate already requested while the current
+// one is multiplied and halved, and stops at the first d <= margin.  Every loop is wave-uniform (a group that is done idles with
+// an empty mask: the ballots, the shuffles and the barrier need it) and bounded by max_trials and the row length.  The four
+// counts are added in LDS per wave and leave as one integer atomic per counter and workgroup.
+template <class T, int R16>
+__device__ __forceinline__ void warp_row(const T* __restrict__ row, int rank, int lane, T (&out)[R16]) {
+#pragma unroll
+  for (int q = 0; q < R16; q++) {
+    const int c = lane + kBprLanes * q;
+    if (c < rank) out[q] = row[c];
+  }
+}
+
+template <class T, int R16>
+__global__ __launch_bounds__(kBprThreads) void warp_search_kernel(BprStep a, WarpSearch w, int rank, const T* __restrict__ U,
+                                                                  const T* __restrict__ V, int32_t* __restrict__ tu,
+                                                                  int32_t* __restrict__ ti, int32_t* __restrict__ tj,
+                                                                  int32_t* __restrict__ tt, double* __restrict__ z,
+                                                                  uint32_t* __restrict__ keys, uint32_t* __restrict__ pay,
+                                                                  unsigned long long* __restrict__ counts) {
+  __shared__ double s_w[kWarpMaxTrials];
+  __shared__ unsigned s_cnt[4];
+  if (threadIdx.x < kWarpMaxTrials) s_w[threadIdx.x] = (int)threadIdx.x < w.max_trials ? w.weights[threadIdx.x] : 0.0;
+  if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0u;
+  __syncthreads();
+  const int k = blockIdx.x * kBprGroups + (threadIdx.x >> 4), lane = threadIdx.x & 15;
+  const int shift = threadIdx.x & 48;   // where the group's 16 bits stand in the wave's ballot
+  const bool has = k < a.cnt;
+  int u = 0, b = 0, L = 0, pos = 0;
+  unsigned q0 = 0, g = 0;
+  T ur[R16], vi[R16], cur[R16], nxt[R16];
+#pragma unroll
+  for (int q = 0; q < R16; q++) ur[q] = vi[q] = cur[q] = nxt[q] = (T)0;
+  if (has) {
+    const int64_t p = (int64_t)a.step + (int64_t)k * a.n_steps;
+    int lo = 0, hi = a.n_rows;   // p[lo] <= p < p[hi]
+    while (hi - lo > 1) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if ((int64_t)a.p[mid] <= p) lo = mid; else hi = mid;
+    }
+    u = lo; b = a.p[u]; L = a.p[u + 1] - b;
+    q0 = (unsigned)(p - b);
+    g = (unsigned)((u64)a.row0 + (a.mode == 0 ? (u64)u : 0ull));
+    unsigned o[4];
+    philox4x32_10(q0, g, 7u, a.c3, a.k0, a.k1, o);
+    pos = a.j[b + (int)(((u64)o[0] * (u64)(unsigned)L) >> 32)];
+    warp_row<T, R16>(U + (size_t)u * rank, rank, lane, ur);
+    warp_row<T, R16>(V + (size_t)pos * rank, rank, lane, vi);
+  }
+  bool done = false, seen = false, correct = false;   // (the same in the 16 lanes of a group)
+  int jn = -1, tk = 0;
+  double dk = 0.0;
+  unsigned scored = 0u;                               // (the same in the 64 lanes of a wave)
+  const int n_rounds = (w.max_trials + kBprLanes - 1) / kBprLanes;
+  for (int r = 0; r < n_rounds; r++) {
+    const bool active = has && !done;
+    if (!__any(active)) break;
+    const int t = kBprLanes * r + lane + 1;
+    int cand = 0;
+    bool admissible = false;
+    if (active && t <= w.max_trials) {
+      unsigned o[4];
+      philox4x32_10(q0, g, 7u + 256u * (unsigned)(t >> 2), a.c3, a.k0, a.k1, o);
+      const int wi = t & 3;
+      const unsigned word = wi == 0 ? o[0] : (wi == 1 ? o[1] : (wi == 2 ? o[2] : o[3]));
+      cand = (int)(((u64)word * (u64)(unsigned)a.n_items) >> 32);
+      int l = 0, h = L;   // the first entry of the row that is >= cand
+      while (l < h) {
+        const int mid = l + ((h - l) >> 1);
+        if (a.j[b + mid] < cand) l = mid + 1; else h = mid;
+      }
+      admissible = !(l < L && a.j[b + l] == cand);
+    }
+    unsigned mask = (unsigned)(__ballot(admissible) >> shift) & 0xffffu;
+    bool live = mask != 0u;
+    int lcur = live ? __ffs(mask) - 1 : 0;
+    int ccur = __shfl(cand, lcur, kBprLanes);
+    if (live) warp_row<T, R16>(V + (size_t)ccur * rank, rank, lane, cur);
+    u64 lb;
+    while ((lb = __ballot(live)) != 0ull) {
+      scored += (unsigned)__popcll(lb) >> 4;
+      const unsigned rest = mask & (mask - 1u);
+      const bool more = live && rest != 0u;
+      const int lnext = more ? __ffs(rest) - 1 : 0;
+      const int cnext = __shfl(cand, lnext, kBprLanes);
+      if (more) warp_row<T, R16>(V + (size_t)cnext * rank, rank, lane, nxt);   // in flight during the products and the halving
+      double part = 0.0;
+#pragma unroll
+      for (int q = 0; q < R16; q++) {
+        if (lane + kBprLanes * q < rank) {
+          const double diff = (double)vi[q] - (double)cur[q];
+          part = part + (double)ur[q] * diff;
+        }
+      }
+      const double d = bpr_reduce16(part);
+      if (live) {
+        if (!seen) {
+          seen = true;
+          correct = d > 0.0;
+        }
+        if (d <= w.margin) {
+          done = true;
+          jn = ccur;
+          tk = kBprLanes * r + lcur + 1;
+          dk = d;
+        }
+      }
+      mask = rest; lcur = lnext; ccur = cnext;
+#pragma unroll
+      for (int q = 0; q < R16; q++) cur[q] = nxt[q];
+      live = !done && mask != 0u;
+    }
+  }
+  const bool lead = has && lane == 0;
+  const u64 bv = __ballot(lead && done), bl = __ballot(lead && seen), bc = __ballot(lead && correct);
+  if ((threadIdx.x & 63) == 0) {
+    if (bv) atomicAdd(&s_cnt[0], (unsigned)__popcll(bv));
+    if (bl) atomicAdd(&s_cnt[1], (unsigned)__popcll(bl));
+    if (bc) atomicAdd(&s_cnt[2], (unsigned)__popcll(bc));
+    if (scored) atomicAdd(&s_cnt[3], scored);
+  }
+  if (lead) {
+    tu[k] = u;
+    ti[k] = pos;
+    tj[k] = jn;
+    if (tt) tt[k] = tk;
+    z[k] = done ? s_w[tk - 1] / (1.0 + bpr_exp(dk)) : 0.0;
+    if (keys) {
+      keys[2 * (size_t)k] = done ? (uint32_t)pos : (uint32_t)a.n_items;
+      keys[2 * (size_t)k + 1] = done ? (uint32_t)jn : (uint32_t)a.n_items;
+      pay[2 * (size_t)k] = 2u * (uint32_t)k;
+      pay[2 * (size_t)k + 1] = 2u * (uint32_t)k + 1u;
+    }
+  }
+  __syncthreads();
+  if (counts && threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(counts + threadIdx.x, (unsigned long long)s_cnt[threadIdx.x]);
 }
 
 // The update of a destination row with `count` >= 1 contributions whose total the group holds (lane l: the coordinates
@@ -368,7 +514,7 @@ inline BprStep bpr_step_of(const BprRun& r, int epoch, int step) {
 }
 
 template <class T, int R16>
-hipError_t bpr_run(const BprRun& r, int epoch0, int n_epochs, int only_step, T* U, T* V, double* aU, double* aV,
+hipError_t bpr_run(const BprRun& r, const WarpSearch* w, int epoch0, int n_epochs, int only_step, T* U, T* V, double* aU, double* aV,
                    unsigned long long* counts, hipStream_t s) {
   hipError_t err;
   const int cmax = bpr_cnt(r.nnz, only_step < 0 ? 0 : only_step, r.n_steps), rank = r.rank, ni = r.n_items;
@@ -416,10 +562,17 @@ hipError_t bpr_run(const BprRun& r, int epoch0, int n_epochs, int only_step, T* 
       if (a.cnt <= 0) continue;
       const int cnt = a.cnt;
       const dim3 per_k = bpr_grid(cnt, kBprThreads), per_group = bpr_grid(cnt, kBprGroups);
-      hipLaunchKernelGGL(bpr_sample_kernel, per_k, block, 0, s, a, tu.as<int32_t>(), ti.as<int32_t>(), tj.as<int32_t>(),
-                         r.update_items ? keys.as<uint32_t>() : (uint32_t*)nullptr, r.update_items ? pay.as<uint32_t>() : (uint32_t*)nullptr);
-      hipLaunchKernelGGL((bpr_z_kernel<T>), per_group, block, 0, s, (const int32_t*)tu.as<int32_t>(), (const int32_t*)ti.as<int32_t>(),
-                         (const int32_t*)tj.as<int32_t>(), cnt, rank, (const T*)U, (const T*)V, z.as<double>(), counts + 2 * (size_t)e);
+      if (w) {   // WARP: the search writes what the sample and score kernels write
+        hipLaunchKernelGGL((warp_search_kernel<T, R16>), per_group, block, 0, s, a, *w, rank, (const T*)U, (const T*)V, tu.as<int32_t>(),
+                           ti.as<int32_t>(), tj.as<int32_t>(), (int32_t*)nullptr, z.as<double>(),
+                           r.update_items ? keys.as<uint32_t>() : (uint32_t*)nullptr, r.update_items ? pay.as<uint32_t>() : (uint32_t*)nullptr,
+                           counts + 4 * (size_t)e);
+      } else {
+        hipLaunchKernelGGL(bpr_sample_kernel, per_k, block, 0, s, a, tu.as<int32_t>(), ti.as<int32_t>(), tj.as<int32_t>(),
+                           r.update_items ? keys.as<uint32_t>() : (uint32_t*)nullptr, r.update_items ? pay.as<uint32_t>() : (uint32_t*)nullptr);
+        hipLaunchKernelGGL((bpr_z_kernel<T>), per_group, block, 0, s, (const int32_t*)tu.as<int32_t>(), (const int32_t*)ti.as<int32_t>(),
+                           (const int32_t*)tj.as<int32_t>(), cnt, rank, (const T*)U, (const T*)V, z.as<double>(), counts + 2 * (size_t)e);
+      }
       hipLaunchKernelGGL((bpr_users_kernel<T, R16>), per_group, block, 0, s, (const int32_t*)tu.as<int32_t>(),
                          (const int32_t*)ti.as<int32_t>(), (const int32_t*)tj.as<int32_t>(), (const double*)z.as<double>(), cnt, rank,
                          (const T*)U, (const T*)V, (const double*)aU, r.lr, r.lambda, by_user, stage.as<T>(), stage_a.as<double>(),
@@ -463,19 +616,62 @@ hipError_t launch_bpr_triples(const BprRun& r, int epoch, int step, int32_t* tu,
   return hipGetLastError();
 }
 
+namespace {
+template <class T>
+hipError_t bpr_run_any(const BprRun& r, const WarpSearch* w, int epoch0, int n_epochs, int only_step, T* U, T* V, double* aU, double* aV,
+                       unsigned long long* counts, hipStream_t s) {
+  const int r16 = (r.rank + kBprLanes - 1) / kBprLanes;
+  if (r16 <= 1) return bpr_run<T, 1>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
+  if (r16 <= 2) return bpr_run<T, 2>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
+  if (r16 <= 4) return bpr_run<T, 4>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
+  if (r16 <= 8) return bpr_run<T, 8>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
+  return bpr_run<T, 16>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
+}
+
+template <class T, int R16>
+void warp_search(const BprStep& a, const WarpSearch& w, int rank, const T* U, const T* V, int32_t* tu, int32_t* ti, int32_t* tj,
+                 int32_t* tt, double* z, hipStream_t s) {
+  hipLaunchKernelGGL((warp_search_kernel<T, R16>), bpr_grid(a.cnt, kBprGroups), dim3(kBprThreads), 0, s, a, w, rank, U, V, tu, ti, tj, tt,
+                     z, (uint32_t*)nullptr, (uint32_t*)nullptr, (unsigned long long*)nullptr);
+}
+}  // namespace
+
 template <class T>
 hipError_t launch_bpr_run(const BprRun& r, int epoch0, int n_epochs, int only_step, T* U, T* V, double* aU, double* aV,
                           unsigned long long* counts, hipStream_t s) {
-  const int r16 = (r.rank + kBprLanes - 1) / kBprLanes;
-  if (r16 <= 1) return bpr_run<T, 1>(r, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
-  if (r16 <= 2) return bpr_run<T, 2>(r, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
-  if (r16 <= 4) return bpr_run<T, 4>(r, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
-  if (r16 <= 8) return bpr_run<T, 8>(r, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
-  return bpr_run<T, 16>(r, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
+  return bpr_run_any<T>(r, nullptr, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
 }
 template hipError_t launch_bpr_run<float>(const BprRun&, int, int, int, float*, float*, double*, double*, unsigned long long*, hipStream_t);
 template hipError_t launch_bpr_run<double>(const BprRun&, int, int, int, double*, double*, double*, double*, unsigned long long*,
                                            hipStream_t);
+
+template <class T>
+hipError_t launch_warp_run(const BprRun& r, const WarpSearch& w, int epoch0, int n_epochs, int only_step, T* U, T* V, double* aU,
+                           double* aV, unsigned long long* counts, hipStream_t s) {
+  return bpr_run_any<T>(r, &w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
+}
+template hipError_t launch_warp_run<float>(const BprRun&, const WarpSearch&, int, int, int, float*, float*, double*, double*,
+                                           unsigned long long*, hipStream_t);
+template hipError_t launch_warp_run<double>(const BprRun&, const WarpSearch&, int, int, int, double*, double*, double*, double*,
+                                            unsigned long long*, hipStream_t);
+
+template <class T>
+hipError_t launch_warp_triples(const BprRun& r, const WarpSearch& w, int epoch, int step, const T* U, const T* V, int32_t* tu, int32_t* ti,
+                               int32_t* tj, int32_t* tt, double* z, hipStream_t s) {
+  const BprStep a = bpr_step_of(r, epoch, step);
+  if (a.cnt <= 0) return hipSuccess;
+  const int r16 = (r.rank + kBprLanes - 1) / kBprLanes;
+  if (r16 <= 1) warp_search<T, 1>(a, w, r.rank, U, V, tu, ti, tj, tt, z, s);
+  else if (r16 <= 2) warp_search<T, 2>(a, w, r.rank, U, V, tu, ti, tj, tt, z, s);
+  else if (r16 <= 4) warp_search<T, 4>(a, w, r.rank, U, V, tu, ti, tj, tt, z, s);
+  else if (r16 <= 8) warp_search<T, 8>(a, w, r.rank, U, V, tu, ti, tj, tt, z, s);
+  else warp_search<T, 16>(a, w, r.rank, U, V, tu, ti, tj, tt, z, s);
+  return hipGetLastError();
+}
+template hipError_t launch_warp_triples<float>(const BprRun&, const WarpSearch&, int, int, const float*, const float*, int32_t*, int32_t*,
+                                               int32_t*, int32_t*, double*, hipStream_t);
+template hipError_t launch_warp_triples<double>(const BprRun&, const WarpSearch&, int, int, const double*, const double*, int32_t*,
+                                                int32_t*, int32_t*, int32_t*, double*, hipStream_t);
 
 #undef RSP_TRY
 

@@ -1790,7 +1790,8 @@ int rsparse_hip_init_factors_device(uint64_t seed, int stream, int64_t row0, int
 
 extern "C++" {
 namespace {
-// BPR (wrmf_bpr.hip), both precisions; the host form rsparse_hip_bpr_fit: wrmf_capi_host.cpp
+// BPR (wrmf_bpr.hip), both precisions; the host form rsparse_hip_bpr_fit: wrmf_capi_host.cpp.  w: WARP's search in the place of
+// BPR's sample and score kernels, with four counts per epoch instead of two
 BprRun bpr_run_of(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0, uint64_t seed, int mode,
                   int n_steps, int rank, double lr, double lambda, int update_items) {
   BprRun r;
@@ -1802,24 +1803,25 @@ BprRun bpr_run_of(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_item
 template <class T>
 int bpr_step_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0, uint64_t seed, int mode,
                     int epoch, int step, int n_steps, int rank, double lr, double lambda, int update_items, T* d_U, T* d_V,
-                    double* d_aU, double* d_aV, int64_t* d_counts, void* stream, int max_rank) {
+                    double* d_aU, double* d_aV, int64_t* d_counts, void* stream, int max_rank, const WarpSearch* w = nullptr) {
   int rc = bpr_args(!d_p || !d_j || !d_U || !d_V || !d_aU || !d_aV || !d_counts, n_rows, n_items, nnz, row0, mode, epoch, 1, n_steps,
                     "n_steps", rank, max_rank, lr, lambda);
   if (rc) return rc;
   if (step < 0 || step >= n_steps) return fail(RSPARSE_HIP_ERR_INVALID, "step outside [0, n_steps)");
   if ((rc = bpr_step_size(nnz, n_steps, update_items))) return rc;
   if (n_rows == 0 || nnz == 0) return RSPARSE_HIP_OK;
-  hipError_t e = launch_bpr_run<T>(bpr_run_of(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, n_steps, rank, lr, lambda, update_items),
-                                   epoch, 1, step, d_U, d_V, d_aU, d_aV, reinterpret_cast<unsigned long long*>(d_counts),
-                                   (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "launch_bpr_run");
+  const BprRun r = bpr_run_of(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, n_steps, rank, lr, lambda, update_items);
+  unsigned long long* counts = reinterpret_cast<unsigned long long*>(d_counts);
+  hipError_t e = w ? launch_warp_run<T>(r, *w, epoch, 1, step, d_U, d_V, d_aU, d_aV, counts, (hipStream_t)stream)
+                   : launch_bpr_run<T>(r, epoch, 1, step, d_U, d_V, d_aU, d_aV, counts, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, w ? "launch_warp_run" : "launch_bpr_run");
   return RSPARSE_HIP_OK;
 }
 
 template <class T>
 int bpr_epochs_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0, uint64_t seed, int mode,
                       int epoch0, int n_epochs, int batch, int rank, double lr, double lambda, int update_items, T* d_U, T* d_V,
-                      double* d_aU, double* d_aV, int64_t* d_counts, void* stream, int max_rank) {
+                      double* d_aU, double* d_aV, int64_t* d_counts, void* stream, int max_rank, const WarpSearch* w = nullptr) {
   int rc = bpr_args(!d_p || !d_j || !d_U || !d_V || !d_aU || !d_aV || !d_counts, n_rows, n_items, nnz, row0, mode, epoch0, n_epochs,
                     batch, "batch", rank, max_rank, lr, lambda);
   if (rc) return rc;
@@ -1827,11 +1829,13 @@ int bpr_epochs_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_
   if ((rc = bpr_step_size(nnz, n_steps, update_items))) return rc;
   if (n_rows == 0 || n_epochs == 0) return RSPARSE_HIP_OK;
   hipStream_t s = (hipStream_t)stream;
-  HIP_TRY(hipMemsetAsync(d_counts, 0, 2 * (size_t)n_epochs * sizeof(int64_t), s));
+  HIP_TRY(hipMemsetAsync(d_counts, 0, (w ? 4 : 2) * (size_t)n_epochs * sizeof(int64_t), s));
   if (nnz == 0) return RSPARSE_HIP_OK;
-  hipError_t e = launch_bpr_run<T>(bpr_run_of(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, n_steps, rank, lr, lambda, update_items),
-                                   epoch0, n_epochs, -1, d_U, d_V, d_aU, d_aV, reinterpret_cast<unsigned long long*>(d_counts), s);
-  if (e != hipSuccess) return hip_fail(e, "launch_bpr_run");
+  const BprRun r = bpr_run_of(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, n_steps, rank, lr, lambda, update_items);
+  unsigned long long* counts = reinterpret_cast<unsigned long long*>(d_counts);
+  hipError_t e = w ? launch_warp_run<T>(r, *w, epoch0, n_epochs, -1, d_U, d_V, d_aU, d_aV, counts, s)
+                   : launch_bpr_run<T>(r, epoch0, n_epochs, -1, d_U, d_V, d_aU, d_aV, counts, s);
+  if (e != hipSuccess) return hip_fail(e, w ? "launch_warp_run" : "launch_bpr_run");
   return RSPARSE_HIP_OK;
 }
 }  // namespace
@@ -1882,6 +1886,61 @@ int rsparse_hip_bpr_epochs_f64_device(const int32_t* d_p, const int32_t* d_j, in
   return bpr_epochs_device<double>(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, epoch0, n_epochs, batch, rank, learning_rate,
                                    lambda, update_items, d_U, d_V, d_aU, d_aV, d_counts, stream, RSPARSE_HIP_MAX_RANK_F64);
 }
+
+extern "C++" {
+namespace {
+// WARP: the search alone
+template <class T>
+int warp_triples_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0, uint64_t seed,
+                        int mode, int epoch, int step, int n_steps, int max_trials, double margin, const double* weights, int rank,
+                        const T* d_U, const T* d_V, int32_t* d_u, int32_t* d_i, int32_t* d_neg, int32_t* d_t, double* d_z, void* stream,
+                        int max_rank) {
+  int rc = bpr_args(!d_p || !d_j || !d_U || !d_V || !d_u || !d_i || !d_neg || !d_t || !d_z, n_rows, n_items, nnz, row0, mode, epoch, 1,
+                    n_steps, "n_steps", rank, max_rank, 0.0, 0.0);
+  if (rc) return rc;
+  if (step < 0 || step >= n_steps) return fail(RSPARSE_HIP_ERR_INVALID, "step outside [0, n_steps)");
+  WarpSearch w;
+  if ((rc = warp_search_of(max_trials, margin, weights, w))) return rc;
+  if (n_rows == 0 || nnz == 0) return RSPARSE_HIP_OK;
+  hipError_t e = launch_warp_triples<T>(bpr_run_of(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, n_steps, rank, 0.0, 0.0, 0), w, epoch,
+                                        step, d_U, d_V, d_u, d_i, d_neg, d_t, d_z, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_warp_triples");
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int rsparse_hip_warp_triples_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                    uint64_t seed, int mode, int epoch, int step, int n_steps, int max_trials, double margin,
+                                    const double* weights, int rank, const float* d_U, const float* d_V, int32_t* d_u, int32_t* d_i,
+                                    int32_t* d_neg, int32_t* d_t, double* d_z, void* stream) {
+  return warp_triples_device<float>(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, epoch, step, n_steps, max_trials, margin, weights,
+                                    rank, d_U, d_V, d_u, d_i, d_neg, d_t, d_z, stream, RSPARSE_HIP_MAX_RANK);
+}
+
+int rsparse_hip_warp_triples_f64_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0,
+                                        uint64_t seed, int mode, int epoch, int step, int n_steps, int max_trials, double margin,
+                                        const double* weights, int rank, const double* d_U, const double* d_V, int32_t* d_u,
+                                        int32_t* d_i, int32_t* d_neg, int32_t* d_t, double* d_z, void* stream) {
+  return warp_triples_device<double>(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, epoch, step, n_steps, max_trials, margin, weights,
+                                     rank, d_U, d_V, d_u, d_i, d_neg, d_t, d_z, stream, RSPARSE_HIP_MAX_RANK_F64);
+}
+
+// (the search is checked first: a refusal of it must not depend on what the BPR checks would say of a NULL table)
+#define RSPARSE_WARP_ENTRY(NAME, T, BODY, A, B, C, MAXRANK)                                                                           \
+  int NAME(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0, uint64_t seed, int mode, int A, \
+           int B, int C, int max_trials, double margin, const double* weights, int rank, double learning_rate, double lambda,          \
+           int update_items, T* d_U, T* d_V, double* d_aU, double* d_aV, int64_t* d_counts, void* stream) {                            \
+    WarpSearch w;                                                                                                                      \
+    if (int rc = warp_search_of(max_trials, margin, weights, w)) return rc;                                                            \
+    return BODY<T>(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, A, B, C, rank, learning_rate, lambda, update_items, d_U, d_V,     \
+                   d_aU, d_aV, d_counts, stream, MAXRANK, &w);                                                                         \
+  }
+RSPARSE_WARP_ENTRY(rsparse_hip_warp_step_device, float, bpr_step_device, epoch, step, n_steps, RSPARSE_HIP_MAX_RANK)
+RSPARSE_WARP_ENTRY(rsparse_hip_warp_step_f64_device, double, bpr_step_device, epoch, step, n_steps, RSPARSE_HIP_MAX_RANK_F64)
+RSPARSE_WARP_ENTRY(rsparse_hip_warp_epochs_device, float, bpr_epochs_device, epoch0, n_epochs, batch, RSPARSE_HIP_MAX_RANK)
+RSPARSE_WARP_ENTRY(rsparse_hip_warp_epochs_f64_device, double, bpr_epochs_device, epoch0, n_epochs, batch, RSPARSE_HIP_MAX_RANK_F64)
+#undef RSPARSE_WARP_ENTRY
 
 namespace {
 // the device form of both samplers: d_cum == nullptr is the uniform stream, otherwise the weighted one under that prefix

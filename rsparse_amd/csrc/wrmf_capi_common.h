@@ -474,6 +474,22 @@ inline int bpr_step_size(int64_t nnz, int n_steps, int update_items) {
   return RSPARSE_HIP_OK;
 }
 
+// WARP: what its entries refuse beyond bpr_args, and the search as the kernel takes it
+inline int warp_search_of(int max_trials, double margin, const double* weights, WarpSearch& w) {
+  const auto ok = [](double v) { return v >= 0.0 && v <= 1.7976931348623157e308; };   // (NaN fails both)
+  if (max_trials < 1 || max_trials > RSPARSE_HIP_WARP_MAX_TRIALS)
+    return fail(RSPARSE_HIP_ERR_INVALID, "max_trials outside [1, 64] (RSPARSE_HIP_WARP_MAX_TRIALS)");
+  if (!(margin >= -1.7976931348623157e308 && margin <= 1.7976931348623157e308)) return fail(RSPARSE_HIP_ERR_INVALID, "margin is not finite");
+  if (!weights) return fail(RSPARSE_HIP_ERR_INVALID, "weights is NULL");
+  w.max_trials = max_trials;
+  w.margin = margin;
+  for (int t = 0; t < RSPARSE_HIP_WARP_MAX_TRIALS; t++) {
+    w.weights[t] = t < max_trials ? weights[t] : 0.0;
+    if (!ok(w.weights[t])) return fail(RSPARSE_HIP_ERR_INVALID, "a weights entry is negative or not finite");
+  }
+  return RSPARSE_HIP_OK;
+}
+
 // rsparse_hip_score_pairs_device / _f64_device (kernels: wrmf_score.hip).  Handed in:
 //   int workspace(size_t n, double*& buf)    makes sure of n doubles of the side's grow-only workspace
 // which is only asked for the sums without the scores: the scores then live there, and their count, p[n_rows], has to be

@@ -519,6 +519,22 @@ template <class T>
 hipError_t launch_bpr_run(const BprRun& r, int epoch0, int n_epochs, int only_step, T* U, T* V, double* aU, double* aV,
                           unsigned long long* counts, hipStream_t s);
 
+// WARP (wrmf_bpr.hip; defined in rsparse_wrmf_hip.h): a BPR run whose triples come from the search.  triples: the search alone on
+// the factors U, V (ld = r.rank) -> (u, i, j, t, z) of one step.  run: as launch_bpr_run with FOUR counts per epoch, ADDED to:
+// counts[4 e ..] = n_valid, n_looked, n_correct, n_scored.  The search travels to the kernel by value.
+constexpr int kWarpMaxTrials = 64;   // RSPARSE_HIP_WARP_MAX_TRIALS
+struct WarpSearch {
+  int max_trials;
+  double margin;
+  double weights[kWarpMaxTrials];
+};
+template <class T>
+hipError_t launch_warp_triples(const BprRun& r, const WarpSearch& w, int epoch, int step, const T* U, const T* V, int32_t* tu, int32_t* ti,
+                               int32_t* tj, int32_t* tt, double* z, hipStream_t s);
+template <class T>
+hipError_t launch_warp_run(const BprRun& r, const WarpSearch& w, int epoch0, int n_epochs, int only_step, T* U, T* V, double* aU,
+                           double* aV, unsigned long long* counts, hipStream_t s);
+
 // top-k within per-user candidate lists (wrmf_candidates.hip), T = float or double, 1 <= topk <= kTopLargeMax: for every row of
 // the CSR pattern (cand_p: n_users + 1 slots, absolute positions into cand_j; p0 = cand_p[0], nnz = cand_p[n_users] - p0, read by
 // the caller; columns ascending and unique within a row) the topk best admissible candidates by launch_score_pairs' scores

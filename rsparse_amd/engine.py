@@ -1005,6 +1005,59 @@ class HipBackend:
         self._bpr_call("epochs", p, j, n_items, nnz, row0, seed, mode, epoch0, n_epochs, batch, U, V, aU, aV, lr, lam, update_items, counts)
         return counts[:int(n_epochs)]
 
+    @staticmethod
+    def _warp_search(max_trials, margin, weights):
+        """the search as the C ABI takes it: (max_trials, margin, the weights' address), and the array that must outlive the call"""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        assert w.ndim == 1 and w.size == int(max_trials)
+        return (int(max_trials), float(margin), w.ctypes.data), w
+
+    def warp_triples(self, p, j, n_items, nnz, row0, seed, mode, epoch, step, n_steps, max_trials, margin, weights, U, V):
+        """WARP's search alone for one step, from the factors U, V (rsparse_amd.warp.warp_triples is the definition) ->
+        (u, i, neg, t: int32; z: float64) on the device; neg = -1, t = 0, z = 0 for a void triple"""
+        assert p.dtype == torch.int32 and j.dtype == torch.int32 and U.dtype == V.dtype and U.dtype in (torch.float32, torch.float64)
+        assert U.is_cuda and U.is_contiguous() and V.is_contiguous() and U.shape[1] == V.shape[1] and V.shape[0] == int(n_items)
+        assert U.shape[0] == p.numel() - 1
+        cnt = max(0, -(-(int(nnz) - int(step)) // int(n_steps)))
+        out = torch.empty((4, max(cnt, 1)), dtype=torch.int32, device=self.device)
+        z = torch.empty(max(cnt, 1), dtype=torch.float64, device=self.device)
+        search, keep = self._warp_search(max_trials, margin, weights)
+        fn = getattr(self.lib, "rsparse_hip_warp_triples%s_device" % ("_f64" if U.dtype == torch.float64 else ""))
+        some = lambda t: t.data_ptr() if t.numel() else out.data_ptr()
+        _lib.check(fn(some(p), some(j), int(p.numel()) - 1, int(n_items), int(nnz), int(row0), int(seed), int(mode), int(epoch), int(step),
+                      int(n_steps), *search, int(U.shape[1]), some(U), some(V), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                      out[3].data_ptr(), z.data_ptr(), self._stream()))
+        return out[0, :cnt], out[1, :cnt], out[2, :cnt], out[3, :cnt], z[:cnt]
+
+    def _warp_call(self, name, p, j, n_items, nnz, row0, seed, mode, a, b, c, search, U, V, aU, aV, lr, lam, update_items, counts):
+        assert p.dtype == torch.int32 and j.dtype == torch.int32 and U.dtype == V.dtype and U.dtype in (torch.float32, torch.float64)
+        assert U.is_cuda and U.is_contiguous() and V.is_contiguous() and U.shape[1] == V.shape[1] and V.shape[0] == int(n_items)
+        assert aU.dtype == torch.float64 and aV.dtype == torch.float64 and aU.numel() == U.shape[0] and aV.numel() == V.shape[0]
+        assert U.shape[0] == p.numel() - 1 and aU.is_contiguous() and aV.is_contiguous()
+        search, keep = self._warp_search(*search)
+        fn = getattr(self.lib, "rsparse_hip_warp_%s%s_device" % (name, "_f64" if U.dtype == torch.float64 else ""))
+        some = lambda t: t.data_ptr() if t.numel() else counts.data_ptr()   # (an empty tensor has no address to pass)
+        _lib.check(fn(some(p), some(j), int(U.shape[0]), int(n_items), int(nnz), int(row0), int(seed), int(mode), int(a), int(b), int(c),
+                      *search, int(U.shape[1]), float(lr), float(lam), int(bool(update_items)), some(U), some(V), some(aU), some(aV),
+                      counts.data_ptr(), self._stream()))
+        return counts
+
+    def warp_step(self, p, j, n_items, nnz, row0, seed, mode, epoch, step, n_steps, max_trials, margin, weights, U, V, aU, aV, lr, lam,
+                  update_items=True):
+        """one WARP step in place, as `bpr_step` (rsparse_amd.warp.warp_step_reference is the definition) ->
+        (n_valid, n_looked, n_correct, n_scored): int64 on the device"""
+        counts = torch.zeros(4, dtype=torch.int64, device=self.device)
+        return self._warp_call("step", p, j, n_items, nnz, row0, seed, mode, epoch, step, n_steps, (max_trials, margin, weights), U, V, aU,
+                               aV, lr, lam, update_items, counts)
+
+    def warp_epochs(self, p, j, n_items, nnz, row0, seed, mode, epoch0, n_epochs, batch, max_trials, margin, weights, U, V, aU, aV, lr,
+                    lam, update_items=True):
+        """the WARP epochs [epoch0, epoch0 + n_epochs), as `bpr_epochs` -> (n_epochs, 4) int64 on the device"""
+        counts = torch.zeros((max(int(n_epochs), 1), 4), dtype=torch.int64, device=self.device)
+        self._warp_call("epochs", p, j, n_items, nnz, row0, seed, mode, epoch0, n_epochs, batch, (max_trials, margin, weights), U, V, aU,
+                        aV, lr, lam, update_items, counts)
+        return counts[:int(n_epochs)]
+
     def _knn_rows(self, xp, xj, neighbors, q, xv):
         """the operands the ItemKNN evaluation entries share with `knn_recommend`, as the C ABI takes them: -> (the leading
         arguments, `some`: the address of a tensor, or of xp for an empty one; the tensors that must outlive the call)"""

@@ -77,6 +77,12 @@ canonical CSR; slot p belongs to row u of L entries at position q = p - indptr[u
               all three in the row: the triple is VOID (-1) and takes no part in anything -- no input can make the sampler spin
 
 Integers only.  A triple depends on (seed, mode, epoch, g, q, the row, n_items) alone.  epoch < 2^31.
+
+`STREAM_WARP` is the eighth: the positive and up to 64 negative candidates per slot of the WARP fit (rsparse_amd/warp.py).  A slot
+makes several Philox CALLS: call c has counter (q, g, 7 + 256 c, epoch + 2^31 mode), q, g and the key as for `STREAM_BPR` -- the
+third word of every other stream is 0..6, so no call collides with one of them.  Word 0 of call 0 gives the positive as above;
+trial t = 1, 2, ... is word t & 3 of call t >> 2 and its candidate is (o n_items) >> 32.  Which trials are looked at depends on the
+model (the search stops at a violator); the words do not.
 """
 import numpy as np
 
@@ -86,6 +92,7 @@ STREAM_USERS, STREAM_ITEMS, STREAM_NEGATIVES = 0, 1, 2
 STREAM_SPLIT, STREAM_LEAVE_OUT = 3, 4
 STREAM_WEIGHTED_NEGATIVES = 5
 STREAM_BPR = 6
+STREAM_WARP = 7
 MAX_NEGATIVES = 8192   # RSPARSE_HIP_MAX_NEGATIVES
 _MASK = np.uint64(0xFFFFFFFF)
 _S32 = np.uint64(32)
