@@ -60,10 +60,12 @@ def __getattr__(name):
     if name in ("SLIM", "slim_columns_reference", "slim_weights_reference"):
         from . import slim
         return getattr(slim, name)
-    if name in ("BPR", "bpr_triples", "bpr_step_reference", "bpr_fit_reference"):
+    if name in ("BPR", "bpr_triples", "bpr_step_reference", "bpr_fit_reference", "compose_reference", "bpr_feat_step_reference",
+                "bpr_feat_fit_reference"):
         from . import bpr
         return getattr(bpr, name)
-    if name in ("WARP", "rank_weights", "warp_triples", "warp_step_reference", "warp_fit_reference"):
+    if name in ("WARP", "rank_weights", "warp_triples", "warp_step_reference", "warp_fit_reference", "warp_feat_step_reference",
+                "warp_feat_fit_reference"):
         from . import warp
         return getattr(warp, name)
     if name == "metrics":

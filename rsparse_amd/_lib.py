@@ -30,6 +30,8 @@ RANKS_BATCH = 1024  # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that th
 
 _c_int, _c_uint, _c_dbl, _c_i64, _c_u64 = ctypes.c_int, ctypes.c_uint, ctypes.c_double, ctypes.c_int64, ctypes.c_uint64
 _vp = ctypes.c_void_p
+_BPR_HEAD = [_vp, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_u64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_dbl, _c_dbl, _c_int]
+_FEAT_TAIL = [_vp] * 6 + [_c_int, _c_i64] + [_vp] * 7
 _WARP_HEAD = [_vp, _vp, _c_int, _c_int, _c_i64, _c_i64, _c_u64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_dbl, _vp, _c_int]
 
 # name -> (restype, argtypes); mirrors include/rsparse_wrmf_hip.h one to one
@@ -170,6 +172,12 @@ SIGNATURES = {
        for n in ("step", "epochs") for f in ("", "_f64")},
     "rsparse_hip_warp_fit": (_c_int, [_vp, _vp, _c_int, _c_int, _c_u64, _c_int, _c_int, _c_int, _c_dbl, _vp, _c_int, _c_dbl, _c_dbl, _vp, _vp,
                                       _vp, _vp, _vp]),
+    # item features: V = F H alone; then BPR's / WARP's leading arguments through update_items, F by item and by feature
+    # (fp, fj, fx, cp, ci, cx, n_feat, nnz_f), then U, H, V, aU, aH, counts, stream
+    **{"rsparse_hip_compose_rows%s_device" % f: (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_i64, _c_int, _vp, _vp, _vp]) for f in ("", "_f64")},
+    **{"rsparse_hip_bpr_feat_%s%s_device" % (n, f): (_c_int, _BPR_HEAD + _FEAT_TAIL) for n in ("step", "epochs") for f in ("", "_f64")},
+    **{"rsparse_hip_warp_feat_%s%s_device" % (n, f): (_c_int, _WARP_HEAD + [_c_dbl, _c_dbl, _c_int] + _FEAT_TAIL)
+       for n in ("step", "epochs") for f in ("", "_f64")},
     "rsparse_hip_top_candidates_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl, _vp,
                                                    _vp, _vp]),
     "rsparse_hip_top_candidates_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl,

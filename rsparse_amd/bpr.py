@@ -42,7 +42,26 @@ widened from the model's dtype; nothing is fused.
 neither reads the items for update nor writes them.  A fit starts from `rng.init_factors` (streams 0 and 1, scale 0.01) with
 a = 0; a fold-in from zero rows with a = 0 and runs `transform_iter` epochs of one step each.
 
+Item features (`fit_transform(x, item_features=F)`): an item's embedding is not a free row but F[i, :] H, a
+combination of the embeddings H (n_feat x rank) of the item's features, and every gradient goes through F to H -- the hybrid
+model of the modelled-on `RankMF` (LightFM), which gives an item nobody has interacted with an embedding from its metadata.
+F: n_items x n_feat, canonical CSR, finite values in the factors' dtype; aH: one float64 per feature, from 0.  One step:
+
+    compose     V[i, c] = the sum over the stored features f of row i, in ascending f, of F[i, f] * H[f, c], sequentially from
+                +0.0, rounded once into the dtype; an item without features has a zero row
+    triples, z_k, the user side: as above, from the snapshot (U, V)
+    item i      with c_i >= 1 contributions: G_i = its `total` above (before the regularisation term); V is not updated from it
+    feature f   its column of F (the items that carry f, ascending) is cut into chunks of CHUNK consecutive STORED POSITIONS;
+                within a chunk the items with c_i >= 1 contribute F[i, f] * G_i, summed sequentially from +0.0 (the others are
+                skipped); the chunk sums are added sequentially to a total that starts at +0.0; C_f = the sum of those c_i.
+                C_f >= 1: `update` with count = C_f, row = H[f], a = aH[f]; every other feature keeps its bits
+
+The cut by stored position is known from F alone.  With F the identity this is the definition above with H = V, bit for bit.
+The modelled-on solver hands every feature of an item the same gradient, whatever the feature's value (rankmf.cpp:254-265); here
+the gradient is scaled by F[i, f], the derivative of the composition.
+
   bpr_triples, bpr_exp, bpr_step_reference, bpr_fit_reference     the definition, in numpy
+  compose_reference, bpr_feat_step_reference, bpr_feat_fit_reference     the same through item features
   BPR                                                             the model: `WRMF`'s inference surface on these factors
 """
 import math
@@ -233,6 +252,110 @@ def bpr_fit_reference(indptr, indices, n_items, U, V, n_iter, seed, learning_rat
     return U, V, aU, aV, trace
 
 
+def canonical_features(item_features, n_items, dtype):
+    """item_features (anything scipy makes a matrix of, n_items rows) -> canonical CSR in `dtype`: duplicates summed, columns
+    ascending, explicit zeros kept out, values finite"""
+    F = sp.csr_matrix(item_features, dtype=np.float64)
+    if F.shape[0] != int(n_items) or F.shape[1] < 1:
+        raise ValueError("item_features must be n_items x n_feat with n_feat >= 1")
+    F = sp.csr_matrix(F.astype(dtype))
+    F.sum_duplicates()
+    F.eliminate_zeros()
+    F.sort_indices()
+    if not np.isfinite(F.data).all():
+        raise ValueError("item_features holds a value that is not finite in the factors' precision")
+    return F
+
+
+def compose_reference(F, H):
+    """V = F H of the definition: per item its stored features in ascending order, sequentially from +0.0, one rounding into
+    H's dtype.  F: canonical scipy CSR"""
+    H = np.asarray(H)
+    ip, idx, val = F.indptr.astype(np.int64), F.indices, F.data.astype(np.float64)
+    acc, length = np.zeros((F.shape[0], H.shape[1])), np.diff(ip)
+    for t in range(int(length.max()) if length.size else 0):
+        rows = np.flatnonzero(length > t)
+        acc[rows] = acc[rows] + val[ip[rows] + t][:, None] * H[idx[ip[rows] + t]].astype(np.float64)
+    return acc.astype(H.dtype)
+
+
+def _feature_sums(Fc, G, counts):
+    """the definition's per-feature sums: Fc = F as canonical CSC, G (n_items, rank) and counts (n_items,) the items' totals
+    and contribution counts -> (totals (n_feat, rank), C (n_feat,))"""
+    n_feat, rank = Fc.shape[1], G.shape[1]
+    cp, item, val = Fc.indptr.astype(np.int64), Fc.indices.astype(np.int64), Fc.data.astype(np.float64)
+    length = np.diff(cp)
+    col = np.repeat(np.arange(n_feat, dtype=np.int64), length)
+    pos = np.arange(item.size, dtype=np.int64) - cp[col]
+    live = counts[item] > 0
+    C = np.zeros(n_feat, dtype=np.int64)
+    np.add.at(C, col[live], counts[item[live]])
+    n_chunks = -(-length // CHUNK)
+    chunk0 = np.concatenate([[0], np.cumsum(n_chunks)])
+    slot, t = chunk0[col] + pos // CHUNK, pos % CHUNK
+    acc, totals = np.zeros((int(chunk0[-1]), rank)), np.zeros((n_feat, rank))
+    for tt in range(CHUNK):
+        sel = np.flatnonzero(live & (t == tt))
+        acc[slot[sel]] = acc[slot[sel]] + val[sel][:, None] * G[item[sel]]
+    slot_col = np.repeat(np.arange(n_feat, dtype=np.int64), n_chunks)
+    slot_m = np.arange(acc.shape[0], dtype=np.int64) - chunk0[slot_col]
+    for m in range(int(n_chunks.max()) if n_chunks.size else 0):
+        sel = np.flatnonzero(slot_m == m)
+        totals[slot_col[sel]] = totals[slot_col[sel]] + acc[sel]
+    return totals, C
+
+
+def feat_step_from_z(U, H, aU, aH, F, u, i, j, z, diff, learning_rate, lambda_):
+    """the rows, sums and updates of one step through the features F (canonical CSR) for the triples (u, i, j) (none void,
+    int64) with their z and diff = V[i] - V[j] of the composed V -> (U', H', aU', aH')"""
+    rank = U.shape[1]
+    tot_u, cnt_u = _ordered_sums(u, z[:, None] * diff, U.shape[0])
+    U2, aU2 = _apply(U, aU, tot_u, cnt_u, learning_rate, lambda_)
+    Uu = U[u].astype(np.float64)
+    dest = np.stack([i, j], axis=1).reshape(-1)
+    contrib = np.stack([z[:, None] * Uu, (-z)[:, None] * Uu], axis=1).reshape(-1, rank)
+    G, cnt_v = _ordered_sums(dest, contrib, F.shape[0])
+    Fc = sp.csc_matrix(F)
+    Fc.sort_indices()
+    tot_h, cnt_h = _feature_sums(Fc, G, cnt_v)
+    H2, aH2 = _apply(H, aH, tot_h, cnt_h, learning_rate, lambda_)
+    return U2, H2, aU2, aH2
+
+
+def bpr_feat_step_reference(U, H, aU, aH, F, tu, ti, tj, learning_rate, lambda_):
+    """One step of the definition through the item features F on the triples (tu, ti, tj) (in the order k; tj = -1: void) from
+    the snapshot (U, H) with the Adagrad states (aU, aH) -> (U', H', aU', aH', n_valid, n_correct); nothing is changed in place.
+    The gradient of a feature is scaled by F[i, f] (the modelled-on solver leaves the value out)."""
+    U, H = np.asarray(U), np.asarray(H)
+    aU, aH = np.asarray(aU, dtype=np.float64), np.asarray(aH, dtype=np.float64)
+    V = compose_reference(F, H)
+    keep = np.flatnonzero(np.asarray(tj) >= 0)
+    u, i, j = (np.asarray(t, dtype=np.int64)[keep] for t in (tu, ti, tj))
+    diff = V[i].astype(np.float64) - V[j].astype(np.float64)
+    d = sum16(U[u].astype(np.float64) * diff)
+    z = 1.0 / (1.0 + bpr_exp(d))
+    return feat_step_from_z(U, H, aU, aH, F, u, i, j, z, diff, learning_rate, lambda_) + (int(keep.size), int((d > 0).sum()))
+
+
+def bpr_feat_fit_reference(indptr, indices, F, U, H, n_iter, seed, learning_rate, lambda_, batch, aU=None, aH=None, epoch0=0):
+    """n_iter epochs of the definition through the item features F (canonical CSR, n_items x n_feat) from (U, H) ->
+    (U, H, aU, aH, trace), trace = [(n_valid, n_correct)] per epoch; the items are `compose_reference(F, H)`"""
+    ip = np.asarray(indptr, dtype=np.int64)
+    U, H = np.array(U), np.array(H)
+    aU = np.zeros(U.shape[0]) if aU is None else np.array(aU, dtype=np.float64)
+    aH = np.zeros(H.shape[0]) if aH is None else np.array(aH, dtype=np.float64)
+    n_steps = n_steps_of(ip[-1], batch)
+    trace = []
+    for e in range(epoch0, epoch0 + int(n_iter)):
+        nv = nc = 0
+        for s in range(n_steps):
+            t = bpr_triples(seed, 0, e, 0, ip, indices, F.shape[0], s, n_steps)
+            U, H, aU, aH, v, c = bpr_feat_step_reference(U, H, aU, aH, F, *t, learning_rate, lambda_)
+            nv, nc = nv + v, nc + c
+        trace.append((nv, nc))
+    return U, H, aU, aH, trace
+
+
 def _check_args(rank, learning_rate, lambda_, batch, transform_iter):
     for name, v in (("rank", rank), ("batch", batch), ("transform_iter", transform_iter)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
@@ -253,7 +376,10 @@ class BPR(WRMF):
     `bpr_epochs` (the CPU stand-in of the tests) runs the numpy definition.
     Fitted: `components` (rank x n_items), `user_adagrad` / `item_adagrad` (float64), `trace` = [(n_valid, n_correct)] per epoch
     (n_correct / n_valid is the AUC estimate the modelled-on solver prints), `seed`.  `transform` / `predict` / `evaluate` and the
-    rest of WRMF's surface fold the rows of x in with the items frozen; `explain` is not available."""
+    rest of WRMF's surface fold the rows of x in with the items frozen; `explain` is not available.
+    `fit_transform(x, item_features=F)` (F: scipy sparse, n_items x n_feat) fits the hybrid model of the module's docstring:
+    `components` is then the composed (F H)', `feature_embeddings` / `feature_adagrad` hold H and aH (`item_adagrad` is None);
+    `compose_items(F_new)` gives the embeddings of unseen items and `with_items(F_new)` a model whose catalogue they are."""
 
     def __init__(self, rank=10, learning_rate=0.1, lambda_=0.01, batch=4096, transform_iter=50, precision="float", rng=None,
                  device=None, backend=None):
@@ -266,7 +392,8 @@ class BPR(WRMF):
         self.seed = None
         self.trace = []
         self.user_adagrad = self.item_adagrad = None
-        self._aV = None
+        self.feature_embeddings = self.feature_adagrad = None
+        self._aV = self._H = None
 
     def _epochs(self, m, U, V, aU, aV, n_iter, mode, update_items):
         """n_iter epochs on the canonical rows m, in place where the backend has the kernels -> (U, V, aU, aV, trace)"""
@@ -280,8 +407,74 @@ class BPR(WRMF):
                                update_items)
         return U, V, aU, aV, [(int(v), int(c)) for v, c in counts.cpu().numpy()]
 
-    def fit_transform(self, x, n_iter=10):
-        """n_iter epochs over the users x items matrix x -> the user factors (n_users x rank)"""
+    def _epochs_feat(self, m, F, U, H, aU, aH, n_iter):
+        """n_iter epochs of a fit through the canonical item features F -> (U, H, aU, aH, V = F H, trace)"""
+        be = self._backend()
+        if not hasattr(be, "bpr_feat_epochs"):
+            out = bpr_feat_fit_reference(m.indptr, m.indices, F, U.numpy(), H.numpy(), n_iter, self.seed, self._lr, self._lambda, self._batch)
+            U, H, aU, aH = (torch.from_numpy(np.ascontiguousarray(t)) for t in out[:4])
+            return U, H, aU, aH, torch.from_numpy(compose_reference(F, H.numpy())), out[4]
+        p, j = be.to_device(m.indptr, torch.int32), be.to_device(m.indices, torch.int32)
+        feat = be.item_features(F, H.dtype)
+        counts, _ = be.bpr_feat_epochs(p, j, m.nnz, 0, self.seed, 0, 0, n_iter, self._batch, feat, U, H, aU, aH, self._lr, self._lambda)
+        return U, H, aU, aH, be.compose_rows(feat, H), [(int(v), int(c)) for v, c in counts.cpu().numpy()]
+
+    def _fit_features(self, m, item_features, n_iter):
+        n_user, n_item = m.shape
+        be, k, tdt = self._backend(), self._rank, self._dev_t()
+        F = canonical_features(item_features, n_item, self._dev_np())
+        if hasattr(be, "init_factors"):
+            U, H = be.init_factors(self.seed, _rng.STREAM_USERS, n_user, k, tdt), be.init_factors(self.seed, _rng.STREAM_ITEMS, F.shape[1], k, tdt)
+        else:
+            U, H = (be.to_device(_rng.init_factors(self.seed, s, 0, n, k, 0.01, dtype=self._dev_np()), tdt)
+                    for s, n in ((_rng.STREAM_USERS, n_user), (_rng.STREAM_ITEMS, F.shape[1])))
+        aU, aH = (torch.zeros(n, dtype=torch.float64, device=U.device) for n in (n_user, F.shape[1]))
+        U, H, aU, aH, V, self.trace = self._epochs_feat(m, F, U, H, aU, aH, int(n_iter))
+        self._drop_replicas(be)
+        self._set_items(V, np.bincount(m.indices, minlength=n_item).astype(np.int64))
+        self._H = H
+        self.feature_embeddings, self.feature_adagrad = H.cpu().numpy().astype(self._np_dtype()), aH.cpu().numpy()
+        self.user_adagrad, self.item_adagrad = aU.cpu().numpy(), None
+        return U.cpu().numpy().astype(self._np_dtype())
+
+    def _set_items(self, V, cnt_item):
+        """the composed items V (frozen: a fold-in never reads their Adagrad state) as the model's catalogue"""
+        self._V, self._aV = V, torch.zeros(V.shape[0], dtype=torch.float64, device=V.device)
+        self._cnt_item = cnt_item
+        self.components = V.cpu().numpy().T.astype(self._np_dtype())
+
+    def compose_items(self, item_features):
+        """the embeddings F_new H of items given by their features (n_new x n_feat) -> (n_new x rank); a model fitted with
+        item_features only"""
+        if self._H is None:
+            raise RuntimeError("model is not fitted with item_features")
+        return self._compose_device(item_features).cpu().numpy().astype(self._np_dtype())
+
+    def _compose_device(self, item_features):
+        be = self._backend()
+        F = sp.csr_matrix(item_features)
+        if F.shape[1] != self._H.shape[0]:
+            raise ValueError("item_features must have the fitted model's n_feat columns")
+        F = canonical_features(F, F.shape[0], self._dev_np())
+        if not hasattr(be, "compose_rows"):
+            return torch.from_numpy(compose_reference(F, self._H.numpy()))
+        return be.compose_rows(be.item_features(F, self._H.dtype), self._H)
+
+    def with_items(self, item_features):
+        """a model with the same users' space whose catalogue is the items given by their features (n_new x n_feat): `predict`,
+        `score`, `similar_items` and the rest then rank those items, cold-start ones included.  No item of it counts as seen in
+        training."""
+        import copy
+        if self._H is None:
+            raise RuntimeError("model is not fitted with item_features")
+        V = self._compose_device(item_features)
+        other = copy.copy(self)
+        other._set_items(V, np.zeros(V.shape[0], dtype=np.int64))
+        return other
+
+    def fit_transform(self, x, n_iter=10, item_features=None):
+        """n_iter epochs over the users x items matrix x -> the user factors (n_users x rank).  item_features (scipy sparse,
+        n_items x n_feat): the items are composed from feature embeddings (the class docstring); None: a free row per item."""
         if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or n_iter < 0:
             raise ValueError("n_iter must be an integer >= 0")
         if self._dist()[0] > 1:
@@ -290,6 +483,9 @@ class BPR(WRMF):
         n_user, n_item = m.shape
         be = self._backend()
         self.seed = int(self._rng.integers(2 ** 63))
+        if item_features is not None:
+            return self._fit_features(m, item_features, n_iter)
+        self._H = self.feature_embeddings = self.feature_adagrad = None
         k, tdt = self._rank, self._dev_t()
         if hasattr(be, "init_factors"):
             U, V = be.init_factors(self.seed, _rng.STREAM_USERS, n_user, k, tdt), be.init_factors(self.seed, _rng.STREAM_ITEMS, n_item, k, tdt)

@@ -27,12 +27,16 @@
 //
 // WARP (rsparse_amd/warp.py is its definition) replaces 1 and 2 by one launch, warp_search_kernel: per slot up to
 // max_trials dependent draw-and-score trials that stop at the first candidate inside the margin; 3 - 6 run behind it unchanged.
+//
+// Item features (the kernels are in wrmf_bpr_features.hip): V is composed from the feature rows H before a step,
+// and 5b is replaced by the item totals without the update and a backward pass through F into H.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 #include "../../include/rsparse_wrmf_hip.h"
 #include "wrmf_internal.h"
 #include "wrmf_device.h"
+#include "wrmf_bpr_device.h"
 
 #pragma clang fp contract(off)
 
@@ -40,11 +44,8 @@ namespace rsparse_hip {
 namespace {
 
 using namespace dev;
+using namespace bprdev;
 
-constexpr int kBprThreads = 256;
-constexpr int kBprLanes = 16;                          // lanes of a group: the 16 partial sums of the definition's dot product
-constexpr int kBprGroups = kBprThreads / kBprLanes;    // groups per workgroup
-constexpr int kBprChunk = RSPARSE_HIP_BPR_CHUNK;
 static_assert(kWarpMaxTrials == RSPARSE_HIP_WARP_MAX_TRIALS && kWarpMaxTrials <= kBprThreads, "the weights are staged by one pass of a workgroup");
 
 struct BprStep {
@@ -93,15 +94,6 @@ __global__ __launch_bounds__(kBprThreads) void bpr_sample_kernel(BprStep a, int3
     pay[2 * (size_t)k] = 2u * (uint32_t)k;
     pay[2 * (size_t)k + 1] = 2u * (uint32_t)k + 1u;
   }
-}
-
-// the definition's halving of the 16 partial sums: every lane of the group ends with the same bits
-__device__ __forceinline__ double bpr_reduce16(double v) {
-  v = v + __shfl_xor(v, 8, kBprLanes);
-  v = v + __shfl_xor(v, 4, kBprLanes);
-  v = v + __shfl_xor(v, 2, kBprLanes);
-  v = v + __shfl_xor(v, 1, kBprLanes);
-  return v;
 }
 
 // E(d) of the definition: plain arithmetic, no library exponential
@@ -304,37 +296,6 @@ __global__ __launch_bounds__(kBprThreads) void warp_search_kernel(BprStep a, War
   if (counts && threadIdx.x < 4 && s_cnt[threadIdx.x]) atomicAdd(counts + threadIdx.x, (unsigned long long)s_cnt[threadIdx.x]);
 }
 
-// The update of a destination row with `count` >= 1 contributions whose total the group holds (lane l: the coordinates
-// l + 16 q): g = total - (lambda count) row, a' = a + <g, g> / rank, row' = row + (lr g) / sqrt(a') unless a' == 0.
-// out may be the row itself; another place receives the unchanged row when a' == 0.
-template <class T, int R16>
-__device__ __forceinline__ void bpr_update(double (&tot)[R16], int count, const T* row, T* out, double a, double* a_out, int rank,
-                                           double lr, double lambda, int lane) {
-  const double lc = lambda * (double)count;
-  double part = 0.0;
-#pragma unroll
-  for (int q = 0; q < R16; q++) {
-    const int c = lane + kBprLanes * q;
-    if (c < rank) {
-      const double g = tot[q] - lc * (double)row[c];
-      tot[q] = g;
-      part = part + g * g;
-    }
-  }
-  const double an = a + bpr_reduce16(part) / (double)rank;
-  const double root = sqrt(an);
-#pragma unroll
-  for (int q = 0; q < R16; q++) {
-    const int c = lane + kBprLanes * q;
-    if (c < rank) {
-      const T old = row[c];
-      if (an != 0.0) out[c] = (T)((double)old + (lr * tot[q]) / root);
-      else if (out != row) out[c] = old;
-    }
-  }
-  if (lane == 0) *a_out = an;
-}
-
 // 3. a group per run of equal u; the staging slot of a run is its user (by_user) or its first k, whichever array is smaller
 template <class T, int R16>
 __global__ __launch_bounds__(kBprThreads) void bpr_users_kernel(const int32_t* __restrict__ tu, const int32_t* __restrict__ ti,
@@ -417,26 +378,6 @@ __global__ __launch_bounds__(kBprThreads) void bpr_chunks_kernel(const int32_t* 
   nch[t] = len > kBprChunk ? (len + kBprChunk - 1) / kBprChunk : 0;
 }
 
-// the sum of the m <= kBprChunk contributions at the sorted positions e0 .. of an item, sequentially from +0.0
-template <class T, int R16>
-__device__ __forceinline__ void bpr_item_walk(const uint32_t* __restrict__ spay, const int32_t* __restrict__ tu,
-                                              const double* __restrict__ z, const T* __restrict__ U, int rank, int e0, int m, int lane,
-                                              double (&acc)[R16]) {
-#pragma unroll
-  for (int q = 0; q < R16; q++) acc[q] = 0.0;
-  for (int e = e0; e < e0 + m; e++) {
-    const uint32_t pay = spay[e];
-    const int k = (int)(pay >> 1);
-    const double zk = z[k], zz = (pay & 1u) ? -zk : zk;
-    const T* ur = U + (size_t)tu[k] * rank;
-#pragma unroll
-    for (int q = 0; q < R16; q++) {
-      const int c = lane + kBprLanes * q;
-      if (c < rank) acc[q] = acc[q] + zz * (double)ur[c];
-    }
-  }
-}
-
 // 5a. a group per chunk slot of the long segments
 template <class T, int R16>
 __global__ __launch_bounds__(kBprThreads) void bpr_item_chunks_kernel(const uint32_t* __restrict__ spay, const int32_t* __restrict__ seg,
@@ -472,22 +413,7 @@ __global__ __launch_bounds__(kBprThreads) void bpr_items_kernel(const uint32_t* 
   const int e0 = seg[t], len = seg[t + 1] - e0;
   if (len <= 0) return;
   double acc[R16], tot[R16];
-  if (len <= kBprChunk) {
-    bpr_item_walk<T, R16>(spay, tu, z, U, rank, e0, len, lane, acc);
-#pragma unroll
-    for (int q = 0; q < R16; q++) tot[q] = 0.0 + acc[q];
-  } else {
-#pragma unroll
-    for (int q = 0; q < R16; q++) tot[q] = 0.0;
-    const int g0 = choff[t], n = choff[t + 1] - g0;
-    for (int g = g0; g < g0 + n; g++) {
-#pragma unroll
-      for (int q = 0; q < R16; q++) {
-        const int c = lane + kBprLanes * q;
-        if (c < rank) tot[q] = tot[q] + csum[(size_t)g * rank + c];
-      }
-    }
-  }
+  bpr_item_total<T, R16>(spay, choff, tu, z, U, rank, csum, t, e0, len, lane, acc, tot);
   T* row = V + (size_t)t * rank;
   bpr_update<T, R16>(tot, len, row, row, aV[t], aV + t, rank, lr, lambda, lane);
 }
@@ -499,8 +425,6 @@ inline int bpr_bits(int n) {   // bits that hold 0 .. n
 }
 
 inline int bpr_cnt(int64_t nnz, int step, int n_steps) { return (int)((nnz - step + n_steps - 1) / n_steps); }
-
-inline dim3 bpr_grid(int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); }
 
 #define RSP_TRY(e) do { if ((err = (e)) != hipSuccess) return err; } while (0)
 
@@ -515,7 +439,7 @@ inline BprStep bpr_step_of(const BprRun& r, int epoch, int step) {
 
 template <class T, int R16>
 hipError_t bpr_run(const BprRun& r, const WarpSearch* w, int epoch0, int n_epochs, int only_step, T* U, T* V, double* aU, double* aV,
-                   unsigned long long* counts, hipStream_t s) {
+                   unsigned long long* counts, hipStream_t s, const BprFeatures* ft) {
   hipError_t err;
   const int cmax = bpr_cnt(r.nnz, only_step < 0 ? 0 : only_step, r.n_steps), rank = r.rank, ni = r.n_items;
   if (cmax <= 0) return hipSuccess;
@@ -556,6 +480,30 @@ hipError_t bpr_run(const BprRun& r, const WarpSearch* w, int epoch0, int n_epoch
     RSP_TRY(csum.alloc(slots * rank * 8));
   }
   const dim3 block(kBprThreads);
+  // item features: V is composed from H here and again behind every step that moved H.  The chunk offsets of the long columns
+  // depend on F alone and are made once; a column of len > 64 positions has ceil(len / 64) < len / 32 slots, so nnz_f / 32 + 1
+  // slots bound the workspace and the grid without reading the count back.
+  const bool feat = ft && r.update_items;
+  const int nf = ft ? ft->n_feat : 0;
+  const size_t fslots = ft ? (size_t)(ft->nnz_f / 32) + 1 : 0;
+  DevBuf G, icnt, fnch, fchoff, fscan_tmp, fsum, fcnt;
+  size_t fscan_bytes = 0;
+  if (ft) RSP_TRY(launch_compose_rows<T>(ft->fp, ft->fj, (const T*)ft->fx, ni, rank, (const T*)ft->H, V, s));
+  if (feat) {
+    RSP_TRY(G.alloc((size_t)ni * rank * 8));
+    RSP_TRY(icnt.alloc((size_t)ni * 4));
+    RSP_TRY(fnch.alloc(((size_t)nf + 1) * 4));
+    RSP_TRY(fchoff.alloc(((size_t)nf + 1) * 4));
+    RSP_TRY(fsum.alloc(fslots * rank * 8));
+    RSP_TRY(fcnt.alloc(fslots * 4));
+    RSP_TRY(rocprim::exclusive_scan(nullptr, fscan_bytes, fnch.as<int32_t>(), fchoff.as<int32_t>(), (int32_t)0, (size_t)nf + 1,
+                                    rocprim::plus<int32_t>(), s));
+    RSP_TRY(fscan_tmp.alloc(fscan_bytes));
+    hipLaunchKernelGGL(bpr_chunks_kernel, bpr_grid((int64_t)nf + 1, kBprThreads), block, 0, s, ft->cp, nf, fnch.as<int32_t>());
+    RSP_TRY(hipGetLastError());
+    RSP_TRY(rocprim::exclusive_scan(fscan_tmp.p, fscan_bytes, fnch.as<int32_t>(), fchoff.as<int32_t>(), (int32_t)0, (size_t)nf + 1,
+                                    rocprim::plus<int32_t>(), s));
+  }
   for (int e = 0; e < n_epochs; e++) {
     for (int st = only_step < 0 ? 0 : only_step; st < (only_step < 0 ? r.n_steps : only_step + 1); st++) {
       const BprStep a = bpr_step_of(r, epoch0 + e, st);
@@ -592,9 +540,16 @@ hipError_t bpr_run(const BprRun& r, const WarpSearch* w, int epoch0, int n_epoch
         hipLaunchKernelGGL((bpr_item_chunks_kernel<T, R16>), bpr_grid((int64_t)step_slots, kBprGroups), block, 0, s,
                            (const uint32_t*)pay_out.as<uint32_t>(), (const int32_t*)seg.as<int32_t>(), (const int32_t*)choff.as<int32_t>(),
                            ni, (const int32_t*)tu.as<int32_t>(), (const double*)z.as<double>(), (const T*)U, rank, csum.as<double>());
-        hipLaunchKernelGGL((bpr_items_kernel<T, R16>), bpr_grid(ni, kBprGroups), block, 0, s, (const uint32_t*)pay_out.as<uint32_t>(),
-                           (const int32_t*)seg.as<int32_t>(), (const int32_t*)choff.as<int32_t>(), ni, (const int32_t*)tu.as<int32_t>(),
-                           (const double*)z.as<double>(), (const T*)U, rank, (const double*)csum.as<double>(), r.lr, r.lambda, V, aV);
+        if (feat) {
+          RSP_TRY(launch_bpr_feat_backward<T>(*ft, ni, rank, fslots, fchoff.as<int32_t>(), pay_out.as<uint32_t>(), seg.as<int32_t>(),
+                                              choff.as<int32_t>(), tu.as<int32_t>(), z.as<double>(), (const T*)U, csum.as<double>(),
+                                              G.as<double>(), icnt.as<int32_t>(), fsum.as<double>(), fcnt.as<int32_t>(), r.lr, r.lambda, s));
+          RSP_TRY(launch_compose_rows<T>(ft->fp, ft->fj, (const T*)ft->fx, ni, rank, (const T*)ft->H, V, s));
+        } else {
+          hipLaunchKernelGGL((bpr_items_kernel<T, R16>), bpr_grid(ni, kBprGroups), block, 0, s, (const uint32_t*)pay_out.as<uint32_t>(),
+                             (const int32_t*)seg.as<int32_t>(), (const int32_t*)choff.as<int32_t>(), ni, (const int32_t*)tu.as<int32_t>(),
+                             (const double*)z.as<double>(), (const T*)U, rank, (const double*)csum.as<double>(), r.lr, r.lambda, V, aV);
+        }
       }
       hipLaunchKernelGGL((bpr_copy_kernel<T>), per_group, block, 0, s, (const int32_t*)tu.as<int32_t>(),
                          (const int32_t*)scount.as<int32_t>(), cnt, rank, by_user, (const T*)stage.as<T>(), (const double*)stage_a.as<double>(), U,
@@ -619,13 +574,13 @@ hipError_t launch_bpr_triples(const BprRun& r, int epoch, int step, int32_t* tu,
 namespace {
 template <class T>
 hipError_t bpr_run_any(const BprRun& r, const WarpSearch* w, int epoch0, int n_epochs, int only_step, T* U, T* V, double* aU, double* aV,
-                       unsigned long long* counts, hipStream_t s) {
+                       unsigned long long* counts, hipStream_t s, const BprFeatures* ft) {
   const int r16 = (r.rank + kBprLanes - 1) / kBprLanes;
-  if (r16 <= 1) return bpr_run<T, 1>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
-  if (r16 <= 2) return bpr_run<T, 2>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
-  if (r16 <= 4) return bpr_run<T, 4>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
-  if (r16 <= 8) return bpr_run<T, 8>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
-  return bpr_run<T, 16>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
+  if (r16 <= 1) return bpr_run<T, 1>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s, ft);
+  if (r16 <= 2) return bpr_run<T, 2>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s, ft);
+  if (r16 <= 4) return bpr_run<T, 4>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s, ft);
+  if (r16 <= 8) return bpr_run<T, 8>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s, ft);
+  return bpr_run<T, 16>(r, w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s, ft);
 }
 
 template <class T, int R16>
@@ -638,22 +593,23 @@ void warp_search(const BprStep& a, const WarpSearch& w, int rank, const T* U, co
 
 template <class T>
 hipError_t launch_bpr_run(const BprRun& r, int epoch0, int n_epochs, int only_step, T* U, T* V, double* aU, double* aV,
-                          unsigned long long* counts, hipStream_t s) {
-  return bpr_run_any<T>(r, nullptr, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
+                          unsigned long long* counts, hipStream_t s, const BprFeatures* ft) {
+  return bpr_run_any<T>(r, nullptr, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s, ft);
 }
-template hipError_t launch_bpr_run<float>(const BprRun&, int, int, int, float*, float*, double*, double*, unsigned long long*, hipStream_t);
+template hipError_t launch_bpr_run<float>(const BprRun&, int, int, int, float*, float*, double*, double*, unsigned long long*, hipStream_t,
+                                          const BprFeatures*);
 template hipError_t launch_bpr_run<double>(const BprRun&, int, int, int, double*, double*, double*, double*, unsigned long long*,
-                                           hipStream_t);
+                                           hipStream_t, const BprFeatures*);
 
 template <class T>
 hipError_t launch_warp_run(const BprRun& r, const WarpSearch& w, int epoch0, int n_epochs, int only_step, T* U, T* V, double* aU,
-                           double* aV, unsigned long long* counts, hipStream_t s) {
-  return bpr_run_any<T>(r, &w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s);
+                           double* aV, unsigned long long* counts, hipStream_t s, const BprFeatures* ft) {
+  return bpr_run_any<T>(r, &w, epoch0, n_epochs, only_step, U, V, aU, aV, counts, s, ft);
 }
 template hipError_t launch_warp_run<float>(const BprRun&, const WarpSearch&, int, int, int, float*, float*, double*, double*,
-                                           unsigned long long*, hipStream_t);
+                                           unsigned long long*, hipStream_t, const BprFeatures*);
 template hipError_t launch_warp_run<double>(const BprRun&, const WarpSearch&, int, int, int, double*, double*, double*, double*,
-                                            unsigned long long*, hipStream_t);
+                                            unsigned long long*, hipStream_t, const BprFeatures*);
 
 template <class T>
 hipError_t launch_warp_triples(const BprRun& r, const WarpSearch& w, int epoch, int step, const T* U, const T* V, int32_t* tu, int32_t* ti,

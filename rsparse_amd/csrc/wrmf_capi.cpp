@@ -1800,20 +1800,54 @@ BprRun bpr_run_of(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_item
   return r;
 }
 
+// item features: what the feature entries refuse beyond bpr_args, and the matrices as the run takes them
+inline int bpr_features_of(const int32_t* fp, const int32_t* fj, const void* fx, const int32_t* cp, const int32_t* ci, const void* cx,
+                           int n_feat, int64_t nnz_f, void* H, double* aH, BprFeatures& ft) {
+  if (!fp || !fj || !fx || !cp || !ci || !cx || !H || !aH)
+    return fail(RSPARSE_HIP_ERR_INVALID, "a feature array (F by item or by feature, H or aH) is NULL");
+  if (n_feat < 1) return fail(RSPARSE_HIP_ERR_INVALID, "n_feat < 1");
+  if (nnz_f < 0 || nnz_f > 0x7fffffffLL) return fail(RSPARSE_HIP_ERR_INVALID, "nnz_f < 0 or nnz_f >= 2^31");
+  ft.fp = fp; ft.fj = fj; ft.fx = fx; ft.cp = cp; ft.ci = ci; ft.cx = cx; ft.n_feat = n_feat; ft.nnz_f = nnz_f; ft.H = H; ft.aH = aH;
+  return RSPARSE_HIP_OK;
+}
+
+template <class T>
+int compose_only(const BprFeatures& ft, int n_items, int rank, T* d_V, hipStream_t s) {
+  hipError_t e = launch_compose_rows<T>(ft.fp, ft.fj, (const T*)ft.fx, n_items, rank, (const T*)ft.H, d_V, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_compose_rows");
+  return RSPARSE_HIP_OK;
+}
+
+template <class T>
+int compose_rows_device(const int32_t* d_fp, const int32_t* d_fj, const T* d_fx, int n_items, int n_feat, int64_t nnz_f, int rank,
+                        const T* d_H, T* d_V, void* stream, int max_rank) {
+  if (!d_fp || !d_fj || !d_fx || !d_H || !d_V) return fail(RSPARSE_HIP_ERR_INVALID, "a feature array, H or V is NULL");
+  if (n_items < 0 || n_feat < 1 || nnz_f < 0 || nnz_f > 0x7fffffffLL)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_items < 0, n_feat < 1, nnz_f < 0 or nnz_f >= 2^31)");
+  if (rank < 1) return fail(RSPARSE_HIP_ERR_INVALID, "rank < 1");
+  if (rank > max_rank) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > " + std::to_string(max_rank) + " is not on the device path");
+  if (n_items == 0) return RSPARSE_HIP_OK;
+  hipError_t e = launch_compose_rows<T>(d_fp, d_fj, d_fx, n_items, rank, d_H, d_V, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_compose_rows");
+  return RSPARSE_HIP_OK;
+}
+
 template <class T>
 int bpr_step_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0, uint64_t seed, int mode,
                     int epoch, int step, int n_steps, int rank, double lr, double lambda, int update_items, T* d_U, T* d_V,
-                    double* d_aU, double* d_aV, int64_t* d_counts, void* stream, int max_rank, const WarpSearch* w = nullptr) {
+                    double* d_aU, double* d_aV, int64_t* d_counts, void* stream, int max_rank, const WarpSearch* w = nullptr,
+                    const BprFeatures* ft = nullptr) {
   int rc = bpr_args(!d_p || !d_j || !d_U || !d_V || !d_aU || !d_aV || !d_counts, n_rows, n_items, nnz, row0, mode, epoch, 1, n_steps,
                     "n_steps", rank, max_rank, lr, lambda);
   if (rc) return rc;
   if (step < 0 || step >= n_steps) return fail(RSPARSE_HIP_ERR_INVALID, "step outside [0, n_steps)");
   if ((rc = bpr_step_size(nnz, n_steps, update_items))) return rc;
-  if (n_rows == 0 || nnz == 0) return RSPARSE_HIP_OK;
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  if (nnz == 0) return ft ? compose_only<T>(*ft, n_items, rank, d_V, (hipStream_t)stream) : RSPARSE_HIP_OK;
   const BprRun r = bpr_run_of(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, n_steps, rank, lr, lambda, update_items);
   unsigned long long* counts = reinterpret_cast<unsigned long long*>(d_counts);
-  hipError_t e = w ? launch_warp_run<T>(r, *w, epoch, 1, step, d_U, d_V, d_aU, d_aV, counts, (hipStream_t)stream)
-                   : launch_bpr_run<T>(r, epoch, 1, step, d_U, d_V, d_aU, d_aV, counts, (hipStream_t)stream);
+  hipError_t e = w ? launch_warp_run<T>(r, *w, epoch, 1, step, d_U, d_V, d_aU, d_aV, counts, (hipStream_t)stream, ft)
+                   : launch_bpr_run<T>(r, epoch, 1, step, d_U, d_V, d_aU, d_aV, counts, (hipStream_t)stream, ft);
   if (e != hipSuccess) return hip_fail(e, w ? "launch_warp_run" : "launch_bpr_run");
   return RSPARSE_HIP_OK;
 }
@@ -1821,20 +1855,22 @@ int bpr_step_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_it
 template <class T>
 int bpr_epochs_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0, uint64_t seed, int mode,
                       int epoch0, int n_epochs, int batch, int rank, double lr, double lambda, int update_items, T* d_U, T* d_V,
-                      double* d_aU, double* d_aV, int64_t* d_counts, void* stream, int max_rank, const WarpSearch* w = nullptr) {
+                      double* d_aU, double* d_aV, int64_t* d_counts, void* stream, int max_rank, const WarpSearch* w = nullptr,
+                      const BprFeatures* ft = nullptr) {
   int rc = bpr_args(!d_p || !d_j || !d_U || !d_V || !d_aU || !d_aV || !d_counts, n_rows, n_items, nnz, row0, mode, epoch0, n_epochs,
                     batch, "batch", rank, max_rank, lr, lambda);
   if (rc) return rc;
   const int n_steps = mode == 1 || nnz == 0 ? 1 : (int)((nnz + batch - 1) / batch);
   if ((rc = bpr_step_size(nnz, n_steps, update_items))) return rc;
-  if (n_rows == 0 || n_epochs == 0) return RSPARSE_HIP_OK;
+  if (n_rows == 0) return RSPARSE_HIP_OK;
   hipStream_t s = (hipStream_t)stream;
+  if (n_epochs == 0) return ft ? compose_only<T>(*ft, n_items, rank, d_V, s) : RSPARSE_HIP_OK;
   HIP_TRY(hipMemsetAsync(d_counts, 0, (w ? 4 : 2) * (size_t)n_epochs * sizeof(int64_t), s));
-  if (nnz == 0) return RSPARSE_HIP_OK;
+  if (nnz == 0) return ft ? compose_only<T>(*ft, n_items, rank, d_V, s) : RSPARSE_HIP_OK;
   const BprRun r = bpr_run_of(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, n_steps, rank, lr, lambda, update_items);
   unsigned long long* counts = reinterpret_cast<unsigned long long*>(d_counts);
-  hipError_t e = w ? launch_warp_run<T>(r, *w, epoch0, n_epochs, -1, d_U, d_V, d_aU, d_aV, counts, s)
-                   : launch_bpr_run<T>(r, epoch0, n_epochs, -1, d_U, d_V, d_aU, d_aV, counts, s);
+  hipError_t e = w ? launch_warp_run<T>(r, *w, epoch0, n_epochs, -1, d_U, d_V, d_aU, d_aV, counts, s, ft)
+                   : launch_bpr_run<T>(r, epoch0, n_epochs, -1, d_U, d_V, d_aU, d_aV, counts, s, ft);
   if (e != hipSuccess) return hip_fail(e, w ? "launch_warp_run" : "launch_bpr_run");
   return RSPARSE_HIP_OK;
 }
@@ -1941,6 +1977,51 @@ RSPARSE_WARP_ENTRY(rsparse_hip_warp_step_f64_device, double, bpr_step_device, ep
 RSPARSE_WARP_ENTRY(rsparse_hip_warp_epochs_device, float, bpr_epochs_device, epoch0, n_epochs, batch, RSPARSE_HIP_MAX_RANK)
 RSPARSE_WARP_ENTRY(rsparse_hip_warp_epochs_f64_device, double, bpr_epochs_device, epoch0, n_epochs, batch, RSPARSE_HIP_MAX_RANK_F64)
 #undef RSPARSE_WARP_ENTRY
+
+// item features: V = F H alone, and the BPR / WARP steps and epochs through F (the feature arrays are checked first, then BPR's)
+int rsparse_hip_compose_rows_device(const int32_t* d_fp, const int32_t* d_fj, const float* d_fx, int n_items, int n_feat, int64_t nnz_f,
+                                    int rank, const float* d_H, float* d_V, void* stream) {
+  return compose_rows_device<float>(d_fp, d_fj, d_fx, n_items, n_feat, nnz_f, rank, d_H, d_V, stream, RSPARSE_HIP_MAX_RANK);
+}
+int rsparse_hip_compose_rows_f64_device(const int32_t* d_fp, const int32_t* d_fj, const double* d_fx, int n_items, int n_feat,
+                                        int64_t nnz_f, int rank, const double* d_H, double* d_V, void* stream) {
+  return compose_rows_device<double>(d_fp, d_fj, d_fx, n_items, n_feat, nnz_f, rank, d_H, d_V, stream, RSPARSE_HIP_MAX_RANK_F64);
+}
+
+#define RSPARSE_FEAT_TAIL(T)                                                                                                          \
+  const int32_t *d_fp, const int32_t *d_fj, const T *d_fx, const int32_t *d_cp, const int32_t *d_ci, const T *d_cx, int n_feat,       \
+      int64_t nnz_f, T *d_U, T *d_H, T *d_V, double *d_aU, double *d_aH, int64_t *d_counts, void *stream
+// (d_aH stands in BPR's d_aV slot of the body: a run with features never touches an item's Adagrad state)
+#define RSPARSE_FEAT_BODY(BODY, T, A, B, C, MAXRANK, W)                                                                               \
+  BprFeatures ft;                                                                                                                     \
+  if (int rc = bpr_features_of(d_fp, d_fj, d_fx, d_cp, d_ci, d_cx, n_feat, nnz_f, d_H, d_aH, ft)) return rc;                          \
+  return BODY<T>(d_p, d_j, n_rows, n_items, nnz, row0, seed, mode, A, B, C, rank, learning_rate, lambda, update_items, d_U, d_V,      \
+                 d_aU, d_aH, d_counts, stream, MAXRANK, W, &ft);
+#define RSPARSE_BPR_FEAT_ENTRY(NAME, T, BODY, A, B, C, MAXRANK)                                                                       \
+  int NAME(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0, uint64_t seed, int mode, int A, \
+           int B, int C, int rank, double learning_rate, double lambda, int update_items, RSPARSE_FEAT_TAIL(T)) {                     \
+    RSPARSE_FEAT_BODY(BODY, T, A, B, C, MAXRANK, nullptr)                                                                             \
+  }
+#define RSPARSE_WARP_FEAT_ENTRY(NAME, T, BODY, A, B, C, MAXRANK)                                                                      \
+  int NAME(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_items, int64_t nnz, int64_t row0, uint64_t seed, int mode, int A, \
+           int B, int C, int max_trials, double margin, const double* weights, int rank, double learning_rate, double lambda,          \
+           int update_items, RSPARSE_FEAT_TAIL(T)) {                                                                                  \
+    WarpSearch w;                                                                                                                      \
+    if (int rc = warp_search_of(max_trials, margin, weights, w)) return rc;                                                            \
+    RSPARSE_FEAT_BODY(BODY, T, A, B, C, MAXRANK, &w)                                                                                  \
+  }
+RSPARSE_BPR_FEAT_ENTRY(rsparse_hip_bpr_feat_step_device, float, bpr_step_device, epoch, step, n_steps, RSPARSE_HIP_MAX_RANK)
+RSPARSE_BPR_FEAT_ENTRY(rsparse_hip_bpr_feat_step_f64_device, double, bpr_step_device, epoch, step, n_steps, RSPARSE_HIP_MAX_RANK_F64)
+RSPARSE_BPR_FEAT_ENTRY(rsparse_hip_bpr_feat_epochs_device, float, bpr_epochs_device, epoch0, n_epochs, batch, RSPARSE_HIP_MAX_RANK)
+RSPARSE_BPR_FEAT_ENTRY(rsparse_hip_bpr_feat_epochs_f64_device, double, bpr_epochs_device, epoch0, n_epochs, batch, RSPARSE_HIP_MAX_RANK_F64)
+RSPARSE_WARP_FEAT_ENTRY(rsparse_hip_warp_feat_step_device, float, bpr_step_device, epoch, step, n_steps, RSPARSE_HIP_MAX_RANK)
+RSPARSE_WARP_FEAT_ENTRY(rsparse_hip_warp_feat_step_f64_device, double, bpr_step_device, epoch, step, n_steps, RSPARSE_HIP_MAX_RANK_F64)
+RSPARSE_WARP_FEAT_ENTRY(rsparse_hip_warp_feat_epochs_device, float, bpr_epochs_device, epoch0, n_epochs, batch, RSPARSE_HIP_MAX_RANK)
+RSPARSE_WARP_FEAT_ENTRY(rsparse_hip_warp_feat_epochs_f64_device, double, bpr_epochs_device, epoch0, n_epochs, batch, RSPARSE_HIP_MAX_RANK_F64)
+#undef RSPARSE_BPR_FEAT_ENTRY
+#undef RSPARSE_WARP_FEAT_ENTRY
+#undef RSPARSE_FEAT_BODY
+#undef RSPARSE_FEAT_TAIL
 
 namespace {
 // the device form of both samplers: d_cum == nullptr is the uniform stream, otherwise the weighted one under that prefix

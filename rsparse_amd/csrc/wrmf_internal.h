@@ -514,10 +514,35 @@ struct BprRun {
   double lr, lambda;
   bool update_items;
 };
+// Item features (defined in rsparse_wrmf_hip.h): F, n_items x n_feat, by item (fp, fj, fx: CSR) and by feature (cp, ci, cx: CSC),
+// both canonical, values of the factors' type; nnz_f = fp[n_items] handed in.  A run with features reads and updates H
+// (n_feat x rank) and aH in the place of V and aV; V is then the composed F H: written before every step and after the last
+// one, never updated (aV is not touched).  !update_items: V is composed once and H only read.
+struct BprFeatures {
+  const int32_t *fp, *fj;
+  const void* fx;
+  const int32_t *cp, *ci;
+  const void* cx;
+  int n_feat;
+  int64_t nnz_f;
+  void* H;
+  double* aH;
+};
 hipError_t launch_bpr_triples(const BprRun& r, int epoch, int step, int32_t* tu, int32_t* ti, int32_t* tj, hipStream_t s);
 template <class T>
 hipError_t launch_bpr_run(const BprRun& r, int epoch0, int n_epochs, int only_step, T* U, T* V, double* aU, double* aV,
-                          unsigned long long* counts, hipStream_t s);
+                          unsigned long long* counts, hipStream_t s, const BprFeatures* ft = nullptr);
+// wrmf_bpr_features.hip.  compose: V = F H alone (rows of F: fp, fj, fx), no synchronisation.  backward: what a step with
+// features runs in the place of the item update, behind the sort, the segments and the chunk sums of the step (spay, seg, choff,
+// csum): the item totals G (n_items x rank) and counts icnt, then the pass through F by feature into ft.H, ft.aH; fchoff: the
+// chunk offsets of the columns longer than one chunk, fslots the bound of their count that sized fsum / fcnt
+template <class T>
+hipError_t launch_bpr_feat_backward(const BprFeatures& ft, int n_items, int rank, size_t fslots, const int32_t* fchoff, const uint32_t* spay,
+                                    const int32_t* seg, const int32_t* choff, const int32_t* tu, const double* z, const T* U,
+                                    const double* csum, double* G, int32_t* icnt, double* fsum, int32_t* fcnt, double lr, double lambda,
+                                    hipStream_t s);
+template <class T>
+hipError_t launch_compose_rows(const int32_t* fp, const int32_t* fj, const T* fx, int n_items, int rank, const T* H, T* V, hipStream_t s);
 
 // WARP (wrmf_bpr.hip; defined in rsparse_wrmf_hip.h): a BPR run whose triples come from the search.  triples: the search alone on
 // the factors U, V (ld = r.rank) -> (u, i, j, t, z) of one step.  run: as launch_bpr_run with FOUR counts per epoch, ADDED to:
@@ -533,7 +558,7 @@ hipError_t launch_warp_triples(const BprRun& r, const WarpSearch& w, int epoch, 
                                int32_t* tj, int32_t* tt, double* z, hipStream_t s);
 template <class T>
 hipError_t launch_warp_run(const BprRun& r, const WarpSearch& w, int epoch0, int n_epochs, int only_step, T* U, T* V, double* aU,
-                           double* aV, unsigned long long* counts, hipStream_t s);
+                           double* aV, unsigned long long* counts, hipStream_t s, const BprFeatures* ft = nullptr);
 
 // top-k within per-user candidate lists (wrmf_candidates.hip), T = float or double, 1 <= topk <= kTopLargeMax: for every row of
 // the CSR pattern (cand_p: n_users + 1 slots, absolute positions into cand_j; p0 = cand_p[0], nnz = cand_p[n_users] - p0, read by

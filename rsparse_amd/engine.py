@@ -1058,6 +1058,78 @@ class HipBackend:
                         aV, lr, lam, update_items, counts)
         return counts[:int(n_epochs)]
 
+    def item_features(self, F, dtype):
+        """a canonical scipy CSR F (n_items x n_feat) -> (fp, fj, fx, cp, ci, cx, n_feat) on the device: F by item and, through
+        `transpose_csc`, by feature; values of `dtype`"""
+        fp, fj, fx = self.to_device(F.indptr, torch.int32), self.to_device(F.indices, torch.int32), self.to_device(F.data, dtype)
+        n_items, n_feat = F.shape
+        # the CSR rows of F are the CSC columns of its transpose (n_feat x n_items): transposed, feature -> its items, ascending
+        cp, ci, cx = self.transpose_csc(n_feat, n_items, fp, fj, fx) if F.nnz else (torch.zeros(n_feat + 1, dtype=torch.int32, device=self.device), fj, fx)
+        return fp, fj, fx, cp, ci, cx, int(n_feat)
+
+    def compose_rows(self, feat, H):
+        """V = F H in the definition's order (rsparse_amd.bpr.compose_reference; bpr_compose_kernel of wrmf_bpr_features.hip) for the
+        device features `feat` of `item_features` and H (n_feat x rank, float32 or float64, contiguous) -> V (n_items x rank)"""
+        fp, fj, fx, _, _, _, n_feat = feat
+        assert H.is_cuda and H.is_contiguous() and H.shape[0] == n_feat and H.dtype == fx.dtype and H.dtype in (torch.float32, torch.float64)
+        n_items = int(fp.numel()) - 1
+        V = torch.empty((n_items, int(H.shape[1])), dtype=H.dtype, device=self.device)
+        fn = getattr(self.lib, "rsparse_hip_compose_rows%s_device" % ("_f64" if H.dtype == torch.float64 else ""))
+        some = lambda t: t.data_ptr() if t.numel() else fp.data_ptr()   # (an empty tensor has no address to pass)
+        _lib.check(fn(fp.data_ptr(), some(fj), some(fx), n_items, n_feat, int(fj.numel()), int(H.shape[1]), H.data_ptr(), some(V), self._stream()))
+        return V
+
+    def _feat_call(self, loss, name, p, j, nnz, row0, seed, mode, a, b, c, search, feat, U, H, aU, aH, lr, lam, update_items, counts):
+        """the BPR / WARP step or epochs through item features, in place on U, H, aU, aH -> the composed V (n_items x rank)"""
+        fp, fj, fx, cp, ci, cx, n_feat = feat
+        assert p.dtype == torch.int32 and j.dtype == torch.int32 and U.dtype == H.dtype == fx.dtype and U.dtype in (torch.float32, torch.float64)
+        assert U.is_cuda and U.is_contiguous() and H.is_contiguous() and U.shape[1] == H.shape[1] and H.shape[0] == n_feat
+        assert aU.dtype == torch.float64 and aH.dtype == torch.float64 and aU.numel() == U.shape[0] and aH.numel() == n_feat
+        assert U.shape[0] == p.numel() - 1 and aU.is_contiguous() and aH.is_contiguous() and cp.numel() == n_feat + 1
+        n_items = int(fp.numel()) - 1
+        V = torch.zeros((n_items, int(U.shape[1])), dtype=U.dtype, device=self.device)
+        keep = ()
+        if search is not None:
+            search, keep = self._warp_search(*search)
+        fn = getattr(self.lib, "rsparse_hip_%s_feat_%s%s_device" % (loss, name, "_f64" if U.dtype == torch.float64 else ""))
+        some = lambda t: t.data_ptr() if t.numel() else counts.data_ptr()   # (an empty tensor has no address to pass)
+        _lib.check(fn(some(p), some(j), int(U.shape[0]), n_items, int(nnz), int(row0), int(seed), int(mode), int(a), int(b), int(c),
+                      *(search or ()), int(U.shape[1]), float(lr), float(lam), int(bool(update_items)), fp.data_ptr(), some(fj), some(fx),
+                      cp.data_ptr(), some(ci), some(cx), n_feat, int(fj.numel()), some(U), H.data_ptr(), some(V), some(aU), aH.data_ptr(),
+                      counts.data_ptr(), self._stream()))
+        del keep
+        return V
+
+    def bpr_feat_step(self, p, j, nnz, row0, seed, mode, epoch, step, n_steps, feat, U, H, aU, aH, lr, lam, update_items=True):
+        """one BPR step through the item features `feat` (of `item_features`), in place on U, H (n_feat x rank) and aU, aH
+        (rsparse_amd.bpr.bpr_feat_step_reference is the definition) -> ((n_valid, n_correct): int64 on the device, V = F H')"""
+        counts = torch.zeros(2, dtype=torch.int64, device=self.device)
+        V = self._feat_call("bpr", "step", p, j, nnz, row0, seed, mode, epoch, step, n_steps, None, feat, U, H, aU, aH, lr, lam, update_items, counts)
+        return counts, V
+
+    def bpr_feat_epochs(self, p, j, nnz, row0, seed, mode, epoch0, n_epochs, batch, feat, U, H, aU, aH, lr, lam, update_items=True):
+        """the BPR epochs [epoch0, epoch0 + n_epochs) through the item features, as `bpr_epochs` -> ((n_epochs, 2) counts, V)"""
+        counts = torch.zeros((max(int(n_epochs), 1), 2), dtype=torch.int64, device=self.device)
+        V = self._feat_call("bpr", "epochs", p, j, nnz, row0, seed, mode, epoch0, n_epochs, batch, None, feat, U, H, aU, aH, lr, lam, update_items,
+                            counts)
+        return counts[:int(n_epochs)], V
+
+    def warp_feat_step(self, p, j, nnz, row0, seed, mode, epoch, step, n_steps, max_trials, margin, weights, feat, U, H, aU, aH, lr, lam,
+                       update_items=True):
+        """one WARP step through the item features, as `bpr_feat_step` -> ((n_valid, n_looked, n_correct, n_scored), V)"""
+        counts = torch.zeros(4, dtype=torch.int64, device=self.device)
+        V = self._feat_call("warp", "step", p, j, nnz, row0, seed, mode, epoch, step, n_steps, (max_trials, margin, weights), feat, U, H, aU, aH,
+                            lr, lam, update_items, counts)
+        return counts, V
+
+    def warp_feat_epochs(self, p, j, nnz, row0, seed, mode, epoch0, n_epochs, batch, max_trials, margin, weights, feat, U, H, aU, aH, lr, lam,
+                         update_items=True):
+        """the WARP epochs through the item features, as `warp_epochs` -> ((n_epochs, 4) counts, V)"""
+        counts = torch.zeros((max(int(n_epochs), 1), 4), dtype=torch.int64, device=self.device)
+        V = self._feat_call("warp", "epochs", p, j, nnz, row0, seed, mode, epoch0, n_epochs, batch, (max_trials, margin, weights), feat, U, H,
+                            aU, aH, lr, lam, update_items, counts)
+        return counts[:int(n_epochs)], V
+
     def _knn_rows(self, xp, xj, neighbors, q, xv):
         """the operands the ItemKNN evaluation entries share with `knn_recommend`, as the C ABI takes them: -> (the leading
         arguments, `some`: the address of a tensor, or of xp for an empty one; the tensors that must outlive the call)"""

@@ -31,7 +31,11 @@ estimate), n_scored (admissible trials scored, the violator included: n_scored /
 Not here: the `sigmoid` kernel, RMSprop, user and item feature matrices, per-role lambdas, and the classic hinge WARP without the
 logistic factor.
 
+Item features (`fit_transform(x, item_features=F)`): BPR's hybrid model (the docstring of rsparse_amd/bpr.py) with this search on
+the composed items.
+
   rank_weights, warp_triples, warp_step_reference, warp_fit_reference     the definition, in numpy
+  warp_feat_step_reference, warp_feat_fit_reference                       the same through item features
   WARP                                                                    the model: `BPR`'s surface on this loss
 """
 import math
@@ -40,7 +44,7 @@ import numpy as np
 
 from . import _lib
 from . import rng as _rng
-from .bpr import BPR, bpr_exp, n_steps_of, step_from_z, step_slot_rows, sum16
+from .bpr import BPR, bpr_exp, compose_reference, feat_step_from_z, n_steps_of, step_from_z, step_slot_rows, sum16
 
 MAX_TRIALS = _lib.WARP_MAX_TRIALS
 
@@ -136,6 +140,41 @@ def warp_fit_reference(indptr, indices, n_items, U, V, n_iter, seed, max_trials,
     return U, V, aU, aV, trace
 
 
+def warp_feat_step_reference(U, H, aU, aH, F, seed, epoch, indptr, indices, max_trials, margin, weights, learning_rate, lambda_, step=0,
+                             n_steps=1):
+    """One step of the definition through the item features F (canonical CSR; rsparse_amd.bpr has the feature side) from the
+    snapshot (U, H) -> (U', H', aU', aH', n_valid, n_looked, n_correct, n_scored); nothing is changed in place."""
+    U, H = np.asarray(U), np.asarray(H)
+    aU, aH = np.asarray(aU, dtype=np.float64), np.asarray(aH, dtype=np.float64)
+    V = compose_reference(F, H)
+    tu, ti, tj, _, z, _, counts = warp_triples(seed, 0, epoch, 0, indptr, indices, V.shape[0], U, V, max_trials, margin, weights, step, n_steps)
+    keep = np.flatnonzero(tj >= 0)
+    u, i, j = (t.astype(np.int64)[keep] for t in (tu, ti, tj))
+    diff = V[i].astype(np.float64) - V[j].astype(np.float64)
+    return feat_step_from_z(U, H, aU, aH, F, u, i, j, z[keep], diff, learning_rate, lambda_) + (int(keep.size),) + counts
+
+
+def warp_feat_fit_reference(indptr, indices, F, U, H, n_iter, seed, max_trials, margin, weights, learning_rate, lambda_, batch, aU=None,
+                            aH=None, epoch0=0):
+    """n_iter epochs of the definition through the item features F from (U, H) -> (U, H, aU, aH, trace),
+    trace = [(n_valid, n_looked, n_correct, n_scored)] per epoch"""
+    ip = np.asarray(indptr, dtype=np.int64)
+    U, H = np.array(U), np.array(H)
+    aU = np.zeros(U.shape[0]) if aU is None else np.array(aU, dtype=np.float64)
+    aH = np.zeros(H.shape[0]) if aH is None else np.array(aH, dtype=np.float64)
+    n_steps = n_steps_of(ip[-1], batch)
+    trace = []
+    for e in range(epoch0, epoch0 + int(n_iter)):
+        total = np.zeros(4, dtype=np.int64)
+        for s in range(n_steps):
+            out = warp_feat_step_reference(U, H, aU, aH, F, seed, e, ip, indices, max_trials, margin, weights, learning_rate, lambda_, s,
+                                           n_steps)
+            U, H, aU, aH = out[:4]
+            total += np.array(out[4:], dtype=np.int64)
+        trace.append(tuple(int(c) for c in total))
+    return U, H, aU, aH, trace
+
+
 class WARP(BPR):
     """Matrix factorisation on the WARP loss (the module's docstring is the definition): `BPR` with max_trials (1 .. 64) draws per
     slot at most and a finite margin.  Fitted, beyond BPR's: `trace` = [(n_valid, n_looked, n_correct, n_scored)] per epoch and
@@ -162,3 +201,19 @@ class WARP(BPR):
         counts = be.warp_epochs(p, j, m.shape[1], m.nnz, 0, self.seed, mode, 0, n_iter, self._batch, T, margin, w, U, V, aU, aV, self._lr,
                                 self._lambda, update_items)
         return U, V, aU, aV, [tuple(int(c) for c in row) for row in counts.cpu().numpy()]
+
+    def _epochs_feat(self, m, F, U, H, aU, aH, n_iter):
+        import torch
+        be = self._backend()
+        T, margin = self._max_trials, self._margin
+        self.rank_weights = w = rank_weights(m.shape[1], T)
+        if not hasattr(be, "warp_feat_epochs"):
+            out = warp_feat_fit_reference(m.indptr, m.indices, F, U.numpy(), H.numpy(), n_iter, self.seed, T, margin, w, self._lr,
+                                          self._lambda, self._batch)
+            U, H, aU, aH = (torch.from_numpy(np.ascontiguousarray(t)) for t in out[:4])
+            return U, H, aU, aH, torch.from_numpy(compose_reference(F, H.numpy())), out[4]
+        p, j = be.to_device(m.indptr, torch.int32), be.to_device(m.indices, torch.int32)
+        feat = be.item_features(F, H.dtype)
+        counts, _ = be.warp_feat_epochs(p, j, m.nnz, 0, self.seed, 0, 0, n_iter, self._batch, T, margin, w, feat, U, H, aU, aH, self._lr,
+                                        self._lambda)
+        return U, H, aU, aH, be.compose_rows(feat, H), [tuple(int(c) for c in row) for row in counts.cpu().numpy()]
