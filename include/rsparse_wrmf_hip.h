@@ -1319,6 +1319,53 @@ int rsparse_hip_warp_feat_epochs_f64_device(const int32_t* d_p, const int32_t* d
                                             double* d_H, double* d_V, double* d_aU, double* d_aH, int64_t* d_counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Logistic matrix factorisation (Johnson 2014) by its exact full gradient (wrmf_lmf.hip)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The definition (rsparse_amd/lmf.py states it in numpy: lmf_dense_reference, lmf_half_reference, lmf_fit_reference).  x: users x
+ * items, canonical CSR, values > 0; c_ui = alpha x_ui.  K = rank + 2: a user row is [x_u (rank), b_u, 1], an item row [y_i (rank), 1,
+ * b_i], so s_ui = row_u . row_i = x_u . y_i + b_u + b_i.  The coordinate that holds the 1 is FROZEN (K - 1 of users, K - 2 of
+ * items); lambda applies to the first `rank` coordinates only.  One half-iteration over the rows A (n_rows x K) against the fixed
+ * side B (n_str x K) and the side's CSR (p, j, x):
+ *     D[r, :]  = sum over ALL t < n_str of sigma(A[r] . B[t]) B[t, :]
+ *     Sp[r, :] = sum over the stored t of row r of c_rt (1 - sigma(A[r] . B[j_t])) B[j_t, :]
+ *     g        = Sp - D - lambda A[r] on the first `rank` coordinates (without the lambda term on the others); g[frozen] = 0
+ *     a'       = a + g g per coordinate (float64, from 0)
+ *     A'[r, c] = A[r, c] + lr g[c] / sqrt(a'[c]) where a'[c] > 0 and g[c] != 0, otherwise unchanged; rounded once to float
+ * An iteration is the user half (B = the items) and then the item half (B = the new users, on the transposed CSR): alternating
+ * Adagrad ascent on the log-likelihood
+ *     sum_stored c s - sum_stored c softplus(s) - sum_all softplus(s) - lambda / 2 (|X|^2 + |Y|^2),   softplus(s) = max(s, 0) +
+ *     log1p(exp(-|s|)).
+ * D runs on the fp32 matrix cores (exact products, fp32 accumulation, v_exp_f32 / v_rcp_f32 sigmoid): it is held to the float64
+ * definition by the error bound of DESIGN.md 3.37, not bit for bit; everything else is float64 arithmetic with one rounding.
+ * No sampler and no atomics: a repeated call returns the same bits.
+ *
+ * The streamed side may be cut into slices of slice_rows rows (a multiple of 32; 0: planned from n_rows and n_str alone, never from
+ * the device), each with its own fp32 partial of D; the step adds them in ascending order.  rsparse_hip_lmf_slices returns the
+ * number of slices (or -1 for arguments the entries below refuse) and, where slice_rows_out is not NULL, their length.
+ * A row of more than RSPARSE_HIP_LMF_LONG_ROW entries is taken by a whole workgroup of the step kernel. */
+#define RSPARSE_HIP_LMF_MAX_K 128
+#define RSPARSE_HIP_LMF_LONG_ROW 512
+int rsparse_hip_lmf_slices(int n_rows, int n_str, int slice_rows, int* slice_rows_out);
+
+/* d_D: n_slices x n_rows x K floats, slice-major; d_softplus (nullable): n_slices x n_rows doubles, the rows' sums over the slice of
+ * softplus(A[r] . B[t]).  NULL or negative arguments, n_str < 1, K < 1 or a slice_rows that is no multiple of 32:
+ * RSPARSE_HIP_ERR_INVALID; K > RSPARSE_HIP_LMF_MAX_K: RSPARSE_HIP_ERR_UNSUPPORTED. */
+int rsparse_hip_lmf_dense_device(const float* d_A, int n_rows, const float* d_B, int n_str, int K, int slice_rows, float* d_D,
+                                 double* d_softplus, void* stream);
+/* the sparse term, the gradient against the sum of the n_slices partials d_D, and the update of d_A (n_rows x K) and d_aA (its
+ * float64 Adagrad state) in place.  0 <= rank <= K, frozen in [-1, K) (-1: none).  d_rowsums (nullable, n_rows doubles): per row
+ * sum_stored (c s - c softplus(s)), minus the row's entries of d_softplus (nullable, as above) */
+int rsparse_hip_lmf_step_device(const int32_t* d_p, const int32_t* d_j, const float* d_x, int n_rows, int n_str, double alpha,
+                                float* d_A, double* d_aA, const float* d_B, const float* d_D, int n_slices, const double* d_softplus,
+                                int K, int rank, int frozen, double learning_rate, double lambda, double* d_rowsums, void* stream);
+/* both of the above, the partials in the library's grow-only workspace; d_rowsums (nullable): the rows' shares of the
+ * log-likelihood without the lambda term, at the factors the half started from */
+int rsparse_hip_lmf_half_device(const int32_t* d_p, const int32_t* d_j, const float* d_x, int n_rows, int n_str, double alpha,
+                                float* d_A, double* d_aA, const float* d_B, int K, int rank, int frozen, double learning_rate,
+                                double lambda, int slice_rows, double* d_rowsums, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * why this item: per-item contributions to a score (Hu, Koren and Volinsky, section 5; `explain` of the `implicit` library)
  * ---------------------------------------------------------------------------------------------- */
 

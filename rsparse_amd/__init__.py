@@ -22,6 +22,8 @@ Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit
                               on the device, equal to the numpy definition; WRMF's inference surface with an SGD fold-in
   rsparse_amd.WARP            BPR with a searched negative and a rank weight (Weston et al. 2011): up to 64 draw-and-score trials per
                               slot in one kernel on the device, equal to the numpy definition; BPR's surface
+  rsparse_amd.LogisticMF      logistic matrix factorisation (Johnson 2014) by its exact full gradient: sigma(U V') V fused on the fp32
+                              matrix cores, alternating Adagrad ascent, no sampling and no atomics; WRMF's inference surface
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
   rsparse_amd.engine          device-resident, row-sharded driver (one process per GPU)
   rsparse_amd.synth           synthetic interaction matrices for the BASELINE configs
@@ -68,6 +70,9 @@ def __getattr__(name):
                 "warp_feat_fit_reference"):
         from . import warp
         return getattr(warp, name)
+    if name in ("LogisticMF", "lmf_dense_reference", "lmf_half_reference", "lmf_loglik_reference", "lmf_fit_reference"):
+        from . import lmf
+        return getattr(lmf, name)
     if name == "metrics":
         import importlib
         return importlib.import_module(".metrics", __name__)

@@ -26,6 +26,7 @@ EASE_CELLS_RATIO = 16   # a row of m cells is scored at its cells, not as a dens
 SLIM_LDS_SUPPORT = 2048   # RSPARSE_HIP_SLIM_LDS_SUPPORT: the support entries of a SLIM column (wrmf_slim.hip) that stay in LDS
 WARP_MAX_TRIALS = 64   # RSPARSE_HIP_WARP_MAX_TRIALS: the trials of one WARP search, at most
 BPR_CHUNK = 64   # RSPARSE_HIP_BPR_CHUNK: consecutive contributions of a destination row that are summed as one chunk (wrmf_bpr.hip)
+LMF_MAX_K, LMF_LONG_ROW = 128, 512   # RSPARSE_HIP_LMF_MAX_K / _LONG_ROW: the widest factor row and the row-length edge of wrmf_lmf.hip
 RANKS_BATCH = 1024  # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that the rank count takes at a time
 
 _c_int, _c_uint, _c_dbl, _c_i64, _c_u64 = ctypes.c_int, ctypes.c_uint, ctypes.c_double, ctypes.c_int64, ctypes.c_uint64
@@ -178,6 +179,15 @@ SIGNATURES = {
     **{"rsparse_hip_bpr_feat_%s%s_device" % (n, f): (_c_int, _BPR_HEAD + _FEAT_TAIL) for n in ("step", "epochs") for f in ("", "_f64")},
     **{"rsparse_hip_warp_feat_%s%s_device" % (n, f): (_c_int, _WARP_HEAD + [_c_dbl, _c_dbl, _c_int] + _FEAT_TAIL)
        for n in ("step", "epochs") for f in ("", "_f64")},
+    # logistic MF: (A, n_rows, B, n_str, K, slice_rows, D, softplus, stream); (p, j, x, n_rows, n_str, alpha, A, aA, B, D, n_slices,
+    # softplus, K, rank, frozen, lr, lambda, rowsums, stream); (p, j, x, n_rows, n_str, alpha, A, aA, B, K, rank, frozen, lr, lambda,
+    # slice_rows, rowsums, stream)
+    "rsparse_hip_lmf_slices": (_c_int, [_c_int, _c_int, _c_int, ctypes.POINTER(_c_int)]),
+    "rsparse_hip_lmf_dense_device": (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
+    "rsparse_hip_lmf_step_device": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_dbl, _vp, _vp, _vp, _vp, _c_int, _vp, _c_int, _c_int, _c_int,
+                                             _c_dbl, _c_dbl, _vp, _vp]),
+    "rsparse_hip_lmf_half_device": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_dbl, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _c_dbl,
+                                             _c_int, _vp, _vp]),
     "rsparse_hip_top_candidates_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl, _vp,
                                                    _vp, _vp]),
     "rsparse_hip_top_candidates_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl,

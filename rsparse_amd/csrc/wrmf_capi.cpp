@@ -68,6 +68,7 @@ struct Workspace {
   GrowBuf<double> score_buf{all};   // pointwise predictions (wrmf_score.hip): the scores of a call that asks for the error sums only;
                                     // top-k within candidate lists (wrmf_candidates.hip): its scores / keys, bits and row lists
   GrowBuf<double> softals_buf{all};   // soft-ALS half-iteration (wrmf_softals.hip): w, s, t and the partial sums of split rows
+  GrowBuf<double> lmf_buf{all};   // logistic MF (wrmf_lmf.hip): the slices' softplus sums and fp32 partials of the dense term
   GrowBuf<char> knn_buf{all};     // ItemKNN (wrmf_itemknn.hip): a batch of dense rows, all zeros between calls
   bool knn_dirty = false;         // ... unless a call failed between its scatter and its zeroing
   GrowBuf<float> mf_G{all};       // wrmf_chol_mf.hip at rank 65..127: XtX padded to 128 x 128
@@ -2022,6 +2023,80 @@ RSPARSE_WARP_FEAT_ENTRY(rsparse_hip_warp_feat_epochs_f64_device, double, bpr_epo
 #undef RSPARSE_WARP_FEAT_ENTRY
 #undef RSPARSE_FEAT_BODY
 #undef RSPARSE_FEAT_TAIL
+
+// Logistic MF (wrmf_lmf.hip)
+namespace {
+// what every entry refuses before a device is touched -> the plan of the streamed side
+int lmf_args(bool null_arg, int n_rows, int n_str, int K, int slice_rows, LmfPlan& plan) {
+  if (null_arg) return fail(RSPARSE_HIP_ERR_INVALID, "NULL array");
+  if (n_rows < 0 || n_str < 1 || K < 1 || slice_rows < 0)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, n_str < 1, K < 1 or slice_rows < 0)");
+  if (slice_rows % 32) return fail(RSPARSE_HIP_ERR_INVALID, "slice_rows must be a multiple of 32");
+  if (K > RSPARSE_HIP_LMF_MAX_K) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "K > 128 is not on the device path");
+  plan = lmf_plan(n_rows, n_str, slice_rows);
+  if (plan.n_slices > 65535) return fail(RSPARSE_HIP_ERR_INVALID, "more than 65535 slices");
+  return RSPARSE_HIP_OK;
+}
+int lmf_step_args(bool null_arg, int n_rows, int n_str, int n_slices, int K, int rank, int frozen, double alpha, double lr, double lambda) {
+  if (null_arg) return fail(RSPARSE_HIP_ERR_INVALID, "NULL array");
+  if (n_rows < 0 || n_str < 1 || K < 1 || n_slices < 1 || rank < 0 || rank > K || frozen < -1 || frozen >= K)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, n_str < 1, K < 1, n_slices < 1, rank or frozen outside K)");
+  if (!(alpha >= 0.0) || !(lr >= 0.0) || !(lambda >= 0.0) || alpha > 1e300 || lr > 1e300 || lambda > 1e300)
+    return fail(RSPARSE_HIP_ERR_INVALID, "alpha, learning_rate and lambda must be finite and >= 0");
+  if (K > RSPARSE_HIP_LMF_MAX_K) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "K > 128 is not on the device path");
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+
+int rsparse_hip_lmf_slices(int n_rows, int n_str, int slice_rows, int* slice_rows_out) {
+  LmfPlan plan;
+  if (lmf_args(false, n_rows, n_str, 1, slice_rows, plan)) return -1;
+  if (slice_rows_out) *slice_rows_out = plan.slice_rows;
+  return plan.n_slices;
+}
+
+int rsparse_hip_lmf_dense_device(const float* d_A, int n_rows, const float* d_B, int n_str, int K, int slice_rows, float* d_D,
+                                 double* d_softplus, void* stream) {
+  LmfPlan plan;
+  if (int rc = lmf_args(!d_A || !d_B || !d_D, n_rows, n_str, K, slice_rows, plan)) return rc;
+  hipError_t e = launch_lmf_dense(d_A, n_rows, d_B, n_str, K, plan, d_D, d_softplus, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_lmf_dense");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_lmf_step_device(const int32_t* d_p, const int32_t* d_j, const float* d_x, int n_rows, int n_str, double alpha,
+                                float* d_A, double* d_aA, const float* d_B, const float* d_D, int n_slices, const double* d_softplus,
+                                int K, int rank, int frozen, double learning_rate, double lambda, double* d_rowsums, void* stream) {
+  if (int rc = lmf_step_args(!d_p || !d_j || !d_x || !d_A || !d_aA || !d_B || !d_D, n_rows, n_str, n_slices, K, rank, frozen, alpha,
+                             learning_rate, lambda))
+    return rc;
+  hipError_t e = launch_lmf_step(d_p, d_j, d_x, n_rows, n_str, alpha, d_A, d_aA, d_B, d_D, n_slices, d_softplus, K, rank, frozen,
+                                 learning_rate, lambda, d_rowsums, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_lmf_step");
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_lmf_half_device(const int32_t* d_p, const int32_t* d_j, const float* d_x, int n_rows, int n_str, double alpha,
+                                float* d_A, double* d_aA, const float* d_B, int K, int rank, int frozen, double learning_rate,
+                                double lambda, int slice_rows, double* d_rowsums, void* stream) {
+  LmfPlan plan;
+  if (int rc = lmf_args(!d_p || !d_j || !d_x || !d_A || !d_aA || !d_B, n_rows, n_str, K, slice_rows, plan)) return rc;
+  if (int rc = lmf_step_args(false, n_rows, n_str, plan.n_slices, K, rank, frozen, alpha, learning_rate, lambda)) return rc;
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = g_ws.ensure_device()) return rc;
+  // the slices' softplus sums (doubles) in front of their partials of D (floats)
+  const size_t cells = (size_t)plan.n_slices * (size_t)n_rows, nsp = d_rowsums ? (cells + 1) / 2 * 2 : 0;   // (D stays 16-byte aligned)
+  HIP_TRY(g_ws.lmf_buf.ensure(nsp + (cells * (size_t)K + 1) / 2));
+  double* sp = d_rowsums ? (double*)g_ws.lmf_buf : nullptr;
+  float* D = reinterpret_cast<float*>((double*)g_ws.lmf_buf + nsp);
+  hipError_t e = launch_lmf_dense(d_A, n_rows, d_B, n_str, K, plan, D, sp, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_lmf_dense");
+  e = launch_lmf_step(d_p, d_j, d_x, n_rows, n_str, alpha, d_A, d_aA, d_B, D, plan.n_slices, sp, K, rank, frozen, learning_rate, lambda,
+                      d_rowsums, s);
+  if (e != hipSuccess) return hip_fail(e, "launch_lmf_step");
+  return RSPARSE_HIP_OK;
+}
 
 namespace {
 // the device form of both samplers: d_cum == nullptr is the uniform stream, otherwise the weighted one under that prefix

@@ -404,6 +404,21 @@ template <class T>
 hipError_t launch_softals_half(const int32_t* P, const int32_t* J, const T* X, const T* M, const T* W, int n_rows, int n_cols, int r,
                                bool res, bool has_t, T* out, double* sumsq, double* ws, hipStream_t s);
 
+// Logistic MF (wrmf_lmf.hip; defined in rsparse_wrmf_hip.h), fp32 factors, 1 <= K <= 128.  plan: how the streamed side's n_str
+// rows are cut (slice_rows = 0: planned from n_rows and n_str alone; else that length, a multiple of 32).  dense: D[s] (n_rows x K,
+// one per slice) = sum over the slice's t of sigma(A[r] . B[t]) B[t], softplus (nullable: n_slices x n_rows doubles) the rows' sums of
+// softplus(A[r] . B[t]).  step: the sparse term over the CSR (P, J, X), the gradient against the slices' sum, and the Adagrad
+// update of A and aA in place; rowsum (nullable): per row sum_stored (c s - c softplus(s)) minus the slices' softplus sums.
+struct LmfPlan {
+  int slice_rows = 0, n_slices = 0;
+};
+LmfPlan lmf_plan(int n_rows, int n_str, int slice_rows);
+hipError_t launch_lmf_dense(const float* A, int n_rows, const float* B, int n_str, int K, const LmfPlan& plan, float* D, double* softplus,
+                            hipStream_t s);
+hipError_t launch_lmf_step(const int32_t* P, const int32_t* J, const float* X, int n_rows, int n_str, double alpha, float* A, double* aA,
+                           const float* B, const float* D, int n_slices, const double* softplus, int K, int rank, int frozen, double lr,
+                           double lambda, double* rowsum, hipStream_t s);
+
 // ItemKNN (wrmf_itemknn.hip; defined in rsparse_wrmf_hip.h).  `rows` dense rows of n_items cells per batch in ws (uint32 cells
 // for the binary neighbours, uint64 for the weighted ones and for the lists), which is all zeros on entry and again when the
 // enqueued work is done.  h_ip: the host copy of ip[item0 .. item1]; h_xp: of xp[0 .. n_rows].  1 <= K <= 256, 1 <= k <= 1024.

@@ -1058,6 +1058,69 @@ class HipBackend:
                         aV, lr, lam, update_items, counts)
         return counts[:int(n_epochs)]
 
+    def lmf_slices(self, n_rows, n_str, slice_rows=0):
+        """how the logistic-MF dense launch cuts the n_str streamed rows (slice_rows = 0: planned from the two sizes alone)
+        -> (the number of slices, their length)"""
+        sr = ctypes.c_int(0)
+        n = self.lib.rsparse_hip_lmf_slices(int(n_rows), int(n_str), int(slice_rows), ctypes.byref(sr))
+        if n < 0:
+            raise ValueError("lmf_slices: n_rows >= 0, n_str >= 1 and a slice_rows that is a multiple of 32 are needed")
+        return n, sr.value
+
+    @staticmethod
+    def _lmf_sides(A, B):
+        assert A.dtype == torch.float32 and B.dtype == torch.float32 and A.is_cuda and A.is_contiguous() and B.is_contiguous()
+        assert A.dim() == 2 and B.dim() == 2 and A.shape[1] == B.shape[1]
+        return int(A.shape[0]), int(B.shape[0]), int(A.shape[1])
+
+    def lmf_dense(self, A, B, slice_rows=0, want_softplus=False):
+        """the dense term of a logistic-MF half-iteration (lmf_dense_kernel of wrmf_lmf.hip; rsparse_amd.lmf.lmf_dense_reference
+        is the definition): D[s, r, :] = the sum over the rows t of slice s of B of sigma(A[r] . B[t]) B[t, :], on the fp32 matrix
+        cores.  A (n_rows x K), B (n_str x K): float32 on the device, K <= 128.  -> (D (n_slices, n_rows, K) float32, the rows'
+        softplus sums (n_slices, n_rows) float64 or None) on the device; the slices are to be added in ascending order."""
+        n_rows, n_str, K = self._lmf_sides(A, B)
+        n_slices, _ = self.lmf_slices(n_rows, n_str, slice_rows)
+        D = torch.empty((n_slices, n_rows, K), dtype=torch.float32, device=self.device)
+        sp = torch.empty((n_slices, n_rows), dtype=torch.float64, device=self.device) if want_softplus else None
+        some = lambda t: t.data_ptr() if t.numel() else B.data_ptr()   # (an empty tensor has no address to pass)
+        _lib.check(self.lib.rsparse_hip_lmf_dense_device(some(A), n_rows, B.data_ptr(), n_str, K, int(slice_rows), some(D),
+                                                         None if sp is None else some(sp), self._stream()))
+        return D, sp
+
+    def _lmf_csr(self, p, j, x, A, aA, n_str):
+        assert p.dtype == torch.int32 and j.dtype == torch.int32 and x.dtype == torch.float32 and x.numel() == j.numel()
+        assert aA.dtype == torch.float64 and aA.is_contiguous() and tuple(aA.shape) == tuple(A.shape) and p.numel() == A.shape[0] + 1
+        some = lambda t: t.data_ptr() if t.numel() else p.data_ptr()
+        return some(p), some(j), some(x), int(A.shape[0]), int(n_str)
+
+    def lmf_step(self, p, j, x, alpha, A, aA, B, D, rank, frozen, lr, lam, softplus=None, want_rowsums=False):
+        """the sparse term, the gradient against the sum of the slices D (n_slices, n_rows, K) and the Adagrad update of A and aA
+        (float64, A's shape) in place, over the CSR (p, j: int32; x: float32 values, c = alpha x) whose columns index B
+        (lmf_step_kernel; rsparse_amd.lmf.lmf_half_reference is the definition).  -> the rows' sum_stored (c s - c softplus(s))
+        minus their entries of `softplus` (float64 on the device), or None"""
+        n_rows, n_str, K = self._lmf_sides(A, B)
+        assert D.dtype == torch.float32 and D.is_contiguous() and D.dim() == 3 and tuple(D.shape[1:]) == (n_rows, K) and D.shape[0] >= 1
+        assert softplus is None or (softplus.dtype == torch.float64 and tuple(softplus.shape) == (D.shape[0], n_rows))
+        rows = torch.zeros(n_rows, dtype=torch.float64, device=self.device) if want_rowsums else None
+        some = lambda t: t.data_ptr() if t.numel() else p.data_ptr()
+        _lib.check(self.lib.rsparse_hip_lmf_step_device(*self._lmf_csr(p, j, x, A, aA, n_str), float(alpha), some(A), some(aA), B.data_ptr(),
+                                                        some(D), int(D.shape[0]), None if softplus is None else some(softplus), K,
+                                                        int(rank), int(frozen), float(lr), float(lam),
+                                                        None if rows is None else some(rows), self._stream()))
+        return rows
+
+    def lmf_half(self, p, j, x, alpha, A, aA, B, rank, frozen, lr, lam, slice_rows=0, want_rowsums=False):
+        """one logistic-MF half-iteration in place: `lmf_dense` into the library's workspace, then `lmf_step`; no host
+        synchronisation.  -> the rows' shares of the log-likelihood (without the lambda term) at the factors the half started
+        from, float64 on the device, or None"""
+        n_rows, n_str, K = self._lmf_sides(A, B)
+        rows = torch.zeros(n_rows, dtype=torch.float64, device=self.device) if want_rowsums else None
+        some = lambda t: t.data_ptr() if t.numel() else p.data_ptr()
+        _lib.check(self.lib.rsparse_hip_lmf_half_device(*self._lmf_csr(p, j, x, A, aA, n_str), float(alpha), some(A), some(aA), B.data_ptr(),
+                                                        K, int(rank), int(frozen), float(lr), float(lam), int(slice_rows),
+                                                        None if rows is None else some(rows), self._stream()))
+        return rows
+
     def item_features(self, F, dtype):
         """a canonical scipy CSR F (n_items x n_feat) -> (fp, fj, fx, cp, ci, cx, n_feat) on the device: F by item and, through
         `transpose_csc`, by feature; values of `dtype`"""

@@ -1601,7 +1601,7 @@ class WRMF:
         excl = np.unique(np.asarray(list(items_exclude), dtype=np.int64))
         if excl.size and (excl.min() < 0 or excl.max() >= n_item):
             raise ValueError("some of items_exclude indices are bigger than number of items")
-        c0, c1 = (1, self._rank - 1) if self._with_bias else (0, self._rank)   # [item_bias, latent ..., 1]: fit_transform
+        c0, c1 = self._latent_window()   # [item_bias, latent ..., 1]: fit_transform
         be = self._backend()
         ws, me = self._dist()
         from .engine import equal_bounds
