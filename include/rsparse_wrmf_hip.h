@@ -1366,6 +1366,92 @@ int rsparse_hip_lmf_half_device(const int32_t* d_p, const int32_t* d_j, const fl
                                 double lambda, int slice_rows, double* d_rowsums, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Second-order factorization machine (Rendle 2010) by deterministic mini-batch SGD (wrmf_fm.hip)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The definition (rsparse_amd/fm.py states it in numpy: fm_forward_reference, fm_step_reference, fm_fit_reference).  Every
+ * arithmetic operation is a separately rounded float64 operation on parameters widened from their type; nothing is fused.
+ *   x: n_rows x n_feat canonical CSR (p from 0, columns strictly ascending per row, no stored zero, finite values in the
+ *   parameters' type); y: +-1 (binomial) or any finite value (gaussian); omega: finite weights >= 0.  Parameters w0 (one
+ *   element), w (n_feat), V (n_feat x rank row-major) with float64 Adagrad states a0, aw, aV of the same shapes.
+ *   Steps: n_steps = ceil(n_rows / batch); step s holds the rows r = s, s + n_steps, ... ascending, numbered k = 0, 1, ...; a step
+ *   is computed from the snapshot (w0, w, V) at its start.
+ *   osum(list): the list cut into chunks of RSPARSE_HIP_BPR_CHUNK consecutive terms, a chunk summed sequentially from +0.0, the
+ *   chunk sums added sequentially to a total that starts at +0.0.
+ *   Forward, row r with entries e in ascending column (j_e, x_e):  t_ec = V[j_e, c] x_e;  s_c = osum_e(t_ec);  q_c = osum_e(t_ec
+ *   t_ec);  lin = osum_e(w[j_e] x_e);  pair = the BPR dot order over c of (s_c s_c - q_c) (16 partials over c = l, l + 16, ...,
+ *   then the 8/4/2/1 tree);  raw = (w0 + lin) + 0.5 pair.
+ *     binomial: z = 1 / (1 + E(y raw)), E the stated exponential of BPR; delta = (-(omega y)) z
+ *     gaussian: delta = omega (raw - y)
+ *   Backward, per destination, contributions in ascending k: column j linear osum_k(delta_k x), coordinate c osum_k((delta_k x)
+ *   (s_kc - V[j, c] x)), count = the stored entries of j in the step; intercept osum_k(delta_k), count = the step's rows.
+ *   Update of a coordinate theta with state a and count c >= 1 (the others keep their bits): g = total + (lambda c) theta;
+ *   a' = a + g g; theta' = theta - (lr g) / sqrt(a') unless a' == 0, rounded once.  lambda_w / lr_w for w, lambda_v / lr_v for V,
+ *   0 / lr_w for w0.
+ *   Trace per epoch: binomial the number of rows with y raw > 0 (uint64); gaussian osum_k(omega (raw - y)^2) per step, the step
+ *   sums added sequentially (double).  Predict: gaussian raw, binomial 1 / (1 + E(-raw)).
+ * Unlike the modelled-on Hogwild loop: mini-batches from a snapshot, a regulariser that multiplies the parameter and scales with
+ * the count, an Adagrad state from 0 added to before the division, no clipping, no factor 2 in the gaussian gradient.
+ * No float atomics: a repeated call returns the same bits.  A row of more than RSPARSE_HIP_FM_LONG_ROW entries is spread over a
+ * workgroup of the forward kernel.  Valid p arrays are preconditions of the `_device` entries (a column outside [0, n_feat) is read
+ * as the nearest valid one).  NULL or negative arguments, n_feat < 1, rank < 1, n_steps or batch < 1, a step outside [0, n_steps),
+ * a family that is neither, a rate or lambda that is negative or not finite: RSPARSE_HIP_ERR_INVALID; rank >
+ * RSPARSE_HIP_FM_MAX_RANK: RSPARSE_HIP_ERR_UNSUPPORTED. */
+#define RSPARSE_HIP_FM_MAX_RANK 128
+#define RSPARSE_HIP_FM_LONG_ROW 512
+#define RSPARSE_HIP_FM_BINOMIAL 0
+#define RSPARSE_HIP_FM_GAUSSIAN 1
+
+/* The backward index of (x, n_steps): the stored positions sorted by (step of the row, column), their k, the (step, column)
+ * segments and the chunks of the long ones.  d_index NULL: *index_bytes receives the bytes it needs and nothing else happens;
+ * otherwise the index is built into d_index (*index_bytes: its capacity) and the call waits for `stream`.  It does not depend on
+ * the values or their type. */
+int rsparse_hip_fm_index_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_feat, int64_t nnz, int n_steps, void* d_index,
+                                size_t* index_bytes, void* stream);
+/* The forward pass of one step, cnt = ceil((n_rows - step) / n_steps) rows.  With d_y (and d_omega; both indexed by row): d_raw
+ * (nullable), d_delta (cnt) and d_S (cnt x 16 ceil(rank / 16) doubles, zeros beyond rank) are written.  Without d_y: d_link (cnt),
+ * what predict returns.  Enqueued without synchronisation. */
+int rsparse_hip_fm_forward_device(const int32_t* d_p, const int32_t* d_j, const float* d_x, int n_rows, int n_feat, int step, int n_steps,
+                                  int rank, int family, const float* d_w0, const float* d_w, const float* d_V, const double* d_y,
+                                  const double* d_omega, double* d_raw, double* d_delta, double* d_S, double* d_link, void* stream);
+int rsparse_hip_fm_forward_f64_device(const int32_t* d_p, const int32_t* d_j, const double* d_x, int n_rows, int n_feat, int step,
+                                      int n_steps, int rank, int family, const double* d_w0, const double* d_w, const double* d_V,
+                                      const double* d_y, const double* d_omega, double* d_raw, double* d_delta, double* d_S,
+                                      double* d_link, void* stream);
+/* One step in place on the parameters and their states; d_trace (8 bytes) is ADDED to.  d_index: of this (x, n_steps).  Waits for
+ * `stream` before it returns (its scratch is freed). */
+int rsparse_hip_fm_step_device(const int32_t* d_p, const int32_t* d_j, const float* d_x, int n_rows, int n_feat, int64_t nnz,
+                               const void* d_index, int step, int n_steps, int rank, int family, int intercept, double learning_rate_w,
+                               double learning_rate_v, double lambda_w, double lambda_v, const double* d_y, const double* d_omega,
+                               float* d_w0, float* d_w, float* d_V, double* d_a0, double* d_aw, double* d_aV, void* d_trace, void* stream);
+int rsparse_hip_fm_step_f64_device(const int32_t* d_p, const int32_t* d_j, const double* d_x, int n_rows, int n_feat, int64_t nnz,
+                                   const void* d_index, int step, int n_steps, int rank, int family, int intercept,
+                                   double learning_rate_w, double learning_rate_v, double lambda_w, double lambda_v, const double* d_y,
+                                   const double* d_omega, double* d_w0, double* d_w, double* d_V, double* d_a0, double* d_aw,
+                                   double* d_aV, void* d_trace, void* stream);
+/* n_epochs epochs of ceil(n_rows / batch) steps each, on one stream with no host synchronisation between them; d_trace: 8 bytes
+ * per epoch, overwritten.  d_index: of (x, ceil(n_rows / batch)). */
+int rsparse_hip_fm_epochs_device(const int32_t* d_p, const int32_t* d_j, const float* d_x, int n_rows, int n_feat, int64_t nnz,
+                                 const void* d_index, int n_epochs, int batch, int rank, int family, int intercept,
+                                 double learning_rate_w, double learning_rate_v, double lambda_w, double lambda_v, const double* d_y,
+                                 const double* d_omega, float* d_w0, float* d_w, float* d_V, double* d_a0, double* d_aw, double* d_aV,
+                                 void* d_trace, void* stream);
+int rsparse_hip_fm_epochs_f64_device(const int32_t* d_p, const int32_t* d_j, const double* d_x, int n_rows, int n_feat, int64_t nnz,
+                                     const void* d_index, int n_epochs, int batch, int rank, int family, int intercept,
+                                     double learning_rate_w, double learning_rate_v, double lambda_w, double lambda_v, const double* d_y,
+                                     const double* d_omega, double* d_w0, double* d_w, double* d_V, double* d_a0, double* d_aw,
+                                     double* d_aV, void* d_trace, void* stream);
+/* Host arrays, double parameters.  fit: x is checked to be canonical, y is taken as it is (+-1 for binomial); w0 (1), w (n_feat), V
+ * (n_feat x rank row-major) and the states are IN/OUT, so a second call goes on where the first ended (V of a fresh model:
+ * rsparse_hip_init_factors with stream 1 and scale 0.01, everything else 0); trace: 8 bytes per epoch.  predict: out (n_rows). */
+int rsparse_hip_fm_fit(const int32_t* p, const int32_t* j, const double* x, int n_rows, int n_feat, const double* y, const double* omega,
+                       int n_epochs, int batch, int rank, int family, int intercept, double learning_rate_w, double learning_rate_v,
+                       double lambda_w, double lambda_v, double* w0, double* w, double* V, double* a0, double* aw, double* aV,
+                       void* trace);
+int rsparse_hip_fm_predict(const int32_t* p, const int32_t* j, const double* x, int n_rows, int n_feat, int rank, int family,
+                           const double* w0, const double* w, const double* V, double* out);
+
+/* ------------------------------------------------------------------------------------------------
  * why this item: per-item contributions to a score (Hu, Koren and Volinsky, section 5; `explain` of the `implicit` library)
  * ---------------------------------------------------------------------------------------------- */
 

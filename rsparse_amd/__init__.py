@@ -24,6 +24,9 @@ Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit
                               slot in one kernel on the device, equal to the numpy definition; BPR's surface
   rsparse_amd.LogisticMF      logistic matrix factorisation (Johnson 2014) by its exact full gradient: sigma(U V') V fused on the fp32
                               matrix cores, alternating Adagrad ascent, no sampling and no atomics; WRMF's inference surface
+  rsparse_amd.FactorizationMachine   second-order factorization machine (Rendle 2010) over a samples x features matrix, binomial or
+                              gaussian, by deterministic mini-batch SGD with per-coordinate Adagrad on the device, equal to the
+                              numpy definition; partial_fit / fit / predict
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
   rsparse_amd.engine          device-resident, row-sharded driver (one process per GPU)
   rsparse_amd.synth           synthetic interaction matrices for the BASELINE configs
@@ -73,6 +76,9 @@ def __getattr__(name):
     if name in ("LogisticMF", "lmf_dense_reference", "lmf_half_reference", "lmf_loglik_reference", "lmf_fit_reference"):
         from . import lmf
         return getattr(lmf, name)
+    if name in ("FactorizationMachine", "fm_forward_reference", "fm_step_reference", "fm_fit_reference", "fm_predict_reference"):
+        from . import fm
+        return getattr(fm, name)
     if name == "metrics":
         import importlib
         return importlib.import_module(".metrics", __name__)

@@ -27,6 +27,7 @@ SLIM_LDS_SUPPORT = 2048   # RSPARSE_HIP_SLIM_LDS_SUPPORT: the support entries of
 WARP_MAX_TRIALS = 64   # RSPARSE_HIP_WARP_MAX_TRIALS: the trials of one WARP search, at most
 BPR_CHUNK = 64   # RSPARSE_HIP_BPR_CHUNK: consecutive contributions of a destination row that are summed as one chunk (wrmf_bpr.hip)
 LMF_MAX_K, LMF_LONG_ROW = 128, 512   # RSPARSE_HIP_LMF_MAX_K / _LONG_ROW: the widest factor row and the row-length edge of wrmf_lmf.hip
+FM_MAX_RANK, FM_LONG_ROW = 128, 512   # RSPARSE_HIP_FM_MAX_RANK / _LONG_ROW: the widest V and the row-length edge of wrmf_fm.hip
 RANKS_BATCH = 1024  # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that the rank count takes at a time
 
 _c_int, _c_uint, _c_dbl, _c_i64, _c_u64 = ctypes.c_int, ctypes.c_uint, ctypes.c_double, ctypes.c_int64, ctypes.c_uint64
@@ -188,6 +189,15 @@ SIGNATURES = {
                                              _c_dbl, _c_dbl, _vp, _vp]),
     "rsparse_hip_lmf_half_device": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_dbl, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _c_dbl,
                                              _c_int, _vp, _vp]),
+    # factorization machine: (p, j, n_rows, n_feat, nnz, n_steps, index, index_bytes, stream); (p, j, x, n_rows, n_feat, step, n_steps,
+    # rank, family, w0, w, V, y, omega, raw, delta, S, link, stream); (p, j, x, n_rows, n_feat, nnz, index, step | n_epochs, n_steps |
+    # batch, rank, family, intercept, lr_w, lr_v, lambda_w, lambda_v, y, omega, w0, w, V, a0, aw, aV, trace, stream)
+    "rsparse_hip_fm_index_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_i64, _c_int, _vp, ctypes.POINTER(ctypes.c_size_t), _vp]),
+    **{"rsparse_hip_fm_forward%s_device" % f: (_c_int, [_vp] * 3 + [_c_int] * 6 + [_vp] * 10) for f in ("", "_f64")},
+    **{"rsparse_hip_fm_%s%s_device" % (n, f): (_c_int, [_vp] * 3 + [_c_int, _c_int, _c_i64, _vp] + [_c_int] * 5 + [_c_dbl] * 4 + [_vp] * 10)
+       for n in ("step", "epochs") for f in ("", "_f64")},
+    "rsparse_hip_fm_fit": (_c_int, [_vp] * 3 + [_c_int, _c_int, _vp, _vp] + [_c_int] * 5 + [_c_dbl] * 4 + [_vp] * 7),
+    "rsparse_hip_fm_predict": (_c_int, [_vp] * 3 + [_c_int] * 4 + [_vp] * 4),
     "rsparse_hip_top_candidates_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl, _vp,
                                                    _vp, _vp]),
     "rsparse_hip_top_candidates_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl,

@@ -2098,6 +2098,113 @@ int rsparse_hip_lmf_half_device(const int32_t* d_p, const int32_t* d_j, const fl
   return RSPARSE_HIP_OK;
 }
 
+extern "C++" {
+namespace {
+// the factorization machine (wrmf_fm.hip), both precisions; the host forms rsparse_hip_fm_fit / _predict: wrmf_capi_host.cpp
+int fm_args(bool missing, int n_rows, int n_feat, int64_t nnz, int n_steps, const char* steps_name, int rank, int family) {
+  if (missing) return fail(RSPARSE_HIP_ERR_INVALID, "the matrix, a parameter, a state, a target or an output is NULL");
+  if (n_rows < 0 || n_feat < 1 || nnz < 0 || nnz > 0x7fffffffLL)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, n_feat < 1, nnz < 0 or nnz >= 2^31)");
+  if (n_steps < 1) return fail(RSPARSE_HIP_ERR_INVALID, std::string(steps_name) + " < 1");
+  if (rank < 1) return fail(RSPARSE_HIP_ERR_INVALID, "rank < 1");
+  if (family != RSPARSE_HIP_FM_BINOMIAL && family != RSPARSE_HIP_FM_GAUSSIAN)
+    return fail(RSPARSE_HIP_ERR_INVALID, "family is neither RSPARSE_HIP_FM_BINOMIAL nor RSPARSE_HIP_FM_GAUSSIAN");
+  if (rank > RSPARSE_HIP_FM_MAX_RANK)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > " + std::to_string(RSPARSE_HIP_FM_MAX_RANK) + " is not on the device path");
+  return RSPARSE_HIP_OK;
+}
+
+FmData fm_data_of(const int32_t* d_p, const int32_t* d_j, const void* d_x, int n_rows, int n_feat, int64_t nnz, int n_steps, int rank,
+                  int family) {
+  FmData d;
+  d.p = d_p; d.j = d_j; d.x = d_x; d.n_rows = n_rows; d.n_feat = n_feat; d.nnz = nnz; d.n_steps = n_steps; d.rank = rank; d.family = family;
+  return d;
+}
+
+template <class T>
+int fm_forward_device(const int32_t* d_p, const int32_t* d_j, const T* d_x, int n_rows, int n_feat, int step, int n_steps, int rank,
+                      int family, const T* d_w0, const T* d_w, const T* d_V, const double* d_y, const double* d_omega, double* d_raw,
+                      double* d_delta, double* d_S, double* d_link, void* stream) {
+  const bool missing = !d_p || !d_j || !d_x || !d_w0 || !d_w || !d_V || (d_y ? (!d_omega || !d_delta || !d_S) : !d_link);
+  if (int rc = fm_args(missing, n_rows, n_feat, 0, n_steps, "n_steps", rank, family)) return rc;
+  if (step < 0 || step >= n_steps) return fail(RSPARSE_HIP_ERR_INVALID, "step outside [0, n_steps)");
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  hipError_t e = launch_fm_forward<T>(fm_data_of(d_p, d_j, d_x, n_rows, n_feat, 0, n_steps, rank, family), step, d_w0, d_w, d_V, d_y,
+                                      d_omega, d_raw, d_delta, d_S, d_link, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_fm_forward");
+  return RSPARSE_HIP_OK;
+}
+
+// the step `only_step` (n_epochs = 1) or whole epochs (only_step < 0) of n_steps steps
+template <class T>
+int fm_run_device(const int32_t* d_p, const int32_t* d_j, const T* d_x, int n_rows, int n_feat, int64_t nnz, const void* d_index,
+                  int n_epochs, int only_step, int n_steps, const char* steps_name, int rank, int family, int intercept, double lr_w,
+                  double lr_v, double lambda_w, double lambda_v, const double* d_y, const double* d_omega, T* d_w0, T* d_w, T* d_V,
+                  double* d_a0, double* d_aw, double* d_aV, void* d_trace, void* stream) {
+  const bool missing = !d_p || !d_j || !d_x || !d_index || !d_y || !d_omega || !d_w0 || !d_w || !d_V || !d_a0 || !d_aw || !d_aV || !d_trace;
+  if (int rc = fm_args(missing, n_rows, n_feat, nnz, n_steps, steps_name, rank, family)) return rc;
+  const auto ok = [](double v) { return v >= 0.0 && v <= 1.7976931348623157e308; };   // (NaN fails both)
+  if (!ok(lr_w) || !ok(lr_v) || !ok(lambda_w) || !ok(lambda_v))
+    return fail(RSPARSE_HIP_ERR_INVALID, "a learning rate or a lambda is negative or not finite");
+  if (n_epochs < 0) return fail(RSPARSE_HIP_ERR_INVALID, "n_epochs < 0");
+  hipStream_t s = (hipStream_t)stream;
+  if (only_step < 0 && n_epochs) HIP_TRY(hipMemsetAsync(d_trace, 0, (size_t)n_epochs * 8, s));
+  if (n_rows == 0 || n_epochs == 0) return RSPARSE_HIP_OK;
+  FmOpt o;
+  o.intercept = intercept != 0; o.lr_w = lr_w; o.lr_v = lr_v; o.lambda_w = lambda_w; o.lambda_v = lambda_v;
+  hipError_t e = launch_fm_run<T>(fm_data_of(d_p, d_j, d_x, n_rows, n_feat, nnz, n_steps, rank, family), d_index, o, n_epochs, only_step,
+                                  d_y, d_omega, d_w0, d_w, d_V, d_a0, d_aw, d_aV, d_trace, s);
+  if (e == hipErrorInvalidValue) return fail(RSPARSE_HIP_ERR_INVALID, "d_index was not built for this nnz and these steps");
+  if (e != hipSuccess) return hip_fail(e, "launch_fm_run");
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int rsparse_hip_fm_index_device(const int32_t* d_p, const int32_t* d_j, int n_rows, int n_feat, int64_t nnz, int n_steps, void* d_index,
+                                size_t* index_bytes, void* stream) {
+  if (!index_bytes) return fail(RSPARSE_HIP_ERR_INVALID, "index_bytes is NULL");
+  if (int rc = fm_args(false, n_rows, n_feat, nnz, n_steps, "n_steps", 1, RSPARSE_HIP_FM_BINOMIAL)) return rc;
+  if (n_steps > (n_rows > 0 ? n_rows : 1)) return fail(RSPARSE_HIP_ERR_INVALID, "n_steps > n_rows");
+  const size_t need = fm_index_bytes(nnz, n_steps);
+  if (!d_index) {
+    *index_bytes = need;
+    return RSPARSE_HIP_OK;
+  }
+  if (!d_p || !d_j) return fail(RSPARSE_HIP_ERR_INVALID, "the matrix is NULL");
+  if (*index_bytes < need) return fail(RSPARSE_HIP_ERR_INVALID, "d_index holds fewer bytes than the index needs");
+  hipError_t e = launch_fm_index(fm_data_of(d_p, d_j, nullptr, n_rows, n_feat, nnz, n_steps, 1, 0), d_index, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_fm_index");
+  return RSPARSE_HIP_OK;
+}
+
+#define RSPARSE_FM_ENTRIES(SUFFIX, T)                                                                                                   \
+  int rsparse_hip_fm_forward##SUFFIX(const int32_t* d_p, const int32_t* d_j, const T* d_x, int n_rows, int n_feat, int step, int n_steps, \
+                                     int rank, int family, const T* d_w0, const T* d_w, const T* d_V, const double* d_y,                 \
+                                     const double* d_omega, double* d_raw, double* d_delta, double* d_S, double* d_link, void* stream) { \
+    return fm_forward_device<T>(d_p, d_j, d_x, n_rows, n_feat, step, n_steps, rank, family, d_w0, d_w, d_V, d_y, d_omega, d_raw,         \
+                                d_delta, d_S, d_link, stream);                                                                           \
+  }                                                                                                                                       \
+  int rsparse_hip_fm_step##SUFFIX(const int32_t* d_p, const int32_t* d_j, const T* d_x, int n_rows, int n_feat, int64_t nnz,             \
+                                  const void* d_index, int step, int n_steps, int rank, int family, int intercept, double lr_w,          \
+                                  double lr_v, double lambda_w, double lambda_v, const double* d_y, const double* d_omega, T* d_w0,       \
+                                  T* d_w, T* d_V, double* d_a0, double* d_aw, double* d_aV, void* d_trace, void* stream) {                \
+    if (step < 0 || step >= n_steps) return fail(RSPARSE_HIP_ERR_INVALID, "step outside [0, n_steps)");                                  \
+    return fm_run_device<T>(d_p, d_j, d_x, n_rows, n_feat, nnz, d_index, 1, step, n_steps, "n_steps", rank, family, intercept, lr_w,     \
+                            lr_v, lambda_w, lambda_v, d_y, d_omega, d_w0, d_w, d_V, d_a0, d_aw, d_aV, d_trace, stream);                   \
+  }                                                                                                                                       \
+  int rsparse_hip_fm_epochs##SUFFIX(const int32_t* d_p, const int32_t* d_j, const T* d_x, int n_rows, int n_feat, int64_t nnz,           \
+                                    const void* d_index, int n_epochs, int batch, int rank, int family, int intercept, double lr_w,      \
+                                    double lr_v, double lambda_w, double lambda_v, const double* d_y, const double* d_omega, T* d_w0,     \
+                                    T* d_w, T* d_V, double* d_a0, double* d_aw, double* d_aV, void* d_trace, void* stream) {              \
+    const int n_steps = batch < 1 ? 0 : (n_rows <= 0 ? 1 : (int)(((int64_t)n_rows + batch - 1) / batch));                                \
+    return fm_run_device<T>(d_p, d_j, d_x, n_rows, n_feat, nnz, d_index, n_epochs, -1, n_steps, "batch", rank, family, intercept, lr_w,  \
+                            lr_v, lambda_w, lambda_v, d_y, d_omega, d_w0, d_w, d_V, d_a0, d_aw, d_aV, d_trace, stream);                   \
+  }
+RSPARSE_FM_ENTRIES(_device, float)
+RSPARSE_FM_ENTRIES(_f64_device, double)
+#undef RSPARSE_FM_ENTRIES
+
 namespace {
 // the device form of both samplers: d_cum == nullptr is the uniform stream, otherwise the weighted one under that prefix
 int sample_negatives_device(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* d_seen_p,

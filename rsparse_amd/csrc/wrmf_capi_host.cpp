@@ -1156,6 +1156,97 @@ int rsparse_hip_warp_fit(const int32_t* p, const int32_t* j, int n_users, int n_
 
 extern "C++" {
 namespace {
+// the canonical samples x features matrix of the factorization machine on the device (dP, dJ, dX)
+int fm_upload(const int32_t* p, const int32_t* j, const double* x, int n_rows, int n_feat, int rank, DevBuf& dP, DevBuf& dJ, DevBuf& dX,
+              size_t& nnz) {
+  if (n_rows < 0 || n_feat < 1 || rank < 1) return fail(RSPARSE_HIP_ERR_INVALID, "n_rows < 0, n_feat < 1 or rank < 1");
+  if (rank > RSPARSE_HIP_FM_MAX_RANK)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > " + std::to_string(RSPARSE_HIP_FM_MAX_RANK) + " is not on the device path");
+  if (int rc = check_csr(p, n_rows, "p")) return rc;
+  nnz = (size_t)p[n_rows];
+  if (nnz && (!j || !x)) return fail(RSPARSE_HIP_ERR_INVALID, "j or x is NULL");
+  if (int rc = check_columns(p, j, n_rows, n_feat, "j")) return rc;
+  for (size_t e = 0; e < nnz; e++)
+    if (!(x[e] - x[e] == 0.0) || x[e] == 0.0) return fail(RSPARSE_HIP_ERR_INVALID, "x holds a stored zero or a value that is not finite");
+  HIP_TRY(upload_host(dP, p, (size_t)n_rows + 1));
+  HIP_TRY(upload_host(dJ, j, nnz));
+  HIP_TRY(upload_host(dX, x, nnz));
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int rsparse_hip_fm_fit(const int32_t* p, const int32_t* j, const double* x, int n_rows, int n_feat, const double* y, const double* omega,
+                       int n_epochs, int batch, int rank, int family, int intercept, double learning_rate_w, double learning_rate_v,
+                       double lambda_w, double lambda_v, double* w0, double* w, double* V, double* a0, double* aw, double* aV,
+                       void* trace) {
+  if (!p || !y || !omega || !w0 || !w || !V || !a0 || !aw || !aV || !trace)
+    return fail(RSPARSE_HIP_ERR_INVALID, "the matrix, a target, a parameter, a state or the trace is NULL");
+  if (n_epochs < 0 || batch < 1) return fail(RSPARSE_HIP_ERR_INVALID, "n_epochs < 0 or batch < 1");
+  DevBuf dP, dJ, dX, dY, dO, dW0, dW, dV, dA0, dAW, dAV, dT, dI;
+  size_t nnz = 0;
+  if (int rc = fm_upload(p, j, x, n_rows, n_feat, rank, dP, dJ, dX, nnz)) return rc;
+  for (int r = 0; r < n_rows; r++)
+    if (!(y[r] - y[r] == 0.0) || !(omega[r] >= 0.0 && omega[r] <= 1.7976931348623157e308) ||
+        (family == RSPARSE_HIP_FM_BINOMIAL && y[r] != 1.0 && y[r] != -1.0))
+      return fail(RSPARSE_HIP_ERR_INVALID, "y is not finite (binomial: not +-1) or a weight is negative or not finite");
+  std::memset(trace, 0, (size_t)n_epochs * 8);
+  if (n_rows == 0 || n_epochs == 0) return RSPARSE_HIP_OK;
+  const size_t d = (size_t)n_feat, k = (size_t)rank;
+  const int n_steps = (int)(((int64_t)n_rows + batch - 1) / batch);
+  HIP_TRY(upload_host(dY, y, (size_t)n_rows));
+  HIP_TRY(upload_host(dO, omega, (size_t)n_rows));
+  HIP_TRY(upload_host(dW0, w0, 1));
+  HIP_TRY(upload_host(dW, w, d));
+  HIP_TRY(upload_host(dV, V, d * k));
+  HIP_TRY(upload_host(dA0, a0, 1));
+  HIP_TRY(upload_host(dAW, aw, d));
+  HIP_TRY(upload_host(dAV, aV, d * k));
+  HIP_TRY(dT.alloc((size_t)n_epochs * 8));
+  size_t bytes = 0;
+  int rc = rsparse_hip_fm_index_device(dP.as<int32_t>(), dJ.as<int32_t>(), n_rows, n_feat, (int64_t)nnz, n_steps, nullptr, &bytes, nullptr);
+  if (rc) return rc;
+  HIP_TRY(dI.alloc(bytes));
+  if ((rc = rsparse_hip_fm_index_device(dP.as<int32_t>(), dJ.as<int32_t>(), n_rows, n_feat, (int64_t)nnz, n_steps, dI.p, &bytes, nullptr)))
+    return rc;
+  rc = rsparse_hip_fm_epochs_f64_device(dP.as<int32_t>(), dJ.as<int32_t>(), dX.as<double>(), n_rows, n_feat, (int64_t)nnz, dI.p, n_epochs,
+                                        batch, rank, family, intercept, learning_rate_w, learning_rate_v, lambda_w, lambda_v,
+                                        dY.as<double>(), dO.as<double>(), dW0.as<double>(), dW.as<double>(), dV.as<double>(),
+                                        dA0.as<double>(), dAW.as<double>(), dAV.as<double>(), dT.p, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(download(w0, dW0, 1));
+  HIP_TRY(download(w, dW, d));
+  HIP_TRY(download(V, dV, d * k));
+  HIP_TRY(download(a0, dA0, 1));
+  HIP_TRY(download(aw, dAW, d));
+  HIP_TRY(download(aV, dAV, d * k));
+  HIP_TRY(download(static_cast<int64_t*>(trace), dT, (size_t)n_epochs));
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_fm_predict(const int32_t* p, const int32_t* j, const double* x, int n_rows, int n_feat, int rank, int family,
+                           const double* w0, const double* w, const double* V, double* out) {
+  if (!p || !w0 || !w || !V || !out) return fail(RSPARSE_HIP_ERR_INVALID, "the matrix, a parameter or the output is NULL");
+  DevBuf dP, dJ, dX, dW0, dW, dV, dOut;
+  size_t nnz = 0;
+  if (int rc = fm_upload(p, j, x, n_rows, n_feat, rank, dP, dJ, dX, nnz)) return rc;
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  HIP_TRY(upload_host(dW0, w0, 1));
+  HIP_TRY(upload_host(dW, w, (size_t)n_feat));
+  HIP_TRY(upload_host(dV, V, (size_t)n_feat * rank));
+  HIP_TRY(dOut.alloc((size_t)n_rows * 8));
+  int rc = rsparse_hip_fm_forward_f64_device(dP.as<int32_t>(), dJ.as<int32_t>(), dX.as<double>(), n_rows, n_feat, 0, 1, rank, family,
+                                             dW0.as<double>(), dW.as<double>(), dV.as<double>(), nullptr, nullptr, nullptr, nullptr,
+                                             nullptr, dOut.as<double>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(download(out, dOut, (size_t)n_rows));
+  return RSPARSE_HIP_OK;
+}
+
+extern "C++" {
+namespace {
 // B (n x n column-major, an R matrix) as n row-major rows of ld elements, zeros beyond n; a non-finite entry -> false
 template <class T>
 bool ease_pack_weights(const T* B, int n, size_t ld, std::vector<T>& rows) {

@@ -419,6 +419,34 @@ hipError_t launch_lmf_step(const int32_t* P, const int32_t* J, const float* X, i
                            const float* B, const float* D, int n_slices, const double* softplus, int K, int rank, int frozen, double lr,
                            double lambda, double* rowsum, hipStream_t s);
 
+// Factorization machine (wrmf_fm.hip; defined in rsparse_wrmf_hip.h).  The data: the canonical CSR (p from 0, nnz = p[n_rows] handed
+// in, x in the parameters' type T), the steps of an epoch, 1 <= rank <= 128 and the family.  index: the backward index of
+// (x, n_steps) into fm_index_bytes(nnz, n_steps) bytes; waits for `s`.  forward: step `step` alone from (w0, w, V) -- with y: raw
+// (nullable), delta and S (cnt x 16 ceil(rank / 16) doubles), y and omega indexed by row; without y: link alone.  run: the steps
+// [0, n_steps) (only_step < 0) or the one step only_step of n_epochs epochs in place; trace: 8 bytes per epoch, ADDED to -- the
+// binomial count (uint64) or the gaussian weighted squared error (double).  Allocates its scratch, reads the index's step ranges
+// back once and waits for `s` before it returns; hipErrorInvalidValue: the index was built for another nnz or n_steps.
+struct FmData {
+  const int32_t* p;
+  const int32_t* j;
+  const void* x;
+  int n_rows, n_feat;
+  int64_t nnz;
+  int n_steps, rank, family;
+};
+struct FmOpt {
+  int intercept;
+  double lr_w, lr_v, lambda_w, lambda_v;
+};
+size_t fm_index_bytes(int64_t nnz, int n_steps);
+hipError_t launch_fm_index(const FmData& d, void* ws, hipStream_t s);
+template <class T>
+hipError_t launch_fm_forward(const FmData& d, int step, const T* w0, const T* w, const T* V, const double* y, const double* omega,
+                             double* raw, double* delta, double* S, double* link, hipStream_t s);
+template <class T>
+hipError_t launch_fm_run(const FmData& d, const void* index, const FmOpt& o, int n_epochs, int only_step, const double* y,
+                         const double* omega, T* w0, T* w, T* V, double* a0, double* aw, double* aV, void* trace, hipStream_t s);
+
 // ItemKNN (wrmf_itemknn.hip; defined in rsparse_wrmf_hip.h).  `rows` dense rows of n_items cells per batch in ws (uint32 cells
 // for the binary neighbours, uint64 for the weighted ones and for the lists), which is all zeros on entry and again when the
 // enqueued work is done.  h_ip: the host copy of ip[item0 .. item1]; h_xp: of xp[0 .. n_rows].  1 <= K <= 256, 1 <= k <= 1024.

@@ -1121,6 +1121,87 @@ class HipBackend:
                                                         None if rows is None else some(rows), self._stream()))
         return rows
 
+    @staticmethod
+    def _fm_family(family):
+        return {"binomial": 0, "gaussian": 1}[family]
+
+    def _fm_csr(self, p, j, x, w0, w, V):
+        """the checks the factorization-machine calls share -> (p, j, x, n_rows, n_feat) as the C ABI takes them, and the suffix"""
+        assert p.dtype == torch.int32 and j.dtype == torch.int32 and p.is_cuda and x.dtype == V.dtype and V.dtype in (torch.float32, torch.float64)
+        assert w0.dtype == w.dtype == V.dtype and w0.numel() == 1 and V.is_contiguous() and w.is_contiguous() and w.numel() == V.shape[0]
+        assert j.numel() == x.numel() and V.shape[0] >= 1
+        some = lambda t: t.data_ptr() if t.numel() else p.data_ptr()   # (an empty tensor has no address to pass)
+        return (p.data_ptr(), some(j), some(x), int(p.numel()) - 1, int(V.shape[0])), ("_f64" if V.dtype == torch.float64 else "")
+
+    def fm_index(self, p, j, n_feat, n_steps):
+        """the backward index of the canonical CSR (p, j: int32 on the device) for epochs of n_steps steps (wrmf_fm.hip: one stable
+        radix sort by (step, column), the segments and the chunks of the long ones) -> (the index's bytes on the device, nnz, n_steps).
+        One host synchronisation; built once per (x, n_steps)."""
+        assert p.dtype == torch.int32 and j.dtype == torch.int32 and p.is_cuda
+        n_rows, nnz = int(p.numel()) - 1, int(j.numel())
+        need = ctypes.c_size_t(0)
+        head = (p.data_ptr(), j.data_ptr() if nnz else p.data_ptr(), n_rows, int(n_feat), nnz, int(n_steps))
+        _lib.check(self.lib.rsparse_hip_fm_index_device(*head, None, ctypes.byref(need), self._stream()))
+        ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.rsparse_hip_fm_index_device(*head, ws.data_ptr(), ctypes.byref(need), self._stream()))
+        return ws, nnz, int(n_steps)
+
+    def fm_forward(self, p, j, x, family, step, n_steps, w0, w, V, y, omega):
+        """the forward pass of step `step` of n_steps from (w0, w, V) (rsparse_amd.fm.fm_forward_reference is the definition; y and
+        omega: float64 over the rows) -> (raw, delta, S): float64 on the device, S of 16 ceil(rank / 16) columns"""
+        head, f = self._fm_csr(p, j, x, w0, w, V)
+        assert y.dtype == torch.float64 and omega.dtype == torch.float64 and y.numel() == omega.numel() == head[3]
+        cnt, rank = max(0, -(-(head[3] - int(step)) // int(n_steps))), int(V.shape[1])
+        raw, delta = (torch.zeros(max(cnt, 1), dtype=torch.float64, device=self.device) for _ in range(2))
+        S = torch.zeros((max(cnt, 1), 16 * (-(-rank // 16))), dtype=torch.float64, device=self.device)
+        some = lambda t: t.data_ptr() if t.numel() else raw.data_ptr()
+        _lib.check(getattr(self.lib, "rsparse_hip_fm_forward%s_device" % f)(*head, int(step), int(n_steps), rank, self._fm_family(family),
+                                                                            w0.data_ptr(), w.data_ptr(), V.data_ptr(), some(y), some(omega),
+                                                                            raw.data_ptr(), delta.data_ptr(), S.data_ptr(), None,
+                                                                            self._stream()))
+        return raw[:cnt], delta[:cnt], S[:cnt]
+
+    def fm_predict(self, p, j, x, family, w0, w, V):
+        """predict of the definition on every row: the forward kernel without the update's outputs -> float64 on the device"""
+        head, f = self._fm_csr(p, j, x, w0, w, V)
+        out = torch.zeros(max(head[3], 1), dtype=torch.float64, device=self.device)
+        _lib.check(getattr(self.lib, "rsparse_hip_fm_forward%s_device" % f)(*head, 0, 1, int(V.shape[1]), self._fm_family(family),
+                                                                            w0.data_ptr(), w.data_ptr(), V.data_ptr(), None, None, None,
+                                                                            None, None, out.data_ptr(), self._stream()))
+        return out[:head[3]]
+
+    def _fm_run(self, name, p, j, x, index, a, b, family, intercept, y, omega, w0, w, V, a0, aw, aV, lr_w, lr_v, lam_w, lam_v, trace):
+        head, f = self._fm_csr(p, j, x, w0, w, V)
+        ws, nnz, _ = index
+        assert nnz == int(j.numel()) and y.dtype == torch.float64 and omega.dtype == torch.float64 and y.numel() == omega.numel() == head[3]
+        assert all(t.dtype == torch.float64 and t.is_contiguous() for t in (a0, aw, aV)) and a0.numel() == 1 and aw.shape == w.shape and aV.shape == V.shape
+        some = lambda t: t.data_ptr() if t.numel() else trace.data_ptr()
+        _lib.check(getattr(self.lib, "rsparse_hip_fm_%s%s_device" % (name, f))(
+            *head, nnz, ws.data_ptr(), int(a), int(b), int(V.shape[1]), self._fm_family(family), int(bool(intercept)), float(lr_w), float(lr_v),
+            float(lam_w), float(lam_v), some(y), some(omega), w0.data_ptr(), w.data_ptr(), V.data_ptr(), a0.data_ptr(), aw.data_ptr(),
+            aV.data_ptr(), trace.data_ptr(), self._stream()))
+        return trace
+
+    def _fm_trace(self, n, family):
+        return torch.zeros(max(int(n), 1), dtype=torch.int64 if family == "binomial" else torch.float64, device=self.device)
+
+    def fm_step(self, p, j, x, index, step, family, intercept, y, omega, w0, w, V, a0, aw, aV, lr_w, lr_v, lam_w, lam_v):
+        """one step of the factorization machine in place on (w0, w, V) and their float64 Adagrad states (rsparse_amd.fm.
+        fm_step_reference is the definition; index: of `fm_index`) -> the step's trace term on the device: the int64 count of rows with
+        y raw > 0 (binomial) or the float64 weighted squared error (gaussian)"""
+        return self._fm_run("step", p, j, x, index, step, index[2], family, intercept, y, omega, w0, w, V, a0, aw, aV, lr_w, lr_v, lam_w, lam_v,
+                            self._fm_trace(1, family))
+
+    def fm_epochs(self, p, j, x, index, n_epochs, family, intercept, y, omega, w0, w, V, a0, aw, aV, lr_w, lr_v, lam_w, lam_v):
+        """n_epochs epochs of the index's n_steps steps each, in place, on one stream with no host synchronisation between them ->
+        the trace, one entry per epoch, on the device"""
+        n_rows, n_steps = int(p.numel()) - 1, index[2]
+        batch = max(1, -(-n_rows // n_steps))
+        assert max(1, -(-n_rows // batch)) == n_steps, "the index was built for another number of steps"
+        trace = self._fm_run("epochs", p, j, x, index, n_epochs, batch, family, intercept, y, omega, w0, w, V, a0, aw, aV, lr_w, lr_v, lam_w,
+                             lam_v, self._fm_trace(n_epochs, family))
+        return trace[:int(n_epochs)]
+
     def item_features(self, F, dtype):
         """a canonical scipy CSR F (n_items x n_feat) -> (fp, fj, fx, cp, ci, cx, n_feat) on the device: F by item and, through
         `transpose_csc`, by feature; values of `dtype`"""
