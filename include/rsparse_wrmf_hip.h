@@ -1452,6 +1452,37 @@ int rsparse_hip_fm_predict(const int32_t* p, const int32_t* j, const double* x, 
                            const double* w0, const double* w, const double* V, double* out);
 
 /* ------------------------------------------------------------------------------------------------
+ * iALS++: implicit ALS by exact block (subspace) solves (Rendle, Krichene, Zhang, Koren 2021; wrmf_subspace.hip)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The definition (rsparse_amd/ialspp.py states it in numpy: ialspp_block_reference, ialspp_half_reference, ialspp_fit_reference).
+ * The objective is the implicit one of the half-iterations above: sum over ALL cells of c_ui (p_ui - w_u . h_i)^2 + lambda (|W|^2 +
+ * |H|^2), with c_ui the stored value (> 0) and p_ui = 1 at a stored cell, c = 1 and p = 0 elsewhere.  One half updates W (n x k)
+ * with H (m x k) fixed: G = H^T H, e_ui = w_u . h_i at the stored cells, then for the blocks pi = [0, b), [b, 2 b), ... in order
+ * (the last one narrower when b does not divide k):
+ *     D = W G[:, pi] with the CURRENT W (n x |pi|), and for every row u, the empty ones included,
+ *     g = D[u] + lambda w_u,pi + sum_{i in row} ((c_ui - 1) e_ui - c_ui) h_i,pi
+ *     A = G_pi,pi + lambda I + sum_{i in row} (c_ui - 1) h_i,pi h_i,pi^T
+ *     delta = A^-1 g;   w_u,pi <- w_u,pi - delta;   e_ui <- e_ui - h_i,pi . delta for the row's cells.
+ * With one block (b >= k) a half is the exact solve; the objective never increases over a block.
+ *
+ * rsparse_hip_subspace_block_device is the part inside "for every row" of ONE block: D (n_rows x width, leading dimension ldd), the
+ * block d_G of G (width x width, leading dimension ldg; lambda NOT in it) and e (one float per stored cell, in CSR order) are
+ * inputs; d_W (leading dimension ldw) is updated on the columns [c0, c0 + width) alone and d_e in place.  d_H (leading dimension
+ * ldh) is read on the same columns: the rank appears nowhere.  nnz = d_p[n_rows] (d_p starts at 0).  fp32, exact fp32 products on the
+ * matrix cores, no float atomics: a repeated call returns the same bits.  A row whose system is not positive definite is left
+ * unchanged, with its e, and counted as unresolved (rsparse_hip_take_numeric_failures).  A row of more than
+ * RSPARSE_HIP_SUBSPACE_LONG_ROW cells is split over the waves of a workgroup, and over several workgroups beyond that.
+ * NULL arrays, n_rows < 0, nnz < 0, width < 1, c0 < 0, a leading dimension smaller than what it spans, or a lambda that is negative
+ * or not finite: RSPARSE_HIP_ERR_INVALID; width > b, width > 64 or b not 32 or 64: RSPARSE_HIP_ERR_UNSUPPORTED -- all before a device
+ * is touched. */
+#define RSPARSE_HIP_SUBSPACE_LONG_ROW 256
+#define RSPARSE_HIP_SUBSPACE_SEGMENT 8192   /* a workgroup's share of a split row: this, or nnz / 2048 where that is more */
+int rsparse_hip_subspace_block_device(const int32_t* d_p, const int32_t* d_j, const float* d_x, int n_rows, int64_t nnz,
+                                      const float* d_H, int ldh, int c0, int width, int b, const float* d_G, int ldg, const float* d_D,
+                                      int ldd, double lambda, float* d_W, int ldw, float* d_e, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * why this item: per-item contributions to a score (Hu, Koren and Volinsky, section 5; `explain` of the `implicit` library)
  * ---------------------------------------------------------------------------------------------- */
 

@@ -27,6 +27,8 @@ SLIM_LDS_SUPPORT = 2048   # RSPARSE_HIP_SLIM_LDS_SUPPORT: the support entries of
 WARP_MAX_TRIALS = 64   # RSPARSE_HIP_WARP_MAX_TRIALS: the trials of one WARP search, at most
 BPR_CHUNK = 64   # RSPARSE_HIP_BPR_CHUNK: consecutive contributions of a destination row that are summed as one chunk (wrmf_bpr.hip)
 LMF_MAX_K, LMF_LONG_ROW = 128, 512   # RSPARSE_HIP_LMF_MAX_K / _LONG_ROW: the widest factor row and the row-length edge of wrmf_lmf.hip
+SUBSPACE_LONG_ROW, SUBSPACE_SEGMENT = 256, 8192   # RSPARSE_HIP_SUBSPACE_LONG_ROW / _SEGMENT: the row-length edge of wrmf_subspace.hip and
+#                                                 the least number of entries a workgroup takes of a row that is split
 FM_MAX_RANK, FM_LONG_ROW = 128, 512   # RSPARSE_HIP_FM_MAX_RANK / _LONG_ROW: the widest V and the row-length edge of wrmf_fm.hip
 RANKS_BATCH = 1024  # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that the rank count takes at a time
 
@@ -189,6 +191,9 @@ SIGNATURES = {
                                              _c_dbl, _c_dbl, _vp, _vp]),
     "rsparse_hip_lmf_half_device": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_dbl, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _c_dbl,
                                              _c_int, _vp, _vp]),
+    # iALS++ block step: (p, j, x, n_rows, nnz, H, ldh, c0, width, b, G, ldg, D, ldd, lambda, W, ldw, e, stream)
+    "rsparse_hip_subspace_block_device": (_c_int, [_vp, _vp, _vp, _c_int, _c_i64, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp,
+                                                   _c_int, _c_dbl, _vp, _c_int, _vp, _vp]),
     # factorization machine: (p, j, n_rows, n_feat, nnz, n_steps, index, index_bytes, stream); (p, j, x, n_rows, n_feat, step, n_steps,
     # rank, family, w0, w, V, y, omega, raw, delta, S, link, stream); (p, j, x, n_rows, n_feat, nnz, index, step | n_epochs, n_steps |
     # batch, rank, family, intercept, lr_w, lr_v, lambda_w, lambda_v, y, omega, w0, w, V, a0, aw, aV, trace, stream)

@@ -69,6 +69,7 @@ struct Workspace {
                                     // top-k within candidate lists (wrmf_candidates.hip): its scores / keys, bits and row lists
   GrowBuf<double> softals_buf{all};   // soft-ALS half-iteration (wrmf_softals.hip): w, s, t and the partial sums of split rows
   GrowBuf<double> lmf_buf{all};   // logistic MF (wrmf_lmf.hip): the slices' softplus sums and fp32 partials of the dense term
+  GrowBuf<char> sub_buf{all};     // iALS++ block step (wrmf_subspace.hip): the long rows' segments and partial sums
   GrowBuf<char> knn_buf{all};     // ItemKNN (wrmf_itemknn.hip): a batch of dense rows, all zeros between calls
   bool knn_dirty = false;         // ... unless a call failed between its scatter and its zeroing
   GrowBuf<float> mf_G{all};       // wrmf_chol_mf.hip at rank 65..127: XtX padded to 128 x 128
@@ -2095,6 +2096,28 @@ int rsparse_hip_lmf_half_device(const int32_t* d_p, const int32_t* d_j, const fl
   e = launch_lmf_step(d_p, d_j, d_x, n_rows, n_str, alpha, d_A, d_aA, d_B, D, plan.n_slices, sp, K, rank, frozen, learning_rate, lambda,
                       d_rowsums, s);
   if (e != hipSuccess) return hip_fail(e, "launch_lmf_step");
+  return RSPARSE_HIP_OK;
+}
+
+// iALS++ block step (wrmf_subspace.hip)
+int rsparse_hip_subspace_block_device(const int32_t* d_p, const int32_t* d_j, const float* d_x, int n_rows, int64_t nnz,
+                                      const float* d_H, int ldh, int c0, int width, int b, const float* d_G, int ldg, const float* d_D,
+                                      int ldd, double lambda, float* d_W, int ldw, float* d_e, void* stream) {
+  if (!d_p || !d_H || !d_G || !d_D || !d_W || (nnz > 0 && (!d_j || !d_x || !d_e))) return fail(RSPARSE_HIP_ERR_INVALID, "NULL array");
+  if (n_rows < 0 || nnz < 0 || width < 1 || c0 < 0) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, nnz < 0, width < 1 or c0 < 0)");
+  if (nnz > INT32_MAX) return fail(RSPARSE_HIP_ERR_INVALID, "nnz does not fit the 32-bit row pointers");
+  if (b != 32 && b != 64) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "the block width b must be 32 or 64");
+  if (width > b) return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "width > b (at most 64 coordinates per block)");
+  if ((int64_t)ldh < (int64_t)c0 + width || (int64_t)ldw < (int64_t)c0 + width || ldg < width || ldd < width)
+    return fail(RSPARSE_HIP_ERR_INVALID, "a leading dimension is smaller than the columns it spans");
+  if (!(lambda >= 0.0) || lambda > 1e300) return fail(RSPARSE_HIP_ERR_INVALID, "lambda must be finite and >= 0");
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  if (int rc = g_ws.ensure_device()) return rc;
+  HIP_TRY(g_ws.sub_buf.ensure(subspace_ws_bytes(n_rows, nnz)));
+  // ([3]: unresolved rows of the calls since rsparse_hip_take_numeric_failures, see launch_fail_roll -- the row keeps its values)
+  hipError_t e = launch_subspace_block(d_p, d_j, d_x, n_rows, nnz, d_H, ldh, c0, width, d_G, ldg, d_D, ldd, (float)lambda, d_W, ldw, d_e,
+                                       g_ws.fails + 3, (char*)g_ws.sub_buf, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_subspace_block");
   return RSPARSE_HIP_OK;
 }
 

@@ -419,6 +419,15 @@ hipError_t launch_lmf_step(const int32_t* P, const int32_t* J, const float* X, i
                            const float* B, const float* D, int n_slices, const double* softplus, int K, int rank, int frozen, double lr,
                            double lambda, double* rowsum, hipStream_t s);
 
+// iALS++ block step (wrmf_subspace.hip; defined in rsparse_wrmf_hip.h): the block [c0, c0 + width), 1 <= width <= 64, of every row of
+// the CSR (P, J, X; nnz = P[n_rows] handed in) against H (leading dimension ldh), G_pi,pi (ldg), D (ldd); W (ldw) and e in place;
+// *fails += the rows whose system was not positive definite (left unchanged).  ws: subspace_ws_bytes(n_rows, nnz) bytes, 16-byte
+// aligned, for the long rows' segments and partial sums (sized from nnz alone: nothing is read back).
+size_t subspace_ws_bytes(int n_rows, int64_t nnz);
+hipError_t launch_subspace_block(const int32_t* P, const int32_t* J, const float* X, int n_rows, int64_t nnz, const float* H, int ldh,
+                                 int c0, int width, const float* G, int ldg, const float* D, int ldd, float lambda, float* W, int ldw,
+                                 float* e, int* fails, void* ws, hipStream_t s);
+
 // Factorization machine (wrmf_fm.hip; defined in rsparse_wrmf_hip.h).  The data: the canonical CSR (p from 0, nnz = p[n_rows] handed
 // in, x in the parameters' type T), the steps of an epoch, 1 <= rank <= 128 and the family.  index: the backward index of
 // (x, n_steps) into fm_index_bytes(nnz, n_steps) bytes; waits for `s`.  forward: step `step` alone from (w0, w, V) -- with y: raw

@@ -1121,6 +1121,22 @@ class HipBackend:
                                                         None if rows is None else some(rows), self._stream()))
         return rows
 
+    def subspace_block(self, p, j, x, H, c0, width, b, G_block, D, lambda_, W, e):
+        """one iALS++ block step in place (wrmf_subspace.hip; rsparse_amd.ialspp.ialspp_block_reference is the definition): the
+        columns [c0, c0 + width) of W (n x k) and e (float32, one per stored cell) over the CSR (p, j: int32; x: float32
+        confidences) whose columns index the rows of H (m x k); G_block = (H'H)[pi, pi] WITHOUT lambda (width x width, any row
+        stride), D = W (H'H)[:, pi] (n x width).  width <= b, b = 32 or 64.  Nothing is read back."""
+        assert p.dtype == torch.int32 and j.dtype == torch.int32 and x.dtype == torch.float32 and e.dtype == torch.float32
+        assert x.numel() == j.numel() == e.numel() and e.is_contiguous() and p.numel() == W.shape[0] + 1
+        for t in (H, W, G_block, D):
+            assert t.dtype == torch.float32 and t.is_cuda and t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1)
+        assert W.shape[1] == H.shape[1] and tuple(D.shape) == (W.shape[0], width) and tuple(G_block.shape) == (width, width)
+        ld = lambda t: int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+        some = lambda t: t.data_ptr() if t.numel() else p.data_ptr()
+        _lib.check(self.lib.rsparse_hip_subspace_block_device(p.data_ptr(), some(j), some(x), int(W.shape[0]), int(j.numel()), some(H),
+                                                              ld(H), int(c0), int(width), int(b), G_block.data_ptr(), ld(G_block),
+                                                              some(D), ld(D), float(lambda_), some(W), ld(W), some(e), self._stream()))
+
     @staticmethod
     def _fm_family(family):
         return {"binomial": 0, "gaussian": 1}[family]
