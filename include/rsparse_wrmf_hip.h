@@ -1452,6 +1452,70 @@ int rsparse_hip_fm_predict(const int32_t* p, const int32_t* j, const double* x, 
                            const double* w0, const double* w, const double* V, double* out);
 
 /* ------------------------------------------------------------------------------------------------
+ * GloVe (Pennington, Socher, Manning 2014) by deterministic mini-batch SGD (wrmf_glove.hip)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The definition (rsparse_amd/glove.py states it in numpy: glove_slots_reference, glove_step_reference, glove_fit_reference).  Every
+ * arithmetic operation is a separately rounded float64 operation on parameters widened from their type; nothing is fused.
+ *   Input: the nnz stored positions of a canonical n x n matrix with positive values, in CSR order (rows ascending, columns strictly
+ *   ascending per row): rows[p], cols[p], fx[p] = (x / x_max)^alpha below x_max and 1 from there on, lx[p] = log(x), the last two
+ *   computed by the host and rounded once into the parameters' type.  No transcendental is evaluated on the device.
+ *   Parameters W_i, W_j (n x rank row-major), b_i, b_j (n) with float64 Adagrad states aW_i, aW_j, ab_i, ab_j of the same shapes
+ *   (a fresh model: 1.0).
+ *   Steps: n_steps = ceil(nnz / batch); step s holds the positions p = s, s + n_steps, ... ascending, numbered k = 0, 1, ...; a step
+ *   is computed from the snapshot of the parameters at its start.
+ *   osum(list): the list cut into chunks of RSPARSE_HIP_BPR_CHUNK consecutive terms, a chunk summed sequentially from +0.0, the
+ *   chunk sums added sequentially to a total that starts at +0.0.
+ *   Slot k with (r, c) = (rows[p], cols[p]):  dot = the BPR dot order over q of W_i[r, q] W_j[c, q] (16 partials over q = l, l + 16,
+ *   ..., then the 8/4/2/1 tree);  inner = clip(((dot + b_i[r]) + b_j[c]) - lx[p], -100, 100);  cost = fx[p] inner;  term = cost inner.
+ *   Per destination, contributions in ascending k: row r coordinate q osum_k(cost_k W_j[c_k, q]), bias b_i[r] osum_k(cost_k), count =
+ *   the slots of r in the step; column c coordinate q osum_k(cost_k W_i[r_k, q]), bias b_j[c] osum_k(cost_k), count = the slots of c.
+ *   Update of a coordinate theta with state a and count >= 1 (the others keep their bits): g = total + (lambda count) theta;
+ *   a' = a + g g; theta' = theta - (lr g) / sqrt(a') unless a' == 0, rounded once.  lambda for W, 0 for the biases.
+ *   Trace: a step's term is 0.5 osum_k(term_k); an epoch's cost is the sequential sum of its steps' terms (the modelled-on class
+ *   reports it divided by nnz).
+ * Unlike the modelled-on Hogwild loop (src/GloVe.cpp): mini-batches from a snapshot, an Adagrad state added to before the division, a
+ * lambda that is used (an L2 term that scales with the count), no shuffle, a triangular matrix symmetrised once by the host.
+ * No float atomics: a repeated call returns the same bits.  Positions in CSR order are a precondition of the `_device` entries (a row
+ * or column outside [0, n) is read as the nearest valid one).  NULL or negative arguments, n < 1, rank < 1, n_steps or batch < 1,
+ * n_steps > nnz, a step outside [0, n_steps), a rate or lambda that is negative or not finite: RSPARSE_HIP_ERR_INVALID; rank >
+ * RSPARSE_HIP_GLOVE_MAX_RANK: RSPARSE_HIP_ERR_UNSUPPORTED. */
+#define RSPARSE_HIP_GLOVE_MAX_RANK 128
+
+/* The index of (rows, cols, n_steps), both sides: per step the positions grouped by row (their CSR order; no sort) and by column
+ * (one stable radix sort), their k, the segments and the chunks of the long ones.  d_index NULL: *index_bytes receives the bytes it
+ * needs and nothing else happens; otherwise the index is built into d_index (*index_bytes: its capacity) and the call waits for
+ * `stream`.  It does not depend on the values or their type. */
+int rsparse_hip_glove_index_device(const int32_t* d_rows, const int32_t* d_cols, int n, int64_t nnz, int n_steps, void* d_index,
+                                   size_t* index_bytes, void* stream);
+/* One step in place on the parameters and their states; d_trace (one double) is ADDED to.  d_index: of this (rows, cols, n_steps).
+ * Waits for `stream` before it returns (its scratch, O(batch rank) bytes, is freed). */
+int rsparse_hip_glove_step_device(const int32_t* d_rows, const int32_t* d_cols, const float* d_fx, const float* d_lx, int n, int64_t nnz,
+                                  const void* d_index, int step, int n_steps, int rank, double learning_rate, double lambda,
+                                  float* d_Wi, float* d_Wj, float* d_bi, float* d_bj, double* d_aWi, double* d_aWj, double* d_abi,
+                                  double* d_abj, double* d_trace, void* stream);
+int rsparse_hip_glove_step_f64_device(const int32_t* d_rows, const int32_t* d_cols, const double* d_fx, const double* d_lx, int n,
+                                      int64_t nnz, const void* d_index, int step, int n_steps, int rank, double learning_rate,
+                                      double lambda, double* d_Wi, double* d_Wj, double* d_bi, double* d_bj, double* d_aWi,
+                                      double* d_aWj, double* d_abi, double* d_abj, double* d_trace, void* stream);
+/* n_epochs epochs of ceil(nnz / batch) steps each, on one stream with no host synchronisation between them; d_trace: one double per
+ * epoch, overwritten with the epoch's cost.  d_index: of (rows, cols, ceil(nnz / batch)). */
+int rsparse_hip_glove_epochs_device(const int32_t* d_rows, const int32_t* d_cols, const float* d_fx, const float* d_lx, int n,
+                                    int64_t nnz, const void* d_index, int n_epochs, int batch, int rank, double learning_rate,
+                                    double lambda, float* d_Wi, float* d_Wj, float* d_bi, float* d_bj, double* d_aWi, double* d_aWj,
+                                    double* d_abi, double* d_abj, double* d_trace, void* stream);
+int rsparse_hip_glove_epochs_f64_device(const int32_t* d_rows, const int32_t* d_cols, const double* d_fx, const double* d_lx, int n,
+                                        int64_t nnz, const void* d_index, int n_epochs, int batch, int rank, double learning_rate,
+                                        double lambda, double* d_Wi, double* d_Wj, double* d_bi, double* d_bj, double* d_aWi,
+                                        double* d_aWj, double* d_abi, double* d_abj, double* d_trace, void* stream);
+/* Host arrays, double parameters.  The positions are checked to be in CSR order and inside the matrix, fx and lx to be finite; the
+ * parameters and the states are IN/OUT, so a second call goes on where the first ended (a fresh model: rsparse_hip_init_factors with
+ * stream 0 for W_i and 1 for W_j at scale 0.1, biases 0, states 1); trace: one double per epoch. */
+int rsparse_hip_glove_fit(const int32_t* rows, const int32_t* cols, const double* fx, const double* lx, int n, int64_t nnz, int n_epochs,
+                          int batch, int rank, double learning_rate, double lambda, double* Wi, double* Wj, double* bi, double* bj,
+                          double* aWi, double* aWj, double* abi, double* abj, double* trace);
+
+/* ------------------------------------------------------------------------------------------------
  * iALS++: implicit ALS by exact block (subspace) solves (Rendle, Krichene, Zhang, Koren 2021; wrmf_subspace.hip)
  * ---------------------------------------------------------------------------------------------- */
 

@@ -27,6 +27,9 @@ Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit
   rsparse_amd.FactorizationMachine   second-order factorization machine (Rendle 2010) over a samples x features matrix, binomial or
                               gaussian, by deterministic mini-batch SGD with per-coordinate Adagrad on the device, equal to the
                               numpy definition; partial_fit / fit / predict
+  rsparse_amd.GloVe           GloVe embeddings (Pennington et al. 2014) of a square co-occurrence matrix by deterministic mini-batch
+                              SGD with per-coordinate Adagrad on the device, equal to the numpy definition; fit_transform /
+                              components / most_similar
   rsparse_amd.IALSpp          implicit ALS by exact block (subspace) solves, iALS++ (Rendle et al. 2021): WRMF's objective, a b x b
                               system per row and block assembled on the fp32 matrix cores; WRMF's inference surface
   rsparse_amd.als             als_implicit()/als_explicit() wrappers over the stateless C ABI
@@ -81,6 +84,9 @@ def __getattr__(name):
     if name in ("FactorizationMachine", "fm_forward_reference", "fm_step_reference", "fm_fit_reference", "fm_predict_reference"):
         from . import fm
         return getattr(fm, name)
+    if name in ("GloVe", "glove_slots_reference", "glove_step_reference", "glove_fit_reference"):
+        from . import glove
+        return getattr(glove, name)
     if name in ("IALSpp", "ialspp_block_reference", "ialspp_half_reference", "ialspp_fit_reference", "ialspp_objective"):
         from . import ialspp
         return getattr(ialspp, name)

@@ -30,6 +30,7 @@ LMF_MAX_K, LMF_LONG_ROW = 128, 512   # RSPARSE_HIP_LMF_MAX_K / _LONG_ROW: the wi
 SUBSPACE_LONG_ROW, SUBSPACE_SEGMENT = 256, 8192   # RSPARSE_HIP_SUBSPACE_LONG_ROW / _SEGMENT: the row-length edge of wrmf_subspace.hip and
 #                                                 the least number of entries a workgroup takes of a row that is split
 FM_MAX_RANK, FM_LONG_ROW = 128, 512   # RSPARSE_HIP_FM_MAX_RANK / _LONG_ROW: the widest V and the row-length edge of wrmf_fm.hip
+GLOVE_MAX_RANK = 128   # RSPARSE_HIP_GLOVE_MAX_RANK: the widest W_i / W_j of wrmf_glove.hip
 RANKS_BATCH = 1024  # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that the rank count takes at a time
 
 _c_int, _c_uint, _c_dbl, _c_i64, _c_u64 = ctypes.c_int, ctypes.c_uint, ctypes.c_double, ctypes.c_int64, ctypes.c_uint64
@@ -203,6 +204,10 @@ SIGNATURES = {
        for n in ("step", "epochs") for f in ("", "_f64")},
     "rsparse_hip_fm_fit": (_c_int, [_vp] * 3 + [_c_int, _c_int, _vp, _vp] + [_c_int] * 5 + [_c_dbl] * 4 + [_vp] * 7),
     "rsparse_hip_fm_predict": (_c_int, [_vp] * 3 + [_c_int] * 4 + [_vp] * 4),
+    "rsparse_hip_glove_index_device": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_int, _vp, ctypes.POINTER(ctypes.c_size_t), _vp]),
+    **{"rsparse_hip_glove_%s%s_device" % (n, f): (_c_int, [_vp] * 4 + [_c_int, _c_i64, _vp] + [_c_int] * 3 + [_c_dbl] * 2 + [_vp] * 10)
+       for n in ("step", "epochs") for f in ("", "_f64")},
+    "rsparse_hip_glove_fit": (_c_int, [_vp] * 4 + [_c_int, _c_i64] + [_c_int] * 3 + [_c_dbl] * 2 + [_vp] * 9),
     "rsparse_hip_top_candidates_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl, _vp,
                                                    _vp, _vp]),
     "rsparse_hip_top_candidates_f64_device": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_dbl,

@@ -17,7 +17,7 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 SRC = [CSRC / n for n in ("wrmf_kernels.hip", "wrmf_cgq.hip", "wrmf_cgp.hip", "wrmf_ne.hip", "wrmf_chol.hip", "wrmf_chol_wave.hip", "wrmf_chol_mf.hip", "wrmf_cg_mf.hip", "wrmf_chol_lr.hip",
-                          "wrmf_topk.hip", "wrmf_topk_large.hip", "wrmf_similar.hip", "wrmf_metrics.hip", "wrmf_hits.hip", "wrmf_lists.hip", "wrmf_diversity.hip", "wrmf_mmr.hip", "wrmf_ranks.hip", "wrmf_score.hip", "wrmf_softals.hip", "wrmf_itemknn.hip", "wrmf_ease.hip", "wrmf_slim.hip", "wrmf_bpr.hip", "wrmf_bpr_features.hip", "wrmf_lmf.hip", "wrmf_fm.hip", "wrmf_subspace.hip", "wrmf_candidates.hip", "wrmf_sample.hip", "wrmf_sample_weighted.hip", "wrmf_split.hip", "wrmf_confidence.hip", "wrmf_events.hip", "wrmf_explain.hip", "wrmf_init.hip", "wrmf_ingest.hip", "wrmf_nnls.hip", "wrmf_bias.hip", "wrmf_lu.hip",
+                          "wrmf_topk.hip", "wrmf_topk_large.hip", "wrmf_similar.hip", "wrmf_metrics.hip", "wrmf_hits.hip", "wrmf_lists.hip", "wrmf_diversity.hip", "wrmf_mmr.hip", "wrmf_ranks.hip", "wrmf_score.hip", "wrmf_softals.hip", "wrmf_itemknn.hip", "wrmf_ease.hip", "wrmf_slim.hip", "wrmf_bpr.hip", "wrmf_bpr_features.hip", "wrmf_lmf.hip", "wrmf_fm.hip", "wrmf_glove.hip", "wrmf_subspace.hip", "wrmf_candidates.hip", "wrmf_sample.hip", "wrmf_sample_weighted.hip", "wrmf_split.hip", "wrmf_confidence.hip", "wrmf_events.hip", "wrmf_explain.hip", "wrmf_init.hip", "wrmf_ingest.hip", "wrmf_nnls.hip", "wrmf_bias.hip", "wrmf_lu.hip",
                           "wrmf_f64.hip", "wrmf_wide.hip", "wrmf_wide_cg.hip", "wrmf_ctx_kernels.hip", "wrmf_schedule.cpp", "wrmf_capi.cpp", "wrmf_f64_capi.cpp", "wrmf_capi_host.cpp", "wrmf_ctx.cpp")]
 HEADERS = [CSRC / "wrmf_chol_mf.attrs.csv", CSRC / "wrmf_mf.h", CSRC / "wrmf_internal.h", CSRC / "wrmf_capi_common.h", CSRC / "wrmf_schedule.h", CSRC / "wrmf_device.h", CSRC / "wrmf_bpr_device.h", CSRC / "wrmf_sample_team.h", CSRC / "wrmf_wave.h", CSRC / "wrmf_csr_rows.h", CSRC / "wrmf_ldlt.h", CSRC / "wrmf_f64.h", CSRC / "wrmf_topk_plan.h", CSRC / "wrmf_ctx_layout.h", PKG.parent / "include" / "rsparse_wrmf_hip.h"]
 DEPS = SRC + HEADERS
@@ -47,6 +47,9 @@ EXTRA_FLAGS["wrmf_lmf.hip"] = ["-ffp-contract=off", "-Xclang", "-target-feature"
 # wrmf_fm.hip: the forward sums, the link, the gradient sums and the Adagrad update of rsparse_amd/fm.py are separately rounded
 # float64 operations; its only fp32 work is moving parameters
 EXTRA_FLAGS["wrmf_fm.hip"] = ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+# wrmf_glove.hip: the scores, the gradient sums and the Adagrad update of rsparse_amd/glove.py are separately rounded float64
+# operations; its only fp32 work is moving parameters
+EXTRA_FLAGS["wrmf_glove.hip"] = ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 AUDITED = {"wrmf_chol_mf.hip", "wrmf_cg_mf.hip"}
 REG_LIMIT = {"wrmf_cg_mf.hip": 512}   # (one wave per SIMD by design: 320 accumulator registers per row)
 # Kernels that fit two waves per SIMD only without a spill (the 24-quad team kernel of wrmf_cgq.hip keeps 192 registers of
@@ -115,6 +118,12 @@ NO_SPILL = {"wrmf_cgq.hip": ("14als_cgq_kernelILi128ELi24ELi4ELi4E",),
             # walks; the index kernels are integer-only
             "wrmf_fm.hip": ("fm_forward_kernel", "fm_w0_kernel", "fm_chunks_kernel", "fm_update_kernel", "fm_keys_kernel",
                             "fm_heads_kernel", "fm_entries_kernel", "fm_nch_kernel", "fm_steps_kernel"),
+            # a walk keeps the destination's row, a chunk's sum and the total (three doubles per 16 coordinates and lane) beside two
+            # gathered rows and three stages of indices: scratch would sit inside the serial walk; the index kernels
+            # are integer-only
+            "wrmf_glove.hip": ("glove_chunks_kernel", "glove_update_kernel", "glove_commit_kernel", "glove_cost_kernel",
+                               "glove_row_keys_kernel", "glove_col_keys_kernel", "glove_heads_kernel", "glove_entries_kernel",
+                               "glove_nch_kernel", "glove_steps_kernel"),
             # the wave kernels hold 64 accumulator registers of A, a 64-register chunk in flight and then the 64 registers of the
             # lane's row through 64 pivot steps: scratch would sit inside the factorisation
             "wrmf_subspace.hip": ("subspace_wave_kernel", "subspace_long_kernel", "subspace_finish_kernel", "subspace_apply_kernel",

@@ -2228,6 +2228,88 @@ RSPARSE_FM_ENTRIES(_device, float)
 RSPARSE_FM_ENTRIES(_f64_device, double)
 #undef RSPARSE_FM_ENTRIES
 
+extern "C++" {
+namespace {
+// GloVe (wrmf_glove.hip), both precisions; the host form rsparse_hip_glove_fit: wrmf_capi_host.cpp
+int glove_args(bool missing, int n, int64_t nnz, int n_steps, const char* steps_name, int rank) {
+  if (missing) return fail(RSPARSE_HIP_ERR_INVALID, "the positions, a parameter, a state or an output is NULL");
+  if (n < 1 || nnz < 0 || nnz > 0x7fffffffLL) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n < 1, nnz < 0 or nnz >= 2^31)");
+  if (n_steps < 1) return fail(RSPARSE_HIP_ERR_INVALID, std::string(steps_name) + " < 1");
+  if (rank < 1) return fail(RSPARSE_HIP_ERR_INVALID, "rank < 1");
+  if (rank > RSPARSE_HIP_GLOVE_MAX_RANK)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > " + std::to_string(RSPARSE_HIP_GLOVE_MAX_RANK) + " is not on the device path");
+  if ((int64_t)n_steps > (nnz > 0 ? nnz : 1)) return fail(RSPARSE_HIP_ERR_INVALID, "n_steps > nnz");
+  return RSPARSE_HIP_OK;
+}
+
+GloveData glove_data_of(const int32_t* d_rows, const int32_t* d_cols, const void* d_fx, const void* d_lx, int n, int64_t nnz, int n_steps,
+                        int rank) {
+  GloveData d;
+  d.rows = d_rows; d.cols = d_cols; d.fx = d_fx; d.lx = d_lx; d.n = n; d.nnz = nnz; d.n_steps = n_steps; d.rank = rank;
+  return d;
+}
+
+// the step `only_step` (n_epochs = 1) or whole epochs (only_step < 0) of n_steps steps
+template <class T>
+int glove_run_device(const int32_t* d_rows, const int32_t* d_cols, const T* d_fx, const T* d_lx, int n, int64_t nnz, const void* d_index,
+                     int n_epochs, int only_step, int n_steps, const char* steps_name, int rank, double lr, double lambda, T* d_Wi,
+                     T* d_Wj, T* d_bi, T* d_bj, double* d_aWi, double* d_aWj, double* d_abi, double* d_abj, double* d_trace,
+                     void* stream) {
+  const bool missing = !d_rows || !d_cols || !d_fx || !d_lx || !d_index || !d_Wi || !d_Wj || !d_bi || !d_bj || !d_aWi || !d_aWj ||
+                       !d_abi || !d_abj || !d_trace;
+  if (int rc = glove_args(missing, n, nnz, n_steps, steps_name, rank)) return rc;
+  const auto ok = [](double v) { return v >= 0.0 && v <= 1.7976931348623157e308; };   // (NaN fails both)
+  if (!ok(lr) || !ok(lambda)) return fail(RSPARSE_HIP_ERR_INVALID, "the learning rate or lambda is negative or not finite");
+  if (n_epochs < 0) return fail(RSPARSE_HIP_ERR_INVALID, "n_epochs < 0");
+  hipStream_t s = (hipStream_t)stream;
+  if (only_step < 0 && n_epochs) HIP_TRY(hipMemsetAsync(d_trace, 0, (size_t)n_epochs * 8, s));
+  if (nnz == 0 || n_epochs == 0) return RSPARSE_HIP_OK;
+  hipError_t e = launch_glove_run<T>(glove_data_of(d_rows, d_cols, d_fx, d_lx, n, nnz, n_steps, rank), d_index, lr, lambda, n_epochs,
+                                     only_step, d_Wi, d_Wj, d_bi, d_bj, d_aWi, d_aWj, d_abi, d_abj, d_trace, s);
+  if (e == hipErrorInvalidValue) return fail(RSPARSE_HIP_ERR_INVALID, "d_index was not built for this n, nnz and these steps");
+  if (e != hipSuccess) return hip_fail(e, "launch_glove_run");
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int rsparse_hip_glove_index_device(const int32_t* d_rows, const int32_t* d_cols, int n, int64_t nnz, int n_steps, void* d_index,
+                                   size_t* index_bytes, void* stream) {
+  if (!index_bytes) return fail(RSPARSE_HIP_ERR_INVALID, "index_bytes is NULL");
+  if (int rc = glove_args(false, n, nnz, n_steps, "n_steps", 1)) return rc;
+  const size_t need = glove_index_bytes(nnz, n_steps);
+  if (!d_index) {
+    *index_bytes = need;
+    return RSPARSE_HIP_OK;
+  }
+  if (!d_rows || !d_cols) return fail(RSPARSE_HIP_ERR_INVALID, "the positions are NULL");
+  if (*index_bytes < need) return fail(RSPARSE_HIP_ERR_INVALID, "d_index holds fewer bytes than the index needs");
+  hipError_t e = launch_glove_index(glove_data_of(d_rows, d_cols, nullptr, nullptr, n, nnz, n_steps, 1), d_index, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_glove_index");
+  return RSPARSE_HIP_OK;
+}
+
+#define RSPARSE_GLOVE_ENTRIES(SUFFIX, T)                                                                                                \
+  int rsparse_hip_glove_step##SUFFIX(const int32_t* d_rows, const int32_t* d_cols, const T* d_fx, const T* d_lx, int n, int64_t nnz,     \
+                                     const void* d_index, int step, int n_steps, int rank, double learning_rate, double lambda,          \
+                                     T* d_Wi, T* d_Wj, T* d_bi, T* d_bj, double* d_aWi, double* d_aWj, double* d_abi, double* d_abj,      \
+                                     double* d_trace, void* stream) {                                                                     \
+    if (step < 0 || step >= n_steps) return fail(RSPARSE_HIP_ERR_INVALID, "step outside [0, n_steps)");                                  \
+    return glove_run_device<T>(d_rows, d_cols, d_fx, d_lx, n, nnz, d_index, 1, step, n_steps, "n_steps", rank, learning_rate, lambda,    \
+                               d_Wi, d_Wj, d_bi, d_bj, d_aWi, d_aWj, d_abi, d_abj, d_trace, stream);                                     \
+  }                                                                                                                                       \
+  int rsparse_hip_glove_epochs##SUFFIX(const int32_t* d_rows, const int32_t* d_cols, const T* d_fx, const T* d_lx, int n, int64_t nnz,   \
+                                       const void* d_index, int n_epochs, int batch, int rank, double learning_rate, double lambda,      \
+                                       T* d_Wi, T* d_Wj, T* d_bi, T* d_bj, double* d_aWi, double* d_aWj, double* d_abi, double* d_abj,    \
+                                       double* d_trace, void* stream) {                                                                   \
+    const int n_steps = batch < 1 ? 0 : (nnz <= 0 ? 1 : (int)((nnz + batch - 1) / batch));                                               \
+    return glove_run_device<T>(d_rows, d_cols, d_fx, d_lx, n, nnz, d_index, n_epochs, -1, n_steps, "batch", rank, learning_rate, lambda, \
+                               d_Wi, d_Wj, d_bi, d_bj, d_aWi, d_aWj, d_abi, d_abj, d_trace, stream);                                     \
+  }
+RSPARSE_GLOVE_ENTRIES(_device, float)
+RSPARSE_GLOVE_ENTRIES(_f64_device, double)
+#undef RSPARSE_GLOVE_ENTRIES
+
 namespace {
 // the device form of both samplers: d_cum == nullptr is the uniform stream, otherwise the weighted one under that prefix
 int sample_negatives_device(uint64_t seed, int64_t row0, int n_rows, int n_item, int n, const int32_t* d_seen_p,

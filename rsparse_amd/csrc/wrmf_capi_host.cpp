@@ -1245,6 +1245,64 @@ int rsparse_hip_fm_predict(const int32_t* p, const int32_t* j, const double* x, 
   return RSPARSE_HIP_OK;
 }
 
+int rsparse_hip_glove_fit(const int32_t* rows, const int32_t* cols, const double* fx, const double* lx, int n, int64_t nnz, int n_epochs,
+                          int batch, int rank, double learning_rate, double lambda, double* Wi, double* Wj, double* bi, double* bj,
+                          double* aWi, double* aWj, double* abi, double* abj, double* trace) {
+  if (!Wi || !Wj || !bi || !bj || !aWi || !aWj || !abi || !abj || !trace)
+    return fail(RSPARSE_HIP_ERR_INVALID, "a parameter, a state or the trace is NULL");
+  if (n < 1 || nnz < 0 || nnz > 0x7fffffffLL || rank < 1)
+    return fail(RSPARSE_HIP_ERR_INVALID, "n < 1, nnz < 0, nnz >= 2^31 or rank < 1");
+  if (n_epochs < 0 || batch < 1) return fail(RSPARSE_HIP_ERR_INVALID, "n_epochs < 0 or batch < 1");
+  if (rank > RSPARSE_HIP_GLOVE_MAX_RANK)
+    return fail(RSPARSE_HIP_ERR_UNSUPPORTED, "rank > " + std::to_string(RSPARSE_HIP_GLOVE_MAX_RANK) + " is not on the device path");
+  if (nnz && (!rows || !cols || !fx || !lx)) return fail(RSPARSE_HIP_ERR_INVALID, "rows, cols, fx or lx is NULL");
+  for (int64_t e = 0; e < nnz; e++) {
+    if (rows[e] < 0 || rows[e] >= n || cols[e] < 0 || cols[e] >= n) return fail(RSPARSE_HIP_ERR_INVALID, "a position outside the matrix");
+    if (e && (rows[e] < rows[e - 1] || (rows[e] == rows[e - 1] && cols[e] <= cols[e - 1])))
+      return fail(RSPARSE_HIP_ERR_INVALID, "the positions are not in CSR order (rows ascending, columns strictly ascending per row)");
+    if (!(fx[e] - fx[e] == 0.0) || !(lx[e] - lx[e] == 0.0)) return fail(RSPARSE_HIP_ERR_INVALID, "fx or lx holds a value that is not finite");
+  }
+  std::memset(trace, 0, (size_t)n_epochs * 8);
+  if (nnz == 0 || n_epochs == 0) return RSPARSE_HIP_OK;
+  const size_t m = (size_t)nnz, nn = (size_t)n, k = (size_t)rank;
+  DevBuf dR, dC, dF, dL, dWi, dWj, dBi, dBj, dAWi, dAWj, dABi, dABj, dT, dI;
+  HIP_TRY(upload_host(dR, rows, m));
+  HIP_TRY(upload_host(dC, cols, m));
+  HIP_TRY(upload_host(dF, fx, m));
+  HIP_TRY(upload_host(dL, lx, m));
+  HIP_TRY(upload_host(dWi, Wi, nn * k));
+  HIP_TRY(upload_host(dWj, Wj, nn * k));
+  HIP_TRY(upload_host(dBi, bi, nn));
+  HIP_TRY(upload_host(dBj, bj, nn));
+  HIP_TRY(upload_host(dAWi, aWi, nn * k));
+  HIP_TRY(upload_host(dAWj, aWj, nn * k));
+  HIP_TRY(upload_host(dABi, abi, nn));
+  HIP_TRY(upload_host(dABj, abj, nn));
+  HIP_TRY(dT.alloc((size_t)n_epochs * 8));
+  const int n_steps = (int)((nnz + batch - 1) / batch);
+  size_t bytes = 0;
+  int rc = rsparse_hip_glove_index_device(dR.as<int32_t>(), dC.as<int32_t>(), n, nnz, n_steps, nullptr, &bytes, nullptr);
+  if (rc) return rc;
+  HIP_TRY(dI.alloc(bytes));
+  if ((rc = rsparse_hip_glove_index_device(dR.as<int32_t>(), dC.as<int32_t>(), n, nnz, n_steps, dI.p, &bytes, nullptr))) return rc;
+  rc = rsparse_hip_glove_epochs_f64_device(dR.as<int32_t>(), dC.as<int32_t>(), dF.as<double>(), dL.as<double>(), n, nnz, dI.p, n_epochs,
+                                           batch, rank, learning_rate, lambda, dWi.as<double>(), dWj.as<double>(), dBi.as<double>(),
+                                           dBj.as<double>(), dAWi.as<double>(), dAWj.as<double>(), dABi.as<double>(), dABj.as<double>(),
+                                           dT.as<double>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(download(Wi, dWi, nn * k));
+  HIP_TRY(download(Wj, dWj, nn * k));
+  HIP_TRY(download(bi, dBi, nn));
+  HIP_TRY(download(bj, dBj, nn));
+  HIP_TRY(download(aWi, dAWi, nn * k));
+  HIP_TRY(download(aWj, dAWj, nn * k));
+  HIP_TRY(download(abi, dABi, nn));
+  HIP_TRY(download(abj, dABj, nn));
+  HIP_TRY(download(trace, dT, (size_t)n_epochs));
+  return RSPARSE_HIP_OK;
+}
+
 extern "C++" {
 namespace {
 // B (n x n column-major, an R matrix) as n row-major rows of ld elements, zeros beyond n; a non-finite entry -> false

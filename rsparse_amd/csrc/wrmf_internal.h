@@ -456,6 +456,27 @@ template <class T>
 hipError_t launch_fm_run(const FmData& d, const void* index, const FmOpt& o, int n_epochs, int only_step, const double* y,
                          const double* omega, T* w0, T* w, T* V, double* a0, double* aw, double* aV, void* trace, hipStream_t s);
 
+// GloVe (wrmf_glove.hip; defined in rsparse_wrmf_hip.h).  The data: the stored positions of the canonical n x n matrix in CSR order
+// (rows ascending, nnz of them; fx and lx in the parameters' type T), the steps of an epoch (1 <= n_steps <= nnz) and 1 <= rank <=
+// 128.  index: both sides' index of (rows, cols, n_steps) into glove_index_bytes(nnz, n_steps) bytes; waits for `s`.  run: the steps
+// [0, n_steps) (only_step < 0) or the one step only_step of n_epochs epochs in place; trace: one double per epoch (only_step >= 0:
+// one double), ADDED to.  Allocates its scratch, reads the index's step ranges back once and waits for `s` before it returns;
+// hipErrorInvalidValue: the index was built for another n, nnz or n_steps.
+struct GloveData {
+  const int32_t* rows;
+  const int32_t* cols;
+  const void* fx;
+  const void* lx;
+  int n;
+  int64_t nnz;
+  int n_steps, rank;
+};
+size_t glove_index_bytes(int64_t nnz, int n_steps);
+hipError_t launch_glove_index(const GloveData& d, void* ws, hipStream_t s);
+template <class T>
+hipError_t launch_glove_run(const GloveData& d, const void* index, double lr, double lambda, int n_epochs, int only_step, T* Wi, T* Wj,
+                            T* bi, T* bj, double* aWi, double* aWj, double* abi, double* abj, double* trace, hipStream_t s);
+
 // ItemKNN (wrmf_itemknn.hip; defined in rsparse_wrmf_hip.h).  `rows` dense rows of n_items cells per batch in ws (uint32 cells
 // for the binary neighbours, uint64 for the weighted ones and for the lists), which is all zeros on entry and again when the
 // enqueued work is done.  h_ip: the host copy of ip[item0 .. item1]; h_xp: of xp[0 .. n_rows].  1 <= K <= 256, 1 <= k <= 1024.

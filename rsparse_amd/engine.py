@@ -1218,6 +1218,50 @@ class HipBackend:
                              lam_v, self._fm_trace(n_epochs, family))
         return trace[:int(n_epochs)]
 
+    def glove_index(self, rows, cols, n, n_steps):
+        """both sides' index of the stored positions (rows, cols: int32 on the device, in CSR order) of an n x n matrix for epochs of
+        n_steps steps (wrmf_glove.hip: the row side from the order itself, the column side by one stable radix sort) -> (the index's
+        bytes on the device, nnz, n_steps, n).  One host synchronisation; built once per (x, n_steps)."""
+        assert rows.dtype == torch.int32 and cols.dtype == torch.int32 and rows.is_cuda and rows.numel() == cols.numel()
+        nnz = int(rows.numel())
+        need = ctypes.c_size_t(0)
+        head = (rows.data_ptr(), cols.data_ptr(), int(n), nnz, int(n_steps))
+        _lib.check(self.lib.rsparse_hip_glove_index_device(*head, None, ctypes.byref(need), self._stream()))
+        ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.rsparse_hip_glove_index_device(*head, ws.data_ptr(), ctypes.byref(need), self._stream()))
+        return ws, nnz, int(n_steps), int(n)
+
+    def _glove_run(self, name, rows, cols, fx, lx, index, a, b, W_i, W_j, b_i, b_j, aW_i, aW_j, ab_i, ab_j, lr, lam, trace):
+        ws, nnz, _, n = index
+        dt = W_i.dtype
+        assert dt in (torch.float32, torch.float64) and all(t.dtype == dt and t.is_contiguous() for t in (fx, lx, W_j, b_i, b_j))
+        assert nnz == int(rows.numel()) == int(fx.numel()) == int(lx.numel()) and W_i.is_contiguous()
+        assert tuple(W_i.shape) == tuple(W_j.shape) == tuple(aW_i.shape) == tuple(aW_j.shape) and W_i.shape[0] == n
+        assert b_i.numel() == b_j.numel() == ab_i.numel() == ab_j.numel() == n
+        assert all(t.dtype == torch.float64 and t.is_contiguous() for t in (aW_i, aW_j, ab_i, ab_j))
+        f = "_f64" if dt == torch.float64 else ""
+        _lib.check(getattr(self.lib, "rsparse_hip_glove_%s%s_device" % (name, f))(
+            rows.data_ptr(), cols.data_ptr(), fx.data_ptr(), lx.data_ptr(), n, nnz, ws.data_ptr(), int(a), int(b), int(W_i.shape[1]),
+            float(lr), float(lam), W_i.data_ptr(), W_j.data_ptr(), b_i.data_ptr(), b_j.data_ptr(), aW_i.data_ptr(), aW_j.data_ptr(),
+            ab_i.data_ptr(), ab_j.data_ptr(), trace.data_ptr(), self._stream()))
+        return trace
+
+    def glove_step(self, rows, cols, fx, lx, index, step, W_i, W_j, b_i, b_j, aW_i, aW_j, ab_i, ab_j, lr, lam):
+        """one GloVe step in place on (W_i, W_j, b_i, b_j) and their float64 Adagrad states (rsparse_amd.glove.glove_step_reference
+        is the definition; index: of `glove_index`) -> the step's trace term, one float64 on the device"""
+        trace = torch.zeros(1, dtype=torch.float64, device=self.device)
+        return self._glove_run("step", rows, cols, fx, lx, index, step, index[2], W_i, W_j, b_i, b_j, aW_i, aW_j, ab_i, ab_j, lr, lam, trace)
+
+    def glove_epochs(self, rows, cols, fx, lx, index, n_epochs, W_i, W_j, b_i, b_j, aW_i, aW_j, ab_i, ab_j, lr, lam):
+        """n_epochs epochs of the index's n_steps steps each, in place, on one stream with no host synchronisation between them ->
+        the cost of every epoch (not divided by nnz), float64 on the device"""
+        nnz, n_steps = index[1], index[2]
+        batch = max(1, -(-nnz // n_steps))
+        assert max(1, -(-nnz // batch)) == n_steps, "the index was built for another number of steps"
+        trace = torch.zeros(max(int(n_epochs), 1), dtype=torch.float64, device=self.device)
+        self._glove_run("epochs", rows, cols, fx, lx, index, n_epochs, batch, W_i, W_j, b_i, b_j, aW_i, aW_j, ab_i, ab_j, lr, lam, trace)
+        return trace[:int(n_epochs)]
+
     def item_features(self, F, dtype):
         """a canonical scipy CSR F (n_items x n_feat) -> (fp, fj, fx, cp, ci, cx, n_feat) on the device: F by item and, through
         `transpose_csc`, by feature; values of `dtype`"""
