@@ -1516,6 +1516,90 @@ int rsparse_hip_glove_fit(const int32_t* rows, const int32_t* cols, const double
                           double* aWi, double* aWj, double* abi, double* abj, double* trace);
 
 /* ------------------------------------------------------------------------------------------------
+ * FTRL-proximal elastic-net GLM (McMahan et al. 2013) by deterministic mini-batches (wrmf_ftrl.hip)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The definition (rsparse_amd/ftrl.py states it in numpy: ftrl_weights_reference, ftrl_keep_reference, ftrl_forward_reference,
+ * ftrl_step_reference, ftrl_fit_reference, tsum).  Every arithmetic operation is a separately rounded float64 operation on values
+ * widened from the state's type; nothing is fused.
+ *   x: the canonical CSR of the factorization machine.  y: {0, 1} (binomial), any finite value (gaussian), finite and >= 0
+ *   (poisson); omega: finite weights >= 0.  State: zn, n_feat interleaved pairs (z_j, n_j) in the model's type, from +0.0;
+ *   16-byte aligned.  alpha = learning_rate > 0, beta = learning_rate_decay > 0, lambda >= 0, l1_ratio in [0, 1], l1 = lambda
+ *   l1_ratio, l2 = lambda (1 - l1_ratio), dropout in [0, 1), clip = RSPARSE_HIP_FTRL_CLIP.
+ *   Steps: as the factorization machine's; `epoch` counts the epochs over the life of the model.
+ *   Weight from the snapshot: w_j = +0.0 where |z_j| <= l1, else (-1 / ((beta + sqrt(n_j)) / alpha + l2)) (z_j - sgn(z_j) l1).
+ *   Dropout: the entry at position t of row r takes word o[t & 3] of Philox4x32-10 with counter (t >> 2, r, 8, epoch), key
+ *   (lo32(seed), hi32(seed)); KEPT iff word >= T = floor(dropout 2^32); x' = x keep_scale, keep_scale = 1 / (1 - dropout).
+ *   tsum(list): the list cut into chunks of 64 consecutive terms, a short last one padded with +0.0; a chunk reduced by the tree
+ *   v[t] = v[t] + v[t + 32], then 16, 8, 4, 2, 1; the chunk sums added sequentially to a total that starts at +0.0.
+ *   Forward, row r with ALL its stored entries in ascending column: raw = tsum_e(w[j_e] x'_e for a kept entry, +0.0 for a dropped
+ *   one); p = 1 / (1 + E(-raw)) (binomial), raw (gaussian), E(raw) (poisson), E the stated exponential of BPR with its clamp at
+ *   +-40; d = omega (p - y); g_e = min(max(d x'_e, -clip), clip) for a kept entry, +0.0 for a dropped one.
+ *   Backward, column j, its stored entries of the step in ascending k: G = tsum(g), Q = tsum(g g), c = the KEPT entries.
+ *   Update of a column with c >= 1 (every other keeps its bits): nn = n_j + Q; sigma = (sqrt(nn) - sqrt(n_j)) / alpha;
+ *   z_j' = z_j + (G - sigma w_j); n_j' = nn; each rounded once into the type.
+ *   predict: the forward pass without dropout.
+ * Unlike the modelled-on Hogwild loop: mini-batches from a snapshot (Q and one sigma per column and step), dropout from a counter
+ * stream, x keep_scale for x / (1 - dropout), the stated exponential, all three families.
+ * No float atomics: a repeated call returns the same bits.  The forward kernel gives a row to a group of 4, 16 or 64 lanes, the
+ * narrowest with 2 G >= nnz / n_rows (the update kernel likewise by nnz / segments); a row of more than
+ * RSPARSE_HIP_FTRL_LONG_ROW entries is spread over the waves of a workgroup.  Every width gives the same bits.
+ * NULL arguments, negative dimensions, n_feat < 1, n_steps or batch < 1, a step outside [0, n_steps), a family outside the three,
+ * dropout outside [0, 1), l1_ratio outside [0, 1], a rate that is not positive and finite, a lambda that is negative or not
+ * finite, an epoch that leaves [0, 2^31), a zn that is not 16-byte aligned: RSPARSE_HIP_ERR_INVALID, before a device is touched. */
+#define RSPARSE_HIP_FTRL_LONG_ROW 512
+#define RSPARSE_HIP_FTRL_CLIP 1000.0
+#define RSPARSE_HIP_FTRL_BINOMIAL 0
+#define RSPARSE_HIP_FTRL_GAUSSIAN 1
+#define RSPARSE_HIP_FTRL_POISSON 2
+
+/* The forward pass of one step.  With d_y (and d_omega; both by row): d_prob[r] for the step's rows and d_d[k], k < ceil((n_rows -
+ * step) / n_steps).  Without d_y: predict -- d_prob[r] alone, dropout, seed and epoch unused.  nnz only picks the group width.
+ * Enqueued without synchronisation. */
+int rsparse_hip_ftrl_forward_device(const int32_t* d_p, const int32_t* d_j, const float* d_x, int n_rows, int n_feat, int64_t nnz,
+                                    int step, int n_steps, int family, double learning_rate, double learning_rate_decay, double lambda,
+                                    double l1_ratio, double dropout, uint64_t seed, int epoch, const float* d_zn, const double* d_y,
+                                    const double* d_omega, double* d_prob, double* d_d, void* stream);
+int rsparse_hip_ftrl_forward_f64_device(const int32_t* d_p, const int32_t* d_j, const double* d_x, int n_rows, int n_feat, int64_t nnz,
+                                        int step, int n_steps, int family, double learning_rate, double learning_rate_decay,
+                                        double lambda, double l1_ratio, double dropout, uint64_t seed, int epoch, const double* d_zn,
+                                        const double* d_y, const double* d_omega, double* d_prob, double* d_d, void* stream);
+/* One step in place on d_zn; d_prob[r] of the step's rows is written.  d_index: of rsparse_hip_fm_index_device for this (x,
+ * n_steps).  Waits for `stream` before it returns (its scratch is freed). */
+int rsparse_hip_ftrl_step_device(const int32_t* d_p, const int32_t* d_j, const float* d_x, int n_rows, int n_feat, int64_t nnz,
+                                 const void* d_index, int step, int n_steps, int family, double learning_rate,
+                                 double learning_rate_decay, double lambda, double l1_ratio, double dropout, uint64_t seed, int epoch,
+                                 const double* d_y, const double* d_omega, float* d_zn, double* d_prob, void* stream);
+int rsparse_hip_ftrl_step_f64_device(const int32_t* d_p, const int32_t* d_j, const double* d_x, int n_rows, int n_feat, int64_t nnz,
+                                     const void* d_index, int step, int n_steps, int family, double learning_rate,
+                                     double learning_rate_decay, double lambda, double l1_ratio, double dropout, uint64_t seed,
+                                     int epoch, const double* d_y, const double* d_omega, double* d_zn, double* d_prob, void* stream);
+/* n_epochs epochs, numbered epoch0, epoch0 + 1, ..., of ceil(n_rows / batch) steps each, on one stream with no host synchronisation
+ * between them; d_prob (n_rows) holds p of the LAST epoch.  d_index: of (x, ceil(n_rows / batch)). */
+int rsparse_hip_ftrl_epochs_device(const int32_t* d_p, const int32_t* d_j, const float* d_x, int n_rows, int n_feat, int64_t nnz,
+                                   const void* d_index, int n_epochs, int batch, int family, double learning_rate,
+                                   double learning_rate_decay, double lambda, double l1_ratio, double dropout, uint64_t seed,
+                                   int epoch0, const double* d_y, const double* d_omega, float* d_zn, double* d_prob, void* stream);
+int rsparse_hip_ftrl_epochs_f64_device(const int32_t* d_p, const int32_t* d_j, const double* d_x, int n_rows, int n_feat, int64_t nnz,
+                                       const void* d_index, int n_epochs, int batch, int family, double learning_rate,
+                                       double learning_rate_decay, double lambda, double l1_ratio, double dropout, uint64_t seed,
+                                       int epoch0, const double* d_y, const double* d_omega, double* d_zn, double* d_prob,
+                                       void* stream);
+/* d_w[j] = w_j of the definition for every feature (float64).  Enqueued without synchronisation. */
+int rsparse_hip_ftrl_weights_device(const float* d_zn, int n_feat, double learning_rate, double learning_rate_decay, double lambda,
+                                    double l1_ratio, double* d_w, void* stream);
+int rsparse_hip_ftrl_weights_f64_device(const double* d_zn, int n_feat, double learning_rate, double learning_rate_decay,
+                                        double lambda, double l1_ratio, double* d_w, void* stream);
+/* Host arrays, double state.  fit: x is checked to be canonical; z and n (n_feat each) are IN/OUT, so a second call with epoch0
+ * moved on continues where the first ended; prob (n_rows): p of the last epoch.  predict: out (n_rows). */
+int rsparse_hip_ftrl_fit(const int32_t* p, const int32_t* j, const double* x, int n_rows, int n_feat, const double* y,
+                         const double* omega, int n_epochs, int batch, int family, double learning_rate, double learning_rate_decay,
+                         double lambda, double l1_ratio, double dropout, uint64_t seed, int epoch0, double* z, double* n, double* prob);
+int rsparse_hip_ftrl_predict(const int32_t* p, const int32_t* j, const double* x, int n_rows, int n_feat, int family,
+                             double learning_rate, double learning_rate_decay, double lambda, double l1_ratio, const double* z,
+                             const double* n, double* out);
+
+/* ------------------------------------------------------------------------------------------------
  * iALS++: implicit ALS by exact block (subspace) solves (Rendle, Krichene, Zhang, Koren 2021; wrmf_subspace.hip)
  * ---------------------------------------------------------------------------------------------- */
 

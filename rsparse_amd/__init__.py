@@ -84,6 +84,10 @@ def __getattr__(name):
     if name in ("FactorizationMachine", "fm_forward_reference", "fm_step_reference", "fm_fit_reference", "fm_predict_reference"):
         from . import fm
         return getattr(fm, name)
+    if name in ("FTRL", "tsum", "ftrl_weights_reference", "ftrl_keep_reference", "ftrl_forward_reference", "ftrl_step_reference",
+                "ftrl_fit_reference"):
+        from . import ftrl
+        return getattr(ftrl, name)
     if name in ("GloVe", "glove_slots_reference", "glove_step_reference", "glove_fit_reference"):
         from . import glove
         return getattr(glove, name)

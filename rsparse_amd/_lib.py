@@ -30,6 +30,8 @@ LMF_MAX_K, LMF_LONG_ROW = 128, 512   # RSPARSE_HIP_LMF_MAX_K / _LONG_ROW: the wi
 SUBSPACE_LONG_ROW, SUBSPACE_SEGMENT = 256, 8192   # RSPARSE_HIP_SUBSPACE_LONG_ROW / _SEGMENT: the row-length edge of wrmf_subspace.hip and
 #                                                 the least number of entries a workgroup takes of a row that is split
 FM_MAX_RANK, FM_LONG_ROW = 128, 512   # RSPARSE_HIP_FM_MAX_RANK / _LONG_ROW: the widest V and the row-length edge of wrmf_fm.hip
+# RSPARSE_HIP_FTRL_*: the families, the gradient clip and the row-length edge of wrmf_ftrl.hip
+FTRL_BINOMIAL, FTRL_GAUSSIAN, FTRL_POISSON, FTRL_CLIP, FTRL_LONG_ROW = 0, 1, 2, 1000.0, 512
 GLOVE_MAX_RANK = 128   # RSPARSE_HIP_GLOVE_MAX_RANK: the widest W_i / W_j of wrmf_glove.hip
 RANKS_BATCH = 1024  # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that the rank count takes at a time
 
@@ -204,6 +206,17 @@ SIGNATURES = {
        for n in ("step", "epochs") for f in ("", "_f64")},
     "rsparse_hip_fm_fit": (_c_int, [_vp] * 3 + [_c_int, _c_int, _vp, _vp] + [_c_int] * 5 + [_c_dbl] * 4 + [_vp] * 7),
     "rsparse_hip_fm_predict": (_c_int, [_vp] * 3 + [_c_int] * 4 + [_vp] * 4),
+    # FTRL: (p, j, x, n_rows, n_feat, nnz, step, n_steps, GLM, dropout, seed, epoch, zn, y, omega, prob, d, stream); (p, j, x, n_rows,
+    # n_feat, nnz, index, step | n_epochs, n_steps | batch, GLM, dropout, seed, epoch, y, omega, zn, prob, stream); (zn, n_feat, alpha,
+    # beta, lambda, l1_ratio, w, stream).  GLM = family, learning_rate, learning_rate_decay, lambda, l1_ratio
+    **{"rsparse_hip_ftrl_forward%s_device" % f: (_c_int, [_vp] * 3 + [_c_int, _c_int, _c_i64, _c_int, _c_int, _c_int] + [_c_dbl] * 5 +
+                                                 [_c_u64, _c_int] + [_vp] * 6) for f in ("", "_f64")},
+    **{"rsparse_hip_ftrl_%s%s_device" % (n, f): (_c_int, [_vp] * 3 + [_c_int, _c_int, _c_i64, _vp, _c_int, _c_int, _c_int] + [_c_dbl] * 5 +
+                                                 [_c_u64, _c_int] + [_vp] * 5) for n in ("step", "epochs") for f in ("", "_f64")},
+    **{"rsparse_hip_ftrl_weights%s_device" % f: (_c_int, [_vp, _c_int] + [_c_dbl] * 4 + [_vp, _vp]) for f in ("", "_f64")},
+    "rsparse_hip_ftrl_fit": (_c_int, [_vp] * 3 + [_c_int, _c_int, _vp, _vp, _c_int, _c_int, _c_int] + [_c_dbl] * 5 + [_c_u64, _c_int] +
+                             [_vp] * 3),
+    "rsparse_hip_ftrl_predict": (_c_int, [_vp] * 3 + [_c_int] * 3 + [_c_dbl] * 4 + [_vp] * 3),
     "rsparse_hip_glove_index_device": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_int, _vp, ctypes.POINTER(ctypes.c_size_t), _vp]),
     **{"rsparse_hip_glove_%s%s_device" % (n, f): (_c_int, [_vp] * 4 + [_c_int, _c_i64, _vp] + [_c_int] * 3 + [_c_dbl] * 2 + [_vp] * 10)
        for n in ("step", "epochs") for f in ("", "_f64")},

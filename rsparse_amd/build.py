@@ -17,9 +17,9 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 SRC = [CSRC / n for n in ("wrmf_kernels.hip", "wrmf_cgq.hip", "wrmf_cgp.hip", "wrmf_ne.hip", "wrmf_chol.hip", "wrmf_chol_wave.hip", "wrmf_chol_mf.hip", "wrmf_cg_mf.hip", "wrmf_chol_lr.hip",
-                          "wrmf_topk.hip", "wrmf_topk_large.hip", "wrmf_similar.hip", "wrmf_metrics.hip", "wrmf_hits.hip", "wrmf_lists.hip", "wrmf_diversity.hip", "wrmf_mmr.hip", "wrmf_ranks.hip", "wrmf_score.hip", "wrmf_softals.hip", "wrmf_itemknn.hip", "wrmf_ease.hip", "wrmf_slim.hip", "wrmf_bpr.hip", "wrmf_bpr_features.hip", "wrmf_lmf.hip", "wrmf_fm.hip", "wrmf_glove.hip", "wrmf_subspace.hip", "wrmf_candidates.hip", "wrmf_sample.hip", "wrmf_sample_weighted.hip", "wrmf_split.hip", "wrmf_confidence.hip", "wrmf_events.hip", "wrmf_explain.hip", "wrmf_init.hip", "wrmf_ingest.hip", "wrmf_nnls.hip", "wrmf_bias.hip", "wrmf_lu.hip",
+                          "wrmf_topk.hip", "wrmf_topk_large.hip", "wrmf_similar.hip", "wrmf_metrics.hip", "wrmf_hits.hip", "wrmf_lists.hip", "wrmf_diversity.hip", "wrmf_mmr.hip", "wrmf_ranks.hip", "wrmf_score.hip", "wrmf_softals.hip", "wrmf_itemknn.hip", "wrmf_ease.hip", "wrmf_slim.hip", "wrmf_bpr.hip", "wrmf_bpr_features.hip", "wrmf_lmf.hip", "wrmf_fm.hip", "wrmf_ftrl.hip", "wrmf_glove.hip", "wrmf_subspace.hip", "wrmf_candidates.hip", "wrmf_sample.hip", "wrmf_sample_weighted.hip", "wrmf_split.hip", "wrmf_confidence.hip", "wrmf_events.hip", "wrmf_explain.hip", "wrmf_init.hip", "wrmf_ingest.hip", "wrmf_nnls.hip", "wrmf_bias.hip", "wrmf_lu.hip",
                           "wrmf_f64.hip", "wrmf_wide.hip", "wrmf_wide_cg.hip", "wrmf_ctx_kernels.hip", "wrmf_schedule.cpp", "wrmf_capi.cpp", "wrmf_f64_capi.cpp", "wrmf_capi_host.cpp", "wrmf_ctx.cpp")]
-HEADERS = [CSRC / "wrmf_chol_mf.attrs.csv", CSRC / "wrmf_mf.h", CSRC / "wrmf_internal.h", CSRC / "wrmf_capi_common.h", CSRC / "wrmf_schedule.h", CSRC / "wrmf_device.h", CSRC / "wrmf_bpr_device.h", CSRC / "wrmf_sample_team.h", CSRC / "wrmf_wave.h", CSRC / "wrmf_csr_rows.h", CSRC / "wrmf_ldlt.h", CSRC / "wrmf_f64.h", CSRC / "wrmf_topk_plan.h", CSRC / "wrmf_ctx_layout.h", PKG.parent / "include" / "rsparse_wrmf_hip.h"]
+HEADERS = [CSRC / "wrmf_chol_mf.attrs.csv", CSRC / "wrmf_mf.h", CSRC / "wrmf_internal.h", CSRC / "wrmf_capi_common.h", CSRC / "wrmf_schedule.h", CSRC / "wrmf_device.h", CSRC / "wrmf_bpr_device.h", CSRC / "wrmf_fm_index.h", CSRC / "wrmf_sample_team.h", CSRC / "wrmf_wave.h", CSRC / "wrmf_csr_rows.h", CSRC / "wrmf_ldlt.h", CSRC / "wrmf_f64.h", CSRC / "wrmf_topk_plan.h", CSRC / "wrmf_ctx_layout.h", PKG.parent / "include" / "rsparse_wrmf_hip.h"]
 DEPS = SRC + HEADERS
 OUT = PKG / "lib" / "librsparse_wrmf_hip.so"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
@@ -50,6 +50,9 @@ EXTRA_FLAGS["wrmf_fm.hip"] = ["-ffp-contract=off", "-Xclang", "-target-feature",
 # wrmf_glove.hip: the scores, the gradient sums and the Adagrad update of rsparse_amd/glove.py are separately rounded float64
 # operations; its only fp32 work is moving parameters
 EXTRA_FLAGS["wrmf_glove.hip"] = ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+# wrmf_ftrl.hip: the weights, the tree sums, the link and the update of rsparse_amd/ftrl.py are separately rounded float64
+# operations; its only fp32 work is moving the state
+EXTRA_FLAGS["wrmf_ftrl.hip"] = ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 AUDITED = {"wrmf_chol_mf.hip", "wrmf_cg_mf.hip"}
 REG_LIMIT = {"wrmf_cg_mf.hip": 512}   # (one wave per SIMD by design: 320 accumulator registers per row)
 # Kernels that fit two waves per SIMD only without a spill (the 24-quad team kernel of wrmf_cgq.hip keeps 192 registers of
@@ -118,6 +121,9 @@ NO_SPILL = {"wrmf_cgq.hip": ("14als_cgq_kernelILi128ELi24ELi4ELi4E",),
             # walks; the index kernels are integer-only
             "wrmf_fm.hip": ("fm_forward_kernel", "fm_w0_kernel", "fm_chunks_kernel", "fm_update_kernel", "fm_keys_kernel",
                             "fm_heads_kernel", "fm_entries_kernel", "fm_nch_kernel", "fm_steps_kernel"),
+            # a lane keeps the 64 / G term slots of a chunk (columns, values and state pairs of two chunks in flight at G = 4: the
+            # widest set) and a double per slot for the tree: scratch would sit between a gather and its use
+            "wrmf_ftrl.hip": ("ftrl_forward_kernel", "ftrl_chunks_kernel", "ftrl_update_kernel", "ftrl_weights_kernel"),
             # a walk keeps the destination's row, a chunk's sum and the total (three doubles per 16 coordinates and lane) beside two
             # gathered rows and three stages of indices: scratch would sit inside the serial walk; the index kernels
             # are integer-only

@@ -2230,6 +2230,119 @@ RSPARSE_FM_ENTRIES(_f64_device, double)
 
 extern "C++" {
 namespace {
+// FTRL (wrmf_ftrl.hip), both precisions; the host forms rsparse_hip_ftrl_fit / _predict: wrmf_capi_host.cpp.  Everything is
+// checked before a device is touched.
+int ftrl_opt_of(int family, double alpha, double beta, double lambda, double l1_ratio, double dropout, uint64_t seed, FtrlOpt& o) {
+  const auto pos = [](double v) { return v > 0.0 && v <= 1.7976931348623157e308; };   // (NaN fails)
+  if (family != RSPARSE_HIP_FTRL_BINOMIAL && family != RSPARSE_HIP_FTRL_GAUSSIAN && family != RSPARSE_HIP_FTRL_POISSON)
+    return fail(RSPARSE_HIP_ERR_INVALID, "family is none of RSPARSE_HIP_FTRL_BINOMIAL, _GAUSSIAN, _POISSON");
+  if (!pos(alpha) || !pos(beta)) return fail(RSPARSE_HIP_ERR_INVALID, "learning_rate and learning_rate_decay must be positive and finite");
+  if (!(lambda >= 0.0 && lambda <= 1.7976931348623157e308)) return fail(RSPARSE_HIP_ERR_INVALID, "lambda is negative or not finite");
+  if (!(l1_ratio >= 0.0 && l1_ratio <= 1.0)) return fail(RSPARSE_HIP_ERR_INVALID, "l1_ratio outside [0, 1]");
+  if (!(dropout >= 0.0 && dropout < 1.0)) return fail(RSPARSE_HIP_ERR_INVALID, "dropout outside [0, 1)");
+  o.family = family; o.alpha = alpha; o.beta = beta;
+  o.l1 = lambda * l1_ratio;
+  o.l2 = lambda * (1.0 - l1_ratio);
+  o.keep_scale = 1.0 / (1.0 - dropout);
+  o.drop_t = (uint32_t)(dropout * 4294967296.0);   // floor: dropout < 1 keeps it below 2^32
+  o.k0 = (uint32_t)seed; o.k1 = (uint32_t)(seed >> 32);
+  return RSPARSE_HIP_OK;
+}
+
+int ftrl_args(bool missing, int n_rows, int n_feat, int64_t nnz, int n_steps, const char* steps_name, const void* d_zn) {
+  if (missing) return fail(RSPARSE_HIP_ERR_INVALID, "the matrix, the state, a target or an output is NULL");
+  if (n_rows < 0 || n_feat < 1 || nnz < 0 || nnz > 0x7fffffffLL)
+    return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n_rows < 0, n_feat < 1, nnz < 0 or nnz >= 2^31)");
+  if (n_steps < 1) return fail(RSPARSE_HIP_ERR_INVALID, std::string(steps_name) + " < 1");
+  if (reinterpret_cast<uintptr_t>(d_zn) % 16) return fail(RSPARSE_HIP_ERR_INVALID, "d_zn is not 16-byte aligned");
+  return RSPARSE_HIP_OK;
+}
+
+template <class T>
+int ftrl_forward_device(const int32_t* d_p, const int32_t* d_j, const T* d_x, int n_rows, int n_feat, int64_t nnz, int step, int n_steps,
+                        int family, double alpha, double beta, double lambda, double l1_ratio, double dropout, uint64_t seed, int epoch,
+                        const T* d_zn, const double* d_y, const double* d_omega, double* d_prob, double* d_d, void* stream) {
+  const bool missing = !d_p || !d_j || !d_x || !d_zn || !d_prob || (d_y && (!d_omega || !d_d));
+  if (int rc = ftrl_args(missing, n_rows, n_feat, nnz, n_steps, "n_steps", d_zn)) return rc;
+  FtrlOpt o;
+  if (int rc = ftrl_opt_of(family, alpha, beta, lambda, l1_ratio, dropout, seed, o)) return rc;
+  if (step < 0 || step >= n_steps) return fail(RSPARSE_HIP_ERR_INVALID, "step outside [0, n_steps)");
+  if (epoch < 0) return fail(RSPARSE_HIP_ERR_INVALID, "epoch < 0");
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  hipError_t e = launch_ftrl_forward<T>(fm_data_of(d_p, d_j, d_x, n_rows, n_feat, nnz, n_steps, 1, 0), o, step, (uint32_t)epoch, d_zn, d_y,
+                                        d_omega, d_prob, d_d, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_ftrl_forward");
+  return RSPARSE_HIP_OK;
+}
+
+// the step `only_step` (n_epochs = 1) or whole epochs (only_step < 0) of n_steps steps
+template <class T>
+int ftrl_run_device(const int32_t* d_p, const int32_t* d_j, const T* d_x, int n_rows, int n_feat, int64_t nnz, const void* d_index,
+                    int n_epochs, int only_step, int n_steps, const char* steps_name, int family, double alpha, double beta,
+                    double lambda, double l1_ratio, double dropout, uint64_t seed, int epoch0, const double* d_y, const double* d_omega,
+                    T* d_zn, double* d_prob, void* stream) {
+  const bool missing = !d_p || !d_j || !d_x || !d_index || !d_y || !d_omega || !d_zn || !d_prob;
+  if (int rc = ftrl_args(missing, n_rows, n_feat, nnz, n_steps, steps_name, d_zn)) return rc;
+  FtrlOpt o;
+  if (int rc = ftrl_opt_of(family, alpha, beta, lambda, l1_ratio, dropout, seed, o)) return rc;
+  if (n_epochs < 0) return fail(RSPARSE_HIP_ERR_INVALID, "n_epochs < 0");
+  if (epoch0 < 0 || (int64_t)epoch0 + n_epochs > 0x7fffffffLL) return fail(RSPARSE_HIP_ERR_INVALID, "the epochs leave [0, 2^31)");
+  if (n_rows == 0 || n_epochs == 0) return RSPARSE_HIP_OK;
+  hipError_t e = launch_ftrl_run<T>(fm_data_of(d_p, d_j, d_x, n_rows, n_feat, nnz, n_steps, 1, 0), d_index, o, n_epochs, only_step,
+                                    (uint32_t)epoch0, d_y, d_omega, d_zn, d_prob, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) return fail(RSPARSE_HIP_ERR_INVALID, "d_index was not built for this nnz and these steps");
+  if (e != hipSuccess) return hip_fail(e, "launch_ftrl_run");
+  return RSPARSE_HIP_OK;
+}
+
+template <class T>
+int ftrl_weights_device(const T* d_zn, int n_feat, double alpha, double beta, double lambda, double l1_ratio, double* d_w, void* stream) {
+  if (!d_zn || !d_w || n_feat < 1) return fail(RSPARSE_HIP_ERR_INVALID, "the state or the output is NULL, or n_feat < 1");
+  if (reinterpret_cast<uintptr_t>(d_zn) % 16 || reinterpret_cast<uintptr_t>(d_w) % 16)
+    return fail(RSPARSE_HIP_ERR_INVALID, "d_zn or d_w is not 16-byte aligned");
+  FtrlOpt o;
+  if (int rc = ftrl_opt_of(RSPARSE_HIP_FTRL_GAUSSIAN, alpha, beta, lambda, l1_ratio, 0.0, 0, o)) return rc;
+  hipError_t e = launch_ftrl_weights<T>(d_zn, n_feat, o, d_w, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_ftrl_weights");
+  return RSPARSE_HIP_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+#define RSPARSE_FTRL_ENTRIES(SUFFIX, T)                                                                                                 \
+  int rsparse_hip_ftrl_forward##SUFFIX(const int32_t* d_p, const int32_t* d_j, const T* d_x, int n_rows, int n_feat, int64_t nnz,        \
+                                       int step, int n_steps, int family, double learning_rate, double learning_rate_decay,             \
+                                       double lambda, double l1_ratio, double dropout, uint64_t seed, int epoch, const T* d_zn,          \
+                                       const double* d_y, const double* d_omega, double* d_prob, double* d_d, void* stream) {            \
+    return ftrl_forward_device<T>(d_p, d_j, d_x, n_rows, n_feat, nnz, step, n_steps, family, learning_rate, learning_rate_decay, lambda, \
+                                  l1_ratio, dropout, seed, epoch, d_zn, d_y, d_omega, d_prob, d_d, stream);                              \
+  }                                                                                                                                       \
+  int rsparse_hip_ftrl_step##SUFFIX(const int32_t* d_p, const int32_t* d_j, const T* d_x, int n_rows, int n_feat, int64_t nnz,           \
+                                    const void* d_index, int step, int n_steps, int family, double learning_rate,                        \
+                                    double learning_rate_decay, double lambda, double l1_ratio, double dropout, uint64_t seed,           \
+                                    int epoch, const double* d_y, const double* d_omega, T* d_zn, double* d_prob, void* stream) {        \
+    if (n_steps >= 1 && (step < 0 || step >= n_steps)) return fail(RSPARSE_HIP_ERR_INVALID, "step outside [0, n_steps)");               \
+    return ftrl_run_device<T>(d_p, d_j, d_x, n_rows, n_feat, nnz, d_index, 1, step, n_steps, "n_steps", family, learning_rate,           \
+                              learning_rate_decay, lambda, l1_ratio, dropout, seed, epoch, d_y, d_omega, d_zn, d_prob, stream);          \
+  }                                                                                                                                       \
+  int rsparse_hip_ftrl_epochs##SUFFIX(const int32_t* d_p, const int32_t* d_j, const T* d_x, int n_rows, int n_feat, int64_t nnz,         \
+                                      const void* d_index, int n_epochs, int batch, int family, double learning_rate,                    \
+                                      double learning_rate_decay, double lambda, double l1_ratio, double dropout, uint64_t seed,         \
+                                      int epoch0, const double* d_y, const double* d_omega, T* d_zn, double* d_prob, void* stream) {     \
+    const int n_steps = batch < 1 ? 0 : (n_rows <= 0 ? 1 : (int)(((int64_t)n_rows + batch - 1) / batch));                                \
+    return ftrl_run_device<T>(d_p, d_j, d_x, n_rows, n_feat, nnz, d_index, n_epochs, -1, n_steps, "batch", family, learning_rate,        \
+                              learning_rate_decay, lambda, l1_ratio, dropout, seed, epoch0, d_y, d_omega, d_zn, d_prob, stream);         \
+  }                                                                                                                                       \
+  int rsparse_hip_ftrl_weights##SUFFIX(const T* d_zn, int n_feat, double learning_rate, double learning_rate_decay, double lambda,       \
+                                       double l1_ratio, double* d_w, void* stream) {                                                     \
+    return ftrl_weights_device<T>(d_zn, n_feat, learning_rate, learning_rate_decay, lambda, l1_ratio, d_w, stream);                      \
+  }
+RSPARSE_FTRL_ENTRIES(_device, float)
+RSPARSE_FTRL_ENTRIES(_f64_device, double)
+#undef RSPARSE_FTRL_ENTRIES
+
+extern "C++" {
+namespace {
 // GloVe (wrmf_glove.hip), both precisions; the host form rsparse_hip_glove_fit: wrmf_capi_host.cpp
 int glove_args(bool missing, int n, int64_t nnz, int n_steps, const char* steps_name, int rank) {
   if (missing) return fail(RSPARSE_HIP_ERR_INVALID, "the positions, a parameter, a state or an output is NULL");

@@ -1245,6 +1245,90 @@ int rsparse_hip_fm_predict(const int32_t* p, const int32_t* j, const double* x, 
   return RSPARSE_HIP_OK;
 }
 
+extern "C++" {
+namespace {
+// the parameter ranges of FTRL, looked at before anything is uploaded (the device entries state the same)
+bool ftrl_host_params(int family, double alpha, double beta, double lambda, double l1_ratio) {
+  const double big = 1.7976931348623157e308;
+  return family >= RSPARSE_HIP_FTRL_BINOMIAL && family <= RSPARSE_HIP_FTRL_POISSON && alpha > 0.0 && alpha <= big && beta > 0.0 &&
+         beta <= big && lambda >= 0.0 && lambda <= big && l1_ratio >= 0.0 && l1_ratio <= 1.0;
+}
+}  // namespace
+}  // extern "C++"
+
+// FTRL on host arrays: z and n travel as the interleaved pairs the kernels read
+int rsparse_hip_ftrl_fit(const int32_t* p, const int32_t* j, const double* x, int n_rows, int n_feat, const double* y,
+                         const double* omega, int n_epochs, int batch, int family, double learning_rate, double learning_rate_decay,
+                         double lambda, double l1_ratio, double dropout, uint64_t seed, int epoch0, double* z, double* n, double* prob) {
+  if (!p || !y || !omega || !z || !n || !prob) return fail(RSPARSE_HIP_ERR_INVALID, "the matrix, a target, the state or the output is NULL");
+  if (n_epochs < 0 || batch < 1) return fail(RSPARSE_HIP_ERR_INVALID, "n_epochs < 0 or batch < 1");
+  if (!ftrl_host_params(family, learning_rate, learning_rate_decay, lambda, l1_ratio) || !(dropout >= 0.0 && dropout < 1.0) || epoch0 < 0)
+    return fail(RSPARSE_HIP_ERR_INVALID, "a rate, lambda, l1_ratio, dropout, the family or epoch0 is outside its range");
+  DevBuf dP, dJ, dX, dY, dO, dZN, dProb, dI;
+  size_t nnz = 0;
+  if (int rc = fm_upload(p, j, x, n_rows, n_feat, 1, dP, dJ, dX, nnz)) return rc;
+  for (int r = 0; r < n_rows; r++)
+    if (!(y[r] - y[r] == 0.0) || !(omega[r] >= 0.0 && omega[r] <= 1.7976931348623157e308) ||
+        (family == RSPARSE_HIP_FTRL_BINOMIAL && y[r] != 0.0 && y[r] != 1.0) || (family == RSPARSE_HIP_FTRL_POISSON && y[r] < 0.0))
+      return fail(RSPARSE_HIP_ERR_INVALID, "y is not finite (binomial: not 0 / 1; poisson: negative) or a weight is negative or not finite");
+  if (n_rows == 0 || n_epochs == 0) return RSPARSE_HIP_OK;
+  const size_t d = (size_t)n_feat;
+  std::vector<double> zn(2 * d);
+  for (size_t f = 0; f < d; f++) {
+    zn[2 * f] = z[f];
+    zn[2 * f + 1] = n[f];
+  }
+  const int n_steps = (int)(((int64_t)n_rows + batch - 1) / batch);
+  HIP_TRY(upload_host(dY, y, (size_t)n_rows));
+  HIP_TRY(upload_host(dO, omega, (size_t)n_rows));
+  HIP_TRY(upload_host(dZN, zn.data(), 2 * d));
+  HIP_TRY(dProb.alloc((size_t)n_rows * 8));
+  size_t bytes = 0;
+  int rc = rsparse_hip_fm_index_device(dP.as<int32_t>(), dJ.as<int32_t>(), n_rows, n_feat, (int64_t)nnz, n_steps, nullptr, &bytes, nullptr);
+  if (rc) return rc;
+  HIP_TRY(dI.alloc(bytes));
+  if ((rc = rsparse_hip_fm_index_device(dP.as<int32_t>(), dJ.as<int32_t>(), n_rows, n_feat, (int64_t)nnz, n_steps, dI.p, &bytes, nullptr)))
+    return rc;
+  rc = rsparse_hip_ftrl_epochs_f64_device(dP.as<int32_t>(), dJ.as<int32_t>(), dX.as<double>(), n_rows, n_feat, (int64_t)nnz, dI.p, n_epochs,
+                                          batch, family, learning_rate, learning_rate_decay, lambda, l1_ratio, dropout, seed, epoch0,
+                                          dY.as<double>(), dO.as<double>(), dZN.as<double>(), dProb.as<double>(), nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(download(zn.data(), dZN, 2 * d));
+  HIP_TRY(download(prob, dProb, (size_t)n_rows));
+  for (size_t f = 0; f < d; f++) {
+    z[f] = zn[2 * f];
+    n[f] = zn[2 * f + 1];
+  }
+  return RSPARSE_HIP_OK;
+}
+
+int rsparse_hip_ftrl_predict(const int32_t* p, const int32_t* j, const double* x, int n_rows, int n_feat, int family,
+                             double learning_rate, double learning_rate_decay, double lambda, double l1_ratio, const double* z,
+                             const double* n, double* out) {
+  if (!p || !z || !n || !out) return fail(RSPARSE_HIP_ERR_INVALID, "the matrix, the state or the output is NULL");
+  if (!ftrl_host_params(family, learning_rate, learning_rate_decay, lambda, l1_ratio))
+    return fail(RSPARSE_HIP_ERR_INVALID, "a rate, lambda, l1_ratio or the family is outside its range");
+  DevBuf dP, dJ, dX, dZN, dOut;
+  size_t nnz = 0;
+  if (int rc = fm_upload(p, j, x, n_rows, n_feat, 1, dP, dJ, dX, nnz)) return rc;
+  if (n_rows == 0) return RSPARSE_HIP_OK;
+  std::vector<double> zn(2 * (size_t)n_feat);
+  for (size_t f = 0; f < (size_t)n_feat; f++) {
+    zn[2 * f] = z[f];
+    zn[2 * f + 1] = n[f];
+  }
+  HIP_TRY(upload_host(dZN, zn.data(), zn.size()));
+  HIP_TRY(dOut.alloc((size_t)n_rows * 8));
+  int rc = rsparse_hip_ftrl_forward_f64_device(dP.as<int32_t>(), dJ.as<int32_t>(), dX.as<double>(), n_rows, n_feat, (int64_t)nnz, 0, 1,
+                                               family, learning_rate, learning_rate_decay, lambda, l1_ratio, 0.0, 0, 0, dZN.as<double>(),
+                                               nullptr, nullptr, dOut.as<double>(), nullptr, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(download(out, dOut, (size_t)n_rows));
+  return RSPARSE_HIP_OK;
+}
+
 int rsparse_hip_glove_fit(const int32_t* rows, const int32_t* cols, const double* fx, const double* lx, int n, int64_t nnz, int n_epochs,
                           int batch, int rank, double learning_rate, double lambda, double* Wi, double* Wj, double* bi, double* bj,
                           double* aWi, double* aWj, double* abi, double* abj, double* trace) {

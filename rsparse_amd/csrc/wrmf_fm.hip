@@ -30,6 +30,7 @@
 #include "wrmf_internal.h"
 #include "wrmf_device.h"
 #include "wrmf_bpr_device.h"
+#include "wrmf_fm_index.h"
 
 #pragma clang fp contract(off)
 
@@ -38,30 +39,12 @@ namespace {
 
 using namespace dev;
 using namespace bprdev;
+using namespace fmidx;
 
 constexpr int kFmLongRow = RSPARSE_HIP_FM_LONG_ROW;
-constexpr int kFmMagic = 0x464d4958;
 constexpr int kFmTile = kBprThreads;   // chunk sums of one round of the w0 kernel
 
-// ---- the backward index ----------------------------------------------------------------------------------------------------------
-// the workspace, in int32 units: header (magic, n_steps, nnz, n_seg), step_seg[n_steps + 1], step_ch[n_steps + 1], then
-// spay[nnz], sk[nnz], seg_col[nnz], seg_ptr[nnz + 1], choff[nnz + 1] (n_seg <= nnz bounds the last three)
-struct FmIndex {
-  int32_t *hdr, *step_seg, *step_ch, *sk, *seg_col, *seg_ptr, *choff;
-  uint32_t* spay;
-  size_t ints;
-};
-inline FmIndex fm_index_of(void* ws, int64_t nnz, int n_steps) {
-  FmIndex ix;
-  int32_t* b = static_cast<int32_t*>(ws);
-  const size_t n = (size_t)nnz, ns = (size_t)n_steps + 1, head = (4 + 2 * ns + 3) / 4 * 4;
-  ix.hdr = b; ix.step_seg = b + 4; ix.step_ch = b + 4 + ns;
-  ix.spay = reinterpret_cast<uint32_t*>(b + head);
-  ix.sk = b + head + n; ix.seg_col = b + head + 2 * n; ix.seg_ptr = b + head + 3 * n; ix.choff = b + head + 4 * n + 1;
-  ix.ints = head + 5 * n + 2;
-  return ix;
-}
-
+// ---- the backward index (its layout: wrmf_fm_index.h, which wrmf_ftrl.hip reads too) --------------------------------------------
 __device__ __forceinline__ int fm_row_of(const int32_t* __restrict__ p, int n_rows, int64_t pos) {
   int lo = 0, hi = n_rows;   // p[lo] <= pos < p[hi]
   while (hi - lo > 1) {
@@ -70,7 +53,6 @@ __device__ __forceinline__ int fm_row_of(const int32_t* __restrict__ p, int n_ro
   }
   return lo;
 }
-__device__ __forceinline__ int fm_col(int j, int n_feat) { return j < 0 ? 0 : (j >= n_feat ? n_feat - 1 : j); }   // (never outside w and V)
 
 __global__ __launch_bounds__(kBprThreads) void fm_keys_kernel(const int32_t* __restrict__ p, const int32_t* __restrict__ j, int n_rows,
                                                               int n_feat, int nnz, int n_steps, int col_bits, u64* __restrict__ keys,
@@ -137,28 +119,6 @@ inline int fm_bits(int64_t n) {   // bits that hold 0 .. n - 1, at least 1
 #define RSP_TRY(e) do { if ((err = (e)) != hipSuccess) return err; } while (0)
 
 // ---- the forward pass --------------------------------------------------------------------------------------------------------------
-// E(d) of the definition (rsparse_amd/bpr.py: bpr_exp): plain arithmetic, no library exponential
-__device__ __forceinline__ double fm_exp(double d) {
-  d = d < -40.0 ? -40.0 : (d > 40.0 ? 40.0 : d);
-  const double kk = rint(d * 1.4426950408889634);
-  const double r = (d - kk * 6.93147180369123816490e-01) - kk * 1.90821492927058770002e-10;
-  double q = 1.0 / 6227020800.0;
-  q = q * r + 1.0 / 479001600.0;
-  q = q * r + 1.0 / 39916800.0;
-  q = q * r + 1.0 / 3628800.0;
-  q = q * r + 1.0 / 362880.0;
-  q = q * r + 1.0 / 40320.0;
-  q = q * r + 1.0 / 5040.0;
-  q = q * r + 1.0 / 720.0;
-  q = q * r + 1.0 / 120.0;
-  q = q * r + 1.0 / 24.0;
-  q = q * r + 1.0 / 6.0;
-  q = q * r + 1.0 / 2.0;
-  q = q * r + 1.0;
-  q = q * r + 1.0;
-  return ldexp(q, (int)kk);
-}
-
 template <class T, int R16>
 __device__ __forceinline__ void fm_row_load(const T* __restrict__ row, int rank, int lane, T (&out)[R16]) {
 #pragma unroll

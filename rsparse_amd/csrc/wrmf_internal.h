@@ -456,6 +456,26 @@ template <class T>
 hipError_t launch_fm_run(const FmData& d, const void* index, const FmOpt& o, int n_epochs, int only_step, const double* y,
                          const double* omega, T* w0, T* w, T* V, double* a0, double* aw, double* aV, void* trace, hipStream_t s);
 
+// FTRL-proximal GLM (wrmf_ftrl.hip; defined in rsparse_wrmf_hip.h).  The data: FmData (rank and family unused) and the index of
+// launch_fm_index.  zn: the interleaved (z_j, n_j) pairs, 16-byte aligned.  forward: step `step` alone from zn -- with y: p (by
+// ROW) and d (by k), dropout from (key, epoch); without y: p alone, no dropout.  run: the steps [0, n_steps) (only_step < 0) or the
+// one step only_step of n_epochs epochs numbered from epoch0, in place; p (by row) is left from the last epoch.  Allocates its
+// scratch, reads the index's step ranges back once and waits for `s` before it returns; hipErrorInvalidValue as launch_fm_run.
+// weights: zn -> w (n_feat doubles).
+struct FtrlOpt {
+  int family;
+  double alpha, beta, l1, l2, keep_scale;   // l1 = lambda l1_ratio, l2 = lambda (1 - l1_ratio), keep_scale = 1 / (1 - dropout)
+  uint32_t drop_t, k0, k1;                  // floor(dropout 2^32); the key (lo32(seed), hi32(seed))
+};
+template <class T>
+hipError_t launch_ftrl_forward(const FmData& d, const FtrlOpt& o, int step, uint32_t epoch, const T* zn, const double* y,
+                               const double* omega, double* p_out, double* dk, hipStream_t s);
+template <class T>
+hipError_t launch_ftrl_run(const FmData& d, const void* index, const FtrlOpt& o, int n_epochs, int only_step, uint32_t epoch0,
+                           const double* y, const double* omega, T* zn, double* p_out, hipStream_t s);
+template <class T>
+hipError_t launch_ftrl_weights(const T* zn, int n_feat, const FtrlOpt& o, double* w, hipStream_t s);
+
 // GloVe (wrmf_glove.hip; defined in rsparse_wrmf_hip.h).  The data: the stored positions of the canonical n x n matrix in CSR order
 // (rows ascending, nnz of them; fx and lx in the parameters' type T), the steps of an epoch (1 <= n_steps <= nnz) and 1 <= rank <=
 // 128.  index: both sides' index of (rows, cols, n_steps) into glove_index_bytes(nnz, n_steps) bytes; waits for `s`.  run: the steps

@@ -1218,6 +1218,77 @@ class HipBackend:
                              lam_v, self._fm_trace(n_epochs, family))
         return trace[:int(n_epochs)]
 
+    def _ftrl_head(self, p, j, x, zn):
+        """the checks the FTRL calls share -> (p, j, x, n_rows, n_feat, nnz) as the C ABI takes them, and the suffix.  zn: the (n_feat,
+        2) tensor of the interleaved pairs (z_j, n_j)"""
+        assert p.dtype == torch.int32 and j.dtype == torch.int32 and p.is_cuda and x.dtype == zn.dtype and zn.dtype in (torch.float32, torch.float64)
+        assert zn.dim() == 2 and zn.shape[1] == 2 and zn.shape[0] >= 1 and zn.is_contiguous() and zn.is_cuda and j.numel() == x.numel()
+        some = lambda t: t.data_ptr() if t.numel() else p.data_ptr()   # (an empty tensor has no address to pass)
+        return (p.data_ptr(), some(j), some(x), int(p.numel()) - 1, int(zn.shape[0]), int(j.numel())), ("_f64" if zn.dtype == torch.float64 else "")
+
+    @staticmethod
+    def _ftrl_glm(family, alpha, beta, lambda_, l1_ratio):
+        return ({"binomial": _lib.FTRL_BINOMIAL, "gaussian": _lib.FTRL_GAUSSIAN, "poisson": _lib.FTRL_POISSON}[family], float(alpha),
+                float(beta), float(lambda_), float(l1_ratio))
+
+    def ftrl_forward(self, p, j, x, step, n_steps, family, alpha, beta, lambda_, l1_ratio, dropout, seed, epoch, zn, y, omega):
+        """the forward pass of step `step` of n_steps from the snapshot zn (rsparse_amd.ftrl.ftrl_forward_reference is the definition;
+        y and omega: float64 over the rows) -> (p over the step's rows k, d over k): float64 on the device"""
+        head, f = self._ftrl_head(p, j, x, zn)
+        assert y.dtype == torch.float64 and omega.dtype == torch.float64 and y.numel() == omega.numel() == head[3]
+        cnt = max(0, -(-(head[3] - int(step)) // int(n_steps)))
+        prob = torch.zeros(max(head[3], 1), dtype=torch.float64, device=self.device)
+        d = torch.zeros(max(cnt, 1), dtype=torch.float64, device=self.device)
+        some = lambda t: t.data_ptr() if t.numel() else prob.data_ptr()
+        _lib.check(getattr(self.lib, "rsparse_hip_ftrl_forward%s_device" % f)(
+            *head, int(step), int(n_steps), *self._ftrl_glm(family, alpha, beta, lambda_, l1_ratio), float(dropout), int(seed), int(epoch),
+            zn.data_ptr(), some(y), some(omega), prob.data_ptr(), d.data_ptr(), self._stream()))
+        return prob[:head[3]][int(step)::int(n_steps)], d[:cnt]
+
+    def ftrl_predict(self, p, j, x, family, alpha, beta, lambda_, l1_ratio, zn):
+        """predict of the definition on every row: the forward kernel without y and without dropout -> float64 on the device"""
+        head, f = self._ftrl_head(p, j, x, zn)
+        out = torch.zeros(max(head[3], 1), dtype=torch.float64, device=self.device)
+        _lib.check(getattr(self.lib, "rsparse_hip_ftrl_forward%s_device" % f)(
+            *head, 0, 1, *self._ftrl_glm(family, alpha, beta, lambda_, l1_ratio), 0.0, 0, 0, zn.data_ptr(), None, None, out.data_ptr(),
+            None, self._stream()))
+        return out[:head[3]]
+
+    def _ftrl_run(self, name, p, j, x, index, a, b, family, alpha, beta, lambda_, l1_ratio, dropout, seed, epoch, y, omega, zn):
+        head, f = self._ftrl_head(p, j, x, zn)
+        ws, nnz, _ = index
+        assert nnz == head[5] and y.dtype == torch.float64 and omega.dtype == torch.float64 and y.numel() == omega.numel() == head[3]
+        prob = torch.zeros(max(head[3], 1), dtype=torch.float64, device=self.device)
+        some = lambda t: t.data_ptr() if t.numel() else prob.data_ptr()
+        _lib.check(getattr(self.lib, "rsparse_hip_ftrl_%s%s_device" % (name, f))(
+            *head, ws.data_ptr(), int(a), int(b), *self._ftrl_glm(family, alpha, beta, lambda_, l1_ratio), float(dropout), int(seed),
+            int(epoch), some(y), some(omega), zn.data_ptr(), prob.data_ptr(), self._stream()))
+        return prob[:head[3]]
+
+    def ftrl_step(self, p, j, x, index, step, family, alpha, beta, lambda_, l1_ratio, dropout, seed, epoch, y, omega, zn):
+        """one step of FTRL in place on zn (rsparse_amd.ftrl.ftrl_step_reference is the definition; index: of `fm_index`) -> p of the
+        step's rows in the order k, float64 on the device"""
+        out = self._ftrl_run("step", p, j, x, index, step, index[2], family, alpha, beta, lambda_, l1_ratio, dropout, seed, epoch, y, omega, zn)
+        return out[int(step)::index[2]]
+
+    def ftrl_epochs(self, p, j, x, index, n_epochs, family, alpha, beta, lambda_, l1_ratio, dropout, seed, epoch0, y, omega, zn):
+        """n_epochs epochs (numbered from epoch0) of the index's n_steps steps each, in place on zn, on one stream with no host
+        synchronisation between them -> p of every row at its step's snapshot in the last epoch, float64 on the device"""
+        n_rows, n_steps = int(p.numel()) - 1, index[2]
+        batch = max(1, -(-n_rows // n_steps))
+        assert max(1, -(-n_rows // batch)) == n_steps, "the index was built for another number of steps"
+        return self._ftrl_run("epochs", p, j, x, index, n_epochs, batch, family, alpha, beta, lambda_, l1_ratio, dropout, seed, epoch0, y,
+                              omega, zn)
+
+    def ftrl_weights(self, alpha, beta, lambda_, l1_ratio, zn):
+        """w of every feature from the pairs zn (a streaming pass) -> float64 on the device"""
+        assert zn.dim() == 2 and zn.shape[1] == 2 and zn.is_contiguous() and zn.is_cuda and zn.dtype in (torch.float32, torch.float64)
+        w = torch.zeros(int(zn.shape[0]), dtype=torch.float64, device=self.device)
+        f = "_f64" if zn.dtype == torch.float64 else ""
+        _lib.check(getattr(self.lib, "rsparse_hip_ftrl_weights%s_device" % f)(zn.data_ptr(), int(zn.shape[0]), float(alpha), float(beta),
+                                                                             float(lambda_), float(l1_ratio), w.data_ptr(), self._stream()))
+        return w
+
     def glove_index(self, rows, cols, n, n_steps):
         """both sides' index of the stored positions (rows, cols: int32 on the device, in CSR order) of an n x n matrix for epochs of
         n_steps steps (wrmf_glove.hip: the row side from the order itself, the column side by one stable radix sort) -> (the index's

@@ -83,6 +83,12 @@ makes several Philox CALLS: call c has counter (q, g, 7 + 256 c, epoch + 2^31 mo
 third word of every other stream is 0..6, so no call collides with one of them.  Word 0 of call 0 gives the positive as above;
 trial t = 1, 2, ... is word t & 3 of call t >> 2 and its candidate is (o n_items) >> 32.  Which trials are looked at depends on the
 model (the search stops at a violator); the words do not.
+
+`STREAM_FTRL` is the ninth: the dropout of the FTRL fit (rsparse_amd/ftrl.py: `ftrl_keep_reference` is the numpy form,
+rsparse_amd/csrc/wrmf_ftrl.hip recomputes it on the device in the forward and in the update).  The stored entry at position t of
+the row with global index r takes word o[t & 3] of the call with counter (t >> 2, r, 8, epoch), key (lo32(seed), hi32(seed)), and is
+KEPT iff word >= T, T = floor(dropout 2^32).  `STREAM_WARP`'s third words are 7 + 256 c, so 8 is free.  A flag depends on (seed,
+epoch, r, t) alone: not on the step, the batch or the rows fitted together.  epoch < 2^31.
 """
 import numpy as np
 
@@ -93,6 +99,7 @@ STREAM_SPLIT, STREAM_LEAVE_OUT = 3, 4
 STREAM_WEIGHTED_NEGATIVES = 5
 STREAM_BPR = 6
 STREAM_WARP = 7
+STREAM_FTRL = 8
 MAX_NEGATIVES = 8192   # RSPARSE_HIP_MAX_NEGATIVES
 _MASK = np.uint64(0xFFFFFFFF)
 _S32 = np.uint64(32)
