@@ -1631,6 +1631,27 @@ int rsparse_hip_subspace_block_device(const int32_t* d_p, const int32_t* d_j, co
                                       int ldd, double lambda, float* d_W, int ldw, float* d_e, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The inverse of a symmetric positive definite float64 matrix by a blocked symmetric sweep (wrmf_spdinv.hip)
+ * ---------------------------------------------------------------------------------------------- */
+
+/* The definition (rsparse_amd/ease.py states it in numpy: spd_sweep_reference).  On a copy S of A, for the pivot blocks K = [k0, k0 +
+ * nb), k0 = 0, RSPARSE_HIP_SPDINV_BLOCK, 2 RSPARSE_HIP_SPDINV_BLOCK, ... in order (the last one narrower):
+ *     T = S[:, K];  D = inv(S[K, K]), symmetric;  W = T D;  S = S - W T^T;  S[:, K] = W;  S[K, :] = W^T;  S[K, K] = -D
+ * and inv(A) = -S after the last block: block Gauss-Jordan on an SPD matrix, n^3 flops, the same work in every step.  The pivot
+ * block is inverted from its Cholesky factor in one workgroup; W = T D and the update S -= W T^T run on v_mfma_f64_16x16x4_f64, the
+ * update with a 128 x 128 tile of the lower triangle per workgroup held in accumulator registers.  All arithmetic is float64, no
+ * atomics on doubles, every sum in an order the launch geometry fixes: a repeated call returns the same bits.  3 ceil(n / 64) + 1
+ * launches on the caller's stream, no host synchronisation.
+ *
+ * In place: d_A (n x n, leading dimension ld >= n, float64, symmetric positive definite; both triangles are read as given in the
+ * lower one -- element (i, j), i >= j, at d_A[i ld + j]) becomes inv(A), exactly symmetric; the ld - n padding columns are not
+ * touched.  A pivot block that is not positive definite (a pivot that is not positive and finite) is counted as unresolved in the
+ * failure block (rsparse_hip_take_numeric_failures) and the remaining launches do nothing: the contents of d_A are then unspecified.
+ * d_A == NULL, n < 0, ld < n -> ERR_INVALID; n == 0 -> OK; both before a device is touched. */
+#define RSPARSE_HIP_SPDINV_BLOCK 64
+int rsparse_hip_spd_inverse_f64_device(double* d_A, int n, int ld, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * why this item: per-item contributions to a score (Hu, Koren and Volinsky, section 5; `explain` of the `implicit` library)
  * ---------------------------------------------------------------------------------------------- */
 

@@ -15,7 +15,8 @@ Only the hot path of the reference (R/model_WRMF.R + inst/include/wrmf_{implicit
                               from end to end: neighbour table and top-k lists on the device, equal to the numpy definition;
                               with weighting= on quantised values: BM25 / TF-IDF cosine, dot, asymmetric cosine, P3alpha / RP3beta
   rsparse_amd.EASE            the closed-form item-item model of Steck 2019: Gram rows and top-k lists under a dense items x items
-                              weight matrix on the device, equal to the numpy definition
+                              weight matrix on the device, equal to the numpy definition; inverse="sweep" inverts the Gram matrix
+                              in place by a hand-written fp64 blocked symmetric sweep (HipBackend.spd_inverse) instead of torch's
   rsparse_amd.SLIM            the sparse linear method of Ning and Karypis 2011: a non-negative elastic net per item column by
                               coordinate descent on the device, equal to the numpy definition; EASE's inference surface
   rsparse_amd.BPR             matrix factorisation on the pairwise ranking loss of Rendle et al. 2009 by deterministic mini-batch SGD

@@ -33,6 +33,7 @@ FM_MAX_RANK, FM_LONG_ROW = 128, 512   # RSPARSE_HIP_FM_MAX_RANK / _LONG_ROW: the
 # RSPARSE_HIP_FTRL_*: the families, the gradient clip and the row-length edge of wrmf_ftrl.hip
 FTRL_BINOMIAL, FTRL_GAUSSIAN, FTRL_POISSON, FTRL_CLIP, FTRL_LONG_ROW = 0, 1, 2, 1000.0, 512
 GLOVE_MAX_RANK = 128   # RSPARSE_HIP_GLOVE_MAX_RANK: the widest W_i / W_j of wrmf_glove.hip
+SPDINV_BLOCK = 64   # RSPARSE_HIP_SPDINV_BLOCK: the pivot block of the symmetric sweep (wrmf_spdinv.hip)
 RANKS_BATCH = 1024  # RSPARSE_HIP_RANKS_BATCH: held-out entries of a row that the rank count takes at a time
 
 _c_int, _c_uint, _c_dbl, _c_i64, _c_u64 = ctypes.c_int, ctypes.c_uint, ctypes.c_double, ctypes.c_int64, ctypes.c_uint64
@@ -197,6 +198,8 @@ SIGNATURES = {
     # iALS++ block step: (p, j, x, n_rows, nnz, H, ldh, c0, width, b, G, ldg, D, ldd, lambda, W, ldw, e, stream)
     "rsparse_hip_subspace_block_device": (_c_int, [_vp, _vp, _vp, _c_int, _c_i64, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp,
                                                    _c_int, _c_dbl, _vp, _c_int, _vp, _vp]),
+    # SPD inverse in place: (A, n, ld, stream)
+    "rsparse_hip_spd_inverse_f64_device": (_c_int, [_vp, _c_int, _c_int, _vp]),
     # factorization machine: (p, j, n_rows, n_feat, nnz, n_steps, index, index_bytes, stream); (p, j, x, n_rows, n_feat, step, n_steps,
     # rank, family, w0, w, V, y, omega, raw, delta, S, link, stream); (p, j, x, n_rows, n_feat, nnz, index, step | n_epochs, n_steps |
     # batch, rank, family, intercept, lr_w, lr_v, lambda_w, lambda_v, y, omega, w0, w, V, a0, aw, aV, trace, stream)

@@ -70,6 +70,7 @@ struct Workspace {
   GrowBuf<double> softals_buf{all};   // soft-ALS half-iteration (wrmf_softals.hip): w, s, t and the partial sums of split rows
   GrowBuf<double> lmf_buf{all};   // logistic MF (wrmf_lmf.hip): the slices' softplus sums and fp32 partials of the dense term
   GrowBuf<char> sub_buf{all};     // iALS++ block step (wrmf_subspace.hip): the long rows' segments and partial sums
+  GrowBuf<double> spd_buf{all};   // SPD inverse (wrmf_spdinv.hip): the panel T, -W, the pivot block's inverse and the failure flag
   GrowBuf<char> knn_buf{all};     // ItemKNN (wrmf_itemknn.hip): a batch of dense rows, all zeros between calls
   bool knn_dirty = false;         // ... unless a call failed between its scatter and its zeroing
   GrowBuf<float> mf_G{all};       // wrmf_chol_mf.hip at rank 65..127: XtX padded to 128 x 128
@@ -2118,6 +2119,19 @@ int rsparse_hip_subspace_block_device(const int32_t* d_p, const int32_t* d_j, co
   hipError_t e = launch_subspace_block(d_p, d_j, d_x, n_rows, nnz, d_H, ldh, c0, width, d_G, ldg, d_D, ldd, (float)lambda, d_W, ldw, d_e,
                                        g_ws.fails + 3, (char*)g_ws.sub_buf, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "launch_subspace_block");
+  return RSPARSE_HIP_OK;
+}
+
+// SPD inverse by the blocked symmetric sweep (wrmf_spdinv.hip)
+int rsparse_hip_spd_inverse_f64_device(double* d_A, int n, int ld, void* stream) {
+  if (!d_A) return fail(RSPARSE_HIP_ERR_INVALID, "d_A is NULL");
+  if (n < 0 || ld < n) return fail(RSPARSE_HIP_ERR_INVALID, "bad dimensions (n < 0 or ld < n)");
+  if (n == 0) return RSPARSE_HIP_OK;
+  if (int rc = g_ws.ensure_device()) return rc;
+  HIP_TRY(g_ws.spd_buf.ensure(spdinv_ws_doubles(n)));
+  // ([3]: the unresolved count, as the block step above)
+  hipError_t e = launch_spd_inverse_f64(d_A, n, ld, g_ws.spd_buf, g_ws.fails + 3, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "launch_spd_inverse_f64");
   return RSPARSE_HIP_OK;
 }
 

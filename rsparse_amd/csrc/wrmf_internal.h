@@ -428,6 +428,12 @@ hipError_t launch_subspace_block(const int32_t* P, const int32_t* J, const float
                                  int c0, int width, const float* G, int ldg, const float* D, int ldd, float lambda, float* W, int ldw,
                                  float* e, int* fails, void* ws, hipStream_t s);
 
+// In-place inverse of an SPD float64 matrix by the blocked symmetric sweep (wrmf_spdinv.hip; defined in rsparse_wrmf_hip.h): A (n x n,
+// leading dimension ld, its lower triangle read) becomes inv(A), both triangles.  ws: spdinv_ws_doubles(n) doubles, 16-byte aligned;
+// *fails += 1 when a pivot block was not positive definite (A is then unspecified).  3 ceil(n / 64) + 1 launches on s, no wait.
+size_t spdinv_ws_doubles(int n);
+hipError_t launch_spd_inverse_f64(double* A, int n, int ld, double* ws, int* fails, hipStream_t s);
+
 // Factorization machine (wrmf_fm.hip; defined in rsparse_wrmf_hip.h).  The data: the canonical CSR (p from 0, nnz = p[n_rows] handed
 // in, x in the parameters' type T), the steps of an epoch, 1 <= rank <= 128 and the family.  index: the backward index of
 // (x, n_steps) into fm_index_bytes(nnz, n_steps) bytes; waits for `s`.  forward: step `step` alone from (w0, w, V) -- with y: raw

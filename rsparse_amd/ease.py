@@ -34,6 +34,8 @@ positive NaN): the device keeps 0 for "no cell" and all ones for "masked".
   score_keys, key_scores            the order key and its inverse
   spd_inverse, cholesky_inverse_blocked, weights_from_inverse      the factorisation (torch.linalg.cholesky_ex, torch.cholesky_inverse /
                                     torch.cholesky_solve) and the step from P to B
+  spd_sweep_reference               the inverse by a blocked symmetric sweep, in numpy: the definition of `HipBackend.spd_inverse`
+                                    (wrmf_spdinv.hip), which `EASE(inverse="sweep")` fits with
   EASE                              the model: fit / predict / evaluate / similar_items, and score / sample_negatives /
                                     held_out_ranks / evaluate_ranks with the conventions of `ItemKNN`'s
 """
@@ -243,6 +245,42 @@ def spd_inverse(A):
 spd_inverse.on_host = False
 
 
+NOT_SPD = "EASE: G + lambda I is not positive definite (a pivot block of the sweep failed); at lambda = 0 the Gram matrix of a real " \
+          "interaction matrix is singular"
+
+
+def spd_sweep_reference(A, block=_lib.SPDINV_BLOCK):
+    """-> inv(A) for a symmetric positive definite A by the blocked symmetric sweep (block Gauss-Jordan, the "sweep operator"), float64
+    numpy.  On a copy S of A, for the pivot blocks K = [k0, k0 + block), k0 = 0, block, 2 block, ... in order (the last one narrower):
+
+        T = S[:, K];  D = inv(S[K, K]), symmetrised;  W = T D;  S = S - W T^T;  S[:, K] = W;  S[K, :] = W^T;  S[K, K] = -D
+
+    and inv(A) = -S after the last block.  The loop is uniform: blocks swept earlier are updated by the same formula.  A diagonal
+    block that is not positive definite (its Cholesky factorisation fails or is not finite) means A is not:
+    RsparseHipError(ERR_NUMERIC)."""
+    S = np.array(A, dtype=np.float64)
+    n, block = S.shape[0], int(block)
+    assert S.ndim == 2 and S.shape[1] == n and block >= 1
+    for k0 in range(0, n, block):
+        K = slice(k0, min(k0 + block, n))
+        T = S[:, K].copy()
+        try:
+            L = np.linalg.cholesky(S[K, K])
+        except np.linalg.LinAlgError:
+            L = None
+        if L is None or not np.isfinite(L).all():
+            raise _numeric(NOT_SPD)
+        M = np.linalg.inv(L)
+        D = M.T @ M
+        D = (D + D.T) / 2
+        W = T @ D
+        S -= W @ T.T
+        S[:, K] = W
+        S[K, :] = W.T
+        S[K, K] = -D
+    return -S
+
+
 def weights_from_inverse(P, dtype, ld=None):
     """-> B of the definition from P (a float64 tensor) as an (n_items, ld) tensor of `dtype` on P's device whose first n_items
     columns are B and whose others are zeros (ld: default n_items).  A P_jj that is not positive and finite: ERR_NUMERIC."""
@@ -263,12 +301,17 @@ class EASE:
     lambda_: the ridge term, finite and >= 0 (500 suits MovieLens-sized data; 0 is singular on real data); precision: "float" or
     "double", the dtype of the resident weights B (the factorisation is float64 either way); device / backend: as `WRMF`.  A
     backend without `item_gram` / `ease_recommend` (the CPU stand-in of the tests) runs the numpy definitions.
+    inverse: "torch" (the default: `spd_inverse`, torch's Cholesky and solves) or "sweep" (`HipBackend.spd_inverse`, the blocked
+    symmetric sweep of wrmf_spdinv.hip, in place in the Gram matrix; `spd_sweep_reference` on a backend without it).
     Fitted: `B` (downloaded on access), `item_count`."""
 
-    def __init__(self, lambda_=500.0, precision="float", device=None, backend=None):
+    def __init__(self, lambda_=500.0, precision="float", device=None, backend=None, inverse="torch"):
         self._lambda = _check_lambda(lambda_)
         if precision not in PRECISIONS:
             raise ValueError("precision must be 'float' or 'double'")
+        if inverse not in ("torch", "sweep"):
+            raise ValueError("inverse must be 'torch' or 'sweep'")
+        self._inverse = inverse
         self._dtype = PRECISIONS[precision]
         self._device = device
         self._be = backend
@@ -308,7 +351,11 @@ class EASE:
         be = self._backend()
         t_dtype = torch.float32 if self._dtype == np.float32 else torch.float64
         if not hasattr(be, "item_gram"):
-            B = torch.from_numpy(ease_weights_reference(ease_gram_reference(m, self._lambda), self._dtype))
+            A = ease_gram_reference(m, self._lambda)
+            if self._inverse == "sweep":
+                B = weights_from_inverse(torch.from_numpy(spd_sweep_reference(A)), t_dtype)
+            else:
+                B = torch.from_numpy(ease_weights_reference(A, self._dtype))
             cnt = np.bincount(m.indices, minlength=n_items).astype(np.int64)
         else:
             up, uj = be.to_device(m.indptr, torch.int32), be.to_device(m.indices, torch.int32)
@@ -317,7 +364,13 @@ class EASE:
             ip, iu, _ = be.transpose_csc(n_items, n_users, up, uj, ones)
             A = be.item_gram(ip, iu, up, uj, n_users, n_items, self._lambda, ws_rows=ws_rows)
             cnt = np.diff(ip.cpu().numpy().astype(np.int64))
-            P = spd_inverse(A)
+            if self._inverse == "sweep":
+                try:
+                    P = be.spd_inverse(A)   # (in place: P is A)
+                except _lib.RsparseHipError as e:
+                    raise _numeric(NOT_SPD) if e.code == _lib.ERR_NUMERIC else e
+            else:
+                P = spd_inverse(A)
             del A
             elems = ROW_BYTES // np.dtype(self._dtype).itemsize
             B = weights_from_inverse(P, t_dtype, (n_items + elems - 1) // elems * elems)

@@ -879,6 +879,22 @@ class HipBackend:
                                                          int(item0), item1, float(lambda_), some(out), ld, int(ws_rows), self._stream()))
         return out
 
+    def spd_inverse(self, A):
+        """A (n x n float64 on the device, symmetric positive definite, unit column stride, any row stride >= n; its lower triangle
+        is read) becomes inv(A) IN PLACE, exactly symmetric, by the blocked symmetric sweep of wrmf_spdinv.hip
+        (rsparse_amd.ease.spd_sweep_reference is the definition) -> A.  A matrix that is not positive definite:
+        RsparseHipError(ERR_NUMERIC), the contents of A are then unspecified.  One host synchronisation, for that verdict."""
+        assert A.dtype == torch.float64 and A.is_cuda and A.dim() == 2 and A.shape[0] == A.shape[1]
+        n = int(A.shape[0])
+        assert n <= 1 or (A.stride(1) == 1 and A.stride(0) >= n)
+        if n == 0:
+            return A
+        self.check_numeric()   # (what earlier calls left in the failure block is theirs)
+        _lib.check(self.lib.rsparse_hip_spd_inverse_f64_device(A.data_ptr(), n, int(A.stride(0)) if n > 1 else 1, self._stream()))
+        if self.numeric_counts()[0]:
+            raise _lib.RsparseHipError(_lib.ERR_NUMERIC, "spd_inverse: the matrix is not positive definite")
+        return A
+
     def ease_recommend(self, xp, xj, B, n_items, k, nr_p=None, nr_j=None, exclude0=None, ws_rows=0):
         """the EASE lists of the rows of a CSR pattern (xp, xj: int32 on the device) under the dense weights B: an (n_items, ld)
         float32 or float64 tensor on the device whose first n_items columns are the matrix, rows 16-byte aligned (wrmf_ease.hip;
